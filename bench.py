@@ -36,7 +36,19 @@ the gather then goes through gloo): plumbing check on a one-GPU box.
 --plumbing-only runs launch, rendezvous, gather and the JSON line without a GPU
 (synthetic tiles, no rendering, "value": null).
 
-Extra objects on the JSON line:
+A plain run does only what the headline needs: set-up, warm-up, the K timed steps and the
+line (metric, value, unit, ms_per_step, dtype, config, ranks, gather, adaptation).  The
+objects below take runs of their own and are measured with --full only; without it they are
+null on the line.  --dump-outputs DIR writes what the timed region computed, as a caller of
+it receives it, after the timed steps: DIR/radiance.npy (float32, the gathered frame,
+height x width x 4; a frame above 48 MB is written as a fixed, seeded sample of 2^20 pixels,
+their flat indices in DIR/radiance_pixels.npy) and DIR/ray_counts.npy (float64: closest-hit
+and shadow rays of the timed steps).  Every value written is finite: the frame's NaN pixels
+(the reference's arithmetic makes them too) are 0 in radiance.npy and listed, element by
+element, in DIR/radiance_nonfinite.npy (see dump_outputs).  The same arguments give the same
+inputs every run.
+
+Extra objects on the JSON line (--full):
   per_frame    the reference's OWN call pattern beside the headline: K x Render::RenderFrame() =
                Integrator::Integrate() through the fifteen stage hooks, one sample per pixel per call,
                ResolveRadiance + host sync every frame (src/render.cpp:197): mrays_per_s, ms_per_frame --
@@ -707,7 +719,13 @@ def main():
                     "per device): exercises the agreement that falls back to the gloo gather")
     ap.add_argument("--plumbing-only", action="store_true", help="no GPU: launch, rendezvous, gather and report only")
     ap.add_argument("--no-scene-cache", action="store_true", help="N > 1: every rank builds the scene and the BVH itself")
+    ap.add_argument("--full", action="store_true", help="also measure and check everything beside the headline: cold_job, per_frame, roofline, "
+                    "parity against the reference's kernels, cpu_baseline, surface_area_fold, scaling_estimate (off: those are null)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what they computed to DIR/*.npy "
+                    "(radiance.npy, ray_counts.npy; see the module docstring)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     cfg = CONFIGS[args.config]
     args.width = args.width or cfg["width"]
     args.height = args.height or cfg["height"]
@@ -790,7 +808,7 @@ def main():
     t_setup = time.time() - t0
     setup_breakdown = render.setup_seconds()                 # Render's constructor: BVH build / Finalize / frame / UploadGPUData (its stages: the `upload:` line of the tree report)
     cold_job = None
-    if world == 1 and args.cold_job_spp > 0 and not args.per_frame_only:
+    if args.full and world == 1 and args.cold_job_spp > 0 and not args.per_frame_only:
         try:
             cold_job = cold_job_leg(args, render, host, capi, capi.load(), torch, setup_breakdown)
         except Exception as e:                                # noqa: BLE001 -- reported, never fatal to the measurement
@@ -994,11 +1012,13 @@ def main():
         per_rank = [None] * world
         dist.all_gather_object(per_rank, mine)
     full = gather(True)                                      # untimed: the image for the checks below
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, full, agg)
     # N > 1: the gathered frame against the reference's own kernels (untimed, bounded: 2 samples of the full frame on rank 0's
     # host cores, the same 2 samples by the N tiles, one more gather).  Reported, never fatal: a failure here must not cost
     # the line its measurement.
     tiled_parity = None
-    if world > 1 and not args.no_cpu_baseline:
+    if args.full and world > 1 and not args.no_cpu_baseline:
         n_ref, ref_frame, note = [0], None, None
         if rank == 0:
             try:
@@ -1055,7 +1075,7 @@ def main():
 
     isolated, live_step = None, None
     overlap_on = args.overlap_shadow is None or args.overlap_shadow != 0
-    if world == 1:
+    if args.full and world == 1:
         live_step = profiled_step(overlap_on, "one more step of %d spp in the timed region's mode (untimed, instrumented)" % sps)
         if overlap_on:
             # (twice, the faster kept: one of ~20 such steps runs a fifth slower -- clocks after the sustained timed region -- and every
@@ -1065,7 +1085,7 @@ def main():
             assert lib.rt_set_option(frame, capi.OPT_OVERLAP_SHADOW, 1) == 0
 
     per_frame = None
-    if world == 1 and args.per_frame_frames > 0:
+    if args.full and world == 1 and args.per_frame_frames > 0:
         if args.stage_pipes:
             assert lib.rt_set_option(frame, capi.OPT_STAGE_PIPES, args.stage_pipes) == 0
         per_frame = per_frame_leg(args, render, lib, frame, capi, args.per_frame_frames, ahead=args.samples_ahead)
@@ -1084,8 +1104,9 @@ def main():
         nan_px = int((~torch.isfinite(full[..., :3]).all(-1)).sum().item())
         # CPU legs on a reduced frame of the same scene (bounded, see docstring)
         small_w, small_h = 320, 180          # oracle counters + CPU baseline frame
-        arrays = render.scene_arrays()
-        per_ray, baseline, ref_img, ref_spp, libm_img = cpu_legs(args, arrays, host.default_camera(small_w, small_h), small_w, small_h, cam)
+        arrays = render.scene_arrays() if args.full else None
+        per_ray, baseline, ref_img, ref_spp, libm_img = (cpu_legs(args, arrays, host.default_camera(small_w, small_h), small_w, small_h, cam)
+                                                         if args.full else (None, None, None, 0, None))
         parity = tiled_parity
         if ref_img is not None and world == 1:
             # the SAME samples on the GPU (outside the timed region), compared with the reference kernels' image
@@ -1170,8 +1191,8 @@ def main():
             # mirror spheres produce them by the hundred, and the reference produces the same ones -- `parity` compares them
             # when the CPU leg runs); reported as config.non_finite_pixels, and a frame FULL of them is a bug
             assert nan_px <= 1e-2 * args.width * args.height, "too many non-finite pixels: %d" % nan_px
-        roofline = roofline_object(args, world, live_step, per_ray, isolated)
-        if isolated is not None:
+        roofline = roofline_object(args, world, live_step, per_ray, isolated) if args.full else None
+        if roofline is not None and isolated is not None:
             roofline["live_isolated"] = isolated
         trees_now = trees_after_warmup.strip().split("\n")
         # The headline runs on the fold ADAPTED to this view (RT_CTX_OPT_ADAPTIVE_FOLD, bit 1: the warm-up waits for it).  Beside it: what the
@@ -1187,7 +1208,7 @@ def main():
                               note="seconds_to_adapted: the first rt_integrate's probe + the worker thread's folds + the upload, as the warm-up saw them "
                                    "(bit 1: it waits; the library default adopts whenever the worker is done and renders on the upload's fold meanwhile)")
         surface_area_fold = None
-        if args.adaptive_fold and world == 1 and args.surface_area_fold_steps > 0 and not args.per_frame_only:
+        if args.full and args.adaptive_fold and world == 1 and args.surface_area_fold_steps > 0 and not args.per_frame_only:
             try:
                 render.set_adaptive_fold(0)                      # ... and uploads again
                 sa_steps = max(args.surface_area_fold_steps, min(args.steps, int(round(0.4 / max(dt_max / max(args.steps, 1), 1e-6)))))   # >= 0.4 s of work
@@ -1215,7 +1236,7 @@ def main():
         est_path = os.path.join(ROOT, "profiles", "r06_tile_efficiency.json")
         if not os.path.exists(est_path):
             est_path = os.path.join(ROOT, "profiles", "r05_tile_efficiency.json")
-        if os.path.exists(est_path) and args.config == 4:
+        if args.full and os.path.exists(est_path) and args.config == 4:
             try:
                 scaling_estimate = json.load(open(est_path))
                 scaling_estimate["measured"] = False
@@ -1242,6 +1263,7 @@ def main():
                     steps=args.steps, warmup=args.warmup, ms_per_step=round(dt_max * 1e3 / args.steps, 4),
                     ms_per_spp=round(dt_max * 1e3 / spp_timed, 4),
                     higher_is_better=True, scaling="strong", vs_baseline=None, dtype="f32", data="real" if (args.scene or args.config == 1) else "synthetic",
+                    full=bool(args.full),
                     config=dict(workload=(("scene file %s (scale %g, flip_yz %d)" % (os.path.basename(args.scene), args.scale, args.flip_yz))
                                           if args.scene else (cfg["name"] % dict(blob=args.blob_tris, ball=args.ball_tris))) +
                                          ", %dx%d, %d-bounce, %d spp per step, default camera, directional light + "
@@ -1274,6 +1296,41 @@ def main():
     if group is not None:
         group.close()
     return 0
+
+
+RADIANCE_DUMP_BYTES = 48 << 20        # a larger frame is dumped as a sample of ...
+RADIANCE_DUMP_PIXELS = 1 << 20        # ... this many pixels, chosen by a fixed seed
+
+
+NONFINITE_CODES = ((1.0, np.isnan), (2.0, np.isposinf), (3.0, np.isneginf))     # radiance_nonfinite.npy's second column
+
+
+def dump_outputs(out_dir, image, rays):
+    """--dump-outputs: the timed region's result as a caller receives it -- the gathered frame (float32, height x width x 4) and the
+    closest-hit / shadow rays it traced (float64) -- so that two builds can be compared output for output.  Every file holds finite
+    numbers only: the frame may hold NaN pixels (the reference's own inf * 0 in the mirror branch, material.h:79-81), which are
+    written as 0 in radiance.npy and listed in radiance_nonfinite.npy as (flat element index, 1 = NaN / 2 = +inf / 3 = -inf)
+    rows -- a file written only when there is such an element -- so that the dump still says exactly what was computed."""
+    os.makedirs(out_dir, exist_ok=True)
+    img = np.ascontiguousarray(image.numpy() if hasattr(image, "numpy") else image, dtype=np.float32)
+    for name in ("radiance_pixels.npy", "radiance_nonfinite.npy"):          # (an earlier dump's into the same directory)
+        if os.path.exists(os.path.join(out_dir, name)):
+            os.remove(os.path.join(out_dir, name))
+    if img.nbytes > RADIANCE_DUMP_BYTES:
+        h, w, c = img.shape
+        pick = np.sort(np.random.default_rng(0).choice(h * w, RADIANCE_DUMP_PIXELS, replace=False))
+        np.save(os.path.join(out_dir, "radiance_pixels.npy"), pick.astype(np.float64))
+        img = img.reshape(h * w, c)[pick]
+    flat = img.reshape(-1)
+    bad = np.flatnonzero(~np.isfinite(flat))
+    if len(bad):
+        kind = np.zeros(len(bad), np.float64)
+        for code, test in NONFINITE_CODES:
+            kind[test(flat[bad])] = code
+        np.save(os.path.join(out_dir, "radiance_nonfinite.npy"), np.stack([bad.astype(np.float64), kind], 1))
+        img = np.where(np.isfinite(img), img, np.float32(0.0))
+    np.save(os.path.join(out_dir, "radiance.npy"), img)
+    np.save(os.path.join(out_dir, "ray_counts.npy"), np.asarray(rays, dtype=np.float64).reshape(2))
 
 
 def render_ctx_info(capi, host, render):

@@ -169,6 +169,10 @@ def test_tga_loader_roundtrip(tmp_path):
     assert img.shape == (1, 4) and (img == (30 | (20 << 8) | (10 << 16) | (40 << 24))).all()
 
 
+# sha256 of the packed RGBA8 texels the reference's stb build (oracle/_ref, LoadSTB) decodes from tests/golden/jpeg/checker3.jpg
+CHECKER3_STB_SHA256 = "cb8c85a90bb9055fc384ea980834a0bf5c7513c95a0f07d9b72a9cbb63806345"
+
+
 def test_jpeg_loader_matches_stb_image_texels():
     """LoadJPEG restates stb_image's integer pipeline (IDCT, upsampling, colour conversion); the
     committed files were decoded by the REFERENCE's stb build (tests/golden/make_jpeg_golden.py):
@@ -179,6 +183,9 @@ def test_jpeg_loader_matches_stb_image_texels():
     for name in want.files:
         got = host.load_jpeg(os.path.join(d, name + ".jpg"))
         assert got.shape == want[name].shape and np.array_equal(got, want[name]), name
+    # the reference's own asset (progressive 4:2:0, 1024 x 1024), pinned by the hash of the texels its stb build decodes
+    got = host.load_jpeg(os.path.join(d, "checker3.jpg"))
+    assert got.shape == (1024, 1024) and hashlib.sha256(got.tobytes()).hexdigest() == CHECKER3_STB_SHA256
     with pytest.raises(host.RtError):
         host.load_jpeg(os.path.join(d, "jpeg_texels.npz"))          # not a JPEG
 
@@ -274,9 +281,8 @@ class TestAgainstReferenceHost:
                         PI.fromarray(photo(w, h, rng), "RGB").save(p, "JPEG", quality=q, subsampling=sub, progressive=prog,
                                                                      restart_marker_blocks=restart, optimize=bool(n % 2))
                         assert np.array_equal(_ref.load_stb(p), host.load_jpeg(p)), (w, h, sub, prog, q, restart)
-        asset = "/root/reference/assets/checker3.jpg"               # the reference's own (progressive 4:2:0) asset
-        if os.path.exists(asset):
-            assert np.array_equal(_ref.load_stb(asset), host.load_jpeg(asset))
+        asset = os.path.join(ROOT, "tests", "golden", "jpeg", "checker3.jpg")     # the reference's own (progressive 4:2:0) asset
+        assert np.array_equal(_ref.load_stb(asset), host.load_jpeg(asset))
 
     def test_obj_loader_identical_to_reference_scene(self, tmp_path):
         meshes = [S.quad((-1, -1, 0), (1, -1, 0), (1, 1, 0), (-1, 1, 0)) + (0,),

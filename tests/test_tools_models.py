@@ -94,3 +94,40 @@ def test_code_object_identity_and_the_stale_flag_of_the_roofline(tmp_path):
         assert r["achieved"] is None and "error" in r["counters"]                 # says so instead of silently changing `bound`
     finally:
         bench.COUNTERS_FILE = old
+
+
+def test_bench_dump_outputs_writes_the_frame_or_a_fixed_sample_of_it(tmp_path):
+    """bench.py --dump-outputs: the gathered frame as float32 and the ray counts as float64; a frame above the byte budget
+    is written as the same seeded sample of pixels every time, with their flat indices beside it."""
+    import bench
+    small = np.arange(6 * 5 * 4, dtype=np.float32).reshape(6, 5, 4)
+    bench.dump_outputs(str(tmp_path / "a"), small, [7.0, 3.0])
+    assert np.array_equal(np.load(tmp_path / "a" / "radiance.npy"), small)
+    rays = np.load(tmp_path / "a" / "ray_counts.npy")
+    assert rays.dtype == np.float64 and rays.tolist() == [7.0, 3.0]
+    assert not (tmp_path / "a" / "radiance_pixels.npy").exists()
+    h, w = 2160, 3840                                                   # config 5's frame: 127 MiB of float32
+    big = np.random.default_rng(5).random((h, w, 4), dtype=np.float32)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), big, [1.0, 2.0])
+    img, pix = np.load(tmp_path / "b" / "radiance.npy"), np.load(tmp_path / "b" / "radiance_pixels.npy")
+    assert img.dtype == np.float32 and pix.dtype == np.float64 and img.shape == (bench.RADIANCE_DUMP_PIXELS, 4)
+    assert img.nbytes + pix.nbytes <= 64 << 20 and (np.diff(pix) > 0).all()
+    assert np.array_equal(img, big.reshape(-1, 4)[pix.astype(np.int64)])
+    assert np.array_equal(pix, np.load(tmp_path / "c" / "radiance_pixels.npy"))
+    # NaN / inf elements: radiance.npy stays finite, radiance_nonfinite.npy says which element was what, the frame comes back exactly
+    odd = small.copy()
+    odd[1, 2, 0], odd[4, 0, 3], odd[5, 4, 1] = np.nan, np.inf, -np.inf
+    bench.dump_outputs(str(tmp_path / "a"), odd, [7.0, 3.0])               # (over the first dump: no stale files either way)
+    img, bad = np.load(tmp_path / "a" / "radiance.npy"), np.load(tmp_path / "a" / "radiance_nonfinite.npy")
+    assert np.isfinite(img).all() and np.isfinite(bad).all() and bad.dtype == np.float64
+    assert bad.tolist() == [[np.ravel_multi_index((1, 2, 0), odd.shape), 1.0], [np.ravel_multi_index((4, 0, 3), odd.shape), 2.0],
+                            [np.ravel_multi_index((5, 4, 1), odd.shape), 3.0]]
+    back = img.reshape(-1).copy()
+    back[bad[:, 0].astype(np.int64)] = np.choose(bad[:, 1].astype(np.int64) - 1, [np.nan, np.inf, -np.inf])
+    assert np.array_equal(back.reshape(odd.shape), odd, equal_nan=True)
+    bench.dump_outputs(str(tmp_path / "a"), small, [7.0, 3.0])
+    assert not (tmp_path / "a" / "radiance_nonfinite.npy").exists()
+    for d in ("a", "b"):
+        for f in (tmp_path / d).iterdir():
+            assert np.isfinite(np.load(f)).all(), f

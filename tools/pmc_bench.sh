@@ -8,8 +8,8 @@ D=$R/gpurun_out/$OUT
 mkdir -p $D
 cd /tmp && export TMPDIR=/tmp
 ARGS="$*"
-rocprofv3 --kernel-trace --stats --output-format csv -d $D -o stats -- python $R/bench.py $ARGS --no-cpu-baseline > $D/stats.log 2>&1
-run() { name=$1; shift; rocprofv3 --pmc "$@" --output-format csv -d $D -o $name -- python $R/bench.py $ARGS --no-cpu-baseline > $D/$name.log 2>&1; }
+rocprofv3 --kernel-trace --stats --output-format csv -d $D -o stats -- python $R/bench.py $ARGS --full --no-cpu-baseline > $D/stats.log 2>&1
+run() { name=$1; shift; rocprofv3 --pmc "$@" --output-format csv -d $D -o $name -- python $R/bench.py $ARGS --full --no-cpu-baseline > $D/$name.log 2>&1; }
 run fetch FETCH_SIZE TCC_EA0_RDREQ_sum
 run write WRITE_SIZE TCC_EA0_WRREQ_sum
 run tcc TCC_HIT_sum TCC_MISS_sum TCC_REQ_sum

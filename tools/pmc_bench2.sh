@@ -8,7 +8,7 @@ R=$GRAFT_REPO_ROOT
 D=$R/gpurun_out/$OUT
 mkdir -p $D
 cd /tmp && export TMPDIR=/tmp
-ARGS="$* --no-cpu-baseline"
+ARGS="$* --full --no-cpu-baseline"
 timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $D/stats -o stats -- python $R/bench.py $ARGS > $D/stats.log 2>&1
 run() { name=$1; shift; timeout 900 rocprofv3 --pmc "$@" --output-format csv -d $D/$name -o $name -- python $R/bench.py $ARGS > $D/$name.log 2>&1; }
 mb() { name=$1; what=$2; shift 2; timeout 300 rocprofv3 --pmc "$@" --output-format csv -d $D/mb_$name -o mb_$name -- $R/tools/bin/issue_mb $what > $D/mb_$name.log 2>&1; }
