@@ -371,6 +371,40 @@ int rt_frame_read_radiance(rt_frame* frame, float* host_rgba);
 void* rt_frame_radiance_device_ptr(rt_frame* frame);
 uint32_t rt_frame_sample_count(rt_frame* frame);
 
+/* ---- spatial filter (opt-in extension; no reference counterpart): the edge-avoiding a-trous wavelet filter of Dammertz et al.
+ * 2010 over the shaded colour, guided by first-hit albedo, normal and depth (raytracing_amd/csrc/spatial_filter.h states it
+ * exactly).  A new output beside rt_frame_resolve: the frame's radiance and every other result are untouched.
+ *   - pass i = 0 .. iterations-1 spaces its 5 x 5 B3-spline taps 2^i pixels apart; a tap's weight falls with the colour distance
+ *     (sigma_color, tightened 2x per pass), 1 - dot of the normals (sigma_normal) and the relative depth step per pixel (sigma_depth);
+ *   - RT_FILTER_DEMODULATE filters radiance / albedo and multiplies the albedo back afterwards (texture detail stays sharp);
+ *   - pixels without a first hit, and pixels with a non-finite colour, pass through unchanged and give nothing to their neighbours.
+ * The guides come from a primary pass of its own: one ray per pixel through the pixel CENTRE from the camera position (the lens
+ * centre: the guides are sharp with an aperture too), traced once per camera / frame size / scene and cached on the frame.
+ * Whole images only (the stencil crosses rows): a tile frame (tile_count > 1) is refused. */
+#define RT_FILTER_DEMODULATE 1u    /* filter radiance / albedo, multiply the albedo back afterwards */
+#define RT_FILTER_MAX_ITERATIONS 8u
+typedef struct rt_filter_desc
+{
+    uint32_t iterations;           /* 0 .. 8; pass i spaces its 5x5 taps 2^i pixels apart; 0 = no filtering (rt_frame_resolve's image) */
+    uint32_t flags;                /* RT_FILTER_DEMODULATE */
+    float sigma_color, sigma_normal, sigma_depth;   /* each > 0 and finite */
+} rt_filter_desc;
+/* the defaults: the best mean of tools/filter_sweep.py's grid (tone-mapped MSE of filtered 4-spp frames against 1024-spp ones, relative to the
+ * unfiltered 4-spp frame's, 128 x 128, 4 bounces: Cornell box 0.072, coverage scene 0.238) */
+#define RT_FILTER_DESC_DEFAULT { 2u, RT_FILTER_DEMODULATE, 8.0f, 0.05f, 0.1f }
+
+/* resolve + filter: the image rt_frame_resolve would return, filtered; RGBA float, alpha 1, synchronous.
+ * Fails (frame untouched) for NULL arguments, desc values out of range, RT_OPT_AOV != 0 or a tile frame. */
+int rt_frame_filter(rt_frame* frame, const rt_filter_desc* desc, float* host_rgba);
+/* the guide images the filter uses for the frame's current camera (computed if stale): albedo RGBA (alpha 0), unit normal RGBA
+ * (alpha 0), depth (RT_MAX_RENDER_DIST where the pixel-centre ray misses); any array may be NULL.  *passes (nullable) = how many
+ * guide passes this frame has run so far. */
+int rt_frame_read_guides(rt_frame* frame, float* albedo_rgba, float* normal_rgba, float* depth, uint32_t* passes);
+/* the filter on caller arrays (HDR in, HDR out, no tone mapping; width x height, row-major): on the GPU of ctx, or the host
+ * restatement of the same arithmetic when ctx == NULL.  The two agree bit for bit. */
+int rt_debug_filter(rt_ctx* ctx, uint32_t width, uint32_t height, const float* hdr_rgba, const float* albedo_rgba,
+    const float* normal_rgba, const float* depth, const rt_filter_desc* desc, float* out_hdr_rgba);
+
 /* ---- statistics: the queue counters the reference keeps in
  * ray_counter_buffer_[2] / shadow_ray_counter_buffer_ (cl_pt_integrator.hpp:85-86),
  * sampled per bounce and accumulated on the device. */

@@ -51,6 +51,25 @@ class rt_frame_desc(C.Structure):
                 ("tile_count", C.c_uint32), ("band_height", C.c_uint32)]
 
 
+class rt_filter_desc(C.Structure):
+    _fields_ = [("iterations", C.c_uint32), ("flags", C.c_uint32),
+                ("sigma_color", C.c_float), ("sigma_normal", C.c_float), ("sigma_depth", C.c_float)]
+
+
+FILTER_DEMODULATE = 1
+FILTER_DEFAULT = dict(iterations=2, flags=FILTER_DEMODULATE, sigma_color=8.0, sigma_normal=0.05, sigma_depth=0.1)   # RT_FILTER_DESC_DEFAULT
+
+
+def filter_desc(desc=None, **kw):
+    """an rt_filter_desc from None (the header's defaults), a dict, keywords or an rt_filter_desc"""
+    if isinstance(desc, rt_filter_desc):
+        return desc
+    v = dict(FILTER_DEFAULT)
+    v.update(desc or {})
+    v.update(kw)
+    return rt_filter_desc(v["iterations"], v["flags"], v["sigma_color"], v["sigma_normal"], v["sigma_depth"])
+
+
 EXPORTS = [
     "rt_ctx_create", "rt_ctx_destroy", "rt_finish", "rt_last_error", "rt_ctx_device_info", "rt_ctx_stream",
     "rt_ctx_set_option", "rt_upload_blue_noise_tables", "rt_host_register", "rt_host_unregister",
@@ -67,6 +86,7 @@ EXPORTS = [
     "rt_group_create", "rt_group_unique_id", "rt_group_join", "rt_group_size", "rt_group_local_count", "rt_group_local_rank", "rt_group_comm_count",
     "rt_group_gather_radiance", "rt_group_destroy", "rt_group_last_error", "rt_group_denoise", "rt_group_create_local",
     "rt_group_create_unchecked",
+    "rt_frame_filter", "rt_frame_read_guides", "rt_debug_filter",
 ]
 
 OPT_MAX_BOUNCES, OPT_WHITE_FURNACE, OPT_SAMPLER, OPT_AOV, OPT_DENOISER, OPT_DROP_LAST, OPT_PROFILE, OPT_TRACE_VARIANT, OPT_TRACE_WAVES, OPT_SAMPLES_IN_FLIGHT, OPT_SELECT_FORM_BOX, OPT_PACKET_BOUNCES, OPT_TRACE_TUNE, OPT_DEBUG_ALLOC_LIMIT, OPT_PATH_STATE_LIMIT_MB, OPT_PIPELINES, OPT_SHADE_PARTITION, OPT_OVERLAP_SHADOW, OPT_SMALL_LAUNCH_PATHS, OPT_COMPACT_LOG, OPT_DEBUG_LOG_POOL_DIV, OPT_TRACE_TAIL_LANES, OPT_TRACE_TAIL_PATHS, OPT_CHUNK_REFILL, OPT_STAGE_PIPES, OPT_FRAME_KERNEL, OPT_SAMPLES_AHEAD = range(27)
@@ -137,6 +157,9 @@ def load():
         "rt_group_gather_radiance": (i32, [vp, C.POINTER(vp), i32, vp, C.POINTER(vp)]), "rt_group_destroy": (i32, [vp]),
         "rt_group_last_error": (C.c_char_p, [vp]),
         "rt_group_denoise": (i32, [vp, C.POINTER(vp), i32, vp, vp]), "rt_group_create_local": (i32, [i32, i32, C.POINTER(vp)]),
+        "rt_frame_filter": (i32, [vp, C.POINTER(rt_filter_desc), vp]),
+        "rt_frame_read_guides": (i32, [vp, vp, vp, vp, C.POINTER(u32)]),
+        "rt_debug_filter": (i32, [vp, u32, u32, vp, vp, vp, vp, C.POINTER(rt_filter_desc), vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -149,6 +172,24 @@ def _check(lib, ctx, rc):
     if rc != 0:
         msg = lib.rt_last_error(ctx)
         raise RtError(msg.decode() if msg else "unknown error")
+
+
+def debug_filter(ctx, hdr, albedo, normal, depth, desc=None):
+    """rt_debug_filter: the spatial filter over caller arrays (hdr, albedo, normal: float32[h, w, 4]; depth: float32[h, w]) on ctx's GPU,
+    or the host restatement when ctx is None.  Returns the filtered HDR image float32[h, w, 4]."""
+    lib = load()
+    hdr = np.ascontiguousarray(hdr, np.float32)
+    h, w = hdr.shape[:2]
+    alb, nrm = (np.ascontiguousarray(a, np.float32) for a in (albedo, normal))
+    dep = np.ascontiguousarray(depth, np.float32)
+    if alb.shape != hdr.shape or nrm.shape != hdr.shape or dep.shape != (h, w) or hdr.shape != (h, w, 4):
+        raise ValueError("debug_filter: hdr, albedo, normal must be [h, w, 4], depth [h, w]")
+    out = np.zeros_like(hdr)
+    handle = ctx.handle if ctx is not None else None
+    d = filter_desc(desc)
+    if lib.rt_debug_filter(handle, w, h, hdr.ctypes.data, alb.ctypes.data, nrm.ctypes.data, dep.ctypes.data, C.byref(d), out.ctypes.data):
+        raise RtError(lib.rt_last_error(handle).decode())
+    return out
 
 
 def choose_tree(scene, shadow=True, mode=1):
@@ -461,6 +502,21 @@ class Frame:
         out = np.zeros((self.local_rows, self.width, 4), np.float32)
         self._c(self.lib.rt_frame_resolve(self.handle, out.ctypes.data))
         return out
+
+    def filter(self, desc=None):
+        """rt_frame_filter: the resolved image passed through the spatial filter (float32[rows, width, 4]); desc None = the header's defaults"""
+        out = np.zeros((self.local_rows, self.width, 4), np.float32)
+        self._c(self.lib.rt_frame_filter(self.handle, C.byref(filter_desc(desc)), out.ctypes.data))
+        return out
+
+    def guides(self):
+        """rt_frame_read_guides: (albedo float32[h, w, 4], normal float32[h, w, 4], depth float32[h, w], guide passes run so far)"""
+        alb = np.zeros((self.local_rows, self.width, 4), np.float32)
+        nrm = np.zeros_like(alb)
+        dep = np.zeros((self.local_rows, self.width), np.float32)
+        passes = C.c_uint32()
+        self._c(self.lib.rt_frame_read_guides(self.handle, alb.ctypes.data, nrm.ctypes.data, dep.ctypes.data, C.byref(passes)))
+        return alb, nrm, dep, passes.value
 
     def present(self, out=None):
         """rt_frame_present: resolve + Finish() on the frame's kernels; the image travels to `out` (kept alive by the caller) on a

@@ -23,6 +23,7 @@
 #include <chrono>
 #include "wide_bvh.h"        // the host-side fold, the pair layout, the adaptation's host walks (wide_bvh.cpp)
 #include "device_fold.h"     // ... and the fold + crossing counts on the device (device_fold.hip)
+#include "spatial_filter_host.h"   // the spatial filter's guide pass and a-trous passes (spatial_filter.hip)
 using namespace rtw;
 
 namespace
@@ -251,6 +252,7 @@ struct rt_frame
     struct Span { hipEvent_t a, b; int cls; };
     std::vector<Span> spans;
     std::vector<hipEvent_t> event_pool;
+    struct SfGuides* sf = nullptr;     // rt_frame_filter / rt_frame_read_guides: the guide pass's buffers and what they were made for (made on first use)
 };
 
 static int sync_frame_streams(rt_frame* f);
@@ -258,6 +260,29 @@ static void ahead_discard(rt_frame* f);      // RT_OPT_SAMPLES_AHEAD: whatever w
 static void ahead_destroy(rt_frame* f);
 static bool ahead_wanted(const rt_frame* f);
 static int ahead_holds(const rt_frame* f, uint32_t sample);
+
+// The spatial filter's state on a frame (rt_frame_filter, rt_frame_read_guides): made on first use, freed by rt_frame_destroy.  Its own rays, hits,
+// counter and spill area: batches traced ahead (RT_OPT_SAMPLES_AHEAD) may be using the frame's per-path buffers on other streams.  After the guide
+// pass o4 / d4 are free again and serve as the a-trous passes' two ping-pong images.  80 bytes per pixel + the spill area.
+struct SfGuides
+{
+    float4* o4 = nullptr; float4* d4 = nullptr; float4* hits = nullptr;
+    float4* alb = nullptr; float4* nz = nullptr;       // the guides: albedo (w 0); unit normal + depth
+    uint32_t* count = nullptr;
+    uint2* spill = nullptr;
+    rt_camera camera;                                  // what the guides were made for
+    uint64_t scene = 0;
+    bool valid = false;
+    uint32_t passes = 0;                               // guide passes so far
+};
+static void free_filter_state(rt_frame* f)
+{
+    if (!f->sf) return;
+    void* ptrs[] = {f->sf->o4, f->sf->d4, f->sf->hits, f->sf->alb, f->sf->nz, f->sf->count, f->sf->spill};
+    for (void* p : ptrs) if (p) (void)hipFree(p);
+    delete f->sf;
+    f->sf = nullptr;
+}
 
 namespace
 {
@@ -1312,6 +1337,7 @@ int rt_frame_destroy(rt_frame* f)
     if (f->resolved_b) (void)hipFree(f->resolved_b);
     for (auto& s : f->spans) { (void)hipEventDestroy(s.a); (void)hipEventDestroy(s.b); }
     for (auto e : f->event_pool) (void)hipEventDestroy(e);
+    free_filter_state(f);
     delete f;
     return RT_OK;
 }
@@ -1630,6 +1656,8 @@ void launch_trace(rt_frame* f, const float4* o4, const float4* d4, const uint32_
     switch (variant)
     {
     case 0:
+        // (the spatial filter's guide pass, ensure_guides, launches through here with a stand-in f->p that holds only `hits`: what this case reads
+        //  from f->p must stay hits + dlog's pointers, or ensure_guides must set the rest too)
         hipLaunchKernelGGL(k_trace_v1<SHADOW>, dim3(f->trace_waves_per_cu ? (((uint32_t)ctx->prop.multiProcessorCount *
             (f->trace_waves_per_cu < 13u ? f->trace_waves_per_cu : 13u) + 7u) & ~7u) : f->trace_blocks), dim3(64), 0, f->tl_stream, ctx->scene.d, o4, d4,
             aux, count, SHADOW ? (float4*)nullptr : f->p->hits, dlog(f), f->select_form_box, f->tl_spill);
@@ -2390,6 +2418,153 @@ int rt_frame_read_radiance(rt_frame* f, float* host_rgba)
     return RT_OK;
 }
 
+
+// ---- spatial filter (spatial_filter.h states it; the kernels live in spatial_filter.hip)
+static int check_filter_desc(rt_ctx* ctx, const char* who, const rt_filter_desc* d)
+{
+    if (d->iterations > RT_FILTER_MAX_ITERATIONS) return fail(ctx, std::string(who) + ": iterations must be 0 .. 8");
+    if (d->flags & ~RT_FILTER_DEMODULATE) return fail(ctx, std::string(who) + ": unknown flags (RT_FILTER_DEMODULATE is the only one)");
+    const float sig[3] = {d->sigma_color, d->sigma_normal, d->sigma_depth};
+    for (float v : sig)
+        if (!(v > 0.0f) || !std::isfinite(v)) return fail(ctx, std::string(who) + ": sigma_color, sigma_normal and sigma_depth must be > 0 and finite");
+    return RT_OK;
+}
+
+static int check_filter_frame(rt_frame* f, const char* who)
+{
+    if (f->tile.nranks > 1) return fail(f->ctx, std::string(who) + ": a tile frame (tile_count > 1): the filter's stencil crosses rows, it needs the whole image");
+    return RT_OK;
+}
+
+// the guides for the frame's current camera: one pixel-centre ray per pixel, traced by k_trace_v1<false> (the reference's BVH2 walk) on the context's
+// stream with the filter's own buffers, then k_aov's formulas.  Recomputed when the camera or the scene (rt_scene_upload) has changed since.
+static int ensure_guides(rt_frame* f, const char* who)
+{
+    rt_ctx* ctx = f->ctx;
+    if (!ctx->scene.valid) return fail(ctx, std::string(who) + ": no scene uploaded");
+    const size_t n = f->n_local;
+    if (!f->sf)
+    {
+        SfGuides* g = new SfGuides();
+        const size_t spill_bytes = (size_t)f->trace_blocks * 64u * (RT_TRACE_STACK_MAX - RT_TRACE_STACK_LDS) * sizeof(uint2);
+        bool ok = hipMalloc((void**)&g->o4, n * sizeof(float4)) == hipSuccess && hipMalloc((void**)&g->d4, n * sizeof(float4)) == hipSuccess &&
+                  hipMalloc((void**)&g->hits, n * sizeof(float4)) == hipSuccess && hipMalloc((void**)&g->alb, n * sizeof(float4)) == hipSuccess &&
+                  hipMalloc((void**)&g->nz, n * sizeof(float4)) == hipSuccess && hipMalloc((void**)&g->count, sizeof(uint32_t)) == hipSuccess &&
+                  hipMalloc((void**)&g->spill, spill_bytes) == hipSuccess;
+        f->sf = g;
+        if (!ok)
+        {
+            (void)hipGetLastError();
+            free_filter_state(f);
+            return fail(ctx, std::string(who) + ": out of device memory for the guide pass (80 bytes per pixel)");
+        }
+    }
+    SfGuides* g = f->sf;
+    if (g->valid && g->scene == ctx->scene_uploads && memcmp(&g->camera, &f->camera, sizeof(rt_camera)) == 0) return RT_OK;
+    g->valid = false;
+    HIPCHK(ctx, sfilt::guide_rays(ctx->stream, f->tile.width, f->tile.height, f->camera, rt_tanf(0.5f * f->camera.fov), g->o4, g->d4));
+    HIPCHK(ctx, hipMemsetD32Async((hipDeviceptr_t)g->count, (int)n, 1, ctx->stream));
+    {
+        // the closest-hit trace through launch_trace's per-ray kernel k_trace_v1<false> (the reference's BVH2 walk), pointed at the filter's own hits,
+        // spill area and the context's stream for this one launch.  (Through launch_trace and not a launch of its own: a new use of the template kernel
+        // here moves where clang places its code, and the hot path's code object -- codeobj.code_object_sha256 -- must stay byte for byte what it is.)
+        PathPipe guide_pipe;
+        guide_pipe.hits = g->hits;
+        PathPipe* const keep_p = f->p;
+        const hipStream_t keep_stream = f->tl_stream;
+        uint2* const keep_spill = f->tl_spill;
+        const uint32_t keep_variant = f->trace_variant, keep_waves = f->trace_waves_per_cu;
+        f->p = &guide_pipe; f->tl_stream = ctx->stream; f->tl_spill = g->spill; f->trace_variant = 0; f->trace_waves_per_cu = 0;   // grid = trace_blocks
+        launch_trace<false>(f, g->o4, g->d4, (const uint32_t*)nullptr, g->count, 0);
+        f->p = keep_p; f->tl_stream = keep_stream; f->tl_spill = keep_spill; f->trace_variant = keep_variant; f->trace_waves_per_cu = keep_waves;
+    }
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, sfilt::guide_values(ctx->stream, ctx->scene.d, g->o4, g->hits, (uint32_t)n, g->alb, g->nz));
+    g->camera = f->camera;
+    g->scene = ctx->scene_uploads;
+    g->valid = true;
+    ++g->passes;
+    return RT_OK;
+}
+
+int rt_frame_filter(rt_frame* f, const rt_filter_desc* desc, float* host_rgba)
+{
+    if (!f || !desc || !host_rgba) return fail(nullptr, "rt_frame_filter: NULL argument");
+    rt_ctx* ctx = f->ctx;
+    (void)hipSetDevice(ctx->device);
+    if (check_filter_desc(ctx, "rt_frame_filter", desc) != RT_OK || check_filter_frame(f, "rt_frame_filter") != RT_OK) return RT_ERROR;
+    if (f->aov != 0) return fail(ctx, "rt_frame_filter: RT_OPT_AOV != 0: the filter is for the shaded colour only");
+    if (desc->iterations == 0) return rt_frame_resolve(f, host_rgba);      // exactly rt_frame_resolve's image
+    if (f->n_local == 0) return RT_OK;
+    if (ensure_guides(f, "rt_frame_filter") != RT_OK) return RT_ERROR;
+    if (rt_frame_present_wait(f) != RT_OK) return RT_ERROR;                // as rt_frame_resolve: f->resolved is the output image
+    if (flush_stage(f) != RT_OK) return RT_ERROR;
+    SfGuides* g = f->sf;
+    HIPCHK(ctx, sfilt::passes(ctx->stream, f->tile.width, f->tile.height, f->radiance, g->alb, g->nz, desc->iterations, desc->flags, desc->sigma_color,
+        desc->sigma_normal, desc->sigma_depth, f->denoiser == 0u, (float)f->sample_count, 1, g->o4, g->d4, f->resolved));
+    HIPCHK(ctx, hipMemcpyAsync(host_rgba, f->resolved, (size_t)f->n_local * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return RT_OK;
+}
+
+int rt_frame_read_guides(rt_frame* f, float* albedo_rgba, float* normal_rgba, float* depth, uint32_t* passes)
+{
+    if (!f) return fail(nullptr, "rt_frame_read_guides: NULL argument");
+    rt_ctx* ctx = f->ctx;
+    (void)hipSetDevice(ctx->device);
+    if (check_filter_frame(f, "rt_frame_read_guides") != RT_OK) return RT_ERROR;
+    if (f->n_local == 0) { if (passes) *passes = 0; return RT_OK; }
+    if (ensure_guides(f, "rt_frame_read_guides") != RT_OK) return RT_ERROR;
+    const size_t n = f->n_local;
+    if (albedo_rgba) HIPCHK(ctx, hipMemcpyAsync(albedo_rgba, f->sf->alb, n * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
+    std::vector<float4> nz((normal_rgba || depth) ? n : 0);
+    if (!nz.empty()) HIPCHK(ctx, hipMemcpyAsync(nz.data(), f->sf->nz, n * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    for (size_t i = 0; i < nz.size(); ++i)
+    {
+        if (normal_rgba) { normal_rgba[4 * i] = nz[i].x; normal_rgba[4 * i + 1] = nz[i].y; normal_rgba[4 * i + 2] = nz[i].z; normal_rgba[4 * i + 3] = 0.0f; }
+        if (depth) depth[i] = nz[i].w;
+    }
+    if (passes) *passes = f->sf->passes;
+    return RT_OK;
+}
+
+int rt_debug_filter(rt_ctx* ctx, uint32_t width, uint32_t height, const float* hdr_rgba, const float* albedo_rgba, const float* normal_rgba,
+    const float* depth, const rt_filter_desc* desc, float* out_hdr_rgba)
+{
+    if (!hdr_rgba || !albedo_rgba || !normal_rgba || !depth || !desc || !out_hdr_rgba) return fail(ctx, "rt_debug_filter: NULL argument");
+    if (width == 0 || height == 0) return fail(ctx, "rt_debug_filter: empty image");
+    if (check_filter_desc(ctx, "rt_debug_filter", desc) != RT_OK) return RT_ERROR;
+    const size_t n = (size_t)width * height;
+    if (desc->iterations == 0) { memcpy(out_hdr_rgba, hdr_rgba, n * sizeof(float4)); return RT_OK; }
+    std::vector<float> nz(4 * n);
+    for (size_t i = 0; i < n; ++i)
+    {
+        nz[4 * i] = normal_rgba[4 * i]; nz[4 * i + 1] = normal_rgba[4 * i + 1]; nz[4 * i + 2] = normal_rgba[4 * i + 2]; nz[4 * i + 3] = depth[i];
+    }
+    if (!ctx)
+    {
+        sfilt::host_passes(width, height, hdr_rgba, albedo_rgba, nz.data(), desc->iterations, desc->flags, desc->sigma_color, desc->sigma_normal,
+            desc->sigma_depth, out_hdr_rgba);
+        return RT_OK;
+    }
+    (void)hipSetDevice(ctx->device);
+    float4* buf[6] = {};
+    const size_t bytes = n * sizeof(float4);
+    bool ok = true;
+    for (float4*& b : buf) ok = ok && hipMalloc((void**)&b, bytes) == hipSuccess;
+    ok = ok && hipMemcpyAsync(buf[0], hdr_rgba, bytes, hipMemcpyHostToDevice, ctx->stream) == hipSuccess &&
+         hipMemcpyAsync(buf[1], albedo_rgba, bytes, hipMemcpyHostToDevice, ctx->stream) == hipSuccess &&
+         hipMemcpyAsync(buf[2], nz.data(), bytes, hipMemcpyHostToDevice, ctx->stream) == hipSuccess;
+    hipError_t e = ok ? sfilt::passes(ctx->stream, width, height, buf[0], buf[1], buf[2], desc->iterations, desc->flags, desc->sigma_color, desc->sigma_normal,
+        desc->sigma_depth, 0, 1.0f, 0, buf[3], buf[4], buf[5]) : hipErrorOutOfMemory;
+    if (e == hipSuccess) e = hipMemcpyAsync(out_hdr_rgba, buf[5], bytes, hipMemcpyDeviceToHost, ctx->stream);
+    hipError_t es = hipStreamSynchronize(ctx->stream);
+    for (float4* b : buf) if (b) (void)hipFree(b);
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) { (void)hipGetLastError(); return fail(ctx, std::string("rt_debug_filter: ") + hipGetErrorString(e)); }
+    return RT_OK;
+}
 void* rt_frame_radiance_device_ptr(rt_frame* f) { return f ? (void*)f->radiance : nullptr; }
 uint32_t rt_frame_sample_count(rt_frame* f) { return f ? f->sample_count : 0; }
 

@@ -72,6 +72,7 @@ HIPPathTraceIntegrator::HIPPathTraceIntegrator(std::uint32_t width, std::uint32_
     : Integrator(width, height, acc_structure), context_(context)
 {
     rt_frame_desc fd = {width, height, tile.rank, tile.count, tile.band_height};
+    tile_count_ = tile.count;
     Check(rt_frame_create(context_.Get(), &fd, &frame_));
     // a constructor that throws runs no destructor: whatever follows the frame's creation gives it back itself
     try
@@ -202,7 +203,16 @@ void HIPPathTraceIntegrator::ResolveRadiance()
 {
     // the frame's kernels have finished when this returns (Finish(), cl_pt_integrator.cpp:682); the image travels to
     // resolved_ meanwhile and GetResolvedImage() waits for it
-    if (resolve_every_frame_) Check(rt_frame_present(frame_, resolved_.data()));
+    if (!resolve_every_frame_) return;
+    if (filter_on_) Check(rt_frame_filter(frame_, &filter_, resolved_.data()));      // synchronous: the filtered image is in resolved_ on return
+    else Check(rt_frame_present(frame_, resolved_.data()));
+}
+
+void HIPPathTraceIntegrator::SetSpatialFilter(rt_filter_desc const* desc)
+{
+    if (desc && tile_count_ > 1) throw HIPException("SetSpatialFilter: a tile of a larger image: the filter needs the whole image");
+    if (desc) filter_ = *desc;
+    filter_on_ = desc != nullptr;
 }
 
 void HIPPathTraceIntegrator::IntegrateSamples(std::uint32_t n_samples)
@@ -229,7 +239,8 @@ std::vector<float> HIPPathTraceIntegrator::ReadRadianceSum() const
 
 std::vector<float> const& HIPPathTraceIntegrator::ResolveNow()
 {
-    Check(rt_frame_resolve(frame_, resolved_.data()));
+    if (filter_on_) Check(rt_frame_filter(frame_, &filter_, resolved_.data()));
+    else Check(rt_frame_resolve(frame_, resolved_.data()));
     return resolved_;
 }
 

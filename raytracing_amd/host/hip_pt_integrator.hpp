@@ -78,6 +78,10 @@ public:
     void SetSamplesAhead(std::uint32_t mode);
     // packed uint8 tables, see tools/make_blue_noise_asset.py (default: relative to the CWD like the env map)
     void SetBlueNoiseTablePath(std::string path) { blue_noise_path_ = std::move(path); }
+    // The spatial filter (rt_frame_filter, the edge-avoiding a-trous wavelet filter): desc = its settings (copied; RT_FILTER_DESC_DEFAULT is a good
+    // start), nullptr = off (the default).  While it is on, ResolveRadiance() and ResolveNow() produce the FILTERED image through rt_frame_filter --
+    // synchronously, without the asynchronous present.  A tile of a larger image (TileDesc::count > 1) refuses: the filter needs the whole image.
+    void SetSpatialFilter(rt_filter_desc const* desc);
     rt_frame* GetFrame() const { return frame_; }
 
 protected:
@@ -106,6 +110,9 @@ private:
     std::vector<float> resolved_;
     bool resolved_pinned_ = false;     // resolved_ is page-locked (rt_host_register)
     bool resolve_every_frame_ = true;
+    bool filter_on_ = false;           // SetSpatialFilter
+    rt_filter_desc filter_ = RT_FILTER_DESC_DEFAULT;
+    std::uint32_t tile_count_ = 1;
     std::string blue_noise_path_ = "assets/blue_noise/heitz2019_256spp_256d.bin";
 };
 } // namespace rt

@@ -28,6 +28,8 @@ int main(int argc, char** argv)
         float scale = 1.0f, aperture = 0.0f, focus = 10.0f;
         bool flip_yz = false, furnace = false, tiled_path = false, shared_device = false, plan_only = false, resolve = true;
         unsigned scene_options = 0;      // rt::Scene::Options (opt-in extensions)
+        int filter_iterations = -1;      // --filter n: the spatial filter (rt_frame_filter); -1 = off
+        rt_filter_desc filter = RT_FILTER_DESC_DEFAULT;
         for (int i = 1; i < argc; ++i)
         {
             auto next = [&]() -> const char* { if (i + 1 >= argc) { std::cerr << "missing value for " << argv[i] << "\n"; exit(2); } return argv[++i]; };
@@ -52,6 +54,16 @@ int main(int argc, char** argv)
             else if (!strcmp(argv[i], "--plan")) plan_only = atoi(next()) != 0;              // print the tiling and exit: no GPU, no scene
             else if (!strcmp(argv[i], "--wide_texture_indices")) { if (atoi(next()) != 0) scene_options |= rt::Scene::kWideTextureIndices; }
             else if (!strcmp(argv[i], "--emissive_nee")) { if (atoi(next()) != 0) scene_options |= rt::Scene::kEmissiveNee; }
+            else if (!strcmp(argv[i], "--filter")) filter_iterations = atoi(next());          // the spatial filter with n iterations; --out writes the filtered image
+            else if (!strcmp(argv[i], "--filter_sigmas"))
+            {
+                const char* v = next();
+                if (sscanf(v, "%f,%f,%f", &filter.sigma_color, &filter.sigma_normal, &filter.sigma_depth) != 3)
+                {
+                    std::cerr << "--filter_sigmas wants c,n,z (three numbers)\n";
+                    return 2;
+                }
+            }
             else if (!strcmp(argv[i], "--help"))
             {
                 std::cout << "rt_render -w W -h H --scene file.obj [--scale s] [--flip_yz 0|1] [--spp n] [--bounces b]"
@@ -63,8 +75,19 @@ int main(int argc, char** argv)
                              "  the fifteen hooks, one sample per pixel, ResolveRadiance + Finish() every frame (src/render.cpp:172-204);\n"
                              "  --samples_ahead 0 makes every one of them trace its own sample (default 1: a standing camera's next samples are traced ahead in batches)\n"
                              "  extensions (off = the reference's behaviour): --wide_texture_indices 1 loads scenes with more than 255\n"
-                             "  textures; --emissive_nee 1 adds the emissive triangles to next-event estimation\n";
+                             "  textures; --emissive_nee 1 adds the emissive triangles to next-event estimation\n"
+                             "  --filter n [--filter_sigmas c,n,z] runs the spatial filter (n a-trous iterations, 0 .. 8; sigmas default to\n"
+                             "  RT_FILTER_DESC_DEFAULT's) and --out then writes the filtered, tone-mapped image; whole images only (not with --gpus > 1)\n";
                 return 0;
+            }
+        }
+        if (filter_iterations >= 0)
+        {
+            filter.iterations = (std::uint32_t)filter_iterations;
+            if (gpus > 1)
+            {
+                std::cerr << "--filter needs the whole image on one GPU: not with --gpus > 1\n";
+                return 2;
             }
         }
         if (plan_only)
@@ -89,6 +112,7 @@ int main(int argc, char** argv)
             std::vector<int> devices;
             for (unsigned d = 0; d < gpus; ++d) devices.push_back(shared_device ? 0 : (int)d);
             rt::TiledRender tiled(width, height, scene, devices);
+            tiled.SetSpatialFilter(filter_iterations >= 0 ? &filter : nullptr);   // (refuses any filter)
             for (unsigned d = 0; d < gpus; ++d) std::cout << "tile " << d << " on device " << devices[d] << ": " << tiled.GetContext(d).DeviceName() << std::endl;
             std::cout << "gather: " << (tiled.GetRcclRanks() ? "RCCL ncclGather, communicator of " + std::to_string(tiled.GetRcclRanks()) + " ranks"
                                                               : std::string("device copies on one GPU (local group)")) << std::endl;
@@ -126,6 +150,7 @@ int main(int argc, char** argv)
         render.SetCamera(cam);
         render.GetIntegrator().SetMaxBounces(bounces);
         render.GetIntegrator().EnableWhiteFurnace(furnace);
+        render.GetIntegrator().SetSpatialFilter(filter_iterations >= 0 ? &filter : nullptr);
         if (frames != 0)
         {
             // timing run: wait for the fold adaptation instead of adopting it whenever its worker is done (RT_CTX_OPT_ADAPTIVE_FOLD | 2, as bench.py does)
@@ -161,7 +186,9 @@ int main(int argc, char** argv)
         rt_stats st = render.GetIntegrator().GetStats();
         double rays = (double)st.closest_rays + (double)st.shadow_rays;
         std::cout << spp << " spp in " << dt << " s, " << rays / dt / 1e6 << " Mrays/s" << std::endl;
-        if (!out.empty())
+        if (!out.empty() && filter_iterations >= 0)
+            WritePFM(out.c_str(), render.GetIntegrator().ResolveNow(), width, height);     // the filtered, tone-mapped image
+        else if (!out.empty())
         {
             std::vector<float> sum = render.GetIntegrator().ReadRadianceSum();
             for (float& v : sum) v /= (float)spp;

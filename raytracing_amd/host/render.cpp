@@ -158,6 +158,11 @@ void TiledRender::EnableWhiteFurnace(bool enable)
     for (auto& i : integrators_) i->EnableWhiteFurnace(enable);
 }
 
+void TiledRender::SetSpatialFilter(rt_filter_desc const* desc)
+{
+    if (desc) throw HIPException("TiledRender: the spatial filter needs the whole image (its stencil crosses the tiles' rows); gather and filter on one GPU instead");
+}
+
 void TiledRender::RenderSamples(std::uint32_t n)
 {
     std::vector<std::thread> workers;

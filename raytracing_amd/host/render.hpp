@@ -65,6 +65,8 @@ public:
     void SetCamera(Camera const& camera);
     void SetMaxBounces(std::uint32_t max_bounces);
     void EnableWhiteFurnace(bool enable);
+    // The spatial filter needs the whole image (its stencil crosses the tiles' rows): any desc throws; nullptr (off) is accepted.
+    void SetSpatialFilter(rt_filter_desc const* desc);
     void RenderSamples(std::uint32_t n);                  // every tile, concurrently; returns when all are enqueued and finished
     std::vector<float> GatherRadiance(int root = 0);      // height x width x RGBA running sums, image order
     rt_stats GetStats() const;                            // ray counters summed over the tiles
