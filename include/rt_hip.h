@@ -405,6 +405,47 @@ int rt_frame_read_guides(rt_frame* frame, float* albedo_rgba, float* normal_rgba
 int rt_debug_filter(rt_ctx* ctx, uint32_t width, uint32_t height, const float* hdr_rgba, const float* albedo_rgba,
     const float* normal_rgba, const float* depth, const rt_filter_desc* desc, float* out_hdr_rgba);
 
+/* ---- temporal filter (opt-in extension; no reference counterpart): the spatiotemporal variance-guided filter (SVGF) of Schied et al.
+ * 2017 for a moving camera's one-sample frames (raytracing_amd/csrc/temporal_filter.h states it exactly).  A new output
+ * beside rt_frame_resolve and rt_frame_filter: the frame's radiance and every other result are untouched.  Per call:
+ *   - reproject: every pixel's first hit (the spatial filter's guides) is projected into the PREVIOUS call's camera; bilinear taps whose depth
+ *     and normal agree supply a colour history and the luminance moments (mu1, mu2) with their length L;
+ *   - accumulate: the (demodulated) colour and moments blend into the history by max(alpha, 1 / L);
+ *   - variance: mu2 - mu1^2 where L >= 4, a 7 x 7 spatial estimate elsewhere;
+ *   - iterations a-trous passes whose colour weight scales with the variance (sigma_luminance); pass 0's output is the next call's history.
+ * The history lives on the frame: made on first use, freed by rt_frame_destroy, dropped by rt_scene_upload and rt_frame_filter_history_reset.
+ * Whole images only (a tile frame is refused), the shaded colour only (RT_OPT_AOV != 0 is refused), and not over the reference's temporal
+ * denoiser (RT_OPT_DENOISER != 0 is refused: two temporal accumulations in a row). */
+typedef struct rt_temporal_filter_desc
+{
+    uint32_t iterations;           /* 0 .. 8 variance-guided a-trous passes; pass i spaces its 5x5 taps 2^i pixels apart */
+    uint32_t flags;                /* RT_FILTER_DEMODULATE */
+    float alpha_color;             /* 0 .. 1: the least weight of this call's colour in the history (1 = no history) */
+    float alpha_moments;           /* 0 .. 1: the same for the luminance moments */
+    float sigma_luminance, sigma_normal, sigma_depth;   /* each > 0 and finite */
+} rt_temporal_filter_desc;
+/* the defaults: the best mean of tools/temporal_filter_sweep.py's grid (tone-mapped MSE of the last of 16 moving-camera 1-spp frames against
+ * 1024 spp, relative to the unfiltered frame's, 128 x 128, 4 bounces: Cornell box 0.090, coverage scene 0.215) */
+#define RT_TEMPORAL_FILTER_DESC_DEFAULT { 5u, RT_FILTER_DEMODULATE, 0.2f, 0.2f, 2.0f, 0.05f, 0.1f }
+
+/* resolve + reproject + accumulate + filter: RGBA float, tone-mapped (Reinhard), alpha 1, synchronous; the history advances by this call.
+ * alpha_color = 1 with zero iterations is rt_frame_resolve's image bit for bit.  Fails (frame and history untouched) for NULL arguments, desc
+ * values out of range, a tile frame, RT_OPT_AOV != 0 or RT_OPT_DENOISER != 0. */
+int rt_frame_filter_temporal(rt_frame* frame, const rt_temporal_filter_desc* desc, float* host_rgba);
+/* drop the history: every pixel misses at the next rt_frame_filter_temporal */
+int rt_frame_filter_history_reset(rt_frame* frame);
+/* the history after the last call: colour RGBA (demodulated with RT_FILTER_DEMODULATE; alpha 0), moments_len RGBA = (mu1, mu2, L, 0); L = 0
+ * where nothing may reproject from (no first hit, a pass-through pixel, no call yet, a dropped history).  Either array may be NULL. */
+int rt_frame_read_filter_history(rt_frame* frame, float* color_rgba, float* moments_len);
+/* the temporal filter on caller arrays (width x height, row-major, 4 floats per pixel except depth): HDR in, HDR out (no tone mapping),
+ * on the GPU of ctx or the host restatement of the same arithmetic when ctx == NULL; the two agree bit for bit.  prev_cam == NULL, or bytes
+ * equal to cam's, reuse each pixel's own history (a standing camera); otherwise the history is reprojected from prev_cam with prev_normal /
+ * prev_depth.  hist_color / hist_moments: the previous call's history (L = 0: none); the new history is written to the *_out arrays. */
+int rt_debug_filter_temporal(rt_ctx* ctx, uint32_t width, uint32_t height, const rt_camera* cam, const rt_camera* prev_cam,
+    const float* hdr_rgba, const float* albedo_rgba, const float* normal_rgba, const float* depth, const float* prev_normal_rgba,
+    const float* prev_depth, const float* hist_color, const float* hist_moments, const rt_temporal_filter_desc* desc, float* out_hdr_rgba,
+    float* hist_color_out, float* hist_moments_out);
+
 /* ---- statistics: the queue counters the reference keeps in
  * ray_counter_buffer_[2] / shadow_ray_counter_buffer_ (cl_pt_integrator.hpp:85-86),
  * sampled per bounce and accumulated on the device. */

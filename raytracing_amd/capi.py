@@ -70,6 +70,26 @@ def filter_desc(desc=None, **kw):
     return rt_filter_desc(v["iterations"], v["flags"], v["sigma_color"], v["sigma_normal"], v["sigma_depth"])
 
 
+class rt_temporal_filter_desc(C.Structure):
+    _fields_ = [("iterations", C.c_uint32), ("flags", C.c_uint32), ("alpha_color", C.c_float), ("alpha_moments", C.c_float),
+                ("sigma_luminance", C.c_float), ("sigma_normal", C.c_float), ("sigma_depth", C.c_float)]
+
+
+# RT_TEMPORAL_FILTER_DESC_DEFAULT
+TEMPORAL_FILTER_DEFAULT = dict(iterations=5, flags=FILTER_DEMODULATE, alpha_color=0.2, alpha_moments=0.2, sigma_luminance=2.0, sigma_normal=0.05,
+                               sigma_depth=0.1)
+
+
+def temporal_filter_desc(desc=None, **kw):
+    """an rt_temporal_filter_desc from None (the header's defaults), a dict, keywords or an rt_temporal_filter_desc"""
+    if isinstance(desc, rt_temporal_filter_desc):
+        return desc
+    v = dict(TEMPORAL_FILTER_DEFAULT)
+    v.update(desc or {})
+    v.update(kw)
+    return rt_temporal_filter_desc(*(v[k] for k, _ in rt_temporal_filter_desc._fields_))
+
+
 EXPORTS = [
     "rt_ctx_create", "rt_ctx_destroy", "rt_finish", "rt_last_error", "rt_ctx_device_info", "rt_ctx_stream",
     "rt_ctx_set_option", "rt_upload_blue_noise_tables", "rt_host_register", "rt_host_unregister",
@@ -87,6 +107,7 @@ EXPORTS = [
     "rt_group_gather_radiance", "rt_group_destroy", "rt_group_last_error", "rt_group_denoise", "rt_group_create_local",
     "rt_group_create_unchecked",
     "rt_frame_filter", "rt_frame_read_guides", "rt_debug_filter",
+    "rt_frame_filter_temporal", "rt_frame_filter_history_reset", "rt_frame_read_filter_history", "rt_debug_filter_temporal",
 ]
 
 OPT_MAX_BOUNCES, OPT_WHITE_FURNACE, OPT_SAMPLER, OPT_AOV, OPT_DENOISER, OPT_DROP_LAST, OPT_PROFILE, OPT_TRACE_VARIANT, OPT_TRACE_WAVES, OPT_SAMPLES_IN_FLIGHT, OPT_SELECT_FORM_BOX, OPT_PACKET_BOUNCES, OPT_TRACE_TUNE, OPT_DEBUG_ALLOC_LIMIT, OPT_PATH_STATE_LIMIT_MB, OPT_PIPELINES, OPT_SHADE_PARTITION, OPT_OVERLAP_SHADOW, OPT_SMALL_LAUNCH_PATHS, OPT_COMPACT_LOG, OPT_DEBUG_LOG_POOL_DIV, OPT_TRACE_TAIL_LANES, OPT_TRACE_TAIL_PATHS, OPT_CHUNK_REFILL, OPT_STAGE_PIPES, OPT_FRAME_KERNEL, OPT_SAMPLES_AHEAD = range(27)
@@ -160,6 +181,10 @@ def load():
         "rt_frame_filter": (i32, [vp, C.POINTER(rt_filter_desc), vp]),
         "rt_frame_read_guides": (i32, [vp, vp, vp, vp, C.POINTER(u32)]),
         "rt_debug_filter": (i32, [vp, u32, u32, vp, vp, vp, vp, C.POINTER(rt_filter_desc), vp]),
+        "rt_frame_filter_temporal": (i32, [vp, C.POINTER(rt_temporal_filter_desc), vp]),
+        "rt_frame_filter_history_reset": (i32, [vp]),
+        "rt_frame_read_filter_history": (i32, [vp, vp, vp]),
+        "rt_debug_filter_temporal": (i32, [vp, u32, u32, vp, vp] + [vp] * 8 + [C.POINTER(rt_temporal_filter_desc), vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -190,6 +215,30 @@ def debug_filter(ctx, hdr, albedo, normal, depth, desc=None):
     if lib.rt_debug_filter(handle, w, h, hdr.ctypes.data, alb.ctypes.data, nrm.ctypes.data, dep.ctypes.data, C.byref(d), out.ctypes.data):
         raise RtError(lib.rt_last_error(handle).decode())
     return out
+
+
+def debug_filter_temporal(ctx, cam, prev_cam, hdr, albedo, normal, depth, prev_normal, prev_depth, hist_color, hist_moments, desc=None):
+    """rt_debug_filter_temporal: one call of the temporal filter over caller arrays (hdr, albedo, normal, prev_normal, hist_color, hist_moments:
+    float32[h, w, 4]; depth, prev_depth: float32[h, w]; cam, prev_cam: types.camera, prev_cam None = a standing camera) on ctx's GPU, or the
+    host restatement when ctx is None.  Returns (HDR image, colour history, moments history (mu1, mu2, L, 0)), each float32[h, w, 4]."""
+    lib = load()
+    hdr = np.ascontiguousarray(hdr, np.float32)
+    h, w = hdr.shape[:2]
+    four = [np.ascontiguousarray(a, np.float32) for a in (albedo, normal, prev_normal, hist_color, hist_moments)]
+    dep, pdep = (np.ascontiguousarray(a, np.float32) for a in (depth, prev_depth))
+    if hdr.shape != (h, w, 4) or any(a.shape != hdr.shape for a in four) or dep.shape != (h, w) or pdep.shape != (h, w):
+        raise ValueError("debug_filter_temporal: images must be [h, w, 4], depths [h, w]")
+    alb, nrm, pnrm, hc, hm = four
+    cam = np.ascontiguousarray(cam)
+    pc = np.ascontiguousarray(prev_cam) if prev_cam is not None else None
+    out, hc_out, hm_out = np.zeros_like(hdr), np.zeros_like(hdr), np.zeros_like(hdr)
+    handle = ctx.handle if ctx is not None else None
+    d = temporal_filter_desc(desc)
+    if lib.rt_debug_filter_temporal(handle, w, h, cam.ctypes.data, pc.ctypes.data if pc is not None else None, hdr.ctypes.data, alb.ctypes.data,
+                                    nrm.ctypes.data, dep.ctypes.data, pnrm.ctypes.data, pdep.ctypes.data, hc.ctypes.data, hm.ctypes.data, C.byref(d),
+                                    out.ctypes.data, hc_out.ctypes.data, hm_out.ctypes.data):
+        raise RtError(lib.rt_last_error(handle).decode())
+    return out, hc_out, hm_out
 
 
 def choose_tree(scene, shadow=True, mode=1):
@@ -517,6 +566,24 @@ class Frame:
         passes = C.c_uint32()
         self._c(self.lib.rt_frame_read_guides(self.handle, alb.ctypes.data, nrm.ctypes.data, dep.ctypes.data, C.byref(passes)))
         return alb, nrm, dep, passes.value
+
+    def filter_temporal(self, desc=None):
+        """rt_frame_filter_temporal: the resolved image reprojected, accumulated with the frame's history and passed through the variance-guided
+        filter (float32[rows, width, 4], tone-mapped); the history advances.  desc None = the header's defaults"""
+        out = np.zeros((self.local_rows, self.width, 4), np.float32)
+        self._c(self.lib.rt_frame_filter_temporal(self.handle, C.byref(temporal_filter_desc(desc)), out.ctypes.data))
+        return out
+
+    def filter_history(self):
+        """rt_frame_read_filter_history: (colour float32[h, w, 4], moments float32[h, w, 4] = (mu1, mu2, L, 0))"""
+        col = np.zeros((self.local_rows, self.width, 4), np.float32)
+        mom = np.zeros_like(col)
+        self._c(self.lib.rt_frame_read_filter_history(self.handle, col.ctypes.data, mom.ctypes.data))
+        return col, mom
+
+    def filter_history_reset(self):
+        """rt_frame_filter_history_reset: every pixel misses at the next filter_temporal"""
+        self._c(self.lib.rt_frame_filter_history_reset(self.handle))
 
     def present(self, out=None):
         """rt_frame_present: resolve + Finish() on the frame's kernels; the image travels to `out` (kept alive by the caller) on a

@@ -24,6 +24,7 @@
 #include "wide_bvh.h"        // the host-side fold, the pair layout, the adaptation's host walks (wide_bvh.cpp)
 #include "device_fold.h"     // ... and the fold + crossing counts on the device (device_fold.hip)
 #include "spatial_filter_host.h"   // the spatial filter's guide pass and a-trous passes (spatial_filter.hip)
+#include "temporal_filter_host.h"  // the temporal filter's accumulation, variance and variance-guided passes (temporal_filter.hip)
 using namespace rtw;
 
 namespace
@@ -253,6 +254,7 @@ struct rt_frame
     std::vector<Span> spans;
     std::vector<hipEvent_t> event_pool;
     struct SfGuides* sf = nullptr;     // rt_frame_filter / rt_frame_read_guides: the guide pass's buffers and what they were made for (made on first use)
+    struct TfState* tf = nullptr;      // rt_frame_filter_temporal: the history (made on first use)
 };
 
 static int sync_frame_streams(rt_frame* f);
@@ -282,6 +284,28 @@ static void free_filter_state(rt_frame* f)
     for (void* p : ptrs) if (p) (void)hipFree(p);
     delete f->sf;
     f->sf = nullptr;
+}
+
+// The temporal filter's history on a frame (rt_frame_filter_temporal): made on first use, freed by rt_frame_destroy.  64 bytes per pixel: the colour
+// history, two moments images (mu1, mu2, L) -- the accumulation reads one and writes the other, which is then the history -- and the previous call's
+// normal + depth guide, copied after each call (the guide pass overwrites its own for a new camera).  Its scratch images are the spatial filter's o4 / d4.
+struct TfState
+{
+    float4* hist = nullptr;
+    float4* mom[2] = {nullptr, nullptr};
+    float4* prev_nz = nullptr;
+    uint32_t cur = 0;                                  // mom[cur] is the history
+    rt_camera prev_cam;                                // the previous call's camera and scene (rt_scene_upload count)
+    uint64_t prev_scene = 0;
+    bool has_prev = false;                             // false: no call yet, or the history was dropped
+};
+static void free_temporal_state(rt_frame* f)
+{
+    if (!f->tf) return;
+    void* ptrs[] = {f->tf->hist, f->tf->mom[0], f->tf->mom[1], f->tf->prev_nz};
+    for (void* p : ptrs) if (p) (void)hipFree(p);
+    delete f->tf;
+    f->tf = nullptr;
 }
 
 namespace
@@ -1338,6 +1362,7 @@ int rt_frame_destroy(rt_frame* f)
     for (auto& s : f->spans) { (void)hipEventDestroy(s.a); (void)hipEventDestroy(s.b); }
     for (auto e : f->event_pool) (void)hipEventDestroy(e);
     free_filter_state(f);
+    free_temporal_state(f);
     delete f;
     return RT_OK;
 }
@@ -2563,6 +2588,152 @@ int rt_debug_filter(rt_ctx* ctx, uint32_t width, uint32_t height, const float* h
     for (float4* b : buf) if (b) (void)hipFree(b);
     if (e == hipSuccess) e = es;
     if (e != hipSuccess) { (void)hipGetLastError(); return fail(ctx, std::string("rt_debug_filter: ") + hipGetErrorString(e)); }
+    return RT_OK;
+}
+
+
+// ---- temporal filter (temporal_filter.h states it; the kernels live in temporal_filter.hip)
+static int check_temporal_desc(rt_ctx* ctx, const char* who, const rt_temporal_filter_desc* d)
+{
+    if (d->iterations > RT_FILTER_MAX_ITERATIONS) return fail(ctx, std::string(who) + ": iterations must be 0 .. 8");
+    if (d->flags & ~RT_FILTER_DEMODULATE) return fail(ctx, std::string(who) + ": unknown flags (RT_FILTER_DEMODULATE is the only one)");
+    if (!(d->alpha_color >= 0.0f && d->alpha_color <= 1.0f) || !(d->alpha_moments >= 0.0f && d->alpha_moments <= 1.0f))
+        return fail(ctx, std::string(who) + ": alpha_color and alpha_moments must be in 0 .. 1");
+    const float sig[3] = {d->sigma_luminance, d->sigma_normal, d->sigma_depth};
+    for (float v : sig)
+        if (!(v > 0.0f) || !std::isfinite(v)) return fail(ctx, std::string(who) + ": sigma_luminance, sigma_normal and sigma_depth must be > 0 and finite");
+    return RT_OK;
+}
+
+int rt_frame_filter_temporal(rt_frame* f, const rt_temporal_filter_desc* desc, float* host_rgba)
+{
+    static const char* who = "rt_frame_filter_temporal";
+    if (!f || !desc || !host_rgba) return fail(nullptr, "rt_frame_filter_temporal: NULL argument");
+    rt_ctx* ctx = f->ctx;
+    (void)hipSetDevice(ctx->device);
+    if (check_temporal_desc(ctx, who, desc) != RT_OK || check_filter_frame(f, who) != RT_OK) return RT_ERROR;
+    if (f->aov != 0) return fail(ctx, "rt_frame_filter_temporal: RT_OPT_AOV != 0: the filter is for the shaded colour only");
+    if (f->denoiser != 0)
+        return fail(ctx, "rt_frame_filter_temporal: RT_OPT_DENOISER != 0: the frame is already accumulated over time by the reference's denoiser");
+    if (f->n_local == 0) return RT_OK;
+    const size_t n = f->n_local;
+    if (!f->tf)
+    {
+        TfState* t = new TfState();
+        bool ok = hipMalloc((void**)&t->hist, n * sizeof(float4)) == hipSuccess && hipMalloc((void**)&t->mom[0], n * sizeof(float4)) == hipSuccess &&
+                  hipMalloc((void**)&t->mom[1], n * sizeof(float4)) == hipSuccess && hipMalloc((void**)&t->prev_nz, n * sizeof(float4)) == hipSuccess;
+        f->tf = t;
+        ok = ok && hipMemsetAsync(t->hist, 0, n * sizeof(float4), ctx->stream) == hipSuccess &&
+             hipMemsetAsync(t->mom[0], 0, n * sizeof(float4), ctx->stream) == hipSuccess;
+        if (!ok)
+        {
+            (void)hipGetLastError();
+            free_temporal_state(f);
+            return fail(ctx, "rt_frame_filter_temporal: out of device memory for the history (64 bytes per pixel)");
+        }
+    }
+    if (ensure_guides(f, who) != RT_OK) return RT_ERROR;
+    if (rt_frame_present_wait(f) != RT_OK) return RT_ERROR;                // as rt_frame_resolve: f->resolved is the output image
+    if (flush_stage(f) != RT_OK) return RT_ERROR;
+    TfState* t = f->tf;
+    SfGuides* g = f->sf;
+    tfilt::Call c;
+    c.width = f->tile.width; c.height = f->tile.height;
+    c.cam = f->camera;
+    c.prev = t->has_prev ? t->prev_cam : f->camera;
+    c.mode = !t->has_prev || t->prev_scene != ctx->scene_uploads ? tfilt::NO_HISTORY
+           : memcmp(&t->prev_cam, &f->camera, sizeof(rt_camera)) == 0 ? tfilt::IDENTITY : tfilt::REPROJECT;
+    c.desc = *desc;
+    c.divide = 1; c.spp = (float)f->sample_count; c.tonemap = 1;
+    HIPCHK(ctx, tfilt::run(ctx->stream, c, f->radiance, g->alb, g->nz, t->prev_nz, t->hist, t->mom[t->cur], t->hist, t->mom[t->cur ^ 1u], g->o4, g->d4,
+        f->resolved));
+    t->cur ^= 1u;
+    HIPCHK(ctx, hipMemcpyAsync(t->prev_nz, g->nz, n * sizeof(float4), hipMemcpyDeviceToDevice, ctx->stream));
+    t->prev_cam = f->camera;
+    t->prev_scene = ctx->scene_uploads;
+    t->has_prev = true;
+    HIPCHK(ctx, hipMemcpyAsync(host_rgba, f->resolved, n * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return RT_OK;
+}
+
+int rt_frame_filter_history_reset(rt_frame* f)
+{
+    if (!f) return fail(nullptr, "rt_frame_filter_history_reset: NULL argument");
+    rt_ctx* ctx = f->ctx;
+    (void)hipSetDevice(ctx->device);
+    if (!f->tf) return RT_OK;
+    f->tf->has_prev = false;
+    HIPCHK(ctx, hipMemsetAsync(f->tf->hist, 0, (size_t)f->n_local * sizeof(float4), ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(f->tf->mom[f->tf->cur], 0, (size_t)f->n_local * sizeof(float4), ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return RT_OK;
+}
+
+int rt_frame_read_filter_history(rt_frame* f, float* color_rgba, float* moments_len)
+{
+    if (!f) return fail(nullptr, "rt_frame_read_filter_history: NULL argument");
+    rt_ctx* ctx = f->ctx;
+    (void)hipSetDevice(ctx->device);
+    if (check_filter_frame(f, "rt_frame_read_filter_history") != RT_OK) return RT_ERROR;
+    const size_t n = f->n_local;
+    if (!f->tf)
+    {
+        if (color_rgba) memset(color_rgba, 0, n * sizeof(float4));
+        if (moments_len) memset(moments_len, 0, n * sizeof(float4));
+        return RT_OK;
+    }
+    if (color_rgba) HIPCHK(ctx, hipMemcpyAsync(color_rgba, f->tf->hist, n * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
+    if (moments_len) HIPCHK(ctx, hipMemcpyAsync(moments_len, f->tf->mom[f->tf->cur], n * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return RT_OK;
+}
+
+int rt_debug_filter_temporal(rt_ctx* ctx, uint32_t width, uint32_t height, const rt_camera* cam, const rt_camera* prev_cam, const float* hdr_rgba,
+    const float* albedo_rgba, const float* normal_rgba, const float* depth, const float* prev_normal_rgba, const float* prev_depth,
+    const float* hist_color, const float* hist_moments, const rt_temporal_filter_desc* desc, float* out_hdr_rgba, float* hist_color_out,
+    float* hist_moments_out)
+{
+    if (!cam || !hdr_rgba || !albedo_rgba || !normal_rgba || !depth || !prev_normal_rgba || !prev_depth || !hist_color || !hist_moments || !desc ||
+        !out_hdr_rgba || !hist_color_out || !hist_moments_out)
+        return fail(ctx, "rt_debug_filter_temporal: NULL argument");
+    if (width == 0 || height == 0) return fail(ctx, "rt_debug_filter_temporal: empty image");
+    if (check_temporal_desc(ctx, "rt_debug_filter_temporal", desc) != RT_OK) return RT_ERROR;
+    const size_t n = (size_t)width * height;
+    std::vector<float> nz(4 * n), pnz(4 * n);
+    for (size_t i = 0; i < n; ++i)
+    {
+        for (int k = 0; k < 3; ++k) { nz[4 * i + k] = normal_rgba[4 * i + k]; pnz[4 * i + k] = prev_normal_rgba[4 * i + k]; }
+        nz[4 * i + 3] = depth[i]; pnz[4 * i + 3] = prev_depth[i];
+    }
+    tfilt::Call c;
+    c.width = width; c.height = height;
+    c.cam = *cam;
+    c.prev = prev_cam ? *prev_cam : *cam;
+    c.mode = !prev_cam || memcmp(prev_cam, cam, sizeof(rt_camera)) == 0 ? tfilt::IDENTITY : tfilt::REPROJECT;
+    c.desc = *desc;
+    c.divide = 0; c.spp = 1.0f; c.tonemap = 0;
+    if (!ctx)
+    {
+        tfilt::host_run(c, hdr_rgba, albedo_rgba, nz.data(), pnz.data(), hist_color, hist_moments, hist_color_out, hist_moments_out, out_hdr_rgba);
+        return RT_OK;
+    }
+    (void)hipSetDevice(ctx->device);
+    float4* buf[11] = {};         // hdr, albedo, nz, prev nz, hist in, moments in, hist out, moments out, a, b, out
+    const size_t bytes = n * sizeof(float4);
+    bool ok = true;
+    for (float4*& b : buf) ok = ok && hipMalloc((void**)&b, bytes) == hipSuccess;
+    const void* in[6] = {hdr_rgba, albedo_rgba, nz.data(), pnz.data(), hist_color, hist_moments};
+    for (int k = 0; k < 6; ++k) ok = ok && hipMemcpyAsync(buf[k], in[k], bytes, hipMemcpyHostToDevice, ctx->stream) == hipSuccess;
+    hipError_t e = ok ? tfilt::run(ctx->stream, c, buf[0], buf[1], buf[2], buf[3], buf[4], buf[5], buf[6], buf[7], buf[8], buf[9], buf[10])
+                      : hipErrorOutOfMemory;
+    if (e == hipSuccess) e = hipMemcpyAsync(out_hdr_rgba, buf[10], bytes, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(hist_color_out, buf[6], bytes, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(hist_moments_out, buf[7], bytes, hipMemcpyDeviceToHost, ctx->stream);
+    hipError_t es = hipStreamSynchronize(ctx->stream);
+    for (float4* b : buf) if (b) (void)hipFree(b);
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) { (void)hipGetLastError(); return fail(ctx, std::string("rt_debug_filter_temporal: ") + hipGetErrorString(e)); }
     return RT_OK;
 }
 void* rt_frame_radiance_device_ptr(rt_frame* f) { return f ? (void*)f->radiance : nullptr; }

@@ -18,7 +18,7 @@ EXPORTS = [
     "rth_bvh_nodes", "rth_load_hdr", "rth_load_tga", "rth_load_png", "rth_loaded_image_data", "rth_default_camera",
     "rth_make_camera", "rth_render_create", "rth_render_destroy", "rth_render_set_camera",
     "rth_render_set_max_bounces", "rth_render_enable_white_furnace", "rth_render_set_sampler",
-    "rth_render_enable_denoiser", "rth_render_set_spatial_filter", "rth_render_set_resolve_every_frame", "rth_render_frame", "rth_render_samples",
+    "rth_render_enable_denoiser", "rth_render_set_spatial_filter", "rth_render_set_temporal_filter", "rth_render_set_resolve_every_frame", "rth_render_frame", "rth_render_samples",
     "rth_render_finish", "rth_render_local_rows", "rth_render_global_row", "rth_render_sample_count",
     "rth_render_read_radiance", "rth_render_read_resolved", "rth_render_stats", "rth_render_frame_handle",
     "rth_render_ctx_handle", "rth_render_num_nodes", "rth_render_nodes", "rth_render_set_aov", "rth_render_resolve",
@@ -58,7 +58,7 @@ def load():
         "rth_render_set_camera": (i32, [vp, vp]), "rth_render_set_max_bounces": (i32, [vp, u32]),
         "rth_render_enable_white_furnace": (i32, [vp, i32]), "rth_render_set_sampler": (i32, [vp, i32]),
         "rth_render_enable_denoiser": (i32, [vp, i32]), "rth_render_set_resolve_every_frame": (i32, [vp, i32]),
-        "rth_render_set_spatial_filter": (i32, [vp, vp]),
+        "rth_render_set_spatial_filter": (i32, [vp, vp]), "rth_render_set_temporal_filter": (i32, [vp, vp]),
         "rth_render_frame": (i32, [vp]), "rth_render_samples": (i32, [vp, u32]), "rth_render_reserve_samples": (i32, [vp, u32]), "rth_render_finish": (i32, [vp]),
         "rth_render_setup_seconds": (None, [vp, C.POINTER(C.c_double)]),
         "rth_render_local_rows": (u32, [vp]), "rth_render_global_row": (u32, [vp, u32]),
@@ -305,6 +305,13 @@ class Render:
         from . import capi
         d = capi.filter_desc(desc) if on else None
         self._c(self.lib.rth_render_set_spatial_filter(self.handle, C.byref(d) if d is not None else None))
+    def set_temporal_filter(self, desc=None, on=True):
+        """HIPPathTraceIntegrator::SetTemporalFilter: resolve_now() / the per-frame resolve then produce the temporally filtered image
+        (rt_frame_filter_temporal), each advancing the history.  desc: None = the header's defaults, a dict or capi.rt_temporal_filter_desc;
+        on=False switches the filter off."""
+        from . import capi
+        d = capi.temporal_filter_desc(desc) if on else None
+        self._c(self.lib.rth_render_set_temporal_filter(self.handle, C.byref(d) if d is not None else None))
     def set_resolve_every_frame(self, e): self._c(self.lib.rth_render_set_resolve_every_frame(self.handle, int(e)))
     def setup_seconds(self):
         """what the constructor spent: BVH build (or adoption of a cached tree), Scene::Finalize, the integrator's frame, UploadGPUData"""

@@ -168,6 +168,7 @@ void HIPPathTraceIntegrator::SetAOV(AOV aov)
 void HIPPathTraceIntegrator::EnableDenoiser(bool enable)
 {
     if (enable == enable_denoiser_) return;
+    if (enable && temporal_on_) throw HIPException("EnableDenoiser: the temporal filter is on (SetTemporalFilter): two temporal accumulations in a row");
     Check(rt_set_option(frame_, RT_OPT_DENOISER, enable ? 1u : 0u));
     enable_denoiser_ = enable;
     RequestReset();
@@ -205,14 +206,25 @@ void HIPPathTraceIntegrator::ResolveRadiance()
     // resolved_ meanwhile and GetResolvedImage() waits for it
     if (!resolve_every_frame_) return;
     if (filter_on_) Check(rt_frame_filter(frame_, &filter_, resolved_.data()));      // synchronous: the filtered image is in resolved_ on return
+    else if (temporal_on_) Check(rt_frame_filter_temporal(frame_, &temporal_, resolved_.data()));   // likewise
     else Check(rt_frame_present(frame_, resolved_.data()));
 }
 
 void HIPPathTraceIntegrator::SetSpatialFilter(rt_filter_desc const* desc)
 {
     if (desc && tile_count_ > 1) throw HIPException("SetSpatialFilter: a tile of a larger image: the filter needs the whole image");
+    if (desc && temporal_on_) throw HIPException("SetSpatialFilter: the temporal filter is on (SetTemporalFilter): switch it off first");
     if (desc) filter_ = *desc;
     filter_on_ = desc != nullptr;
+}
+
+void HIPPathTraceIntegrator::SetTemporalFilter(rt_temporal_filter_desc const* desc)
+{
+    if (desc && tile_count_ > 1) throw HIPException("SetTemporalFilter: a tile of a larger image: the filter needs the whole image");
+    if (desc && filter_on_) throw HIPException("SetTemporalFilter: the spatial filter is on (SetSpatialFilter): switch it off first");
+    if (desc && enable_denoiser_) throw HIPException("SetTemporalFilter: the denoiser is on (EnableDenoiser): two temporal accumulations in a row");
+    if (desc) temporal_ = *desc;
+    temporal_on_ = desc != nullptr;
 }
 
 void HIPPathTraceIntegrator::IntegrateSamples(std::uint32_t n_samples)
@@ -240,6 +252,7 @@ std::vector<float> HIPPathTraceIntegrator::ReadRadianceSum() const
 std::vector<float> const& HIPPathTraceIntegrator::ResolveNow()
 {
     if (filter_on_) Check(rt_frame_filter(frame_, &filter_, resolved_.data()));
+    else if (temporal_on_) Check(rt_frame_filter_temporal(frame_, &temporal_, resolved_.data()));
     else Check(rt_frame_resolve(frame_, resolved_.data()));
     return resolved_;
 }

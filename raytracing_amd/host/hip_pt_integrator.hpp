@@ -82,6 +82,11 @@ public:
     // start), nullptr = off (the default).  While it is on, ResolveRadiance() and ResolveNow() produce the FILTERED image through rt_frame_filter --
     // synchronously, without the asynchronous present.  A tile of a larger image (TileDesc::count > 1) refuses: the filter needs the whole image.
     void SetSpatialFilter(rt_filter_desc const* desc);
+    // The temporal filter (rt_frame_filter_temporal, SVGF): desc = its settings (copied; RT_TEMPORAL_FILTER_DESC_DEFAULT is a good start), nullptr =
+    // off (the default).  While it is on, ResolveRadiance() and ResolveNow() produce the temporally filtered image, synchronously, and each of them
+    // advances the frame's history by one call.  It excludes SetSpatialFilter and EnableDenoiser(true): turning one on while another is on throws.
+    // A tile of a larger image refuses it.
+    void SetTemporalFilter(rt_temporal_filter_desc const* desc);
     rt_frame* GetFrame() const { return frame_; }
 
 protected:
@@ -112,6 +117,8 @@ private:
     bool resolve_every_frame_ = true;
     bool filter_on_ = false;           // SetSpatialFilter
     rt_filter_desc filter_ = RT_FILTER_DESC_DEFAULT;
+    bool temporal_on_ = false;         // SetTemporalFilter
+    rt_temporal_filter_desc temporal_ = RT_TEMPORAL_FILTER_DESC_DEFAULT;
     std::uint32_t tile_count_ = 1;
     std::string blue_noise_path_ = "assets/blue_noise/heitz2019_256spp_256d.bin";
 };

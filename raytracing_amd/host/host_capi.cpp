@@ -197,6 +197,11 @@ int rth_render_set_spatial_filter(void* r, const rt_filter_desc* desc)
 {
     return guard([&]() { ((rt::Render*)r)->GetIntegrator().SetSpatialFilter(desc); return 0; }, 1);
 }
+// desc NULL = off
+int rth_render_set_temporal_filter(void* r, const rt_temporal_filter_desc* desc)
+{
+    return guard([&]() { ((rt::Render*)r)->GetIntegrator().SetTemporalFilter(desc); return 0; }, 1);
+}
 int rth_render_set_resolve_every_frame(void* r, int e) { ((rt::Render*)r)->GetIntegrator().SetResolveEveryFrame(e != 0); return 0; }
 int rth_render_frame(void* r) { return guard([&]() { ((rt::Render*)r)->RenderFrame(); return 0; }, 1); }
 int rth_render_samples(void* r, uint32_t n) { return guard([&]() { ((rt::Render*)r)->RenderSamples(n); return 0; }, 1); }

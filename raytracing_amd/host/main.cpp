@@ -30,6 +30,10 @@ int main(int argc, char** argv)
         unsigned scene_options = 0;      // rt::Scene::Options (opt-in extensions)
         int filter_iterations = -1;      // --filter n: the spatial filter (rt_frame_filter); -1 = off
         rt_filter_desc filter = RT_FILTER_DESC_DEFAULT;
+        int temporal_iterations = -1;    // --temporal_filter n: the temporal filter (rt_frame_filter_temporal); -1 = off
+        rt_temporal_filter_desc temporal = RT_TEMPORAL_FILTER_DESC_DEFAULT;
+        bool moving = false;             // --camera_step dx,dy,dz: the camera moves by that much every --frames frame
+        float camera_step[3] = {0.0f, 0.0f, 0.0f};
         for (int i = 1; i < argc; ++i)
         {
             auto next = [&]() -> const char* { if (i + 1 >= argc) { std::cerr << "missing value for " << argv[i] << "\n"; exit(2); } return argv[++i]; };
@@ -64,6 +68,35 @@ int main(int argc, char** argv)
                     return 2;
                 }
             }
+            else if (!strcmp(argv[i], "--temporal_filter")) temporal_iterations = atoi(next());   // the temporal filter with n iterations
+            else if (!strcmp(argv[i], "--temporal_alphas"))
+            {
+                const char* v = next();
+                if (sscanf(v, "%f,%f", &temporal.alpha_color, &temporal.alpha_moments) != 2)
+                {
+                    std::cerr << "--temporal_alphas wants c,m (two numbers)\n";
+                    return 2;
+                }
+            }
+            else if (!strcmp(argv[i], "--temporal_sigmas"))
+            {
+                const char* v = next();
+                if (sscanf(v, "%f,%f,%f", &temporal.sigma_luminance, &temporal.sigma_normal, &temporal.sigma_depth) != 3)
+                {
+                    std::cerr << "--temporal_sigmas wants l,n,z (three numbers)\n";
+                    return 2;
+                }
+            }
+            else if (!strcmp(argv[i], "--camera_step"))
+            {
+                const char* v = next();
+                if (sscanf(v, "%f,%f,%f", &camera_step[0], &camera_step[1], &camera_step[2]) != 3)
+                {
+                    std::cerr << "--camera_step wants dx,dy,dz (three numbers)\n";
+                    return 2;
+                }
+                moving = true;
+            }
             else if (!strcmp(argv[i], "--help"))
             {
                 std::cout << "rt_render -w W -h H --scene file.obj [--scale s] [--flip_yz 0|1] [--spp n] [--bounces b]"
@@ -77,7 +110,11 @@ int main(int argc, char** argv)
                              "  extensions (off = the reference's behaviour): --wide_texture_indices 1 loads scenes with more than 255\n"
                              "  textures; --emissive_nee 1 adds the emissive triangles to next-event estimation\n"
                              "  --filter n [--filter_sigmas c,n,z] runs the spatial filter (n a-trous iterations, 0 .. 8; sigmas default to\n"
-                             "  RT_FILTER_DESC_DEFAULT's) and --out then writes the filtered, tone-mapped image; whole images only (not with --gpus > 1)\n";
+                             "  RT_FILTER_DESC_DEFAULT's) and --out then writes the filtered, tone-mapped image; whole images only (not with --gpus > 1)\n"
+                             "  --temporal_filter n [--temporal_alphas c,m] [--temporal_sigmas l,n,z] runs the temporal filter (SVGF; n a-trous\n"
+                             "  iterations, 0 .. 8; the rest default to RT_TEMPORAL_FILTER_DESC_DEFAULT's) on every frame; whole images only\n"
+                             "  --frames n --camera_step dx,dy,dz renders n frames of one sample each, the camera moving by (dx,dy,dz) every frame\n"
+                             "  (the reference's moving-camera loop: each frame is reset); --out then writes the last frame's image\n";
                 return 0;
             }
         }
@@ -89,6 +126,25 @@ int main(int argc, char** argv)
                 std::cerr << "--filter needs the whole image on one GPU: not with --gpus > 1\n";
                 return 2;
             }
+        }
+        if (temporal_iterations >= 0)
+        {
+            temporal.iterations = (std::uint32_t)temporal_iterations;
+            if (gpus > 1)
+            {
+                std::cerr << "--temporal_filter needs the whole image on one GPU: not with --gpus > 1\n";
+                return 2;
+            }
+            if (filter_iterations >= 0)
+            {
+                std::cerr << "--temporal_filter and --filter exclude each other\n";
+                return 2;
+            }
+        }
+        if (moving && frames == 0)
+        {
+            std::cerr << "--camera_step needs --frames n\n";
+            return 2;
         }
         if (plan_only)
         {
@@ -113,6 +169,7 @@ int main(int argc, char** argv)
             for (unsigned d = 0; d < gpus; ++d) devices.push_back(shared_device ? 0 : (int)d);
             rt::TiledRender tiled(width, height, scene, devices);
             tiled.SetSpatialFilter(filter_iterations >= 0 ? &filter : nullptr);   // (refuses any filter)
+            tiled.SetTemporalFilter(temporal_iterations >= 0 ? &temporal : nullptr);
             for (unsigned d = 0; d < gpus; ++d) std::cout << "tile " << d << " on device " << devices[d] << ": " << tiled.GetContext(d).DeviceName() << std::endl;
             std::cout << "gather: " << (tiled.GetRcclRanks() ? "RCCL ncclGather, communicator of " + std::to_string(tiled.GetRcclRanks()) + " ranks"
                                                               : std::string("device copies on one GPU (local group)")) << std::endl;
@@ -151,6 +208,31 @@ int main(int argc, char** argv)
         render.GetIntegrator().SetMaxBounces(bounces);
         render.GetIntegrator().EnableWhiteFurnace(furnace);
         render.GetIntegrator().SetSpatialFilter(filter_iterations >= 0 ? &filter : nullptr);
+        render.GetIntegrator().SetTemporalFilter(temporal_iterations >= 0 ? &temporal : nullptr);
+        if (moving)
+        {
+            // the reference's moving-camera loop (Render::RenderFrame: a changed camera resets the frame): frame i is one sample at the start camera
+            // moved by i * camera_step, resolved (and filtered) at its end
+            render.UploadGPUData();
+            render.GetIntegrator().SetResolveEveryFrame(true);
+            render.GetIntegrator().SetSamplesAhead(samples_ahead);
+            auto tf = std::chrono::steady_clock::now();
+            for (unsigned i = 0; i < frames; ++i)
+            {
+                rt::Camera c = cam;
+                c.position.x = cam.position.x + (float)i * camera_step[0];
+                c.position.y = cam.position.y + (float)i * camera_step[1];
+                c.position.z = cam.position.z + (float)i * camera_step[2];
+                render.SetCamera(c);
+                render.RenderFrame();
+            }
+            std::vector<float> const& img = render.GetIntegrator().GetResolvedImage();
+            double df = std::chrono::duration<double>(std::chrono::steady_clock::now() - tf).count();
+            std::cout << frames << " moving-camera frames (one sample each" << (temporal_iterations >= 0 ? ", temporally filtered" : "") << ") in " << df
+                      << " s: " << df * 1e3 / frames << " ms per frame" << std::endl;
+            if (!out.empty()) WritePFM(out.c_str(), img, width, height);     // the last frame's resolved (filtered), tone-mapped image
+            return 0;
+        }
         if (frames != 0)
         {
             // timing run: wait for the fold adaptation instead of adopting it whenever its worker is done (RT_CTX_OPT_ADAPTIVE_FOLD | 2, as bench.py does)
@@ -186,7 +268,7 @@ int main(int argc, char** argv)
         rt_stats st = render.GetIntegrator().GetStats();
         double rays = (double)st.closest_rays + (double)st.shadow_rays;
         std::cout << spp << " spp in " << dt << " s, " << rays / dt / 1e6 << " Mrays/s" << std::endl;
-        if (!out.empty() && filter_iterations >= 0)
+        if (!out.empty() && (filter_iterations >= 0 || temporal_iterations >= 0))
             WritePFM(out.c_str(), render.GetIntegrator().ResolveNow(), width, height);     // the filtered, tone-mapped image
         else if (!out.empty())
         {

@@ -163,6 +163,11 @@ void TiledRender::SetSpatialFilter(rt_filter_desc const* desc)
     if (desc) throw HIPException("TiledRender: the spatial filter needs the whole image (its stencil crosses the tiles' rows); gather and filter on one GPU instead");
 }
 
+void TiledRender::SetTemporalFilter(rt_temporal_filter_desc const* desc)
+{
+    if (desc) throw HIPException("TiledRender: the temporal filter needs the whole image (its reprojection and stencil cross the tiles' rows)");
+}
+
 void TiledRender::RenderSamples(std::uint32_t n)
 {
     std::vector<std::thread> workers;

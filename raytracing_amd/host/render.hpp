@@ -67,6 +67,8 @@ public:
     void EnableWhiteFurnace(bool enable);
     // The spatial filter needs the whole image (its stencil crosses the tiles' rows): any desc throws; nullptr (off) is accepted.
     void SetSpatialFilter(rt_filter_desc const* desc);
+    // Likewise the temporal filter (its history would have to cross the tiles' rows): any desc throws; nullptr (off) is accepted.
+    void SetTemporalFilter(rt_temporal_filter_desc const* desc);
     void RenderSamples(std::uint32_t n);                  // every tile, concurrently; returns when all are enqueued and finished
     std::vector<float> GatherRadiance(int root = 0);      // height x width x RGBA running sums, image order
     rt_stats GetStats() const;                            // ray counters summed over the tiles
