@@ -1,5 +1,5 @@
 // material_kernels.h -- the material record and its texture lookups (material.h:251-369, utils.h:123-190): what k_shade and the spatial filter's
-// guide pass (spatial_filter.hip) both need.  Device functions only: including it compiles no kernel.
+// guide pass (filters.hip) both need.  Device functions only: including it compiles no kernel.
 #pragma once
 #include "kernels_common.h"
 

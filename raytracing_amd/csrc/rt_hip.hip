@@ -23,8 +23,7 @@
 #include <chrono>
 #include "wide_bvh.h"        // the host-side fold, the pair layout, the adaptation's host walks (wide_bvh.cpp)
 #include "device_fold.h"     // ... and the fold + crossing counts on the device (device_fold.hip)
-#include "spatial_filter_host.h"   // the spatial filter's guide pass and a-trous passes (spatial_filter.hip)
-#include "temporal_filter_host.h"  // the temporal filter's accumulation, variance and variance-guided passes (temporal_filter.hip)
+#include "filters_host.h"         // the filters' guide pass, a-trous passes and temporal stages (filters.hip)
 using namespace rtw;
 
 namespace
@@ -263,6 +262,35 @@ static void ahead_destroy(rt_frame* f);
 static bool ahead_wanted(const rt_frame* f);
 static int ahead_holds(const rt_frame* f, uint32_t sample);
 
+// A filter state's device buffers: each one's address and size.  A state lists them once (buffers()), for the allocation and for the free.
+struct DevBuf { void** p; size_t bytes; };
+static void free_buffers(const std::vector<DevBuf>& bufs)
+{
+    for (const DevBuf& b : bufs) if (*b.p) { (void)hipFree(*b.p); *b.p = nullptr; }
+}
+// a new state S with every buffer of s->buffers(sizes...) allocated, or nullptr with everything freed again if one allocation fails
+template <class S, class... Sizes> static S* alloc_state(Sizes... sizes)
+{
+    S* s = new S();
+    const std::vector<DevBuf> bufs = s->buffers(sizes...);
+    for (const DevBuf& b : bufs)
+        if (hipMalloc(b.p, b.bytes) != hipSuccess)
+        {
+            (void)hipGetLastError();
+            free_buffers(bufs);
+            delete s;
+            return nullptr;
+        }
+    return s;
+}
+template <class S> static void free_state(S*& s)
+{
+    if (!s) return;
+    free_buffers(s->buffers());
+    delete s;
+    s = nullptr;
+}
+
 // The spatial filter's state on a frame (rt_frame_filter, rt_frame_read_guides): made on first use, freed by rt_frame_destroy.  Its own rays, hits,
 // counter and spill area: batches traced ahead (RT_OPT_SAMPLES_AHEAD) may be using the frame's per-path buffers on other streams.  After the guide
 // pass o4 / d4 are free again and serve as the a-trous passes' two ping-pong images.  80 bytes per pixel + the spill area.
@@ -276,15 +304,13 @@ struct SfGuides
     uint64_t scene = 0;
     bool valid = false;
     uint32_t passes = 0;                               // guide passes so far
+    std::vector<DevBuf> buffers(size_t n = 0, size_t spill_bytes = 0)
+    {
+        const size_t b = n * sizeof(float4);
+        return {{(void**)&o4, b}, {(void**)&d4, b}, {(void**)&hits, b}, {(void**)&alb, b}, {(void**)&nz, b}, {(void**)&count, sizeof(uint32_t)},
+                {(void**)&spill, spill_bytes}};
+    }
 };
-static void free_filter_state(rt_frame* f)
-{
-    if (!f->sf) return;
-    void* ptrs[] = {f->sf->o4, f->sf->d4, f->sf->hits, f->sf->alb, f->sf->nz, f->sf->count, f->sf->spill};
-    for (void* p : ptrs) if (p) (void)hipFree(p);
-    delete f->sf;
-    f->sf = nullptr;
-}
 
 // The temporal filter's history on a frame (rt_frame_filter_temporal): made on first use, freed by rt_frame_destroy.  64 bytes per pixel: the colour
 // history, two moments images (mu1, mu2, L) -- the accumulation reads one and writes the other, which is then the history -- and the previous call's
@@ -298,15 +324,12 @@ struct TfState
     rt_camera prev_cam;                                // the previous call's camera and scene (rt_scene_upload count)
     uint64_t prev_scene = 0;
     bool has_prev = false;                             // false: no call yet, or the history was dropped
+    std::vector<DevBuf> buffers(size_t n = 0)
+    {
+        const size_t b = n * sizeof(float4);
+        return {{(void**)&hist, b}, {(void**)&mom[0], b}, {(void**)&mom[1], b}, {(void**)&prev_nz, b}};
+    }
 };
-static void free_temporal_state(rt_frame* f)
-{
-    if (!f->tf) return;
-    void* ptrs[] = {f->tf->hist, f->tf->mom[0], f->tf->mom[1], f->tf->prev_nz};
-    for (void* p : ptrs) if (p) (void)hipFree(p);
-    delete f->tf;
-    f->tf = nullptr;
-}
 
 namespace
 {
@@ -1361,8 +1384,8 @@ int rt_frame_destroy(rt_frame* f)
     if (f->resolved_b) (void)hipFree(f->resolved_b);
     for (auto& s : f->spans) { (void)hipEventDestroy(s.a); (void)hipEventDestroy(s.b); }
     for (auto e : f->event_pool) (void)hipEventDestroy(e);
-    free_filter_state(f);
-    free_temporal_state(f);
+    free_state(f->sf);
+    free_state(f->tf);
     delete f;
     return RT_OK;
 }
@@ -2444,15 +2467,29 @@ int rt_frame_read_radiance(rt_frame* f, float* host_rgba)
 }
 
 
-// ---- spatial filter (spatial_filter.h states it; the kernels live in spatial_filter.hip)
+// ---- the spatial and temporal filters (spatial_filter.h and temporal_filter.h state them; the kernels live in filters.hip)
+// the checks both filters' descriptors share: iterations, flags, (the temporal filter's alphas,) three sigmas > 0 and finite
+static int check_desc(rt_ctx* ctx, const char* who, uint32_t iterations, uint32_t flags, const float (&sigmas)[3], const char* sigma_names,
+    bool alphas_ok = true)
+{
+    if (iterations > RT_FILTER_MAX_ITERATIONS) return fail(ctx, std::string(who) + ": iterations must be 0 .. 8");
+    if (flags & ~RT_FILTER_DEMODULATE) return fail(ctx, std::string(who) + ": unknown flags (RT_FILTER_DEMODULATE is the only one)");
+    if (!alphas_ok) return fail(ctx, std::string(who) + ": alpha_color and alpha_moments must be in 0 .. 1");
+    for (float v : sigmas)
+        if (!(v > 0.0f) || !std::isfinite(v)) return fail(ctx, std::string(who) + ": " + sigma_names + " must be > 0 and finite");
+    return RT_OK;
+}
+
 static int check_filter_desc(rt_ctx* ctx, const char* who, const rt_filter_desc* d)
 {
-    if (d->iterations > RT_FILTER_MAX_ITERATIONS) return fail(ctx, std::string(who) + ": iterations must be 0 .. 8");
-    if (d->flags & ~RT_FILTER_DEMODULATE) return fail(ctx, std::string(who) + ": unknown flags (RT_FILTER_DEMODULATE is the only one)");
-    const float sig[3] = {d->sigma_color, d->sigma_normal, d->sigma_depth};
-    for (float v : sig)
-        if (!(v > 0.0f) || !std::isfinite(v)) return fail(ctx, std::string(who) + ": sigma_color, sigma_normal and sigma_depth must be > 0 and finite");
-    return RT_OK;
+    return check_desc(ctx, who, d->iterations, d->flags, {d->sigma_color, d->sigma_normal, d->sigma_depth}, "sigma_color, sigma_normal and sigma_depth");
+}
+
+static int check_temporal_desc(rt_ctx* ctx, const char* who, const rt_temporal_filter_desc* d)
+{
+    const bool alphas_ok = d->alpha_color >= 0.0f && d->alpha_color <= 1.0f && d->alpha_moments >= 0.0f && d->alpha_moments <= 1.0f;
+    return check_desc(ctx, who, d->iterations, d->flags, {d->sigma_luminance, d->sigma_normal, d->sigma_depth},
+                      "sigma_luminance, sigma_normal and sigma_depth", alphas_ok);
 }
 
 static int check_filter_frame(rt_frame* f, const char* who)
@@ -2470,24 +2507,14 @@ static int ensure_guides(rt_frame* f, const char* who)
     const size_t n = f->n_local;
     if (!f->sf)
     {
-        SfGuides* g = new SfGuides();
         const size_t spill_bytes = (size_t)f->trace_blocks * 64u * (RT_TRACE_STACK_MAX - RT_TRACE_STACK_LDS) * sizeof(uint2);
-        bool ok = hipMalloc((void**)&g->o4, n * sizeof(float4)) == hipSuccess && hipMalloc((void**)&g->d4, n * sizeof(float4)) == hipSuccess &&
-                  hipMalloc((void**)&g->hits, n * sizeof(float4)) == hipSuccess && hipMalloc((void**)&g->alb, n * sizeof(float4)) == hipSuccess &&
-                  hipMalloc((void**)&g->nz, n * sizeof(float4)) == hipSuccess && hipMalloc((void**)&g->count, sizeof(uint32_t)) == hipSuccess &&
-                  hipMalloc((void**)&g->spill, spill_bytes) == hipSuccess;
-        f->sf = g;
-        if (!ok)
-        {
-            (void)hipGetLastError();
-            free_filter_state(f);
-            return fail(ctx, std::string(who) + ": out of device memory for the guide pass (80 bytes per pixel)");
-        }
+        f->sf = alloc_state<SfGuides>(n, spill_bytes);
+        if (!f->sf) return fail(ctx, std::string(who) + ": out of device memory for the guide pass (80 bytes per pixel)");
     }
     SfGuides* g = f->sf;
     if (g->valid && g->scene == ctx->scene_uploads && memcmp(&g->camera, &f->camera, sizeof(rt_camera)) == 0) return RT_OK;
     g->valid = false;
-    HIPCHK(ctx, sfilt::guide_rays(ctx->stream, f->tile.width, f->tile.height, f->camera, rt_tanf(0.5f * f->camera.fov), g->o4, g->d4));
+    HIPCHK(ctx, filt::guide_rays(ctx->stream, f->tile.width, f->tile.height, f->camera, rt_tanf(0.5f * f->camera.fov), g->o4, g->d4));
     HIPCHK(ctx, hipMemsetD32Async((hipDeviceptr_t)g->count, (int)n, 1, ctx->stream));
     {
         // the closest-hit trace through launch_trace's per-ray kernel k_trace_v1<false> (the reference's BVH2 walk), pointed at the filter's own hits,
@@ -2504,7 +2531,7 @@ static int ensure_guides(rt_frame* f, const char* who)
         f->p = keep_p; f->tl_stream = keep_stream; f->tl_spill = keep_spill; f->trace_variant = keep_variant; f->trace_waves_per_cu = keep_waves;
     }
     HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, sfilt::guide_values(ctx->stream, ctx->scene.d, g->o4, g->hits, (uint32_t)n, g->alb, g->nz));
+    HIPCHK(ctx, filt::guide_values(ctx->stream, ctx->scene.d, g->o4, g->hits, (uint32_t)n, g->alb, g->nz));
     g->camera = f->camera;
     g->scene = ctx->scene_uploads;
     g->valid = true;
@@ -2512,24 +2539,77 @@ static int ensure_guides(rt_frame* f, const char* who)
     return RT_OK;
 }
 
-int rt_frame_filter(rt_frame* f, const rt_filter_desc* desc, float* host_rgba)
+// the refusals both frame filters share after their descriptor's check: a tile frame, RT_OPT_AOV
+static int check_filter_call(rt_frame* f, const char* who)
 {
-    if (!f || !desc || !host_rgba) return fail(nullptr, "rt_frame_filter: NULL argument");
+    if (check_filter_frame(f, who) != RT_OK) return RT_ERROR;
+    if (f->aov != 0) return fail(f->ctx, std::string(who) + ": RT_OPT_AOV != 0: the filter is for the shaded colour only");
+    return RT_OK;
+}
+
+// what both frame filters need before their passes: the guides, the frame's own work done, f->resolved free to be the output image (as rt_frame_resolve)
+static int filter_inputs_ready(rt_frame* f, const char* who)
+{
+    if (ensure_guides(f, who) != RT_OK || rt_frame_present_wait(f) != RT_OK || flush_stage(f) != RT_OK) return RT_ERROR;
+    return RT_OK;
+}
+
+// the frame filters' read-back: the output image f->resolved to the caller
+static int read_filtered(rt_frame* f, float* host_rgba)
+{
     rt_ctx* ctx = f->ctx;
-    (void)hipSetDevice(ctx->device);
-    if (check_filter_desc(ctx, "rt_frame_filter", desc) != RT_OK || check_filter_frame(f, "rt_frame_filter") != RT_OK) return RT_ERROR;
-    if (f->aov != 0) return fail(ctx, "rt_frame_filter: RT_OPT_AOV != 0: the filter is for the shaded colour only");
-    if (desc->iterations == 0) return rt_frame_resolve(f, host_rgba);      // exactly rt_frame_resolve's image
-    if (f->n_local == 0) return RT_OK;
-    if (ensure_guides(f, "rt_frame_filter") != RT_OK) return RT_ERROR;
-    if (rt_frame_present_wait(f) != RT_OK) return RT_ERROR;                // as rt_frame_resolve: f->resolved is the output image
-    if (flush_stage(f) != RT_OK) return RT_ERROR;
-    SfGuides* g = f->sf;
-    HIPCHK(ctx, sfilt::passes(ctx->stream, f->tile.width, f->tile.height, f->radiance, g->alb, g->nz, desc->iterations, desc->flags, desc->sigma_color,
-        desc->sigma_normal, desc->sigma_depth, f->denoiser == 0u, (float)f->sample_count, 1, g->o4, g->d4, f->resolved));
     HIPCHK(ctx, hipMemcpyAsync(host_rgba, f->resolved, (size_t)f->n_local * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return RT_OK;
+}
+
+// the debug entry points' guide: normal (xyz) + depth per pixel
+static std::vector<float> pack_nz(const float* normal_rgba, const float* depth, size_t n)
+{
+    std::vector<float> nz(4 * n);
+    for (size_t i = 0; i < n; ++i)
+    {
+        nz[4 * i] = normal_rgba[4 * i]; nz[4 * i + 1] = normal_rgba[4 * i + 1]; nz[4 * i + 2] = normal_rgba[4 * i + 2]; nz[4 * i + 3] = depth[i];
+    }
+    return nz;
+}
+
+// the debug entry points on ctx's device: n_images images of n pixels, the first in.size() uploaded from `in`, run(images), the last out.size()
+// downloaded to `out`; every image is freed on every path and a failure is reported as "who: <HIP error>" (a template: C++ linkage inside extern "C")
+extern "C++" template <class F> static int debug_on_device(rt_ctx* ctx, const char* who, size_t n, size_t n_images, std::initializer_list<const void*> in,
+    std::initializer_list<void*> out, F&& run)
+{
+    (void)hipSetDevice(ctx->device);
+    std::vector<float4*> buf(n_images, nullptr);
+    const size_t bytes = n * sizeof(float4);
+    bool ok = true;
+    for (float4*& b : buf) ok = ok && hipMalloc((void**)&b, bytes) == hipSuccess;
+    size_t k = 0;
+    for (const void* p : in) ok = ok && hipMemcpyAsync(buf[k++], p, bytes, hipMemcpyHostToDevice, ctx->stream) == hipSuccess;
+    hipError_t e = ok ? run(buf.data()) : hipErrorOutOfMemory;
+    k = n_images - out.size();
+    for (void* p : out) if (e == hipSuccess) e = hipMemcpyAsync(p, buf[k++], bytes, hipMemcpyDeviceToHost, ctx->stream);
+    hipError_t es = hipStreamSynchronize(ctx->stream);
+    for (float4* b : buf) if (b) (void)hipFree(b);
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) { (void)hipGetLastError(); return fail(ctx, std::string(who) + ": " + hipGetErrorString(e)); }
+    return RT_OK;
+}
+
+int rt_frame_filter(rt_frame* f, const rt_filter_desc* desc, float* host_rgba)
+{
+    static const char* who = "rt_frame_filter";
+    if (!f || !desc || !host_rgba) return fail(nullptr, "rt_frame_filter: NULL argument");
+    rt_ctx* ctx = f->ctx;
+    (void)hipSetDevice(ctx->device);
+    if (check_filter_desc(ctx, who, desc) != RT_OK || check_filter_call(f, who) != RT_OK) return RT_ERROR;
+    if (desc->iterations == 0) return rt_frame_resolve(f, host_rgba);      // exactly rt_frame_resolve's image
+    if (f->n_local == 0) return RT_OK;
+    if (filter_inputs_ready(f, who) != RT_OK) return RT_ERROR;
+    SfGuides* g = f->sf;
+    const filt::Spatial s = {f->tile.width, f->tile.height, *desc, f->denoiser == 0u, (float)f->sample_count, 1};
+    HIPCHK(ctx, filt::spatial(ctx->stream, s, f->radiance, g->alb, g->nz, g->o4, g->d4, f->resolved));
+    return read_filtered(f, host_rgba);
 }
 
 int rt_frame_read_guides(rt_frame* f, float* albedo_rgba, float* normal_rgba, float* depth, uint32_t* passes)
@@ -2557,52 +2637,22 @@ int rt_frame_read_guides(rt_frame* f, float* albedo_rgba, float* normal_rgba, fl
 int rt_debug_filter(rt_ctx* ctx, uint32_t width, uint32_t height, const float* hdr_rgba, const float* albedo_rgba, const float* normal_rgba,
     const float* depth, const rt_filter_desc* desc, float* out_hdr_rgba)
 {
+    static const char* who = "rt_debug_filter";
     if (!hdr_rgba || !albedo_rgba || !normal_rgba || !depth || !desc || !out_hdr_rgba) return fail(ctx, "rt_debug_filter: NULL argument");
     if (width == 0 || height == 0) return fail(ctx, "rt_debug_filter: empty image");
-    if (check_filter_desc(ctx, "rt_debug_filter", desc) != RT_OK) return RT_ERROR;
+    if (check_filter_desc(ctx, who, desc) != RT_OK) return RT_ERROR;
     const size_t n = (size_t)width * height;
     if (desc->iterations == 0) { memcpy(out_hdr_rgba, hdr_rgba, n * sizeof(float4)); return RT_OK; }
-    std::vector<float> nz(4 * n);
-    for (size_t i = 0; i < n; ++i)
-    {
-        nz[4 * i] = normal_rgba[4 * i]; nz[4 * i + 1] = normal_rgba[4 * i + 1]; nz[4 * i + 2] = normal_rgba[4 * i + 2]; nz[4 * i + 3] = depth[i];
-    }
+    const std::vector<float> nz = pack_nz(normal_rgba, depth, n);
+    const filt::Spatial s = {width, height, *desc, 0, 1.0f, 0};
     if (!ctx)
     {
-        sfilt::host_passes(width, height, hdr_rgba, albedo_rgba, nz.data(), desc->iterations, desc->flags, desc->sigma_color, desc->sigma_normal,
-            desc->sigma_depth, out_hdr_rgba);
+        filt::spatial_host(s, hdr_rgba, albedo_rgba, nz.data(), out_hdr_rgba);
         return RT_OK;
     }
-    (void)hipSetDevice(ctx->device);
-    float4* buf[6] = {};
-    const size_t bytes = n * sizeof(float4);
-    bool ok = true;
-    for (float4*& b : buf) ok = ok && hipMalloc((void**)&b, bytes) == hipSuccess;
-    ok = ok && hipMemcpyAsync(buf[0], hdr_rgba, bytes, hipMemcpyHostToDevice, ctx->stream) == hipSuccess &&
-         hipMemcpyAsync(buf[1], albedo_rgba, bytes, hipMemcpyHostToDevice, ctx->stream) == hipSuccess &&
-         hipMemcpyAsync(buf[2], nz.data(), bytes, hipMemcpyHostToDevice, ctx->stream) == hipSuccess;
-    hipError_t e = ok ? sfilt::passes(ctx->stream, width, height, buf[0], buf[1], buf[2], desc->iterations, desc->flags, desc->sigma_color, desc->sigma_normal,
-        desc->sigma_depth, 0, 1.0f, 0, buf[3], buf[4], buf[5]) : hipErrorOutOfMemory;
-    if (e == hipSuccess) e = hipMemcpyAsync(out_hdr_rgba, buf[5], bytes, hipMemcpyDeviceToHost, ctx->stream);
-    hipError_t es = hipStreamSynchronize(ctx->stream);
-    for (float4* b : buf) if (b) (void)hipFree(b);
-    if (e == hipSuccess) e = es;
-    if (e != hipSuccess) { (void)hipGetLastError(); return fail(ctx, std::string("rt_debug_filter: ") + hipGetErrorString(e)); }
-    return RT_OK;
-}
-
-
-// ---- temporal filter (temporal_filter.h states it; the kernels live in temporal_filter.hip)
-static int check_temporal_desc(rt_ctx* ctx, const char* who, const rt_temporal_filter_desc* d)
-{
-    if (d->iterations > RT_FILTER_MAX_ITERATIONS) return fail(ctx, std::string(who) + ": iterations must be 0 .. 8");
-    if (d->flags & ~RT_FILTER_DEMODULATE) return fail(ctx, std::string(who) + ": unknown flags (RT_FILTER_DEMODULATE is the only one)");
-    if (!(d->alpha_color >= 0.0f && d->alpha_color <= 1.0f) || !(d->alpha_moments >= 0.0f && d->alpha_moments <= 1.0f))
-        return fail(ctx, std::string(who) + ": alpha_color and alpha_moments must be in 0 .. 1");
-    const float sig[3] = {d->sigma_luminance, d->sigma_normal, d->sigma_depth};
-    for (float v : sig)
-        if (!(v > 0.0f) || !std::isfinite(v)) return fail(ctx, std::string(who) + ": sigma_luminance, sigma_normal and sigma_depth must be > 0 and finite");
-    return RT_OK;
+    // images: hdr, albedo, nz, ping, pong, out
+    return debug_on_device(ctx, who, n, 6, {hdr_rgba, albedo_rgba, nz.data()}, {out_hdr_rgba},
+                           [&](float4** b) { return filt::spatial(ctx->stream, s, b[0], b[1], b[2], b[3], b[4], b[5]); });
 }
 
 int rt_frame_filter_temporal(rt_frame* f, const rt_temporal_filter_desc* desc, float* host_rgba)
@@ -2611,50 +2661,42 @@ int rt_frame_filter_temporal(rt_frame* f, const rt_temporal_filter_desc* desc, f
     if (!f || !desc || !host_rgba) return fail(nullptr, "rt_frame_filter_temporal: NULL argument");
     rt_ctx* ctx = f->ctx;
     (void)hipSetDevice(ctx->device);
-    if (check_temporal_desc(ctx, who, desc) != RT_OK || check_filter_frame(f, who) != RT_OK) return RT_ERROR;
-    if (f->aov != 0) return fail(ctx, "rt_frame_filter_temporal: RT_OPT_AOV != 0: the filter is for the shaded colour only");
+    if (check_temporal_desc(ctx, who, desc) != RT_OK || check_filter_call(f, who) != RT_OK) return RT_ERROR;
     if (f->denoiser != 0)
         return fail(ctx, "rt_frame_filter_temporal: RT_OPT_DENOISER != 0: the frame is already accumulated over time by the reference's denoiser");
     if (f->n_local == 0) return RT_OK;
     const size_t n = f->n_local;
     if (!f->tf)
     {
-        TfState* t = new TfState();
-        bool ok = hipMalloc((void**)&t->hist, n * sizeof(float4)) == hipSuccess && hipMalloc((void**)&t->mom[0], n * sizeof(float4)) == hipSuccess &&
-                  hipMalloc((void**)&t->mom[1], n * sizeof(float4)) == hipSuccess && hipMalloc((void**)&t->prev_nz, n * sizeof(float4)) == hipSuccess;
-        f->tf = t;
-        ok = ok && hipMemsetAsync(t->hist, 0, n * sizeof(float4), ctx->stream) == hipSuccess &&
-             hipMemsetAsync(t->mom[0], 0, n * sizeof(float4), ctx->stream) == hipSuccess;
-        if (!ok)
+        TfState* t = alloc_state<TfState>(n);
+        if (t && (hipMemsetAsync(t->hist, 0, n * sizeof(float4), ctx->stream) != hipSuccess ||
+                  hipMemsetAsync(t->mom[0], 0, n * sizeof(float4), ctx->stream) != hipSuccess))
         {
             (void)hipGetLastError();
-            free_temporal_state(f);
-            return fail(ctx, "rt_frame_filter_temporal: out of device memory for the history (64 bytes per pixel)");
+            free_state(t);
         }
+        if (!t) return fail(ctx, "rt_frame_filter_temporal: out of device memory for the history (64 bytes per pixel)");
+        f->tf = t;
     }
-    if (ensure_guides(f, who) != RT_OK) return RT_ERROR;
-    if (rt_frame_present_wait(f) != RT_OK) return RT_ERROR;                // as rt_frame_resolve: f->resolved is the output image
-    if (flush_stage(f) != RT_OK) return RT_ERROR;
+    if (filter_inputs_ready(f, who) != RT_OK) return RT_ERROR;
     TfState* t = f->tf;
     SfGuides* g = f->sf;
-    tfilt::Call c;
+    filt::Temporal c;
     c.width = f->tile.width; c.height = f->tile.height;
     c.cam = f->camera;
     c.prev = t->has_prev ? t->prev_cam : f->camera;
-    c.mode = !t->has_prev || t->prev_scene != ctx->scene_uploads ? tfilt::NO_HISTORY
-           : memcmp(&t->prev_cam, &f->camera, sizeof(rt_camera)) == 0 ? tfilt::IDENTITY : tfilt::REPROJECT;
+    c.mode = !t->has_prev || t->prev_scene != ctx->scene_uploads ? filt::NO_HISTORY
+           : memcmp(&t->prev_cam, &f->camera, sizeof(rt_camera)) == 0 ? filt::IDENTITY : filt::REPROJECT;
     c.desc = *desc;
     c.divide = 1; c.spp = (float)f->sample_count; c.tonemap = 1;
-    HIPCHK(ctx, tfilt::run(ctx->stream, c, f->radiance, g->alb, g->nz, t->prev_nz, t->hist, t->mom[t->cur], t->hist, t->mom[t->cur ^ 1u], g->o4, g->d4,
-        f->resolved));
+    HIPCHK(ctx, filt::temporal(ctx->stream, c, f->radiance, g->alb, g->nz, t->prev_nz, t->hist, t->mom[t->cur], t->hist, t->mom[t->cur ^ 1u], g->o4,
+        g->d4, f->resolved));
     t->cur ^= 1u;
     HIPCHK(ctx, hipMemcpyAsync(t->prev_nz, g->nz, n * sizeof(float4), hipMemcpyDeviceToDevice, ctx->stream));
     t->prev_cam = f->camera;
     t->prev_scene = ctx->scene_uploads;
     t->has_prev = true;
-    HIPCHK(ctx, hipMemcpyAsync(host_rgba, f->resolved, n * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return RT_OK;
+    return read_filtered(f, host_rgba);
 }
 
 int rt_frame_filter_history_reset(rt_frame* f)
@@ -2694,47 +2736,30 @@ int rt_debug_filter_temporal(rt_ctx* ctx, uint32_t width, uint32_t height, const
     const float* hist_color, const float* hist_moments, const rt_temporal_filter_desc* desc, float* out_hdr_rgba, float* hist_color_out,
     float* hist_moments_out)
 {
+    static const char* who = "rt_debug_filter_temporal";
     if (!cam || !hdr_rgba || !albedo_rgba || !normal_rgba || !depth || !prev_normal_rgba || !prev_depth || !hist_color || !hist_moments || !desc ||
         !out_hdr_rgba || !hist_color_out || !hist_moments_out)
         return fail(ctx, "rt_debug_filter_temporal: NULL argument");
     if (width == 0 || height == 0) return fail(ctx, "rt_debug_filter_temporal: empty image");
-    if (check_temporal_desc(ctx, "rt_debug_filter_temporal", desc) != RT_OK) return RT_ERROR;
+    if (check_temporal_desc(ctx, who, desc) != RT_OK) return RT_ERROR;
     const size_t n = (size_t)width * height;
-    std::vector<float> nz(4 * n), pnz(4 * n);
-    for (size_t i = 0; i < n; ++i)
-    {
-        for (int k = 0; k < 3; ++k) { nz[4 * i + k] = normal_rgba[4 * i + k]; pnz[4 * i + k] = prev_normal_rgba[4 * i + k]; }
-        nz[4 * i + 3] = depth[i]; pnz[4 * i + 3] = prev_depth[i];
-    }
-    tfilt::Call c;
+    const std::vector<float> nz = pack_nz(normal_rgba, depth, n), pnz = pack_nz(prev_normal_rgba, prev_depth, n);
+    filt::Temporal c;
     c.width = width; c.height = height;
     c.cam = *cam;
     c.prev = prev_cam ? *prev_cam : *cam;
-    c.mode = !prev_cam || memcmp(prev_cam, cam, sizeof(rt_camera)) == 0 ? tfilt::IDENTITY : tfilt::REPROJECT;
+    c.mode = !prev_cam || memcmp(prev_cam, cam, sizeof(rt_camera)) == 0 ? filt::IDENTITY : filt::REPROJECT;
     c.desc = *desc;
     c.divide = 0; c.spp = 1.0f; c.tonemap = 0;
     if (!ctx)
     {
-        tfilt::host_run(c, hdr_rgba, albedo_rgba, nz.data(), pnz.data(), hist_color, hist_moments, hist_color_out, hist_moments_out, out_hdr_rgba);
+        filt::temporal_host(c, hdr_rgba, albedo_rgba, nz.data(), pnz.data(), hist_color, hist_moments, hist_color_out, hist_moments_out, out_hdr_rgba);
         return RT_OK;
     }
-    (void)hipSetDevice(ctx->device);
-    float4* buf[11] = {};         // hdr, albedo, nz, prev nz, hist in, moments in, hist out, moments out, a, b, out
-    const size_t bytes = n * sizeof(float4);
-    bool ok = true;
-    for (float4*& b : buf) ok = ok && hipMalloc((void**)&b, bytes) == hipSuccess;
-    const void* in[6] = {hdr_rgba, albedo_rgba, nz.data(), pnz.data(), hist_color, hist_moments};
-    for (int k = 0; k < 6; ++k) ok = ok && hipMemcpyAsync(buf[k], in[k], bytes, hipMemcpyHostToDevice, ctx->stream) == hipSuccess;
-    hipError_t e = ok ? tfilt::run(ctx->stream, c, buf[0], buf[1], buf[2], buf[3], buf[4], buf[5], buf[6], buf[7], buf[8], buf[9], buf[10])
-                      : hipErrorOutOfMemory;
-    if (e == hipSuccess) e = hipMemcpyAsync(out_hdr_rgba, buf[10], bytes, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(hist_color_out, buf[6], bytes, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(hist_moments_out, buf[7], bytes, hipMemcpyDeviceToHost, ctx->stream);
-    hipError_t es = hipStreamSynchronize(ctx->stream);
-    for (float4* b : buf) if (b) (void)hipFree(b);
-    if (e == hipSuccess) e = es;
-    if (e != hipSuccess) { (void)hipGetLastError(); return fail(ctx, std::string("rt_debug_filter_temporal: ") + hipGetErrorString(e)); }
-    return RT_OK;
+    // images: hdr, albedo, nz, prev nz, hist in, moments in, a, b, out, hist out, moments out
+    return debug_on_device(ctx, who, n, 11, {hdr_rgba, albedo_rgba, nz.data(), pnz.data(), hist_color, hist_moments},
+                           {out_hdr_rgba, hist_color_out, hist_moments_out},
+                           [&](float4** b) { return filt::temporal(ctx->stream, c, b[0], b[1], b[2], b[3], b[4], b[5], b[9], b[10], b[6], b[7], b[8]); });
 }
 void* rt_frame_radiance_device_ptr(rt_frame* f) { return f ? (void*)f->radiance : nullptr; }
 uint32_t rt_frame_sample_count(rt_frame* f) { return f ? f->sample_count : 0; }

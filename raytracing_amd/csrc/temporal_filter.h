@@ -1,11 +1,11 @@
 /* temporal_filter.h -- the spatiotemporal variance-guided filter (SVGF, Schied et al. HPG 2017) for one pixel, shared by the kernels of
- * temporal_filter.hip and their host restatement behind rt_debug_filter_temporal(NULL, ...).  Both are compiled with -ffp-contract=off and
- * no fast-math and evaluate the exponential with rt_detmath.h's rt_expf, so they agree bit for bit.  spatial_filter.h's rules hold unchanged
- * where they apply: h_p, demodulation by albedo >= 1e-3 (sf_load), the pass-through pixels, the B3 taps 2^i apart, the normal and depth terms,
- * the c_p + sum w (c_q - c_p) / sum w form of every weighted mean.
+ * filters.hip and their host restatement behind rt_debug_filter_temporal(NULL, ...).  Both are compiled with -ffp-contract=off and
+ * no fast-math and evaluate the exponential with rt_detmath.h's rt_expf, so they agree bit for bit.  spatial_filter.h's rules, and its functions
+ * that state them, hold unchanged where they apply: h_p, demodulation by albedo >= 1e-3 (sf_load), the pass-through pixels, the B3 taps 2^i apart,
+ * the normal and depth terms, the c_p + sum w (c_q - c_p) / sum w form of every weighted mean.
  *
  * Per call, per pixel p of the whole image (width x height):
- *   1. reproject: X = cam.position + z_p d_p (d_p: k_sf_guide_rays' pixel-centre direction, recomputed here); X is projected through the
+ *   1. reproject: X = cam.position + z_p d_p (d_p: sf_guide_dir, the guide pass's pixel-centre direction); X is projected through the
  *      previous call's camera with ProjectScreen's arithmetic (aov_kernels.h) to the continuous pixel (u W - 0.5, v H - 0.5); X behind that
  *      camera, or a position outside (-1, W) x (-1, H), misses.  Bilinear 2 x 2 taps; a tap counts iff its bilinear weight is > 0, it lies
  *      inside the image, its history length is > 0 (it was valid at the previous call), |z_prev,q - |X - prev.position|| <= TF_DEPTH_TOL
@@ -89,22 +89,6 @@ RTD_FN float tf_lum(sf_f4 c) { return 0.2126f * c.x + 0.7152f * c.y + 0.0722f * 
 RTD_FN float tf_max(float a, float b) { return a < b ? b : a; }
 RTD_FN float tf_dot(float ax, float ay, float az, float bx, float by, float bz) { return ax * bx + ay * by + az * bz; }
 
-/* k_sf_guide_rays' direction for pixel (px, py), operation for operation */
-RTD_FN void tf_guide_dir(const rt_camera& cam, float tan_half_fov, uint32_t width, uint32_t height, uint32_t px, uint32_t py, float d[3])
-{
-    float inv_width = 1.0f / (float)width;
-    float inv_height = 1.0f / (float)height;
-    float x = ((float)px + 0.5f) * inv_width;
-    float y = ((float)py + 0.5f) * inv_height;
-    x = (x * 2.0f - 1.0f) * tan_half_fov * cam.aspect_ratio;
-    y = (y * 2.0f - 1.0f) * tan_half_fov;
-    const float fx = cam.front.x, fy = cam.front.y, fz = cam.front.z, ux = cam.up.x, uy = cam.up.y, uz = cam.up.z;
-    const float rx = fy * uz - fz * uy, ry = fz * ux - fx * uz, rz = fx * uy - fy * ux;     // cross3(front, up)
-    const float dx = rx * x + ux * y + fx, dy = ry * x + uy * y + fy, dz = rz * x + uz * y + fz;
-    const float l = __builtin_sqrtf(dx * dx + dy * dy + dz * dz);
-    d[0] = dx / l; d[1] = dy / l; d[2] = dz / l;
-}
-
 /* ProjectScreen (aov_kernels.h) of X through cam, as a continuous pixel position; 0 when X is not in front of the camera */
 RTD_FN int tf_project(const rt_camera& cam, float tan_half_fov, uint32_t width, uint32_t height, const float X[3], float* sx, float* sy)
 {
@@ -130,10 +114,8 @@ RTD_FN void tf_accumulate_pixel(const TfAccum& A, uint32_t x, uint32_t y)
 {
     const uint32_t i = y * A.width + x;
     const sf_f4 gp = A.nz[i];
-    SfPass L = {};
-    L.col = A.col; L.alb = A.alb; L.flags = SF_FIRST | A.flags; L.spp = A.spp;
     int through = 0;
-    const sf_f4 c = sf_load(L, i, gp.w, &through);
+    const sf_f4 c = sf_load(A.col, A.alb, SF_FIRST | A.flags, A.spp, i, gp.w, &through);
     if (through)
     {
         const sf_f4 zero = {0.0f, 0.0f, 0.0f, 0.0f};
@@ -152,7 +134,7 @@ RTD_FN void tf_accumulate_pixel(const TfAccum& A, uint32_t x, uint32_t y)
     else if (A.mode == TF_REPROJECT)
     {
         float d[3], X[3];
-        tf_guide_dir(A.cam, A.tan_cam, A.width, A.height, x, y, d);
+        sf_guide_dir(A.cam, A.tan_cam, A.width, A.height, x, y, d);
         X[0] = A.cam.position.x + gp.w * d[0]; X[1] = A.cam.position.y + gp.w * d[1]; X[2] = A.cam.position.z + gp.w * d[2];
         const float ex = X[0] - A.prev.position.x, ey = X[1] - A.prev.position.y, ez = X[2] - A.prev.position.z;
         const float dist = __builtin_sqrtf(ex * ex + ey * ey + ez * ez);
@@ -222,30 +204,21 @@ RTD_FN sf_f4 tf_variance_pixel(const TfVar& V, uint32_t x, uint32_t y)
     {
         const sf_f4 gp = V.nz[i];
         float sw = 0.0f, s1 = 0.0f, s2 = 0.0f;
-        for (int k = -TF_VAR_RADIUS; k <= TF_VAR_RADIUS; ++k)
-        {
-            const int qy = (int)y + k;
-            if (qy < 0 || qy >= (int)V.height) continue;
-            for (int j = -TF_VAR_RADIUS; j <= TF_VAR_RADIUS; ++j)
+        sf_stencil(x, y, V.width, V.height, TF_VAR_RADIUS, 1, [&](int j, int k, uint32_t qi) {
+            const sf_f4 mq = V.mom[qi];
+            if (!(mq.z > 0.0f)) return;
+            const sf_f4 gq = V.nz[qi];
+            // sf_depth_term at step 1, written out: through the function, clang splits this kernel's guide loads and it runs ~5 % slower
+            float ez = 0.0f;
+            if (j != 0 || k != 0)
             {
-                const int qx = (int)x + j;
-                if (qx < 0 || qx >= (int)V.width) continue;
-                const uint32_t qi = (uint32_t)qy * V.width + (uint32_t)qx;
-                const sf_f4 mq = V.mom[qi];
-                if (!(mq.z > 0.0f)) continue;
-                const sf_f4 gq = V.nz[qi];
-                const float dn = 1.0f - (gp.x * gq.x + gp.y * gq.y + gp.z * gq.z);
-                float ez = 0.0f;
-                if (j != 0 || k != 0)
-                {
-                    const int mm = (j < 0 ? -j : j) > (k < 0 ? -k : k) ? (j < 0 ? -j : j) : (k < 0 ? -k : k);
-                    ez = __builtin_fabsf(gp.w - gq.w) * V.inv_z / (gp.w * (float)mm);
-                }
-                const float w = rt_expf(-(dn * V.inv_n + ez));
-                sw = sw + w;
-                s1 = s1 + w * (mq.x - m.x); s2 = s2 + w * (mq.y - m.y);
+                const int mm = (j < 0 ? -j : j) > (k < 0 ? -k : k) ? (j < 0 ? -j : j) : (k < 0 ? -k : k);
+                ez = __builtin_fabsf(gp.w - gq.w) * V.inv_z / (gp.w * (float)mm);
             }
-        }
+            const float w = rt_expf(-(sf_normal_term(gp, gq) * V.inv_n + ez));
+            sw = sw + w;
+            s1 = s1 + w * (mq.x - m.x); s2 = s2 + w * (mq.y - m.y);
+        });
         if (sw > 0.0f) { m1 = m.x + s1 / sw; m2 = m.y + s2 / sw; }
     }
     const float var = m2 - m1 * m1;
@@ -267,52 +240,27 @@ RTD_FN sf_f4 tf_pass_pixel(const TfPass& P, uint32_t x, uint32_t y)
     else if (valid)
     {
         float gw = 0.0f, gs = 0.0f;
-        for (int k = -1; k <= 1; ++k)
-        {
-            const int qy = (int)y + k;
-            if (qy < 0 || qy >= (int)P.height) continue;
-            for (int j = -1; j <= 1; ++j)
-            {
-                const int qx = (int)x + j;
-                if (qx < 0 || qx >= (int)P.width) continue;
-                const uint32_t qi = (uint32_t)qy * P.width + (uint32_t)qx;
-                if (!(P.mom[qi].z > 0.0f)) continue;
-                const float kw = g3[j + 1] * g3[k + 1];
-                gw = gw + kw;
-                gs = gs + kw * P.col[qi].w;
-            }
-        }
+        sf_stencil(x, y, P.width, P.height, 1, 1, [&](int j, int k, uint32_t qi) {
+            if (!(P.mom[qi].z > 0.0f)) return;
+            const float kw = g3[j + 1] * g3[k + 1];
+            gw = gw + kw;
+            gs = gs + kw * P.col[qi].w;
+        });
         const float den = P.sigma_l * __builtin_sqrtf(gs / gw) + TF_LUM_EPS;
         const float lp = tf_lum(cp);
         const sf_f4 gp = P.nz[i];
         float sw = 0.0f, sx = 0.0f, sy = 0.0f, sz = 0.0f, sv = 0.0f;
         const int s = (int)P.step;
-        for (int k = -2; k <= 2; ++k)
-        {
-            const int qy = (int)y + s * k;
-            if (qy < 0 || qy >= (int)P.height) continue;
-            for (int j = -2; j <= 2; ++j)
-            {
-                const int qx = (int)x + s * j;
-                if (qx < 0 || qx >= (int)P.width) continue;
-                const uint32_t qi = (uint32_t)qy * P.width + (uint32_t)qx;
-                if (!(P.mom[qi].z > 0.0f)) continue;
-                const sf_f4 cq = P.col[qi];
-                const sf_f4 gq = P.nz[qi];
-                const float dn = 1.0f - (gp.x * gq.x + gp.y * gq.y + gp.z * gq.z);
-                float ez = 0.0f;
-                if (j != 0 || k != 0)
-                {
-                    const int m = (j < 0 ? -j : j) > (k < 0 ? -k : k) ? (j < 0 ? -j : j) : (k < 0 ? -k : k);
-                    ez = __builtin_fabsf(gp.w - gq.w) * P.inv_z / (gp.w * (float)(s * m));
-                }
-                const float e = __builtin_fabsf(lp - tf_lum(cq)) / den + dn * P.inv_n + ez;
-                const float w = b[j + 2] * b[k + 2] * rt_expf(-e);
-                sw = sw + w;
-                sx = sx + w * (cq.x - cp.x); sy = sy + w * (cq.y - cp.y); sz = sz + w * (cq.z - cp.z);
-                sv = sv + (w * w) * cq.w;
-            }
-        }
+        sf_stencil(x, y, P.width, P.height, 2, s, [&](int j, int k, uint32_t qi) {
+            if (!(P.mom[qi].z > 0.0f)) return;
+            const sf_f4 cq = P.col[qi];
+            const sf_f4 gq = P.nz[qi];
+            const float e = __builtin_fabsf(lp - tf_lum(cq)) / den + sf_normal_term(gp, gq) * P.inv_n + sf_depth_term(gp, gq, P.inv_z, s, j, k);
+            const float w = b[j + 2] * b[k + 2] * rt_expf(-e);
+            sw = sw + w;
+            sx = sx + w * (cq.x - cp.x); sy = sy + w * (cq.y - cp.y); sz = sz + w * (cq.z - cp.z);
+            sv = sv + (w * w) * cq.w;
+        });
         if (sw > 0.0f) { r.x = cp.x + sx / sw; r.y = cp.y + sy / sw; r.z = cp.z + sz / sw; r.w = sv / (sw * sw); }
     }
     if (P.hist)
@@ -323,19 +271,9 @@ RTD_FN sf_f4 tf_pass_pixel(const TfPass& P, uint32_t x, uint32_t y)
     }
     if (P.flags & SF_LAST)
     {
-        if (!valid || own || !sf_finite3(r))
-        {
-            r = P.src[i];                                         // h_p exactly
-            if (P.flags & SF_DIVIDE) { r.x = r.x / P.spp; r.y = r.y / P.spp; r.z = r.z / P.spp; }
-        }
-        else if (P.flags & SF_DEMOD)
-        {
-            const sf_f4 a = P.alb[i];
-            if (a.x >= SF_ALBEDO_MIN) r.x = r.x * a.x;
-            if (a.y >= SF_ALBEDO_MIN) r.y = r.y * a.y;
-            if (a.z >= SF_ALBEDO_MIN) r.z = r.z * a.z;
-        }
-        if (P.flags & SF_TONEMAP) { r.x = r.x / (r.x + 1.0f); r.y = r.y / (r.y + 1.0f); r.z = r.z / (r.z + 1.0f); }
+        if (!valid || own || !sf_finite3(r)) r = sf_h(P.src, P.flags, P.spp, i);       // h_p exactly
+        else if (P.flags & SF_DEMOD) r = sf_remodulate(r, P.alb[i]);
+        if (P.flags & SF_TONEMAP) r = sf_reinhard(r);
         r.w = 1.0f;
     }
     return r;
