@@ -118,6 +118,11 @@ enum rt_ctx_option
                                       the child it hands most rays on to right behind it, i.e. in the same 128-byte line (the L2 of gfx950 fetches whole lines:
                                       a 64-byte record that misses pays for its line-mate anyway).  A permutation of the records: no result depends on it.
                                       Takes effect at the next rt_scene_upload. */
+    , RT_CTX_OPT_REFITTABLE = 10   /* 0 (default): a scene's triangles move only by rt_scene_upload again; nothing is kept, rt_scene_refit* is refused.
+                                      1: rt_scene_upload keeps what a refit needs on the device -- who holds each child-pair record and each 4-wide record,
+                                      the exact box of every 4-wide record, arrival counters: 8 bytes per child-pair record + 40 per 4-wide record, about 34 bytes
+                                      per triangle.  Upload's results, trees and report are the same either way.  Takes effect at the
+                                      next rt_scene_upload. */
     , RT_CTX_OPT_ADAPT_WAIT = 6    /* 1 / 0: sets / clears bit 1 of RT_CTX_OPT_ADAPTIVE_FOLD (rt_integrate waits for an adaptation it has
                                       started) for the scene IN PLACE, at once; the context's option, which the next upload reads, stays
                                       (bench.py: the headline waits for its fold, the moving-camera leg runs as the library ships) */
@@ -168,6 +173,24 @@ typedef struct rt_scene_desc
                                       hit_surface.cl:39).  Changes the estimator, not the expected image: DESIGN.md section 7b */
 
 int rt_scene_upload(rt_ctx* ctx, const rt_scene_desc* scene);
+
+/* The scene's triangles MOVED (a door opens, a character deforms): topology, split axes and every fold stay, all bounds are made again on the device from the
+ * new vertices -- a leaf's = min / max over its vertices, an interior node's = min / max of its two children -- in the triangle records, the child-pair records
+ * and every 4-wide tree the scene holds (the reference fold, an adapted or imported fold, the shadow rays' own tree, the pair layout alike), then the frames and
+ * 8-bit planes of the 4-wide records by the builder's own quantisation.  Milliseconds where rt_scene_upload takes a third of a second or more.
+ *   triangles: the reference layout, the SAME count and the same (BVH) order as the upload; positions, normals, texture coordinates and mtl_index may change.
+ *   rt_scene_refit takes a host array, rt_scene_refit_buffer an rt_buffer of num_triangles * sizeof(rt_triangle) bytes of this context (no PCIe copy: the per-frame path).
+ * Afterwards the context behaves, for every entry point and option, exactly as a fresh one would after rt_scene_upload of the moved triangles with the node array
+ * "same topology, same split axes, bounds refitted": radiance, resolved image, counters, AOVs, guides and filter outputs are bit-identical (the trees WALKED may differ
+ * from what a fresh upload would choose, which never changes a result; a refitted tree is a worse tree after a large deformation -- upload again then).
+ * Refused with the scene untouched: RT_CTX_OPT_REFITTABLE off at upload, no scene, another count or size, the tolerance mode (RT_CTX_OPT_CLOSEST_TREE != 0), a
+ * non-finite position or mtl_index >= num_materials (checked by a read-only kernel first), or node arrays whose leaves are not consecutive ranges covering the
+ * triangle array.  Otherwise: quiesces as rt_scene_upload does (samples traced ahead are dropped); a fold adaptation is retired -- one in flight is cancelled --
+ * and the records adapted so far stay in use; guide caches and temporal histories drop as on upload; frames keep their accumulation: rt_reset them.
+ * A record that no longer qualifies for k_trace_w4 after the move (cell above 2^20, coordinates beyond 2^28) does not fail the call: the scene is traced by the
+ * BVH2 kernels, as after an upload of such a tree, until a later refit qualifies again; rt_scene_tree_report's "refit" line says which. */
+int rt_scene_refit(rt_ctx* ctx, const rt_triangle* triangles, uint32_t num_triangles);
+int rt_scene_refit_buffer(rt_ctx* ctx, rt_buffer* triangles);
 
 /* One fold adaptation per process GROUP instead of one per rank (N ranks that tile one image hold the same scene and would each probe, rotate and fold for
  * identical records): the context's current 4-wide records -- the closest-hit rays' and the shadow rays' (n_shadow == 0: they share), as adapted so far -- to
@@ -560,6 +583,14 @@ int rt_frame_debug_timeline(rt_frame* frame, int arm, unsigned long long* out);
 int rt_debug_wide_bvh(const rt_bvh_node* nodes, uint32_t num_nodes, int collapse, void* records, uint32_t* roots, uint32_t capacity,
     uint32_t* num_records, uint32_t* entry_ref);
 
+/* The refit on its own: `nodes` (reference layout: first child at i + 1, second at offset > i + 1) and any fold of it (`records`, a tree over all num_records
+ * from entry_ref; num_records may be 0) refitted to `triangles` -- out_nodes[num_nodes]: offsets, counts and axes untouched, leaf bounds = min / max over the leaf's
+ * vertices, interior bounds = min / max of the children; out_records[num_records]: ref, order and slot placement untouched, frame and planes made again.  Either
+ * output may be NULL.  ctx == NULL: the host restatement; otherwise refit.hip's kernels on ctx's device (the two agree bit for bit, bounds by value).
+ * Returns RT_OK, RT_ERROR, or RT_REFIT_DISQUALIFIED: refitted, but a record no longer qualifies for k_trace_w4 (its bytes are left as they were). */
+#define RT_REFIT_DISQUALIFIED 2
+int rt_debug_refit(rt_ctx* ctx, const rt_bvh_node* nodes, uint32_t num_nodes, const rt_triangle* triangles, uint32_t num_triangles, const void* records, uint32_t num_records,
+                   uint32_t entry_ref, rt_bvh_node* out_nodes, void* out_records);
 /* What the last rt_scene_upload measured when it chose the trees (one line per ray population; "" when it had no choice), then the
  * latest fold adaptation's line (RT_CTX_OPT_ADAPTIVE_FOLD).  The pointer is valid until the next rt_integrate or rt_scene_upload on
  * this context (an adaptation rewrites its line): copy it. */

@@ -108,6 +108,7 @@ EXPORTS = [
     "rt_group_create_unchecked",
     "rt_frame_filter", "rt_frame_read_guides", "rt_debug_filter",
     "rt_frame_filter_temporal", "rt_frame_filter_history_reset", "rt_frame_read_filter_history", "rt_debug_filter_temporal",
+    "rt_scene_refit", "rt_scene_refit_buffer", "rt_debug_refit",
 ]
 
 OPT_MAX_BOUNCES, OPT_WHITE_FURNACE, OPT_SAMPLER, OPT_AOV, OPT_DENOISER, OPT_DROP_LAST, OPT_PROFILE, OPT_TRACE_VARIANT, OPT_TRACE_WAVES, OPT_SAMPLES_IN_FLIGHT, OPT_SELECT_FORM_BOX, OPT_PACKET_BOUNCES, OPT_TRACE_TUNE, OPT_DEBUG_ALLOC_LIMIT, OPT_PATH_STATE_LIMIT_MB, OPT_PIPELINES, OPT_SHADE_PARTITION, OPT_OVERLAP_SHADOW, OPT_SMALL_LAUNCH_PATHS, OPT_COMPACT_LOG, OPT_DEBUG_LOG_POOL_DIV, OPT_TRACE_TAIL_LANES, OPT_TRACE_TAIL_PATHS, OPT_CHUNK_REFILL, OPT_STAGE_PIPES, OPT_FRAME_KERNEL, OPT_SAMPLES_AHEAD = range(27)
@@ -185,6 +186,8 @@ def load():
         "rt_frame_filter_history_reset": (i32, [vp]),
         "rt_frame_read_filter_history": (i32, [vp, vp, vp]),
         "rt_debug_filter_temporal": (i32, [vp, u32, u32, vp, vp] + [vp] * 8 + [C.POINTER(rt_temporal_filter_desc), vp, vp, vp]),
+        "rt_scene_refit": (i32, [vp, vp, u32]), "rt_scene_refit_buffer": (i32, [vp, vp]),
+        "rt_debug_refit": (i32, [vp, vp, u32, vp, u32, vp, u32, u32, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -239,6 +242,29 @@ def debug_filter_temporal(ctx, cam, prev_cam, hdr, albedo, normal, depth, prev_n
                                     out.ctypes.data, hc_out.ctypes.data, hm_out.ctypes.data):
         raise RtError(lib.rt_last_error(handle).decode())
     return out, hc_out, hm_out
+
+
+def debug_refit(ctx, nodes, triangles, records=None, entry=0):
+    """rt_debug_refit: `nodes` (reference layout) and any fold of it (`records`: the 64-byte records as a structured or uint8 array, `entry`) refitted to
+    `triangles` (same count and order).  ctx None = the host restatement, else refit.hip's kernels on ctx's GPU.
+    Returns (nodes, records, disqualified): disqualified = a record no longer qualifies for k_trace_w4 (its bytes are left as they were)."""
+    lib = load()
+    nodes = np.ascontiguousarray(nodes, T.bvh_node)
+    tris = np.ascontiguousarray(triangles, T.triangle)
+    out_nodes = np.zeros_like(nodes)
+    n_rec = 0 if records is None else len(records)
+    recs = out_recs = None
+    if n_rec:
+        recs = np.ascontiguousarray(records)
+        if recs.dtype.itemsize * (recs.size // n_rec) != 64:
+            raise RtError("debug_refit: records must be 64 bytes each")
+        out_recs = np.zeros_like(recs)
+    handle = ctx.handle if ctx is not None else None
+    rc = lib.rt_debug_refit(handle, nodes.ctypes.data, len(nodes), tris.ctypes.data, len(tris), recs.ctypes.data if n_rec else None, n_rec, entry,
+                            out_nodes.ctypes.data, out_recs.ctypes.data if n_rec else None)
+    if rc not in (0, 2):
+        raise RtError(lib.rt_last_error(handle).decode())
+    return out_nodes, out_recs, rc == 2
 
 
 def choose_tree(scene, shadow=True, mode=1):
@@ -394,7 +420,7 @@ class Context:
         h = C.c_void_p()
         _check(self.lib, None, self.lib.rt_ctx_create(device, C.byref(h)))
         self.handle = h
-        self._frames = []          # weakrefs: frames must be destroyed before their context
+        self._frames = []          # weakrefs: frames (and buffers) must be destroyed before their context
 
     def device_info(self):
         name = C.create_string_buffer(256)
@@ -435,6 +461,25 @@ class Context:
         """RT_CTX_OPT_ADAPT_MIN_INTERVAL_MS (default 500): a camera that keeps leaving the adapted view starts at most one fold
         adaptation per this many milliseconds (not applied when bit 1 of the adaptive-fold mode waits for every adaptation)"""
         _check(self.lib, self.handle, self.lib.rt_ctx_set_option(self.handle, 5, ms))
+
+    def set_refittable(self, on=True):
+        """RT_CTX_OPT_REFITTABLE (effective at the next upload_scene): keep what refit_scene() needs on the device (about 34 bytes per triangle)"""
+        _check(self.lib, self.handle, self.lib.rt_ctx_set_option(self.handle, 10, 1 if on else 0))
+
+    def refit_scene(self, triangles):
+        """rt_scene_refit / rt_scene_refit_buffer: the uploaded scene's triangles moved (same count, same order).  `triangles`: a structured array
+        (types.triangle), or a Buffer of this context that holds them (no host copy).  Frames keep their sums: reset() them."""
+        if isinstance(triangles, Buffer):
+            _check(self.lib, self.handle, self.lib.rt_scene_refit_buffer(self.handle, triangles.handle))
+            return
+        t = np.ascontiguousarray(triangles)
+        if t.dtype != T.triangle:
+            raise RtError("refit_scene: triangles has the wrong dtype")
+        _check(self.lib, self.handle, self.lib.rt_scene_refit(self.handle, t.ctypes.data, len(t)))
+
+    def create_buffer(self, data):
+        """an rt_buffer of this context holding `data` (any contiguous array)"""
+        return Buffer(self, data)
 
     def tree_report(self):
         return self.lib.rt_scene_tree_report(self.handle).decode()
@@ -485,6 +530,36 @@ class Context:
                     fr.close()
             self._frames = []
             self.lib.rt_ctx_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Buffer:
+    """rt_buffer: device memory of a context (CLContext's buffers); close() it before its context."""
+
+    def __init__(self, ctx, data):
+        self.lib = ctx.lib
+        self.ctx = ctx
+        a = np.ascontiguousarray(data)
+        h = C.c_void_p()
+        _check(self.lib, ctx.handle, self.lib.rt_buffer_create(ctx.handle, a.nbytes, a.ctypes.data, C.byref(h)))
+        self.handle = h
+        self.nbytes = a.nbytes
+        import weakref
+        ctx._frames.append(weakref.ref(self))
+
+    def write(self, data, offset=0):
+        a = np.ascontiguousarray(data)
+        _check(self.lib, self.ctx.handle, self.lib.rt_buffer_write(self.handle, offset, a.ctypes.data, a.nbytes))
+
+    def close(self):
+        if self.handle:
+            self.lib.rt_buffer_destroy(self.handle)
             self.handle = None
 
     def __del__(self):

@@ -20,6 +20,7 @@
 #pragma once
 #include "kernels_common.h"
 #include "wide_node.h"
+#include "wide_quant.h"
 
 // what "area" means to the collapse: the host's ownbvh::Metric (iso * half the surface area + projected areas along <= 8 directions);
 // n_dirs < 0: the plain surface area dx dy + dy dz + dz dx (build_wide_bvh without a metric)
@@ -312,31 +313,10 @@ __global__ __launch_bounds__(64) void k_fold_emit(FoldState s, const uint32_t* _
     const float nmin[3] = {nodes[n].bounds_min.x, nodes[n].bounds_min.y, nodes[n].bounds_min.z};
     const float nmax[3] = {nodes[n].bounds_max.x, nodes[n].bounds_max.y, nodes[n].bounds_max.z};
     float origin[3]; int exps[3];
-    for (int a = 0; a < 3; ++a)
-    {
-        // cell = 2^e: 254 cells span the node (one spare for the floor of the origin); the grid stays exactly representable
-        // (|origin| / cell < 2^23 leaves room for + 255 below 2^24): build_wide_bvh's rule, the exponent found without a logarithm
-        const double extent = (double)nmax[a] - (double)nmin[a];
-        const double amax = fmax(fabs((double)nmin[a]), fabs((double)nmax[a]));
-        int e = -126;
-        if (extent > 0.0)
-        {
-            int ex = 0;
-            const double m = frexp(extent / 254.0, &ex);           // extent / 254 = m * 2^ex, m in [0.5, 1): ceil(log2) = ex, or ex - 1 for a power of two
-            const int c = m == 0.5 ? ex - 1 : ex;
-            e = c > e ? c : e;
-        }
-        while (ldexp(254.0, e) < extent) ++e;
-        while (amax > 0.0 && amax / ldexp(1.0, e) >= 8388608.0 - 256.0) ++e;
-        if (e > 20 || amax >= 268435456.0) { *s.error = FOLD_FRAME; return; }
-        const double cell = ldexp(1.0, e);
-        const double o = floor((double)nmin[a] / cell) * cell;
-        origin[a] = (float)o;
-        if ((double)origin[a] != o) { *s.error = FOLD_FRAME; return; }
-        exps[a] = e;
-    }
+    // build_wide_bvh's frame and planes: wide_quant.h, the one function both call
+    if (!wide_frame(nmin, nmax, origin, exps)) { *s.error = FOLD_FRAME; return; }
     r.ox = origin[0]; r.oy = origin[1]; r.oz = origin[2];
-    r.meta = (uint32_t)(exps[0] + 127) | (uint32_t)(exps[1] + 127) << 8 | (uint32_t)(exps[2] + 127) << 16 | f.n_slots << 24;
+    r.meta = wide_meta(exps, f.n_slots);
     r.order = order_bits;
     for (int k = 0; k < 4; ++k)
     {
@@ -350,17 +330,9 @@ __global__ __launch_bounds__(64) void k_fold_emit(FoldState s, const uint32_t* _
         r.ref[k] = (c.num_primitives_axis >> 16) != 0u ? (RT_LEAF_BIT | c.offset) : s.is_root[slot[k]];
         const float cmin[3] = {c.bounds_min.x, c.bounds_min.y, c.bounds_min.z};
         const float cmax[3] = {c.bounds_max.x, c.bounds_max.y, c.bounds_max.z};
-        for (int a = 0; a < 3; ++a)
-        {
-            const double cell = ldexp(1.0, exps[a]);
-            double lo = floor(((double)cmin[a] - (double)origin[a]) / cell);
-            double hi = ceil(((double)cmax[a] - (double)origin[a]) / cell);
-            while ((double)origin[a] + lo * cell > (double)cmin[a]) lo -= 1.0;     // containment settled on the grid points themselves
-            while ((double)origin[a] + hi * cell < (double)cmax[a]) hi += 1.0;
-            if (lo < 0.0 || hi > 255.0 || lo > hi) { *s.error = FOLD_FRAME; return; }
-            r.lo[a] |= (uint32_t)lo << (8 * k);
-            r.hi[a] |= (uint32_t)hi << (8 * k);
-        }
+        uint32_t lo[3], hi[3];
+        if (!wide_quantise(cmin, cmax, origin, exps, lo, hi)) { *s.error = FOLD_FRAME; return; }
+        for (int a = 0; a < 3; ++a) { r.lo[a] |= lo[a] << (8 * k); r.hi[a] |= hi[a] << (8 * k); }
     }
     out[w] = r;
 }

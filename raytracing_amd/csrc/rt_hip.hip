@@ -23,6 +23,7 @@
 #include <chrono>
 #include "wide_bvh.h"        // the host-side fold, the pair layout, the adaptation's host walks (wide_bvh.cpp)
 #include "device_fold.h"     // ... and the fold + crossing counts on the device (device_fold.hip)
+#include "refit.h"           // the refit of the scene's trees when its triangles move (refit.hip)
 #include "filters_host.h"         // the filters' guide pass, a-trous passes and temporal stages (filters.hip)
 using namespace rtw;
 
@@ -57,6 +58,13 @@ struct Scene
     // axis, e.g. an overhead light (0, -1, 0)): k_trace_w4 would hand every one of them to its small follow-up launch,
     // so the automatic choice traces the shadow queue with k_trace2 (select-form slab test inline, full residency)
     bool slow_shadow = false;
+    // RT_CTX_OPT_REFITTABLE (refit_impl.h): what rt_scene_refit keeps beside the scene; nullptr = the option was off at upload (or refit_refusal says why not)
+    refit::State* refit = nullptr;
+    std::string refit_refusal;
+    bool refit_wide_built = false;   // wide_ok as upload left it (a refit that meets a record that no longer qualifies clears wide_ok until one qualifies again)
+    bool adapt_retired = false;      // a refit has retired the fold adaptation
+    uint32_t n_materials = 0;
+    uint64_t refits = 0;
 };
 } // namespace
 
@@ -82,6 +90,7 @@ struct rt_ctx
     uint32_t wide_layout = 0;               // RT_CTX_OPT_WIDE_LAYOUT: 1 = the 4-wide records stored in (parent, likeliest child) pairs, one pair per 128-byte line (pair_layout)
     uint32_t tree_builder = 2;              // RT_CTX_OPT_TREE_BUILDER: the shadow rays' own binary tree -- 0 = own_bvh.h's full-sweep SAH on host threads, 1 = PLOC on the device (ploc_kernels.h),
                                             // 2 (default) = both start, the device's is measured first and the host's build is abandoned if it wins its measurement
+    uint32_t refittable = 0;                // RT_CTX_OPT_REFITTABLE: rt_scene_upload keeps what rt_scene_refit needs (refit.h)
     uint32_t device_fold = 1;               // RT_CTX_OPT_DEVICE_FOLD: the SAH collapse into 4-wide records runs on the device (fold_kernels.h); 0 = on host threads
     uint64_t scene_uploads = 0;             // rt_scene_upload calls so far (what a frame's measured choices were made for)
     std::vector<rt_frame*> frames;   // the frames alive on this context (rt_finish waits for their side streams too)
@@ -362,6 +371,7 @@ void free_scene(Scene& s)
     void* ptrs[] = {s.nodes, s.tris_rt, s.tris_sh, s.materials, s.textures, s.texture_data, s.lights, s.env, s.emissive, s.wnodes, s.mat_tex16, s.wnodes_sh, s.wnodes_cl};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     if (s.adapt) drop_fold_adapt(s.adapt);
+    if (s.refit) { refit::release(*s.refit); delete s.refit; }
     s = Scene();
 }
 } // namespace
@@ -490,6 +500,7 @@ int rt_ctx_set_option(rt_ctx* ctx, int option, uint32_t value)
     if (option == RT_CTX_OPT_ADAPTIVE_FOLD) { ctx->adaptive_fold = value & 31u; return RT_OK; }
     if (option == RT_CTX_OPT_DEVICE_FOLD) { ctx->device_fold = value ? 1u : 0u; return RT_OK; }
     if (option == RT_CTX_OPT_WIDE_LAYOUT) { ctx->wide_layout = value ? 1u : 0u; return RT_OK; }
+    if (option == RT_CTX_OPT_REFITTABLE) { ctx->refittable = value ? 1u : 0u; return RT_OK; }
     if (option == RT_CTX_OPT_TREE_BUILDER) { ctx->tree_builder = value > 2u ? 2u : value; return RT_OK; }
     if (option == RT_CTX_OPT_ADAPT_WAIT)
     {
@@ -571,6 +582,8 @@ namespace
 } // namespace
 
 extern "C" {
+
+#include "refit_impl.h"
 
 // ---- scene -----------------------------------------------------------------
 int rt_scene_upload(rt_ctx* ctx, const rt_scene_desc* sd)
@@ -913,6 +926,7 @@ int rt_scene_upload(rt_ctx* ctx, const rt_scene_desc* sd)
             sh->build_seconds, sh->fold_seconds, t_choose, t_rest, nt, nn, s.n_wide, s.n_wide_sh);
         s.tree_report += line;
     }
+    if (ctx->refittable) refit_arm(ctx, sd, n_interior + 1u);
     return RT_OK;
 }
 

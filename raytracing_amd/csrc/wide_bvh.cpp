@@ -9,6 +9,7 @@
 #include <memory>
 #include <thread>
 #include "rt_hip.h"
+#include "wide_quant.h"
 
 namespace rtw
 {
@@ -374,27 +375,11 @@ bool build_wide_bvh(const rt_bvh_node* nodes, uint32_t nn, int collapse, std::ve
         const float nmax[3] = {nodes[n].bounds_max.x, nodes[n].bounds_max.y, nodes[n].bounds_max.z};
         float origin[3];
         int exps[3];
-        for (int a = 0; a < 3; ++a)
-        {
-            // cell = 2^e: 254 cells span the node (one spare for the floor of the origin), and the grid
-            // stays exactly representable: |origin| / cell < 2^23 leaves room for + 255 below 2^24
-            const double extent = (double)nmax[a] - (double)nmin[a];
-            const double amax = std::max(std::fabs((double)nmin[a]), std::fabs((double)nmax[a]));
-            int e = -126;
-            if (extent > 0.0) e = std::max(e, (int)std::ceil(std::log2(extent / 254.0)));
-            while (std::ldexp(254.0, e) < extent) ++e;
-            while (amax > 0.0 && amax / std::ldexp(1.0, e) >= 8388608.0 - 256.0) ++e;
-            // k_trace_w4 evaluates slab distances as q * (cell * inv) + (origin - org) * inv: bounded operands keep that
-            // finite for every ray it accepts (trace_kernels.h, loop C)
-            if (e > 20 || amax >= 268435456.0) return false;
-            const double cell = std::ldexp(1.0, e);
-            const double o = std::floor((double)nmin[a] / cell) * cell;
-            origin[a] = (float)o;
-            if ((double)origin[a] != o) return false;                     // cannot happen by construction
-            exps[a] = e;
-        }
+        // the frame: 254 cells of a power-of-two size span the node, the grid stays exactly representable (wide_quant.h: one function for this fold,
+        // k_fold_emit and the refit)
+        if (!wide_frame(nmin, nmax, origin, exps)) return false;
         r.ox = origin[0]; r.oy = origin[1]; r.oz = origin[2];
-        r.meta = (uint32_t)(exps[0] + 127) | (uint32_t)(exps[1] + 127) << 8 | (uint32_t)(exps[2] + 127) << 16 | f.n_slots << 24;
+        r.meta = wide_meta(exps, f.n_slots);
         r.order = arr->order;
         for (int k = 0; k < 4; ++k)
         {
@@ -408,19 +393,9 @@ bool build_wide_bvh(const rt_bvh_node* nodes, uint32_t nn, int collapse, std::ve
             r.ref[k] = is_leaf(slot[k]) ? (RT_LEAF_BIT | c.offset) : wide_of[slot[k]];
             const float cmin[3] = {c.bounds_min.x, c.bounds_min.y, c.bounds_min.z};
             const float cmax[3] = {c.bounds_max.x, c.bounds_max.y, c.bounds_max.z};
-            for (int a = 0; a < 3; ++a)
-            {
-                const double cell = std::ldexp(1.0, exps[a]);
-                double lo = std::floor(((double)cmin[a] - (double)origin[a]) / cell);
-                double hi = std::ceil(((double)cmax[a] - (double)origin[a]) / cell);
-                // the difference above is rounded (a bound of 1e-17 beside an origin of -0.2 vanishes in it): settle the
-                // containment on the grid points themselves, which are exact in binary32 and binary64 alike
-                while ((double)origin[a] + lo * cell > (double)cmin[a]) lo -= 1.0;
-                while ((double)origin[a] + hi * cell < (double)cmax[a]) hi += 1.0;
-                if (lo < 0.0 || hi > 255.0 || lo > hi) return false;      // cannot happen: the child is inside the node
-                r.lo[a] |= (uint32_t)lo << (8 * k);
-                r.hi[a] |= (uint32_t)hi << (8 * k);
-            }
+            uint32_t lo[3], hi[3];
+            if (!wide_quantise(cmin, cmax, origin, exps, lo, hi)) return false;      // cannot happen: the child is inside the node
+            for (int a = 0; a < 3; ++a) { r.lo[a] |= lo[a] << (8 * k); r.hi[a] |= hi[a] << (8 * k); }
         }
         return true;
     };

@@ -24,6 +24,7 @@ EXPORTS = [
     "rth_render_ctx_handle", "rth_render_num_nodes", "rth_render_nodes", "rth_render_set_aov", "rth_render_resolve",
     "rth_render_set_blue_noise_path", "rth_render_reserve_samples", "rth_scene_save_cache", "rth_load_jpeg",
     "rth_render_upload_gpu_data", "rth_render_setup_seconds", "rth_render_create_with_options",
+    "rth_render_set_refittable", "rth_render_refit",
 ]
 
 
@@ -65,6 +66,7 @@ def load():
         "rth_render_sample_count": (u32, [vp]), "rth_render_read_radiance": (i32, [vp, vp]),
         "rth_render_read_resolved": (i32, [vp, vp]), "rth_render_stats": (i32, [vp, C.POINTER(rt_stats)]),
         "rth_render_frame_handle": (vp, [vp]), "rth_render_ctx_handle": (vp, [vp]), "rth_render_upload_gpu_data": (i32, [vp]),
+        "rth_render_set_refittable": (i32, [vp, i32]), "rth_render_refit": (i32, [vp, vp, u32]),
         "rth_render_num_nodes": (u32, [vp]), "rth_render_nodes": (vp, [vp]),
         "rth_render_set_aov": (i32, [vp, i32]), "rth_render_resolve": (i32, [vp, vp]),
         "rth_render_set_blue_noise_path": (i32, [vp, cp]),
@@ -290,6 +292,18 @@ class Render:
         """RT_CTX_OPT_ADAPTIVE_FOLD: bit 0 = the first frame probes its own rays and both 4-wide trees are folded again for them (exact; the
         report line appears in tree_report() once the fold is adopted), bit 1 = the frame waits for it, bit 2 = small trees too."""
         self.set_ctx_option(4, mode, upload)
+
+    def set_refittable(self, on=True):
+        """RT_CTX_OPT_REFITTABLE, then the scene is uploaded again: what refit() needs is kept on the device (about 34 bytes per triangle)"""
+        self._c(self.lib.rth_render_set_refittable(self.handle, int(on)))
+
+    def refit(self, triangles):
+        """The scene's triangles moved (types.triangle[], the count and BVH order of scene_arrays()['triangles']): every tree is refitted on the device
+        and the accumulation restarts.  Results equal a fresh upload of the moved triangles with the same topology, bit for bit."""
+        t = np.ascontiguousarray(triangles)
+        if t.dtype != T.triangle:
+            raise RtError("refit: triangles has the wrong dtype")
+        self._c(self.lib.rth_render_refit(self.handle, t.ctypes.data, len(t)))
 
     def tree_report(self):
         from . import capi

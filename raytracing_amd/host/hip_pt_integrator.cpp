@@ -140,6 +140,17 @@ void HIPPathTraceIntegrator::UploadGPUData(Scene const& scene, AccelerationStruc
     Check(rt_scene_upload(context_.Get(), &sd));
 }
 
+void HIPPathTraceIntegrator::SetRefittable(bool on)
+{
+    Check(rt_ctx_set_option(context_.Get(), RT_CTX_OPT_REFITTABLE, on ? 1u : 0u));
+}
+
+void HIPPathTraceIntegrator::RefitGeometry(Triangle const* triangles, std::size_t count)
+{
+    Check(rt_scene_refit(context_.Get(), (const rt_triangle*)triangles, (uint32_t)count));
+    RequestReset();
+}
+
 void HIPPathTraceIntegrator::SetCameraData(Camera const& camera)
 {
     prev_camera_ = camera_;

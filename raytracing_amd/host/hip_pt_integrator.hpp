@@ -87,6 +87,11 @@ public:
     // advances the frame's history by one call.  It excludes SetSpatialFilter and EnableDenoiser(true): turning one on while another is on throws.
     // A tile of a larger image refuses it.
     void SetTemporalFilter(rt_temporal_filter_desc const* desc);
+    // Moving geometry (rt_scene_refit).  SetRefittable: RT_CTX_OPT_REFITTABLE on this integrator's context -- effective at the next
+    // UploadGPUData.  RefitGeometry: the uploaded scene's triangles moved (same count, same BVH order): every tree is refitted on the device in milliseconds
+    // where UploadGPUData takes a third of a second or more; requests a reset, since the accumulated samples show the old pose.
+    void SetRefittable(bool on);
+    void RefitGeometry(Triangle const* triangles, std::size_t count);
     rt_frame* GetFrame() const { return frame_; }
 
 protected:

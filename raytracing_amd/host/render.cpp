@@ -148,6 +148,17 @@ void TiledRender::SetCamera(Camera const& camera)
     camera_changed_ = true;
 }
 
+void TiledRender::SetRefittable(bool on)
+{
+    for (auto& i : integrators_) { i->SetRefittable(on); i->UploadGPUData(scene_, *acc_structure_); }
+    folds_shared_ = false;                                  // the uploads made their own folds again
+}
+
+void TiledRender::RefitGeometry(Triangle const* triangles, std::size_t count)
+{
+    for (auto& i : integrators_) i->RefitGeometry(triangles, count);
+}
+
 void TiledRender::SetMaxBounces(std::uint32_t max_bounces)
 {
     for (auto& i : integrators_) i->SetMaxBounces(max_bounces);

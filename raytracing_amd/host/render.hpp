@@ -30,6 +30,10 @@ public:
     HIPContext& GetContext() { return *context_; }
     // Uploads the scene again (after an rt_ctx_set_option that changes the device-side layout: tools, A/B runs)
     void UploadGPUData() { integrator_->UploadGPUData(scene_, *acc_structure_); }
+    // Moving geometry: SetRefittable(true) uploads the scene again with what a refit needs kept on the device; RefitGeometry takes the moved triangles (the
+    // scene's count and BVH order: GetTriangles() of the finalised scene) and restarts the accumulation.  The host Scene object keeps the pose it was built for.
+    void SetRefittable(bool on) { integrator_->SetRefittable(on); UploadGPUData(); }
+    void RefitGeometry(Triangle const* triangles, std::size_t count) { integrator_->RefitGeometry(triangles, count); }
     AccelerationStructure const& GetAccelerationStructure() const { return *acc_structure_; }
     std::uint32_t GetWidth() const { return width_; }
     std::uint32_t GetHeight() const { return height_; }
@@ -69,6 +73,9 @@ public:
     void SetSpatialFilter(rt_filter_desc const* desc);
     // Likewise the temporal filter (its history would have to cross the tiles' rows): any desc throws; nullptr (off) is accepted.
     void SetTemporalFilter(rt_temporal_filter_desc const* desc);
+    // Moving geometry, forwarded to every tile's context (the scene is replicated; folds imported from tile 0 refit like any other)
+    void SetRefittable(bool on);
+    void RefitGeometry(Triangle const* triangles, std::size_t count);
     void RenderSamples(std::uint32_t n);                  // every tile, concurrently; returns when all are enqueued and finished
     std::vector<float> GatherRadiance(int root = 0);      // height x width x RGBA running sums, image order
     rt_stats GetStats() const;                            // ray counters summed over the tiles
