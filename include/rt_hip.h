@@ -123,6 +123,13 @@ enum rt_ctx_option
                                       the exact box of every 4-wide record, arrival counters: 8 bytes per child-pair record + 40 per 4-wide record, about 34 bytes
                                       per triangle.  Upload's results, trees and report are the same either way.  Takes effect at the
                                       next rt_scene_upload. */
+    , RT_CTX_OPT_REFIT_MOTION = 11 /* 0 (default): a refit drops every temporal filter history, as an upload does; nothing is kept or allocated.
+                                      1 (needs RT_CTX_OPT_REFITTABLE = 1; without it nothing is allocated and the refit calls stay refused): rt_scene_upload
+                                      allocates room for ONE previous pose -- three positions and three shading normals per triangle, the first six float4 of
+                                      the shading record, 96 bytes per triangle -- and every successful refit first copies the pose it is about to replace
+                                      there.  rt_frame_filter_temporal then follows the moved surfaces instead of dropping its history (see there; DESIGN.md
+                                      section 7f).  If the room cannot be allocated the option is treated as off and rt_scene_tree_report says so.  Every
+                                      other result is the same either way.  Takes effect at the next rt_scene_upload. */
     , RT_CTX_OPT_ADAPT_WAIT = 6    /* 1 / 0: sets / clears bit 1 of RT_CTX_OPT_ADAPTIVE_FOLD (rt_integrate waits for an adaptation it has
                                       started) for the scene IN PLACE, at once; the context's option, which the next upload reads, stays
                                       (bench.py: the headline waits for its fold, the moving-camera leg runs as the library ships) */
@@ -186,7 +193,7 @@ int rt_scene_upload(rt_ctx* ctx, const rt_scene_desc* scene);
  * Refused with the scene untouched: RT_CTX_OPT_REFITTABLE off at upload, no scene, another count or size, the tolerance mode (RT_CTX_OPT_CLOSEST_TREE != 0), a
  * non-finite position or mtl_index >= num_materials (checked by a read-only kernel first), or node arrays whose leaves are not consecutive ranges covering the
  * triangle array.  Otherwise: quiesces as rt_scene_upload does (samples traced ahead are dropped); a fold adaptation is retired -- one in flight is cancelled --
- * and the records adapted so far stay in use; guide caches and temporal histories drop as on upload; frames keep their accumulation: rt_reset them.
+ * and the records adapted so far stay in use; guide caches and temporal histories drop as on upload (RT_CTX_OPT_REFIT_MOTION = 1: the histories follow the move); frames keep their accumulation: rt_reset them.
  * A record that no longer qualifies for k_trace_w4 after the move (cell above 2^20, coordinates beyond 2^28) does not fail the call: the scene is traced by the
  * BVH2 kernels, as after an upload of such a tree, until a later refit qualifies again; rt_scene_tree_report's "refit" line says which. */
 int rt_scene_refit(rt_ctx* ctx, const rt_triangle* triangles, uint32_t num_triangles);
@@ -454,6 +461,12 @@ typedef struct rt_temporal_filter_desc
 /* resolve + reproject + accumulate + filter: RGBA float, tone-mapped (Reinhard), alpha 1, synchronous; the history advances by this call.
  * alpha_color = 1 with zero iterations is rt_frame_resolve's image bit for bit.  Fails (frame and history untouched) for NULL arguments, desc
  * values out of range, a tile frame, RT_OPT_AOV != 0 or RT_OPT_DENOISER != 0. */
+/* Moved geometry.  A history made before an rt_scene_upload is dropped.  A history made before an rt_scene_refit* is dropped too (a stale history on a moved
+ * surface ghosts) unless RT_CTX_OPT_REFIT_MOTION kept the pose that refit replaced AND exactly one refit lies between the previous call and this one: then
+ * every pixel with a first hit is reprojected from where its surface point WAS -- the hit's barycentrics on the same triangle of the kept pose, projected
+ * through the previous call's camera -- and the tap's normal is tested against the normal the point had there; depth test, taps and everything after are the
+ * ordinary rule (a standing camera reprojects too).  The kept pose is ONE deep: two or more refits between two calls give a fresh history.  That is a stated
+ * limit; call the filter once per refit. */
 int rt_frame_filter_temporal(rt_frame* frame, const rt_temporal_filter_desc* desc, float* host_rgba);
 /* drop the history: every pixel misses at the next rt_frame_filter_temporal */
 int rt_frame_filter_history_reset(rt_frame* frame);
@@ -468,6 +481,22 @@ int rt_debug_filter_temporal(rt_ctx* ctx, uint32_t width, uint32_t height, const
     const float* hdr_rgba, const float* albedo_rgba, const float* normal_rgba, const float* depth, const float* prev_normal_rgba,
     const float* prev_depth, const float* hist_color, const float* hist_moments, const rt_temporal_filter_desc* desc, float* out_hdr_rgba,
     float* hist_color_out, float* hist_moments_out);
+/* the same with the motion images of moved geometry: prev_position_rgba = (where the pixel's first hit was at the previous call, 1), w = 0: no motion known
+ * (the camera-only rule for that pixel); prev_pose_normal_rgba = (its unit normal there, 0).  Either NULL: rt_debug_filter_temporal exactly.  With both, the
+ * history is reprojected (through prev_cam, or cam when prev_cam is NULL) also when the two cameras are equal. */
+int rt_debug_filter_temporal_motion(rt_ctx* ctx, uint32_t width, uint32_t height, const rt_camera* cam, const rt_camera* prev_cam,
+    const float* hdr_rgba, const float* albedo_rgba, const float* normal_rgba, const float* depth, const float* prev_normal_rgba,
+    const float* prev_depth, const float* hist_color, const float* hist_moments, const float* prev_position_rgba,
+    const float* prev_pose_normal_rgba, const rt_temporal_filter_desc* desc, float* out_hdr_rgba, float* hist_color_out, float* hist_moments_out);
+/* the motion images for the frame's current camera and the pose the context's last refit replaced (guides and images computed if stale): per pixel
+ * (previous position, 1) and (previous unit normal, 0); zeros where the pixel-centre ray misses, and everywhere while the context keeps no pose
+ * (RT_CTX_OPT_REFIT_MOTION off at upload, or no refit yet).  Either array may be NULL.  A tile frame is refused.  32 bytes per pixel on the device, made
+ * on first use. */
+int rt_frame_read_guide_motion(rt_frame* frame, float* prev_position_rgba, float* prev_normal_rgba);
+/* the motion images' kernel on caller data: n pixels, hits = 4 floats per pixel (u, v, the primitive index's bits, unused; an index >= num_triangles = no
+ * hit), prev_triangles = the previous pose in the reference layout.  ctx == NULL: the host restatement; the two agree bit for bit. */
+int rt_debug_guide_motion(rt_ctx* ctx, uint32_t n, const float* hits, const rt_triangle* prev_triangles, uint32_t num_triangles,
+    float* out_position_rgba, float* out_normal_rgba);
 
 /* ---- statistics: the queue counters the reference keeps in
  * ray_counter_buffer_[2] / shadow_ray_counter_buffer_ (cl_pt_integrator.hpp:85-86),

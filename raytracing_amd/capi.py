@@ -109,6 +109,7 @@ EXPORTS = [
     "rt_frame_filter", "rt_frame_read_guides", "rt_debug_filter",
     "rt_frame_filter_temporal", "rt_frame_filter_history_reset", "rt_frame_read_filter_history", "rt_debug_filter_temporal",
     "rt_scene_refit", "rt_scene_refit_buffer", "rt_debug_refit",
+    "rt_frame_read_guide_motion", "rt_debug_guide_motion", "rt_debug_filter_temporal_motion",
 ]
 
 OPT_MAX_BOUNCES, OPT_WHITE_FURNACE, OPT_SAMPLER, OPT_AOV, OPT_DENOISER, OPT_DROP_LAST, OPT_PROFILE, OPT_TRACE_VARIANT, OPT_TRACE_WAVES, OPT_SAMPLES_IN_FLIGHT, OPT_SELECT_FORM_BOX, OPT_PACKET_BOUNCES, OPT_TRACE_TUNE, OPT_DEBUG_ALLOC_LIMIT, OPT_PATH_STATE_LIMIT_MB, OPT_PIPELINES, OPT_SHADE_PARTITION, OPT_OVERLAP_SHADOW, OPT_SMALL_LAUNCH_PATHS, OPT_COMPACT_LOG, OPT_DEBUG_LOG_POOL_DIV, OPT_TRACE_TAIL_LANES, OPT_TRACE_TAIL_PATHS, OPT_CHUNK_REFILL, OPT_STAGE_PIPES, OPT_FRAME_KERNEL, OPT_SAMPLES_AHEAD = range(27)
@@ -188,6 +189,9 @@ def load():
         "rt_debug_filter_temporal": (i32, [vp, u32, u32, vp, vp] + [vp] * 8 + [C.POINTER(rt_temporal_filter_desc), vp, vp, vp]),
         "rt_scene_refit": (i32, [vp, vp, u32]), "rt_scene_refit_buffer": (i32, [vp, vp]),
         "rt_debug_refit": (i32, [vp, vp, u32, vp, u32, vp, u32, u32, vp, vp]),
+        "rt_frame_read_guide_motion": (i32, [vp, vp, vp]),
+        "rt_debug_guide_motion": (i32, [vp, u32, vp, vp, u32, vp, vp]),
+        "rt_debug_filter_temporal_motion": (i32, [vp, u32, u32, vp, vp] + [vp] * 10 + [C.POINTER(rt_temporal_filter_desc), vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -224,6 +228,37 @@ def debug_filter_temporal(ctx, cam, prev_cam, hdr, albedo, normal, depth, prev_n
     """rt_debug_filter_temporal: one call of the temporal filter over caller arrays (hdr, albedo, normal, prev_normal, hist_color, hist_moments:
     float32[h, w, 4]; depth, prev_depth: float32[h, w]; cam, prev_cam: types.camera, prev_cam None = a standing camera) on ctx's GPU, or the
     host restatement when ctx is None.  Returns (HDR image, colour history, moments history (mu1, mu2, L, 0)), each float32[h, w, 4]."""
+    return _debug_filter_temporal(ctx, cam, prev_cam, hdr, albedo, normal, depth, prev_normal, prev_depth, hist_color, hist_moments, None, None, desc, False)
+
+
+def debug_filter_temporal_motion(ctx, cam, prev_cam, hdr, albedo, normal, depth, prev_normal, prev_depth, hist_color, hist_moments, prev_position,
+                                 prev_pose_normal, desc=None):
+    """rt_debug_filter_temporal_motion: debug_filter_temporal with the motion images of moved geometry (prev_position float32[h, w, 4] = (where the
+    pixel's first hit was at the previous call, 1), w 0 = no motion known; prev_pose_normal = (its unit normal there, 0)).  Either None: exactly
+    debug_filter_temporal.  With both the history is reprojected even under a standing camera."""
+    return _debug_filter_temporal(ctx, cam, prev_cam, hdr, albedo, normal, depth, prev_normal, prev_depth, hist_color, hist_moments, prev_position,
+                                  prev_pose_normal, desc, True)
+
+
+def debug_guide_motion(ctx, hits, prev_triangles):
+    """rt_debug_guide_motion: per pixel of hits (float32[..., 4] = u, v, the primitive index's bits, unused; an index >= len(prev_triangles) = no hit)
+    where the hit was in the pose prev_triangles (types.triangle) and its unit normal there: (float32[..., 4] = (X', 1), float32[..., 4] = (n', 0)),
+    zeros without a hit.  ctx None = the host restatement, else the kernel on ctx's GPU."""
+    lib = load()
+    hits = np.ascontiguousarray(hits, np.float32)
+    tris = np.ascontiguousarray(prev_triangles)
+    if hits.shape[-1] != 4 or tris.dtype != T.triangle:
+        raise ValueError("debug_guide_motion: hits must be [..., 4] float32, prev_triangles types.triangle")
+    pos, nrm = np.zeros_like(hits), np.zeros_like(hits)
+    handle = ctx.handle if ctx is not None else None
+    if lib.rt_debug_guide_motion(handle, hits.size // 4, hits.ctypes.data, tris.ctypes.data if len(tris) else None, len(tris), pos.ctypes.data,
+                                 nrm.ctypes.data):
+        raise RtError(lib.rt_last_error(handle).decode())
+    return pos, nrm
+
+
+def _debug_filter_temporal(ctx, cam, prev_cam, hdr, albedo, normal, depth, prev_normal, prev_depth, hist_color, hist_moments, prev_position,
+                           prev_pose_normal, desc, motion_entry):
     lib = load()
     hdr = np.ascontiguousarray(hdr, np.float32)
     h, w = hdr.shape[:2]
@@ -237,9 +272,17 @@ def debug_filter_temporal(ctx, cam, prev_cam, hdr, albedo, normal, depth, prev_n
     out, hc_out, hm_out = np.zeros_like(hdr), np.zeros_like(hdr), np.zeros_like(hdr)
     handle = ctx.handle if ctx is not None else None
     d = temporal_filter_desc(desc)
-    if lib.rt_debug_filter_temporal(handle, w, h, cam.ctypes.data, pc.ctypes.data if pc is not None else None, hdr.ctypes.data, alb.ctypes.data,
-                                    nrm.ctypes.data, dep.ctypes.data, pnrm.ctypes.data, pdep.ctypes.data, hc.ctypes.data, hm.ctypes.data, C.byref(d),
-                                    out.ctypes.data, hc_out.ctypes.data, hm_out.ctypes.data):
+    head = (handle, w, h, cam.ctypes.data, pc.ctypes.data if pc is not None else None, hdr.ctypes.data, alb.ctypes.data, nrm.ctypes.data, dep.ctypes.data,
+            pnrm.ctypes.data, pdep.ctypes.data, hc.ctypes.data, hm.ctypes.data)
+    tail = (C.byref(d), out.ctypes.data, hc_out.ctypes.data, hm_out.ctypes.data)
+    if motion_entry:
+        pp, pn = (np.ascontiguousarray(a, np.float32) if a is not None else None for a in (prev_position, prev_pose_normal))
+        if any(a is not None and a.shape != hdr.shape for a in (pp, pn)):
+            raise ValueError("debug_filter_temporal_motion: the motion images must be [h, w, 4]")
+        rc = lib.rt_debug_filter_temporal_motion(*head, pp.ctypes.data if pp is not None else None, pn.ctypes.data if pn is not None else None, *tail)
+    else:
+        rc = lib.rt_debug_filter_temporal(*head, *tail)
+    if rc:
         raise RtError(lib.rt_last_error(handle).decode())
     return out, hc_out, hm_out
 
@@ -466,6 +509,11 @@ class Context:
         """RT_CTX_OPT_REFITTABLE (effective at the next upload_scene): keep what refit_scene() needs on the device (about 34 bytes per triangle)"""
         _check(self.lib, self.handle, self.lib.rt_ctx_set_option(self.handle, 10, 1 if on else 0))
 
+    def set_refit_motion(self, on=True):
+        """RT_CTX_OPT_REFIT_MOTION (effective at the next upload_scene; needs set_refittable): every refit keeps the pose it replaces (96 bytes per
+        triangle) and Frame.filter_temporal() follows the moved surfaces instead of dropping its history"""
+        _check(self.lib, self.handle, self.lib.rt_ctx_set_option(self.handle, 11, 1 if on else 0))
+
     def refit_scene(self, triangles):
         """rt_scene_refit / rt_scene_refit_buffer: the uploaded scene's triangles moved (same count, same order).  `triangles`: a structured array
         (types.triangle), or a Buffer of this context that holds them (no host copy).  Frames keep their sums: reset() them."""
@@ -641,6 +689,14 @@ class Frame:
         passes = C.c_uint32()
         self._c(self.lib.rt_frame_read_guides(self.handle, alb.ctypes.data, nrm.ctypes.data, dep.ctypes.data, C.byref(passes)))
         return alb, nrm, dep, passes.value
+
+    def guide_motion(self):
+        """rt_frame_read_guide_motion: (previous position float32[h, w, 4] = (X', 1), previous normal float32[h, w, 4] = (n', 0)) of every pixel's first
+        hit in the pose the context's last refit replaced; zeros without a hit or while the context keeps no pose"""
+        pos = np.zeros((self.local_rows, self.width, 4), np.float32)
+        nrm = np.zeros_like(pos)
+        self._c(self.lib.rt_frame_read_guide_motion(self.handle, pos.ctypes.data, nrm.ctypes.data))
+        return pos, nrm
 
     def filter_temporal(self, desc=None):
         """rt_frame_filter_temporal: the resolved image reprojected, accumulated with the frame's history and passed through the variance-guided

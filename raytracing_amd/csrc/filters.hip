@@ -62,6 +62,37 @@ __global__ __launch_bounds__(256) void k_sf_guide_values(DScene sc, const float4
     nz[i] = make_float4(normal.x, normal.y, normal.z, length3(F3(ro.x, ro.y, ro.z) - position));
 }
 
+// RT_CTX_OPT_REFIT_MOTION: the pose a refit is about to replace -- the first six float4 (three positions, three shading normals) of every 128-byte shading
+// record, 96 bytes per triangle.  One thread per float4: a wave reads 96 of every 128 bytes it touches and writes whole lines; pure streaming, no LDS.
+__global__ __launch_bounds__(256) void k_sf_snapshot_pose(const float4* __restrict__ tsh, uint32_t nt, float4* __restrict__ snap)
+{
+    const size_t i = (size_t)blockIdx.x * 256u + threadIdx.x;
+    if (i >= (size_t)nt * 6u) return;
+    const size_t t = i / 6u;
+    snap[i] = tsh[t * 8u + (i - t * 6u)];
+}
+
+// where each pixel's first hit was in the snapshot's pose (tf_guide_motion): one thread per pixel, a gather of 96 bytes; a pixel without a hit gets zeros
+__global__ __launch_bounds__(256) void k_sf_guide_motion(const float4* __restrict__ snap, uint32_t nt, const float4* __restrict__ hits, uint32_t n,
+    float4* __restrict__ prev_pos, float4* __restrict__ prev_n)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const float4 hit = hits[i];
+    const uint32_t prim = __float_as_uint(hit.z);
+    sf_f4 pos = {0.0f, 0.0f, 0.0f, 0.0f}, nrm = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (prim < nt)                                               // RT_INVALID_ID (a miss) is above every count
+    {
+        const float4* tp = snap + (size_t)prim * 6;
+        const float4 q0 = tp[0], q1 = tp[1], q2 = tp[2], q3 = tp[3], q4 = tp[4], q5 = tp[5];
+        const sf_f4 rec[6] = {{q0.x, q0.y, q0.z, 0.0f}, {q1.x, q1.y, q1.z, 0.0f}, {q2.x, q2.y, q2.z, 0.0f},
+                              {q3.x, q3.y, q3.z, 0.0f}, {q4.x, q4.y, q4.z, 0.0f}, {q5.x, q5.y, q5.z, 0.0f}};
+        tf_guide_motion(rec, hit.x, hit.y, &pos, &nrm);
+    }
+    prev_pos[i] = make_float4(pos.x, pos.y, pos.z, pos.w);
+    prev_n[i] = make_float4(nrm.x, nrm.y, nrm.z, nrm.w);
+}
+
 // the per-pixel kernels: one thread per pixel, 16 x 16 blocks; false for a thread outside the width x height image
 __device__ inline bool pixel16(uint32_t width, uint32_t height, uint32_t& x, uint32_t& y)
 {
@@ -158,7 +189,7 @@ struct TemporalPlan
 
 // the accumulation writes a, the variance b; pass i reads b (even i) / a (odd i) and writes the other, the last one `out`
 TemporalPlan temporal_plan(const filt::Temporal& c, const float4* col, const float4* alb, const float4* nz, const float4* prev_nz, const float4* hist_in,
-    const float4* mom_in, float4* hist_out, float4* mom_out, float4* a, float4* b, float4* out)
+    const float4* mom_in, float4* hist_out, float4* mom_out, float4* a, float4* b, float4* out, const float4* prev_pos, const float4* prev_n)
 {
     const rt_temporal_filter_desc& d = c.desc;
     const uint32_t demod = (d.flags & RT_FILTER_DEMODULATE) ? SF_DEMOD : 0u, divide = c.divide ? SF_DIVIDE : 0u;
@@ -170,6 +201,8 @@ TemporalPlan temporal_plan(const filt::Temporal& c, const float4* col, const flo
     p.A.tan_cam = rt_tanf(0.5f * c.cam.fov); p.A.tan_prev = rt_tanf(0.5f * c.prev.fov);
     p.A.width = c.width; p.A.height = c.height; p.A.mode = c.mode; p.A.flags = demod | divide; p.A.spp = c.spp;
     p.A.alpha_color = d.alpha_color; p.A.alpha_moments = d.alpha_moments;
+    const bool motion = prev_pos && prev_n;
+    p.A.prev_pos = motion ? (const sf_f4*)prev_pos : nullptr; p.A.prev_n = motion ? (const sf_f4*)prev_n : nullptr;
     const float inv_n = 1.0f / d.sigma_normal, inv_z = 1.0f / d.sigma_depth;
     p.V = {};
     p.V.acc = (const sf_f4*)a; p.V.mom = (const sf_f4*)mom_out; p.V.nz = (const sf_f4*)nz; p.V.out = (sf_f4*)b;
@@ -208,6 +241,68 @@ hipError_t guide_values(hipStream_t stream, const DScene& sc, const float4* o4, 
     return hipGetLastError();
 }
 
+hipError_t snapshot_pose(hipStream_t stream, const float4* tris_sh, uint32_t nt, float4* snap)
+{
+    if (nt == 0) return hipSuccess;
+    const size_t blocks = ((size_t)nt * 6u + 255u) / 256u;
+    if (blocks > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_sf_snapshot_pose, dim3((uint32_t)blocks), dim3(256), 0, stream, tris_sh, nt, snap);
+    return hipGetLastError();
+}
+
+hipError_t guide_motion(hipStream_t stream, const float4* snap, uint32_t nt, const float4* hits, uint32_t n, float4* prev_pos, float4* prev_n)
+{
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_sf_guide_motion, dim3((n + 255u) / 256u), dim3(256), 0, stream, snap, nt, hits, n, prev_pos, prev_n);
+    return hipGetLastError();
+}
+
+std::vector<float> pose_records(const rt_triangle* tris, uint32_t nt)
+{
+    std::vector<float> r((size_t)nt * 24, 0.0f);
+    for (uint32_t t = 0; t < nt; ++t)
+    {
+        const rt_vertex* v[3] = {&tris[t].v1, &tris[t].v2, &tris[t].v3};
+        float* q = r.data() + (size_t)t * 24;
+        for (int k = 0; k < 3; ++k)
+        {
+            q[4 * k] = v[k]->position.x; q[4 * k + 1] = v[k]->position.y; q[4 * k + 2] = v[k]->position.z;
+            q[12 + 4 * k] = v[k]->normal.x; q[12 + 4 * k + 1] = v[k]->normal.y; q[12 + 4 * k + 2] = v[k]->normal.z;
+        }
+    }
+    return r;
+}
+
+void guide_motion_host(const float* records, uint32_t nt, const float* hits, uint32_t n, float* prev_pos, float* prev_n)
+{
+    const std::vector<float4> rec = staged(records, (size_t)nt * 6);
+    for (uint32_t i = 0; i < n; ++i)
+    {
+        uint32_t prim;
+        memcpy(&prim, hits + 4 * (size_t)i + 2, sizeof(prim));
+        sf_f4 pos = {0.0f, 0.0f, 0.0f, 0.0f}, nrm = {0.0f, 0.0f, 0.0f, 0.0f};
+        if (prim < nt) tf_guide_motion((const sf_f4*)rec.data() + (size_t)prim * 6, hits[4 * (size_t)i], hits[4 * (size_t)i + 1], &pos, &nrm);
+        memcpy(prev_pos + 4 * (size_t)i, &pos, sizeof(pos));
+        memcpy(prev_n + 4 * (size_t)i, &nrm, sizeof(nrm));
+    }
+}
+
+hipError_t guide_motion_device(hipStream_t stream, const float* records, uint32_t nt, const float* hits, uint32_t n, float* prev_pos, float* prev_n)
+{
+    const size_t rb = std::max<size_t>((size_t)nt * 96, 16), pb = (size_t)n * sizeof(float4);
+    float4* d[4] = {nullptr, nullptr, nullptr, nullptr};            // records, hits, prev_pos, prev_n
+    hipError_t e = hipMalloc((void**)&d[0], rb);
+    for (int k = 1; k < 4 && e == hipSuccess; ++k) e = hipMalloc((void**)&d[k], pb);
+    if (e == hipSuccess && nt) e = hipMemcpyAsync(d[0], records, (size_t)nt * 96, hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d[1], hits, pb, hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess) e = guide_motion(stream, d[0], nt, d[1], n, d[2], d[3]);
+    if (e == hipSuccess) e = hipMemcpyAsync(prev_pos, d[2], pb, hipMemcpyDeviceToHost, stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(prev_n, d[3], pb, hipMemcpyDeviceToHost, stream);
+    const hipError_t es = hipStreamSynchronize(stream);
+    for (float4* b : d) if (b) (void)hipFree(b);
+    return e == hipSuccess ? es : e;
+}
+
 hipError_t spatial(hipStream_t stream, const Spatial& s, const float4* col, const float4* alb, const float4* nz, float4* ping, float4* pong, float4* out)
 {
     for (const SfPass& P : spatial_plan(s, col, alb, nz, ping, pong, out))
@@ -228,9 +323,10 @@ void spatial_host(const Spatial& s, const float* col, const float* alb, const fl
 }
 
 hipError_t temporal(hipStream_t stream, const Temporal& c, const float4* col, const float4* alb, const float4* nz, const float4* prev_nz,
-    const float4* hist_in, const float4* mom_in, float4* hist_out, float4* mom_out, float4* a, float4* b, float4* out)
+    const float4* hist_in, const float4* mom_in, float4* hist_out, float4* mom_out, float4* a, float4* b, float4* out, const float4* prev_pos,
+    const float4* prev_n)
 {
-    const TemporalPlan p = temporal_plan(c, col, alb, nz, prev_nz, hist_in, mom_in, hist_out, mom_out, a, b, out);
+    const TemporalPlan p = temporal_plan(c, col, alb, nz, prev_nz, hist_in, mom_in, hist_out, mom_out, a, b, out, prev_pos, prev_n);
     hipError_t e = launch_pixels(stream, k_tf_accumulate, p.A, c.width, c.height);
     if (e == hipSuccess && c.desc.iterations) e = launch_pixels(stream, k_tf_variance, p.V, c.width, c.height);
     for (size_t i = 0; i < p.passes.size() && e == hipSuccess; ++i) e = launch_pixels(stream, k_tf_pass, p.passes[i], c.width, c.height);
@@ -238,13 +334,14 @@ hipError_t temporal(hipStream_t stream, const Temporal& c, const float4* col, co
 }
 
 void temporal_host(const Temporal& c, const float* col, const float* alb, const float* nz, const float* prev_nz, const float* hist_in,
-    const float* mom_in, float* hist_out, float* mom_out, float* out)
+    const float* mom_in, float* hist_out, float* mom_out, float* out, const float* prev_pos, const float* prev_n)
 {
     const size_t n = (size_t)c.width * c.height;
+    const bool motion = prev_pos && prev_n;
     std::vector<float4> c0 = staged(col, n), al = staged(alb, n), g = staged(nz, n), pg = staged(prev_nz, n), hi = staged(hist_in, n),
-                        mi = staged(mom_in, n), ho(n), mo(n), a(n), b(n), res(n);
+                        mi = staged(mom_in, n), ho(n), mo(n), a(n), b(n), res(n), pp = staged(prev_pos, motion ? n : 0), pn = staged(prev_n, motion ? n : 0);
     const TemporalPlan p = temporal_plan(c, c0.data(), al.data(), g.data(), pg.data(), hi.data(), mi.data(), ho.data(), mo.data(), a.data(), b.data(),
-                                         res.data());
+                                         res.data(), motion ? pp.data() : nullptr, motion ? pn.data() : nullptr);
     host_pixels(c.width, c.height, [&](uint32_t x, uint32_t y) { tf_accumulate_pixel(p.A, x, y); });
     if (c.desc.iterations)
         host_pixels(c.width, c.height, [&](uint32_t x, uint32_t y) { p.V.out[(size_t)y * c.width + x] = tf_variance_pixel(p.V, x, y); });

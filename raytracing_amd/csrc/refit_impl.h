@@ -17,6 +17,17 @@ static void refit_arm(rt_ctx* ctx, const rt_scene_desc* sd, uint32_t n_pairs)
         refit::release(*s.refit); delete s.refit; s.refit = nullptr;
         s.refit_refusal = "the refit state could not be allocated at upload";
     }
+    if (!s.refit || !ctx->refit_motion) return;
+    // RT_CTX_OPT_REFIT_MOTION: room for the pose a refit replaces; without it the option is off for this scene
+    char line[200];
+    if (hipMalloc(&s.pose_snap, (size_t)s.n_tris * 96u) != hipSuccess)
+    {
+        (void)hipGetLastError();
+        s.pose_snap = nullptr;
+        snprintf(line, sizeof(line), "previous pose: could not be allocated at upload, RT_CTX_OPT_REFIT_MOTION is treated as off\n");
+    }
+    else snprintf(line, sizeof(line), "previous pose: RT_CTX_OPT_REFIT_MOTION keeps 96 bytes per triangle (%.1f MB)\n", (double)s.n_tris * 96.0 / 1e6);
+    s.tree_report += line;
 }
 
 // the 4-wide trees the scene holds NOW (an adaptation or rt_scene_import_folds may have replaced the records since the links were made)
@@ -50,6 +61,12 @@ static int refit_device(rt_ctx* ctx, const rt_triangle* d_tris, const char* who)
     // for -- and the records adapted so far stay in use
     const bool had_adapt = s.adapt != nullptr;
     if (s.adapt) { drop_fold_adapt(s.adapt); s.adapt = nullptr; (void)hipSetDevice(ctx->device); }
+    // RT_CTX_OPT_REFIT_MOTION: the pose about to be replaced, while the shading records still hold it
+    if (s.pose_snap)
+    {
+        s.pose_valid = false;
+        HIPCHK(ctx, filt::snapshot_pose(ctx->stream, (const float4*)s.tris_sh, s.n_tris, (float4*)s.pose_snap));
+    }
     const auto t0 = std::chrono::steady_clock::now();
     refit::Result res;
     if (!refit_link_trees(ctx) ||
@@ -65,13 +82,17 @@ static int refit_device(rt_ctx* ctx, const rt_triangle* d_tris, const char* who)
     s.wide_ok = s.refit_wide_built && !fallback;
     ++ctx->scene_uploads;                                                  // guide caches, temporal histories, measured choices: dropped as on upload
     ++s.refits;
+    ++ctx->refit_index;
+    s.pose_valid = s.pose_snap != nullptr;
     {
         const size_t at = s.tree_report.find("refit ");
         if (at != std::string::npos) s.tree_report.erase(at);
-        char line[400];
-        snprintf(line, sizeof(line), "refit %llu: %.3f ms on the device (%u triangles, %u child-pair records, %u + %u wide records, %.1f MB kept for it); %s; %s\n",
+        char pose[96] = "";
+        if (s.pose_snap) snprintf(pose, sizeof(pose), " + %.1f MB for the previous pose, 96 bytes per triangle", (double)s.n_tris * 96.0 / 1e6);
+        char line[500];
+        snprintf(line, sizeof(line), "refit %llu: %.3f ms on the device (%u triangles, %u child-pair records, %u + %u wide records, %.1f MB kept for it%s); %s; %s\n",
             (unsigned long long)s.refits, 1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(), s.n_tris, s.refit->n_pairs,
-            s.refit->trees[0].n, s.refit->trees[1].n, (double)s.refit->bytes / 1e6,
+            s.refit->trees[0].n, s.refit->trees[1].n, (double)s.refit->bytes / 1e6, pose,
             fallback ? "a 4-wide record no longer qualifies -> the BVH2 kernels until a refit qualifies again" : (s.refit_wide_built ? "the 4-wide trees qualify" : "no 4-wide tree"),
             had_adapt || s.adapt_retired ? "the fold adaptation is retired (the records adapted so far stay)" : "no fold adaptation");
         s.adapt_retired = s.adapt_retired || had_adapt;

@@ -65,6 +65,10 @@ struct Scene
     bool adapt_retired = false;      // a refit has retired the fold adaptation
     uint32_t n_materials = 0;
     uint64_t refits = 0;
+    // RT_CTX_OPT_REFIT_MOTION: the pose before the last refit, 6 float4 per triangle (filt::snapshot_pose); nullptr = the option was off at upload (or the
+    // allocation failed: treated as off).  pose_valid: a refit has filled it.
+    void* pose_snap = nullptr;
+    bool pose_valid = false;
 };
 } // namespace
 
@@ -92,7 +96,10 @@ struct rt_ctx
                                             // 2 (default) = both start, the device's is measured first and the host's build is abandoned if it wins its measurement
     uint32_t refittable = 0;                // RT_CTX_OPT_REFITTABLE: rt_scene_upload keeps what rt_scene_refit needs (refit.h)
     uint32_t device_fold = 1;               // RT_CTX_OPT_DEVICE_FOLD: the SAH collapse into 4-wide records runs on the device (fold_kernels.h); 0 = on host threads
+    uint32_t refit_motion = 0;              // RT_CTX_OPT_REFIT_MOTION: a refit keeps the pose it replaces, for the temporal filter (needs refittable)
     uint64_t scene_uploads = 0;             // rt_scene_upload calls so far (what a frame's measured choices were made for)
+    uint64_t upload_epoch = 0;              // changes on rt_scene_upload only; refit_index: the successful refits within it.  A temporal history made for
+    uint64_t refit_index = 0;               // (epoch, index - 1) can follow the geometry through the one pose the scene keeps (Scene::pose_snap)
     std::vector<rt_frame*> frames;   // the frames alive on this context (rt_finish waits for their side streams too)
     uint8_t* blue_noise = nullptr;   // sobol[65536] | scramblingTile[131072] | rankingTile[131072]
     float* gamma_lut = nullptr;      // pow(byte / 255, 2.2f), 256 entries (k_fill_gamma_lut)
@@ -263,6 +270,7 @@ struct rt_frame
     std::vector<hipEvent_t> event_pool;
     struct SfGuides* sf = nullptr;     // rt_frame_filter / rt_frame_read_guides: the guide pass's buffers and what they were made for (made on first use)
     struct TfState* tf = nullptr;      // rt_frame_filter_temporal: the history (made on first use)
+    struct SfMotion* sm = nullptr;     // RT_CTX_OPT_REFIT_MOTION: where each first hit was before the last refit (made on first use)
 };
 
 static int sync_frame_streams(rt_frame* f);
@@ -330,13 +338,30 @@ struct TfState
     float4* mom[2] = {nullptr, nullptr};
     float4* prev_nz = nullptr;
     uint32_t cur = 0;                                  // mom[cur] is the history
-    rt_camera prev_cam;                                // the previous call's camera and scene (rt_scene_upload count)
+    rt_camera prev_cam;                                // the previous call's camera and scene (rt_scene_upload count; upload epoch and refit index)
     uint64_t prev_scene = 0;
+    uint64_t prev_epoch = 0, prev_refit = 0;
     bool has_prev = false;                             // false: no call yet, or the history was dropped
     std::vector<DevBuf> buffers(size_t n = 0)
     {
         const size_t b = n * sizeof(float4);
         return {{(void**)&hist, b}, {(void**)&mom[0], b}, {(void**)&mom[1], b}, {(void**)&prev_nz, b}};
+    }
+};
+
+// RT_CTX_OPT_REFIT_MOTION on a frame (rt_frame_filter_temporal after a refit, rt_frame_read_guide_motion): per pixel where its first hit was in the pose
+// before the last refit and its normal there (filt::guide_motion over the guide pass's hits).  32 bytes per pixel, made on first use on a context that keeps
+// a pose, freed by rt_frame_destroy.
+struct SfMotion
+{
+    float4* prev_pos = nullptr; float4* prev_n = nullptr;
+    rt_camera camera;                                  // what the images were made for
+    uint64_t scene = 0;
+    bool valid = false;
+    std::vector<DevBuf> buffers(size_t n = 0)
+    {
+        const size_t b = n * sizeof(float4);
+        return {{(void**)&prev_pos, b}, {(void**)&prev_n, b}};
     }
 };
 
@@ -372,6 +397,7 @@ void free_scene(Scene& s)
     for (void* p : ptrs) if (p) (void)hipFree(p);
     if (s.adapt) drop_fold_adapt(s.adapt);
     if (s.refit) { refit::release(*s.refit); delete s.refit; }
+    if (s.pose_snap) (void)hipFree(s.pose_snap);
     s = Scene();
 }
 } // namespace
@@ -501,6 +527,7 @@ int rt_ctx_set_option(rt_ctx* ctx, int option, uint32_t value)
     if (option == RT_CTX_OPT_DEVICE_FOLD) { ctx->device_fold = value ? 1u : 0u; return RT_OK; }
     if (option == RT_CTX_OPT_WIDE_LAYOUT) { ctx->wide_layout = value ? 1u : 0u; return RT_OK; }
     if (option == RT_CTX_OPT_REFITTABLE) { ctx->refittable = value ? 1u : 0u; return RT_OK; }
+    if (option == RT_CTX_OPT_REFIT_MOTION) { ctx->refit_motion = value ? 1u : 0u; return RT_OK; }
     if (option == RT_CTX_OPT_TREE_BUILDER) { ctx->tree_builder = value > 2u ? 2u : value; return RT_OK; }
     if (option == RT_CTX_OPT_ADAPT_WAIT)
     {
@@ -603,6 +630,8 @@ int rt_scene_upload(rt_ctx* ctx, const rt_scene_desc* sd)
         if (sync_frame_streams(f) != RT_OK) return RT_ERROR;
     free_scene(ctx->scene);
     ++ctx->scene_uploads;
+    ++ctx->upload_epoch;
+    ctx->refit_index = 0;
     Scene& s = ctx->scene;
     const uint32_t nt = sd->num_triangles, nn = sd->num_nodes;
     const auto t_upload = std::chrono::steady_clock::now();
@@ -1400,6 +1429,7 @@ int rt_frame_destroy(rt_frame* f)
     for (auto e : f->event_pool) (void)hipEventDestroy(e);
     free_state(f->sf);
     free_state(f->tf);
+    free_state(f->sm);
     delete f;
     return RT_OK;
 }
@@ -2553,6 +2583,27 @@ static int ensure_guides(rt_frame* f, const char* who)
     return RT_OK;
 }
 
+// RT_CTX_OPT_REFIT_MOTION: the frame's motion images for its current camera and the context's current snapshot (which must exist); the guides first
+static int ensure_motion(rt_frame* f, const char* who)
+{
+    rt_ctx* ctx = f->ctx;
+    if (ensure_guides(f, who) != RT_OK) return RT_ERROR;
+    const size_t n = f->n_local;
+    if (!f->sm)
+    {
+        f->sm = alloc_state<SfMotion>(n);
+        if (!f->sm) return fail(ctx, std::string(who) + ": out of device memory for the motion images (32 bytes per pixel)");
+    }
+    SfMotion* m = f->sm;
+    if (m->valid && m->scene == ctx->scene_uploads && memcmp(&m->camera, &f->camera, sizeof(rt_camera)) == 0) return RT_OK;
+    m->valid = false;
+    HIPCHK(ctx, filt::guide_motion(ctx->stream, (const float4*)ctx->scene.pose_snap, ctx->scene.n_tris, f->sf->hits, (uint32_t)n, m->prev_pos, m->prev_n));
+    m->camera = f->camera;
+    m->scene = ctx->scene_uploads;
+    m->valid = true;
+    return RT_OK;
+}
+
 // the refusals both frame filters share after their descriptor's check: a tile frame, RT_OPT_AOV
 static int check_filter_call(rt_frame* f, const char* who)
 {
@@ -2699,16 +2750,23 @@ int rt_frame_filter_temporal(rt_frame* f, const rt_temporal_filter_desc* desc, f
     c.width = f->tile.width; c.height = f->tile.height;
     c.cam = f->camera;
     c.prev = t->has_prev ? t->prev_cam : f->camera;
-    c.mode = !t->has_prev || t->prev_scene != ctx->scene_uploads ? filt::NO_HISTORY
+    // what the history was made for against the scene now: the same upload and pose = as ever; the same upload, one refit on and the context kept the pose
+    // that refit replaced = followed through the motion images; anything else (another upload, two refits or more, no pose kept) = dropped
+    const bool same_upload = t->has_prev && t->prev_epoch == ctx->upload_epoch;
+    const bool follow = same_upload && t->prev_refit + 1u == ctx->refit_index && ctx->scene.pose_snap && ctx->scene.pose_valid;
+    if (follow && ensure_motion(f, who) != RT_OK) return RT_ERROR;
+    c.mode = follow ? filt::REPROJECT
+           : !same_upload || t->prev_refit != ctx->refit_index ? filt::NO_HISTORY
            : memcmp(&t->prev_cam, &f->camera, sizeof(rt_camera)) == 0 ? filt::IDENTITY : filt::REPROJECT;
     c.desc = *desc;
     c.divide = 1; c.spp = (float)f->sample_count; c.tonemap = 1;
     HIPCHK(ctx, filt::temporal(ctx->stream, c, f->radiance, g->alb, g->nz, t->prev_nz, t->hist, t->mom[t->cur], t->hist, t->mom[t->cur ^ 1u], g->o4,
-        g->d4, f->resolved));
+        g->d4, f->resolved, follow ? f->sm->prev_pos : nullptr, follow ? f->sm->prev_n : nullptr));
     t->cur ^= 1u;
     HIPCHK(ctx, hipMemcpyAsync(t->prev_nz, g->nz, n * sizeof(float4), hipMemcpyDeviceToDevice, ctx->stream));
     t->prev_cam = f->camera;
     t->prev_scene = ctx->scene_uploads;
+    t->prev_epoch = ctx->upload_epoch; t->prev_refit = ctx->refit_index;
     t->has_prev = true;
     return read_filtered(f, host_rgba);
 }
@@ -2745,16 +2803,66 @@ int rt_frame_read_filter_history(rt_frame* f, float* color_rgba, float* moments_
     return RT_OK;
 }
 
+int rt_frame_read_guide_motion(rt_frame* f, float* prev_position_rgba, float* prev_normal_rgba)
+{
+    static const char* who = "rt_frame_read_guide_motion";
+    if (!f) return fail(nullptr, "rt_frame_read_guide_motion: NULL argument");
+    rt_ctx* ctx = f->ctx;
+    (void)hipSetDevice(ctx->device);
+    if (check_filter_frame(f, who) != RT_OK) return RT_ERROR;
+    const size_t n = f->n_local;
+    if (n == 0) return RT_OK;
+    if (!ctx->scene.valid || !ctx->scene.pose_snap || !ctx->scene.pose_valid)           // no snapshot: no motion known anywhere
+    {
+        if (prev_position_rgba) memset(prev_position_rgba, 0, n * sizeof(float4));
+        if (prev_normal_rgba) memset(prev_normal_rgba, 0, n * sizeof(float4));
+        return RT_OK;
+    }
+    if (ensure_motion(f, who) != RT_OK) return RT_ERROR;
+    if (prev_position_rgba) HIPCHK(ctx, hipMemcpyAsync(prev_position_rgba, f->sm->prev_pos, n * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
+    if (prev_normal_rgba) HIPCHK(ctx, hipMemcpyAsync(prev_normal_rgba, f->sm->prev_n, n * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return RT_OK;
+}
+
+int rt_debug_guide_motion(rt_ctx* ctx, uint32_t n, const float* hits, const rt_triangle* prev_triangles, uint32_t num_triangles, float* out_position_rgba,
+    float* out_normal_rgba)
+{
+    if (!hits || (!prev_triangles && num_triangles) || !out_position_rgba || !out_normal_rgba) return fail(ctx, "rt_debug_guide_motion: NULL argument");
+    if (n == 0) return RT_OK;
+    const std::vector<float> records = filt::pose_records(prev_triangles, num_triangles);
+    if (!ctx)
+    {
+        filt::guide_motion_host(records.data(), num_triangles, hits, n, out_position_rgba, out_normal_rgba);
+        return RT_OK;
+    }
+    (void)hipSetDevice(ctx->device);
+    const hipError_t e = filt::guide_motion_device(ctx->stream, records.data(), num_triangles, hits, n, out_position_rgba, out_normal_rgba);
+    if (e != hipSuccess) { (void)hipGetLastError(); return fail(ctx, std::string("rt_debug_guide_motion: ") + hipGetErrorString(e)); }
+    return RT_OK;
+}
+
 int rt_debug_filter_temporal(rt_ctx* ctx, uint32_t width, uint32_t height, const rt_camera* cam, const rt_camera* prev_cam, const float* hdr_rgba,
     const float* albedo_rgba, const float* normal_rgba, const float* depth, const float* prev_normal_rgba, const float* prev_depth,
     const float* hist_color, const float* hist_moments, const rt_temporal_filter_desc* desc, float* out_hdr_rgba, float* hist_color_out,
     float* hist_moments_out)
 {
+    return rt_debug_filter_temporal_motion(ctx, width, height, cam, prev_cam, hdr_rgba, albedo_rgba, normal_rgba, depth, prev_normal_rgba, prev_depth, hist_color,
+        hist_moments, nullptr, nullptr, desc, out_hdr_rgba, hist_color_out, hist_moments_out);
+}
+
+int rt_debug_filter_temporal_motion(rt_ctx* ctx, uint32_t width, uint32_t height, const rt_camera* cam, const rt_camera* prev_cam, const float* hdr_rgba,
+    const float* albedo_rgba, const float* normal_rgba, const float* depth, const float* prev_normal_rgba, const float* prev_depth,
+    const float* hist_color, const float* hist_moments, const float* prev_position_rgba, const float* prev_pose_normal_rgba,
+    const rt_temporal_filter_desc* desc, float* out_hdr_rgba, float* hist_color_out, float* hist_moments_out)
+{
+    // (the messages name rt_debug_filter_temporal, the family: the entry without motion images is this one with two NULLs)
     static const char* who = "rt_debug_filter_temporal";
     if (!cam || !hdr_rgba || !albedo_rgba || !normal_rgba || !depth || !prev_normal_rgba || !prev_depth || !hist_color || !hist_moments || !desc ||
         !out_hdr_rgba || !hist_color_out || !hist_moments_out)
         return fail(ctx, "rt_debug_filter_temporal: NULL argument");
     if (width == 0 || height == 0) return fail(ctx, "rt_debug_filter_temporal: empty image");
+    const bool motion = prev_position_rgba && prev_pose_normal_rgba;
     if (check_temporal_desc(ctx, who, desc) != RT_OK) return RT_ERROR;
     const size_t n = (size_t)width * height;
     const std::vector<float> nz = pack_nz(normal_rgba, depth, n), pnz = pack_nz(prev_normal_rgba, prev_depth, n);
@@ -2762,14 +2870,20 @@ int rt_debug_filter_temporal(rt_ctx* ctx, uint32_t width, uint32_t height, const
     c.width = width; c.height = height;
     c.cam = *cam;
     c.prev = prev_cam ? *prev_cam : *cam;
-    c.mode = !prev_cam || memcmp(prev_cam, cam, sizeof(rt_camera)) == 0 ? filt::IDENTITY : filt::REPROJECT;
+    c.mode = !motion && (!prev_cam || memcmp(prev_cam, cam, sizeof(rt_camera)) == 0) ? filt::IDENTITY : filt::REPROJECT;
     c.desc = *desc;
     c.divide = 0; c.spp = 1.0f; c.tonemap = 0;
     if (!ctx)
     {
-        filt::temporal_host(c, hdr_rgba, albedo_rgba, nz.data(), pnz.data(), hist_color, hist_moments, hist_color_out, hist_moments_out, out_hdr_rgba);
+        filt::temporal_host(c, hdr_rgba, albedo_rgba, nz.data(), pnz.data(), hist_color, hist_moments, hist_color_out, hist_moments_out, out_hdr_rgba,
+            motion ? prev_position_rgba : nullptr, motion ? prev_pose_normal_rgba : nullptr);
         return RT_OK;
     }
+    // with motion images: hdr, albedo, nz, prev nz, hist in, moments in, prev position, prev pose normal, a, b, out, hist out, moments out
+    if (motion)
+        return debug_on_device(ctx, who, n, 13, {hdr_rgba, albedo_rgba, nz.data(), pnz.data(), hist_color, hist_moments, prev_position_rgba, prev_pose_normal_rgba},
+                               {out_hdr_rgba, hist_color_out, hist_moments_out},
+                               [&](float4** b) { return filt::temporal(ctx->stream, c, b[0], b[1], b[2], b[3], b[4], b[5], b[11], b[12], b[8], b[9], b[10], b[6], b[7]); });
     // images: hdr, albedo, nz, prev nz, hist in, moments in, a, b, out, hist out, moments out
     return debug_on_device(ctx, who, n, 11, {hdr_rgba, albedo_rgba, nz.data(), pnz.data(), hist_color, hist_moments},
                            {out_hdr_rgba, hist_color_out, hist_moments_out},

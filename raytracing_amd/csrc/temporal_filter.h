@@ -12,6 +12,10 @@
  *      |X - prev.position| and dot(n_p, n_prev,q) >= TF_NORMAL_MIN.  The counting weights are renormalised; no tap counts = a miss.
  *      TF_IDENTITY (same camera bytes, same scene): one tap, p itself, weight 1, counting iff its history length is > 0.
  *      TF_NO_HISTORY: every pixel misses.
+ *      Moved geometry (prev_pos / prev_n set: the first hit in the pose BEFORE the last refit, tf_guide_motion; only under TF_REPROJECT, also with a
+ *      standing camera): a pixel with prev_pos.w != 0 takes X = prev_pos.xyz instead of cam.position + z_p d_p, and its normal test reads
+ *      dot(prev_n, n_prev,q) >= TF_NORMAL_MIN.  Nothing else changes: the previous call's guides saw the previous pose, so |X - prev.position| against
+ *      z_prev,q compares like with like.  prev_pos.w == 0 (no motion known), or both images null: the rule above, bit for bit.
  *   2. accumulate: c_p demodulated, l = 0.2126 r + 0.7152 g + 0.0722 b.  Hit: L' = min(L_h + 1, TF_MAX_LEN) (L_h the largest length among
  *      the counting taps), alpha = max(alpha_color, 1 / L'), alpha_m = max(alpha_moments, 1 / L'); colour C_h + alpha (c_p - C_h), moments
  *      M_h + alpha_m ((l, l^2) - M_h); alpha == 1 takes c_p exactly (alpha_m == 1 (l, l^2) exactly).  Miss: L' = 1, c_p, (l, l^2).
@@ -57,6 +61,8 @@ struct TfAccum
     uint32_t mode;          /* TF_NO_HISTORY, TF_IDENTITY, TF_REPROJECT */
     uint32_t flags;         /* SF_DIVIDE, SF_DEMOD */
     float spp, alpha_color, alpha_moments;
+    const sf_f4* prev_pos;  /* moved geometry: where each first hit was before the last refit (xyz, w = 1; w = 0: no motion known), or null */
+    const sf_f4* prev_n;    /* ... and its unit normal there (w 0); null iff prev_pos is */
 };
 
 struct TfVar
@@ -109,6 +115,19 @@ RTD_FN int tf_project(const rt_camera& cam, float tan_half_fov, uint32_t width, 
     return 1;
 }
 
+/* where a first hit at barycentrics (bu, bv) was in another pose of its triangle: rec = that pose's three positions and three shading normals
+ * (the xyz of the shading record's q0 .. q5), interpolated in k_sf_guide_values' operand order.  pos = (X', 1), nrm = (n', 0). */
+RTD_FN void tf_guide_motion(const sf_f4* rec, float bu, float bv, sf_f4* pos, sf_f4* nrm)
+{
+    const sf_f4 p1 = rec[0], p2 = rec[1], p3 = rec[2], n1 = rec[3], n2 = rec[4], n3 = rec[5];
+    const float w0 = 1.0f - bu - bv;
+    pos->x = p1.x * w0 + p2.x * bu + p3.x * bv; pos->y = p1.y * w0 + p2.y * bu + p3.y * bv; pos->z = p1.z * w0 + p2.z * bu + p3.z * bv;
+    pos->w = 1.0f;
+    const float nx = n1.x * w0 + n2.x * bu + n3.x * bv, ny = n1.y * w0 + n2.y * bu + n3.y * bv, nz = n1.z * w0 + n2.z * bu + n3.z * bv;
+    const float l = __builtin_sqrtf(nx * nx + ny * ny + nz * nz);
+    nrm->x = nx / l; nrm->y = ny / l; nrm->z = nz / l; nrm->w = 0.0f;
+}
+
 /* steps 1 and 2 for pixel (x, y) */
 RTD_FN void tf_accumulate_pixel(const TfAccum& A, uint32_t x, uint32_t y)
 {
@@ -134,8 +153,24 @@ RTD_FN void tf_accumulate_pixel(const TfAccum& A, uint32_t x, uint32_t y)
     else if (A.mode == TF_REPROJECT)
     {
         float d[3], X[3];
-        sf_guide_dir(A.cam, A.tan_cam, A.width, A.height, x, y, d);
-        X[0] = A.cam.position.x + gp.w * d[0]; X[1] = A.cam.position.y + gp.w * d[1]; X[2] = A.cam.position.z + gp.w * d[2];
+        float npx = gp.x, npy = gp.y, npz = gp.z;              /* the normal the taps are tested against */
+        int moved = 0;
+        if (A.prev_pos)
+        {
+            const sf_f4 pp = A.prev_pos[i];
+            if (pp.w != 0.0f)
+            {
+                const sf_f4 pn = A.prev_n[i];
+                moved = 1;
+                X[0] = pp.x; X[1] = pp.y; X[2] = pp.z;
+                npx = pn.x; npy = pn.y; npz = pn.z;
+            }
+        }
+        if (!moved)
+        {
+            sf_guide_dir(A.cam, A.tan_cam, A.width, A.height, x, y, d);
+            X[0] = A.cam.position.x + gp.w * d[0]; X[1] = A.cam.position.y + gp.w * d[1]; X[2] = A.cam.position.z + gp.w * d[2];
+        }
         const float ex = X[0] - A.prev.position.x, ey = X[1] - A.prev.position.y, ez = X[2] - A.prev.position.z;
         const float dist = __builtin_sqrtf(ex * ex + ey * ey + ez * ez);
         float sx = 0.0f, sy = 0.0f;
@@ -156,7 +191,7 @@ RTD_FN void tf_accumulate_pixel(const TfAccum& A, uint32_t x, uint32_t y)
                 if (!(mq.z > 0.0f)) continue;
                 const sf_f4 gq = A.prev_nz[qi];
                 if (!(__builtin_fabsf(gq.w - dist) <= TF_DEPTH_TOL * dist)) continue;
-                if (!(tf_dot(gp.x, gp.y, gp.z, gq.x, gq.y, gq.z) >= TF_NORMAL_MIN)) continue;
+                if (!(tf_dot(npx, npy, npz, gq.x, gq.y, gq.z) >= TF_NORMAL_MIN)) continue;
                 const sf_f4 cq = A.hist[qi];
                 if (!hit) { hit = 1; ch = cq; mh = mq; }
                 sw = sw + bw;

@@ -24,7 +24,7 @@ EXPORTS = [
     "rth_render_ctx_handle", "rth_render_num_nodes", "rth_render_nodes", "rth_render_set_aov", "rth_render_resolve",
     "rth_render_set_blue_noise_path", "rth_render_reserve_samples", "rth_scene_save_cache", "rth_load_jpeg",
     "rth_render_upload_gpu_data", "rth_render_setup_seconds", "rth_render_create_with_options",
-    "rth_render_set_refittable", "rth_render_refit",
+    "rth_render_set_refittable", "rth_render_refit", "rth_render_set_refit_motion",
 ]
 
 
@@ -67,6 +67,7 @@ def load():
         "rth_render_read_resolved": (i32, [vp, vp]), "rth_render_stats": (i32, [vp, C.POINTER(rt_stats)]),
         "rth_render_frame_handle": (vp, [vp]), "rth_render_ctx_handle": (vp, [vp]), "rth_render_upload_gpu_data": (i32, [vp]),
         "rth_render_set_refittable": (i32, [vp, i32]), "rth_render_refit": (i32, [vp, vp, u32]),
+        "rth_render_set_refit_motion": (i32, [vp, i32]),
         "rth_render_num_nodes": (u32, [vp]), "rth_render_nodes": (vp, [vp]),
         "rth_render_set_aov": (i32, [vp, i32]), "rth_render_resolve": (i32, [vp, vp]),
         "rth_render_set_blue_noise_path": (i32, [vp, cp]),
@@ -296,6 +297,11 @@ class Render:
     def set_refittable(self, on=True):
         """RT_CTX_OPT_REFITTABLE, then the scene is uploaded again: what refit() needs is kept on the device (about 34 bytes per triangle)"""
         self._c(self.lib.rth_render_set_refittable(self.handle, int(on)))
+
+    def set_refit_motion(self, on=True):
+        """RT_CTX_OPT_REFIT_MOTION (after set_refittable), then the scene is uploaded again: every refit() keeps the pose it replaces (96 bytes per
+        triangle) and, with set_temporal_filter on, the next resolve filters with the history followed across the move instead of dropped"""
+        self._c(self.lib.rth_render_set_refit_motion(self.handle, int(on)))
 
     def refit(self, triangles):
         """The scene's triangles moved (types.triangle[], the count and BVH order of scene_arrays()['triangles']): every tree is refitted on the device

@@ -143,6 +143,13 @@ void HIPPathTraceIntegrator::UploadGPUData(Scene const& scene, AccelerationStruc
 void HIPPathTraceIntegrator::SetRefittable(bool on)
 {
     Check(rt_ctx_set_option(context_.Get(), RT_CTX_OPT_REFITTABLE, on ? 1u : 0u));
+    refittable_ = on;
+}
+
+void HIPPathTraceIntegrator::SetRefitMotion(bool on)
+{
+    if (on && !refittable_) throw HIPException("SetRefitMotion: SetRefittable(true) first (RT_CTX_OPT_REFIT_MOTION needs RT_CTX_OPT_REFITTABLE)");
+    Check(rt_ctx_set_option(context_.Get(), RT_CTX_OPT_REFIT_MOTION, on ? 1u : 0u));
 }
 
 void HIPPathTraceIntegrator::RefitGeometry(Triangle const* triangles, std::size_t count)

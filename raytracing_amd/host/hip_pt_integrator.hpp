@@ -92,6 +92,10 @@ public:
     // where UploadGPUData takes a third of a second or more; requests a reset, since the accumulated samples show the old pose.
     void SetRefittable(bool on);
     void RefitGeometry(Triangle const* triangles, std::size_t count);
+    // RT_CTX_OPT_REFIT_MOTION: every refit keeps the pose it replaces (96 bytes per triangle), and with SetTemporalFilter on the
+    // next ResolveRadiance() after a RefitGeometry filters with the history followed across the move instead of dropped.  Effective at the next
+    // UploadGPUData; throws unless SetRefittable(true) came first.  One pose deep: resolve once per refit.
+    void SetRefitMotion(bool on);
     rt_frame* GetFrame() const { return frame_; }
 
 protected:
@@ -126,5 +130,6 @@ private:
     rt_temporal_filter_desc temporal_ = RT_TEMPORAL_FILTER_DESC_DEFAULT;
     std::uint32_t tile_count_ = 1;
     std::string blue_noise_path_ = "assets/blue_noise/heitz2019_256spp_256d.bin";
+    bool refittable_ = false;     // SetRefittable's last value (SetRefitMotion needs it)
 };
 } // namespace rt

@@ -235,6 +235,7 @@ const void* rth_render_nodes(void* r) { return ((rt::Render*)r)->GetAcceleration
 void* rth_render_frame_handle(void* r) { return ((rt::Render*)r)->GetIntegrator().GetFrame(); }
 void* rth_render_ctx_handle(void* r) { return ((rt::Render*)r)->GetContext().Get(); }
 int rth_render_set_refittable(void* r, int on) { return guard([&]() { ((rt::Render*)r)->SetRefittable(on != 0); return 0; }, 1); }
+int rth_render_set_refit_motion(void* r, int on) { return guard([&]() { ((rt::Render*)r)->SetRefitMotion(on != 0); return 0; }, 1); }
 int rth_render_refit(void* r, const void* triangles, uint32_t count) { return guard([&]() { ((rt::Render*)r)->RefitGeometry((const rt::Triangle*)triangles, count); return 0; }, 1); }
 int rth_render_upload_gpu_data(void* r) { return guard([&]() { ((rt::Render*)r)->UploadGPUData(); return 0; }, 1); }
 

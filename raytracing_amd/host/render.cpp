@@ -154,6 +154,12 @@ void TiledRender::SetRefittable(bool on)
     folds_shared_ = false;                                  // the uploads made their own folds again
 }
 
+void TiledRender::SetRefitMotion(bool on)
+{
+    for (auto& i : integrators_) { i->SetRefitMotion(on); i->UploadGPUData(scene_, *acc_structure_); }
+    folds_shared_ = false;
+}
+
 void TiledRender::RefitGeometry(Triangle const* triangles, std::size_t count)
 {
     for (auto& i : integrators_) i->RefitGeometry(triangles, count);

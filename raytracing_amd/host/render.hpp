@@ -34,6 +34,9 @@ public:
     // scene's count and BVH order: GetTriangles() of the finalised scene) and restarts the accumulation.  The host Scene object keeps the pose it was built for.
     void SetRefittable(bool on) { integrator_->SetRefittable(on); UploadGPUData(); }
     void RefitGeometry(Triangle const* triangles, std::size_t count) { integrator_->RefitGeometry(triangles, count); }
+    // ... and SetRefitMotion(true) (after SetRefittable(true)) uploads it again with room for the pose each refit replaces: the temporal filter then follows
+    // the moved surfaces across a RefitGeometry instead of dropping its history
+    void SetRefitMotion(bool on) { integrator_->SetRefitMotion(on); UploadGPUData(); }
     AccelerationStructure const& GetAccelerationStructure() const { return *acc_structure_; }
     std::uint32_t GetWidth() const { return width_; }
     std::uint32_t GetHeight() const { return height_; }
@@ -76,6 +79,8 @@ public:
     // Moving geometry, forwarded to every tile's context (the scene is replicated; folds imported from tile 0 refit like any other)
     void SetRefittable(bool on);
     void RefitGeometry(Triangle const* triangles, std::size_t count);
+    // forwarded too (the option only: the filters stay refused on tiles)
+    void SetRefitMotion(bool on);
     void RenderSamples(std::uint32_t n);                  // every tile, concurrently; returns when all are enqueued and finished
     std::vector<float> GatherRadiance(int root = 0);      // height x width x RGBA running sums, image order
     rt_stats GetStats() const;                            // ray counters summed over the tiles
