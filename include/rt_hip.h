@@ -331,7 +331,7 @@ enum rt_option
                                       radiance between two stages replays the recorded stages with the stage kernels first.  Same radiance and ray
                                       counters bit for bit.  Not with AOVs / the denoiser, the compact log, RT_SCENE_EMISSIVE_NEE or profiling
                                       (those samples take the stage kernels). */
-    , RT_OPT_SAMPLES_AHEAD = 26     /* 0 (default: off) / 1 (automatic depth: batches of ~16 M paths, i.e. 8 samples of a 1080p frame) / k = 2 .. 64 samples per batch;
+    , RT_OPT_SAMPLES_AHEAD = 26     /* 0 (default: off) / 1 (automatic depth: batches of ~32 M paths, i.e. 16 samples of a 1080p frame) / k = 2 .. 64 samples per batch;
                                       + 256: the two banks launch on a stream each (their batches overlap) instead of one after the other on one stream.
                                       The stage API -- the reference's frame-by-frame pattern, one Integrate() per frame at one sample per pixel,
                                       src/render.cpp:197 -- traces the NEXT samples of a standing camera ahead: after three samples without rt_reset the frame

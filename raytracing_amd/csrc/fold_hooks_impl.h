@@ -81,37 +81,34 @@ static int fold_adopt(rt_ctx* ctx)
     a->state = FoldAdapt::IDLE;
     a->finished.store(false);
     char line[720];
-    const size_t at = s.tree_report.find("adaptive fold");              // one line, the latest adaptation's
-    if (at != std::string::npos) s.tree_report.erase(at);
+    std::string text;                                                   // one entry, the latest adaptation's
     if (a->o.empty())
     {
-        s.tree_report += "adaptive fold: the probe frame brought no rays back -> the fold stays as it is\n";
+        text = "adaptive fold: the probe frame brought no rays back -> the fold stays as it is\n";
         a->state = FoldAdapt::OFF;
     }
     else if (a->upload_failed)
     {
         // the scene keeps the fold it has: a failed adaptation costs nothing but itself (and is not tried again)
-        s.tree_report += "adaptive fold: not adopted (device allocation or copy failed)\n";
+        text = "adaptive fold: not adopted (device allocation or copy failed)\n";
         a->state = FoldAdapt::OFF;
     }
     else
     {
-        const bool shared = s.d.wnodes_sh == s.d.wnodes;               // the shadow rays walk the closest-hit records
         if (a->ok)
         {
-            void* old = s.wnodes;
-            s.wnodes = a->new_cl;
-            s.d.wnodes = (const float4*)a->new_cl; s.d.w_entry_ref = a->entry; s.n_wide = (uint32_t)a->wide.size();
-            if (shared && !a->ok_sh) { s.wnodes_sh = old; a->roots_sh = a->roots; s.n_wide_sh = (uint32_t)a->roots.size(); }   // ... and keep walking the old ones (theirs now)
-            else if (old) a->retired.push_back(old);
+            const bool keep_old = s.shadow_shares_closest() && !a->ok_sh;
+            const WideTree old = s.replace_tree(TREE_REF, WideTree{a->new_cl, (uint32_t)a->wide.size(), a->entry});
+            if (keep_old) { (void)s.replace_tree(TREE_SHADOW, old); s.walk_trees(TREE_REF, TREE_SHADOW); a->roots_sh = a->roots; }   // the shadow rays keep walking the old records (theirs now)
+            else if (old.recs) a->retired.push_back(old.recs);
             a->roots.swap(a->roots_new);
             a->new_cl = nullptr;
         }
         if (a->ok_sh)
         {
-            if (s.wnodes_sh) a->retired.push_back(s.wnodes_sh);
-            s.wnodes_sh = a->new_sh;
-            s.d.wnodes_sh = (const float4*)a->new_sh; s.d.w_sh_entry_ref = a->entry_sh; s.n_wide_sh = (uint32_t)a->wide_sh.size();
+            const WideTree old = s.replace_tree(TREE_SHADOW, WideTree{a->new_sh, (uint32_t)a->wide_sh.size(), a->entry_sh});
+            if (old.recs) a->retired.push_back(old.recs);
+            s.walk_trees(TREE_REF, TREE_SHADOW);
             a->roots_sh.swap(a->roots_sh_new);
             if (a->rotations != 0) a->bvh2_sh.swap(a->bvh2_sh_new);          // the shadow rays' binary tree from now on
             a->new_sh = nullptr;
@@ -121,27 +118,28 @@ static int fold_adopt(rt_ctx* ctx)
             "shadow %.2f -> %.2f (%s); %.2f s on a worker thread (probe unpacked %.2f; closest-hit re-fold %.2f beside the shadow side's: plain re-fold %.2f, rotations %.2f = pointer form %.2f + ray lists %.2f + passes %.2f + linear layout %.2f, "
             "re-fold after them %.2f, occluder order %.2f; upload %.2f)\n", a->adaptations, a->o.size(), a->sh_o.size(), a->cost[0][0], a->cost[0][1], a->ok ? "adopted" : "kept",
             a->cost[1][0], a->cost[1][1], a->ok_sh ? "adopted" : "kept", a->seconds, a->stage_s[0], a->stage_s[1], a->stage_s[2], a->stage_s[3], a->rotate_s[0], a->rotate_s[1], a->rotate_s[2], a->rotate_s[3], a->stage_s[4], a->stage_s[5], a->stage_s[6]);
-        s.tree_report += line;
+        text = line;
         if (a->ok_sh && a->reordered != 0)
         {
-            s.tree_report.pop_back();
+            text.pop_back();
             snprintf(line, sizeof(line), "; %u shadow records' slots stored likeliest occluder first\n", a->reordered);
-            s.tree_report += line;
+            text += line;
         }
         if (a->ok_sh && a->rotations != 0)
         {
-            s.tree_report.pop_back();
+            text.pop_back();
             snprintf(line, sizeof(line), "; the shadow rays' binary tree rotated for the probe rays' crossings first (%u rotations)\n", a->rotations);
-            s.tree_report += line;
+            text += line;
         }
         const uint64_t truncated = truncated_walks_exchange();
         if (truncated != 0)
         {
-            s.tree_report.pop_back();
+            text.pop_back();
             snprintf(line, sizeof(line), "; %llu host walks met a subtree deeper than their 126-entry stack (weights only)\n", (unsigned long long)truncated);
-            s.tree_report += line;
+            text += line;
         }
     }
+    replace_report_line(s.tree_report, "adaptive fold", text);
     // the rays and the records have served; the binary trees stay for the next camera
     for (auto* v : {&a->o, &a->d, &a->sh_o, &a->sh_d}) std::vector<float4>().swap(*v);
     for (auto* v : {&a->wide, &a->wide_sh}) std::vector<WideNode>().swap(*v);
@@ -186,9 +184,7 @@ static int fold_adapt_hook(rt_frame* f)
         if (fold_probe_enqueue(f, *a) != RT_OK)
         {
             a->state = FoldAdapt::OFF;
-            const size_t at = s.tree_report.find("adaptive fold");
-            if (at != std::string::npos) s.tree_report.erase(at);
-            s.tree_report += "adaptive fold: the probe frame failed (" + f->ctx->error + ") -> the fold stays as it is\n";
+            replace_report_line(s.tree_report, "adaptive fold", "adaptive fold: the probe frame failed (" + f->ctx->error + ") -> the fold stays as it is\n");
             return RT_OK;
         }
         a->state = FoldAdapt::PROBING;
@@ -226,18 +222,18 @@ int rt_scene_export_folds(rt_ctx* ctx, void* closest_records, void* shadow_recor
 {
     if (!ctx || !n_closest || !n_shadow) return fail(ctx, "rt_scene_export_folds: NULL argument");
     Scene& s = ctx->scene;
-    if (!s.valid || !s.wide_ok || !s.wnodes) return fail(ctx, "rt_scene_export_folds: the scene has no 4-wide tree");
+    if (!s.valid || !s.wide_ok || !s.trees[TREE_REF].recs) return fail(ctx, "rt_scene_export_folds: the scene has no 4-wide tree");
     (void)hipSetDevice(ctx->device);
-    const bool own_shadow = s.d.wnodes_sh != s.d.wnodes && s.wnodes_sh != nullptr;
-    const uint32_t n_cl = s.wnodes_cl != nullptr && s.d.wnodes == (const float4*)s.wnodes_cl ? s.n_wide_cl : s.n_wide;   // (tolerance mode: the closest-hit rays walk wnodes_cl)
+    const bool own_shadow = s.shadow == TREE_SHADOW;
+    const uint32_t n_cl = s.closest_tree().n;                                                 // (tolerance mode: the closest-hit rays' own tree)
     *n_closest = n_cl;
-    *n_shadow = own_shadow ? s.n_wide_sh : 0u;
+    *n_shadow = own_shadow ? s.shadow_tree().n : 0u;
     if (entries2) { entries2[0] = s.d.w_entry_ref; entries2[1] = s.d.w_sh_entry_ref; }
     if (!closest_records) return RT_OK;                                                       // size query
     if (n_cl > capacity || *n_shadow > capacity) return fail(ctx, "rt_scene_export_folds: capacity too small");
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     HIPCHK(ctx, hipMemcpy(closest_records, s.d.wnodes, (size_t)n_cl * sizeof(WideNode), hipMemcpyDeviceToHost));
-    if (own_shadow && shadow_records) HIPCHK(ctx, hipMemcpy(shadow_records, s.d.wnodes_sh, (size_t)s.n_wide_sh * sizeof(WideNode), hipMemcpyDeviceToHost));
+    if (own_shadow && shadow_records) HIPCHK(ctx, hipMemcpy(shadow_records, s.d.wnodes_sh, (size_t)s.shadow_tree().n * sizeof(WideNode), hipMemcpyDeviceToHost));
     return RT_OK;
 }
 
@@ -265,27 +261,21 @@ int rt_scene_import_folds(rt_ctx* ctx, const void* closest_records, uint32_t n_c
     if (!sane((const WideNode*)closest_records, n_closest, entry_closest)) return fail(ctx, "rt_scene_import_folds: the closest-hit records do not fit this scene (a ref outside the records / the triangles)");
     if (n_shadow && (!shadow_records || !sane((const WideNode*)shadow_records, n_shadow, entry_shadow))) return fail(ctx, "rt_scene_import_folds: the shadow records do not fit this scene");
     // nothing in flight may still read the records that go: batches traced ahead are dropped, every stream drains, an adaptation of this context's own is abandoned
-    for (rt_frame* f : ctx->frames) ahead_discard(f);
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    for (rt_frame* f : ctx->frames)
-        if (sync_frame_streams(f) != RT_OK) return RT_ERROR;
+    if (quiesce(ctx) != RT_OK) return RT_ERROR;
     if (s.adapt) { drop_fold_adapt(s.adapt); s.adapt = nullptr; }
-    void *cl = nullptr, *sh = nullptr;
-    int rc = dev_alloc_copy(ctx, &cl, closest_records, (size_t)n_closest * sizeof(WideNode));
-    if (rc == RT_OK && n_shadow) rc = dev_alloc_copy(ctx, &sh, shadow_records, (size_t)n_shadow * sizeof(WideNode));
+    DevMem cl, sh;
+    int rc = dev_alloc_copy(ctx, &cl.p, closest_records, (size_t)n_closest * sizeof(WideNode));
+    if (rc == RT_OK && n_shadow) rc = dev_alloc_copy(ctx, &sh.p, shadow_records, (size_t)n_shadow * sizeof(WideNode));
     if (rc == RT_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = fail(ctx, "rt_scene_import_folds: upload failed");
-    if (rc != RT_OK) { if (cl) (void)hipFree(cl); if (sh) (void)hipFree(sh); (void)hipGetLastError(); return RT_ERROR; }
-    const bool closest_is_own = s.wnodes_cl != nullptr && s.d.wnodes == (const float4*)s.wnodes_cl;      // (tolerance mode: the closest-hit rays walk wnodes_cl)
-    if (closest_is_own) { (void)hipFree(s.wnodes_cl); s.wnodes_cl = cl; s.n_wide_cl = n_closest; }
-    else { if (s.wnodes) (void)hipFree(s.wnodes); s.wnodes = cl; s.n_wide = n_closest; }
-    s.d.wnodes = (const float4*)cl; s.d.w_entry_ref = entry_closest;
-    if (s.wnodes_sh) { (void)hipFree(s.wnodes_sh); s.wnodes_sh = nullptr; s.n_wide_sh = 0; }
-    if (n_shadow) { s.wnodes_sh = sh; s.n_wide_sh = n_shadow; s.d.wnodes_sh = (const float4*)sh; s.d.w_sh_entry_ref = entry_shadow; }
-    else { s.d.wnodes_sh = s.d.wnodes; s.d.w_sh_entry_ref = s.d.w_entry_ref; }
+    if (rc != RT_OK) { (void)hipGetLastError(); return RT_ERROR; }
+    // the tree the closest-hit rays walk (their own in the tolerance mode) and the shadow rays' own are replaced; without shadow records the shadow rays
+    // walk what the closest-hit rays walk
+    DevMem old_cl, old_sh;
+    old_cl.p = s.replace_tree(s.closest, WideTree{cl.release(), n_closest, entry_closest}).recs;
+    old_sh.p = s.replace_tree(TREE_SHADOW, WideTree{sh.release(), n_shadow, entry_shadow}).recs;
+    s.walk_trees(s.closest, n_shadow ? TREE_SHADOW : s.closest);
     char line[200];
-    const size_t at = s.tree_report.find("imported folds");
-    if (at != std::string::npos) s.tree_report.erase(at);
     snprintf(line, sizeof(line), "imported folds: %u closest-hit + %u shadow records taken from another context of the group; this context's own adaptation is off\n", n_closest, n_shadow);
-    s.tree_report += line;
+    replace_report_line(s.tree_report, "imported folds", line);
     return RT_OK;
 }

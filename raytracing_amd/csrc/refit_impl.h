@@ -34,10 +34,11 @@ static void refit_arm(rt_ctx* ctx, const rt_scene_desc* sd, uint32_t n_pairs)
 static bool refit_link_trees(rt_ctx* ctx)
 {
     Scene& s = ctx->scene;
-    const bool wide = s.refit_wide_built && s.wnodes && s.n_wide != 0u;
-    const bool own_sh = wide && s.wnodes_sh && s.n_wide_sh != 0u && s.d.wnodes_sh == (const float4*)s.wnodes_sh;
-    return refit::link_tree(ctx->stream, *s.refit, 0, wide ? (WideNode*)s.wnodes : nullptr, s.n_wide, s.d.w_entry_ref) &&
-           refit::link_tree(ctx->stream, *s.refit, 1, own_sh ? (WideNode*)s.wnodes_sh : nullptr, s.n_wide_sh, s.d.w_sh_entry_ref);
+    const WideTree &ref = s.trees[TREE_REF], &sh = s.trees[TREE_SHADOW];
+    const bool wide = s.refit_wide_built && ref.recs && ref.n != 0u;
+    const bool own_sh = wide && s.shadow == TREE_SHADOW && sh.recs && sh.n != 0u;           // tree 1: only records of the shadow rays' own
+    return refit::link_tree(ctx->stream, *s.refit, 0, wide ? (WideNode*)ref.recs : nullptr, ref.n, s.d.w_entry_ref) &&
+           refit::link_tree(ctx->stream, *s.refit, 1, own_sh ? (WideNode*)sh.recs : nullptr, sh.n, s.d.w_sh_entry_ref);
 }
 
 static int refit_device(rt_ctx* ctx, const rt_triangle* d_tris, const char* who)
@@ -52,11 +53,7 @@ static int refit_device(rt_ctx* ctx, const rt_triangle* d_tris, const char* who)
     case refit::BAD_MATERIAL: return fail(ctx, name + ": material index out of range");
     default: (void)hipGetLastError(); return fail(ctx, name + ": the validation kernel failed");
     }
-    // nothing may still read what is about to be rewritten: exactly rt_scene_upload's quiescence
-    for (rt_frame* f : ctx->frames) ahead_discard(f);
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    for (rt_frame* f : ctx->frames)
-        if (sync_frame_streams(f) != RT_OK) return RT_ERROR;
+    if (quiesce(ctx) != RT_OK) return RT_ERROR;                            // nothing may still read what is about to be rewritten
     // an adaptation's host copies (the binary trees, the triangles' corners) are stale from here on: it is retired -- one in flight is cancelled and waited
     // for -- and the records adapted so far stay in use
     const bool had_adapt = s.adapt != nullptr;
@@ -85,8 +82,6 @@ static int refit_device(rt_ctx* ctx, const rt_triangle* d_tris, const char* who)
     ++ctx->refit_index;
     s.pose_valid = s.pose_snap != nullptr;
     {
-        const size_t at = s.tree_report.find("refit ");
-        if (at != std::string::npos) s.tree_report.erase(at);
         char pose[96] = "";
         if (s.pose_snap) snprintf(pose, sizeof(pose), " + %.1f MB for the previous pose, 96 bytes per triangle", (double)s.n_tris * 96.0 / 1e6);
         char line[500];
@@ -96,7 +91,7 @@ static int refit_device(rt_ctx* ctx, const rt_triangle* d_tris, const char* who)
             fallback ? "a 4-wide record no longer qualifies -> the BVH2 kernels until a refit qualifies again" : (s.refit_wide_built ? "the 4-wide trees qualify" : "no 4-wide tree"),
             had_adapt || s.adapt_retired ? "the fold adaptation is retired (the records adapted so far stay)" : "no fold adaptation");
         s.adapt_retired = s.adapt_retired || had_adapt;
-        s.tree_report += line;
+        replace_report_line(s.tree_report, "refit ", line);
     }
     return RT_OK;
 }
@@ -107,7 +102,7 @@ static int refit_refused(rt_ctx* ctx, const char* who, uint64_t count_or_bytes, 
     Scene& s = ctx->scene;
     if (!ctx->scene.valid) return fail(ctx, name + ": no scene");
     if (!s.refit) return fail(ctx, name + (s.refit_refusal.empty() ? ": RT_CTX_OPT_REFITTABLE was off when the scene was uploaded" : ": " + s.refit_refusal));
-    if (ctx->closest_tree != 0u || s.wnodes_cl) return fail(ctx, name + ": not in the tolerance mode (RT_CTX_OPT_CLOSEST_TREE != 0)");
+    if (ctx->closest_tree != 0u || s.trees[TREE_CLOSEST].recs) return fail(ctx, name + ": not in the tolerance mode (RT_CTX_OPT_CLOSEST_TREE != 0)");
     if (bytes ? count_or_bytes != (uint64_t)s.n_tris * sizeof(rt_triangle) : count_or_bytes != s.n_tris)
         return fail(ctx, name + ": the triangle count differs from the uploaded scene's");
     return RT_OK;
@@ -127,11 +122,10 @@ int rt_scene_refit(rt_ctx* ctx, const rt_triangle* triangles, uint32_t num_trian
     if (!ctx || !triangles) return fail(ctx, "rt_scene_refit: NULL argument");
     if (refit_refused(ctx, "rt_scene_refit", num_triangles, false) != RT_OK) return RT_ERROR;
     (void)hipSetDevice(ctx->device);
-    void* d_tris = nullptr;
-    if (dev_alloc_copy(ctx, &d_tris, triangles, (size_t)num_triangles * sizeof(rt_triangle)) != RT_OK) { if (d_tris) (void)hipFree(d_tris); return RT_ERROR; }
-    const int rc = refit_device(ctx, (const rt_triangle*)d_tris, "rt_scene_refit");
+    DevMem d_tris;
+    if (dev_alloc_copy(ctx, &d_tris.p, triangles, (size_t)num_triangles * sizeof(rt_triangle)) != RT_OK) return RT_ERROR;
+    const int rc = refit_device(ctx, (const rt_triangle*)d_tris.p, "rt_scene_refit");
     (void)hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d_tris);
     return rc;
 }
 
