@@ -353,7 +353,7 @@ enum rt_option
                                        launch (RT_OPT_SMALL_LAUNCH_PATHS).  0 in a field = its default.
                                        Results are identical for every value. */
 };
-int rt_set_option(rt_frame* frame, int option, uint32_t value);
+int rt_set_option(rt_frame* frame, int option, uint32_t value);    /* a value out of range is refused before anything is launched or waited for */
 int rt_set_camera(rt_frame* frame, const rt_camera* camera);       /* SetCameraData, cl_pt_integrator.cpp:365-371 */
 
 /* ---- stages: the protected virtuals Integrator::Integrate() schedules

@@ -5,6 +5,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <assert.h>
 #include <math.h>
 #include <cmath>
 #include <algorithm>
@@ -14,6 +15,7 @@
 #include <thread>
 #include <atomic>
 #include <array>
+#include <functional>
 #include "rt_hip.h"
 #include "kernels.h"
 #include "own_bvh.h"
@@ -127,6 +129,36 @@ struct rt_buffer
     size_t bytes;
 };
 
+// An owner's device buffers: each one's address and size (clear: it starts from zero).  An owner lists them once (buffers()), for the allocation and for the free.
+struct DevBuf { void** p; size_t bytes; bool clear = false; };
+static size_t total_bytes(const std::vector<DevBuf>& bufs) { size_t n = 0; for (const DevBuf& b : bufs) n += b.bytes; return n; }
+static void free_buffers(const std::vector<DevBuf>& bufs)
+{
+    for (const DevBuf& b : bufs) if (*b.p) { (void)hipFree(*b.p); *b.p = nullptr; }
+}
+// a new state S with every buffer of s->buffers(sizes...) allocated, or nullptr with everything freed again if one allocation fails
+template <class S, class... Sizes> static S* alloc_state(Sizes... sizes)
+{
+    S* s = new S();
+    const std::vector<DevBuf> bufs = s->buffers(sizes...);
+    for (const DevBuf& b : bufs)
+        if (hipMalloc(b.p, b.bytes) != hipSuccess)
+        {
+            (void)hipGetLastError();
+            free_buffers(bufs);
+            delete s;
+            return nullptr;
+        }
+    return s;
+}
+template <class S> static void free_state(S*& s)
+{
+    if (!s) return;
+    free_buffers(s->buffers());
+    delete s;
+    s = nullptr;
+}
+
 #define RT_MAX_PIPES 4
 // Per-path state of one chunk in flight and the stream its launches go to (see rt_frame::ps).
 struct PathPipe
@@ -158,7 +190,29 @@ struct PathPipe
     uint32_t prev_bounces = 0;
     uint32_t fold_accumulates = 0;     // the sequence in flight is a 2nd+ chunk of its batch: its counters ADD to last_*
     bool shadow_pending = false;       // rt_shade issued, rt_intersect_shadow not yet
+    // The per-path buffers for `paths` paths in flight and a log of `log_elems` entries, in the order they are allocated (alloc_path_buffers /
+    // free_path_buffers; no arguments: all of them, for the free).  The queues carry 4 elements of padding, the slow lists 64, the log 16 bytes;
+    // ovf_slot exists in the compact layout only.  RT_PATH_FIXED_BYTES is this list without the log and ovf_slot, per path.
+    std::vector<DevBuf> buffers(size_t paths = 0, size_t log_elems = 0, bool compact = true)
+    {
+        const size_t q = (paths + 4) * sizeof(float4), w = (paths + 4) * sizeof(uint32_t), slow = (paths + 64) * sizeof(uint32_t);
+        std::vector<DevBuf> b = {{(void**)&o4[0], q}, {(void**)&o4[1], q}, {(void**)&d4[0], q}, {(void**)&d4[1], q}, {(void**)&thr[0], q}, {(void**)&thr[1], q},
+            {(void**)&hits, q}, {(void**)&sh_o4[0], q}, {(void**)&sh_d4[0], q}, {(void**)&sh_o4[1], q}, {(void**)&sh_d4[1], q}, {(void**)&sh_aux[0], w},
+            {(void**)&sh_aux[1], w}, {(void**)&rlog, log_elems * 3u * sizeof(float) + 16u}};
+        if (compact) b.push_back({(void**)&ovf_slot, w});
+        b.insert(b.end(), {DevBuf{(void**)&cnt, paths * sizeof(uint32_t)}, DevBuf{(void**)&slow_list, slow}, DevBuf{(void**)&sh_slow_list, slow}});
+        return b;
+    }
+    // what a pipe keeps for the frame's life (ensure_pipe_resources); its streams have drained.  Pipe 0's stream is borrowed: never destroyed.
+    void destroy(bool own_stream)
+    {
+        for (void* m : {(void*)counters, (void*)spill, (void*)sh_spill}) if (m) (void)hipFree(m);
+        for (hipEvent_t e : {done, ev_shaded, ev_shadow[0], ev_shadow[1]}) if (e) (void)hipEventDestroy(e);
+        if (side) (void)hipStreamDestroy(side);
+        if (own_stream && stream) (void)hipStreamDestroy(stream);
+    }
 };
+#define RT_PATH_FIXED_BYTES (11u * 16u + 5u * 4u)   // ray queues o4, d4, thr (x2), hits, shadow queue o4, d4 (x2) = 11 x 16; sh_aux (x2), cnt, two slow lists = 5 x 4
 
 // RT_OPT_SAMPLES_AHEAD: samples of the stage API traced ahead of the caller's Integrate() calls (below, "samples ahead").  A BANK is a frame of its
 // own -- same tile, same options, its own per-path buffers -- that holds one batch; two banks, so that one computes while the other is consumed.
@@ -169,6 +223,14 @@ struct AheadBank
     hipEvent_t done = nullptr;              // the batch's last launch (the bank's stream, after its side stream has been joined)
     hipEvent_t order = nullptr;             // what the bank's stream waits for before it starts another batch: the owner's last replay of the old one
 };
+// what a bank is made for: a change in any of the sixteen makes the banks over (ahead_key / ahead_configure, samples_ahead_impl.h)
+struct AheadKey
+{
+    uint32_t followed[12] = {};             // the options of RT_AHEAD_FOLLOWED, in its order
+    uint32_t small_launch = 0, tail_paths = 0;   // RT_OPT_SMALL_LAUNCH_PATHS (unset: 0xFFFFFFFF), RT_OPT_TRACE_TAIL_PATHS
+    uint32_t depth = 0;                     // samples per batch (ahead_depth)
+    uint32_t two_streams = 0;               // RT_OPT_SAMPLES_AHEAD + 256: one stream per bank
+};
 struct Ahead
 {
     AheadBank bank[2];
@@ -176,7 +238,7 @@ struct Ahead
     uint32_t quiet = 0;                     // samples advanced since the last reset / discard
     uint32_t depth = 0, last_n = 0;         // the most samples a batch holds (resolved for this tile); the latest batch's size (the ramp: 2, 4, .. depth)
     bool configured = false;
-    uint32_t mirrored[16] = {};             // the owner's options as the banks have them
+    AheadKey mirrored;                      // the owner's options as the banks have them
     rt_camera camera;                       // what the batches in flight were traced for
     uint64_t scene = 0;
     uint64_t launched = 0, consumed = 0, discarded = 0;   // samples
@@ -187,7 +249,7 @@ struct rt_frame
     rt_ctx* ctx;
     DTile tile;
     uint32_t n_local;
-    float4* radiance; float4* resolved;
+    float4* radiance = nullptr; float4* resolved = nullptr;
     // rt_frame_present: the resolved image goes to the host on a stream of its own while the next frame is traced
     float4* resolved_b = nullptr;      // the second device image (double buffering)
     hipStream_t present_stream = nullptr;
@@ -214,9 +276,19 @@ struct rt_frame
     uint32_t ahead_opt = 0;            // RT_OPT_SAMPLES_AHEAD
     Ahead* ahead = nullptr;            // ... its banks (made when the first batch is launched)
     rt_frame* ahead_owner = nullptr;   // this frame IS a bank of that frame
-    uint32_t* frame_counts = nullptr; uint32_t* frame_slow = nullptr;              // k_frame's per-wave rows and slow-ray lists
-    uint2* frame_spill = nullptr;                                                  // ... and its blocks' stack spill area
-    uint32_t frame_blocks = 0, frame_chunks_per_wave = 0;
+    struct KFrame                      // k_frame's grid and its buffers, all three or none (blocks != 0: they exist)
+    {
+        uint32_t* counts = nullptr; uint32_t* slow = nullptr;                      // per-wave rows and slow-ray lists
+        uint2* spill = nullptr;                                                    // ... and its blocks' stack spill area
+        uint32_t blocks = 0;
+        std::vector<DevBuf> buffers(size_t n_blocks = 0, size_t chunks_per_wave = 0)
+        {
+            return {{(void**)&counts, n_blocks * RT_FRAME_COUNT_STRIDE * sizeof(uint32_t)}, {(void**)&slow, n_blocks * chunks_per_wave * 64u * sizeof(uint32_t)},
+                    {(void**)&spill, n_blocks * 64u * (RT_W4_STACK_MAX - 12) * sizeof(uint2)}};
+        }
+        void release() { free_buffers(buffers()); blocks = 0; }
+    } kf;
+    uint32_t frame_chunks_per_wave = 0;
     uint64_t frame_launches = 0;                                                   // samples rendered by k_frame so far (rt_stats)
     // RT_OPT_FRAME_KERNEL = 255: the choice is MEASURED -- k_frame wins by 1.4 - 1.8 x on scenes of up to ~1 M triangles and loses 7 - 10 % on the 2.8 M /
     // 10 M ones (profiles/r05_call13.log), so the first frames of a scene time both: frames 0 - 1 (stage kernels) and 2 - 3 (k_frame) warm up, frames 4 - 19
@@ -286,6 +358,13 @@ struct rt_frame
     struct SfGuides* sf = nullptr;     // rt_frame_filter / rt_frame_read_guides: the guide pass's buffers and what they were made for (made on first use)
     struct TfState* tf = nullptr;      // rt_frame_filter_temporal: the history (made on first use)
     struct SfMotion* sm = nullptr;     // RT_CTX_OPT_REFIT_MOTION: where each first hit was before the last refit (made on first use)
+    // the images a frame is made with, n pixels each (the radiance and the resolved image are written before they are read: rt_reset, rt_frame_resolve)
+    std::vector<DevBuf> images(size_t n = 0)
+    {
+        return {{(void**)&radiance, n * sizeof(float4)}, {(void**)&resolved, n * sizeof(float4)}, {(void**)&aov_buf.diffuse_albedo, n * sizeof(float4), true},
+                {(void**)&aov_buf.depth, n * sizeof(float), true}, {(void**)&aov_buf.normal, n * sizeof(float4), true}, {(void**)&aov_buf.velocity, n * sizeof(float2), true},
+                {(void**)&prev_radiance, n * sizeof(float4), true}, {(void**)&prev_depth, n * sizeof(float), true}};
+    }
 };
 
 static int sync_frame_streams(rt_frame* f);
@@ -293,35 +372,6 @@ static void ahead_discard(rt_frame* f);      // RT_OPT_SAMPLES_AHEAD: whatever w
 static void ahead_destroy(rt_frame* f);
 static bool ahead_wanted(const rt_frame* f);
 static int ahead_holds(const rt_frame* f, uint32_t sample);
-
-// A filter state's device buffers: each one's address and size.  A state lists them once (buffers()), for the allocation and for the free.
-struct DevBuf { void** p; size_t bytes; };
-static void free_buffers(const std::vector<DevBuf>& bufs)
-{
-    for (const DevBuf& b : bufs) if (*b.p) { (void)hipFree(*b.p); *b.p = nullptr; }
-}
-// a new state S with every buffer of s->buffers(sizes...) allocated, or nullptr with everything freed again if one allocation fails
-template <class S, class... Sizes> static S* alloc_state(Sizes... sizes)
-{
-    S* s = new S();
-    const std::vector<DevBuf> bufs = s->buffers(sizes...);
-    for (const DevBuf& b : bufs)
-        if (hipMalloc(b.p, b.bytes) != hipSuccess)
-        {
-            (void)hipGetLastError();
-            free_buffers(bufs);
-            delete s;
-            return nullptr;
-        }
-    return s;
-}
-template <class S> static void free_state(S*& s)
-{
-    if (!s) return;
-    free_buffers(s->buffers());
-    delete s;
-    s = nullptr;
-}
 
 // The spatial filter's state on a frame (rt_frame_filter, rt_frame_read_guides): made on first use, freed by rt_frame_destroy.  Its own rays, hits,
 // counter and spill area: batches traced ahead (RT_OPT_SAMPLES_AHEAD) may be using the frame's per-path buffers on other streams.  After the guide
@@ -1048,18 +1098,7 @@ void free_path_buffers(rt_frame* f)
         if (q.side) (void)hipStreamSynchronize(q.side);
         q.shadow_in_flight[0] = q.shadow_in_flight[1] = false;
     }
-    for (PathPipe& q : f->ps)
-    {
-        void* ptrs[] = {q.o4[0], q.o4[1], q.d4[0], q.d4[1], q.thr[0], q.thr[1], q.hits, q.sh_o4[0], q.sh_d4[0],
-            q.sh_aux[0], q.sh_o4[1], q.sh_d4[1], q.sh_aux[1], q.rlog, q.cnt, q.slow_list, q.sh_slow_list, q.ovf_slot};
-        for (void* p : ptrs) if (p) (void)hipFree(p);
-        for (int i = 0; i < 2; ++i)
-        {
-            q.o4[i] = nullptr; q.d4[i] = nullptr; q.thr[i] = nullptr;
-            q.sh_o4[i] = nullptr; q.sh_d4[i] = nullptr; q.sh_aux[i] = nullptr;
-        }
-        q.hits = nullptr; q.rlog = nullptr; q.cnt = nullptr; q.slow_list = nullptr; q.sh_slow_list = nullptr; q.ovf_slot = nullptr;
-    }
+    for (PathPipe& q : f->ps) free_buffers(q.buffers());
 }
 
 // Per-path state: ray queues for `slots` samples in flight and the radiance log
@@ -1074,14 +1113,16 @@ bool log_is_compact(const rt_frame* f, uint32_t slots)
     return asked && !f->log_full_forced && slots >= 8u && f->pipelines == 1u && 2u * (f->max_bounces + 1u) >= RT_LOG_INLINE + 4u;
 }
 
-// ray queues o4, d4, thr (x2), hits, shadow queue o4, d4 (x2) = 11 x 16; sh_aux (x2), cnt, two slow lists = 5 x 4;
-// log, full layout: 2 (B + 1) entries of 12 bytes -- 412 bytes at 8 bounces (rounds 1-2: 540); compact layout: 6 inline
-// entries + the path's share of the overflow pool + its block index -- 290 bytes at 8 bounces, 314 at 16.
+// A path's bytes in the full layout: the fixed buffers + a log of 2 (B + 1) entries of 12 bytes -- 412 bytes at 8 bounces (rounds 1-2: 540).
+size_t full_bytes_per_path(uint32_t max_bounces) { return RT_PATH_FIXED_BYTES + 12u * 2u * (max_bounces + 1u); }
+
+// ... and in the layout a batch of `slots` samples in flight gets; compact: 6 inline entries + the path's share of the overflow pool + its block
+// index -- 290 bytes at 8 bounces, 314 at 16.
 size_t bytes_per_path(const rt_frame* f, uint32_t slots)
 {
+    if (!log_is_compact(f, slots)) return full_bytes_per_path(f->max_bounces);
     const size_t entries = 2u * (f->max_bounces + 1u);
-    if (!log_is_compact(f, slots)) return 11u * 16u + 5u * 4u + 12u * entries;
-    return 11u * 16u + 5u * 4u + 4u + 12u * RT_LOG_INLINE + (12u * (entries - RT_LOG_INLINE) + f->log_pool_div - 1u) / f->log_pool_div;
+    return RT_PATH_FIXED_BYTES + 4u + 12u * RT_LOG_INLINE + (12u * (entries - RT_LOG_INLINE) + f->log_pool_div - 1u) / f->log_pool_div;
 }
 
 // auto: the most samples (<= 1024; a multiple of 8 above 8, of 16 above 64 -- rounds 1-2 took powers of two, which left up to
@@ -1170,21 +1211,13 @@ int alloc_path_buffers(rt_frame* f, uint32_t slots)
     f->log_inline = compact ? RT_LOG_INLINE : f->log_entries;
     f->log_ovf_blocks = compact ? (uint32_t)(paths / f->log_pool_div > 64u ? paths / f->log_pool_div : 64u) : 0u;
     const size_t log_elems = (size_t)f->log_inline * paths + (size_t)(f->log_entries - f->log_inline) * f->log_ovf_blocks;
-    size_t q = (size_t)(paths + 4) * sizeof(float4);
+    // RT_PATH_FIXED_BYTES is the list's own sum: what one more path adds to everything but the log
+    assert(total_bytes(PathPipe().buffers(2, 0, false)) - total_bytes(PathPipe().buffers(1, 0, false)) == RT_PATH_FIXED_BYTES);
     bool ok = true;
     for (uint32_t i = 0; i < f->n_pipes && ok; ++i)
     {
         PathPipe& pp = f->ps[i];
-        void** ptrs[] = {(void**)&pp.o4[0], (void**)&pp.o4[1], (void**)&pp.d4[0], (void**)&pp.d4[1],
-            (void**)&pp.thr[0], (void**)&pp.thr[1], (void**)&pp.hits, (void**)&pp.sh_o4[0],
-            (void**)&pp.sh_d4[0], (void**)&pp.sh_o4[1], (void**)&pp.sh_d4[1]};
-        for (void** p : ptrs) ok = ok && hipMalloc(p, q) == hipSuccess;
-        for (uint32_t*& p : pp.sh_aux) ok = ok && hipMalloc((void**)&p, (size_t)(paths + 4) * sizeof(uint32_t)) == hipSuccess;
-        ok = ok && hipMalloc((void**)&pp.rlog, log_elems * 3u * sizeof(float) + 16u) == hipSuccess;
-        if (compact) ok = ok && hipMalloc((void**)&pp.ovf_slot, (size_t)(paths + 4) * sizeof(uint32_t)) == hipSuccess;
-        ok = ok && hipMalloc((void**)&pp.cnt, (size_t)paths * sizeof(uint32_t)) == hipSuccess;
-        ok = ok && hipMalloc((void**)&pp.slow_list, (size_t)(paths + 64) * sizeof(uint32_t)) == hipSuccess;
-        ok = ok && hipMalloc((void**)&pp.sh_slow_list, (size_t)(paths + 64) * sizeof(uint32_t)) == hipSuccess;
+        for (const DevBuf& b : pp.buffers((size_t)paths, log_elems, compact)) ok = ok && hipMalloc(b.p, b.bytes) == hipSuccess;
         // ordered on the context's stream: the pipes' streams wait for it before their first launch (fork_pipes)
         ok = ok && hipMemsetAsync(pp.cnt, 0, (size_t)paths * sizeof(uint32_t), ctx->stream) == hipSuccess;
         pp.cur_slots = 0;
@@ -1395,6 +1428,26 @@ int flush_stage(rt_frame* f, bool keep = false)
     if (for_stage_pipes(f, [&]() { return keep ? flush_log_keep(f) : flush_log(f); }) != RT_OK) return RT_ERROR;
     return n > 1 ? join_pipes(f) : RT_OK;
 }
+
+// RT_OPT_FRAME_KERNEL = 255 measures again: another workload, or another grid
+void fk_auto_restart(rt_frame* f) { f->fk_auto.frames = 0; f->fk_auto.timing = -1; f->fk_auto.decided = false; f->fk_auto.use_kernel = false; }
+
+// An option that decides the per-path layout changes (rt_set_option).  Nothing of this frame is in flight any more -- its log replayed, its pipes joined
+// where the change moves chunks between them (`join`), the context's stream drained -- then `change` applies the new value and the buffers are laid out again.
+//   change  returns the samples in flight to lay the buffers out for, 0 to leave them as they are, or -1 after a failure of its own
+//   grow    the layout goes through ensure_slots (an allocation that is large enough stays), not alloc_path_buffers
+//   undo    after a layout that failed: puts the old value back, and the buffers come back for the samples they held (nullptr: the new value stays)
+int relayout(rt_frame* f, bool join, bool grow, const std::function<int()>& change, const std::function<void()>& undo = nullptr)
+{
+    if (flush_log(f) != RT_OK || (join && join_pipes(f) != RT_OK)) return RT_ERROR;
+    HIPCHK(f->ctx, hipStreamSynchronize(f->ctx->stream));
+    const uint32_t old_slots = f->slots;
+    const int slots = change();
+    if (slots <= 0) return slots < 0 ? RT_ERROR : RT_OK;
+    if ((grow ? ensure_slots(f, (uint32_t)slots) : alloc_path_buffers(f, (uint32_t)slots)) == RT_OK) return RT_OK;
+    if (undo) { undo(); (void)alloc_path_buffers(f, old_slots); }
+    return RT_ERROR;
+}
 } // namespace
 
 extern "C" {
@@ -1429,24 +1482,10 @@ static int create_frame(rt_ctx* ctx, const rt_frame_desc* fd, rt_frame** out, hi
     size_t n = f->n_local ? f->n_local : 1;
     f->trace_blocks = (uint32_t)ctx->prop.multiProcessorCount * 12u;
     f->trace_blocks = (f->trace_blocks + 7u) & ~7u;
-    f->radiance = nullptr;
-    f->resolved = nullptr;
     f->ps[0].stream = borrowed_main_stream;              // (NULL: ensure_pipe_resources gives pipe 0 the context's stream)
     bool ok = true;
-    ok = ok && hipMalloc((void**)&f->radiance, n * sizeof(float4)) == hipSuccess;
-    ok = ok && hipMalloc((void**)&f->resolved, n * sizeof(float4)) == hipSuccess;
-    ok = ok && hipMalloc((void**)&f->aov_buf.diffuse_albedo, n * sizeof(float4)) == hipSuccess;
-    ok = ok && hipMalloc((void**)&f->aov_buf.depth, n * sizeof(float)) == hipSuccess;
-    ok = ok && hipMalloc((void**)&f->aov_buf.normal, n * sizeof(float4)) == hipSuccess;
-    ok = ok && hipMalloc((void**)&f->aov_buf.velocity, n * sizeof(float2)) == hipSuccess;
-    ok = ok && hipMalloc((void**)&f->prev_radiance, n * sizeof(float4)) == hipSuccess;
-    ok = ok && hipMalloc((void**)&f->prev_depth, n * sizeof(float)) == hipSuccess;
-    ok = ok && hipMemsetAsync(f->aov_buf.diffuse_albedo, 0, n * sizeof(float4), ctx->stream) == hipSuccess;
-    ok = ok && hipMemsetAsync(f->aov_buf.depth, 0, n * sizeof(float), ctx->stream) == hipSuccess;
-    ok = ok && hipMemsetAsync(f->aov_buf.normal, 0, n * sizeof(float4), ctx->stream) == hipSuccess;
-    ok = ok && hipMemsetAsync(f->aov_buf.velocity, 0, n * sizeof(float2), ctx->stream) == hipSuccess;
-    ok = ok && hipMemsetAsync(f->prev_radiance, 0, n * sizeof(float4), ctx->stream) == hipSuccess;
-    ok = ok && hipMemsetAsync(f->prev_depth, 0, n * sizeof(float), ctx->stream) == hipSuccess;
+    for (const DevBuf& b : f->images(n)) ok = ok && hipMalloc(b.p, b.bytes) == hipSuccess;
+    for (const DevBuf& b : f->images(n)) if (b.clear) ok = ok && hipMemsetAsync(*b.p, 0, b.bytes, ctx->stream) == hipSuccess;
     ok = ok && alloc_path_buffers(f, 1) == RT_OK;     // grows on demand (ensure_slots)
     ok = ok && ensure_pipe_resources(f, f->pipelines) == RT_OK;
     if (!ok)
@@ -1469,39 +1508,23 @@ int rt_frame_destroy(rt_frame* f)
     (void)hipSetDevice(f->ctx->device);
     ahead_destroy(f);                                     // its banks first (frames of their own)
     f->ctx->frames.erase(std::remove(f->ctx->frames.begin(), f->ctx->frames.end(), f), f->ctx->frames.end());
-    for (PathPipe& q : f->ps)
-    {
-        if (q.stream) (void)hipStreamSynchronize(q.stream);
-        if (q.side) (void)hipStreamSynchronize(q.side);
-    }
+    // every stream it launches on has drained before anything is freed
+    for (PathPipe& q : f->ps) for (hipStream_t st : {q.stream, q.side}) if (st) (void)hipStreamSynchronize(st);
+    if (f->present_stream) (void)hipStreamSynchronize(f->present_stream);
     (void)hipStreamSynchronize(f->ctx->stream);
+    // device memory: the per-path buffers, the images, k_frame's buffers
     free_path_buffers(f);
-    void* ptrs[] = {f->radiance, f->resolved, f->aov_buf.diffuse_albedo, f->aov_buf.depth,
-        f->aov_buf.normal, f->aov_buf.velocity, f->prev_radiance, f->prev_depth};
-    for (void* p : ptrs) if (p) (void)hipFree(p);
-    for (uint32_t i = 0; i < RT_MAX_PIPES; ++i)
-    {
-        PathPipe& q = f->ps[i];
-        if (q.counters) (void)hipFree(q.counters);
-        if (q.spill) (void)hipFree(q.spill);
-        if (q.sh_spill) (void)hipFree(q.sh_spill);
-        if (q.done) (void)hipEventDestroy(q.done);
-        if (q.side) (void)hipStreamSynchronize(q.side);
-        if (q.ev_shaded) (void)hipEventDestroy(q.ev_shaded);
-        for (hipEvent_t e : q.ev_shadow) if (e) (void)hipEventDestroy(e);
-        if (q.side) (void)hipStreamDestroy(q.side);
-        if (i > 0 && q.stream) (void)hipStreamDestroy(q.stream);
-    }
-    if (f->present_stream) { (void)hipStreamSynchronize(f->present_stream); (void)hipStreamDestroy(f->present_stream); }
-    if (f->frame_counts) (void)hipFree(f->frame_counts);
-    if (f->frame_slow) (void)hipFree(f->frame_slow);
-    if (f->frame_spill) (void)hipFree(f->frame_spill);
-    for (auto& pair : f->fk_auto.ev) for (hipEvent_t e : pair) if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : f->ev_resolved) if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : f->ev_copied) if (e) (void)hipEventDestroy(e);
+    free_buffers(f->images());
+    f->kf.release();
     if (f->resolved_b) (void)hipFree(f->resolved_b);
-    for (auto& s : f->spans) { (void)hipEventDestroy(s.a); (void)hipEventDestroy(s.b); }
+    // streams and events (pipe 0's stream is the context's or a bank owner's)
+    for (uint32_t i = 0; i < RT_MAX_PIPES; ++i) f->ps[i].destroy(i > 0);
+    if (f->present_stream) (void)hipStreamDestroy(f->present_stream);
+    for (auto& pair : f->fk_auto.ev) for (hipEvent_t e : pair) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : {f->ev_resolved[0], f->ev_resolved[1], f->ev_copied[0], f->ev_copied[1]}) if (e) (void)hipEventDestroy(e);
+    for (auto& sp : f->spans) { (void)hipEventDestroy(sp.a); (void)hipEventDestroy(sp.b); }
     for (auto e : f->event_pool) (void)hipEventDestroy(e);
+    // the filters' states
     free_state(f->sf);
     free_state(f->tf);
     free_state(f->sm);
@@ -1534,41 +1557,25 @@ int rt_set_option(rt_frame* f, int option, uint32_t value)
         return RT_OK;
     case RT_OPT_MAX_BOUNCES:
         if (value > RT_MAX_BOUNCES_LIMIT) return fail(f->ctx, "rt_set_option: max_bounces above RT_MAX_BOUNCES_LIMIT");
-        if (value != f->max_bounces)
-        {
-            f->fk_auto.frames = 0; f->fk_auto.timing = -1; f->fk_auto.decided = false; f->fk_auto.use_kernel = false;   //  another workload: RT_OPT_FRAME_KERNEL = 255 measures again
-            if (flush_log(f) != RT_OK) return RT_ERROR;
-            HIPCHK(f->ctx, hipStreamSynchronize(f->ctx->stream));
-            f->max_bounces = value;
-            f->log_full_forced = false;               // another path length: the compact layout gets another chance
-            f->fallback_limit_mb = 0;
-            return ensure_slots(f, 1);                // log rows / payload split follow max_bounces
-        }
-        return RT_OK;
+        if (value == f->max_bounces) return RT_OK;
+        fk_auto_restart(f);
+        // log rows / payload split follow max_bounces; another path length: the compact layout gets another chance
+        return relayout(f, false, true, [&]() { f->max_bounces = value; f->log_full_forced = false; f->fallback_limit_mb = 0; return 1; });
     case RT_OPT_SAMPLES_IN_FLIGHT:
+    {
         if (value > 1024) return fail(f->ctx, "rt_set_option: samples in flight must be 0 (auto) or 1..1024");
-        if (value != f->slots_opt)
-        {
-            if (flush_log(f) != RT_OK) return RT_ERROR;
-            HIPCHK(f->ctx, hipStreamSynchronize(f->ctx->stream));
-            uint32_t old = f->slots_opt, old_slots = f->slots;
-            f->slots_opt = value;
-            f->reserved_explicitly = false; f->samples_asked = 0;      // (the caller decides anew how the buffers are sized: lean growth starts over)
-            // an explicit count is allocated now; auto (0) grows with the batches requested
-            if (alloc_path_buffers(f, value ? value : 1u) != RT_OK)
-            {
-                f->slots_opt = old;
-                (void)alloc_path_buffers(f, old_slots);
-                return RT_ERROR;
-            }
-        }
-        return RT_OK;
+        if (value == f->slots_opt) return RT_OK;
+        const uint32_t old = f->slots_opt;
+        // an explicit count is allocated now; auto (0) grows with the batches requested.  The caller decides anew how the buffers are sized: lean growth starts over
+        return relayout(f, false, false, [&]() { f->slots_opt = value; f->reserved_explicitly = false; f->samples_asked = 0; return value ? (int)value : 1; },
+                        [&]() { f->slots_opt = old; });
+    }
     case RT_OPT_WHITE_FURNACE: f->white_furnace = value ? 1 : 0; return RT_OK;
     case RT_OPT_SAMPLER:
         if (value > 1) return fail(f->ctx, "rt_set_option: sampler must be 0 (kRandom) or 1 (kBlueNoise)");
         if (value == 1 && !f->ctx->blue_noise)
             return fail(f->ctx, "rt_set_option: SamplerType::kBlueNoise needs rt_upload_blue_noise_tables first");
-        if (value != f->sampler) { f->fk_auto.frames = 0; f->fk_auto.timing = -1; f->fk_auto.decided = false; f->fk_auto.use_kernel = false; }
+        if (value != f->sampler) fk_auto_restart(f);
         f->sampler = value;
         return RT_OK;
     case RT_OPT_AOV:
@@ -1586,7 +1593,7 @@ int rt_set_option(rt_frame* f, int option, uint32_t value)
         f->denoiser = value;
         return RT_OK;
     case RT_OPT_TRACE_DROP_LAST_BOUNCE_RAYS:
-        if ((value ? 1u : 0u) != f->drop_last) { f->fk_auto.frames = 0; f->fk_auto.timing = -1; f->fk_auto.decided = false; f->fk_auto.use_kernel = false; }
+        if ((value ? 1u : 0u) != f->drop_last) fk_auto_restart(f);
         f->drop_last = value ? 1 : 0;
         return RT_OK;
     case RT_OPT_PROFILE_KERNELS: f->profile = value ? 1 : 0; return RT_OK;
@@ -1600,57 +1607,27 @@ int rt_set_option(rt_frame* f, int option, uint32_t value)
     case RT_OPT_OVERLAP_SHADOW: f->overlap_shadow = value ? 1u : 0u; return RT_OK;
     case RT_OPT_PIPELINES:
         if (value == 0 || value > RT_MAX_PIPES) return fail(f->ctx, "rt_set_option: pipelines must be 1..RT_MAX_PIPES");
-        if (value != f->pipelines)
-        {
-            if (flush_log(f) != RT_OK || join_pipes(f) != RT_OK) return RT_ERROR;
-            HIPCHK(f->ctx, hipStreamSynchronize(f->ctx->stream));
-            if (ensure_pipe_resources(f, value) != RT_OK) return RT_ERROR;
-            f->pipelines = value;
-            return alloc_path_buffers(f, f->slots);
-        }
-        return RT_OK;
+        if (value == f->pipelines) return RT_OK;
+        return relayout(f, true, false, [&]() { if (ensure_pipe_resources(f, value) != RT_OK) return -1; f->pipelines = value; return (int)f->slots; });
     case RT_OPT_FRAME_KERNEL:
         if (f->deferred.active) return fail(f->ctx, "rt_set_option: RT_OPT_FRAME_KERNEL cannot change while a sample is in flight (rt_advance_sample first)");
-        if (value != f->frame_kernel)
-        {
-            // (the grid and its buffers are sized by the value: the next launch makes them again)
-            HIPCHK(f->ctx, hipStreamSynchronize(f->ctx->stream));
-            if (f->frame_counts) (void)hipFree(f->frame_counts);
-            if (f->frame_slow) (void)hipFree(f->frame_slow);
-            if (f->frame_spill) (void)hipFree(f->frame_spill);
-            f->frame_counts = nullptr; f->frame_slow = nullptr; f->frame_spill = nullptr; f->frame_blocks = 0;
-            f->frame_kernel = value == 255u ? 255u : (value > 64u ? 64u : value);
-            f->fk_auto.frames = 0; f->fk_auto.timing = -1; f->fk_auto.decided = false; f->fk_auto.use_kernel = false;
-        }
+        if (value == f->frame_kernel) return RT_OK;
+        HIPCHK(f->ctx, hipStreamSynchronize(f->ctx->stream));
+        f->kf.release();                                  // (the grid and its buffers are sized by the value: the next launch makes them again)
+        f->frame_kernel = value == 255u ? 255u : (value > 64u ? 64u : value);
+        fk_auto_restart(f);
         return RT_OK;
     case RT_OPT_STAGE_PIPES:
         if (value == 0 || value > RT_MAX_PIPES) return fail(f->ctx, "rt_set_option: stage pipes must be 1..RT_MAX_PIPES");
-        if (value != f->stage_pipes)
-        {
-            if (f->p->cur_slots != 0) return fail(f->ctx, "rt_set_option: RT_OPT_STAGE_PIPES cannot change while a sample is in flight (rt_advance_sample first)");
-            if (flush_log(f) != RT_OK || join_pipes(f) != RT_OK) return RT_ERROR;
-            HIPCHK(f->ctx, hipStreamSynchronize(f->ctx->stream));
-            if (ensure_pipe_resources(f, value) != RT_OK) return RT_ERROR;
-            f->stage_pipes = value;
-            f->stage_chunks = 1;
-            if (f->slots == 1) return alloc_path_buffers(f, 1);
-        }
-        return RT_OK;
+        if (value == f->stage_pipes) return RT_OK;
+        if (f->p->cur_slots != 0) return fail(f->ctx, "rt_set_option: RT_OPT_STAGE_PIPES cannot change while a sample is in flight (rt_advance_sample first)");
+        return relayout(f, true, false, [&]() { if (ensure_pipe_resources(f, value) != RT_OK) return -1; f->stage_pipes = value; f->stage_chunks = 1; return f->slots == 1 ? 1 : 0; });
     case RT_OPT_PATH_STATE_LIMIT_MB:
-        if (value != f->state_limit_mb)
-        {
-            if (flush_log(f) != RT_OK) return RT_ERROR;
-            HIPCHK(f->ctx, hipStreamSynchronize(f->ctx->stream));
-            uint32_t old = f->state_limit_mb;
-            f->state_limit_mb = value;
-            if (alloc_path_buffers(f, f->slots) != RT_OK)
-            {
-                f->state_limit_mb = old;
-                (void)alloc_path_buffers(f, f->slots);
-                return RT_ERROR;
-            }
-        }
-        return RT_OK;
+    {
+        if (value == f->state_limit_mb) return RT_OK;
+        const uint32_t old = f->state_limit_mb;
+        return relayout(f, false, false, [&]() { f->state_limit_mb = value; return (int)f->slots; }, [&]() { f->state_limit_mb = old; });
+    }
     case RT_OPT_DEBUG_ALLOC_LIMIT: f->debug_alloc_limit = value; return RT_OK;
     case RT_OPT_SMALL_LAUNCH_PATHS: f->small_launch_paths = value; f->small_launch_set = true; return RT_OK;
     case RT_OPT_TRACE_TAIL_LANES: f->trace_tail_lanes = value > 64u ? 64u : value; return RT_OK;
@@ -1659,13 +1636,14 @@ int rt_set_option(rt_frame* f, int option, uint32_t value)
     case RT_OPT_COMPACT_LOG:
     case RT_OPT_DEBUG_LOG_POOL_DIV:
         if (option == RT_OPT_DEBUG_LOG_POOL_DIV && value == 0) return fail(f->ctx, "rt_set_option: RT_OPT_DEBUG_LOG_POOL_DIV must be >= 1");
-        if (flush_log(f) != RT_OK) return RT_ERROR;
-        HIPCHK(f->ctx, hipStreamSynchronize(f->ctx->stream));
         if (option == RT_OPT_COMPACT_LOG && value > 2u) return fail(f->ctx, "rt_set_option: RT_OPT_COMPACT_LOG is 0, 1 or 2");
-        if (option == RT_OPT_COMPACT_LOG) f->compact_log_opt = value; else f->log_pool_div = value;
-        f->log_full_forced = false;
-        f->fallback_limit_mb = 0;
-        return alloc_path_buffers(f, f->slots);
+        return relayout(f, false, false, [&]()
+        {
+            if (option == RT_OPT_COMPACT_LOG) f->compact_log_opt = value; else f->log_pool_div = value;
+            f->log_full_forced = false;
+            f->fallback_limit_mb = 0;
+            return (int)f->slots;
+        });
     case RT_OPT_TRACE_VARIANT:
         if (!(value == 0 || value == 5 || (value >= 8 && value <= 11))) return fail(f->ctx, "rt_set_option: unknown trace kernel variant (0, 5, 8..11)");
         f->trace_variant = value;
@@ -1932,7 +1910,7 @@ int launch_frame_kernel_t(rt_frame* f)
 {
     rt_ctx* ctx = f->ctx;
     PathPipe& q = f->ps[0];
-    if (f->frame_blocks == 0u)
+    if (f->kf.blocks == 0u)
     {
         // RT_OPT_FRAME_KERNEL = 1: as many one-wave blocks as the device keeps resident (the kernel's registers decide), every wave with the same
         // number of chunks; = k >= 2: k chunks per wave, i.e. MORE blocks than are resident -- the hardware starts the next block where one has
@@ -1944,21 +1922,19 @@ int launch_frame_kernel_t(rt_frame* f)
         const uint32_t resident = std::max(8u, (uint32_t)ctx->prop.multiProcessorCount * (uint32_t)per_cu);
         const uint32_t cpw = f->frame_kernel >= 2u && f->frame_kernel != 255u ? f->frame_kernel : (n_chunks + resident - 1u) / resident;     // chunks per wave
         //  all three or none: the grid's size is committed only with its buffers, so a failed allocation cannot leave a later
-        // launch with frame_blocks != 0 and a NULL buffer
+        // launch with kf.blocks != 0 and a NULL buffer
         const uint32_t n_blocks = (((n_chunks + cpw - 1u) / cpw) + 7u) & ~7u;
-        uint32_t *counts = nullptr, *slow = nullptr; uint2* spill = nullptr;
-        const bool ok = f->debug_alloc_limit != 0xFFFFFFFFu &&                       // (RT_OPT_DEBUG_ALLOC_LIMIT = 0xFFFFFFFF: the test hook for this path)
-                        hipMalloc((void**)&counts, (size_t)n_blocks * RT_FRAME_COUNT_STRIDE * sizeof(uint32_t)) == hipSuccess &&
-                        hipMalloc((void**)&slow, (size_t)n_blocks * cpw * 64u * sizeof(uint32_t)) == hipSuccess &&
-                        hipMalloc((void**)&spill, (size_t)n_blocks * 64u * (RT_W4_STACK_MAX - 12) * sizeof(uint2)) == hipSuccess;
+        rt_frame::KFrame k;
+        bool ok = f->debug_alloc_limit != 0xFFFFFFFFu;                               // (RT_OPT_DEBUG_ALLOC_LIMIT = 0xFFFFFFFF: the test hook for this path)
+        for (const DevBuf& b : k.buffers(n_blocks, cpw)) ok = ok && hipMalloc(b.p, b.bytes) == hipSuccess;
         if (!ok)
         {
             (void)hipGetLastError();
-            for (void* p : {(void*)counts, (void*)slow, (void*)spill}) if (p) (void)hipFree(p);
+            k.release();
             return fail(ctx, "rt_advance_sample: out of device memory for k_frame's per-wave buffers");
         }
-        f->frame_counts = counts; f->frame_slow = slow; f->frame_spill = spill;
-        f->frame_blocks = n_blocks;
+        k.blocks = n_blocks;
+        f->kf = k;
         f->frame_chunks_per_wave = cpw;
     }
     // the previous sample's per-bounce counters go to the totals first (k_raygen does this for the stage kernels)
@@ -1980,9 +1956,9 @@ int launch_frame_kernel_t(rt_frame* f)
     fa.hits = q.hits;
     fa.sh_o4 = q.sh_o4[0]; fa.sh_d4 = q.sh_d4[0]; fa.sh_aux = q.sh_aux[0];
     fa.radiance = f->radiance;
-    fa.spill = f->frame_spill;
-    fa.slow_list = f->frame_slow;
-    fa.wave_counts = f->frame_counts;
+    fa.spill = f->kf.spill;
+    fa.slow_list = f->kf.slow;
+    fa.wave_counts = f->kf.counts;
     fa.cam = f->camera;
     fa.tan_half_fov = rt_tanf(0.5f * f->camera.fov);
     fa.max_bounces = f->max_bounces;
@@ -1991,8 +1967,8 @@ int launch_frame_kernel_t(rt_frame* f)
     fa.tune = ((t & 0xFFu) ? (t & 0xFFu) : (RT_TRACE2_DEFAULT_TUNE & 0xFFu)) | ((((t >> 8) & 0xFFu) ? ((t >> 8) & 0xFFu) : ((RT_TRACE2_DEFAULT_TUNE >> 8) & 0xFFu)) << 8);
     fa.tail_q = f->trace_tail_lanes;
     fa.chunks_per_wave = f->frame_chunks_per_wave;
-    hipLaunchKernelGGL((k_frame<FURNACE, BLUE>), dim3(f->frame_blocks), dim3(64), 0, q.stream, ctx->scene.d, f->tile, fa);
-    hipLaunchKernelGGL(k_frame_sum, dim3(130), dim3(256), 0, q.stream, (const uint32_t*)f->frame_counts, f->frame_blocks, f->max_bounces, q.counters);
+    hipLaunchKernelGGL((k_frame<FURNACE, BLUE>), dim3(f->kf.blocks), dim3(64), 0, q.stream, ctx->scene.d, f->tile, fa);
+    hipLaunchKernelGGL(k_frame_sum, dim3(130), dim3(256), 0, q.stream, (const uint32_t*)f->kf.counts, f->kf.blocks, f->max_bounces, q.counters);
     HIPCHK(ctx, hipGetLastError());
     q.chunk_base = 0;
     q.chunk_count = f->n_local;
@@ -2291,6 +2267,26 @@ int rt_copy_history(rt_frame* f)                        // CopyHistoryBuffers, :
     return RT_OK;
 }
 
+// The wavefront loop of the rays in the current pipe's queue (rt_integrate's chunks, the batches traced ahead): closest-hit trace, then per bounce
+// k_shade, shadow trace, next closest-hit trace.  The shadow trace of bounce b and the closest-hit trace of bounce b + 1 both depend on k_shade(b)
+// only, and k_shade(b + 1) on the latter only (the shadow queue is double-buffered): with overlap_shadow the shadow trace goes to the pipe's side
+// stream, AFTER the next closest-hit launch has been enqueued -- it moves in as that launch's last rays drain and leaves as k_shade(b + 1) moves
+// in, so neither tail idles the machine (tools/launch_timeline.py: 0.75-0.95 ms each).  per_frame: the AOVs of the first hits (ComputeAOVs).
+static int trace_bounces(rt_frame* f, bool per_frame)
+{
+    if (rt_intersect(f, 0) != RT_OK) return RT_ERROR;
+    for (uint32_t bounce = 0; bounce <= f->max_bounces; ++bounce)
+    {
+        const bool more = bounce < f->max_bounces;
+        if (bounce == 0 && per_frame && rt_compute_aovs(f) != RT_OK) return RT_ERROR;
+        if (rt_shade(f, bounce) != RT_OK) return RT_ERROR;
+        if (f->side_active && more && rt_intersect(f, bounce + 1u) != RT_OK) return RT_ERROR;
+        if (rt_intersect_shadow(f, bounce) != RT_OK) return RT_ERROR;
+        if (!f->side_active && more && rt_intersect(f, bounce + 1u) != RT_OK) return RT_ERROR;
+    }
+    return RT_OK;
+}
+
 #include "samples_ahead_impl.h"
 
 int rt_advance_sample(rt_frame* f)                      // AdvanceSampleCount, :510-514
@@ -2411,20 +2407,7 @@ int rt_integrate(rt_frame* f, uint32_t n_samples)       // n x Integrator::Integ
         {
             f->p = &f->ps[c % f->n_pipes];
             if (generate_rays(f, batch, base, c >= f->n_pipes) != RT_OK) { rc = RT_ERROR; break; }
-            // Per bounce: closest-hit trace, k_shade, shadow trace.  The shadow trace of bounce b and the closest-hit
-            // trace of bounce b + 1 both depend on k_shade(b) only, and k_shade(b + 1) on the latter only (the shadow
-            // queue is double-buffered): with overlap_shadow the shadow trace goes to the pipe's side stream, AFTER the
-            // next closest-hit launch has been enqueued -- it moves in as that launch's last rays drain and leaves as
-            // k_shade(b + 1) moves in, so neither tail idles the machine (tools/launch_timeline.py: 0.75-0.95 ms each).
-            if (rt_intersect(f, 0) != RT_OK) rc = RT_ERROR;
-            for (uint32_t bounce = 0; bounce <= f->max_bounces && rc == RT_OK; ++bounce)
-            {
-                if (bounce == 0 && per_frame && rt_compute_aovs(f) != RT_OK) rc = RT_ERROR;
-                else if (rt_shade(f, bounce) != RT_OK) rc = RT_ERROR;
-                else if (f->side_active && bounce < f->max_bounces && rt_intersect(f, bounce + 1u) != RT_OK) rc = RT_ERROR;
-                else if (rt_intersect_shadow(f, bounce) != RT_OK) rc = RT_ERROR;
-                else if (!f->side_active && bounce < f->max_bounces && rt_intersect(f, bounce + 1u) != RT_OK) rc = RT_ERROR;
-            }
+            rc = trace_bounces(f, per_frame);
             // Compact log layout: did this sequence run the overflow pool dry?  (The one host synchronisation of a batch; the
             // full layout has none.)  If so nothing of it has reached the radiance yet: drop it, switch the frame to the full
             // layout within the same memory, and run the SAME chunk again -- the sum stays exact.
@@ -2440,7 +2423,6 @@ int rt_integrate(rt_frame* f, uint32_t n_samples)       // n x Integrator::Integ
                 }
                 if (dry)
                 {
-                    const uint64_t held = (uint64_t)f->log_stride * bytes_per_path(f, f->slots) * f->n_pipes;
                     if (hipMemsetAsync(f->p->counters->queue, 0, sizeof(f->p->counters->queue) + sizeof(f->p->counters->shadow), f->p->stream) != hipSuccess ||
                         hipMemsetAsync(&f->p->counters->log_ovf_flag, 0, sizeof(uint32_t), f->p->stream) != hipSuccess ||
                         hipStreamSynchronize(f->p->stream) != hipSuccess)
@@ -2454,7 +2436,6 @@ int rt_integrate(rt_frame* f, uint32_t n_samples)       // n x Integrator::Integ
                     // the full layout takes more bytes per path: it may use what the library would have given it in the first
                     // place (half of the HBM), and beyond that runs the same batch size in more chunks
                     f->fallback_limit_mb = 144u << 10;
-                    (void)held;
                     ++f->log_fallbacks;
                     if (alloc_path_buffers(f, f->slots) != RT_OK) { rc = RT_ERROR; break; }     // cnt starts from zero again
                     continue;                                                                   // the same `base`, the new chunk size
@@ -3143,11 +3124,11 @@ int rt_frame_debug_frame_rows(rt_frame* f, uint32_t* out, uint32_t capacity_rows
     if (!f || !n_rows || !row_words) return fail(nullptr, "rt_frame_debug_frame_rows: NULL argument");
     rt_ctx* ctx = f->ctx;
     (void)hipSetDevice(ctx->device);
-    *n_rows = f->frame_blocks; *row_words = RT_FRAME_COUNT_STRIDE;
-    if (!out || f->frame_blocks == 0u || !f->frame_counts) return RT_OK;
-    if (capacity_rows < f->frame_blocks) return fail(ctx, "rt_frame_debug_frame_rows: the caller's array is too small");
+    *n_rows = f->kf.blocks; *row_words = RT_FRAME_COUNT_STRIDE;
+    if (!out || f->kf.blocks == 0u || !f->kf.counts) return RT_OK;
+    if (capacity_rows < f->kf.blocks) return fail(ctx, "rt_frame_debug_frame_rows: the caller's array is too small");
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    HIPCHK(ctx, hipMemcpy(out, f->frame_counts, (size_t)f->frame_blocks * RT_FRAME_COUNT_STRIDE * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIPCHK(ctx, hipMemcpy(out, f->kf.counts, (size_t)f->kf.blocks * RT_FRAME_COUNT_STRIDE * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return RT_OK;
 }
 

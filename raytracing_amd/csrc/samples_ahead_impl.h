@@ -38,7 +38,7 @@ static uint32_t ahead_depth(const rt_frame* f)
     if (k == 0) return 0;
     if (k == 1 || k == 255) { k = (32000000ull + n - 1) / n; if (k > 64) k = 64; }
     const uint64_t budget = f->state_limit_mb ? ((uint64_t)f->state_limit_mb << 20) : (64ull << 30);
-    const uint64_t per_sample = 2ull * n * (11u * 16u + 5u * 4u + 12u * 2u * (f->max_bounces + 1u));
+    const uint64_t per_sample = 2ull * n * full_bytes_per_path(f->max_bounces);
     if (k * per_sample > budget) k = budget / per_sample;
     return k >= 2 ? (uint32_t)k : 0u;
 }
@@ -51,12 +51,30 @@ static bool ahead_wanted(const rt_frame* f)
            f->stage_pipes <= 1u && f->pipelines == 1u && f->ctx->scene.valid && ahead_depth(f) >= 2u;
 }
 
-static void ahead_mirror(const rt_frame* f, uint32_t (&m)[16])
+// ---- what a bank follows ---------------------------------------------------------------------------------------------------------------
+// Every RT_OPT_* is in one of three classes.  A new option goes into the table, into ahead_wanted, or into the last list with its reason.
+//  * FOLLOWED BY THE BANKS (they decide what a batch computes or how it is launched): the twelve rows of RT_AHEAD_FOLLOWED, and as the named exception
+//    RT_OPT_SMALL_LAUNCH_PATHS and RT_OPT_TRACE_TAIL_PATHS (64-bit fields, one with a "set" flag: copied by ahead_configure, compared by ahead_key).
+//  * RULES THE MODE OUT (ahead_wanted): RT_OPT_AOV, RT_OPT_DENOISER (read between stages), RT_OPT_PROFILE_KERNELS (events per launch),
+//    RT_OPT_PIPELINES, RT_OPT_STAGE_PIPES (one chunk on one stream).
+//  * DOES NOT CONCERN A BANK: RT_OPT_SAMPLES_AHEAD (the mode itself: its depth and stream bit are in the key), RT_OPT_PATH_STATE_LIMIT_MB (bounds the depth:
+//    in the key), RT_OPT_SAMPLES_IN_FLIGHT (a bank holds `depth` samples), RT_OPT_COMPACT_LOG, RT_OPT_DEBUG_LOG_POOL_DIV (a bank has no limit: full layout),
+//    RT_OPT_FRAME_KERNEL (banks trace batches), RT_OPT_DEBUG_ALLOC_LIMIT (the owner's test hook), RT_OPT_TRACE_PACKET_BOUNCES (accepts only 0).
+static const struct { int option; uint32_t rt_frame::*field; } RT_AHEAD_FOLLOWED[12] = {
+    {RT_OPT_MAX_BOUNCES, &rt_frame::max_bounces}, {RT_OPT_SAMPLER, &rt_frame::sampler}, {RT_OPT_WHITE_FURNACE, &rt_frame::white_furnace},
+    {RT_OPT_TRACE_DROP_LAST_BOUNCE_RAYS, &rt_frame::drop_last}, {RT_OPT_OVERLAP_SHADOW, &rt_frame::overlap_shadow}, {RT_OPT_TRACE_VARIANT, &rt_frame::trace_variant},
+    {RT_OPT_TRACE_TUNE, &rt_frame::trace_tune}, {RT_OPT_SHADE_PARTITION, &rt_frame::shade_partition}, {RT_OPT_TRACE_TAIL_LANES, &rt_frame::trace_tail_lanes},
+    {RT_OPT_CHUNK_REFILL, &rt_frame::chunk_refill}, {RT_OPT_TRACE_WAVES_PER_CU, &rt_frame::trace_waves_per_cu}, {RT_OPT_TRACE_SELECT_FORM_BOX, &rt_frame::select_form_box}};
+
+static AheadKey ahead_key(const rt_frame* f)
 {
-    const uint32_t v[16] = {f->max_bounces, f->sampler, f->white_furnace, f->drop_last, f->overlap_shadow, f->trace_variant, f->trace_tune, f->shade_partition,
-        f->trace_tail_lanes, f->chunk_refill, f->trace_waves_per_cu, f->select_form_box ? 1u : 0u, f->small_launch_set ? (uint32_t)std::min<uint64_t>(f->small_launch_paths, 0xFFFFFFFFull) : 0xFFFFFFFFu,
-        (uint32_t)std::min<uint64_t>(f->trace_tail_paths, 0xFFFFFFFFull), ahead_depth(f), f->ahead_opt & 0x100u};
-    memcpy(m, v, sizeof(v));
+    AheadKey k;
+    for (int i = 0; i < 12; ++i) k.followed[i] = f->*RT_AHEAD_FOLLOWED[i].field;
+    k.small_launch = f->small_launch_set ? (uint32_t)std::min<uint64_t>(f->small_launch_paths, 0xFFFFFFFFull) : 0xFFFFFFFFu;
+    k.tail_paths = (uint32_t)std::min<uint64_t>(f->trace_tail_paths, 0xFFFFFFFFull);
+    k.depth = ahead_depth(f);
+    k.two_streams = f->ahead_opt & 0x100u;
+    return k;
 }
 
 // The banks exist, are laid out for `depth` samples in flight and have the owner's options.  (Anything here may wait for the device: it runs when
@@ -66,12 +84,11 @@ static int ahead_configure(rt_frame* f)
     rt_ctx* ctx = f->ctx;
     if (!f->ahead) f->ahead = new Ahead();
     Ahead& A = *f->ahead;
-    uint32_t want[16];
-    ahead_mirror(f, want);
-    if (A.configured && memcmp(want, A.mirrored, sizeof(want)) == 0) return RT_OK;
+    const AheadKey want = ahead_key(f);
+    if (A.configured && memcmp(&want, &A.mirrored, sizeof(want)) == 0) return RT_OK;
     ahead_discard(f);
     A.configured = false;
-    const bool two_streams = (f->ahead_opt & 0x100u) != 0u;
+    const bool two_streams = want.two_streams != 0u;
     for (int i = 0; i < 2; ++i)
     {
         // the banks' launches go beside the frame's own: one stream for both banks (their batches in order) or one each (they overlap)
@@ -89,25 +106,21 @@ static int ahead_configure(rt_frame* f)
         if (!b.order) HIPCHK(ctx, hipEventCreateWithFlags(&b.order, hipEventDisableTiming));
         if (sync_frame_streams(b.h) != RT_OK) return RT_ERROR;
         rt_frame* h = b.h;
-        const std::pair<int, uint32_t> options[] = {{RT_OPT_MAX_BOUNCES, f->max_bounces}, {RT_OPT_SAMPLER, f->sampler}, {RT_OPT_WHITE_FURNACE, f->white_furnace},
-            {RT_OPT_TRACE_DROP_LAST_BOUNCE_RAYS, f->drop_last}, {RT_OPT_OVERLAP_SHADOW, f->overlap_shadow}, {RT_OPT_TRACE_VARIANT, f->trace_variant},
-            {RT_OPT_TRACE_TUNE, f->trace_tune}, {RT_OPT_SHADE_PARTITION, f->shade_partition}, {RT_OPT_TRACE_TAIL_LANES, f->trace_tail_lanes},
-            {RT_OPT_CHUNK_REFILL, f->chunk_refill}, {RT_OPT_TRACE_WAVES_PER_CU, f->trace_waves_per_cu}, {RT_OPT_TRACE_SELECT_FORM_BOX, f->select_form_box ? 1u : 0u}};
-        for (const auto& o : options)
-            if (rt_set_option(h, o.first, o.second) != RT_OK) return RT_ERROR;
+        for (const auto& row : RT_AHEAD_FOLLOWED)
+            if (rt_set_option(h, row.option, f->*row.field) != RT_OK) return RT_ERROR;
         h->trace_tail_paths = f->trace_tail_paths;
         h->small_launch_paths = f->small_launch_paths; h->small_launch_set = f->small_launch_set;
-        if (ensure_slots(h, want[14]) != RT_OK) return RT_ERROR;
+        if (ensure_slots(h, want.depth) != RT_OK) return RT_ERROR;
         if (h->slots < 2u || h->chunk_pixels < (f->n_local ? f->n_local : 1u)) return fail(ctx, "RT_OPT_SAMPLES_AHEAD: a bank could not be laid out for the whole tile");
     }
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));       // the banks' allocations were cleared on the context's stream
-    A.depth = std::min(want[14], std::min(A.bank[0].h->slots, A.bank[1].h->slots));
-    memcpy(A.mirrored, want, sizeof(want));
+    A.depth = std::min(want.depth, std::min(A.bank[0].h->slots, A.bank[1].h->slots));
+    A.mirrored = want;
     A.configured = true;
     return RT_OK;
 }
 
-// A batch: samples base .. base + n - 1 through the wavefront loop of bank i, as rt_integrate runs one (the same launches in the same order), but the
+// A batch: samples base .. base + n - 1 through the wavefront loop of bank i, as rt_integrate runs one (trace_bounces), but the
 // log is left as it is: its replay happens sample by sample, by ahead_consume.
 static int ahead_launch(rt_frame* f, int i, uint32_t base, uint32_t n)
 {
@@ -125,14 +138,7 @@ static int ahead_launch(rt_frame* f, int i, uint32_t base, uint32_t n)
     h->fused = true;
     h->side_active = side_on(h);
     int rc = generate_rays(h, n, 0, false);
-    if (rc == RT_OK) rc = rt_intersect(h, 0);
-    for (uint32_t bounce = 0; bounce <= h->max_bounces && rc == RT_OK; ++bounce)
-    {
-        if (rt_shade(h, bounce) != RT_OK) rc = RT_ERROR;
-        else if (h->side_active && bounce < h->max_bounces && rt_intersect(h, bounce + 1u) != RT_OK) rc = RT_ERROR;
-        else if (rt_intersect_shadow(h, bounce) != RT_OK) rc = RT_ERROR;
-        else if (!h->side_active && bounce < h->max_bounces && rt_intersect(h, bounce + 1u) != RT_OK) rc = RT_ERROR;
-    }
+    if (rc == RT_OK) rc = trace_bounces(h, false);
     if (rc == RT_OK && (wait_shadow(h, 0) != RT_OK || wait_shadow(h, 1) != RT_OK)) rc = RT_ERROR;
     h->fused = false;
     if (rc == RT_OK && hipEventRecord(b.done, st) != hipSuccess) rc = fail(ctx, "RT_OPT_SAMPLES_AHEAD: recording a batch's end failed");
