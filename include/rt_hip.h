@@ -199,6 +199,24 @@ int rt_scene_upload(rt_ctx* ctx, const rt_scene_desc* scene);
 int rt_scene_refit(rt_ctx* ctx, const rt_triangle* triangles, uint32_t num_triangles);
 int rt_scene_refit_buffer(rt_ctx* ctx, rt_buffer* triangles);
 
+/* The scene's OBJECTS moved, each by one 3x4 matrix (the door that opens): 12 floats per object instead of 160 bytes per triangle.
+ *   rt_scene_set_objects, after rt_scene_upload on a context with RT_CTX_OPT_REFITTABLE = 1: object_of_triangle[num_triangles] (the upload's BVH order), every
+ *     entry < num_objects, is copied to the device; the scene's CURRENT pose becomes the rest pose (made from the shading records: positions, normals, texture
+ *     coordinates, mtl_index -- every field a refit reads); the staging area of a pose is allocated, so rt_scene_pose allocates nothing.  324 bytes per triangle
+ *     (rest pose 160, object index 4, staging area 160; rt_scene_tree_report's "posed objects" line).  Refused, with what an earlier call set left in place: a NULL
+ *     argument, no scene, a scene that is not refittable, another triangle count, num_objects == 0, an index >= num_objects.  Calling it again replaces indices
+ *     and rest pose; rt_scene_upload drops both; rt_scene_refit* leaves both alone (the rest pose is what set_objects saw, not the last refit).
+ *   rt_scene_pose: matrices3x4[num_objects * 12], row-major, m[0..3] = row x (three linear terms, then the translation).  Poses are ABSOLUTE: every call poses
+ *     the rest pose, so M1 then M2 equals M2 alone.  position' = ((m0 x + m1 y) + m2 z) + m3 per row; normal' = the cofactor matrix of the 3x3 part times the
+ *     normal, times -1 if det < 0, normalised if its squared length is positive and finite; texture coordinates and mtl_index are copied; an object whose matrix is
+ *     bit for bit the identity's is copied, so posing everything by the identity gives the rest pose back byte for byte.  k_pose_triangles writes the staging
+ *     area and the refit above runs on it unchanged: afterwards the context is, for every entry point and option, bit for bit what rt_scene_refit of
+ *     rt_debug_pose(NULL, ...)'s output would have left (validation first, so an overflowing pose is refused with the scene untouched; quiescence; the kept
+ *     previous pose of RT_CTX_OPT_REFIT_MOTION; the report's "refit" line).  Refused before any launch: a NULL argument, no objects set, another num_objects, a
+ *     non-finite matrix entry, everything rt_scene_refit refuses. */
+int rt_scene_set_objects(rt_ctx* ctx, const uint32_t* object_of_triangle, uint32_t num_triangles, uint32_t num_objects);
+int rt_scene_pose(rt_ctx* ctx, const float* matrices3x4, uint32_t num_objects);
+
 /* One fold adaptation per process GROUP instead of one per rank (N ranks that tile one image hold the same scene and would each probe, rotate and fold for
  * identical records): the context's current 4-wide records -- the closest-hit rays' and the shadow rays' (n_shadow == 0: they share), as adapted so far -- to
  * host buffers of `capacity` records each (records NULL: size query; entries2 = {closest entry, shadow entry}), and into another context that has uploaded
@@ -620,6 +638,11 @@ int rt_debug_wide_bvh(const rt_bvh_node* nodes, uint32_t num_nodes, int collapse
 #define RT_REFIT_DISQUALIFIED 2
 int rt_debug_refit(rt_ctx* ctx, const rt_bvh_node* nodes, uint32_t num_nodes, const rt_triangle* triangles, uint32_t num_triangles, const void* records, uint32_t num_records,
                    uint32_t entry_ref, rt_bvh_node* out_nodes, void* out_records);
+/* The pose on its own: out[num_triangles] = rest[num_triangles] with triangle i posed by matrix object_of_triangle[i] (rt_scene_pose's arithmetic; .w lanes,
+ * texture coordinates, mtl_index and padding copied).  ctx == NULL: the host restatement; otherwise k_pose_triangles on uploaded copies, on ctx's device (the two
+ * agree bit for bit).  Refused: a NULL array, no triangles, no objects, an index >= num_objects, a non-finite matrix entry. */
+int rt_debug_pose(rt_ctx* ctx, const rt_triangle* rest, const uint32_t* object_of_triangle, uint32_t num_triangles, const float* matrices3x4, uint32_t num_objects,
+                  rt_triangle* out);
 /* What the last rt_scene_upload measured when it chose the trees (one line per ray population; "" when it had no choice), then the
  * latest fold adaptation's line (RT_CTX_OPT_ADAPTIVE_FOLD).  The pointer is valid until the next rt_integrate or rt_scene_upload on
  * this context (an adaptation rewrites its line): copy it. */

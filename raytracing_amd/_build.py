@@ -41,7 +41,7 @@ def hipcc():
     raise RuntimeError("hipcc not found")
 
 
-# librt_hip.so = five translation units (round 6; rt_hip.hip alone was 3 600 lines): the C-ABI with the hot path's kernels, the tree work on the device
+# librt_hip.so = several translation units (rt_hip.hip alone was 3 600 lines): the C-ABI with the hot path's kernels, the tree work on the device
 # (a code object of its own: the hot path's is not rebuilt or re-hashed when the builder changes), the spatial and temporal filters' kernels (likewise), and the host
 # side of the tree work.
 HIP_UNITS = [
@@ -49,6 +49,7 @@ HIP_UNITS = [
     ("device_fold", "device_fold.hip", True),  # fold_kernels.h + its host driver
     ("filters", "filters.hip", True),          # the guide pass, the spatial filter's a-trous passes, the temporal filter's stages (a code object of its own, like device_fold's)
     ("refit", "refit.hip", True),              # the refit of the scene's trees when its triangles move: kernels + their host driver + the host restatement (a code object of its own)
+    ("pose", "pose.hip", True),                # the scene's objects posed from one matrix per object: kernels + host driver + the host restatement (a code object of its own)
     ("wide_bvh", "wide_bvh.cpp", False),       # build_wide_bvh, pair layout, the adaptation's host walks (no device code)
 ]
 

@@ -109,6 +109,7 @@ EXPORTS = [
     "rt_frame_filter", "rt_frame_read_guides", "rt_debug_filter",
     "rt_frame_filter_temporal", "rt_frame_filter_history_reset", "rt_frame_read_filter_history", "rt_debug_filter_temporal",
     "rt_scene_refit", "rt_scene_refit_buffer", "rt_debug_refit",
+    "rt_scene_set_objects", "rt_scene_pose", "rt_debug_pose",
     "rt_frame_read_guide_motion", "rt_debug_guide_motion", "rt_debug_filter_temporal_motion",
 ]
 
@@ -189,6 +190,8 @@ def load():
         "rt_debug_filter_temporal": (i32, [vp, u32, u32, vp, vp] + [vp] * 8 + [C.POINTER(rt_temporal_filter_desc), vp, vp, vp]),
         "rt_scene_refit": (i32, [vp, vp, u32]), "rt_scene_refit_buffer": (i32, [vp, vp]),
         "rt_debug_refit": (i32, [vp, vp, u32, vp, u32, vp, u32, u32, vp, vp]),
+        "rt_scene_set_objects": (i32, [vp, vp, u32, u32]), "rt_scene_pose": (i32, [vp, vp, u32]),
+        "rt_debug_pose": (i32, [vp, vp, vp, u32, vp, u32, vp]),
         "rt_frame_read_guide_motion": (i32, [vp, vp, vp]),
         "rt_debug_guide_motion": (i32, [vp, u32, vp, vp, u32, vp, vp]),
         "rt_debug_filter_temporal_motion": (i32, [vp, u32, u32, vp, vp] + [vp] * 10 + [C.POINTER(rt_temporal_filter_desc), vp, vp, vp]),
@@ -308,6 +311,32 @@ def debug_refit(ctx, nodes, triangles, records=None, entry=0):
     if rc not in (0, 2):
         raise RtError(lib.rt_last_error(handle).decode())
     return out_nodes, out_recs, rc == 2
+
+
+def _matrices3x4(matrices, who):
+    m = np.ascontiguousarray(matrices, np.float32)
+    if m.ndim == 2 and m.shape[1] == 12:
+        m = m.reshape(-1, 3, 4)
+    if m.ndim != 3 or m.shape[1:] != (3, 4):
+        raise RtError(who + ": matrices must be float32[num_objects, 3, 4]")
+    return m
+
+
+def debug_pose(ctx, rest, object_of_triangle, matrices, num_objects=None):
+    """rt_debug_pose: `rest` (types.triangle) with triangle i posed by matrices[object_of_triangle[i]] (float32[num_objects, 3, 4], row-major, the translation in
+    the fourth column).  ctx None = the host restatement, else pose.hip's kernel on ctx's GPU.  Returns the posed triangles."""
+    lib = load()
+    tris = np.ascontiguousarray(rest, T.triangle)
+    ids = np.ascontiguousarray(object_of_triangle, np.uint32)
+    if ids.shape != (len(tris),):
+        raise RtError("debug_pose: one object index per triangle")
+    m = _matrices3x4(matrices, "debug_pose")
+    out = np.zeros_like(tris)
+    handle = ctx.handle if ctx is not None else None
+    rc = lib.rt_debug_pose(handle, tris.ctypes.data, ids.ctypes.data, len(tris), m.ctypes.data, len(m) if num_objects is None else num_objects, out.ctypes.data)
+    if rc != 0:
+        raise RtError(lib.rt_last_error(handle).decode())
+    return out
 
 
 def choose_tree(scene, shadow=True, mode=1):
@@ -524,6 +553,20 @@ class Context:
         if t.dtype != T.triangle:
             raise RtError("refit_scene: triangles has the wrong dtype")
         _check(self.lib, self.handle, self.lib.rt_scene_refit(self.handle, t.ctypes.data, len(t)))
+
+    def set_objects(self, object_of_triangle, num_objects):
+        """rt_scene_set_objects: which object each triangle of the uploaded scene belongs to (uint32, the upload's order).  The scene's current pose becomes the
+        rest pose of pose_scene(); needs set_refittable() before upload_scene().  324 bytes per triangle on the device."""
+        ids = np.ascontiguousarray(object_of_triangle, np.uint32)
+        if ids.ndim != 1:
+            raise RtError("set_objects: one object index per triangle")
+        _check(self.lib, self.handle, self.lib.rt_scene_set_objects(self.handle, ids.ctypes.data, len(ids), num_objects))
+
+    def pose_scene(self, matrices):
+        """rt_scene_pose: the rest pose posed by one matrix per object (float32[num_objects, 3, 4]; absolute, never relative to the last pose), written on the
+        device and refitted as refit_scene() would.  Frames keep their sums: reset() them."""
+        m = _matrices3x4(matrices, "pose_scene")
+        _check(self.lib, self.handle, self.lib.rt_scene_pose(self.handle, m.ctypes.data, len(m)))
 
     def create_buffer(self, data):
         """an rt_buffer of this context holding `data` (any contiguous array)"""

@@ -26,6 +26,7 @@
 #include "wide_bvh.h"        // the host-side fold, the pair layout, the adaptation's host walks (wide_bvh.cpp)
 #include "device_fold.h"     // ... and the fold + crossing counts on the device (device_fold.hip)
 #include "refit.h"           // the refit of the scene's trees when its triangles move (refit.hip)
+#include "pose_host.h"       // the scene's objects posed from one matrix per object (pose.hip)
 #include "filters_host.h"         // the filters' guide pass, a-trous passes and temporal stages (filters.hip)
 using namespace rtw;
 
@@ -86,6 +87,8 @@ struct Scene
     // allocation failed: treated as off).  pose_valid: a refit has filled it.
     void* pose_snap = nullptr;
     bool pose_valid = false;
+    // rt_scene_set_objects (pose_impl.h): the rest pose, every triangle's object and the staging area of rt_scene_pose; nullptr = no objects set
+    pose::State* pose = nullptr;
 };
 } // namespace
 
@@ -474,6 +477,7 @@ void free_scene(Scene& s)
     if (s.adapt) drop_fold_adapt(s.adapt);
     if (s.refit) { refit::release(*s.refit); delete s.refit; }
     if (s.pose_snap) (void)hipFree(s.pose_snap);
+    if (s.pose) { pose::release(*s.pose); delete s.pose; }
     s = Scene();
 }
 
@@ -1051,6 +1055,7 @@ struct Upload
 extern "C" {
 
 #include "refit_impl.h"
+#include "pose_impl.h"
 
 // ---- scene -----------------------------------------------------------------
 int rt_scene_upload(rt_ctx* ctx, const rt_scene_desc* sd)

@@ -25,6 +25,8 @@ EXPORTS = [
     "rth_render_set_blue_noise_path", "rth_render_reserve_samples", "rth_scene_save_cache", "rth_load_jpeg",
     "rth_render_upload_gpu_data", "rth_render_setup_seconds", "rth_render_create_with_options",
     "rth_render_set_refittable", "rth_render_refit", "rth_render_set_refit_motion",
+    "rth_render_set_objects", "rth_render_pose",
+    "rth_scene_set_triangle_objects", "rth_scene_num_objects", "rth_scene_object_name", "rth_scene_num_triangle_objects", "rth_scene_triangle_objects",
 ]
 
 
@@ -43,6 +45,8 @@ def load():
         "rth_scene_emissive_nee": (i32, [vp]),
         "rth_scene_from_arrays": (vp, [vp, u32, vp, u32, vp, u32, vp, u32]),
         "rth_scene_destroy": (None, [vp]),
+        "rth_scene_set_triangle_objects": (i32, [vp, vp, u32, vp, u32]), "rth_scene_num_objects": (u32, [vp]), "rth_scene_object_name": (cp, [vp, u32]),
+        "rth_scene_num_triangle_objects": (u32, [vp]), "rth_scene_triangle_objects": (vp, [vp]),
         "rth_scene_add_directional_light": (None, [vp] + [f32] * 6),
         "rth_scene_add_point_light": (None, [vp] + [f32] * 6),
         "rth_scene_set_env_path": (None, [vp, cp]), "rth_scene_set_env_image": (i32, [vp, vp, u32, u32]),
@@ -68,6 +72,7 @@ def load():
         "rth_render_frame_handle": (vp, [vp]), "rth_render_ctx_handle": (vp, [vp]), "rth_render_upload_gpu_data": (i32, [vp]),
         "rth_render_set_refittable": (i32, [vp, i32]), "rth_render_refit": (i32, [vp, vp, u32]),
         "rth_render_set_refit_motion": (i32, [vp, i32]),
+        "rth_render_set_objects": (i32, [vp, vp, u32, u32]), "rth_render_pose": (i32, [vp, vp, u32]),
         "rth_render_num_nodes": (u32, [vp]), "rth_render_nodes": (vp, [vp]),
         "rth_render_set_aov": (i32, [vp, i32]), "rth_render_resolve": (i32, [vp, vp]),
         "rth_render_set_blue_noise_path": (i32, [vp, cp]),
@@ -140,8 +145,10 @@ class Scene:
     _GETTERS = (("triangles", T.triangle), ("materials", T.packed_material), ("textures", T.texture),
                 ("texture_data", np.uint32), ("lights", T.light), ("emissive", np.uint32))
 
-    def __init__(self, path=None, scale=1.0, flip_yz=False, arrays=None, wide_texture_indices=False, emissive_nee=False):
-        """wide_texture_indices / emissive_nee: this repository's opt-in extensions (rt::Scene::Options)"""
+    def __init__(self, path=None, scale=1.0, flip_yz=False, arrays=None, wide_texture_indices=False, emissive_nee=False, objects=False):
+        """wide_texture_indices / emissive_nee / objects: this repository's opt-in extensions (rt::Scene::Options).  objects=True numbers the OBJ's o / g
+        shapes; with arrays=, `objects` (or arrays["objects"]) is the object index of every triangle (uint32).  Either way object_names() and, after
+        build_bvh() and finalize(), triangle_objects() say which triangles are which object: what Render.set_objects() takes."""
         self.lib = load()
         self.bvh = None
         if arrays is not None:
@@ -157,9 +164,14 @@ class Scene:
                     raise _err(self.lib)
             if self.handle and emissive_nee:
                 self.lib.rth_scene_set_emissive_nee(self.handle, 1)
+            ids = a.get("objects") if objects is False or objects is None else objects
+            if self.handle and ids is not None and ids is not True:
+                ids = np.ascontiguousarray(ids, np.uint32)
+                if self.lib.rth_scene_set_triangle_objects(self.handle, ids.ctypes.data, ids.size, None, 0):
+                    raise _err(self.lib)
         else:
             self.handle = self.lib.rth_scene_load_ex(path.encode(), scale, int(flip_yz),
-                                                     (1 if wide_texture_indices else 0) | (2 if emissive_nee else 0))
+                                                     (1 if wide_texture_indices else 0) | (2 if emissive_nee else 0) | (4 if objects else 0))
         if not self.handle:
             raise _err(self.lib)
 
@@ -187,6 +199,15 @@ class Scene:
     def finalize(self):
         if self.lib.rth_scene_finalize(self.handle):
             raise _err(self.lib)
+
+    def object_names(self):
+        """Scene::GetObjectNames: the OBJ's o / g shapes in file order (objects=True); unnamed objects are ''"""
+        return [self.lib.rth_scene_object_name(self.handle, i).decode() for i in range(self.lib.rth_scene_num_objects(self.handle))]
+
+    def triangle_objects(self):
+        """Scene::GetTriangleObjects: the object of every triangle, in the triangles' order after build_bvh() and finalize() (empty before)"""
+        n = self.lib.rth_scene_num_triangle_objects(self.handle)
+        return _arr(self.lib.rth_scene_triangle_objects(self.handle), n, np.uint32).copy() if n else np.zeros(0, np.uint32)
 
     def save_cache(self, path):
         """Binary scene cache: reordered triangles + BVH nodes + materials + textures; Scene(path) loads it."""
@@ -310,6 +331,24 @@ class Render:
         if t.dtype != T.triangle:
             raise RtError("refit: triangles has the wrong dtype")
         self._c(self.lib.rth_render_refit(self.handle, t.ctypes.data, len(t)))
+
+    def set_objects(self, object_of_triangle, num_objects):
+        """Which object each triangle belongs to (uint32, the BVH order of scene_arrays()['triangles']), after set_refittable(): the scene's current pose
+        becomes the rest pose of pose().  An upload (set_refittable, set_ctx_option, ...) drops the objects: set them again."""
+        ids = np.ascontiguousarray(object_of_triangle, np.uint32)
+        if ids.ndim != 1:
+            raise RtError("set_objects: one object index per triangle")
+        self._c(self.lib.rth_render_set_objects(self.handle, ids.ctypes.data, len(ids), num_objects))
+
+    def pose(self, matrices):
+        """The scene's objects moved: one row-major 3x4 matrix per object (float32[num_objects, 3, 4] or [num_objects, 12], the translation in the fourth column), always applied to
+        the rest pose.  The posed triangles are written and refitted on the device and the accumulation restarts; results equal refit() of the same triangles."""
+        from . import capi
+        try:
+            m = capi._matrices3x4(matrices, "pose")
+        except capi.RtError as e:
+            raise RtError(str(e))
+        self._c(self.lib.rth_render_pose(self.handle, m.ctypes.data, len(m)))
 
     def tree_report(self):
         from . import capi

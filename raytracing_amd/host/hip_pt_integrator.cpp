@@ -158,6 +158,17 @@ void HIPPathTraceIntegrator::RefitGeometry(Triangle const* triangles, std::size_
     RequestReset();
 }
 
+void HIPPathTraceIntegrator::SetObjects(std::uint32_t const* object_of_triangle, std::size_t triangle_count, std::uint32_t object_count)
+{
+    Check(rt_scene_set_objects(context_.Get(), object_of_triangle, (uint32_t)triangle_count, object_count));
+}
+
+void HIPPathTraceIntegrator::PoseObjects(float const* matrices3x4, std::size_t object_count)
+{
+    Check(rt_scene_pose(context_.Get(), matrices3x4, (uint32_t)object_count));
+    RequestReset();
+}
+
 void HIPPathTraceIntegrator::SetCameraData(Camera const& camera)
 {
     prev_camera_ = camera_;

@@ -96,6 +96,12 @@ public:
     // next ResolveRadiance() after a RefitGeometry filters with the history followed across the move instead of dropped.  Effective at the next
     // UploadGPUData; throws unless SetRefittable(true) came first.  One pose deep: resolve once per refit.
     void SetRefitMotion(bool on);
+    // Posed objects (rt_scene_set_objects / rt_scene_pose), after SetRefittable(true) and UploadGPUData.  SetObjects: every triangle's
+    // object (the uploaded BVH order); the scene's current pose becomes the rest pose; dropped by the next UploadGPUData.  PoseObjects: one row-major 3x4 matrix
+    // per object, 12 floats each, absolute (always applied to the rest pose); the triangles are written and refitted on the device; requests a reset.  Both throw
+    // HIPException with the library's message on a refusal.
+    void SetObjects(std::uint32_t const* object_of_triangle, std::size_t triangle_count, std::uint32_t object_count);
+    void PoseObjects(float const* matrices3x4, std::size_t object_count);
     rt_frame* GetFrame() const { return frame_; }
 
 protected:

@@ -27,7 +27,7 @@ void* rth_scene_load(const char* path, float scale, int flip_yz)
     return guard([&]() -> void* { return new rt::Scene(path, scale, flip_yz != 0); }, nullptr);
 }
 
-// options: rt::Scene::Options (1 = wide texture indices, 2 = emissive-triangle next-event estimation)
+// options: rt::Scene::Options (1 = wide texture indices, 2 = emissive-triangle next-event estimation, 4 = number the OBJ's o / g shapes)
 void* rth_scene_load_ex(const char* path, float scale, int flip_yz, unsigned options)
 {
     return guard([&]() -> void* { return new rt::Scene(path, scale, flip_yz != 0, options); }, nullptr);
@@ -54,6 +54,20 @@ void* rth_scene_from_arrays(const rt_triangle* tris, uint32_t ntris, const rt_pa
         return new rt::Scene(std::move(t), std::move(m), std::move(tx), std::move(td));
     }, nullptr);
 }
+
+// kObjects / SetTriangleObjects: names may be NULL (the objects are then unnamed)
+int rth_scene_set_triangle_objects(void* s, const uint32_t* ids, uint32_t n, const char* const* names, uint32_t num_names)
+{
+    return guard([&]() {
+        std::vector<std::string> nm;
+        for (uint32_t k = 0; names && k < num_names; ++k) nm.emplace_back(names[k]);
+        ((rt::Scene*)s)->SetTriangleObjects(std::vector<uint32_t>(ids, ids + n), std::move(nm));
+        return 0; }, 1);
+}
+uint32_t rth_scene_num_objects(void* s) { return (uint32_t)((rt::Scene*)s)->GetObjectNames().size(); }
+const char* rth_scene_object_name(void* s, uint32_t i) { return ((rt::Scene*)s)->GetObjectNames()[i].c_str(); }
+uint32_t rth_scene_num_triangle_objects(void* s) { return (uint32_t)((rt::Scene*)s)->GetTriangleObjects().size(); }
+const void* rth_scene_triangle_objects(void* s) { return ((rt::Scene*)s)->GetTriangleObjects().data(); }
 
 void rth_scene_destroy(void* s) { delete (rt::Scene*)s; }
 void rth_scene_add_directional_light(void* s, float dx, float dy, float dz, float r, float g, float b)
@@ -237,6 +251,11 @@ void* rth_render_ctx_handle(void* r) { return ((rt::Render*)r)->GetContext().Get
 int rth_render_set_refittable(void* r, int on) { return guard([&]() { ((rt::Render*)r)->SetRefittable(on != 0); return 0; }, 1); }
 int rth_render_set_refit_motion(void* r, int on) { return guard([&]() { ((rt::Render*)r)->SetRefitMotion(on != 0); return 0; }, 1); }
 int rth_render_refit(void* r, const void* triangles, uint32_t count) { return guard([&]() { ((rt::Render*)r)->RefitGeometry((const rt::Triangle*)triangles, count); return 0; }, 1); }
+int rth_render_set_objects(void* r, const uint32_t* object_of_triangle, uint32_t num_triangles, uint32_t num_objects)
+{
+    return guard([&]() { ((rt::Render*)r)->SetObjects(object_of_triangle, num_triangles, num_objects); return 0; }, 1);
+}
+int rth_render_pose(void* r, const float* matrices3x4, uint32_t num_objects) { return guard([&]() { ((rt::Render*)r)->PoseObjects(matrices3x4, num_objects); return 0; }, 1); }
 int rth_render_upload_gpu_data(void* r) { return guard([&]() { ((rt::Render*)r)->UploadGPUData(); return 0; }, 1); }
 
 } // extern "C"

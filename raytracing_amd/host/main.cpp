@@ -34,6 +34,9 @@ int main(int argc, char** argv)
         rt_temporal_filter_desc temporal = RT_TEMPORAL_FILTER_DESC_DEFAULT;
         bool moving = false;             // --camera_step dx,dy,dz: the camera moves by that much every --frames frame
         float camera_step[3] = {0.0f, 0.0f, 0.0f};
+        struct ObjectStep { unsigned object; float d[3]; };
+        std::vector<ObjectStep> object_steps;   // --object_step i,dx,dy,dz (repeatable): frame k poses object i by the translation k * (dx,dy,dz)
+        bool list_objects = false;              // --list_objects 1: print the OBJ's o / g shapes (index and name) and exit; needs no GPU
         for (int i = 1; i < argc; ++i)
         {
             auto next = [&]() -> const char* { if (i + 1 >= argc) { std::cerr << "missing value for " << argv[i] << "\n"; exit(2); } return argv[++i]; };
@@ -97,6 +100,18 @@ int main(int argc, char** argv)
                 }
                 moving = true;
             }
+            else if (!strcmp(argv[i], "--object_step"))
+            {
+                ObjectStep s;
+                if (sscanf(next(), "%u,%f,%f,%f", &s.object, &s.d[0], &s.d[1], &s.d[2]) != 4)
+                {
+                    std::cerr << "--object_step wants i,dx,dy,dz (an object index and three numbers)\n";
+                    return 2;
+                }
+                object_steps.push_back(s);
+                scene_options |= rt::Scene::kObjects;
+            }
+            else if (!strcmp(argv[i], "--list_objects")) { if (atoi(next()) != 0) { list_objects = true; scene_options |= rt::Scene::kObjects; } }
             else if (!strcmp(argv[i], "--help"))
             {
                 std::cout << "rt_render -w W -h H --scene file.obj [--scale s] [--flip_yz 0|1] [--spp n] [--bounces b]"
@@ -114,7 +129,10 @@ int main(int argc, char** argv)
                              "  --temporal_filter n [--temporal_alphas c,m] [--temporal_sigmas l,n,z] runs the temporal filter (SVGF; n a-trous\n"
                              "  iterations, 0 .. 8; the rest default to RT_TEMPORAL_FILTER_DESC_DEFAULT's) on every frame; whole images only\n"
                              "  --frames n --camera_step dx,dy,dz renders n frames of one sample each, the camera moving by (dx,dy,dz) every frame\n"
-                             "  (the reference's moving-camera loop: each frame is reset); --out then writes the last frame's image\n";
+                             "  (the reference's moving-camera loop: each frame is reset); --out then writes the last frame's image\n"
+                             "  --list_objects 1 prints the scene's objects (the OBJ's o / g shapes: index and name) and exits\n"
+                             "  --frames n --object_step i,dx,dy,dz (repeatable) poses object i by the translation k * (dx,dy,dz) in frame k, on the device\n"
+                             "  (rt_scene_pose: the scene is uploaded refittable, and with --temporal_filter the history follows the move); one GPU only\n";
                 return 0;
             }
         }
@@ -146,6 +164,11 @@ int main(int argc, char** argv)
             std::cerr << "--camera_step needs --frames n\n";
             return 2;
         }
+        if (!object_steps.empty() && (frames == 0 || gpus > 1 || tiled_path))
+        {
+            std::cerr << "--object_step needs --frames n and one GPU\n";
+            return 2;
+        }
         if (plan_only)
         {
             // which rows each GPU renders (TiledRender::TileRows = rt_frame_desc's rule); needs neither a GPU nor the scene
@@ -163,6 +186,17 @@ int main(int argc, char** argv)
         }
         rt::Scene scene(scene_path.c_str(), scale, flip_yz, scene_options);
         scene.AddDirectionalLight({-0.6f, -1.5f, 3.5f}, {15.0f, 10.0f, 5.0f});   // main.cpp:58
+        if (list_objects)
+        {
+            for (std::size_t k = 0; k < scene.GetObjectNames().size(); ++k) std::cout << k << " " << scene.GetObjectNames()[k] << std::endl;
+            return 0;
+        }
+        for (const ObjectStep& s : object_steps)
+            if (s.object >= scene.GetObjectNames().size())
+            {
+                std::cerr << "--object_step: the scene has " << scene.GetObjectNames().size() << " objects (--list_objects 1)\n";
+                return 2;
+            }
         if (gpus > 1 || tiled_path)
         {
             std::vector<int> devices;
@@ -209,16 +243,37 @@ int main(int argc, char** argv)
         render.GetIntegrator().EnableWhiteFurnace(furnace);
         render.GetIntegrator().SetSpatialFilter(filter_iterations >= 0 ? &filter : nullptr);
         render.GetIntegrator().SetTemporalFilter(temporal_iterations >= 0 ? &temporal : nullptr);
-        if (moving)
+        const bool posing = !object_steps.empty();
+        if (posing)                                                           // effective at the loop's upload below
+        {
+            render.GetIntegrator().SetRefittable(true);
+            if (temporal_iterations >= 0) render.GetIntegrator().SetRefitMotion(true);
+        }
+        if (moving || posing)
         {
             // the reference's moving-camera loop (Render::RenderFrame: a changed camera resets the frame): frame i is one sample at the start camera
             // moved by i * camera_step, resolved (and filtered) at its end
             render.UploadGPUData();
             render.GetIntegrator().SetResolveEveryFrame(true);
             render.GetIntegrator().SetSamplesAhead(samples_ahead);
+            const std::size_t n_objects = scene.GetObjectNames().size();
+            if (posing) render.SetObjects(scene.GetTriangleObjects().data(), scene.GetTriangleObjects().size(), (std::uint32_t)n_objects);
+            std::vector<float> matrices(n_objects * 12, 0.0f);
             auto tf = std::chrono::steady_clock::now();
             for (unsigned i = 0; i < frames; ++i)
             {
+                if (posing)                                                   // every object the identity, the stepped ones translated by i * step
+                {
+                    for (std::size_t k = 0; k < n_objects; ++k)
+                    {
+                        float* m = &matrices[k * 12];
+                        for (int e = 0; e < 12; ++e) m[e] = 0.0f;
+                        m[0] = m[5] = m[10] = 1.0f;
+                    }
+                    for (const ObjectStep& s : object_steps)
+                        for (int a = 0; a < 3; ++a) matrices[(std::size_t)s.object * 12 + 4 * a + 3] += (float)i * s.d[a];
+                    render.PoseObjects(matrices.data(), n_objects);
+                }
                 rt::Camera c = cam;
                 c.position.x = cam.position.x + (float)i * camera_step[0];
                 c.position.y = cam.position.y + (float)i * camera_step[1];
@@ -228,7 +283,7 @@ int main(int argc, char** argv)
             }
             std::vector<float> const& img = render.GetIntegrator().GetResolvedImage();
             double df = std::chrono::duration<double>(std::chrono::steady_clock::now() - tf).count();
-            std::cout << frames << " moving-camera frames (one sample each" << (temporal_iterations >= 0 ? ", temporally filtered" : "") << ") in " << df
+            std::cout << frames << (posing ? (moving ? " moving-camera, posed-object" : " posed-object") : " moving-camera") << " frames (one sample each" << (temporal_iterations >= 0 ? ", temporally filtered" : "") << ") in " << df
                       << " s: " << df * 1e3 / frames << " ms per frame" << std::endl;
             if (!out.empty()) WritePFM(out.c_str(), img, width, height);     // the last frame's resolved (filtered), tone-mapped image
             return 0;

@@ -165,6 +165,16 @@ void TiledRender::RefitGeometry(Triangle const* triangles, std::size_t count)
     for (auto& i : integrators_) i->RefitGeometry(triangles, count);
 }
 
+void TiledRender::SetObjects(std::uint32_t const* object_of_triangle, std::size_t triangle_count, std::uint32_t object_count)
+{
+    for (auto& i : integrators_) i->SetObjects(object_of_triangle, triangle_count, object_count);
+}
+
+void TiledRender::PoseObjects(float const* matrices3x4, std::size_t object_count)
+{
+    for (auto& i : integrators_) i->PoseObjects(matrices3x4, object_count);
+}
+
 void TiledRender::SetMaxBounces(std::uint32_t max_bounces)
 {
     for (auto& i : integrators_) i->SetMaxBounces(max_bounces);

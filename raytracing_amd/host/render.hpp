@@ -37,6 +37,10 @@ public:
     // ... and SetRefitMotion(true) (after SetRefittable(true)) uploads it again with room for the pose each refit replaces: the temporal filter then follows
     // the moved surfaces across a RefitGeometry instead of dropping its history
     void SetRefitMotion(bool on) { integrator_->SetRefitMotion(on); UploadGPUData(); }
+    // Posed objects, after SetRefittable(true): which object each triangle belongs to (the finalised scene's BVH order), then one 3x4
+    // matrix per object and pose -- 12 floats per object instead of RefitGeometry's 160 bytes per triangle.  An upload drops the objects: set them again.
+    void SetObjects(std::uint32_t const* object_of_triangle, std::size_t triangle_count, std::uint32_t object_count) { integrator_->SetObjects(object_of_triangle, triangle_count, object_count); }
+    void PoseObjects(float const* matrices3x4, std::size_t object_count) { integrator_->PoseObjects(matrices3x4, object_count); }
     AccelerationStructure const& GetAccelerationStructure() const { return *acc_structure_; }
     std::uint32_t GetWidth() const { return width_; }
     std::uint32_t GetHeight() const { return height_; }
@@ -81,6 +85,9 @@ public:
     void RefitGeometry(Triangle const* triangles, std::size_t count);
     // forwarded too (the option only: the filters stay refused on tiles)
     void SetRefitMotion(bool on);
+    // posed objects, forwarded to every tile's context likewise (tiles work because the refit does)
+    void SetObjects(std::uint32_t const* object_of_triangle, std::size_t triangle_count, std::uint32_t object_count);
+    void PoseObjects(float const* matrices3x4, std::size_t object_count);
     void RenderSamples(std::uint32_t n);                  // every tile, concurrently; returns when all are enqueued and finished
     std::vector<float> GatherRadiance(int root = 0);      // height x width x RGBA running sums, image order
     rt_stats GetStats() const;                            // ray counters summed over the tiles

@@ -382,6 +382,7 @@ Scene::Scene(const char* filename, float scale, bool flip_yz, unsigned options)
 {
     wide_texture_indices_ = (options & kWideTextureIndices) != 0;
     emissive_nee_ = (options & kEmissiveNee) != 0;
+    number_objects_ = (options & kObjects) != 0;
     if (IsCacheFile(filename))
     {
         LoadCache(filename);
@@ -409,6 +410,19 @@ void Scene::SetMaterialTextureIndices(std::vector<std::uint16_t> indices)
     wide_texture_indices_ = !material_texture_indices_.empty();
 }
 
+void Scene::SetTriangleObjects(std::vector<std::uint32_t> const& object_of_triangle, std::vector<std::string> names)
+{
+    if (object_of_triangle.size() != triangles_.size()) throw std::runtime_error("SetTriangleObjects: one object index per triangle expected");
+    std::uint32_t count = 0;
+    for (std::uint32_t id : object_of_triangle) count = id >= count ? id + 1u : count;
+    if (names.empty()) names.resize(count);
+    if (count > names.size()) throw std::runtime_error("SetTriangleObjects: an object index has no name");
+    for (std::size_t i = 0; i < triangles_.size(); ++i) triangles_[i].padding[0] = object_of_triangle[i];
+    object_names_ = std::move(names);
+    triangle_objects_.clear();
+    objects_in_padding_ = true;
+}
+
 void Scene::Load(const char* filename, float scale, bool flip_yz)
 {
     std::string fname(filename);
@@ -423,7 +437,9 @@ void Scene::Load(const char* filename, float scale, bool flip_yz)
     std::vector<ObjMaterial> obj_materials;
     std::unordered_map<std::string, int> material_map;
     int material = -1;
-    struct Face { VertexIndex i[3]; int material; };
+    struct Face { VertexIndex i[3]; int material; std::uint32_t object; };
+    std::string shape_name;                                  // kObjects: the last o / g line's
+    std::vector<std::string> shapes;
     std::vector<Face> faces;
 
     std::string line;
@@ -463,7 +479,9 @@ void Scene::Load(const char* filename, float scale, bool flip_yz)
                 poly.push_back(vi);
                 t += strspn(t, " \t\r");
             }
-            auto emit = [&](int a, int b, int c) { faces.push_back(Face{{poly[a], poly[b], poly[c]}, material}); };
+            if (number_objects_ && (shapes.empty() || shapes.back() != shape_name)) shapes.push_back(shape_name);
+            const std::uint32_t object = shapes.empty() ? 0u : (std::uint32_t)shapes.size() - 1u;
+            auto emit = [&](int a, int b, int c) { faces.push_back(Face{{poly[a], poly[b], poly[c]}, material, object}); };
             if (poly.size() == 3) emit(0, 1, 2);
             else if (poly.size() == 4)
             {
@@ -506,6 +524,14 @@ void Scene::Load(const char* filename, float scale, bool flip_yz)
                 LoadMtl(folder.empty() ? mtl_base + lib : ResolveAssetPath(folder, lib), obj_materials, material_map);
                 if (obj_materials.size() > before) break;   // first library that loads wins
             }
+            continue;
+        }
+        if (number_objects_ && (t[0] == 'o' || t[0] == 'g') && IsSpace(t[1]))
+        {
+            t += 2;
+            t += strspn(t, " \t");
+            shape_name = t;
+            while (!shape_name.empty() && IsSpace(shape_name.back())) shape_name.pop_back();
             continue;
         }
         // o / g / s / others: no effect on the flattened triangle list
@@ -601,7 +627,9 @@ void Scene::Load(const char* filename, float scale, bool flip_yz)
         for (int k = 0; k < 3; ++k) { flip(vx[k].position); flip(vx[k].normal); }
         std::uint32_t mtl = (f.material >= 0 && (size_t)f.material < materials_.size()) ? (std::uint32_t)f.material : 0u;
         triangles_.emplace_back(vx[0], vx[1], vx[2], mtl);
+        if (number_objects_) triangles_.back().padding[0] = f.object;
     }
+    if (number_objects_) { object_names_ = std::move(shapes); objects_in_padding_ = true; }
     if (materials_.empty()) materials_.push_back(PackedMaterial{0, 0, 0, 0, 0});
 }
 
@@ -664,6 +692,12 @@ void Scene::AddDirectionalLight(float3 direction, float3 radiance)   // stores t
 
 void Scene::Finalize()   // scene.cpp:353-361
 {
+    if (objects_in_padding_)                                 // the indices have come through the BVH reorder: out of the triangles again
+    {
+        triangle_objects_.resize(triangles_.size());
+        for (std::size_t i = 0; i < triangles_.size(); ++i) { triangle_objects_[i] = triangles_[i].padding[0]; triangles_[i].padding[0] = 0u; }
+        objects_in_padding_ = false;
+    }
     CollectEmissiveTriangles();
     scene_info_.analytic_light_count = (std::uint32_t)lights_.size();
     if (!env_preset_)

@@ -26,7 +26,9 @@ public:
     //                        packed material (PackAlbedo's assert, scene.cpp:55; constants.h:35) -- a scene with more
     //                        textures fails to load without it
     //   kEmissiveNee:        next-event estimation also samples the emissive triangles (GetEmissiveIndices)
-    enum Options : unsigned { kWideTextureIndices = 1u, kEmissiveNee = 2u };
+    //   kObjects:            the OBJ's o / g shapes are numbered and every triangle remembers its shape (GetObjectNames, GetTriangleObjects: what
+    //                        rt_scene_set_objects / Render::SetObjects take).  Off, the loaded bytes are the reference's.
+    enum Options : unsigned { kWideTextureIndices = 1u, kEmissiveNee = 2u, kObjects = 4u };
     Scene(const char* filename, float scale, bool flip_yz, unsigned options);
     // Caller-built arrays (procedural scenes / binary caches); no file IO.
     Scene(std::vector<Triangle> triangles, std::vector<PackedMaterial> materials, std::vector<Texture> textures,
@@ -65,6 +67,14 @@ public:
     void SetEmissiveNee(bool enable) { emissive_nee_ = enable; }
     bool GetEmissiveNee() const { return emissive_nee_; }
     Image const& GetEnvImage() const { return env_image_; }
+    // extension (kObjects, or SetTriangleObjects for caller-built arrays): the objects' names, and after Finalize() the object of every triangle in the order
+    // the triangles then have (the BVH's).  On its way through Bvh::BuildCPU's reorder -- which copies whole Triangles -- an index rides in
+    // Triangle::padding[0], which no kernel, relayout or cache reads; Finalize() takes it out again, so the bytes that are uploaded hold zero there.
+    // A new shape begins where a face follows an o / g line whose name differs from the current shape's ("o x" + "g x" is one shape); faces before any
+    // such line belong to a shape named "".  A scene cache does not keep objects.
+    std::vector<std::string> const& GetObjectNames() const { return object_names_; }
+    std::vector<std::uint32_t> const& GetTriangleObjects() const { return triangle_objects_; }
+    void SetTriangleObjects(std::vector<std::uint32_t> const& object_of_triangle, std::vector<std::string> names);   // before the BVH is built
 
 private:
     void Load(const char* filename, float scale, bool flip_yz);
@@ -83,6 +93,10 @@ private:
     std::vector<std::uint16_t> material_texture_indices_;   // extension: see GetMaterialTextureIndices
     bool wide_texture_indices_ = false;
     bool emissive_nee_ = false;
+    bool number_objects_ = false;                           // kObjects
+    bool objects_in_padding_ = false;                       // between Load / SetTriangleObjects and Finalize
+    std::vector<std::string> object_names_;
+    std::vector<std::uint32_t> triangle_objects_;
     SceneInfo scene_info_ = {};
     Image env_image_;
     std::string env_path_ = "assets/ibl/CGSkies_0036_free.hdr";
