@@ -217,6 +217,49 @@ int rt_scene_refit_buffer(rt_ctx* ctx, rt_buffer* triangles);
 int rt_scene_set_objects(rt_ctx* ctx, const uint32_t* object_of_triangle, uint32_t num_triangles, uint32_t num_objects);
 int rt_scene_pose(rt_ctx* ctx, const float* matrices3x4, uint32_t num_objects);
 
+/* ---- ray queries: the CALLER's rays against the uploaded scene (opt-in extension).  Every other ray this library traces is one a frame
+ * generated; these are a host program's own: which object lies under a pixel, visibility and probe rays, baking over the uploaded trees, collision rays against
+ * a posed scene.
+ *   rays: rt_ray as the reference means it (trace_bvh.cl:148,28-73): origin.w = t_min, direction.w = t_max; a candidate hit is rejected when t < t_min ||
+ *     t > t_max, a box's entry distance is max(..., t_min).  t_min > t_max is therefore a miss.  A ray with a non-finite component in origin, direction, t_min
+ *     or t_max, and a ray whose direction is all zeros, is not walked: a miss (not occluded).
+ *   RT_QUERY_CLOSEST: hits[i] = bc, primitive_id (BVH order, as everywhere in this ABI) and t, bit for bit what the reference's IntersectRays gives that ray on
+ *     the scene's current triangles (its topology and near / far order decide ties); on a miss only primitive_id = RT_INVALID_ID is specified.  surfaces[i]:
+ *     the hit's surface (rt_surface).  At least one of hits / surfaces; occluded[i] (optional) = 1 on a hit.
+ *   RT_QUERY_ANY_HIT: occluded[i] = 1 when anything lies within [t_min, t_max], else 0 -- exact; WHICH triangle is not reported (the shadow rays' own tree visits
+ *     leaves in its own order: only the OR over all leaves is tree-independent).  hits and surfaces must be NULL.
+ * Closest-hit queries walk what a frame's closest-hit rays walk at the moment (the current 4-wide records, adapted folds included; the child-pair records with
+ * RT_CTX_OPT_WIDE_BVH = 0 or a tree that does not qualify), any-hit queries the shadow rays' tree.  A query runs on the context's stream, after every refit,
+ * pose or upload before it, and touches no frame: accumulation, samples traced ahead, guide caches, filter histories and rt_stats are as if it had not happened.
+ *   rt_scene_trace: host arrays, staged through device scratch the context keeps (grown on demand, chunks of at most 4 Mi rays: any n needs bounded memory;
+ *     rt_scene_tree_report's "ray queries" line has its size); returns when the outputs are written.
+ *   rt_scene_trace_buffer: rt_buffers of this context holding n records each (rt_ray / rt_hit / uint32_t / rt_surface); only enqueues -- rt_finish or
+ *     rt_buffer_read waits; allocates at most the walk's stack spill area.
+ * A traversal stack that ran over its bound (excluded by the bound's argument; checked all the same) is never silent: the query's kernel raises a
+ * flag, and the next call that waits for the context's stream -- rt_scene_trace itself, rt_finish, rt_buffer_read -- fails with that message and clears it.
+ * Refused with nothing launched: a NULL context, NULL rays with n > 0, no scene, an unknown mode, closest mode without hits and surfaces, any-hit mode with
+ * hits or surfaces or without occluded, a buffer of another context or smaller than n records.  n == 0 is RT_OK and does nothing. */
+#define RT_QUERY_CLOSEST 0u
+#define RT_QUERY_ANY_HIT 1u
+typedef struct rt_surface
+{
+    float position[3];         uint32_t primitive_id;   /* RT_INVALID_ID on a miss: every other field 0 then */
+    float geometric_normal[3]; uint32_t mtl_index;      /* normalize(cross(p2 - p1, p3 - p1)); zeros for a degenerate triangle */
+    float shading_normal[3];   uint32_t object;         /* rt_scene_set_objects' index of the triangle, RT_INVALID_ID if none set */
+    float texcoord[2];         float t;  uint32_t flags; /* bit 0: hit; bit 1: dot(direction, geometric_normal) > 0 (back face) */
+} rt_surface;
+int rt_scene_trace(rt_ctx* ctx, const rt_ray* rays, uint32_t n, uint32_t mode, rt_hit* hits_or_null, uint32_t* occluded_or_null, rt_surface* surfaces_or_null);
+int rt_scene_trace_buffer(rt_ctx* ctx, rt_buffer* rays, uint32_t n, uint32_t mode, rt_buffer* hits_or_null, rt_buffer* occluded_or_null, rt_buffer* surfaces_or_null);
+/* The closest hit of the ray through the CENTRE of pixel (x, y) -- image coordinates -- of the frame's current camera: the guide pass's ray (origin = the camera
+ * position, direction = the filters' pixel-centre direction, t_min 0, t_max RT_MAX_RENDER_DIST), so surface.shading_normal and |origin - position| are bit for
+ * bit rt_frame_read_guides' normal and depth of that pixel.  Any output may be NULL.  Refused: a NULL frame, no scene, x >= width or y >= height, a tile frame. */
+int rt_frame_pick(rt_frame* frame, uint32_t x, uint32_t y, rt_ray* ray_or_null, rt_hit* hit_or_null, rt_surface* surface_or_null);
+/* the surface records on their own: out[i] of rays[i] and hits[i] over caller triangles (object_of_triangle NULL: object = RT_INVALID_ID); a hit whose
+ * primitive_id is not below num_triangles counts as a miss.  ctx == NULL: the host restatement (query.h); otherwise k_query_surface on uploaded copies.  The
+ * two agree bit for bit. */
+int rt_debug_query_surface(rt_ctx* ctx_or_null, const rt_triangle* triangles, uint32_t num_triangles, const uint32_t* object_of_triangle_or_null,
+                           const rt_ray* rays, const rt_hit* hits, uint32_t n, rt_surface* out);
+
 /* One fold adaptation per process GROUP instead of one per rank (N ranks that tile one image hold the same scene and would each probe, rotate and fold for
  * identical records): the context's current 4-wide records -- the closest-hit rays' and the shadow rays' (n_shadow == 0: they share), as adapted so far -- to
  * host buffers of `capacity` records each (records NULL: size query; entries2 = {closest entry, shadow entry}), and into another context that has uploaded
@@ -716,4 +759,5 @@ int rt_debug_eval(rt_ctx* ctx, int fn, const float* a, const float* b, float* ou
 #ifdef __cplusplus
 }
 #endif
+RT_STATIC_ASSERT(sizeof(rt_surface) == 64, "rt_surface");
 #endif /* RT_HIP_H */

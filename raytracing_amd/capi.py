@@ -111,6 +111,7 @@ EXPORTS = [
     "rt_scene_refit", "rt_scene_refit_buffer", "rt_debug_refit",
     "rt_scene_set_objects", "rt_scene_pose", "rt_debug_pose",
     "rt_frame_read_guide_motion", "rt_debug_guide_motion", "rt_debug_filter_temporal_motion",
+    "rt_scene_trace", "rt_scene_trace_buffer", "rt_frame_pick", "rt_debug_query_surface",
 ]
 
 OPT_MAX_BOUNCES, OPT_WHITE_FURNACE, OPT_SAMPLER, OPT_AOV, OPT_DENOISER, OPT_DROP_LAST, OPT_PROFILE, OPT_TRACE_VARIANT, OPT_TRACE_WAVES, OPT_SAMPLES_IN_FLIGHT, OPT_SELECT_FORM_BOX, OPT_PACKET_BOUNCES, OPT_TRACE_TUNE, OPT_DEBUG_ALLOC_LIMIT, OPT_PATH_STATE_LIMIT_MB, OPT_PIPELINES, OPT_SHADE_PARTITION, OPT_OVERLAP_SHADOW, OPT_SMALL_LAUNCH_PATHS, OPT_COMPACT_LOG, OPT_DEBUG_LOG_POOL_DIV, OPT_TRACE_TAIL_LANES, OPT_TRACE_TAIL_PATHS, OPT_CHUNK_REFILL, OPT_STAGE_PIPES, OPT_FRAME_KERNEL, OPT_SAMPLES_AHEAD = range(27)
@@ -195,6 +196,9 @@ def load():
         "rt_frame_read_guide_motion": (i32, [vp, vp, vp]),
         "rt_debug_guide_motion": (i32, [vp, u32, vp, vp, u32, vp, vp]),
         "rt_debug_filter_temporal_motion": (i32, [vp, u32, u32, vp, vp] + [vp] * 10 + [C.POINTER(rt_temporal_filter_desc), vp, vp, vp]),
+        "rt_scene_trace": (i32, [vp, vp, u32, u32, vp, vp, vp]), "rt_scene_trace_buffer": (i32, [vp, vp, u32, u32, vp, vp, vp]),
+        "rt_frame_pick": (i32, [vp, u32, u32, vp, vp, vp]),
+        "rt_debug_query_surface": (i32, [vp, vp, u32, vp, vp, vp, u32, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -334,6 +338,44 @@ def debug_pose(ctx, rest, object_of_triangle, matrices, num_objects=None):
     out = np.zeros_like(tris)
     handle = ctx.handle if ctx is not None else None
     rc = lib.rt_debug_pose(handle, tris.ctypes.data, ids.ctypes.data, len(tris), m.ctypes.data, len(m) if num_objects is None else num_objects, out.ctypes.data)
+    if rc != 0:
+        raise RtError(lib.rt_last_error(handle).decode())
+    return out
+
+
+QUERY_CLOSEST, QUERY_ANY_HIT = 0, 1
+INVALID_ID = 0xFFFFFFFF
+
+
+def ray_records(rays):
+    """the one rule for a query's rays: types.ray records as they are, or float32[n, 8] = origin.xyz, t_min, direction.xyz, t_max per row"""
+    a = np.asarray(rays)
+    if a.dtype == T.ray:
+        return np.ascontiguousarray(a).reshape(-1)
+    a = np.ascontiguousarray(a, np.float32)
+    if a.ndim != 2 or a.shape[1] != 8:
+        raise RtError("rays must be types.ray records or float32[n, 8] (origin.xyz, t_min, direction.xyz, t_max)")
+    return a.view(T.ray).reshape(-1)
+
+
+def debug_query_surface(ctx, triangles, rays, hits, object_of_triangle=None):
+    """rt_debug_query_surface: the surface records (types.surface) of `hits` (types.hit) of `rays` over `triangles` (types.triangle); object_of_triangle
+    None = object 0xFFFFFFFF.  ctx None = the host restatement (csrc/query.h), else k_query_surface on ctx's GPU."""
+    lib = load()
+    tris = np.ascontiguousarray(triangles, T.triangle)
+    r = ray_records(rays)
+    h = np.ascontiguousarray(hits, T.hit)
+    if len(r) != len(h):
+        raise RtError("debug_query_surface: one hit per ray")
+    ids = None
+    if object_of_triangle is not None:
+        ids = np.ascontiguousarray(object_of_triangle, np.uint32)
+        if ids.shape != (len(tris),):
+            raise RtError("debug_query_surface: one object index per triangle")
+    out = np.zeros(len(r), T.surface)
+    handle = ctx.handle if ctx is not None else None
+    rc = lib.rt_debug_query_surface(handle, tris.ctypes.data if len(tris) else None, len(tris), ids.ctypes.data if ids is not None else None,
+                                    r.ctypes.data if len(r) else None, h.ctypes.data if len(h) else None, len(r), out.ctypes.data if len(r) else None)
     if rc != 0:
         raise RtError(lib.rt_last_error(handle).decode())
     return out
@@ -568,6 +610,29 @@ class Context:
         m = _matrices3x4(matrices, "pose_scene")
         _check(self.lib, self.handle, self.lib.rt_scene_pose(self.handle, m.ctypes.data, len(m)))
 
+    def trace(self, rays, any_hit=False, surfaces=False):
+        """rt_scene_trace: the caller's rays (ray_records' rule) against the uploaded scene.  Closest hits: types.hit[n], or (hits, types.surface[n]) with
+        surfaces=True.  any_hit=True: uint32[n], 1 where anything lies within [t_min, t_max]."""
+        r = ray_records(rays)
+        n = len(r)
+        p = lambda a: a.ctypes.data if a is not None and len(a) else None
+        if any_hit:
+            if surfaces:
+                raise RtError("trace: an any-hit query reports no surfaces")
+            occ = np.zeros(n, np.uint32)
+            _check(self.lib, self.handle, self.lib.rt_scene_trace(self.handle, p(r), n, QUERY_ANY_HIT, None, occ.ctypes.data, None))
+            return occ
+        hits = np.zeros(n, T.hit)
+        surf = np.zeros(n, T.surface) if surfaces else None
+        _check(self.lib, self.handle, self.lib.rt_scene_trace(self.handle, p(r), n, QUERY_CLOSEST, hits.ctypes.data, None, surf.ctypes.data if surfaces else None))
+        return (hits, surf) if surfaces else hits
+
+    def trace_buffer(self, rays, n, any_hit=False, hits=None, occluded=None, surfaces=None):
+        """rt_scene_trace_buffer: the same over Buffers of this context (n records each; an output that is not wanted is None).  Only enqueues:
+        Buffer.read() or finish() waits."""
+        h = lambda b: b.handle if b is not None else None
+        _check(self.lib, self.handle, self.lib.rt_scene_trace_buffer(self.handle, h(rays), n, QUERY_ANY_HIT if any_hit else QUERY_CLOSEST, h(hits), h(occluded), h(surfaces)))
+
     def create_buffer(self, data):
         """an rt_buffer of this context holding `data` (any contiguous array)"""
         return Buffer(self, data)
@@ -647,6 +712,13 @@ class Buffer:
     def write(self, data, offset=0):
         a = np.ascontiguousarray(data)
         _check(self.lib, self.ctx.handle, self.lib.rt_buffer_write(self.handle, offset, a.ctypes.data, a.nbytes))
+
+    def read(self, dtype, count, offset=0):
+        """rt_buffer_read (blocking): `count` records of `dtype` from byte `offset`"""
+        out = np.zeros(count, dtype)
+        if count:
+            _check(self.lib, self.ctx.handle, self.lib.rt_buffer_read(self.handle, offset, out.ctypes.data, out.nbytes))
+        return out
 
     def close(self):
         if self.handle:
@@ -732,6 +804,13 @@ class Frame:
         passes = C.c_uint32()
         self._c(self.lib.rt_frame_read_guides(self.handle, alb.ctypes.data, nrm.ctypes.data, dep.ctypes.data, C.byref(passes)))
         return alb, nrm, dep, passes.value
+
+    def pick(self, x, y):
+        """rt_frame_pick: (ray, hit, surface) -- types.ray, types.hit, types.surface scalars -- of the ray through the centre of pixel (x, y) of the
+        frame's current camera (the guide pass's ray)"""
+        ray, hit, surf = np.zeros(1, T.ray), np.zeros(1, T.hit), np.zeros(1, T.surface)
+        self._c(self.lib.rt_frame_pick(self.handle, x, y, ray.ctypes.data, hit.ctypes.data, surf.ctypes.data))
+        return ray[0], hit[0], surf[0]
 
     def guide_motion(self):
         """rt_frame_read_guide_motion: (previous position float32[h, w, 4] = (X', 1), previous normal float32[h, w, 4] = (n', 0)) of every pixel's first

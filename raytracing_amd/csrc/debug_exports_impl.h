@@ -22,7 +22,17 @@ int rt_debug_wide_bvh(const rt_bvh_node* nodes, uint32_t num_nodes, int collapse
     return RT_OK;
 }
 
-const char* rt_scene_tree_report(rt_ctx* ctx) { return ctx ? ctx->scene.tree_report.c_str() : ""; }
+const char* rt_scene_tree_report(rt_ctx* ctx)
+{
+    if (!ctx) return "";
+    if (ctx->query.bytes() == 0u || !ctx->scene.valid) return ctx->scene.tree_report.c_str();
+    // what the context keeps for its ray queries (query_host.h) is the context's, not the scene's: its line is added here, when the report is asked for
+    char line[200];
+    snprintf(line, sizeof(line), "ray queries: %.1f MB kept on the device (stack spill area %.1f MB + staging)\n", (double)ctx->query.bytes() / 1e6,
+        (double)ctx->query.spill_bytes() / 1e6);
+    ctx->report_out = ctx->scene.tree_report + line;
+    return ctx->report_out.c_str();
+}
 
 int rt_debug_device_fold(rt_ctx* ctx, const rt_bvh_node* nodes, uint32_t num_nodes, double iso_weight, const float* dirs, uint32_t n_dirs, const double* weights,
     void* records, uint32_t* roots, uint32_t capacity, uint32_t* num_records, uint32_t* entry_ref, double* seconds)

@@ -28,6 +28,7 @@
 #include "refit.h"           // the refit of the scene's trees when its triangles move (refit.hip)
 #include "pose_host.h"       // the scene's objects posed from one matrix per object (pose.hip)
 #include "filters_host.h"         // the filters' guide pass, a-trous passes and temporal stages (filters.hip)
+#include "query_host.h"      // caller-supplied rays traced against the uploaded scene (query.hip)
 using namespace rtw;
 
 namespace
@@ -123,6 +124,8 @@ struct rt_ctx
     std::vector<rt_frame*> frames;   // the frames alive on this context (rt_finish waits for their side streams too)
     uint8_t* blue_noise = nullptr;   // sobol[65536] | scramblingTile[131072] | rankingTile[131072]
     float* gamma_lut = nullptr;      // pow(byte / 255, 2.2f), 256 entries (k_fill_gamma_lut)
+    query::Scratch query;            // rt_scene_trace*: the walk's stack spill area and the host form's staging arrays (query_host.h)
+    std::string report_out;          // rt_scene_tree_report's answer when it has a "ray queries" line to add to the scene's report
 };
 
 struct rt_buffer
@@ -459,6 +462,16 @@ int dev_alloc_copy(rt_ctx* ctx, void** out, const void* src, size_t bytes)
     return RT_OK;
 }
 
+// Ray queries: the walk's status word (pinned host memory; bit 0: a traversal stack ran over its bound, query_kernels.h), read and cleared wherever the
+// context's stream has just been waited for -- rt_scene_trace, rt_finish, rt_buffer_read -- so that the buffer form's queries report it too.
+int query_check_status(rt_ctx* ctx, const char* who)
+{
+    volatile uint32_t* st = ctx->query.status;
+    if (!st || *st == 0u) return RT_OK;
+    *st = 0u;
+    return fail(ctx, std::string(who) + ": a ray query's traversal stack ran over its bound (a tree deeper than the walk's stack): that query's results are not valid");
+}
+
 // A device allocation with an owner (move-only in spirit: never copied): freed when the holder goes, unless release() has handed it on.
 struct DevMem
 {
@@ -541,6 +554,7 @@ int rt_ctx_destroy(rt_ctx* ctx)
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
     free_scene(ctx->scene);
+    query::release(ctx->query);
     if (ctx->blue_noise) (void)hipFree(ctx->blue_noise);
     if (ctx->gamma_lut) (void)hipFree(ctx->gamma_lut);
     (void)hipStreamDestroy(ctx->stream);
@@ -558,7 +572,7 @@ int rt_finish(rt_ctx* ctx)
     // (not for the banks of RT_OPT_SAMPLES_AHEAD: what they trace ahead is the library's own business until a later Integrate() consumes it)
     for (rt_frame* f : ctx->frames)
         if (!f->ahead_owner && sync_frame_streams(f) != RT_OK) return RT_ERROR;
-    return RT_OK;
+    return query_check_status(ctx, "rt_finish");
 }
 
 int rt_ctx_device_info(rt_ctx* ctx, char* name, size_t name_len, int* compute_units, size_t* hbm_bytes)
@@ -683,7 +697,7 @@ int rt_buffer_read(rt_buffer* buf, size_t offset, void* dst, size_t bytes)
     if (offset + bytes > buf->bytes) return fail(buf->ctx, "rt_buffer_read: out of range");
     HIPCHK(buf->ctx, hipMemcpyAsync(dst, (char*)buf->ptr + offset, bytes, hipMemcpyDeviceToHost, buf->ctx->stream));
     HIPCHK(buf->ctx, hipStreamSynchronize(buf->ctx->stream));
-    return RT_OK;
+    return query_check_status(buf->ctx, "rt_buffer_read");
 }
 
 int rt_buffer_copy(rt_buffer* src, rt_buffer* dst, size_t src_offset, size_t dst_offset, size_t bytes)
@@ -1056,6 +1070,7 @@ extern "C" {
 
 #include "refit_impl.h"
 #include "pose_impl.h"
+#include "query_impl.h"
 
 // ---- scene -----------------------------------------------------------------
 int rt_scene_upload(rt_ctx* ctx, const rt_scene_desc* sd)

@@ -68,6 +68,27 @@ RT_DEV bool box_test_fast(float bminx, float bminy, float bminz, float bmaxx, fl
     return tmax >= tmin;
 }
 
+// RayTriangle (trace_bvh.cl:28-73) on a trace-triangle record (p1, e1 = p2 - p1, e2 = p3 - p1) with the ray's own [t_min, t_max]: true = accepted, with the
+// barycentrics and the distance.  The statement the walks' inline copies follow (v1_trace_ray, k_trace2, w4_trace_body: kept inline there -- the hot path's code
+// object is pinned byte for byte); k_query_trace calls it.
+RT_DEV bool ray_triangle(const f3 org, const f3 dir, const f3 p1, const f3 e1, const f3 e2, const float t_min, const float t_max, float& u_out, float& v_out, float& t_out)
+{
+    const f3 pvec = cross3(dir, e2);
+    const float det = dot3(e1, pvec);
+    if (det < 1e-8f || -det > 1e-8f) return false;
+    const float inv_det = 1.0f / det;
+    const f3 tvec = org - p1;
+    const float u = dot3(tvec, pvec) * inv_det;
+    if (u < 0.0f || u > 1.0f) return false;
+    const f3 qvec = cross3(tvec, e1);
+    const float v = dot3(dir, qvec) * inv_det;
+    if (v < 0.0f || u + v > 1.0f) return false;
+    const float t = dot3(e2, qvec) * inv_det;
+    if (t < t_min || t > t_max) return false;
+    u_out = u; v_out = v; t_out = t;
+    return true;
+}
+
 // AccumulateDirectSamples fused (accumulate_direct_samples.cl:46-52): k_shade logged the direct sample tentatively; an occluded
 // shadow ray zeroes that entry (adding +0.0 is the identity).  Entries beyond the inline rows live in the path's overflow block.
 RT_DEV void log_retract(const DLog& L, uint32_t entry, uint32_t id)

@@ -25,7 +25,7 @@ EXPORTS = [
     "rth_render_set_blue_noise_path", "rth_render_reserve_samples", "rth_scene_save_cache", "rth_load_jpeg",
     "rth_render_upload_gpu_data", "rth_render_setup_seconds", "rth_render_create_with_options",
     "rth_render_set_refittable", "rth_render_refit", "rth_render_set_refit_motion",
-    "rth_render_set_objects", "rth_render_pose",
+    "rth_render_set_objects", "rth_render_pose", "rth_render_pick", "rth_render_integrator_pick", "rth_render_trace",
     "rth_scene_set_triangle_objects", "rth_scene_num_objects", "rth_scene_object_name", "rth_scene_num_triangle_objects", "rth_scene_triangle_objects",
 ]
 
@@ -73,6 +73,7 @@ def load():
         "rth_render_set_refittable": (i32, [vp, i32]), "rth_render_refit": (i32, [vp, vp, u32]),
         "rth_render_set_refit_motion": (i32, [vp, i32]),
         "rth_render_set_objects": (i32, [vp, vp, u32, u32]), "rth_render_pose": (i32, [vp, vp, u32]),
+        "rth_render_pick": (i32, [vp, u32, u32, vp, vp, vp]), "rth_render_integrator_pick": (i32, [vp, u32, u32, vp, vp, vp]), "rth_render_trace": (i32, [vp, vp, u32, i32, vp, vp, vp]),
         "rth_render_num_nodes": (u32, [vp]), "rth_render_nodes": (vp, [vp]),
         "rth_render_set_aov": (i32, [vp, i32]), "rth_render_resolve": (i32, [vp, vp]),
         "rth_render_set_blue_noise_path": (i32, [vp, cp]),
@@ -349,6 +350,37 @@ class Render:
         except capi.RtError as e:
             raise RtError(str(e))
         self._c(self.lib.rth_render_pose(self.handle, m.ctypes.data, len(m)))
+
+    def pick(self, x, y):
+        """What lies under the centre of pixel (x, y) of the Render's current camera, also one set since the last frame (Render::Pick; the frame is not touched): a dict of the surface's fields (primitive_id
+        0xFFFFFFFF and zeros on a miss) plus `ray` and `hit`; when the scene was loaded with objects, also `object_name` of the triangle's object (None on a miss)"""
+        ray, hit, surf = np.zeros(1, T.ray), np.zeros(1, T.hit), np.zeros(1, T.surface)
+        self._c(self.lib.rth_render_pick(self.handle, x, y, ray.ctypes.data, hit.ctypes.data, surf.ctypes.data))
+        out = {k: (surf[0][k].copy() if surf[0][k].ndim else surf[0][k].item()) for k in T.surface.names}
+        out["ray"], out["hit"] = ray[0], hit[0]
+        names = self.scene.object_names()
+        if names:
+            objects = self.scene.triangle_objects()
+            prim = out["primitive_id"]
+            if out["object"] == 0xFFFFFFFF and prim < len(objects):
+                out["object"] = int(objects[prim])                      # no objects set on the device: the scene's own table says whose triangle it is
+            out["object_name"] = names[out["object"]] if prim != 0xFFFFFFFF and out["object"] < len(names) else None
+        return out
+
+    def trace(self, rays, any_hit=False, surfaces=False):
+        """The caller's rays against the scene as it is posed now (HIPPathTraceIntegrator::TraceRays; rays: types.ray records or float32[n, 8]): types.hit[n],
+        (hits, types.surface[n]) with surfaces=True, or uint32[n] verdicts with any_hit=True"""
+        from . import capi
+        r = capi.ray_records(rays)
+        n = len(r)
+        if any_hit:
+            occ = np.zeros(n, np.uint32)
+            self._c(self.lib.rth_render_trace(self.handle, r.ctypes.data if n else None, n, 1, None, occ.ctypes.data, None))
+            return occ
+        hits = np.zeros(n, T.hit)
+        surf = np.zeros(n, T.surface) if surfaces else None
+        self._c(self.lib.rth_render_trace(self.handle, r.ctypes.data if n else None, n, 0, hits.ctypes.data, None, surf.ctypes.data if surfaces else None))
+        return (hits, surf) if surfaces else hits
 
     def tree_report(self):
         from . import capi

@@ -18,6 +18,8 @@
 //   ResolveRadiance :677-684           -> rt_frame_resolve (the frame's only host sync)
 #include "hip_pt_integrator.hpp"
 #include <cstdio>
+#include <cstring>
+#include "spatial_filter.h"       // sf_guide_dir: the guide pass's pixel-centre direction (PickThrough shares it with rt_frame_pick)
 #include "acceleration_structure.hpp"
 #include "scene.hpp"
 
@@ -167,6 +169,39 @@ void HIPPathTraceIntegrator::PoseObjects(float const* matrices3x4, std::size_t o
 {
     Check(rt_scene_pose(context_.Get(), matrices3x4, (uint32_t)object_count));
     RequestReset();
+}
+
+void HIPPathTraceIntegrator::TraceRays(rt_ray const* rays, std::size_t count, bool any_hit, rt_hit* hits, std::uint32_t* occluded, rt_surface* surfaces)
+{
+    if (count > 0xFFFFFFFFull) throw HIPException("HIPPathTraceIntegrator::TraceRays: more than 2^32 - 1 rays in one call");
+    Check(rt_scene_trace(context_.Get(), rays, (uint32_t)count, any_hit ? RT_QUERY_ANY_HIT : RT_QUERY_CLOSEST, hits, occluded, surfaces));
+}
+
+void HIPPathTraceIntegrator::Pick(std::uint32_t x, std::uint32_t y, rt_ray* ray, rt_hit* hit, rt_surface* surface)
+{
+    Check(rt_frame_pick(frame_, x, y, ray, hit, surface));
+}
+
+void HIPPathTraceIntegrator::PickThrough(Camera const& camera, std::uint32_t x, std::uint32_t y, rt_ray* ray, rt_hit* hit, rt_surface* surface)
+{
+    if (rt_frame_local_rows(frame_) != height_) throw HIPException("HIPPathTraceIntegrator::PickThrough: a tile frame: pick on a frame of the whole image");
+    if (x >= width_ || y >= height_) throw HIPException("HIPPathTraceIntegrator::PickThrough: the pixel is outside the image");
+    // rt_frame_pick's ray for this camera: sf_guide_dir (spatial_filter.h, the guide pass's direction, the same binary32 arithmetic on the host), from the
+    // camera position, t_min 0, t_max RT_MAX_RENDER_DIST
+    rt_camera cam;
+    static_assert(sizeof(cam) == sizeof(camera), "Camera is rt_camera");
+    std::memcpy(&cam, &camera, sizeof(cam));
+    float d[3];
+    sf_guide_dir(cam, rt_tanf(0.5f * cam.fov), width_, height_, x, y, d);
+    rt_ray r;
+    r.origin = {cam.position.x, cam.position.y, cam.position.z, 0.0f};
+    r.direction = {d[0], d[1], d[2], RT_MAX_RENDER_DIST};
+    rt_hit h;
+    rt_surface s;
+    Check(rt_scene_trace(context_.Get(), &r, 1u, RT_QUERY_CLOSEST, &h, nullptr, &s));
+    if (ray) *ray = r;
+    if (hit) *hit = h;
+    if (surface) *surface = s;
 }
 
 void HIPPathTraceIntegrator::SetCameraData(Camera const& camera)

@@ -102,6 +102,14 @@ public:
     // HIPException with the library's message on a refusal.
     void SetObjects(std::uint32_t const* object_of_triangle, std::size_t triangle_count, std::uint32_t object_count);
     void PoseObjects(float const* matrices3x4, std::size_t object_count);
+    // Ray queries (rt_scene_trace / rt_frame_pick): the caller's rays against the uploaded scene as it is posed now.  TraceRays: closest hits
+    // (hits and / or surfaces, either may be null) or, any_hit, one 0 / 1 word per ray in occluded; a count of 2^32 or more is refused.  Pick: the ray through the
+    // centre of pixel (x, y) of the frame's current camera, its hit and surface (any may be null).  PickThrough: the same for a camera the frame has not been given
+    // (Render's pending one): the ray is made here with the guide pass's own function and traced as a query, so neither the frame's camera nor its previous
+    // camera moves.  All throw HIPException with the library's message on a refusal; none requests a reset or touches the frame.
+    void TraceRays(rt_ray const* rays, std::size_t count, bool any_hit, rt_hit* hits, std::uint32_t* occluded, rt_surface* surfaces);
+    void Pick(std::uint32_t x, std::uint32_t y, rt_ray* ray, rt_hit* hit, rt_surface* surface);
+    void PickThrough(Camera const& camera, std::uint32_t x, std::uint32_t y, rt_ray* ray, rt_hit* hit, rt_surface* surface);
     rt_frame* GetFrame() const { return frame_; }
 
 protected:

@@ -256,6 +256,16 @@ int rth_render_set_objects(void* r, const uint32_t* object_of_triangle, uint32_t
     return guard([&]() { ((rt::Render*)r)->SetObjects(object_of_triangle, num_triangles, num_objects); return 0; }, 1);
 }
 int rth_render_pose(void* r, const float* matrices3x4, uint32_t num_objects) { return guard([&]() { ((rt::Render*)r)->PoseObjects(matrices3x4, num_objects); return 0; }, 1); }
+int rth_render_pick(void* r, uint32_t x, uint32_t y, rt_ray* ray, rt_hit* hit, rt_surface* surface) { return guard([&]() { ((rt::Render*)r)->Pick(x, y, ray, hit, surface); return 0; }, 1); }
+// HIPPathTraceIntegrator::Pick itself: the FRAME's camera (what the last RenderFrame / RenderSamples handed over), where rth_render_pick uses the Render's
+int rth_render_integrator_pick(void* r, uint32_t x, uint32_t y, rt_ray* ray, rt_hit* hit, rt_surface* surface)
+{
+    return guard([&]() { ((rt::Render*)r)->GetIntegrator().Pick(x, y, ray, hit, surface); return 0; }, 1);
+}
+int rth_render_trace(void* r, const rt_ray* rays, uint32_t n, int any_hit, rt_hit* hits, uint32_t* occluded, rt_surface* surfaces)
+{
+    return guard([&]() { ((rt::Render*)r)->TraceRays(rays, n, any_hit != 0, hits, occluded, surfaces); return 0; }, 1);
+}
 int rth_render_upload_gpu_data(void* r) { return guard([&]() { ((rt::Render*)r)->UploadGPUData(); return 0; }, 1); }
 
 } // extern "C"

@@ -36,6 +36,8 @@ int main(int argc, char** argv)
         float camera_step[3] = {0.0f, 0.0f, 0.0f};
         struct ObjectStep { unsigned object; float d[3]; };
         std::vector<ObjectStep> object_steps;   // --object_step i,dx,dy,dz (repeatable): frame k poses object i by the translation k * (dx,dy,dz)
+        struct PickAt { unsigned x, y; };
+        std::vector<PickAt> picks;              // --pick x,y (repeatable): after the scene is uploaded and posed, print what lies under that pixel
         bool list_objects = false;              // --list_objects 1: print the OBJ's o / g shapes (index and name) and exit; needs no GPU
         for (int i = 1; i < argc; ++i)
         {
@@ -111,6 +113,13 @@ int main(int argc, char** argv)
                 object_steps.push_back(s);
                 scene_options |= rt::Scene::kObjects;
             }
+            else if (!strcmp(argv[i], "--pick"))
+            {
+                PickAt p;
+                if (sscanf(next(), "%u,%u", &p.x, &p.y) != 2) { std::cerr << "--pick wants x,y (image coordinates)\n"; return 2; }
+                picks.push_back(p);
+                scene_options |= rt::Scene::kObjects;
+            }
             else if (!strcmp(argv[i], "--list_objects")) { if (atoi(next()) != 0) { list_objects = true; scene_options |= rt::Scene::kObjects; } }
             else if (!strcmp(argv[i], "--help"))
             {
@@ -132,7 +141,9 @@ int main(int argc, char** argv)
                              "  (the reference's moving-camera loop: each frame is reset); --out then writes the last frame's image\n"
                              "  --list_objects 1 prints the scene's objects (the OBJ's o / g shapes: index and name) and exits\n"
                              "  --frames n --object_step i,dx,dy,dz (repeatable) poses object i by the translation k * (dx,dy,dz) in frame k, on the device\n"
-                             "  (rt_scene_pose: the scene is uploaded refittable, and with --temporal_filter the history follows the move); one GPU only\n";
+                             "  (rt_scene_pose: the scene is uploaded refittable, and with --temporal_filter the history follows the move); one GPU only\n"
+                             "  --pick x,y (repeatable) prints what lies under the centre of that pixel once the scene is uploaded and posed: primitive, t, position,\n"
+                             "  normals, texture coordinates, material and object (index and name); one GPU only\n";
                 return 0;
             }
         }
@@ -167,6 +178,11 @@ int main(int argc, char** argv)
         if (!object_steps.empty() && (frames == 0 || gpus > 1 || tiled_path))
         {
             std::cerr << "--object_step needs --frames n and one GPU\n";
+            return 2;
+        }
+        if (!picks.empty() && (gpus > 1 || tiled_path))
+        {
+            std::cerr << "--pick needs one GPU\n";
             return 2;
         }
         if (plan_only)
@@ -243,6 +259,26 @@ int main(int argc, char** argv)
         render.GetIntegrator().EnableWhiteFurnace(furnace);
         render.GetIntegrator().SetSpatialFilter(filter_iterations >= 0 ? &filter : nullptr);
         render.GetIntegrator().SetTemporalFilter(temporal_iterations >= 0 ? &temporal : nullptr);
+        // --pick: one line per pixel (rt_frame_pick through Render::Pick); the object is the scene's own table's where none was set on the device
+        auto print_picks = [&]()
+        {
+            for (const PickAt& p : picks)
+            {
+                rt_hit h; rt_surface s;
+                render.Pick(p.x, p.y, nullptr, &h, &s);
+                std::cout << "pick " << p.x << "," << p.y << ": ";
+                if (s.primitive_id == RT_INVALID_ID) { std::cout << "miss" << std::endl; continue; }
+                std::uint32_t object = s.object;
+                if (object == RT_INVALID_ID && s.primitive_id < scene.GetTriangleObjects().size()) object = scene.GetTriangleObjects()[s.primitive_id];
+                std::cout << "primitive " << s.primitive_id << " t " << s.t << " position " << s.position[0] << " " << s.position[1] << " " << s.position[2]
+                          << " geometric_normal " << s.geometric_normal[0] << " " << s.geometric_normal[1] << " " << s.geometric_normal[2]
+                          << " shading_normal " << s.shading_normal[0] << " " << s.shading_normal[1] << " " << s.shading_normal[2]
+                          << " texcoord " << s.texcoord[0] << " " << s.texcoord[1] << " material " << s.mtl_index << " object ";
+                if (object < scene.GetObjectNames().size()) std::cout << object << " " << scene.GetObjectNames()[object];
+                else std::cout << "none";
+                std::cout << ((s.flags & 2u) ? " (back face)" : "") << std::endl;
+            }
+        };
         const bool posing = !object_steps.empty();
         if (posing)                                                           // effective at the loop's upload below
         {
@@ -286,6 +322,7 @@ int main(int argc, char** argv)
             std::cout << frames << (posing ? (moving ? " moving-camera, posed-object" : " posed-object") : " moving-camera") << " frames (one sample each" << (temporal_iterations >= 0 ? ", temporally filtered" : "") << ") in " << df
                       << " s: " << df * 1e3 / frames << " ms per frame" << std::endl;
             if (!out.empty()) WritePFM(out.c_str(), img, width, height);     // the last frame's resolved (filtered), tone-mapped image
+            print_picks();
             return 0;
         }
         if (frames != 0)
@@ -323,6 +360,7 @@ int main(int argc, char** argv)
         rt_stats st = render.GetIntegrator().GetStats();
         double rays = (double)st.closest_rays + (double)st.shadow_rays;
         std::cout << spp << " spp in " << dt << " s, " << rays / dt / 1e6 << " Mrays/s" << std::endl;
+        print_picks();
         if (!out.empty() && (filter_iterations >= 0 || temporal_iterations >= 0))
             WritePFM(out.c_str(), render.GetIntegrator().ResolveNow(), width, height);     // the filtered, tone-mapped image
         else if (!out.empty())

@@ -41,6 +41,11 @@ public:
     // matrix per object and pose -- 12 floats per object instead of RefitGeometry's 160 bytes per triangle.  An upload drops the objects: set them again.
     void SetObjects(std::uint32_t const* object_of_triangle, std::size_t triangle_count, std::uint32_t object_count) { integrator_->SetObjects(object_of_triangle, triangle_count, object_count); }
     void PoseObjects(float const* matrices3x4, std::size_t object_count) { integrator_->PoseObjects(matrices3x4, object_count); }
+    // Ray queries: what lies under pixel (x, y) of the Render's current camera -- also one set since the last frame, which the integrator
+    // has not been given yet: the ray is made from it here and traced as a query, the frame (its camera and previous camera included) is not touched -- and the
+    // caller's own rays against the scene as it is posed now
+    void Pick(std::uint32_t x, std::uint32_t y, rt_ray* ray, rt_hit* hit, rt_surface* surface) { integrator_->PickThrough(camera_, x, y, ray, hit, surface); }
+    void TraceRays(rt_ray const* rays, std::size_t count, bool any_hit, rt_hit* hits, std::uint32_t* occluded, rt_surface* surfaces) { integrator_->TraceRays(rays, count, any_hit, hits, occluded, surfaces); }
     AccelerationStructure const& GetAccelerationStructure() const { return *acc_structure_; }
     std::uint32_t GetWidth() const { return width_; }
     std::uint32_t GetHeight() const { return height_; }
