@@ -133,6 +133,8 @@ enum rt_ctx_option
     , RT_CTX_OPT_ADAPT_WAIT = 6    /* 1 / 0: sets / clears bit 1 of RT_CTX_OPT_ADAPTIVE_FOLD (rt_integrate waits for an adaptation it has
                                       started) for the scene IN PLACE, at once; the context's option, which the next upload reads, stays
                                       (bench.py: the headline waits for its fold, the moving-camera leg runs as the library ships) */
+    , RT_CTX_OPT_BAKE_CHUNK_POINTS = 12 /* rt_scene_bake stages at most this many points at a time (default and upper bound 1 Mi; 0 = the default).  No result
+                                      depends on it (tests force it small).  Takes effect at once. */
 };
 int rt_ctx_set_option(rt_ctx* ctx, int option, uint32_t value);
 /* The blue-noise sampler tables (src/utils/blue_noise_sampler.hpp: sobol_256spp_256d[256*256],
@@ -259,6 +261,49 @@ int rt_frame_pick(rt_frame* frame, uint32_t x, uint32_t y, rt_ray* ray_or_null, 
  * two agree bit for bit. */
 int rt_debug_query_surface(rt_ctx* ctx_or_null, const rt_triangle* triangles, uint32_t num_triangles, const uint32_t* object_of_triangle_or_null,
                            const rt_ray* rays, const rt_hit* hits, uint32_t n, rt_surface* out);
+
+/* ---- occlusion bakes: ambient occlusion and bent normals at the CALLER's points (opt-in extension).  Per point a cosine-weighted
+ * hemisphere of `samples` any-hit rays about the point's normal is generated, walked and reduced on the device: 32 bytes per point in, 16 out, no ray or verdict
+ * ever crosses PCIe.  raytracing_amd/csrc/bake.h states every step of the arithmetic (the rays, the frame, the order of the reduction).
+ *   points: eight floats each -- position xyz, w ignored, normal xyz (any length), w ignored; with RT_BAKE_FROM_SURFACES rt_surface records instead (position,
+ *     shading_normal negated when flags bit 1 -- back face -- is set; a record with flags bit 0 clear, a miss, is skipped): rt_scene_trace_buffer's surfaces feed a
+ *     bake without a trip to the host.
+ *   a point is SKIPPED -- none of its rays walked, unoccluded = RT_INVALID_ID, bent_normal zeros -- when a position or normal component is not finite, when
+ *     the normal's squared length is zero or not finite, or when it is a miss record.
+ *   every other point: ray k has origin = position + unit normal * bias, t_min 0, t_max radius; unoccluded = the rays for which nothing lies within [0, radius]
+ *     (exact any-hit verdicts over the shadow rays' tree, as RT_QUERY_ANY_HIT's); the sampling is cosine-weighted, so unoccluded / samples is the ambient
+ *     occlusion term.  bent_normal = the normalised sum of the unoccluded rays' directions in bake.h's order, zeros when that sum's squared length is zero or
+ *     not finite.  The rays of point i depend on (i, seed): i = the point's index within the call.
+ * A bake runs on the context's stream, after every refit, pose or upload before it, and touches no frame and no rt_stats field, like a query; a traversal
+ * stack that ran over its bound is reported as a query's is.
+ *   rt_scene_bake: host arrays, staged in chunks of at most 1 Mi points (RT_CTX_OPT_BAKE_CHUNK_POINTS) through scratch the context keeps; a chunk carries the
+ *     index of its first point, so chunking changes no result; returns when `out` is written.
+ *   rt_scene_bake_buffer: rt_buffers of this context holding n records each; only enqueues.
+ * Refused with nothing launched: a NULL context, NULL points / desc / out with n > 0, no scene, samples not a power of two in 16 .. 4096, a bias or radius that
+ * is not finite, radius <= 0, unknown flag bits, a buffer of another context or smaller than n records.  n == 0 is RT_OK and does nothing. */
+#define RT_BAKE_FROM_SURFACES 1u
+typedef struct rt_bake_desc
+{
+    uint32_t samples;  /* rays per point: a power of two, 16 .. 4096 */
+    uint32_t seed;
+    uint32_t flags;    /* RT_BAKE_FROM_SURFACES */
+    float bias;        /* origin = position + unit normal * bias */
+    float radius;      /* t_max; t_min = 0 */
+} rt_bake_desc;
+typedef struct rt_bake_result
+{
+    float bent_normal[3];
+    uint32_t unoccluded;
+} rt_bake_result;
+int rt_scene_bake(rt_ctx* ctx, const void* points, uint32_t n, const rt_bake_desc* desc, rt_bake_result* out);
+int rt_scene_bake_buffer(rt_ctx* ctx, rt_buffer* points, uint32_t n, const rt_bake_desc* desc, rt_buffer* out);
+/* the rays of a bake on their own: rays_out[p * samples + k] = ray k of points[p], whose index is first_index + p (t_min 0 in origin.w, radius in
+ * direction.w); a skipped point's rays are all zeros.  ctx == NULL: the host restatement (bake.h); otherwise k_bake_rays on an uploaded copy.  The two agree
+ * bit for bit.  At most 2^28 rays per call. */
+int rt_debug_bake_rays(rt_ctx* ctx_or_null, const void* points, uint32_t n, uint32_t first_index, const rt_bake_desc* desc, rt_ray* rays_out);
+/* the reduction on its own (host only): out[p] from rays[p * samples ..] and their verdicts (occluded[] != 0: something lies within the ray's range), in
+ * bake.h's order.  A point whose first ray has an all-zero direction is a skipped one. */
+int rt_debug_bake_reduce(const rt_ray* rays, const uint32_t* occluded, uint32_t n, uint32_t samples, rt_bake_result* out);
 
 /* One fold adaptation per process GROUP instead of one per rank (N ranks that tile one image hold the same scene and would each probe, rotate and fold for
  * identical records): the context's current 4-wide records -- the closest-hit rays' and the shadow rays' (n_shadow == 0: they share), as adapted so far -- to
@@ -760,4 +805,5 @@ int rt_debug_eval(rt_ctx* ctx, int fn, const float* a, const float* b, float* ou
 }
 #endif
 RT_STATIC_ASSERT(sizeof(rt_surface) == 64, "rt_surface");
+RT_STATIC_ASSERT(sizeof(rt_bake_result) == 16 && sizeof(rt_bake_desc) == 20, "rt_bake_result / rt_bake_desc");
 #endif /* RT_HIP_H */

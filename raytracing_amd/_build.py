@@ -51,6 +51,7 @@ HIP_UNITS = [
     ("refit", "refit.hip", True),              # the refit of the scene's trees when its triangles move: kernels + their host driver + the host restatement (a code object of its own)
     ("pose", "pose.hip", True),                # the scene's objects posed from one matrix per object: kernels + host driver + the host restatement (a code object of its own)
     ("query", "query.hip", True),              # caller-supplied rays traced against the uploaded scene, the surface record of a hit: kernels + host driver + the host restatement (a code object of its own)
+    ("bake", "bake.hip", True),                # ambient occlusion and bent normals at caller-supplied points: kernels + host driver + the host restatement (a code object of its own)
     ("wide_bvh", "wide_bvh.cpp", False),       # build_wide_bvh, pair layout, the adaptation's host walks (no device code)
 ]
 

@@ -112,6 +112,7 @@ EXPORTS = [
     "rt_scene_set_objects", "rt_scene_pose", "rt_debug_pose",
     "rt_frame_read_guide_motion", "rt_debug_guide_motion", "rt_debug_filter_temporal_motion",
     "rt_scene_trace", "rt_scene_trace_buffer", "rt_frame_pick", "rt_debug_query_surface",
+    "rt_scene_bake", "rt_scene_bake_buffer", "rt_debug_bake_rays", "rt_debug_bake_reduce",
 ]
 
 OPT_MAX_BOUNCES, OPT_WHITE_FURNACE, OPT_SAMPLER, OPT_AOV, OPT_DENOISER, OPT_DROP_LAST, OPT_PROFILE, OPT_TRACE_VARIANT, OPT_TRACE_WAVES, OPT_SAMPLES_IN_FLIGHT, OPT_SELECT_FORM_BOX, OPT_PACKET_BOUNCES, OPT_TRACE_TUNE, OPT_DEBUG_ALLOC_LIMIT, OPT_PATH_STATE_LIMIT_MB, OPT_PIPELINES, OPT_SHADE_PARTITION, OPT_OVERLAP_SHADOW, OPT_SMALL_LAUNCH_PATHS, OPT_COMPACT_LOG, OPT_DEBUG_LOG_POOL_DIV, OPT_TRACE_TAIL_LANES, OPT_TRACE_TAIL_PATHS, OPT_CHUNK_REFILL, OPT_STAGE_PIPES, OPT_FRAME_KERNEL, OPT_SAMPLES_AHEAD = range(27)
@@ -199,6 +200,9 @@ def load():
         "rt_scene_trace": (i32, [vp, vp, u32, u32, vp, vp, vp]), "rt_scene_trace_buffer": (i32, [vp, vp, u32, u32, vp, vp, vp]),
         "rt_frame_pick": (i32, [vp, u32, u32, vp, vp, vp]),
         "rt_debug_query_surface": (i32, [vp, vp, u32, vp, vp, vp, u32, vp]),
+        "rt_scene_bake": (i32, [vp, vp, u32, C.POINTER(rt_bake_desc), vp]), "rt_scene_bake_buffer": (i32, [vp, vp, u32, C.POINTER(rt_bake_desc), vp]),
+        "rt_debug_bake_rays": (i32, [vp, vp, u32, u32, C.POINTER(rt_bake_desc), vp]),
+        "rt_debug_bake_reduce": (i32, [vp, vp, u32, u32, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -378,6 +382,61 @@ def debug_query_surface(ctx, triangles, rays, hits, object_of_triangle=None):
                                     r.ctypes.data if len(r) else None, h.ctypes.data if len(h) else None, len(r), out.ctypes.data if len(r) else None)
     if rc != 0:
         raise RtError(lib.rt_last_error(handle).decode())
+    return out
+
+
+BAKE_FROM_SURFACES = 1
+BAKE_BIAS_DEFAULT, BAKE_RADIUS_DEFAULT = 1e-3, 1.0
+
+
+class rt_bake_desc(C.Structure):
+    _fields_ = [("samples", C.c_uint32), ("seed", C.c_uint32), ("flags", C.c_uint32), ("bias", C.c_float), ("radius", C.c_float)]
+
+
+def bake_points(points, from_surfaces=False):
+    """the one rule for a bake's points: float32[n, 8] = position.xyz, -, normal.xyz, - per row; from_surfaces: types.surface records"""
+    a = np.asarray(points)
+    if from_surfaces:
+        if a.dtype != T.surface:
+            raise RtError("points must be types.surface records (from_surfaces)")
+        return np.ascontiguousarray(a).reshape(-1)
+    a = np.ascontiguousarray(a, np.float32)
+    if a.ndim != 2 or a.shape[1] != 8:
+        raise RtError("points must be float32[n, 8] (position.xyz, -, normal.xyz, -)")
+    return a
+
+
+def bake_desc(samples, seed=0, bias=BAKE_BIAS_DEFAULT, radius=BAKE_RADIUS_DEFAULT, from_surfaces=False, flags=None):
+    return rt_bake_desc(int(samples), int(seed) & 0xFFFFFFFF, (BAKE_FROM_SURFACES if from_surfaces else 0) if flags is None else flags, bias, radius)
+
+
+def debug_bake_rays(ctx, points, samples, seed=0, bias=BAKE_BIAS_DEFAULT, radius=BAKE_RADIUS_DEFAULT, from_surfaces=False, first_index=0):
+    """rt_debug_bake_rays: the rays a bake walks, types.ray[n, samples] (a skipped point's are zeros); the index of points[0] is first_index.
+    ctx None = the host restatement (csrc/bake.h), else k_bake_rays on ctx's GPU."""
+    lib = load()
+    pts = bake_points(points, from_surfaces)
+    d = bake_desc(samples, seed, bias, radius, from_surfaces)
+    n = len(pts)
+    out = np.zeros((n, max(int(samples), 0)), T.ray)
+    handle = ctx.handle if ctx is not None else None
+    rc = lib.rt_debug_bake_rays(handle, pts.ctypes.data if n else None, n, first_index, C.byref(d), out.ctypes.data if out.size else None)
+    if rc != 0:
+        raise RtError(lib.rt_last_error(handle).decode())
+    return out
+
+
+def debug_bake_reduce(rays, occluded, samples):
+    """rt_debug_bake_reduce (host only): types.bake_result[n] of types.ray[n, samples] and their verdicts uint32[n, samples], in bake.h's order"""
+    lib = load()
+    r = np.ascontiguousarray(rays, T.ray).reshape(-1)
+    o = np.ascontiguousarray(occluded, np.uint32).reshape(-1)
+    if samples <= 0 or len(r) % samples or len(o) != len(r):
+        raise RtError("debug_bake_reduce: n * samples rays and one verdict per ray")
+    n = len(r) // samples
+    out = np.zeros(n, T.bake_result)
+    rc = lib.rt_debug_bake_reduce(r.ctypes.data if n else None, o.ctypes.data if n else None, n, samples, out.ctypes.data if n else None)
+    if rc != 0:
+        raise RtError(lib.rt_last_error(None).decode())
     return out
 
 
@@ -632,6 +691,26 @@ class Context:
         Buffer.read() or finish() waits."""
         h = lambda b: b.handle if b is not None else None
         _check(self.lib, self.handle, self.lib.rt_scene_trace_buffer(self.handle, h(rays), n, QUERY_ANY_HIT if any_hit else QUERY_CLOSEST, h(hits), h(occluded), h(surfaces)))
+
+    def bake(self, points, samples, seed=0, bias=BAKE_BIAS_DEFAULT, radius=BAKE_RADIUS_DEFAULT, from_surfaces=False):
+        """rt_scene_bake: ambient occlusion and bent normals at the caller's points (bake_points' rule): types.bake_result[n] -- unoccluded / samples is the
+        ambient occlusion term, 0xFFFFFFFF marks a skipped point"""
+        pts = bake_points(points, from_surfaces)
+        d = bake_desc(samples, seed, bias, radius, from_surfaces)
+        out = np.zeros(len(pts), T.bake_result)
+        _check(self.lib, self.handle, self.lib.rt_scene_bake(self.handle, pts.ctypes.data if len(pts) else None, len(pts), C.byref(d), out.ctypes.data if len(pts) else None))
+        return out
+
+    def bake_buffer(self, points, n, out, samples, seed=0, bias=BAKE_BIAS_DEFAULT, radius=BAKE_RADIUS_DEFAULT, from_surfaces=False):
+        """rt_scene_bake_buffer: the same over Buffers of this context (n point records in, n types.bake_result out).  Only enqueues: Buffer.read() or
+        finish() waits."""
+        d = bake_desc(samples, seed, bias, radius, from_surfaces)
+        h = lambda b: b.handle if b is not None else None
+        _check(self.lib, self.handle, self.lib.rt_scene_bake_buffer(self.handle, h(points), n, C.byref(d), h(out)))
+
+    def set_bake_chunk_points(self, points):
+        """RT_CTX_OPT_BAKE_CHUNK_POINTS: bake() stages at most this many points at a time (0 = the default, 1 Mi); no result depends on it"""
+        _check(self.lib, self.handle, self.lib.rt_ctx_set_option(self.handle, 12, points))
 
     def create_buffer(self, data):
         """an rt_buffer of this context holding `data` (any contiguous array)"""

@@ -25,11 +25,17 @@ int rt_debug_wide_bvh(const rt_bvh_node* nodes, uint32_t num_nodes, int collapse
 const char* rt_scene_tree_report(rt_ctx* ctx)
 {
     if (!ctx) return "";
-    if (ctx->query.bytes() == 0u || !ctx->scene.valid) return ctx->scene.tree_report.c_str();
-    // what the context keeps for its ray queries (query_host.h) is the context's, not the scene's: its line is added here, when the report is asked for
-    char line[200];
-    snprintf(line, sizeof(line), "ray queries: %.1f MB kept on the device (stack spill area %.1f MB + staging)\n", (double)ctx->query.bytes() / 1e6,
-        (double)ctx->query.spill_bytes() / 1e6);
+    if ((ctx->query.bytes() == 0u && ctx->bake.bytes() == 0u) || !ctx->scene.valid) return ctx->scene.tree_report.c_str();
+    // what the context keeps for its ray queries and bakes (query_host.h, bake_host.h) is the context's, not the scene's: its line is added here, when the
+    // report is asked for
+    char line[300];
+    if (ctx->bake.bytes() == 0u)
+        snprintf(line, sizeof(line), "ray queries: %.1f MB kept on the device (stack spill area %.1f MB + staging)\n", (double)ctx->query.bytes() / 1e6,
+            (double)ctx->query.spill_bytes() / 1e6);
+    else
+        snprintf(line, sizeof(line), "ray queries: %.1f MB kept on the device (stack spill area %.1f MB + staging; of that the bakes' %.1f MB: spill area %.1f MB + staging)\n",
+            (double)(ctx->query.bytes() + ctx->bake.bytes()) / 1e6, (double)(ctx->query.spill_bytes() + ctx->bake.spill_bytes()) / 1e6, (double)ctx->bake.bytes() / 1e6,
+            (double)ctx->bake.spill_bytes() / 1e6);
     ctx->report_out = ctx->scene.tree_report + line;
     return ctx->report_out.c_str();
 }

@@ -29,6 +29,7 @@
 #include "pose_host.h"       // the scene's objects posed from one matrix per object (pose.hip)
 #include "filters_host.h"         // the filters' guide pass, a-trous passes and temporal stages (filters.hip)
 #include "query_host.h"      // caller-supplied rays traced against the uploaded scene (query.hip)
+#include "bake_host.h"       // ambient occlusion and bent normals at caller-supplied points (bake.hip)
 using namespace rtw;
 
 namespace
@@ -125,6 +126,8 @@ struct rt_ctx
     uint8_t* blue_noise = nullptr;   // sobol[65536] | scramblingTile[131072] | rankingTile[131072]
     float* gamma_lut = nullptr;      // pow(byte / 255, 2.2f), 256 entries (k_fill_gamma_lut)
     query::Scratch query;            // rt_scene_trace*: the walk's stack spill area and the host form's staging arrays (query_host.h)
+    bake::Scratch bake;              // rt_scene_bake*: the walk's stack spill area and the host form's staging arrays (bake_host.h)
+    uint32_t bake_chunk_points = bake::CHUNK_POINTS;   // RT_CTX_OPT_BAKE_CHUNK_POINTS
     std::string report_out;          // rt_scene_tree_report's answer when it has a "ray queries" line to add to the scene's report
 };
 
@@ -555,6 +558,7 @@ int rt_ctx_destroy(rt_ctx* ctx)
     (void)hipStreamSynchronize(ctx->stream);
     free_scene(ctx->scene);
     query::release(ctx->query);
+    bake::release(ctx->bake);
     if (ctx->blue_noise) (void)hipFree(ctx->blue_noise);
     if (ctx->gamma_lut) (void)hipFree(ctx->gamma_lut);
     (void)hipStreamDestroy(ctx->stream);
@@ -653,6 +657,7 @@ int rt_ctx_set_option(rt_ctx* ctx, int option, uint32_t value)
         if (ctx->scene.adapt) fold_adapt_set_interval(ctx->scene.adapt, value);     // the scene in place too
         return RT_OK;
     }
+    if (option == RT_CTX_OPT_BAKE_CHUNK_POINTS) { ctx->bake_chunk_points = value == 0u || value > (uint32_t)bake::CHUNK_POINTS ? (uint32_t)bake::CHUNK_POINTS : value; return RT_OK; }
     return fail(ctx, "rt_ctx_set_option: unknown option");
 }
 
@@ -1071,6 +1076,7 @@ extern "C" {
 #include "refit_impl.h"
 #include "pose_impl.h"
 #include "query_impl.h"
+#include "bake_impl.h"
 
 // ---- scene -----------------------------------------------------------------
 int rt_scene_upload(rt_ctx* ctx, const rt_scene_desc* sd)

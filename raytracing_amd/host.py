@@ -26,6 +26,7 @@ EXPORTS = [
     "rth_render_upload_gpu_data", "rth_render_setup_seconds", "rth_render_create_with_options",
     "rth_render_set_refittable", "rth_render_refit", "rth_render_set_refit_motion",
     "rth_render_set_objects", "rth_render_pose", "rth_render_pick", "rth_render_integrator_pick", "rth_render_trace",
+    "rth_render_bake", "rth_render_occlusion_image",
     "rth_scene_set_triangle_objects", "rth_scene_num_objects", "rth_scene_object_name", "rth_scene_num_triangle_objects", "rth_scene_triangle_objects",
 ]
 
@@ -74,6 +75,7 @@ def load():
         "rth_render_set_refit_motion": (i32, [vp, i32]),
         "rth_render_set_objects": (i32, [vp, vp, u32, u32]), "rth_render_pose": (i32, [vp, vp, u32]),
         "rth_render_pick": (i32, [vp, u32, u32, vp, vp, vp]), "rth_render_integrator_pick": (i32, [vp, u32, u32, vp, vp, vp]), "rth_render_trace": (i32, [vp, vp, u32, i32, vp, vp, vp]),
+        "rth_render_bake": (i32, [vp, vp, u32, vp, vp]), "rth_render_occlusion_image": (i32, [vp, vp, vp]),
         "rth_render_num_nodes": (u32, [vp]), "rth_render_nodes": (vp, [vp]),
         "rth_render_set_aov": (i32, [vp, i32]), "rth_render_resolve": (i32, [vp, vp]),
         "rth_render_set_blue_noise_path": (i32, [vp, cp]),
@@ -381,6 +383,25 @@ class Render:
         surf = np.zeros(n, T.surface) if surfaces else None
         self._c(self.lib.rth_render_trace(self.handle, r.ctypes.data if n else None, n, 0, hits.ctypes.data, None, surf.ctypes.data if surfaces else None))
         return (hits, surf) if surfaces else hits
+
+    def bake(self, points, samples, seed=0, bias=1e-3, radius=1.0, from_surfaces=False):
+        """Ambient occlusion and bent normals at the caller's points against the scene as it is posed now (HIPPathTraceIntegrator::BakeOcclusion; points:
+        float32[n, 8] = position.xyz, -, normal.xyz, -, or types.surface records with from_surfaces): types.bake_result[n]"""
+        from . import capi
+        pts = capi.bake_points(points, from_surfaces)
+        d = capi.bake_desc(samples, seed, bias, radius, from_surfaces)
+        out = np.zeros(len(pts), T.bake_result)
+        self._c(self.lib.rth_render_bake(self.handle, pts.ctypes.data if len(pts) else None, len(pts), C.addressof(d), out.ctypes.data if len(pts) else None))
+        return out
+
+    def occlusion_image(self, samples, radius, bias=1e-3, seed=0):
+        """The exact ambient occlusion image of the Render's current camera (Render::OcclusionImage): float32[height, width] = unoccluded / samples of the
+        pixel-centre ray's first hit, 1 where it misses; traced and baked on the device, the frame is not touched"""
+        from . import capi
+        d = capi.bake_desc(samples, seed, bias, radius)
+        out = np.zeros((self.height, self.width), np.float32)
+        self._c(self.lib.rth_render_occlusion_image(self.handle, C.addressof(d), out.ctypes.data))
+        return out
 
     def tree_report(self):
         from . import capi

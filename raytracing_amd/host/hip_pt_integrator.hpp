@@ -110,6 +110,13 @@ public:
     void TraceRays(rt_ray const* rays, std::size_t count, bool any_hit, rt_hit* hits, std::uint32_t* occluded, rt_surface* surfaces);
     void Pick(std::uint32_t x, std::uint32_t y, rt_ray* ray, rt_hit* hit, rt_surface* surface);
     void PickThrough(Camera const& camera, std::uint32_t x, std::uint32_t y, rt_ray* ray, rt_hit* hit, rt_surface* surface);
+    // Occlusion bakes (rt_scene_bake).  BakeOcclusion: ambient occlusion and bent normals at the caller's points (eight floats each, or
+    // rt_surface records with RT_BAKE_FROM_SURFACES in desc.flags); a count of 2^32 or more is refused.  OcclusionImageThrough: for every pixel of the frame's size
+    // the pixel-centre ray of `camera` -- made as PickThrough makes it -- is traced into an rt_surface on the device and those are baked there (RT_BAKE_FROM_SURFACES);
+    // out[y * width + x] = unoccluded / samples, 1 where nothing is walked (a miss; a hit without a usable shading normal).  Both throw HIPException with the
+    // library's message on a refusal; neither requests a reset or touches the frame.
+    void BakeOcclusion(void const* points, std::size_t count, rt_bake_desc const& desc, rt_bake_result* out);
+    void OcclusionImageThrough(Camera const& camera, rt_bake_desc desc, float* out);
     rt_frame* GetFrame() const { return frame_; }
 
 protected:

@@ -266,6 +266,14 @@ int rth_render_trace(void* r, const rt_ray* rays, uint32_t n, int any_hit, rt_hi
 {
     return guard([&]() { ((rt::Render*)r)->TraceRays(rays, n, any_hit != 0, hits, occluded, surfaces); return 0; }, 1);
 }
+int rth_render_bake(void* r, const void* points, uint32_t n, const rt_bake_desc* desc, rt_bake_result* out)
+{
+    return guard([&]() { if (!desc) throw rt::HIPException("rth_render_bake: desc is NULL"); ((rt::Render*)r)->BakeOcclusion(points, n, *desc, out); return 0; }, 1);
+}
+int rth_render_occlusion_image(void* r, const rt_bake_desc* desc, float* out)
+{
+    return guard([&]() { if (!desc) throw rt::HIPException("rth_render_occlusion_image: desc is NULL"); ((rt::Render*)r)->OcclusionImage(*desc, out); return 0; }, 1);
+}
 int rth_render_upload_gpu_data(void* r) { return guard([&]() { ((rt::Render*)r)->UploadGPUData(); return 0; }, 1); }
 
 } // extern "C"

@@ -38,6 +38,8 @@ int main(int argc, char** argv)
         std::vector<ObjectStep> object_steps;   // --object_step i,dx,dy,dz (repeatable): frame k poses object i by the translation k * (dx,dy,dz)
         struct PickAt { unsigned x, y; };
         std::vector<PickAt> picks;              // --pick x,y (repeatable): after the scene is uploaded and posed, print what lies under that pixel
+        std::string ao_out;                     // --ao out.pfm: after the scene is uploaded and posed, write the ambient occlusion image of the camera (grey, RGB equal)
+        rt_bake_desc ao = {64u, 0u, 0u, 1e-3f, 1.0f};   // --ao_samples n --ao_radius r --ao_bias b
         bool list_objects = false;              // --list_objects 1: print the OBJ's o / g shapes (index and name) and exit; needs no GPU
         for (int i = 1; i < argc; ++i)
         {
@@ -120,6 +122,10 @@ int main(int argc, char** argv)
                 picks.push_back(p);
                 scene_options |= rt::Scene::kObjects;
             }
+            else if (!strcmp(argv[i], "--ao")) ao_out = next();
+            else if (!strcmp(argv[i], "--ao_samples")) ao.samples = (unsigned)atoi(next());
+            else if (!strcmp(argv[i], "--ao_radius")) ao.radius = (float)atof(next());
+            else if (!strcmp(argv[i], "--ao_bias")) ao.bias = (float)atof(next());
             else if (!strcmp(argv[i], "--list_objects")) { if (atoi(next()) != 0) { list_objects = true; scene_options |= rt::Scene::kObjects; } }
             else if (!strcmp(argv[i], "--help"))
             {
@@ -143,7 +149,10 @@ int main(int argc, char** argv)
                              "  --frames n --object_step i,dx,dy,dz (repeatable) poses object i by the translation k * (dx,dy,dz) in frame k, on the device\n"
                              "  (rt_scene_pose: the scene is uploaded refittable, and with --temporal_filter the history follows the move); one GPU only\n"
                              "  --pick x,y (repeatable) prints what lies under the centre of that pixel once the scene is uploaded and posed: primitive, t, position,\n"
-                             "  normals, texture coordinates, material and object (index and name); one GPU only\n";
+                             "  normals, texture coordinates, material and object (index and name); one GPU only\n"
+                             "  --ao out.pfm --ao_samples n --ao_radius r [--ao_bias b] writes the exact ambient occlusion image of the camera once the scene is uploaded\n"
+                             "  and posed: per pixel the share of n cosine-weighted rays (a power of two, 16 .. 4096; default 64) from the first hit that meet nothing within r\n"
+                             "  (default 1), 1 where the pixel sees nothing; traced and baked on the device (rt_scene_bake_buffer); one GPU only\n";
                 return 0;
             }
         }
@@ -183,6 +192,11 @@ int main(int argc, char** argv)
         if (!picks.empty() && (gpus > 1 || tiled_path))
         {
             std::cerr << "--pick needs one GPU\n";
+            return 2;
+        }
+        if (!ao_out.empty() && (gpus > 1 || tiled_path))
+        {
+            std::cerr << "--ao needs one GPU\n";
             return 2;
         }
         if (plan_only)
@@ -279,6 +293,16 @@ int main(int argc, char** argv)
                 std::cout << ((s.flags & 2u) ? " (back face)" : "") << std::endl;
             }
         };
+        // --ao: Render::OcclusionImage of the camera as it stands, written as a grey PFM
+        auto write_ao = [&]()
+        {
+            if (ao_out.empty()) return;
+            std::vector<float> grey((size_t)width * height), rgba((size_t)width * height * 4);
+            render.OcclusionImage(ao, grey.data());
+            for (size_t i = 0; i < grey.size(); ++i) { rgba[4 * i] = rgba[4 * i + 1] = rgba[4 * i + 2] = grey[i]; rgba[4 * i + 3] = 1.0f; }
+            WritePFM(ao_out.c_str(), rgba, width, height);
+            std::cout << "ambient occlusion (" << ao.samples << " rays per pixel, radius " << ao.radius << ") written to " << ao_out << std::endl;
+        };
         const bool posing = !object_steps.empty();
         if (posing)                                                           // effective at the loop's upload below
         {
@@ -323,6 +347,7 @@ int main(int argc, char** argv)
                       << " s: " << df * 1e3 / frames << " ms per frame" << std::endl;
             if (!out.empty()) WritePFM(out.c_str(), img, width, height);     // the last frame's resolved (filtered), tone-mapped image
             print_picks();
+            write_ao();
             return 0;
         }
         if (frames != 0)
@@ -361,6 +386,7 @@ int main(int argc, char** argv)
         double rays = (double)st.closest_rays + (double)st.shadow_rays;
         std::cout << spp << " spp in " << dt << " s, " << rays / dt / 1e6 << " Mrays/s" << std::endl;
         print_picks();
+        write_ao();
         if (!out.empty() && (filter_iterations >= 0 || temporal_iterations >= 0))
             WritePFM(out.c_str(), render.GetIntegrator().ResolveNow(), width, height);     // the filtered, tone-mapped image
         else if (!out.empty())

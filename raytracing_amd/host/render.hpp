@@ -46,6 +46,10 @@ public:
     // caller's own rays against the scene as it is posed now
     void Pick(std::uint32_t x, std::uint32_t y, rt_ray* ray, rt_hit* hit, rt_surface* surface) { integrator_->PickThrough(camera_, x, y, ray, hit, surface); }
     void TraceRays(rt_ray const* rays, std::size_t count, bool any_hit, rt_hit* hits, std::uint32_t* occluded, rt_surface* surfaces) { integrator_->TraceRays(rays, count, any_hit, hits, occluded, surfaces); }
+    // Occlusion bakes: ambient occlusion and bent normals at the caller's points, and the exact ambient occlusion image of the Render's
+    // current camera (also one set since the last frame), width x height floats, 1 where the pixel-centre ray misses; the frame is not touched
+    void BakeOcclusion(void const* points, std::size_t count, rt_bake_desc const& desc, rt_bake_result* out) { integrator_->BakeOcclusion(points, count, desc, out); }
+    void OcclusionImage(rt_bake_desc const& desc, float* out) { integrator_->OcclusionImageThrough(camera_, desc, out); }
     AccelerationStructure const& GetAccelerationStructure() const { return *acc_structure_; }
     std::uint32_t GetWidth() const { return width_; }
     std::uint32_t GetHeight() const { return height_; }
