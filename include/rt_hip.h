@@ -305,6 +305,43 @@ int rt_debug_bake_rays(rt_ctx* ctx_or_null, const void* points, uint32_t n, uint
  * bake.h's order.  A point whose first ray has an all-zero direction is a skipped one. */
 int rt_debug_bake_reduce(const rt_ray* rays, const uint32_t* occluded, uint32_t n, uint32_t samples, rt_bake_result* out);
 
+/* ---- nearest surface point: which triangle is nearest to each of the CALLER's points, where on it, and how far (opt-in extension).
+ * raytracing_amd/csrc/nearest.h states every step of the arithmetic: the distance to one triangle (Ericson's region test, the blend in rt_surface's operand
+ * order, the clamp to the triangle's box, d2 = |p - q|^2) and the distance to a box that prunes the walk.
+ *   the answer for a point: over all triangles the one with the smallest d2 <= max_distance^2 (the square rounded once; max_distance may be +inf); a tie in d2
+ *     goes to the lowest primitive_id (BVH order, rt_hit's).  That is a statement about the triangles alone: the result is bit for bit the brute-force minimum
+ *     (rt_debug_nearest), whichever tree is walked, whichever fold is in place, after any refit or pose.
+ *   rt_nearest: position = the closest point (inside the triangle's box), distance = sqrtf(d2), bc = (weight of p2, weight of p3) as rt_hit's, flags =
+ *     RT_NEAREST_FOUND | RT_NEAREST_BACK_SIDE when dot3(p - position, cross3(p2 - p1, p3 - p1)) < 0 | the feature (0 face, 1 edge, 2 vertex) << 2.
+ *     Nothing found: primitive_id = RT_INVALID_ID, zeros, flags 0.
+ *   a point is NOT SEARCHED (the same record) when a position component is not finite or max_distance is NaN or negative.
+ *   surfaces (optional): the rt_surface of the nearest point, made as a ray query makes it (query.h) with direction = position - p and t = distance; a miss
+ *     record where nothing was found.  Its flags bit 1 (back face) agrees with RT_NEAREST_BACK_SIDE except where the normalised geometric normal degenerates
+ *     (zeros: a triangle without area, or one whose squared normal overflows or underflows) or the product with it rounds to zero.  The records feed
+ *     rt_scene_bake_buffer(RT_BAKE_FROM_SURFACES) without a trip to the host.
+ * A nearest query runs on the context's stream, after every refit, pose or upload before it, and touches no frame and no rt_stats field, like a ray query;
+ * it uses the ray queries' stack spill area and staging arrays, and a traversal stack that ran over its bound is reported as a ray query's is.
+ *   rt_scene_nearest: host arrays, staged in chunks; returns when the outputs are written.
+ *   rt_scene_nearest_buffer: rt_buffers of this context holding n records each; only enqueues.
+ * Refused with nothing launched: a NULL context, NULL points with n > 0, no scene, both outputs NULL, a buffer of another context or smaller than n records.
+ * n == 0 is RT_OK and does nothing. */
+typedef struct rt_point   { float position[3]; float max_distance; } rt_point;      /* 16 bytes; max_distance may be +inf */
+typedef struct rt_nearest { float position[3]; float distance; float bc[2];
+                            uint32_t primitive_id; uint32_t flags; } rt_nearest;    /* 32 bytes */
+#define RT_NEAREST_FOUND 1u
+#define RT_NEAREST_BACK_SIDE 2u           /* the point lies behind the triangle's geometric normal */
+#define RT_NEAREST_FEATURE_SHIFT 2        /* bits 2..3: 0 face, 1 edge, 2 vertex */
+int rt_scene_nearest(rt_ctx* ctx, const rt_point* points, uint32_t n, rt_nearest* out_or_null, rt_surface* surfaces_or_null);
+int rt_scene_nearest_buffer(rt_ctx* ctx, rt_buffer* points, uint32_t n, rt_buffer* out_or_null, rt_buffer* surfaces_or_null);
+/* brute force over all of `triangles` (primitive_id = the index): nearest.h on the host (ctx == NULL) or k_nearest_brute on uploaded copies.  The two agree
+ * bit for bit. */
+int rt_debug_nearest(rt_ctx* ctx_or_null, const rt_triangle* triangles, uint32_t num_triangles, const rt_point* points, uint32_t n, rt_nearest* out);
+/* the kernel's walk on the host (no device): over the child-pair form of `nodes` (wide = 0) or over build_wide_bvh's 4-wide records of them (wide = 1), pruned
+ * by nearest_box_d2; triangles_tested_or_null[i] = how many triangles point i was tested against.  Refused when the tree does not qualify for the 4-wide
+ * layout (wide = 1) or is deeper than the walk's stack. */
+int rt_debug_nearest_walk(const rt_bvh_node* nodes, uint32_t num_nodes, const rt_triangle* triangles, uint32_t num_triangles, int wide,
+                          const rt_point* points, uint32_t n, rt_nearest* out, uint32_t* triangles_tested_or_null);
+
 /* One fold adaptation per process GROUP instead of one per rank (N ranks that tile one image hold the same scene and would each probe, rotate and fold for
  * identical records): the context's current 4-wide records -- the closest-hit rays' and the shadow rays' (n_shadow == 0: they share), as adapted so far -- to
  * host buffers of `capacity` records each (records NULL: size query; entries2 = {closest entry, shadow entry}), and into another context that has uploaded
@@ -806,4 +843,5 @@ int rt_debug_eval(rt_ctx* ctx, int fn, const float* a, const float* b, float* ou
 #endif
 RT_STATIC_ASSERT(sizeof(rt_surface) == 64, "rt_surface");
 RT_STATIC_ASSERT(sizeof(rt_bake_result) == 16 && sizeof(rt_bake_desc) == 20, "rt_bake_result / rt_bake_desc");
+RT_STATIC_ASSERT(sizeof(rt_point) == 16 && sizeof(rt_nearest) == 32, "rt_point / rt_nearest");
 #endif /* RT_HIP_H */

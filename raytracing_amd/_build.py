@@ -52,6 +52,7 @@ HIP_UNITS = [
     ("pose", "pose.hip", True),                # the scene's objects posed from one matrix per object: kernels + host driver + the host restatement (a code object of its own)
     ("query", "query.hip", True),              # caller-supplied rays traced against the uploaded scene, the surface record of a hit: kernels + host driver + the host restatement (a code object of its own)
     ("bake", "bake.hip", True),                # ambient occlusion and bent normals at caller-supplied points: kernels + host driver + the host restatement (a code object of its own)
+    ("nearest", "nearest.hip", True),          # the nearest surface point to caller-supplied points: kernels + host driver + the host's brute force and walk (a code object of its own)
     ("wide_bvh", "wide_bvh.cpp", False),       # build_wide_bvh, pair layout, the adaptation's host walks (no device code)
 ]
 

@@ -113,6 +113,7 @@ EXPORTS = [
     "rt_frame_read_guide_motion", "rt_debug_guide_motion", "rt_debug_filter_temporal_motion",
     "rt_scene_trace", "rt_scene_trace_buffer", "rt_frame_pick", "rt_debug_query_surface",
     "rt_scene_bake", "rt_scene_bake_buffer", "rt_debug_bake_rays", "rt_debug_bake_reduce",
+    "rt_scene_nearest", "rt_scene_nearest_buffer", "rt_debug_nearest", "rt_debug_nearest_walk",
 ]
 
 OPT_MAX_BOUNCES, OPT_WHITE_FURNACE, OPT_SAMPLER, OPT_AOV, OPT_DENOISER, OPT_DROP_LAST, OPT_PROFILE, OPT_TRACE_VARIANT, OPT_TRACE_WAVES, OPT_SAMPLES_IN_FLIGHT, OPT_SELECT_FORM_BOX, OPT_PACKET_BOUNCES, OPT_TRACE_TUNE, OPT_DEBUG_ALLOC_LIMIT, OPT_PATH_STATE_LIMIT_MB, OPT_PIPELINES, OPT_SHADE_PARTITION, OPT_OVERLAP_SHADOW, OPT_SMALL_LAUNCH_PATHS, OPT_COMPACT_LOG, OPT_DEBUG_LOG_POOL_DIV, OPT_TRACE_TAIL_LANES, OPT_TRACE_TAIL_PATHS, OPT_CHUNK_REFILL, OPT_STAGE_PIPES, OPT_FRAME_KERNEL, OPT_SAMPLES_AHEAD = range(27)
@@ -203,6 +204,9 @@ def load():
         "rt_scene_bake": (i32, [vp, vp, u32, C.POINTER(rt_bake_desc), vp]), "rt_scene_bake_buffer": (i32, [vp, vp, u32, C.POINTER(rt_bake_desc), vp]),
         "rt_debug_bake_rays": (i32, [vp, vp, u32, u32, C.POINTER(rt_bake_desc), vp]),
         "rt_debug_bake_reduce": (i32, [vp, vp, u32, u32, vp]),
+        "rt_scene_nearest": (i32, [vp, vp, u32, vp, vp]), "rt_scene_nearest_buffer": (i32, [vp, vp, u32, vp, vp]),
+        "rt_debug_nearest": (i32, [vp, vp, u32, vp, u32, vp]),
+        "rt_debug_nearest_walk": (i32, [vp, u32, vp, u32, i32, vp, u32, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -438,6 +442,55 @@ def debug_bake_reduce(rays, occluded, samples):
     if rc != 0:
         raise RtError(lib.rt_last_error(None).decode())
     return out
+
+
+NEAREST_FOUND, NEAREST_BACK_SIDE, NEAREST_FEATURE_SHIFT = 1, 2, 2
+NEAREST_FACE, NEAREST_EDGE, NEAREST_VERTEX = 0, 1, 2
+
+
+def point_records(points):
+    """the one rule for a nearest query's points: types.point records as they are, float32[n, 4] = position.xyz, max_distance per row, or float32[n, 3] =
+    position.xyz with no limit (max_distance = +inf)"""
+    a = np.asarray(points)
+    if a.dtype == T.point:
+        return np.ascontiguousarray(a).reshape(-1)
+    a = np.ascontiguousarray(a, np.float32)
+    if a.ndim == 2 and a.shape[1] == 3:
+        a = np.ascontiguousarray(np.concatenate([a, np.full((len(a), 1), np.inf, np.float32)], axis=1))
+    if a.ndim != 2 or a.shape[1] != 4:
+        raise RtError("points must be types.point records, float32[n, 4] (position.xyz, max_distance) or float32[n, 3] (no limit)")
+    return a.view(T.point).reshape(-1)
+
+
+def debug_nearest(ctx, triangles, points):
+    """rt_debug_nearest: types.nearest[n], brute force over all `triangles` (types.triangle) for `points` (point_records' rule).  ctx None = the host
+    (csrc/nearest.h), else k_nearest_brute on ctx's GPU."""
+    lib = load()
+    tris = np.ascontiguousarray(triangles, T.triangle)
+    pts = point_records(points)
+    out = np.zeros(len(pts), T.nearest)
+    handle = ctx.handle if ctx is not None else None
+    rc = lib.rt_debug_nearest(handle, tris.ctypes.data if len(tris) else None, len(tris), pts.ctypes.data if len(pts) else None, len(pts),
+                              out.ctypes.data if len(pts) else None)
+    if rc != 0:
+        raise RtError(lib.rt_last_error(handle).decode())
+    return out
+
+
+def debug_nearest_walk(nodes, triangles, points, wide=True, counts=False):
+    """rt_debug_nearest_walk (host only): k_nearest's walk over the child-pair form of `nodes` (types.bvh_node; wide=False) or over build_wide_bvh's 4-wide
+    records of them (wide=True): types.nearest[n], or (records, uint32[n] triangles tested per point) with counts=True"""
+    lib = load()
+    nd = np.ascontiguousarray(nodes, T.bvh_node)
+    tris = np.ascontiguousarray(triangles, T.triangle)
+    pts = point_records(points)
+    out = np.zeros(len(pts), T.nearest)
+    tested = np.zeros(len(pts), np.uint32)
+    rc = lib.rt_debug_nearest_walk(nd.ctypes.data if len(nd) else None, len(nd), tris.ctypes.data if len(tris) else None, len(tris), int(wide),
+                                   pts.ctypes.data if len(pts) else None, len(pts), out.ctypes.data if len(pts) else None, tested.ctypes.data if len(pts) else None)
+    if rc != 0:
+        raise RtError(lib.rt_last_error(None).decode())
+    return (out, tested) if counts else out
 
 
 def choose_tree(scene, shadow=True, mode=1):
@@ -691,6 +744,22 @@ class Context:
         Buffer.read() or finish() waits."""
         h = lambda b: b.handle if b is not None else None
         _check(self.lib, self.handle, self.lib.rt_scene_trace_buffer(self.handle, h(rays), n, QUERY_ANY_HIT if any_hit else QUERY_CLOSEST, h(hits), h(occluded), h(surfaces)))
+
+    def nearest(self, points, surfaces=False):
+        """rt_scene_nearest: for each of the caller's points (point_records' rule) the nearest triangle of the uploaded scene, where on it and how far:
+        types.nearest[n], or (records, types.surface[n]) with surfaces=True"""
+        pts = point_records(points)
+        n = len(pts)
+        out = np.zeros(n, T.nearest)
+        surf = np.zeros(n, T.surface) if surfaces else None
+        _check(self.lib, self.handle, self.lib.rt_scene_nearest(self.handle, pts.ctypes.data if n else None, n, out.ctypes.data, surf.ctypes.data if surfaces else None))
+        return (out, surf) if surfaces else out
+
+    def nearest_buffer(self, points, n, out=None, surfaces=None):
+        """rt_scene_nearest_buffer: the same over Buffers of this context (n records each; an output that is not wanted is None).  Only enqueues:
+        Buffer.read() or finish() waits."""
+        h = lambda b: b.handle if b is not None else None
+        _check(self.lib, self.handle, self.lib.rt_scene_nearest_buffer(self.handle, h(points), n, h(out), h(surfaces)))
 
     def bake(self, points, samples, seed=0, bias=BAKE_BIAS_DEFAULT, radius=BAKE_RADIUS_DEFAULT, from_surfaces=False):
         """rt_scene_bake: ambient occlusion and bent normals at the caller's points (bake_points' rule): types.bake_result[n] -- unoccluded / samples is the

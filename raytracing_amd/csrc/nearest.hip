@@ -1,0 +1,246 @@
+// nearest.hip -- the nearest surface point to caller-supplied points (rt_scene_nearest / rt_scene_nearest_buffer / rt_debug_nearest / rt_debug_nearest_walk,
+// DESIGN.md section 7j): the kernels (nearest_kernels.h), their host driver, and the host's brute force and walk over the same arithmetic (nearest.h).  A
+// translation unit and a code object of its own so that the hot path's code object (rt_hip.hip, codeobj.code_object_sha256) does not change.
+// -ffp-contract=off like every other unit.
+#include <hip/hip_runtime.h>
+#include <string.h>
+#include <thread>
+#include <vector>
+#include "rt_hip.h"
+#include "nearest_kernels.h"
+#include "nearest_host.h"
+#include "wide_bvh.h"
+
+namespace nearest
+{
+static_assert(sizeof(rt_point) == sizeof(float4) && sizeof(rt_nearest) == 2 * sizeof(float4) && sizeof(rt_surface) == 4 * sizeof(float4), "records as 16-byte pieces");
+#define RT_NEAREST_WAVES_PER_CU 24u     // 6 KiB of LDS per block: 26 fit a CU's 160 KiB; the registers allow 24
+
+static bool clean() { return hipGetLastError() == hipSuccess; }
+
+bool launch(hipStream_t stream, query::Scratch& q, const DScene& sc, bool use_wide, uint32_t n_tris, const uint32_t* object_of_triangle, int compute_units,
+    const rt_point* d_points, uint32_t n, rt_nearest* d_out, rt_surface* d_surfaces)
+{
+    if (n == 0u) return true;
+    const uint32_t n_chunks = n / 64u + (n % 64u != 0u ? 1u : 0u);
+    const uint32_t resident = (((uint32_t)compute_units * RT_NEAREST_WAVES_PER_CU) + 7u) & ~7u;
+    const uint32_t blocks = n_chunks < resident ? n_chunks : resident;
+    if (!q.status)
+    {
+        if (hipHostMalloc((void**)&q.status, 4) != hipSuccess) { (void)hipGetLastError(); q.status = nullptr; return false; }
+        *q.status = 0u;
+    }
+    if (blocks > q.spill_blocks)
+    {
+        if (q.spill) { (void)hipStreamSynchronize(stream); (void)hipFree(q.spill); q.spill = nullptr; q.spill_blocks = 0; }
+        if (hipMalloc((void**)&q.spill, (size_t)blocks * 64u * RT_QUERY_SPILL_PER_LANE * sizeof(uint2)) != hipSuccess) { (void)hipGetLastError(); q.spill = nullptr; return false; }
+        q.spill_blocks = blocks;
+    }
+    // the records k_nearest_surface reads: the caller's, or the first 32 bytes of each surface record
+    float4* found = (float4*)d_out;
+    uint32_t found_stride = 2u;
+    if (!found) { found = (float4*)d_surfaces; found_stride = 4u; }
+    if (use_wide)
+        hipLaunchKernelGGL(k_nearest<true>, dim3(blocks), dim3(64), 0, stream, sc, (const float4*)d_points, n, found, found_stride, q.spill, q.status);
+    else
+        hipLaunchKernelGGL(k_nearest<false>, dim3(blocks), dim3(64), 0, stream, sc, (const float4*)d_points, n, found, found_stride, q.spill, q.status);
+    if (!clean()) return false;
+    if (d_surfaces)
+    {
+        hipLaunchKernelGGL(k_nearest_surface, dim3(n / 256u + (n % 256u != 0u ? 1u : 0u)), dim3(256), 0, stream, sc.tris_sh, n_tris, object_of_triangle,
+            (const float4*)d_points, (const float4*)found, found_stride, n, (float4*)d_surfaces);
+        if (!clean()) return false;
+    }
+    return true;
+}
+
+static void corners(const rt_triangle& t, float (&p1)[3], float (&p2)[3], float (&p3)[3])
+{
+    p1[0] = t.v1.position.x; p1[1] = t.v1.position.y; p1[2] = t.v1.position.z;
+    p2[0] = t.v2.position.x; p2[1] = t.v2.position.y; p2[2] = t.v2.position.z;
+    p3[0] = t.v3.position.x; p3[1] = t.v3.position.y; p3[2] = t.v3.position.z;
+}
+
+static void brute_range(const rt_triangle* tris, uint32_t n_tris, const rt_point* points, uint32_t first, uint32_t end, rt_nearest* out)
+{
+    for (uint32_t i = first; i < end; ++i)
+    {
+        const float* p = points[i].position;
+        out[i] = nearest_none();
+        if (!nearest_searched(p, points[i].max_distance)) continue;
+        float best = points[i].max_distance * points[i].max_distance;
+        uint32_t best_prim = RT_INVALID_ID;
+        float p1[3], p2[3], p3[3];
+        for (uint32_t t = 0; t < n_tris; ++t)
+        {
+            corners(tris[t], p1, p2, p3);
+            const NpTriangle c = nearest_point_triangle(p, p1, p2, p3);
+            if (nearest_accepts(c.d2, t, best, best_prim)) { best = c.d2; best_prim = t; }
+        }
+        if (best_prim == RT_INVALID_ID) continue;
+        corners(tris[best_prim], p1, p2, p3);
+        out[i] = nearest_record(p, p1, p2, p3, best_prim);
+    }
+}
+
+void brute_host(const rt_triangle* tris, uint32_t n_tris, const rt_point* points, uint32_t n, rt_nearest* out)
+{
+    // every point is on its own: above a million pairs the points are shared out among up to 16 threads (no result depends on it)
+    const uint32_t threads = (uint64_t)n * n_tris < (1u << 20) ? 1u : (n < 16u ? n : 16u);
+    if (threads <= 1u) { brute_range(tris, n_tris, points, 0u, n, out); return; }
+    std::vector<std::thread> pool;
+    for (uint32_t t = 0; t < threads; ++t)
+        pool.emplace_back(brute_range, tris, n_tris, points, (uint32_t)((uint64_t)n * t / threads), (uint32_t)((uint64_t)n * (t + 1u) / threads), out);
+    for (std::thread& t : pool) t.join();
+}
+
+bool brute_device(hipStream_t stream, const rt_triangle* tris, uint32_t n_tris, const rt_point* points, uint32_t n, rt_nearest* out)
+{
+    void *d_tris = nullptr, *d_points = nullptr, *d_out = nullptr;
+    auto get = [&](void*& p, const void* src, size_t bytes)
+    {
+        if (hipMalloc(&p, bytes ? bytes : 16) != hipSuccess) { (void)hipGetLastError(); p = nullptr; return false; }
+        return !src || bytes == 0 || hipMemcpyAsync(p, src, bytes, hipMemcpyHostToDevice, stream) == hipSuccess;
+    };
+    bool ok = get(d_tris, tris, (size_t)n_tris * sizeof(rt_triangle)) && get(d_points, points, (size_t)n * sizeof(rt_point)) && get(d_out, nullptr, (size_t)n * sizeof(rt_nearest));
+    if (ok)
+    {
+        hipLaunchKernelGGL(k_nearest_brute, dim3(n / 256u + (n % 256u != 0u ? 1u : 0u)), dim3(256), 0, stream, (const rt_triangle*)d_tris, n_tris, (const float4*)d_points, n,
+            (float4*)d_out);
+        ok = clean() && hipMemcpyAsync(out, d_out, (size_t)n * sizeof(rt_nearest), hipMemcpyDeviceToHost, stream) == hipSuccess;
+    }
+    ok = hipStreamSynchronize(stream) == hipSuccess && ok;
+    (void)hipGetLastError();
+    for (void* p : {d_tris, d_points, d_out}) if (p) (void)hipFree(p);
+    return ok;
+}
+
+const char* walk_host(const rt_bvh_node* nodes, uint32_t nn, const rt_triangle* tris, uint32_t n_tris, bool wide, const rt_point* points, uint32_t n,
+    rt_nearest* out, uint32_t* tested)
+{
+    // the `last` flags of the trace records, and the child-pair form's references: an interior node's index, RT_LEAF_BIT | first triangle for a leaf
+    std::vector<uint8_t> last(n_tris, 0);
+    for (uint32_t i = 0; i < nn; ++i)
+    {
+        const uint32_t np = nodes[i].num_primitives_axis >> 16;
+        if (np > 0u)
+        {
+            if ((uint64_t)nodes[i].offset + np > n_tris) return "a leaf's triangles lie outside the array";
+            last[nodes[i].offset + np - 1u] = 1;
+        }
+        else if (i + 1u >= nn || nodes[i].offset <= i || nodes[i].offset >= nn) return "an interior node's children lie outside the array";
+    }
+    auto node_ref = [&](uint32_t c) { return (nodes[c].num_primitives_axis >> 16) != 0u ? RT_LEAF_BIT | nodes[c].offset : c; };
+    std::vector<WideNode> recs;
+    uint32_t wide_entry = 0;
+    if (wide && !rtw::build_wide_bvh(nodes, nn, rtw::RT_WIDE_SAH, recs, wide_entry)) return "the tree does not qualify for the 4-wide layout";
+    const float INF = __builtin_inff();
+
+    for (uint32_t i = 0; i < n; ++i)
+    {
+        const float* p = points[i].position;
+        out[i] = nearest_none();
+        if (tested) tested[i] = 0u;
+        if (!nearest_searched(p, points[i].max_distance)) continue;
+        float best = points[i].max_distance * points[i].max_distance;
+        uint32_t best_prim = RT_INVALID_ID, count = 0u;
+        struct Entry { uint32_t ref; float d2; } stack[RT_W4_STACK_MAX];
+        int sp = 0;
+        uint32_t ref = RT_IDLE_REF;
+        if (wide) ref = wide_entry;
+        else
+        {
+            // the super-root record: child 0 = (the root's box, the root), child 1 empty
+            const float lo[3] = {nodes[0].bounds_min.x, nodes[0].bounds_min.y, nodes[0].bounds_min.z}, hi[3] = {nodes[0].bounds_max.x, nodes[0].bounds_max.y, nodes[0].bounds_max.z};
+            if (!(nearest_box_d2(p, lo, hi) > best)) ref = node_ref(0);
+        }
+        auto pop = [&]()
+        {
+            ref = RT_IDLE_REF;
+            while (sp > 0)
+            {
+                --sp;
+                if (!(stack[sp].d2 > best)) { ref = stack[sp].ref; break; }
+            }
+        };
+        float p1[3], p2[3], p3[3];
+        while (ref != RT_IDLE_REF)
+        {
+            if ((int)ref < -1)
+            {
+                const uint32_t prim = ref & ~RT_LEAF_BIT;
+                if (prim >= n_tris) return "a leaf reference lies outside the triangle array";
+                corners(tris[prim], p1, p2, p3);
+                const NpTriangle t = nearest_point_triangle(p, p1, p2, p3);
+                ++count;
+                if (nearest_accepts(t.d2, prim, best, best_prim)) { best = t.d2; best_prim = prim; }
+                if (last[prim]) pop();
+                else ref = RT_LEAF_BIT | (prim + 1u);
+                continue;
+            }
+            uint32_t r[4] = {RT_EMPTY_REF, RT_EMPTY_REF, RT_EMPTY_REF, RT_EMPTY_REF};
+            float e[4] = {INF, INF, INF, INF};
+            if (wide)
+            {
+                if (ref >= recs.size()) return "a record reference lies outside the 4-wide tree";
+                const WideNode& w = recs[ref];
+                const float origin[3] = {w.ox, w.oy, w.oz};
+                float cell[3];
+                for (int a = 0; a < 3; ++a) { const uint32_t bits = ((w.meta >> (8 * a)) & 0xFFu) << 23; memcpy(&cell[a], &bits, 4); }
+                for (int k = 0; k < 4; ++k)
+                {
+                    float lo[3], hi[3];
+                    for (int a = 0; a < 3; ++a)
+                    {
+                        lo[a] = (float)((w.lo[a] >> (8 * k)) & 0xFFu) * cell[a] + origin[a];
+                        hi[a] = (float)((w.hi[a] >> (8 * k)) & 0xFFu) * cell[a] + origin[a];
+                    }
+                    r[k] = w.ref[k];
+                    e[k] = nearest_box_d2(p, lo, hi);
+                }
+            }
+            else
+            {
+                const uint32_t c[2] = {ref + 1u, nodes[ref].offset};
+                for (int k = 0; k < 2; ++k)
+                {
+                    const rt_bvh_node& b = nodes[c[k]];
+                    const float lo[3] = {b.bounds_min.x, b.bounds_min.y, b.bounds_min.z}, hi[3] = {b.bounds_max.x, b.bounds_max.y, b.bounds_max.z};
+                    r[k] = node_ref(c[k]);
+                    e[k] = nearest_box_d2(p, lo, hi);
+                }
+            }
+            for (int k = 0; k < 4; ++k)
+            {
+                const bool pass = r[k] != RT_EMPTY_REF && !(e[k] > best);
+                r[k] = pass ? r[k] : RT_EMPTY_REF;
+                e[k] = pass ? e[k] : INF;
+            }
+            auto exchange = [&](int a, int b)
+            {
+                if (e[b] < e[a]) { const float te = e[a]; e[a] = e[b]; e[b] = te; const uint32_t tr = r[a]; r[a] = r[b]; r[b] = tr; }
+            };
+            exchange(0, 1); exchange(2, 3); exchange(0, 2); exchange(1, 3); exchange(1, 2);
+            uint32_t next = RT_IDLE_REF;
+            float next_e = 0.0f;
+            for (int k = 3; k >= 0; --k)
+                if (r[k] != RT_EMPTY_REF)
+                {
+                    if (next != RT_IDLE_REF)
+                    {
+                        if (sp >= RT_W4_STACK_MAX) return "the tree is deeper than the walk's stack";
+                        stack[sp].ref = next; stack[sp].d2 = next_e; ++sp;
+                    }
+                    next = r[k]; next_e = e[k];
+                }
+            if (next != RT_IDLE_REF) ref = next;
+            else pop();
+        }
+        if (tested) tested[i] = count;
+        if (best_prim == RT_INVALID_ID) continue;
+        corners(tris[best_prim], p1, p2, p3);
+        out[i] = nearest_record(p, p1, p2, p3, best_prim);
+    }
+    return nullptr;
+}
+} // namespace nearest

@@ -1,0 +1,249 @@
+// nearest_kernels.h -- the kernels of a nearest-point query (rt_scene_nearest / rt_scene_nearest_buffer / rt_debug_nearest): for each
+// CALLER-supplied point the nearest triangle of the uploaded scene, where on it, and how far.  The arithmetic is nearest.h's.
+//
+//   k_nearest<WIDE>    one lane per point, 64-thread blocks: rt_point in (16 bytes, one dwordx4), rt_nearest out (32 bytes, two dwordx4)
+//   k_nearest_brute    one lane per point over ALL triangles of an rt_triangle array (rt_debug_nearest's device form: the same nearest.h with no tree)
+//   k_nearest_surface  one lane per point: rt_surface (64 bytes) of the nearest point, by query.h's query_surface
+//
+// The walk.  k_query_trace's fused one-loop shape, restated (query_kernels.h is not touched, so its instructions stay what they were): a lane's point is at a
+// reference -- a 4-wide record (WIDE), a child-pair record (!WIDE), or a triangle of a leaf -- and every pass of the one loop fetches the lane's next 64 bytes
+// with the same four 16-byte loads and takes its step.  What differs from a ray's walk is the test and the order: a box is passed when !(nearest_box_d2 > best),
+// the nearest passing box is visited next, and the others wait on the stack with their nearest_box_d2 as the entry value, farthest deepest; a pop re-tests
+// !(entry > best).  nearest_box_d2 <= d2 holds in binary32 itself for every box that holds a triangle's corners (nearest.h), so no order, no fold and no
+// quantisation of a box can change the result: it is the brute-force minimum bit for bit.
+//   * a 4-wide record: the four slots' boxes are origin + q * cell, exactly representable (wide_quant.h: wide_frame keeps the grid in binary32's reach,
+//     wide_quantise rounds outward), so the bound applies to them as to any box; RT_EMPTY_REF slots are skipped.
+//   * a child-pair record: the two children's exact boxes, the same step with two candidates.
+//   * a leaf: its triangles in array order until the `last` flag.  The corners come from the 128-byte SHADING record (its first 64 bytes: p1, p2, p3 and a
+//     normal that is not used): the 64-byte trace record holds p1 and the rounded edges p2 - p1, p3 - p1, from which p2 and p3 cannot be had bit for bit.  The
+//     trace record is read for its `last` flag alone (one dword, issued with the four loads).  The leaf's exact box in the trace record is not tested again:
+//     a slot's box is that box rounded outward by less than a cell, and the test would cost every leaf a pass of its own.
+//   * a point that is not searched (nearest.h) is not walked.  Points far outside the scene need no special walk: the gaps stay finite or overflow to +inf on
+//     both sides of every comparison.
+// WIDE is the launch's, not the lane's: nearest::launch takes the 4-wide records when Scene::wide_ok holds (query::launch's rule), the child-pair records
+// otherwise (RT_CTX_OPT_WIDE_BVH = 0, a refit that disqualified the wide tree).
+//
+// Stack: (ref, nearest_box_d2) entries, RT_QUERY_STACK_LDS per lane in LDS in k_query_trace's lane-major 8-byte layout, the rest in the lane's slice of the
+// ray queries' spill area, RT_W4_STACK_MAX in all (at most three pending slots per wide level, one pending child per pair level).  A push beyond it is not
+// written; it raises the ray queries' status word.
+//
+// Grid: k_query_trace's persistent strided chunks of 64 consecutive points.
+#pragma once
+#include "query_kernels.h"
+#include "nearest.h"
+
+namespace nearest
+{
+template <bool WIDE>
+__global__ __launch_bounds__(64) void k_nearest(DScene sc, const float4* __restrict__ points, uint32_t n, float4* __restrict__ out, uint32_t out_stride /* in float4 */,
+    uint2* __restrict__ spill, uint32_t* __restrict__ status)
+{
+    __shared__ uint2 stack[RT_QUERY_STACK_LDS][64];
+    const uint32_t lane = threadIdx.x;
+    uint2* const my_spill = spill + (size_t)(blockIdx.x * 64u + lane) * RT_QUERY_SPILL_PER_LANE;
+    const char* const node_base = reinterpret_cast<const char*>(WIDE ? sc.wnodes : sc.nodes);
+    const char* const tri_base = reinterpret_cast<const char*>(sc.tris_sh);
+    const float* const flag_base = reinterpret_cast<const float*>(sc.tris_rt);
+    const float INF = __builtin_inff();
+    const uint32_t n_chunks = (n >> 6) + ((n & 63u) != 0u ? 1u : 0u);
+    bool overflow = false;
+
+    for (uint32_t chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x)
+    {
+        const uint32_t i = chunk * 64u + lane;
+        uint32_t ref = RT_IDLE_REF, best_prim = RT_INVALID_ID;
+        float p[3] = {0.0f, 0.0f, 0.0f};
+        float best = 0.0f;
+        int sp = 0;
+        if (i < n)
+        {
+            const float4 q = q_load(points + i);
+            p[0] = q.x; p[1] = q.y; p[2] = q.z;
+            if (nearest_searched(p, q.w))
+            {
+                best = q.w * q.w;
+                ref = WIDE ? sc.w_entry_ref : sc.entry_ref;
+            }
+        }
+
+        auto push = [&](uint32_t r, float entry)
+        {
+            const uint2 e = make_uint2(r, __float_as_uint(entry));
+            if (sp < RT_QUERY_STACK_LDS) stack[sp][lane] = e;
+            else if (sp < RT_W4_STACK_MAX) my_spill[sp - RT_QUERY_STACK_LDS] = e;
+            else { overflow = true; return; }
+            ++sp;
+        };
+        auto pop = [&]()
+        {
+            ref = RT_IDLE_REF;
+            while (sp > 0)
+            {
+                --sp;
+                const uint2 e = sp < RT_QUERY_STACK_LDS ? stack[sp][lane] : spill_load64(my_spill + (sp - RT_QUERY_STACK_LDS));
+                if (!(__uint_as_float(e.y) > best)) { ref = e.x; break; }
+            }
+        };
+
+        while (__ballot(ref != RT_IDLE_REF) != 0ull)
+        {
+            if (ref != RT_IDLE_REF)
+            {
+                const bool at_leaf = (int)ref < -1;
+                const uint32_t prim = ref & ~RT_LEAF_BIT;
+                float last = 0.0f;
+                if (at_leaf) last = flag_base[((size_t)prim << 4) + 3u];
+                const float4* rp = reinterpret_cast<const float4*>(at_leaf ? tri_base + ((size_t)prim << 7) : node_base + ((size_t)ref << 6));
+                const float4 q0 = rp[0], q1 = rp[1], q2 = rp[2], q3 = rp[3];
+                if (at_leaf)
+                {
+                    const float p1[3] = {q0.x, q0.y, q0.z}, p2[3] = {q1.x, q1.y, q1.z}, p3[3] = {q2.x, q2.y, q2.z};
+                    const NpTriangle t = nearest_point_triangle(p, p1, p2, p3);
+                    if (nearest_accepts(t.d2, prim, best, best_prim)) { best = t.d2; best_prim = prim; }
+                    if (last != 0.0f) pop();
+                    else ref = RT_LEAF_BIT | (prim + 1u);
+                }
+                else
+                {
+                    uint32_t r[4];
+                    float e[4];
+                    if (WIDE)
+                    {
+                        const uint32_t meta = __float_as_uint(q0.w);
+                        const float cell[3] = {__uint_as_float((meta & 0xFFu) << 23), __uint_as_float(((meta >> 8) & 0xFFu) << 23), __uint_as_float(((meta >> 16) & 0xFFu) << 23)};
+                        const float origin[3] = {q0.x, q0.y, q0.z};
+                        const uint32_t low[3] = {__float_as_uint(q1.x), __float_as_uint(q1.y), __float_as_uint(q1.z)};
+                        const uint32_t high[3] = {__float_as_uint(q1.w), __float_as_uint(q2.x), __float_as_uint(q2.y)};
+                        r[0] = __float_as_uint(q2.z); r[1] = __float_as_uint(q2.w); r[2] = __float_as_uint(q3.x); r[3] = __float_as_uint(q3.y);
+#pragma unroll
+                        for (int k = 0; k < 4; ++k)
+                        {
+                            float lo[3], hi[3];
+#pragma unroll
+                            for (int a = 0; a < 3; ++a)
+                            {
+                                lo[a] = (float)((low[a] >> (8 * k)) & 0xFFu) * cell[a] + origin[a];       // exact (wide_frame)
+                                hi[a] = (float)((high[a] >> (8 * k)) & 0xFFu) * cell[a] + origin[a];
+                            }
+                            e[k] = nearest_box_d2(p, lo, hi);
+                        }
+                    }
+                    else
+                    {
+                        const float lo0[3] = {q0.x, q0.y, q2.x}, hi0[3] = {q0.z, q0.w, q2.y}, lo1[3] = {q1.x, q1.y, q2.z}, hi1[3] = {q1.z, q1.w, q2.w};
+                        r[0] = __float_as_uint(q3.x); r[1] = __float_as_uint(q3.y); r[2] = RT_EMPTY_REF; r[3] = RT_EMPTY_REF;
+                        e[0] = nearest_box_d2(p, lo0, hi0); e[1] = nearest_box_d2(p, lo1, hi1); e[2] = INF; e[3] = INF;
+                    }
+                    // a slot that is empty or too far leaves the step: marked by RT_EMPTY_REF, keyed +inf
+#pragma unroll
+                    for (int k = 0; k < 4; ++k)
+                    {
+                        const bool pass = r[k] != RT_EMPTY_REF && !(e[k] > best);
+                        r[k] = pass ? r[k] : RT_EMPTY_REF;
+                        e[k] = pass ? e[k] : INF;
+                    }
+                    // ascending by nearest_box_d2 (five exchanges; two candidates need the first only)
+                    auto exchange = [&](int a, int b)
+                    {
+                        const bool s = e[b] < e[a];
+                        const float te = s ? e[b] : e[a]; e[b] = s ? e[a] : e[b]; e[a] = te;
+                        const uint32_t tr = s ? r[b] : r[a]; r[b] = s ? r[a] : r[b]; r[a] = tr;
+                    };
+                    exchange(0, 1);
+                    if (WIDE) { exchange(2, 3); exchange(0, 2); exchange(1, 3); exchange(1, 2); }
+                    // the nearest passing slot is visited next, the others wait on the stack, farthest deepest
+                    uint32_t next = RT_IDLE_REF;
+                    float next_e = 0.0f;
+#pragma unroll
+                    for (int k = WIDE ? 3 : 1; k >= 0; --k)
+                        if (r[k] != RT_EMPTY_REF)
+                        {
+                            if (next != RT_IDLE_REF) push(next, next_e);
+                            next = r[k]; next_e = e[k];
+                        }
+                    if (next != RT_IDLE_REF) ref = next;
+                    else pop();
+                }
+            }
+        }
+
+        if (i < n)
+        {
+            rt_nearest o = nearest_none();
+            if (best_prim != RT_INVALID_ID)
+            {
+                const float4* tp = sc.tris_sh + (size_t)best_prim * 8;
+                const float4 a = tp[0], b = tp[1], c = tp[2];
+                const float p1[3] = {a.x, a.y, a.z}, p2[3] = {b.x, b.y, b.z}, p3[3] = {c.x, c.y, c.z};
+                o = nearest_record(p, p1, p2, p3, best_prim);
+            }
+            float4* op = out + (size_t)i * out_stride;
+            q_store(op, make_float4(o.position[0], o.position[1], o.position[2], o.distance));
+            q_store(op + 1, make_float4(o.bc[0], o.bc[1], __uint_as_float(o.primitive_id), __uint_as_float(o.flags)));
+        }
+    }
+    if (overflow) *status = 1u;                                  // pinned host memory: the host reads it after it has waited for the stream
+}
+
+__global__ __launch_bounds__(256) void k_nearest_brute(const rt_triangle* __restrict__ tris, uint32_t n_tris, const float4* __restrict__ points, uint32_t n,
+    float4* __restrict__ out)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const float4 q = points[i];
+    const float p[3] = {q.x, q.y, q.z};
+    rt_nearest o = nearest_none();
+    if (nearest_searched(p, q.w))
+    {
+        float best = q.w * q.w;
+        uint32_t best_prim = RT_INVALID_ID;
+        for (uint32_t t = 0; t < n_tris; ++t)
+        {
+            const rt_triangle& tr = tris[t];
+            const float p1[3] = {tr.v1.position.x, tr.v1.position.y, tr.v1.position.z}, p2[3] = {tr.v2.position.x, tr.v2.position.y, tr.v2.position.z},
+                        p3[3] = {tr.v3.position.x, tr.v3.position.y, tr.v3.position.z};
+            const NpTriangle c = nearest_point_triangle(p, p1, p2, p3);
+            if (nearest_accepts(c.d2, t, best, best_prim)) { best = c.d2; best_prim = t; }
+        }
+        if (best_prim != RT_INVALID_ID)
+        {
+            const rt_triangle& tr = tris[best_prim];
+            const float p1[3] = {tr.v1.position.x, tr.v1.position.y, tr.v1.position.z}, p2[3] = {tr.v2.position.x, tr.v2.position.y, tr.v2.position.z},
+                        p3[3] = {tr.v3.position.x, tr.v3.position.y, tr.v3.position.z};
+            o = nearest_record(p, p1, p2, p3, best_prim);
+        }
+    }
+    out[2 * (size_t)i] = make_float4(o.position[0], o.position[1], o.position[2], o.distance);
+    out[2 * (size_t)i + 1] = make_float4(o.bc[0], o.bc[1], __uint_as_float(o.primitive_id), __uint_as_float(o.flags));
+}
+
+// found[i * found_stride .. + 1] = point i's rt_nearest; it may be the first 32 bytes of out[i] itself (a query that returns surfaces only keeps its records
+// there): lane i reads it before it writes.  `tris` = the scene's 128-byte shading records (k_query_surface<true>'s reading of them).
+__global__ __launch_bounds__(256) void k_nearest_surface(const float4* __restrict__ tris, uint32_t n_tris, const uint32_t* __restrict__ object_of_triangle,
+    const float4* __restrict__ points, const float4* found, uint32_t found_stride, uint32_t n, float4* out)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const float4 f0 = found[(size_t)i * found_stride], f1 = found[(size_t)i * found_stride + 1];
+    const uint32_t prim = __float_as_uint(f1.z);
+    rt_surface s = qs_miss();
+    if (prim < n_tris)                                           // RT_INVALID_ID (nothing found) is above every count
+    {
+        QsTriangle t;
+        const float4* tp = tris + (size_t)prim * 8;
+        const float4 q0 = tp[0], q1 = tp[1], q2 = tp[2], q3 = tp[3], q4 = tp[4], q5 = tp[5], q6 = tp[6];
+        t.p1[0] = q0.x; t.p1[1] = q0.y; t.p1[2] = q0.z; t.p2[0] = q1.x; t.p2[1] = q1.y; t.p2[2] = q1.z; t.p3[0] = q2.x; t.p3[1] = q2.y; t.p3[2] = q2.z;
+        t.n1[0] = q3.x; t.n1[1] = q3.y; t.n1[2] = q3.z; t.n2[0] = q4.x; t.n2[1] = q4.y; t.n2[2] = q4.z; t.n3[0] = q5.x; t.n3[1] = q5.y; t.n3[2] = q5.z;
+        t.uv1[0] = q0.w; t.uv1[1] = q1.w; t.uv2[0] = q2.w; t.uv2[1] = q3.w; t.uv3[0] = q4.w; t.uv3[1] = q5.w;
+        t.mtl_index = __float_as_uint(q6.x);
+        const float4 pt = points[i];
+        const float d[3] = {f0.x - pt.x, f0.y - pt.y, f0.z - pt.z};          // q - p: the direction from the point to the surface
+        s = query_surface(t, d, f1.x, f1.y, f0.w, prim, object_of_triangle ? object_of_triangle[prim] : RT_INVALID_ID);
+    }
+    float4* o = out + (size_t)i * 4;
+    o[0] = make_float4(s.position[0], s.position[1], s.position[2], __uint_as_float(s.primitive_id));
+    o[1] = make_float4(s.geometric_normal[0], s.geometric_normal[1], s.geometric_normal[2], __uint_as_float(s.mtl_index));
+    o[2] = make_float4(s.shading_normal[0], s.shading_normal[1], s.shading_normal[2], __uint_as_float(s.object));
+    o[3] = make_float4(s.texcoord[0], s.texcoord[1], s.t, __uint_as_float(s.flags));
+}
+} // namespace nearest

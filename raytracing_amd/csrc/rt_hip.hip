@@ -30,6 +30,7 @@
 #include "filters_host.h"         // the filters' guide pass, a-trous passes and temporal stages (filters.hip)
 #include "query_host.h"      // caller-supplied rays traced against the uploaded scene (query.hip)
 #include "bake_host.h"       // ambient occlusion and bent normals at caller-supplied points (bake.hip)
+#include "nearest_host.h"    // the nearest surface point to caller-supplied points (nearest.hip)
 using namespace rtw;
 
 namespace
@@ -1077,6 +1078,7 @@ extern "C" {
 #include "pose_impl.h"
 #include "query_impl.h"
 #include "bake_impl.h"
+#include "nearest_impl.h"
 
 // ---- scene -----------------------------------------------------------------
 int rt_scene_upload(rt_ctx* ctx, const rt_scene_desc* sd)

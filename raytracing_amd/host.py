@@ -26,7 +26,7 @@ EXPORTS = [
     "rth_render_upload_gpu_data", "rth_render_setup_seconds", "rth_render_create_with_options",
     "rth_render_set_refittable", "rth_render_refit", "rth_render_set_refit_motion",
     "rth_render_set_objects", "rth_render_pose", "rth_render_pick", "rth_render_integrator_pick", "rth_render_trace",
-    "rth_render_bake", "rth_render_occlusion_image",
+    "rth_render_bake", "rth_render_occlusion_image", "rth_render_nearest",
     "rth_scene_set_triangle_objects", "rth_scene_num_objects", "rth_scene_object_name", "rth_scene_num_triangle_objects", "rth_scene_triangle_objects",
 ]
 
@@ -76,6 +76,7 @@ def load():
         "rth_render_set_objects": (i32, [vp, vp, u32, u32]), "rth_render_pose": (i32, [vp, vp, u32]),
         "rth_render_pick": (i32, [vp, u32, u32, vp, vp, vp]), "rth_render_integrator_pick": (i32, [vp, u32, u32, vp, vp, vp]), "rth_render_trace": (i32, [vp, vp, u32, i32, vp, vp, vp]),
         "rth_render_bake": (i32, [vp, vp, u32, vp, vp]), "rth_render_occlusion_image": (i32, [vp, vp, vp]),
+        "rth_render_nearest": (i32, [vp, vp, u32, vp, vp]),
         "rth_render_num_nodes": (u32, [vp]), "rth_render_nodes": (vp, [vp]),
         "rth_render_set_aov": (i32, [vp, i32]), "rth_render_resolve": (i32, [vp, vp]),
         "rth_render_set_blue_noise_path": (i32, [vp, cp]),
@@ -402,6 +403,29 @@ class Render:
         out = np.zeros((self.height, self.width), np.float32)
         self._c(self.lib.rth_render_occlusion_image(self.handle, C.addressof(d), out.ctypes.data))
         return out
+
+    def nearest(self, points):
+        """The nearest surface point to each of the caller's points against the scene as it is posed now (Render::Nearest; points: capi.point_records' rule):
+        a list of dicts like pick()'s -- the surface's fields (primitive_id 0xFFFFFFFF and zeros where nothing was found) plus `nearest`, the types.nearest
+        record (position, distance, bc, flags); when the scene was loaded with objects, also `object_name`"""
+        from . import capi
+        pts = capi.point_records(points)
+        n = len(pts)
+        found, surf = np.zeros(n, T.nearest), np.zeros(n, T.surface)
+        self._c(self.lib.rth_render_nearest(self.handle, pts.ctypes.data if n else None, n, found.ctypes.data, surf.ctypes.data))
+        names = self.scene.object_names()
+        objects = self.scene.triangle_objects() if names else None
+        result = []
+        for i in range(n):
+            out = {k: (surf[i][k].copy() if surf[i][k].ndim else surf[i][k].item()) for k in T.surface.names}
+            out["nearest"] = found[i]
+            if names:
+                prim = out["primitive_id"]
+                if out["object"] == 0xFFFFFFFF and prim < len(objects):
+                    out["object"] = int(objects[prim])                  # no objects set on the device: the scene's own table says whose triangle it is
+                out["object_name"] = names[out["object"]] if prim != 0xFFFFFFFF and out["object"] < len(names) else None
+            result.append(out)
+        return result
 
     def tree_report(self):
         from . import capi

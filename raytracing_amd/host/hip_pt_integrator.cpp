@@ -177,6 +177,12 @@ void HIPPathTraceIntegrator::TraceRays(rt_ray const* rays, std::size_t count, bo
     Check(rt_scene_trace(context_.Get(), rays, (uint32_t)count, any_hit ? RT_QUERY_ANY_HIT : RT_QUERY_CLOSEST, hits, occluded, surfaces));
 }
 
+void HIPPathTraceIntegrator::NearestPoints(rt_point const* points, std::size_t count, rt_nearest* out, rt_surface* surfaces)
+{
+    if (count > 0xFFFFFFFFull) throw HIPException("HIPPathTraceIntegrator::NearestPoints: more than 2^32 - 1 points in one call");
+    Check(rt_scene_nearest(context_.Get(), points, (uint32_t)count, out, surfaces));
+}
+
 void HIPPathTraceIntegrator::Pick(std::uint32_t x, std::uint32_t y, rt_ray* ray, rt_hit* hit, rt_surface* surface)
 {
     Check(rt_frame_pick(frame_, x, y, ray, hit, surface));

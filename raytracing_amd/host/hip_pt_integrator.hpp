@@ -117,6 +117,10 @@ public:
     // library's message on a refusal; neither requests a reset or touches the frame.
     void BakeOcclusion(void const* points, std::size_t count, rt_bake_desc const& desc, rt_bake_result* out);
     void OcclusionImageThrough(Camera const& camera, rt_bake_desc desc, float* out);
+    // Nearest surface points (rt_scene_nearest): for each of the caller's points the nearest triangle of the scene as it is posed now, where
+    // on it and how far, optionally with the rt_surface there; a count of 2^32 or more is refused.  Throws HIPException with the library's message on a
+    // refusal; requests no reset and does not touch the frame.
+    void NearestPoints(rt_point const* points, std::size_t count, rt_nearest* out, rt_surface* surfaces);
     rt_frame* GetFrame() const { return frame_; }
 
 protected:

@@ -274,6 +274,10 @@ int rth_render_occlusion_image(void* r, const rt_bake_desc* desc, float* out)
 {
     return guard([&]() { if (!desc) throw rt::HIPException("rth_render_occlusion_image: desc is NULL"); ((rt::Render*)r)->OcclusionImage(*desc, out); return 0; }, 1);
 }
+int rth_render_nearest(void* r, const rt_point* points, uint32_t n, rt_nearest* out, rt_surface* surfaces)
+{
+    return guard([&]() { ((rt::Render*)r)->Nearest(points, n, out, surfaces); return 0; }, 1);
+}
 int rth_render_upload_gpu_data(void* r) { return guard([&]() { ((rt::Render*)r)->UploadGPUData(); return 0; }, 1); }
 
 } // extern "C"

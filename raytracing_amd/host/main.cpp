@@ -2,6 +2,7 @@
 // (src/main.cpp:34-58: -w -h --scene --scale --flip_yz) plus the knobs the GUI
 // exposed (--bounces, --furnace, aperture/focus) and --spp / --out for batch use.
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -40,6 +41,7 @@ int main(int argc, char** argv)
         std::vector<PickAt> picks;              // --pick x,y (repeatable): after the scene is uploaded and posed, print what lies under that pixel
         std::string ao_out;                     // --ao out.pfm: after the scene is uploaded and posed, write the ambient occlusion image of the camera (grey, RGB equal)
         rt_bake_desc ao = {64u, 0u, 0u, 1e-3f, 1.0f};   // --ao_samples n --ao_radius r --ao_bias b
+        std::vector<rt_point> nearest_points;   // --nearest x,y,z[,r] (repeatable): after the scene is uploaded and posed, print the nearest surface point (within r)
         bool list_objects = false;              // --list_objects 1: print the OBJ's o / g shapes (index and name) and exit; needs no GPU
         for (int i = 1; i < argc; ++i)
         {
@@ -122,6 +124,18 @@ int main(int argc, char** argv)
                 picks.push_back(p);
                 scene_options |= rt::Scene::kObjects;
             }
+            else if (!strcmp(argv[i], "--nearest"))
+            {
+                rt_point q;
+                q.max_distance = INFINITY;
+                if (sscanf(next(), "%f,%f,%f,%f", &q.position[0], &q.position[1], &q.position[2], &q.max_distance) < 3)
+                {
+                    std::cerr << "--nearest wants x,y,z or x,y,z,r (a point and an optional largest distance)\n";
+                    return 2;
+                }
+                nearest_points.push_back(q);
+                scene_options |= rt::Scene::kObjects;
+            }
             else if (!strcmp(argv[i], "--ao")) ao_out = next();
             else if (!strcmp(argv[i], "--ao_samples")) ao.samples = (unsigned)atoi(next());
             else if (!strcmp(argv[i], "--ao_radius")) ao.radius = (float)atof(next());
@@ -152,7 +166,9 @@ int main(int argc, char** argv)
                              "  normals, texture coordinates, material and object (index and name); one GPU only\n"
                              "  --ao out.pfm --ao_samples n --ao_radius r [--ao_bias b] writes the exact ambient occlusion image of the camera once the scene is uploaded\n"
                              "  and posed: per pixel the share of n cosine-weighted rays (a power of two, 16 .. 4096; default 64) from the first hit that meet nothing within r\n"
-                             "  (default 1), 1 where the pixel sees nothing; traced and baked on the device (rt_scene_bake_buffer); one GPU only\n";
+                             "  (default 1), 1 where the pixel sees nothing; traced and baked on the device (rt_scene_bake_buffer); one GPU only\n"
+                             "  --nearest x,y,z[,r] (repeatable) prints the nearest surface point to that point (within r) once the scene is uploaded and posed: primitive,\n"
+                             "  distance, position, feature (face, edge or vertex), material and object (index and name); one GPU only\n";
                 return 0;
             }
         }
@@ -192,6 +208,11 @@ int main(int argc, char** argv)
         if (!picks.empty() && (gpus > 1 || tiled_path))
         {
             std::cerr << "--pick needs one GPU\n";
+            return 2;
+        }
+        if (!nearest_points.empty() && (gpus > 1 || tiled_path))
+        {
+            std::cerr << "--nearest needs one GPU\n";
             return 2;
         }
         if (!ao_out.empty() && (gpus > 1 || tiled_path))
@@ -293,6 +314,29 @@ int main(int argc, char** argv)
                 std::cout << ((s.flags & 2u) ? " (back face)" : "") << std::endl;
             }
         };
+        // --nearest: one line per point (rt_scene_nearest through Render::Nearest); the object as --pick names it
+        auto print_nearest = [&]()
+        {
+            if (nearest_points.empty()) return;
+            std::vector<rt_nearest> found(nearest_points.size());
+            std::vector<rt_surface> surf(nearest_points.size());
+            render.Nearest(nearest_points.data(), nearest_points.size(), found.data(), surf.data());
+            for (size_t i = 0; i < found.size(); ++i)
+            {
+                const rt_point& q = nearest_points[i];
+                const rt_nearest& f = found[i];
+                std::cout << "nearest " << q.position[0] << "," << q.position[1] << "," << q.position[2] << ": ";
+                if (f.primitive_id == RT_INVALID_ID) { std::cout << "none" << std::endl; continue; }
+                std::uint32_t object = surf[i].object;
+                if (object == RT_INVALID_ID && f.primitive_id < scene.GetTriangleObjects().size()) object = scene.GetTriangleObjects()[f.primitive_id];
+                static const char* const feature[4] = {"face", "edge", "vertex", "?"};
+                std::cout << "primitive " << f.primitive_id << " distance " << f.distance << " position " << f.position[0] << " " << f.position[1] << " " << f.position[2]
+                          << " feature " << feature[(f.flags >> RT_NEAREST_FEATURE_SHIFT) & 3u] << " material " << surf[i].mtl_index << " object ";
+                if (object < scene.GetObjectNames().size()) std::cout << object << " " << scene.GetObjectNames()[object];
+                else std::cout << "none";
+                std::cout << ((f.flags & RT_NEAREST_BACK_SIDE) ? " (back side)" : "") << std::endl;
+            }
+        };
         // --ao: Render::OcclusionImage of the camera as it stands, written as a grey PFM
         auto write_ao = [&]()
         {
@@ -347,6 +391,7 @@ int main(int argc, char** argv)
                       << " s: " << df * 1e3 / frames << " ms per frame" << std::endl;
             if (!out.empty()) WritePFM(out.c_str(), img, width, height);     // the last frame's resolved (filtered), tone-mapped image
             print_picks();
+            print_nearest();
             write_ao();
             return 0;
         }
@@ -386,6 +431,7 @@ int main(int argc, char** argv)
         double rays = (double)st.closest_rays + (double)st.shadow_rays;
         std::cout << spp << " spp in " << dt << " s, " << rays / dt / 1e6 << " Mrays/s" << std::endl;
         print_picks();
+        print_nearest();
         write_ao();
         if (!out.empty() && (filter_iterations >= 0 || temporal_iterations >= 0))
             WritePFM(out.c_str(), render.GetIntegrator().ResolveNow(), width, height);     // the filtered, tone-mapped image

@@ -50,6 +50,8 @@ public:
     // current camera (also one set since the last frame), width x height floats, 1 where the pixel-centre ray misses; the frame is not touched
     void BakeOcclusion(void const* points, std::size_t count, rt_bake_desc const& desc, rt_bake_result* out) { integrator_->BakeOcclusion(points, count, desc, out); }
     void OcclusionImage(rt_bake_desc const& desc, float* out) { integrator_->OcclusionImageThrough(camera_, desc, out); }
+    // the nearest surface point to each of the caller's points; the frame is not touched
+    void Nearest(rt_point const* points, std::size_t count, rt_nearest* out, rt_surface* surfaces) { integrator_->NearestPoints(points, count, out, surfaces); }
     AccelerationStructure const& GetAccelerationStructure() const { return *acc_structure_; }
     std::uint32_t GetWidth() const { return width_; }
     std::uint32_t GetHeight() const { return height_; }

@@ -24,6 +24,9 @@ surface = np.dtype([("position", "<f4", (3,)), ("primitive_id", "<u4"), ("geomet
                     ("shading_normal", "<f4", (3,)), ("object", "<u4"), ("texcoord", "<f4", (2,)), ("t", "<f4"), ("flags", "<u4")])
 # rt_bake_result (include/rt_hip.h): what an occlusion bake reports of a point; a skipped point is unoccluded = 0xFFFFFFFF and zeros
 bake_result = np.dtype([("bent_normal", "<f4", (3,)), ("unoccluded", "<u4")])
+# rt_point / rt_nearest (include/rt_hip.h): a nearest-point query's point (max_distance may be +inf) and its answer; nothing found is primitive_id = 0xFFFFFFFF and zeros
+point = np.dtype([("position", "<f4", (3,)), ("max_distance", "<f4")])
+nearest = np.dtype([("position", "<f4", (3,)), ("distance", "<f4"), ("bc", "<f4", (2,)), ("primitive_id", "<u4"), ("flags", "<u4")])
 camera = np.dtype([("position", float3), ("front", float3), ("up", float3), ("fov", "<f4"),
                    ("aspect_ratio", "<f4"), ("aperture", "<f4"), ("focus_distance", "<f4")])
 
@@ -31,6 +34,7 @@ assert ray.itemsize == 32 and hit.itemsize == 16 and scene_info.itemsize == 16
 assert packed_material.itemsize == 20 and light.itemsize == 48 and texture.itemsize == 16
 assert vertex.itemsize == 48 and triangle.itemsize == 160 and bvh_node.itemsize == 48
 assert camera.itemsize == 64 and surface.itemsize == 64 and bake_result.itemsize == 16
+assert point.itemsize == 16 and nearest.itemsize == 32
 
 
 def default_camera(width, height):
