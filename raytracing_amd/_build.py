@@ -50,9 +50,9 @@ HIP_UNITS = [
     ("filters", "filters.hip", True),          # the guide pass, the spatial filter's a-trous passes, the temporal filter's stages (a code object of its own, like device_fold's)
     ("refit", "refit.hip", True),              # the refit of the scene's trees when its triangles move: kernels + their host driver + the host restatement (a code object of its own)
     ("pose", "pose.hip", True),                # the scene's objects posed from one matrix per object: kernels + host driver + the host restatement (a code object of its own)
-    ("query", "query.hip", True),              # caller-supplied rays traced against the uploaded scene, the surface record of a hit: kernels + host driver + the host restatement (a code object of its own)
-    ("bake", "bake.hip", True),                # ambient occlusion and bent normals at caller-supplied points: kernels + host driver + the host restatement (a code object of its own)
-    ("nearest", "nearest.hip", True),          # the nearest surface point to caller-supplied points: kernels + host driver + the host's brute force and walk (a code object of its own)
+    ("query", "query.hip", True),              # caller-supplied rays traced against the uploaded scene, the surface record of a hit: kernels (the walk itself: walk_kernels.h, shared with bake and nearest) + the host driver core of all three + the host restatement (a code object of its own)
+    ("bake", "bake.hip", True),                # ambient occlusion and bent normals at caller-supplied points: kernels on walk_kernels.h + host driver on query.hip's core + the host restatement (a code object of its own)
+    ("nearest", "nearest.hip", True),          # the nearest surface point to caller-supplied points: kernels on walk_kernels.h's stack + host driver on query.hip's core + the host's brute force and walk (a code object of its own)
     ("wide_bvh", "wide_bvh.cpp", False),       # build_wide_bvh, pair layout, the adaptation's host walks (no device code)
 ]
 

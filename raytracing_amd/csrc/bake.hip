@@ -10,33 +10,7 @@
 namespace bake
 {
 static_assert(sizeof(rt_bake_result) == sizeof(float4) && sizeof(rt_surface) == 4 * sizeof(float4) && sizeof(rt_ray) == 2 * sizeof(float4), "records as 16-byte pieces");
-#define RT_BAKE_WAVES_PER_CU 20u        // 6 KiB of LDS per block: 26 fit a CU's 160 KiB; the registers (84 VGPRs) allow 5 waves per SIMD
-
-static bool clean() { return hipGetLastError() == hipSuccess; }
-
-size_t Scratch::spill_bytes() const { return (size_t)spill_blocks * 64u * RT_QUERY_SPILL_PER_LANE * sizeof(uint2); }
-size_t Scratch::bytes() const { return spill_bytes() + stage_bytes[0] + stage_bytes[1]; }
-
-void release(Scratch& s)
-{
-    if (s.spill) (void)hipFree(s.spill);
-    for (int k = 0; k < 2; ++k) if (s.stage[k]) (void)hipFree(s.stage[k]);
-    s = Scratch();
-}
-
-bool reserve(hipStream_t stream, Scratch& s, int k, size_t bytes)
-{
-    if (bytes <= s.stage_bytes[k]) return true;
-    if (s.stage[k])
-    {
-        (void)hipStreamSynchronize(stream);
-        (void)hipFree(s.stage[k]);
-        s.stage[k] = nullptr; s.stage_bytes[k] = 0;
-    }
-    if (hipMalloc(&s.stage[k], bytes) != hipSuccess) { (void)hipGetLastError(); s.stage[k] = nullptr; return false; }
-    s.stage_bytes[k] = bytes;
-    return true;
-}
+#define RT_BAKE_WAVES_PER_CU 20u        // 6 KiB of LDS per block: 26 fit a CU's 160 KiB; the registers (82 VGPRs) allow 5 waves per SIMD
 
 const char* desc_refusal(const rt_bake_desc& d)
 {
@@ -47,28 +21,16 @@ const char* desc_refusal(const rt_bake_desc& d)
     return nullptr;
 }
 
-bool launch(hipStream_t stream, Scratch& s, uint32_t** status, const DScene& sc, bool use_wide, int compute_units, const void* d_points, uint32_t n,
+bool launch(hipStream_t stream, query::Scratch& s, uint32_t** status, const DScene& sc, bool use_wide, int compute_units, const void* d_points, uint32_t n,
     uint32_t first_index, const rt_bake_desc& d, rt_bake_result* d_out)
 {
     if (n == 0u) return true;
     const uint32_t per_wave = d.samples < 64u ? 64u / d.samples : 1u;
-    const uint32_t n_groups = n / per_wave + (n % per_wave != 0u ? 1u : 0u);
-    const uint32_t resident = (((uint32_t)compute_units * RT_BAKE_WAVES_PER_CU) + 7u) & ~7u;
-    const uint32_t blocks = n_groups < resident ? n_groups : resident;
-    if (!*status)
-    {
-        if (hipHostMalloc((void**)status, 4) != hipSuccess) { (void)hipGetLastError(); *status = nullptr; return false; }
-        **status = 0u;
-    }
-    if (blocks > s.spill_blocks)
-    {
-        if (s.spill) { (void)hipStreamSynchronize(stream); (void)hipFree(s.spill); s.spill = nullptr; s.spill_blocks = 0; }
-        if (hipMalloc((void**)&s.spill, (size_t)blocks * 64u * RT_QUERY_SPILL_PER_LANE * sizeof(uint2)) != hipSuccess) { (void)hipGetLastError(); s.spill = nullptr; return false; }
-        s.spill_blocks = blocks;
-    }
+    const uint32_t blocks = query::prepare(stream, s, status, compute_units, RT_BAKE_WAVES_PER_CU, n / per_wave + (n % per_wave != 0u ? 1u : 0u));
+    if (blocks == 0u) return false;
     hipLaunchKernelGGL(k_bake, dim3(blocks), dim3(64), 0, stream, sc, (const float4*)d_points, (d.flags & RT_BAKE_FROM_SURFACES) ? 1u : 0u, n, first_index, d.samples,
         d.seed, d.bias, d.radius, (float4*)d_out, s.spill, use_wide ? 1u : 0u, *status);
-    return clean();
+    return query::clean();
 }
 
 void debug_rays_host(const void* points, uint32_t n, uint32_t first_index, const rt_bake_desc& d, rt_ray* out)
@@ -97,19 +59,14 @@ void debug_rays_host(const void* points, uint32_t n, uint32_t first_index, const
 bool debug_rays_device(hipStream_t stream, const void* points, uint32_t n, uint32_t first_index, const rt_bake_desc& d, rt_ray* out)
 {
     const size_t n_rays = (size_t)n * d.samples;
-    void *d_points = nullptr, *d_rays = nullptr;
-    bool ok = hipMalloc(&d_points, (size_t)n * point_bytes(d)) == hipSuccess && hipMalloc(&d_rays, n_rays * sizeof(rt_ray)) == hipSuccess &&
-              hipMemcpyAsync(d_points, points, (size_t)n * point_bytes(d), hipMemcpyHostToDevice, stream) == hipSuccess;
+    query::DeviceTemps tmp(stream);
+    void* const d_points = tmp.get(points, (size_t)n * point_bytes(d));
+    void* const d_rays = tmp.get(nullptr, n_rays * sizeof(rt_ray));
+    const bool ok = d_points && d_rays;
     if (ok)
-    {
         hipLaunchKernelGGL(k_bake_rays, dim3((uint32_t)((n_rays + 255u) / 256u)), dim3(256), 0, stream, (const float4*)d_points, (d.flags & RT_BAKE_FROM_SURFACES) ? 1u : 0u, n,
             first_index, d.samples, d.seed, d.bias, d.radius, (float4*)d_rays);
-        ok = clean() && hipMemcpyAsync(out, d_rays, n_rays * sizeof(rt_ray), hipMemcpyDeviceToHost, stream) == hipSuccess;
-    }
-    ok = hipStreamSynchronize(stream) == hipSuccess && ok;
-    (void)hipGetLastError();
-    for (void* p : {d_points, d_rays}) if (p) (void)hipFree(p);
-    return ok;
+    return tmp.finish(ok && query::clean(), out, d_rays, n_rays * sizeof(rt_ray));
 }
 
 void debug_reduce_host(const rt_ray* rays, const uint32_t* occluded, uint32_t n, uint32_t samples, rt_bake_result* out)

@@ -7,6 +7,7 @@
 #include <stdint.h>
 #include <stddef.h>
 #include "rt_hip.h"
+#include "query_host.h"
 
 struct DScene;
 
@@ -14,25 +15,14 @@ namespace bake
 {
 enum { CHUNK_POINTS = 1u << 20 };        // rt_scene_bake stages at most this many points at a time (RT_CTX_OPT_BAKE_CHUNK_POINTS: fewer)
 
-// what a context keeps for its bakes: the walk's stack spill area (sized by the grid) and rt_scene_bake's two staging arrays (grown on demand)
-struct Scratch
-{
-    uint2* spill = nullptr; uint32_t spill_blocks = 0;
-    void* stage[2] = {nullptr, nullptr};     // points, results
-    size_t stage_bytes[2] = {0, 0};
-    size_t bytes() const;                    // the device memory above
-    size_t spill_bytes() const;
-};
-void release(Scratch& s);
-bool reserve(hipStream_t stream, Scratch& s, int k, size_t bytes);
-
 // why a description is refused (nullptr: it is fine): samples a power of two in 16 .. 4096, finite bias, finite radius > 0, known flags
 const char* desc_refusal(const rt_bake_desc& d);
 inline size_t point_bytes(const rt_bake_desc& d) { return (d.flags & RT_BAKE_FROM_SURFACES) ? sizeof(rt_surface) : 32u; }
 
 // k_bake over d_points[n] on `stream`, nothing waited for.  first_index: the index of d_points[0] within the caller's array (a chunk of the host form).
+// s: the context's second query::Scratch, the bakes' own (its spill area; stages 0 and 1 hold the host form's points and results).
 // *status: the query's status word (pinned host memory), allocated here if it is not yet.  false: an allocation or the launch failed.
-bool launch(hipStream_t stream, Scratch& s, uint32_t** status, const DScene& sc, bool use_wide, int compute_units, const void* d_points, uint32_t n,
+bool launch(hipStream_t stream, query::Scratch& s, uint32_t** status, const DScene& sc, bool use_wide, int compute_units, const void* d_points, uint32_t n,
     uint32_t first_index, const rt_bake_desc& d, rt_bake_result* d_out);
 
 // rt_debug_bake_rays: n * samples rays, point-major, on the host or by k_bake_rays on an uploaded copy of the points

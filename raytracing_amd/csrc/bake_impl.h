@@ -18,12 +18,8 @@ static int bake_refused(rt_ctx* ctx, const char* who, bool points, uint32_t n, c
 static int bake_launch(rt_ctx* ctx, const char* who, const void* d_points, uint32_t n, uint32_t first_index, const rt_bake_desc& desc, rt_bake_result* d_out)
 {
     const Scene& s = ctx->scene;
-    if (!bake::launch(ctx->stream, ctx->bake, &ctx->query.status, s.d, s.wide_ok, ctx->prop.multiProcessorCount, d_points, n, first_index, desc, d_out))
-    {
-        (void)hipGetLastError();
-        return fail(ctx, std::string(who) + ": the bake could not be launched (the stack spill area could not be allocated, or the launch failed)");
-    }
-    return RT_OK;
+    return launch_result(ctx, who, bake::launch(ctx->stream, ctx->bake, &ctx->query.status, s.d, s.wide_ok, ctx->prop.multiProcessorCount, d_points, n, first_index, desc, d_out),
+        ": the bake could not be launched (the stack spill area could not be allocated, or the launch failed)");
 }
 
 int rt_scene_bake(rt_ctx* ctx, const void* points, uint32_t n, const rt_bake_desc* desc, rt_bake_result* out)
@@ -31,33 +27,16 @@ int rt_scene_bake(rt_ctx* ctx, const void* points, uint32_t n, const rt_bake_des
     if (ctx && n == 0u) return RT_OK;
     if (bake_refused(ctx, "rt_scene_bake", points != nullptr, n, desc, out != nullptr) != RT_OK) return RT_ERROR;
     (void)hipSetDevice(ctx->device);
-    bake::Scratch& b = ctx->bake;
-    const size_t record = bake::point_bytes(*desc);
-    for (uint32_t first = 0; first < n; )
-    {
-        const uint32_t m = n - first < ctx->bake_chunk_points ? n - first : ctx->bake_chunk_points;
-        if (!bake::reserve(ctx->stream, b, 0, (size_t)m * record) || !bake::reserve(ctx->stream, b, 1, (size_t)m * sizeof(rt_bake_result)))
-            return fail(ctx, "rt_scene_bake: out of device memory for the staging arrays");
-        HIPCHK(ctx, hipMemcpyAsync(b.stage[0], (const char*)points + (size_t)first * record, (size_t)m * record, hipMemcpyHostToDevice, ctx->stream));
-        if (bake_launch(ctx, "rt_scene_bake", b.stage[0], m, first, *desc, (rt_bake_result*)b.stage[1]) != RT_OK) return RT_ERROR;
-        HIPCHK(ctx, hipMemcpyAsync(out + first, b.stage[1], (size_t)m * sizeof(rt_bake_result), hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        if (query_check_status(ctx, "rt_scene_bake") != RT_OK) return RT_ERROR;
-        first += m;
-    }
-    return RT_OK;
+    query::Scratch& b = ctx->bake;
+    return staged_call(ctx, "rt_scene_bake", b, {{(void*)points, bake::point_bytes(*desc), 0, true}, {out, sizeof(rt_bake_result), 1, false}}, n, ctx->bake_chunk_points,
+        [&](uint32_t first, uint32_t m) { return bake_launch(ctx, "rt_scene_bake", b.stage[0], m, first, *desc, (rt_bake_result*)b.stage[1]); });
 }
 
 int rt_scene_bake_buffer(rt_ctx* ctx, rt_buffer* points, uint32_t n, const rt_bake_desc* desc, rt_buffer* out)
 {
     if (ctx && n == 0u) return RT_OK;
     if (bake_refused(ctx, "rt_scene_bake_buffer", points != nullptr, n, desc, out != nullptr) != RT_OK) return RT_ERROR;
-    const struct { rt_buffer* b; size_t record; const char* what; } bufs[2] = {{points, bake::point_bytes(*desc), "points"}, {out, sizeof(rt_bake_result), "out"}};
-    for (const auto& b : bufs)
-    {
-        if (b.b->ctx != ctx) return fail(ctx, std::string("rt_scene_bake_buffer: the ") + b.what + " buffer belongs to another context");
-        if (b.b->bytes < (size_t)n * b.record) return fail(ctx, std::string("rt_scene_bake_buffer: the ") + b.what + " buffer is smaller than n records");
-    }
+    if (buffers_refused(ctx, "rt_scene_bake_buffer", {{points, bake::point_bytes(*desc), "points"}, {out, sizeof(rt_bake_result), "out"}}, n) != RT_OK) return RT_ERROR;
     (void)hipSetDevice(ctx->device);
     return bake_launch(ctx, "rt_scene_bake_buffer", points->ptr, n, 0u, *desc, (rt_bake_result*)out->ptr);
 }

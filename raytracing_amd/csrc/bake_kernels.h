@@ -9,15 +9,16 @@
 // own -- so a lane whose ray has ended starts its next one at once (the lane refill k_query_trace cannot have: a query's lanes share nothing that says which
 // ray is next), and no result depends on which lane ends when.  The wave moves on to its next group when every lane has run dry.
 //
-// The walk is k_query_trace<true>'s, restated with t_min = 0 and t_max = radius (query_kernels.h explains it and argues its exactness; the step code is restated
-// rather than shared so that the query kernels' instructions stay what they were): the 4-wide shadow records with w4_test_slots in stored order, the exact
-// child-pair records for RT_SIGN_SLOW rays, origins beyond 2^29 and scenes without a usable 4-wide tree; the same stack -- RT_QUERY_STACK_LDS entries per lane
-// in LDS, the rest in the lane's slice of a spill area sized by the grid, RT_W4_STACK_MAX in all, an overrun raises *status and stores nothing.
+// The walk is k_query_trace<true>'s with t_min = 0 and t_max = radius: walk_kernels.h's ray_setup, ray_step<true> and Stack, which explains it and argues its
+// exactness -- the 4-wide shadow records with w4_test_slots in stored order, the exact child-pair records for RT_SIGN_SLOW rays, origins beyond 2^29 and scenes
+// without a usable 4-wide tree; RT_QUERY_STACK_LDS stack entries per lane in LDS, the rest in the lane's slice of a spill area sized by the grid,
+// RT_W4_STACK_MAX in all, an overrun raises *status and stores nothing.  An any-hit walk ends where a triangle is accepted, so the step's lowered t_max and its
+// barycentrics are dropped: the verdict is all a bake keeps.
 //
 // Reduction.  The count: every lane counts its own unoccluded rays (at most 64); per bit of that count one ballot, masked to the point's lanes and popcounted.
 // The bent normal: bake.h's halving tree over the L slot sums with __shfl_down inside the point's L lanes (lanes l >= s read values that no later step uses).
 #pragma once
-#include "query_kernels.h"
+#include "walk_kernels.h"
 #include "bake.h"
 
 namespace bake
@@ -26,20 +27,15 @@ __global__ __launch_bounds__(64) void k_bake(DScene sc, const float4* __restrict
     uint32_t samples, uint32_t seed, float bias, float radius, float4* __restrict__ out, uint2* __restrict__ spill, uint32_t use_wide,
     uint32_t* __restrict__ status)
 {
-    __shared__ uint2 stack[RT_QUERY_STACK_LDS][64];
+    __shared__ walk::StackLds lds;
+    walk::Stack stack(lds, spill);
     const uint32_t lane = threadIdx.x;
-    uint2* const my_spill = spill + (size_t)(blockIdx.x * 64u + lane) * RT_QUERY_SPILL_PER_LANE;
-    const char* const wide_base = reinterpret_cast<const char*>(sc.wnodes_sh);
-    const char* const pair_base = reinterpret_cast<const char*>(sc.nodes);
-    const char* const tri_base = reinterpret_cast<const char*>(sc.tris_rt);
-    const float INF = __builtin_inff();
     const uint32_t L = samples < 64u ? samples : 64u;            // lanes (= reduction slots) per point
     const uint32_t per_wave = 64u / L;
     const uint32_t sub = lane / L, slot = lane % L;
     const unsigned long long seg_mask = (L == 64u ? ~0ull : ((1ull << L) - 1ull)) << (sub * L);
     const uint32_t n_groups = n / per_wave + (n % per_wave != 0u ? 1u : 0u);
     const uint32_t stride = from_surfaces ? 4u : 2u;             // float4 per point record
-    bool overflow = false;
 
     for (uint32_t group = blockIdx.x; group < n_groups; group += gridDim.x)
     {
@@ -47,7 +43,6 @@ __global__ __launch_bounds__(64) void k_bake(DScene sc, const float4* __restrict
         BakeFrame f;
         f.walked = false;
         float r1 = 0.0f, r2 = 0.0f;
-        bool far_origin = false;
         if (p < n)
         {
             const float4* rec = points + (size_t)p * stride;
@@ -62,38 +57,32 @@ __global__ __launch_bounds__(64) void k_bake(DScene sc, const float4* __restrict
             }
             f = bake_frame(pos, nrm, record_ok, bias);
             bake_rotations(first_index + (uint32_t)p, seed, &r1, &r2);
-            far_origin = !(hw_max3(__builtin_fabsf(f.origin[0]), __builtin_fabsf(f.origin[1]), __builtin_fabsf(f.origin[2])) < 0x1p29f);
             // an origin that the bias made non-finite: its rays are not walked by a query either (ray_walkable) -- every ray a miss
         }
         const f3 org = F3(f.origin[0], f.origin[1], f.origin[2]);
         const bool origin_ok = __builtin_isfinite(org.x) && __builtin_isfinite(org.y) && __builtin_isfinite(org.z);
 
-        uint32_t ref = RT_IDLE_REF, k = slot, cnt = 0u, sign_bits = 0u, octant4 = 0u;
-        f3 dir = F3s(0.0f), inv = F3s(0.0f), sum = F3s(0.0f);
-        bool pairs = false, hit = false;
-        int sp = 0;
+        uint32_t ref = RT_IDLE_REF, k = slot, cnt = 0u;
+        walk::Ray ray = walk::ray_idle();
+        f3 sum = F3s(0.0f);
+        bool hit = false;
 
         // ray k of this lane's point: its direction and where its walk starts
         auto start = [&]()
         {
             float d[3];
             bake_direction(f, r1, r2, k, samples, d);
-            dir = F3(d[0], d[1], d[2]);
-            const float4 q = ray_inverse(dir);                                // trace_bvh.cl:125-129
-            inv = F3(q.x, q.y, q.z);
-            sign_bits = __float_as_uint(q.w) & 0xFFu;
-            octant4 = 4u * (sign_bits & 7u);
-            pairs = use_wide == 0u || (sign_bits & RT_SIGN_SLOW) != 0u || far_origin;
+            ray = walk::ray_setup(org, F3(d[0], d[1], d[2]), use_wide);
             hit = false;
-            sp = 0;
-            const bool walkable = origin_ok && __builtin_isfinite(dir.x) && __builtin_isfinite(dir.y) && __builtin_isfinite(dir.z) &&
-                                  !(dir.x == 0.0f && dir.y == 0.0f && dir.z == 0.0f);
-            ref = walkable ? (pairs ? sc.entry_ref : sc.w_sh_entry_ref) : RT_IDLE_REF;
+            stack.sp = 0;
+            const bool walkable = origin_ok && __builtin_isfinite(d[0]) && __builtin_isfinite(d[1]) && __builtin_isfinite(d[2]) &&
+                                  !(d[0] == 0.0f && d[1] == 0.0f && d[2] == 0.0f);
+            ref = walkable ? walk::ray_entry<true>(sc, ray) : RT_IDLE_REF;
         };
         // a ray has ended: its verdict joins the lane's sum, and the lane's next ray starts
         auto finish = [&]()
         {
-            if (!hit) { sum = sum + dir; ++cnt; }
+            if (!hit) { sum = sum + ray.dir; ++cnt; }
             k += L;
         };
         if (f.walked)
@@ -103,92 +92,13 @@ __global__ __launch_bounds__(64) void k_bake(DScene sc, const float4* __restrict
         }
         else k = samples;
 
-        auto push = [&](uint32_t r, float entry)
-        {
-            const uint2 e = make_uint2(r, __float_as_uint(entry));
-            if (sp < RT_QUERY_STACK_LDS) stack[sp][lane] = e;
-            else if (sp < RT_W4_STACK_MAX) my_spill[sp - RT_QUERY_STACK_LDS] = e;
-            else { overflow = true; return; }
-            ++sp;
-        };
-        auto pop = [&]()
-        {
-            ref = RT_IDLE_REF;
-            while (sp > 0)
-            {
-                --sp;
-                const uint2 e = sp < RT_QUERY_STACK_LDS ? stack[sp][lane] : spill_load64(my_spill + (sp - RT_QUERY_STACK_LDS));
-                if (radius >= __uint_as_float(e.y)) { ref = e.x; break; }
-            }
-        };
-        auto tested = [](uint32_t r) { return (int)r < -1 ? r | RT_LEAF_CONT_BIT : r; };
-
         while (__ballot(ref != RT_IDLE_REF) != 0ull)
         {
             if (ref != RT_IDLE_REF)
             {
-                const bool at_leaf = (int)ref < -1;
-                const uint32_t prim = ref & ~(RT_LEAF_BIT | RT_LEAF_CONT_BIT);
-                const float4* rp = reinterpret_cast<const float4*>(at_leaf ? tri_base + ((size_t)prim << 6) : (pairs ? pair_base : wide_base) + ((size_t)ref << 6));
-                const float4 q0 = rp[0], q1 = rp[1], q2 = rp[2], q3 = rp[3];
-                if (at_leaf)
-                {
-                    bool inside = true;
-                    if (!(ref & RT_LEAF_CONT_BIT))
-                    {
-                        float entry;
-                        inside = box_test_fast(q1.w, q2.w, q3.x, q3.y, q3.z, q3.w, org, inv, 0.0f, radius, entry);
-                    }
-                    if (!inside) pop();
-                    else
-                    {
-                        const bool last = q0.w != 0.0f;
-                        float t = 0.0f, hu = 0.0f, hv = 0.0f;
-                        const bool accepted = ray_triangle(org, dir, F3(q0.x, q0.y, q0.z), F3(q1.x, q1.y, q1.z), F3(q2.x, q2.y, q2.z), 0.0f, radius, hu, hv, t);
-                        if (accepted) { hit = true; ref = RT_IDLE_REF; }         // goto endtrace, trace_bvh.cl:164-167
-                        else if (last) pop();
-                        else ref = (RT_LEAF_BIT | RT_LEAF_CONT_BIT) | (prim + 1u);
-                    }
-                }
-                else if (pairs)
-                {
-                    const uint32_t c0 = __float_as_uint(q3.x), c1 = __float_as_uint(q3.y), axis = __float_as_uint(q3.z);
-                    float a0, a1;
-                    bool h0, h1;
-                    if (sign_bits & RT_SIGN_SLOW)
-                    {
-                        h0 = box_test(RT_NODE_C0(q0, q1, q2), org, inv, 0.0f, radius, a0);
-                        h1 = box_test(RT_NODE_C1(q0, q1, q2), org, inv, 0.0f, radius, a1);
-                    }
-                    else
-                    {
-                        h0 = box_test_fast(RT_NODE_C0(q0, q1, q2), org, inv, 0.0f, radius, a0);
-                        h1 = box_test_fast(RT_NODE_C1(q0, q1, q2), org, inv, 0.0f, radius, a1);
-                    }
-                    h1 = h1 && c1 != RT_EMPTY_REF;
-                    const bool swap = ((sign_bits >> axis) & 1u) != 0u;
-                    const uint32_t near_ref = swap ? c1 : c0, far_ref = swap ? c0 : c1;
-                    const bool near_hit = swap ? h1 : h0, far_hit = swap ? h0 : h1;
-                    if (near_hit && far_hit) push(tested(far_ref), swap ? a0 : a1);
-                    if (near_hit) ref = tested(near_ref);
-                    else if (far_hit) ref = tested(far_ref);
-                    else pop();
-                }
-                else
-                {
-                    uint32_t r[4];
-                    float e[4];
-                    w4_test_slots<true>(q0, q1, q2, q3, org, inv, sign_bits, octant4, 0.0f, radius, r, e);
-                    const bool v0 = e[0] < INF, v1 = e[1] < INF, v2 = e[2] < INF, v3 = e[3] < INF;
-                    if (v3 && (v0 || v1 || v2)) push(r[3], e[3]);
-                    if (v2 && (v0 || v1)) push(r[2], e[2]);
-                    if (v1 && v0) push(r[1], e[1]);
-                    if (v0) ref = r[0];
-                    else if (v1) ref = r[1];
-                    else if (v2) ref = r[2];
-                    else if (v3) ref = r[3];
-                    else pop();
-                }
+                float t_max = radius, hit_u = 0.0f, hit_v = 0.0f;             // the step's own copies: only its verdict is kept
+                uint32_t hit_prim = RT_INVALID_ID;
+                if (walk::ray_step<true>(sc, ray, 0.0f, t_max, ref, stack, hit_u, hit_v, hit_prim)) hit = true;
                 if (ref == RT_IDLE_REF)                                       // this lane's ray ended in this pass: the refill
                 {
                     finish();
@@ -216,7 +126,7 @@ __global__ __launch_bounds__(64) void k_bake(DScene sc, const float4* __restrict
             out[p] = f.walked ? make_float4(bent[0], bent[1], bent[2], __uint_as_float(unoccluded)) : make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(RT_INVALID_ID));
         }
     }
-    if (overflow) *status = 1u;                                  // pinned host memory, as k_query_trace's
+    stack.report(status);
 }
 
 // rays[p * samples + k] = ray k of point p as k_bake walks it; a skipped point's rays are all zeros (a zero direction: a ray no query walks)

@@ -16,26 +16,12 @@ namespace nearest
 static_assert(sizeof(rt_point) == sizeof(float4) && sizeof(rt_nearest) == 2 * sizeof(float4) && sizeof(rt_surface) == 4 * sizeof(float4), "records as 16-byte pieces");
 #define RT_NEAREST_WAVES_PER_CU 24u     // 6 KiB of LDS per block: 26 fit a CU's 160 KiB; the registers allow 24
 
-static bool clean() { return hipGetLastError() == hipSuccess; }
-
 bool launch(hipStream_t stream, query::Scratch& q, const DScene& sc, bool use_wide, uint32_t n_tris, const uint32_t* object_of_triangle, int compute_units,
     const rt_point* d_points, uint32_t n, rt_nearest* d_out, rt_surface* d_surfaces)
 {
     if (n == 0u) return true;
-    const uint32_t n_chunks = n / 64u + (n % 64u != 0u ? 1u : 0u);
-    const uint32_t resident = (((uint32_t)compute_units * RT_NEAREST_WAVES_PER_CU) + 7u) & ~7u;
-    const uint32_t blocks = n_chunks < resident ? n_chunks : resident;
-    if (!q.status)
-    {
-        if (hipHostMalloc((void**)&q.status, 4) != hipSuccess) { (void)hipGetLastError(); q.status = nullptr; return false; }
-        *q.status = 0u;
-    }
-    if (blocks > q.spill_blocks)
-    {
-        if (q.spill) { (void)hipStreamSynchronize(stream); (void)hipFree(q.spill); q.spill = nullptr; q.spill_blocks = 0; }
-        if (hipMalloc((void**)&q.spill, (size_t)blocks * 64u * RT_QUERY_SPILL_PER_LANE * sizeof(uint2)) != hipSuccess) { (void)hipGetLastError(); q.spill = nullptr; return false; }
-        q.spill_blocks = blocks;
-    }
+    const uint32_t blocks = query::prepare(stream, q, &q.status, compute_units, RT_NEAREST_WAVES_PER_CU, n / 64u + (n % 64u != 0u ? 1u : 0u));
+    if (blocks == 0u) return false;
     // the records k_nearest_surface reads: the caller's, or the first 32 bytes of each surface record
     float4* found = (float4*)d_out;
     uint32_t found_stride = 2u;
@@ -44,21 +30,14 @@ bool launch(hipStream_t stream, query::Scratch& q, const DScene& sc, bool use_wi
         hipLaunchKernelGGL(k_nearest<true>, dim3(blocks), dim3(64), 0, stream, sc, (const float4*)d_points, n, found, found_stride, q.spill, q.status);
     else
         hipLaunchKernelGGL(k_nearest<false>, dim3(blocks), dim3(64), 0, stream, sc, (const float4*)d_points, n, found, found_stride, q.spill, q.status);
-    if (!clean()) return false;
+    if (!query::clean()) return false;
     if (d_surfaces)
     {
         hipLaunchKernelGGL(k_nearest_surface, dim3(n / 256u + (n % 256u != 0u ? 1u : 0u)), dim3(256), 0, stream, sc.tris_sh, n_tris, object_of_triangle,
             (const float4*)d_points, (const float4*)found, found_stride, n, (float4*)d_surfaces);
-        if (!clean()) return false;
+        if (!query::clean()) return false;
     }
     return true;
-}
-
-static void corners(const rt_triangle& t, float (&p1)[3], float (&p2)[3], float (&p3)[3])
-{
-    p1[0] = t.v1.position.x; p1[1] = t.v1.position.y; p1[2] = t.v1.position.z;
-    p2[0] = t.v2.position.x; p2[1] = t.v2.position.y; p2[2] = t.v2.position.z;
-    p3[0] = t.v3.position.x; p3[1] = t.v3.position.y; p3[2] = t.v3.position.z;
 }
 
 static void brute_range(const rt_triangle* tris, uint32_t n_tris, const rt_point* points, uint32_t first, uint32_t end, rt_nearest* out)
@@ -73,12 +52,12 @@ static void brute_range(const rt_triangle* tris, uint32_t n_tris, const rt_point
         float p1[3], p2[3], p3[3];
         for (uint32_t t = 0; t < n_tris; ++t)
         {
-            corners(tris[t], p1, p2, p3);
+            walk::triangle_corners(tris[t], p1, p2, p3);
             const NpTriangle c = nearest_point_triangle(p, p1, p2, p3);
             if (nearest_accepts(c.d2, t, best, best_prim)) { best = c.d2; best_prim = t; }
         }
         if (best_prim == RT_INVALID_ID) continue;
-        corners(tris[best_prim], p1, p2, p3);
+        walk::triangle_corners(tris[best_prim], p1, p2, p3);
         out[i] = nearest_record(p, p1, p2, p3, best_prim);
     }
 }
@@ -96,23 +75,15 @@ void brute_host(const rt_triangle* tris, uint32_t n_tris, const rt_point* points
 
 bool brute_device(hipStream_t stream, const rt_triangle* tris, uint32_t n_tris, const rt_point* points, uint32_t n, rt_nearest* out)
 {
-    void *d_tris = nullptr, *d_points = nullptr, *d_out = nullptr;
-    auto get = [&](void*& p, const void* src, size_t bytes)
-    {
-        if (hipMalloc(&p, bytes ? bytes : 16) != hipSuccess) { (void)hipGetLastError(); p = nullptr; return false; }
-        return !src || bytes == 0 || hipMemcpyAsync(p, src, bytes, hipMemcpyHostToDevice, stream) == hipSuccess;
-    };
-    bool ok = get(d_tris, tris, (size_t)n_tris * sizeof(rt_triangle)) && get(d_points, points, (size_t)n * sizeof(rt_point)) && get(d_out, nullptr, (size_t)n * sizeof(rt_nearest));
+    query::DeviceTemps tmp(stream);
+    void* const d_tris = tmp.get(tris, (size_t)n_tris * sizeof(rt_triangle));
+    void* const d_points = tmp.get(points, (size_t)n * sizeof(rt_point));
+    void* const d_out = tmp.get(nullptr, (size_t)n * sizeof(rt_nearest));
+    const bool ok = d_tris && d_points && d_out;
     if (ok)
-    {
         hipLaunchKernelGGL(k_nearest_brute, dim3(n / 256u + (n % 256u != 0u ? 1u : 0u)), dim3(256), 0, stream, (const rt_triangle*)d_tris, n_tris, (const float4*)d_points, n,
             (float4*)d_out);
-        ok = clean() && hipMemcpyAsync(out, d_out, (size_t)n * sizeof(rt_nearest), hipMemcpyDeviceToHost, stream) == hipSuccess;
-    }
-    ok = hipStreamSynchronize(stream) == hipSuccess && ok;
-    (void)hipGetLastError();
-    for (void* p : {d_tris, d_points, d_out}) if (p) (void)hipFree(p);
-    return ok;
+    return tmp.finish(ok && query::clean(), out, d_out, (size_t)n * sizeof(rt_nearest));
 }
 
 const char* walk_host(const rt_bvh_node* nodes, uint32_t nn, const rt_triangle* tris, uint32_t n_tris, bool wide, const rt_point* points, uint32_t n,
@@ -170,7 +141,7 @@ const char* walk_host(const rt_bvh_node* nodes, uint32_t nn, const rt_triangle* 
             {
                 const uint32_t prim = ref & ~RT_LEAF_BIT;
                 if (prim >= n_tris) return "a leaf reference lies outside the triangle array";
-                corners(tris[prim], p1, p2, p3);
+                walk::triangle_corners(tris[prim], p1, p2, p3);
                 const NpTriangle t = nearest_point_triangle(p, p1, p2, p3);
                 ++count;
                 if (nearest_accepts(t.d2, prim, best, best_prim)) { best = t.d2; best_prim = prim; }
@@ -238,7 +209,7 @@ const char* walk_host(const rt_bvh_node* nodes, uint32_t nn, const rt_triangle* 
         }
         if (tested) tested[i] = count;
         if (best_prim == RT_INVALID_ID) continue;
-        corners(tris[best_prim], p1, p2, p3);
+        walk::triangle_corners(tris[best_prim], p1, p2, p3);
         out[i] = nearest_record(p, p1, p2, p3, best_prim);
     }
     return nullptr;

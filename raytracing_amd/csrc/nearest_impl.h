@@ -17,12 +17,8 @@ static int nearest_refused(rt_ctx* ctx, const char* who, bool points, uint32_t n
 static int nearest_launch(rt_ctx* ctx, const char* who, const rt_point* d_points, uint32_t n, rt_nearest* d_out, rt_surface* d_surfaces)
 {
     const Scene& s = ctx->scene;
-    if (!nearest::launch(ctx->stream, ctx->query, s.d, s.wide_ok, s.n_tris, s.pose ? s.pose->ids : nullptr, ctx->prop.multiProcessorCount, d_points, n, d_out, d_surfaces))
-    {
-        (void)hipGetLastError();
-        return fail(ctx, std::string(who) + ": the query could not be launched (the stack spill area could not be allocated, or a launch failed)");
-    }
-    return RT_OK;
+    return launch_result(ctx, who, nearest::launch(ctx->stream, ctx->query, s.d, s.wide_ok, s.n_tris, s.pose ? s.pose->ids : nullptr, ctx->prop.multiProcessorCount, d_points, n,
+        d_out, d_surfaces), QUERY_NOT_LAUNCHED);
 }
 
 int rt_scene_nearest(rt_ctx* ctx, const rt_point* points, uint32_t n, rt_nearest* out, rt_surface* surfaces)
@@ -32,36 +28,19 @@ int rt_scene_nearest(rt_ctx* ctx, const rt_point* points, uint32_t n, rt_nearest
     (void)hipSetDevice(ctx->device);
     query::Scratch& q = ctx->query;
     // the ray queries' staging arrays: [0] the points, [1] the records, [3] the surfaces
-    for (uint32_t first = 0; first < n; )
-    {
-        const uint32_t m = n - first < (uint32_t)query::CHUNK_RAYS ? n - first : (uint32_t)query::CHUNK_RAYS;
-        if (!query::reserve(ctx->stream, q, 0, (size_t)m * sizeof(rt_point)) || (out && !query::reserve(ctx->stream, q, 1, (size_t)m * sizeof(rt_nearest))) ||
-            (surfaces && !query::reserve(ctx->stream, q, 3, (size_t)m * sizeof(rt_surface))))
-            return fail(ctx, "rt_scene_nearest: out of device memory for the staging arrays");
-        HIPCHK(ctx, hipMemcpyAsync(q.stage[0], points + first, (size_t)m * sizeof(rt_point), hipMemcpyHostToDevice, ctx->stream));
-        if (nearest_launch(ctx, "rt_scene_nearest", (const rt_point*)q.stage[0], m, out ? (rt_nearest*)q.stage[1] : nullptr, surfaces ? (rt_surface*)q.stage[3] : nullptr) != RT_OK)
-            return RT_ERROR;
-        if (out) HIPCHK(ctx, hipMemcpyAsync(out + first, q.stage[1], (size_t)m * sizeof(rt_nearest), hipMemcpyDeviceToHost, ctx->stream));
-        if (surfaces) HIPCHK(ctx, hipMemcpyAsync(surfaces + first, q.stage[3], (size_t)m * sizeof(rt_surface), hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        if (query_check_status(ctx, "rt_scene_nearest") != RT_OK) return RT_ERROR;
-        first += m;
-    }
-    return RT_OK;
+    return staged_call(ctx, "rt_scene_nearest", q, {{(void*)points, sizeof(rt_point), 0, true}, {out, sizeof(rt_nearest), 1, false}, {surfaces, sizeof(rt_surface), 3, false}}, n,
+        (uint32_t)query::CHUNK_RAYS, [&](uint32_t, uint32_t m)
+        {
+            return nearest_launch(ctx, "rt_scene_nearest", (const rt_point*)q.stage[0], m, out ? (rt_nearest*)q.stage[1] : nullptr, surfaces ? (rt_surface*)q.stage[3] : nullptr);
+        });
 }
 
 int rt_scene_nearest_buffer(rt_ctx* ctx, rt_buffer* points, uint32_t n, rt_buffer* out, rt_buffer* surfaces)
 {
     if (ctx && n == 0u) return RT_OK;
     if (nearest_refused(ctx, "rt_scene_nearest_buffer", points != nullptr, n, out != nullptr, surfaces != nullptr) != RT_OK) return RT_ERROR;
-    const struct { rt_buffer* b; size_t record; const char* what; } bufs[3] = {{points, sizeof(rt_point), "points"}, {out, sizeof(rt_nearest), "out"},
-        {surfaces, sizeof(rt_surface), "surfaces"}};
-    for (const auto& b : bufs)
-    {
-        if (!b.b) continue;
-        if (b.b->ctx != ctx) return fail(ctx, std::string("rt_scene_nearest_buffer: the ") + b.what + " buffer belongs to another context");
-        if (b.b->bytes < (size_t)n * b.record) return fail(ctx, std::string("rt_scene_nearest_buffer: the ") + b.what + " buffer is smaller than n records");
-    }
+    if (buffers_refused(ctx, "rt_scene_nearest_buffer", {{points, sizeof(rt_point), "points"}, {out, sizeof(rt_nearest), "out"}, {surfaces, sizeof(rt_surface), "surfaces"}}, n) != RT_OK)
+        return RT_ERROR;
     (void)hipSetDevice(ctx->device);
     return nearest_launch(ctx, "rt_scene_nearest_buffer", (const rt_point*)points->ptr, n, out ? (rt_nearest*)out->ptr : nullptr, surfaces ? (rt_surface*)surfaces->ptr : nullptr);
 }

@@ -5,7 +5,7 @@
 //   k_nearest_brute    one lane per point over ALL triangles of an rt_triangle array (rt_debug_nearest's device form: the same nearest.h with no tree)
 //   k_nearest_surface  one lane per point: rt_surface (64 bytes) of the nearest point, by query.h's query_surface
 //
-// The walk.  k_query_trace's fused one-loop shape, restated (query_kernels.h is not touched, so its instructions stay what they were): a lane's point is at a
+// The walk.  k_query_trace's fused one-loop shape on walk_kernels.h's Stack (the box step below is this kernel's own): a lane's point is at a
 // reference -- a 4-wide record (WIDE), a child-pair record (!WIDE), or a triangle of a leaf -- and every pass of the one loop fetches the lane's next 64 bytes
 // with the same four 16-byte loads and takes its step.  What differs from a ray's walk is the test and the order: a box is passed when !(nearest_box_d2 > best),
 // the nearest passing box is visited next, and the others wait on the stack with their nearest_box_d2 as the entry value, farthest deepest; a pop re-tests
@@ -23,13 +23,12 @@
 // WIDE is the launch's, not the lane's: nearest::launch takes the 4-wide records when Scene::wide_ok holds (query::launch's rule), the child-pair records
 // otherwise (RT_CTX_OPT_WIDE_BVH = 0, a refit that disqualified the wide tree).
 //
-// Stack: (ref, nearest_box_d2) entries, RT_QUERY_STACK_LDS per lane in LDS in k_query_trace's lane-major 8-byte layout, the rest in the lane's slice of the
-// ray queries' spill area, RT_W4_STACK_MAX in all (at most three pending slots per wide level, one pending child per pair level).  A push beyond it is not
-// written; it raises the ray queries' status word.
+// Stack: walk::Stack with (ref, nearest_box_d2) entries, in the ray queries' spill area (at most three pending slots per wide level, one pending child per
+// pair level).  A push beyond RT_W4_STACK_MAX is not written; it raises the ray queries' status word.
 //
 // Grid: k_query_trace's persistent strided chunks of 64 consecutive points.
 #pragma once
-#include "query_kernels.h"
+#include "walk_kernels.h"
 #include "nearest.h"
 
 namespace nearest
@@ -38,15 +37,14 @@ template <bool WIDE>
 __global__ __launch_bounds__(64) void k_nearest(DScene sc, const float4* __restrict__ points, uint32_t n, float4* __restrict__ out, uint32_t out_stride /* in float4 */,
     uint2* __restrict__ spill, uint32_t* __restrict__ status)
 {
-    __shared__ uint2 stack[RT_QUERY_STACK_LDS][64];
+    __shared__ walk::StackLds lds;
+    walk::Stack stack(lds, spill);
     const uint32_t lane = threadIdx.x;
-    uint2* const my_spill = spill + (size_t)(blockIdx.x * 64u + lane) * RT_QUERY_SPILL_PER_LANE;
     const char* const node_base = reinterpret_cast<const char*>(WIDE ? sc.wnodes : sc.nodes);
     const char* const tri_base = reinterpret_cast<const char*>(sc.tris_sh);
     const float* const flag_base = reinterpret_cast<const float*>(sc.tris_rt);
     const float INF = __builtin_inff();
     const uint32_t n_chunks = (n >> 6) + ((n & 63u) != 0u ? 1u : 0u);
-    bool overflow = false;
 
     for (uint32_t chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x)
     {
@@ -54,7 +52,7 @@ __global__ __launch_bounds__(64) void k_nearest(DScene sc, const float4* __restr
         uint32_t ref = RT_IDLE_REF, best_prim = RT_INVALID_ID;
         float p[3] = {0.0f, 0.0f, 0.0f};
         float best = 0.0f;
-        int sp = 0;
+        stack.sp = 0;
         if (i < n)
         {
             const float4 q = q_load(points + i);
@@ -66,24 +64,7 @@ __global__ __launch_bounds__(64) void k_nearest(DScene sc, const float4* __restr
             }
         }
 
-        auto push = [&](uint32_t r, float entry)
-        {
-            const uint2 e = make_uint2(r, __float_as_uint(entry));
-            if (sp < RT_QUERY_STACK_LDS) stack[sp][lane] = e;
-            else if (sp < RT_W4_STACK_MAX) my_spill[sp - RT_QUERY_STACK_LDS] = e;
-            else { overflow = true; return; }
-            ++sp;
-        };
-        auto pop = [&]()
-        {
-            ref = RT_IDLE_REF;
-            while (sp > 0)
-            {
-                --sp;
-                const uint2 e = sp < RT_QUERY_STACK_LDS ? stack[sp][lane] : spill_load64(my_spill + (sp - RT_QUERY_STACK_LDS));
-                if (!(__uint_as_float(e.y) > best)) { ref = e.x; break; }
-            }
-        };
+        auto pop = [&]() { ref = stack.pop([&](float entry) { return !(entry > best); }); };
 
         while (__ballot(ref != RT_IDLE_REF) != 0ull)
         {
@@ -158,7 +139,7 @@ __global__ __launch_bounds__(64) void k_nearest(DScene sc, const float4* __restr
                     for (int k = WIDE ? 3 : 1; k >= 0; --k)
                         if (r[k] != RT_EMPTY_REF)
                         {
-                            if (next != RT_IDLE_REF) push(next, next_e);
+                            if (next != RT_IDLE_REF) stack.push(next, next_e);
                             next = r[k]; next_e = e[k];
                         }
                     if (next != RT_IDLE_REF) ref = next;
@@ -177,12 +158,10 @@ __global__ __launch_bounds__(64) void k_nearest(DScene sc, const float4* __restr
                 const float p1[3] = {a.x, a.y, a.z}, p2[3] = {b.x, b.y, b.z}, p3[3] = {c.x, c.y, c.z};
                 o = nearest_record(p, p1, p2, p3, best_prim);
             }
-            float4* op = out + (size_t)i * out_stride;
-            q_store(op, make_float4(o.position[0], o.position[1], o.position[2], o.distance));
-            q_store(op + 1, make_float4(o.bc[0], o.bc[1], __uint_as_float(o.primitive_id), __uint_as_float(o.flags)));
+            walk::store_nearest(out + (size_t)i * out_stride, o);
         }
     }
-    if (overflow) *status = 1u;                                  // pinned host memory: the host reads it after it has waited for the stream
+    stack.report(status);
 }
 
 __global__ __launch_bounds__(256) void k_nearest_brute(const rt_triangle* __restrict__ tris, uint32_t n_tris, const float4* __restrict__ points, uint32_t n,
@@ -197,28 +176,24 @@ __global__ __launch_bounds__(256) void k_nearest_brute(const rt_triangle* __rest
     {
         float best = q.w * q.w;
         uint32_t best_prim = RT_INVALID_ID;
+        float p1[3], p2[3], p3[3];
         for (uint32_t t = 0; t < n_tris; ++t)
         {
-            const rt_triangle& tr = tris[t];
-            const float p1[3] = {tr.v1.position.x, tr.v1.position.y, tr.v1.position.z}, p2[3] = {tr.v2.position.x, tr.v2.position.y, tr.v2.position.z},
-                        p3[3] = {tr.v3.position.x, tr.v3.position.y, tr.v3.position.z};
+            walk::triangle_corners(tris[t], p1, p2, p3);
             const NpTriangle c = nearest_point_triangle(p, p1, p2, p3);
             if (nearest_accepts(c.d2, t, best, best_prim)) { best = c.d2; best_prim = t; }
         }
         if (best_prim != RT_INVALID_ID)
         {
-            const rt_triangle& tr = tris[best_prim];
-            const float p1[3] = {tr.v1.position.x, tr.v1.position.y, tr.v1.position.z}, p2[3] = {tr.v2.position.x, tr.v2.position.y, tr.v2.position.z},
-                        p3[3] = {tr.v3.position.x, tr.v3.position.y, tr.v3.position.z};
+            walk::triangle_corners(tris[best_prim], p1, p2, p3);
             o = nearest_record(p, p1, p2, p3, best_prim);
         }
     }
-    out[2 * (size_t)i] = make_float4(o.position[0], o.position[1], o.position[2], o.distance);
-    out[2 * (size_t)i + 1] = make_float4(o.bc[0], o.bc[1], __uint_as_float(o.primitive_id), __uint_as_float(o.flags));
+    walk::store_nearest(out + 2 * (size_t)i, o);
 }
 
 // found[i * found_stride .. + 1] = point i's rt_nearest; it may be the first 32 bytes of out[i] itself (a query that returns surfaces only keeps its records
-// there): lane i reads it before it writes.  `tris` = the scene's 128-byte shading records (k_query_surface<true>'s reading of them).
+// there): lane i reads it before it writes.  `tris` = the scene's 128-byte shading records (walk::read_shading_triangle).
 __global__ __launch_bounds__(256) void k_nearest_surface(const float4* __restrict__ tris, uint32_t n_tris, const uint32_t* __restrict__ object_of_triangle,
     const float4* __restrict__ points, const float4* found, uint32_t found_stride, uint32_t n, float4* out)
 {
@@ -229,21 +204,11 @@ __global__ __launch_bounds__(256) void k_nearest_surface(const float4* __restric
     rt_surface s = qs_miss();
     if (prim < n_tris)                                           // RT_INVALID_ID (nothing found) is above every count
     {
-        QsTriangle t;
-        const float4* tp = tris + (size_t)prim * 8;
-        const float4 q0 = tp[0], q1 = tp[1], q2 = tp[2], q3 = tp[3], q4 = tp[4], q5 = tp[5], q6 = tp[6];
-        t.p1[0] = q0.x; t.p1[1] = q0.y; t.p1[2] = q0.z; t.p2[0] = q1.x; t.p2[1] = q1.y; t.p2[2] = q1.z; t.p3[0] = q2.x; t.p3[1] = q2.y; t.p3[2] = q2.z;
-        t.n1[0] = q3.x; t.n1[1] = q3.y; t.n1[2] = q3.z; t.n2[0] = q4.x; t.n2[1] = q4.y; t.n2[2] = q4.z; t.n3[0] = q5.x; t.n3[1] = q5.y; t.n3[2] = q5.z;
-        t.uv1[0] = q0.w; t.uv1[1] = q1.w; t.uv2[0] = q2.w; t.uv2[1] = q3.w; t.uv3[0] = q4.w; t.uv3[1] = q5.w;
-        t.mtl_index = __float_as_uint(q6.x);
+        const QsTriangle t = walk::read_shading_triangle(tris, prim);
         const float4 pt = points[i];
         const float d[3] = {f0.x - pt.x, f0.y - pt.y, f0.z - pt.z};          // q - p: the direction from the point to the surface
         s = query_surface(t, d, f1.x, f1.y, f0.w, prim, object_of_triangle ? object_of_triangle[prim] : RT_INVALID_ID);
     }
-    float4* o = out + (size_t)i * 4;
-    o[0] = make_float4(s.position[0], s.position[1], s.position[2], __uint_as_float(s.primitive_id));
-    o[1] = make_float4(s.geometric_normal[0], s.geometric_normal[1], s.geometric_normal[2], __uint_as_float(s.mtl_index));
-    o[2] = make_float4(s.shading_normal[0], s.shading_normal[1], s.shading_normal[2], __uint_as_float(s.object));
-    o[3] = make_float4(s.texcoord[0], s.texcoord[1], s.t, __uint_as_float(s.flags));
+    walk::store_surface(out + (size_t)i * 4, s);
 }
 } // namespace nearest

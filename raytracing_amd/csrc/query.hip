@@ -13,7 +13,7 @@ namespace query
 static_assert(sizeof(rt_ray) == 2 * sizeof(float4) && sizeof(rt_hit) == sizeof(float4) && sizeof(rt_surface) == 4 * sizeof(float4), "records as 16-byte pieces");
 #define RT_QUERY_WAVES_PER_CU 24u       // 6 KiB of LDS per block: 26 fit a CU's 160 KiB; the registers allow 24
 
-static bool clean() { return hipGetLastError() == hipSuccess; }
+bool clean() { return hipGetLastError() == hipSuccess; }
 
 size_t Scratch::spill_bytes() const { return (size_t)spill_blocks * 64u * RT_QUERY_SPILL_PER_LANE * sizeof(uint2); }
 size_t Scratch::bytes() const
@@ -45,24 +45,51 @@ bool reserve(hipStream_t stream, Scratch& s, int k, size_t bytes)
     return true;
 }
 
-bool launch(hipStream_t stream, Scratch& s, const DScene& sc, bool use_wide, uint32_t n_tris, const uint32_t* object_of_triangle, int compute_units,
-    const rt_ray* d_rays, uint32_t n, uint32_t mode, rt_hit* d_hits, uint32_t* d_occluded, rt_surface* d_surfaces)
+uint32_t prepare(hipStream_t stream, Scratch& s, uint32_t** status, int compute_units, uint32_t waves_per_cu, uint32_t n_groups)
 {
-    if (n == 0u) return true;
-    const uint32_t n_chunks = n / 64u + (n % 64u != 0u ? 1u : 0u);
-    const uint32_t resident = (((uint32_t)compute_units * RT_QUERY_WAVES_PER_CU) + 7u) & ~7u;
-    const uint32_t blocks = n_chunks < resident ? n_chunks : resident;
-    if (!s.status)
+    const uint32_t resident = (((uint32_t)compute_units * waves_per_cu) + 7u) & ~7u;
+    const uint32_t blocks = n_groups < resident ? n_groups : resident;
+    if (!*status)
     {
-        if (hipHostMalloc((void**)&s.status, 4) != hipSuccess) { (void)hipGetLastError(); s.status = nullptr; return false; }
-        *s.status = 0u;
+        if (hipHostMalloc((void**)status, 4) != hipSuccess) { (void)hipGetLastError(); *status = nullptr; return 0u; }
+        **status = 0u;
     }
     if (blocks > s.spill_blocks)
     {
         if (s.spill) { (void)hipStreamSynchronize(stream); (void)hipFree(s.spill); s.spill = nullptr; s.spill_blocks = 0; }
-        if (hipMalloc((void**)&s.spill, (size_t)blocks * 64u * RT_QUERY_SPILL_PER_LANE * sizeof(uint2)) != hipSuccess) { (void)hipGetLastError(); s.spill = nullptr; return false; }
+        if (hipMalloc((void**)&s.spill, (size_t)blocks * 64u * RT_QUERY_SPILL_PER_LANE * sizeof(uint2)) != hipSuccess) { (void)hipGetLastError(); s.spill = nullptr; return 0u; }
         s.spill_blocks = blocks;
     }
+    return blocks;
+}
+
+DeviceTemps::~DeviceTemps()
+{
+    for (int k = 0; k < count; ++k) (void)hipFree(held[k]);
+}
+
+void* DeviceTemps::get(const void* src, size_t bytes)
+{
+    void* p = nullptr;
+    if (count == 8 || hipMalloc(&p, bytes ? bytes : 16) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+    held[count++] = p;
+    return !src || bytes == 0 || hipMemcpyAsync(p, src, bytes, hipMemcpyHostToDevice, stream) == hipSuccess ? p : nullptr;
+}
+
+bool DeviceTemps::finish(bool launched, void* out, const void* d_out, size_t bytes)
+{
+    bool ok = launched && hipMemcpyAsync(out, d_out, bytes, hipMemcpyDeviceToHost, stream) == hipSuccess;
+    ok = hipStreamSynchronize(stream) == hipSuccess && ok;
+    (void)hipGetLastError();
+    return ok;
+}
+
+bool launch(hipStream_t stream, Scratch& s, const DScene& sc, bool use_wide, uint32_t n_tris, const uint32_t* object_of_triangle, int compute_units,
+    const rt_ray* d_rays, uint32_t n, uint32_t mode, rt_hit* d_hits, uint32_t* d_occluded, rt_surface* d_surfaces)
+{
+    if (n == 0u) return true;
+    const uint32_t blocks = prepare(stream, s, &s.status, compute_units, RT_QUERY_WAVES_PER_CU, n / 64u + (n % 64u != 0u ? 1u : 0u));
+    if (blocks == 0u) return false;
     // the hits k_query_surface reads: the caller's, or the first 16 bytes of each surface record
     float4* hits = (float4*)d_hits;
     uint32_t hit_stride = 1u;
@@ -107,23 +134,16 @@ void debug_surface_host(const rt_triangle* tris, uint32_t n_tris, const uint32_t
 bool debug_surface_device(hipStream_t stream, const rt_triangle* tris, uint32_t n_tris, const uint32_t* object_of_triangle, const rt_ray* rays, const rt_hit* hits,
     uint32_t n, rt_surface* out)
 {
-    void *d_tris = nullptr, *d_ids = nullptr, *d_rays = nullptr, *d_hits = nullptr, *d_out = nullptr;
-    auto get = [&](void*& p, const void* src, size_t bytes)
-    {
-        if (hipMalloc(&p, bytes ? bytes : 16) != hipSuccess) { (void)hipGetLastError(); p = nullptr; return false; }
-        return !src || bytes == 0 || hipMemcpyAsync(p, src, bytes, hipMemcpyHostToDevice, stream) == hipSuccess;
-    };
-    bool ok = get(d_tris, tris, (size_t)n_tris * sizeof(rt_triangle)) && (!object_of_triangle || get(d_ids, object_of_triangle, (size_t)n_tris * 4)) &&
-              get(d_rays, rays, (size_t)n * sizeof(rt_ray)) && get(d_hits, hits, (size_t)n * sizeof(rt_hit)) && get(d_out, nullptr, (size_t)n * sizeof(rt_surface));
+    DeviceTemps tmp(stream);
+    void* const d_tris = tmp.get(tris, (size_t)n_tris * sizeof(rt_triangle));
+    void* const d_ids = object_of_triangle ? tmp.get(object_of_triangle, (size_t)n_tris * 4) : nullptr;
+    void* const d_rays = tmp.get(rays, (size_t)n * sizeof(rt_ray));
+    void* const d_hits = tmp.get(hits, (size_t)n * sizeof(rt_hit));
+    void* const d_out = tmp.get(nullptr, (size_t)n * sizeof(rt_surface));
+    const bool ok = d_tris && (d_ids || !object_of_triangle) && d_rays && d_hits && d_out;
     if (ok)
-    {
         hipLaunchKernelGGL(k_query_surface<false>, dim3(n / 256u + (n % 256u != 0u ? 1u : 0u)), dim3(256), 0, stream, (const float4*)d_tris, n_tris, (const uint32_t*)d_ids,
             (const float4*)d_rays, (const float4*)d_hits, 1u, n, (float4*)d_out);
-        ok = clean() && hipMemcpyAsync(out, d_out, (size_t)n * sizeof(rt_surface), hipMemcpyDeviceToHost, stream) == hipSuccess;
-    }
-    ok = hipStreamSynchronize(stream) == hipSuccess && ok;
-    (void)hipGetLastError();
-    for (void* p : {d_tris, d_ids, d_rays, d_hits, d_out}) if (p) (void)hipFree(p);
-    return ok;
+    return tmp.finish(ok && clean(), out, d_out, (size_t)n * sizeof(rt_surface));
 }
 } // namespace query

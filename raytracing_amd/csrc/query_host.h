@@ -14,12 +14,13 @@ namespace query
 {
 enum { CHUNK_RAYS = 4u << 20 };          // rt_scene_trace stages at most this many rays at a time
 
-// what a context keeps for its queries: the walk's stack spill area (sized by the grid), a status word, and rt_scene_trace's staging arrays (grown on demand)
+// what a context keeps for its queries: the walk's stack spill area (sized by the grid), a status word, and the host forms' staging arrays (grown on demand).
+// A context has two: one for its ray and nearest-point queries, which owns the status word, and one for its bakes (stages 0 and 1, no status word of its own).
 struct Scratch
 {
     uint2* spill = nullptr; uint32_t spill_blocks = 0;
-    uint32_t* status = nullptr;                         // pinned host memory the kernel can write; bit 0: a traversal stack ran over its bound (query_kernels.h)
-    void* stage[4] = {nullptr, nullptr, nullptr, nullptr};   // rays, hits, occluded, surfaces
+    uint32_t* status = nullptr;                         // pinned host memory the kernel can write; bit 0: a traversal stack ran over its bound (walk_kernels.h)
+    void* stage[4] = {nullptr, nullptr, nullptr, nullptr};   // rays | points, hits | records | results, occluded, surfaces
     size_t stage_bytes[4] = {0, 0, 0, 0};
     size_t bytes() const;          // the device memory above
     size_t spill_bytes() const;
@@ -27,6 +28,26 @@ struct Scratch
 void release(Scratch& s);
 // stage[k] holds at least `bytes` (the stream is waited for before a smaller array is freed); false: out of device memory
 bool reserve(hipStream_t stream, Scratch& s, int k, size_t bytes);
+
+// Before a walk's launch: *status is allocated if it is not yet, s's spill area is grown to the grid (the stream is waited for before a smaller one is freed).
+// The grid: n_groups blocks of one wave, at most what waves_per_cu keeps resident (rounded up to 8).  0: out of memory.
+uint32_t prepare(hipStream_t stream, Scratch& s, uint32_t** status, int compute_units, uint32_t waves_per_cu, uint32_t n_groups);
+// no launch or runtime error is pending (and none is left pending)
+bool clean();
+
+// The debug paths' temporary device copies: get() allocates one and uploads `src` into it when there is one; all are freed when the holder goes.
+struct DeviceTemps
+{
+    hipStream_t stream;
+    void* held[8];
+    int count = 0;
+    explicit DeviceTemps(hipStream_t s) : stream(s) {}
+    DeviceTemps(const DeviceTemps&) = delete; DeviceTemps& operator=(const DeviceTemps&) = delete;
+    ~DeviceTemps();
+    void* get(const void* src, size_t bytes);       // nullptr: the allocation or the upload failed
+    // after the launch: d_out's `bytes` to `out`, the stream waited for.  launched: what clean() said after the launch
+    bool finish(bool launched, void* out, const void* d_out, size_t bytes);
+};
 
 // The query's launches on `stream`, nothing waited for: k_query_trace over d_rays[n], then k_query_surface when d_surfaces is given.  mode: RT_QUERY_*; use_wide:
 // the scene's 4-wide trees are usable; object_of_triangle: the device table of rt_scene_set_objects or nullptr.  In closest mode d_hits may be nullptr when

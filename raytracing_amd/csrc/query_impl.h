@@ -16,16 +16,58 @@ static int query_refused(rt_ctx* ctx, const char* who, bool rays, uint32_t n, ui
     return RT_OK;
 }
 
+// One array of a host form's call: `host` is the caller's (NULL: not asked for), staged through stage[stage] of the scratch, up before the launch or down after it.
+struct StagedArray { void* host; size_t record; int stage; bool up; };
+
+// A host form's loop, shared by rt_scene_trace, rt_scene_bake and rt_scene_nearest: at most `chunk` records at a time are staged -- reserve, copy up,
+// launch(first, m) on the staged arrays, copy down, wait for the stream, read the walk's status word.
+static int staged_call(rt_ctx* ctx, const char* who, query::Scratch& s, std::initializer_list<StagedArray> arrays, uint32_t n, uint32_t chunk,
+    const std::function<int(uint32_t first, uint32_t m)>& launch)
+{
+    for (uint32_t first = 0; first < n; )
+    {
+        const uint32_t m = n - first < chunk ? n - first : chunk;
+        for (const StagedArray& a : arrays)
+            if (a.host && !query::reserve(ctx->stream, s, a.stage, (size_t)m * a.record)) return fail(ctx, std::string(who) + ": out of device memory for the staging arrays");
+        for (const StagedArray& a : arrays)
+            if (a.host && a.up) HIPCHK(ctx, hipMemcpyAsync(s.stage[a.stage], (const char*)a.host + (size_t)first * a.record, (size_t)m * a.record, hipMemcpyHostToDevice, ctx->stream));
+        if (launch(first, m) != RT_OK) return RT_ERROR;
+        for (const StagedArray& a : arrays)
+            if (a.host && !a.up) HIPCHK(ctx, hipMemcpyAsync((char*)a.host + (size_t)first * a.record, s.stage[a.stage], (size_t)m * a.record, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        if (query_check_status(ctx, who) != RT_OK) return RT_ERROR;
+        first += m;
+    }
+    return RT_OK;
+}
+
+// what a buffer form refuses of its buffers (NULL: not passed)
+struct BufferArg { rt_buffer* b; size_t record; const char* what; };
+static int buffers_refused(rt_ctx* ctx, const char* who, std::initializer_list<BufferArg> bufs, uint32_t n)
+{
+    for (const BufferArg& b : bufs)
+    {
+        if (!b.b) continue;
+        if (b.b->ctx != ctx) return fail(ctx, std::string(who) + ": the " + b.what + " buffer belongs to another context");
+        if (b.b->bytes < (size_t)n * b.record) return fail(ctx, std::string(who) + ": the " + b.what + " buffer is smaller than n records");
+    }
+    return RT_OK;
+}
+
+// a driver's launch() said `ok`; why_not: the message behind `who` when it did not
+static int launch_result(rt_ctx* ctx, const char* who, bool ok, const char* why_not)
+{
+    if (ok) return RT_OK;
+    (void)hipGetLastError();
+    return fail(ctx, std::string(who) + why_not);
+}
+static const char QUERY_NOT_LAUNCHED[] = ": the query could not be launched (the stack spill area could not be allocated, or a launch failed)";
+
 static int query_launch(rt_ctx* ctx, const char* who, const rt_ray* d_rays, uint32_t n, uint32_t mode, rt_hit* d_hits, uint32_t* d_occluded, rt_surface* d_surfaces)
 {
     const Scene& s = ctx->scene;
-    if (!query::launch(ctx->stream, ctx->query, s.d, s.wide_ok, s.n_tris, s.pose ? s.pose->ids : nullptr, ctx->prop.multiProcessorCount, d_rays, n, mode, d_hits,
-            d_occluded, d_surfaces))
-    {
-        (void)hipGetLastError();
-        return fail(ctx, std::string(who) + ": the query could not be launched (the stack spill area could not be allocated, or a launch failed)");
-    }
-    return RT_OK;
+    return launch_result(ctx, who, query::launch(ctx->stream, ctx->query, s.d, s.wide_ok, s.n_tris, s.pose ? s.pose->ids : nullptr, ctx->prop.multiProcessorCount, d_rays, n,
+        mode, d_hits, d_occluded, d_surfaces), QUERY_NOT_LAUNCHED);
 }
 
 int rt_scene_trace(rt_ctx* ctx, const rt_ray* rays, uint32_t n, uint32_t mode, rt_hit* hits, uint32_t* occluded, rt_surface* surfaces)
@@ -34,38 +76,21 @@ int rt_scene_trace(rt_ctx* ctx, const rt_ray* rays, uint32_t n, uint32_t mode, r
     if (query_refused(ctx, "rt_scene_trace", rays != nullptr, n, mode, hits != nullptr, occluded != nullptr, surfaces != nullptr) != RT_OK) return RT_ERROR;
     (void)hipSetDevice(ctx->device);
     query::Scratch& q = ctx->query;
-    for (uint32_t first = 0; first < n; )
-    {
-        const uint32_t m = n - first < (uint32_t)query::CHUNK_RAYS ? n - first : (uint32_t)query::CHUNK_RAYS;
-        if (!query::reserve(ctx->stream, q, 0, (size_t)m * sizeof(rt_ray)) || (hits && !query::reserve(ctx->stream, q, 1, (size_t)m * sizeof(rt_hit))) ||
-            (occluded && !query::reserve(ctx->stream, q, 2, (size_t)m * sizeof(uint32_t))) || (surfaces && !query::reserve(ctx->stream, q, 3, (size_t)m * sizeof(rt_surface))))
-            return fail(ctx, "rt_scene_trace: out of device memory for the staging arrays");
-        HIPCHK(ctx, hipMemcpyAsync(q.stage[0], rays + first, (size_t)m * sizeof(rt_ray), hipMemcpyHostToDevice, ctx->stream));
-        if (query_launch(ctx, "rt_scene_trace", (const rt_ray*)q.stage[0], m, mode, hits ? (rt_hit*)q.stage[1] : nullptr, occluded ? (uint32_t*)q.stage[2] : nullptr,
-                surfaces ? (rt_surface*)q.stage[3] : nullptr) != RT_OK)
-            return RT_ERROR;
-        if (hits) HIPCHK(ctx, hipMemcpyAsync(hits + first, q.stage[1], (size_t)m * sizeof(rt_hit), hipMemcpyDeviceToHost, ctx->stream));
-        if (occluded) HIPCHK(ctx, hipMemcpyAsync(occluded + first, q.stage[2], (size_t)m * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-        if (surfaces) HIPCHK(ctx, hipMemcpyAsync(surfaces + first, q.stage[3], (size_t)m * sizeof(rt_surface), hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        if (query_check_status(ctx, "rt_scene_trace") != RT_OK) return RT_ERROR;
-        first += m;
-    }
-    return RT_OK;
+    return staged_call(ctx, "rt_scene_trace", q, {{(void*)rays, sizeof(rt_ray), 0, true}, {hits, sizeof(rt_hit), 1, false}, {occluded, sizeof(uint32_t), 2, false},
+        {surfaces, sizeof(rt_surface), 3, false}}, n, (uint32_t)query::CHUNK_RAYS, [&](uint32_t, uint32_t m)
+        {
+            return query_launch(ctx, "rt_scene_trace", (const rt_ray*)q.stage[0], m, mode, hits ? (rt_hit*)q.stage[1] : nullptr, occluded ? (uint32_t*)q.stage[2] : nullptr,
+                surfaces ? (rt_surface*)q.stage[3] : nullptr);
+        });
 }
 
 int rt_scene_trace_buffer(rt_ctx* ctx, rt_buffer* rays, uint32_t n, uint32_t mode, rt_buffer* hits, rt_buffer* occluded, rt_buffer* surfaces)
 {
     if (ctx && n == 0u) return RT_OK;
     if (query_refused(ctx, "rt_scene_trace_buffer", rays != nullptr, n, mode, hits != nullptr, occluded != nullptr, surfaces != nullptr) != RT_OK) return RT_ERROR;
-    const struct { rt_buffer* b; size_t record; const char* what; } bufs[4] = {{rays, sizeof(rt_ray), "rays"}, {hits, sizeof(rt_hit), "hits"},
-        {occluded, sizeof(uint32_t), "occluded"}, {surfaces, sizeof(rt_surface), "surfaces"}};
-    for (const auto& b : bufs)
-    {
-        if (!b.b) continue;
-        if (b.b->ctx != ctx) return fail(ctx, std::string("rt_scene_trace_buffer: the ") + b.what + " buffer belongs to another context");
-        if (b.b->bytes < (size_t)n * b.record) return fail(ctx, std::string("rt_scene_trace_buffer: the ") + b.what + " buffer is smaller than n records");
-    }
+    if (buffers_refused(ctx, "rt_scene_trace_buffer", {{rays, sizeof(rt_ray), "rays"}, {hits, sizeof(rt_hit), "hits"}, {occluded, sizeof(uint32_t), "occluded"},
+            {surfaces, sizeof(rt_surface), "surfaces"}}, n) != RT_OK)
+        return RT_ERROR;
     (void)hipSetDevice(ctx->device);
     return query_launch(ctx, "rt_scene_trace_buffer", (const rt_ray*)rays->ptr, n, mode, hits ? (rt_hit*)hits->ptr : nullptr, occluded ? (uint32_t*)occluded->ptr : nullptr,
         surfaces ? (rt_surface*)surfaces->ptr : nullptr);

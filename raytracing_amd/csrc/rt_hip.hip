@@ -127,7 +127,7 @@ struct rt_ctx
     uint8_t* blue_noise = nullptr;   // sobol[65536] | scramblingTile[131072] | rankingTile[131072]
     float* gamma_lut = nullptr;      // pow(byte / 255, 2.2f), 256 entries (k_fill_gamma_lut)
     query::Scratch query;            // rt_scene_trace*: the walk's stack spill area and the host form's staging arrays (query_host.h)
-    bake::Scratch bake;              // rt_scene_bake*: the walk's stack spill area and the host form's staging arrays (bake_host.h)
+    query::Scratch bake;             // rt_scene_bake*: the same of its own (stages 0 and 1; the status word stays query.status), reported apart by rt_scene_tree_report
     uint32_t bake_chunk_points = bake::CHUNK_POINTS;   // RT_CTX_OPT_BAKE_CHUNK_POINTS
     std::string report_out;          // rt_scene_tree_report's answer when it has a "ray queries" line to add to the scene's report
 };
@@ -559,7 +559,7 @@ int rt_ctx_destroy(rt_ctx* ctx)
     (void)hipStreamSynchronize(ctx->stream);
     free_scene(ctx->scene);
     query::release(ctx->query);
-    bake::release(ctx->bake);
+    query::release(ctx->bake);
     if (ctx->blue_noise) (void)hipFree(ctx->blue_noise);
     if (ctx->gamma_lut) (void)hipFree(ctx->gamma_lut);
     (void)hipStreamDestroy(ctx->stream);

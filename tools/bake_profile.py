@@ -11,11 +11,12 @@ unfused route over the IDENTICAL rays once: chunk by chunk the device form of rt
 and through rt_scene_trace_buffer in any-hit mode (k_query_trace<true>; 2^24 rays per launch, so that the rays of a chunk fit a host array).  Compared are
 k_bake's average time per launch and the SUM of k_query_trace<true>'s launches of the one pass; the unfused route's generation and reduction count as zero.
 The rows of those kernels go to the CSV with the sample count in a first column; the ratios are added to --out's JSON when it exists."""
-import argparse, csv, glob, json, os, shutil, subprocess, sys, tempfile, time
+import argparse, json, os, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import bench
+import kernel_stats
 from raytracing_amd import capi, codeobj, host, scenes as S, types as T
 
 ap = argparse.ArgumentParser()
@@ -34,31 +35,22 @@ CHUNK_RAYS = 1 << 24
 if a.kernel_stats:
     rows, header, ratios = [], None, {}
     for samples in SAMPLES:
-        tmp = tempfile.mkdtemp(prefix="bake_profile_")
-        try:
-            subprocess.check_call(["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", tmp, "--", sys.executable, os.path.abspath(__file__),
-                                   "--config", str(a.config), "--kernel-calls", str(a.kernel_calls), "--radius-fraction", repr(a.radius_fraction),
-                                   "--kernels-only", str(samples)], cwd=ROOT)
-            found = sorted(glob.glob(os.path.join(tmp, "**", "*kernel_stats.csv"), recursive=True))
-            if not found:
-                raise SystemExit("rocprofv3 wrote no kernel statistics under " + tmp)
-            table = list(csv.reader(open(found[0])))
-            header = ["samples"] + table[0]
-            col = {name: i for i, name in enumerate(table[0])}
-            t = {}
-            for r in table[1:]:
-                for k in MEASURED:
-                    if k in r[0] and "k_bake_rays" not in r[0]:
-                        rows.append([str(samples)] + r)
-                        t[k] = dict(calls=int(r[col["Calls"]]), total_ns=int(r[col["TotalDurationNs"]]), average_ns=float(r[col["AverageNs"]]))
-            if len(t) == 2:
-                ratios[str(samples)] = dict(k_bake_ms_per_launch=t["k_bake"]["average_ns"] / 1e6, k_bake_launches=t["k_bake"]["calls"],
-                                            k_query_trace_any_hit_ms_one_pass=t["k_query_trace<true>"]["total_ns"] / 1e6, k_query_trace_launches=t["k_query_trace<true>"]["calls"],
-                                            k_bake_over_k_query_trace=t["k_bake"]["average_ns"] / t["k_query_trace<true>"]["total_ns"])
-        finally:
-            shutil.rmtree(tmp, ignore_errors=True)
-    with open(a.kernel_stats, "w", newline="") as f:
-        csv.writer(f).writerows([header] + rows)
+        head, kept = kernel_stats.child_rows(__file__, ["--config", a.config, "--kernel-calls", a.kernel_calls, "--radius-fraction", repr(a.radius_fraction),
+                                                        "--kernels-only", samples], lambda name: any(k in name for k in MEASURED) and "k_bake_rays" not in name,
+                                             ROOT, "bake_profile_")
+        header = ["samples"] + head
+        col = {name: i for i, name in enumerate(head)}
+        t = {}
+        for r in kept:
+            for k in MEASURED:
+                if k in r[0]:
+                    rows.append([str(samples)] + r)
+                    t[k] = dict(calls=int(r[col["Calls"]]), total_ns=int(r[col["TotalDurationNs"]]), average_ns=float(r[col["AverageNs"]]))
+        if len(t) == 2:
+            ratios[str(samples)] = dict(k_bake_ms_per_launch=t["k_bake"]["average_ns"] / 1e6, k_bake_launches=t["k_bake"]["calls"],
+                                        k_query_trace_any_hit_ms_one_pass=t["k_query_trace<true>"]["total_ns"] / 1e6, k_query_trace_launches=t["k_query_trace<true>"]["calls"],
+                                        k_bake_over_k_query_trace=t["k_bake"]["average_ns"] / t["k_query_trace<true>"]["total_ns"])
+    kernel_stats.write(a.kernel_stats, header, rows)
     for r in rows:
         print(", ".join(r[:6])[:240])
     print(json.dumps(ratios, indent=1))

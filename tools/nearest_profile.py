@@ -10,11 +10,12 @@ over --calls calls by the host clock after a warm-up, points per second, and whe
 The second form gives k_nearest's OWN time by one clock: per tree it starts `rocprofv3 --kernel-trace --stats -d DIR -- python tools/nearest_profile.py
 --kernels-only WIDE` as a fresh child process, without counters -- which launches the query --calls + 3 times on each point set -- and keeps the rows of
 k_nearest, with the tree and the point set in the first columns (the child runs one point set per process, so the rows cannot mix)."""
-import argparse, csv, glob, json, os, shutil, subprocess, sys, tempfile, time
+import argparse, json, os, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import bench
+import kernel_stats
 from raytracing_amd import capi, codeobj, host, scenes as S, types as T
 
 ap = argparse.ArgumentParser()
@@ -31,20 +32,11 @@ if a.kernel_stats:
     rows, header = [], None
     for wide in (1, 0):
         for which in SETS:
-            tmp = tempfile.mkdtemp(prefix="nearest_profile_")
-            try:
-                subprocess.check_call(["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", tmp, "--", sys.executable, os.path.abspath(__file__),
-                                       "--config", str(a.config), "--calls", str(a.calls), "--grid", str(a.grid), "--kernels-only", "%d,%s" % (wide, which)], cwd=ROOT)
-                found = sorted(glob.glob(os.path.join(tmp, "**", "*kernel_stats.csv"), recursive=True))
-                if not found:
-                    raise SystemExit("rocprofv3 wrote no kernel statistics under " + tmp)
-                table = list(csv.reader(open(found[0])))
-                header = ["tree", "points"] + table[0]
-                rows += [["wide" if wide else "pairs", which] + r for r in table[1:] if "k_nearest" in r[0]]
-            finally:
-                shutil.rmtree(tmp, ignore_errors=True)
-    with open(a.kernel_stats, "w", newline="") as f:
-        csv.writer(f).writerows([header] + rows)
+            head, kept = kernel_stats.child_rows(__file__, ["--config", a.config, "--calls", a.calls, "--grid", a.grid, "--kernels-only", "%d,%s" % (wide, which)],
+                                                 lambda name: "k_nearest" in name, ROOT, "nearest_profile_")
+            header = ["tree", "points"] + head
+            rows += [["wide" if wide else "pairs", which] + r for r in kept]
+    kernel_stats.write(a.kernel_stats, header, rows)
     for r in rows:
         print(", ".join(r[:7]))
     sys.exit(0)

@@ -11,11 +11,12 @@ The second form gives every kernel's OWN time by one clock: per queue it starts 
 --kernels-only BOUNCE` as a fresh child process -- which walks to the queue with k_trace2 (RT_OPT_TRACE_VARIANT = 8: other kernel names than the ones
 measured), then launches the query, k_trace_w4 and k_trace_v1 --calls + 3 times each on that queue, no event brackets -- and keeps the rows of those
 kernels (and of k_trace2: with a two-entry stack k_trace_w4's follow-up over its slow-ray list, otherwise the walk), with the queue in a first column."""
-import argparse, csv, glob, json, os, shutil, subprocess, sys, tempfile, time
+import argparse, json, os, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import bench
+import kernel_stats
 from raytracing_amd import capi, codeobj, host, scenes as S, types as T
 
 ap = argparse.ArgumentParser()
@@ -30,23 +31,11 @@ MEASURED = ("k_query_trace", "k_trace_w4", "k_trace_v1", "k_trace2")      # k_tr
 if a.kernel_stats:
     rows, header = [], None
     for bounce in (0, 2):
-        tmp = tempfile.mkdtemp(prefix="query_profile_")
-        try:
-            subprocess.check_call(["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", tmp, "--", sys.executable, os.path.abspath(__file__),
-                                   "--config", str(a.config), "--calls", str(a.calls), "--kernels-only", str(bounce)], cwd=ROOT)
-            found = sorted(glob.glob(os.path.join(tmp, "**", "*kernel_stats.csv"), recursive=True))
-            if not found:
-                raise SystemExit("rocprofv3 wrote no kernel statistics under " + tmp)
-            table = list(csv.reader(open(found[0])))
-            header = ["queue"] + table[0]
-            for r in table[1:]:
-                name = r[0]
-                if any(k in name for k in MEASURED):
-                    rows.append(["bounce_%d" % bounce] + r)
-        finally:
-            shutil.rmtree(tmp, ignore_errors=True)
-    with open(a.kernel_stats, "w", newline="") as f:
-        csv.writer(f).writerows([header] + rows)
+        head, kept = kernel_stats.child_rows(__file__, ["--config", a.config, "--calls", a.calls, "--kernels-only", bounce], lambda name: any(k in name for k in MEASURED),
+                                             ROOT, "query_profile_")
+        header = ["queue"] + head
+        rows += [["bounce_%d" % bounce] + r for r in kept]
+    kernel_stats.write(a.kernel_stats, header, rows)
     for r in rows:
         print(", ".join(r[:6]))
     sys.exit(0)
