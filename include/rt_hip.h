@@ -802,6 +802,14 @@ int rt_debug_device_tree(rt_ctx* ctx, const rt_bvh_node* nodes, uint32_t num_nod
 int rt_debug_wide_bvh_weights(const rt_bvh_node* nodes, uint32_t num_nodes, const double* weights, void* records, uint32_t* roots, uint32_t capacity,
     uint32_t* num_records, uint32_t* entry_ref);
 
+/* The adaptation's crossing counts on their own: counts[num_nodes] = how many of the n_rays rays (origins_tmax: x, y, z, t_max per ray; directions: x, y, z, - per
+ * ray) pass the slab test of each node of `nodes` within [0, t_max] (plain binary32: a weight, not a result); *truncated = nodes that passed while more than
+ * RT_COUNT_STACK - 3 = 61 nodes of that ray's walk were pending: such a node is counted, the subtree below it is not walked (a chain of 62 or more interior nodes
+ * with their leaves pending, first child deepest).  ctx == NULL: the host's walk (wide_bvh.cpp, count_box_passes); otherwise k_count_box_passes on ctx's device.
+ * The two obey the same rule and agree count for count, truncated walks included. */
+int rt_debug_count_box_passes(rt_ctx* ctx, const rt_bvh_node* nodes, uint32_t num_nodes, const float* origins_tmax, const float* directions, uint32_t n_rays,
+    uint32_t* counts, unsigned long long* truncated);
+
 /* RT_CTX_OPT_ADAPTIVE_FOLD's host half on its own (no device): the fold of `nodes` adapted to n_rays rays (origins_tmax: x, y, z, t_max per
  * ray; directions: x, y, z, - per ray) -- its records (and, optional, the node each one tests), and cost2 = {the surface-area fold's, the adapted
  * fold's} box passes at record roots per ray; *cheaper = the adapted fold would be adopted. */

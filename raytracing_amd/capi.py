@@ -102,7 +102,7 @@ EXPORTS = [
     "rt_compute_aovs", "rt_denoise", "rt_copy_history",
     "rt_frame_resolve", "rt_frame_present", "rt_frame_present_wait", "rt_frame_read_radiance", "rt_frame_radiance_device_ptr", "rt_frame_sample_count",
     "rt_frame_get_stats", "rt_frame_get_profile", "rt_frame_copy_radiance", "rt_frame_debug_read_queue", "rt_frame_debug_read_hits", "rt_debug_eval",
-    "rt_debug_wide_bvh", "rt_frame_debug_timeline", "rt_frame_debug_frame_rows", "rt_debug_own_bvh", "rt_debug_wide_bvh_metric", "rt_scene_tree_report", "rt_debug_choose_tree", "rt_debug_adapt_fold", "rt_debug_fold_abandon", "rt_debug_adapt_shadow_side", "rt_debug_rotate_tree", "rt_debug_fold_view_left", "rt_debug_device_fold", "rt_debug_wide_bvh_weights", "rt_debug_pair_layout", "rt_debug_device_tree", "rt_scene_export_folds", "rt_scene_import_folds",
+    "rt_debug_wide_bvh", "rt_frame_debug_timeline", "rt_frame_debug_frame_rows", "rt_debug_own_bvh", "rt_debug_wide_bvh_metric", "rt_scene_tree_report", "rt_debug_choose_tree", "rt_debug_adapt_fold", "rt_debug_fold_abandon", "rt_debug_adapt_shadow_side", "rt_debug_rotate_tree", "rt_debug_fold_view_left", "rt_debug_device_fold", "rt_debug_wide_bvh_weights", "rt_debug_pair_layout", "rt_debug_device_tree", "rt_debug_count_box_passes", "rt_scene_export_folds", "rt_scene_import_folds",
     "rt_group_create", "rt_group_unique_id", "rt_group_join", "rt_group_size", "rt_group_local_count", "rt_group_local_rank", "rt_group_comm_count",
     "rt_group_gather_radiance", "rt_group_destroy", "rt_group_last_error", "rt_group_denoise", "rt_group_create_local",
     "rt_group_create_unchecked",
@@ -170,6 +170,7 @@ def load():
         "rt_debug_wide_bvh_weights": (i32, [vp, u32, vp, vp, vp, u32, C.POINTER(u32), C.POINTER(u32)]),
         "rt_debug_pair_layout": (i32, [vp, u32, vp, vp, u32]),
         "rt_debug_device_tree": (i32, [vp, vp, u32, C.c_double, vp, u32, vp, u32, C.POINTER(u32), C.POINTER(C.c_double), C.POINTER(u32), u32, vp, C.c_double]),
+        "rt_debug_count_box_passes": (i32, [vp, vp, u32, vp, vp, u32, vp, C.POINTER(C.c_ulonglong)]),
         "rt_scene_export_folds": (i32, [vp, vp, vp, u32, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32)]),
         "rt_scene_import_folds": (i32, [vp, vp, u32, u32, vp, u32, u32]),
         "rt_debug_rotate_tree": (i32, [vp, u32, vp, vp, u32, i32, vp, C.POINTER(C.c_double), C.POINTER(u32), i32, C.c_double]),
@@ -580,6 +581,22 @@ def wide_bvh_weights(nodes, weights):
     if lib.rt_debug_wide_bvh_weights(nodes.ctypes.data, len(nodes), w.ctypes.data, out.ctypes.data, roots.ctypes.data, cap, C.byref(n), C.byref(entry)):
         raise RtError(lib.rt_last_error(None).decode())
     return out[:n.value].copy(), entry.value, roots[:n.value].copy()
+
+
+def count_box_passes(ctx, nodes, origins_tmax, directions):
+    """rt_debug_count_box_passes: per node of the LinearBVHNode[] `nodes`, how many of the rays (as adapt_fold takes them) pass its slab test.  ctx None = the host's walk,
+    else k_count_box_passes on ctx's GPU.  Returns (counts uint32[len(nodes)], walks cut short by the stack bound)."""
+    lib = load()
+    nodes = np.ascontiguousarray(nodes, T.bvh_node)
+    o = np.ascontiguousarray(origins_tmax, np.float32).reshape(-1, 4)
+    d = np.ascontiguousarray(directions, np.float32).reshape(-1, 4)
+    assert len(o) == len(d)
+    counts = np.zeros(len(nodes), np.uint32)
+    cut = C.c_ulonglong()
+    handle = ctx.handle if ctx is not None else None
+    if lib.rt_debug_count_box_passes(handle, nodes.ctypes.data, len(nodes), o.ctypes.data, d.ctypes.data, len(o), counts.ctypes.data, C.byref(cut)):
+        raise RtError(lib.rt_last_error(handle).decode())
+    return counts, cut.value
 
 
 def adapt_fold(nodes, origins_tmax, directions):

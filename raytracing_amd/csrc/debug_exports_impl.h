@@ -191,6 +191,46 @@ int rt_debug_wide_bvh_metric(const rt_bvh_node* nodes, uint32_t num_nodes, doubl
     return RT_OK;
 }
 
+// The adaptation's crossing counts on their own: the host's walk (ctx == NULL) or k_count_box_passes on ctx's device -- the same rule, compared count for count
+// by tests/test_gpu_tree_edges.py.
+int rt_debug_count_box_passes(rt_ctx* ctx, const rt_bvh_node* nodes, uint32_t num_nodes, const float* origins_tmax, const float* directions, uint32_t n_rays,
+    uint32_t* counts, unsigned long long* truncated)
+{
+    if (!nodes || num_nodes == 0 || !counts || (n_rays != 0 && (!origins_tmax || !directions))) return fail(ctx, "rt_debug_count_box_passes: NULL argument");
+    // what both walks take for granted (FoldAdapt's trees have passed build_wide_bvh): every interior node's children lie inside the array
+    for (uint32_t i = 0; i < num_nodes; ++i)
+        if ((nodes[i].num_primitives_axis >> 16) == 0u && (i + 1u >= num_nodes || nodes[i].offset >= num_nodes || nodes[i].offset <= i + 1u))
+            return fail(ctx, "rt_debug_count_box_passes: the node array is not a tree in the reference's layout");
+    std::vector<float4> o(n_rays), d(n_rays);
+    for (uint32_t i = 0; i < n_rays; ++i)
+    {
+        o[i] = make_float4(origins_tmax[4 * i], origins_tmax[4 * i + 1], origins_tmax[4 * i + 2], origins_tmax[4 * i + 3]);
+        d[i] = make_float4(directions[4 * i], directions[4 * i + 1], directions[4 * i + 2], 0.0f);
+    }
+    std::vector<uint32_t> got;
+    uint64_t cut_short = 0;
+    if (!ctx)
+    {
+        std::atomic<bool> cancel{false};
+        std::atomic<uint64_t> n_cut{0};
+        count_box_passes(nodes, num_nodes, o.data(), d.data(), o.size(), got, cancel, &n_cut);
+        cut_short = n_cut.load();
+    }
+    else
+    {
+        (void)hipSetDevice(ctx->device);
+        void* d_nodes = nullptr;
+        if (dev_alloc_copy(ctx, &d_nodes, nodes, (size_t)num_nodes * sizeof(rt_bvh_node)) != RT_OK) return RT_ERROR;
+        const bool ok = devfold::count_box_passes(ctx->stream, (const rt_bvh_node*)d_nodes, num_nodes, o.data(), d.data(), o.size(), got, &cut_short);
+        (void)hipStreamSynchronize(ctx->stream);
+        (void)hipFree(d_nodes);
+        if (!ok) return fail(ctx, "rt_debug_count_box_passes: the device path failed");
+    }
+    memcpy(counts, got.data(), (size_t)num_nodes * sizeof(uint32_t));
+    if (truncated) *truncated = cut_short;
+    return RT_OK;
+}
+
 // RT_CTX_OPT_ADAPTIVE_FOLD's host half on its own (no device): the surface-area fold of `nodes`, then the fold adapted to `n_rays` rays
 // (origin.xyz + t_max in .w, direction.xyz) -- the records of the latter, and what both cost those rays (box passes at record roots).
 int rt_debug_adapt_fold(const rt_bvh_node* nodes, uint32_t num_nodes, const float* origins_tmax, const float* directions, uint32_t n_rays,

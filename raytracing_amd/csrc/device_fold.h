@@ -19,7 +19,7 @@ bool fold(hipStream_t stream, const rt_bvh_node* d_nodes, uint32_t nn, const rt_
     const std::atomic<bool>* cancel = nullptr, double* seconds = nullptr);
 // A binary tree over exactly the LEAVES of d_ref_nodes[nn] (device, reference layout) built on the device: PLOC with `metric` as the merge cost (ploc_kernels.h).  On success
 // *d_tree = the tree in the reference's linear layout on the device (hipMalloc'ed: the caller frees it; fold() takes it as it is), *n_tree = 2 leaves - 1, and -- when asked
-// for -- its host copy.  false: a leaf root, a metric of more than 8 directions, an allocation that failed, `cancel`, or the clustering did not finish within its round limit.
+// for -- its host copy.  false: a leaf root, a metric of more than 8 directions, an allocation that failed, `cancel`, or the clustering did not finish within its round limit (400 rounds, or leaves - 1 -- always enough -- for a tree of up to 4096 leaves).
 bool build_tree(hipStream_t stream, const rt_bvh_node* d_ref_nodes, uint32_t nn, const rt_bvh_node& root_node, const ownbvh::Metric* metric, rt_bvh_node** d_tree, uint32_t* n_tree,
     std::vector<rt_bvh_node>* tree_out, const std::atomic<bool>* cancel = nullptr, double* seconds = nullptr, uint32_t* rounds_out = nullptr,
     const float* light_dir = nullptr /* the Morton order's frame: (u, v, this direction); NULL = the world axes */, uint32_t radius = 0 /* 0 = PLOC_RADIUS */, double stretch = 1.0);

@@ -228,9 +228,12 @@ bool build_tree(hipStream_t stream, const rt_bvh_node* d_ref_nodes, uint32_t nn,
     hipLaunchKernelGGL(k_ploc_init, dim3(leaf_blocks), dim3(256), 0, stream, d_ref_nodes, (const uint32_t*)leaf_nodes, (const uint32_t*)values_sorted, n_leaves, pool, parent, cluster[0]);
     uint32_t n = n_leaves, next_id = n_leaves, rounds = 0;
     int cur = 0;
+    // every round merges at least the globally cheapest pair (typical: ~30 rounds), so n_leaves - 1 rounds always finish; where every cost ties (coincident leaves)
+    // a round merges that one pair only.  A small tree is given the rounds it can need; a large one that has not finished in 400 is left to the host's builder.
+    const uint32_t round_limit = n_leaves <= 4096u ? std::max(400u, n_leaves) : 400u;
     while (n > 1u)
     {
-        if (++rounds > 400u || cancelled()) { (void)hipGetLastError(); return false; }       // (every round merges at least the globally cheapest pair; typical: ~30 rounds)
+        if (++rounds > round_limit || cancelled()) { (void)hipGetLastError(); return false; }
         const uint32_t blocks = (n + 255u) / 256u;
         hipLaunchKernelGGL(k_ploc_nearest, dim3(blocks), dim3(256), 0, stream, (const PlocNode*)pool, (const uint32_t*)cluster[cur], n, fm, radius, nearest);
         hipLaunchKernelGGL(k_ploc_decide, dim3(blocks), dim3(256), 0, stream, (const uint32_t*)nearest, n, keep, merge);

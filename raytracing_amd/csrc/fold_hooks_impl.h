@@ -135,7 +135,7 @@ static int fold_adopt(rt_ctx* ctx)
         if (truncated != 0)
         {
             text.pop_back();
-            snprintf(line, sizeof(line), "; %llu host walks met a subtree deeper than their 126-entry stack (weights only)\n", (unsigned long long)truncated);
+            snprintf(line, sizeof(line), "; %llu host walks met a subtree deeper than their stack (weights only)\n", (unsigned long long)truncated);
             text += line;
         }
     }

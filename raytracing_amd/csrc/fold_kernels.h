@@ -338,7 +338,7 @@ __global__ __launch_bounds__(64) void k_fold_emit(FoldState s, const uint32_t* _
 }
 
 // counts[n] += rays whose slab test of binary-tree node n passes within [0, o.w] (plain binary32: a weight, not a result) -- the host's
-// count_box_passes, one thread per probe ray, a 64-entry stack per thread (deeper subtrees are left out and counted in *truncated)
+// count_box_passes, one thread per probe ray, RT_COUNT_STACK pending nodes per thread (wide_node.h: deeper subtrees are left out and counted in *truncated, on the host alike)
 __global__ __launch_bounds__(64) void k_count_box_passes(const rt_bvh_node* __restrict__ nodes, uint32_t nn, const float4* __restrict__ o, const float4* __restrict__ d,
     uint32_t n_rays, uint32_t* __restrict__ counts, uint32_t* __restrict__ truncated)
 {
@@ -347,7 +347,7 @@ __global__ __launch_bounds__(64) void k_count_box_passes(const rt_bvh_node* __re
     const float4 ro = o[r], rd = d[r];
     const float org[3] = {ro.x, ro.y, ro.z}, inv[3] = {1.0f / rd.x, 1.0f / rd.y, 1.0f / rd.z};
     const float t_max = ro.w;
-    uint32_t stack[64];
+    uint32_t stack[RT_COUNT_STACK];
     int sp = 0;
     stack[sp++] = 0;
     while (sp > 0)
@@ -365,7 +365,7 @@ __global__ __launch_bounds__(64) void k_count_box_passes(const rt_bvh_node* __re
         if (!(t0 <= t1)) continue;
         atomicAdd(&counts[n], 1u);
         if ((b.num_primitives_axis >> 16) != 0u) continue;
-        if (sp > 61) { atomicAdd(truncated, 1u); continue; }
+        if (sp > RT_COUNT_STACK - 3) { atomicAdd(truncated, 1u); continue; }
         if (b.offset >= nn || n + 1u >= nn) continue;
         stack[sp++] = b.offset;
         stack[sp++] = n + 1u;

@@ -529,16 +529,18 @@ unsigned adapt_threads(size_t work_items, size_t per_thread)
 }
 static std::atomic<uint64_t> g_truncated_walks{0};
 uint64_t truncated_walks_exchange() { return g_truncated_walks.exchange(0); }
-void truncated_walks_add(uint64_t n) { g_truncated_walks.fetch_add(n, std::memory_order_relaxed); }   // host walks (weights only) that met a binary tree deeper than their 126-entry stack
+void truncated_walks_add(uint64_t n) { g_truncated_walks.fetch_add(n, std::memory_order_relaxed); }   // host walks (weights only) that met a binary tree deeper than their stack
 
 // counts[n] = rays whose slab test of binary-tree node n passes within [0, o.w] (plain binary32 arithmetic: a weight, not a result)
+// (k_count_box_passes' rule, RT_COUNT_STACK pending nodes included: wide_node.h); truncated: where to count the walks cut short, NULL = the report's counter
 void count_box_passes(const rt_bvh_node* nodes, uint32_t nn, const float4* o, const float4* d, size_t n_rays, std::vector<uint32_t>& counts,
-    const std::atomic<bool>& cancel)
+    const std::atomic<bool>& cancel, std::atomic<uint64_t>* truncated)
 {
     counts.assign(nn, 0u);
+    std::atomic<uint64_t>& cut_short = truncated ? *truncated : g_truncated_walks;
     auto run = [&](size_t r0, size_t r1)
     {
-        uint32_t stack[128];
+        uint32_t stack[RT_COUNT_STACK];
         for (size_t r = r0; r < r1 && !cancel.load(std::memory_order_relaxed); ++r)
         {
             const float org[3] = {o[r].x, o[r].y, o[r].z}, inv[3] = {1.0f / d[r].x, 1.0f / d[r].y, 1.0f / d[r].z};
@@ -560,7 +562,7 @@ void count_box_passes(const rt_bvh_node* nodes, uint32_t nn, const float4* o, co
                 if (!(t0 <= t1)) continue;
                 __atomic_fetch_add(&counts[n], 1u, __ATOMIC_RELAXED);
                 if ((b.num_primitives_axis >> 16) != 0) continue;
-                if (sp > 125) { g_truncated_walks.fetch_add(1, std::memory_order_relaxed); continue; }
+                if (sp > RT_COUNT_STACK - 3) { cut_short.fetch_add(1, std::memory_order_relaxed); continue; }
                 if (b.offset >= nn || n + 1u >= nn) continue;
                 stack[sp++] = b.offset;
                 stack[sp++] = n + 1u;

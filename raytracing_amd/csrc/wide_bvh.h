@@ -38,7 +38,8 @@ unsigned adapt_threads(size_t work_items, size_t per_thread);
 uint64_t truncated_walks_exchange();
 void truncated_walks_add(uint64_t n);
 
-void count_box_passes(const rt_bvh_node* nodes, uint32_t nn, const float4* o, const float4* d, size_t n_rays, std::vector<uint32_t>& counts, const std::atomic<bool>& cancel);
+void count_box_passes(const rt_bvh_node* nodes, uint32_t nn, const float4* o, const float4* d, size_t n_rays, std::vector<uint32_t>& counts, const std::atomic<bool>& cancel,
+    std::atomic<uint64_t>* truncated = nullptr /* walks cut short (RT_COUNT_STACK, wide_node.h) are counted here; NULL: in truncated_walks_exchange()'s counter */);
 void nearest_occluders(const std::vector<rt_bvh_node>& tree, const std::vector<float>& tri9, const std::vector<float4>& o, const std::vector<float4>& d,
     std::vector<uint32_t>& prim, const std::atomic<bool>& cancel);
 uint32_t occluder_first(std::vector<WideNode>& wide, const std::vector<uint32_t>& roots, const std::vector<rt_bvh_node>& tree, const std::vector<uint32_t>& prim);

@@ -24,6 +24,27 @@ def test_librt_hip_exports_every_declared_symbol():
     assert sorted(capi.EXPORTS) == names          # the Python binding covers the whole ABI
 
 
+def test_the_crossing_counts_debug_entry_is_declared_bound_and_refuses_bad_input():
+    """rt_debug_count_box_passes: ctx-or-NULL like rt_debug_refit; the host half runs without a GPU"""
+    import numpy as np
+    from raytracing_amd import types as T
+    assert "rt_debug_count_box_passes" in _declared("rt_hip.h") and "rt_debug_count_box_passes" in capi.EXPORTS
+    fn = capi.load().rt_debug_count_box_passes
+    assert fn.argtypes is not None and len(fn.argtypes) == 8
+    leaf = np.zeros(1, T.bvh_node)
+    leaf["num_primitives_axis"] = 1 << 16
+    for c in "xyz":
+        leaf["bounds_min"][c], leaf["bounds_max"][c] = -1.0, 1.0
+    o = np.array([[0, 0, -5, 1e30], [0, 0, -5, 1.0], [3, 0, -5, 1e30]], np.float32)
+    d = np.array([[0, 0, 1, 0]] * 3, np.float32)
+    counts, cut = capi.count_box_passes(None, leaf, o, d)
+    assert counts.tolist() == [1] and cut == 0                      # one ray reaches the box; one ends before it, one passes beside it
+    bad = np.zeros(3, T.bvh_node)                                   # an interior node whose second child lies outside the array
+    bad["offset"][0] = 7
+    with pytest.raises(capi.RtError, match="not a tree"):
+        capi.count_box_passes(None, bad, o, d)
+
+
 def test_librt_host_exports():
     lib = ctypes.CDLL(host.LIB_PATH)
     for n in host.EXPORTS:

@@ -170,23 +170,20 @@ def test_shadow_verdicts_on_a_dense_mesh(env_map):
     assert steps(out["own, projected area"]["shadow"]) < steps(out["reference"]["shadow"])
 
 
-@pytest.mark.parametrize("seed", range(6))
-def test_shadow_verdicts_on_random_soups(seed, env_map):
-    """Slivers, coincident triangles (ties!), lights inside the geometry, an axis-parallel light (those rays take the BVH2 walk)."""
-    rng = np.random.default_rng(100 + seed)
-    n = int(rng.integers(2, 600))
-    P = rng.normal(size=(n, 1, 3)) * 1.2 + rng.normal(size=(n, 3, 3)) * float(10.0 ** rng.uniform(-1.2, 0.0)) + np.array([0.0, 2.5, 1.0])
-    P = P.astype(np.float32)
-    if seed % 2:
-        P[: n // 4] = P[0]
-    N = np.cross(P[:, 1] - P[:, 0], P[:, 2] - P[:, 0])
-    N = (N / np.maximum(np.linalg.norm(N, axis=1, keepdims=True), 1e-20)).astype(np.float32)[:, None, :].repeat(3, 1)
-    tris = S.to_triangles([(P, N, np.zeros((n, 3, 2), np.float32), 0)])
-    mats = np.array([S.make_material(kd=(0.7, 0.6, 0.5), ks=(0.3, 0.3, 0.3), roughness=0.3)], dtype=T.packed_material)
+def shadow_soup_arrays(seed, env_map):
+    """the soup of tests/_trees.py as a finished scene: the lights of this file, and an axis-parallel one for seed 3"""
+    from tests._trees import shadow_soup
+    tris, mats = shadow_soup(seed)
     s = host.Scene(arrays=dict(triangles=tris, materials=mats))
     if seed == 3:
         s.add_directional_light((0.0, 0.0, 1.0), (5.0, 5.0, 5.0))
-    arrays = _finish(s, env_map)
+    return _finish(s, env_map)
+
+
+@pytest.mark.parametrize("seed", range(6))
+def test_shadow_verdicts_on_random_soups(seed, env_map):
+    """Slivers, coincident triangles (ties!), lights inside the geometry, an axis-parallel light (those rays take the BVH2 walk)."""
+    arrays = shadow_soup_arrays(seed, env_map)
     if (arrays["nodes"]["num_primitives_axis"][0] >> 16) != 0:
         pytest.skip("a single leaf: no tree to build")
     trees, _ = trees_of(arrays)

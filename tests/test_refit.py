@@ -16,6 +16,7 @@ import pytest
 from raytracing_amd import capi, host, scenes as S, types as T
 from tests.test_wide_bvh import check, wide_of, bvh_of, WIDE
 from tests.test_own_tree import own_tree
+from tests._trees import refit_soup, leaf_root_scene, two_triangle_scene
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MATS = np.array([S.make_material(kd=(0.7, 0.7, 0.7))], dtype=T.packed_material)
@@ -115,14 +116,8 @@ def test_node_refit_and_folds_on_the_golden_scenes(golden_scenes):
 
 @pytest.mark.parametrize("seed", range(6))
 def test_node_refit_and_folds_on_random_soups(seed):
-    rng = np.random.default_rng(100 + seed)
-    n = int(rng.integers(3, 600))
-    scale = float(10.0 ** rng.integers(-4, 5))
-    offset = rng.normal(size=3) * float(10.0 ** rng.integers(-3, 6))
-    P = (rng.normal(size=(n, 1, 3)) * scale + rng.normal(size=(n, 3, 3)) * scale * float(10.0 ** rng.integers(-4, 1)) + offset).astype(np.float32)
-    N = np.tile(np.array([0, 0, 1], np.float32), (n, 3, 1))
-    tris = S.to_triangles([(P, N, np.zeros((n, 3, 2), np.float32), 0)])
-    nodes, tris = bvh_of(tris, MATS)
+    tris, mats, rng = refit_soup(seed)
+    nodes, tris = bvh_of(tris, mats)
     folds = folds_of(nodes)
     refit_and_check(nodes, smooth(tris, 0.1), folds)
     refit_and_check(nodes, jitter(tris, rng, 0.2), folds)
@@ -168,21 +163,15 @@ def test_refit_back_to_the_first_pose_reproduces_the_first_records(golden_scenes
     same_records(r2, rec)
 
 
-def one_triangle(p):
-    P = np.asarray(p, np.float32).reshape(1, 3, 3)
-    return S.to_triangles([(P, np.tile(np.array([0, 0, 1], np.float32), (1, 3, 1)), np.zeros((1, 3, 2), np.float32), 0)])
-
-
 def test_a_leaf_root_and_a_two_triangle_scene():
-    nodes, tris = bvh_of(one_triangle([[0, 0, 0], [1, 0, 0], [0, 1, 0]]), MATS)
+    nodes, tris = bvh_of(*leaf_root_scene())
     assert len(nodes) == 1
     pose = moved(tris, positions(tris) + np.float32(3.0))
     got, rec, bad = capi.debug_refit(None, nodes, pose)
     same_nodes(got, np_refit(nodes, pose))
     assert rec is None and not bad
     check(got)
-    two = np.concatenate([one_triangle([[0, 0, 0], [1, 0, 0], [0, 1, 0]]), one_triangle([[5, 5, 5], [6, 5, 5], [5, 6, 7]])])
-    nodes, tris = bvh_of(two, MATS)
+    nodes, tris = bvh_of(*two_triangle_scene())
     assert len(nodes) == 3
     refit_and_check(nodes, jitter(tris, np.random.default_rng(1), 0.3), folds_of(nodes))
 

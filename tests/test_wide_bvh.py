@@ -219,13 +219,8 @@ def test_the_exchange_network_serves_every_shape_a_record_can_fold():
 
 @pytest.mark.parametrize("seed", range(8))
 def test_the_sah_collapse_is_optimal_on_small_trees(seed):
-    rng = np.random.default_rng(100 + seed)
-    n = int(rng.integers(5, 120))
-    P = (rng.normal(size=(n, 1, 3)) * rng.uniform(0.2, 3.0, size=(1, 1, 3)) + rng.normal(size=(n, 3, 3)) * 0.05).astype(np.float32)
-    N = np.tile(np.array([0, 0, 1], np.float32), (n, 3, 1))
-    tris = S.to_triangles([(P, N, np.zeros((n, 3, 2), np.float32), 0)])
-    mats = np.array([S.make_material(kd=(0.7, 0.7, 0.7))], dtype=T.packed_material)
-    nodes, _ = bvh_of(tris, mats)
+    from tests._trees import sah_soup
+    nodes, _ = bvh_of(*sah_soup(seed))
     if (int(nodes["num_primitives_axis"][0]) >> 16) != 0:
         return
     import sys
@@ -257,18 +252,8 @@ def test_wide_tree_of_the_cornell_box_and_a_dense_mesh():
 @pytest.mark.parametrize("seed", range(6))
 def test_wide_tree_of_random_soups_with_extreme_coordinates(seed):
     """Slivers, coincident triangles, huge offsets (coarse fp32 grid) and tiny extents."""
-    rng = np.random.default_rng(seed)
-    n = int(rng.integers(1, 400))
-    scale = float(10.0 ** rng.integers(-6, 7))
-    offset = rng.normal(size=3) * float(10.0 ** rng.integers(-3, 8))
-    P = (rng.normal(size=(n, 1, 3)) * scale + rng.normal(size=(n, 3, 3)) * scale * float(10.0 ** rng.integers(-5, 1)) + offset)
-    P = P.astype(np.float32)
-    if seed % 2:
-        P[: n // 3] = P[0]                                   # coincident triangles
-    N = np.tile(np.array([0, 0, 1], np.float32), (n, 3, 1))
-    tris = S.to_triangles([(P, N, np.zeros((n, 3, 2), np.float32), 0)])
-    mats = np.array([S.make_material(kd=(0.7, 0.7, 0.7))], dtype=T.packed_material)
-    nodes, _ = bvh_of(tris, mats)
+    from tests._trees import extreme_soup
+    nodes, _ = bvh_of(*extreme_soup(seed))
     check(nodes)
     check(nodes, collapse=2)
 
