@@ -342,6 +342,42 @@ int rt_debug_nearest(rt_ctx* ctx_or_null, const rt_triangle* triangles, uint32_t
 int rt_debug_nearest_walk(const rt_bvh_node* nodes, uint32_t num_nodes, const rt_triangle* triangles, uint32_t num_triangles, int wide,
                           const rt_point* points, uint32_t n, rt_nearest* out, uint32_t* triangles_tested_or_null);
 
+/* ---- all hits: every surface a CALLER's ray crosses, counted, the nearest of them sorted (opt-in extension).  What lies behind the
+ * first surface (select-through picking), whether a point is inside a closed object (entries against exits along a ray), layer order and thickness.
+ * raytracing_amd/csrc/all_hits.h states the arithmetic.
+ *   the HIT SET of a walked ray: of every leaf of the scene's reference tree whose box passes the reference's box test with the ray's own [t_min, t_max],
+ *     every triangle that the two-sided ray-triangle test accepts with that same range.  t_max is never lowered.  The test is the reference's (ray_triangle,
+ *     trace_bvh.cl:28-73) with one rule changed: it rejects |det| < 1e-8 where the reference rejects every det < 1e-8 -- the reference culls back faces, and
+ *     a set without them would hold no exits.  That is a statement about leaves and triangles alone: the set is the same whichever tree or fold is walked,
+ *     after any refit or pose, and rt_debug_trace_all gives it by brute force.
+ *   rt_ray_hits: count = the members; entering = the members with det > 0 (the ray runs against cross(p2 - p1, p3 - p1)): exactly the triangles a ray query
+ *     could report, so entering > 0 is RT_QUERY_ANY_HIT's verdict and RT_QUERY_CLOSEST's hit is the nearest entering member; count - entering = the exits;
+ *     stored = min(count, max_hits); flags bit 0 = the ray was walked, bit 8 + j = stored hit j is an exit.
+ *   hits (optional, max_hits records per ray, max_hits <= RT_ALL_HITS_MAX): the `stored` smallest members in ascending (t, primitive_id) order, t compared as
+ *     binary32: coincident triangles are both reported, lowest primitive_id first.  bc and t of an entering member are bit for bit a ray query's.  The records
+ *     from `stored` up to max_hits are primitive_id = RT_INVALID_ID and zeros.  A smaller max_hits gives a prefix of the same list.
+ *   surfaces (optional, max_hits per ray): the rt_surface of each stored hit as a ray query makes it (query.h); miss records beyond `stored`.
+ *   a ray that is not walked (a non-finite component, an all-zero direction) gives zeros and invalid hits; t_min > t_max gives count 0.
+ * Runs on the context's stream like a ray query, touches no frame and no rt_stats field, and uses the ray queries' spill area, status word and staging arrays.
+ *   rt_scene_trace_all: host arrays, staged in chunks of at most 4 Mi hit records; returns when the outputs are written.
+ *   rt_scene_trace_all_buffer: rt_buffers of this context (n rt_ray, n rt_ray_hits, n * max_hits rt_hit / rt_surface); only enqueues.
+ *   rt_frame_pick_all: rt_frame_pick's ray through the centre of pixel (x, y).
+ * Refused with nothing launched: a NULL context, NULL rays with n > 0, no scene, out NULL, max_hits > RT_ALL_HITS_MAX, hits or surfaces with max_hits == 0, a
+ * buffer of another context or too small, a pixel outside the image, a tile frame.  n == 0 is RT_OK and does nothing. */
+#define RT_ALL_HITS_MAX 8
+#define RT_RAY_HITS_WALKED 1u
+#define RT_RAY_HITS_EXIT_SHIFT 8
+typedef struct rt_ray_hits { uint32_t count; uint32_t entering; uint32_t stored; uint32_t flags; } rt_ray_hits;      /* 16 bytes */
+int rt_scene_trace_all(rt_ctx* ctx, const rt_ray* rays, uint32_t n, uint32_t max_hits, rt_ray_hits* out, rt_hit* hits_or_null, rt_surface* surfaces_or_null);
+int rt_scene_trace_all_buffer(rt_ctx* ctx, rt_buffer* rays, uint32_t n, uint32_t max_hits, rt_buffer* out, rt_buffer* hits_or_null, rt_buffer* surfaces_or_null);
+int rt_frame_pick_all(rt_frame* frame, uint32_t x, uint32_t y, uint32_t max_hits, rt_ray* ray_or_null, rt_ray_hits* out, rt_hit* hits_or_null,
+                      rt_surface* surfaces_or_null);
+/* brute force over the leaves of `nodes`, no tree walk: each leaf's box test, then the triangle test on the trace-record form of its triangles (p1,
+ * fl(p2 - p1), fl(p3 - p1)); primitive_id = the index.  ctx == NULL: the host (all_hits.h); otherwise k_all_hits_brute on uploaded copies.  The two agree bit
+ * for bit.  hits may be NULL when max_hits == 0.  Refused: a NULL argument, a leaf whose triangles lie outside the array, max_hits > RT_ALL_HITS_MAX. */
+int rt_debug_trace_all(rt_ctx* ctx_or_null, const rt_bvh_node* nodes, uint32_t num_nodes, const rt_triangle* triangles, uint32_t num_triangles,
+                       const rt_ray* rays, uint32_t n, uint32_t max_hits, rt_ray_hits* out, rt_hit* hits);
+
 /* One fold adaptation per process GROUP instead of one per rank (N ranks that tile one image hold the same scene and would each probe, rotate and fold for
  * identical records): the context's current 4-wide records -- the closest-hit rays' and the shadow rays' (n_shadow == 0: they share), as adapted so far -- to
  * host buffers of `capacity` records each (records NULL: size query; entries2 = {closest entry, shadow entry}), and into another context that has uploaded
@@ -852,4 +888,5 @@ int rt_debug_eval(rt_ctx* ctx, int fn, const float* a, const float* b, float* ou
 RT_STATIC_ASSERT(sizeof(rt_surface) == 64, "rt_surface");
 RT_STATIC_ASSERT(sizeof(rt_bake_result) == 16 && sizeof(rt_bake_desc) == 20, "rt_bake_result / rt_bake_desc");
 RT_STATIC_ASSERT(sizeof(rt_point) == 16 && sizeof(rt_nearest) == 32, "rt_point / rt_nearest");
+RT_STATIC_ASSERT(sizeof(rt_ray_hits) == 16, "rt_ray_hits");
 #endif /* RT_HIP_H */

@@ -114,6 +114,7 @@ EXPORTS = [
     "rt_scene_trace", "rt_scene_trace_buffer", "rt_frame_pick", "rt_debug_query_surface",
     "rt_scene_bake", "rt_scene_bake_buffer", "rt_debug_bake_rays", "rt_debug_bake_reduce",
     "rt_scene_nearest", "rt_scene_nearest_buffer", "rt_debug_nearest", "rt_debug_nearest_walk",
+    "rt_scene_trace_all", "rt_scene_trace_all_buffer", "rt_frame_pick_all", "rt_debug_trace_all",
 ]
 
 OPT_MAX_BOUNCES, OPT_WHITE_FURNACE, OPT_SAMPLER, OPT_AOV, OPT_DENOISER, OPT_DROP_LAST, OPT_PROFILE, OPT_TRACE_VARIANT, OPT_TRACE_WAVES, OPT_SAMPLES_IN_FLIGHT, OPT_SELECT_FORM_BOX, OPT_PACKET_BOUNCES, OPT_TRACE_TUNE, OPT_DEBUG_ALLOC_LIMIT, OPT_PATH_STATE_LIMIT_MB, OPT_PIPELINES, OPT_SHADE_PARTITION, OPT_OVERLAP_SHADOW, OPT_SMALL_LAUNCH_PATHS, OPT_COMPACT_LOG, OPT_DEBUG_LOG_POOL_DIV, OPT_TRACE_TAIL_LANES, OPT_TRACE_TAIL_PATHS, OPT_CHUNK_REFILL, OPT_STAGE_PIPES, OPT_FRAME_KERNEL, OPT_SAMPLES_AHEAD = range(27)
@@ -208,6 +209,9 @@ def load():
         "rt_scene_nearest": (i32, [vp, vp, u32, vp, vp]), "rt_scene_nearest_buffer": (i32, [vp, vp, u32, vp, vp]),
         "rt_debug_nearest": (i32, [vp, vp, u32, vp, u32, vp]),
         "rt_debug_nearest_walk": (i32, [vp, u32, vp, u32, i32, vp, u32, vp, vp]),
+        "rt_scene_trace_all": (i32, [vp, vp, u32, u32, vp, vp, vp]), "rt_scene_trace_all_buffer": (i32, [vp, vp, u32, u32, vp, vp, vp]),
+        "rt_frame_pick_all": (i32, [vp, u32, u32, u32, vp, vp, vp, vp]),
+        "rt_debug_trace_all": (i32, [vp, vp, u32, vp, u32, vp, u32, u32, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -365,6 +369,29 @@ def ray_records(rays):
     if a.ndim != 2 or a.shape[1] != 8:
         raise RtError("rays must be types.ray records or float32[n, 8] (origin.xyz, t_min, direction.xyz, t_max)")
     return a.view(T.ray).reshape(-1)
+
+
+ALL_HITS_MAX = 8          # RT_ALL_HITS_MAX
+RAY_HITS_WALKED = 1       # rt_ray_hits.flags bit 0
+RAY_HITS_EXIT_SHIFT = 8   # rt_ray_hits.flags bit 8 + j: stored hit j is an exit
+
+
+def debug_trace_all(ctx, nodes, triangles, rays, max_hits=ALL_HITS_MAX):
+    """rt_debug_trace_all: (types.ray_hits[n], types.hit[n, max_hits]) of `rays` (ray_records' rule) by brute force over the leaves of `nodes`
+    (types.bvh_node) and `triangles` (types.triangle) -- no tree walk.  ctx None = the host (csrc/all_hits.h), else k_all_hits_brute on ctx's GPU."""
+    lib = load()
+    nd = np.ascontiguousarray(nodes, T.bvh_node)
+    tris = np.ascontiguousarray(triangles, T.triangle)
+    r = ray_records(rays)
+    out = np.zeros(len(r), T.ray_hits)
+    hits = np.zeros((len(r), max_hits), T.hit)
+    handle = ctx.handle if ctx is not None else None
+    rc = lib.rt_debug_trace_all(handle, nd.ctypes.data if len(nd) else None, len(nd), tris.ctypes.data if len(tris) else None, len(tris),
+                                r.ctypes.data if len(r) else None, len(r), max_hits, out.ctypes.data if len(r) else None,
+                                hits.ctypes.data if hits.size else None)
+    if rc != 0:
+        raise RtError(lib.rt_last_error(handle).decode())
+    return out, hits
 
 
 def debug_query_surface(ctx, triangles, rays, hits, object_of_triangle=None):
@@ -762,6 +789,30 @@ class Context:
         h = lambda b: b.handle if b is not None else None
         _check(self.lib, self.handle, self.lib.rt_scene_trace_buffer(self.handle, h(rays), n, QUERY_ANY_HIT if any_hit else QUERY_CLOSEST, h(hits), h(occluded), h(surfaces)))
 
+    def trace_all(self, rays, max_hits=ALL_HITS_MAX, surfaces=False):
+        """rt_scene_trace_all: every surface each of the caller's rays (ray_records' rule) crosses: (types.ray_hits[n], types.hit[n, max_hits]) -- the
+        counts, and the nearest max_hits crossings in ascending (t, primitive_id) order -- or (records, hits, types.surface[n, max_hits]) with
+        surfaces=True.  max_hits=0: the records alone."""
+        r = ray_records(rays)
+        n = len(r)
+        out = np.zeros(n, T.ray_hits)
+        if max_hits == 0:
+            if surfaces:
+                raise RtError("trace_all: surfaces need max_hits > 0")
+            _check(self.lib, self.handle, self.lib.rt_scene_trace_all(self.handle, r.ctypes.data if n else None, n, 0, out.ctypes.data, None, None))
+            return out
+        hits = np.zeros((n, max_hits), T.hit)
+        surf = np.zeros((n, max_hits), T.surface) if surfaces else None
+        _check(self.lib, self.handle, self.lib.rt_scene_trace_all(self.handle, r.ctypes.data if n else None, n, max_hits, out.ctypes.data, hits.ctypes.data,
+                                                                    surf.ctypes.data if surfaces else None))
+        return (out, hits, surf) if surfaces else (out, hits)
+
+    def trace_all_buffer(self, rays, n, max_hits, out, hits=None, surfaces=None):
+        """rt_scene_trace_all_buffer: the same over Buffers of this context (n rays and records, n * max_hits hits / surfaces; an output that is not
+        wanted is None).  Only enqueues: Buffer.read() or finish() waits."""
+        h = lambda b: b.handle if b is not None else None
+        _check(self.lib, self.handle, self.lib.rt_scene_trace_all_buffer(self.handle, h(rays), n, max_hits, h(out), h(hits), h(surfaces)))
+
     def nearest(self, points, surfaces=False):
         """rt_scene_nearest: for each of the caller's points (point_records' rule) the nearest triangle of the uploaded scene, where on it and how far:
         types.nearest[n], or (records, types.surface[n]) with surfaces=True"""
@@ -976,6 +1027,15 @@ class Frame:
         ray, hit, surf = np.zeros(1, T.ray), np.zeros(1, T.hit), np.zeros(1, T.surface)
         self._c(self.lib.rt_frame_pick(self.handle, x, y, ray.ctypes.data, hit.ctypes.data, surf.ctypes.data))
         return ray[0], hit[0], surf[0]
+
+    def pick_all(self, x, y, max_hits=ALL_HITS_MAX):
+        """rt_frame_pick_all: (ray, record, hits, surfaces) -- a types.ray and a types.ray_hits scalar, types.hit[max_hits], types.surface[max_hits] -- of
+        every surface the ray through the centre of pixel (x, y) crosses, nearest first"""
+        ray, rec = np.zeros(1, T.ray), np.zeros(1, T.ray_hits)
+        hits, surf = np.zeros(max_hits, T.hit), np.zeros(max_hits, T.surface)
+        self._c(self.lib.rt_frame_pick_all(self.handle, x, y, max_hits, ray.ctypes.data, rec.ctypes.data, hits.ctypes.data if max_hits else None,
+                                           surf.ctypes.data if max_hits else None))
+        return ray[0], rec[0], hits, surf
 
     def guide_motion(self):
         """rt_frame_read_guide_motion: (previous position float32[h, w, 4] = (X', 1), previous normal float32[h, w, 4] = (n', 0)) of every pixel's first

@@ -31,6 +31,7 @@
 #include "query_host.h"      // caller-supplied rays traced against the uploaded scene (query.hip)
 #include "bake_host.h"       // ambient occlusion and bent normals at caller-supplied points (bake.hip)
 #include "nearest_host.h"    // the nearest surface point to caller-supplied points (nearest.hip)
+#include "all_hits_host.h"   // every surface a caller-supplied ray crosses (all_hits.hip)
 using namespace rtw;
 
 namespace
@@ -1079,6 +1080,7 @@ extern "C" {
 #include "query_impl.h"
 #include "bake_impl.h"
 #include "nearest_impl.h"
+#include "all_hits_impl.h"
 
 // ---- scene -----------------------------------------------------------------
 int rt_scene_upload(rt_ctx* ctx, const rt_scene_desc* sd)

@@ -1,10 +1,11 @@
-// walk_kernels.h -- what the kernels of the caller-facing queries share (DESIGN.md sections 7h, 7i, 7j): k_query_trace (query_kernels.h), k_bake (bake_kernels.h)
-// and k_nearest (nearest_kernels.h) are built from the pieces below.  The frame's own walks (trace_kernels.h, rt_hip.hip's code object) are not: this header is
-// included by query.hip, bake.hip and nearest.hip only.
+// walk_kernels.h -- what the kernels of the caller-facing queries share (DESIGN.md sections 7h - 7k): k_query_trace (query_kernels.h), k_bake (bake_kernels.h),
+// k_nearest (nearest_kernels.h) and k_all_hits (all_hits_kernels.h) are built from the pieces below.  The frame's own walks (trace_kernels.h, rt_hip.hip's code
+// object) are not: this header is included by query.hip, bake.hip, nearest.hip and all_hits.hip only.
 //
 //   Stack          a lane's traversal stack: push, and a pop that takes the walk's re-test
 //   Ray, ray_setup a ray as its walk needs it: 1/dir, the sign bits, the octant, and which records it walks
-//   ray_step       one pass of a ray's fused loop: the fetch of one 64-byte record and its leaf, child-pair or 4-wide step
+//   ray_step       one pass of a ray's fused loop: the fetch of one 64-byte record and its leaf, child-pair or 4-wide step; what an accepted triangle does
+//                  to the walk is the step's mode (closest, any hit, all hits)
 //   read_shading_triangle, store_surface, store_nearest, triangle_corners   the records' readers and writers
 //
 // Why the frame's walks are not borrowed: v1_trace_ray, k_trace2 and w4_trace_body fix t_min = 0, take rays in the queues' layout (o4.w = t_max, d4.w = a path
@@ -36,6 +37,7 @@
 #pragma once
 #include "trace_kernels.h"
 #include "query.h"
+#include "all_hits.h"
 
 #define RT_QUERY_STACK_LDS 12
 #define RT_QUERY_SPILL_PER_LANE (RT_W4_STACK_MAX - RT_QUERY_STACK_LDS)
@@ -113,12 +115,21 @@ RT_DEV Ray ray_setup(const f3 org, const f3 dir, uint32_t use_wide)
 template <bool ANY_HIT>
 RT_DEV uint32_t ray_entry(const DScene& sc, const Ray& r) { return r.pairs ? sc.entry_ref : (ANY_HIT ? sc.w_sh_entry_ref : sc.w_entry_ref); }
 
+// what a walk does with a triangle it accepts.  RAY_CLOSEST (= false, as k_query_trace<false> names it): t_max is lowered to it and the walk goes on.
+// RAY_ANY_HIT (= true): the walk ends there.  RAY_ALL_HITS: the triangle is handed to the caller's sink, t_max stays, the walk goes on -- an any-hit walk
+// (the shadow rays' tree, stored order) that does not stop; its triangle test is all_hits.h's two-sided one.
+enum { RAY_CLOSEST = 0, RAY_ANY_HIT = 1, RAY_ALL_HITS = 2 };
+struct NoSink { RT_DEV void operator()(uint32_t, float, float) const {} };
+
 // One pass of the fused loop for a lane whose ray is at `ref` (not RT_IDLE_REF): the record's fetch and its step.  `ref` becomes the next reference, or
 // RT_IDLE_REF when the ray has ended.  true: a triangle was accepted in this pass -- hit_u, hit_v and hit_prim are its, t_max its distance (an any-hit walk ends
-// there, so a caller of ANY_HIT that only wants the verdict may hand in copies and drop them).
-template <bool ANY_HIT>
-RT_DEV bool ray_step(const DScene& sc, const Ray& ray, const float t_min, float& t_max, uint32_t& ref, Stack& stack, float& hit_u, float& hit_v, uint32_t& hit_prim)
+// there, so a caller of ANY_HIT that only wants the verdict may hand in copies and drop them).  RAY_ALL_HITS: sink(prim, t, det) for the accepted triangle;
+// hit_u, hit_v, hit_prim and t_max are left alone.
+template <int MODE, class Sink = NoSink>
+RT_DEV bool ray_step(const DScene& sc, const Ray& ray, const float t_min, float& t_max, uint32_t& ref, Stack& stack, float& hit_u, float& hit_v, uint32_t& hit_prim,
+    Sink&& sink = Sink())
 {
+    constexpr bool ANY_HIT = MODE != RAY_CLOSEST;          // which tree, and the 4-wide slots in stored order
     const float INF = __builtin_inff();
     // (read from the kernel's argument here: handed in as a struct of three, the per-lane choice among them became an indexed load from scratch)
     const char* const wide_base = reinterpret_cast<const char*>(ANY_HIT ? sc.wnodes_sh : sc.wnodes);
@@ -150,11 +161,24 @@ RT_DEV bool ray_step(const DScene& sc, const Ray& ray, const float t_min, float&
         {
             const bool last = q0.w != 0.0f;
             float t = 0.0f;
-            accepted = ray_triangle(org, dir, F3(q0.x, q0.y, q0.z), F3(q1.x, q1.y, q1.z), F3(q2.x, q2.y, q2.z), t_min, t_max, hit_u, hit_v, t);
-            if (accepted) { hit_prim = prim; t_max = t; }            // trace_bvh.cl:159-162
-            if (ANY_HIT && accepted) ref = RT_IDLE_REF;              // goto endtrace, :164-167
-            else if (last) pop();
-            else ref = (RT_LEAF_BIT | RT_LEAF_CONT_BIT) | (prim + 1u);
+            if constexpr (MODE == RAY_ALL_HITS)
+            {
+                const float o[3] = {org.x, org.y, org.z}, d[3] = {dir.x, dir.y, dir.z};
+                const float p1[3] = {q0.x, q0.y, q0.z}, e1[3] = {q1.x, q1.y, q1.z}, e2[3] = {q2.x, q2.y, q2.z};
+                float u, v, det;
+                accepted = ah_triangle(o, d, p1, e1, e2, t_min, t_max, &u, &v, &t, &det);
+                if (accepted) sink(prim, t, det);
+                if (last) pop();
+                else ref = (RT_LEAF_BIT | RT_LEAF_CONT_BIT) | (prim + 1u);
+            }
+            else
+            {
+                accepted = ray_triangle(org, dir, F3(q0.x, q0.y, q0.z), F3(q1.x, q1.y, q1.z), F3(q2.x, q2.y, q2.z), t_min, t_max, hit_u, hit_v, t);
+                if (accepted) { hit_prim = prim; t_max = t; }            // trace_bvh.cl:159-162
+                if (ANY_HIT && accepted) ref = RT_IDLE_REF;              // goto endtrace, :164-167
+                else if (last) pop();
+                else ref = (RT_LEAF_BIT | RT_LEAF_CONT_BIT) | (prim + 1u);
+            }
         }
     }
     else if (pairs)

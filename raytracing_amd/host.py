@@ -26,7 +26,7 @@ EXPORTS = [
     "rth_render_upload_gpu_data", "rth_render_setup_seconds", "rth_render_create_with_options",
     "rth_render_set_refittable", "rth_render_refit", "rth_render_set_refit_motion",
     "rth_render_set_objects", "rth_render_pose", "rth_render_pick", "rth_render_integrator_pick", "rth_render_trace",
-    "rth_render_bake", "rth_render_occlusion_image", "rth_render_nearest",
+    "rth_render_bake", "rth_render_occlusion_image", "rth_render_nearest", "rth_render_trace_all", "rth_render_pick_all",
     "rth_scene_set_triangle_objects", "rth_scene_num_objects", "rth_scene_object_name", "rth_scene_num_triangle_objects", "rth_scene_triangle_objects",
 ]
 
@@ -77,6 +77,7 @@ def load():
         "rth_render_pick": (i32, [vp, u32, u32, vp, vp, vp]), "rth_render_integrator_pick": (i32, [vp, u32, u32, vp, vp, vp]), "rth_render_trace": (i32, [vp, vp, u32, i32, vp, vp, vp]),
         "rth_render_bake": (i32, [vp, vp, u32, vp, vp]), "rth_render_occlusion_image": (i32, [vp, vp, vp]),
         "rth_render_nearest": (i32, [vp, vp, u32, vp, vp]),
+        "rth_render_trace_all": (i32, [vp, vp, u32, u32, vp, vp, vp]), "rth_render_pick_all": (i32, [vp, u32, u32, u32, vp, vp, vp, vp]),
         "rth_render_num_nodes": (u32, [vp]), "rth_render_nodes": (vp, [vp]),
         "rth_render_set_aov": (i32, [vp, i32]), "rth_render_resolve": (i32, [vp, vp]),
         "rth_render_set_blue_noise_path": (i32, [vp, cp]),
@@ -404,10 +405,21 @@ class Render:
         self._c(self.lib.rth_render_occlusion_image(self.handle, C.addressof(d), out.ctypes.data))
         return out
 
-    def nearest(self, points):
+    def _surface_dict(self, surf, names, objects):
+        """a types.surface record as pick() reports it: its fields, and `object_name` when the scene was loaded with objects"""
+        out = {k: (surf[k].copy() if surf[k].ndim else surf[k].item()) for k in T.surface.names}
+        if names:
+            prim = out["primitive_id"]
+            if out["object"] == 0xFFFFFFFF and prim < len(objects):
+                out["object"] = int(objects[prim])                      # no objects set on the device: the scene's own table says whose triangle it is
+            out["object_name"] = names[out["object"]] if prim != 0xFFFFFFFF and out["object"] < len(names) else None
+        return out
+
+    def nearest(self, points, signed=False):
         """The nearest surface point to each of the caller's points against the scene as it is posed now (Render::Nearest; points: capi.point_records' rule):
         a list of dicts like pick()'s -- the surface's fields (primitive_id 0xFFFFFFFF and zeros where nothing was found) plus `nearest`, the types.nearest
-        record (position, distance, bc, flags); when the scene was loaded with objects, also `object_name`"""
+        record (position, distance, bc, flags); when the scene was loaded with objects, also `object_name`.  signed=True adds `inside` (inside()'s verdict
+        for the point) and `signed_distance` (the distance, negative inside)."""
         from . import capi
         pts = capi.point_records(points)
         n = len(pts)
@@ -415,17 +427,66 @@ class Render:
         self._c(self.lib.rth_render_nearest(self.handle, pts.ctypes.data if n else None, n, found.ctypes.data, surf.ctypes.data))
         names = self.scene.object_names()
         objects = self.scene.triangle_objects() if names else None
+        within = self.inside(pts["position"]) if signed and n else np.zeros(n, bool)
         result = []
         for i in range(n):
-            out = {k: (surf[i][k].copy() if surf[i][k].ndim else surf[i][k].item()) for k in T.surface.names}
+            out = self._surface_dict(surf[i], names, objects)
             out["nearest"] = found[i]
-            if names:
-                prim = out["primitive_id"]
-                if out["object"] == 0xFFFFFFFF and prim < len(objects):
-                    out["object"] = int(objects[prim])                  # no objects set on the device: the scene's own table says whose triangle it is
-                out["object_name"] = names[out["object"]] if prim != 0xFFFFFFFF and out["object"] < len(names) else None
+            if signed:
+                out["inside"] = bool(within[i])
+                out["signed_distance"] = -float(found[i]["distance"]) if within[i] else float(found[i]["distance"])
             result.append(out)
         return result
+
+    def trace_all(self, rays, max_hits=8, surfaces=False):
+        """Every surface each of the caller's rays crosses in the scene as it is posed now (HIPPathTraceIntegrator::TraceAllHits; rays: types.ray records or
+        float32[n, 8]): (types.ray_hits[n], types.hit[n, max_hits]) -- the counts and the nearest max_hits crossings in ascending (t, primitive_id) order --
+        or (records, hits, types.surface[n, max_hits]) with surfaces=True; max_hits=0: the records alone"""
+        from . import capi
+        r = capi.ray_records(rays)
+        n = len(r)
+        out = np.zeros(n, T.ray_hits)
+        if max_hits == 0:
+            if surfaces:
+                raise RtError("trace_all: surfaces need max_hits > 0")
+            self._c(self.lib.rth_render_trace_all(self.handle, r.ctypes.data if n else None, n, 0, out.ctypes.data, None, None))
+            return out
+        hits = np.zeros((n, max_hits), T.hit)
+        surf = np.zeros((n, max_hits), T.surface) if surfaces else None
+        self._c(self.lib.rth_render_trace_all(self.handle, r.ctypes.data if n else None, n, max_hits, out.ctypes.data, hits.ctypes.data, surf.ctypes.data if surfaces else None))
+        return (out, hits, surf) if surfaces else (out, hits)
+
+    def pick_all(self, x, y, max_hits=8):
+        """Every surface under the centre of pixel (x, y) of the Render's current camera, nearest first (Render::PickAll; the frame is not touched): a list of
+        at most max_hits dicts like pick()'s -- the surface's fields plus `hit` and `exit` (the ray leaves through this surface: it meets the triangle from
+        behind); `object_name` when the scene was loaded with objects.  The door behind the glass is the second entry."""
+        ray, rec = np.zeros(1, T.ray), np.zeros(1, T.ray_hits)
+        hits, surf = np.zeros(max(max_hits, 1), T.hit), np.zeros(max(max_hits, 1), T.surface)
+        self._c(self.lib.rth_render_pick_all(self.handle, x, y, max_hits, ray.ctypes.data, rec.ctypes.data, hits.ctypes.data if max_hits else None,
+                                             surf.ctypes.data if max_hits else None))
+        names = self.scene.object_names()
+        objects = self.scene.triangle_objects() if names else None
+        result = []
+        for j in range(int(rec[0]["stored"])):
+            out = self._surface_dict(surf[j], names, objects)
+            out["ray"], out["hit"] = ray[0], hits[j]
+            out["exit"] = bool((int(rec[0]["flags"]) >> (8 + j)) & 1)
+            result.append(out)
+        return result
+
+    INSIDE_DIRECTION = (0.36, 0.48, 0.8)          # a unit vector whose components are exact in decimal: callers can reproduce inside()'s rays
+
+    def inside(self, points, direction=INSIDE_DIRECTION):
+        """Whether each point (float32[n, 3]) lies inside the scene's surfaces: one ray per point along `direction`, t_min 0, t_max RT_MAX_RENDER_DIST, counted
+        by trace_all(max_hits=0); a point is inside exactly when the ray leaves more surfaces than it enters (count - entering > entering).  A statement
+        about closed, consistently wound surfaces (outward cross(p2 - p1, p3 - p1)): an open sheet or mixed winding gives a count, not a verdict.  bool[n]."""
+        p = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        rays = np.zeros((len(p), 8), np.float32)
+        rays[:, 0:3] = p
+        rays[:, 4:7] = np.asarray(direction, np.float32)
+        rays[:, 7] = 20000.0                                              # RT_MAX_RENDER_DIST
+        rec = self.trace_all(rays, max_hits=0)
+        return (rec["count"].astype(np.int64) - rec["entering"]) > rec["entering"]
 
     def tree_report(self):
         from . import capi

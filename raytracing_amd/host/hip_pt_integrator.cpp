@@ -188,10 +188,10 @@ void HIPPathTraceIntegrator::Pick(std::uint32_t x, std::uint32_t y, rt_ray* ray,
     Check(rt_frame_pick(frame_, x, y, ray, hit, surface));
 }
 
-void HIPPathTraceIntegrator::PickThrough(Camera const& camera, std::uint32_t x, std::uint32_t y, rt_ray* ray, rt_hit* hit, rt_surface* surface)
+rt_ray HIPPathTraceIntegrator::PickRayThrough(Camera const& camera, std::uint32_t x, std::uint32_t y, char const* who) const
 {
-    if (rt_frame_local_rows(frame_) != height_) throw HIPException("HIPPathTraceIntegrator::PickThrough: a tile frame: pick on a frame of the whole image");
-    if (x >= width_ || y >= height_) throw HIPException("HIPPathTraceIntegrator::PickThrough: the pixel is outside the image");
+    if (rt_frame_local_rows(frame_) != height_) throw HIPException(std::string("HIPPathTraceIntegrator::") + who + ": a tile frame: pick on a frame of the whole image");
+    if (x >= width_ || y >= height_) throw HIPException(std::string("HIPPathTraceIntegrator::") + who + ": the pixel is outside the image");
     // rt_frame_pick's ray for this camera: sf_guide_dir (spatial_filter.h, the guide pass's direction, the same binary32 arithmetic on the host), from the
     // camera position, t_min 0, t_max RT_MAX_RENDER_DIST
     rt_camera cam;
@@ -202,6 +202,31 @@ void HIPPathTraceIntegrator::PickThrough(Camera const& camera, std::uint32_t x, 
     rt_ray r;
     r.origin = {cam.position.x, cam.position.y, cam.position.z, 0.0f};
     r.direction = {d[0], d[1], d[2], RT_MAX_RENDER_DIST};
+    return r;
+}
+
+void HIPPathTraceIntegrator::TraceAllHits(rt_ray const* rays, std::size_t count, std::uint32_t max_hits, rt_ray_hits* out, rt_hit* hits, rt_surface* surfaces)
+{
+    if (count > 0xFFFFFFFFull) throw HIPException("HIPPathTraceIntegrator::TraceAllHits: more than 2^32 - 1 rays in one call");
+    Check(rt_scene_trace_all(context_.Get(), rays, (uint32_t)count, max_hits, out, hits, surfaces));
+}
+
+void HIPPathTraceIntegrator::PickAll(std::uint32_t x, std::uint32_t y, std::uint32_t max_hits, rt_ray* ray, rt_ray_hits* out, rt_hit* hits, rt_surface* surfaces)
+{
+    Check(rt_frame_pick_all(frame_, x, y, max_hits, ray, out, hits, surfaces));
+}
+
+void HIPPathTraceIntegrator::PickAllThrough(Camera const& camera, std::uint32_t x, std::uint32_t y, std::uint32_t max_hits, rt_ray* ray, rt_ray_hits* out, rt_hit* hits,
+    rt_surface* surfaces)
+{
+    const rt_ray r = PickRayThrough(camera, x, y, "PickAllThrough");
+    Check(rt_scene_trace_all(context_.Get(), &r, 1u, max_hits, out, hits, surfaces));
+    if (ray) *ray = r;
+}
+
+void HIPPathTraceIntegrator::PickThrough(Camera const& camera, std::uint32_t x, std::uint32_t y, rt_ray* ray, rt_hit* hit, rt_surface* surface)
+{
+    const rt_ray r = PickRayThrough(camera, x, y, "PickThrough");
     rt_hit h;
     rt_surface s;
     Check(rt_scene_trace(context_.Get(), &r, 1u, RT_QUERY_CLOSEST, &h, nullptr, &s));

@@ -121,6 +121,13 @@ public:
     // on it and how far, optionally with the rt_surface there; a count of 2^32 or more is refused.  Throws HIPException with the library's message on a
     // refusal; requests no reset and does not touch the frame.
     void NearestPoints(rt_point const* points, std::size_t count, rt_nearest* out, rt_surface* surfaces);
+    // All hits (rt_scene_trace_all / rt_frame_pick_all): every surface each ray crosses -- the counts in out, the nearest max_hits crossings
+    // in hits and surfaces (max_hits records per ray; either may be null).  PickAll: the ray through the centre of pixel (x, y) of the frame's current camera;
+    // PickAllThrough: the same for a camera the frame has not been given, as PickThrough.  All throw HIPException with the library's message on a refusal; none
+    // requests a reset or touches the frame.
+    void TraceAllHits(rt_ray const* rays, std::size_t count, std::uint32_t max_hits, rt_ray_hits* out, rt_hit* hits, rt_surface* surfaces);
+    void PickAll(std::uint32_t x, std::uint32_t y, std::uint32_t max_hits, rt_ray* ray, rt_ray_hits* out, rt_hit* hits, rt_surface* surfaces);
+    void PickAllThrough(Camera const& camera, std::uint32_t x, std::uint32_t y, std::uint32_t max_hits, rt_ray* ray, rt_ray_hits* out, rt_hit* hits, rt_surface* surfaces);
     rt_frame* GetFrame() const { return frame_; }
 
 protected:
@@ -143,6 +150,8 @@ protected:
 private:
     void Check(int rc) const;
     void SyncOptions();
+    // rt_frame_pick's ray for a camera the frame has not been given; throws (naming `who`) for a tile frame or a pixel outside the image
+    rt_ray PickRayThrough(Camera const& camera, std::uint32_t x, std::uint32_t y, char const* who) const;
 
     HIPContext& context_;
     rt_frame* frame_ = nullptr;

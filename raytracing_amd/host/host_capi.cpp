@@ -266,6 +266,14 @@ int rth_render_trace(void* r, const rt_ray* rays, uint32_t n, int any_hit, rt_hi
 {
     return guard([&]() { ((rt::Render*)r)->TraceRays(rays, n, any_hit != 0, hits, occluded, surfaces); return 0; }, 1);
 }
+int rth_render_trace_all(void* r, const rt_ray* rays, uint32_t n, uint32_t max_hits, rt_ray_hits* out, rt_hit* hits, rt_surface* surfaces)
+{
+    return guard([&]() { ((rt::Render*)r)->TraceAllHits(rays, n, max_hits, out, hits, surfaces); return 0; }, 1);
+}
+int rth_render_pick_all(void* r, uint32_t x, uint32_t y, uint32_t max_hits, rt_ray* ray, rt_ray_hits* out, rt_hit* hits, rt_surface* surfaces)
+{
+    return guard([&]() { ((rt::Render*)r)->PickAll(x, y, max_hits, ray, out, hits, surfaces); return 0; }, 1);
+}
 int rth_render_bake(void* r, const void* points, uint32_t n, const rt_bake_desc* desc, rt_bake_result* out)
 {
     return guard([&]() { if (!desc) throw rt::HIPException("rth_render_bake: desc is NULL"); ((rt::Render*)r)->BakeOcclusion(points, n, *desc, out); return 0; }, 1);

@@ -39,6 +39,8 @@ int main(int argc, char** argv)
         std::vector<ObjectStep> object_steps;   // --object_step i,dx,dy,dz (repeatable): frame k poses object i by the translation k * (dx,dy,dz)
         struct PickAt { unsigned x, y; };
         std::vector<PickAt> picks;              // --pick x,y (repeatable): after the scene is uploaded and posed, print what lies under that pixel
+        std::vector<PickAt> picks_all;          // --pick_all x,y (repeatable): every surface under that pixel, nearest first, one line per surface
+        bool nearest_signed = false;            // --signed 1: --nearest also prints whether the point is inside (exits outnumber entries along (0.36, 0.48, 0.8))
         std::string ao_out;                     // --ao out.pfm: after the scene is uploaded and posed, write the ambient occlusion image of the camera (grey, RGB equal)
         rt_bake_desc ao = {64u, 0u, 0u, 1e-3f, 1.0f};   // --ao_samples n --ao_radius r --ao_bias b
         std::vector<rt_point> nearest_points;   // --nearest x,y,z[,r] (repeatable): after the scene is uploaded and posed, print the nearest surface point (within r)
@@ -124,6 +126,14 @@ int main(int argc, char** argv)
                 picks.push_back(p);
                 scene_options |= rt::Scene::kObjects;
             }
+            else if (!strcmp(argv[i], "--pick_all"))
+            {
+                PickAt p;
+                if (sscanf(next(), "%u,%u", &p.x, &p.y) != 2) { std::cerr << "--pick_all wants x,y (image coordinates)\n"; return 2; }
+                picks_all.push_back(p);
+                scene_options |= rt::Scene::kObjects;
+            }
+            else if (!strcmp(argv[i], "--signed")) nearest_signed = atoi(next()) != 0;
             else if (!strcmp(argv[i], "--nearest"))
             {
                 rt_point q;
@@ -167,6 +177,8 @@ int main(int argc, char** argv)
                              "  --ao out.pfm --ao_samples n --ao_radius r [--ao_bias b] writes the exact ambient occlusion image of the camera once the scene is uploaded\n"
                              "  and posed: per pixel the share of n cosine-weighted rays (a power of two, 16 .. 4096; default 64) from the first hit that meet nothing within r\n"
                              "  (default 1), 1 where the pixel sees nothing; traced and baked on the device (rt_scene_bake_buffer); one GPU only\n"
+                             "  --pick_all x,y (repeatable) prints every surface under that pixel, nearest first, one line per surface; --signed 1 makes --nearest print whether\n"
+                             "    the point is inside (more exits than entries along (0.36, 0.48, 0.8))\n"
                              "  --nearest x,y,z[,r] (repeatable) prints the nearest surface point to that point (within r) once the scene is uploaded and posed: primitive,\n"
                              "  distance, position, feature (face, edge or vertex), material and object (index and name); one GPU only\n";
                 return 0;
@@ -203,6 +215,11 @@ int main(int argc, char** argv)
         if (!object_steps.empty() && (frames == 0 || gpus > 1 || tiled_path))
         {
             std::cerr << "--object_step needs --frames n and one GPU\n";
+            return 2;
+        }
+        if (!picks_all.empty() && (gpus > 1 || tiled_path))
+        {
+            std::cerr << "--pick_all needs one GPU\n";
             return 2;
         }
         if (!picks.empty() && (gpus > 1 || tiled_path))
@@ -314,6 +331,26 @@ int main(int argc, char** argv)
                 std::cout << ((s.flags & 2u) ? " (back face)" : "") << std::endl;
             }
         };
+        // --pick_all: one line per surface under the pixel, nearest first (rt_scene_trace_all through Render::PickAll); the object as --pick names it
+        auto print_picks_all = [&]()
+        {
+            for (const PickAt& p : picks_all)
+            {
+                rt_ray_hits rec; rt_hit h[RT_ALL_HITS_MAX]; rt_surface s[RT_ALL_HITS_MAX];
+                render.PickAll(p.x, p.y, RT_ALL_HITS_MAX, nullptr, &rec, h, s);
+                std::cout << "pick_all " << p.x << "," << p.y << ": " << rec.count << " surfaces, " << rec.entering << " entered" << std::endl;
+                for (std::uint32_t j = 0; j < rec.stored; ++j)
+                {
+                    std::uint32_t object = s[j].object;
+                    if (object == RT_INVALID_ID && s[j].primitive_id < scene.GetTriangleObjects().size()) object = scene.GetTriangleObjects()[s[j].primitive_id];
+                    std::cout << "  " << j << ": primitive " << s[j].primitive_id << " t " << s[j].t << " position " << s[j].position[0] << " " << s[j].position[1] << " "
+                              << s[j].position[2] << " material " << s[j].mtl_index << " object ";
+                    if (object < scene.GetObjectNames().size()) std::cout << object << " " << scene.GetObjectNames()[object];
+                    else std::cout << "none";
+                    std::cout << (((rec.flags >> (RT_RAY_HITS_EXIT_SHIFT + j)) & 1u) ? " (exit)" : "") << std::endl;
+                }
+            }
+        };
         // --nearest: one line per point (rt_scene_nearest through Render::Nearest); the object as --pick names it
         auto print_nearest = [&]()
         {
@@ -321,6 +358,18 @@ int main(int argc, char** argv)
             std::vector<rt_nearest> found(nearest_points.size());
             std::vector<rt_surface> surf(nearest_points.size());
             render.Nearest(nearest_points.data(), nearest_points.size(), found.data(), surf.data());
+            std::vector<rt_ray_hits> crossed(nearest_points.size());
+            if (nearest_signed)
+            {
+                std::vector<rt_ray> rays(nearest_points.size());
+                for (size_t i = 0; i < rays.size(); ++i)
+                {
+                    const rt_point& q = nearest_points[i];
+                    rays[i].origin = {q.position[0], q.position[1], q.position[2], 0.0f};
+                    rays[i].direction = {0.36f, 0.48f, 0.8f, RT_MAX_RENDER_DIST};
+                }
+                render.TraceAllHits(rays.data(), rays.size(), 0u, crossed.data(), nullptr, nullptr);
+            }
             for (size_t i = 0; i < found.size(); ++i)
             {
                 const rt_point& q = nearest_points[i];
@@ -334,7 +383,9 @@ int main(int argc, char** argv)
                           << " feature " << feature[(f.flags >> RT_NEAREST_FEATURE_SHIFT) & 3u] << " material " << surf[i].mtl_index << " object ";
                 if (object < scene.GetObjectNames().size()) std::cout << object << " " << scene.GetObjectNames()[object];
                 else std::cout << "none";
-                std::cout << ((f.flags & RT_NEAREST_BACK_SIDE) ? " (back side)" : "") << std::endl;
+                std::cout << ((f.flags & RT_NEAREST_BACK_SIDE) ? " (back side)" : "");
+                if (nearest_signed) std::cout << " inside " << (crossed[i].count - crossed[i].entering > crossed[i].entering ? 1 : 0);
+                std::cout << std::endl;
             }
         };
         // --ao: Render::OcclusionImage of the camera as it stands, written as a grey PFM
@@ -391,6 +442,7 @@ int main(int argc, char** argv)
                       << " s: " << df * 1e3 / frames << " ms per frame" << std::endl;
             if (!out.empty()) WritePFM(out.c_str(), img, width, height);     // the last frame's resolved (filtered), tone-mapped image
             print_picks();
+            print_picks_all();
             print_nearest();
             write_ao();
             return 0;
@@ -431,6 +483,7 @@ int main(int argc, char** argv)
         double rays = (double)st.closest_rays + (double)st.shadow_rays;
         std::cout << spp << " spp in " << dt << " s, " << rays / dt / 1e6 << " Mrays/s" << std::endl;
         print_picks();
+        print_picks_all();
         print_nearest();
         write_ao();
         if (!out.empty() && (filter_iterations >= 0 || temporal_iterations >= 0))
