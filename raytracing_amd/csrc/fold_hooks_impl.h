@@ -52,14 +52,14 @@ static int fold_probe_enqueue(rt_frame* f, FoldAdapt& a)
         {
             const uint32_t in = bounce & 1u;
             if (rt_intersect(p, bounce) != RT_OK) { rc = RT_ERROR; break; }
-            if (!back(a.probe_block(sample, bounce, 0), p->p->o4[in], q) || !back(a.probe_block(sample, bounce, 1), p->p->d4[in], q) ||
-                !back(a.probe_block(sample, bounce, 2), p->p->hits, q)) { rc = RT_ERROR; break; }
+            if (!back(a.probe_block(sample, bounce, 0), p->ps[0].o4[in], q) || !back(a.probe_block(sample, bounce, 1), p->ps[0].d4[in], q) ||
+                !back(a.probe_block(sample, bounce, 2), p->ps[0].hits, q)) { rc = RT_ERROR; break; }
             if (rt_shade(p, bounce) != RT_OK) { rc = RT_ERROR; break; }
-            if (!back(a.probe_block(sample, bounce, 3), p->p->sh_o4[in], q) || !back(a.probe_block(sample, bounce, 4), p->p->sh_d4[in], q)) { rc = RT_ERROR; break; }
+            if (!back(a.probe_block(sample, bounce, 3), p->ps[0].sh_o4[in], q) || !back(a.probe_block(sample, bounce, 4), p->ps[0].sh_d4[in], q)) { rc = RT_ERROR; break; }
             if (rt_intersect_shadow(p, bounce) != RT_OK) rc = RT_ERROR;
         }
         // the sample's counters: queue[b] and shadow[b] of every bounce are still there (k_raygen resets them for the NEXT sequence)
-        if (rc == RT_OK && !back(a.probe_counters(sample), p->p->counters, sizeof(DCounters))) rc = RT_ERROR;
+        if (rc == RT_OK && !back(a.probe_counters(sample), p->ps[0].counters, sizeof(DCounters))) rc = RT_ERROR;
         if (rc == RT_OK && rt_advance_sample(p) != RT_OK) rc = RT_ERROR;
     }
     if (rc == RT_OK && hipEventRecord(a.probe_done, ctx->stream) != hipSuccess) rc = RT_ERROR;

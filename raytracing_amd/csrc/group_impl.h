@@ -348,7 +348,7 @@ int rt_group_gather_radiance(rt_group* g, rt_frame* const* frames, int root, flo
             if (ensure(g, &m.recv, &m.recv_elems, (size_t)stride * 2 * (size_t)g->nranks) != RT_OK) return RT_ERROR;
             if (ensure(g, &m.image, &m.image_elems, (size_t)width * height) != RT_OK) return RT_ERROR;
         }
-        if (flush_log_keep(f) != RT_OK) return gfail(g, std::string("rt_group_gather_radiance: ") + f->ctx->error);
+        if (flush_log_keep(f, f->ps[0]) != RT_OK) return gfail(g, std::string("rt_group_gather_radiance: ") + f->ctx->error);
         if (f->n_local)
         {
             hipError_t e = hipMemcpyAsync(m.send, f->radiance, (size_t)f->n_local * sizeof(float4), hipMemcpyDeviceToDevice, f->ctx->stream);
@@ -403,7 +403,7 @@ int rt_group_denoise(rt_group* g, rt_frame* const* frames, int root, float* host
         if (hipSetDevice(m.device) != hipSuccess) return gfail(g, "rt_group_denoise: hipSetDevice failed");
         if (ensure(g, &m.send, &m.send_elems, (size_t)stride * 2) != RT_OK) return RT_ERROR;
         if (m.rank == root && ensure(g, &m.recv, &m.recv_elems, (size_t)stride * 2 * (size_t)g->nranks) != RT_OK) return RT_ERROR;
-        if (flush_log_keep(f) != RT_OK) return gfail(g, std::string("rt_group_denoise: ") + f->ctx->error);
+        if (flush_log_keep(f, f->ps[0]) != RT_OK) return gfail(g, std::string("rt_group_denoise: ") + f->ctx->error);
         if (f->n_local)
         {
             float* send = (float*)m.send;

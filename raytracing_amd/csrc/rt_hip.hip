@@ -201,6 +201,7 @@ struct PathPipe
     uint32_t prev_bounces = 0;
     uint32_t fold_accumulates = 0;     // the sequence in flight is a 2nd+ chunk of its batch: its counters ADD to last_*
     bool shadow_pending = false;       // rt_shade issued, rt_intersect_shadow not yet
+    uint64_t batch_paths() const { return (uint64_t)chunk_count * (cur_slots ? cur_slots : 1u); }   // paths of the batch in flight (a trace launch's size class)
     // The per-path buffers for `paths` paths in flight and a log of `log_elems` entries, in the order they are allocated (alloc_path_buffers /
     // free_path_buffers; no arguments: all of them, for the free).  The queues carry 4 elements of padding, the slow lists 64, the log 16 bytes;
     // ovf_slot exists in the compact layout only.  RT_PATH_FIXED_BYTES is this list without the log and ovf_slot, per path.
@@ -272,7 +273,6 @@ struct rt_frame
     // case.  More pipes let chunks overlap; measured on MI355X this does NOT pay (a trace launch costs ~0.8 ms
     // beyond its rays whatever shares the machine with it: profiles/r02_pipelines_sweep.log), so the default is 1.
     PathPipe ps[RT_MAX_PIPES];
-    PathPipe* p = &ps[0];          // the pipe the stage functions work on
     uint32_t pipelines = 1;        // RT_OPT_PIPELINES: pipes rt_integrate may use
     uint32_t stage_pipes = 1;      // RT_OPT_STAGE_PIPES: ONE sample per pixel in flight (the stage API, rt_integrate(f, 1): the reference's frame-by-frame
                                    // pattern) is cut into this many chunks, each on a pipe (stream) of its own: every launch of that pattern is
@@ -328,7 +328,6 @@ struct rt_frame
     bool log_full_forced = false;  // a batch ran its pool dry: this frame stays on the full layout (until bounces / scene change)
     uint32_t fallback_limit_mb = 0;   // ... within the bytes the compact layout held (chunk_plan)
     uint32_t log_fallbacks = 0;    // batches repeated in the full layout
-    bool fused = false;            // inside rt_integrate: whole samples, nothing reads the radiance between stages
     uint32_t trace_blocks;       // v1 grid
     uint32_t trace_variant = 5;  // RT_OPT_TRACE_VARIANT (5 = auto)
     uint64_t small_launch_paths = 3000000ull;   // RT_OPT_SMALL_LAUNCH_PATHS: launches of fewer rays run k_trace_w4 in chunk mode
@@ -341,11 +340,8 @@ struct rt_frame
     uint32_t select_form_box = 0;      // RT_OPT_TRACE_SELECT_FORM_BOX: every ray takes the select-form slab test
     uint32_t trace_tune = 0;           // RT_OPT_TRACE_TUNE: k_trace2 loop thresholds (0 = defaults)
     uint32_t timeline = 0;             // rt_frame_debug_timeline armed: k_trace_w4<closest> records its launch timeline
-    uint32_t timeline_bounce = 0;
     uint32_t overlap_shadow = 1;       // RT_OPT_OVERLAP_SHADOW
-    bool side_active = false;          // shadow traces go to PathPipe::side (set per stage call: side_on())
-    // where the next trace launch goes (set by rt_intersect / rt_intersect_shadow)
-    hipStream_t tl_stream = nullptr; uint2* tl_spill = nullptr; uint32_t* tl_slow_list = nullptr; uint32_t tl_flavour = 0;
+    bool side_active = false;          // shadow traces go to PathPipe::side (what the last shade step decided, side_on(): it holds until that bounce's shadow trace)
     uint32_t shade_partition = 3;      // RT_OPT_SHADE_PARTITION: bit 0: k_shade sorts each block's entries hits first / misses last; bit 1: groups its output rays by octant
     uint32_t debug_alloc_limit = 0;    // RT_OPT_DEBUG_ALLOC_LIMIT: allocations above this many samples in flight fail
     // integrator state
@@ -377,6 +373,9 @@ struct rt_frame
                 {(void**)&prev_radiance, n * sizeof(float4), true}, {(void**)&prev_depth, n * sizeof(float), true}};
     }
 };
+
+// the tile's pixels, at least 1: a rank may hold no row of a small image, and buffers, grids and chunks are sized for one pixel then
+static uint32_t tile_pixels(const rt_frame* f) { return f->n_local ? f->n_local : 1u; }
 
 static int sync_frame_streams(rt_frame* f);
 static void ahead_discard(rt_frame* f);      // RT_OPT_SAMPLES_AHEAD: whatever was traced ahead is dropped (reset, another camera, another option, a peek)
@@ -1160,7 +1159,7 @@ size_t bytes_per_path(const rt_frame* f, uint32_t slots)
 // samples inside 32-bit path ids and the per-path buffers under 144 GiB (half of the 288 GB of HBM)
 uint32_t auto_slots(const rt_frame* f)
 {
-    const uint64_t n = f->n_local ? f->n_local : 1;
+    const uint64_t n = tile_pixels(f);
     const uint64_t max_paths = 0xFFFFFFF0ull;
     uint64_t by_memory = (144ull << 30) / (n * bytes_per_path(f, 1024u));        // the compact layout, if this frame may use it ...
     if (by_memory < 8u) by_memory = (144ull << 30) / (n * bytes_per_path(f, 1u));  // ... which takes 8 samples in flight
@@ -1190,7 +1189,7 @@ uint32_t slot_cap(const rt_frame* f)
 //    (multiples of 4096 pixels), still dealt round-robin to the pipes.
 void chunk_plan(const rt_frame* f, uint32_t slots, uint32_t& n_pipes, uint32_t& chunk_pixels)
 {
-    const uint64_t n = f->n_local ? f->n_local : 1;
+    const uint64_t n = tile_pixels(f);
     slots = slots ? slots : 1u;
     n_pipes = 1;
     if (f->pipelines > 1 && slots >= 2 && n * slots >= 4000000ull) n_pipes = f->pipelines < RT_MAX_PIPES ? f->pipelines : RT_MAX_PIPES;
@@ -1232,7 +1231,6 @@ int alloc_path_buffers(rt_frame* f, uint32_t slots)
         return fail(ctx, "out of device memory for the per-path buffers (RT_OPT_DEBUG_ALLOC_LIMIT)");
     f->slots = slots ? slots : 1u;
     chunk_plan(f, f->slots, f->n_pipes, f->chunk_pixels);
-    f->p = &f->ps[0];
     uint64_t paths = (uint64_t)f->chunk_pixels * f->slots;
     if (paths > 0xFFFFFFF0ull) return fail(ctx, "samples in flight x tile pixels exceeds the 32-bit path-id range");
     f->log_stride = (uint32_t)paths;
@@ -1324,16 +1322,15 @@ int ensure_pipe_resources(rt_frame* f, uint32_t count)
     return RT_OK;
 }
 
-int flush_log(rt_frame* f, bool keep_open = false);
-int ensure_whole_tile(rt_frame* f);
+int flush_log(rt_frame* f, PathPipe& p, bool keep_open = false);
 
-// The main stream of the current pipe waits for the shadow trace that last used shadow queue `q` (rt_integrate runs
-// those on PathPipe::side); nothing to do when none is outstanding.
-int wait_shadow(rt_frame* f, uint32_t q)
+// The pipe's main stream waits for the shadow trace that last used its shadow queue `q` (those run on PathPipe::side);
+// nothing to do when none is outstanding.
+int wait_shadow(rt_frame* f, PathPipe& p, uint32_t q)
 {
-    if (!f->p->shadow_in_flight[q]) return RT_OK;
-    HIPCHK(f->ctx, hipStreamWaitEvent(f->p->stream, f->p->ev_shadow[q], 0));
-    f->p->shadow_in_flight[q] = false;
+    if (!p.shadow_in_flight[q]) return RT_OK;
+    HIPCHK(f->ctx, hipStreamWaitEvent(p.stream, p.ev_shadow[q], 0));
+    p.shadow_in_flight[q] = false;
     return RT_OK;
 }
 
@@ -1352,7 +1349,7 @@ int ensure_slots(rt_frame* f, uint32_t want)
     if (want <= f->slots && 2u * (f->max_bounces + 1u) <= f->log_entries && f->chunk_pixels == chunk_for(f, f->slots) &&
         (f->log_ovf_blocks != 0u) == log_is_compact(f, f->slots))
         return RT_OK;
-    if (flush_log(f) != RT_OK || join_pipes(f) != RT_OK) return RT_ERROR;
+    if (flush_log(f, f->ps[0]) != RT_OK || join_pipes(f) != RT_OK) return RT_ERROR;
     HIPCHK(f->ctx, hipStreamSynchronize(f->ctx->stream));
     uint32_t keep = f->slots < cap ? f->slots : cap;
     uint32_t n = want > keep ? want : keep;
@@ -1367,11 +1364,11 @@ int ensure_slots(rt_frame* f, uint32_t want)
     return RT_OK;
 }
 
-// the radiance log of the current pipe as the kernels see it
-DLog dlog(const rt_frame* f)
+// the radiance log of a pipe as the kernels see it
+DLog dlog(const rt_frame* f, const PathPipe& p)
 {
     DLog L;
-    L.rlog = f->p->rlog; L.cnt = f->p->cnt; L.ovf_slot = f->log_ovf_blocks ? f->p->ovf_slot : nullptr;
+    L.rlog = p.rlog; L.cnt = p.cnt; L.ovf_slot = f->log_ovf_blocks ? p.ovf_slot : nullptr;
     L.stride = f->log_stride; L.inline_entries = f->log_inline; L.ovf_blocks = f->log_ovf_blocks;
     return L;
 }
@@ -1381,26 +1378,26 @@ DLog dlog(const rt_frame* f)
 // that is large enough in SLOTS): re-allocate for one sample in flight, which the caller has checked does fit.
 int ensure_whole_tile(rt_frame* f)
 {
-    if (f->chunk_pixels >= (f->n_local ? f->n_local : 1u)) return RT_OK;
-    if (f->p->cur_slots != 0) return fail(f->ctx, "rt_generate_rays: the previous sample was not advanced (rt_advance_sample)");
-    if (flush_log(f) != RT_OK || join_pipes(f) != RT_OK) return RT_ERROR;
+    if (f->chunk_pixels >= tile_pixels(f)) return RT_OK;
+    if (f->ps[0].cur_slots != 0) return fail(f->ctx, "rt_generate_rays: the previous sample was not advanced (rt_advance_sample)");
+    if (flush_log(f, f->ps[0]) != RT_OK || join_pipes(f) != RT_OK) return RT_ERROR;
     HIPCHK(f->ctx, hipStreamSynchronize(f->ctx->stream));
     return alloc_path_buffers(f, 1);
 }
 
-// Adds the logged contributions of the batch in flight to the running sum.
-int flush_log(rt_frame* f, bool keep_open)
+// Adds the logged contributions of the batch in flight on pipe `p` to the running sum.
+int flush_log(rt_frame* f, PathPipe& p, bool keep_open)
 {
     rt_ctx* ctx = f->ctx;
-    if (f->p->cur_slots == 0 || f->n_local == 0 || f->p->chunk_count == 0) { f->p->cur_slots = 0; return RT_OK; }
-    if (f->p->shadow_pending)
+    if (p.cur_slots == 0 || f->n_local == 0 || p.chunk_count == 0) { p.cur_slots = 0; return RT_OK; }
+    if (p.shadow_pending)
         return fail(ctx, "radiance requested between rt_shade and rt_intersect_shadow (direct samples still tentative)");
-    if (wait_shadow(f, 0) != RT_OK || wait_shadow(f, 1) != RT_OK) return RT_ERROR;   // their verdicts are in the log
-    uint32_t blocks = (f->p->chunk_count + 255u) / 256u;
-    hipLaunchKernelGGL(k_flush, dim3(blocks), dim3(256), 0, f->p->stream, f->radiance + f->p->chunk_base, dlog(f),
-        f->p->chunk_count, f->p->cur_slots, f->chunk_pixels, keep_open && f->log_ovf_blocks != 0u ? 1u : 0u, 0u);
+    if (wait_shadow(f, p, 0) != RT_OK || wait_shadow(f, p, 1) != RT_OK) return RT_ERROR;   // their verdicts are in the log
+    uint32_t blocks = (p.chunk_count + 255u) / 256u;
+    hipLaunchKernelGGL(k_flush, dim3(blocks), dim3(256), 0, p.stream, f->radiance + p.chunk_base, dlog(f, p),
+        p.chunk_count, p.cur_slots, f->chunk_pixels, keep_open && f->log_ovf_blocks != 0u ? 1u : 0u, 0u);
     if (hipGetLastError() != hipSuccess) return fail(ctx, "k_flush launch failed");
-    f->p->cur_slots = 0;
+    p.cur_slots = 0;
     return RT_OK;
 }
 
@@ -1426,27 +1423,22 @@ namespace
 {
 // Mid-sample read (stage API / debugging): apply what has been logged so far but
 // keep the sample open -- later contributions append again from entry 0.
-int flush_log_keep(rt_frame* f)
+int flush_log_keep(rt_frame* f, PathPipe& p)
 {
-    uint32_t keep = f->p->cur_slots;
-    int rc = flush_log(f, true);
-    f->p->cur_slots = keep;
+    uint32_t keep = p.cur_slots;
+    int rc = flush_log(f, p, true);
+    p.cur_slots = keep;
     return rc;
 }
 
-// The stage API over every pipe that holds a chunk of its sample (RT_OPT_STAGE_PIPES; one pipe is the plain case): `body` runs with f->p on
-// each of them in turn.
+// The stage API over every pipe that holds a chunk of its sample (RT_OPT_STAGE_PIPES; one pipe is the plain case): `body` is handed each
+// of them in turn.
 template <class F>
 int for_stage_pipes(rt_frame* f, F&& body)
 {
     int rc = RT_OK;
     const uint32_t n = f->stage_chunks ? f->stage_chunks : 1u;
-    for (uint32_t i = 0; i < n && rc == RT_OK; ++i)
-    {
-        f->p = &f->ps[i];
-        rc = body();
-    }
-    f->p = &f->ps[0];
+    for (uint32_t i = 0; i < n && rc == RT_OK; ++i) rc = body(f->ps[i]);
     return rc;
 }
 
@@ -1455,12 +1447,64 @@ int flush_stage(rt_frame* f, bool keep = false)
 {
     if (f->deferred.active && deferred_materialize(f) != RT_OK) return RT_ERROR;    // RT_OPT_FRAME_KERNEL: the recorded stages run after all
     const uint32_t n = f->stage_chunks ? f->stage_chunks : 1u;
-    if (for_stage_pipes(f, [&]() { return keep ? flush_log_keep(f) : flush_log(f); }) != RT_OK) return RT_ERROR;
+    if (for_stage_pipes(f, [&](PathPipe& p) { return keep ? flush_log_keep(f, p) : flush_log(f, p); }) != RT_OK) return RT_ERROR;
     return n > 1 ? join_pipes(f) : RT_OK;
 }
 
 // RT_OPT_FRAME_KERNEL = 255 measures again: another workload, or another grid
 void fk_auto_restart(rt_frame* f) { f->fk_auto.frames = 0; f->fk_auto.timing = -1; f->fk_auto.decided = false; f->fk_auto.use_kernel = false; }
+
+// RT_OPT_FRAME_KERNEL = 255, at the start of a stage-API sample of the whole tile on one pipe: frames 0 - 3 warm up (two each way), frames 4 - 19 alternate
+// stage kernels / k_frame and are timed; once the last timed frame's events have completed, the faster way stays (until the next scene upload)
+void fk_auto_begin_frame(rt_frame* f)
+{
+    rt_ctx* ctx = f->ctx;
+    auto& m = f->fk_auto;
+    if (m.scene != ctx->scene_uploads) { m.frames = 0; m.timing = -1; m.decided = false; m.use_kernel = false; m.scene = ctx->scene_uploads; }
+    m.timing = -1;
+    m.skip = false;
+    if (!m.decided)
+    {
+        const int k = m.frames;
+        if (k >= 20 && hipEventQuery(m.ev[15][1]) == hipSuccess)
+        {
+            m.ms_stage = m.ms_kernel = 0.0f;
+            bool ok = true;
+            for (int i = 0; i < 16 && ok; ++i)
+            {
+                float t = 0.0f;
+                ok = hipEventElapsedTime(&t, m.ev[i][0], m.ev[i][1]) == hipSuccess;
+                ((i & 1) ? m.ms_kernel : m.ms_stage) += t;
+            }
+            if (!ok) (void)hipGetLastError();
+            m.decided = true;
+            m.use_kernel = ok && m.ms_kernel < m.ms_stage;
+        }
+        else if (k >= 4 && k < 20 && ctx->scene.adapt && (ctx->scene.adapt->state == FoldAdapt::ARMED || ctx->scene.adapt->state == FoldAdapt::PROBING || ctx->scene.adapt->state == FoldAdapt::COMPUTING))
+        {
+            //  a fold adaptation is under way -- probe launches on this stream, a fold swapped mid-window: such a frame is not one
+            // of the sixteen that are compared (it runs through the stage kernels, untimed; the schedule goes on once the folds have settled)
+            m.skip = true;
+        }
+        else if (k >= 4 && k < 20)
+        {
+            m.timing = k - 4;
+            bool ok = true;
+            for (hipEvent_t& e : m.ev[m.timing]) if (!e) ok = ok && hipEventCreate(&e) == hipSuccess;
+            if (!ok || hipEventRecord(m.ev[m.timing][0], ctx->stream) != hipSuccess) { (void)hipGetLastError(); m.decided = true; m.use_kernel = false; m.timing = -1; }
+        }
+        if (!m.decided && !m.skip) ++m.frames;
+    }
+    if (m.decided) m.frames = 1 << 20;          // (frame_kernel_eligible reads `decided`; keep frames - 1 out of the schedule's range)
+}
+
+// ... and at its end: the closing event of a frame that is being timed
+void fk_auto_end_frame(rt_frame* f)
+{
+    if (f->fk_auto.timing < 0) return;
+    (void)hipEventRecord(f->fk_auto.ev[f->fk_auto.timing][1], f->ctx->stream);
+    f->fk_auto.timing = -1;
+}
 
 // An option that decides the per-path layout changes (rt_set_option).  Nothing of this frame is in flight any more -- its log replayed, its pipes joined
 // where the change moves chunks between them (`join`), the context's stream drained -- then `change` applies the new value and the buffers are laid out again.
@@ -1469,7 +1513,7 @@ void fk_auto_restart(rt_frame* f) { f->fk_auto.frames = 0; f->fk_auto.timing = -
 //   undo    after a layout that failed: puts the old value back, and the buffers come back for the samples they held (nullptr: the new value stays)
 int relayout(rt_frame* f, bool join, bool grow, const std::function<int()>& change, const std::function<void()>& undo = nullptr)
 {
-    if (flush_log(f) != RT_OK || (join && join_pipes(f) != RT_OK)) return RT_ERROR;
+    if (flush_log(f, f->ps[0]) != RT_OK || (join && join_pipes(f) != RT_OK)) return RT_ERROR;
     HIPCHK(f->ctx, hipStreamSynchronize(f->ctx->stream));
     const uint32_t old_slots = f->slots;
     const int slots = change();
@@ -1509,7 +1553,7 @@ static int create_frame(rt_ctx* ctx, const rt_frame_desc* fd, rt_frame** out, hi
     f->tile.local_rows = rows;
     if ((uint64_t)rows * fd->width > 0x7FFFFFFFull) { delete f; return fail(ctx, "rt_frame_create: tile too large"); }
     f->n_local = rows * fd->width;
-    size_t n = f->n_local ? f->n_local : 1;
+    const size_t n = tile_pixels(f);
     f->trace_blocks = (uint32_t)ctx->prop.multiProcessorCount * 12u;
     f->trace_blocks = (f->trace_blocks + 7u) & ~7u;
     f->ps[0].stream = borrowed_main_stream;              // (NULL: ensure_pipe_resources gives pipe 0 the context's stream)
@@ -1650,7 +1694,7 @@ int rt_set_option(rt_frame* f, int option, uint32_t value)
     case RT_OPT_STAGE_PIPES:
         if (value == 0 || value > RT_MAX_PIPES) return fail(f->ctx, "rt_set_option: stage pipes must be 1..RT_MAX_PIPES");
         if (value == f->stage_pipes) return RT_OK;
-        if (f->p->cur_slots != 0) return fail(f->ctx, "rt_set_option: RT_OPT_STAGE_PIPES cannot change while a sample is in flight (rt_advance_sample first)");
+        if (f->ps[0].cur_slots != 0) return fail(f->ctx, "rt_set_option: RT_OPT_STAGE_PIPES cannot change while a sample is in flight (rt_advance_sample first)");
         return relayout(f, true, false, [&]() { if (ensure_pipe_resources(f, value) != RT_OK) return -1; f->stage_pipes = value; f->stage_chunks = 1; return f->slots == 1 ? 1 : 0; });
     case RT_OPT_PATH_STATE_LIMIT_MB:
     {
@@ -1702,7 +1746,7 @@ namespace
 struct KernelSpan
 {
     rt_frame* f; int cls; hipStream_t st; hipEvent_t a = nullptr, b = nullptr;
-    KernelSpan(rt_frame* f_, int cls_, hipStream_t stream = nullptr) : f(f_), cls(cls_), st(stream ? stream : f_->p->stream)
+    KernelSpan(rt_frame* f_, int cls_, hipStream_t stream) : f(f_), cls(cls_), st(stream)
     {
         if (!f->profile) return;
         auto get = [&]() { hipEvent_t e = nullptr; if (!f->event_pool.empty()) { e = f->event_pool.back(); f->event_pool.pop_back(); } else (void)hipEventCreate(&e); return e; };
@@ -1728,70 +1772,91 @@ struct KernelSpan
 
 namespace
 {
-// k_trace2: separate wave-uniform loops (trace_kernels.h).  One-wave blocks; the persistent grid is sized to the
-// LDS-limited residency: 160 KiB / (entries * 512 B) per CU.
 #define RT_TRACE2_DEFAULT_TUNE (32u | (8u << 8))     // profiles/r02_ktrace2_tune_sweep.log, r02_w4_tune_sweep.log
 #define RT_W4_DEFAULT_RAYS_PER_LANE 0u               // k_trace_w4's live-counter grid (trace_kernels.h); 0 = every wave
+
+// What a trace launch needs besides its rays: where it goes and what it writes.  The stage that launches builds one from its pipe (the guide pass: from
+// the filter's own buffers) and hands it down by value.
+struct TraceTarget
+{
+    hipStream_t stream;
+    uint2* spill; uint32_t* slow_list;     // the launch's stack spill area; the queue indices k_trace_w4 leaves to k_trace2
+    uint32_t flavour;                      // which work heads and slow-ray count of `counters`: 0 = closest hit, 1 + q = shadow queue q
+    float4* hits;                          // nullptr: a shadow trace
+    DLog log; DCounters* counters;
+    uint64_t paths;                        // paths of the batch the rays belong to (a launch's size class; its live count is on the device)
+    uint32_t timeline_slot;                // rt_frame_debug_timeline: the bounce whose slot the instrumented closest-hit instance records into
+    uint32_t variant, waves_per_cu;        // RT_OPT_TRACE_VARIANT, RT_OPT_TRACE_WAVES_PER_CU as this launch takes them
+};
+
+// the persistent grid of one-wave blocks for an LDS stack of `stack_entries` entries: 160 KiB / (entries * 512 B) waves per CU, at most 32 and at most
+// waves_per_cu (0 = no cap), rounded up to a multiple of 8 blocks (one per XCD)
+uint32_t persistent_blocks(const rt_ctx* ctx, uint32_t stack_entries, uint32_t waves_per_cu)
+{
+    uint32_t per_cu = (160u * 1024u) / (stack_entries * 512u);
+    if (per_cu > 32u) per_cu = 32u;
+    if (waves_per_cu && waves_per_cu < per_cu) per_cu = waves_per_cu;
+    return ((uint32_t)ctx->prop.multiProcessorCount * per_cu + 7u) & ~7u;
+}
+
+// RT_OPT_TRACE_TUNE's node and leaf thresholds, field by field (0 = that field's default), as node | leaf << 8
+uint32_t tune_thresholds(uint32_t t)
+{
+    const uint32_t node_q = (t & 0xFFu) ? (t & 0xFFu) : (RT_TRACE2_DEFAULT_TUNE & 0xFFu);
+    const uint32_t leaf_q = ((t >> 8) & 0xFFu) ? ((t >> 8) & 0xFFu) : ((RT_TRACE2_DEFAULT_TUNE >> 8) & 0xFFu);
+    return node_q | leaf_q << 8;
+}
+
+// k_trace2: separate wave-uniform loops (trace_kernels.h).  One-wave blocks on the persistent grid of the LDS-limited residency.
 template <bool SHADOW, int STACK>
-void launch_trace2(rt_frame* f, const float4* o4, const float4* d4, const uint32_t* aux, const uint32_t* count)
+void launch_trace2(rt_frame* f, const TraceTarget& t, const float4* o4, const float4* d4, const uint32_t* aux, const uint32_t* count)
 {
     rt_ctx* ctx = f->ctx;
-    uint32_t per_cu = (160u * 1024u) / (STACK * 512u);
-    if (per_cu > 32u) per_cu = 32u;
-    if (f->trace_waves_per_cu && f->trace_waves_per_cu < per_cu) per_cu = f->trace_waves_per_cu;
-    uint32_t blocks = ((uint32_t)ctx->prop.multiProcessorCount * per_cu + 7u) & ~7u;
+    const uint32_t blocks = persistent_blocks(ctx, STACK, t.waves_per_cu);
     uint32_t tune = f->trace_tune ? f->trace_tune : RT_TRACE2_DEFAULT_TUNE;
     if ((tune & 0xFFu) > 64u) tune = (tune & ~0xFFu) | 64u;
     if ((tune & 0xFFu) == 0u) tune |= 1u;
-    hipLaunchKernelGGL((k_trace2<SHADOW, STACK>), dim3(blocks), dim3(64), 0, f->tl_stream, ctx->scene.d, o4, d4, aux, count,
-        &f->p->counters->head[f->tl_flavour][0], SHADOW ? (float4*)nullptr : f->p->hits,
-        dlog(f), f->select_form_box, f->tl_spill, tune, (const uint32_t*)nullptr,
-        &f->p->counters->stack_spills);
+    hipLaunchKernelGGL((k_trace2<SHADOW, STACK>), dim3(blocks), dim3(64), 0, t.stream, ctx->scene.d, o4, d4, aux, count,
+        &t.counters->head[t.flavour][0], t.hits,
+        t.log, f->select_form_box, t.spill, tune, (const uint32_t*)nullptr,
+        &t.counters->stack_spills);
 }
 
 // k_trace_w4 over the 4-wide quantized tree, then k_trace2 over the (normally empty) list of rays it left out
 template <bool SHADOW, int STACK>
-void launch_trace_w4(rt_frame* f, const float4* o4, const float4* d4, const uint32_t* aux, const uint32_t* count, uint32_t /*bounce*/)
+void launch_trace_w4(rt_frame* f, const TraceTarget& t, const float4* o4, const float4* d4, const uint32_t* aux, const uint32_t* count)
 {
     rt_ctx* ctx = f->ctx;
-    uint32_t per_cu = (160u * 1024u) / (STACK * 512u);
-    if (per_cu > 32u) per_cu = 32u;
-    if (f->trace_waves_per_cu && f->trace_waves_per_cu < per_cu) per_cu = f->trace_waves_per_cu;
-    uint32_t blocks = ((uint32_t)ctx->prop.multiProcessorCount * per_cu + 7u) & ~7u;
+    const uint32_t blocks = persistent_blocks(ctx, STACK, t.waves_per_cu);
     // RT_OPT_TRACE_TUNE, field by field (0 = that field's default)
-    const uint32_t t = f->trace_tune;
-    uint32_t node_q = (t & 0xFFu) ? (t & 0xFFu) : (RT_TRACE2_DEFAULT_TUNE & 0xFFu);
-    const uint32_t leaf_q = ((t >> 8) & 0xFFu) ? ((t >> 8) & 0xFFu) : ((RT_TRACE2_DEFAULT_TUNE >> 8) & 0xFFu);
-    if (node_q > 64u) node_q = 64u;
-    uint32_t rays_per_lane = (t >> 24) ? (t >> 24) : RT_W4_DEFAULT_RAYS_PER_LANE;
+    const uint32_t thresholds = tune_thresholds(f->trace_tune);
+    const uint32_t node_q = (thresholds & 0xFFu) > 64u ? 64u : (thresholds & 0xFFu);
+    uint32_t rays_per_lane = (f->trace_tune >> 24) ? (f->trace_tune >> 24) : RT_W4_DEFAULT_RAYS_PER_LANE;
     if (rays_per_lane == 255u) rays_per_lane = 0u;                          // 255 = every wave of the residency-sized grid
-    const uint32_t tune = node_q | leaf_q << 8 | (t & 0xFF0000u) | rays_per_lane << 24;
-    const uint32_t s = f->tl_flavour;
+    const uint32_t tune = node_q | (thresholds & 0xFF00u) | (f->trace_tune & 0xFF0000u) | rays_per_lane << 24;
+    const uint32_t s = t.flavour;
+    DCounters* const c = t.counters;
     // the instance with loop D and refilled chunks (below): static assignment stays ahead of the shared work heads up to larger launches
     // there -- 8 M rays instead of 3 M (4 / 8 / 16 samples of a 1080p frame in flight: +2.7 / +8.4 / +4.8 %, profiles/r04_call20.log)
-    const uint64_t batch_paths = (uint64_t)f->p->chunk_count * (f->p->cur_slots ? f->p->cur_slots : 1u);
-    const bool tail_instance = STACK == 12 && f->trace_tail_lanes != 0u && batch_paths < f->trace_tail_paths && !(!SHADOW && f->timeline);
+    const bool tail_instance = STACK == 12 && f->trace_tail_lanes != 0u && t.paths < f->trace_tail_paths && !(!SHADOW && f->timeline);
     const uint64_t small = f->small_launch_set || !tail_instance ? f->small_launch_paths : 8000000ull;
     const uint32_t chunk_below = small > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)small;
     // (Camera-ray launches refilled instead of chunked -- coherent rays, short tails? -- measured: 2477 instead of 2876 Mrays/s per frame,
     // profiles/r04_call14.log: a refilling launch of any size pays its ~0.6 ms drain.)
     unsigned long long* const no_timeline = nullptr;
-    // the instance with loop D (the fused tail pass) where the whole batch is a small launch: the kernel then runs in chunk
-    // mode whatever its live counter says (count <= paths < chunk_below)
-    const bool tail = tail_instance;
     if (!SHADOW && STACK == 12 && f->timeline)          // tools/launch_timeline.py: the instrumented instance
-        hipLaunchKernelGGL((k_trace_w4<false, 12, true, false>), dim3(blocks), dim3(64), 0, f->tl_stream, ctx->scene.d, o4, d4, aux, count,
-            &f->p->counters->head[s][0], f->p->hits, dlog(f), f->tl_spill, tune, f->tl_slow_list,
-            &f->p->counters->slow_count[s], &f->p->counters->stack_spills, &f->p->counters->tl_start[f->timeline_bounce & 63u],
-            f->timeline_bounce & 63u, chunk_below, 0u, f->chunk_refill);
-    else if (tail)
-        hipLaunchKernelGGL((k_trace_w4<SHADOW, 12, false, true>), dim3(blocks), dim3(64), 0, f->tl_stream, ctx->scene.d, o4, d4, aux, count,
-            &f->p->counters->head[s][0], SHADOW ? (float4*)nullptr : f->p->hits, dlog(f),
-            f->tl_spill, tune, f->tl_slow_list, &f->p->counters->slow_count[s], &f->p->counters->stack_spills, no_timeline, 0u, chunk_below, f->trace_tail_lanes, f->chunk_refill);
+        hipLaunchKernelGGL((k_trace_w4<false, 12, true, false>), dim3(blocks), dim3(64), 0, t.stream, ctx->scene.d, o4, d4, aux, count,
+            &c->head[s][0], t.hits, t.log, t.spill, tune, t.slow_list,
+            &c->slow_count[s], &c->stack_spills, &c->tl_start[t.timeline_slot & 63u],
+            t.timeline_slot & 63u, chunk_below, 0u, f->chunk_refill);
+    else if (tail_instance)       // loop D (the fused tail pass) where the whole batch is a small launch: chunk mode whatever the live counter says (count <= paths < chunk_below)
+        hipLaunchKernelGGL((k_trace_w4<SHADOW, 12, false, true>), dim3(blocks), dim3(64), 0, t.stream, ctx->scene.d, o4, d4, aux, count,
+            &c->head[s][0], t.hits, t.log,
+            t.spill, tune, t.slow_list, &c->slow_count[s], &c->stack_spills, no_timeline, 0u, chunk_below, f->trace_tail_lanes, f->chunk_refill);
     else
-        hipLaunchKernelGGL((k_trace_w4<SHADOW, STACK, false, false>), dim3(blocks), dim3(64), 0, f->tl_stream, ctx->scene.d, o4, d4, aux, count,
-            &f->p->counters->head[s][0], SHADOW ? (float4*)nullptr : f->p->hits, dlog(f),
-            f->tl_spill, tune, f->tl_slow_list, &f->p->counters->slow_count[s], &f->p->counters->stack_spills, no_timeline, 0u, chunk_below, 0u, f->chunk_refill);
+        hipLaunchKernelGGL((k_trace_w4<SHADOW, STACK, false, false>), dim3(blocks), dim3(64), 0, t.stream, ctx->scene.d, o4, d4, aux, count,
+            &c->head[s][0], t.hits, t.log,
+            t.spill, tune, t.slow_list, &c->slow_count[s], &c->stack_spills, no_timeline, 0u, chunk_below, 0u, f->chunk_refill);
     // The follow-up over the (normally empty) slow list: waves with a two-entry LDS stack (the rest of the stack
     // lives in the spill area) -- 1 KiB of LDS and a few registers, so it finds room beside the resident waves of the
     // OTHER stream's persistent launch (RT_OPT_OVERLAP_SHADOW) instead of waiting for that launch to end: with the
@@ -1801,18 +1866,17 @@ void launch_trace_w4(rt_frame* f, const float4* o4, const float4* d4, const uint
     // with a long one (every shadow ray towards an axis-aligned point-light arrangement, say) the list is not serialised
     // onto one wave per CU.  Scenes whose directional lights make MOST shadow rays slow never get here (Scene::slow_shadow).
     uint32_t blocks2 = ((uint32_t)ctx->prop.multiProcessorCount * 4u + 7u) & ~7u;
-    hipLaunchKernelGGL((k_trace2<SHADOW, 2>), dim3(blocks2), dim3(64), 0, f->tl_stream, ctx->scene.d, o4, d4, aux,
-        (const uint32_t*)&f->p->counters->slow_count[s], &f->p->counters->slow_head[s][0], SHADOW ? (float4*)nullptr : f->p->hits,
-        dlog(f), f->select_form_box, f->tl_spill, tune & 0xFFFFu, (const uint32_t*)f->tl_slow_list,
-        &f->p->counters->stack_spills);
+    hipLaunchKernelGGL((k_trace2<SHADOW, 2>), dim3(blocks2), dim3(64), 0, t.stream, ctx->scene.d, o4, d4, aux,
+        (const uint32_t*)&c->slow_count[s], &c->slow_head[s][0], t.hits,
+        t.log, f->select_form_box, t.spill, tune & 0xFFFFu, (const uint32_t*)t.slow_list,
+        &c->stack_spills);
 }
 
 template <bool SHADOW>
-void launch_trace(rt_frame* f, const float4* o4, const float4* d4, const uint32_t* aux, const uint32_t* count,
-    uint32_t bounce)
+void launch_trace(rt_frame* f, const TraceTarget& t, const float4* o4, const float4* d4, const uint32_t* aux, const uint32_t* count)
 {
     rt_ctx* ctx = f->ctx;
-    uint32_t variant = f->trace_variant;
+    uint32_t variant = t.variant;
     if (variant == 5)
     {
         // auto: the 4-wide quantized tree wherever it was built -- 4214 (round 1's k_trace) / 4400 (k_trace2) / 5042
@@ -1823,27 +1887,24 @@ void launch_trace(rt_frame* f, const float4* o4, const float4* d4, const uint32_
         // k_trace_w4 switches to its chunk mode by itself when a launch is small (RT_OPT_SMALL_LAUNCH_PATHS, decided in the
         // kernel from the live queue counter).  Without the wide tree, small batches take the per-ray loop of v1, which
         // beats the refilling BVH2 kernel there (1511 vs 737 Mrays/s at one 1080p sample in flight, profiles/r03_call02_*)
-        const uint64_t paths = (uint64_t)f->p->chunk_count * (f->p->cur_slots ? f->p->cur_slots : 1u);
-        if ((variant == 8u || !ctx->scene.wide_ok) && paths < 2000000ull) variant = 0u;
+        if ((variant == 8u || !ctx->scene.wide_ok) && t.paths < 2000000ull) variant = 0u;
     }
     if ((variant == 10u || variant == 11u) && !ctx->scene.wide_ok) variant = 8u;
     if ((variant == 8u || variant == 9u) && !ctx->scene.offsets32) variant = 0u;
     switch (variant)
     {
     case 0:
-        // (the spatial filter's guide pass, ensure_guides, launches through here with a stand-in f->p that holds only `hits`: what this case reads
-        //  from f->p must stay hits + dlog's pointers, or ensure_guides must set the rest too)
-        hipLaunchKernelGGL(k_trace_v1<SHADOW>, dim3(f->trace_waves_per_cu ? (((uint32_t)ctx->prop.multiProcessorCount *
-            (f->trace_waves_per_cu < 13u ? f->trace_waves_per_cu : 13u) + 7u) & ~7u) : f->trace_blocks), dim3(64), 0, f->tl_stream, ctx->scene.d, o4, d4,
-            aux, count, SHADOW ? (float4*)nullptr : f->p->hits, dlog(f), f->select_form_box, f->tl_spill);
+        hipLaunchKernelGGL(k_trace_v1<SHADOW>, dim3(t.waves_per_cu ? (((uint32_t)ctx->prop.multiProcessorCount *
+            (t.waves_per_cu < 13u ? t.waves_per_cu : 13u) + 7u) & ~7u) : f->trace_blocks), dim3(64), 0, t.stream, ctx->scene.d, o4, d4,
+            aux, count, t.hits, t.log, f->select_form_box, t.spill);
         break;
     case 8:
-        if (!SHADOW && ctx->scene.d.entry_ref < 4000000u) launch_trace2<SHADOW, 10>(f, o4, d4, aux, count);
-        else launch_trace2<SHADOW, 12>(f, o4, d4, aux, count);
+        if (!SHADOW && ctx->scene.d.entry_ref < 4000000u) launch_trace2<SHADOW, 10>(f, t, o4, d4, aux, count);
+        else launch_trace2<SHADOW, 12>(f, t, o4, d4, aux, count);
         break;
-    case 9: launch_trace2<SHADOW, 12>(f, o4, d4, aux, count); break;
-    case 11: launch_trace_w4<SHADOW, 16>(f, o4, d4, aux, count, bounce); break;
-    default: launch_trace_w4<SHADOW, 12>(f, o4, d4, aux, count, bounce); break;
+    case 9: launch_trace2<SHADOW, 12>(f, t, o4, d4, aux, count); break;
+    case 11: launch_trace_w4<SHADOW, 16>(f, t, o4, d4, aux, count); break;
+    default: launch_trace_w4<SHADOW, 12>(f, t, o4, d4, aux, count); break;
     }
 }
 } // namespace
@@ -1858,12 +1919,8 @@ int rt_reset(rt_frame* f)                               // CLPathTraceIntegrator
     if (join_pipes(f) != RT_OK) return RT_ERROR;
     ahead_discard(f);                        // RT_OPT_SAMPLES_AHEAD: the samples traced ahead continued a sum that starts again
     if (!f->denoiser) f->sample_count = 0;   // Reset() keeps the frame index while denoising (:499-504)
-    for (uint32_t i = 0; i < RT_MAX_PIPES; ++i)           // a shadow trace still running on a side stream writes the log
-    {
-        f->p = &f->ps[i];
-        if (f->p->stream && (wait_shadow(f, 0) != RT_OK || wait_shadow(f, 1) != RT_OK)) { f->p = &f->ps[0]; return RT_ERROR; }
-    }
-    f->p = &f->ps[0];
+    for (PathPipe& q : f->ps)                             // a shadow trace still running on a side stream writes the log
+        if (q.stream && (wait_shadow(f, q, 0) != RT_OK || wait_shadow(f, q, 1) != RT_OK)) return RT_ERROR;
     f->stage_chunks = 1;
     f->deferred.active = false; f->deferred.ahead = false;  // a recorded sample that was never advanced: nothing has run
     for (uint32_t i = 0; i < RT_MAX_PIPES; ++i)
@@ -1878,7 +1935,7 @@ int rt_reset(rt_frame* f)                               // CLPathTraceIntegrator
         if (q.cnt) HIPCHK(ctx, hipMemsetAsync(q.cnt, 0, (size_t)f->log_stride * sizeof(uint32_t), ctx->stream));
         if (q.counters) HIPCHK(ctx, hipMemsetAsync(q.counters, 0, sizeof(DCounters), ctx->stream));
     }
-    HIPCHK(ctx, hipMemsetAsync(f->radiance, 0, (size_t)(f->n_local ? f->n_local : 1) * sizeof(float4), ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(f->radiance, 0, (size_t)tile_pixels(f) * sizeof(float4), ctx->stream));
     return RT_OK;
 }
 
@@ -1887,26 +1944,26 @@ int rt_reset(rt_frame* f)                               // CLPathTraceIntegrator
 namespace
 {
 // Primary rays for `n_slots` consecutive samples (sample indices sample_count ..
-// sample_count + n_slots - 1) in one launch; they then travel through the same queues.
-int generate_rays(rt_frame* f, uint32_t n_slots, uint32_t chunk_base = 0, bool later_chunk_on_this_pipe = false)
+// sample_count + n_slots - 1) in one launch on pipe `p`; they then travel through that pipe's queues.
+int generate_rays(rt_frame* f, PathPipe& p, uint32_t n_slots, uint32_t chunk_base = 0, bool later_chunk_on_this_pipe = false)
 {
     rt_ctx* ctx = f->ctx;
-    if (f->p->cur_slots != 0) return fail(ctx, "rt_generate_rays: the previous sample was not advanced (rt_advance_sample)");
+    if (p.cur_slots != 0) return fail(ctx, "rt_generate_rays: the previous sample was not advanced (rt_advance_sample)");
     if (chunk_base == 0 && ensure_slots(f, n_slots) != RT_OK) return RT_ERROR;
     if (n_slots > f->slots) return fail(ctx, "rt_generate_rays: more samples than the frame can keep in flight");
-    if (chunk_base >= (f->n_local ? f->n_local : 1u)) return fail(ctx, "rt_generate_rays: chunk outside the tile");
-    f->p->chunk_base = chunk_base;
-    f->p->chunk_count = f->n_local - chunk_base < f->chunk_pixels ? f->n_local - chunk_base : f->chunk_pixels;
+    if (chunk_base >= tile_pixels(f)) return fail(ctx, "rt_generate_rays: chunk outside the tile");
+    p.chunk_base = chunk_base;
+    p.chunk_count = f->n_local - chunk_base < f->chunk_pixels ? f->n_local - chunk_base : f->chunk_pixels;
     float tan_half_fov = rt_tanf(0.5f * f->camera.fov);  // raygeneration.cl:108, uniform -> host
-    uint32_t blocks = (f->p->chunk_count * n_slots + 255u) / 256u;
+    uint32_t blocks = (p.chunk_count * n_slots + 255u) / 256u;
     if (blocks == 0) blocks = 1;
-    KernelSpan span(f, 0);
-    hipLaunchKernelGGL(k_raygen, dim3(blocks), dim3(256), 0, f->p->stream, f->tile, f->camera, f->sample_count, n_slots,
-        tan_half_fov, f->p->prev_bounces, f->p->o4[0], f->p->d4[0], f->p->thr[0], f->p->counters, f->p->chunk_base, f->p->chunk_count,
-        f->chunk_pixels, f->p->fold_accumulates);
-    f->p->fold_accumulates = later_chunk_on_this_pipe ? 1u : 0u;     // what the NEXT fold does with this sequence's counters
-    f->p->prev_bounces = f->max_bounces;
-    f->p->cur_slots = n_slots;
+    KernelSpan span(f, 0, p.stream);
+    hipLaunchKernelGGL(k_raygen, dim3(blocks), dim3(256), 0, p.stream, f->tile, f->camera, f->sample_count, n_slots,
+        tan_half_fov, p.prev_bounces, p.o4[0], p.d4[0], p.thr[0], p.counters, p.chunk_base, p.chunk_count,
+        f->chunk_pixels, p.fold_accumulates);
+    p.fold_accumulates = later_chunk_on_this_pipe ? 1u : 0u;     // what the NEXT fold does with this sequence's counters
+    p.prev_bounces = f->max_bounces;
+    p.cur_slots = n_slots;
     HIPCHK(ctx, hipGetLastError());
     return RT_OK;
 }
@@ -1926,13 +1983,20 @@ namespace
 bool frame_kernel_eligible(const rt_frame* f)
 {
     const rt_ctx* ctx = f->ctx;
-    const uint32_t n_local = f->n_local ? f->n_local : 1u;
+    const uint32_t n_local = tile_pixels(f);
     // (fk_auto.frames has been advanced past the frame being started: frame k = frames - 1)
     const int fk = f->fk_auto.frames - 1;
     const bool wanted = f->frame_kernel == 255u ? (f->fk_auto.decided ? f->fk_auto.use_kernel : (!f->fk_auto.skip && (fk == 2 || fk == 3 || (fk >= 4 && (fk & 1))))) : f->frame_kernel != 0u;
     return wanted && f->n_local != 0u && !(f->denoiser || f->aov != 0) && ctx->scene.wide_ok && !ctx->scene.slow_shadow &&
            ctx->scene.d.emissive_nee == 0u && f->log_ovf_blocks == 0u && f->n_pipes == 1u && f->chunk_pixels >= n_local && f->stage_chunks <= 1u &&
            (f->trace_variant == 5u || f->trace_variant == 10u) && !f->profile && !f->timeline && f->select_form_box == 0u && f->max_bounces < 63u;
+}
+
+// the blue-noise sampler's three tables as k_shade and k_frame read them (one allocation; nullptr: not uploaded)
+void set_blue_noise(ShadeArgs& a, const rt_ctx* ctx)
+{
+    a.bn_sobol = ctx->blue_noise; a.bn_scramble = ctx->blue_noise ? ctx->blue_noise + 65536 : nullptr;
+    a.bn_rank = ctx->blue_noise ? ctx->blue_noise + 65536 + 131072 : nullptr;
 }
 
 template <bool FURNACE, bool BLUE>
@@ -1974,9 +2038,8 @@ int launch_frame_kernel_t(rt_frame* f)
     FrameArgs fa;
     memset(&fa, 0, sizeof(fa));
     ShadeArgs& a = fa.shade;
-    a.log = dlog(f); a.counters = q.counters;
-    a.bn_sobol = ctx->blue_noise; a.bn_scramble = ctx->blue_noise ? ctx->blue_noise + 65536 : nullptr;
-    a.bn_rank = ctx->blue_noise ? ctx->blue_noise + 65536 + 131072 : nullptr;
+    a.log = dlog(f, q); a.counters = q.counters;
+    set_blue_noise(a, ctx);
     a.sample_base = f->sample_count;
     a.n_local = f->chunk_pixels ? f->chunk_pixels : 1;
     a.pix_base = 0;
@@ -1993,8 +2056,7 @@ int launch_frame_kernel_t(rt_frame* f)
     fa.tan_half_fov = rt_tanf(0.5f * f->camera.fov);
     fa.max_bounces = f->max_bounces;
     fa.drop_last = f->drop_last;
-    const uint32_t t = f->trace_tune;
-    fa.tune = ((t & 0xFFu) ? (t & 0xFFu) : (RT_TRACE2_DEFAULT_TUNE & 0xFFu)) | ((((t >> 8) & 0xFFu) ? ((t >> 8) & 0xFFu) : ((RT_TRACE2_DEFAULT_TUNE >> 8) & 0xFFu)) << 8);
+    fa.tune = tune_thresholds(f->trace_tune);
     fa.tail_q = f->trace_tail_lanes;
     fa.chunks_per_wave = f->frame_chunks_per_wave;
     hipLaunchKernelGGL((k_frame<FURNACE, BLUE>), dim3(f->kf.blocks), dim3(64), 0, q.stream, ctx->scene.d, f->tile, fa);
@@ -2013,6 +2075,89 @@ int launch_frame_kernel(rt_frame* f)
     return blue ? launch_frame_kernel_t<false, true>(f) : launch_frame_kernel_t<false, false>(f);
 }
 
+// ---- the three stages, one pipe's work each: the C entry points run them over the pipes that hold the stage API's sample, rt_integrate and the banks
+// (trace_bounces) over the pipe of each chunk ------------------------------------------------------------------------------------------
+// IntersectRays: the closest-hit trace of pipe p's ray queue of `bounce`
+int intersect_pipe(rt_frame* f, PathPipe& p, uint32_t bounce)
+{
+    rt_ctx* ctx = f->ctx;
+    const uint32_t in = bounce & 1u;
+    const TraceTarget t = {p.stream, p.spill, p.slow_list, 0u, p.hits, dlog(f, p), p.counters, p.batch_paths(), bounce, f->trace_variant, f->trace_waves_per_cu};
+    KernelSpan span(f, 1, p.stream);
+    launch_trace<false>(f, t, p.o4[in], p.d4[in], (const uint32_t*)nullptr, &p.counters->queue[bounce]);
+    HIPCHK(ctx, hipGetLastError());
+    return RT_OK;
+}
+
+// ShadeMissedRays + ShadeSurfaceHits.  count_in_ray: whole samples (rt_integrate, the banks) -- nothing reads the radiance between their stages
+int shade_pipe(rt_frame* f, PathPipe& p, uint32_t bounce, bool count_in_ray)
+{
+    rt_ctx* ctx = f->ctx;
+    uint32_t in = bounce & 1u, out = (bounce + 1u) & 1u;
+    ShadeArgs a;
+    a.in_o4 = p.o4[in]; a.in_d4 = p.d4[in]; a.in_thr = p.thr[in]; a.hits = p.hits;
+    a.out_o4 = p.o4[out]; a.out_d4 = p.d4[out]; a.out_thr = p.thr[out];
+    a.sh_o4 = p.sh_o4[bounce & 1u]; a.sh_d4 = p.sh_d4[bounce & 1u]; a.sh_aux = p.sh_aux[bounce & 1u];
+    a.log = dlog(f, p); a.counters = p.counters;
+    set_blue_noise(a, ctx);
+    a.bounce = bounce; a.sample_base = f->sample_count;
+    a.emit_outgoing = (f->drop_last && bounce >= f->max_bounces) ? 0u : 1u;
+    a.n_local = f->chunk_pixels ? f->chunk_pixels : 1;
+    a.pix_base = p.chunk_base;
+    a.count_in_ray = count_in_ray ? 1u : 0u;
+    a.partition = f->shade_partition;
+    a.final_bounce = bounce >= f->max_bounces ? 1u : 0u;
+    uint32_t blocks = ((uint32_t)p.batch_paths() + RT_SHADE_BLOCK - 1u) / RT_SHADE_BLOCK;
+    if (blocks == 0) blocks = 1;
+    p.shadow_pending = true;
+    // this bounce refills shadow queue [bounce & 1] and rewinds its work heads: the shadow trace of bounce - 2 is done with them
+    if (wait_shadow(f, p, bounce & 1u) != RT_OK) return RT_ERROR;
+    KernelSpan span(f, 2, p.stream);
+    const bool blue = f->sampler == 1;   // kernel variants are AOT (the reference rebuilds with -D..., :267-285)
+    const bool nee = ctx->scene.d.emissive_nee != 0;     // opt-in extension (rt_scene_desc::flags)
+#define RT_LAUNCH_SHADE(FURNACE, BLUE, NEE) \
+    do { if (f->log_ovf_blocks) hipLaunchKernelGGL((k_shade<FURNACE, BLUE, NEE, true>), dim3(blocks), dim3(RT_SHADE_BLOCK), 0, p.stream, ctx->scene.d, f->tile, a); \
+         else hipLaunchKernelGGL((k_shade<FURNACE, BLUE, NEE, false>), dim3(blocks), dim3(RT_SHADE_BLOCK), 0, p.stream, ctx->scene.d, f->tile, a); } while (0)
+    if (nee)
+    {
+        if (f->white_furnace && blue) RT_LAUNCH_SHADE(true, true, true);
+        else if (f->white_furnace) RT_LAUNCH_SHADE(true, false, true);
+        else if (blue) RT_LAUNCH_SHADE(false, true, true);
+        else RT_LAUNCH_SHADE(false, false, true);
+    }
+    else if (f->white_furnace && blue) RT_LAUNCH_SHADE(true, true, false);
+    else if (f->white_furnace) RT_LAUNCH_SHADE(true, false, false);
+    else if (blue) RT_LAUNCH_SHADE(false, true, false);
+    else RT_LAUNCH_SHADE(false, false, false);
+#undef RT_LAUNCH_SHADE
+    HIPCHK(ctx, hipGetLastError());
+    f->side_active = side_on(f);
+    if (f->side_active) HIPCHK(ctx, hipEventRecord(p.ev_shaded, p.stream));
+    return RT_OK;
+}
+
+// IntersectShadowRays + AccumulateDirectSamples: the trace of pipe p's shadow queue of `bounce`, on the side stream where the shade step chose it
+int shadow_pipe(rt_frame* f, PathPipe& p, uint32_t bounce)
+{
+    rt_ctx* ctx = f->ctx;
+    const uint32_t q = bounce & 1u;
+    const TraceTarget t = {f->side_active ? p.side : p.stream, p.sh_spill, p.sh_slow_list, 1u + q, nullptr, dlog(f, p), p.counters, p.batch_paths(), bounce,
+                           f->trace_variant, f->trace_waves_per_cu};
+    if (f->side_active) HIPCHK(ctx, hipStreamWaitEvent(p.side, p.ev_shaded, 0));
+    {
+        KernelSpan span(f, 3, t.stream);
+        launch_trace<true>(f, t, p.sh_o4[q], p.sh_d4[q], (const uint32_t*)p.sh_aux[q], &p.counters->shadow[bounce]);
+    }
+    p.shadow_pending = false;
+    HIPCHK(ctx, hipGetLastError());
+    if (f->side_active)
+    {
+        HIPCHK(ctx, hipEventRecord(p.ev_shadow[q], p.side));
+        p.shadow_in_flight[q] = true;
+    }
+    return RT_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -2027,7 +2172,7 @@ static int deferred_materialize(rt_frame* f)
     // RT_OPT_SAMPLES_AHEAD: somebody looks between the stages of a sample that sits in a bank -- the frame traces it itself after all, and what
     // was traced ahead (that sample's slot first of all) is dropped
     if (f->deferred.ahead) { f->deferred.ahead = false; ahead_discard(f); }
-    if (generate_rays(f, 1) != RT_OK) return RT_ERROR;
+    if (generate_rays(f, f->ps[0], 1) != RT_OK) return RT_ERROR;
     for (uint32_t b = 0; b <= done; ++b)
     {
         const int upto = b < done ? 3 : next;                            // stages of bounce b that were recorded
@@ -2050,13 +2195,13 @@ int rt_generate_rays(rt_frame* f)                       // GenerateRays, :516-52
     // whose buffers are compact is driven through the stages.
     if (f->log_ovf_blocks != 0u)
     {
-        if (f->p->cur_slots != 0 || f->deferred.active) return fail(ctx, "rt_generate_rays: the previous sample was not advanced (rt_advance_sample)");
-        if (flush_log(f) != RT_OK || join_pipes(f) != RT_OK) return RT_ERROR;
+        if (f->ps[0].cur_slots != 0 || f->deferred.active) return fail(ctx, "rt_generate_rays: the previous sample was not advanced (rt_advance_sample)");
+        if (flush_log(f, f->ps[0]) != RT_OK || join_pipes(f) != RT_OK) return RT_ERROR;
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
         f->log_full_forced = true;
         if (alloc_path_buffers(f, f->slots ? f->slots : 1u) != RT_OK) return RT_ERROR;
     }
-    const uint32_t n_local = f->n_local ? f->n_local : 1u;
+    const uint32_t n_local = tile_pixels(f);
     uint32_t np = 1, cp = 0;
     chunk_plan(f, 1, np, cp);
     if ((uint64_t)cp * np < n_local)
@@ -2070,67 +2215,26 @@ int rt_generate_rays(rt_frame* f)                       // GenerateRays, :516-52
         if (f->ahead && ahead_wanted(f) && ahead_holds(f, f->sample_count) >= 0)
         {
             // RT_OPT_SAMPLES_AHEAD: this sample has been traced ahead -- nothing is launched, the stages are recorded, rt_advance_sample replays its log
-            if (f->p->cur_slots != 0) return fail(ctx, "rt_generate_rays: the previous sample was not advanced (rt_advance_sample)");
+            if (f->ps[0].cur_slots != 0) return fail(ctx, "rt_generate_rays: the previous sample was not advanced (rt_advance_sample)");
             f->deferred.active = true; f->deferred.bounce = 0; f->deferred.next = 0; f->deferred.ahead = true;
             return RT_OK;
         }
-        if (f->frame_kernel == 255u)
-        {
-            // frames 0 - 3 warm up (two each way), frames 4 - 19 alternate stage kernels / k_frame and are timed; once the last timed frame's events
-            // have completed, the faster way stays (until the next scene upload)
-            auto& m = f->fk_auto;
-            if (m.scene != ctx->scene_uploads) { m.frames = 0; m.timing = -1; m.decided = false; m.use_kernel = false; m.scene = ctx->scene_uploads; }
-            m.timing = -1;
-            m.skip = false;
-            if (!m.decided)
-            {
-                const int k = m.frames;
-                if (k >= 20 && hipEventQuery(m.ev[15][1]) == hipSuccess)
-                {
-                    m.ms_stage = m.ms_kernel = 0.0f;
-                    bool ok = true;
-                    for (int i = 0; i < 16 && ok; ++i)
-                    {
-                        float t = 0.0f;
-                        ok = hipEventElapsedTime(&t, m.ev[i][0], m.ev[i][1]) == hipSuccess;
-                        ((i & 1) ? m.ms_kernel : m.ms_stage) += t;
-                    }
-                    if (!ok) (void)hipGetLastError();
-                    m.decided = true;
-                    m.use_kernel = ok && m.ms_kernel < m.ms_stage;
-                }
-                else if (k >= 4 && k < 20 && ctx->scene.adapt && (ctx->scene.adapt->state == FoldAdapt::ARMED || ctx->scene.adapt->state == FoldAdapt::PROBING || ctx->scene.adapt->state == FoldAdapt::COMPUTING))
-                {
-                    //  a fold adaptation is under way -- probe launches on this stream, a fold swapped mid-window: such a frame is not one
-                    // of the sixteen that are compared (it runs through the stage kernels, untimed; the schedule goes on once the folds have settled)
-                    m.skip = true;
-                }
-                else if (k >= 4 && k < 20)
-                {
-                    m.timing = k - 4;
-                    bool ok = true;
-                    for (hipEvent_t& e : m.ev[m.timing]) if (!e) ok = ok && hipEventCreate(&e) == hipSuccess;
-                    if (!ok || hipEventRecord(m.ev[m.timing][0], ctx->stream) != hipSuccess) { (void)hipGetLastError(); m.decided = true; m.use_kernel = false; m.timing = -1; }
-                }
-                if (!m.decided && !m.skip) ++m.frames;
-            }
-            if (m.decided) m.frames = 1 << 20;          // (frame_kernel_eligible reads `decided`; keep frames - 1 out of the schedule's range)
-        }
+        if (f->frame_kernel == 255u) fk_auto_begin_frame(f);
         if (frame_kernel_eligible(f))
         {
             // RT_OPT_FRAME_KERNEL: nothing is launched yet -- the stages are recorded, rt_advance_sample launches k_frame
-            if (f->p->cur_slots != 0) return fail(ctx, "rt_generate_rays: the previous sample was not advanced (rt_advance_sample)");
+            if (f->ps[0].cur_slots != 0) return fail(ctx, "rt_generate_rays: the previous sample was not advanced (rt_advance_sample)");
             if (ensure_slots(f, 1) != RT_OK) return RT_ERROR;
             if (frame_kernel_eligible(f)) { f->deferred.active = true; f->deferred.bounce = 0; f->deferred.next = 0; f->deferred.ahead = false; return RT_OK; }
         }
-        return generate_rays(f, 1);
+        return generate_rays(f, f->ps[0], 1);
     }
     // RT_OPT_STAGE_PIPES: the sample's chunks travel side by side, one per pipe; an allocation made for a larger batch (one pipe, the
     // whole tile) gives way to the one-sample layout
     if (f->chunk_pixels != cp || f->n_pipes != np)
     {
         for (const PathPipe& q : f->ps) if (q.cur_slots != 0) return fail(ctx, "rt_generate_rays: the previous sample was not advanced (rt_advance_sample)");
-        if (flush_log(f) != RT_OK || join_pipes(f) != RT_OK) return RT_ERROR;
+        if (flush_log(f, f->ps[0]) != RT_OK || join_pipes(f) != RT_OK) return RT_ERROR;
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
         if (alloc_path_buffers(f, 1) != RT_OK) return RT_ERROR;
         if (f->chunk_pixels != cp || f->n_pipes != np) return fail(ctx, "rt_generate_rays: the one-sample layout did not come out as planned");
@@ -2139,7 +2243,7 @@ int rt_generate_rays(rt_frame* f)                       // GenerateRays, :516-52
     const uint32_t n_chunks = (n_local + f->chunk_pixels - 1u) / f->chunk_pixels;
     f->stage_chunks = n_chunks;
     uint32_t c = 0;
-    return for_stage_pipes(f, [&]() { return generate_rays(f, 1, (c++) * f->chunk_pixels, false); });
+    return for_stage_pipes(f, [&](PathPipe& p) { return generate_rays(f, p, 1, (c++) * f->chunk_pixels, false); });
 }
 
 int rt_intersect(rt_frame* f, uint32_t bounce)          // IntersectRays, :522-539
@@ -2151,17 +2255,7 @@ int rt_intersect(rt_frame* f, uint32_t bounce)          // IntersectRays, :522-5
         if (f->deferred.next == 0 && bounce == f->deferred.bounce) { f->deferred.next = 1; return RT_OK; }
         if (deferred_materialize(f) != RT_OK) return RT_ERROR;
     }
-    uint32_t in = bounce & 1u;
-    f->timeline_bounce = bounce;
-    auto one = [&]() -> int
-    {
-        f->tl_stream = f->p->stream; f->tl_spill = f->p->spill; f->tl_slow_list = f->p->slow_list; f->tl_flavour = 0;
-        KernelSpan span(f, 1);
-        launch_trace<false>(f, f->p->o4[in], f->p->d4[in], (const uint32_t*)nullptr, &f->p->counters->queue[bounce], bounce);
-        HIPCHK(ctx, hipGetLastError());
-        return RT_OK;
-    };
-    return f->fused ? one() : for_stage_pipes(f, one);                   // (rt_integrate walks its pipes itself)
+    return for_stage_pipes(f, [&](PathPipe& p) { return intersect_pipe(f, p, bounce); });
 }
 
 int rt_shade_miss(rt_frame* f, uint32_t) { return f ? RT_OK : fail(nullptr, "rt_shade_miss: frame is NULL"); }
@@ -2179,52 +2273,7 @@ int rt_shade(rt_frame* f, uint32_t bounce)              // ShadeMissedRays + Sha
         if (f->deferred.next == 1 && bounce == f->deferred.bounce) { f->deferred.next = 2; return RT_OK; }
         if (deferred_materialize(f) != RT_OK) return RT_ERROR;
     }
-    auto one = [&]() -> int
-    {
-    uint32_t in = bounce & 1u, out = (bounce + 1u) & 1u;
-    ShadeArgs a;
-    a.in_o4 = f->p->o4[in]; a.in_d4 = f->p->d4[in]; a.in_thr = f->p->thr[in]; a.hits = f->p->hits;
-    a.out_o4 = f->p->o4[out]; a.out_d4 = f->p->d4[out]; a.out_thr = f->p->thr[out];
-    a.sh_o4 = f->p->sh_o4[bounce & 1u]; a.sh_d4 = f->p->sh_d4[bounce & 1u]; a.sh_aux = f->p->sh_aux[bounce & 1u];
-    a.log = dlog(f); a.counters = f->p->counters;
-    a.bn_sobol = ctx->blue_noise; a.bn_scramble = ctx->blue_noise ? ctx->blue_noise + 65536 : nullptr;
-    a.bn_rank = ctx->blue_noise ? ctx->blue_noise + 65536 + 131072 : nullptr;
-    a.bounce = bounce; a.sample_base = f->sample_count;
-    a.emit_outgoing = (f->drop_last && bounce >= f->max_bounces) ? 0u : 1u;
-    a.n_local = f->chunk_pixels ? f->chunk_pixels : 1;
-    a.pix_base = f->p->chunk_base;
-    a.count_in_ray = f->fused ? 1u : 0u;
-    a.partition = f->shade_partition;
-    a.final_bounce = bounce >= f->max_bounces ? 1u : 0u;
-    uint32_t blocks = (f->p->chunk_count * (f->p->cur_slots ? f->p->cur_slots : 1u) + RT_SHADE_BLOCK - 1u) / RT_SHADE_BLOCK;
-    if (blocks == 0) blocks = 1;
-    f->p->shadow_pending = true;
-    // this bounce refills shadow queue [bounce & 1] and rewinds its work heads: the shadow trace of bounce - 2 is done with them
-    if (wait_shadow(f, bounce & 1u) != RT_OK) return RT_ERROR;
-    KernelSpan span(f, 2);
-    const bool blue = f->sampler == 1;   // kernel variants are AOT (the reference rebuilds with -D..., :267-285)
-    const bool nee = ctx->scene.d.emissive_nee != 0;     // opt-in extension (rt_scene_desc::flags)
-#define RT_LAUNCH_SHADE(FURNACE, BLUE, NEE) \
-    do { if (f->log_ovf_blocks) hipLaunchKernelGGL((k_shade<FURNACE, BLUE, NEE, true>), dim3(blocks), dim3(RT_SHADE_BLOCK), 0, f->p->stream, ctx->scene.d, f->tile, a); \
-         else hipLaunchKernelGGL((k_shade<FURNACE, BLUE, NEE, false>), dim3(blocks), dim3(RT_SHADE_BLOCK), 0, f->p->stream, ctx->scene.d, f->tile, a); } while (0)
-    if (nee)
-    {
-        if (f->white_furnace && blue) RT_LAUNCH_SHADE(true, true, true);
-        else if (f->white_furnace) RT_LAUNCH_SHADE(true, false, true);
-        else if (blue) RT_LAUNCH_SHADE(false, true, true);
-        else RT_LAUNCH_SHADE(false, false, true);
-    }
-    else if (f->white_furnace && blue) RT_LAUNCH_SHADE(true, true, false);
-    else if (f->white_furnace) RT_LAUNCH_SHADE(true, false, false);
-    else if (blue) RT_LAUNCH_SHADE(false, true, false);
-    else RT_LAUNCH_SHADE(false, false, false);
-#undef RT_LAUNCH_SHADE
-    HIPCHK(ctx, hipGetLastError());
-    f->side_active = side_on(f);
-    if (f->side_active) HIPCHK(ctx, hipEventRecord(f->p->ev_shaded, f->p->stream));
-    return RT_OK;
-    };
-    return f->fused ? one() : for_stage_pipes(f, one);
+    return for_stage_pipes(f, [&](PathPipe& p) { return shade_pipe(f, p, bounce, false); });
 }
 
 int rt_intersect_shadow(rt_frame* f, uint32_t bounce)   // IntersectShadowRays + AccumulateDirectSamples, :564-580,645-649
@@ -2236,38 +2285,20 @@ int rt_intersect_shadow(rt_frame* f, uint32_t bounce)   // IntersectShadowRays +
         if (f->deferred.next == 2 && bounce == f->deferred.bounce) { f->deferred.next = 0; ++f->deferred.bounce; return RT_OK; }
         if (deferred_materialize(f) != RT_OK) return RT_ERROR;
     }
-    const uint32_t q = bounce & 1u;
-    auto one = [&]() -> int
-    {
-        f->tl_stream = f->side_active ? f->p->side : f->p->stream;
-        f->tl_spill = f->p->sh_spill; f->tl_slow_list = f->p->sh_slow_list; f->tl_flavour = 1u + q;
-        if (f->side_active) HIPCHK(ctx, hipStreamWaitEvent(f->p->side, f->p->ev_shaded, 0));
-        {
-            KernelSpan span(f, 3, f->tl_stream);
-            launch_trace<true>(f, f->p->sh_o4[q], f->p->sh_d4[q], (const uint32_t*)f->p->sh_aux[q], &f->p->counters->shadow[bounce], bounce);
-        }
-        f->p->shadow_pending = false;
-        HIPCHK(ctx, hipGetLastError());
-        if (f->side_active)
-        {
-            HIPCHK(ctx, hipEventRecord(f->p->ev_shadow[q], f->p->side));
-            f->p->shadow_in_flight[q] = true;
-        }
-        return RT_OK;
-    };
-    return f->fused ? one() : for_stage_pipes(f, one);
+    return for_stage_pipes(f, [&](PathPipe& p) { return shadow_pipe(f, p, bounce); });
 }
 
 int rt_compute_aovs(rt_frame* f)                        // ComputeAOVs, :541-562 (after rt_intersect(frame, 0))
 {
     FRAME_PROLOGUE(f, "rt_compute_aovs");
     if (f->aov == 0 && !f->denoiser) return RT_OK;      // outputs unobservable: skip the work
-    if (f->p->cur_slots != 1) return fail(ctx, "rt_compute_aovs: AOVs need one sample in flight (use the stage API or rt_integrate with the denoiser/AOV option set)");
+    const PathPipe& p = f->ps[0];                       // (AOVs need the whole tile in one chunk: it travels on pipe 0)
+    if (p.cur_slots != 1) return fail(ctx, "rt_compute_aovs: AOVs need one sample in flight (use the stage API or rt_integrate with the denoiser/AOV option set)");
     if (f->n_local == 0) return RT_OK;
     uint32_t blocks = (f->n_local + 255u) / 256u;
     hipLaunchKernelGGL(k_aov_clear, dim3(blocks), dim3(256), 0, ctx->stream, f->aov_buf, f->n_local);
-    hipLaunchKernelGGL(k_aov, dim3(blocks), dim3(256), 0, ctx->stream, ctx->scene.d, (const float4*)f->p->o4[0],
-        (const float4*)f->p->d4[0], (const float4*)f->p->hits, (const uint32_t*)&f->p->counters->queue[0], f->camera, f->prev_camera,
+    hipLaunchKernelGGL(k_aov, dim3(blocks), dim3(256), 0, ctx->stream, ctx->scene.d, (const float4*)p.o4[0],
+        (const float4*)p.d4[0], (const float4*)p.hits, (const uint32_t*)&p.counters->queue[0], f->camera, f->prev_camera,
         rt_tanf(0.5f * f->camera.fov), rt_tanf(0.5f * f->prev_camera.fov), f->aov_buf);
     HIPCHK(ctx, hipGetLastError());
     return RT_OK;
@@ -2277,7 +2308,7 @@ int rt_denoise(rt_frame* f)                             // Denoise, :665-668
 {
     FRAME_PROLOGUE(f, "rt_denoise");
     if (f->denoiser != 1 || f->n_local == 0) return RT_OK;   // 2: rt_group_denoise does it on the gathered image
-    if (flush_log(f) != RT_OK) return RT_ERROR;
+    if (flush_log(f, f->ps[0]) != RT_OK) return RT_ERROR;
     uint32_t blocks = (f->n_local + 255u) / 256u;
     hipLaunchKernelGGL(k_denoise, dim3(blocks), dim3(256), 0, ctx->stream, f->tile.width, f->tile.height, f->radiance,
         (const float4*)f->prev_radiance, (const float*)f->aov_buf.depth, (const float*)f->prev_depth,
@@ -2297,22 +2328,22 @@ int rt_copy_history(rt_frame* f)                        // CopyHistoryBuffers, :
     return RT_OK;
 }
 
-// The wavefront loop of the rays in the current pipe's queue (rt_integrate's chunks, the batches traced ahead): closest-hit trace, then per bounce
+// The wavefront loop of the rays in pipe p's queue (rt_integrate's chunks, the batches traced ahead): closest-hit trace, then per bounce
 // k_shade, shadow trace, next closest-hit trace.  The shadow trace of bounce b and the closest-hit trace of bounce b + 1 both depend on k_shade(b)
 // only, and k_shade(b + 1) on the latter only (the shadow queue is double-buffered): with overlap_shadow the shadow trace goes to the pipe's side
 // stream, AFTER the next closest-hit launch has been enqueued -- it moves in as that launch's last rays drain and leaves as k_shade(b + 1) moves
 // in, so neither tail idles the machine (tools/launch_timeline.py: 0.75-0.95 ms each).  per_frame: the AOVs of the first hits (ComputeAOVs).
-static int trace_bounces(rt_frame* f, bool per_frame)
+static int trace_bounces(rt_frame* f, PathPipe& p, bool per_frame)
 {
-    if (rt_intersect(f, 0) != RT_OK) return RT_ERROR;
+    if (intersect_pipe(f, p, 0) != RT_OK) return RT_ERROR;
     for (uint32_t bounce = 0; bounce <= f->max_bounces; ++bounce)
     {
         const bool more = bounce < f->max_bounces;
         if (bounce == 0 && per_frame && rt_compute_aovs(f) != RT_OK) return RT_ERROR;
-        if (rt_shade(f, bounce) != RT_OK) return RT_ERROR;
-        if (f->side_active && more && rt_intersect(f, bounce + 1u) != RT_OK) return RT_ERROR;
-        if (rt_intersect_shadow(f, bounce) != RT_OK) return RT_ERROR;
-        if (!f->side_active && more && rt_intersect(f, bounce + 1u) != RT_OK) return RT_ERROR;
+        if (shade_pipe(f, p, bounce, true) != RT_OK) return RT_ERROR;
+        if (f->side_active && more && intersect_pipe(f, p, bounce + 1u) != RT_OK) return RT_ERROR;
+        if (shadow_pipe(f, p, bounce) != RT_OK) return RT_ERROR;
+        if (!f->side_active && more && intersect_pipe(f, p, bounce + 1u) != RT_OK) return RT_ERROR;
     }
     return RT_OK;
 }
@@ -2355,16 +2386,16 @@ int rt_advance_sample(rt_frame* f)                      // AdvanceSampleCount, :
             }
             f->deferred.active = false;
             f->sample_count += 1;
-            if (f->fk_auto.timing >= 0) { (void)hipEventRecord(f->fk_auto.ev[f->fk_auto.timing][1], f->ctx->stream); f->fk_auto.timing = -1; }
+            fk_auto_end_frame(f);
             ahead_after_plain_sample(f);
             return RT_OK;
         }
         if (deferred_materialize(f) != RT_OK) return RT_ERROR;
     }
-    uint32_t n = f->p->cur_slots ? f->p->cur_slots : 1u;
+    uint32_t n = f->ps[0].cur_slots ? f->ps[0].cur_slots : 1u;
     if (flush_stage(f) != RT_OK) return RT_ERROR;        // radiance_buffer_ += this sample's contributions (of every chunk: RT_OPT_STAGE_PIPES)
     f->sample_count += n;
-    if (f->fk_auto.timing >= 0) { (void)hipEventRecord(f->fk_auto.ev[f->fk_auto.timing][1], f->ctx->stream); f->fk_auto.timing = -1; }   // RT_OPT_FRAME_KERNEL = 255
+    fk_auto_end_frame(f);                                // RT_OPT_FRAME_KERNEL = 255
     ahead_after_plain_sample(f);
     return RT_OK;
 }
@@ -2405,7 +2436,7 @@ int rt_integrate(rt_frame* f, uint32_t n_samples)       // n x Integrator::Integ
     f->samples_asked += n_samples;
     if (!per_frame && f->slots_opt == 0u && !f->reserved_explicitly && want > f->slots)
     {
-        const uint64_t per_slot = (uint64_t)bytes_per_path(f, want) * (f->n_local ? f->n_local : 1u);
+        const uint64_t per_slot = (uint64_t)bytes_per_path(f, want) * tile_pixels(f);
         const uint64_t lean = std::max<uint64_t>(16u, (f->samples_asked + 7u) / 8u), floor_slots = (8ull << 30) / (per_slot ? per_slot : 1u);
         const uint64_t grown = std::max<uint64_t>(std::max(lean, floor_slots), f->slots);
         if (grown < want) want = (uint32_t)grown;
@@ -2414,12 +2445,11 @@ int rt_integrate(rt_frame* f, uint32_t n_samples)       // n x Integrator::Integ
     // ensure_slots may have halved the batch to fit the device (slots_limit): never ask for more than it got
     if (!per_frame) cap = slot_cap(f) < f->slots ? slot_cap(f) : f->slots;
     if (cap == 0) cap = 1;
-    if (per_frame && chunk_for(f, 1) >= (f->n_local ? f->n_local : 1u) && ensure_whole_tile(f) != RT_OK) return RT_ERROR;
-    if (per_frame && f->chunk_pixels < (f->n_local ? f->n_local : 1u))
+    if (per_frame && chunk_for(f, 1) >= tile_pixels(f) && ensure_whole_tile(f) != RT_OK) return RT_ERROR;
+    if (per_frame && f->chunk_pixels < tile_pixels(f))
         return fail(ctx, "rt_integrate: AOVs / the denoiser need the whole tile in one chunk (raise RT_OPT_PATH_STATE_LIMIT_MB)");
     if (fork_pipes(f) != RT_OK) return RT_ERROR;
     int rc = RT_OK;
-    f->fused = true;
     f->side_active = side_on(f);
     while (done < n_samples && rc == RT_OK)
     {
@@ -2433,35 +2463,35 @@ int rt_integrate(rt_frame* f, uint32_t n_samples)       // n x Integrator::Integ
         // chunks' launches overlap each other's tails.  A chunk always lands on the same pipe: its log replays
         // (k_flush) stay in sample order.
         uint32_t c = 0;
-        for (uint32_t base = 0; base < (f->n_local ? f->n_local : 1u) && rc == RT_OK; ++c)
+        for (uint32_t base = 0; base < tile_pixels(f) && rc == RT_OK; ++c)
         {
-            f->p = &f->ps[c % f->n_pipes];
-            if (generate_rays(f, batch, base, c >= f->n_pipes) != RT_OK) { rc = RT_ERROR; break; }
-            rc = trace_bounces(f, per_frame);
+            PathPipe& p = f->ps[c % f->n_pipes];
+            if (generate_rays(f, p, batch, base, c >= f->n_pipes) != RT_OK) { rc = RT_ERROR; break; }
+            rc = trace_bounces(f, p, per_frame);
             // Compact log layout: did this sequence run the overflow pool dry?  (The one host synchronisation of a batch; the
             // full layout has none.)  If so nothing of it has reached the radiance yet: drop it, switch the frame to the full
             // layout within the same memory, and run the SAME chunk again -- the sum stays exact.
             if (rc == RT_OK && f->log_ovf_blocks != 0u)
             {
                 uint32_t dry = 0;
-                if (wait_shadow(f, 0) != RT_OK || wait_shadow(f, 1) != RT_OK) { rc = RT_ERROR; break; }
-                if (hipMemcpyAsync(&dry, &f->p->counters->log_ovf_flag, sizeof(dry), hipMemcpyDeviceToHost, f->p->stream) != hipSuccess ||
-                    hipStreamSynchronize(f->p->stream) != hipSuccess)
+                if (wait_shadow(f, p, 0) != RT_OK || wait_shadow(f, p, 1) != RT_OK) { rc = RT_ERROR; break; }
+                if (hipMemcpyAsync(&dry, &p.counters->log_ovf_flag, sizeof(dry), hipMemcpyDeviceToHost, p.stream) != hipSuccess ||
+                    hipStreamSynchronize(p.stream) != hipSuccess)
                 {
                     rc = fail(ctx, "rt_integrate: reading the log-pool flag failed");
                     break;
                 }
                 if (dry)
                 {
-                    if (hipMemsetAsync(f->p->counters->queue, 0, sizeof(f->p->counters->queue) + sizeof(f->p->counters->shadow), f->p->stream) != hipSuccess ||
-                        hipMemsetAsync(&f->p->counters->log_ovf_flag, 0, sizeof(uint32_t), f->p->stream) != hipSuccess ||
-                        hipStreamSynchronize(f->p->stream) != hipSuccess)
+                    if (hipMemsetAsync(p.counters->queue, 0, sizeof(p.counters->queue) + sizeof(p.counters->shadow), p.stream) != hipSuccess ||
+                        hipMemsetAsync(&p.counters->log_ovf_flag, 0, sizeof(uint32_t), p.stream) != hipSuccess ||
+                        hipStreamSynchronize(p.stream) != hipSuccess)
                     {
                         rc = fail(ctx, "rt_integrate: discarding a batch failed");
                         break;
                     }
-                    f->p->cur_slots = 0;
-                    f->p->shadow_pending = false;
+                    p.cur_slots = 0;
+                    p.shadow_pending = false;
                     f->log_full_forced = true;
                     // the full layout takes more bytes per path: it may use what the library would have given it in the first
                     // place (half of the HBM), and beyond that runs the same batch size in more chunks
@@ -2471,17 +2501,14 @@ int rt_integrate(rt_frame* f, uint32_t n_samples)       // n x Integrator::Integ
                     continue;                                                                   // the same `base`, the new chunk size
                 }
             }
-            if (rc == RT_OK && flush_log(f) != RT_OK) rc = RT_ERROR;          // radiance_buffer_ += this chunk's contributions
+            if (rc == RT_OK && flush_log(f, p) != RT_OK) rc = RT_ERROR;       // radiance_buffer_ += this chunk's contributions
             base += f->chunk_pixels;
         }
-        f->p = &f->ps[0];
         if (rc != RT_OK) break;
         f->sample_count += batch;                                            // AdvanceSampleCount, :510-514
         if (f->denoiser && (join_pipes(f) != RT_OK || rt_denoise(f) != RT_OK || rt_copy_history(f) != RT_OK)) rc = RT_ERROR;
         done += batch;
     }
-    f->p = &f->ps[0];
-    f->fused = false;
     if (rc != RT_OK)
         for (PathPipe& q : f->ps)                        // a failed batch leaves no shadow trace running behind the caller's back
         {
@@ -2647,18 +2674,12 @@ static int ensure_guides(rt_frame* f, const char* who)
     HIPCHK(ctx, filt::guide_rays(ctx->stream, f->tile.width, f->tile.height, f->camera, rt_tanf(0.5f * f->camera.fov), g->o4, g->d4));
     HIPCHK(ctx, hipMemsetD32Async((hipDeviceptr_t)g->count, (int)n, 1, ctx->stream));
     {
-        // the closest-hit trace through launch_trace's per-ray kernel k_trace_v1<false> (the reference's BVH2 walk), pointed at the filter's own hits,
-        // spill area and the context's stream for this one launch.  (Through launch_trace and not a launch of its own: a new use of the template kernel
-        // here moves where clang places its code, and the hot path's code object -- codeobj.code_object_sha256 -- must stay byte for byte what it is.)
-        PathPipe guide_pipe;
-        guide_pipe.hits = g->hits;
-        PathPipe* const keep_p = f->p;
-        const hipStream_t keep_stream = f->tl_stream;
-        uint2* const keep_spill = f->tl_spill;
-        const uint32_t keep_variant = f->trace_variant, keep_waves = f->trace_waves_per_cu;
-        f->p = &guide_pipe; f->tl_stream = ctx->stream; f->tl_spill = g->spill; f->trace_variant = 0; f->trace_waves_per_cu = 0;   // grid = trace_blocks
-        launch_trace<false>(f, g->o4, g->d4, (const uint32_t*)nullptr, g->count, 0);
-        f->p = keep_p; f->tl_stream = keep_stream; f->tl_spill = keep_spill; f->trace_variant = keep_variant; f->trace_waves_per_cu = keep_waves;
+        // the closest-hit trace through launch_trace's per-ray kernel k_trace_v1<false> (variant 0: the reference's BVH2 walk; waves 0: the grid is trace_blocks), on the
+        // context's stream with the filter's own hits and spill area; a closest-hit trace logs nothing and that kernel counts nothing.  (Through launch_trace and
+        // not a launch of its own: a new use of the template kernel here moves where clang places its code, and the hot path's code object --
+        // codeobj.code_object_sha256 -- must stay byte for byte what it is.)
+        const TraceTarget t = {ctx->stream, g->spill, nullptr, 0u, g->hits, DLog{}, nullptr, (uint64_t)n, 0u, 0u, 0u};
+        launch_trace<false>(f, t, g->o4, g->d4, (const uint32_t*)nullptr, g->count);
     }
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, filt::guide_values(ctx->stream, ctx->scene.d, g->o4, g->hits, (uint32_t)n, g->alb, g->nz));
@@ -3074,9 +3095,10 @@ int rt_frame_debug_read_queue(rt_frame* f, int which, uint32_t bounce, rt_ray* r
     if (bounce > RT_MAX_BOUNCES_LIMIT + 1) return fail(ctx, "rt_frame_debug_read_queue: bounce out of range");
     if (f->stage_chunks > 1) return fail(ctx, "rt_frame_debug_read_queue: the sample in flight is spread over several pipes (set RT_OPT_STAGE_PIPES to 1 for the debug readers)");
     if (f->deferred.active && deferred_materialize(f) != RT_OK) return RT_ERROR;
-    if (f->p->side) HIPCHK(ctx, hipStreamSynchronize(f->p->side));      // a shadow trace may be retracting log entries
+    const PathPipe& q = f->ps[0];                                          // (one chunk: the sample in flight is on pipe 0)
+    if (q.side) HIPCHK(ctx, hipStreamSynchronize(q.side));                 // a shadow trace may be retracting log entries
     DCounters h;
-    HIPCHK(ctx, hipMemcpyAsync(&h, f->p->counters, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(&h, q.counters, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     uint32_t n = which == 0 ? h.queue[bounce] : h.shadow[bounce];
     if (n > f->log_stride) return fail(ctx, "rt_frame_debug_read_queue: corrupt counter");
@@ -3084,28 +3106,28 @@ int rt_frame_debug_read_queue(rt_frame* f, int which, uint32_t bounce, rt_ray* r
     if (n == 0) return RT_OK;
     if (!rays && !pixel_indices && !payload) return RT_OK;                 // size query (two-call pattern)
     if (n > capacity) return fail(ctx, "rt_frame_debug_read_queue: the queue holds more entries than the caller's arrays");
-    const float4* so = which == 0 ? f->p->o4[bounce & 1u] : f->p->sh_o4[bounce & 1u];
-    const float4* sdir = which == 0 ? f->p->d4[bounce & 1u] : f->p->sh_d4[bounce & 1u];
+    const float4* so = which == 0 ? q.o4[bounce & 1u] : q.sh_o4[bounce & 1u];
+    const float4* sdir = which == 0 ? q.d4[bounce & 1u] : q.sh_d4[bounce & 1u];
     std::vector<float4> o(n), d(n), p(n);
     HIPCHK(ctx, hipMemcpy(o.data(), so, (size_t)n * 16, hipMemcpyDeviceToHost));
     HIPCHK(ctx, hipMemcpy(d.data(), sdir, (size_t)n * 16, hipMemcpyDeviceToHost));
-    if (which == 0) HIPCHK(ctx, hipMemcpy(p.data(), f->p->thr[bounce & 1u], (size_t)n * 16, hipMemcpyDeviceToHost));
+    if (which == 0) HIPCHK(ctx, hipMemcpy(p.data(), q.thr[bounce & 1u], (size_t)n * 16, hipMemcpyDeviceToHost));
     for (uint32_t i = 0; i < n; ++i)
     {
         uint32_t pl;
         memcpy(&pl, &d[i].w, 4);
         uint32_t id = pl;
-        uint32_t local_pix = f->p->chunk_base + id % (f->chunk_pixels ? f->chunk_pixels : 1);
+        uint32_t local_pix = q.chunk_base + id % (f->chunk_pixels ? f->chunk_pixels : 1);
         if (which == 1)   // the deferred direct-light sample lives in the radiance log
         {
             uint32_t entry = 0;
-            HIPCHK(ctx, hipMemcpy(&entry, f->p->sh_aux[bounce & 1u] + i, 4, hipMemcpyDeviceToHost));
+            HIPCHK(ctx, hipMemcpy(&entry, q.sh_aux[bounce & 1u] + i, 4, hipMemcpyDeviceToHost));
             p[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
             uint32_t oblk = 0;
-            if (entry >= f->log_inline) HIPCHK(ctx, hipMemcpy(&oblk, f->p->ovf_slot + id, 4, hipMemcpyDeviceToHost));
+            if (entry >= f->log_inline) HIPCHK(ctx, hipMemcpy(&oblk, q.ovf_slot + id, 4, hipMemcpyDeviceToHost));
             const size_t at = entry < f->log_inline ? (size_t)entry * f->log_stride + id
                                                     : (size_t)f->log_inline * f->log_stride + (size_t)(entry - f->log_inline) * f->log_ovf_blocks + oblk;
-            HIPCHK(ctx, hipMemcpy(&p[i], f->p->rlog + 3u * at, 12, hipMemcpyDeviceToHost));
+            HIPCHK(ctx, hipMemcpy(&p[i], q.rlog + 3u * at, 12, hipMemcpyDeviceToHost));
         }
         if (rays)
         {
@@ -3133,7 +3155,7 @@ int rt_frame_debug_read_hits(rt_frame* f, rt_hit* hits, uint32_t count)
     if (f->deferred.active && deferred_materialize(f) != RT_OK) return RT_ERROR;
     std::vector<float4> h(count ? count : 1);
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    HIPCHK(ctx, hipMemcpy(h.data(), f->p->hits, (size_t)count * 16, hipMemcpyDeviceToHost));
+    HIPCHK(ctx, hipMemcpy(h.data(), f->ps[0].hits, (size_t)count * 16, hipMemcpyDeviceToHost));
     for (uint32_t i = 0; i < count; ++i)
     {
         hits[i].bc.x = h[i].x; hits[i].bc.y = h[i].y;

@@ -33,7 +33,7 @@ static int ahead_holds(const rt_frame* f, uint32_t s)
 // 128 together 1.56; the 4K / 16-bounce config: 22.7 / 19.4 / 17.9 ms at 1 / 2 / 4 -- profiles/r06_call01.log), within 64 GiB of path state for the two banks.
 static uint32_t ahead_depth(const rt_frame* f)
 {
-    const uint64_t n = f->n_local ? f->n_local : 1u;
+    const uint64_t n = tile_pixels(f);
     uint64_t k = f->ahead_opt & 0xFFu;
     if (k == 0) return 0;
     if (k == 1 || k == 255) { k = (32000000ull + n - 1) / n; if (k > 64) k = 64; }
@@ -111,7 +111,7 @@ static int ahead_configure(rt_frame* f)
         h->trace_tail_paths = f->trace_tail_paths;
         h->small_launch_paths = f->small_launch_paths; h->small_launch_set = f->small_launch_set;
         if (ensure_slots(h, want.depth) != RT_OK) return RT_ERROR;
-        if (h->slots < 2u || h->chunk_pixels < (f->n_local ? f->n_local : 1u)) return fail(ctx, "RT_OPT_SAMPLES_AHEAD: a bank could not be laid out for the whole tile");
+        if (h->slots < 2u || h->chunk_pixels < tile_pixels(f)) return fail(ctx, "RT_OPT_SAMPLES_AHEAD: a bank could not be laid out for the whole tile");
     }
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));       // the banks' allocations were cleared on the context's stream
     A.depth = std::min(want.depth, std::min(A.bank[0].h->slots, A.bank[1].h->slots));
@@ -134,21 +134,19 @@ static int ahead_launch(rt_frame* f, int i, uint32_t base, uint32_t n)
     // behind whatever the owner's stream holds: the last replay out of this bank's log
     HIPCHK(ctx, hipEventRecord(b.order, ctx->stream));
     HIPCHK(ctx, hipStreamWaitEvent(st, b.order, 0));
-    h->p = &h->ps[0];
-    h->fused = true;
+    PathPipe& p = h->ps[0];
     h->side_active = side_on(h);
-    int rc = generate_rays(h, n, 0, false);
-    if (rc == RT_OK) rc = trace_bounces(h, false);
-    if (rc == RT_OK && (wait_shadow(h, 0) != RT_OK || wait_shadow(h, 1) != RT_OK)) rc = RT_ERROR;
-    h->fused = false;
+    int rc = generate_rays(h, p, n, 0, false);
+    if (rc == RT_OK) rc = trace_bounces(h, p, false);
+    if (rc == RT_OK && (wait_shadow(h, p, 0) != RT_OK || wait_shadow(h, p, 1) != RT_OK)) rc = RT_ERROR;
     if (rc == RT_OK && hipEventRecord(b.done, st) != hipSuccess) rc = fail(ctx, "RT_OPT_SAMPLES_AHEAD: recording a batch's end failed");
     if (rc != RT_OK)
     {
         // nothing of a batch that could not be enqueued is ever replayed
         (void)hipGetLastError();
         (void)sync_frame_streams(h);
-        (void)hipMemsetAsync(h->ps[0].cnt, 0, (size_t)h->log_stride * sizeof(uint32_t), st);
-        h->ps[0].cur_slots = 0; h->ps[0].shadow_pending = false; h->ps[0].shadow_in_flight[0] = h->ps[0].shadow_in_flight[1] = false;
+        (void)hipMemsetAsync(p.cnt, 0, (size_t)h->log_stride * sizeof(uint32_t), st);
+        p.cur_slots = 0; p.shadow_pending = false; p.shadow_in_flight[0] = p.shadow_in_flight[1] = false;
         b.n = b.next = 0;
         return RT_ERROR;
     }
@@ -168,7 +166,7 @@ static int ahead_consume(rt_frame* f, int i)
     rt_frame* h = b.h;
     HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, b.done, 0));
     const uint32_t blocks = (f->n_local + 255u) / 256u;
-    hipLaunchKernelGGL(k_flush, dim3(blocks), dim3(256), 0, ctx->stream, f->radiance, dlog(h), f->n_local, 1u, h->chunk_pixels, 0u, b.next);
+    hipLaunchKernelGGL(k_flush, dim3(blocks), dim3(256), 0, ctx->stream, f->radiance, dlog(h, h->ps[0]), f->n_local, 1u, h->chunk_pixels, 0u, b.next);
     HIPCHK(ctx, hipGetLastError());
     ++b.next;
     ++f->sample_count;

@@ -314,6 +314,46 @@ def test_stage_pipes_carry_one_sample_as_chunks_on_streams_of_their_own(golden_s
     one.close(); ctx.close()
 
 
+def test_guide_pass_between_the_stages_of_a_sample_on_several_pipes_disturbs_nothing(golden_scenes):
+    """The guide pass (rt_frame_read_guides) launches its one trace on the context's stream with the filter's own hits and spill area.  Its FIRST
+    launch in the middle of a stage-API sample whose chunks travel on two pipes (RT_OPT_STAGE_PIPES = 2) -- between rt_intersect(0) and rt_shade(0) --
+    and a second call served from the cache between rt_shade(1) and rt_intersect_shadow(1) leave the sample's later launches on their own pipes:
+    same radiance, ray counters and guides, bit for bit, as a frame that runs its samples undisturbed and reads the guides afterwards."""
+    w, h, b = 640, 416, 3                                    # the stage-pipes test's shape: the smallest that has two pipes
+    sc = golden_scenes["coverage"]
+    cam = T.default_camera(w, h)
+    ctx = capi.Context(0)
+    ctx.upload_scene(sc)
+    def run(disturb):
+        fr = capi.Frame(ctx, w, h)
+        fr.set_camera(cam); fr.set_max_bounces(b)
+        fr.set_option(capi.OPT_STAGE_PIPES, 2)
+        for sample in range(3):
+            fr.generate_rays()
+            for bounce in range(b + 1):
+                fr.intersect(bounce)
+                if disturb and sample == 0 and bounce == 0:
+                    assert fr.guides()[3] == 1               # the guide pass's first launch
+                fr.shade(bounce)
+                if disturb and sample == 0 and bounce == 1:
+                    assert fr.guides()[3] == 1               # served from the cache
+                fr.intersect_shadow(bounce)
+            fr.advance_sample()
+        rad, st = fr.radiance().copy(), fr.stats()
+        assert st.pipelines == 2 and st.chunk_pixels < w * h
+        alb, nrm, dep, passes = fr.guides()
+        assert passes == 1
+        fr.close()
+        return rad, st, alb, nrm, dep
+    rad_a, st_a, alb_a, nrm_a, dep_a = run(False)
+    rad_b, st_b, alb_b, nrm_b, dep_b = run(True)
+    assert rad_b.tobytes() == rad_a.tobytes()
+    assert (st_b.closest_rays, st_b.shadow_rays) == (st_a.closest_rays, st_a.shadow_rays)
+    assert list(st_b.last_active[:4]) == list(st_a.last_active[:4]) and list(st_b.last_shadow[:4]) == list(st_a.last_shadow[:4])
+    assert alb_b.tobytes() == alb_a.tobytes() and nrm_b.tobytes() == nrm_a.tobytes() and dep_b.tobytes() == dep_a.tobytes()
+    ctx.close()
+
+
 def test_pipelined_chunks_on_several_streams_are_bit_identical(golden_scenes):
     """RT_OPT_PIPELINES: a large batch (>= 4 M paths) is cut into chunks that travel through the wavefront loop on
     separate pipes (per-path buffers + HIP stream each) so that launch tails overlap.  1, 2, 3 and 4 pipes, with and
