@@ -25,7 +25,7 @@ bool launch(hipStream_t stream, query::Scratch& q, const DScene& sc, bool use_wi
     uint32_t hit_stride = 1u;
     if (!hits && d_surfaces) { hits = (float4*)d_surfaces; hit_stride = 4u; }
     const uint32_t blocks = query::prepare(stream, q, &q.status, compute_units, max_hits > 0u && hits ? RT_ALL_HITS_LIST_WAVES_PER_CU : RT_ALL_HITS_COUNT_WAVES_PER_CU,
-        n / 64u + (n % 64u != 0u ? 1u : 0u));
+        dev::blocks_for(n, 64u));
     if (blocks == 0u) return false;
     if (max_hits > 0u && hits)
         hipLaunchKernelGGL(k_all_hits<true>, dim3(blocks), dim3(64), 0, stream, sc, (const float4*)d_rays, n, max_hits, (float4*)d_out, hits, hit_stride, q.spill,
@@ -33,13 +33,13 @@ bool launch(hipStream_t stream, query::Scratch& q, const DScene& sc, bool use_wi
     else
         hipLaunchKernelGGL(k_all_hits<false>, dim3(blocks), dim3(64), 0, stream, sc, (const float4*)d_rays, n, max_hits, (float4*)d_out, (float4*)nullptr, 1u, q.spill,
             use_wide ? 1u : 0u, q.status);
-    if (!query::clean()) return false;
+    if (!dev::clean()) return false;
     if (d_surfaces && max_hits > 0u)
     {
         const unsigned long long total = (unsigned long long)n * max_hits;
-        hipLaunchKernelGGL(k_all_hits_surface, dim3((uint32_t)((total + 255ull) / 256ull)), dim3(256), 0, stream, sc.tris_sh, n_tris, object_of_triangle,
+        hipLaunchKernelGGL(k_all_hits_surface, dim3(dev::blocks_for(total, 256u)), dim3(256), 0, stream, sc.tris_sh, n_tris, object_of_triangle,
             (const float4*)d_rays, (const float4*)hits, hit_stride, max_hits, total, (float4*)d_surfaces);
-        if (!query::clean()) return false;
+        if (!dev::clean()) return false;
     }
     return true;
 }
@@ -125,7 +125,7 @@ void brute_host(const rt_bvh_node* nodes, uint32_t nn, const rt_triangle* tris, 
 bool brute_device(hipStream_t stream, const rt_bvh_node* nodes, uint32_t nn, const rt_triangle* tris, uint32_t n_tris, const rt_ray* rays, uint32_t n,
     uint32_t max_hits, rt_ray_hits* out, rt_hit* hits)
 {
-    query::DeviceTemps tmp(stream);
+    dev::Temps tmp(stream);
     void* const d_nodes = tmp.get(nodes, (size_t)nn * sizeof(rt_bvh_node));
     void* const d_tris = tmp.get(tris, (size_t)n_tris * sizeof(rt_triangle));
     void* const d_rays = tmp.get(rays, (size_t)n * sizeof(rt_ray));
@@ -133,9 +133,9 @@ bool brute_device(hipStream_t stream, const rt_bvh_node* nodes, uint32_t nn, con
     void* const d_hits = tmp.get(nullptr, (size_t)n * max_hits * sizeof(rt_hit));
     bool ok = d_nodes && d_tris && d_rays && d_out && d_hits;
     if (ok)
-        hipLaunchKernelGGL(k_all_hits_brute, dim3(n / 256u + (n % 256u != 0u ? 1u : 0u)), dim3(256), 0, stream, (const rt_bvh_node*)d_nodes, nn, (const rt_triangle*)d_tris,
+        hipLaunchKernelGGL(k_all_hits_brute, dim3(dev::blocks_for(n, 256u)), dim3(256), 0, stream, (const rt_bvh_node*)d_nodes, nn, (const rt_triangle*)d_tris,
             (const float4*)d_rays, n, max_hits, (float4*)d_out, (float4*)d_hits);
-    ok = ok && query::clean();
+    ok = ok && dev::clean();
     if (ok && max_hits > 0u) ok = hipMemcpyAsync(hits, d_hits, (size_t)n * max_hits * sizeof(rt_hit), hipMemcpyDeviceToHost, stream) == hipSuccess;
     return tmp.finish(ok, out, d_out, (size_t)n * sizeof(rt_ray_hits));
 }

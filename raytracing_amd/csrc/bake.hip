@@ -26,11 +26,11 @@ bool launch(hipStream_t stream, query::Scratch& s, uint32_t** status, const DSce
 {
     if (n == 0u) return true;
     const uint32_t per_wave = d.samples < 64u ? 64u / d.samples : 1u;
-    const uint32_t blocks = query::prepare(stream, s, status, compute_units, RT_BAKE_WAVES_PER_CU, n / per_wave + (n % per_wave != 0u ? 1u : 0u));
+    const uint32_t blocks = query::prepare(stream, s, status, compute_units, RT_BAKE_WAVES_PER_CU, dev::blocks_for(n, per_wave));
     if (blocks == 0u) return false;
     hipLaunchKernelGGL(k_bake, dim3(blocks), dim3(64), 0, stream, sc, (const float4*)d_points, (d.flags & RT_BAKE_FROM_SURFACES) ? 1u : 0u, n, first_index, d.samples,
         d.seed, d.bias, d.radius, (float4*)d_out, s.spill, use_wide ? 1u : 0u, *status);
-    return query::clean();
+    return dev::clean();
 }
 
 void debug_rays_host(const void* points, uint32_t n, uint32_t first_index, const rt_bake_desc& d, rt_ray* out)
@@ -59,14 +59,14 @@ void debug_rays_host(const void* points, uint32_t n, uint32_t first_index, const
 bool debug_rays_device(hipStream_t stream, const void* points, uint32_t n, uint32_t first_index, const rt_bake_desc& d, rt_ray* out)
 {
     const size_t n_rays = (size_t)n * d.samples;
-    query::DeviceTemps tmp(stream);
+    dev::Temps tmp(stream);
     void* const d_points = tmp.get(points, (size_t)n * point_bytes(d));
     void* const d_rays = tmp.get(nullptr, n_rays * sizeof(rt_ray));
     const bool ok = d_points && d_rays;
     if (ok)
-        hipLaunchKernelGGL(k_bake_rays, dim3((uint32_t)((n_rays + 255u) / 256u)), dim3(256), 0, stream, (const float4*)d_points, (d.flags & RT_BAKE_FROM_SURFACES) ? 1u : 0u, n,
+        hipLaunchKernelGGL(k_bake_rays, dim3(dev::blocks_for(n_rays, 256u)), dim3(256), 0, stream, (const float4*)d_points, (d.flags & RT_BAKE_FROM_SURFACES) ? 1u : 0u, n,
             first_index, d.samples, d.seed, d.bias, d.radius, (float4*)d_rays);
-    return tmp.finish(ok && query::clean(), out, d_rays, n_rays * sizeof(rt_ray));
+    return tmp.finish(ok && dev::clean(), out, d_rays, n_rays * sizeof(rt_ray));
 }
 
 void debug_reduce_host(const rt_ray* rays, const uint32_t* occluded, uint32_t n, uint32_t samples, rt_bake_result* out)

@@ -52,15 +52,14 @@ int rt_debug_device_fold(rt_ctx* ctx, const rt_bvh_node* nodes, uint32_t num_nod
         m.iso = iso_weight;
         for (uint32_t i = 0; i < n_dirs && dirs; ++i) m.dirs.push_back({std::fabs((double)dirs[3 * i]), std::fabs((double)dirs[3 * i + 1]), std::fabs((double)dirs[3 * i + 2])});
     }
-    void* d_nodes = nullptr;
-    if (dev_alloc_copy(ctx, &d_nodes, nodes, (size_t)num_nodes * sizeof(rt_bvh_node)) != RT_OK) return RT_ERROR;
+    dev::Mem d_nodes;
+    if (dev_fill(ctx, "rt_debug_device_fold", d_nodes, nodes, (size_t)num_nodes * sizeof(rt_bvh_node)) != RT_OK) return RT_ERROR;
     WideNode* d_recs = nullptr;
     std::vector<uint32_t> folded;
     std::vector<WideNode> wide;
-    const bool ok = devfold::fold(ctx->stream, (const rt_bvh_node*)d_nodes, num_nodes, nodes[0], with_metric ? &m : nullptr, weights, &d_recs, num_records, entry_ref, &folded, &wide, nullptr, seconds);
+    const bool ok = devfold::fold(ctx->stream, d_nodes.get<const rt_bvh_node>(), num_nodes, nodes[0], with_metric ? &m : nullptr, weights, &d_recs, num_records, entry_ref, &folded, &wide, nullptr, seconds);
+    const dev::Mem folded_records(d_recs);                          // the fold's records are the caller's to free; only the host copies are wanted here
     (void)hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d_nodes);
-    if (d_recs) (void)hipFree(d_recs);
     if (!ok) return fail(ctx, "rt_debug_device_fold: the tree does not qualify for the 4-wide layout, or the device path failed");
     if (records)
     {
@@ -79,15 +78,14 @@ int rt_debug_device_tree(rt_ctx* ctx, const rt_bvh_node* nodes, uint32_t num_nod
     ownbvh::Metric m;
     m.iso = iso_weight;
     for (uint32_t i = 0; i < n_dirs && dirs; ++i) m.dirs.push_back({std::fabs((double)dirs[3 * i]), std::fabs((double)dirs[3 * i + 1]), std::fabs((double)dirs[3 * i + 2])});
-    void* d_nodes = nullptr;
-    if (dev_alloc_copy(ctx, &d_nodes, nodes, (size_t)num_nodes * sizeof(rt_bvh_node)) != RT_OK) return RT_ERROR;
+    dev::Mem d_nodes;
+    if (dev_fill(ctx, "rt_debug_device_tree", d_nodes, nodes, (size_t)num_nodes * sizeof(rt_bvh_node)) != RT_OK) return RT_ERROR;
     rt_bvh_node* d_tree = nullptr;
     uint32_t n = 0;
     std::vector<rt_bvh_node> tree;
-    const bool ok = devfold::build_tree(ctx->stream, (const rt_bvh_node*)d_nodes, num_nodes, nodes[0], &m, &d_tree, &n, &tree, nullptr, seconds, rounds, frame_dir, radius, stretch);
+    const bool ok = devfold::build_tree(ctx->stream, d_nodes.get<const rt_bvh_node>(), num_nodes, nodes[0], &m, &d_tree, &n, &tree, nullptr, seconds, rounds, frame_dir, radius, stretch);
+    const dev::Mem built_tree(d_tree);                              // likewise: only the host copy is wanted here
     (void)hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d_nodes);
-    if (d_tree) (void)hipFree(d_tree);
     if (!ok) return fail(ctx, "rt_debug_device_tree: nothing to build (leaf root), or the device path failed");
     *num_out = n;
     if (out_nodes)
@@ -219,11 +217,10 @@ int rt_debug_count_box_passes(rt_ctx* ctx, const rt_bvh_node* nodes, uint32_t nu
     else
     {
         (void)hipSetDevice(ctx->device);
-        void* d_nodes = nullptr;
-        if (dev_alloc_copy(ctx, &d_nodes, nodes, (size_t)num_nodes * sizeof(rt_bvh_node)) != RT_OK) return RT_ERROR;
-        const bool ok = devfold::count_box_passes(ctx->stream, (const rt_bvh_node*)d_nodes, num_nodes, o.data(), d.data(), o.size(), got, &cut_short);
+        dev::Mem d_nodes;
+        if (dev_fill(ctx, "rt_debug_count_box_passes", d_nodes, nodes, (size_t)num_nodes * sizeof(rt_bvh_node)) != RT_OK) return RT_ERROR;
+        const bool ok = devfold::count_box_passes(ctx->stream, d_nodes.get<const rt_bvh_node>(), num_nodes, o.data(), d.data(), o.size(), got, &cut_short);
         (void)hipStreamSynchronize(ctx->stream);
-        (void)hipFree(d_nodes);
         if (!ok) return fail(ctx, "rt_debug_count_box_passes: the device path failed");
     }
     memcpy(counts, got.data(), (size_t)num_nodes * sizeof(uint32_t));

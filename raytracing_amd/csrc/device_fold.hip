@@ -9,26 +9,14 @@
 #include <chrono>
 #include <cmath>
 #include "device_fold.h"
+#include "device_memory.h"
 #include "fold_kernels.h"
 #include "ploc_kernels.h"
 #include <hipcub/hipcub.hpp>
 
 namespace devfold
 {
-struct Buffers
-{
-    std::vector<void*> all;
-    ~Buffers() { for (void* p : all) if (p) (void)hipFree(p); }
-    template <class T> bool get(T*& out, size_t count)
-    {
-        void* p = nullptr;
-        if (hipMalloc(&p, count * sizeof(T) + 16) != hipSuccess) { (void)hipGetLastError(); out = nullptr; return false; }
-        all.push_back(p);
-        out = (T*)p;
-        return true;
-    }
-    void release(void* p) { for (void*& q : all) if (q == p) q = nullptr; }     // ownership goes to the caller
-};
+enum { TAIL = 16 };       // bytes every array here gets beyond its elements (dev::alloc)
 
 static FoldMetric metric_of(const ownbvh::Metric* m)
 {
@@ -57,7 +45,7 @@ bool fold(hipStream_t stream, const rt_bvh_node* d_nodes, uint32_t nn, const rt_
     if (metric && metric->dirs.size() > 8u) return false;
     if (nn < 3u) return false;
     auto cancelled = [&]() { return cancel && cancel->load(std::memory_order_relaxed); };
-    Buffers buf;
+    dev::Temps buf(stream, TAIL);
     FoldState s;
     memset(&s, 0, sizeof(s));
     s.nodes = d_nodes; s.nn = nn;
@@ -66,13 +54,13 @@ bool fold(hipStream_t stream, const rt_bvh_node* d_nodes, uint32_t nn, const rt_
     uint32_t *frontier[2] = {nullptr, nullptr}, *d_counts = nullptr, *block_sums = nullptr, *d_roots = nullptr;
     const uint32_t scan_blocks = (nn + FOLD_SCAN_BLOCK - 1u) / FOLD_SCAN_BLOCK;
     const uint32_t max_records = nn / 2u + 1u;
-    bool ok = buf.get(s.parent, nn) && buf.get(s.arrived, nn) && buf.get(s.T, nn) && buf.get(s.F, (size_t)nn * 3u) && buf.get(s.split, (size_t)nn * 3u) &&
-              buf.get(s.open, nn) && buf.get(s.is_root, nn) && buf.get(s.depth, nn) && buf.get(s.error, 1) && buf.get(frontier[0], max_records) &&
-              buf.get(frontier[1], max_records) && buf.get(d_counts, 4) && buf.get(block_sums, scan_blocks + 1u) && buf.get(d_roots, max_records);
-    if (ok && host_weights) ok = buf.get(d_weights, nn) && hipMemcpyAsync(d_weights, host_weights, (size_t)nn * sizeof(double), hipMemcpyHostToDevice, stream) == hipSuccess;
+    bool ok = buf.array(s.parent, nn) && buf.array(s.arrived, nn) && buf.array(s.T, nn) && buf.array(s.F, (size_t)nn * 3u) && buf.array(s.split, (size_t)nn * 3u) &&
+              buf.array(s.open, nn) && buf.array(s.is_root, nn) && buf.array(s.depth, nn) && buf.array(s.error, 1) && buf.array(frontier[0], max_records) &&
+              buf.array(frontier[1], max_records) && buf.array(d_counts, 4) && buf.array(block_sums, scan_blocks + 1u) && buf.array(d_roots, max_records);
+    if (ok && host_weights) ok = buf.array(d_weights, nn) && hipMemcpyAsync(d_weights, host_weights, (size_t)nn * sizeof(double), hipMemcpyHostToDevice, stream) == hipSuccess;
     if (!ok) { (void)hipGetLastError(); return false; }
     s.weights = d_weights;
-    const uint32_t node_blocks = (nn + 255u) / 256u;
+    const uint32_t node_blocks = dev::blocks_for(nn, 256u);
     ok = hipMemsetAsync(s.error, 0, sizeof(int), stream) == hipSuccess && hipMemsetAsync(s.open, 0, nn, stream) == hipSuccess &&
          hipMemsetAsync(s.split, 0, (size_t)nn * 3u, stream) == hipSuccess;
     if (!ok) { (void)hipGetLastError(); return false; }
@@ -90,7 +78,7 @@ bool fold(hipStream_t stream, const rt_bvh_node* d_nodes, uint32_t nn, const rt_
         uint32_t* cur = frontier[(level - 1u) & 1u]; uint32_t* nxt = frontier[level & 1u];
         ok = hipMemsetAsync(d_counts, 0, sizeof(uint32_t), stream) == hipSuccess;
         if (!ok) break;
-        hipLaunchKernelGGL(k_fold_roots, dim3((n_front + 255u) / 256u), dim3(256), 0, stream, s, (const uint32_t*)cur, n_front, nxt, d_counts, level);
+        hipLaunchKernelGGL(k_fold_roots, dim3(dev::blocks_for(n_front, 256u)), dim3(256), 0, stream, s, (const uint32_t*)cur, n_front, nxt, d_counts, level);
         uint32_t got[2] = {0, 0};
         ok = hipMemcpyAsync(&got[0], d_counts, sizeof(uint32_t), hipMemcpyDeviceToHost, stream) == hipSuccess &&
              hipMemcpyAsync(&err, s.error, sizeof(int), hipMemcpyDeviceToHost, stream) == hipSuccess && hipStreamSynchronize(stream) == hipSuccess;
@@ -107,8 +95,8 @@ bool fold(hipStream_t stream, const rt_bvh_node* d_nodes, uint32_t nn, const rt_
     ok = hipMemcpyAsync(&total, d_counts + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, stream) == hipSuccess && hipStreamSynchronize(stream) == hipSuccess;
     if (!ok || total == 0u || total > max_records || total >= (1u << 26)) { (void)hipGetLastError(); return false; }      // 32-bit byte offsets in the kernel
     WideNode* recs = nullptr;
-    if (!buf.get(recs, total)) return false;
-    hipLaunchKernelGGL(k_fold_emit, dim3((total + 63u) / 64u), dim3(64), 0, stream, s, (const uint32_t*)d_roots, total, recs);
+    if (!buf.array(recs, total)) return false;
+    hipLaunchKernelGGL(k_fold_emit, dim3(dev::blocks_for(total, 64u)), dim3(64), 0, stream, s, (const uint32_t*)d_roots, total, recs);
     ok = hipMemcpyAsync(&err, s.error, sizeof(int), hipMemcpyDeviceToHost, stream) == hipSuccess;
     if (ok && roots_out) { roots_out->resize(total); ok = hipMemcpyAsync(roots_out->data(), d_roots, (size_t)total * sizeof(uint32_t), hipMemcpyDeviceToHost, stream) == hipSuccess; }
     if (ok && records_out) { records_out->resize(total); ok = hipMemcpyAsync(records_out->data(), recs, (size_t)total * sizeof(WideNode), hipMemcpyDeviceToHost, stream) == hipSuccess; }
@@ -120,8 +108,7 @@ bool fold(hipStream_t stream, const rt_bvh_node* d_nodes, uint32_t nn, const rt_
         if (records_out) records_out->clear();
         return false;
     }
-    buf.release(recs);
-    *d_records = recs; *n_records = total; *entry_ref = 0;
+    *d_records = buf.keep(recs); *n_records = total; *entry_ref = 0;
     if (seconds) *seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     return true;
 }
@@ -196,34 +183,34 @@ bool build_tree(hipStream_t stream, const rt_bvh_node* d_ref_nodes, uint32_t nn,
     if (metric && metric->dirs.size() > 8u) return false;
     auto cancelled = [&]() { return cancel && cancel->load(std::memory_order_relaxed); };
     const FoldMetric fm = metric_of(metric);
-    Buffers buf;
+    dev::Temps buf(stream, TAIL);
     uint32_t *flags = nullptr, *leaf_nodes = nullptr, *block_sums = nullptr, *d_counts = nullptr, *values = nullptr, *values_sorted = nullptr;
     unsigned long long *keys = nullptr, *keys_sorted = nullptr;
     int* d_err = nullptr;
     const uint32_t scan_blocks = (nn + FOLD_SCAN_BLOCK - 1u) / FOLD_SCAN_BLOCK;
-    bool ok = buf.get(flags, nn) && buf.get(leaf_nodes, nn) && buf.get(block_sums, scan_blocks + 1u) && buf.get(d_counts, 4) && buf.get(d_err, 1);
+    bool ok = buf.array(flags, nn) && buf.array(leaf_nodes, nn) && buf.array(block_sums, scan_blocks + 1u) && buf.array(d_counts, 4) && buf.array(d_err, 1);
     if (!ok) return false;
     ok = hipMemsetAsync(d_err, 0, sizeof(int), stream) == hipSuccess;
-    hipLaunchKernelGGL(k_ploc_flag_leaves, dim3((nn + 255u) / 256u), dim3(256), 0, stream, d_ref_nodes, nn, flags);
+    hipLaunchKernelGGL(k_ploc_flag_leaves, dim3(dev::blocks_for(nn, 256u)), dim3(256), 0, stream, d_ref_nodes, nn, flags);
     uint32_t n_leaves = 0;
     ok = ok && scan_flags(stream, flags, nn, block_sums, d_counts, leaf_nodes, &n_leaves);
     if (!ok || n_leaves < 2u || 2ull * n_leaves - 1u > 0x7FFFFFFFull) { (void)hipGetLastError(); return false; }
     const uint32_t n_nodes = 2u * n_leaves - 1u;
     // Morton order of the leaves
-    ok = buf.get(keys, n_leaves) && buf.get(keys_sorted, n_leaves) && buf.get(values, n_leaves) && buf.get(values_sorted, n_leaves);
+    ok = buf.array(keys, n_leaves) && buf.array(keys_sorted, n_leaves) && buf.array(values, n_leaves) && buf.array(values_sorted, n_leaves);
     if (!ok) return false;
-    const uint32_t leaf_blocks = (n_leaves + 255u) / 256u;
+    const uint32_t leaf_blocks = dev::blocks_for(n_leaves, 256u);
     hipLaunchKernelGGL(k_ploc_keys, dim3(leaf_blocks), dim3(256), 0, stream, d_ref_nodes, (const uint32_t*)leaf_nodes, n_leaves, ploc_frame(root_node, light_dir, stretch > 0.0 ? stretch : 1.0), keys, values);
     size_t temp_bytes = 0;
     void* temp = nullptr;
     if (hipcub::DeviceRadixSort::SortPairs(nullptr, temp_bytes, keys, keys_sorted, values, values_sorted, (int)n_leaves, 0, 63, stream) != hipSuccess) { (void)hipGetLastError(); return false; }
-    { char* t = nullptr; if (!buf.get(t, temp_bytes + 256u)) return false; temp = t; }
+    { char* t = nullptr; if (!buf.array(t, temp_bytes + 256u)) return false; temp = t; }
     if (hipcub::DeviceRadixSort::SortPairs(temp, temp_bytes, keys, keys_sorted, values, values_sorted, (int)n_leaves, 0, 63, stream) != hipSuccess) { (void)hipGetLastError(); return false; }
     // the pool of nodes (leaves first, in Morton order) and the cluster lists
     PlocNode* pool = nullptr;
     uint32_t *parent = nullptr, *cluster[2] = {nullptr, nullptr}, *nearest = nullptr, *keep = nullptr, *merge = nullptr, *keep_list = nullptr, *merge_list = nullptr, *block_sums2 = nullptr;
-    ok = buf.get(pool, n_nodes) && buf.get(parent, n_nodes) && buf.get(cluster[0], n_leaves) && buf.get(cluster[1], n_leaves) && buf.get(nearest, n_leaves) && buf.get(keep, n_leaves) &&
-         buf.get(merge, n_leaves) && buf.get(keep_list, n_leaves) && buf.get(merge_list, n_leaves) && buf.get(block_sums2, (n_leaves + FOLD_SCAN_BLOCK - 1u) / FOLD_SCAN_BLOCK + 1u);
+    ok = buf.array(pool, n_nodes) && buf.array(parent, n_nodes) && buf.array(cluster[0], n_leaves) && buf.array(cluster[1], n_leaves) && buf.array(nearest, n_leaves) && buf.array(keep, n_leaves) &&
+         buf.array(merge, n_leaves) && buf.array(keep_list, n_leaves) && buf.array(merge_list, n_leaves) && buf.array(block_sums2, (n_leaves + FOLD_SCAN_BLOCK - 1u) / FOLD_SCAN_BLOCK + 1u);
     if (!ok) return false;
     hipLaunchKernelGGL(k_ploc_init, dim3(leaf_blocks), dim3(256), 0, stream, d_ref_nodes, (const uint32_t*)leaf_nodes, (const uint32_t*)values_sorted, n_leaves, pool, parent, cluster[0]);
     uint32_t n = n_leaves, next_id = n_leaves, rounds = 0;
@@ -234,7 +221,7 @@ bool build_tree(hipStream_t stream, const rt_bvh_node* d_ref_nodes, uint32_t nn,
     while (n > 1u)
     {
         if (++rounds > round_limit || cancelled()) { (void)hipGetLastError(); return false; }
-        const uint32_t blocks = (n + 255u) / 256u;
+        const uint32_t blocks = dev::blocks_for(n, 256u);
         hipLaunchKernelGGL(k_ploc_nearest, dim3(blocks), dim3(256), 0, stream, (const PlocNode*)pool, (const uint32_t*)cluster[cur], n, fm, radius, nearest);
         hipLaunchKernelGGL(k_ploc_decide, dim3(blocks), dim3(256), 0, stream, (const uint32_t*)nearest, n, keep, merge);
         // positions of the survivors and ids of the new nodes, both in position order (the scan turns a flag into its rank: the flags themselves are needed again, so copies are scanned)
@@ -255,18 +242,17 @@ bool build_tree(hipStream_t stream, const rt_bvh_node* d_ref_nodes, uint32_t nn,
     // sizes, then the reference's linear layout
     uint32_t *arrived = nullptr, *size = nullptr, *index_of = nullptr;
     rt_bvh_node* out = nullptr;
-    ok = buf.get(arrived, n_nodes) && buf.get(size, n_nodes) && buf.get(index_of, n_nodes) && buf.get(out, n_nodes);
+    ok = buf.array(arrived, n_nodes) && buf.array(size, n_nodes) && buf.array(index_of, n_nodes) && buf.array(out, n_nodes);
     ok = ok && hipMemsetAsync(arrived, 0, (size_t)n_nodes * sizeof(uint32_t), stream) == hipSuccess;
     if (!ok) { (void)hipGetLastError(); return false; }
     hipLaunchKernelGGL(k_ploc_sizes, dim3(leaf_blocks), dim3(256), 0, stream, (const PlocNode*)pool, (const uint32_t*)parent, n_leaves, n_nodes, arrived, size, d_err);
-    hipLaunchKernelGGL(k_ploc_emit, dim3((n_nodes + 255u) / 256u), dim3(256), 0, stream, d_ref_nodes, (const PlocNode*)pool, (const uint32_t*)parent, (const uint32_t*)size, n_nodes, root, out, index_of, d_err);
+    hipLaunchKernelGGL(k_ploc_emit, dim3(dev::blocks_for(n_nodes, 256u)), dim3(256), 0, stream, d_ref_nodes, (const PlocNode*)pool, (const uint32_t*)parent, (const uint32_t*)size, n_nodes, root, out, index_of, d_err);
     int err = 0;
     ok = hipMemcpyAsync(&err, d_err, sizeof(int), hipMemcpyDeviceToHost, stream) == hipSuccess;
     if (ok && tree_out) { tree_out->resize(n_nodes); ok = hipMemcpyAsync(tree_out->data(), out, (size_t)n_nodes * sizeof(rt_bvh_node), hipMemcpyDeviceToHost, stream) == hipSuccess; }
     ok = ok && hipStreamSynchronize(stream) == hipSuccess;
     if (!ok || err != FOLD_OK || cancelled()) { (void)hipGetLastError(); if (tree_out) tree_out->clear(); return false; }
-    buf.release(out);
-    *d_tree = out; *n_tree = n_nodes;
+    *d_tree = buf.keep(out); *n_tree = n_nodes;
     if (rounds_out) *rounds_out = rounds;
     if (seconds) *seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     return true;
@@ -278,14 +264,14 @@ bool count_box_passes(hipStream_t stream, const rt_bvh_node* d_nodes, uint32_t n
 {
     counts.assign(nn, 0u);
     if (n_rays == 0 || n_rays > 0x7FFFFFFFull) return n_rays == 0;
-    Buffers buf;
+    dev::Temps buf(stream, TAIL);
     float4 *d_o = nullptr, *d_d = nullptr; uint32_t *d_counts = nullptr, *d_trunc = nullptr;
-    bool ok = buf.get(d_o, n_rays) && buf.get(d_d, n_rays) && buf.get(d_counts, nn) && buf.get(d_trunc, 1);
+    bool ok = buf.array(d_o, n_rays) && buf.array(d_d, n_rays) && buf.array(d_counts, nn) && buf.array(d_trunc, 1);
     ok = ok && hipMemcpyAsync(d_o, o, n_rays * sizeof(float4), hipMemcpyHostToDevice, stream) == hipSuccess &&
          hipMemcpyAsync(d_d, d, n_rays * sizeof(float4), hipMemcpyHostToDevice, stream) == hipSuccess &&
          hipMemsetAsync(d_counts, 0, (size_t)nn * sizeof(uint32_t), stream) == hipSuccess && hipMemsetAsync(d_trunc, 0, sizeof(uint32_t), stream) == hipSuccess;
     if (!ok) { (void)hipGetLastError(); return false; }
-    hipLaunchKernelGGL(k_count_box_passes, dim3((uint32_t)((n_rays + 63u) / 64u)), dim3(64), 0, stream, d_nodes, nn, (const float4*)d_o, (const float4*)d_d, (uint32_t)n_rays, d_counts, d_trunc);
+    hipLaunchKernelGGL(k_count_box_passes, dim3(dev::blocks_for(n_rays, 64u)), dim3(64), 0, stream, d_nodes, nn, (const float4*)d_o, (const float4*)d_d, (uint32_t)n_rays, d_counts, d_trunc);
     uint32_t trunc = 0;
     ok = hipMemcpyAsync(counts.data(), d_counts, (size_t)nn * sizeof(uint32_t), hipMemcpyDeviceToHost, stream) == hipSuccess &&
          hipMemcpyAsync(&trunc, d_trunc, sizeof(uint32_t), hipMemcpyDeviceToHost, stream) == hipSuccess && hipStreamSynchronize(stream) == hipSuccess;

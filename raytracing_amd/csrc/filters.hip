@@ -11,6 +11,7 @@
 #include "kernels_common.h"
 #include "temporal_filter.h"
 #include "filters_host.h"
+#include "device_memory.h"
 
 #include "material_kernels.h"     // ApplyTextures: the albedo guide
 
@@ -289,17 +290,17 @@ void guide_motion_host(const float* records, uint32_t nt, const float* hits, uin
 
 hipError_t guide_motion_device(hipStream_t stream, const float* records, uint32_t nt, const float* hits, uint32_t n, float* prev_pos, float* prev_n)
 {
-    const size_t rb = std::max<size_t>((size_t)nt * 96, 16), pb = (size_t)n * sizeof(float4);
-    float4* d[4] = {nullptr, nullptr, nullptr, nullptr};            // records, hits, prev_pos, prev_n
-    hipError_t e = hipMalloc((void**)&d[0], rb);
-    for (int k = 1; k < 4 && e == hipSuccess; ++k) e = hipMalloc((void**)&d[k], pb);
+    const size_t pb = (size_t)n * sizeof(float4);
+    dev::Temps tmp(stream);
+    float4* d[4] = {nullptr, nullptr, nullptr, nullptr};            // records (six pieces each), hits, prev_pos, prev_n
+    hipError_t e = hipSuccess;
+    for (int k = 0; k < 4 && e == hipSuccess; ++k) e = tmp.array(d[k], k == 0 ? (size_t)nt * 6 : (size_t)n) ? hipSuccess : hipErrorOutOfMemory;
     if (e == hipSuccess && nt) e = hipMemcpyAsync(d[0], records, (size_t)nt * 96, hipMemcpyHostToDevice, stream);
     if (e == hipSuccess) e = hipMemcpyAsync(d[1], hits, pb, hipMemcpyHostToDevice, stream);
     if (e == hipSuccess) e = guide_motion(stream, d[0], nt, d[1], n, d[2], d[3]);
     if (e == hipSuccess) e = hipMemcpyAsync(prev_pos, d[2], pb, hipMemcpyDeviceToHost, stream);
     if (e == hipSuccess) e = hipMemcpyAsync(prev_n, d[3], pb, hipMemcpyDeviceToHost, stream);
     const hipError_t es = hipStreamSynchronize(stream);
-    for (float4* b : d) if (b) (void)hipFree(b);
     return e == hipSuccess ? es : e;
 }
 

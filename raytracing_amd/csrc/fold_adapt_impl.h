@@ -12,7 +12,7 @@ struct OwnTree
 {
     std::vector<WideNode> wide; uint32_t entry = 0; bool ok = false; const char* name = ""; std::thread worker;
     std::vector<rt_bvh_node> bvh2; std::vector<uint32_t> roots;    // the binary tree the records fold, and the node each record tests (FoldAdapt)
-    WideNode* d_wide = nullptr;                                    // the records on the device already (RT_CTX_OPT_DEVICE_FOLD); whoever adopts them owns them
+    dev::Mem d_wide;                                               // the records on the device already (RT_CTX_OPT_DEVICE_FOLD); whoever adopts them owns them
     int device = -1;                                               // >= 0: fold on that device (a stream of the worker's own)
     bool pairs = false;                                            // RT_CTX_OPT_WIDE_LAYOUT
     bool device_builder = false;                                   // RT_CTX_OPT_TREE_BUILDER: the binary tree itself is built on the device (PLOC, ploc_kernels.h) ...
@@ -26,26 +26,27 @@ struct OwnTree
         if (device < 0 || hipSetDevice(device) != hipSuccess) { (void)hipGetLastError(); return false; }
         hipStream_t st = nullptr;
         if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) { (void)hipGetLastError(); return false; }
-        void* d_ref = nullptr;
-        rt_bvh_node* d_tree = nullptr;
+        dev::Mem d_ref, d_tree;                                    // the reference's nodes and the tree built from them: freed on the way out, the stream waited for
+        rt_bvh_node* tree = nullptr;
+        WideNode* recs = nullptr;
         uint32_t n_tree = 0, n = 0;
-        bool done = hipMalloc(&d_ref, (size_t)sd->num_nodes * sizeof(rt_bvh_node)) == hipSuccess &&
-                    hipMemcpyAsync(d_ref, sd->nodes, (size_t)sd->num_nodes * sizeof(rt_bvh_node), hipMemcpyHostToDevice, st) == hipSuccess;
+        const size_t ref_bytes = (size_t)sd->num_nodes * sizeof(rt_bvh_node);
+        bool done = d_ref.alloc(ref_bytes) && d_ref.upload(st, sd->nodes, ref_bytes);
         const auto t0 = std::chrono::steady_clock::now();
-        done = done && devfold::build_tree(st, (const rt_bvh_node*)d_ref, sd->num_nodes, sd->nodes[0], &m, &d_tree, &n_tree, &bvh2, nullptr, nullptr, &ploc_rounds);
+        done = done && devfold::build_tree(st, d_ref.get<const rt_bvh_node>(), sd->num_nodes, sd->nodes[0], &m, &tree, &n_tree, &bvh2, nullptr, nullptr, &ploc_rounds);
+        d_tree = dev::Mem(tree);
         build_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         const auto t1 = std::chrono::steady_clock::now();
-        done = done && devfold::fold(st, d_tree, n_tree, bvh2[0], &m, nullptr, &d_wide, &n, &entry, &roots, &wide) && n != 0u;
+        done = done && devfold::fold(st, tree, n_tree, bvh2[0], &m, nullptr, &recs, &n, &entry, &roots, &wide) && n != 0u;
+        d_wide = dev::Mem(recs);
         (void)hipStreamSynchronize(st);
-        if (d_ref) (void)hipFree(d_ref);
-        if (d_tree) (void)hipFree(d_tree);
         (void)hipStreamDestroy(st);
         (void)hipGetLastError();
-        if (!done) { if (d_wide) { (void)hipFree(d_wide); d_wide = nullptr; } bvh2.clear(); wide.clear(); roots.clear(); return false; }
+        if (!done) { d_wide.free(); bvh2.clear(); wide.clear(); roots.clear(); return false; }
         if (pairs)
         {
             pair_layout_by_area(wide, roots, bvh2.data(), (uint32_t)bvh2.size(), &m);
-            if (hipMemcpy(d_wide, wide.data(), wide.size() * sizeof(WideNode), hipMemcpyHostToDevice) != hipSuccess) { (void)hipGetLastError(); (void)hipFree(d_wide); d_wide = nullptr; return false; }
+            if (hipMemcpy(d_wide.get(), wide.data(), wide.size() * sizeof(WideNode), hipMemcpyHostToDevice) != hipSuccess) { (void)hipGetLastError(); d_wide.free(); return false; }
         }
         fold_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count();
         built_on_device = true;
@@ -62,27 +63,28 @@ struct OwnTree
         if (device >= 0 && hipSetDevice(device) == hipSuccess)
         {
             hipStream_t st = nullptr;
-            void* d_nodes = nullptr;
             if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) == hipSuccess)
             {
-                if (hipMalloc(&d_nodes, bvh2.size() * sizeof(rt_bvh_node)) == hipSuccess &&
-                    hipMemcpyAsync(d_nodes, bvh2.data(), bvh2.size() * sizeof(rt_bvh_node), hipMemcpyHostToDevice, st) == hipSuccess)
+                dev::Mem d_nodes;                                  // (freed at the end of this block: the stream has been waited for)
+                const size_t bytes = bvh2.size() * sizeof(rt_bvh_node);
+                if (d_nodes.alloc(bytes) && d_nodes.upload(st, bvh2.data(), bytes))
                 {
                     uint32_t n = 0;
-                    done = devfold::fold(st, (const rt_bvh_node*)d_nodes, (uint32_t)bvh2.size(), bvh2[0], &m, nullptr, &d_wide, &n, &entry, &roots, &wide) && n != 0u;
+                    WideNode* recs = nullptr;
+                    done = devfold::fold(st, d_nodes.get<const rt_bvh_node>(), (uint32_t)bvh2.size(), bvh2[0], &m, nullptr, &recs, &n, &entry, &roots, &wide) && n != 0u;
+                    d_wide = dev::Mem(recs);
                 }
                 (void)hipStreamSynchronize(st);
-                if (d_nodes) (void)hipFree(d_nodes);
                 (void)hipStreamDestroy(st);
             }
             (void)hipGetLastError();
-            if (!done && d_wide) { (void)hipFree(d_wide); d_wide = nullptr; }
+            if (!done) d_wide.free();
         }
         if (!done) done = build_wide_bvh(bvh2.data(), (uint32_t)bvh2.size(), RT_WIDE_SAH, wide, entry, &roots, &m) && !wide.empty();
         if (done && pairs)
         {
             pair_layout_by_area(wide, roots, bvh2.data(), (uint32_t)bvh2.size(), &m);
-            if (d_wide && hipMemcpy(d_wide, wide.data(), wide.size() * sizeof(WideNode), hipMemcpyHostToDevice) != hipSuccess) { (void)hipGetLastError(); (void)hipFree(d_wide); d_wide = nullptr; }
+            if (d_wide && hipMemcpy(d_wide.get(), wide.data(), wide.size() * sizeof(WideNode), hipMemcpyHostToDevice) != hipSuccess) { (void)hipGetLastError(); d_wide.free(); }
         }
         fold_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         return done;
@@ -108,7 +110,7 @@ struct OwnTree
         });
     }
     void join() { if (worker.joinable()) worker.join(); }
-    ~OwnTree() { join(); if (d_wide) (void)hipFree(d_wide); }
+    ~OwnTree() { join(); }
 };
 
 // What every candidate of one ray population is measured against and with: the proxy rays (an area-weighted pass over all triangles), the leaf of every first
@@ -241,18 +243,17 @@ bool refold_for_rays(const std::vector<rt_bvh_node>& tree, const std::vector<flo
     std::vector<uint32_t> counts;
     struct DeviceTree
     {
-        hipStream_t st = nullptr; void* nodes = nullptr;
-        ~DeviceTree() { if (st) (void)hipStreamSynchronize(st); if (nodes) (void)hipFree(nodes); if (st) (void)hipStreamDestroy(st); (void)hipGetLastError(); }
-    } dev;
+        hipStream_t st = nullptr; dev::Mem nodes;                  // (nodes is freed after this destructor has waited for the stream)
+        ~DeviceTree() { if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); } (void)hipGetLastError(); }
+    } dt;
     bool on_device = false;
-    if (fold_device >= 0 && hipSetDevice(fold_device) == hipSuccess && hipStreamCreateWithFlags(&dev.st, hipStreamNonBlocking) == hipSuccess)
+    if (fold_device >= 0 && hipSetDevice(fold_device) == hipSuccess && hipStreamCreateWithFlags(&dt.st, hipStreamNonBlocking) == hipSuccess)
     {
-        on_device = hipMalloc(&dev.nodes, (size_t)nn * sizeof(rt_bvh_node)) == hipSuccess &&
-                    hipMemcpyAsync(dev.nodes, tree.data(), (size_t)nn * sizeof(rt_bvh_node), hipMemcpyHostToDevice, dev.st) == hipSuccess;
+        on_device = dt.nodes.alloc((size_t)nn * sizeof(rt_bvh_node)) && dt.nodes.upload(dt.st, tree.data(), (size_t)nn * sizeof(rt_bvh_node));
         if (on_device)
         {
             uint64_t truncated = 0;
-            on_device = devfold::count_box_passes(dev.st, (const rt_bvh_node*)dev.nodes, nn, o.data(), d.data(), o.size(), counts, &truncated);
+            on_device = devfold::count_box_passes(dt.st, dt.nodes.get<const rt_bvh_node>(), nn, o.data(), d.data(), o.size(), counts, &truncated);
             if (truncated) truncated_walks_add(truncated);
         }
         if (!on_device) (void)hipGetLastError();
@@ -305,8 +306,8 @@ bool refold_for_rays(const std::vector<rt_bvh_node>& tree, const std::vector<flo
     {
         WideNode* d_recs = nullptr;
         uint32_t n_recs = 0;
-        folded = devfold::fold(dev.st, (const rt_bvh_node*)dev.nodes, nn, tree[0], nullptr, w.data(), &d_recs, &n_recs, &entry, &roots_new, &out, &cancel) && !out.empty();
-        if (d_recs) (void)hipFree(d_recs);                                 // (the records travel with fold_upload, with the shadow side's slot order applied)
+        folded = devfold::fold(dt.st, dt.nodes.get<const rt_bvh_node>(), nn, tree[0], nullptr, w.data(), &d_recs, &n_recs, &entry, &roots_new, &out, &cancel) && !out.empty();
+        dev::drop(d_recs);                                                 // (the records travel with fold_upload, with the shadow side's slot order applied)
         (void)hipGetLastError();
         if (cancel.load()) return false;
     }

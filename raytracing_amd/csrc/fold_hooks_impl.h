@@ -263,16 +263,15 @@ int rt_scene_import_folds(rt_ctx* ctx, const void* closest_records, uint32_t n_c
     // nothing in flight may still read the records that go: batches traced ahead are dropped, every stream drains, an adaptation of this context's own is abandoned
     if (quiesce(ctx) != RT_OK) return RT_ERROR;
     if (s.adapt) { drop_fold_adapt(s.adapt); s.adapt = nullptr; }
-    DevMem cl, sh;
-    int rc = dev_alloc_copy(ctx, &cl.p, closest_records, (size_t)n_closest * sizeof(WideNode));
-    if (rc == RT_OK && n_shadow) rc = dev_alloc_copy(ctx, &sh.p, shadow_records, (size_t)n_shadow * sizeof(WideNode));
+    dev::Mem cl, sh;
+    int rc = dev_fill(ctx, "rt_scene_import_folds", cl, closest_records, (size_t)n_closest * sizeof(WideNode));
+    if (rc == RT_OK && n_shadow) rc = dev_fill(ctx, "rt_scene_import_folds", sh, shadow_records, (size_t)n_shadow * sizeof(WideNode));
     if (rc == RT_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = fail(ctx, "rt_scene_import_folds: upload failed");
     if (rc != RT_OK) { (void)hipGetLastError(); return RT_ERROR; }
     // the tree the closest-hit rays walk (their own in the tolerance mode) and the shadow rays' own are replaced; without shadow records the shadow rays
     // walk what the closest-hit rays walk
-    DevMem old_cl, old_sh;
-    old_cl.p = s.replace_tree(s.closest, WideTree{cl.release(), n_closest, entry_closest}).recs;
-    old_sh.p = s.replace_tree(TREE_SHADOW, WideTree{sh.release(), n_shadow, entry_shadow}).recs;
+    dev::Mem old_cl(s.replace_tree(s.closest, WideTree{cl.release(), n_closest, entry_closest}).recs);
+    dev::Mem old_sh(s.replace_tree(TREE_SHADOW, WideTree{sh.release(), n_shadow, entry_shadow}).recs);
     s.walk_trees(s.closest, n_shadow ? TREE_SHADOW : s.closest);
     char line[200];
     snprintf(line, sizeof(line), "imported folds: %u closest-hit + %u shadow records taken from another context of the group; this context's own adaptation is off\n", n_closest, n_shadow);

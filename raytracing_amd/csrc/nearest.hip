@@ -20,7 +20,7 @@ bool launch(hipStream_t stream, query::Scratch& q, const DScene& sc, bool use_wi
     const rt_point* d_points, uint32_t n, rt_nearest* d_out, rt_surface* d_surfaces)
 {
     if (n == 0u) return true;
-    const uint32_t blocks = query::prepare(stream, q, &q.status, compute_units, RT_NEAREST_WAVES_PER_CU, n / 64u + (n % 64u != 0u ? 1u : 0u));
+    const uint32_t blocks = query::prepare(stream, q, &q.status, compute_units, RT_NEAREST_WAVES_PER_CU, dev::blocks_for(n, 64u));
     if (blocks == 0u) return false;
     // the records k_nearest_surface reads: the caller's, or the first 32 bytes of each surface record
     float4* found = (float4*)d_out;
@@ -30,12 +30,12 @@ bool launch(hipStream_t stream, query::Scratch& q, const DScene& sc, bool use_wi
         hipLaunchKernelGGL(k_nearest<true>, dim3(blocks), dim3(64), 0, stream, sc, (const float4*)d_points, n, found, found_stride, q.spill, q.status);
     else
         hipLaunchKernelGGL(k_nearest<false>, dim3(blocks), dim3(64), 0, stream, sc, (const float4*)d_points, n, found, found_stride, q.spill, q.status);
-    if (!query::clean()) return false;
+    if (!dev::clean()) return false;
     if (d_surfaces)
     {
-        hipLaunchKernelGGL(k_nearest_surface, dim3(n / 256u + (n % 256u != 0u ? 1u : 0u)), dim3(256), 0, stream, sc.tris_sh, n_tris, object_of_triangle,
+        hipLaunchKernelGGL(k_nearest_surface, dim3(dev::blocks_for(n, 256u)), dim3(256), 0, stream, sc.tris_sh, n_tris, object_of_triangle,
             (const float4*)d_points, (const float4*)found, found_stride, n, (float4*)d_surfaces);
-        if (!query::clean()) return false;
+        if (!dev::clean()) return false;
     }
     return true;
 }
@@ -75,15 +75,15 @@ void brute_host(const rt_triangle* tris, uint32_t n_tris, const rt_point* points
 
 bool brute_device(hipStream_t stream, const rt_triangle* tris, uint32_t n_tris, const rt_point* points, uint32_t n, rt_nearest* out)
 {
-    query::DeviceTemps tmp(stream);
+    dev::Temps tmp(stream);
     void* const d_tris = tmp.get(tris, (size_t)n_tris * sizeof(rt_triangle));
     void* const d_points = tmp.get(points, (size_t)n * sizeof(rt_point));
     void* const d_out = tmp.get(nullptr, (size_t)n * sizeof(rt_nearest));
     const bool ok = d_tris && d_points && d_out;
     if (ok)
-        hipLaunchKernelGGL(k_nearest_brute, dim3(n / 256u + (n % 256u != 0u ? 1u : 0u)), dim3(256), 0, stream, (const rt_triangle*)d_tris, n_tris, (const float4*)d_points, n,
+        hipLaunchKernelGGL(k_nearest_brute, dim3(dev::blocks_for(n, 256u)), dim3(256), 0, stream, (const rt_triangle*)d_tris, n_tris, (const float4*)d_points, n,
             (float4*)d_out);
-    return tmp.finish(ok && query::clean(), out, d_out, (size_t)n * sizeof(rt_nearest));
+    return tmp.finish(ok && dev::clean(), out, d_out, (size_t)n * sizeof(rt_nearest));
 }
 
 const char* walk_host(const rt_bvh_node* nodes, uint32_t nn, const rt_triangle* tris, uint32_t n_tris, bool wide, const rt_point* points, uint32_t n,

@@ -14,6 +14,7 @@
 #include <vector>
 #include "pose.h"
 #include "pose_host.h"
+#include "device_memory.h"
 
 namespace pose
 {
@@ -53,18 +54,6 @@ __global__ __launch_bounds__(256) void k_pose_triangles(const float4* __restrict
 }
 
 // ---- the host side ---------------------------------------------------------------------------------------------------------------------------------
-static inline dim3 grid_of(uint32_t n) { return dim3((n + 255u) / 256u); }
-static bool clean() { return hipGetLastError() == hipSuccess; }
-template <class T> static bool get(T*& p, size_t bytes, size_t& total)
-{
-    void* q = nullptr;
-    if (hipMalloc(&q, bytes ? bytes : 16) != hipSuccess) { (void)hipGetLastError(); p = nullptr; return false; }
-    p = (T*)q;
-    total += bytes;
-    return true;
-}
-template <class T> static void drop(T*& p) { if (p) (void)hipFree(p); p = nullptr; }
-
 bool ids_in_range(const uint32_t* ids, uint32_t nt, uint32_t n_objects)
 {
     for (uint32_t i = 0; i < nt; ++i) if (ids[i] >= n_objects) return false;
@@ -84,7 +73,7 @@ static void make_objects(const float* m, uint32_t n_objects, Object* out)
 
 void release(State& st)
 {
-    drop(st.rest); drop(st.ids); drop(st.staged); drop(st.objects);
+    dev::drop(st.rest); dev::drop(st.ids); dev::drop(st.staged); dev::drop(st.objects);
     if (st.host_objects) (void)hipHostFree(st.host_objects);
     st = State();
 }
@@ -93,13 +82,14 @@ bool arm(hipStream_t stream, State& st, const float4* tris_sh, const uint32_t* i
 {
     release(st);
     st.n_tris = nt; st.n_objects = n_objects;
-    bool ok = get(st.rest, (size_t)nt * REST_BYTES, st.bytes) && get(st.ids, (size_t)nt * ID_BYTES, st.bytes) && get(st.staged, (size_t)nt * STAGED_BYTES, st.bytes) &&
-              get(st.objects, (size_t)n_objects * sizeof(Object), st.bytes) && hipHostMalloc(&st.host_objects, (size_t)n_objects * sizeof(Object)) == hipSuccess &&
+    st.bytes = (size_t)nt * BYTES_PER_TRIANGLE + (size_t)n_objects * sizeof(Object);
+    bool ok = dev::get(st.rest, (size_t)nt * REST_BYTES) && dev::get(st.ids, (size_t)nt * ID_BYTES) && dev::get(st.staged, (size_t)nt * STAGED_BYTES) &&
+              dev::get(st.objects, (size_t)n_objects * sizeof(Object)) && hipHostMalloc(&st.host_objects, (size_t)n_objects * sizeof(Object)) == hipSuccess &&
               hipMemcpyAsync(st.ids, ids, (size_t)nt * ID_BYTES, hipMemcpyHostToDevice, stream) == hipSuccess;
     if (ok)
     {
-        hipLaunchKernelGGL(k_pose_rest, grid_of(nt), dim3(256), 0, stream, tris_sh, nt, (float4*)st.rest);
-        ok = clean();
+        hipLaunchKernelGGL(k_pose_rest, dim3(dev::blocks_for(nt, 256u)), dim3(256), 0, stream, tris_sh, nt, (float4*)st.rest);
+        ok = dev::clean();
     }
     ok = hipStreamSynchronize(stream) == hipSuccess && ok;
     if (!ok) { (void)hipGetLastError(); release(st); }
@@ -110,9 +100,9 @@ bool run(hipStream_t stream, State& st, const float* matrices3x4)
 {
     make_objects(matrices3x4, st.n_objects, (Object*)st.host_objects);
     if (hipMemcpyAsync(st.objects, st.host_objects, (size_t)st.n_objects * sizeof(Object), hipMemcpyHostToDevice, stream) != hipSuccess) return false;
-    hipLaunchKernelGGL(k_pose_triangles, grid_of(st.n_tris), dim3(256), 0, stream, (const float4*)st.rest, (const uint32_t*)st.ids, (const Object*)st.objects,
+    hipLaunchKernelGGL(k_pose_triangles, dim3(dev::blocks_for(st.n_tris, 256u)), dim3(256), 0, stream, (const float4*)st.rest, (const uint32_t*)st.ids, (const Object*)st.objects,
         st.n_tris, st.n_objects, (float4*)st.staged);
-    return clean();
+    return dev::clean();
 }
 
 void debug_host(const rt_triangle* rest, const uint32_t* ids, uint32_t nt, const float* matrices3x4, uint32_t n_objects, rt_triangle* out)
@@ -131,23 +121,14 @@ bool debug_device(hipStream_t stream, const rt_triangle* rest, const uint32_t* i
 {
     std::vector<Object> objects(n_objects);
     make_objects(matrices3x4, n_objects, objects.data());
-    rt_triangle *d_rest = nullptr, *d_out = nullptr;
-    uint32_t* d_ids = nullptr;
-    Object* d_objects = nullptr;
-    size_t bytes = 0;
-    bool ok = get(d_rest, (size_t)nt * sizeof(rt_triangle), bytes) && get(d_out, (size_t)nt * sizeof(rt_triangle), bytes) && get(d_ids, (size_t)nt * 4, bytes) &&
-              get(d_objects, (size_t)n_objects * sizeof(Object), bytes) &&
-              hipMemcpyAsync(d_rest, rest, (size_t)nt * sizeof(rt_triangle), hipMemcpyHostToDevice, stream) == hipSuccess &&
-              hipMemcpyAsync(d_ids, ids, (size_t)nt * 4, hipMemcpyHostToDevice, stream) == hipSuccess &&
-              hipMemcpyAsync(d_objects, objects.data(), (size_t)n_objects * sizeof(Object), hipMemcpyHostToDevice, stream) == hipSuccess;
+    dev::Temps tmp(stream);
+    void* const d_rest = tmp.get(rest, (size_t)nt * sizeof(rt_triangle));
+    void* const d_ids = tmp.get(ids, (size_t)nt * 4);
+    void* const d_objects = tmp.get(objects.data(), (size_t)n_objects * sizeof(Object));
+    void* const d_out = tmp.get(nullptr, (size_t)nt * sizeof(rt_triangle));
+    const bool ok = d_rest && d_ids && d_objects && d_out;
     if (ok)
-    {
-        hipLaunchKernelGGL(k_pose_triangles, grid_of(nt), dim3(256), 0, stream, (const float4*)d_rest, (const uint32_t*)d_ids, (const Object*)d_objects, nt, n_objects, (float4*)d_out);
-        ok = clean() && hipMemcpyAsync(out, d_out, (size_t)nt * sizeof(rt_triangle), hipMemcpyDeviceToHost, stream) == hipSuccess;
-    }
-    ok = hipStreamSynchronize(stream) == hipSuccess && ok;
-    (void)hipGetLastError();
-    drop(d_rest); drop(d_out); drop(d_ids); drop(d_objects);
-    return ok;
+        hipLaunchKernelGGL(k_pose_triangles, dim3(dev::blocks_for(nt, 256u)), dim3(256), 0, stream, (const float4*)d_rest, (const uint32_t*)d_ids, (const Object*)d_objects, nt, n_objects, (float4*)d_out);
+    return tmp.finish(ok && dev::clean(), out, d_out, (size_t)nt * sizeof(rt_triangle));
 }
 } // namespace pose

@@ -13,8 +13,6 @@ namespace query
 static_assert(sizeof(rt_ray) == 2 * sizeof(float4) && sizeof(rt_hit) == sizeof(float4) && sizeof(rt_surface) == 4 * sizeof(float4), "records as 16-byte pieces");
 #define RT_QUERY_WAVES_PER_CU 24u       // 6 KiB of LDS per block: 26 fit a CU's 160 KiB; the registers allow 24
 
-bool clean() { return hipGetLastError() == hipSuccess; }
-
 size_t Scratch::spill_bytes() const { return (size_t)spill_blocks * 64u * RT_QUERY_SPILL_PER_LANE * sizeof(uint2); }
 size_t Scratch::bytes() const
 {
@@ -63,32 +61,11 @@ uint32_t prepare(hipStream_t stream, Scratch& s, uint32_t** status, int compute_
     return blocks;
 }
 
-DeviceTemps::~DeviceTemps()
-{
-    for (int k = 0; k < count; ++k) (void)hipFree(held[k]);
-}
-
-void* DeviceTemps::get(const void* src, size_t bytes)
-{
-    void* p = nullptr;
-    if (count == 8 || hipMalloc(&p, bytes ? bytes : 16) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-    held[count++] = p;
-    return !src || bytes == 0 || hipMemcpyAsync(p, src, bytes, hipMemcpyHostToDevice, stream) == hipSuccess ? p : nullptr;
-}
-
-bool DeviceTemps::finish(bool launched, void* out, const void* d_out, size_t bytes)
-{
-    bool ok = launched && hipMemcpyAsync(out, d_out, bytes, hipMemcpyDeviceToHost, stream) == hipSuccess;
-    ok = hipStreamSynchronize(stream) == hipSuccess && ok;
-    (void)hipGetLastError();
-    return ok;
-}
-
 bool launch(hipStream_t stream, Scratch& s, const DScene& sc, bool use_wide, uint32_t n_tris, const uint32_t* object_of_triangle, int compute_units,
     const rt_ray* d_rays, uint32_t n, uint32_t mode, rt_hit* d_hits, uint32_t* d_occluded, rt_surface* d_surfaces)
 {
     if (n == 0u) return true;
-    const uint32_t blocks = prepare(stream, s, &s.status, compute_units, RT_QUERY_WAVES_PER_CU, n / 64u + (n % 64u != 0u ? 1u : 0u));
+    const uint32_t blocks = prepare(stream, s, &s.status, compute_units, RT_QUERY_WAVES_PER_CU, dev::blocks_for(n, 64u));
     if (blocks == 0u) return false;
     // the hits k_query_surface reads: the caller's, or the first 16 bytes of each surface record
     float4* hits = (float4*)d_hits;
@@ -100,12 +77,12 @@ bool launch(hipStream_t stream, Scratch& s, const DScene& sc, bool use_wide, uin
     else
         hipLaunchKernelGGL(k_query_trace<false>, dim3(blocks), dim3(64), 0, stream, sc, (const float4*)d_rays, n, hits, hit_stride, d_occluded, s.spill,
             use_wide ? 1u : 0u, s.status);
-    if (!clean()) return false;
+    if (!dev::clean()) return false;
     if (d_surfaces)
     {
-        hipLaunchKernelGGL(k_query_surface<true>, dim3(n / 256u + (n % 256u != 0u ? 1u : 0u)), dim3(256), 0, stream, sc.tris_sh, n_tris, object_of_triangle, (const float4*)d_rays,
+        hipLaunchKernelGGL(k_query_surface<true>, dim3(dev::blocks_for(n, 256u)), dim3(256), 0, stream, sc.tris_sh, n_tris, object_of_triangle, (const float4*)d_rays,
             (const float4*)hits, hit_stride, n, (float4*)d_surfaces);
-        if (!clean()) return false;
+        if (!dev::clean()) return false;
     }
     return true;
 }
@@ -134,7 +111,7 @@ void debug_surface_host(const rt_triangle* tris, uint32_t n_tris, const uint32_t
 bool debug_surface_device(hipStream_t stream, const rt_triangle* tris, uint32_t n_tris, const uint32_t* object_of_triangle, const rt_ray* rays, const rt_hit* hits,
     uint32_t n, rt_surface* out)
 {
-    DeviceTemps tmp(stream);
+    dev::Temps tmp(stream);
     void* const d_tris = tmp.get(tris, (size_t)n_tris * sizeof(rt_triangle));
     void* const d_ids = object_of_triangle ? tmp.get(object_of_triangle, (size_t)n_tris * 4) : nullptr;
     void* const d_rays = tmp.get(rays, (size_t)n * sizeof(rt_ray));
@@ -142,8 +119,8 @@ bool debug_surface_device(hipStream_t stream, const rt_triangle* tris, uint32_t 
     void* const d_out = tmp.get(nullptr, (size_t)n * sizeof(rt_surface));
     const bool ok = d_tris && (d_ids || !object_of_triangle) && d_rays && d_hits && d_out;
     if (ok)
-        hipLaunchKernelGGL(k_query_surface<false>, dim3(n / 256u + (n % 256u != 0u ? 1u : 0u)), dim3(256), 0, stream, (const float4*)d_tris, n_tris, (const uint32_t*)d_ids,
+        hipLaunchKernelGGL(k_query_surface<false>, dim3(dev::blocks_for(n, 256u)), dim3(256), 0, stream, (const float4*)d_tris, n_tris, (const uint32_t*)d_ids,
             (const float4*)d_rays, (const float4*)d_hits, 1u, n, (float4*)d_out);
-    return tmp.finish(ok && clean(), out, d_out, (size_t)n * sizeof(rt_surface));
+    return tmp.finish(ok && dev::clean(), out, d_out, (size_t)n * sizeof(rt_surface));
 }
 } // namespace query

@@ -7,6 +7,7 @@
 #include <stdint.h>
 #include <stddef.h>
 #include "rt_hip.h"
+#include "device_memory.h"
 
 struct DScene;
 
@@ -32,22 +33,6 @@ bool reserve(hipStream_t stream, Scratch& s, int k, size_t bytes);
 // Before a walk's launch: *status is allocated if it is not yet, s's spill area is grown to the grid (the stream is waited for before a smaller one is freed).
 // The grid: n_groups blocks of one wave, at most what waves_per_cu keeps resident (rounded up to 8).  0: out of memory.
 uint32_t prepare(hipStream_t stream, Scratch& s, uint32_t** status, int compute_units, uint32_t waves_per_cu, uint32_t n_groups);
-// no launch or runtime error is pending (and none is left pending)
-bool clean();
-
-// The debug paths' temporary device copies: get() allocates one and uploads `src` into it when there is one; all are freed when the holder goes.
-struct DeviceTemps
-{
-    hipStream_t stream;
-    void* held[8];
-    int count = 0;
-    explicit DeviceTemps(hipStream_t s) : stream(s) {}
-    DeviceTemps(const DeviceTemps&) = delete; DeviceTemps& operator=(const DeviceTemps&) = delete;
-    ~DeviceTemps();
-    void* get(const void* src, size_t bytes);       // nullptr: the allocation or the upload failed
-    // after the launch: d_out's `bytes` to `out`, the stream waited for.  launched: what clean() said after the launch
-    bool finish(bool launched, void* out, const void* d_out, size_t bytes);
-};
 
 // The query's launches on `stream`, nothing waited for: k_query_trace over d_rays[n], then k_query_surface when d_surfaces is given.  mode: RT_QUERY_*; use_wide:
 // the scene's 4-wide trees are usable; object_of_triangle: the device table of rt_scene_set_objects or nullptr.  In closest mode d_hits may be nullptr when

@@ -22,6 +22,7 @@
 #include <vector>
 #include "refit.h"
 #include "wide_quant.h"
+#include "device_memory.h"
 
 #ifndef RT_LEAF_BIT
 #define RT_LEAF_BIT 0x80000000u
@@ -302,27 +303,18 @@ __global__ __launch_bounds__(256) void k_refit_debug_nodes(const rt_bvh_node* __
 }
 
 // ---- the host side ---------------------------------------------------------------------------------------------------------------------------------
-static inline dim3 grid_of(uint32_t n) { return dim3((n + 255u) / 256u); }
-static bool clean() { return hipGetLastError() == hipSuccess; }
-
-template <class T> static bool get(T*& p, size_t count, size_t& bytes)
-{
-    void* q = nullptr;
-    if (hipMalloc(&q, count * sizeof(T) + 16) != hipSuccess) { (void)hipGetLastError(); p = nullptr; return false; }
-    p = (T*)q;
-    bytes += count * sizeof(T);
-    return true;
-}
-template <class T> static void drop(T*& p) { if (p) (void)hipFree(p); p = nullptr; }
+// every array here gets 16 bytes of tail beyond its elements (dev::alloc); the bookkeeping for the tree report counts the elements only
+enum { TAIL = 16 };
 
 bool prepare(hipStream_t stream, State& st, const float4* pairs, uint32_t n_pairs)
 {
     release(st);
     st.n_pairs = n_pairs;
-    if (!get(st.d_status, 4, st.bytes) || !get(st.pair_parent, n_pairs, st.bytes) || !get(st.pair_arrived, n_pairs, st.bytes)) { release(st); return false; }
+    if (!dev::get(st.d_status, 4 * 4 + TAIL) || !dev::get(st.pair_parent, (size_t)n_pairs * 4 + TAIL) || !dev::get(st.pair_arrived, (size_t)n_pairs * 4 + TAIL)) { release(st); return false; }
+    st.bytes = 4 * 4 + (size_t)n_pairs * 8;
     if (hipMemsetAsync(st.pair_parent, 0xFF, (size_t)n_pairs * 4, stream) != hipSuccess) { release(st); return false; }
-    hipLaunchKernelGGL(k_refit_pair_links, grid_of(n_pairs), dim3(256), 0, stream, pairs, n_pairs, st.pair_parent);
-    if (!clean()) { release(st); return false; }
+    hipLaunchKernelGGL(k_refit_pair_links, dim3(dev::blocks_for(n_pairs, 256u)), dim3(256), 0, stream, pairs, n_pairs, st.pair_parent);
+    if (!dev::clean()) { release(st); return false; }
     return true;
 }
 
@@ -330,28 +322,27 @@ bool link_tree(hipStream_t stream, State& st, int which, WideNode* records, uint
 {
     Tree& t = st.trees[which];
     if (records && n != 0u && t.linked_for == records && t.linked_n == n) { t.entry = entry; return true; }
-    for (void* p : {(void*)t.parent, (void*)t.boxes, (void*)t.arrived}) if (p) (void)hipFree(p);
+    dev::drop(t.parent); dev::drop(t.boxes); dev::drop(t.arrived);
     if (t.linked_n) st.bytes -= (size_t)t.linked_n * 40;
     t = Tree();
     if (!records || n == 0u) return true;
-    size_t bytes = 0;
-    if (!get(t.parent, n, bytes) || !get(t.arrived, n, bytes) || !get(t.boxes, (size_t)n * 8, bytes) ||
-        hipMemsetAsync(t.parent, 0xFF, (size_t)n * 4, stream) != hipSuccess)
+    bool ok = dev::get(t.parent, (size_t)n * 4 + TAIL) && dev::get(t.arrived, (size_t)n * 4 + TAIL) && dev::get(t.boxes, (size_t)n * 32 + TAIL) &&
+              hipMemsetAsync(t.parent, 0xFF, (size_t)n * 4, stream) == hipSuccess;
+    if (ok)
     {
-        drop(t.parent); drop(t.arrived); drop(t.boxes);
-        return false;
+        hipLaunchKernelGGL(k_refit_wide_links, dim3(dev::blocks_for(n, 256u)), dim3(256), 0, stream, (const WideNode*)records, n, t.parent);
+        ok = dev::clean();
     }
-    hipLaunchKernelGGL(k_refit_wide_links, grid_of(n), dim3(256), 0, stream, (const WideNode*)records, n, t.parent);
-    if (!clean()) { drop(t.parent); drop(t.arrived); drop(t.boxes); return false; }
+    if (!ok) { dev::drop(t.parent); dev::drop(t.arrived); dev::drop(t.boxes); return false; }
     t.records = records; t.n = n; t.entry = entry; t.linked_for = records; t.linked_n = n;
-    st.bytes += bytes;
+    st.bytes += (size_t)n * 40;
     return true;
 }
 
 void release(State& st)
 {
-    for (Tree& t : st.trees) { drop(t.parent); drop(t.boxes); drop(t.arrived); t = Tree(); }
-    drop(st.pair_parent); drop(st.pair_arrived); drop(st.d_status);
+    for (Tree& t : st.trees) { dev::drop(t.parent); dev::drop(t.boxes); dev::drop(t.arrived); t = Tree(); }
+    dev::drop(st.pair_parent); dev::drop(st.pair_arrived); dev::drop(st.d_status);
     st.n_pairs = 0; st.bytes = 0;
 }
 
@@ -359,8 +350,8 @@ int validate(hipStream_t stream, State& st, const rt_triangle* d_tris, uint32_t 
 {
     int status = -1;
     if (hipMemsetAsync(st.d_status, 0, 4 * sizeof(int), stream) != hipSuccess) return -1;
-    hipLaunchKernelGGL(k_refit_validate, grid_of(nt), dim3(256), 0, stream, d_tris, nt, num_materials, st.d_status);
-    if (!clean() || hipMemcpyAsync(&status, st.d_status, sizeof(int), hipMemcpyDeviceToHost, stream) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess) return -1;
+    hipLaunchKernelGGL(k_refit_validate, dim3(dev::blocks_for(nt, 256u)), dim3(256), 0, stream, d_tris, nt, num_materials, st.d_status);
+    if (!dev::clean() || hipMemcpyAsync(&status, st.d_status, sizeof(int), hipMemcpyDeviceToHost, stream) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess) return -1;
     return status;
 }
 
@@ -369,17 +360,17 @@ bool run(hipStream_t stream, State& st, const rt_triangle* d_tris, uint32_t nt, 
     if (hipMemsetAsync(st.d_status, 0, 4 * sizeof(int), stream) != hipSuccess || hipMemsetAsync(st.pair_arrived, 0, (size_t)st.n_pairs * 4, stream) != hipSuccess) return false;
     for (Tree& t : st.trees)
         if (t.n && hipMemsetAsync(t.arrived, 0, (size_t)t.n * 4, stream) != hipSuccess) return false;
-    hipLaunchKernelGGL(k_refit_triangles, grid_of(nt), dim3(256), 0, stream, d_tris, nt, tris_rt, tris_sh);
-    hipLaunchKernelGGL(k_refit_pairs, grid_of(st.n_pairs), dim3(256), 0, stream, pairs, st.n_pairs, (const uint32_t*)st.pair_parent, st.pair_arrived, (const float4*)tris_rt, nt, st.d_status);
+    hipLaunchKernelGGL(k_refit_triangles, dim3(dev::blocks_for(nt, 256u)), dim3(256), 0, stream, d_tris, nt, tris_rt, tris_sh);
+    hipLaunchKernelGGL(k_refit_pairs, dim3(dev::blocks_for(st.n_pairs, 256u)), dim3(256), 0, stream, pairs, st.n_pairs, (const uint32_t*)st.pair_parent, st.pair_arrived, (const float4*)tris_rt, nt, st.d_status);
     for (int w = 0; w < 2; ++w)
     {
         Tree& t = st.trees[w];
         if (t.n == 0u) continue;
-        hipLaunchKernelGGL(k_refit_wide, grid_of(t.n), dim3(256), 0, stream, t.records, t.n, t.entry, (const uint32_t*)t.parent, t.arrived, t.boxes, (const float4*)tris_rt, nt, st.d_status, 2 + w);
+        hipLaunchKernelGGL(k_refit_wide, dim3(dev::blocks_for(t.n, 256u)), dim3(256), 0, stream, t.records, t.n, t.entry, (const uint32_t*)t.parent, t.arrived, t.boxes, (const float4*)tris_rt, nt, st.d_status, 2 + w);
     }
     int status[4] = {0, 0, 0, 0};
     float root[12];
-    if (!clean() || hipMemcpyAsync(status, st.d_status, sizeof(status), hipMemcpyDeviceToHost, stream) != hipSuccess ||
+    if (!dev::clean() || hipMemcpyAsync(status, st.d_status, sizeof(status), hipMemcpyDeviceToHost, stream) != hipSuccess ||
         hipMemcpyAsync(root, pairs + (size_t)super_root * 4, sizeof(root), hipMemcpyDeviceToHost, stream) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess) return false;
     out.error = status[1];
     out.wide_bad[0] = status[2] != 0; out.wide_bad[1] = status[3] != 0;
@@ -523,35 +514,31 @@ bool debug_device(hipStream_t stream, const rt_bvh_node* nodes, uint32_t nn, con
     std::vector<uint32_t> order;
     if (!check_input(nodes, nn, tris, nt, records, n_records, entry, order, error)) return false;
     State st;
-    rt_bvh_node *d_nodes = nullptr, *d_out = nullptr;
-    rt_triangle* d_tris = nullptr;
-    float4 *trt = nullptr, *pairs = nullptr;
-    WideNode* d_recs = nullptr;
-    size_t bytes = 0;
+    dev::Temps tmp(stream, TAIL);
     const uint32_t n_pairs = nn + 1u;                               // record i = node i (leaves: stand-ins nobody refers to), record nn = the super-root
-    bool ok = get(d_nodes, nn, bytes) && get(d_out, nn, bytes) && get(d_tris, nt, bytes) && get(trt, (size_t)nt * 4, bytes) && get(pairs, (size_t)n_pairs * 4, bytes) &&
-              (n_records == 0u || get(d_recs, n_records, bytes));
-    ok = ok && hipMemcpyAsync(d_nodes, nodes, (size_t)nn * sizeof(rt_bvh_node), hipMemcpyHostToDevice, stream) == hipSuccess &&
-         hipMemcpyAsync(d_tris, tris, (size_t)nt * sizeof(rt_triangle), hipMemcpyHostToDevice, stream) == hipSuccess &&
-         (n_records == 0u || hipMemcpyAsync(d_recs, records, (size_t)n_records * sizeof(WideNode), hipMemcpyHostToDevice, stream) == hipSuccess) &&
-         hipMemsetAsync(trt, 0, (size_t)nt * 64, stream) == hipSuccess && hipMemsetAsync(pairs, 0xFF, (size_t)n_pairs * 64, stream) == hipSuccess;
+    rt_bvh_node* const d_nodes = (rt_bvh_node*)tmp.get(nodes, (size_t)nn * sizeof(rt_bvh_node));
+    rt_triangle* const d_tris = (rt_triangle*)tmp.get(tris, (size_t)nt * sizeof(rt_triangle));
+    WideNode* const d_recs = n_records ? (WideNode*)tmp.get(records, (size_t)n_records * sizeof(WideNode)) : nullptr;
+    rt_bvh_node* d_out = nullptr;
+    float4 *trt = nullptr, *pairs = nullptr;
+    bool ok = d_nodes && d_tris && (d_recs || n_records == 0u) && tmp.array(d_out, nn) && tmp.array(trt, (size_t)nt * 4) && tmp.array(pairs, (size_t)n_pairs * 4) &&
+              hipMemsetAsync(trt, 0, (size_t)nt * 64, stream) == hipSuccess && hipMemsetAsync(pairs, 0xFF, (size_t)n_pairs * 64, stream) == hipSuccess;
     Result res;
     if (ok)
     {
-        hipLaunchKernelGGL(k_refit_debug_records, grid_of(nn), dim3(256), 0, stream, (const rt_bvh_node*)d_nodes, nn, trt, pairs);
-        ok = clean() && prepare(stream, st, pairs, n_pairs) && link_tree(stream, st, 0, d_recs, n_records, entry) &&
+        hipLaunchKernelGGL(k_refit_debug_records, dim3(dev::blocks_for(nn, 256u)), dim3(256), 0, stream, (const rt_bvh_node*)d_nodes, nn, trt, pairs);
+        ok = dev::clean() && prepare(stream, st, pairs, n_pairs) && link_tree(stream, st, 0, d_recs, n_records, entry) &&
              run(stream, st, d_tris, nt, trt, nullptr, pairs, nn, res);
     }
     if (ok)
     {
-        hipLaunchKernelGGL(k_refit_debug_nodes, grid_of(nn), dim3(256), 0, stream, (const rt_bvh_node*)d_nodes, nn, (const float4*)trt, (const float4*)pairs, d_out);
-        ok = clean() && (!out_nodes || hipMemcpyAsync(out_nodes, d_out, (size_t)nn * sizeof(rt_bvh_node), hipMemcpyDeviceToHost, stream) == hipSuccess) &&
+        hipLaunchKernelGGL(k_refit_debug_nodes, dim3(dev::blocks_for(nn, 256u)), dim3(256), 0, stream, (const rt_bvh_node*)d_nodes, nn, (const float4*)trt, (const float4*)pairs, d_out);
+        ok = dev::clean() && (!out_nodes || hipMemcpyAsync(out_nodes, d_out, (size_t)nn * sizeof(rt_bvh_node), hipMemcpyDeviceToHost, stream) == hipSuccess) &&
              (!out_records || n_records == 0u || hipMemcpyAsync(out_records, d_recs, (size_t)n_records * sizeof(WideNode), hipMemcpyDeviceToHost, stream) == hipSuccess);
     }
     ok = hipStreamSynchronize(stream) == hipSuccess && ok;
     (void)hipGetLastError();
     release(st);
-    drop(d_nodes); drop(d_out); drop(d_tris); drop(trt); drop(pairs); drop(d_recs);
     if (!ok) { error = "the device path failed (allocation, copy or launch)"; return false; }
     if (res.error != OK) { error = "the kernels met a reference outside the arrays"; return false; }
     if (wide_bad) *wide_bad = res.wide_bad[0];

@@ -122,9 +122,9 @@ int rt_scene_refit(rt_ctx* ctx, const rt_triangle* triangles, uint32_t num_trian
     if (!ctx || !triangles) return fail(ctx, "rt_scene_refit: NULL argument");
     if (refit_refused(ctx, "rt_scene_refit", num_triangles, false) != RT_OK) return RT_ERROR;
     (void)hipSetDevice(ctx->device);
-    DevMem d_tris;
-    if (dev_alloc_copy(ctx, &d_tris.p, triangles, (size_t)num_triangles * sizeof(rt_triangle)) != RT_OK) return RT_ERROR;
-    const int rc = refit_device(ctx, (const rt_triangle*)d_tris.p, "rt_scene_refit");
+    dev::Mem d_tris;
+    if (dev_fill(ctx, "rt_scene_refit", d_tris, triangles, (size_t)num_triangles * sizeof(rt_triangle)) != RT_OK) return RT_ERROR;
+    const int rc = refit_device(ctx, d_tris.get<const rt_triangle>(), "rt_scene_refit");
     (void)hipStreamSynchronize(ctx->stream);
     return rc;
 }

@@ -32,6 +32,7 @@
 #include "bake_host.h"       // ambient occlusion and bent normals at caller-supplied points (bake.hip)
 #include "nearest_host.h"    // the nearest surface point to caller-supplied points (nearest.hip)
 #include "all_hits_host.h"   // every surface a caller-supplied ray crosses (all_hits.hip)
+#include "device_memory.h"   // who owns a device allocation: dev::Mem, dev::Temps
 using namespace rtw;
 
 namespace
@@ -457,12 +458,21 @@ int fail(rt_ctx* ctx, const std::string& msg)
             return fail(ctx, std::string(#expr) + ": " + hipGetErrorString(e_));                  \
     } while (0)
 
-int dev_alloc_copy(rt_ctx* ctx, void** out, const void* src, size_t bytes)
+// m = `bytes` of device memory with src's bytes on their way into it on ctx's stream (no src: nothing is copied); a failure is `who`'s error
+int dev_fill(rt_ctx* ctx, const char* who, dev::Mem& m, const void* src, size_t bytes)
 {
-    *out = nullptr;
-    size_t alloc = bytes ? bytes : 16;
-    HIPCHK(ctx, hipMalloc(out, alloc));
-    if (bytes && src) HIPCHK(ctx, hipMemcpyAsync(*out, src, bytes, hipMemcpyHostToDevice, ctx->stream));
+    if (!m.alloc(bytes)) return fail(ctx, std::string(who) + ": out of device memory");
+    if (!m.upload(ctx->stream, src, bytes)) return fail(ctx, std::string(who) + ": " + hipGetErrorString(hipGetLastError()));
+    return RT_OK;
+}
+
+// the same for a raw field of the Scene (free_scene's to free): it is set only when the allocation and the copy both worked
+int scene_array(rt_ctx* ctx, void** field, const void* src, size_t bytes)
+{
+    dev::Mem m;
+    *field = nullptr;
+    if (dev_fill(ctx, "rt_scene_upload", m, src, bytes) != RT_OK) return RT_ERROR;
+    *field = m.release();
     return RT_OK;
 }
 
@@ -475,16 +485,6 @@ int query_check_status(rt_ctx* ctx, const char* who)
     *st = 0u;
     return fail(ctx, std::string(who) + ": a ray query's traversal stack ran over its bound (a tree deeper than the walk's stack): that query's results are not valid");
 }
-
-// A device allocation with an owner (move-only in spirit: never copied): freed when the holder goes, unless release() has handed it on.
-struct DevMem
-{
-    void* p = nullptr;
-    DevMem() = default;
-    DevMem(const DevMem&) = delete; DevMem& operator=(const DevMem&) = delete;
-    ~DevMem() { if (p) (void)hipFree(p); }
-    void* release() { void* q = p; p = nullptr; return q; }
-};
 
 void free_scene(Scene& s)
 {
@@ -887,40 +887,41 @@ struct Upload
     // just read (device_fold.h), on the same stream, before that array is freed with the stage's other temporaries.
     int relayout_on_device()
     {
-        DevMem raw_tris, raw_nodes, d_index, d_last, d_err;
-        rc |= dev_alloc_copy(ctx, &raw_tris.p, sd->triangles, (size_t)nt * sizeof(rt_triangle));
-        rc |= dev_alloc_copy(ctx, &raw_nodes.p, sd->nodes, (size_t)nn * sizeof(rt_bvh_node));
-        rc |= dev_alloc_copy(ctx, &d_index.p, interior_index.data(), (size_t)nn * sizeof(uint32_t));
-        rc |= dev_alloc_copy(ctx, &d_last.p, nullptr, (size_t)nt);
-        rc |= dev_alloc_copy(ctx, &d_err.p, nullptr, sizeof(int));
-        rc |= dev_alloc_copy(ctx, &s.nodes, nullptr, (size_t)(n_interior + 1) * 64);   // + the super-root record
-        rc |= dev_alloc_copy(ctx, &s.tris_rt, nullptr, (size_t)nt * 64);
-        rc |= dev_alloc_copy(ctx, &s.tris_sh, nullptr, (size_t)nt * 128);
+        static const char* who = "rt_scene_upload";
+        dev::Mem raw_tris, raw_nodes, d_index, d_last, d_err;
+        rc |= dev_fill(ctx, who, raw_tris, sd->triangles, (size_t)nt * sizeof(rt_triangle));
+        rc |= dev_fill(ctx, who, raw_nodes, sd->nodes, (size_t)nn * sizeof(rt_bvh_node));
+        rc |= dev_fill(ctx, who, d_index, interior_index.data(), (size_t)nn * sizeof(uint32_t));
+        rc |= dev_fill(ctx, who, d_last, nullptr, (size_t)nt);
+        rc |= dev_fill(ctx, who, d_err, nullptr, sizeof(int));
+        rc |= scene_array(ctx, &s.nodes, nullptr, (size_t)(n_interior + 1) * 64);   // + the super-root record
+        rc |= scene_array(ctx, &s.tris_rt, nullptr, (size_t)nt * 64);
+        rc |= scene_array(ctx, &s.tris_sh, nullptr, (size_t)nt * 128);
         if (rc != RT_OK) return RT_ERROR;
         int relayout_err = RL_OK;
-        bool ok = hipMemsetAsync(d_last.p, 0, (size_t)nt, ctx->stream) == hipSuccess &&
-                  hipMemsetAsync(d_err.p, 0, sizeof(int), ctx->stream) == hipSuccess;
+        bool ok = hipMemsetAsync(d_last.get(), 0, (size_t)nt, ctx->stream) == hipSuccess &&
+                  hipMemsetAsync(d_err.get(), 0, sizeof(int), ctx->stream) == hipSuccess;
         if (ok)
         {
             hipLaunchKernelGGL(k_relayout_mark_leaves, dim3((nn + 255u) / 256u), dim3(256), 0, ctx->stream,
-                (const rt_bvh_node*)raw_nodes.p, nn, nt, (uint8_t*)d_last.p, (int*)d_err.p);
+                raw_nodes.get<const rt_bvh_node>(), nn, nt, d_last.get<uint8_t>(), d_err.get<int>());
             hipLaunchKernelGGL(k_relayout_nodes, dim3((nn + 255u) / 256u), dim3(256), 0, ctx->stream,
-                (const rt_bvh_node*)raw_nodes.p, nn, (const uint32_t*)d_index.p, (float4*)s.nodes, (int*)d_err.p);
+                raw_nodes.get<const rt_bvh_node>(), nn, d_index.get<const uint32_t>(), (float4*)s.nodes, d_err.get<int>());
             hipLaunchKernelGGL(k_relayout_triangles, dim3((nt + 255u) / 256u), dim3(256), 0, ctx->stream,
-                (const rt_triangle*)raw_tris.p, nt, sd->num_materials, (const uint8_t*)d_last.p, (float4*)s.tris_rt,
-                (float4*)s.tris_sh, (int*)d_err.p);
+                raw_tris.get<const rt_triangle>(), nt, sd->num_materials, d_last.get<const uint8_t>(), (float4*)s.tris_rt,
+                (float4*)s.tris_sh, d_err.get<int>());
             hipLaunchKernelGGL(k_relayout_leaf_bounds, dim3((nn + 255u) / 256u), dim3(256), 0, ctx->stream,
-                (const rt_bvh_node*)raw_nodes.p, nn, nt, (float4*)s.tris_rt);
+                raw_nodes.get<const rt_bvh_node>(), nn, nt, (float4*)s.tris_rt);
             ok = hipGetLastError() == hipSuccess &&
                  hipMemcpyAsync((char*)s.nodes + (size_t)n_interior * 64, super_root.data(), 64, hipMemcpyHostToDevice,
                      ctx->stream) == hipSuccess &&
-                 hipMemcpyAsync(&relayout_err, d_err.p, sizeof(int), hipMemcpyDeviceToHost, ctx->stream) == hipSuccess &&
+                 hipMemcpyAsync(&relayout_err, d_err.get(), sizeof(int), hipMemcpyDeviceToHost, ctx->stream) == hipSuccess &&
                  hipStreamSynchronize(ctx->stream) == hipSuccess;
         }
         if (ok && relayout_err == RL_OK && ctx->device_fold && ctx->build_wide == 1u && fits_offsets32(nt))
         {
             const bool want_host_copy = ctx->wide_layout != 0u || (may_own && (ctx->shadow_tree == 1u || ctx->closest_tree == 1u));   // the pair layout and the choice by proxy rays work on the host
-            folded_on_device = devfold::fold(ctx->stream, (const rt_bvh_node*)raw_nodes.p, nn, sd->nodes[0], nullptr, nullptr, (WideNode**)&s.trees[TREE_REF].recs, &n_wide_dev, &w_entry,
+            folded_on_device = devfold::fold(ctx->stream, raw_nodes.get<const rt_bvh_node>(), nn, sd->nodes[0], nullptr, nullptr, (WideNode**)&s.trees[TREE_REF].recs, &n_wide_dev, &w_entry,
                                              &wide_roots, want_host_copy ? &wide : nullptr, nullptr, &t_dev_fold);
             (void)hipGetLastError();
         }
@@ -938,14 +939,14 @@ struct Upload
     // the small arrays, as the caller gave them
     void upload_tables()
     {
-        rc |= dev_alloc_copy(ctx, &s.materials, sd->materials, (size_t)sd->num_materials * sizeof(rt_packed_material));
-        rc |= dev_alloc_copy(ctx, &s.textures, sd->textures, (size_t)sd->num_textures * sizeof(rt_texture));
-        rc |= dev_alloc_copy(ctx, &s.texture_data, sd->texture_data, (size_t)sd->num_texture_data * 4);
-        rc |= dev_alloc_copy(ctx, &s.lights, lights.data(), lights.size() * sizeof(float4));
-        rc |= dev_alloc_copy(ctx, &s.env, sd->env_rgba, (size_t)sd->env_width * sd->env_height * 16);
-        rc |= dev_alloc_copy(ctx, &s.emissive, sd->emissive_indices, (size_t)sd->num_emissive * 4);
+        rc |= scene_array(ctx, &s.materials, sd->materials, (size_t)sd->num_materials * sizeof(rt_packed_material));
+        rc |= scene_array(ctx, &s.textures, sd->textures, (size_t)sd->num_textures * sizeof(rt_texture));
+        rc |= scene_array(ctx, &s.texture_data, sd->texture_data, (size_t)sd->num_texture_data * 4);
+        rc |= scene_array(ctx, &s.lights, lights.data(), lights.size() * sizeof(float4));
+        rc |= scene_array(ctx, &s.env, sd->env_rgba, (size_t)sd->env_width * sd->env_height * 16);
+        rc |= scene_array(ctx, &s.emissive, sd->emissive_indices, (size_t)sd->num_emissive * 4);
         if (sd->material_texture_indices)
-            rc |= dev_alloc_copy(ctx, &s.mat_tex16, sd->material_texture_indices, (size_t)sd->num_materials * 6 * sizeof(uint16_t));
+            rc |= scene_array(ctx, &s.mat_tex16, sd->material_texture_indices, (size_t)sd->num_materials * 6 * sizeof(uint16_t));
         t_device = lap() - t_dev_fold;
     }
 
@@ -963,7 +964,7 @@ struct Upload
             pair_layout_by_area(wide, wide_roots, sd->nodes, nn, (const ownbvh::Metric*)nullptr);
             if (folded_on_device && hipMemcpyAsync(ref.recs, wide.data(), wide.size() * sizeof(WideNode), hipMemcpyHostToDevice, ctx->stream) != hipSuccess) rc |= fail(ctx, "rt_scene_upload: uploading the paired records failed");
         }
-        if (!folded_on_device && have_wide) rc |= dev_alloc_copy(ctx, &ref.recs, wide.data(), wide.size() * sizeof(WideNode));
+        if (!folded_on_device && have_wide) rc |= scene_array(ctx, &ref.recs, wide.data(), wide.size() * sizeof(WideNode));
         ref.n = have_wide ? n_wide_ref : 0u;
         ref.entry = w_entry;
         t_fold = lap() + t_dev_fold;
@@ -996,8 +997,8 @@ struct Upload
         {
             WideTree& t = s.trees[slot];
             t.n = (uint32_t)own.wide.size(); t.entry = own.entry;
-            if (own.d_wide) { t.recs = own.d_wide; own.d_wide = nullptr; }                     // folded on the device: the records are there
-            else rc |= dev_alloc_copy(ctx, &t.recs, own.wide.data(), own.wide.size() * sizeof(WideNode));
+            if (own.d_wide) t.recs = own.d_wide.release();                                     // folded on the device: the records are there
+            else rc |= scene_array(ctx, &t.recs, own.wide.data(), own.wide.size() * sizeof(WideNode));
         };
         if (have_wide && n_wide_ref != 0u && may_own && ctx->shadow_tree)
         {
@@ -2752,17 +2753,17 @@ extern "C++" template <class F> static int debug_on_device(rt_ctx* ctx, const ch
     std::initializer_list<void*> out, F&& run)
 {
     (void)hipSetDevice(ctx->device);
+    dev::Temps tmp(ctx->stream);
     std::vector<float4*> buf(n_images, nullptr);
     const size_t bytes = n * sizeof(float4);
     bool ok = true;
-    for (float4*& b : buf) ok = ok && hipMalloc((void**)&b, bytes) == hipSuccess;
+    for (float4*& b : buf) ok = ok && tmp.array(b, n);
     size_t k = 0;
     for (const void* p : in) ok = ok && hipMemcpyAsync(buf[k++], p, bytes, hipMemcpyHostToDevice, ctx->stream) == hipSuccess;
     hipError_t e = ok ? run(buf.data()) : hipErrorOutOfMemory;
     k = n_images - out.size();
     for (void* p : out) if (e == hipSuccess) e = hipMemcpyAsync(p, buf[k++], bytes, hipMemcpyDeviceToHost, ctx->stream);
     hipError_t es = hipStreamSynchronize(ctx->stream);
-    for (float4* b : buf) if (b) (void)hipFree(b);
     if (e == hipSuccess) e = es;
     if (e != hipSuccess) { (void)hipGetLastError(); return fail(ctx, std::string(who) + ": " + hipGetErrorString(e)); }
     return RT_OK;
