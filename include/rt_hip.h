@@ -378,6 +378,52 @@ int rt_frame_pick_all(rt_frame* frame, uint32_t x, uint32_t y, uint32_t max_hits
 int rt_debug_trace_all(rt_ctx* ctx_or_null, const rt_bvh_node* nodes, uint32_t num_nodes, const rt_triangle* triangles, uint32_t num_triangles,
                        const rt_ray* rays, uint32_t n, uint32_t max_hits, rt_ray_hits* out, rt_hit* hits);
 
+/* ---- within: every triangle within a radius of each of the CALLER's points, counted, the nearest of them sorted (opt-in extension).
+ * A contact set, a selection brush, how many surfaces lie within a bias, the k nearest triangles.  raytracing_amd/csrc/within.h states the rule; the
+ * distances are nearest.h's, unchanged.  rt_point is reused: max_distance is the radius and may be +inf.
+ *   a point is SEARCHED under rt_scene_nearest's rule.  r2 = max_distance * max_distance, rounded once.
+ *   the MEMBER SET M of a searched point: every triangle whose d2 (nearest_point_triangle on the shading record's corners, rt_scene_nearest's operands)
+ *     satisfies d2 <= r2; a NaN d2 is no member.  Members are ordered by ascending (d2, primitive_id), d2 compared as binary32.
+ *   without RT_WITHIN_K_NEAREST: count = |M|, stored = min(count, max_near), nearest_primitive = the first member or RT_INVALID_ID (rt_scene_nearest's
+ *     primitive_id for the same point), flags bit 0 = searched; near[i * max_near + j] = rt_scene_nearest's record form of member j for j < stored, the
+ *     nothing-found record beyond.  The walk's bound is r2 and is never lowered: a subtree is skipped exactly when nearest_box_d2 > r2.
+ *   with RT_WITHIN_K_NEAREST (max_near >= 1): the same first min(|M|, max_near) members are listed, count == stored (nothing beyond the list is looked
+ *     for), flags bit 1 is set.  The bound starts at r2 and becomes the last list entry's d2 once the list is full; the comparison stays strict, so a tie
+ *     with the last entry is visited and the lower primitive_id wins.  max_near = 1 gives rt_scene_nearest's record byte for byte.  With neither near nor
+ *     surfaces there is no list to shrink the search by: the counting walk runs and the record is made from its count (the same record, a full walk's cost).
+ *   a smaller max_near gives a prefix of a larger one's list.  A point that is not searched gives zeros, RT_INVALID_ID and nothing-found records.
+ *   surfaces (optional, max_near per point): the rt_surface of each listed member as rt_scene_nearest makes it; miss records beyond `stored`.  A call
+ *     that asks for surfaces only keeps its rt_nearest records in the first 32 bytes of each surface record on the way.
+ *   M is a statement about triangles and nearest.h alone -- bit for bit rt_debug_within's brute force, whichever records are walked (the 4-wide fold, an
+ *     adapted or imported fold, the child-pair records), after any refit or pose: nearest_box_d2 <= d2 holds in binary32 for every box that holds a
+ *     triangle's corners, so a subtree skipped at bound b holds only triangles with d2 > b; b is r2 (no member is skipped) or the k-th smallest d2 met so
+ *     far, which is never below the final one (no listed member is skipped).
+ * Runs on the context's stream like a nearest query, touches no frame and no rt_stats field, and uses the ray queries' spill area, status word and staging
+ * arrays.
+ *   rt_scene_within: host arrays, staged in chunks of at most 4 Mi member records; returns when the outputs are written.
+ *   rt_scene_within_buffer: rt_buffers of this context (n rt_point, n rt_point_hits, n * max_near rt_nearest / rt_surface); only enqueues.
+ * Refused with nothing launched: a NULL context, no scene, NULL points with n > 0, out NULL, max_near > RT_WITHIN_MAX, near or surfaces with max_near == 0,
+ * RT_WITHIN_K_NEAREST with max_near == 0, unknown option bits, a buffer of another context or too small.  n == 0 is RT_OK and does nothing. */
+#define RT_WITHIN_MAX 8
+#define RT_WITHIN_K_NEAREST 1u      /* options bit: do not count, shrink the search to the max_near-th member */
+#define RT_POINT_HITS_SEARCHED 1u   /* rt_point_hits.flags bit 0 */
+#define RT_POINT_HITS_K_NEAREST 2u  /* rt_point_hits.flags bit 1: a k-nearest answer, count == stored */
+typedef struct rt_point_hits { uint32_t count; uint32_t stored; uint32_t nearest_primitive; uint32_t flags; } rt_point_hits;      /* 16 bytes */
+int rt_scene_within(rt_ctx* ctx, const rt_point* points, uint32_t n, uint32_t max_near, uint32_t options, rt_point_hits* out, rt_nearest* near_or_null,
+                    rt_surface* surfaces_or_null);
+int rt_scene_within_buffer(rt_ctx* ctx, rt_buffer* points, uint32_t n, uint32_t max_near, uint32_t options, rt_buffer* out, rt_buffer* near_or_null,
+                           rt_buffer* surfaces_or_null);
+/* brute force over all of `triangles` (primitive_id = the index): within.h on the host (ctx == NULL) or k_within_brute on uploaded copies.  The two agree bit
+ * for bit.  near may be NULL when max_near == 0.  Refused: a NULL argument, max_near > RT_WITHIN_MAX, RT_WITHIN_K_NEAREST with max_near == 0, unknown
+ * option bits. */
+int rt_debug_within(rt_ctx* ctx_or_null, const rt_triangle* triangles, uint32_t num_triangles, const rt_point* points, uint32_t n, uint32_t max_near,
+                    uint32_t options, rt_point_hits* out, rt_nearest* near);
+/* the kernel's walk on the host (no device), over the child-pair form of `nodes` (wide = 0) or build_wide_bvh's 4-wide records of them (wide = 1), with the
+ * bound above; triangles_tested_or_null[i] = how many triangles point i was tested against.  Refused where rt_debug_nearest_walk is, and as rt_debug_within. */
+int rt_debug_within_walk(const rt_bvh_node* nodes, uint32_t num_nodes, const rt_triangle* triangles, uint32_t num_triangles, int wide,
+                         const rt_point* points, uint32_t n, uint32_t max_near, uint32_t options, rt_point_hits* out, rt_nearest* near,
+                         uint32_t* triangles_tested_or_null);
+
 /* One fold adaptation per process GROUP instead of one per rank (N ranks that tile one image hold the same scene and would each probe, rotate and fold for
  * identical records): the context's current 4-wide records -- the closest-hit rays' and the shadow rays' (n_shadow == 0: they share), as adapted so far -- to
  * host buffers of `capacity` records each (records NULL: size query; entries2 = {closest entry, shadow entry}), and into another context that has uploaded
@@ -889,4 +935,5 @@ RT_STATIC_ASSERT(sizeof(rt_surface) == 64, "rt_surface");
 RT_STATIC_ASSERT(sizeof(rt_bake_result) == 16 && sizeof(rt_bake_desc) == 20, "rt_bake_result / rt_bake_desc");
 RT_STATIC_ASSERT(sizeof(rt_point) == 16 && sizeof(rt_nearest) == 32, "rt_point / rt_nearest");
 RT_STATIC_ASSERT(sizeof(rt_ray_hits) == 16, "rt_ray_hits");
+RT_STATIC_ASSERT(sizeof(rt_point_hits) == 16, "rt_point_hits");
 #endif /* RT_HIP_H */

@@ -53,6 +53,7 @@ HIP_UNITS = [
     ("query", "query.hip", True),              # caller-supplied rays traced against the uploaded scene, the surface record of a hit: kernels (the walk itself: walk_kernels.h, shared with bake and nearest) + the host driver core of all three + the host restatement (a code object of its own)
     ("bake", "bake.hip", True),                # ambient occlusion and bent normals at caller-supplied points: kernels on walk_kernels.h + host driver on query.hip's core + the host restatement (a code object of its own)
     ("nearest", "nearest.hip", True),          # the nearest surface point to caller-supplied points: kernels on walk_kernels.h's stack + host driver on query.hip's core + the host's brute force and walk (a code object of its own)
+    ("within", "within.hip", True),            # every triangle within a radius of caller-supplied points, counted and sorted: kernels on walk_kernels.h's stack and point_box_step + host driver on query.hip's core + the host's brute force and walk (a code object of its own)
     ("all_hits", "all_hits.hip", True),        # every surface a caller-supplied ray crosses, counted and sorted: kernels on walk_kernels.h + host driver on query.hip's core + the host's brute force (a code object of its own)
     ("wide_bvh", "wide_bvh.cpp", False),       # build_wide_bvh, pair layout, the adaptation's host walks (no device code)
 ]

@@ -115,6 +115,7 @@ EXPORTS = [
     "rt_scene_bake", "rt_scene_bake_buffer", "rt_debug_bake_rays", "rt_debug_bake_reduce",
     "rt_scene_nearest", "rt_scene_nearest_buffer", "rt_debug_nearest", "rt_debug_nearest_walk",
     "rt_scene_trace_all", "rt_scene_trace_all_buffer", "rt_frame_pick_all", "rt_debug_trace_all",
+    "rt_scene_within", "rt_scene_within_buffer", "rt_debug_within", "rt_debug_within_walk",
 ]
 
 OPT_MAX_BOUNCES, OPT_WHITE_FURNACE, OPT_SAMPLER, OPT_AOV, OPT_DENOISER, OPT_DROP_LAST, OPT_PROFILE, OPT_TRACE_VARIANT, OPT_TRACE_WAVES, OPT_SAMPLES_IN_FLIGHT, OPT_SELECT_FORM_BOX, OPT_PACKET_BOUNCES, OPT_TRACE_TUNE, OPT_DEBUG_ALLOC_LIMIT, OPT_PATH_STATE_LIMIT_MB, OPT_PIPELINES, OPT_SHADE_PARTITION, OPT_OVERLAP_SHADOW, OPT_SMALL_LAUNCH_PATHS, OPT_COMPACT_LOG, OPT_DEBUG_LOG_POOL_DIV, OPT_TRACE_TAIL_LANES, OPT_TRACE_TAIL_PATHS, OPT_CHUNK_REFILL, OPT_STAGE_PIPES, OPT_FRAME_KERNEL, OPT_SAMPLES_AHEAD = range(27)
@@ -212,6 +213,9 @@ def load():
         "rt_scene_trace_all": (i32, [vp, vp, u32, u32, vp, vp, vp]), "rt_scene_trace_all_buffer": (i32, [vp, vp, u32, u32, vp, vp, vp]),
         "rt_frame_pick_all": (i32, [vp, u32, u32, u32, vp, vp, vp, vp]),
         "rt_debug_trace_all": (i32, [vp, vp, u32, vp, u32, vp, u32, u32, vp, vp]),
+        "rt_scene_within": (i32, [vp, vp, u32, u32, u32, vp, vp, vp]), "rt_scene_within_buffer": (i32, [vp, vp, u32, u32, u32, vp, vp, vp]),
+        "rt_debug_within": (i32, [vp, vp, u32, vp, u32, u32, u32, vp, vp]),
+        "rt_debug_within_walk": (i32, [vp, u32, vp, u32, i32, vp, u32, u32, u32, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -521,6 +525,46 @@ def debug_nearest_walk(nodes, triangles, points, wide=True, counts=False):
     return (out, tested) if counts else out
 
 
+WITHIN_MAX = 8              # RT_WITHIN_MAX
+WITHIN_K_NEAREST = 1        # RT_WITHIN_K_NEAREST: list the max_near nearest members and look no further
+POINT_HITS_SEARCHED = 1     # rt_point_hits.flags bit 0
+POINT_HITS_K_NEAREST = 2    # rt_point_hits.flags bit 1
+
+
+def debug_within(ctx, triangles, points, max_near=WITHIN_MAX, k_nearest=False):
+    """rt_debug_within: (types.point_hits[n], types.nearest[n, max_near]) of `points` (point_records' rule; max_distance is the radius) by brute force
+    over all `triangles` (types.triangle).  ctx None = the host (csrc/within.h), else k_within_brute on ctx's GPU."""
+    lib = load()
+    tris = np.ascontiguousarray(triangles, T.triangle)
+    pts = point_records(points)
+    out = np.zeros(len(pts), T.point_hits)
+    near = np.zeros((len(pts), max_near), T.nearest)
+    handle = ctx.handle if ctx is not None else None
+    rc = lib.rt_debug_within(handle, tris.ctypes.data if len(tris) else None, len(tris), pts.ctypes.data if len(pts) else None, len(pts), max_near,
+                             WITHIN_K_NEAREST if k_nearest else 0, out.ctypes.data if len(pts) else None, near.ctypes.data if near.size else None)
+    if rc != 0:
+        raise RtError(lib.rt_last_error(handle).decode())
+    return out, near
+
+
+def debug_within_walk(nodes, triangles, points, max_near=WITHIN_MAX, k_nearest=False, wide=True, counts=False):
+    """rt_debug_within_walk (host only): k_within's walk over the child-pair form of `nodes` (types.bvh_node; wide=False) or over build_wide_bvh's 4-wide
+    records of them (wide=True): (types.point_hits[n], types.nearest[n, max_near]), with uint32[n] triangles tested per point appended when counts=True"""
+    lib = load()
+    nd = np.ascontiguousarray(nodes, T.bvh_node)
+    tris = np.ascontiguousarray(triangles, T.triangle)
+    pts = point_records(points)
+    out = np.zeros(len(pts), T.point_hits)
+    near = np.zeros((len(pts), max_near), T.nearest)
+    tested = np.zeros(len(pts), np.uint32)
+    rc = lib.rt_debug_within_walk(nd.ctypes.data if len(nd) else None, len(nd), tris.ctypes.data if len(tris) else None, len(tris), int(wide),
+                                  pts.ctypes.data if len(pts) else None, len(pts), max_near, WITHIN_K_NEAREST if k_nearest else 0,
+                                  out.ctypes.data if len(pts) else None, near.ctypes.data if near.size else None, tested.ctypes.data if len(pts) else None)
+    if rc != 0:
+        raise RtError(lib.rt_last_error(None).decode())
+    return (out, near, tested) if counts else (out, near)
+
+
 def choose_tree(scene, shadow=True, mode=1):
     """rt_debug_choose_tree (host only, no GPU): the 4-wide tree rt_scene_upload would give this scene's shadow / closest-hit
     rays under RT_CTX_OPT_SHADOW_TREE / RT_CTX_OPT_CLOSEST_TREE = mode.  scene: dict with triangles, nodes, lights.
@@ -828,6 +872,32 @@ class Context:
         Buffer.read() or finish() waits."""
         h = lambda b: b.handle if b is not None else None
         _check(self.lib, self.handle, self.lib.rt_scene_nearest_buffer(self.handle, h(points), n, h(out), h(surfaces)))
+
+    def within(self, points, max_near=WITHIN_MAX, k_nearest=False, surfaces=False):
+        """rt_scene_within: every triangle of the uploaded scene within max_distance of each of the caller's points (point_records' rule):
+        (types.point_hits[n], types.nearest[n, max_near]) -- the counts, and the nearest max_near members in ascending (d2, primitive_id) order -- or
+        (records, members, types.surface[n, max_near]) with surfaces=True.  max_near=0: the records alone.  k_nearest: list the max_near nearest and
+        look no further (count == stored)."""
+        pts = point_records(points)
+        n = len(pts)
+        out = np.zeros(n, T.point_hits)
+        options = WITHIN_K_NEAREST if k_nearest else 0
+        if max_near == 0:
+            if surfaces:
+                raise RtError("within: surfaces need max_near > 0")
+            _check(self.lib, self.handle, self.lib.rt_scene_within(self.handle, pts.ctypes.data if n else None, n, 0, options, out.ctypes.data, None, None))
+            return out
+        near = np.zeros((n, max_near), T.nearest)
+        surf = np.zeros((n, max_near), T.surface) if surfaces else None
+        _check(self.lib, self.handle, self.lib.rt_scene_within(self.handle, pts.ctypes.data if n else None, n, max_near, options, out.ctypes.data, near.ctypes.data,
+                                                                 surf.ctypes.data if surfaces else None))
+        return (out, near, surf) if surfaces else (out, near)
+
+    def within_buffer(self, points, n, max_near, out, near=None, surfaces=None, k_nearest=False):
+        """rt_scene_within_buffer: the same over Buffers of this context (n points and records, n * max_near members / surfaces; an output that is not
+        wanted is None).  Only enqueues: Buffer.read() or finish() waits."""
+        h = lambda b: b.handle if b is not None else None
+        _check(self.lib, self.handle, self.lib.rt_scene_within_buffer(self.handle, h(points), n, max_near, WITHIN_K_NEAREST if k_nearest else 0, h(out), h(near), h(surfaces)))
 
     def bake(self, points, samples, seed=0, bias=BAKE_BIAS_DEFAULT, radius=BAKE_RADIUS_DEFAULT, from_surfaces=False):
         """rt_scene_bake: ambient occlusion and bent normals at the caller's points (bake_points' rule): types.bake_result[n] -- unoccluded / samples is the

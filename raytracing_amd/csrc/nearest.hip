@@ -4,6 +4,7 @@
 // -ffp-contract=off like every other unit.
 #include <hip/hip_runtime.h>
 #include <string.h>
+#include <functional>
 #include <thread>
 #include <vector>
 #include "rt_hip.h"
@@ -86,8 +87,8 @@ bool brute_device(hipStream_t stream, const rt_triangle* tris, uint32_t n_tris, 
     return tmp.finish(ok && dev::clean(), out, d_out, (size_t)n * sizeof(rt_nearest));
 }
 
-const char* walk_host(const rt_bvh_node* nodes, uint32_t nn, const rt_triangle* tris, uint32_t n_tris, bool wide, const rt_point* points, uint32_t n,
-    rt_nearest* out, uint32_t* tested)
+const char* walk_points(const rt_bvh_node* nodes, uint32_t nn, const rt_triangle* tris, uint32_t n_tris, bool wide, const rt_point* points, uint32_t n,
+    uint32_t* tested, const std::function<float(uint32_t, uint32_t, const NpTriangle&, float)>& triangle)
 {
     // the `last` flags of the trace records, and the child-pair form's references: an interior node's index, RT_LEAF_BIT | first triangle for a leaf
     std::vector<uint8_t> last(n_tris, 0);
@@ -110,11 +111,10 @@ const char* walk_host(const rt_bvh_node* nodes, uint32_t nn, const rt_triangle* 
     for (uint32_t i = 0; i < n; ++i)
     {
         const float* p = points[i].position;
-        out[i] = nearest_none();
         if (tested) tested[i] = 0u;
         if (!nearest_searched(p, points[i].max_distance)) continue;
-        float best = points[i].max_distance * points[i].max_distance;
-        uint32_t best_prim = RT_INVALID_ID, count = 0u;
+        float best = points[i].max_distance * points[i].max_distance;          // the bound that prunes
+        uint32_t count = 0u;
         struct Entry { uint32_t ref; float d2; } stack[RT_W4_STACK_MAX];
         int sp = 0;
         uint32_t ref = RT_IDLE_REF;
@@ -144,7 +144,7 @@ const char* walk_host(const rt_bvh_node* nodes, uint32_t nn, const rt_triangle* 
                 walk::triangle_corners(tris[prim], p1, p2, p3);
                 const NpTriangle t = nearest_point_triangle(p, p1, p2, p3);
                 ++count;
-                if (nearest_accepts(t.d2, prim, best, best_prim)) { best = t.d2; best_prim = prim; }
+                best = triangle(i, prim, t, best);
                 if (last[prim]) pop();
                 else ref = RT_LEAF_BIT | (prim + 1u);
                 continue;
@@ -208,9 +208,28 @@ const char* walk_host(const rt_bvh_node* nodes, uint32_t nn, const rt_triangle* 
             else pop();
         }
         if (tested) tested[i] = count;
-        if (best_prim == RT_INVALID_ID) continue;
-        walk::triangle_corners(tris[best_prim], p1, p2, p3);
-        out[i] = nearest_record(p, p1, p2, p3, best_prim);
+    }
+    return nullptr;
+}
+
+const char* walk_host(const rt_bvh_node* nodes, uint32_t nn, const rt_triangle* tris, uint32_t n_tris, bool wide, const rt_point* points, uint32_t n,
+    rt_nearest* out, uint32_t* tested)
+{
+    std::vector<uint32_t> best_prim(n, RT_INVALID_ID);
+    if (const char* why = walk_points(nodes, nn, tris, n_tris, wide, points, n, tested, [&](uint32_t i, uint32_t prim, const NpTriangle& t, float best)
+        {
+            if (!nearest_accepts(t.d2, prim, best, best_prim[i])) return best;
+            best_prim[i] = prim;
+            return t.d2;
+        }))
+        return why;
+    float p1[3], p2[3], p3[3];
+    for (uint32_t i = 0; i < n; ++i)
+    {
+        out[i] = nearest_none();
+        if (best_prim[i] == RT_INVALID_ID) continue;
+        walk::triangle_corners(tris[best_prim[i]], p1, p2, p3);
+        out[i] = nearest_record(points[i].position, p1, p2, p3, best_prim[i]);
     }
     return nullptr;
 }

@@ -6,10 +6,12 @@
 #include <hip/hip_vector_types.h>
 #include <stdint.h>
 #include <stddef.h>
+#include <functional>
 #include "rt_hip.h"
 #include "query_host.h"
 
 struct DScene;
+struct NpTriangle;          // nearest.h
 
 namespace nearest
 {
@@ -22,6 +24,12 @@ bool launch(hipStream_t stream, query::Scratch& q, const DScene& sc, bool use_wi
 // rt_debug_nearest: brute force over all triangles, on the host or by k_nearest_brute on uploaded copies
 void brute_host(const rt_triangle* tris, uint32_t n_tris, const rt_point* points, uint32_t n, rt_nearest* out);
 bool brute_device(hipStream_t stream, const rt_triangle* tris, uint32_t n_tris, const rt_point* points, uint32_t n, rt_nearest* out);
+
+// k_nearest's and k_within's walk on the host over `nodes` (wide: over build_wide_bvh's records of them).  Every searched point starts with the bound
+// max_distance^2; triangle(i, prim, t, bound) is called for each triangle point i reaches (t = nearest_point_triangle's answer) and returns the bound from
+// then on.  tested[i] (optional) = how many triangles point i reached.  nullptr, or why the walk was refused.
+const char* walk_points(const rt_bvh_node* nodes, uint32_t nn, const rt_triangle* tris, uint32_t n_tris, bool wide, const rt_point* points, uint32_t n,
+    uint32_t* tested, const std::function<float(uint32_t, uint32_t, const NpTriangle&, float)>& triangle);
 
 // rt_debug_nearest_walk: k_nearest's walk on the host over `nodes` (wide: over build_wide_bvh's records of them).  nullptr, or why the walk was refused.
 const char* walk_host(const rt_bvh_node* nodes, uint32_t nn, const rt_triangle* tris, uint32_t n_tris, bool wide, const rt_point* points, uint32_t n,

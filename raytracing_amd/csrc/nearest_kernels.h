@@ -5,7 +5,7 @@
 //   k_nearest_brute    one lane per point over ALL triangles of an rt_triangle array (rt_debug_nearest's device form: the same nearest.h with no tree)
 //   k_nearest_surface  one lane per point: rt_surface (64 bytes) of the nearest point, by query.h's query_surface
 //
-// The walk.  k_query_trace's fused one-loop shape on walk_kernels.h's Stack (the box step below is this kernel's own): a lane's point is at a
+// The walk.  k_query_trace's fused one-loop shape on walk_kernels.h's Stack (the box step, walk::point_box_step, is this kernel's and k_within's): a lane's point is at a
 // reference -- a 4-wide record (WIDE), a child-pair record (!WIDE), or a triangle of a leaf -- and every pass of the one loop fetches the lane's next 64 bytes
 // with the same four 16-byte loads and takes its step.  What differs from a ray's walk is the test and the order: a box is passed when !(nearest_box_d2 > best),
 // the nearest passing box is visited next, and the others wait on the stack with their nearest_box_d2 as the entry value, farthest deepest; a pop re-tests
@@ -43,7 +43,6 @@ __global__ __launch_bounds__(64) void k_nearest(DScene sc, const float4* __restr
     const char* const node_base = reinterpret_cast<const char*>(WIDE ? sc.wnodes : sc.nodes);
     const char* const tri_base = reinterpret_cast<const char*>(sc.tris_sh);
     const float* const flag_base = reinterpret_cast<const float*>(sc.tris_rt);
-    const float INF = __builtin_inff();
     const uint32_t n_chunks = (n >> 6) + ((n & 63u) != 0u ? 1u : 0u);
 
     for (uint32_t chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x)
@@ -84,67 +83,7 @@ __global__ __launch_bounds__(64) void k_nearest(DScene sc, const float4* __restr
                     if (last != 0.0f) pop();
                     else ref = RT_LEAF_BIT | (prim + 1u);
                 }
-                else
-                {
-                    uint32_t r[4];
-                    float e[4];
-                    if (WIDE)
-                    {
-                        const uint32_t meta = __float_as_uint(q0.w);
-                        const float cell[3] = {__uint_as_float((meta & 0xFFu) << 23), __uint_as_float(((meta >> 8) & 0xFFu) << 23), __uint_as_float(((meta >> 16) & 0xFFu) << 23)};
-                        const float origin[3] = {q0.x, q0.y, q0.z};
-                        const uint32_t low[3] = {__float_as_uint(q1.x), __float_as_uint(q1.y), __float_as_uint(q1.z)};
-                        const uint32_t high[3] = {__float_as_uint(q1.w), __float_as_uint(q2.x), __float_as_uint(q2.y)};
-                        r[0] = __float_as_uint(q2.z); r[1] = __float_as_uint(q2.w); r[2] = __float_as_uint(q3.x); r[3] = __float_as_uint(q3.y);
-#pragma unroll
-                        for (int k = 0; k < 4; ++k)
-                        {
-                            float lo[3], hi[3];
-#pragma unroll
-                            for (int a = 0; a < 3; ++a)
-                            {
-                                lo[a] = (float)((low[a] >> (8 * k)) & 0xFFu) * cell[a] + origin[a];       // exact (wide_frame)
-                                hi[a] = (float)((high[a] >> (8 * k)) & 0xFFu) * cell[a] + origin[a];
-                            }
-                            e[k] = nearest_box_d2(p, lo, hi);
-                        }
-                    }
-                    else
-                    {
-                        const float lo0[3] = {q0.x, q0.y, q2.x}, hi0[3] = {q0.z, q0.w, q2.y}, lo1[3] = {q1.x, q1.y, q2.z}, hi1[3] = {q1.z, q1.w, q2.w};
-                        r[0] = __float_as_uint(q3.x); r[1] = __float_as_uint(q3.y); r[2] = RT_EMPTY_REF; r[3] = RT_EMPTY_REF;
-                        e[0] = nearest_box_d2(p, lo0, hi0); e[1] = nearest_box_d2(p, lo1, hi1); e[2] = INF; e[3] = INF;
-                    }
-                    // a slot that is empty or too far leaves the step: marked by RT_EMPTY_REF, keyed +inf
-#pragma unroll
-                    for (int k = 0; k < 4; ++k)
-                    {
-                        const bool pass = r[k] != RT_EMPTY_REF && !(e[k] > best);
-                        r[k] = pass ? r[k] : RT_EMPTY_REF;
-                        e[k] = pass ? e[k] : INF;
-                    }
-                    // ascending by nearest_box_d2 (five exchanges; two candidates need the first only)
-                    auto exchange = [&](int a, int b)
-                    {
-                        const bool s = e[b] < e[a];
-                        const float te = s ? e[b] : e[a]; e[b] = s ? e[a] : e[b]; e[a] = te;
-                        const uint32_t tr = s ? r[b] : r[a]; r[b] = s ? r[a] : r[b]; r[a] = tr;
-                    };
-                    exchange(0, 1);
-                    if (WIDE) { exchange(2, 3); exchange(0, 2); exchange(1, 3); exchange(1, 2); }
-                    // the nearest passing slot is visited next, the others wait on the stack, farthest deepest
-                    uint32_t next = RT_IDLE_REF;
-                    float next_e = 0.0f;
-#pragma unroll
-                    for (int k = WIDE ? 3 : 1; k >= 0; --k)
-                        if (r[k] != RT_EMPTY_REF)
-                        {
-                            if (next != RT_IDLE_REF) stack.push(next, next_e);
-                            next = r[k]; next_e = e[k];
-                        }
-                    if (next != RT_IDLE_REF) ref = next;
-                    else pop();
-                }
+                else walk::point_box_step<WIDE>(q0, q1, q2, q3, p, best, ref, stack);
             }
         }
 

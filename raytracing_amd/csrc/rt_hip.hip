@@ -32,6 +32,7 @@
 #include "bake_host.h"       // ambient occlusion and bent normals at caller-supplied points (bake.hip)
 #include "nearest_host.h"    // the nearest surface point to caller-supplied points (nearest.hip)
 #include "all_hits_host.h"   // every surface a caller-supplied ray crosses (all_hits.hip)
+#include "within_host.h"     // every triangle within a radius of caller-supplied points (within.hip)
 #include "device_memory.h"   // who owns a device allocation: dev::Mem, dev::Temps
 using namespace rtw;
 
@@ -1081,6 +1082,7 @@ extern "C" {
 #include "bake_impl.h"
 #include "nearest_impl.h"
 #include "all_hits_impl.h"
+#include "within_impl.h"
 
 // ---- scene -----------------------------------------------------------------
 int rt_scene_upload(rt_ctx* ctx, const rt_scene_desc* sd)

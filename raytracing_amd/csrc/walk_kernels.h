@@ -1,9 +1,10 @@
-// walk_kernels.h -- what the kernels of the caller-facing queries share (DESIGN.md sections 7h - 7k): k_query_trace (query_kernels.h), k_bake (bake_kernels.h),
-// k_nearest (nearest_kernels.h) and k_all_hits (all_hits_kernels.h) are built from the pieces below.  The frame's own walks (trace_kernels.h, rt_hip.hip's code
-// object) are not: this header is included by query.hip, bake.hip, nearest.hip and all_hits.hip only.
+// walk_kernels.h -- what the kernels of the caller-facing queries share (DESIGN.md sections 7h - 7l): k_query_trace (query_kernels.h), k_bake (bake_kernels.h),
+// k_nearest (nearest_kernels.h), k_all_hits (all_hits_kernels.h) and k_within (within_kernels.h) are built from the pieces below.  The frame's own walks (trace_kernels.h, rt_hip.hip's code
+// object) are not: this header is included by query.hip, bake.hip, nearest.hip, all_hits.hip and within.hip only.
 //
 //   Stack          a lane's traversal stack: push, and a pop that takes the walk's re-test
 //   Ray, ray_setup a ray as its walk needs it: 1/dir, the sign bits, the octant, and which records it walks
+//   point_box_step one pass of a point's walk (nearest, within) at a box record: the slots keyed by nearest_box_d2, nearest first
 //   ray_step       one pass of a ray's fused loop: the fetch of one 64-byte record and its leaf, child-pair or 4-wide step; what an accepted triangle does
 //                  to the walk is the step's mode (closest, any hit, all hits)
 //   read_shading_triangle, store_surface, store_nearest, triangle_corners   the records' readers and writers
@@ -38,6 +39,7 @@
 #include "trace_kernels.h"
 #include "query.h"
 #include "all_hits.h"
+#include "nearest.h"
 
 #define RT_QUERY_STACK_LDS 12
 #define RT_QUERY_SPILL_PER_LANE (RT_W4_STACK_MAX - RT_QUERY_STACK_LDS)
@@ -223,6 +225,73 @@ RT_DEV bool ray_step(const DScene& sc, const Ray& ray, const float t_min, float&
         else pop();
     }
     return accepted;
+}
+
+// One pass of a point's walk at a box record (q0 .. q3 = its 64 bytes): the four slots of a 4-wide record or the two children of a child-pair record, each
+// keyed by nearest_box_d2; those that pass !(key > best) ascending by key, the nearest visited next, the others pushed farthest deepest; none: a pop that
+// re-tests !(entry > best).  k_nearest's (nearest_kernels.h) and k_within's (within_kernels.h) step alike: `best` is whatever bound the caller's walk prunes by.
+template <bool WIDE>
+RT_DEV void point_box_step(const float4 q0, const float4 q1, const float4 q2, const float4 q3, const float (&p)[3], const float best, uint32_t& ref, Stack& stack)
+{
+    const float INF = __builtin_inff();
+    uint32_t r[4];
+    float e[4];
+    if (WIDE)
+    {
+        const uint32_t meta = __float_as_uint(q0.w);
+        const float cell[3] = {__uint_as_float((meta & 0xFFu) << 23), __uint_as_float(((meta >> 8) & 0xFFu) << 23), __uint_as_float(((meta >> 16) & 0xFFu) << 23)};
+        const float origin[3] = {q0.x, q0.y, q0.z};
+        const uint32_t low[3] = {__float_as_uint(q1.x), __float_as_uint(q1.y), __float_as_uint(q1.z)};
+        const uint32_t high[3] = {__float_as_uint(q1.w), __float_as_uint(q2.x), __float_as_uint(q2.y)};
+        r[0] = __float_as_uint(q2.z); r[1] = __float_as_uint(q2.w); r[2] = __float_as_uint(q3.x); r[3] = __float_as_uint(q3.y);
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+        {
+            float lo[3], hi[3];
+#pragma unroll
+            for (int a = 0; a < 3; ++a)
+            {
+                lo[a] = (float)((low[a] >> (8 * k)) & 0xFFu) * cell[a] + origin[a];       // exact (wide_frame)
+                hi[a] = (float)((high[a] >> (8 * k)) & 0xFFu) * cell[a] + origin[a];
+            }
+            e[k] = nearest_box_d2(p, lo, hi);
+        }
+    }
+    else
+    {
+        const float lo0[3] = {q0.x, q0.y, q2.x}, hi0[3] = {q0.z, q0.w, q2.y}, lo1[3] = {q1.x, q1.y, q2.z}, hi1[3] = {q1.z, q1.w, q2.w};
+        r[0] = __float_as_uint(q3.x); r[1] = __float_as_uint(q3.y); r[2] = RT_EMPTY_REF; r[3] = RT_EMPTY_REF;
+        e[0] = nearest_box_d2(p, lo0, hi0); e[1] = nearest_box_d2(p, lo1, hi1); e[2] = INF; e[3] = INF;
+    }
+    // a slot that is empty or too far leaves the step: marked by RT_EMPTY_REF, keyed +inf
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+    {
+        const bool pass = r[k] != RT_EMPTY_REF && !(e[k] > best);
+        r[k] = pass ? r[k] : RT_EMPTY_REF;
+        e[k] = pass ? e[k] : INF;
+    }
+    // ascending by nearest_box_d2 (five exchanges; two candidates need the first only)
+    auto exchange = [&](int a, int b)
+    {
+        const bool s = e[b] < e[a];
+        const float te = s ? e[b] : e[a]; e[b] = s ? e[a] : e[b]; e[a] = te;
+        const uint32_t tr = s ? r[b] : r[a]; r[b] = s ? r[a] : r[b]; r[a] = tr;
+    };
+    exchange(0, 1);
+    if (WIDE) { exchange(2, 3); exchange(0, 2); exchange(1, 3); exchange(1, 2); }
+    // the nearest passing slot is visited next, the others wait on the stack, farthest deepest
+    uint32_t next = RT_IDLE_REF;
+    float next_e = 0.0f;
+#pragma unroll
+    for (int k = WIDE ? 3 : 1; k >= 0; --k)
+        if (r[k] != RT_EMPTY_REF)
+        {
+            if (next != RT_IDLE_REF) stack.push(next, next_e);
+            next = r[k]; next_e = e[k];
+        }
+    if (next != RT_IDLE_REF) ref = next;
+    else ref = stack.pop([&](float entry) { return !(entry > best); });
 }
 
 // a triangle's 128-byte shading record (p1 uv1.x | p2 uv1.y | p3 uv2.x | n1 uv2.y | n2 uv3.x | n3 uv3.y | mtl_index ...) as query_surface reads it

@@ -26,7 +26,7 @@ EXPORTS = [
     "rth_render_upload_gpu_data", "rth_render_setup_seconds", "rth_render_create_with_options",
     "rth_render_set_refittable", "rth_render_refit", "rth_render_set_refit_motion",
     "rth_render_set_objects", "rth_render_pose", "rth_render_pick", "rth_render_integrator_pick", "rth_render_trace",
-    "rth_render_bake", "rth_render_occlusion_image", "rth_render_nearest", "rth_render_trace_all", "rth_render_pick_all",
+    "rth_render_bake", "rth_render_occlusion_image", "rth_render_nearest", "rth_render_within", "rth_render_trace_all", "rth_render_pick_all",
     "rth_scene_set_triangle_objects", "rth_scene_num_objects", "rth_scene_object_name", "rth_scene_num_triangle_objects", "rth_scene_triangle_objects",
 ]
 
@@ -77,6 +77,7 @@ def load():
         "rth_render_pick": (i32, [vp, u32, u32, vp, vp, vp]), "rth_render_integrator_pick": (i32, [vp, u32, u32, vp, vp, vp]), "rth_render_trace": (i32, [vp, vp, u32, i32, vp, vp, vp]),
         "rth_render_bake": (i32, [vp, vp, u32, vp, vp]), "rth_render_occlusion_image": (i32, [vp, vp, vp]),
         "rth_render_nearest": (i32, [vp, vp, u32, vp, vp]),
+        "rth_render_within": (i32, [vp, vp, u32, u32, u32, vp, vp, vp]),
         "rth_render_trace_all": (i32, [vp, vp, u32, u32, vp, vp, vp]), "rth_render_pick_all": (i32, [vp, u32, u32, u32, vp, vp, vp, vp]),
         "rth_render_num_nodes": (u32, [vp]), "rth_render_nodes": (vp, [vp]),
         "rth_render_set_aov": (i32, [vp, i32]), "rth_render_resolve": (i32, [vp, vp]),
@@ -437,6 +438,45 @@ class Render:
                 out["signed_distance"] = -float(found[i]["distance"]) if within[i] else float(found[i]["distance"])
             result.append(out)
         return result
+
+    def within(self, points, radius=None, k=0, k_nearest=False):
+        """Every triangle of the scene as it is posed now within a radius of each of the caller's points (Render::Within; points: capi.point_records' rule,
+        whose max_distance is the radius; radius=r overrides it for every point): one dict per point -- `count` (the triangles within the radius; with
+        k_nearest, the listed ones), `nearest_primitive` (0xFFFFFFFF when there is none) and `members`, the nearest min(count, k) of them in ascending
+        (distance, primitive_id) order as dicts like nearest()'s (the surface's fields plus `nearest`, the types.nearest record; `object_name` when the scene
+        was loaded with objects).  k <= 8.  k_nearest=True looks no further than the k-th member: the same list, sooner."""
+        from . import capi
+        pts = capi.point_records(points)
+        if radius is not None:
+            pts = pts.copy()
+            pts["max_distance"] = radius
+        n = len(pts)
+        out = np.zeros(n, T.point_hits)
+        near, surf = np.zeros((n, max(k, 1)), T.nearest), np.zeros((n, max(k, 1)), T.surface)
+        self._c(self.lib.rth_render_within(self.handle, pts.ctypes.data if n else None, n, k, capi.WITHIN_K_NEAREST if k_nearest else 0, out.ctypes.data,
+                                           near.ctypes.data if k else None, surf.ctypes.data if k else None))
+        names = self.scene.object_names()
+        objects = self.scene.triangle_objects() if names else None
+        result = []
+        for i in range(n):
+            members = []
+            for j in range(int(out[i]["stored"])):
+                m = self._surface_dict(surf[i, j], names, objects)
+                m["nearest"] = near[i, j]
+                members.append(m)
+            result.append({"count": int(out[i]["count"]), "nearest_primitive": int(out[i]["nearest_primitive"]), "members": members})
+        return result
+
+    def objects_within(self, point, radius):
+        """Which objects own the triangles within `radius` of `point` (the scene loaded with objects): {"objects": sorted names, "count": the triangles
+        within the radius, "complete": count <= 8}.  The names are those of the NEAREST 8 members: a within query lists no more, and it cannot skip
+        the members it has listed, so there is no exact way to read the rest in batches.  When `complete` is False, `count` says how many triangles the
+        names leave out of account; a smaller radius, or several points, narrows it."""
+        from . import capi
+        if not self.scene.object_names():
+            raise RtError("objects_within: the scene was not loaded with objects")
+        got = self.within(capi.point_records(np.asarray([list(point) + [radius]], np.float32)), k=8)[0]
+        return {"objects": sorted({m["object_name"] for m in got["members"]}), "count": got["count"], "complete": got["count"] <= 8}
 
     def trace_all(self, rays, max_hits=8, surfaces=False):
         """Every surface each of the caller's rays crosses in the scene as it is posed now (HIPPathTraceIntegrator::TraceAllHits; rays: types.ray records or

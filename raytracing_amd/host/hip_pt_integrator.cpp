@@ -183,6 +183,13 @@ void HIPPathTraceIntegrator::NearestPoints(rt_point const* points, std::size_t c
     Check(rt_scene_nearest(context_.Get(), points, (uint32_t)count, out, surfaces));
 }
 
+void HIPPathTraceIntegrator::PointsWithin(rt_point const* points, std::size_t count, std::uint32_t max_near, std::uint32_t options, rt_point_hits* out,
+    rt_nearest* near, rt_surface* surfaces)
+{
+    if (count > 0xFFFFFFFFull) throw HIPException("HIPPathTraceIntegrator::PointsWithin: more than 2^32 - 1 points in one call");
+    Check(rt_scene_within(context_.Get(), points, (uint32_t)count, max_near, options, out, near, surfaces));
+}
+
 void HIPPathTraceIntegrator::Pick(std::uint32_t x, std::uint32_t y, rt_ray* ray, rt_hit* hit, rt_surface* surface)
 {
     Check(rt_frame_pick(frame_, x, y, ray, hit, surface));

@@ -121,6 +121,10 @@ public:
     // on it and how far, optionally with the rt_surface there; a count of 2^32 or more is refused.  Throws HIPException with the library's message on a
     // refusal; requests no reset and does not touch the frame.
     void NearestPoints(rt_point const* points, std::size_t count, rt_nearest* out, rt_surface* surfaces);
+    // Within (rt_scene_within): every triangle of the scene as it is posed now within max_distance of each point -- the counts in out, the
+    // nearest max_near members in near and surfaces (max_near records per point; either may be null); options: RT_WITHIN_K_NEAREST.  Throws HIPException with
+    // the library's message on a refusal; requests no reset and does not touch the frame.
+    void PointsWithin(rt_point const* points, std::size_t count, std::uint32_t max_near, std::uint32_t options, rt_point_hits* out, rt_nearest* near, rt_surface* surfaces);
     // All hits (rt_scene_trace_all / rt_frame_pick_all): every surface each ray crosses -- the counts in out, the nearest max_hits crossings
     // in hits and surfaces (max_hits records per ray; either may be null).  PickAll: the ray through the centre of pixel (x, y) of the frame's current camera;
     // PickAllThrough: the same for a camera the frame has not been given, as PickThrough.  All throw HIPException with the library's message on a refusal; none

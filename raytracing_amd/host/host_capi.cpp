@@ -286,6 +286,10 @@ int rth_render_nearest(void* r, const rt_point* points, uint32_t n, rt_nearest* 
 {
     return guard([&]() { ((rt::Render*)r)->Nearest(points, n, out, surfaces); return 0; }, 1);
 }
+int rth_render_within(void* r, const rt_point* points, uint32_t n, uint32_t max_near, uint32_t options, rt_point_hits* out, rt_nearest* near, rt_surface* surfaces)
+{
+    return guard([&]() { ((rt::Render*)r)->Within(points, n, max_near, options, out, near, surfaces); return 0; }, 1);
+}
 int rth_render_upload_gpu_data(void* r) { return guard([&]() { ((rt::Render*)r)->UploadGPUData(); return 0; }, 1); }
 
 } // extern "C"

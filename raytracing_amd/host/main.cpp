@@ -43,6 +43,8 @@ int main(int argc, char** argv)
         bool nearest_signed = false;            // --signed 1: --nearest also prints whether the point is inside (exits outnumber entries along (0.36, 0.48, 0.8))
         std::string ao_out;                     // --ao out.pfm: after the scene is uploaded and posed, write the ambient occlusion image of the camera (grey, RGB equal)
         rt_bake_desc ao = {64u, 0u, 0u, 1e-3f, 1.0f};   // --ao_samples n --ao_radius r --ao_bias b
+        struct WithinAt { rt_point point; std::uint32_t k; };
+        std::vector<WithinAt> within_points;    // --within x,y,z,r[,k] (repeatable): after the scene is uploaded and posed, print the triangles within r (the k nearest only)
         std::vector<rt_point> nearest_points;   // --nearest x,y,z[,r] (repeatable): after the scene is uploaded and posed, print the nearest surface point (within r)
         bool list_objects = false;              // --list_objects 1: print the OBJ's o / g shapes (index and name) and exit; needs no GPU
         for (int i = 1; i < argc; ++i)
@@ -146,6 +148,19 @@ int main(int argc, char** argv)
                 nearest_points.push_back(q);
                 scene_options |= rt::Scene::kObjects;
             }
+            else if (!strcmp(argv[i], "--within"))
+            {
+                WithinAt q;
+                q.k = 0u;
+                const int got = sscanf(next(), "%f,%f,%f,%f,%u", &q.point.position[0], &q.point.position[1], &q.point.position[2], &q.point.max_distance, &q.k);
+                if (got < 4 || (got == 5 && (q.k < 1u || q.k > RT_WITHIN_MAX)))
+                {
+                    std::cerr << "--within wants x,y,z,r or x,y,z,r,k (a point, a radius and optionally how many of the nearest to look for, 1 .. 8)\n";
+                    return 2;
+                }
+                within_points.push_back(q);
+                scene_options |= rt::Scene::kObjects;
+            }
             else if (!strcmp(argv[i], "--ao")) ao_out = next();
             else if (!strcmp(argv[i], "--ao_samples")) ao.samples = (unsigned)atoi(next());
             else if (!strcmp(argv[i], "--ao_radius")) ao.radius = (float)atof(next());
@@ -179,6 +194,8 @@ int main(int argc, char** argv)
                              "  (default 1), 1 where the pixel sees nothing; traced and baked on the device (rt_scene_bake_buffer); one GPU only\n"
                              "  --pick_all x,y (repeatable) prints every surface under that pixel, nearest first, one line per surface; --signed 1 makes --nearest print whether\n"
                              "    the point is inside (more exits than entries along (0.36, 0.48, 0.8))\n"
+                             "  --within x,y,z,r[,k] (repeatable) prints the triangles within r of that point once the scene is uploaded and posed: their count, and one line\n"
+                             "  for each of the nearest 8 (with k: the k nearest only, and nothing beyond them is looked for)\n"
                              "  --nearest x,y,z[,r] (repeatable) prints the nearest surface point to that point (within r) once the scene is uploaded and posed: primitive,\n"
                              "  distance, position, feature (face, edge or vertex), material and object (index and name); one GPU only\n";
                 return 0;
@@ -230,6 +247,11 @@ int main(int argc, char** argv)
         if (!nearest_points.empty() && (gpus > 1 || tiled_path))
         {
             std::cerr << "--nearest needs one GPU\n";
+            return 2;
+        }
+        if (!within_points.empty() && (gpus > 1 || tiled_path))
+        {
+            std::cerr << "--within needs one GPU\n";
             return 2;
         }
         if (!ao_out.empty() && (gpus > 1 || tiled_path))
@@ -388,6 +410,34 @@ int main(int argc, char** argv)
                 std::cout << std::endl;
             }
         };
+        // --within: one line per point and one per listed member (rt_scene_within through Render::Within); the object as --pick names it
+        auto print_within = [&]()
+        {
+            for (const WithinAt& w : within_points)
+            {
+                const std::uint32_t k = w.k ? w.k : (std::uint32_t)RT_WITHIN_MAX;
+                rt_point_hits rec;
+                rt_nearest near[RT_WITHIN_MAX];
+                rt_surface surf[RT_WITHIN_MAX];
+                render.Within(&w.point, 1, k, w.k ? RT_WITHIN_K_NEAREST : 0u, &rec, near, surf);
+                const rt_point& q = w.point;
+                std::cout << "within " << q.position[0] << "," << q.position[1] << "," << q.position[2] << " radius " << q.max_distance << ": ";
+                if (rec.count == 0u) { std::cout << "none" << std::endl; continue; }
+                std::cout << "count " << rec.count << " listed " << rec.stored << " nearest primitive " << rec.nearest_primitive << (w.k ? " (k nearest)" : "") << std::endl;
+                for (std::uint32_t j = 0; j < rec.stored; ++j)
+                {
+                    const rt_nearest& f = near[j];
+                    std::uint32_t object = surf[j].object;
+                    if (object == RT_INVALID_ID && f.primitive_id < scene.GetTriangleObjects().size()) object = scene.GetTriangleObjects()[f.primitive_id];
+                    static const char* const feature[4] = {"face", "edge", "vertex", "?"};
+                    std::cout << "within   " << j << ": primitive " << f.primitive_id << " distance " << f.distance << " position " << f.position[0] << " " << f.position[1] << " "
+                              << f.position[2] << " feature " << feature[(f.flags >> RT_NEAREST_FEATURE_SHIFT) & 3u] << " material " << surf[j].mtl_index << " object ";
+                    if (object < scene.GetObjectNames().size()) std::cout << object << " " << scene.GetObjectNames()[object];
+                    else std::cout << "none";
+                    std::cout << ((f.flags & RT_NEAREST_BACK_SIDE) ? " (back side)" : "") << std::endl;
+                }
+            }
+        };
         // --ao: Render::OcclusionImage of the camera as it stands, written as a grey PFM
         auto write_ao = [&]()
         {
@@ -444,6 +494,7 @@ int main(int argc, char** argv)
             print_picks();
             print_picks_all();
             print_nearest();
+            print_within();
             write_ao();
             return 0;
         }
@@ -485,6 +536,7 @@ int main(int argc, char** argv)
         print_picks();
         print_picks_all();
         print_nearest();
+        print_within();
         write_ao();
         if (!out.empty() && (filter_iterations >= 0 || temporal_iterations >= 0))
             WritePFM(out.c_str(), render.GetIntegrator().ResolveNow(), width, height);     // the filtered, tone-mapped image

@@ -52,6 +52,8 @@ public:
     void OcclusionImage(rt_bake_desc const& desc, float* out) { integrator_->OcclusionImageThrough(camera_, desc, out); }
     // the nearest surface point to each of the caller's points; the frame is not touched
     void Nearest(rt_point const* points, std::size_t count, rt_nearest* out, rt_surface* surfaces) { integrator_->NearestPoints(points, count, out, surfaces); }
+    // every triangle within max_distance of each of the caller's points, counted and the nearest max_near listed; the frame is not touched
+    void Within(rt_point const* points, std::size_t count, std::uint32_t max_near, std::uint32_t options, rt_point_hits* out, rt_nearest* near, rt_surface* surfaces) { integrator_->PointsWithin(points, count, max_near, options, out, near, surfaces); }
     // every surface a ray crosses, counted and the nearest max_hits sorted; PickAll: through the centre of a pixel of the Render's current camera
     void TraceAllHits(rt_ray const* rays, std::size_t count, std::uint32_t max_hits, rt_ray_hits* out, rt_hit* hits, rt_surface* surfaces) { integrator_->TraceAllHits(rays, count, max_hits, out, hits, surfaces); }
     void PickAll(std::uint32_t x, std::uint32_t y, std::uint32_t max_hits, rt_ray* ray, rt_ray_hits* out, rt_hit* hits, rt_surface* surfaces) { integrator_->PickAllThrough(camera_, x, y, max_hits, ray, out, hits, surfaces); }

@@ -29,6 +29,8 @@ point = np.dtype([("position", "<f4", (3,)), ("max_distance", "<f4")])
 nearest = np.dtype([("position", "<f4", (3,)), ("distance", "<f4"), ("bc", "<f4", (2,)), ("primitive_id", "<u4"), ("flags", "<u4")])
 # rt_ray_hits (include/rt_hip.h): what an all-hits query reports of a ray: the crossings, how many of them enter, how many are listed; flags bit 0 = walked, bit 8 + j = listed hit j is an exit
 ray_hits = np.dtype([("count", "<u4"), ("entering", "<u4"), ("stored", "<u4"), ("flags", "<u4")])
+# rt_point_hits (include/rt_hip.h): what a within query reports of a point: the triangles within its radius, how many of them are listed, the nearest one; flags bit 0 = searched, bit 1 = a k-nearest answer
+point_hits = np.dtype([("count", "<u4"), ("stored", "<u4"), ("nearest_primitive", "<u4"), ("flags", "<u4")])
 camera = np.dtype([("position", float3), ("front", float3), ("up", float3), ("fov", "<f4"),
                    ("aspect_ratio", "<f4"), ("aperture", "<f4"), ("focus_distance", "<f4")])
 
@@ -36,7 +38,7 @@ assert ray.itemsize == 32 and hit.itemsize == 16 and scene_info.itemsize == 16
 assert packed_material.itemsize == 20 and light.itemsize == 48 and texture.itemsize == 16
 assert vertex.itemsize == 48 and triangle.itemsize == 160 and bvh_node.itemsize == 48
 assert camera.itemsize == 64 and surface.itemsize == 64 and bake_result.itemsize == 16
-assert point.itemsize == 16 and nearest.itemsize == 32 and ray_hits.itemsize == 16
+assert point.itemsize == 16 and nearest.itemsize == 32 and ray_hits.itemsize == 16 and point_hits.itemsize == 16
 
 
 def default_camera(width, height):

@@ -3,12 +3,13 @@
 import csv, glob, os, shutil, subprocess, sys, tempfile
 
 
-def child_rows(script, child_args, keep, cwd, prefix):
-    """(header, rows) of rocprofv3's kernel statistics of `python script child_args...`: the rows whose kernel name keep(name) accepts"""
+def child_rows(script, child_args, keep, cwd, prefix, timeout=None):
+    """(header, rows) of rocprofv3's kernel statistics of `python script child_args...`: the rows whose kernel name keep(name) accepts.  timeout: seconds the
+    child may take (subprocess.TimeoutExpired ends the whole tool: nothing more is started after a child that hung)"""
     tmp = tempfile.mkdtemp(prefix=prefix)
     try:
         subprocess.check_call(["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", tmp, "--", sys.executable, os.path.abspath(script)]
-                              + [str(x) for x in child_args], cwd=cwd)
+                              + [str(x) for x in child_args], cwd=cwd, timeout=timeout)
         found = sorted(glob.glob(os.path.join(tmp, "**", "*kernel_stats.csv"), recursive=True))
         if not found:
             raise SystemExit("rocprofv3 wrote no kernel statistics under " + tmp)
