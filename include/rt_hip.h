@@ -424,6 +424,75 @@ int rt_debug_within_walk(const rt_bvh_node* nodes, uint32_t num_nodes, const rt_
                          const rt_point* points, uint32_t n, uint32_t max_near, uint32_t options, rt_point_hits* out, rt_nearest* near,
                          uint32_t* triangles_tested_or_null);
 
+/* ---- overlap: every triangle a CALLER's convex region -- a box, a slab, a frustum, up to 8 half-spaces -- touches or encloses (opt-in extension; DESIGN.md
+ * section 7m).  What lies inside a box, which cells of a grid the surface touches, which objects a trigger volume contains, what is under a dragged
+ * rectangle on screen.  raytracing_amd/csrc/region.h states the rule.
+ *   a region: plane k = (nx, ny, nz, d), s_k(x) = ((nx x0 + ny x1) + nz x2) + d in binary32, each product and sum rounded once; x is outside plane k exactly
+ *     when s_k(x) > 0 (on the plane is inside; a NaN s is not outside).  Normals need not have unit length.  SEARCHED: 1 <= num_planes <= 8 and every one of
+ *     the 4 * num_planes coefficients finite; `reserved` is ignored.
+ *   a triangle, on its shading record's three corners: REJECTED when some plane has all three outside, INSIDE when no plane has any outside, CROSSING
+ *     otherwise; TOUCHING = inside or crossing.  This is the usual conservative cull: a crossing triangle near an edge or a corner of the region need not
+ *     intersect it; a triangle that does intersect it is never rejected.  Inside is exact for the rounded s.
+ *   rt_region_hits: count = the touching triangles, inside = the inside ones, stored = min(count, max_list), flags bit 0 = searched.
+ *   members (optional, max_list <= RT_REGION_LIST_MAX per region): the touching triangles with the LOWEST primitive ids, ascending -- an order no tree
+ *     enters; a smaller max_list gives a prefix.  flags bit 0: inside; bit 8 + k: plane k has 1 or 2 corners outside.  Beyond `stored`: RT_INVALID_ID / 0.
+ *   a region that is not searched gives zeros and invalid entries.
+ *   The sets are a statement about triangles and region.h alone -- bit for bit rt_debug_overlap's brute force, whichever records are walked, after any
+ *     refit or pose: a box is skipped only when one plane has the box's nearest corner outside, and then, in binary32 itself, every corner inside the box
+ *     is outside that plane (region.h has the argument).
+ * Runs on the context's stream like a within query, touches no frame and no rt_stats field, and uses the ray queries' spill area, status word and staging
+ * arrays.
+ *   rt_scene_overlap: host arrays, staged in chunks of at most 4 Mi member records; returns when the outputs are written.
+ *   rt_scene_overlap_buffer: rt_buffers of this context (n rt_region, n rt_region_hits, n * max_list rt_region_member); only enqueues.
+ * Refused with nothing launched: a NULL context, no scene, NULL regions with n > 0, out NULL, max_list > RT_REGION_LIST_MAX, members with max_list == 0, a
+ * buffer of another context or too small.  n == 0 is RT_OK and does nothing. */
+#define RT_REGION_MAX_PLANES 8
+#define RT_REGION_LIST_MAX 8
+#define RT_REGION_HITS_SEARCHED 1u          /* rt_region_hits.flags bit 0 */
+#define RT_REGION_MEMBER_INSIDE 1u          /* rt_region_member.flags bit 0 */
+#define RT_REGION_MEMBER_CROSSING_SHIFT 8   /* rt_region_member.flags bit 8 + k: plane k has 1 or 2 of the corners outside */
+#define RT_SELECT_MAX_REGIONS 32
+typedef struct rt_region { uint32_t num_planes; uint32_t reserved[3]; float planes[RT_REGION_MAX_PLANES][4]; } rt_region;      /* 144 bytes; plane k = (nx, ny, nz, d) */
+typedef struct rt_region_hits { uint32_t count; uint32_t inside; uint32_t stored; uint32_t flags; } rt_region_hits;            /* 16 bytes */
+typedef struct rt_region_member { uint32_t primitive_id; uint32_t flags; } rt_region_member;                                   /* 8 bytes */
+int rt_scene_overlap(rt_ctx* ctx, const rt_region* regions, uint32_t n, uint32_t max_list, rt_region_hits* out, rt_region_member* members_or_null);
+int rt_scene_overlap_buffer(rt_ctx* ctx, rt_buffer* regions, uint32_t n, uint32_t max_list, rt_buffer* out, rt_buffer* members_or_null);
+/* brute force over all of `triangles` (primitive_id = the index): region.h on the host (ctx == NULL) or k_region_brute on uploaded copies.  The two agree
+ * bit for bit.  members may be NULL when max_list == 0.  Refused: a NULL argument, max_list > RT_REGION_LIST_MAX. */
+int rt_debug_overlap(rt_ctx* ctx_or_null, const rt_triangle* triangles, uint32_t num_triangles, const rt_region* regions, uint32_t n, uint32_t max_list,
+                     rt_region_hits* out, rt_region_member* members);
+/* the kernel's walk on the host (no device), over the child-pair form of `nodes` (wide = 0) or build_wide_bvh's 4-wide records of them (wide = 1), pruned by
+ * region.h's box test; triangles_tested_or_null[i] = how many triangles region i was tested against.  Refused where rt_debug_within_walk is. */
+int rt_debug_overlap_walk(const rt_bvh_node* nodes, uint32_t num_nodes, const rt_triangle* triangles, uint32_t num_triangles, int wide,
+                          const rt_region* regions, uint32_t n, uint32_t max_list, rt_region_hits* out, rt_region_member* members,
+                          uint32_t* triangles_tested_or_null);
+/* The COMPLETE answer for a few regions (n <= RT_SELECT_MAX_REGIONS): one lane per triangle instead of one per region, no tree.  Bit r of touching[t] /
+ * inside[t] (num_triangles words, BVH order) says triangle t touches / is inside region r; bit r of object_touching[o] is the OR of the object's triangles'
+ * touching bits (the CAD "crossing" selection), bit r of object_inside[o] is set when the object has at least one triangle and every one of them is inside
+ * (the "window" selection) -- made with atomic ORs and a finishing step, so they depend on no order.  The per-object words need rt_scene_set_objects and
+ * hold its num_objects entries.  A region that is not searched sets no bit.  At least one output.
+ *   rt_scene_select: host arrays; returns when the outputs are written.     rt_scene_select_buffer: rt_buffers of this context; only enqueues (the context
+ *   keeps 4 bytes per object of scratch for the finishing step).
+ * Refused with nothing launched: a NULL context, no scene, NULL regions, n == 0 or n > RT_SELECT_MAX_REGIONS, every output NULL, per-object outputs without
+ * rt_scene_set_objects, a buffer of another context or too small. */
+int rt_scene_select(rt_ctx* ctx, const rt_region* regions, uint32_t n, uint32_t* touching_or_null, uint32_t* inside_or_null, uint32_t* object_touching_or_null,
+                    uint32_t* object_inside_or_null);
+int rt_scene_select_buffer(rt_ctx* ctx, rt_buffer* regions, uint32_t n, rt_buffer* touching_or_null, rt_buffer* inside_or_null, rt_buffer* object_touching_or_null,
+                           rt_buffer* object_inside_or_null);
+/* the same over caller triangles: region.h on the host (ctx == NULL) or k_select on uploaded copies; the two agree bit for bit.  touching and inside are
+ * required; the per-object outputs are written when object_of_triangle is given (every entry < num_objects). */
+int rt_debug_select(rt_ctx* ctx_or_null, const rt_triangle* triangles, uint32_t num_triangles, const uint32_t* object_of_triangle_or_null, uint32_t num_objects,
+                    const rt_region* regions, uint32_t n, uint32_t* touching, uint32_t* inside, uint32_t* object_touching, uint32_t* object_inside);
+/* The marquee: the region of the INCLUSIVE pixel rectangle (x0, y0) .. (x1, y1) of the frame's current camera -- four side planes through the camera position
+ * and the guide pass's directions at the rectangle's pixel corners, a near plane when t_near > 0, a far plane when t_far is finite (region.h fixes every
+ * operand) -- then one rt_scene_select with that region: bit 0 of each word.  Any output may be NULL.  Refused: what rt_frame_pick refuses, x1 < x0,
+ * y1 < y0, a rectangle outside the image, per-object outputs without rt_scene_set_objects. */
+int rt_frame_pick_rect(rt_frame* frame, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, float t_near, float t_far, rt_region* region_or_null,
+                       uint32_t* touching_or_null, uint32_t* inside_or_null, uint32_t* object_touching_or_null, uint32_t* object_inside_or_null);
+/* the rectangle's region on its own (host arithmetic only).  Refused: a NULL argument, an empty image, x1 < x0, y1 < y0, a rectangle outside the image. */
+int rt_debug_rect_region(const rt_camera* camera, uint32_t width, uint32_t height, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, float t_near, float t_far,
+                         rt_region* out);
+
 /* One fold adaptation per process GROUP instead of one per rank (N ranks that tile one image hold the same scene and would each probe, rotate and fold for
  * identical records): the context's current 4-wide records -- the closest-hit rays' and the shadow rays' (n_shadow == 0: they share), as adapted so far -- to
  * host buffers of `capacity` records each (records NULL: size query; entries2 = {closest entry, shadow entry}), and into another context that has uploaded

@@ -54,6 +54,7 @@ HIP_UNITS = [
     ("bake", "bake.hip", True),                # ambient occlusion and bent normals at caller-supplied points: kernels on walk_kernels.h + host driver on query.hip's core + the host restatement (a code object of its own)
     ("nearest", "nearest.hip", True),          # the nearest surface point to caller-supplied points: kernels on walk_kernels.h's stack + host driver on query.hip's core + the host's brute force and walk (a code object of its own)
     ("within", "within.hip", True),            # every triangle within a radius of caller-supplied points, counted and sorted: kernels on walk_kernels.h's stack and point_box_step + host driver on query.hip's core + the host's brute force and walk (a code object of its own)
+    ("region", "region.hip", True),            # every triangle a caller-supplied convex region (up to 8 half-spaces) touches or encloses, counted and listed, and the per-triangle select of a few regions: kernels on walk_kernels.h's stack and region_box_step + host driver on query.hip's core + the host's brute force and walk (a code object of its own)
     ("all_hits", "all_hits.hip", True),        # every surface a caller-supplied ray crosses, counted and sorted: kernels on walk_kernels.h + host driver on query.hip's core + the host's brute force (a code object of its own)
     ("wide_bvh", "wide_bvh.cpp", False),       # build_wide_bvh, pair layout, the adaptation's host walks (no device code)
 ]

@@ -116,6 +116,8 @@ EXPORTS = [
     "rt_scene_nearest", "rt_scene_nearest_buffer", "rt_debug_nearest", "rt_debug_nearest_walk",
     "rt_scene_trace_all", "rt_scene_trace_all_buffer", "rt_frame_pick_all", "rt_debug_trace_all",
     "rt_scene_within", "rt_scene_within_buffer", "rt_debug_within", "rt_debug_within_walk",
+    "rt_scene_overlap", "rt_scene_overlap_buffer", "rt_debug_overlap", "rt_debug_overlap_walk",
+    "rt_scene_select", "rt_scene_select_buffer", "rt_debug_select", "rt_frame_pick_rect", "rt_debug_rect_region",
 ]
 
 OPT_MAX_BOUNCES, OPT_WHITE_FURNACE, OPT_SAMPLER, OPT_AOV, OPT_DENOISER, OPT_DROP_LAST, OPT_PROFILE, OPT_TRACE_VARIANT, OPT_TRACE_WAVES, OPT_SAMPLES_IN_FLIGHT, OPT_SELECT_FORM_BOX, OPT_PACKET_BOUNCES, OPT_TRACE_TUNE, OPT_DEBUG_ALLOC_LIMIT, OPT_PATH_STATE_LIMIT_MB, OPT_PIPELINES, OPT_SHADE_PARTITION, OPT_OVERLAP_SHADOW, OPT_SMALL_LAUNCH_PATHS, OPT_COMPACT_LOG, OPT_DEBUG_LOG_POOL_DIV, OPT_TRACE_TAIL_LANES, OPT_TRACE_TAIL_PATHS, OPT_CHUNK_REFILL, OPT_STAGE_PIPES, OPT_FRAME_KERNEL, OPT_SAMPLES_AHEAD = range(27)
@@ -216,6 +218,13 @@ def load():
         "rt_scene_within": (i32, [vp, vp, u32, u32, u32, vp, vp, vp]), "rt_scene_within_buffer": (i32, [vp, vp, u32, u32, u32, vp, vp, vp]),
         "rt_debug_within": (i32, [vp, vp, u32, vp, u32, u32, u32, vp, vp]),
         "rt_debug_within_walk": (i32, [vp, u32, vp, u32, i32, vp, u32, u32, u32, vp, vp, vp]),
+        "rt_scene_overlap": (i32, [vp, vp, u32, u32, vp, vp]), "rt_scene_overlap_buffer": (i32, [vp, vp, u32, u32, vp, vp]),
+        "rt_debug_overlap": (i32, [vp, vp, u32, vp, u32, u32, vp, vp]),
+        "rt_debug_overlap_walk": (i32, [vp, u32, vp, u32, i32, vp, u32, u32, vp, vp, vp]),
+        "rt_scene_select": (i32, [vp, vp, u32, vp, vp, vp, vp]), "rt_scene_select_buffer": (i32, [vp, vp, u32, vp, vp, vp, vp]),
+        "rt_debug_select": (i32, [vp, vp, u32, vp, u32, vp, u32, vp, vp, vp, vp]),
+        "rt_frame_pick_rect": (i32, [vp, u32, u32, u32, u32, C.c_float, C.c_float, vp, vp, vp, vp, vp]),
+        "rt_debug_rect_region": (i32, [vp, u32, u32, u32, u32, u32, u32, C.c_float, C.c_float, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -565,6 +574,84 @@ def debug_within_walk(nodes, triangles, points, max_near=WITHIN_MAX, k_nearest=F
     return (out, near, tested) if counts else (out, near)
 
 
+REGION_MAX_PLANES = 8       # RT_REGION_MAX_PLANES
+REGION_LIST_MAX = 8         # RT_REGION_LIST_MAX
+REGION_HITS_SEARCHED = 1    # rt_region_hits.flags bit 0
+REGION_MEMBER_INSIDE = 1    # rt_region_member.flags bit 0
+REGION_MEMBER_CROSSING_SHIFT = 8   # rt_region_member.flags bit 8 + k: plane k has 1 or 2 corners outside
+SELECT_MAX_REGIONS = 32     # RT_SELECT_MAX_REGIONS
+
+
+def region_records(regions):
+    """types.region[n], contiguous: an array of them, one scalar, or a list of scalars (types.box_region, types.oriented_box_region, types.planes_region)"""
+    if isinstance(regions, np.ndarray) and regions.dtype == T.region:
+        return np.ascontiguousarray(regions.reshape(-1))
+    return np.ascontiguousarray(np.array(list(regions), T.region).reshape(-1))
+
+
+def debug_overlap(ctx, triangles, regions, max_list=REGION_LIST_MAX):
+    """rt_debug_overlap: (types.region_hits[n], types.region_member[n, max_list]) of `regions` by brute force over all `triangles` (types.triangle).
+    ctx None = the host (csrc/region.h), else k_region_brute on ctx's GPU."""
+    lib = load()
+    tris = np.ascontiguousarray(triangles, T.triangle)
+    rg = region_records(regions)
+    out = np.zeros(len(rg), T.region_hits)
+    members = np.zeros((len(rg), max_list), T.region_member)
+    handle = ctx.handle if ctx is not None else None
+    rc = lib.rt_debug_overlap(handle, tris.ctypes.data if len(tris) else None, len(tris), rg.ctypes.data if len(rg) else None, len(rg), max_list,
+                              out.ctypes.data if len(rg) else None, members.ctypes.data if members.size else None)
+    if rc != 0:
+        raise RtError(lib.rt_last_error(handle).decode())
+    return out, members
+
+
+def debug_overlap_walk(nodes, triangles, regions, max_list=REGION_LIST_MAX, wide=True, counts=False):
+    """rt_debug_overlap_walk (host only): k_region's walk over the child-pair form of `nodes` (types.bvh_node; wide=False) or over build_wide_bvh's 4-wide
+    records of them (wide=True): (types.region_hits[n], types.region_member[n, max_list]), with uint32[n] triangles tested per region appended when counts=True"""
+    lib = load()
+    nd = np.ascontiguousarray(nodes, T.bvh_node)
+    tris = np.ascontiguousarray(triangles, T.triangle)
+    rg = region_records(regions)
+    out = np.zeros(len(rg), T.region_hits)
+    members = np.zeros((len(rg), max_list), T.region_member)
+    tested = np.zeros(len(rg), np.uint32)
+    rc = lib.rt_debug_overlap_walk(nd.ctypes.data if len(nd) else None, len(nd), tris.ctypes.data if len(tris) else None, len(tris), int(wide),
+                                   rg.ctypes.data if len(rg) else None, len(rg), max_list, out.ctypes.data if len(rg) else None,
+                                   members.ctypes.data if members.size else None, tested.ctypes.data if len(rg) else None)
+    if rc != 0:
+        raise RtError(lib.rt_last_error(None).decode())
+    return (out, members, tested) if counts else (out, members)
+
+
+def debug_select(ctx, triangles, regions, object_of_triangle=None, num_objects=0):
+    """rt_debug_select: (touching uint32[nt], inside uint32[nt]) -- bit r: the triangle touches / is inside regions[r], at most 32 regions -- of all
+    `triangles`; with object_of_triangle also (object_touching uint32[num_objects], object_inside uint32[num_objects]).  ctx None = the host
+    (csrc/region.h), else k_select on ctx's GPU."""
+    lib = load()
+    tris = np.ascontiguousarray(triangles, T.triangle)
+    rg = region_records(regions)
+    touching, inside = np.zeros(len(tris), np.uint32), np.zeros(len(tris), np.uint32)
+    ids = np.ascontiguousarray(object_of_triangle, np.uint32) if object_of_triangle is not None else None
+    ot, oi = np.zeros(num_objects, np.uint32), np.zeros(num_objects, np.uint32)
+    handle = ctx.handle if ctx is not None else None
+    p = lambda a: a.ctypes.data if a is not None and a.size else None
+    rc = lib.rt_debug_select(handle, p(tris), len(tris), p(ids), num_objects, p(rg), len(rg), p(touching), p(inside), p(ot) if ids is not None else None,
+                             p(oi) if ids is not None else None)
+    if rc != 0:
+        raise RtError(lib.rt_last_error(handle).decode())
+    return (touching, inside, ot, oi) if ids is not None else (touching, inside)
+
+
+def debug_rect_region(camera, width, height, x0, y0, x1, y1, t_near=0.0, t_far=float("inf")):
+    """rt_debug_rect_region (host only): the types.region scalar of the inclusive pixel rectangle (x0, y0) .. (x1, y1) of `camera` (types.camera)"""
+    lib = load()
+    cam = np.ascontiguousarray(camera, T.camera).reshape(1)
+    out = np.zeros(1, T.region)
+    if lib.rt_debug_rect_region(cam.ctypes.data, width, height, x0, y0, x1, y1, t_near, t_far, out.ctypes.data) != 0:
+        raise RtError(lib.rt_last_error(None).decode())
+    return out[0]
+
+
 def choose_tree(scene, shadow=True, mode=1):
     """rt_debug_choose_tree (host only, no GPU): the 4-wide tree rt_scene_upload would give this scene's shadow / closest-hit
     rays under RT_CTX_OPT_SHADOW_TREE / RT_CTX_OPT_CLOSEST_TREE = mode.  scene: dict with triangles, nodes, lights.
@@ -733,6 +820,7 @@ class Context:
         self.lib = load()
         h = C.c_void_p()
         _check(self.lib, None, self.lib.rt_ctx_create(device, C.byref(h)))
+        self.num_triangles = 0
         self.handle = h
         self._frames = []          # weakrefs: frames (and buffers) must be destroyed before their context
 
@@ -899,6 +987,43 @@ class Context:
         h = lambda b: b.handle if b is not None else None
         _check(self.lib, self.handle, self.lib.rt_scene_within_buffer(self.handle, h(points), n, max_near, WITHIN_K_NEAREST if k_nearest else 0, h(out), h(near), h(surfaces)))
 
+    def overlap(self, regions, max_list=REGION_LIST_MAX):
+        """rt_scene_overlap: every triangle of the uploaded scene that each of the caller's regions (region_records' rule) touches or encloses:
+        (types.region_hits[n], types.region_member[n, max_list]) -- the counts, and the touching triangles with the lowest primitive ids, ascending.
+        max_list=0: the records alone."""
+        rg = region_records(regions)
+        n = len(rg)
+        out = np.zeros(n, T.region_hits)
+        if max_list == 0:
+            _check(self.lib, self.handle, self.lib.rt_scene_overlap(self.handle, rg.ctypes.data if n else None, n, 0, out.ctypes.data, None))
+            return out
+        members = np.zeros((n, max_list), T.region_member)
+        _check(self.lib, self.handle, self.lib.rt_scene_overlap(self.handle, rg.ctypes.data if n else None, n, max_list, out.ctypes.data, members.ctypes.data))
+        return out, members
+
+    def overlap_buffer(self, regions, n, max_list, out, members=None):
+        """rt_scene_overlap_buffer: the same over Buffers of this context (n regions and records, n * max_list members; None: not wanted).  Only
+        enqueues: Buffer.read() or finish() waits."""
+        h = lambda b: b.handle if b is not None else None
+        _check(self.lib, self.handle, self.lib.rt_scene_overlap_buffer(self.handle, h(regions), n, max_list, h(out), h(members)))
+
+    def select(self, regions, objects=0):
+        """rt_scene_select: at most 32 regions against every triangle: (touching uint32[num_triangles], inside uint32[num_triangles]), bit r for
+        regions[r]; objects = set_objects' num_objects: also (object_touching uint32[objects], object_inside uint32[objects])"""
+        rg = region_records(regions)
+        if self.num_triangles == 0:
+            raise RtError("select: no scene uploaded through upload_scene() (the per-triangle words are sized by its triangle count)")
+        touching, inside = np.zeros(self.num_triangles, np.uint32), np.zeros(self.num_triangles, np.uint32)
+        ot, oi = np.zeros(objects, np.uint32), np.zeros(objects, np.uint32)
+        _check(self.lib, self.handle, self.lib.rt_scene_select(self.handle, rg.ctypes.data if len(rg) else None, len(rg), touching.ctypes.data, inside.ctypes.data,
+                                                                 ot.ctypes.data if objects else None, oi.ctypes.data if objects else None))
+        return (touching, inside, ot, oi) if objects else (touching, inside)
+
+    def select_buffer(self, regions, n, touching=None, inside=None, object_touching=None, object_inside=None):
+        """rt_scene_select_buffer: the same over Buffers of this context (None: not wanted).  Only enqueues."""
+        h = lambda b: b.handle if b is not None else None
+        _check(self.lib, self.handle, self.lib.rt_scene_select_buffer(self.handle, h(regions), n, h(touching), h(inside), h(object_touching), h(object_inside)))
+
     def bake(self, points, samples, seed=0, bias=BAKE_BIAS_DEFAULT, radius=BAKE_RADIUS_DEFAULT, from_surfaces=False):
         """rt_scene_bake: ambient occlusion and bent normals at the caller's points (bake_points' rule): types.bake_result[n] -- unoccluded / samples is the
         ambient occlusion term, 0xFFFFFFFF marks a skipped point"""
@@ -952,6 +1077,7 @@ class Context:
             d.material_texture_indices = tex16.ctypes.data
         d.flags = int(scene.get("flags", 0))
         _check(self.lib, self.handle, self.lib.rt_scene_upload(self.handle, C.byref(d)))
+        self.num_triangles = len(s["triangles"])          # what select() and Frame.pick_rect() size their per-triangle words by
 
     def debug_eval(self, fn, a, b=None):
         a = np.ascontiguousarray(a, np.float32)
@@ -1106,6 +1232,19 @@ class Frame:
         self._c(self.lib.rt_frame_pick_all(self.handle, x, y, max_hits, ray.ctypes.data, rec.ctypes.data, hits.ctypes.data if max_hits else None,
                                            surf.ctypes.data if max_hits else None))
         return ray[0], rec[0], hits, surf
+
+    def pick_rect(self, x0, y0, x1, y1, t_near=0.0, t_far=float("inf"), num_triangles=None, objects=0):
+        """rt_frame_pick_rect: (region, touching uint32[num_triangles], inside uint32[num_triangles]) of the inclusive pixel rectangle of the frame's
+        current camera -- bit 0 of each word --, with (object_touching, object_inside) appended when objects = set_objects' num_objects"""
+        nt = self.ctx.num_triangles if num_triangles is None else num_triangles
+        if nt == 0:
+            raise RtError("pick_rect: no scene uploaded through upload_scene() (pass num_triangles: the per-triangle words are sized by it)")
+        g = np.zeros(1, T.region)
+        touching, inside = np.zeros(nt, np.uint32), np.zeros(nt, np.uint32)
+        ot, oi = np.zeros(objects, np.uint32), np.zeros(objects, np.uint32)
+        self._c(self.lib.rt_frame_pick_rect(self.handle, x0, y0, x1, y1, t_near, t_far, g.ctypes.data, touching.ctypes.data, inside.ctypes.data,
+                                            ot.ctypes.data if objects else None, oi.ctypes.data if objects else None))
+        return (g[0], touching, inside, ot, oi) if objects else (g[0], touching, inside)
 
     def guide_motion(self):
         """rt_frame_read_guide_motion: (previous position float32[h, w, 4] = (X', 1), previous normal float32[h, w, 4] = (n', 0)) of every pixel's first

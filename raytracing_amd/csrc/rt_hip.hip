@@ -33,6 +33,7 @@
 #include "nearest_host.h"    // the nearest surface point to caller-supplied points (nearest.hip)
 #include "all_hits_host.h"   // every surface a caller-supplied ray crosses (all_hits.hip)
 #include "within_host.h"     // every triangle within a radius of caller-supplied points (within.hip)
+#include "region_host.h"     // every triangle a caller-supplied convex region touches or encloses (region.hip)
 #include "device_memory.h"   // who owns a device allocation: dev::Mem, dev::Temps
 using namespace rtw;
 
@@ -1083,6 +1084,7 @@ extern "C" {
 #include "nearest_impl.h"
 #include "all_hits_impl.h"
 #include "within_impl.h"
+#include "region_impl.h"
 
 // ---- scene -----------------------------------------------------------------
 int rt_scene_upload(rt_ctx* ctx, const rt_scene_desc* sd)

@@ -1,10 +1,11 @@
 // walk_kernels.h -- what the kernels of the caller-facing queries share (DESIGN.md sections 7h - 7l): k_query_trace (query_kernels.h), k_bake (bake_kernels.h),
-// k_nearest (nearest_kernels.h), k_all_hits (all_hits_kernels.h) and k_within (within_kernels.h) are built from the pieces below.  The frame's own walks (trace_kernels.h, rt_hip.hip's code
-// object) are not: this header is included by query.hip, bake.hip, nearest.hip, all_hits.hip and within.hip only.
+// k_nearest (nearest_kernels.h), k_all_hits (all_hits_kernels.h), k_within (within_kernels.h) and k_region (region_kernels.h) are built from the pieces below.  The frame's own walks (trace_kernels.h, rt_hip.hip's code
+// object) are not: this header is included by query.hip, bake.hip, nearest.hip, all_hits.hip, within.hip and region.hip only.
 //
 //   Stack          a lane's traversal stack: push, and a pop that takes the walk's re-test
 //   Ray, ray_setup a ray as its walk needs it: 1/dir, the sign bits, the octant, and which records it walks
 //   point_box_step one pass of a point's walk (nearest, within) at a box record: the slots keyed by nearest_box_d2, nearest first
+//   region_box_step one pass of a region's walk (overlap) at a box record: every slot region.h's box test passes is visited, in no particular order
 //   ray_step       one pass of a ray's fused loop: the fetch of one 64-byte record and its leaf, child-pair or 4-wide step; what an accepted triangle does
 //                  to the walk is the step's mode (closest, any hit, all hits)
 //   read_shading_triangle, store_surface, store_nearest, triangle_corners   the records' readers and writers
@@ -40,6 +41,7 @@
 #include "query.h"
 #include "all_hits.h"
 #include "nearest.h"
+#include "region.h"
 
 #define RT_QUERY_STACK_LDS 12
 #define RT_QUERY_SPILL_PER_LANE (RT_W4_STACK_MAX - RT_QUERY_STACK_LDS)
@@ -292,6 +294,68 @@ RT_DEV void point_box_step(const float4 q0, const float4 q1, const float4 q2, co
         }
     if (next != RT_IDLE_REF) ref = next;
     else ref = stack.pop([&](float entry) { return !(entry > best); });
+}
+
+// A region's planes as its walk keeps them: 16 bytes per plane and lane in LDS, lane-major (8 KiB per block).  Eight planes are 32 registers and a loop to
+// num_planes would index them per lane -- scratch; a lane reads its own column only, so no barrier is needed.
+typedef float4 RegionLds[RT_REGION_MAX_PLANES][64];          // a kernel declares one, __shared__
+
+// One pass of a region's walk at a box record (q0 .. q3 = its 64 bytes): the four slots of a 4-wide record or the two children of a child-pair record, decoded
+// as point_box_step decodes them, each tested against the lane's planes (region.h's box test).  A counting walk visits every passing slot, so there is no
+// key and no sort: all passing slots but one are pushed, that one is visited next; none: a pop, which always accepts.
+template <bool WIDE>
+RT_DEV void region_box_step(const float4 q0, const float4 q1, const float4 q2, const float4 q3, const RegionLds& planes, const uint32_t num_planes, uint32_t& ref,
+    Stack& stack)
+{
+    constexpr int N = WIDE ? 4 : 2;
+    uint32_t r[N];
+    float lo[N][3], hi[N][3];
+    if (WIDE)
+    {
+        const uint32_t meta = __float_as_uint(q0.w);
+        const float cell[3] = {__uint_as_float((meta & 0xFFu) << 23), __uint_as_float(((meta >> 8) & 0xFFu) << 23), __uint_as_float(((meta >> 16) & 0xFFu) << 23)};
+        const float origin[3] = {q0.x, q0.y, q0.z};
+        const uint32_t low[3] = {__float_as_uint(q1.x), __float_as_uint(q1.y), __float_as_uint(q1.z)};
+        const uint32_t high[3] = {__float_as_uint(q1.w), __float_as_uint(q2.x), __float_as_uint(q2.y)};
+        const uint32_t refs[4] = {__float_as_uint(q2.z), __float_as_uint(q2.w), __float_as_uint(q3.x), __float_as_uint(q3.y)};
+#pragma unroll
+        for (int k = 0; k < N; ++k)
+        {
+            r[k] = refs[k];
+#pragma unroll
+            for (int a = 0; a < 3; ++a)
+            {
+                lo[k][a] = (float)((low[a] >> (8 * k)) & 0xFFu) * cell[a] + origin[a];       // exact (wide_frame)
+                hi[k][a] = (float)((high[a] >> (8 * k)) & 0xFFu) * cell[a] + origin[a];
+            }
+        }
+    }
+    else
+    {
+        lo[0][0] = q0.x; lo[0][1] = q0.y; lo[0][2] = q2.x; hi[0][0] = q0.z; hi[0][1] = q0.w; hi[0][2] = q2.y;
+        lo[1][0] = q1.x; lo[1][1] = q1.y; lo[1][2] = q2.z; hi[1][0] = q1.z; hi[1][1] = q1.w; hi[1][2] = q2.w;
+        r[0] = __float_as_uint(q3.x); r[1] = __float_as_uint(q3.y);
+    }
+    bool pass[N];
+#pragma unroll
+    for (int k = 0; k < N; ++k) pass[k] = r[k] != RT_EMPTY_REF;
+    for (uint32_t j = 0; j < num_planes; ++j)
+    {
+        const float4 p4 = planes[j][threadIdx.x];
+        const float pl[4] = {p4.x, p4.y, p4.z, p4.w};
+#pragma unroll
+        for (int k = 0; k < N; ++k) pass[k] = pass[k] && !region_plane_rejects_box(pl, lo[k], hi[k]);
+    }
+    uint32_t next = RT_IDLE_REF;
+#pragma unroll
+    for (int k = N - 1; k >= 0; --k)
+        if (pass[k])
+        {
+            if (next != RT_IDLE_REF) stack.push(next, 0.0f);
+            next = r[k];
+        }
+    if (next != RT_IDLE_REF) ref = next;
+    else ref = stack.pop([](float) { return true; });
 }
 
 // a triangle's 128-byte shading record (p1 uv1.x | p2 uv1.y | p3 uv2.x | n1 uv2.y | n2 uv3.x | n3 uv3.y | mtl_index ...) as query_surface reads it

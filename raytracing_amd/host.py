@@ -26,7 +26,7 @@ EXPORTS = [
     "rth_render_upload_gpu_data", "rth_render_setup_seconds", "rth_render_create_with_options",
     "rth_render_set_refittable", "rth_render_refit", "rth_render_set_refit_motion",
     "rth_render_set_objects", "rth_render_pose", "rth_render_pick", "rth_render_integrator_pick", "rth_render_trace",
-    "rth_render_bake", "rth_render_occlusion_image", "rth_render_nearest", "rth_render_within", "rth_render_trace_all", "rth_render_pick_all",
+    "rth_render_bake", "rth_render_occlusion_image", "rth_render_nearest", "rth_render_within", "rth_render_overlap", "rth_render_select", "rth_render_pick_rect", "rth_render_integrator_pick_rect", "rth_render_trace_all", "rth_render_pick_all",
     "rth_scene_set_triangle_objects", "rth_scene_num_objects", "rth_scene_object_name", "rth_scene_num_triangle_objects", "rth_scene_triangle_objects",
 ]
 
@@ -78,6 +78,9 @@ def load():
         "rth_render_bake": (i32, [vp, vp, u32, vp, vp]), "rth_render_occlusion_image": (i32, [vp, vp, vp]),
         "rth_render_nearest": (i32, [vp, vp, u32, vp, vp]),
         "rth_render_within": (i32, [vp, vp, u32, u32, u32, vp, vp, vp]),
+        "rth_render_overlap": (i32, [vp, vp, u32, u32, vp, vp]), "rth_render_select": (i32, [vp, vp, u32, vp, vp, vp, vp]),
+        "rth_render_pick_rect": (i32, [vp, u32, u32, u32, u32, C.c_float, C.c_float, vp, vp, vp, vp, vp]),
+        "rth_render_integrator_pick_rect": (i32, [vp, u32, u32, u32, u32, C.c_float, C.c_float, vp, vp, vp]),
         "rth_render_trace_all": (i32, [vp, vp, u32, u32, vp, vp, vp]), "rth_render_pick_all": (i32, [vp, u32, u32, u32, vp, vp, vp, vp]),
         "rth_render_num_nodes": (u32, [vp]), "rth_render_nodes": (vp, [vp]),
         "rth_render_set_aov": (i32, [vp, i32]), "rth_render_resolve": (i32, [vp, vp]),
@@ -477,6 +480,68 @@ class Render:
             raise RtError("objects_within: the scene was not loaded with objects")
         got = self.within(capi.point_records(np.asarray([list(point) + [radius]], np.float32)), k=8)[0]
         return {"objects": sorted({m["object_name"] for m in got["members"]}), "count": got["count"], "complete": got["count"] <= 8}
+
+    def _object_sets(self, touching, inside, bit):
+        """the names of the objects with a triangle whose `touching` word has `bit` ("crossing") and of those all of whose triangles' `inside` words have it
+        ("window"), from the scene's own table of triangle objects: the per-triangle answer is complete, so these are too"""
+        names, objects = self.scene.object_names(), self.scene.triangle_objects()
+        crossing = sorted({names[o] for o in np.unique(objects[(touching >> bit) & 1 != 0])})
+        window = sorted({names[o] for o in np.unique(objects) if ((inside[objects == o] >> bit) & 1).all()})
+        return crossing, window
+
+    def overlap(self, regions, k=0):
+        """Every triangle of the scene as it is posed now that each of the caller's convex regions touches or encloses (Render::Overlap; regions:
+        capi.region_records' rule -- types.box_region, types.oriented_box_region): one dict per region -- `count` (the touching triangles), `inside` (those
+        wholly inside), `searched`, and `members`, the min(count, k) touching triangles with the lowest primitive ids as dicts of `primitive_id`, `inside`
+        and `crossing_planes` (`object_name` when the scene was loaded with objects).  k <= 8; select() is the complete form."""
+        from . import capi
+        rg = capi.region_records(regions)
+        n = len(rg)
+        out, members = np.zeros(n, T.region_hits), np.zeros((n, max(k, 1)), T.region_member)
+        self._c(self.lib.rth_render_overlap(self.handle, rg.ctypes.data if n else None, n, k, out.ctypes.data, members.ctypes.data if k else None))
+        names = self.scene.object_names()
+        objects = self.scene.triangle_objects() if names else None
+        result = []
+        for i in range(n):
+            listed = []
+            for m in members[i][:int(out[i]["stored"])]:
+                d = {"primitive_id": int(m["primitive_id"]), "inside": bool(m["flags"] & capi.REGION_MEMBER_INSIDE),
+                     "crossing_planes": [p for p in range(8) if (int(m["flags"]) >> (capi.REGION_MEMBER_CROSSING_SHIFT + p)) & 1]}
+                if names:
+                    d["object_name"] = names[objects[d["primitive_id"]]]
+                listed.append(d)
+            result.append({"count": int(out[i]["count"]), "inside": int(out[i]["inside"]), "searched": bool(out[i]["flags"] & capi.REGION_HITS_SEARCHED), "members": listed})
+        return result
+
+    def select(self, regions):
+        """At most 32 regions against every triangle of the scene as it is posed now (Render::Select): one dict per region -- `touching` and `inside`, the
+        primitive ids as uint32 arrays, ascending, complete; when the scene was loaded with objects also `objects_touching` (the "crossing" selection: an
+        object with a touching triangle) and `objects_inside` (the "window" selection: every triangle inside), sorted names."""
+        from . import capi
+        rg = capi.region_records(regions)
+        nt = self.lib.rth_scene_num_triangles(self.scene.handle)
+        touching, inside = np.zeros(nt, np.uint32), np.zeros(nt, np.uint32)
+        self._c(self.lib.rth_render_select(self.handle, rg.ctypes.data if len(rg) else None, len(rg), touching.ctypes.data, inside.ctypes.data, None, None))
+        result = []
+        for r in range(len(rg)):
+            d = {"touching": np.flatnonzero((touching >> r) & 1).astype(np.uint32), "inside": np.flatnonzero((inside >> r) & 1).astype(np.uint32)}
+            if self.scene.object_names():
+                d["objects_touching"], d["objects_inside"] = self._object_sets(touching, inside, r)
+            result.append(d)
+        return result
+
+    def pick_rect(self, x0, y0, x1, y1, window=False, t_near=0.0, t_far=float("inf")):
+        """The marquee: what lies under the inclusive pixel rectangle (x0, y0) .. (x1, y1) of the Render's current camera (Render::PickRect; the frame is not
+        touched): {"primitives": the primitive ids the rectangle's region touches -- with window=True those wholly inside it --, "region": the types.region};
+        when the scene was loaded with objects also "objects", the sorted names of the objects with such a triangle (window=True: all of whose triangles are
+        inside)."""
+        nt = self.lib.rth_scene_num_triangles(self.scene.handle)
+        g, touching, inside = np.zeros(1, T.region), np.zeros(nt, np.uint32), np.zeros(nt, np.uint32)
+        self._c(self.lib.rth_render_pick_rect(self.handle, x0, y0, x1, y1, t_near, t_far, g.ctypes.data, touching.ctypes.data, inside.ctypes.data, None, None))
+        out = {"primitives": np.flatnonzero((inside if window else touching) & 1).astype(np.uint32), "region": g[0]}
+        if self.scene.object_names():
+            out["objects"] = self._object_sets(touching, inside, 0)[1 if window else 0]
+        return out
 
     def trace_all(self, rays, max_hits=8, surfaces=False):
         """Every surface each of the caller's rays crosses in the scene as it is posed now (HIPPathTraceIntegrator::TraceAllHits; rays: types.ray records or

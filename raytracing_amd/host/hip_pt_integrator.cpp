@@ -190,6 +190,39 @@ void HIPPathTraceIntegrator::PointsWithin(rt_point const* points, std::size_t co
     Check(rt_scene_within(context_.Get(), points, (uint32_t)count, max_near, options, out, near, surfaces));
 }
 
+void HIPPathTraceIntegrator::RegionsOverlap(rt_region const* regions, std::size_t count, std::uint32_t max_list, rt_region_hits* out, rt_region_member* members)
+{
+    if (count > 0xFFFFFFFFull) throw HIPException("HIPPathTraceIntegrator::RegionsOverlap: more than 2^32 - 1 regions in one call");
+    Check(rt_scene_overlap(context_.Get(), regions, (uint32_t)count, max_list, out, members));
+}
+
+void HIPPathTraceIntegrator::SelectRegions(rt_region const* regions, std::uint32_t count, std::uint32_t* touching, std::uint32_t* inside, std::uint32_t* object_touching,
+    std::uint32_t* object_inside)
+{
+    Check(rt_scene_select(context_.Get(), regions, count, touching, inside, object_touching, object_inside));
+}
+
+void HIPPathTraceIntegrator::PickRect(std::uint32_t x0, std::uint32_t y0, std::uint32_t x1, std::uint32_t y1, float t_near, float t_far, rt_region* region,
+    std::uint32_t* touching, std::uint32_t* inside, std::uint32_t* object_touching, std::uint32_t* object_inside)
+{
+    Check(rt_frame_pick_rect(frame_, x0, y0, x1, y1, t_near, t_far, region, touching, inside, object_touching, object_inside));
+}
+
+void HIPPathTraceIntegrator::PickRectThrough(Camera const& camera, std::uint32_t x0, std::uint32_t y0, std::uint32_t x1, std::uint32_t y1, float t_near, float t_far,
+    rt_region* region, std::uint32_t* touching, std::uint32_t* inside, std::uint32_t* object_touching, std::uint32_t* object_inside)
+{
+    if (rt_frame_local_rows(frame_) != height_) throw HIPException("HIPPathTraceIntegrator::PickRectThrough: a tile frame: pick on a frame of the whole image");
+    // rt_frame_pick_rect's region for this camera (region.h's region_of_rect through rt_debug_rect_region: the same host arithmetic), then its select
+    rt_camera cam;
+    static_assert(sizeof(cam) == sizeof(camera), "Camera is rt_camera");
+    std::memcpy(&cam, &camera, sizeof(cam));
+    rt_region g;
+    if (rt_debug_rect_region(&cam, width_, height_, x0, y0, x1, y1, t_near, t_far, &g) != RT_OK)
+        throw HIPException(std::string("HIPPathTraceIntegrator::PickRectThrough: ") + rt_last_error(nullptr));
+    if (touching || inside || object_touching || object_inside) Check(rt_scene_select(context_.Get(), &g, 1u, touching, inside, object_touching, object_inside));
+    if (region) *region = g;
+}
+
 void HIPPathTraceIntegrator::Pick(std::uint32_t x, std::uint32_t y, rt_ray* ray, rt_hit* hit, rt_surface* surface)
 {
     Check(rt_frame_pick(frame_, x, y, ray, hit, surface));

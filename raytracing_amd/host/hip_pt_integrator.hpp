@@ -125,6 +125,18 @@ public:
     // nearest max_near members in near and surfaces (max_near records per point; either may be null); options: RT_WITHIN_K_NEAREST.  Throws HIPException with
     // the library's message on a refusal; requests no reset and does not touch the frame.
     void PointsWithin(rt_point const* points, std::size_t count, std::uint32_t max_near, std::uint32_t options, rt_point_hits* out, rt_nearest* near, rt_surface* surfaces);
+    // Overlap (rt_scene_overlap / rt_scene_select / rt_frame_pick_rect): RegionsOverlap -- per convex region (up to 8 half-spaces) the counts
+    // of the triangles it touches and encloses in out and the touching ones with the lowest ids in members (max_list per region; may be null); SelectRegions --
+    // at most 32 regions against every triangle, a bit per region in a word per triangle (touching, inside) and per object (after SetObjects; any may be null);
+    // PickRect -- the region of the inclusive pixel rectangle of the frame's current camera, then one select with it (bit 0); PickRectThrough -- the same for a
+    // camera the frame has not been given, as PickThrough.  All throw HIPException with the library's message on a refusal; none requests a reset or touches
+    // the frame.
+    void RegionsOverlap(rt_region const* regions, std::size_t count, std::uint32_t max_list, rt_region_hits* out, rt_region_member* members);
+    void SelectRegions(rt_region const* regions, std::uint32_t count, std::uint32_t* touching, std::uint32_t* inside, std::uint32_t* object_touching, std::uint32_t* object_inside);
+    void PickRect(std::uint32_t x0, std::uint32_t y0, std::uint32_t x1, std::uint32_t y1, float t_near, float t_far, rt_region* region, std::uint32_t* touching,
+        std::uint32_t* inside, std::uint32_t* object_touching, std::uint32_t* object_inside);
+    void PickRectThrough(Camera const& camera, std::uint32_t x0, std::uint32_t y0, std::uint32_t x1, std::uint32_t y1, float t_near, float t_far, rt_region* region,
+        std::uint32_t* touching, std::uint32_t* inside, std::uint32_t* object_touching, std::uint32_t* object_inside);
     // All hits (rt_scene_trace_all / rt_frame_pick_all): every surface each ray crosses -- the counts in out, the nearest max_hits crossings
     // in hits and surfaces (max_hits records per ray; either may be null).  PickAll: the ray through the centre of pixel (x, y) of the frame's current camera;
     // PickAllThrough: the same for a camera the frame has not been given, as PickThrough.  All throw HIPException with the library's message on a refusal; none

@@ -290,6 +290,25 @@ int rth_render_within(void* r, const rt_point* points, uint32_t n, uint32_t max_
 {
     return guard([&]() { ((rt::Render*)r)->Within(points, n, max_near, options, out, near, surfaces); return 0; }, 1);
 }
+int rth_render_overlap(void* r, const rt_region* regions, uint32_t n, uint32_t max_list, rt_region_hits* out, rt_region_member* members)
+{
+    return guard([&]() { ((rt::Render*)r)->Overlap(regions, n, max_list, out, members); return 0; }, 1);
+}
+int rth_render_select(void* r, const rt_region* regions, uint32_t n, uint32_t* touching, uint32_t* inside, uint32_t* object_touching, uint32_t* object_inside)
+{
+    return guard([&]() { ((rt::Render*)r)->Select(regions, n, touching, inside, object_touching, object_inside); return 0; }, 1);
+}
+int rth_render_pick_rect(void* r, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, float t_near, float t_far, rt_region* region, uint32_t* touching, uint32_t* inside,
+    uint32_t* object_touching, uint32_t* object_inside)
+{
+    return guard([&]() { ((rt::Render*)r)->PickRect(x0, y0, x1, y1, t_near, t_far, region, touching, inside, object_touching, object_inside); return 0; }, 1);
+}
+// HIPPathTraceIntegrator::PickRect itself: the FRAME's camera, as rth_render_integrator_pick
+int rth_render_integrator_pick_rect(void* r, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, float t_near, float t_far, rt_region* region, uint32_t* touching,
+    uint32_t* inside)
+{
+    return guard([&]() { ((rt::Render*)r)->GetIntegrator().PickRect(x0, y0, x1, y1, t_near, t_far, region, touching, inside, nullptr, nullptr); return 0; }, 1);
+}
 int rth_render_upload_gpu_data(void* r) { return guard([&]() { ((rt::Render*)r)->UploadGPUData(); return 0; }, 1); }
 
 } // extern "C"

@@ -7,6 +7,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <iostream>
+#include <limits>
 #include <string>
 #include "render.hpp"
 
@@ -45,6 +46,10 @@ int main(int argc, char** argv)
         rt_bake_desc ao = {64u, 0u, 0u, 1e-3f, 1.0f};   // --ao_samples n --ao_radius r --ao_bias b
         struct WithinAt { rt_point point; std::uint32_t k; };
         std::vector<WithinAt> within_points;    // --within x,y,z,r[,k] (repeatable): after the scene is uploaded and posed, print the triangles within r (the k nearest only)
+        struct OverlapAt { float lo[3], hi[3]; std::uint32_t k; };
+        std::vector<OverlapAt> overlap_boxes;   // --overlap lx,ly,lz,hx,hy,hz[,k] (repeatable): after the scene is uploaded and posed, print the triangles the box touches (the k lowest ids)
+        struct RectAt { std::uint32_t x0, y0, x1, y1; bool window; };
+        std::vector<RectAt> pick_rects;         // --pick_rect x0,y0,x1,y1[,window] (repeatable): print what lies under that pixel rectangle (window: wholly inside it)
         std::vector<rt_point> nearest_points;   // --nearest x,y,z[,r] (repeatable): after the scene is uploaded and posed, print the nearest surface point (within r)
         bool list_objects = false;              // --list_objects 1: print the OBJ's o / g shapes (index and name) and exit; needs no GPU
         for (int i = 1; i < argc; ++i)
@@ -161,6 +166,33 @@ int main(int argc, char** argv)
                 within_points.push_back(q);
                 scene_options |= rt::Scene::kObjects;
             }
+            else if (!strcmp(argv[i], "--overlap"))
+            {
+                OverlapAt q;
+                q.k = RT_REGION_LIST_MAX;
+                const int got = sscanf(next(), "%f,%f,%f,%f,%f,%f,%u", &q.lo[0], &q.lo[1], &q.lo[2], &q.hi[0], &q.hi[1], &q.hi[2], &q.k);
+                if (got < 6 || q.k > RT_REGION_LIST_MAX)
+                {
+                    std::cerr << "--overlap wants lx,ly,lz,hx,hy,hz or lx,ly,lz,hx,hy,hz,k (a box's corners and optionally how many triangles to list, 0 .. 8)\n";
+                    return 2;
+                }
+                overlap_boxes.push_back(q);
+                scene_options |= rt::Scene::kObjects;
+            }
+            else if (!strcmp(argv[i], "--pick_rect"))
+            {
+                RectAt q;
+                char word[16] = "";
+                const int got = sscanf(next(), "%u,%u,%u,%u,%15s", &q.x0, &q.y0, &q.x1, &q.y1, word);
+                q.window = got == 5 && !strcmp(word, "window");
+                if (got < 4 || (got == 5 && !q.window))
+                {
+                    std::cerr << "--pick_rect wants x0,y0,x1,y1 or x0,y0,x1,y1,window (an inclusive pixel rectangle; window: only what lies wholly inside it)\n";
+                    return 2;
+                }
+                pick_rects.push_back(q);
+                scene_options |= rt::Scene::kObjects;
+            }
             else if (!strcmp(argv[i], "--ao")) ao_out = next();
             else if (!strcmp(argv[i], "--ao_samples")) ao.samples = (unsigned)atoi(next());
             else if (!strcmp(argv[i], "--ao_radius")) ao.radius = (float)atof(next());
@@ -194,6 +226,9 @@ int main(int argc, char** argv)
                              "  (default 1), 1 where the pixel sees nothing; traced and baked on the device (rt_scene_bake_buffer); one GPU only\n"
                              "  --pick_all x,y (repeatable) prints every surface under that pixel, nearest first, one line per surface; --signed 1 makes --nearest print whether\n"
                              "    the point is inside (more exits than entries along (0.36, 0.48, 0.8))\n"
+                             "  --overlap lx,ly,lz,hx,hy,hz[,k] (repeatable) prints the triangles that axis-aligned box touches once the scene is uploaded and posed: how many,\n"
+                             "  how many lie wholly inside, and one line for each of the k (default 8) lowest primitive ids; --pick_rect x0,y0,x1,y1[,window] (repeatable)\n"
+                             "  prints what lies under that inclusive pixel rectangle: the primitives its region touches (window: wholly inside) and their objects; one GPU only\n"
                              "  --within x,y,z,r[,k] (repeatable) prints the triangles within r of that point once the scene is uploaded and posed: their count, and one line\n"
                              "  for each of the nearest 8 (with k: the k nearest only, and nothing beyond them is looked for)\n"
                              "  --nearest x,y,z[,r] (repeatable) prints the nearest surface point to that point (within r) once the scene is uploaded and posed: primitive,\n"
@@ -252,6 +287,11 @@ int main(int argc, char** argv)
         if (!within_points.empty() && (gpus > 1 || tiled_path))
         {
             std::cerr << "--within needs one GPU\n";
+            return 2;
+        }
+        if ((!overlap_boxes.empty() || !pick_rects.empty()) && (gpus > 1 || tiled_path))
+        {
+            std::cerr << "--overlap and --pick_rect need one GPU\n";
             return 2;
         }
         if (!ao_out.empty() && (gpus > 1 || tiled_path))
@@ -438,6 +478,68 @@ int main(int argc, char** argv)
                 }
             }
         };
+        // --overlap: one line per box and one per listed triangle (rt_scene_overlap through Render::Overlap); the object as --pick names it
+        auto object_of = [&](std::uint32_t prim) { return prim < scene.GetTriangleObjects().size() ? scene.GetTriangleObjects()[prim] : RT_INVALID_ID; };
+        auto print_object = [&](std::uint32_t object)
+        {
+            if (object < scene.GetObjectNames().size()) std::cout << object << " " << scene.GetObjectNames()[object];
+            else std::cout << "none";
+        };
+        auto print_overlaps = [&]()
+        {
+            for (const OverlapAt& b : overlap_boxes)
+            {
+                rt_region g = {};
+                g.num_planes = 6u;
+                for (int a = 0; a < 3; ++a)
+                {
+                    g.planes[a][a] = -1.0f; g.planes[a][3] = b.lo[a];                 // lo - x > 0: outside
+                    g.planes[3 + a][a] = 1.0f; g.planes[3 + a][3] = -b.hi[a];         // x - hi > 0: outside
+                }
+                rt_region_hits rec;
+                rt_region_member members[RT_REGION_LIST_MAX];
+                render.Overlap(&g, 1, b.k, &rec, b.k ? members : nullptr);
+                std::cout << "overlap " << b.lo[0] << "," << b.lo[1] << "," << b.lo[2] << " " << b.hi[0] << "," << b.hi[1] << "," << b.hi[2] << ": ";
+                if (rec.count == 0u) { std::cout << "none" << std::endl; continue; }
+                std::cout << "count " << rec.count << " inside " << rec.inside << " listed " << rec.stored << std::endl;
+                for (std::uint32_t j = 0; j < rec.stored; ++j)
+                {
+                    std::cout << "overlap   " << j << ": primitive " << members[j].primitive_id << ((members[j].flags & RT_REGION_MEMBER_INSIDE) ? " inside" : " crossing") << " object ";
+                    print_object(object_of(members[j].primitive_id));
+                    std::cout << std::endl;
+                }
+            }
+        };
+        // --pick_rect: one line per rectangle and one per object (rt_scene_select of the rectangle's region through Render::PickRect)
+        auto print_pick_rects = [&]()
+        {
+            for (const RectAt& q : pick_rects)
+            {
+                std::vector<std::uint32_t> touching(scene.GetTriangles().size()), inside(scene.GetTriangles().size());
+                render.PickRect(q.x0, q.y0, q.x1, q.y1, 0.0f, std::numeric_limits<float>::infinity(), nullptr, touching.data(), inside.data(), nullptr, nullptr);
+                const std::size_t n_objects = scene.GetObjectNames().size();
+                std::vector<std::uint32_t> any(n_objects, 0u), all(n_objects, 1u), has(n_objects, 0u);
+                std::uint32_t count = 0u;
+                for (std::size_t t = 0; t < touching.size(); ++t)
+                {
+                    const bool picked = ((q.window ? inside[t] : touching[t]) & 1u) != 0u;
+                    count += picked ? 1u : 0u;
+                    const std::uint32_t o = object_of((std::uint32_t)t);
+                    if (o >= n_objects) continue;
+                    has[o] = 1u;
+                    any[o] |= touching[t] & 1u;
+                    all[o] &= inside[t] & 1u;
+                }
+                std::cout << "pick_rect " << q.x0 << "," << q.y0 << " " << q.x1 << "," << q.y1 << (q.window ? " window" : "") << ": primitives " << count << std::endl;
+                for (std::size_t o = 0; o < n_objects; ++o)
+                    if (has[o] && (q.window ? all[o] : any[o]))
+                    {
+                        std::cout << "pick_rect   object ";
+                        print_object((std::uint32_t)o);
+                        std::cout << std::endl;
+                    }
+            }
+        };
         // --ao: Render::OcclusionImage of the camera as it stands, written as a grey PFM
         auto write_ao = [&]()
         {
@@ -495,6 +597,8 @@ int main(int argc, char** argv)
             print_picks_all();
             print_nearest();
             print_within();
+            print_overlaps();
+            print_pick_rects();
             write_ao();
             return 0;
         }
@@ -537,6 +641,8 @@ int main(int argc, char** argv)
         print_picks_all();
         print_nearest();
         print_within();
+        print_overlaps();
+        print_pick_rects();
         write_ao();
         if (!out.empty() && (filter_iterations >= 0 || temporal_iterations >= 0))
             WritePFM(out.c_str(), render.GetIntegrator().ResolveNow(), width, height);     // the filtered, tone-mapped image

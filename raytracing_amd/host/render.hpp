@@ -54,6 +54,11 @@ public:
     void Nearest(rt_point const* points, std::size_t count, rt_nearest* out, rt_surface* surfaces) { integrator_->NearestPoints(points, count, out, surfaces); }
     // every triangle within max_distance of each of the caller's points, counted and the nearest max_near listed; the frame is not touched
     void Within(rt_point const* points, std::size_t count, std::uint32_t max_near, std::uint32_t options, rt_point_hits* out, rt_nearest* near, rt_surface* surfaces) { integrator_->PointsWithin(points, count, max_near, options, out, near, surfaces); }
+    // every triangle a convex region touches or encloses: counted and the lowest ids listed per region (Overlap), a bit per region for every
+    // triangle and object of at most 32 regions (Select), the pixel rectangle of the Render's current camera (PickRect); the frame is not touched
+    void Overlap(rt_region const* regions, std::size_t count, std::uint32_t max_list, rt_region_hits* out, rt_region_member* members) { integrator_->RegionsOverlap(regions, count, max_list, out, members); }
+    void Select(rt_region const* regions, std::uint32_t count, std::uint32_t* touching, std::uint32_t* inside, std::uint32_t* object_touching, std::uint32_t* object_inside) { integrator_->SelectRegions(regions, count, touching, inside, object_touching, object_inside); }
+    void PickRect(std::uint32_t x0, std::uint32_t y0, std::uint32_t x1, std::uint32_t y1, float t_near, float t_far, rt_region* region, std::uint32_t* touching, std::uint32_t* inside, std::uint32_t* object_touching, std::uint32_t* object_inside) { integrator_->PickRectThrough(camera_, x0, y0, x1, y1, t_near, t_far, region, touching, inside, object_touching, object_inside); }
     // every surface a ray crosses, counted and the nearest max_hits sorted; PickAll: through the centre of a pixel of the Render's current camera
     void TraceAllHits(rt_ray const* rays, std::size_t count, std::uint32_t max_hits, rt_ray_hits* out, rt_hit* hits, rt_surface* surfaces) { integrator_->TraceAllHits(rays, count, max_hits, out, hits, surfaces); }
     void PickAll(std::uint32_t x, std::uint32_t y, std::uint32_t max_hits, rt_ray* ray, rt_ray_hits* out, rt_hit* hits, rt_surface* surfaces) { integrator_->PickAllThrough(camera_, x, y, max_hits, ray, out, hits, surfaces); }

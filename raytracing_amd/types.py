@@ -31,6 +31,12 @@ nearest = np.dtype([("position", "<f4", (3,)), ("distance", "<f4"), ("bc", "<f4"
 ray_hits = np.dtype([("count", "<u4"), ("entering", "<u4"), ("stored", "<u4"), ("flags", "<u4")])
 # rt_point_hits (include/rt_hip.h): what a within query reports of a point: the triangles within its radius, how many of them are listed, the nearest one; flags bit 0 = searched, bit 1 = a k-nearest answer
 point_hits = np.dtype([("count", "<u4"), ("stored", "<u4"), ("nearest_primitive", "<u4"), ("flags", "<u4")])
+# rt_region / rt_region_hits / rt_region_member (include/rt_hip.h): an overlap query's convex region -- num_planes half-spaces, plane k = (nx, ny, nz, d), a point x is
+# outside when ((nx x0 + ny x1) + nz x2) + d > 0 --, what it reports of it (the touching and the inside triangles; flags bit 0 = searched) and a listed member
+# (flags bit 0 = inside, bit 8 + k = plane k has 1 or 2 corners outside)
+region = np.dtype([("num_planes", "<u4"), ("reserved", "<u4", (3,)), ("planes", "<f4", (8, 4))])
+region_hits = np.dtype([("count", "<u4"), ("inside", "<u4"), ("stored", "<u4"), ("flags", "<u4")])
+region_member = np.dtype([("primitive_id", "<u4"), ("flags", "<u4")])
 camera = np.dtype([("position", float3), ("front", float3), ("up", float3), ("fov", "<f4"),
                    ("aspect_ratio", "<f4"), ("aperture", "<f4"), ("focus_distance", "<f4")])
 
@@ -39,6 +45,44 @@ assert packed_material.itemsize == 20 and light.itemsize == 48 and texture.items
 assert vertex.itemsize == 48 and triangle.itemsize == 160 and bvh_node.itemsize == 48
 assert camera.itemsize == 64 and surface.itemsize == 64 and bake_result.itemsize == 16
 assert point.itemsize == 16 and nearest.itemsize == 32 and ray_hits.itemsize == 16 and point_hits.itemsize == 16
+assert region.itemsize == 144 and region_hits.itemsize == 16 and region_member.itemsize == 8
+
+
+def planes_region(planes):
+    """a types.region scalar of 1 to 8 planes (nx, ny, nz, d): the points with nx x + ny y + nz z + d <= 0 on every one"""
+    pl = np.asarray(planes, np.float32).reshape(-1, 4)
+    if not 1 <= len(pl) <= 8:
+        raise ValueError("planes_region: a region has 1 to 8 planes, not %d" % len(pl))
+    g = np.zeros((), region)
+    g["num_planes"] = len(pl)
+    g["planes"][:len(pl)] = pl
+    return g
+
+
+def box_region(lo, hi):
+    """the axis-aligned box lo <= x <= hi as a types.region scalar: six planes, -x, -y, -z, then +x, +y, +z"""
+    lo, hi = np.asarray(lo, np.float32), np.asarray(hi, np.float32)
+    pl = np.zeros((6, 4), np.float32)
+    for a in range(3):
+        pl[a, a], pl[a, 3] = -1.0, lo[a]              # lo - x > 0: outside
+        pl[3 + a, a], pl[3 + a, 3] = 1.0, -hi[a]      # x - hi > 0: outside
+    return planes_region(pl)
+
+
+def oriented_box_region(matrix3x4, half_extents):
+    """the box |u_a| <= half_extents[a] in the frame of a 3x4 matrix (rt_scene_pose's layout: x_world = M[:, :3] u + M[:, 3], columns orthogonal, any
+    length) as a types.region scalar of six planes: per axis n = +-column / |column|, through centre +- column * half_extent"""
+    m = np.asarray(matrix3x4, np.float64).reshape(3, 4)
+    h = np.asarray(half_extents, np.float64)
+    pl = np.zeros((6, 4))
+    for a in range(3):
+        col = m[:, a]
+        ln = np.linalg.norm(col)
+        n = col / ln
+        for side, sign in ((a, -1.0), (3 + a, 1.0)):
+            pl[side, :3] = sign * n
+            pl[side, 3] = -(sign * n) @ m[:, 3] - h[a] * ln
+    return planes_region(pl.astype(np.float32))
 
 
 def default_camera(width, height):
