@@ -2,11 +2,11 @@
 // section 7k): the kernels (all_hits_kernels.h), their host driver, and the host's brute force over the same arithmetic (all_hits.h).  A translation unit and a
 // code object of its own so that the hot path's code object (rt_hip.hip, codeobj.code_object_sha256) does not change.  -ffp-contract=off like every other unit.
 #include <hip/hip_runtime.h>
-#include <thread>
 #include <vector>
 #include "rt_hip.h"
 #include "all_hits_kernels.h"
 #include "all_hits_host.h"
+#include "walk_host.h"
 
 namespace all_hits
 {
@@ -54,8 +54,7 @@ const char* leaves_refused(const rt_bvh_node* nodes, uint32_t nn, uint32_t n_tri
     return nullptr;
 }
 
-static void brute_range(const rt_bvh_node* nodes, uint32_t nn, const rt_triangle* tris, const rt_ray* rays, uint32_t first, uint32_t end, uint32_t max_hits,
-    rt_ray_hits* out, rt_hit* hits)
+void brute_host(const rt_bvh_node* nodes, uint32_t nn, const rt_triangle* tris, const rt_ray* rays, uint32_t n, uint32_t max_hits, rt_ray_hits* out, rt_hit* hits)
 {
     auto corners = [&](uint32_t prim, float (&p1)[3], float (&e1)[3], float (&e2)[3])
     {
@@ -63,63 +62,56 @@ static void brute_range(const rt_bvh_node* nodes, uint32_t nn, const rt_triangle
         walk::triangle_corners(tris[prim], p1, p2, p3);
         for (int a = 0; a < 3; ++a) { e1[a] = p2[a] - p1[a]; e2[a] = p3[a] - p1[a]; }
     };
-    for (uint32_t i = first; i < end; ++i)
+    // the work: (ray, node) pairs
+    walk::split_range(n, (uint64_t)n * nn, [&](uint32_t first, uint32_t end)
     {
-        const float o4[4] = {rays[i].origin.x, rays[i].origin.y, rays[i].origin.z, rays[i].origin.w};
-        const float d4[4] = {rays[i].direction.x, rays[i].direction.y, rays[i].direction.z, rays[i].direction.w};
-        const float t_min = o4[3], t_max = d4[3];
-        const bool walked = ah_walkable(o4, d4);
-        uint32_t count = 0u, entering = 0u, exits = 0u;
-        AhList list;
-        ah_list_clear(list);
-        if (walked)
+        for (uint32_t i = first; i < end; ++i)
         {
-            float inv[3];
-            ah_inverse(d4, inv);
-            for (uint32_t k = 0; k < nn; ++k)
+            const float o4[4] = {rays[i].origin.x, rays[i].origin.y, rays[i].origin.z, rays[i].origin.w};
+            const float d4[4] = {rays[i].direction.x, rays[i].direction.y, rays[i].direction.z, rays[i].direction.w};
+            const float t_min = o4[3], t_max = d4[3];
+            const bool walked = ah_walkable(o4, d4);
+            uint32_t count = 0u, entering = 0u, exits = 0u;
+            AhList list;
+            ah_list_clear(list);
+            if (walked)
             {
-                const rt_bvh_node& nd = nodes[k];
-                const uint32_t np = nd.num_primitives_axis >> 16;
-                if (np == 0u) continue;
-                const float lo[3] = {nd.bounds_min.x, nd.bounds_min.y, nd.bounds_min.z}, hi[3] = {nd.bounds_max.x, nd.bounds_max.y, nd.bounds_max.z};
-                if (!ah_box(lo, hi, o4, inv, t_min, t_max)) continue;
-                for (uint32_t prim = nd.offset; prim < nd.offset + np; ++prim)
+                float inv[3];
+                ah_inverse(d4, inv);
+                for (uint32_t k = 0; k < nn; ++k)
                 {
-                    float p1[3], e1[3], e2[3], u, v, t, det;
-                    corners(prim, p1, e1, e2);
-                    if (!ah_triangle(o4, d4, p1, e1, e2, t_min, t_max, &u, &v, &t, &det)) continue;
-                    ++count;
-                    if (det > 0.0f) ++entering;
-                    ah_list_insert(list, t, prim);
+                    const rt_bvh_node& nd = nodes[k];
+                    const uint32_t np = nd.num_primitives_axis >> 16;
+                    if (np == 0u) continue;
+                    const float lo[3] = {nd.bounds_min.x, nd.bounds_min.y, nd.bounds_min.z}, hi[3] = {nd.bounds_max.x, nd.bounds_max.y, nd.bounds_max.z};
+                    if (!ah_box(lo, hi, o4, inv, t_min, t_max)) continue;
+                    for (uint32_t prim = nd.offset; prim < nd.offset + np; ++prim)
+                    {
+                        float p1[3], e1[3], e2[3], u, v, t, det;
+                        corners(prim, p1, e1, e2);
+                        if (!ah_triangle(o4, d4, p1, e1, e2, t_min, t_max, &u, &v, &t, &det)) continue;
+                        ++count;
+                        if (det > 0.0f) ++entering;
+                        ah_list_insert(list, t, prim);
+                    }
                 }
             }
-        }
-        for (uint32_t j = 0; j < max_hits; ++j)
-        {
-            rt_hit h = {{0.0f, 0.0f}, RT_INVALID_ID, 0.0f};
-            if (j < count)
+            for (uint32_t j = 0; j < max_hits; ++j)
             {
-                float p1[3], e1[3], e2[3], u = 0.0f, v = 0.0f, t = 0.0f, det = 0.0f;
-                corners(list.prim[j], p1, e1, e2);
-                (void)ah_triangle(o4, d4, p1, e1, e2, t_min, t_max, &u, &v, &t, &det);
-                if (det < 0.0f) exits |= 1u << j;
-                h.bc.x = u; h.bc.y = v; h.primitive_id = list.prim[j]; h.t = t;
+                rt_hit h = {{0.0f, 0.0f}, RT_INVALID_ID, 0.0f};
+                if (j < count)
+                {
+                    float p1[3], e1[3], e2[3], u = 0.0f, v = 0.0f, t = 0.0f, det = 0.0f;
+                    corners(list.prim[j], p1, e1, e2);
+                    (void)ah_triangle(o4, d4, p1, e1, e2, t_min, t_max, &u, &v, &t, &det);
+                    if (det < 0.0f) exits |= 1u << j;
+                    h.bc.x = u; h.bc.y = v; h.primitive_id = list.prim[j]; h.t = t;
+                }
+                hits[(size_t)i * max_hits + j] = h;
             }
-            hits[(size_t)i * max_hits + j] = h;
+            out[i] = ah_record(count, entering, max_hits, exits, walked);
         }
-        out[i] = ah_record(count, entering, max_hits, exits, walked);
-    }
-}
-
-void brute_host(const rt_bvh_node* nodes, uint32_t nn, const rt_triangle* tris, const rt_ray* rays, uint32_t n, uint32_t max_hits, rt_ray_hits* out, rt_hit* hits)
-{
-    // every ray is on its own: above a million (ray, node) pairs the rays are shared out among up to 16 threads (no result depends on it)
-    const uint32_t threads = (uint64_t)n * nn < (1u << 20) ? 1u : (n < 16u ? n : 16u);
-    if (threads <= 1u) { brute_range(nodes, nn, tris, rays, 0u, n, max_hits, out, hits); return; }
-    std::vector<std::thread> pool;
-    for (uint32_t t = 0; t < threads; ++t)
-        pool.emplace_back(brute_range, nodes, nn, tris, rays, (uint32_t)((uint64_t)n * t / threads), (uint32_t)((uint64_t)n * (t + 1u) / threads), max_hits, out, hits);
-    for (std::thread& t : pool) t.join();
+    });
 }
 
 bool brute_device(hipStream_t stream, const rt_bvh_node* nodes, uint32_t nn, const rt_triangle* tris, uint32_t n_tris, const rt_ray* rays, uint32_t n,

@@ -96,23 +96,12 @@ __global__ __launch_bounds__(64) void k_all_hits(DScene sc, const float4* __rest
     stack.report(status);
 }
 
-// k_query_surface's body with hit j of ray i reading ray i.  hits[k * hit_stride] may be the first 16 bytes of out[k] itself: lane k reads it before it writes.
+// k_query_surface's body (walk::ray_surface) with hit j of ray i reading ray i.  hits[k * hit_stride] may be the first 16 bytes of out[k] itself: lane k reads it before it writes.
 __global__ __launch_bounds__(256) void k_all_hits_surface(const float4* __restrict__ tris, uint32_t n_tris, const uint32_t* __restrict__ object_of_triangle,
     const float4* __restrict__ rays, const float4* hits, uint32_t hit_stride, uint32_t max_hits, unsigned long long total, float4* out)
 {
     const unsigned long long k = (unsigned long long)blockIdx.x * 256u + threadIdx.x;
-    if (k >= total) return;
-    const float4 hit = hits[(size_t)k * hit_stride];
-    const uint32_t prim = __float_as_uint(hit.z);
-    rt_surface s = qs_miss();
-    if (prim < n_tris)                                           // RT_INVALID_ID (no hit stored here) is above every count
-    {
-        const QsTriangle t = walk::read_shading_triangle(tris, prim);
-        const float4 rd = rays[2 * (size_t)(k / max_hits) + 1];
-        const float d[3] = {rd.x, rd.y, rd.z};
-        s = query_surface(t, d, hit.x, hit.y, hit.w, prim, object_of_triangle ? object_of_triangle[prim] : RT_INVALID_ID);
-    }
-    walk::store_surface(out + (size_t)k * 4, s);
+    if (k < total) walk::ray_surface<true>(tris, n_tris, object_of_triangle, rays + 2 * (size_t)(k / max_hits), hits, hit_stride, (size_t)k, out);
 }
 
 // Every leaf of `nodes` (the host has checked that each leaf's triangles lie inside the array): the leaf's box test -- box_test_fast, or box_test for an

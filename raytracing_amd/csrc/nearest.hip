@@ -3,14 +3,11 @@
 // translation unit and a code object of its own so that the hot path's code object (rt_hip.hip, codeobj.code_object_sha256) does not change.
 // -ffp-contract=off like every other unit.
 #include <hip/hip_runtime.h>
-#include <string.h>
 #include <functional>
-#include <thread>
-#include <vector>
 #include "rt_hip.h"
 #include "nearest_kernels.h"
 #include "nearest_host.h"
-#include "wide_bvh.h"
+#include "walk_host.h"
 
 namespace nearest
 {
@@ -41,37 +38,29 @@ bool launch(hipStream_t stream, query::Scratch& q, const DScene& sc, bool use_wi
     return true;
 }
 
-static void brute_range(const rt_triangle* tris, uint32_t n_tris, const rt_point* points, uint32_t first, uint32_t end, rt_nearest* out)
-{
-    for (uint32_t i = first; i < end; ++i)
-    {
-        const float* p = points[i].position;
-        out[i] = nearest_none();
-        if (!nearest_searched(p, points[i].max_distance)) continue;
-        float best = points[i].max_distance * points[i].max_distance;
-        uint32_t best_prim = RT_INVALID_ID;
-        float p1[3], p2[3], p3[3];
-        for (uint32_t t = 0; t < n_tris; ++t)
-        {
-            walk::triangle_corners(tris[t], p1, p2, p3);
-            const NpTriangle c = nearest_point_triangle(p, p1, p2, p3);
-            if (nearest_accepts(c.d2, t, best, best_prim)) { best = c.d2; best_prim = t; }
-        }
-        if (best_prim == RT_INVALID_ID) continue;
-        walk::triangle_corners(tris[best_prim], p1, p2, p3);
-        out[i] = nearest_record(p, p1, p2, p3, best_prim);
-    }
-}
-
 void brute_host(const rt_triangle* tris, uint32_t n_tris, const rt_point* points, uint32_t n, rt_nearest* out)
 {
-    // every point is on its own: above a million pairs the points are shared out among up to 16 threads (no result depends on it)
-    const uint32_t threads = (uint64_t)n * n_tris < (1u << 20) ? 1u : (n < 16u ? n : 16u);
-    if (threads <= 1u) { brute_range(tris, n_tris, points, 0u, n, out); return; }
-    std::vector<std::thread> pool;
-    for (uint32_t t = 0; t < threads; ++t)
-        pool.emplace_back(brute_range, tris, n_tris, points, (uint32_t)((uint64_t)n * t / threads), (uint32_t)((uint64_t)n * (t + 1u) / threads), out);
-    for (std::thread& t : pool) t.join();
+    walk::split_range(n, (uint64_t)n * n_tris, [&](uint32_t first, uint32_t end)
+    {
+        for (uint32_t i = first; i < end; ++i)
+        {
+            const float* p = points[i].position;
+            out[i] = nearest_none();
+            if (!nearest_searched(p, points[i].max_distance)) continue;
+            float best = points[i].max_distance * points[i].max_distance;
+            uint32_t best_prim = RT_INVALID_ID;
+            float p1[3], p2[3], p3[3];
+            for (uint32_t t = 0; t < n_tris; ++t)
+            {
+                walk::triangle_corners(tris[t], p1, p2, p3);
+                const NpTriangle c = nearest_point_triangle(p, p1, p2, p3);
+                if (nearest_accepts(c.d2, t, best, best_prim)) { best = c.d2; best_prim = t; }
+            }
+            if (best_prim == RT_INVALID_ID) continue;
+            walk::triangle_corners(tris[best_prim], p1, p2, p3);
+            out[i] = nearest_record(p, p1, p2, p3, best_prim);
+        }
+    });
 }
 
 bool brute_device(hipStream_t stream, const rt_triangle* tris, uint32_t n_tris, const rt_point* points, uint32_t n, rt_nearest* out)
@@ -90,22 +79,8 @@ bool brute_device(hipStream_t stream, const rt_triangle* tris, uint32_t n_tris, 
 const char* walk_points(const rt_bvh_node* nodes, uint32_t nn, const rt_triangle* tris, uint32_t n_tris, bool wide, const rt_point* points, uint32_t n,
     uint32_t* tested, const std::function<float(uint32_t, uint32_t, const NpTriangle&, float)>& triangle)
 {
-    // the `last` flags of the trace records, and the child-pair form's references: an interior node's index, RT_LEAF_BIT | first triangle for a leaf
-    std::vector<uint8_t> last(n_tris, 0);
-    for (uint32_t i = 0; i < nn; ++i)
-    {
-        const uint32_t np = nodes[i].num_primitives_axis >> 16;
-        if (np > 0u)
-        {
-            if ((uint64_t)nodes[i].offset + np > n_tris) return "a leaf's triangles lie outside the array";
-            last[nodes[i].offset + np - 1u] = 1;
-        }
-        else if (i + 1u >= nn || nodes[i].offset <= i || nodes[i].offset >= nn) return "an interior node's children lie outside the array";
-    }
-    auto node_ref = [&](uint32_t c) { return (nodes[c].num_primitives_axis >> 16) != 0u ? RT_LEAF_BIT | nodes[c].offset : c; };
-    std::vector<WideNode> recs;
-    uint32_t wide_entry = 0;
-    if (wide && !rtw::build_wide_bvh(nodes, nn, rtw::RT_WIDE_SAH, recs, wide_entry)) return "the tree does not qualify for the 4-wide layout";
+    walk::HostTree tree;
+    if (const char* why = tree.prepare(nodes, nn, n_tris, wide)) return why;
     const float INF = __builtin_inff();
 
     for (uint32_t i = 0; i < n; ++i)
@@ -117,14 +92,7 @@ const char* walk_points(const rt_bvh_node* nodes, uint32_t nn, const rt_triangle
         uint32_t count = 0u;
         struct Entry { uint32_t ref; float d2; } stack[RT_W4_STACK_MAX];
         int sp = 0;
-        uint32_t ref = RT_IDLE_REF;
-        if (wide) ref = wide_entry;
-        else
-        {
-            // the super-root record: child 0 = (the root's box, the root), child 1 empty
-            const float lo[3] = {nodes[0].bounds_min.x, nodes[0].bounds_min.y, nodes[0].bounds_min.z}, hi[3] = {nodes[0].bounds_max.x, nodes[0].bounds_max.y, nodes[0].bounds_max.z};
-            if (!(nearest_box_d2(p, lo, hi) > best)) ref = node_ref(0);
-        }
+        uint32_t ref = tree.entry([&](const float (&lo)[3], const float (&hi)[3]) { return !(nearest_box_d2(p, lo, hi) > best); });
         auto pop = [&]()
         {
             ref = RT_IDLE_REF;
@@ -145,47 +113,17 @@ const char* walk_points(const rt_bvh_node* nodes, uint32_t nn, const rt_triangle
                 const NpTriangle t = nearest_point_triangle(p, p1, p2, p3);
                 ++count;
                 best = triangle(i, prim, t, best);
-                if (last[prim]) pop();
+                if (tree.last[prim]) pop();
                 else ref = RT_LEAF_BIT | (prim + 1u);
                 continue;
             }
-            uint32_t r[4] = {RT_EMPTY_REF, RT_EMPTY_REF, RT_EMPTY_REF, RT_EMPTY_REF};
-            float e[4] = {INF, INF, INF, INF};
-            if (wide)
-            {
-                if (ref >= recs.size()) return "a record reference lies outside the 4-wide tree";
-                const WideNode& w = recs[ref];
-                const float origin[3] = {w.ox, w.oy, w.oz};
-                float cell[3];
-                for (int a = 0; a < 3; ++a) { const uint32_t bits = ((w.meta >> (8 * a)) & 0xFFu) << 23; memcpy(&cell[a], &bits, 4); }
-                for (int k = 0; k < 4; ++k)
-                {
-                    float lo[3], hi[3];
-                    for (int a = 0; a < 3; ++a)
-                    {
-                        lo[a] = (float)((w.lo[a] >> (8 * k)) & 0xFFu) * cell[a] + origin[a];
-                        hi[a] = (float)((w.hi[a] >> (8 * k)) & 0xFFu) * cell[a] + origin[a];
-                    }
-                    r[k] = w.ref[k];
-                    e[k] = nearest_box_d2(p, lo, hi);
-                }
-            }
-            else
-            {
-                const uint32_t c[2] = {ref + 1u, nodes[ref].offset};
-                for (int k = 0; k < 2; ++k)
-                {
-                    const rt_bvh_node& b = nodes[c[k]];
-                    const float lo[3] = {b.bounds_min.x, b.bounds_min.y, b.bounds_min.z}, hi[3] = {b.bounds_max.x, b.bounds_max.y, b.bounds_max.z};
-                    r[k] = node_ref(c[k]);
-                    e[k] = nearest_box_d2(p, lo, hi);
-                }
-            }
+            uint32_t r[4];
+            float lo[4][3], hi[4][3], e[4];
+            if (const char* why = tree.slots(ref, r, lo, hi)) return why;
             for (int k = 0; k < 4; ++k)
             {
-                const bool pass = r[k] != RT_EMPTY_REF && !(e[k] > best);
-                r[k] = pass ? r[k] : RT_EMPTY_REF;
-                e[k] = pass ? e[k] : INF;
+                e[k] = r[k] != RT_EMPTY_REF ? nearest_box_d2(p, lo[k], hi[k]) : INF;
+                if (e[k] > best) { r[k] = RT_EMPTY_REF; e[k] = INF; }
             }
             auto exchange = [&](int a, int b)
             {

@@ -5,18 +5,15 @@
 //   k_nearest_brute    one lane per point over ALL triangles of an rt_triangle array (rt_debug_nearest's device form: the same nearest.h with no tree)
 //   k_nearest_surface  one lane per point: rt_surface (64 bytes) of the nearest point, by query.h's query_surface
 //
-// The walk.  k_query_trace's fused one-loop shape on walk_kernels.h's Stack (the box step, walk::point_box_step, is this kernel's and k_within's): a lane's point is at a
-// reference -- a 4-wide record (WIDE), a child-pair record (!WIDE), or a triangle of a leaf -- and every pass of the one loop fetches the lane's next 64 bytes
-// with the same four 16-byte loads and takes its step.  What differs from a ray's walk is the test and the order: a box is passed when !(nearest_box_d2 > best),
+// The walk: walk_kernels.h's volume_step (the fetch, the leaf chain, the `last` rule) with walk::point_box_step at a box record.  What differs from a ray's
+// walk is the test and the order: a box is passed when !(nearest_box_d2 > best),
 // the nearest passing box is visited next, and the others wait on the stack with their nearest_box_d2 as the entry value, farthest deepest; a pop re-tests
 // !(entry > best).  nearest_box_d2 <= d2 holds in binary32 itself for every box that holds a triangle's corners (nearest.h), so no order, no fold and no
 // quantisation of a box can change the result: it is the brute-force minimum bit for bit.
 //   * a 4-wide record: the four slots' boxes are origin + q * cell, exactly representable (wide_quant.h: wide_frame keeps the grid in binary32's reach,
 //     wide_quantise rounds outward), so the bound applies to them as to any box; RT_EMPTY_REF slots are skipped.
 //   * a child-pair record: the two children's exact boxes, the same step with two candidates.
-//   * a leaf: its triangles in array order until the `last` flag.  The corners come from the 128-byte SHADING record (its first 64 bytes: p1, p2, p3 and a
-//     normal that is not used): the 64-byte trace record holds p1 and the rounded edges p2 - p1, p3 - p1, from which p2 and p3 cannot be had bit for bit.  The
-//     trace record is read for its `last` flag alone (one dword, issued with the four loads).  The leaf's exact box in the trace record is not tested again:
+//   * a leaf: its triangles in array order.  The leaf's exact box in the trace record is not tested again:
 //     a slot's box is that box rounded outward by less than a cell, and the test would cost every leaf a pass of its own.
 //   * a point that is not searched (nearest.h) is not walked.  Points far outside the scene need no special walk: the gaps stay finite or overflow to +inf on
 //     both sides of every comparison.
@@ -40,9 +37,6 @@ __global__ __launch_bounds__(64) void k_nearest(DScene sc, const float4* __restr
     __shared__ walk::StackLds lds;
     walk::Stack stack(lds, spill);
     const uint32_t lane = threadIdx.x;
-    const char* const node_base = reinterpret_cast<const char*>(WIDE ? sc.wnodes : sc.nodes);
-    const char* const tri_base = reinterpret_cast<const char*>(sc.tris_sh);
-    const float* const flag_base = reinterpret_cast<const float*>(sc.tris_rt);
     const uint32_t n_chunks = (n >> 6) + ((n & 63u) != 0u ? 1u : 0u);
 
     for (uint32_t chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x)
@@ -63,29 +57,15 @@ __global__ __launch_bounds__(64) void k_nearest(DScene sc, const float4* __restr
             }
         }
 
-        auto pop = [&]() { ref = stack.pop([&](float entry) { return !(entry > best); }); };
-
-        while (__ballot(ref != RT_IDLE_REF) != 0ull)
+        auto leaf = [&](uint32_t prim, const float (&p1)[3], const float (&p2)[3], const float (&p3)[3])
         {
-            if (ref != RT_IDLE_REF)
-            {
-                const bool at_leaf = (int)ref < -1;
-                const uint32_t prim = ref & ~RT_LEAF_BIT;
-                float last = 0.0f;
-                if (at_leaf) last = flag_base[((size_t)prim << 4) + 3u];
-                const float4* rp = reinterpret_cast<const float4*>(at_leaf ? tri_base + ((size_t)prim << 7) : node_base + ((size_t)ref << 6));
-                const float4 q0 = rp[0], q1 = rp[1], q2 = rp[2], q3 = rp[3];
-                if (at_leaf)
-                {
-                    const float p1[3] = {q0.x, q0.y, q0.z}, p2[3] = {q1.x, q1.y, q1.z}, p3[3] = {q2.x, q2.y, q2.z};
-                    const NpTriangle t = nearest_point_triangle(p, p1, p2, p3);
-                    if (nearest_accepts(t.d2, prim, best, best_prim)) { best = t.d2; best_prim = prim; }
-                    if (last != 0.0f) pop();
-                    else ref = RT_LEAF_BIT | (prim + 1u);
-                }
-                else walk::point_box_step<WIDE>(q0, q1, q2, q3, p, best, ref, stack);
-            }
-        }
+            const NpTriangle t = nearest_point_triangle(p, p1, p2, p3);
+            if (nearest_accepts(t.d2, prim, best, best_prim)) { best = t.d2; best_prim = prim; }
+        };
+        auto box = [&](float4 q0, float4 q1, float4 q2, float4 q3) { walk::point_box_step<WIDE>(q0, q1, q2, q3, p, best, ref, stack); };
+        auto keep = [&](float entry) { return !(entry > best); };
+        while (__ballot(ref != RT_IDLE_REF) != 0ull)
+            if (ref != RT_IDLE_REF) walk::volume_step<WIDE>(sc, ref, stack, leaf, box, keep);
 
         if (i < n)
         {
@@ -137,17 +117,6 @@ __global__ __launch_bounds__(256) void k_nearest_surface(const float4* __restric
     const float4* __restrict__ points, const float4* found, uint32_t found_stride, uint32_t n, float4* out)
 {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    if (i >= n) return;
-    const float4 f0 = found[(size_t)i * found_stride], f1 = found[(size_t)i * found_stride + 1];
-    const uint32_t prim = __float_as_uint(f1.z);
-    rt_surface s = qs_miss();
-    if (prim < n_tris)                                           // RT_INVALID_ID (nothing found) is above every count
-    {
-        const QsTriangle t = walk::read_shading_triangle(tris, prim);
-        const float4 pt = points[i];
-        const float d[3] = {f0.x - pt.x, f0.y - pt.y, f0.z - pt.z};          // q - p: the direction from the point to the surface
-        s = query_surface(t, d, f1.x, f1.y, f0.w, prim, object_of_triangle ? object_of_triangle[prim] : RT_INVALID_ID);
-    }
-    walk::store_surface(out + (size_t)i * 4, s);
+    if (i < n) walk::point_surface(tris, n_tris, object_of_triangle, points + i, found, found_stride, i, out);
 }
 } // namespace nearest

@@ -63,17 +63,6 @@ __global__ __launch_bounds__(256) void k_query_surface(const float4* __restrict_
     const float4* __restrict__ rays, const float4* hits, uint32_t hit_stride, uint32_t n, float4* out)
 {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    if (i >= n) return;
-    const float4 hit = hits[(size_t)i * hit_stride];
-    const uint32_t prim = __float_as_uint(hit.z);
-    rt_surface s = qs_miss();
-    if (prim < n_tris)                                           // RT_INVALID_ID (a miss) is above every count
-    {
-        const QsTriangle t = RECORDS ? walk::read_shading_triangle(tris, prim) : qs_triangle(reinterpret_cast<const rt_triangle*>(tris)[prim]);
-        const float4 rd = rays[2 * (size_t)i + 1];
-        const float d[3] = {rd.x, rd.y, rd.z};
-        s = query_surface(t, d, hit.x, hit.y, hit.w, prim, object_of_triangle ? object_of_triangle[prim] : RT_INVALID_ID);
-    }
-    walk::store_surface(out + (size_t)i * 4, s);
+    if (i < n) walk::ray_surface<RECORDS>(tris, n_tris, object_of_triangle, rays + 2 * (size_t)i, hits, hit_stride, i, out);
 }
 } // namespace query

@@ -3,13 +3,11 @@
 // force and walk over the same rule (region.h).  A translation unit and a code object of its own so that the hot path's code object (rt_hip.hip,
 // codeobj.code_object_sha256) does not change.  -ffp-contract=off like every other unit.
 #include <hip/hip_runtime.h>
-#include <string.h>
-#include <thread>
 #include <vector>
 #include "rt_hip.h"
 #include "region_kernels.h"
 #include "region_host.h"
-#include "wide_bvh.h"
+#include "walk_host.h"
 
 namespace region
 {
@@ -87,40 +85,31 @@ static void write_region(const rt_triangle* tris, const rt_region& g, uint32_t c
     *out = region_record(count, inside, max_list, searched);
 }
 
-static void brute_range(const rt_triangle* tris, uint32_t n_tris, const rt_region* regions, uint32_t first, uint32_t end, uint32_t max_list, rt_region_hits* out,
-    rt_region_member* members)
-{
-    for (uint32_t i = first; i < end; ++i)
-    {
-        const rt_region& g = regions[i];
-        const bool searched = region_searched(g.num_planes, &g.planes[0][0]);
-        uint32_t count = 0u, inside = 0u;
-        RgList list;
-        rg_list_clear(list, max_list);
-        float p1[3], p2[3], p3[3];
-        if (searched)
-            for (uint32_t t = 0; t < n_tris; ++t)
-            {
-                walk::triangle_corners(tris[t], p1, p2, p3);
-                const uint32_t cls = region_classify(g.num_planes, &g.planes[0][0], p1, p2, p3);
-                if (cls == RT_REGION_REJECTED) continue;
-                ++count;
-                inside += cls & RT_REGION_MEMBER_INSIDE;
-                rg_list_insert(list, t);
-            }
-        write_region(tris, g, count, inside, list, max_list, searched, out + i, members + (size_t)i * max_list);
-    }
-}
-
 void brute_host(const rt_triangle* tris, uint32_t n_tris, const rt_region* regions, uint32_t n, uint32_t max_list, rt_region_hits* out, rt_region_member* members)
 {
-    // every region is on its own: above a million pairs the regions are shared out among up to 16 threads (no result depends on it)
-    const uint32_t threads = (uint64_t)n * n_tris < (1u << 20) ? 1u : (n < 16u ? n : 16u);
-    if (threads <= 1u) { brute_range(tris, n_tris, regions, 0u, n, max_list, out, members); return; }
-    std::vector<std::thread> pool;
-    for (uint32_t t = 0; t < threads; ++t)
-        pool.emplace_back(brute_range, tris, n_tris, regions, (uint32_t)((uint64_t)n * t / threads), (uint32_t)((uint64_t)n * (t + 1u) / threads), max_list, out, members);
-    for (std::thread& t : pool) t.join();
+    walk::split_range(n, (uint64_t)n * n_tris, [&](uint32_t first, uint32_t end)
+    {
+        for (uint32_t i = first; i < end; ++i)
+        {
+            const rt_region& g = regions[i];
+            const bool searched = region_searched(g.num_planes, &g.planes[0][0]);
+            uint32_t count = 0u, inside = 0u;
+            RgList list;
+            rg_list_clear(list, max_list);
+            float p1[3], p2[3], p3[3];
+            if (searched)
+                for (uint32_t t = 0; t < n_tris; ++t)
+                {
+                    walk::triangle_corners(tris[t], p1, p2, p3);
+                    const uint32_t cls = region_classify(g.num_planes, &g.planes[0][0], p1, p2, p3);
+                    if (cls == RT_REGION_REJECTED) continue;
+                    ++count;
+                    inside += cls & RT_REGION_MEMBER_INSIDE;
+                    rg_list_insert(list, t);
+                }
+            write_region(tris, g, count, inside, list, max_list, searched, out + i, members + (size_t)i * max_list);
+        }
+    });
 }
 
 bool brute_device(hipStream_t stream, const rt_triangle* tris, uint32_t n_tris, const rt_region* regions, uint32_t n, uint32_t max_list, rt_region_hits* out,
@@ -143,22 +132,8 @@ bool brute_device(hipStream_t stream, const rt_triangle* tris, uint32_t n_tris, 
 const char* walk_host(const rt_bvh_node* nodes, uint32_t nn, const rt_triangle* tris, uint32_t n_tris, bool wide, const rt_region* regions, uint32_t n,
     uint32_t max_list, rt_region_hits* out, rt_region_member* members, uint32_t* tested)
 {
-    // nearest::walk_points' preparation: the `last` flags of the trace records, the child-pair form's references, the 4-wide records
-    std::vector<uint8_t> last(n_tris, 0);
-    for (uint32_t i = 0; i < nn; ++i)
-    {
-        const uint32_t np = nodes[i].num_primitives_axis >> 16;
-        if (np > 0u)
-        {
-            if ((uint64_t)nodes[i].offset + np > n_tris) return "a leaf's triangles lie outside the array";
-            last[nodes[i].offset + np - 1u] = 1;
-        }
-        else if (i + 1u >= nn || nodes[i].offset <= i || nodes[i].offset >= nn) return "an interior node's children lie outside the array";
-    }
-    auto node_ref = [&](uint32_t c) { return (nodes[c].num_primitives_axis >> 16) != 0u ? RT_LEAF_BIT | nodes[c].offset : c; };
-    std::vector<WideNode> recs;
-    uint32_t wide_entry = 0;
-    if (wide && !rtw::build_wide_bvh(nodes, nn, rtw::RT_WIDE_SAH, recs, wide_entry)) return "the tree does not qualify for the 4-wide layout";
+    walk::HostTree tree;
+    if (const char* why = tree.prepare(nodes, nn, n_tris, wide)) return why;
 
     for (uint32_t i = 0; i < n; ++i)
     {
@@ -168,24 +143,14 @@ const char* walk_host(const rt_bvh_node* nodes, uint32_t nn, const rt_triangle* 
         uint32_t count = 0u, inside = 0u, visited = 0u;
         RgList list;
         rg_list_clear(list, max_list);
-        auto box_passes = [&](const float lo[3], const float hi[3])
+        auto box_passes = [&](const float (&lo)[3], const float (&hi)[3])
         {
             for (uint32_t k = 0; k < g.num_planes; ++k) if (region_plane_rejects_box(planes + 4u * k, lo, hi)) return false;
             return true;
         };
         uint32_t stack[RT_W4_STACK_MAX];
         int sp = 0;
-        uint32_t ref = RT_IDLE_REF;
-        if (searched)
-        {
-            if (wide) ref = wide_entry;
-            else
-            {
-                // the super-root record: child 0 = (the root's box, the root), child 1 empty
-                const float lo[3] = {nodes[0].bounds_min.x, nodes[0].bounds_min.y, nodes[0].bounds_min.z}, hi[3] = {nodes[0].bounds_max.x, nodes[0].bounds_max.y, nodes[0].bounds_max.z};
-                if (box_passes(lo, hi)) ref = node_ref(0);
-            }
-        }
+        uint32_t ref = searched ? tree.entry(box_passes) : RT_IDLE_REF;
         float p1[3], p2[3], p3[3];
         while (ref != RT_IDLE_REF)
         {
@@ -202,42 +167,15 @@ const char* walk_host(const rt_bvh_node* nodes, uint32_t nn, const rt_triangle* 
                     inside += cls & RT_REGION_MEMBER_INSIDE;
                     rg_list_insert(list, prim);
                 }
-                if (last[prim]) ref = sp > 0 ? stack[--sp] : RT_IDLE_REF;
+                if (tree.last[prim]) ref = sp > 0 ? stack[--sp] : RT_IDLE_REF;
                 else ref = RT_LEAF_BIT | (prim + 1u);
                 continue;
             }
-            uint32_t r[4] = {RT_EMPTY_REF, RT_EMPTY_REF, RT_EMPTY_REF, RT_EMPTY_REF};
-            bool pass[4] = {false, false, false, false};
-            if (wide)
-            {
-                if (ref >= recs.size()) return "a record reference lies outside the 4-wide tree";
-                const WideNode& w = recs[ref];
-                const float origin[3] = {w.ox, w.oy, w.oz};
-                float cell[3];
-                for (int a = 0; a < 3; ++a) { const uint32_t bits = ((w.meta >> (8 * a)) & 0xFFu) << 23; memcpy(&cell[a], &bits, 4); }
-                for (int k = 0; k < 4; ++k)
-                {
-                    float lo[3], hi[3];
-                    for (int a = 0; a < 3; ++a)
-                    {
-                        lo[a] = (float)((w.lo[a] >> (8 * k)) & 0xFFu) * cell[a] + origin[a];
-                        hi[a] = (float)((w.hi[a] >> (8 * k)) & 0xFFu) * cell[a] + origin[a];
-                    }
-                    r[k] = w.ref[k];
-                    pass[k] = r[k] != RT_EMPTY_REF && box_passes(lo, hi);
-                }
-            }
-            else
-            {
-                const uint32_t c[2] = {ref + 1u, nodes[ref].offset};
-                for (int k = 0; k < 2; ++k)
-                {
-                    const rt_bvh_node& b = nodes[c[k]];
-                    const float lo[3] = {b.bounds_min.x, b.bounds_min.y, b.bounds_min.z}, hi[3] = {b.bounds_max.x, b.bounds_max.y, b.bounds_max.z};
-                    r[k] = node_ref(c[k]);
-                    pass[k] = box_passes(lo, hi);
-                }
-            }
+            uint32_t r[4];
+            float lo[4][3], hi[4][3];
+            if (const char* why = tree.slots(ref, r, lo, hi)) return why;
+            bool pass[4];
+            for (int k = 0; k < 4; ++k) pass[k] = r[k] != RT_EMPTY_REF && box_passes(lo[k], hi[k]);
             // walk::region_box_step: every passing slot but one is pushed, that one is visited next
             uint32_t next = RT_IDLE_REF;
             for (int k = 3; k >= 0; --k)

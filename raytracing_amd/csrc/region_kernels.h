@@ -7,9 +7,10 @@
 //   k_select               one lane per TRIANGLE against up to 32 regions: a bit per region in a word per triangle, ORed into a word per object
 //   k_select_finish        one lane per object: object_inside from what k_select gathered
 //
-// The walk is k_within's (within_kernels.h): the same fetch of 64 bytes per pass, the same leaf step's loads, persistent strided chunks of 64 regions,
-// walk::Stack in the ray queries' spill area -- with walk::region_box_step at a box record, which needs no key and no sort: a counting walk visits every
-// passing child, and its pop always accepts.  The lane's planes live in LDS (walk::RegionLds, 8 KiB per block beside the stack's 6 KiB): a lane writes its
+// The walk is walk_kernels.h's volume walk (persistent strided chunks of 64 regions, walk::Stack in the ray queries' spill area) with walk::region_box_step at
+// a box record, which needs no key and no sort: a counting walk visits every passing child, and its pop always accepts.  The fetch and the leaf chain are
+// written out here, word for word walk::volume_step's: on that step the LIST kernels measured 1.4 to 4 % slower at unchanged registers (DESIGN.md section
+// 7m, "the volume walks on one step"), so this one loop stays until that is understood.  A rule changed in volume_step is changed here too.  The lane's planes live in LDS (walk::RegionLds, 8 KiB per block beside the stack's 6 KiB): a lane writes its
 // own column at the chunk's start and reads only that, so there is no barrier.  A region that is not searched is never walked.
 //
 // LIST = false keeps `count` and `inside`.  LIST = true also keeps an RgList (region.h): 8 registers of ids, right-aligned, the flags not kept; after the

@@ -4,8 +4,12 @@
 //
 //   Stack          a lane's traversal stack: push, and a pop that takes the walk's re-test
 //   Ray, ray_setup a ray as its walk needs it: 1/dir, the sign bits, the octant, and which records it walks
+//   volume_step    one pass of a walk that is no ray's (a point's: k_nearest, k_within): the fetch of the record, the leaf chain and the `last` rule; what a
+//                  triangle and a box record do to the walk are the caller's functors (k_region keeps a copy of it: region_kernels.h says why)
+//   decode_slots   a box record's references and boxes: the four quantised slots of a 4-wide record or the two children of a child-pair record
 //   point_box_step one pass of a point's walk (nearest, within) at a box record: the slots keyed by nearest_box_d2, nearest first
 //   region_box_step one pass of a region's walk (overlap) at a box record: every slot region.h's box test passes is visited, in no particular order
+//   point_surface, ray_surface   the rt_surface of one found record (a nearest point, a hit): the body of the four surface kernels
 //   ray_step       one pass of a ray's fused loop: the fetch of one 64-byte record and its leaf, child-pair or 4-wide step; what an accepted triangle does
 //                  to the walk is the step's mode (closest, any hit, all hits)
 //   read_shading_triangle, store_surface, store_nearest, triangle_corners   the records' readers and writers
@@ -229,16 +233,39 @@ RT_DEV bool ray_step(const DScene& sc, const Ray& ray, const float t_min, float&
     return accepted;
 }
 
-// One pass of a point's walk at a box record (q0 .. q3 = its 64 bytes): the four slots of a 4-wide record or the two children of a child-pair record, each
-// keyed by nearest_box_d2; those that pass !(key > best) ascending by key, the nearest visited next, the others pushed farthest deepest; none: a pop that
-// re-tests !(entry > best).  k_nearest's (nearest_kernels.h) and k_within's (within_kernels.h) step alike: `best` is whatever bound the caller's walk prunes by.
-template <bool WIDE>
-RT_DEV void point_box_step(const float4 q0, const float4 q1, const float4 q2, const float4 q3, const float (&p)[3], const float best, uint32_t& ref, Stack& stack)
+// One pass of a volume walk -- a point's or a region's descent, not a ray's -- for a lane whose `ref` is not RT_IDLE_REF: a 4-wide record (WIDE), a child-pair
+// record (!WIDE), or a triangle of a leaf, fetched with the same four 16-byte loads whichever it is.  At a leaf: leaf(prim, p1, p2, p3) with the corners of the
+// 128-byte SHADING record (its first 64 bytes; the 64-byte trace record holds the rounded edges, from which p2 and p3 cannot be had bit for bit, and is read for
+// its `last` flag alone, one dword issued with the four loads), then the leaf chain: the next triangle in array order, or after the `last` one a pop that
+// re-tests keep(entry) -- evaluated after leaf, so a bound the leaf has just lowered is the one that prunes.  At a box record: box(q0, q1, q2, q3), which sets
+// `ref` (point_box_step, region_box_step).  (The bases are read from the kernel's argument here, as ray_step reads them.)
+template <bool WIDE, class Leaf, class Box, class Keep>
+RT_DEV void volume_step(const DScene& sc, uint32_t& ref, Stack& stack, Leaf&& leaf, Box&& box, Keep&& keep)
 {
-    const float INF = __builtin_inff();
-    uint32_t r[4];
-    float e[4];
-    if (WIDE)
+    const bool at_leaf = (int)ref < -1;
+    const uint32_t prim = ref & ~RT_LEAF_BIT;
+    float last = 0.0f;
+    if (at_leaf) last = reinterpret_cast<const float*>(sc.tris_rt)[((size_t)prim << 4) + 3u];
+    const float4* rp = reinterpret_cast<const float4*>(at_leaf ? reinterpret_cast<const char*>(sc.tris_sh) + ((size_t)prim << 7)
+                                                               : reinterpret_cast<const char*>(WIDE ? sc.wnodes : sc.nodes) + ((size_t)ref << 6));
+    const float4 q0 = rp[0], q1 = rp[1], q2 = rp[2], q3 = rp[3];
+    if (at_leaf)
+    {
+        const float p1[3] = {q0.x, q0.y, q0.z}, p2[3] = {q1.x, q1.y, q1.z}, p3[3] = {q2.x, q2.y, q2.z};
+        leaf(prim, p1, p2, p3);
+        if (last != 0.0f) ref = stack.pop(keep);
+        else ref = RT_LEAF_BIT | (prim + 1u);
+    }
+    else box(q0, q1, q2, q3);
+}
+
+// A box record's (q0 .. q3 = its 64 bytes) references and boxes: the four slots of a 4-wide record, origin + q * cell, or the two children of a child-pair
+// record.  An empty slot has the reference RT_EMPTY_REF.
+template <bool WIDE>
+RT_DEV void decode_slots(const float4 q0, const float4 q1, const float4 q2, const float4 q3, uint32_t (&r)[WIDE ? 4 : 2], float (&lo)[WIDE ? 4 : 2][3],
+    float (&hi)[WIDE ? 4 : 2][3])
+{
+    if constexpr (WIDE)
     {
         const uint32_t meta = __float_as_uint(q0.w);
         const float cell[3] = {__uint_as_float((meta & 0xFFu) << 23), __uint_as_float(((meta >> 8) & 0xFFu) << 23), __uint_as_float(((meta >> 16) & 0xFFu) << 23)};
@@ -248,30 +275,40 @@ RT_DEV void point_box_step(const float4 q0, const float4 q1, const float4 q2, co
         r[0] = __float_as_uint(q2.z); r[1] = __float_as_uint(q2.w); r[2] = __float_as_uint(q3.x); r[3] = __float_as_uint(q3.y);
 #pragma unroll
         for (int k = 0; k < 4; ++k)
-        {
-            float lo[3], hi[3];
 #pragma unroll
             for (int a = 0; a < 3; ++a)
             {
-                lo[a] = (float)((low[a] >> (8 * k)) & 0xFFu) * cell[a] + origin[a];       // exact (wide_frame)
-                hi[a] = (float)((high[a] >> (8 * k)) & 0xFFu) * cell[a] + origin[a];
+                lo[k][a] = (float)((low[a] >> (8 * k)) & 0xFFu) * cell[a] + origin[a];       // exact (wide_frame)
+                hi[k][a] = (float)((high[a] >> (8 * k)) & 0xFFu) * cell[a] + origin[a];
             }
-            e[k] = nearest_box_d2(p, lo, hi);
-        }
     }
     else
     {
-        const float lo0[3] = {q0.x, q0.y, q2.x}, hi0[3] = {q0.z, q0.w, q2.y}, lo1[3] = {q1.x, q1.y, q2.z}, hi1[3] = {q1.z, q1.w, q2.w};
-        r[0] = __float_as_uint(q3.x); r[1] = __float_as_uint(q3.y); r[2] = RT_EMPTY_REF; r[3] = RT_EMPTY_REF;
-        e[0] = nearest_box_d2(p, lo0, hi0); e[1] = nearest_box_d2(p, lo1, hi1); e[2] = INF; e[3] = INF;
+        lo[0][0] = q0.x; lo[0][1] = q0.y; lo[0][2] = q2.x; hi[0][0] = q0.z; hi[0][1] = q0.w; hi[0][2] = q2.y;
+        lo[1][0] = q1.x; lo[1][1] = q1.y; lo[1][2] = q2.z; hi[1][0] = q1.z; hi[1][1] = q1.w; hi[1][2] = q2.w;
+        r[0] = __float_as_uint(q3.x); r[1] = __float_as_uint(q3.y);
     }
+}
+
+// One pass of a point's walk at a box record: its slots (decode_slots), each keyed by nearest_box_d2; those that pass !(key > best) ascending by key, the
+// nearest visited next, the others pushed farthest deepest; none: a pop that re-tests !(entry > best).
+//k_nearest's (nearest_kernels.h) and k_within's (within_kernels.h) step alike: `best` is whatever bound the caller's walk prunes by.
+template <bool WIDE>
+RT_DEV void point_box_step(const float4 q0, const float4 q1, const float4 q2, const float4 q3, const float (&p)[3], const float best, uint32_t& ref, Stack& stack)
+{
+    constexpr int N = WIDE ? 4 : 2;
+    const float INF = __builtin_inff();
+    uint32_t rn[N], r[4] = {RT_EMPTY_REF, RT_EMPTY_REF, RT_EMPTY_REF, RT_EMPTY_REF};
+    float lo[N][3], hi[N][3], e[4] = {INF, INF, INF, INF};
+    decode_slots<WIDE>(q0, q1, q2, q3, rn, lo, hi);
     // a slot that is empty or too far leaves the step: marked by RT_EMPTY_REF, keyed +inf
 #pragma unroll
-    for (int k = 0; k < 4; ++k)
+    for (int k = 0; k < N; ++k)
     {
-        const bool pass = r[k] != RT_EMPTY_REF && !(e[k] > best);
-        r[k] = pass ? r[k] : RT_EMPTY_REF;
-        e[k] = pass ? e[k] : INF;
+        const float key = nearest_box_d2(p, lo[k], hi[k]);
+        const bool pass = rn[k] != RT_EMPTY_REF && !(key > best);
+        r[k] = pass ? rn[k] : RT_EMPTY_REF;
+        e[k] = pass ? key : INF;
     }
     // ascending by nearest_box_d2 (five exchanges; two candidates need the first only)
     auto exchange = [&](int a, int b)
@@ -300,9 +337,8 @@ RT_DEV void point_box_step(const float4 q0, const float4 q1, const float4 q2, co
 // num_planes would index them per lane -- scratch; a lane reads its own column only, so no barrier is needed.
 typedef float4 RegionLds[RT_REGION_MAX_PLANES][64];          // a kernel declares one, __shared__
 
-// One pass of a region's walk at a box record (q0 .. q3 = its 64 bytes): the four slots of a 4-wide record or the two children of a child-pair record, decoded
-// as point_box_step decodes them, each tested against the lane's planes (region.h's box test).  A counting walk visits every passing slot, so there is no
-// key and no sort: all passing slots but one are pushed, that one is visited next; none: a pop, which always accepts.
+// One pass of a region's walk at a box record: its slots (decode_slots), each tested against the lane's planes (region.h's box test).  A counting walk
+// visits every passing slot, so there is no key and no sort: all passing slots but one are pushed, that one is visited next; none: a pop, which always accepts.
 template <bool WIDE>
 RT_DEV void region_box_step(const float4 q0, const float4 q1, const float4 q2, const float4 q3, const RegionLds& planes, const uint32_t num_planes, uint32_t& ref,
     Stack& stack)
@@ -310,32 +346,7 @@ RT_DEV void region_box_step(const float4 q0, const float4 q1, const float4 q2, c
     constexpr int N = WIDE ? 4 : 2;
     uint32_t r[N];
     float lo[N][3], hi[N][3];
-    if (WIDE)
-    {
-        const uint32_t meta = __float_as_uint(q0.w);
-        const float cell[3] = {__uint_as_float((meta & 0xFFu) << 23), __uint_as_float(((meta >> 8) & 0xFFu) << 23), __uint_as_float(((meta >> 16) & 0xFFu) << 23)};
-        const float origin[3] = {q0.x, q0.y, q0.z};
-        const uint32_t low[3] = {__float_as_uint(q1.x), __float_as_uint(q1.y), __float_as_uint(q1.z)};
-        const uint32_t high[3] = {__float_as_uint(q1.w), __float_as_uint(q2.x), __float_as_uint(q2.y)};
-        const uint32_t refs[4] = {__float_as_uint(q2.z), __float_as_uint(q2.w), __float_as_uint(q3.x), __float_as_uint(q3.y)};
-#pragma unroll
-        for (int k = 0; k < N; ++k)
-        {
-            r[k] = refs[k];
-#pragma unroll
-            for (int a = 0; a < 3; ++a)
-            {
-                lo[k][a] = (float)((low[a] >> (8 * k)) & 0xFFu) * cell[a] + origin[a];       // exact (wide_frame)
-                hi[k][a] = (float)((high[a] >> (8 * k)) & 0xFFu) * cell[a] + origin[a];
-            }
-        }
-    }
-    else
-    {
-        lo[0][0] = q0.x; lo[0][1] = q0.y; lo[0][2] = q2.x; hi[0][0] = q0.z; hi[0][1] = q0.w; hi[0][2] = q2.y;
-        lo[1][0] = q1.x; lo[1][1] = q1.y; lo[1][2] = q2.z; hi[1][0] = q1.z; hi[1][1] = q1.w; hi[1][2] = q2.w;
-        r[0] = __float_as_uint(q3.x); r[1] = __float_as_uint(q3.y);
-    }
+    decode_slots<WIDE>(q0, q1, q2, q3, r, lo, hi);
     bool pass[N];
 #pragma unroll
     for (int k = 0; k < N; ++k) pass[k] = r[k] != RT_EMPTY_REF;
@@ -378,6 +389,43 @@ RT_DEV void store_surface(float4* o, const rt_surface& s)
     o[1] = make_float4(s.geometric_normal[0], s.geometric_normal[1], s.geometric_normal[2], __uint_as_float(s.mtl_index));
     o[2] = make_float4(s.shading_normal[0], s.shading_normal[1], s.shading_normal[2], __uint_as_float(s.object));
     o[3] = make_float4(s.texcoord[0], s.texcoord[1], s.t, __uint_as_float(s.flags));
+}
+
+// The rt_surface of found record k -- found[k * found_stride .. + 1], an rt_nearest -- of the point *point, by query.h's query_surface along q - p, the
+// direction from the point to the surface.  The record may be the first 32 bytes of out[k] itself: it is read before out[k] is written.
+RT_DEV void point_surface(const float4* __restrict__ tris, uint32_t n_tris, const uint32_t* __restrict__ object_of_triangle, const float4* __restrict__ point,
+    const float4* found, uint32_t found_stride, size_t k, float4* out)
+{
+    const float4 f0 = found[k * found_stride], f1 = found[k * found_stride + 1];
+    const uint32_t prim = __float_as_uint(f1.z);
+    rt_surface s = qs_miss();
+    if (prim < n_tris)                                           // RT_INVALID_ID (nothing found, no member listed here) is above every count
+    {
+        const QsTriangle t = read_shading_triangle(tris, prim);
+        const float4 pt = *point;
+        const float d[3] = {f0.x - pt.x, f0.y - pt.y, f0.z - pt.z};
+        s = query_surface(t, d, f1.x, f1.y, f0.w, prim, object_of_triangle ? object_of_triangle[prim] : RT_INVALID_ID);
+    }
+    store_surface(out + k * 4, s);
+}
+
+// The same of hit k -- hits[k * hit_stride], an rt_hit -- of the ray at ray[0 .. 1].  RECORDS: `tris` = the scene's 128-byte shading records; otherwise
+// rt_triangle[] (rt_debug_query_surface: they stand in for the records).  The hit may be the first 16 bytes of out[k] itself.
+template <bool RECORDS>
+RT_DEV void ray_surface(const float4* __restrict__ tris, uint32_t n_tris, const uint32_t* __restrict__ object_of_triangle, const float4* __restrict__ ray,
+    const float4* hits, uint32_t hit_stride, size_t k, float4* out)
+{
+    const float4 hit = hits[k * hit_stride];
+    const uint32_t prim = __float_as_uint(hit.z);
+    rt_surface s = qs_miss();
+    if (prim < n_tris)                                           // RT_INVALID_ID (a miss, no hit stored here) is above every count
+    {
+        const QsTriangle t = RECORDS ? read_shading_triangle(tris, prim) : qs_triangle(reinterpret_cast<const rt_triangle*>(tris)[prim]);
+        const float4 rd = ray[1];
+        const float d[3] = {rd.x, rd.y, rd.z};
+        s = query_surface(t, d, hit.x, hit.y, hit.w, prim, object_of_triangle ? object_of_triangle[prim] : RT_INVALID_ID);
+    }
+    store_surface(out + k * 4, s);
 }
 
 // an rt_nearest as two 16-byte pieces, past the cache as q_store does (nothing reads it again on the device before a later launch or the host does)

@@ -3,12 +3,12 @@
 // A translation unit and a code object of its own so that the hot path's code object (rt_hip.hip, codeobj.code_object_sha256) does not change.
 // -ffp-contract=off like every other unit.
 #include <hip/hip_runtime.h>
-#include <thread>
 #include <vector>
 #include "rt_hip.h"
 #include "within_kernels.h"
 #include "within_host.h"
 #include "nearest_host.h"
+#include "walk_host.h"
 
 namespace within
 {
@@ -75,42 +75,33 @@ static void write_point(const rt_triangle* tris, const rt_point& pt, uint32_t co
     *out = within_record(count, max_near, options, list.prim[first], searched);
 }
 
-static void brute_range(const rt_triangle* tris, uint32_t n_tris, const rt_point* points, uint32_t first, uint32_t end, uint32_t max_near, uint32_t options,
-    rt_point_hits* out, rt_nearest* near)
-{
-    for (uint32_t i = first; i < end; ++i)
-    {
-        const float* p = points[i].position;
-        const bool searched = nearest_searched(p, points[i].max_distance);
-        uint32_t count = 0u;
-        WnList list;
-        wn_list_clear(list, max_near);
-        if (searched)
-        {
-            const float r2 = points[i].max_distance * points[i].max_distance;
-            float p1[3], p2[3], p3[3];
-            for (uint32_t t = 0; t < n_tris; ++t)
-            {
-                walk::triangle_corners(tris[t], p1, p2, p3);
-                const NpTriangle c = nearest_point_triangle(p, p1, p2, p3);
-                if (!within_member(c.d2, r2)) continue;
-                ++count;
-                wn_list_insert(list, c.d2, t);
-            }
-        }
-        write_point(tris, points[i], count, list, max_near, options, searched, out + i, near + (size_t)i * max_near);
-    }
-}
-
 void brute_host(const rt_triangle* tris, uint32_t n_tris, const rt_point* points, uint32_t n, uint32_t max_near, uint32_t options, rt_point_hits* out, rt_nearest* near)
 {
-    // every point is on its own: above a million pairs the points are shared out among up to 16 threads (no result depends on it)
-    const uint32_t threads = (uint64_t)n * n_tris < (1u << 20) ? 1u : (n < 16u ? n : 16u);
-    if (threads <= 1u) { brute_range(tris, n_tris, points, 0u, n, max_near, options, out, near); return; }
-    std::vector<std::thread> pool;
-    for (uint32_t t = 0; t < threads; ++t)
-        pool.emplace_back(brute_range, tris, n_tris, points, (uint32_t)((uint64_t)n * t / threads), (uint32_t)((uint64_t)n * (t + 1u) / threads), max_near, options, out, near);
-    for (std::thread& t : pool) t.join();
+    walk::split_range(n, (uint64_t)n * n_tris, [&](uint32_t first, uint32_t end)
+    {
+        for (uint32_t i = first; i < end; ++i)
+        {
+            const float* p = points[i].position;
+            const bool searched = nearest_searched(p, points[i].max_distance);
+            uint32_t count = 0u;
+            WnList list;
+            wn_list_clear(list, max_near);
+            if (searched)
+            {
+                const float r2 = points[i].max_distance * points[i].max_distance;
+                float p1[3], p2[3], p3[3];
+                for (uint32_t t = 0; t < n_tris; ++t)
+                {
+                    walk::triangle_corners(tris[t], p1, p2, p3);
+                    const NpTriangle c = nearest_point_triangle(p, p1, p2, p3);
+                    if (!within_member(c.d2, r2)) continue;
+                    ++count;
+                    wn_list_insert(list, c.d2, t);
+                }
+            }
+            write_point(tris, points[i], count, list, max_near, options, searched, out + i, near + (size_t)i * max_near);
+        }
+    });
 }
 
 bool brute_device(hipStream_t stream, const rt_triangle* tris, uint32_t n_tris, const rt_point* points, uint32_t n, uint32_t max_near, uint32_t options,

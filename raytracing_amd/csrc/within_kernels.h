@@ -6,8 +6,7 @@
 //   k_within_brute              one lane per point over ALL triangles of an rt_triangle array (rt_debug_within's device form: within.h with no tree)
 //   k_within_surface            one lane per (point, listed member): rt_surface (64 bytes) of the member's nearest point, by query.h's query_surface
 //
-// The walk is k_nearest's (nearest_kernels.h): the same fetch of 64 bytes per pass, the same leaf step's loads, and walk::point_box_step at a box record -- with
-// another bound.  k_nearest prunes by the best d2 so far; a counting walk (KNN = false) prunes by r2 and never lowers it, so it reaches every leaf whose box
+// The walk: walk_kernels.h's volume_step with walk::point_box_step at a box record, as k_nearest's (nearest_kernels.h) -- with another bound.  k_nearest prunes by the best d2 so far; a counting walk (KNN = false) prunes by r2 and never lowers it, so it reaches every leaf whose box
 // the sphere touches; a k-nearest walk (KNN = true, 1 <= max_near) prunes by r2 until the list's place max_near - 1 is taken and by that place's d2 from then
 // on.  within.h says why either gives the brute force's members bit for bit, whichever records are walked.
 //
@@ -37,9 +36,6 @@ __global__ __launch_bounds__(64) void k_within(DScene sc, const float4* __restri
     __shared__ walk::StackLds lds;
     walk::Stack stack(lds, spill);
     const uint32_t lane = threadIdx.x;
-    const char* const node_base = reinterpret_cast<const char*>(WIDE ? sc.wnodes : sc.nodes);
-    const char* const tri_base = reinterpret_cast<const char*>(sc.tris_sh);
-    const float* const flag_base = reinterpret_cast<const float*>(sc.tris_rt);
     const uint32_t n_chunks = (n >> 6) + ((n & 63u) != 0u ? 1u : 0u);
 
     for (uint32_t chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x)
@@ -65,37 +61,24 @@ __global__ __launch_bounds__(64) void k_within(DScene sc, const float4* __restri
             }
         }
 
-        while (__ballot(ref != RT_IDLE_REF) != 0ull)
+        auto leaf = [&](uint32_t prim, const float (&p1)[3], const float (&p2)[3], const float (&p3)[3])
         {
-            if (ref != RT_IDLE_REF)
+            const NpTriangle t = nearest_point_triangle(p, p1, p2, p3);
+            if (within_member(t.d2, r2))
             {
-                const float prune = KNN ? bound : r2;
-                const bool at_leaf = (int)ref < -1;
-                const uint32_t prim = ref & ~RT_LEAF_BIT;
-                float last = 0.0f;
-                if (at_leaf) last = flag_base[((size_t)prim << 4) + 3u];
-                const float4* rp = reinterpret_cast<const float4*>(at_leaf ? tri_base + ((size_t)prim << 7) : node_base + ((size_t)ref << 6));
-                const float4 q0 = rp[0], q1 = rp[1], q2 = rp[2], q3 = rp[3];
-                if (at_leaf)
+                ++count;
+                if (LIST)
                 {
-                    const float p1[3] = {q0.x, q0.y, q0.z}, p2[3] = {q1.x, q1.y, q1.z}, p3[3] = {q2.x, q2.y, q2.z};
-                    const NpTriangle t = nearest_point_triangle(p, p1, p2, p3);
-                    if (within_member(t.d2, r2))
-                    {
-                        ++count;
-                        if (LIST)
-                        {
-                            wn_list_insert(list, t.d2, prim);
-                            if (KNN) bound = within_knn_bound(list, r2);
-                        }
-                    }
-                    if (!LIST && nearest_accepts(t.d2, prim, bound, best_prim)) { bound = t.d2; best_prim = prim; }
-                    if (last != 0.0f) { const float b = KNN ? bound : r2; ref = stack.pop([&](float entry) { return !(entry > b); }); }
-                    else ref = RT_LEAF_BIT | (prim + 1u);
+                    wn_list_insert(list, t.d2, prim);
+                    if (KNN) bound = within_knn_bound(list, r2);
                 }
-                else walk::point_box_step<WIDE>(q0, q1, q2, q3, p, prune, ref, stack);
             }
-        }
+            if (!LIST && nearest_accepts(t.d2, prim, bound, best_prim)) { bound = t.d2; best_prim = prim; }
+        };
+        auto box = [&](float4 q0, float4 q1, float4 q2, float4 q3) { walk::point_box_step<WIDE>(q0, q1, q2, q3, p, KNN ? bound : r2, ref, stack); };
+        auto keep = [&](float entry) { return !(entry > (KNN ? bound : r2)); };
+        while (__ballot(ref != RT_IDLE_REF) != 0ull)
+            if (ref != RT_IDLE_REF) walk::volume_step<WIDE>(sc, ref, stack, leaf, box, keep);
 
         if (i < n)
         {
@@ -173,23 +156,12 @@ __global__ __launch_bounds__(256) void k_within_brute(const rt_triangle* __restr
     store_record(out + i, within_record(count, max_near, options, first_prim, searched));
 }
 
-// k_nearest_surface's body with member j of point i reading point i.  found[k * found_stride .. + 1] may be the first 32 bytes of out[k] itself: lane k reads
-// it before it writes.
+// k_nearest_surface's body (walk::point_surface) with member j of point i reading point i.  found[k * found_stride .. + 1] may be the first 32 bytes of
+// out[k] itself: lane k reads it before it writes.
 __global__ __launch_bounds__(256) void k_within_surface(const float4* __restrict__ tris, uint32_t n_tris, const uint32_t* __restrict__ object_of_triangle,
     const float4* __restrict__ points, const float4* found, uint32_t found_stride, uint32_t max_near, unsigned long long total, float4* out)
 {
     const unsigned long long k = (unsigned long long)blockIdx.x * 256u + threadIdx.x;
-    if (k >= total) return;
-    const float4 f0 = found[(size_t)k * found_stride], f1 = found[(size_t)k * found_stride + 1];
-    const uint32_t prim = __float_as_uint(f1.z);
-    rt_surface s = qs_miss();
-    if (prim < n_tris)                                           // RT_INVALID_ID (no member listed here) is above every count
-    {
-        const QsTriangle t = walk::read_shading_triangle(tris, prim);
-        const float4 pt = points[(size_t)(k / max_near)];
-        const float d[3] = {f0.x - pt.x, f0.y - pt.y, f0.z - pt.z};          // q - p: the direction from the point to the surface
-        s = query_surface(t, d, f1.x, f1.y, f0.w, prim, object_of_triangle ? object_of_triangle[prim] : RT_INVALID_ID);
-    }
-    walk::store_surface(out + (size_t)k * 4, s);
+    if (k < total) walk::point_surface(tris, n_tris, object_of_triangle, points + (size_t)(k / max_near), found, found_stride, (size_t)k, out);
 }
 } // namespace within

@@ -1,4 +1,4 @@
-"""-m gpu: the pieces k_query_trace, k_bake and k_nearest share (raytracing_amd/csrc/walk_kernels.h) where no other test names them: a traversal stack that
+"""-m gpu: the pieces k_query_trace, k_bake, k_nearest, k_within and k_region share (raytracing_amd/csrc/walk_kernels.h) where no other test names them: a traversal stack that
 runs past its RT_QUERY_STACK_LDS = 12 entries in LDS into the spill area, lanes alone and in partial waves, and the persistent grid's stride.
 
 The scene is a slab stack: N = 16384 unit quads (32768 triangles) at z = 0, 1, ..., N - 1, corners at integer coordinates, normals along -z, built by the
@@ -10,12 +10,16 @@ refuse to run on less.  N is the smallest power of two that reaches it (N = 8192
   rays     from (0.3, 0.6, -1) along +z; even rays are exactly axis-parallel with their origins shifted sideways (1/dir is not finite: the child-pair walk
            with the select-form box test), odd rays are tilted by i * 2^-24 in x and y (the 4-wide walk when the scene has 4-wide trees)
   nearest  points beside the stack at x = 3 + i / 256, spread over its height, no distance limit
+  within   the nearest walk's points with max_distance = inf: every box passes, so the counting walk (it visits every passing child, pushes the rest and
+           never lowers its bound) leaves one pending child per pair level -- the restatement below measures 14; max_near 0 and 8, and k_nearest at 8
+  overlap  even regions are one box that encloses the whole stack (every box passes: the same 14), odd regions are slabs that cut the stack at varying
+           heights, for verdicts of both kinds; max_list 0 and 8
   bake     even points lie on the first quad with normal (0, 0, -1); the bias is -(N / 2 + 0.5), which puts their origins between two quads in the middle of
            the stack, looking down through N / 2 back faces: a long walk whose every triangle is culled (all unoccluded).  Odd points are this test's own
            addition for verdicts of both kinds: normal (0, 0, +1), placed so that the same bias puts their origins at z = -1 below the first quad.
 
 Everything is compared byte for byte: Context.trace with the oracle as tests/test_gpu_query.py obtains it, Context.nearest with the host's brute force,
-Context.bake with the host's rays, the oracle's verdicts of them and the host's reduction as tests/test_gpu_bake.py does.  After every call rt_finish
+Context.within and Context.overlap with the host's brute force, Context.bake with the host's rays, the oracle's verdicts of them and the host's reduction as tests/test_gpu_bake.py does.  After every call rt_finish
 succeeds: no walk raised the stack's status word.  One process, each GPU step once, nothing retried; nothing here provokes a fault."""
 import numpy as np
 import pytest
@@ -31,6 +35,7 @@ N_QUADS = 16384
 STACK_LDS = 12                         # RT_QUERY_STACK_LDS (walk_kernels.h)
 COUNTS = [1, 63, 64, 65, 130]          # a lone lane, a partial wave, a full wave, a second chunk with one lane, two chunks and a partial third
 DISTINCT = 130
+WITHIN_CASES = [(0, False), (8, False), (8, True)]          # (max_near, k_nearest)
 BAKE_BIAS = -(N_QUADS / 2 + 0.5)
 BAKE_RADIUS = float(N_QUADS)
 
@@ -126,6 +131,25 @@ def nearest_pending_depth(nodes, tris, p):
     return deepest
 
 
+def node_boxes(nodes):
+    return (np.stack([nodes[b][k] for k in "xyz"], -1).astype(np.float64) for b in ("bounds_min", "bounds_max"))
+
+
+def counting_pending_depth(nodes, passes):
+    """the same for a counting walk (k_within without k_nearest, k_region) on the child-pair tree: passes[i] = node i's box passes; every passing child is
+    visited, the first next, the other pushed; the bound is never lowered, so a pop always accepts"""
+    stack, deepest, node = [], 0, 0 if passes[0] else None
+    while node is not None:
+        c = []
+        if not int(nodes["num_primitives_axis"][node]) >> 16:
+            c = [i for i in (node + 1, int(nodes["offset"][node])) if passes[i]]
+        if len(c) == 2:
+            stack.append(c[1])
+            deepest = max(deepest, len(stack))
+        node = c[0] if c else stack.pop() if stack else None
+    return deepest
+
+
 class Slab:
     """the scene, the 130 distinct rays and points, the precondition and every expected answer (computed once, shared, never changed)"""
 
@@ -152,6 +176,33 @@ class Slab:
         self.point_depth = min(nearest_pending_depth(nodes, tris, p[:3].astype(np.float64)) for p in self.points)
         assert self.ray_depth >= STACK_LDS + 2, "the rays' pending depth is %d, below %d: the spill area is not reached" % (self.ray_depth, STACK_LDS + 2)
         assert self.point_depth >= STACK_LDS + 2, "the points' pending depth is %d, below %d: the spill area is not reached" % (self.point_depth, STACK_LDS + 2)
+
+        # within and overlap: a counting walk's pending depth depends on which boxes pass alone.  With an infinite radius every box passes for every point,
+        # and the enclosing box's planes reject none: one restatement of the walk speaks for all of them
+        lo, hi = node_boxes(nodes)
+        gap = np.maximum(np.maximum(lo[:, None] - self.points[None, :, :3], self.points[None, :, :3] - hi[:, None]), 0.0)
+        point_passes = ~((gap ** 2).sum(-1) > np.float64(self.points[:, 3])[None])                 # [node, point]: !(nearest_box_d2 > r2)
+        assert point_passes.all()
+        self.within_depth = counting_pending_depth(nodes, point_passes.all(1))
+        assert self.within_depth >= STACK_LDS + 2, "the within points' pending depth is %d, below %d" % (self.within_depth, STACK_LDS + 2)
+        enclosing = T.box_region((-1.0, -1.0, -1.0), (2.0, 2.0, float(N_QUADS)))
+        regions = np.zeros(DISTINCT, T.region)
+        regions[0::2] = enclosing
+        for k in range(1, DISTINCT, 2):                                            # below a plane between two quads; every other one tilted through a quad
+            regions[k] = T.planes_region([(0.25 * (k % 4 == 1), 0.0, 1.0, -(k * 119 % N_QUADS + 0.125))])
+        self.regions = regions
+        pl = np.float64(enclosing["planes"][:int(enclosing["num_planes"])])
+        corner = np.where(pl[None, :, :3] >= 0.0, lo[:, None], hi[:, None])                        # region.h's box test: the corner lowest along the normal
+        box_passes = ~((corner * pl[None, :, :3]).sum(-1) + pl[None, :, 3] > 0.0).any(1)
+        assert box_passes.all()
+        self.region_depth = counting_pending_depth(nodes, box_passes)
+        assert self.region_depth >= STACK_LDS + 2, "the enclosing regions' pending depth is %d, below %d" % (self.region_depth, STACK_LDS + 2)
+        self.within = {(m, knn): capi.debug_within(None, tris, self.points, m, k_nearest=knn) for m, knn in WITHIN_CASES}
+        self.overlap = {m: capi.debug_overlap(None, tris, regions, m) for m in (0, 8)}
+        assert all((got[0]["stored"] == m).any() for (m, _), got in self.within.items())           # a full list
+        counts = self.overlap[8][0]["count"]
+        assert (counts[0::2] == len(tris)).all() and ((counts[1::2] > 0) & (counts[1::2] < len(tris))).all() and len(set(counts[1::2].tolist())) > 1
+        assert (self.overlap[8][0]["stored"] == 8).any()
 
         self.orc = _oracle.Oracle(16, 16, self.scene)
         self.wide, self.entry = wide_of(nodes, 1)
@@ -203,6 +254,28 @@ def test_points_spill_and_equal_brute_force(slab, ctx):
         got = ctx.nearest(slab.points[:n])
         ctx.finish()
         assert got.tobytes() == slab.nearest[:n].tobytes(), (n, int((got["primitive_id"] != slab.nearest["primitive_id"][:n]).sum()))
+
+
+def test_within_spills_and_equals_brute_force(slab, ctx):
+    for max_near, knn in WITHIN_CASES:
+        want, want_near = slab.within[(max_near, knn)]
+        for n in COUNTS:
+            got = ctx.within(slab.points[:n], max_near, k_nearest=knn)
+            ctx.finish()
+            got, near = got if max_near else (got, want_near[:n])
+            assert got.tobytes() == want[:n].tobytes(), (max_near, knn, n, got["count"][:4], want["count"][:4])
+            assert near.tobytes() == want_near[:n].tobytes(), (max_near, knn, n)
+
+
+def test_overlaps_spill_and_equal_brute_force(slab, ctx):
+    for max_list in (0, 8):
+        want, want_members = slab.overlap[max_list]
+        for n in COUNTS:
+            got = ctx.overlap(slab.regions[:n], max_list)
+            ctx.finish()
+            got, members = got if max_list else (got, want_members[:n])
+            assert got.tobytes() == want[:n].tobytes(), (max_list, n, got["count"][:4], want["count"][:4])
+            assert members.tobytes() == want_members[:n].tobytes(), (max_list, n)
 
 
 @pytest.mark.parametrize("samples", [16, 64])
