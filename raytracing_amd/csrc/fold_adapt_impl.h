@@ -1,8 +1,11 @@
-// fold_adapt_impl.h -- part of rt_hip.hip's translation unit (included inside its anonymous namespace): which tree a ray population walks (OwnTree,
+// fold_adapt_impl.h -- part of rt_hip.hip's translation unit (included at file scope): which tree a ray population walks (OwnTree,
 // choose_tree) and the state + worker of RT_CTX_OPT_ADAPTIVE_FOLD (FoldAdapt: crossing counts, re-fold, tree rotations, occluder-first slots, the upload
 // of the adapted records).  The render-thread side -- probe, hand-over, adoption -- is fold_hooks_impl.h.  Split out of rt_hip.hip in round 6.
+// Everything is in the anonymous namespace but FoldAdapt itself, the one name context.h declares (Scene::adapt points at it).
 #pragma once
 
+namespace
+{
 // (the host-side fold, the pair layout and the adaptation's host walks: wide_bvh.cpp; the fold on the device: device_fold.hip)
 // Which tree a ray population walks: the candidate of own_bvh.h against the reference's own topology (`ref_wide`), both
 // walked by proxy rays of that population (tree_select.h).  mode 1: own only if it saves more than 10 % of the steps (the proxy rays are not the
@@ -161,6 +164,8 @@ bool choose_tree(const rt_scene_desc* sd, const std::vector<WideNode>& ref_wide,
     return pick;
 }
 
+} // namespace
+
 // ---- Fold adaptation (RT_CTX_OPT_ADAPTIVE_FOLD) ---------------------------------------------------------------------------------
 // build_wide_bvh's dynamic programme is optimal for whatever visit probability it is given, and the surface area is only the
 // probability of a ray population nobody traces: uniformly distributed lines.  The rays of a frame are not that (they start at
@@ -169,6 +174,8 @@ bool choose_tree(const rt_scene_desc* sd, const std::vector<WideNode>& ref_wide,
 // their hit), and the trees are folded again for those frequencies -- tools/fold_weight_study.py: - 8 % closest-hit and - 10 %
 // shadow record visits on the benchmark scene, out of sample, and 14 000 probe rays are as good as 220 000.
 // Exact by construction: every fold of the same binary tree tests the same leaves in the same order (build_wide_bvh).
+namespace context
+{
 struct FoldAdapt
 {
     enum { ARMED = 1, COMPUTING = 2, IDLE = 3, OFF = 4, PROBING = 5 };   // IDLE: adapted to `camera`; a frame whose camera has moved away arms it again;
@@ -226,6 +233,10 @@ struct FoldAdapt
     size_t probe_counters(uint32_t sample) const { return (size_t)probe_samples * probe_bounces * 5u * probe_paths * sizeof(float4) + (size_t)sample * sizeof(DCounters); }
     ~FoldAdapt();
 };
+} // namespace context
+
+namespace
+{
 void drop_fold_adapt(FoldAdapt* a) { delete a; }
 void fold_adapt_set_interval(FoldAdapt* a, uint32_t ms) { a->min_interval_ms = ms; }
 void fold_adapt_set_wait(FoldAdapt* a, bool wait) { if (wait) a->mode.fetch_or(2u); else a->mode.fetch_and(~2u); }
@@ -494,7 +505,9 @@ void fold_adapt_worker(FoldAdapt* a)
     a->finished.store(true);
 }
 
-FoldAdapt::~FoldAdapt()
+} // namespace
+
+context::FoldAdapt::~FoldAdapt()
 {
     cancel.store(true);
     if (worker.joinable()) worker.join();

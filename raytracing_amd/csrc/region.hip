@@ -248,6 +248,13 @@ bool select_device(hipStream_t stream, const rt_triangle* tris, uint32_t n_tris,
     return tmp.finish(ok, touching, d_touching, (size_t)n_tris * 4u);
 }
 
+const char* rect_refused(uint32_t width, uint32_t height, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1)
+{
+    if (x1 < x0 || y1 < y0) return "an empty rectangle (x1 < x0 or y1 < y0)";
+    if (x1 >= width || y1 >= height) return "the rectangle is outside the image";
+    return nullptr;
+}
+
 rt_region rect_region(const rt_camera& cam, uint32_t width, uint32_t height, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, float t_near, float t_far)
 {
     return region_of_rect(cam, width, height, x0, y0, x1, y1, t_near, t_far);

@@ -40,6 +40,8 @@ void select_host(const rt_triangle* tris, uint32_t n_tris, const uint32_t* ids, 
 bool select_device(hipStream_t stream, const rt_triangle* tris, uint32_t n_tris, const uint32_t* ids, uint32_t n_objects, const rt_region* regions, uint32_t n,
     uint32_t* touching, uint32_t* inside, uint32_t* object_touching, uint32_t* object_inside);
 
-// rt_frame_pick_rect's region: region.h's region_of_rect
+// why the inclusive pixel rectangle (x0, y0) .. (x1, y1) of a width x height image is refused (nullptr: it is fine), for rt_frame_pick_rect and rt_debug_rect_region
+const char* rect_refused(uint32_t width, uint32_t height, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1);
+// ... and its region: region.h's region_of_rect
 rt_region rect_region(const rt_camera& cam, uint32_t width, uint32_t height, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, float t_near, float t_far);
 } // namespace region

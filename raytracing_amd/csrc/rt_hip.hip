@@ -28,120 +28,22 @@
 #include "refit.h"           // the refit of the scene's trees when its triangles move (refit.hip)
 #include "pose_host.h"       // the scene's objects posed from one matrix per object (pose.hip)
 #include "filters_host.h"         // the filters' guide pass, a-trous passes and temporal stages (filters.hip)
-#include "query_host.h"      // caller-supplied rays traced against the uploaded scene (query.hip)
-#include "bake_host.h"       // ambient occlusion and bent normals at caller-supplied points (bake.hip)
-#include "nearest_host.h"    // the nearest surface point to caller-supplied points (nearest.hip)
-#include "all_hits_host.h"   // every surface a caller-supplied ray crosses (all_hits.hip)
-#include "within_host.h"     // every triangle within a radius of caller-supplied points (within.hip)
-#include "region_host.h"     // every triangle a caller-supplied convex region touches or encloses (region.hip)
+#include "query_host.h"      // the queries' scratch areas and the ray through a pixel, for rt_frame_pick and rt_frame_pick_all (query.hip)
+#include "bake_host.h"       // bake::CHUNK_POINTS, for RT_CTX_OPT_BAKE_CHUNK_POINTS (bake.hip)
+#include "region_host.h"     // the region of a pixel rectangle, for rt_frame_pick_rect (region.hip)
 #include "device_memory.h"   // who owns a device allocation: dev::Mem, dev::Temps
+#include "context.h"         // Scene, rt_ctx, rt_buffer, fail / HIPCHK: what this unit shares with the feature units that implement entry points (scene_queries.cpp)
 using namespace rtw;
+using namespace context;
 
 namespace
 {
 thread_local std::string g_thread_error;
 
-struct FoldAdapt;                          // RT_CTX_OPT_ADAPTIVE_FOLD: the state of a scene's fold adaptation (below, after choose_tree)
-void drop_fold_adapt(FoldAdapt* a);        // waits for its worker thread
+void drop_fold_adapt(FoldAdapt* a);        // waits for its worker thread (fold_adapt_impl.h, below, after choose_tree)
 void fold_adapt_set_interval(FoldAdapt* a, uint32_t ms);
 void fold_adapt_set_wait(FoldAdapt* a, bool wait);
-
-// One 4-wide quantized tree on the device: its records (whoever holds the value owns them), how many (0 with a leaf root), the record a walk enters at.
-struct WideTree { void* recs = nullptr; uint32_t n = 0, entry = 0; };
-// The trees a scene can hold: the fold of the reference's tree (build_wide_bvh / devfold::fold; no records when the tree does not qualify), the shadow rays'
-// own (own_bvh.h over the reference's leaves) and, RT_CTX_OPT_CLOSEST_TREE != 0 (tolerance mode), the closest-hit rays' own.
-enum TreeSlot { TREE_REF = 0, TREE_SHADOW = 1, TREE_CLOSEST = 2 };
-
-struct Scene
-{
-    void* nodes = nullptr; void* tris_rt = nullptr; void* tris_sh = nullptr; void* materials = nullptr;
-    void* textures = nullptr; void* texture_data = nullptr; void* lights = nullptr; void* env = nullptr;
-    void* emissive = nullptr;
-    void* mat_tex16 = nullptr;
-    WideTree trees[3];                                           // by TreeSlot
-    TreeSlot closest = TREE_REF, shadow = TREE_REF;              // which of them each ray population walks; an own tree is held exactly while its population walks it
-    const WideTree &closest_tree() const { return trees[closest]; }
-    const WideTree &shadow_tree() const { return trees[shadow]; }
-    bool shadow_shares_closest() const { return shadow == closest; }     // the shadow rays walk the closest-hit rays' records
-    // The only writer of the kernels' view of the trees (d.wnodes, d.w_entry_ref, d.wnodes_sh, d.w_sh_entry_ref): the two operations below end with it.
-    void publish_trees()
-    {
-        d.wnodes = (const float4*)closest_tree().recs; d.w_entry_ref = closest_tree().entry;
-        d.wnodes_sh = (const float4*)shadow_tree().recs; d.w_sh_entry_ref = shadow_tree().entry;
-    }
-    // `slot` holds `tree` from now on; what it held goes back to the caller, who frees it or keeps it until nothing in flight reads it (FoldAdapt::retired)
-    WideTree replace_tree(TreeSlot slot, WideTree tree) { std::swap(trees[slot], tree); publish_trees(); return tree; }
-    void walk_trees(TreeSlot closest_rays, TreeSlot shadow_rays) { closest = closest_rays; shadow = shadow_rays; publish_trees(); }
-    uint32_t n_tris = 0;         // triangles of the uploaded scene (rt_scene_import_folds checks leaf refs against it)
-    std::string tree_report;     // what rt_scene_upload measured when it chose the trees (rt_scene_tree_report)
-    FoldAdapt* adapt = nullptr;  // RT_CTX_OPT_ADAPTIVE_FOLD: armed at upload, run by the first rt_integrate (fold_adapt_hook)
-    DScene d = {};
-    bool valid = false;
-    bool wide_ok = false;     // build_wide_bvh succeeded (k_trace_w4 usable)
-    bool offsets32 = false;   // node and trace-triangle arrays below 4 GiB: k_trace2 addresses them with 32-bit byte offsets
-    // a quarter or more of the shadow rays will have a non-finite 1/dir component (directional lights along a coordinate
-    // axis, e.g. an overhead light (0, -1, 0)): k_trace_w4 would hand every one of them to its small follow-up launch,
-    // so the automatic choice traces the shadow queue with k_trace2 (select-form slab test inline, full residency)
-    bool slow_shadow = false;
-    // RT_CTX_OPT_REFITTABLE (refit_impl.h): what rt_scene_refit keeps beside the scene; nullptr = the option was off at upload (or refit_refusal says why not)
-    refit::State* refit = nullptr;
-    std::string refit_refusal;
-    bool refit_wide_built = false;   // wide_ok as upload left it (a refit that meets a record that no longer qualifies clears wide_ok until one qualifies again)
-    bool adapt_retired = false;      // a refit has retired the fold adaptation
-    uint32_t n_materials = 0;
-    uint64_t refits = 0;
-    // RT_CTX_OPT_REFIT_MOTION: the pose before the last refit, 6 float4 per triangle (filt::snapshot_pose); nullptr = the option was off at upload (or the
-    // allocation failed: treated as off).  pose_valid: a refit has filled it.
-    void* pose_snap = nullptr;
-    bool pose_valid = false;
-    // rt_scene_set_objects (pose_impl.h): the rest pose, every triangle's object and the staging area of rt_scene_pose; nullptr = no objects set
-    pose::State* pose = nullptr;
-};
 } // namespace
-
-struct rt_ctx
-{
-    int device = 0;
-    hipStream_t stream = nullptr;
-    hipDeviceProp_t prop;
-    std::string error;
-    Scene scene;
-    uint32_t treelet_nodes = 7;   // RT_CTX_OPT_TREELET_NODES
-    uint32_t build_wide = 1;      // RT_CTX_OPT_WIDE_BVH
-    uint32_t shadow_tree = 1;     // RT_CTX_OPT_SHADOW_TREE: 1 = shadow rays walk the backend's own tree where it measures cheaper (exact either way),
-                                  // 2 = own unconditionally, 3 = own with the surface-area metric (A/B), 0 = they share the closest-hit tree
-    uint32_t closest_tree = 0;    // RT_CTX_OPT_CLOSEST_TREE: 1 / 2 as above; != 0 is the tolerance mode (NOT bit-exact)
-    uint32_t adaptive_fold = 25;  // RT_CTX_OPT_ADAPTIVE_FOLD (default bits 0 + 3 + 4 since round 5): bit 0 = re-fold the 4-wide trees for the rays rt_integrate actually traces (exact: a fold
-                                  // decides which boxes are tested, never a result), bit 1 = rt_integrate waits for the new fold instead of
-                                  // adopting it when it is ready, bit 2 = also for scenes too small to profit (tests), bit 3 = the shadow rays'
-                                  // binary tree is rotated for the probe rays' crossings before it is folded (tree_rotate.h), bit 4 = the slots of
-                                  // every shadow record are stored likeliest occluder first (measured on the device in round 5, profiles/r05_call01_*:
-                                  // shadow trace 0.314 -> 0.258 ms per sample on the headline scene, bit-identical on all five configs)
-    uint32_t adapt_min_interval_ms = 500;   // RT_CTX_OPT_ADAPT_MIN_INTERVAL_MS
-    uint32_t wide_layout = 0;               // RT_CTX_OPT_WIDE_LAYOUT: 1 = the 4-wide records stored in (parent, likeliest child) pairs, one pair per 128-byte line (pair_layout)
-    uint32_t tree_builder = 2;              // RT_CTX_OPT_TREE_BUILDER: the shadow rays' own binary tree -- 0 = own_bvh.h's full-sweep SAH on host threads, 1 = PLOC on the device (ploc_kernels.h),
-                                            // 2 (default) = both start, the device's is measured first and the host's build is abandoned if it wins its measurement
-    uint32_t refittable = 0;                // RT_CTX_OPT_REFITTABLE: rt_scene_upload keeps what rt_scene_refit needs (refit.h)
-    uint32_t device_fold = 1;               // RT_CTX_OPT_DEVICE_FOLD: the SAH collapse into 4-wide records runs on the device (fold_kernels.h); 0 = on host threads
-    uint32_t refit_motion = 0;              // RT_CTX_OPT_REFIT_MOTION: a refit keeps the pose it replaces, for the temporal filter (needs refittable)
-    uint64_t scene_uploads = 0;             // rt_scene_upload calls so far (what a frame's measured choices were made for)
-    uint64_t upload_epoch = 0;              // changes on rt_scene_upload only; refit_index: the successful refits within it.  A temporal history made for
-    uint64_t refit_index = 0;               // (epoch, index - 1) can follow the geometry through the one pose the scene keeps (Scene::pose_snap)
-    std::vector<rt_frame*> frames;   // the frames alive on this context (rt_finish waits for their side streams too)
-    uint8_t* blue_noise = nullptr;   // sobol[65536] | scramblingTile[131072] | rankingTile[131072]
-    float* gamma_lut = nullptr;      // pow(byte / 255, 2.2f), 256 entries (k_fill_gamma_lut)
-    query::Scratch query;            // rt_scene_trace*: the walk's stack spill area and the host form's staging arrays (query_host.h)
-    query::Scratch bake;             // rt_scene_bake*: the same of its own (stages 0 and 1; the status word stays query.status), reported apart by rt_scene_tree_report
-    uint32_t bake_chunk_points = bake::CHUNK_POINTS;   // RT_CTX_OPT_BAKE_CHUNK_POINTS
-    std::string report_out;          // rt_scene_tree_report's answer when it has a "ray queries" line to add to the scene's report
-};
-
-struct rt_buffer
-{
-    rt_ctx* ctx;
-    void* ptr;
-    size_t bytes;
-};
 
 // An owner's device buffers: each one's address and size (clear: it starts from zero).  An owner lists them once (buffers()), for the allocation and for the free.
 struct DevBuf { void** p; size_t bytes; bool clear = false; };
@@ -443,7 +345,8 @@ struct SfMotion
     }
 };
 
-namespace
+// context.h's functions: the one place a message is stored, the device copies of an upload, the queries' status word
+namespace context
 {
 int fail(rt_ctx* ctx, const std::string& msg)
 {
@@ -451,14 +354,6 @@ int fail(rt_ctx* ctx, const std::string& msg)
     g_thread_error = msg;
     return RT_ERROR;
 }
-
-#define HIPCHK(ctx, expr)                                                                         \
-    do                                                                                            \
-    {                                                                                             \
-        hipError_t e_ = (expr);                                                                   \
-        if (e_ != hipSuccess)                                                                     \
-            return fail(ctx, std::string(#expr) + ": " + hipGetErrorString(e_));                  \
-    } while (0)
 
 // m = `bytes` of device memory with src's bytes on their way into it on ctx's stream (no src: nothing is copied); a failure is `who`'s error
 int dev_fill(rt_ctx* ctx, const char* who, dev::Mem& m, const void* src, size_t bytes)
@@ -487,7 +382,10 @@ int query_check_status(rt_ctx* ctx, const char* who)
     *st = 0u;
     return fail(ctx, std::string(who) + ": a ray query's traversal stack ran over its bound (a tree deeper than the walk's stack): that query's results are not valid");
 }
+} // namespace context
 
+namespace
+{
 void free_scene(Scene& s)
 {
     void* ptrs[] = {s.nodes, s.tris_rt, s.tris_sh, s.materials, s.textures, s.texture_data, s.lights, s.env, s.emissive, s.trees[TREE_REF].recs, s.mat_tex16,
@@ -723,9 +621,10 @@ size_t rt_buffer_size(rt_buffer* buf) { return buf ? buf->bytes : 0; }
 
 } // extern "C"
 
+#include "fold_adapt_impl.h"
+
 namespace
 {
-#include "fold_adapt_impl.h"
 
 // ---- rt_scene_upload's stages ------------------------------------------------------------------------------------------------------
 // do this many 64-byte records stay below 4 GiB?  (k_trace_w4 and k_trace2 address node and trace-triangle records with 32-bit byte offsets)
@@ -1079,12 +978,6 @@ extern "C" {
 
 #include "refit_impl.h"
 #include "pose_impl.h"
-#include "query_impl.h"
-#include "bake_impl.h"
-#include "nearest_impl.h"
-#include "all_hits_impl.h"
-#include "within_impl.h"
-#include "region_impl.h"
 
 // ---- scene -----------------------------------------------------------------
 int rt_scene_upload(rt_ctx* ctx, const rt_scene_desc* sd)
@@ -1741,6 +1634,56 @@ int rt_set_camera(rt_frame* f, const rt_camera* camera)
     f->camera = *camera;
     f->prev_camera = f->camera_last;     // what GenerateAOV sees as prev_camera this frame
     f->camera_last = *camera;
+    return RT_OK;
+}
+
+// ---- picks: a pixel or a rectangle of the frame's camera, asked of the scene's queries (scene_queries.cpp) through their public entries
+// what every pick refuses before it looks at its pixels
+static int pick_refused(const rt_frame* f, const char* who)
+{
+    const std::string name(who);
+    if (!f) return fail(nullptr, name + ": frame is NULL");
+    if (!f->ctx->scene.valid) return fail(f->ctx, name + ": no scene uploaded");
+    if (f->tile.nranks > 1) return fail(f->ctx, name + ": a tile frame (tile_count > 1): pick on a frame of the whole image");
+    return RT_OK;
+}
+
+int rt_frame_pick(rt_frame* f, uint32_t x, uint32_t y, rt_ray* ray, rt_hit* hit, rt_surface* surface)
+{
+    if (pick_refused(f, "rt_frame_pick") != RT_OK) return RT_ERROR;
+    rt_ctx* ctx = f->ctx;
+    if (x >= f->tile.width || y >= f->tile.height) return fail(ctx, "rt_frame_pick: the pixel is outside the image");
+    const rt_ray r = query::pick_ray(f->camera, f->tile.width, f->tile.height, x, y);
+    rt_hit h;
+    rt_surface s;
+    if (rt_scene_trace(ctx, &r, 1u, RT_QUERY_CLOSEST, &h, nullptr, &s) != RT_OK) return RT_ERROR;
+    if (ray) *ray = r;
+    if (hit) *hit = h;
+    if (surface) *surface = s;
+    return RT_OK;
+}
+
+int rt_frame_pick_all(rt_frame* f, uint32_t x, uint32_t y, uint32_t max_hits, rt_ray* ray, rt_ray_hits* out, rt_hit* hits, rt_surface* surfaces)
+{
+    if (pick_refused(f, "rt_frame_pick_all") != RT_OK) return RT_ERROR;
+    rt_ctx* ctx = f->ctx;
+    if (x >= f->tile.width || y >= f->tile.height) return fail(ctx, "rt_frame_pick_all: the pixel is outside the image");
+    const rt_ray r = query::pick_ray(f->camera, f->tile.width, f->tile.height, x, y);
+    if (rt_scene_trace_all(ctx, &r, 1u, max_hits, out, hits, surfaces) != RT_OK) return RT_ERROR;
+    if (ray) *ray = r;
+    return RT_OK;
+}
+
+int rt_frame_pick_rect(rt_frame* f, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, float t_near, float t_far, rt_region* region, uint32_t* touching,
+    uint32_t* inside, uint32_t* object_touching, uint32_t* object_inside)
+{
+    if (pick_refused(f, "rt_frame_pick_rect") != RT_OK) return RT_ERROR;
+    rt_ctx* ctx = f->ctx;
+    if (const char* why = region::rect_refused(f->tile.width, f->tile.height, x0, y0, x1, y1)) return fail(ctx, std::string("rt_frame_pick_rect: ") + why);
+    if ((object_touching || object_inside) && !ctx->scene.pose) return fail(ctx, "rt_frame_pick_rect: the per-object outputs need rt_scene_set_objects");
+    const rt_region g = region::rect_region(f->camera, f->tile.width, f->tile.height, x0, y0, x1, y1, t_near, t_far);
+    if ((touching || inside || object_touching || object_inside) && rt_scene_select(ctx, &g, 1u, touching, inside, object_touching, object_inside) != RT_OK) return RT_ERROR;
+    if (region) *region = g;
     return RT_OK;
 }
 

@@ -1,0 +1,555 @@
+// scene_queries.cpp -- the C entry points of the six query families on an uploaded scene, the bookkeeping around the kernels and launch drivers of
+// query.hip, bake.hip, nearest.hip, all_hits.hip, within.hip and region.hip (DESIGN.md sections 7h - 7m): rt_scene_trace*, rt_scene_bake*,
+// rt_scene_nearest*, rt_scene_trace_all*, rt_scene_within*, rt_scene_overlap*, rt_scene_select* and their rt_debug_* forms.  Host code only, on context.h:
+// a query reads the scene and writes the caller's arrays, it launches on the context's stream -- behind every refit, pose and upload, which end there --
+// and touches no frame.  (The three picks read a frame's camera and tile: they are rt_hip.hip's and call the entries here.)  The stack spill area, the
+// status word and the staging arrays of every family but the bakes are the ray queries' (ctx->query), so rt_scene_tree_report's "ray queries" line
+// counts them; the bakes have a scratch of their own (ctx->bake).
+#include <hip/hip_runtime_api.h>
+#include <stdint.h>
+#include <functional>
+#include <initializer_list>
+#include <string>
+#include "rt_hip.h"
+#include "context.h"
+#include "query_host.h"
+#include "bake_host.h"
+#include "nearest_host.h"
+#include "all_hits_host.h"
+#include "within_host.h"
+#include "region_host.h"
+#include "device_memory.h"
+using namespace context;
+
+// ---- what the families share ---------------------------------------------------------------------------------------------------------------------------
+
+// How every scene form opens: a context, the arrays it asks for before it looks at the scene, a scene, the arrays it asks for after.  (Which array comes
+// before the scene differs by family and is part of each one's contract: a caller sees the first refusal only.)
+struct Needed { const char* what; bool given; };
+static int opening_refused(rt_ctx* ctx, const std::string& name, std::initializer_list<Needed> before_scene, std::initializer_list<Needed> after_scene)
+{
+    if (!ctx) return fail(nullptr, name + ": ctx is NULL");
+    for (const Needed& a : before_scene) if (!a.given) return fail(ctx, name + ": " + a.what + " is NULL");
+    if (!ctx->scene.valid) return fail(ctx, name + ": no scene uploaded");
+    for (const Needed& a : after_scene) if (!a.given) return fail(ctx, name + ": " + a.what + " is NULL");
+    return RT_OK;
+}
+
+// One array of a host form's call: `host` is the caller's (NULL: not asked for), staged through stage[stage] of the scratch, up before the launch or down after it.
+struct StagedArray { void* host; size_t record; int stage; bool up; };
+
+// A host form's loop, shared by every family's: at most `chunk` records at a time are staged -- reserve, copy up, launch(first, m) on the staged arrays,
+// copy down, wait for the stream, read the walk's status word.
+static int staged_call(rt_ctx* ctx, const char* who, query::Scratch& s, std::initializer_list<StagedArray> arrays, uint32_t n, uint32_t chunk,
+    const std::function<int(uint32_t first, uint32_t m)>& launch)
+{
+    for (uint32_t first = 0; first < n; )
+    {
+        const uint32_t m = n - first < chunk ? n - first : chunk;
+        for (const StagedArray& a : arrays)
+            if (a.host && !query::reserve(ctx->stream, s, a.stage, (size_t)m * a.record)) return fail(ctx, std::string(who) + ": out of device memory for the staging arrays");
+        for (const StagedArray& a : arrays)
+            if (a.host && a.up) HIPCHK(ctx, hipMemcpyAsync(s.stage[a.stage], (const char*)a.host + (size_t)first * a.record, (size_t)m * a.record, hipMemcpyHostToDevice, ctx->stream));
+        if (launch(first, m) != RT_OK) return RT_ERROR;
+        for (const StagedArray& a : arrays)
+            if (a.host && !a.up) HIPCHK(ctx, hipMemcpyAsync((char*)a.host + (size_t)first * a.record, s.stage[a.stage], (size_t)m * a.record, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        if (query_check_status(ctx, who) != RT_OK) return RT_ERROR;
+        first += m;
+    }
+    return RT_OK;
+}
+
+// what a buffer form refuses of its buffers (NULL: not passed)
+struct BufferArg { rt_buffer* b; size_t record; const char* what; };
+static int buffers_refused(rt_ctx* ctx, const char* who, std::initializer_list<BufferArg> bufs, uint32_t n)
+{
+    for (const BufferArg& b : bufs)
+    {
+        if (!b.b) continue;
+        if (b.b->ctx != ctx) return fail(ctx, std::string(who) + ": the " + b.what + " buffer belongs to another context");
+        if (b.b->bytes < (size_t)n * b.record) return fail(ctx, std::string(who) + ": the " + b.what + " buffer is smaller than n records");
+    }
+    return RT_OK;
+}
+
+// a driver's launch() said `ok`; why_not: the message behind `who` when it did not
+static int launch_result(rt_ctx* ctx, const char* who, bool ok, const char* why_not)
+{
+    if (ok) return RT_OK;
+    (void)hipGetLastError();
+    return fail(ctx, std::string(who) + why_not);
+}
+static const char QUERY_NOT_LAUNCHED[] = ": the query could not be launched (the stack spill area could not be allocated, or a launch failed)";
+
+// A brute-force debug form's two ways, once its arguments have passed: without a context on_host() computes, with one on_device(stream) does on its device.
+template <class Host, class Device> static int host_or_device(rt_ctx* ctx, const char* who, Host on_host, Device on_device)
+{
+    if (!ctx) { on_host(); return RT_OK; }
+    (void)hipSetDevice(ctx->device);
+    if (!on_device(ctx->stream)) return fail(ctx, std::string(who) + ": the device path failed (allocation, copy or launch)");
+    return RT_OK;
+}
+
+// what a walk form says of a `wide` that is neither
+static const char WIDE_REFUSED[] = ": wide must be 0 (the child-pair form) or 1 (the 4-wide records)";
+
+extern "C" {
+
+// ---- rays: rt_scene_trace / rt_scene_trace_buffer / rt_debug_query_surface (query.hip) ---------------------------------------------
+
+// everything both forms refuse before anything is launched
+static int query_refused(rt_ctx* ctx, const char* who, bool rays, uint32_t n, uint32_t mode, bool hits, bool occluded, bool surfaces)
+{
+    const std::string name(who);
+    if (opening_refused(ctx, name, {{"rays", rays || n == 0u}}, {}) != RT_OK) return RT_ERROR;
+    if (mode != RT_QUERY_CLOSEST && mode != RT_QUERY_ANY_HIT) return fail(ctx, name + ": unknown mode (RT_QUERY_CLOSEST or RT_QUERY_ANY_HIT)");
+    if (mode == RT_QUERY_CLOSEST && !hits && !occluded && !surfaces) return fail(ctx, name + ": no output (hits, occluded and surfaces are all NULL)");
+    if (mode == RT_QUERY_ANY_HIT && (hits || surfaces)) return fail(ctx, name + ": RT_QUERY_ANY_HIT reports no hits or surfaces (which triangle occludes depends on the tree): pass NULL");
+    if (mode == RT_QUERY_ANY_HIT && !occluded) return fail(ctx, name + ": no output (occluded is NULL)");
+    return RT_OK;
+}
+
+static int query_launch(rt_ctx* ctx, const char* who, const rt_ray* d_rays, uint32_t n, uint32_t mode, rt_hit* d_hits, uint32_t* d_occluded, rt_surface* d_surfaces)
+{
+    const Scene& s = ctx->scene;
+    return launch_result(ctx, who, query::launch(ctx->stream, ctx->query, s.d, s.wide_ok, s.n_tris, s.pose ? s.pose->ids : nullptr, ctx->prop.multiProcessorCount, d_rays, n,
+        mode, d_hits, d_occluded, d_surfaces), QUERY_NOT_LAUNCHED);
+}
+
+int rt_scene_trace(rt_ctx* ctx, const rt_ray* rays, uint32_t n, uint32_t mode, rt_hit* hits, uint32_t* occluded, rt_surface* surfaces)
+{
+    if (ctx && n == 0u) return RT_OK;
+    if (query_refused(ctx, "rt_scene_trace", rays != nullptr, n, mode, hits != nullptr, occluded != nullptr, surfaces != nullptr) != RT_OK) return RT_ERROR;
+    (void)hipSetDevice(ctx->device);
+    query::Scratch& q = ctx->query;
+    return staged_call(ctx, "rt_scene_trace", q, {{(void*)rays, sizeof(rt_ray), 0, true}, {hits, sizeof(rt_hit), 1, false}, {occluded, sizeof(uint32_t), 2, false},
+        {surfaces, sizeof(rt_surface), 3, false}}, n, (uint32_t)query::CHUNK_RAYS, [&](uint32_t, uint32_t m)
+        {
+            return query_launch(ctx, "rt_scene_trace", (const rt_ray*)q.stage[0], m, mode, hits ? (rt_hit*)q.stage[1] : nullptr, occluded ? (uint32_t*)q.stage[2] : nullptr,
+                surfaces ? (rt_surface*)q.stage[3] : nullptr);
+        });
+}
+
+int rt_scene_trace_buffer(rt_ctx* ctx, rt_buffer* rays, uint32_t n, uint32_t mode, rt_buffer* hits, rt_buffer* occluded, rt_buffer* surfaces)
+{
+    if (ctx && n == 0u) return RT_OK;
+    if (query_refused(ctx, "rt_scene_trace_buffer", rays != nullptr, n, mode, hits != nullptr, occluded != nullptr, surfaces != nullptr) != RT_OK) return RT_ERROR;
+    if (buffers_refused(ctx, "rt_scene_trace_buffer", {{rays, sizeof(rt_ray), "rays"}, {hits, sizeof(rt_hit), "hits"}, {occluded, sizeof(uint32_t), "occluded"},
+            {surfaces, sizeof(rt_surface), "surfaces"}}, n) != RT_OK)
+        return RT_ERROR;
+    (void)hipSetDevice(ctx->device);
+    return query_launch(ctx, "rt_scene_trace_buffer", (const rt_ray*)rays->ptr, n, mode, hits ? (rt_hit*)hits->ptr : nullptr, occluded ? (uint32_t*)occluded->ptr : nullptr,
+        surfaces ? (rt_surface*)surfaces->ptr : nullptr);
+}
+
+int rt_debug_query_surface(rt_ctx* ctx, const rt_triangle* triangles, uint32_t num_triangles, const uint32_t* object_of_triangle, const rt_ray* rays, const rt_hit* hits,
+    uint32_t n, rt_surface* out)
+{
+    if (n == 0u) return RT_OK;
+    if (!rays || !hits || !out || (!triangles && num_triangles > 0u)) return fail(ctx, "rt_debug_query_surface: NULL argument");
+    return host_or_device(ctx, "rt_debug_query_surface", [&] { query::debug_surface_host(triangles, num_triangles, object_of_triangle, rays, hits, n, out); },
+        [&](hipStream_t st) { return query::debug_surface_device(st, triangles, num_triangles, object_of_triangle, rays, hits, n, out); });
+}
+
+// ---- bakes: rt_scene_bake / rt_scene_bake_buffer / rt_debug_bake_rays / rt_debug_bake_reduce (bake.hip) ----------------------------
+
+// everything both forms refuse before anything is launched
+static int bake_refused(rt_ctx* ctx, const char* who, bool points, uint32_t n, const rt_bake_desc* desc, bool out)
+{
+    const std::string name(who);
+    if (opening_refused(ctx, name, {{"points", points}, {"desc", desc != nullptr}, {"out", out}}, {}) != RT_OK) return RT_ERROR;
+    if (const char* why = bake::desc_refusal(*desc)) return fail(ctx, name + ": " + why);
+    return RT_OK;
+}
+
+static int bake_launch(rt_ctx* ctx, const char* who, const void* d_points, uint32_t n, uint32_t first_index, const rt_bake_desc& desc, rt_bake_result* d_out)
+{
+    const Scene& s = ctx->scene;
+    return launch_result(ctx, who, bake::launch(ctx->stream, ctx->bake, &ctx->query.status, s.d, s.wide_ok, ctx->prop.multiProcessorCount, d_points, n, first_index, desc, d_out),
+        ": the bake could not be launched (the stack spill area could not be allocated, or the launch failed)");
+}
+
+int rt_scene_bake(rt_ctx* ctx, const void* points, uint32_t n, const rt_bake_desc* desc, rt_bake_result* out)
+{
+    if (ctx && n == 0u) return RT_OK;
+    if (bake_refused(ctx, "rt_scene_bake", points != nullptr, n, desc, out != nullptr) != RT_OK) return RT_ERROR;
+    (void)hipSetDevice(ctx->device);
+    query::Scratch& b = ctx->bake;
+    return staged_call(ctx, "rt_scene_bake", b, {{(void*)points, bake::point_bytes(*desc), 0, true}, {out, sizeof(rt_bake_result), 1, false}}, n, ctx->bake_chunk_points,
+        [&](uint32_t first, uint32_t m) { return bake_launch(ctx, "rt_scene_bake", b.stage[0], m, first, *desc, (rt_bake_result*)b.stage[1]); });
+}
+
+int rt_scene_bake_buffer(rt_ctx* ctx, rt_buffer* points, uint32_t n, const rt_bake_desc* desc, rt_buffer* out)
+{
+    if (ctx && n == 0u) return RT_OK;
+    if (bake_refused(ctx, "rt_scene_bake_buffer", points != nullptr, n, desc, out != nullptr) != RT_OK) return RT_ERROR;
+    if (buffers_refused(ctx, "rt_scene_bake_buffer", {{points, bake::point_bytes(*desc), "points"}, {out, sizeof(rt_bake_result), "out"}}, n) != RT_OK) return RT_ERROR;
+    (void)hipSetDevice(ctx->device);
+    return bake_launch(ctx, "rt_scene_bake_buffer", points->ptr, n, 0u, *desc, (rt_bake_result*)out->ptr);
+}
+
+int rt_debug_bake_rays(rt_ctx* ctx, const void* points, uint32_t n, uint32_t first_index, const rt_bake_desc* desc, rt_ray* rays_out)
+{
+    if (n == 0u) return RT_OK;
+    if (!points || !desc || !rays_out) return fail(ctx, "rt_debug_bake_rays: NULL argument");
+    if (const char* why = bake::desc_refusal(*desc)) return fail(ctx, std::string("rt_debug_bake_rays: ") + why);
+    if ((uint64_t)n * desc->samples > (1ull << 28)) return fail(ctx, "rt_debug_bake_rays: more than 2^28 rays");
+    return host_or_device(ctx, "rt_debug_bake_rays", [&] { bake::debug_rays_host(points, n, first_index, *desc, rays_out); },
+        [&](hipStream_t st) { return bake::debug_rays_device(st, points, n, first_index, *desc, rays_out); });
+}
+
+int rt_debug_bake_reduce(const rt_ray* rays, const uint32_t* occluded, uint32_t n, uint32_t samples, rt_bake_result* out)
+{
+    if (n == 0u) return RT_OK;
+    if (!rays || !occluded || !out) return fail(nullptr, "rt_debug_bake_reduce: NULL argument");
+    if (samples < 16u || samples > 4096u || (samples & (samples - 1u)) != 0u) return fail(nullptr, "rt_debug_bake_reduce: samples must be a power of two in 16 .. 4096");
+    bake::debug_reduce_host(rays, occluded, n, samples, out);
+    return RT_OK;
+}
+
+// ---- the nearest surface point: rt_scene_nearest / rt_scene_nearest_buffer / rt_debug_nearest / rt_debug_nearest_walk (nearest.hip) --
+
+// everything both forms refuse before anything is launched
+static int nearest_refused(rt_ctx* ctx, const char* who, bool points, uint32_t n, bool out, bool surfaces)
+{
+    const std::string name(who);
+    if (opening_refused(ctx, name, {{"points", points || n == 0u}}, {}) != RT_OK) return RT_ERROR;
+    if (!out && !surfaces) return fail(ctx, name + ": no output (out and surfaces are both NULL)");
+    return RT_OK;
+}
+
+static int nearest_launch(rt_ctx* ctx, const char* who, const rt_point* d_points, uint32_t n, rt_nearest* d_out, rt_surface* d_surfaces)
+{
+    const Scene& s = ctx->scene;
+    return launch_result(ctx, who, nearest::launch(ctx->stream, ctx->query, s.d, s.wide_ok, s.n_tris, s.pose ? s.pose->ids : nullptr, ctx->prop.multiProcessorCount, d_points, n,
+        d_out, d_surfaces), QUERY_NOT_LAUNCHED);
+}
+
+int rt_scene_nearest(rt_ctx* ctx, const rt_point* points, uint32_t n, rt_nearest* out, rt_surface* surfaces)
+{
+    if (ctx && n == 0u) return RT_OK;
+    if (nearest_refused(ctx, "rt_scene_nearest", points != nullptr, n, out != nullptr, surfaces != nullptr) != RT_OK) return RT_ERROR;
+    (void)hipSetDevice(ctx->device);
+    query::Scratch& q = ctx->query;
+    // the ray queries' staging arrays: [0] the points, [1] the records, [3] the surfaces
+    return staged_call(ctx, "rt_scene_nearest", q, {{(void*)points, sizeof(rt_point), 0, true}, {out, sizeof(rt_nearest), 1, false}, {surfaces, sizeof(rt_surface), 3, false}}, n,
+        (uint32_t)query::CHUNK_RAYS, [&](uint32_t, uint32_t m)
+        {
+            return nearest_launch(ctx, "rt_scene_nearest", (const rt_point*)q.stage[0], m, out ? (rt_nearest*)q.stage[1] : nullptr, surfaces ? (rt_surface*)q.stage[3] : nullptr);
+        });
+}
+
+int rt_scene_nearest_buffer(rt_ctx* ctx, rt_buffer* points, uint32_t n, rt_buffer* out, rt_buffer* surfaces)
+{
+    if (ctx && n == 0u) return RT_OK;
+    if (nearest_refused(ctx, "rt_scene_nearest_buffer", points != nullptr, n, out != nullptr, surfaces != nullptr) != RT_OK) return RT_ERROR;
+    if (buffers_refused(ctx, "rt_scene_nearest_buffer", {{points, sizeof(rt_point), "points"}, {out, sizeof(rt_nearest), "out"}, {surfaces, sizeof(rt_surface), "surfaces"}}, n) != RT_OK)
+        return RT_ERROR;
+    (void)hipSetDevice(ctx->device);
+    return nearest_launch(ctx, "rt_scene_nearest_buffer", (const rt_point*)points->ptr, n, out ? (rt_nearest*)out->ptr : nullptr, surfaces ? (rt_surface*)surfaces->ptr : nullptr);
+}
+
+int rt_debug_nearest(rt_ctx* ctx, const rt_triangle* triangles, uint32_t num_triangles, const rt_point* points, uint32_t n, rt_nearest* out)
+{
+    if (n == 0u) return RT_OK;
+    if (!points || !out || (!triangles && num_triangles > 0u)) return fail(ctx, "rt_debug_nearest: NULL argument");
+    return host_or_device(ctx, "rt_debug_nearest", [&] { nearest::brute_host(triangles, num_triangles, points, n, out); },
+        [&](hipStream_t st) { return nearest::brute_device(st, triangles, num_triangles, points, n, out); });
+}
+
+int rt_debug_nearest_walk(const rt_bvh_node* nodes, uint32_t num_nodes, const rt_triangle* triangles, uint32_t num_triangles, int wide, const rt_point* points,
+    uint32_t n, rt_nearest* out, uint32_t* triangles_tested)
+{
+    if (n == 0u) return RT_OK;
+    if (!nodes || num_nodes == 0u || !triangles || !points || !out) return fail(nullptr, "rt_debug_nearest_walk: NULL argument");
+    if (wide != 0 && wide != 1) return fail(nullptr, std::string("rt_debug_nearest_walk") + WIDE_REFUSED);
+    if (const char* why = nearest::walk_host(nodes, num_nodes, triangles, num_triangles, wide != 0, points, n, out, triangles_tested))
+        return fail(nullptr, std::string("rt_debug_nearest_walk: ") + why);
+    return RT_OK;
+}
+
+// ---- every surface a ray crosses: rt_scene_trace_all / rt_scene_trace_all_buffer / rt_debug_trace_all (all_hits.hip) ---------------
+
+// everything both forms refuse before anything is launched
+static int all_hits_refused(rt_ctx* ctx, const char* who, bool rays, uint32_t n, uint32_t max_hits, bool out, bool hits, bool surfaces)
+{
+    const std::string name(who);
+    if (opening_refused(ctx, name, {{"rays", rays || n == 0u}}, {{"out", out}}) != RT_OK) return RT_ERROR;
+    if (max_hits > RT_ALL_HITS_MAX) return fail(ctx, name + ": max_hits is above RT_ALL_HITS_MAX");
+    if (max_hits == 0u && (hits || surfaces)) return fail(ctx, name + ": hits or surfaces given with max_hits == 0: pass NULL");
+    return RT_OK;
+}
+
+static int all_hits_launch(rt_ctx* ctx, const char* who, const rt_ray* d_rays, uint32_t n, uint32_t max_hits, rt_ray_hits* d_out, rt_hit* d_hits, rt_surface* d_surfaces)
+{
+    const Scene& s = ctx->scene;
+    return launch_result(ctx, who, all_hits::launch(ctx->stream, ctx->query, s.d, s.wide_ok, s.n_tris, s.pose ? s.pose->ids : nullptr, ctx->prop.multiProcessorCount, d_rays, n,
+        max_hits, d_out, d_hits, d_surfaces), QUERY_NOT_LAUNCHED);
+}
+
+int rt_scene_trace_all(rt_ctx* ctx, const rt_ray* rays, uint32_t n, uint32_t max_hits, rt_ray_hits* out, rt_hit* hits, rt_surface* surfaces)
+{
+    if (ctx && n == 0u) return RT_OK;
+    if (all_hits_refused(ctx, "rt_scene_trace_all", rays != nullptr, n, max_hits, out != nullptr, hits != nullptr, surfaces != nullptr) != RT_OK) return RT_ERROR;
+    (void)hipSetDevice(ctx->device);
+    query::Scratch& q = ctx->query;
+    // the ray queries' staging arrays: [0] the rays, [1] the hits, [2] the records, [3] the surfaces; a chunk's rays times max_hits stay within a ray query's chunk
+    const uint32_t per_ray = max_hits > 0u ? max_hits : 1u;
+    return staged_call(ctx, "rt_scene_trace_all", q, {{(void*)rays, sizeof(rt_ray), 0, true}, {hits, sizeof(rt_hit) * per_ray, 1, false}, {out, sizeof(rt_ray_hits), 2, false},
+        {surfaces, sizeof(rt_surface) * per_ray, 3, false}}, n, (uint32_t)query::CHUNK_RAYS / per_ray, [&](uint32_t, uint32_t m)
+        {
+            return all_hits_launch(ctx, "rt_scene_trace_all", (const rt_ray*)q.stage[0], m, max_hits, (rt_ray_hits*)q.stage[2], hits ? (rt_hit*)q.stage[1] : nullptr,
+                surfaces ? (rt_surface*)q.stage[3] : nullptr);
+        });
+}
+
+int rt_scene_trace_all_buffer(rt_ctx* ctx, rt_buffer* rays, uint32_t n, uint32_t max_hits, rt_buffer* out, rt_buffer* hits, rt_buffer* surfaces)
+{
+    if (ctx && n == 0u) return RT_OK;
+    if (all_hits_refused(ctx, "rt_scene_trace_all_buffer", rays != nullptr, n, max_hits, out != nullptr, hits != nullptr, surfaces != nullptr) != RT_OK) return RT_ERROR;
+    if (buffers_refused(ctx, "rt_scene_trace_all_buffer", {{rays, sizeof(rt_ray), "rays"}, {out, sizeof(rt_ray_hits), "out"}, {hits, sizeof(rt_hit) * max_hits, "hits"},
+            {surfaces, sizeof(rt_surface) * max_hits, "surfaces"}}, n) != RT_OK)
+        return RT_ERROR;
+    (void)hipSetDevice(ctx->device);
+    return all_hits_launch(ctx, "rt_scene_trace_all_buffer", (const rt_ray*)rays->ptr, n, max_hits, (rt_ray_hits*)out->ptr, hits ? (rt_hit*)hits->ptr : nullptr,
+        surfaces ? (rt_surface*)surfaces->ptr : nullptr);
+}
+
+int rt_debug_trace_all(rt_ctx* ctx, const rt_bvh_node* nodes, uint32_t num_nodes, const rt_triangle* triangles, uint32_t num_triangles, const rt_ray* rays, uint32_t n,
+    uint32_t max_hits, rt_ray_hits* out, rt_hit* hits)
+{
+    if (n == 0u) return RT_OK;
+    if (!nodes || num_nodes == 0u || !rays || !out || (!triangles && num_triangles > 0u) || (!hits && max_hits > 0u)) return fail(ctx, "rt_debug_trace_all: NULL argument");
+    if (max_hits > RT_ALL_HITS_MAX) return fail(ctx, "rt_debug_trace_all: max_hits is above RT_ALL_HITS_MAX");
+    if (const char* why = all_hits::leaves_refused(nodes, num_nodes, num_triangles)) return fail(ctx, std::string("rt_debug_trace_all: ") + why);
+    return host_or_device(ctx, "rt_debug_trace_all", [&] { all_hits::brute_host(nodes, num_nodes, triangles, rays, n, max_hits, out, hits); },
+        [&](hipStream_t st) { return all_hits::brute_device(st, nodes, num_nodes, triangles, num_triangles, rays, n, max_hits, out, hits); });
+}
+
+// ---- every triangle within a radius: rt_scene_within / rt_scene_within_buffer / rt_debug_within / rt_debug_within_walk (within.hip) --
+
+// what every entry refuses of max_near and options
+static const char* within_shape_refused(uint32_t max_near, uint32_t options)
+{
+    if (max_near > RT_WITHIN_MAX) return "max_near is above RT_WITHIN_MAX";
+    if (options & ~RT_WITHIN_K_NEAREST) return "unknown option bits";
+    if ((options & RT_WITHIN_K_NEAREST) && max_near == 0u) return "RT_WITHIN_K_NEAREST needs max_near >= 1";
+    return nullptr;
+}
+
+// everything both scene forms refuse before anything is launched
+static int within_refused(rt_ctx* ctx, const char* who, bool points, uint32_t n, uint32_t max_near, uint32_t options, bool out, bool near, bool surfaces)
+{
+    const std::string name(who);
+    if (opening_refused(ctx, name, {}, {{"points", points || n == 0u}, {"out", out}}) != RT_OK) return RT_ERROR;
+    if (const char* why = within_shape_refused(max_near, options)) return fail(ctx, name + ": " + why);
+    if (max_near == 0u && (near || surfaces)) return fail(ctx, name + ": near or surfaces given with max_near == 0: pass NULL");
+    return RT_OK;
+}
+
+static int within_launch(rt_ctx* ctx, const char* who, const rt_point* d_points, uint32_t n, uint32_t max_near, uint32_t options, rt_point_hits* d_out,
+    rt_nearest* d_near, rt_surface* d_surfaces)
+{
+    const Scene& s = ctx->scene;
+    return launch_result(ctx, who, within::launch(ctx->stream, ctx->query, s.d, s.wide_ok, s.n_tris, s.pose ? s.pose->ids : nullptr, ctx->prop.multiProcessorCount, d_points, n,
+        max_near, options, d_out, d_near, d_surfaces), QUERY_NOT_LAUNCHED);
+}
+
+int rt_scene_within(rt_ctx* ctx, const rt_point* points, uint32_t n, uint32_t max_near, uint32_t options, rt_point_hits* out, rt_nearest* near, rt_surface* surfaces)
+{
+    if (ctx && n == 0u) return RT_OK;
+    if (within_refused(ctx, "rt_scene_within", points != nullptr, n, max_near, options, out != nullptr, near != nullptr, surfaces != nullptr) != RT_OK) return RT_ERROR;
+    (void)hipSetDevice(ctx->device);
+    query::Scratch& q = ctx->query;
+    // the ray queries' staging arrays: [0] the points, [1] the members' records, [2] the points' records, [3] the surfaces; a chunk's points times max_near
+    // stay within a ray query's chunk
+    const uint32_t per_point = max_near > 0u ? max_near : 1u;
+    return staged_call(ctx, "rt_scene_within", q, {{(void*)points, sizeof(rt_point), 0, true}, {near, sizeof(rt_nearest) * per_point, 1, false},
+        {out, sizeof(rt_point_hits), 2, false}, {surfaces, sizeof(rt_surface) * per_point, 3, false}}, n, (uint32_t)query::CHUNK_RAYS / per_point, [&](uint32_t, uint32_t m)
+        {
+            return within_launch(ctx, "rt_scene_within", (const rt_point*)q.stage[0], m, max_near, options, (rt_point_hits*)q.stage[2], near ? (rt_nearest*)q.stage[1] : nullptr,
+                surfaces ? (rt_surface*)q.stage[3] : nullptr);
+        });
+}
+
+int rt_scene_within_buffer(rt_ctx* ctx, rt_buffer* points, uint32_t n, uint32_t max_near, uint32_t options, rt_buffer* out, rt_buffer* near, rt_buffer* surfaces)
+{
+    if (ctx && n == 0u) return RT_OK;
+    if (within_refused(ctx, "rt_scene_within_buffer", points != nullptr, n, max_near, options, out != nullptr, near != nullptr, surfaces != nullptr) != RT_OK)
+        return RT_ERROR;
+    if (buffers_refused(ctx, "rt_scene_within_buffer", {{points, sizeof(rt_point), "points"}, {out, sizeof(rt_point_hits), "out"}, {near, sizeof(rt_nearest) * max_near, "near"},
+            {surfaces, sizeof(rt_surface) * max_near, "surfaces"}}, n) != RT_OK)
+        return RT_ERROR;
+    (void)hipSetDevice(ctx->device);
+    return within_launch(ctx, "rt_scene_within_buffer", (const rt_point*)points->ptr, n, max_near, options, (rt_point_hits*)out->ptr, near ? (rt_nearest*)near->ptr : nullptr,
+        surfaces ? (rt_surface*)surfaces->ptr : nullptr);
+}
+
+int rt_debug_within(rt_ctx* ctx, const rt_triangle* triangles, uint32_t num_triangles, const rt_point* points, uint32_t n, uint32_t max_near, uint32_t options,
+    rt_point_hits* out, rt_nearest* near)
+{
+    if (n == 0u) return RT_OK;
+    if (const char* why = within_shape_refused(max_near, options)) return fail(ctx, std::string("rt_debug_within: ") + why);
+    if (!points || !out || (!triangles && num_triangles > 0u) || (!near && max_near > 0u)) return fail(ctx, "rt_debug_within: NULL argument");
+    return host_or_device(ctx, "rt_debug_within", [&] { within::brute_host(triangles, num_triangles, points, n, max_near, options, out, near); },
+        [&](hipStream_t st) { return within::brute_device(st, triangles, num_triangles, points, n, max_near, options, out, near); });
+}
+
+int rt_debug_within_walk(const rt_bvh_node* nodes, uint32_t num_nodes, const rt_triangle* triangles, uint32_t num_triangles, int wide, const rt_point* points,
+    uint32_t n, uint32_t max_near, uint32_t options, rt_point_hits* out, rt_nearest* near, uint32_t* triangles_tested)
+{
+    if (n == 0u) return RT_OK;
+    if (const char* why = within_shape_refused(max_near, options)) return fail(nullptr, std::string("rt_debug_within_walk: ") + why);
+    if (!nodes || num_nodes == 0u || !triangles || !points || !out || (!near && max_near > 0u)) return fail(nullptr, "rt_debug_within_walk: NULL argument");
+    if (wide != 0 && wide != 1) return fail(nullptr, std::string("rt_debug_within_walk") + WIDE_REFUSED);
+    if (const char* why = within::walk_host(nodes, num_nodes, triangles, num_triangles, wide != 0, points, n, max_near, options, out, near, triangles_tested))
+        return fail(nullptr, std::string("rt_debug_within_walk: ") + why);
+    return RT_OK;
+}
+
+// ---- the triangles of a convex region, and the select: rt_scene_overlap / rt_scene_overlap_buffer / rt_scene_select / rt_scene_select_buffer /
+// rt_debug_overlap / rt_debug_overlap_walk / rt_debug_select / rt_debug_rect_region (region.hip) ------------------------------------
+
+// everything both overlap forms refuse before anything is launched
+static int overlap_refused(rt_ctx* ctx, const char* who, bool regions, uint32_t n, uint32_t max_list, bool out, bool members)
+{
+    const std::string name(who);
+    if (opening_refused(ctx, name, {}, {{"regions", regions || n == 0u}, {"out", out}}) != RT_OK) return RT_ERROR;
+    if (max_list > RT_REGION_LIST_MAX) return fail(ctx, name + ": max_list is above RT_REGION_LIST_MAX");
+    if (max_list == 0u && members) return fail(ctx, name + ": members given with max_list == 0: pass NULL");
+    return RT_OK;
+}
+
+static int overlap_launch(rt_ctx* ctx, const char* who, const rt_region* d_regions, uint32_t n, uint32_t max_list, rt_region_hits* d_out, rt_region_member* d_members)
+{
+    const Scene& s = ctx->scene;
+    return launch_result(ctx, who, region::launch(ctx->stream, ctx->query, s.d, s.wide_ok, ctx->prop.multiProcessorCount, d_regions, n, max_list, d_out, d_members),
+        QUERY_NOT_LAUNCHED);
+}
+
+int rt_scene_overlap(rt_ctx* ctx, const rt_region* regions, uint32_t n, uint32_t max_list, rt_region_hits* out, rt_region_member* members)
+{
+    if (ctx && n == 0u) return RT_OK;
+    if (overlap_refused(ctx, "rt_scene_overlap", regions != nullptr, n, max_list, out != nullptr, members != nullptr) != RT_OK) return RT_ERROR;
+    (void)hipSetDevice(ctx->device);
+    query::Scratch& q = ctx->query;
+    // the ray queries' staging arrays: [0] the regions, [1] the members, [2] the regions' records; a chunk's regions times max_list stay within a ray query's chunk
+    const uint32_t per_region = max_list > 0u ? max_list : 1u;
+    return staged_call(ctx, "rt_scene_overlap", q, {{(void*)regions, sizeof(rt_region), 0, true}, {members, sizeof(rt_region_member) * per_region, 1, false},
+        {out, sizeof(rt_region_hits), 2, false}}, n, (uint32_t)query::CHUNK_RAYS / per_region, [&](uint32_t, uint32_t m)
+        {
+            return overlap_launch(ctx, "rt_scene_overlap", (const rt_region*)q.stage[0], m, max_list, (rt_region_hits*)q.stage[2], members ? (rt_region_member*)q.stage[1] : nullptr);
+        });
+}
+
+int rt_scene_overlap_buffer(rt_ctx* ctx, rt_buffer* regions, uint32_t n, uint32_t max_list, rt_buffer* out, rt_buffer* members)
+{
+    if (ctx && n == 0u) return RT_OK;
+    if (overlap_refused(ctx, "rt_scene_overlap_buffer", regions != nullptr, n, max_list, out != nullptr, members != nullptr) != RT_OK) return RT_ERROR;
+    if (buffers_refused(ctx, "rt_scene_overlap_buffer", {{regions, sizeof(rt_region), "regions"}, {out, sizeof(rt_region_hits), "out"},
+            {members, sizeof(rt_region_member) * max_list, "members"}}, n) != RT_OK)
+        return RT_ERROR;
+    (void)hipSetDevice(ctx->device);
+    return overlap_launch(ctx, "rt_scene_overlap_buffer", (const rt_region*)regions->ptr, n, max_list, (rt_region_hits*)out->ptr, members ? (rt_region_member*)members->ptr : nullptr);
+}
+
+int rt_debug_overlap(rt_ctx* ctx, const rt_triangle* triangles, uint32_t num_triangles, const rt_region* regions, uint32_t n, uint32_t max_list, rt_region_hits* out,
+    rt_region_member* members)
+{
+    if (n == 0u) return RT_OK;
+    if (max_list > RT_REGION_LIST_MAX) return fail(ctx, "rt_debug_overlap: max_list is above RT_REGION_LIST_MAX");
+    if (!regions || !out || (!triangles && num_triangles > 0u) || (!members && max_list > 0u)) return fail(ctx, "rt_debug_overlap: NULL argument");
+    return host_or_device(ctx, "rt_debug_overlap", [&] { region::brute_host(triangles, num_triangles, regions, n, max_list, out, members); },
+        [&](hipStream_t st) { return region::brute_device(st, triangles, num_triangles, regions, n, max_list, out, members); });
+}
+
+int rt_debug_overlap_walk(const rt_bvh_node* nodes, uint32_t num_nodes, const rt_triangle* triangles, uint32_t num_triangles, int wide, const rt_region* regions,
+    uint32_t n, uint32_t max_list, rt_region_hits* out, rt_region_member* members, uint32_t* triangles_tested)
+{
+    if (n == 0u) return RT_OK;
+    if (max_list > RT_REGION_LIST_MAX) return fail(nullptr, "rt_debug_overlap_walk: max_list is above RT_REGION_LIST_MAX");
+    if (!nodes || num_nodes == 0u || !triangles || !regions || !out || (!members && max_list > 0u)) return fail(nullptr, "rt_debug_overlap_walk: NULL argument");
+    if (wide != 0 && wide != 1) return fail(nullptr, std::string("rt_debug_overlap_walk") + WIDE_REFUSED);
+    if (const char* why = region::walk_host(nodes, num_nodes, triangles, num_triangles, wide != 0, regions, n, max_list, out, members, triangles_tested))
+        return fail(nullptr, std::string("rt_debug_overlap_walk: ") + why);
+    return RT_OK;
+}
+
+// everything both select forms refuse before anything is launched
+static int select_refused(rt_ctx* ctx, const char* who, bool regions, uint32_t n, bool per_triangle, bool per_object)
+{
+    const std::string name(who);
+    if (opening_refused(ctx, name, {}, {{"regions", regions}}) != RT_OK) return RT_ERROR;
+    if (n == 0u || n > RT_SELECT_MAX_REGIONS) return fail(ctx, name + ": n must be 1 .. RT_SELECT_MAX_REGIONS (a bit per region in a 32-bit word)");
+    if (!per_triangle && !per_object) return fail(ctx, name + ": no output (every output is NULL)");
+    if (per_object && !ctx->scene.pose) return fail(ctx, name + ": the per-object outputs need rt_scene_set_objects");
+    return RT_OK;
+}
+
+static int select_launch(rt_ctx* ctx, const char* who, const rt_region* d_regions, uint32_t n, uint32_t* d_touching, uint32_t* d_inside, uint32_t* d_object_touching,
+    uint32_t* d_object_inside)
+{
+    const Scene& s = ctx->scene;
+    return launch_result(ctx, who, region::select(ctx->stream, ctx->query, s.d, s.n_tris, s.pose ? s.pose->ids : nullptr, s.pose ? s.pose->n_objects : 0u, d_regions, n,
+        d_touching, d_inside, d_object_touching, d_object_inside), ": the select could not be launched (out of device memory, or a launch failed)");
+}
+
+int rt_scene_select(rt_ctx* ctx, const rt_region* regions, uint32_t n, uint32_t* touching, uint32_t* inside, uint32_t* object_touching, uint32_t* object_inside)
+{
+    if (select_refused(ctx, "rt_scene_select", regions != nullptr, n, touching || inside, object_touching || object_inside) != RT_OK) return RT_ERROR;
+    (void)hipSetDevice(ctx->device);
+    const Scene& s = ctx->scene;
+    const size_t tri_bytes = (size_t)s.n_tris * 4u, obj_bytes = (size_t)(s.pose ? s.pose->n_objects : 0u) * 4u;
+    dev::Temps tmp(ctx->stream);
+    void* const d_regions = tmp.get(regions, (size_t)n * sizeof(rt_region));
+    uint32_t* const d_t = touching ? (uint32_t*)tmp.get(nullptr, tri_bytes) : nullptr;
+    uint32_t* const d_i = inside ? (uint32_t*)tmp.get(nullptr, tri_bytes) : nullptr;
+    uint32_t* const d_ot = object_touching ? (uint32_t*)tmp.get(nullptr, obj_bytes) : nullptr;
+    uint32_t* const d_oi = object_inside ? (uint32_t*)tmp.get(nullptr, obj_bytes) : nullptr;
+    if (!d_regions || (touching && !d_t) || (inside && !d_i) || (object_touching && !d_ot) || (object_inside && !d_oi))
+        return fail(ctx, "rt_scene_select: out of device memory");
+    if (select_launch(ctx, "rt_scene_select", (const rt_region*)d_regions, n, d_t, d_i, d_ot, d_oi) != RT_OK) return RT_ERROR;
+    if (touching) HIPCHK(ctx, hipMemcpyAsync(touching, d_t, tri_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    if (inside) HIPCHK(ctx, hipMemcpyAsync(inside, d_i, tri_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    if (object_touching) HIPCHK(ctx, hipMemcpyAsync(object_touching, d_ot, obj_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    if (object_inside) HIPCHK(ctx, hipMemcpyAsync(object_inside, d_oi, obj_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return RT_OK;
+}
+
+int rt_scene_select_buffer(rt_ctx* ctx, rt_buffer* regions, uint32_t n, rt_buffer* touching, rt_buffer* inside, rt_buffer* object_touching, rt_buffer* object_inside)
+{
+    if (select_refused(ctx, "rt_scene_select_buffer", regions != nullptr, n, touching || inside, object_touching || object_inside) != RT_OK) return RT_ERROR;
+    const Scene& s = ctx->scene;
+    if (buffers_refused(ctx, "rt_scene_select_buffer", {{regions, sizeof(rt_region), "regions"}}, n) != RT_OK) return RT_ERROR;
+    if (buffers_refused(ctx, "rt_scene_select_buffer", {{touching, 4u, "touching"}, {inside, 4u, "inside"}}, s.n_tris) != RT_OK) return RT_ERROR;
+    if (buffers_refused(ctx, "rt_scene_select_buffer", {{object_touching, 4u, "object_touching"}, {object_inside, 4u, "object_inside"}}, s.pose ? s.pose->n_objects : 0u) != RT_OK)
+        return RT_ERROR;
+    (void)hipSetDevice(ctx->device);
+    auto p = [](rt_buffer* b) { return b ? (uint32_t*)b->ptr : nullptr; };
+    return select_launch(ctx, "rt_scene_select_buffer", (const rt_region*)regions->ptr, n, p(touching), p(inside), p(object_touching), p(object_inside));
+}
+
+int rt_debug_select(rt_ctx* ctx, const rt_triangle* triangles, uint32_t num_triangles, const uint32_t* object_of_triangle, uint32_t num_objects, const rt_region* regions,
+    uint32_t n, uint32_t* touching, uint32_t* inside, uint32_t* object_touching, uint32_t* object_inside)
+{
+    if (n == 0u || n > RT_SELECT_MAX_REGIONS) return fail(ctx, "rt_debug_select: n must be 1 .. RT_SELECT_MAX_REGIONS (a bit per region in a 32-bit word)");
+    if (!regions || ((!triangles || !touching || !inside) && num_triangles > 0u)) return fail(ctx, "rt_debug_select: NULL argument");
+    if (object_of_triangle && (num_objects == 0u || !pose::ids_in_range(object_of_triangle, num_triangles, num_objects)))
+        return fail(ctx, "rt_debug_select: an object index is not below num_objects");
+    return host_or_device(ctx, "rt_debug_select",
+        [&] { region::select_host(triangles, num_triangles, object_of_triangle, num_objects, regions, n, touching, inside, object_touching, object_inside); },
+        [&](hipStream_t st) { return region::select_device(st, triangles, num_triangles, object_of_triangle, num_objects, regions, n, touching, inside, object_touching, object_inside); });
+}
+
+int rt_debug_rect_region(const rt_camera* camera, uint32_t width, uint32_t height, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, float t_near, float t_far,
+    rt_region* out)
+{
+    if (!camera || !out) return fail(nullptr, "rt_debug_rect_region: NULL argument");
+    if (const char* why = region::rect_refused(width, height, x0, y0, x1, y1)) return fail(nullptr, std::string("rt_debug_rect_region: ") + why);
+    *out = region::rect_region(*camera, width, height, x0, y0, x1, y1, t_near, t_far);
+    return RT_OK;
+}
+
+} // extern "C"
