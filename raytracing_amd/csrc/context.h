@@ -1,9 +1,9 @@
-// context.h -- what a context is, for the translation units that implement entry points on it (rt_hip.hip, scene_queries.cpp): the uploaded scene and its
-// trees, the context and the buffer records behind the C-ABI's opaque handles, how an entry point fails, and the device copies an upload makes.  Internal:
-// never installed, never included by include/.  A feature unit gets the scene (ctx->scene: the kernels' view `d`, the trees, the objects' table), the
-// queries' scratch areas, the stream, the device and its properties.  It does not get frames -- rt_frame is rt_hip.hip's alone, so nothing here can wait
-// for a frame's streams or drop what it traced ahead (quiesce, sync_frame_streams, ahead_discard: an entry that needs those belongs in rt_hip.hip) -- nor
-// the fold adaptation's state, which is a name only.
+// context.h -- what a context is, for the translation units that implement entry points on it (rt_hip.hip, scene_upload.cpp, scene_queries.cpp): the
+// uploaded scene and its trees, the context and the buffer records behind the C-ABI's opaque handles, how an entry point fails, and the device copies an
+// upload makes.  Internal: never installed, never included by include/.  A feature unit gets the scene (ctx->scene: the kernels' view `d`, the trees, the
+// objects' table), the queries' scratch areas, the stream, the device and its properties.  It may ask for everything in flight to drain before it frees or
+// rewrites what a launch could still read (quiesce).  It still cannot see a frame -- rt_frame is rt_hip.hip's alone, and so are sync_frame_streams and
+// ahead_discard, which quiesce calls there -- nor the fold adaptation's state, which is a name only here (fold_adapt.h, for the two units that work on it).
 #pragma once
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>
@@ -21,7 +21,7 @@
 
 namespace context
 {
-struct FoldAdapt;                          // RT_CTX_OPT_ADAPTIVE_FOLD: the state of a scene's fold adaptation (fold_adapt_impl.h, rt_hip.hip's)
+struct FoldAdapt;                          // RT_CTX_OPT_ADAPTIVE_FOLD: the state of a scene's fold adaptation (fold_adapt.h)
 
 // One 4-wide quantized tree on the device: its records (whoever holds the value owns them), how many (0 with a leaf root), the record a walk enters at.
 struct WideTree { void* recs = nullptr; uint32_t n = 0, entry = 0; };
@@ -60,7 +60,7 @@ struct Scene
     // axis, e.g. an overhead light (0, -1, 0)): k_trace_w4 would hand every one of them to its small follow-up launch,
     // so the automatic choice traces the shadow queue with k_trace2 (select-form slab test inline, full residency)
     bool slow_shadow = false;
-    // RT_CTX_OPT_REFITTABLE (refit_impl.h): what rt_scene_refit keeps beside the scene; nullptr = the option was off at upload (or refit_refusal says why not)
+    // RT_CTX_OPT_REFITTABLE (scene_upload.cpp): what rt_scene_refit keeps beside the scene; nullptr = the option was off at upload (or refit_refusal says why not)
     refit::State* refit = nullptr;
     std::string refit_refusal;
     bool refit_wide_built = false;   // wide_ok as upload left it (a refit that meets a record that no longer qualifies clears wide_ok until one qualifies again)
@@ -71,7 +71,7 @@ struct Scene
     // allocation failed: treated as off).  pose_valid: a refit has filled it.
     void* pose_snap = nullptr;
     bool pose_valid = false;
-    // rt_scene_set_objects (pose_impl.h): the rest pose, every triangle's object and the staging area of rt_scene_pose; nullptr = no objects set
+    // rt_scene_set_objects (scene_upload.cpp): the rest pose, every triangle's object and the staging area of rt_scene_pose; nullptr = no objects set
     pose::State* pose = nullptr;
 };
 } // namespace context
@@ -143,4 +143,19 @@ int scene_array(rt_ctx* ctx, void** field, const void* src, size_t bytes);
 // Ray queries: the walk's status word (pinned host memory; bit 0: a traversal stack ran over its bound, query_kernels.h), read and cleared wherever the
 // context's stream has just been waited for -- rt_scene_trace, rt_finish, rt_buffer_read -- so that the buffer form's queries report it too.
 int query_check_status(rt_ctx* ctx, const char* who);
+
+// Nothing in flight may still read what is about to be freed or rewritten: batches traced ahead are dropped (RT_OPT_SAMPLES_AHEAD), and every stream a frame
+// launches on -- side streams, pipes, banks -- has drained.  rt_hip.hip's, where the frames are.
+int quiesce(rt_ctx* ctx);
+
+// Everything a scene holds on the device and beside it (its adaptation, refit and pose states) is freed and `s` is an empty scene again.  scene_upload.cpp's:
+// rt_scene_upload and an upload that ends early call it there, rt_ctx_destroy from rt_hip.hip.
+void free_scene(Scene& s);
+
+// The re-layout kernels' four launches on ctx's stream (relayout_kernels.h; they are of the hot path's code object, so rt_hip.hip launches them for
+// Upload::relayout_on_device): the reference's node and triangle arrays on the device -> the child-pair records `nodes` in the order `index` gives, the 64-byte
+// and 128-byte triangle records; `last` (nt bytes) and `err` (one int, an RL_* code of device_scene.h: the first one wins) are the caller's, cleared on the
+// stream before this.  RT_OK: all four were launched.
+int relayout_records(rt_ctx* ctx, const rt_bvh_node* raw_nodes, uint32_t nn, const rt_triangle* raw_tris, uint32_t nt, uint32_t num_materials, const uint32_t* index,
+    uint8_t* last, int* err, float4* nodes, float4* tris_rt, float4* tris_sh);
 } // namespace context

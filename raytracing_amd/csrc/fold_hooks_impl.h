@@ -1,5 +1,7 @@
 // fold_hooks_impl.h -- part of rt_hip.hip's translation unit (included inside its extern "C" block, before rt_integrate): the render-thread side of
-// RT_CTX_OPT_ADAPTIVE_FOLD -- the asynchronous probe frame, the hand-over to the worker (fold_adapt_impl.h), the adoption by pointer exchange, the trigger.
+// RT_CTX_OPT_ADAPTIVE_FOLD -- the asynchronous probe frame, the hand-over to the worker, the adoption by pointer exchange, the trigger.  It reads rt_frame,
+// so it stays with the frames; FoldAdapt itself and what is called on it here -- fold_adapt_worker, fold_view_left, replace_report_line -- are fold_adapt.h's,
+// defined in scene_upload.cpp with the upload's side of the adaptation.
 #pragma once
 
 // ---- RT_CTX_OPT_ADAPTIVE_FOLD: probe, worker hand-over, adoption (FoldAdapt) -------------------------------------------------
@@ -148,20 +150,6 @@ static int fold_adopt(rt_ctx* ctx)
     return RT_OK;
 }
 
-// Has the camera left the view the folds were adapted to?  (tools/fold_weight_study.py --views: a fold adapted to one view costs another view
-// 0 .. + 2 % against the surface-area fold as a rule and up to + 11 % -- street level seen with a fold made from above -- while its own view
-// gains 2 .. 14 %.)  Position by 3 % of the scene's diagonal, direction by 20 degrees, field of view by a tenth.
-static bool fold_view_left(const FoldAdapt& a, const rt_camera& c)
-{
-    const double dx = (double)c.position.x - a.camera.position.x, dy = (double)c.position.y - a.camera.position.y, dz = (double)c.position.z - a.camera.position.z;
-    if (std::sqrt(dx * dx + dy * dy + dz * dz) > 0.03 * a.scene_diagonal) return true;
-    const double la = std::sqrt((double)a.camera.front.x * a.camera.front.x + (double)a.camera.front.y * a.camera.front.y + (double)a.camera.front.z * a.camera.front.z);
-    const double lc = std::sqrt((double)c.front.x * c.front.x + (double)c.front.y * c.front.y + (double)c.front.z * c.front.z);
-    const double dot = (double)c.front.x * a.camera.front.x + (double)c.front.y * a.camera.front.y + (double)c.front.z * a.camera.front.z;
-    if (la > 0.0 && lc > 0.0 && !(dot >= 0.9396926 * la * lc)) return true;
-    return std::fabs((double)c.fov - a.camera.fov) > 0.1 * std::fabs((double)a.camera.fov);
-}
-
 static int fold_adapt_hook(rt_frame* f)
 {
     Scene& s = f->ctx->scene;
@@ -206,75 +194,5 @@ static int fold_adapt_hook(rt_frame* f)
         a->worker = std::thread(fold_adapt_worker, a);
     }
     if (a->state == FoldAdapt::COMPUTING && ((a->mode.load() & 2u) || a->finished.load())) return fold_adopt(f->ctx);
-    return RT_OK;
-}
-
-
-// ---- one adaptation per process GROUP (round 6) ----------------------------------------------------------------------------------------
-// N ranks that tile one image hold the same scene and probe the same low-resolution frame: N identical adaptations (tree rotations on host threads: seconds)
-// for identical records.  Instead one rank adapts and the others TAKE its 4-wide records: rt_scene_export_folds copies the context's current records (the
-// closest-hit rays' and the shadow rays', as adapted so far) to the host, the launcher's own channel carries them (torch.distributed, MPI, a file: 64 bytes
-// per record, ~240 MB for the 2.8 M-triangle scene), rt_scene_import_folds puts them in place of the receiver's own and switches its adaptation off.  The
-// records are indices into the triangle records every rank made from the same scene, so nothing else travels.  Exactness is the fold's: any fold of the same
-// binary tree over the same leaves gives the same results -- and the importer checks what it can: record count, refs within range,
-// leaf refs within the triangle array.
-int rt_scene_export_folds(rt_ctx* ctx, void* closest_records, void* shadow_records, uint32_t capacity, uint32_t* n_closest, uint32_t* n_shadow, uint32_t* entries2)
-{
-    if (!ctx || !n_closest || !n_shadow) return fail(ctx, "rt_scene_export_folds: NULL argument");
-    Scene& s = ctx->scene;
-    if (!s.valid || !s.wide_ok || !s.trees[TREE_REF].recs) return fail(ctx, "rt_scene_export_folds: the scene has no 4-wide tree");
-    (void)hipSetDevice(ctx->device);
-    const bool own_shadow = s.shadow == TREE_SHADOW;
-    const uint32_t n_cl = s.closest_tree().n;                                                 // (tolerance mode: the closest-hit rays' own tree)
-    *n_closest = n_cl;
-    *n_shadow = own_shadow ? s.shadow_tree().n : 0u;
-    if (entries2) { entries2[0] = s.d.w_entry_ref; entries2[1] = s.d.w_sh_entry_ref; }
-    if (!closest_records) return RT_OK;                                                       // size query
-    if (n_cl > capacity || *n_shadow > capacity) return fail(ctx, "rt_scene_export_folds: capacity too small");
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    HIPCHK(ctx, hipMemcpy(closest_records, s.d.wnodes, (size_t)n_cl * sizeof(WideNode), hipMemcpyDeviceToHost));
-    if (own_shadow && shadow_records) HIPCHK(ctx, hipMemcpy(shadow_records, s.d.wnodes_sh, (size_t)s.shadow_tree().n * sizeof(WideNode), hipMemcpyDeviceToHost));
-    return RT_OK;
-}
-
-int rt_scene_import_folds(rt_ctx* ctx, const void* closest_records, uint32_t n_closest, uint32_t entry_closest, const void* shadow_records, uint32_t n_shadow, uint32_t entry_shadow)
-{
-    if (!ctx || !closest_records || n_closest == 0) return fail(ctx, "rt_scene_import_folds: NULL argument");
-    Scene& s = ctx->scene;
-    if (!s.valid || !s.wide_ok) return fail(ctx, "rt_scene_import_folds: the scene has no 4-wide tree to replace (upload it first, with RT_CTX_OPT_WIDE_BVH = 1)");
-    if (n_closest >= (1u << 26) || n_shadow >= (1u << 26)) return fail(ctx, "rt_scene_import_folds: too many records");
-    (void)hipSetDevice(ctx->device);
-    // what can be checked: every ref is a record of the same array, a leaf inside the triangle array, or empty
-    const uint32_t nt = s.n_tris;
-    auto sane = [&](const WideNode* r, uint32_t n, uint32_t entry) -> bool
-    {
-        if (entry >= n) return false;
-        for (uint32_t i = 0; i < n; ++i)
-            for (uint32_t ref : r[i].ref)
-            {
-                if (ref == RT_EMPTY_REF) continue;
-                if (ref & RT_LEAF_BIT) { if ((ref & ~RT_LEAF_BIT) >= nt) return false; }
-                else if (ref >= n) return false;
-            }
-        return true;
-    };
-    if (!sane((const WideNode*)closest_records, n_closest, entry_closest)) return fail(ctx, "rt_scene_import_folds: the closest-hit records do not fit this scene (a ref outside the records / the triangles)");
-    if (n_shadow && (!shadow_records || !sane((const WideNode*)shadow_records, n_shadow, entry_shadow))) return fail(ctx, "rt_scene_import_folds: the shadow records do not fit this scene");
-    // nothing in flight may still read the records that go: batches traced ahead are dropped, every stream drains, an adaptation of this context's own is abandoned
-    if (quiesce(ctx) != RT_OK) return RT_ERROR;
-    if (s.adapt) { drop_fold_adapt(s.adapt); s.adapt = nullptr; }
-    dev::Mem cl, sh;
-    int rc = dev_fill(ctx, "rt_scene_import_folds", cl, closest_records, (size_t)n_closest * sizeof(WideNode));
-    if (rc == RT_OK && n_shadow) rc = dev_fill(ctx, "rt_scene_import_folds", sh, shadow_records, (size_t)n_shadow * sizeof(WideNode));
-    if (rc == RT_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = fail(ctx, "rt_scene_import_folds: upload failed");
-    if (rc != RT_OK) { (void)hipGetLastError(); return RT_ERROR; }
-    // the tree the closest-hit rays walk (their own in the tolerance mode) and the shadow rays' own are replaced; without shadow records the shadow rays
-    // walk what the closest-hit rays walk
-    dev::Mem old_cl(s.replace_tree(s.closest, WideTree{cl.release(), n_closest, entry_closest}).recs);
-    dev::Mem old_sh(s.replace_tree(TREE_SHADOW, WideTree{sh.release(), n_shadow, entry_shadow}).recs);
-    s.walk_trees(s.closest, n_shadow ? TREE_SHADOW : s.closest);
-    char line[200];
-    snprintf(line, sizeof(line), "imported folds: %u closest-hit + %u shadow records taken from another context of the group; this context's own adaptation is off\n", n_closest, n_shadow);
-    replace_report_line(s.tree_report, "imported folds", line);
     return RT_OK;
 }

@@ -37,7 +37,7 @@
 #pragma once
 #include "device_math.h"
 #include "rt_types.h"
-#include "device_scene.h"     // DScene, the kernels' view of an uploaded scene (shared with the host units that hold one: context.h)
+#include "device_scene.h"     // DScene, the kernels' view of an uploaded scene (shared with the host units that hold one: context.h); DCounters
 
 #define RT_LEAF_BIT 0x80000000u
 #define RT_EMPTY_REF 0xFFFFFFFFu
@@ -106,33 +106,7 @@ RT_DEV uint32_t tile_global_row(const DTile& t, uint32_t ly)
     return (band * t.nranks + t.rank) * t.band_h + (ly - band * t.band_h);
 }
 
-#define RT_LOG_SUBPOOLS 64u        // the overflow pool of the compact log is handed out from this many bump counters (k_shade)
-struct DCounters                  // one per frame, device memory
-{
-    uint32_t queue[64];           // queue[b]  = rays in the incoming queue of bounce b
-    uint32_t shadow[64];          // shadow[b] = shadow rays emitted at bounce b
-    unsigned long long total_closest, total_shadow, samples;
-    uint32_t last_queue[64], last_shadow[64];
-    // work-distribution heads of the persistent trace kernels: one per XCD and per
-    // kernel flavour (0 = closest, 1 / 2 = shadow rays of an even / odd bounce: the shadow trace of bounce b may
-    // still be running while k_shade of bounce b + 1 prepares the next one), offsets inside the XCD's region
-    uint32_t head[3][8];
-    // rays k_trace_w4 hands to the BVH2 kernel (non-finite 1/dir): list length and that launch's work heads
-    uint32_t slow_count[4];       // per flavour ([3] unused)
-    uint32_t slow_head[3][8];
-    uint32_t stack_spills;        // lane-steps with stack entries in the HBM spill area (k_trace2 / k_trace_w4), since the last reset
-    uint32_t slow_rays;           // rays k_trace_w4 handed to k_trace2, since the last reset
-    // launch timeline of k_trace_w4<closest> per bounce (rt_frame_debug_timeline), 100 MHz wall clock:
-    // first wave started, first wave found the queue dry, last wave left
-    unsigned long long tl_start[64], tl_dry[64], tl_end[64];
-    // ... of its slowest ray: most traversal steps (wide nodes + triangles) any ray took, and the ticks from hand-out to
-    // retirement (high bits) and steps (low 24 bits) of the ray that took longest ...
-    unsigned long long tl_ray_steps[64], tl_ray_ticks[64];
-    // ... and when its waves left, in 25 us bins after the first wave found the queue dry (all recorded launches together)
-    unsigned long long tl_exit_hist[64];
-    // compact radiance log (DLog): next free overflow block of the batch in flight, and "the pool ran dry"
-    uint32_t log_ovf_next[RT_LOG_SUBPOOLS], log_ovf_flag;
-};
+// (DCounters, the frame's counters -- one per frame, device memory -- and RT_LOG_SUBPOOLS: device_scene.h, where the scene's host unit finds them too)
 
 // ray_inv_dir and ray_sign of TraceBvh (trace_bvh.cl:125-129), packed as (inv.xyz, sign bits)
 #define RT_SIGN_SLOW 8u

@@ -5,9 +5,8 @@
 // ---------------------------------------------------------------------------
 // Scene re-layout on the device (rt_scene_upload): the reference's arrays are copied to HBM
 // as they are and three streaming kernels write the traversal / shading layouts.
-// Error codes (first one wins) are decoded by the host.
+// Error codes (first one wins; RL_OK and its siblings, device_scene.h) are decoded by the host.
 // ---------------------------------------------------------------------------
-enum { RL_OK = 0, RL_CHILD_RANGE = 1, RL_LEAF_RANGE = 2, RL_AXIS = 3, RL_MATERIAL = 4 };
 
 // one thread per LinearBVHNode: leaves mark their last triangle
 __global__ void k_relayout_mark_leaves(const rt_bvh_node* __restrict__ nodes, uint32_t nn, uint32_t nt,

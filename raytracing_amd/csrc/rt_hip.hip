@@ -18,31 +18,21 @@
 #include <functional>
 #include "rt_hip.h"
 #include "kernels.h"
-#include "own_bvh.h"
-#include "treelet_order.h"
-#include "tree_select.h"
-#include "tree_rotate.h"
 #include <chrono>
-#include "wide_bvh.h"        // the host-side fold, the pair layout, the adaptation's host walks (wide_bvh.cpp)
-#include "device_fold.h"     // ... and the fold + crossing counts on the device (device_fold.hip)
-#include "refit.h"           // the refit of the scene's trees when its triangles move (refit.hip)
-#include "pose_host.h"       // the scene's objects posed from one matrix per object (pose.hip)
-#include "filters_host.h"         // the filters' guide pass, a-trous passes and temporal stages (filters.hip)
+#include "wide_bvh.h"        // truncated_walks_exchange, for the adaptation's report line (wide_bvh.cpp)
+#include "filters_host.h"        // the filters' guide pass, a-trous passes and temporal stages (filters.hip)
 #include "query_host.h"      // the queries' scratch areas and the ray through a pixel, for rt_frame_pick and rt_frame_pick_all (query.hip)
 #include "bake_host.h"       // bake::CHUNK_POINTS, for RT_CTX_OPT_BAKE_CHUNK_POINTS (bake.hip)
 #include "region_host.h"     // the region of a pixel rectangle, for rt_frame_pick_rect (region.hip)
 #include "device_memory.h"   // who owns a device allocation: dev::Mem, dev::Temps
-#include "context.h"         // Scene, rt_ctx, rt_buffer, fail / HIPCHK: what this unit shares with the feature units that implement entry points (scene_queries.cpp)
+#include "context.h"         // Scene, rt_ctx, rt_buffer, fail / HIPCHK: what this unit shares with the feature units that implement entry points (scene_upload.cpp, scene_queries.cpp)
+#include "fold_adapt.h"      // FoldAdapt, for the render thread's side of the adaptation (fold_hooks_impl.h); the upload's side and the worker: scene_upload.cpp
 using namespace rtw;
 using namespace context;
 
 namespace
 {
 thread_local std::string g_thread_error;
-
-void drop_fold_adapt(FoldAdapt* a);        // waits for its worker thread (fold_adapt_impl.h, below, after choose_tree)
-void fold_adapt_set_interval(FoldAdapt* a, uint32_t ms);
-void fold_adapt_set_wait(FoldAdapt* a, bool wait);
 } // namespace
 
 // An owner's device buffers: each one's address and size (clear: it starts from zero).  An owner lists them once (buffers()), for the allocation and for the free.
@@ -382,21 +372,6 @@ int query_check_status(rt_ctx* ctx, const char* who)
     *st = 0u;
     return fail(ctx, std::string(who) + ": a ray query's traversal stack ran over its bound (a tree deeper than the walk's stack): that query's results are not valid");
 }
-} // namespace context
-
-namespace
-{
-void free_scene(Scene& s)
-{
-    void* ptrs[] = {s.nodes, s.tris_rt, s.tris_sh, s.materials, s.textures, s.texture_data, s.lights, s.env, s.emissive, s.trees[TREE_REF].recs, s.mat_tex16,
-        s.trees[TREE_SHADOW].recs, s.trees[TREE_CLOSEST].recs};
-    for (void* p : ptrs) if (p) (void)hipFree(p);
-    if (s.adapt) drop_fold_adapt(s.adapt);
-    if (s.refit) { refit::release(*s.refit); delete s.refit; }
-    if (s.pose_snap) (void)hipFree(s.pose_snap);
-    if (s.pose) { pose::release(*s.pose); delete s.pose; }
-    s = Scene();
-}
 
 // Nothing in flight may still read what is about to be freed or rewritten: batches traced ahead are dropped (RT_OPT_SAMPLES_AHEAD), and every stream a frame
 // launches on -- side streams, pipes, banks -- has drained.
@@ -408,15 +383,7 @@ int quiesce(rt_ctx* ctx)
         if (sync_frame_streams(f) != RT_OK) return RT_ERROR;
     return RT_OK;
 }
-
-// The tree report keeps one entry of a kind, the latest: what begins at the first `prefix` goes, `line` is appended.
-void replace_report_line(std::string& report, const char* prefix, const std::string& line)
-{
-    const size_t at = report.find(prefix);
-    if (at != std::string::npos) report.erase(at);
-    report += line;
-}
-} // namespace
+} // namespace context
 
 extern "C" {
 
@@ -621,399 +588,25 @@ size_t rt_buffer_size(rt_buffer* buf) { return buf ? buf->bytes : 0; }
 
 } // extern "C"
 
-#include "fold_adapt_impl.h"
-
-namespace
-{
-
-// ---- rt_scene_upload's stages ------------------------------------------------------------------------------------------------------
-// do this many 64-byte records stay below 4 GiB?  (k_trace_w4 and k_trace2 address node and trace-triangle records with 32-bit byte offsets)
-bool fits_offsets32(uint64_t records) { return records * 64 <= 0xFFFFFFFFull; }
-
-// RT_CTX_OPT_ADAPTIVE_FOLD: is a scene of nn nodes one that gets a fold adaptation?  (bit 0: the option; bit 2: also scenes too small to profit)
-bool adaptation_wanted(const rt_ctx* ctx, uint32_t nn) { return (ctx->adaptive_fold & 1u) && (nn >= 8192u || (ctx->adaptive_fold & 4u)); }
-
-// the triangles' corner positions, 9 floats each (FoldAdapt::tri9)
-void copy_corners(const rt_triangle* tris, uint32_t nt, std::vector<float>& tri9)
-{
-    tri9.resize((size_t)nt * 9);
-    for (uint32_t i = 0; i < nt; ++i)
-    {
-        const rt_triangle& t = tris[i];
-        const rt_float3 v[3] = {t.v1.position, t.v2.position, t.v3.position};
-        for (int k = 0; k < 3; ++k) { tri9[(size_t)i * 9 + 3 * k] = v[k].x; tri9[(size_t)i * 9 + 3 * k + 1] = v[k].y; tri9[(size_t)i * 9 + 3 * k + 2] = v[k].z; }
-    }
-}
-
-// What an upload has worker threads do beside its own work: the candidate trees of the backend's own (Upload::choose_own_trees) and the copies an adaptation
-// keeps of the caller's arrays (FoldAdapt: the binary tree, the triangles' corners -- 157 + 100 MB for 2.8 M triangles).  An upload that ends early
-// gives the host builds up before it joins them.
-struct UploadWorkers
-{
-    OwnTree own_sh, own_cl, own_sh_dev;      // own_sh_dev: the shadow rays' candidate built on the device (RT_CTX_OPT_TREE_BUILDER != 0)
-    std::vector<rt_bvh_node> bvh2; std::vector<float> tri9; std::thread copies;
-    void cancel() { own_sh.cancel_build.store(true); own_cl.cancel_build.store(true); }
-    void join_copies() { if (copies.joinable()) copies.join(); }
-    ~UploadWorkers() { cancel(); join_copies(); }          // (~OwnTree joins)
-};
-
-// One rt_scene_upload: the scene in the making and what its stages hand to each other.  The scene is the context's only once publish() has run; an upload
-// that is refused or fails before that frees with this object whatever the stages had allocated, so the context is left without a scene.
-struct Upload
-{
-    rt_ctx* const ctx; const rt_scene_desc* const sd; const uint32_t nt, nn;
-    Scene s;
-    UploadWorkers w;
-    int rc = RT_OK;                           // device allocations and copies that failed so far (looked at once, after the trees are chosen)
-    bool may_own = false, try_device_tree = false;
-    std::vector<uint32_t> interior_index; uint32_t n_interior = 0;
-    std::vector<float4> super_root, lights;   // host staging (like interior_index and wide): read by copies on the stream until the upload's last synchronisation
-    std::vector<WideNode> wide; std::vector<uint32_t> wide_roots;   // the fold of the reference's tree on the host; the binary-tree node each of its records tests
-    uint32_t w_entry = 0, n_wide_dev = 0, n_wide_ref = 0;
-    bool folded_on_device = false, have_wide = false, have_sh = false, have_cl = false;
-    OwnTree* sh = nullptr;                    // the shadow rays' candidate that was measured last (the one adopted, if one is)
-    std::chrono::steady_clock::time_point t_upload, t_lap;
-    double t_layout = 0.0, t_device = 0.0, t_dev_fold = 0.0, t_fold = 0.0, t_own_wait = 0.0, t_choose = 0.0;
-
-    Upload(rt_ctx* c, const rt_scene_desc* d) : ctx(c), sd(d), nt(d->num_triangles), nn(d->num_nodes), t_upload(std::chrono::steady_clock::now()), t_lap(t_upload) {}
-    ~Upload() { w.cancel(); free_scene(s); }
-    double lap() { const auto n = std::chrono::steady_clock::now(); const double d = std::chrono::duration<double>(n - t_lap).count(); t_lap = n; return d; }
-
-    // the trees of the backend's own (below, "Trees of the backend's own") are built on worker threads meanwhile
-    void start_workers()
-    {
-        OwnTree &own_sh = w.own_sh, &own_cl = w.own_cl, &own_sh_dev = w.own_sh_dev;
-        may_own = ctx->build_wide == 1u && fits_offsets32(nt) && (sd->nodes[0].num_primitives_axis >> 16) == 0;
-        if (ctx->device_fold && ctx->build_wide == 1u) { own_sh.device = ctx->device; own_cl.device = ctx->device; }
-        own_sh.pairs = own_cl.pairs = ctx->wide_layout != 0u;
-        // (the shadow rays' tree only: the closest-hit rays' own tree is the tolerance mode's, host-built)
-        try_device_tree = may_own && ctx->shadow_tree && ctx->tree_builder != 0u && ctx->device_fold != 0u && ctx->build_wide == 1u;
-        if (try_device_tree)
-        {
-            own_sh_dev.device = ctx->device; own_sh_dev.pairs = own_sh.pairs; own_sh_dev.device_builder = true; own_sh_dev.device_only = true;
-            own_sh_dev.start(sd, true, ctx->shadow_tree);
-        }
-        if (may_own && ctx->shadow_tree && !(try_device_tree && ctx->tree_builder == 1u)) own_sh.start(sd, true, ctx->shadow_tree);
-        if (may_own && ctx->closest_tree) own_cl.start(sd, false, ctx->closest_tree);
-        // what an adaptation keeps of the caller's arrays is copied beside everything else instead of after it
-        if (adaptation_wanted(ctx, nn) && ctx->build_wide == 1u && !ctx->closest_tree)
-            w.copies = std::thread([this, corners = (ctx->adaptive_fold & 16u) != 0u]()
-            {
-                w.bvh2.assign(sd->nodes, sd->nodes + nn);
-                if (corners) copy_corners(sd->triangles, nt, w.tri9);
-            });
-    }
-
-    // BVH re-layout, the host's part: LinearBVHNode[] (bvh.cpp:223-245) -> child-pair records, in treelet order (treelet_order.h: a pure permutation of records;
-    // the records themselves are written on the device, relayout_on_device), and the super-root record
-    int order_records()
-    {
-        const int bad = treelet::order(sd->nodes, nn, ctx->treelet_nodes, interior_index, n_interior);
-        if (bad == 1) return fail(ctx, "rt_scene_upload: child index outside the node array");
-        if (bad != 0) return fail(ctx, "rt_scene_upload: the node array is not a tree (cycle)");
-        t_layout = lap();
-        const rt_bvh_node& root = sd->nodes[0];
-        s.d.root_ref = (root.num_primitives_axis >> 16) > 0 ? (RT_LEAF_BIT | root.offset) : 0u;
-        // super-root: child 0 = (root box, root ref), child 1 = empty.  Visiting it IS the
-        // reference's first loop iteration (box test of node 0, trace_bvh.cl:146-148).
-        s.d.entry_ref = n_interior;
-        super_root.resize(4);
-        float4* out = super_root.data();
-        out[0] = make_float4(root.bounds_min.x, root.bounds_min.y, root.bounds_max.x, root.bounds_max.y);
-        out[1] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        out[2] = make_float4(root.bounds_min.z, root.bounds_max.z, 0.0f, 0.0f);
-        uint32_t r0 = s.d.root_ref, r1 = RT_EMPTY_REF, axis = 0;
-        float fr0, fr1, fax;
-        memcpy(&fr0, &r0, 4); memcpy(&fr1, &r1, 4); memcpy(&fax, &axis, 4);
-        out[3] = make_float4(fr0, fr1, fax, 0.0f);
-        s.d.root_min[0] = root.bounds_min.x; s.d.root_min[1] = root.bounds_min.y; s.d.root_min[2] = root.bounds_min.z;
-        s.d.root_max[0] = root.bounds_max.x; s.d.root_max[1] = root.bounds_max.y; s.d.root_max[2] = root.bounds_max.z;
-        return RT_OK;
-    }
-
-    // the lights as the kernels read them, and whether their shadow rays are the slow kind
-    void stage_lights()
-    {
-        lights.resize((size_t)(sd->num_lights ? sd->num_lights : 1) * 3);
-        uint32_t slow_lights = 0;
-        for (uint32_t i = 0; i < sd->num_lights; ++i)
-        {
-            const rt_light& l = sd->lights[i];
-            float ft; uint32_t ty = l.type; memcpy(&ft, &ty, 4);
-            lights[(size_t)i * 3 + 0] = make_float4(l.origin.x, l.origin.y, l.origin.z, 0.0f);
-            lights[(size_t)i * 3 + 1] = make_float4(l.radiance.x, l.radiance.y, l.radiance.z, 0.0f);
-            lights[(size_t)i * 3 + 2] = make_float4(ft, 0.0f, 0.0f, 0.0f);
-            // shadow rays towards a directional light all share its direction (light.h:57-61: origin * 20000, normalised again
-            // by HitSurface): a zero or tiny component makes 1/dir non-finite (RT_SIGN_SLOW) for every one of them
-            if (l.type == RT_LIGHT_TYPE_POINT) continue;
-            const double len = std::sqrt((double)l.origin.x * l.origin.x + (double)l.origin.y * l.origin.y + (double)l.origin.z * l.origin.z);
-            const double lim = len * 0x1p-95;
-            if (!(std::fabs((double)l.origin.x) > lim && std::fabs((double)l.origin.y) > lim && std::fabs((double)l.origin.z) > lim)) ++slow_lights;
-        }
-        s.slow_shadow = slow_lights != 0 && 4u * slow_lights >= sd->num_lights;
-    }
-
-    // the indices the shading kernels follow without a check of their own: texture slots, emissive triangles, texel ranges
-    int check_tables()
-    {
-        for (uint32_t i = 0; i < sd->num_materials; ++i)
-        {
-            // every 8-bit texture slot of a packed material: 0xFF = none (constants.h:35), else an index into textures
-            const rt_packed_material& m = sd->materials[i];
-            const uint32_t idx[6] = {m.diffuse_albedo >> 24, m.specular_albedo >> 24, (m.roughness_metalness >> 8) & 0xFFu,
-                m.roughness_metalness >> 24, (m.ior_emission_idx_transparency >> 8) & 0xFFu, m.ior_emission_idx_transparency >> 24};
-            if (!sd->material_texture_indices)
-                for (uint32_t t : idx)
-                    if (t != RT_INVALID_TEXTURE_IDX && t >= sd->num_textures)
-                        return fail(ctx, "rt_scene_upload: material references a texture that does not exist");
-        }
-        if (sd->material_texture_indices)          // the wide indices replace the packed ones (rt_scene_desc)
-            for (size_t i = 0; i < (size_t)sd->num_materials * 6; ++i)
-                if (sd->material_texture_indices[i] != 0xFFFFu && sd->material_texture_indices[i] >= sd->num_textures)
-                    return fail(ctx, "rt_scene_upload: material_texture_indices references a texture that does not exist");
-        for (uint32_t i = 0; i < sd->num_emissive; ++i)
-            if (sd->emissive_indices[i] >= nt) return fail(ctx, "rt_scene_upload: emissive index outside the triangle array");
-        for (uint32_t i = 0; i < sd->num_textures; ++i)
-        {
-            const rt_texture& t = sd->textures[i];
-            if (t.width <= 0 || t.height <= 0 || t.data_start < 0 ||
-                (uint64_t)t.data_start + (uint64_t)t.width * t.height > sd->num_texture_data)
-                return fail(ctx, "rt_scene_upload: texture outside texture_data");
-        }
-        return RT_OK;
-    }
-
-    // Re-layout on the device: the reference's arrays go to HBM as they are, three streaming kernels write the child-pair node records and the 64-byte /
-    // 128-byte triangle records.  Then, RT_CTX_OPT_DEVICE_FOLD, the reference tree's collapse into 4-wide records from the node array the kernels have
-    // just read (device_fold.h), on the same stream, before that array is freed with the stage's other temporaries.
-    int relayout_on_device()
-    {
-        static const char* who = "rt_scene_upload";
-        dev::Mem raw_tris, raw_nodes, d_index, d_last, d_err;
-        rc |= dev_fill(ctx, who, raw_tris, sd->triangles, (size_t)nt * sizeof(rt_triangle));
-        rc |= dev_fill(ctx, who, raw_nodes, sd->nodes, (size_t)nn * sizeof(rt_bvh_node));
-        rc |= dev_fill(ctx, who, d_index, interior_index.data(), (size_t)nn * sizeof(uint32_t));
-        rc |= dev_fill(ctx, who, d_last, nullptr, (size_t)nt);
-        rc |= dev_fill(ctx, who, d_err, nullptr, sizeof(int));
-        rc |= scene_array(ctx, &s.nodes, nullptr, (size_t)(n_interior + 1) * 64);   // + the super-root record
-        rc |= scene_array(ctx, &s.tris_rt, nullptr, (size_t)nt * 64);
-        rc |= scene_array(ctx, &s.tris_sh, nullptr, (size_t)nt * 128);
-        if (rc != RT_OK) return RT_ERROR;
-        int relayout_err = RL_OK;
-        bool ok = hipMemsetAsync(d_last.get(), 0, (size_t)nt, ctx->stream) == hipSuccess &&
-                  hipMemsetAsync(d_err.get(), 0, sizeof(int), ctx->stream) == hipSuccess;
-        if (ok)
-        {
-            hipLaunchKernelGGL(k_relayout_mark_leaves, dim3((nn + 255u) / 256u), dim3(256), 0, ctx->stream,
-                raw_nodes.get<const rt_bvh_node>(), nn, nt, d_last.get<uint8_t>(), d_err.get<int>());
-            hipLaunchKernelGGL(k_relayout_nodes, dim3((nn + 255u) / 256u), dim3(256), 0, ctx->stream,
-                raw_nodes.get<const rt_bvh_node>(), nn, d_index.get<const uint32_t>(), (float4*)s.nodes, d_err.get<int>());
-            hipLaunchKernelGGL(k_relayout_triangles, dim3((nt + 255u) / 256u), dim3(256), 0, ctx->stream,
-                raw_tris.get<const rt_triangle>(), nt, sd->num_materials, d_last.get<const uint8_t>(), (float4*)s.tris_rt,
-                (float4*)s.tris_sh, d_err.get<int>());
-            hipLaunchKernelGGL(k_relayout_leaf_bounds, dim3((nn + 255u) / 256u), dim3(256), 0, ctx->stream,
-                raw_nodes.get<const rt_bvh_node>(), nn, nt, (float4*)s.tris_rt);
-            ok = hipGetLastError() == hipSuccess &&
-                 hipMemcpyAsync((char*)s.nodes + (size_t)n_interior * 64, super_root.data(), 64, hipMemcpyHostToDevice,
-                     ctx->stream) == hipSuccess &&
-                 hipMemcpyAsync(&relayout_err, d_err.get(), sizeof(int), hipMemcpyDeviceToHost, ctx->stream) == hipSuccess &&
-                 hipStreamSynchronize(ctx->stream) == hipSuccess;
-        }
-        if (ok && relayout_err == RL_OK && ctx->device_fold && ctx->build_wide == 1u && fits_offsets32(nt))
-        {
-            const bool want_host_copy = ctx->wide_layout != 0u || (may_own && (ctx->shadow_tree == 1u || ctx->closest_tree == 1u));   // the pair layout and the choice by proxy rays work on the host
-            folded_on_device = devfold::fold(ctx->stream, raw_nodes.get<const rt_bvh_node>(), nn, sd->nodes[0], nullptr, nullptr, (WideNode**)&s.trees[TREE_REF].recs, &n_wide_dev, &w_entry,
-                                             &wide_roots, want_host_copy ? &wide : nullptr, nullptr, &t_dev_fold);
-            (void)hipGetLastError();
-        }
-        if (!ok) return fail(ctx, "rt_scene_upload: device re-layout failed");
-        switch (relayout_err)
-        {
-        case RL_OK: return RT_OK;
-        case RL_CHILD_RANGE: return fail(ctx, "rt_scene_upload: child index outside the node array");
-        case RL_LEAF_RANGE: return fail(ctx, "rt_scene_upload: leaf range outside the triangle array");
-        case RL_AXIS: return fail(ctx, "rt_scene_upload: bad split axis");
-        default: return fail(ctx, "rt_scene_upload: material index out of range");
-        }
-    }
-
-    // the small arrays, as the caller gave them
-    void upload_tables()
-    {
-        rc |= scene_array(ctx, &s.materials, sd->materials, (size_t)sd->num_materials * sizeof(rt_packed_material));
-        rc |= scene_array(ctx, &s.textures, sd->textures, (size_t)sd->num_textures * sizeof(rt_texture));
-        rc |= scene_array(ctx, &s.texture_data, sd->texture_data, (size_t)sd->num_texture_data * 4);
-        rc |= scene_array(ctx, &s.lights, lights.data(), lights.size() * sizeof(float4));
-        rc |= scene_array(ctx, &s.env, sd->env_rgba, (size_t)sd->env_width * sd->env_height * 16);
-        rc |= scene_array(ctx, &s.emissive, sd->emissive_indices, (size_t)sd->num_emissive * 4);
-        if (sd->material_texture_indices)
-            rc |= scene_array(ctx, &s.mat_tex16, sd->material_texture_indices, (size_t)sd->num_materials * 6 * sizeof(uint16_t));
-        t_device = lap() - t_dev_fold;
-    }
-
-    // the 4-wide quantized tree for k_trace_w4, on host threads if the device has not folded it (optional: trees that do not qualify keep the BVH2 kernels)
-    // (a SAH collapse can be deeper than the kernel's stack bound allows where two levels at a time are not: try both)
-    void fold_reference_tree()
-    {
-        have_wide = folded_on_device || (ctx->build_wide && fits_offsets32(nt) &&
-            ((ctx->build_wide != 2u && build_wide_bvh(sd->nodes, nn, RT_WIDE_SAH, wide, w_entry, &wide_roots)) ||
-             build_wide_bvh(sd->nodes, nn, RT_WIDE_TWO_LEVELS, wide, w_entry, &wide_roots)));
-        n_wide_ref = folded_on_device ? n_wide_dev : (uint32_t)wide.size();
-        WideTree& ref = s.trees[TREE_REF];
-        if (have_wide && ctx->wide_layout && !wide.empty())
-        {
-            pair_layout_by_area(wide, wide_roots, sd->nodes, nn, (const ownbvh::Metric*)nullptr);
-            if (folded_on_device && hipMemcpyAsync(ref.recs, wide.data(), wide.size() * sizeof(WideNode), hipMemcpyHostToDevice, ctx->stream) != hipSuccess) rc |= fail(ctx, "rt_scene_upload: uploading the paired records failed");
-        }
-        if (!folded_on_device && have_wide) rc |= scene_array(ctx, &ref.recs, wide.data(), wide.size() * sizeof(WideNode));
-        ref.n = have_wide ? n_wide_ref : 0u;
-        ref.entry = w_entry;
-        t_fold = lap() + t_dev_fold;
-    }
-
-    // Trees of the backend's own over the reference's leaves (own_bvh.h): one for the shadow rays (exact: an any-hit verdict
-    // does not depend on what sits above the leaves) and -- opt-in, tolerance mode -- one for the closest-hit rays.  Which
-    // candidate a population walks is MEASURED with proxy rays (tree_select.h); the reference's own topology is a candidate,
-    // so the choice is never worse than sharing on that measure.
-    void choose_own_trees()
-    {
-        OwnTree &own_sh = w.own_sh, &own_cl = w.own_cl, &own_sh_dev = w.own_sh_dev;
-        // the shadow rays' candidates: the one built on the device is ready first and is measured first; if it wins, the host's build is abandoned
-        sh = &own_sh;
-        ChoiceInputs shadow_choice;              // (the proxy rays and the reference fold's cost: measured once for both candidates)
-        if (try_device_tree)
-        {
-            own_sh_dev.join();
-            (void)hipSetDevice(ctx->device);
-            if (own_sh_dev.ok && have_wide && n_wide_ref != 0u && choose_tree(sd, wide, w_entry, true, ctx->shadow_tree, own_sh_dev, s.tree_report, &shadow_choice))
-            {
-                sh = &own_sh_dev;
-                own_sh.cancel_build.store(true);
-            }
-        }
-        own_sh.join(); own_cl.join();
-        t_own_wait = lap();
-        (void)hipSetDevice(ctx->device);
-        auto adopt_own = [&](OwnTree& own, TreeSlot slot)
-        {
-            WideTree& t = s.trees[slot];
-            t.n = (uint32_t)own.wide.size(); t.entry = own.entry;
-            if (own.d_wide) t.recs = own.d_wide.release();                                     // folded on the device: the records are there
-            else rc |= scene_array(ctx, &t.recs, own.wide.data(), own.wide.size() * sizeof(WideNode));
-        };
-        if (have_wide && n_wide_ref != 0u && may_own && ctx->shadow_tree)
-        {
-            have_sh = sh == &own_sh_dev || choose_tree(sd, wide, w_entry, true, ctx->shadow_tree, own_sh, s.tree_report, &shadow_choice);
-            if (have_sh) adopt_own(*sh, TREE_SHADOW);
-        }
-        if (have_wide && n_wide_ref != 0u && may_own && ctx->closest_tree)
-        {
-            have_cl = choose_tree(sd, wide, w_entry, false, ctx->closest_tree, own_cl, s.tree_report);
-            if (have_cl) adopt_own(own_cl, TREE_CLOSEST);
-        }
-        t_choose = lap();
-    }
-
-    // RT_CTX_OPT_ADAPTIVE_FOLD: what the first rt_integrate needs to fold these trees again for its own rays (FoldAdapt)
-    void arm_adaptation()
-    {
-        if (!(adaptation_wanted(ctx, nn) && have_wide && n_wide_ref != 0u && !have_cl)) return;
-        FoldAdapt* a = new FoldAdapt();
-        a->mode = ctx->adaptive_fold;
-        a->device = ctx->device;
-        a->device_fold = ctx->device_fold != 0u && ctx->build_wide == 1u;
-        a->pairs = ctx->wide_layout != 0u;
-        a->min_interval_ms = ctx->adapt_min_interval_ms;
-        memset(&a->camera, 0, sizeof(a->camera));
-        const rt_bvh_node& root = sd->nodes[0];
-        const double ex = (double)root.bounds_max.x - root.bounds_min.x, ey = (double)root.bounds_max.y - root.bounds_min.y, ez = (double)root.bounds_max.z - root.bounds_min.z;
-        a->scene_diagonal = std::sqrt(ex * ex + ey * ey + ez * ez);
-        w.join_copies();
-        if (w.bvh2.size() == nn) a->bvh2.swap(w.bvh2); else a->bvh2.assign(sd->nodes, sd->nodes + nn);
-        a->roots = std::move(wide_roots);
-        if (have_sh) { a->bvh2_sh = std::move(sh->bvh2); a->roots_sh = std::move(sh->roots); }
-        if (a->mode.load() & 16u)
-        {
-            if (w.tri9.size() == (size_t)nt * 9) a->tri9.swap(w.tri9); else copy_corners(sd->triangles, nt, a->tri9);
-        }
-        s.adapt = a;
-    }
-
-    // the kernels' view of the scene, the flags, the report's `upload:` line; the scene is the context's from here
-    void publish()
-    {
-        s.d.nodes = (const float4*)s.nodes; s.d.tris_rt = (const float4*)s.tris_rt; s.d.tris_sh = (const float4*)s.tris_sh;
-        s.d.materials = (const rt_packed_material*)s.materials; s.d.mat_tex16 = (const uint16_t*)s.mat_tex16;
-        s.d.textures = (const rt_texture*)s.textures; s.d.texture_data = (const uint32_t*)s.texture_data;
-        s.d.lights = (const float4*)s.lights; s.d.light_count = sd->num_lights;
-        s.d.env = (const float4*)s.env; s.d.env_w = (int)sd->env_width; s.d.env_h = (int)sd->env_height;
-        s.d.gamma_lut = ctx->gamma_lut;
-        s.d.emissive = (const uint32_t*)s.emissive; s.d.emissive_count = sd->num_emissive;
-        s.d.emissive_nee = (sd->flags & RT_SCENE_EMISSIVE_NEE) && sd->num_emissive ? 1u : 0u;
-        s.walk_trees(have_cl ? TREE_CLOSEST : TREE_REF, have_sh ? TREE_SHADOW : TREE_REF);
-        s.n_tris = nt;
-        s.wide_ok = have_wide;
-        s.offsets32 = fits_offsets32(n_interior + 1) && fits_offsets32(nt);
-        if (!s.offsets32)
-            fprintf(stderr, "rt_scene_upload: warning: the node or trace-triangle records reach 4 GiB (%u interior nodes, %u triangles): k_trace_w4 and k_trace2 "
-                            "address them with 32-bit byte offsets, so every launch takes the per-ray kernel k_trace_v1 -- correct, and several times slower\n",
-                n_interior, nt);
-        s.valid = true;
-        // where the upload's time went (rt_scene_tree_report; bench.py prints it as `setup`)
-        char line[400];
-        const double t_rest = lap();
-        snprintf(line, sizeof(line), "upload: %.3f s = record order on the host %.3f + copies and re-layout kernels %.3f + fold of the reference's tree %.3f (%s) + waiting for the own tree(s) %.3f "
-            "(shadow tree: built %s in %.3f, folded in %.3f) + choosing by proxy rays and uploading %.3f + adaptation state %.3f (%u triangles, %u nodes, %u + %u wide records)\n",
-            std::chrono::duration<double>(std::chrono::steady_clock::now() - t_upload).count(), t_layout, t_device, t_fold, folded_on_device ? "on the device" : "on host threads", t_own_wait,
-            sh->built_on_device ? "on the device (PLOC)" : (try_device_tree ? "on host threads (the device-built candidate did not win its measurement)" : "on host threads"),
-            sh->build_seconds, sh->fold_seconds, t_choose, t_rest, nt, nn, s.trees[TREE_REF].n, s.trees[TREE_SHADOW].n);
-        s.tree_report += line;
-        ctx->scene = s;
-        s = Scene();
-    }
-};
-} // namespace
-
-extern "C" {
-
-#include "refit_impl.h"
-#include "pose_impl.h"
-
 // ---- scene -----------------------------------------------------------------
-int rt_scene_upload(rt_ctx* ctx, const rt_scene_desc* sd)
+// The scene's upload, trees, adaptation worker, refit and pose are scene_upload.cpp's.  What stays here of an upload are the launches of the re-layout
+// kernels, which belong to this unit's code object: Upload::relayout_on_device clears `last` and `err` on the stream, calls this, and reads `err` back.
+int context::relayout_records(rt_ctx* ctx, const rt_bvh_node* raw_nodes, uint32_t nn, const rt_triangle* raw_tris, uint32_t nt, uint32_t num_materials, const uint32_t* index,
+    uint8_t* last, int* err, float4* nodes, float4* tris_rt, float4* tris_sh)
 {
-    if (!ctx || !sd) return fail(ctx, "rt_scene_upload: NULL argument");
-    if (!sd->triangles || sd->num_triangles == 0) return fail(ctx, "rt_scene_upload: no triangles");
-    if (!sd->nodes || sd->num_nodes == 0) return fail(ctx, "rt_scene_upload: no BVH nodes");
-    if (!sd->materials || sd->num_materials == 0) return fail(ctx, "rt_scene_upload: no materials");
-    if (!sd->env_rgba || sd->env_width == 0 || sd->env_height == 0)
-        return fail(ctx, "rt_scene_upload: no environment image");
-    (void)hipSetDevice(ctx->device);
-    if (quiesce(ctx) != RT_OK) return RT_ERROR;      // nothing may still read the scene that is about to be freed
-    free_scene(ctx->scene);
-    ++ctx->scene_uploads;
-    ++ctx->upload_epoch;
-    ctx->refit_index = 0;
-    Upload u(ctx, sd);                               // any return before publish(): the context has no scene, the host builds are given up
-    u.start_workers();
-    if (u.order_records() != RT_OK) return RT_ERROR;
-    u.stage_lights();
-    if (u.check_tables() != RT_OK) return RT_ERROR;
-    if (u.relayout_on_device() != RT_OK) return RT_ERROR;
-    u.upload_tables();
-    u.fold_reference_tree();
-    u.choose_own_trees();
-    if (u.rc != RT_OK) return RT_ERROR;
-    u.arm_adaptation();
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // host staging vectors die here
-    u.publish();
-    if (ctx->refittable) refit_arm(ctx, sd, u.n_interior + 1u);
-    return RT_OK;
+    hipLaunchKernelGGL(k_relayout_mark_leaves, dim3((nn + 255u) / 256u), dim3(256), 0, ctx->stream,
+        raw_nodes, nn, nt, last, err);
+    hipLaunchKernelGGL(k_relayout_nodes, dim3((nn + 255u) / 256u), dim3(256), 0, ctx->stream,
+        raw_nodes, nn, index, nodes, err);
+    hipLaunchKernelGGL(k_relayout_triangles, dim3((nt + 255u) / 256u), dim3(256), 0, ctx->stream,
+        raw_tris, nt, num_materials, (const uint8_t*)last, tris_rt,
+        tris_sh, err);
+    hipLaunchKernelGGL(k_relayout_leaf_bounds, dim3((nn + 255u) / 256u), dim3(256), 0, ctx->stream,
+        raw_nodes, nn, nt, tris_rt);
+    return hipGetLastError() == hipSuccess ? RT_OK : RT_ERROR;
 }
 
 // ---- frame -----------------------------------------------------------------
-} // extern "C"
-
 namespace
 {
 void free_path_buffers(rt_frame* f)
@@ -3165,8 +2758,6 @@ int rt_frame_debug_timeline(rt_frame* f, int arm, unsigned long long* out /* [64
     for (int b = 0; b < 64; ++b) out[384 + b] = h[320 + b];   // waves that left in the b-th 25 us after the queue ran dry
     return RT_OK;
 }
-
-#include "debug_exports_impl.h"
 
 int rt_debug_eval(rt_ctx* ctx, int fn, const float* a, const float* b, float* out, uint32_t n)
 {

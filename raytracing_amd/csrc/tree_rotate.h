@@ -3,7 +3,7 @@
 //
 // For any-hit (shadow) rays every binary tree over the reference's leaves gives the reference's verdict (own_bvh.h), so the tree may be
 // whatever is cheapest for the rays that are actually traced.  own_bvh.h builds one from a geometric model of those rays (projected area
-// along the lights); once a probe frame exists (rt_hip.hip: FoldAdapt) the model can be replaced by counting: the cost of an interior node
+// along the lights); once a probe frame exists (fold_adapt.h: FoldAdapt) the model can be replaced by counting: the cost of an interior node
 // is the number of probe rays whose segment crosses its box -- that is how often a walk visits it -- and the tree's cost the sum over its
 // interior nodes.  This file lowers that sum by TREE ROTATIONS (Kensler 2008, "Tree rotations for improving bounding volume hierarchies",
 // with the surface area replaced by the crossing count): at a node n = (L, R) with L = (L1, L2), exchanging R with L1 or L2 changes one box
