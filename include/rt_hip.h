@@ -493,6 +493,58 @@ int rt_frame_pick_rect(rt_frame* frame, uint32_t x0, uint32_t y0, uint32_t x1, u
 int rt_debug_rect_region(const rt_camera* camera, uint32_t width, uint32_t height, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, float t_near, float t_far,
                          rt_region* out);
 
+/* ---- cross: every triangle of the uploaded scene that a CALLER's triangle (a probe) crosses, and where (opt-in extension): contact and
+ * collision work -- which scene triangles a probe mesh cuts and along which segment, which posed objects interpenetrate, whether a mesh cuts itself.
+ * raytracing_amd/csrc/cross.h states the rule.
+ *   a probe: three corners (every fourth component is ignored); SEARCHED when its nine coordinates are finite.
+ *   CROSS(Q, T), T on its shading record's corners (rt_scene_nearest's operands): the closed boxes of the two corner triples overlap on every axis, AND the
+ *     probe's plane (n = cross3(q2 - q1, q3 - q1), d = -dot(n, q1)) does not have T's three corners strictly on one side (skipped when n or d is not finite),
+ *     AND one of six segment-triangle tests accepts: bits 0..2 = Q's edges q1->q2, q2->q3, q3->q1 against T, bits 3..5 = T's edges p1->p2, p2->p3, p3->p1
+ *     against Q; two-sided Moeller-Trumbore, 0 <= t <= 1, a determinant that is zero or NaN rejects.  COPLANAR pairs therefore do not cross.
+ *   rt_probe_hits: count = the crossing triangles, stored = min(count, max_list), first_primitive = the lowest crossing id (RT_INVALID_ID: none), flags bit 0
+ *     = searched, bit 1 = an RT_CROSS_ANY answer.
+ *   members (optional, max_list <= RT_CROSS_LIST_MAX per probe): the crossing triangles with the LOWEST primitive ids, ascending -- an order no tree decides;
+ *     a smaller max_list gives a prefix; entries beyond `stored` hold RT_INVALID_ID and zeros.  flags = the accepting tests' bits; c0 / c1 = the point
+ *     a + t * (b - a) of the lowest / second lowest set bit (one bit: c1 = c0).  In exact arithmetic a generic crossing sets exactly two bits and c0 c1 is
+ *     the intersection segment; rounding may set one bit or three.
+ *   RT_CROSS_ANY: the walk stops at the first member: count is 0 or 1, stored 0, first_primitive RT_INVALID_ID (which member is met first depends on the
+ *     tree), flags bit 1 set; members must be NULL.
+ *   a probe that is not searched gives zeros and invalid entries.
+ *   The sets are a statement about triangles and cross.h alone -- bit for bit rt_debug_cross's brute force, whichever records are walked, after any refit or
+ *     pose (cross.h has the argument).
+ *   rt_scene_cross: host arrays, staged in chunks; returns when the outputs are written.  rt_scene_cross_buffer: rt_buffers of this context (n rt_probe,
+ *     n rt_probe_hits, n * max_list rt_cross_member); only enqueues.
+ *   rt_scene_cross_self / _buffer: probe i is scene triangle first + i (rt_scene_select's triangle order), nothing is uploaded.  A pair is SKIPPED (no member,
+ *     not counted) when both are the same triangle or when some corner of one equals some corner of the other on all three coordinates (neighbours that share
+ *     a vertex always touch).  RT_CROSS_OTHER_OBJECTS (self forms only; needs rt_scene_set_objects) also skips pairs of one object.
+ * Refused with nothing launched: a NULL context, no scene, NULL probes with n > 0, out NULL, max_list > RT_CROSS_LIST_MAX, members with max_list == 0 or with
+ * RT_CROSS_ANY, unknown option bits, RT_CROSS_OTHER_OBJECTS without objects or on a form that is not a self form, first + n beyond the scene, a buffer of
+ * another context or one that is too small.  n == 0: RT_OK. */
+#define RT_CROSS_LIST_MAX 8
+#define RT_CROSS_ANY 1u                     /* options bit 0 */
+#define RT_CROSS_OTHER_OBJECTS 2u           /* options bit 1 (self forms) */
+#define RT_PROBE_HITS_SEARCHED 1u           /* rt_probe_hits.flags bit 0 */
+#define RT_PROBE_HITS_ANY 2u                /* rt_probe_hits.flags bit 1 */
+typedef struct rt_probe { float p1[4], p2[4], p3[4]; } rt_probe;                                                                  /* 48 bytes */
+typedef struct rt_probe_hits { uint32_t count; uint32_t stored; uint32_t first_primitive; uint32_t flags; } rt_probe_hits;      /* 16 bytes */
+typedef struct rt_cross_member { uint32_t primitive_id; uint32_t flags; float c0[3]; float c1[3]; } rt_cross_member;            /* 32 bytes */
+int rt_scene_cross(rt_ctx* ctx, const rt_probe* probes, uint32_t n, uint32_t max_list, uint32_t options, rt_probe_hits* out, rt_cross_member* members_or_null);
+int rt_scene_cross_buffer(rt_ctx* ctx, rt_buffer* probes, uint32_t n, uint32_t max_list, uint32_t options, rt_buffer* out, rt_buffer* members_or_null);
+int rt_scene_cross_self(rt_ctx* ctx, uint32_t first, uint32_t n, uint32_t max_list, uint32_t options, rt_probe_hits* out, rt_cross_member* members_or_null);
+int rt_scene_cross_self_buffer(rt_ctx* ctx, uint32_t first, uint32_t n, uint32_t max_list, uint32_t options, rt_buffer* out, rt_buffer* members_or_null);
+/* brute force over all of `triangles` (primitive_id = the index): cross.h on the host (ctx == NULL) or k_cross_brute on uploaded copies.  The two agree bit
+ * for bit.  members must be NULL when max_list == 0 or with RT_CROSS_ANY (as in the scene forms) and must be given otherwise.  Refused: a NULL argument,
+ * max_list > RT_CROSS_LIST_MAX, unknown option bits, RT_CROSS_OTHER_OBJECTS, members with max_list == 0 or with RT_CROSS_ANY. */
+int rt_debug_cross(rt_ctx* ctx_or_null, const rt_triangle* triangles, uint32_t num_triangles, const rt_probe* probes, uint32_t n, uint32_t max_list,
+                   uint32_t options, rt_probe_hits* out, rt_cross_member* members);
+/* k_cross's walk on the host (no GPU): the child-pair form of `nodes` (wide == 0) or build_wide_bvh's 4-wide records of them (wide == 1), pruned by cross.h's
+ * box tests; triangles_tested_or_null[i] = how many triangles probe i was tested against.  Refused where rt_debug_overlap_walk is. */
+int rt_debug_cross_walk(const rt_bvh_node* nodes, uint32_t num_nodes, const rt_triangle* triangles, uint32_t num_triangles, int wide, const rt_probe* probes,
+                        uint32_t n, uint32_t max_list, uint32_t options, rt_probe_hits* out, rt_cross_member* members, uint32_t* triangles_tested_or_null);
+/* brute force of the self form: probe i is triangles[first + i]; RT_CROSS_OTHER_OBJECTS needs object_of_triangle. */
+int rt_debug_cross_self(rt_ctx* ctx_or_null, const rt_triangle* triangles, uint32_t num_triangles, const uint32_t* object_of_triangle_or_null, uint32_t first,
+                        uint32_t n, uint32_t max_list, uint32_t options, rt_probe_hits* out, rt_cross_member* members);
+
 /* One fold adaptation per process GROUP instead of one per rank (N ranks that tile one image hold the same scene and would each probe, rotate and fold for
  * identical records): the context's current 4-wide records -- the closest-hit rays' and the shadow rays' (n_shadow == 0: they share), as adapted so far -- to
  * host buffers of `capacity` records each (records NULL: size query; entries2 = {closest entry, shadow entry}), and into another context that has uploaded

@@ -118,6 +118,8 @@ EXPORTS = [
     "rt_scene_within", "rt_scene_within_buffer", "rt_debug_within", "rt_debug_within_walk",
     "rt_scene_overlap", "rt_scene_overlap_buffer", "rt_debug_overlap", "rt_debug_overlap_walk",
     "rt_scene_select", "rt_scene_select_buffer", "rt_debug_select", "rt_frame_pick_rect", "rt_debug_rect_region",
+    "rt_scene_cross", "rt_scene_cross_buffer", "rt_scene_cross_self", "rt_scene_cross_self_buffer",
+    "rt_debug_cross", "rt_debug_cross_walk", "rt_debug_cross_self",
 ]
 
 OPT_MAX_BOUNCES, OPT_WHITE_FURNACE, OPT_SAMPLER, OPT_AOV, OPT_DENOISER, OPT_DROP_LAST, OPT_PROFILE, OPT_TRACE_VARIANT, OPT_TRACE_WAVES, OPT_SAMPLES_IN_FLIGHT, OPT_SELECT_FORM_BOX, OPT_PACKET_BOUNCES, OPT_TRACE_TUNE, OPT_DEBUG_ALLOC_LIMIT, OPT_PATH_STATE_LIMIT_MB, OPT_PIPELINES, OPT_SHADE_PARTITION, OPT_OVERLAP_SHADOW, OPT_SMALL_LAUNCH_PATHS, OPT_COMPACT_LOG, OPT_DEBUG_LOG_POOL_DIV, OPT_TRACE_TAIL_LANES, OPT_TRACE_TAIL_PATHS, OPT_CHUNK_REFILL, OPT_STAGE_PIPES, OPT_FRAME_KERNEL, OPT_SAMPLES_AHEAD = range(27)
@@ -225,6 +227,11 @@ def load():
         "rt_debug_select": (i32, [vp, vp, u32, vp, u32, vp, u32, vp, vp, vp, vp]),
         "rt_frame_pick_rect": (i32, [vp, u32, u32, u32, u32, C.c_float, C.c_float, vp, vp, vp, vp, vp]),
         "rt_debug_rect_region": (i32, [vp, u32, u32, u32, u32, u32, u32, C.c_float, C.c_float, vp]),
+        "rt_scene_cross": (i32, [vp, vp, u32, u32, u32, vp, vp]), "rt_scene_cross_buffer": (i32, [vp, vp, u32, u32, u32, vp, vp]),
+        "rt_scene_cross_self": (i32, [vp, u32, u32, u32, u32, vp, vp]), "rt_scene_cross_self_buffer": (i32, [vp, u32, u32, u32, u32, vp, vp]),
+        "rt_debug_cross": (i32, [vp, vp, u32, vp, u32, u32, u32, vp, vp]),
+        "rt_debug_cross_walk": (i32, [vp, u32, vp, u32, i32, vp, u32, u32, u32, vp, vp, vp]),
+        "rt_debug_cross_self": (i32, [vp, vp, u32, vp, u32, u32, u32, u32, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -652,6 +659,75 @@ def debug_rect_region(camera, width, height, x0, y0, x1, y1, t_near=0.0, t_far=f
     return out[0]
 
 
+CROSS_LIST_MAX = 8          # RT_CROSS_LIST_MAX
+CROSS_ANY = 1               # RT_CROSS_ANY: options bit 0, the walk stops at the first member
+CROSS_OTHER_OBJECTS = 2     # RT_CROSS_OTHER_OBJECTS: options bit 1 (self forms), pairs of one object are skipped
+PROBE_HITS_SEARCHED = 1     # rt_probe_hits.flags bit 0
+PROBE_HITS_ANY = 2          # rt_probe_hits.flags bit 1
+
+
+def probe_records(probes):
+    """types.probe[n], contiguous: an array of them, or float[n, 3, 3] corners (types.probes_from_corners)"""
+    if isinstance(probes, np.ndarray) and probes.dtype == T.probe:
+        return np.ascontiguousarray(probes.reshape(-1))
+    return T.probes_from_corners(probes)
+
+
+def _cross_outputs(n, max_list, options):
+    """(out, members or None): an RT_CROSS_ANY answer lists nothing"""
+    out = np.zeros(n, T.probe_hits)
+    members = np.zeros((n, max_list), T.cross_member) if max_list and not options & CROSS_ANY else None
+    return out, members
+
+
+def _p(a):
+    return a.ctypes.data if a is not None and a.size else None
+
+
+def debug_cross(ctx, triangles, probes, max_list=CROSS_LIST_MAX, options=0):
+    """rt_debug_cross: (types.probe_hits[n], types.cross_member[n, max_list]) of `probes` by brute force over all `triangles` (types.triangle); the records
+    alone when nothing is listed (max_list == 0 or CROSS_ANY).  ctx None = the host (csrc/cross.h), else k_cross_brute on ctx's GPU."""
+    lib = load()
+    tris = np.ascontiguousarray(triangles, T.triangle)
+    pr = probe_records(probes)
+    out, members = _cross_outputs(len(pr), max_list, options)
+    handle = ctx.handle if ctx is not None else None
+    if lib.rt_debug_cross(handle, _p(tris), len(tris), _p(pr), len(pr), max_list, options, _p(out), _p(members)) != 0:
+        raise RtError(lib.rt_last_error(handle).decode())
+    return out if members is None else (out, members)
+
+
+def debug_cross_walk(nodes, triangles, probes, max_list=CROSS_LIST_MAX, options=0, wide=True, counts=False):
+    """rt_debug_cross_walk (host only): k_cross's walk over the child-pair form of `nodes` (types.bvh_node; wide=False) or over build_wide_bvh's 4-wide
+    records of them (wide=True): debug_cross's result, with uint32[n] triangles tested per probe appended when counts=True"""
+    lib = load()
+    nd = np.ascontiguousarray(nodes, T.bvh_node)
+    tris = np.ascontiguousarray(triangles, T.triangle)
+    pr = probe_records(probes)
+    out, members = _cross_outputs(len(pr), max_list, options)
+    tested = np.zeros(len(pr), np.uint32)
+    if lib.rt_debug_cross_walk(_p(nd), len(nd), _p(tris), len(tris), int(wide), _p(pr), len(pr), max_list, options, _p(out), _p(members), _p(tested)) != 0:
+        raise RtError(lib.rt_last_error(None).decode())
+    got = (out,) if members is None else (out, members)
+    if counts:
+        got += (tested,)
+    return got[0] if len(got) == 1 else got
+
+
+def debug_cross_self(ctx, triangles, first=0, n=None, max_list=CROSS_LIST_MAX, options=0, object_of_triangle=None):
+    """rt_debug_cross_self: debug_cross's result where probe i is triangles[first + i] (n None: to the end); pairs of one index or of a shared corner are
+    skipped, and with CROSS_OTHER_OBJECTS pairs of one object (object_of_triangle uint32[nt]).  ctx None = the host, else k_cross_brute on ctx's GPU."""
+    lib = load()
+    tris = np.ascontiguousarray(triangles, T.triangle)
+    n = len(tris) - first if n is None else n
+    ids = np.ascontiguousarray(object_of_triangle, np.uint32) if object_of_triangle is not None else None
+    out, members = _cross_outputs(n, max_list, options)
+    handle = ctx.handle if ctx is not None else None
+    if lib.rt_debug_cross_self(handle, _p(tris), len(tris), _p(ids), first, n, max_list, options, _p(out), _p(members)) != 0:
+        raise RtError(lib.rt_last_error(handle).decode())
+    return out if members is None else (out, members)
+
+
 def choose_tree(scene, shadow=True, mode=1):
     """rt_debug_choose_tree (host only, no GPU): the 4-wide tree rt_scene_upload would give this scene's shadow / closest-hit
     rays under RT_CTX_OPT_SHADOW_TREE / RT_CTX_OPT_CLOSEST_TREE = mode.  scene: dict with triangles, nodes, lights.
@@ -1006,6 +1082,32 @@ class Context:
         enqueues: Buffer.read() or finish() waits."""
         h = lambda b: b.handle if b is not None else None
         _check(self.lib, self.handle, self.lib.rt_scene_overlap_buffer(self.handle, h(regions), n, max_list, h(out), h(members)))
+
+    def cross(self, probes, max_list=CROSS_LIST_MAX, options=0):
+        """rt_scene_cross: every triangle of the uploaded scene that each of the caller's triangles (probe_records' rule) crosses:
+        (types.probe_hits[n], types.cross_member[n, max_list]) -- the counts, and the crossing triangles with the lowest primitive ids, ascending, with
+        their contact points; the records alone when nothing is listed (max_list == 0 or CROSS_ANY).  Bit for bit debug_cross's brute force."""
+        pr = probe_records(probes)
+        out, members = _cross_outputs(len(pr), max_list, options)
+        _check(self.lib, self.handle, self.lib.rt_scene_cross(self.handle, _p(pr), len(pr), max_list, options, _p(out), _p(members)))
+        return out if members is None else (out, members)
+
+    def cross_buffer(self, probes, n, max_list, options, out, members=None):
+        """rt_scene_cross_buffer: the same over Buffers of this context (n probes and records, n * max_list members; None: not wanted).  Only enqueues."""
+        h = lambda b: b.handle if b is not None else None
+        _check(self.lib, self.handle, self.lib.rt_scene_cross_buffer(self.handle, h(probes), n, max_list, options, h(out), h(members)))
+
+    def cross_self(self, first, n, max_list=CROSS_LIST_MAX, options=0):
+        """rt_scene_cross_self: Context.cross's result where probe i is scene triangle first + i (select's triangle order); pairs of one index or of a shared
+        corner are skipped, and with CROSS_OTHER_OBJECTS (needs set_objects) pairs of one object"""
+        out, members = _cross_outputs(n, max_list, options)
+        _check(self.lib, self.handle, self.lib.rt_scene_cross_self(self.handle, first, n, max_list, options, _p(out), _p(members)))
+        return out if members is None else (out, members)
+
+    def cross_self_buffer(self, first, n, max_list, options, out, members=None):
+        """rt_scene_cross_self_buffer: the same into Buffers of this context.  Only enqueues."""
+        h = lambda b: b.handle if b is not None else None
+        _check(self.lib, self.handle, self.lib.rt_scene_cross_self_buffer(self.handle, first, n, max_list, options, h(out), h(members)))
 
     def select(self, regions, objects=0):
         """rt_scene_select: at most 32 regions against every triangle: (touching uint32[num_triangles], inside uint32[num_triangles]), bit r for

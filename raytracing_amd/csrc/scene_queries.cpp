@@ -1,6 +1,6 @@
-// scene_queries.cpp -- the C entry points of the six query families on an uploaded scene, the bookkeeping around the kernels and launch drivers of
-// query.hip, bake.hip, nearest.hip, all_hits.hip, within.hip and region.hip (DESIGN.md sections 7h - 7m): rt_scene_trace*, rt_scene_bake*,
-// rt_scene_nearest*, rt_scene_trace_all*, rt_scene_within*, rt_scene_overlap*, rt_scene_select* and their rt_debug_* forms.  Host code only, on context.h:
+// scene_queries.cpp -- the C entry points of the seven query families on an uploaded scene, the bookkeeping around the kernels and launch drivers of
+// query.hip, bake.hip, nearest.hip, all_hits.hip, within.hip, region.hip and cross.hip (DESIGN.md sections 7h - 7n): rt_scene_trace*, rt_scene_bake*,
+// rt_scene_nearest*, rt_scene_trace_all*, rt_scene_within*, rt_scene_overlap*, rt_scene_select*, rt_scene_cross* and their rt_debug_* forms.  Host code only, on context.h:
 // a query reads the scene and writes the caller's arrays, it launches on the context's stream -- behind every refit, pose and upload, which end there --
 // and touches no frame.  (The three picks read a frame's camera and tile: they are rt_hip.hip's and call the entries here.)  The stack spill area, the
 // status word and the staging arrays of every family but the bakes are the ray queries' (ctx->query), so rt_scene_tree_report's "ray queries" line
@@ -18,6 +18,8 @@
 #include "all_hits_host.h"
 #include "within_host.h"
 #include "region_host.h"
+#include "cross_host.h"
+#include "cross.h"
 #include "device_memory.h"
 using namespace context;
 
@@ -550,6 +552,131 @@ int rt_debug_rect_region(const rt_camera* camera, uint32_t width, uint32_t heigh
     if (const char* why = region::rect_refused(width, height, x0, y0, x1, y1)) return fail(nullptr, std::string("rt_debug_rect_region: ") + why);
     *out = region::rect_region(*camera, width, height, x0, y0, x1, y1, t_near, t_far);
     return RT_OK;
+}
+
+// ---- the triangles a caller's triangle crosses, and a scene's self-crossings: rt_scene_cross / rt_scene_cross_buffer / rt_scene_cross_self /
+// rt_scene_cross_self_buffer / rt_debug_cross / rt_debug_cross_walk / rt_debug_cross_self (cross.hip) -------------------------------
+
+// everything the four scene forms refuse before anything is launched; self: probes are the scene's triangles first .. first + n - 1
+static int cross_refused(rt_ctx* ctx, const char* who, bool self, bool probes, uint32_t first, uint32_t n, uint32_t max_list, uint32_t options, bool out, bool members)
+{
+    const std::string name(who);
+    if (opening_refused(ctx, name, {}, {{"probes", self || probes || n == 0u}, {"out", out}}) != RT_OK) return RT_ERROR;
+    if (const char* why = cross_shape_refused(max_list, options, self, members)) return fail(ctx, name + ": " + why);
+    if (self && (uint64_t)first + n > ctx->scene.n_tris) return fail(ctx, name + ": first + n is beyond the scene's triangles");
+    if ((options & RT_CROSS_OTHER_OBJECTS) && !ctx->scene.pose) return fail(ctx, name + ": RT_CROSS_OTHER_OBJECTS needs rt_scene_set_objects");
+    return RT_OK;
+}
+
+static int cross_launch(rt_ctx* ctx, const char* who, const rt_probe* d_probes, uint32_t n, uint32_t max_list, uint32_t options, rt_probe_hits* d_out,
+    rt_cross_member* d_members)
+{
+    const Scene& s = ctx->scene;
+    return launch_result(ctx, who, cross::launch(ctx->stream, ctx->query, s.d, s.wide_ok, ctx->prop.multiProcessorCount, d_probes, n, max_list, options, d_out, d_members),
+        QUERY_NOT_LAUNCHED);
+}
+
+static int cross_self_launch(rt_ctx* ctx, const char* who, uint32_t first, uint32_t n, uint32_t max_list, uint32_t options, rt_probe_hits* d_out, rt_cross_member* d_members)
+{
+    const Scene& s = ctx->scene;
+    return launch_result(ctx, who, cross::launch_self(ctx->stream, ctx->query, s.d, s.wide_ok, ctx->prop.multiProcessorCount, s.pose ? s.pose->ids : nullptr, first, n,
+        max_list, options, d_out, d_members), QUERY_NOT_LAUNCHED);
+}
+
+int rt_scene_cross(rt_ctx* ctx, const rt_probe* probes, uint32_t n, uint32_t max_list, uint32_t options, rt_probe_hits* out, rt_cross_member* members)
+{
+    if (ctx && n == 0u) return RT_OK;
+    if (cross_refused(ctx, "rt_scene_cross", false, probes != nullptr, 0u, n, max_list, options, out != nullptr, members != nullptr) != RT_OK) return RT_ERROR;
+    (void)hipSetDevice(ctx->device);
+    query::Scratch& q = ctx->query;
+    // the ray queries' staging arrays: [0] the probes, [1] the members, [2] the probes' records; a chunk's probes times max_list stay within a ray query's chunk
+    const uint32_t per_probe = max_list > 0u ? max_list : 1u;
+    return staged_call(ctx, "rt_scene_cross", q, {{(void*)probes, sizeof(rt_probe), 0, true}, {members, sizeof(rt_cross_member) * per_probe, 1, false},
+        {out, sizeof(rt_probe_hits), 2, false}}, n, (uint32_t)query::CHUNK_RAYS / per_probe, [&](uint32_t, uint32_t m)
+        {
+            return cross_launch(ctx, "rt_scene_cross", (const rt_probe*)q.stage[0], m, max_list, options, (rt_probe_hits*)q.stage[2], members ? (rt_cross_member*)q.stage[1] : nullptr);
+        });
+}
+
+int rt_scene_cross_buffer(rt_ctx* ctx, rt_buffer* probes, uint32_t n, uint32_t max_list, uint32_t options, rt_buffer* out, rt_buffer* members)
+{
+    if (ctx && n == 0u) return RT_OK;
+    if (cross_refused(ctx, "rt_scene_cross_buffer", false, probes != nullptr, 0u, n, max_list, options, out != nullptr, members != nullptr) != RT_OK) return RT_ERROR;
+    if (buffers_refused(ctx, "rt_scene_cross_buffer", {{probes, sizeof(rt_probe), "probes"}, {out, sizeof(rt_probe_hits), "out"},
+            {members, sizeof(rt_cross_member) * max_list, "members"}}, n) != RT_OK)
+        return RT_ERROR;
+    (void)hipSetDevice(ctx->device);
+    return cross_launch(ctx, "rt_scene_cross_buffer", (const rt_probe*)probes->ptr, n, max_list, options, (rt_probe_hits*)out->ptr, members ? (rt_cross_member*)members->ptr : nullptr);
+}
+
+int rt_scene_cross_self(rt_ctx* ctx, uint32_t first, uint32_t n, uint32_t max_list, uint32_t options, rt_probe_hits* out, rt_cross_member* members)
+{
+    if (ctx && n == 0u) return RT_OK;
+    if (cross_refused(ctx, "rt_scene_cross_self", true, true, first, n, max_list, options, out != nullptr, members != nullptr) != RT_OK) return RT_ERROR;
+    (void)hipSetDevice(ctx->device);
+    query::Scratch& q = ctx->query;
+    // the ray queries' staging arrays: [1] the members, [2] the probes' records; nothing goes up
+    const uint32_t per_probe = max_list > 0u ? max_list : 1u;
+    return staged_call(ctx, "rt_scene_cross_self", q, {{members, sizeof(rt_cross_member) * per_probe, 1, false}, {out, sizeof(rt_probe_hits), 2, false}}, n,
+        (uint32_t)query::CHUNK_RAYS / per_probe, [&](uint32_t done, uint32_t m)
+        {
+            return cross_self_launch(ctx, "rt_scene_cross_self", first + done, m, max_list, options, (rt_probe_hits*)q.stage[2], members ? (rt_cross_member*)q.stage[1] : nullptr);
+        });
+}
+
+int rt_scene_cross_self_buffer(rt_ctx* ctx, uint32_t first, uint32_t n, uint32_t max_list, uint32_t options, rt_buffer* out, rt_buffer* members)
+{
+    if (ctx && n == 0u) return RT_OK;
+    if (cross_refused(ctx, "rt_scene_cross_self_buffer", true, true, first, n, max_list, options, out != nullptr, members != nullptr) != RT_OK) return RT_ERROR;
+    if (buffers_refused(ctx, "rt_scene_cross_self_buffer", {{out, sizeof(rt_probe_hits), "out"}, {members, sizeof(rt_cross_member) * max_list, "members"}}, n) != RT_OK)
+        return RT_ERROR;
+    (void)hipSetDevice(ctx->device);
+    return cross_self_launch(ctx, "rt_scene_cross_self_buffer", first, n, max_list, options, (rt_probe_hits*)out->ptr, members ? (rt_cross_member*)members->ptr : nullptr);
+}
+
+// what the debug forms refuse of their shape: the scene forms' rule (members with max_list == 0 or with RT_CROSS_ANY are refused there too); beyond it a
+// debug form REQUIRES members exactly when it is listed into (max_list > 0 and no RT_CROSS_ANY), which its NULL-argument check says
+static const char* debug_cross_refused(bool self, uint32_t max_list, uint32_t options, bool members)
+{
+    return cross_shape_refused(max_list, options, self, members);
+}
+
+int rt_debug_cross(rt_ctx* ctx, const rt_triangle* triangles, uint32_t num_triangles, const rt_probe* probes, uint32_t n, uint32_t max_list, uint32_t options,
+    rt_probe_hits* out, rt_cross_member* members)
+{
+    if (n == 0u) return RT_OK;
+    if (const char* why = debug_cross_refused(false, max_list, options, members != nullptr)) return fail(ctx, std::string("rt_debug_cross: ") + why);
+    const bool any = (options & RT_CROSS_ANY) != 0u;
+    if (!probes || !out || (!triangles && num_triangles > 0u) || (!members && max_list > 0u && !any)) return fail(ctx, "rt_debug_cross: NULL argument");
+    return host_or_device(ctx, "rt_debug_cross", [&] { cross::brute_host(triangles, num_triangles, probes, nullptr, 0u, n, max_list, options, out, members); },
+        [&](hipStream_t st) { return cross::brute_device(st, triangles, num_triangles, probes, nullptr, 0u, n, max_list, options, out, members); });
+}
+
+int rt_debug_cross_walk(const rt_bvh_node* nodes, uint32_t num_nodes, const rt_triangle* triangles, uint32_t num_triangles, int wide, const rt_probe* probes,
+    uint32_t n, uint32_t max_list, uint32_t options, rt_probe_hits* out, rt_cross_member* members, uint32_t* triangles_tested)
+{
+    if (n == 0u) return RT_OK;
+    if (const char* why = debug_cross_refused(false, max_list, options, members != nullptr)) return fail(nullptr, std::string("rt_debug_cross_walk: ") + why);
+    const bool any = (options & RT_CROSS_ANY) != 0u;
+    if (!nodes || num_nodes == 0u || !triangles || !probes || !out || (!members && max_list > 0u && !any)) return fail(nullptr, "rt_debug_cross_walk: NULL argument");
+    if (wide != 0 && wide != 1) return fail(nullptr, std::string("rt_debug_cross_walk") + WIDE_REFUSED);
+    if (const char* why = cross::walk_host(nodes, num_nodes, triangles, num_triangles, wide != 0, probes, n, max_list, options, out, members, triangles_tested))
+        return fail(nullptr, std::string("rt_debug_cross_walk: ") + why);
+    return RT_OK;
+}
+
+int rt_debug_cross_self(rt_ctx* ctx, const rt_triangle* triangles, uint32_t num_triangles, const uint32_t* object_of_triangle, uint32_t first, uint32_t n,
+    uint32_t max_list, uint32_t options, rt_probe_hits* out, rt_cross_member* members)
+{
+    if (n == 0u) return RT_OK;
+    if (const char* why = debug_cross_refused(true, max_list, options, members != nullptr)) return fail(ctx, std::string("rt_debug_cross_self: ") + why);
+    const bool any = (options & RT_CROSS_ANY) != 0u;
+    if (!triangles || !out || (!members && max_list > 0u && !any)) return fail(ctx, "rt_debug_cross_self: NULL argument");
+    if ((uint64_t)first + n > num_triangles) return fail(ctx, "rt_debug_cross_self: first + n is beyond the triangles");
+    if ((options & RT_CROSS_OTHER_OBJECTS) && !object_of_triangle) return fail(ctx, "rt_debug_cross_self: RT_CROSS_OTHER_OBJECTS needs object_of_triangle");
+    return host_or_device(ctx, "rt_debug_cross_self",
+        [&] { cross::brute_host(triangles, num_triangles, nullptr, object_of_triangle, first, n, max_list, options, out, members); },
+        [&](hipStream_t st) { return cross::brute_device(st, triangles, num_triangles, nullptr, object_of_triangle, first, n, max_list, options, out, members); });
 }
 
 } // extern "C"

@@ -9,6 +9,7 @@
 //   decode_slots   a box record's references and boxes: the four quantised slots of a 4-wide record or the two children of a child-pair record
 //   point_box_step one pass of a point's walk (nearest, within) at a box record: the slots keyed by nearest_box_d2, nearest first
 //   region_box_step one pass of a region's walk (overlap) at a box record: every slot region.h's box test passes is visited, in no particular order
+//   cross_box_step  one pass of a probe's walk (cross, cross_kernels.h) at a box record: the probe's closed box and the two half-spaces of its plane
 //   point_surface, ray_surface   the rt_surface of one found record (a nearest point, a hit): the body of the four surface kernels
 //   ray_step       one pass of a ray's fused loop: the fetch of one 64-byte record and its leaf, child-pair or 4-wide step; what an accepted triangle does
 //                  to the walk is the step's mode (closest, any hit, all hits)
@@ -356,6 +357,37 @@ RT_DEV void region_box_step(const float4 q0, const float4 q1, const float4 q2, c
         const float pl[4] = {p4.x, p4.y, p4.z, p4.w};
 #pragma unroll
         for (int k = 0; k < N; ++k) pass[k] = pass[k] && !region_plane_rejects_box(pl, lo[k], hi[k]);
+    }
+    uint32_t next = RT_IDLE_REF;
+#pragma unroll
+    for (int k = N - 1; k >= 0; --k)
+        if (pass[k])
+        {
+            if (next != RT_IDLE_REF) stack.push(next, 0.0f);
+            next = r[k];
+        }
+    if (next != RT_IDLE_REF) ref = next;
+    else ref = stack.pop([](float) { return true; });
+}
+
+// One pass of a probe's walk (cross) at a box record: its slots (decode_slots), each tested against the probe's closed box (plain comparisons) and, when
+// `plane`, against the two half-spaces of the probe's plane pl = (n, d) and (-n, -d) (region.h's box test; cross.h has the argument).  A counting walk like
+// region_box_step: all passing slots but one are pushed, that one is visited next; none: a pop, which always accepts.  The probe's 10 floats are registers.
+template <bool WIDE>
+RT_DEV void cross_box_step(const float4 q0, const float4 q1, const float4 q2, const float4 q3, const float (&qlo)[3], const float (&qhi)[3], const float (&pl)[4],
+    const bool plane, uint32_t& ref, Stack& stack)
+{
+    constexpr int N = WIDE ? 4 : 2;
+    uint32_t r[N];
+    float lo[N][3], hi[N][3];
+    decode_slots<WIDE>(q0, q1, q2, q3, r, lo, hi);
+    const float neg[4] = {-pl[0], -pl[1], -pl[2], -pl[3]};
+    bool pass[N];
+#pragma unroll
+    for (int k = 0; k < N; ++k)
+    {
+        pass[k] = r[k] != RT_EMPTY_REF && qlo[0] <= hi[k][0] && lo[k][0] <= qhi[0] && qlo[1] <= hi[k][1] && lo[k][1] <= qhi[1] && qlo[2] <= hi[k][2] && lo[k][2] <= qhi[2];
+        pass[k] = pass[k] && !(plane && (region_plane_rejects_box(pl, lo[k], hi[k]) || region_plane_rejects_box(neg, lo[k], hi[k])));
     }
     uint32_t next = RT_IDLE_REF;
 #pragma unroll

@@ -26,7 +26,7 @@ EXPORTS = [
     "rth_render_upload_gpu_data", "rth_render_setup_seconds", "rth_render_create_with_options",
     "rth_render_set_refittable", "rth_render_refit", "rth_render_set_refit_motion",
     "rth_render_set_objects", "rth_render_pose", "rth_render_pick", "rth_render_integrator_pick", "rth_render_trace",
-    "rth_render_bake", "rth_render_occlusion_image", "rth_render_nearest", "rth_render_within", "rth_render_overlap", "rth_render_select", "rth_render_pick_rect", "rth_render_integrator_pick_rect", "rth_render_trace_all", "rth_render_pick_all",
+    "rth_render_bake", "rth_render_occlusion_image", "rth_render_nearest", "rth_render_within", "rth_render_overlap", "rth_render_cross", "rth_render_self_cross", "rth_render_select", "rth_render_pick_rect", "rth_render_integrator_pick_rect", "rth_render_trace_all", "rth_render_pick_all",
     "rth_scene_set_triangle_objects", "rth_scene_num_objects", "rth_scene_object_name", "rth_scene_num_triangle_objects", "rth_scene_triangle_objects",
 ]
 
@@ -78,7 +78,8 @@ def load():
         "rth_render_bake": (i32, [vp, vp, u32, vp, vp]), "rth_render_occlusion_image": (i32, [vp, vp, vp]),
         "rth_render_nearest": (i32, [vp, vp, u32, vp, vp]),
         "rth_render_within": (i32, [vp, vp, u32, u32, u32, vp, vp, vp]),
-        "rth_render_overlap": (i32, [vp, vp, u32, u32, vp, vp]), "rth_render_select": (i32, [vp, vp, u32, vp, vp, vp, vp]),
+        "rth_render_overlap": (i32, [vp, vp, u32, u32, vp, vp]),
+        "rth_render_cross": (i32, [vp, vp, u32, u32, u32, vp, vp]), "rth_render_self_cross": (i32, [vp, u32, u32, u32, u32, vp, vp]), "rth_render_select": (i32, [vp, vp, u32, vp, vp, vp, vp]),
         "rth_render_pick_rect": (i32, [vp, u32, u32, u32, u32, C.c_float, C.c_float, vp, vp, vp, vp, vp]),
         "rth_render_integrator_pick_rect": (i32, [vp, u32, u32, u32, u32, C.c_float, C.c_float, vp, vp, vp]),
         "rth_render_trace_all": (i32, [vp, vp, u32, u32, vp, vp, vp]), "rth_render_pick_all": (i32, [vp, u32, u32, u32, vp, vp, vp, vp]),
@@ -512,6 +513,66 @@ class Render:
                 listed.append(d)
             result.append({"count": int(out[i]["count"]), "inside": int(out[i]["inside"]), "searched": bool(out[i]["flags"] & capi.REGION_HITS_SEARCHED), "members": listed})
         return result
+
+    def _cross_dicts(self, out, members):
+        """one dict per probe of a crossing query's records: `count`, `first_primitive`, `searched` and `members`, dicts of `primitive_id`, `flags` (bits
+        0..2: the probe's edges cut the triangle, 3..5: the triangle's edges cut the probe), `c0` and `c1` (the contact points) and, when the scene was
+        loaded with objects, `object_name`"""
+        from . import capi
+        names = self.scene.object_names()
+        objects = self.scene.triangle_objects() if names else None
+        result = []
+        for i in range(len(out)):
+            listed = []
+            for m in (members[i][:int(out[i]["stored"])] if members is not None else ()):
+                d = {"primitive_id": int(m["primitive_id"]), "flags": int(m["flags"]), "c0": m["c0"].copy(), "c1": m["c1"].copy()}
+                if names:
+                    d["object_name"] = names[objects[d["primitive_id"]]]
+                listed.append(d)
+            result.append({"count": int(out[i]["count"]), "first_primitive": int(out[i]["first_primitive"]),
+                           "searched": bool(out[i]["flags"] & capi.PROBE_HITS_SEARCHED), "members": listed})
+        return result
+
+    def cross(self, probes, k=0, any=False):
+        """Every triangle of the scene as it is posed now that each of the caller's triangles crosses (Render::Cross; probes: capi.probe_records' rule --
+        types.probes_from_triangles, or float[n, 3, 3] corners): one dict per probe (_cross_dicts), the members the min(count, k) crossing triangles with
+        the lowest primitive ids.  k <= 8.  any=True stops at the first crossing: count is 0 or 1 and nothing is listed."""
+        from . import capi
+        pr = capi.probe_records(probes)
+        n = len(pr)
+        options = capi.CROSS_ANY if any else 0
+        out = np.zeros(n, T.probe_hits)
+        members = np.zeros((n, k), T.cross_member) if k and not any else None
+        self._c(self.lib.rth_render_cross(self.handle, pr.ctypes.data if n else None, n, k, options, out.ctypes.data, members.ctypes.data if members is not None else None))
+        return self._cross_dicts(out, members)
+
+    def self_cross(self, first=0, n=None, k=8, other_objects=False):
+        """The scene's own triangles first .. first + n - 1 (n None: to the end) as probes (Render::SelfCross): one dict per probe (_cross_dicts).  Pairs of one
+        triangle or of a shared corner are skipped; other_objects=True (after set_objects) also skips pairs of one object."""
+        from . import capi
+        nt = self.lib.rth_scene_num_triangles(self.scene.handle)
+        n = nt - first if n is None else n
+        out = np.zeros(n, T.probe_hits)
+        members = np.zeros((n, k), T.cross_member) if k else None
+        self._c(self.lib.rth_render_self_cross(self.handle, first, n, k, capi.CROSS_OTHER_OBJECTS if other_objects else 0, out.ctypes.data,
+                                               members.ctypes.data if k else None))
+        return self._cross_dicts(out, members)
+
+    def interpenetrations(self):
+        """Which objects cut into each other in the scene as it is posed now (the scene loaded with objects, after set_objects): the self form with
+        RT_CROSS_OTHER_OBJECTS over all triangles.  {"pairs": the set of (object name, object name) pairs, each sorted, seen in the LISTED members,
+        "complete": no triangle crosses more than the 8 that a list holds}.  When `complete` is False a pair may be missing: a crossing query lists the 8
+        lowest ids and cannot skip them."""
+        names = self.scene.object_names()
+        if not names:
+            raise RtError("interpenetrations: the scene was not loaded with objects")
+        objects = self.scene.triangle_objects()
+        pairs, complete = set(), True
+        for i, got in enumerate(self.self_cross(k=8, other_objects=True)):
+            complete = complete and got["count"] <= 8
+            for m in got["members"]:
+                pairs.add(tuple(sorted((names[objects[i]], m["object_name"]))))
+        return {"pairs": pairs, "complete": complete}
 
     def select(self, regions):
         """At most 32 regions against every triangle of the scene as it is posed now (Render::Select): one dict per region -- `touching` and `inside`, the

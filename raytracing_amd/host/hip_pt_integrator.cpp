@@ -190,6 +190,18 @@ void HIPPathTraceIntegrator::PointsWithin(rt_point const* points, std::size_t co
     Check(rt_scene_within(context_.Get(), points, (uint32_t)count, max_near, options, out, near, surfaces));
 }
 
+void HIPPathTraceIntegrator::TrianglesCross(rt_probe const* probes, std::size_t count, std::uint32_t max_list, std::uint32_t options, rt_probe_hits* out, rt_cross_member* members)
+{
+    if (count > 0xFFFFFFFFull) throw HIPException("HIPPathTraceIntegrator::TrianglesCross: more than 2^32 - 1 probes in one call");
+    Check(rt_scene_cross(context_.Get(), probes, (uint32_t)count, max_list, options, out, members));
+}
+
+void HIPPathTraceIntegrator::SelfCross(std::uint32_t first, std::size_t count, std::uint32_t max_list, std::uint32_t options, rt_probe_hits* out, rt_cross_member* members)
+{
+    if (count > 0xFFFFFFFFull) throw HIPException("HIPPathTraceIntegrator::SelfCross: more than 2^32 - 1 probes in one call");
+    Check(rt_scene_cross_self(context_.Get(), first, (uint32_t)count, max_list, options, out, members));
+}
+
 void HIPPathTraceIntegrator::RegionsOverlap(rt_region const* regions, std::size_t count, std::uint32_t max_list, rt_region_hits* out, rt_region_member* members)
 {
     if (count > 0xFFFFFFFFull) throw HIPException("HIPPathTraceIntegrator::RegionsOverlap: more than 2^32 - 1 regions in one call");

@@ -137,6 +137,13 @@ public:
         std::uint32_t* inside, std::uint32_t* object_touching, std::uint32_t* object_inside);
     void PickRectThrough(Camera const& camera, std::uint32_t x0, std::uint32_t y0, std::uint32_t x1, std::uint32_t y1, float t_near, float t_far, rt_region* region,
         std::uint32_t* touching, std::uint32_t* inside, std::uint32_t* object_touching, std::uint32_t* object_inside);
+    // Cross (rt_scene_cross / rt_scene_cross_self): TrianglesCross -- per caller-supplied triangle the scene triangles it crosses, the counts
+    // in out and the crossing ones with the lowest ids, their six tests' bits and two contact points in members (max_list per probe; may be null); SelfCross --
+    // the same where probe i is scene triangle first + i, neighbours that share a corner skipped (RT_CROSS_OTHER_OBJECTS: pairs of one object too, after
+    // SetObjects).  options: RT_CROSS_ANY, RT_CROSS_OTHER_OBJECTS.  Both throw HIPException with the library's message on a refusal; neither requests a reset or
+    // touches the frame.
+    void TrianglesCross(rt_probe const* probes, std::size_t count, std::uint32_t max_list, std::uint32_t options, rt_probe_hits* out, rt_cross_member* members);
+    void SelfCross(std::uint32_t first, std::size_t count, std::uint32_t max_list, std::uint32_t options, rt_probe_hits* out, rt_cross_member* members);
     // All hits (rt_scene_trace_all / rt_frame_pick_all): every surface each ray crosses -- the counts in out, the nearest max_hits crossings
     // in hits and surfaces (max_hits records per ray; either may be null).  PickAll: the ray through the centre of pixel (x, y) of the frame's current camera;
     // PickAllThrough: the same for a camera the frame has not been given, as PickThrough.  All throw HIPException with the library's message on a refusal; none

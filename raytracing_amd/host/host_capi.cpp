@@ -290,6 +290,14 @@ int rth_render_within(void* r, const rt_point* points, uint32_t n, uint32_t max_
 {
     return guard([&]() { ((rt::Render*)r)->Within(points, n, max_near, options, out, near, surfaces); return 0; }, 1);
 }
+int rth_render_cross(void* r, const rt_probe* probes, uint32_t n, uint32_t max_list, uint32_t options, rt_probe_hits* out, rt_cross_member* members)
+{
+    return guard([&]() { ((rt::Render*)r)->Cross(probes, n, max_list, options, out, members); return 0; }, 1);
+}
+int rth_render_self_cross(void* r, uint32_t first, uint32_t n, uint32_t max_list, uint32_t options, rt_probe_hits* out, rt_cross_member* members)
+{
+    return guard([&]() { ((rt::Render*)r)->SelfCross(first, n, max_list, options, out, members); return 0; }, 1);
+}
 int rth_render_overlap(void* r, const rt_region* regions, uint32_t n, uint32_t max_list, rt_region_hits* out, rt_region_member* members)
 {
     return guard([&]() { ((rt::Render*)r)->Overlap(regions, n, max_list, out, members); return 0; }, 1);

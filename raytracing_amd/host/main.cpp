@@ -1,6 +1,7 @@
 // main.cpp -- headless command line front end with the reference's flags
 // (src/main.cpp:34-58: -w -h --scene --scale --flip_yz) plus the knobs the GUI
 // exposed (--bounces, --furnace, aperture/focus) and --spp / --out for batch use.
+#include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -47,6 +48,9 @@ int main(int argc, char** argv)
         struct WithinAt { rt_point point; std::uint32_t k; };
         std::vector<WithinAt> within_points;    // --within x,y,z,r[,k] (repeatable): after the scene is uploaded and posed, print the triangles within r (the k nearest only)
         struct OverlapAt { float lo[3], hi[3]; std::uint32_t k; };
+        struct CrossAt { rt_probe probe; std::uint32_t k; };
+        std::vector<CrossAt> cross_probes;      // --cross x1,y1,z1,x2,y2,z2,x3,y3,z3[,k] (repeatable): after the scene is uploaded and posed, print the triangles that triangle crosses (the k lowest ids)
+        bool self_cross = false;                // --self_cross 1: print which triangles of the scene cross each other, neighbours that share a corner aside
         std::vector<OverlapAt> overlap_boxes;   // --overlap lx,ly,lz,hx,hy,hz[,k] (repeatable): after the scene is uploaded and posed, print the triangles the box touches (the k lowest ids)
         struct RectAt { std::uint32_t x0, y0, x1, y1; bool window; };
         std::vector<RectAt> pick_rects;         // --pick_rect x0,y0,x1,y1[,window] (repeatable): print what lies under that pixel rectangle (window: wholly inside it)
@@ -166,6 +170,21 @@ int main(int argc, char** argv)
                 within_points.push_back(q);
                 scene_options |= rt::Scene::kObjects;
             }
+            else if (!strcmp(argv[i], "--cross"))
+            {
+                CrossAt q = {};
+                q.k = RT_CROSS_LIST_MAX;
+                float* p[3] = {q.probe.p1, q.probe.p2, q.probe.p3};
+                const int got = sscanf(next(), "%f,%f,%f,%f,%f,%f,%f,%f,%f,%u", &p[0][0], &p[0][1], &p[0][2], &p[1][0], &p[1][1], &p[1][2], &p[2][0], &p[2][1], &p[2][2], &q.k);
+                if (got < 9 || q.k > RT_CROSS_LIST_MAX)
+                {
+                    std::cerr << "--cross wants x1,y1,z1,x2,y2,z2,x3,y3,z3 or the same followed by ,k (a triangle's corners and optionally how many triangles to list, 0 .. 8)\n";
+                    return 2;
+                }
+                cross_probes.push_back(q);
+                scene_options |= rt::Scene::kObjects;
+            }
+            else if (!strcmp(argv[i], "--self_cross")) { if (atoi(next()) != 0) { self_cross = true; scene_options |= rt::Scene::kObjects; } }
             else if (!strcmp(argv[i], "--overlap"))
             {
                 OverlapAt q;
@@ -226,6 +245,9 @@ int main(int argc, char** argv)
                              "  (default 1), 1 where the pixel sees nothing; traced and baked on the device (rt_scene_bake_buffer); one GPU only\n"
                              "  --pick_all x,y (repeatable) prints every surface under that pixel, nearest first, one line per surface; --signed 1 makes --nearest print whether\n"
                              "    the point is inside (more exits than entries along (0.36, 0.48, 0.8))\n"
+                             "  --cross x1,y1,z1,x2,y2,z2,x3,y3,z3[,k] (repeatable) prints the triangles that triangle crosses once the scene is uploaded and posed: how many, and\n"
+                             "  one line for each of the k (default 8) lowest primitive ids with the two contact points; --self_cross 1 prints how many of the scene's own\n"
+                             "  triangles cross another one (neighbours that share a corner aside) and the pairs of objects among them; one GPU only\n"
                              "  --overlap lx,ly,lz,hx,hy,hz[,k] (repeatable) prints the triangles that axis-aligned box touches once the scene is uploaded and posed: how many,\n"
                              "  how many lie wholly inside, and one line for each of the k (default 8) lowest primitive ids; --pick_rect x0,y0,x1,y1[,window] (repeatable)\n"
                              "  prints what lies under that inclusive pixel rectangle: the primitives its region touches (window: wholly inside) and their objects; one GPU only\n"
@@ -287,6 +309,11 @@ int main(int argc, char** argv)
         if (!within_points.empty() && (gpus > 1 || tiled_path))
         {
             std::cerr << "--within needs one GPU\n";
+            return 2;
+        }
+        if ((!cross_probes.empty() || self_cross) && (gpus > 1 || tiled_path))
+        {
+            std::cerr << "--cross and --self_cross need one GPU\n";
             return 2;
         }
         if ((!overlap_boxes.empty() || !pick_rects.empty()) && (gpus > 1 || tiled_path))
@@ -510,6 +537,55 @@ int main(int argc, char** argv)
                 }
             }
         };
+        // --cross: one line per probe and one per listed triangle (rt_scene_cross through Render::Cross); --self_cross: rt_scene_cross_self over all triangles
+        auto print_crosses = [&]()
+        {
+            for (const CrossAt& q : cross_probes)
+            {
+                rt_probe_hits rec;
+                rt_cross_member members[RT_CROSS_LIST_MAX];
+                render.Cross(&q.probe, 1, q.k, 0u, &rec, q.k ? members : nullptr);
+                std::cout << "cross " << q.probe.p1[0] << "," << q.probe.p1[1] << "," << q.probe.p1[2] << " " << q.probe.p2[0] << "," << q.probe.p2[1] << "," << q.probe.p2[2] << " "
+                          << q.probe.p3[0] << "," << q.probe.p3[1] << "," << q.probe.p3[2] << ": ";
+                if (rec.count == 0u) { std::cout << "none" << std::endl; continue; }
+                std::cout << "count " << rec.count << " listed " << rec.stored << std::endl;
+                for (std::uint32_t j = 0; j < rec.stored; ++j)
+                {
+                    const rt_cross_member& m = members[j];
+                    std::cout << "cross   " << j << ": primitive " << m.primitive_id << " tests " << m.flags << " from " << m.c0[0] << "," << m.c0[1] << "," << m.c0[2] << " to "
+                              << m.c1[0] << "," << m.c1[1] << "," << m.c1[2] << " object ";
+                    print_object(object_of(m.primitive_id));
+                    std::cout << std::endl;
+                }
+            }
+            if (self_cross)
+            {
+                const std::size_t nt = scene.GetTriangles().size();
+                std::vector<rt_probe_hits> recs(nt);
+                std::vector<rt_cross_member> members(nt * RT_CROSS_LIST_MAX);
+                render.SelfCross(0u, nt, RT_CROSS_LIST_MAX, 0u, recs.data(), members.data());
+                std::size_t crossing = 0, listed = 0, over = 0;
+                std::vector<std::pair<std::uint32_t, std::uint32_t>> pairs;
+                for (std::size_t t = 0; t < nt; ++t)
+                {
+                    crossing += recs[t].count != 0u; listed += recs[t].stored; over += recs[t].count > RT_CROSS_LIST_MAX;
+                    for (std::uint32_t j = 0; j < recs[t].stored; ++j)
+                    {
+                        const std::uint32_t a = object_of((std::uint32_t)t), b = object_of(members[t * RT_CROSS_LIST_MAX + j].primitive_id);
+                        if (a != b) pairs.push_back({a < b ? a : b, a < b ? b : a});
+                    }
+                }
+                std::sort(pairs.begin(), pairs.end());
+                pairs.erase(std::unique(pairs.begin(), pairs.end()), pairs.end());
+                std::cout << "self_cross: triangles " << nt << " crossing " << crossing << " listed " << listed << " above the list " << over << std::endl;
+                for (const auto& p : pairs)
+                {
+                    std::cout << "self_cross   objects ";
+                    print_object(p.first); std::cout << " | "; print_object(p.second);
+                    std::cout << std::endl;
+                }
+            }
+        };
         // --pick_rect: one line per rectangle and one per object (rt_scene_select of the rectangle's region through Render::PickRect)
         auto print_pick_rects = [&]()
         {
@@ -598,6 +674,7 @@ int main(int argc, char** argv)
             print_nearest();
             print_within();
             print_overlaps();
+            print_crosses();
             print_pick_rects();
             write_ao();
             return 0;
@@ -642,6 +719,7 @@ int main(int argc, char** argv)
         print_nearest();
         print_within();
         print_overlaps();
+        print_crosses();
         print_pick_rects();
         write_ao();
         if (!out.empty() && (filter_iterations >= 0 || temporal_iterations >= 0))

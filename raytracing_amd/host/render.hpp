@@ -56,6 +56,9 @@ public:
     void Within(rt_point const* points, std::size_t count, std::uint32_t max_near, std::uint32_t options, rt_point_hits* out, rt_nearest* near, rt_surface* surfaces) { integrator_->PointsWithin(points, count, max_near, options, out, near, surfaces); }
     // every triangle a convex region touches or encloses: counted and the lowest ids listed per region (Overlap), a bit per region for every
     // triangle and object of at most 32 regions (Select), the pixel rectangle of the Render's current camera (PickRect); the frame is not touched
+    // every scene triangle a caller's triangle crosses, with contact points, and the scene's self-crossings
+    void Cross(rt_probe const* probes, std::size_t count, std::uint32_t max_list, std::uint32_t options, rt_probe_hits* out, rt_cross_member* members) { integrator_->TrianglesCross(probes, count, max_list, options, out, members); }
+    void SelfCross(std::uint32_t first, std::size_t count, std::uint32_t max_list, std::uint32_t options, rt_probe_hits* out, rt_cross_member* members) { integrator_->SelfCross(first, count, max_list, options, out, members); }
     void Overlap(rt_region const* regions, std::size_t count, std::uint32_t max_list, rt_region_hits* out, rt_region_member* members) { integrator_->RegionsOverlap(regions, count, max_list, out, members); }
     void Select(rt_region const* regions, std::uint32_t count, std::uint32_t* touching, std::uint32_t* inside, std::uint32_t* object_touching, std::uint32_t* object_inside) { integrator_->SelectRegions(regions, count, touching, inside, object_touching, object_inside); }
     void PickRect(std::uint32_t x0, std::uint32_t y0, std::uint32_t x1, std::uint32_t y1, float t_near, float t_far, rt_region* region, std::uint32_t* touching, std::uint32_t* inside, std::uint32_t* object_touching, std::uint32_t* object_inside) { integrator_->PickRectThrough(camera_, x0, y0, x1, y1, t_near, t_far, region, touching, inside, object_touching, object_inside); }

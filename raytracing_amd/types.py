@@ -37,6 +37,12 @@ point_hits = np.dtype([("count", "<u4"), ("stored", "<u4"), ("nearest_primitive"
 region = np.dtype([("num_planes", "<u4"), ("reserved", "<u4", (3,)), ("planes", "<f4", (8, 4))])
 region_hits = np.dtype([("count", "<u4"), ("inside", "<u4"), ("stored", "<u4"), ("flags", "<u4")])
 region_member = np.dtype([("primitive_id", "<u4"), ("flags", "<u4")])
+# rt_probe / rt_probe_hits / rt_cross_member (include/rt_hip.h): a crossing query's triangle (every fourth component is ignored), what it reports of it (the
+# crossing triangles, how many are listed, the lowest id; flags bit 0 = searched, bit 1 = an any-mode answer) and a listed member (flags bits 0..2: the probe's
+# edges cut the triangle, bits 3..5: the triangle's edges cut the probe; c0, c1: the contact points of the two lowest set bits)
+probe = np.dtype([("p1", "<f4", (4,)), ("p2", "<f4", (4,)), ("p3", "<f4", (4,))])
+probe_hits = np.dtype([("count", "<u4"), ("stored", "<u4"), ("first_primitive", "<u4"), ("flags", "<u4")])
+cross_member = np.dtype([("primitive_id", "<u4"), ("flags", "<u4"), ("c0", "<f4", (3,)), ("c1", "<f4", (3,))])
 camera = np.dtype([("position", float3), ("front", float3), ("up", float3), ("fov", "<f4"),
                    ("aspect_ratio", "<f4"), ("aperture", "<f4"), ("focus_distance", "<f4")])
 
@@ -46,6 +52,22 @@ assert vertex.itemsize == 48 and triangle.itemsize == 160 and bvh_node.itemsize 
 assert camera.itemsize == 64 and surface.itemsize == 64 and bake_result.itemsize == 16
 assert point.itemsize == 16 and nearest.itemsize == 32 and ray_hits.itemsize == 16 and point_hits.itemsize == 16
 assert region.itemsize == 144 and region_hits.itemsize == 16 and region_member.itemsize == 8
+assert probe.itemsize == 48 and probe_hits.itemsize == 16 and cross_member.itemsize == 32
+
+
+def probes_from_corners(corners):
+    """types.probe[n] of float[n, 3, 3] corners (probe, corner, coordinate)"""
+    c = np.asarray(corners, np.float32).reshape(-1, 3, 3)
+    out = np.zeros(len(c), probe)
+    for k, name in enumerate(("p1", "p2", "p3")):
+        out[name][:, :3] = c[:, k]
+    return out
+
+
+def probes_from_triangles(vertices, faces):
+    """types.probe[len(faces)] of an indexed mesh: vertices float[nv, 3], faces int[nf, 3]"""
+    v, f = np.asarray(vertices, np.float32).reshape(-1, 3), np.asarray(faces, np.int64).reshape(-1, 3)
+    return probes_from_corners(v[f])
 
 
 def planes_region(planes):
