@@ -545,6 +545,52 @@ int rt_debug_cross_walk(const rt_bvh_node* nodes, uint32_t num_nodes, const rt_t
 int rt_debug_cross_self(rt_ctx* ctx_or_null, const rt_triangle* triangles, uint32_t num_triangles, const uint32_t* object_of_triangle_or_null, uint32_t first,
                         uint32_t n, uint32_t max_list, uint32_t options, rt_probe_hits* out, rt_cross_member* members);
 
+/* ---- separation: the nearest triangle of the uploaded scene to a CALLER's triangle (a probe), how far it is and where the two closest points lie (opt-in
+ * extension): the other half of contact work -- a probe that cuts nothing asks how far it is from the scene, posed objects ask how much
+ * clearance is left between them.  A triangle's distance to the scene is not the minimum over its corners (rt_scene_nearest): edge against edge and a scene
+ * corner against the probe's face are candidates too.  raytracing_amd/csrc/separation.h states the rule.
+ *   a probe: rt_probe, three corners (every fourth component is ignored); SEARCHED when its nine coordinates are finite and max_distance >= 0 (one value per
+ *     call; +inf is allowed, a NaN is not searched).
+ *   SEP(Q, T), T on its shading record's corners: when CROSS(Q, T) holds (the cross family's verdict) the distance is 0, both points are that pair's first
+ *     contact point c0 and the feature is 15.  Otherwise the least of fifteen candidates, the lowest index among equal ones: 0..2 a probe corner against T
+ *     (rt_scene_nearest's point-triangle distance), 3..5 a corner of T against the probe, 6 + 3 i + j edge i of the probe against edge j of T (edges 1->2,
+ *     2->3, 3->1; segment against segment, clamped into the segments' boxes).
+ *   rt_separation: the triangle with the least SEP within max_distance, the lowest primitive id among equal ones -- an order no tree decides.  on_probe /
+ *     on_scene = the two closest points, distance = sqrtf of the squared distance (0 for a crossing), feature = the winning candidate, flags =
+ *     RT_SEPARATION_SEARCHED | RT_SEPARATION_FOUND | RT_SEPARATION_CROSSING.  Nothing found: primitive_id = RT_INVALID_ID and zeros (flags keeps SEARCHED).
+ *   The answer is a statement about triangles and separation.h alone -- bit for bit rt_debug_separation's brute force, whichever records are walked, after any
+ *     refit or pose (separation.h has the argument).
+ *   rt_scene_separation: host arrays, staged in chunks; returns when the outputs are written.  rt_scene_separation_buffer: rt_buffers of this context (n
+ *     rt_probe, n rt_separation); only enqueues.
+ *   rt_scene_separation_self / _buffer: probe i is scene triangle first + i, nothing is uploaded.  A pair is SKIPPED when both are the same triangle or share
+ *     a corner (the cross family's rule); RT_SEPARATION_OTHER_OBJECTS (self forms only; needs rt_scene_set_objects) also skips pairs of one object.  SEP is
+ *     not symmetric to the last bit (the edge-pair routine is not): a caller that holds both directions of a pair takes the smaller.
+ * Refused with nothing launched: a NULL context, no scene, NULL probes with n > 0, out NULL, unknown option bits, RT_SEPARATION_OTHER_OBJECTS without objects
+ * or on a form that is not a self form, first + n beyond the scene, a buffer of another context or one that is too small.  n == 0: RT_OK. */
+#define RT_SEPARATION_OTHER_OBJECTS 2u      /* options bit 1 (self forms), RT_CROSS_OTHER_OBJECTS' bit */
+#define RT_SEPARATION_SEARCHED 1u           /* rt_separation.flags bit 0 */
+#define RT_SEPARATION_FOUND 2u              /* rt_separation.flags bit 1 */
+#define RT_SEPARATION_CROSSING 4u           /* rt_separation.flags bit 2 */
+#define RT_SEPARATION_FEATURE_CROSSING 15u  /* rt_separation.feature of a crossing pair */
+typedef struct rt_separation { float on_probe[3]; float distance; float on_scene[3]; uint32_t primitive_id;
+                               uint32_t flags; uint32_t feature; uint32_t pad[2]; } rt_separation;                               /* 48 bytes */
+int rt_scene_separation(rt_ctx* ctx, const rt_probe* probes, uint32_t n, float max_distance, uint32_t options, rt_separation* out);
+int rt_scene_separation_buffer(rt_ctx* ctx, rt_buffer* probes, uint32_t n, float max_distance, uint32_t options, rt_buffer* out);
+int rt_scene_separation_self(rt_ctx* ctx, uint32_t first, uint32_t n, float max_distance, uint32_t options, rt_separation* out);
+int rt_scene_separation_self_buffer(rt_ctx* ctx, uint32_t first, uint32_t n, float max_distance, uint32_t options, rt_buffer* out);
+/* brute force over all of `triangles` (primitive_id = the index): separation.h on the host (ctx == NULL) or k_separation_brute on uploaded copies.  The two
+ * agree bit for bit.  Refused: a NULL argument. */
+int rt_debug_separation(rt_ctx* ctx_or_null, const rt_triangle* triangles, uint32_t num_triangles, const rt_probe* probes, uint32_t n, float max_distance,
+                        rt_separation* out);
+/* k_separation's walk on the host (no GPU): the child-pair form of `nodes` (wide == 0) or build_wide_bvh's 4-wide records of them (wide == 1), the nearest
+ * box first, pruned by separation.h's bound; triangles_tested_or_null[i] = how many triangles probe i was handed at a leaf.  Refused where
+ * rt_debug_nearest_walk is. */
+int rt_debug_separation_walk(const rt_bvh_node* nodes, uint32_t num_nodes, const rt_triangle* triangles, uint32_t num_triangles, int wide, const rt_probe* probes,
+                             uint32_t n, float max_distance, rt_separation* out, uint32_t* triangles_tested_or_null);
+/* brute force of the self form: probe i is triangles[first + i]; RT_SEPARATION_OTHER_OBJECTS needs object_of_triangle. */
+int rt_debug_separation_self(rt_ctx* ctx_or_null, const rt_triangle* triangles, uint32_t num_triangles, const uint32_t* object_of_triangle_or_null,
+                             uint32_t first, uint32_t n, float max_distance, uint32_t options, rt_separation* out);
+
 /* One fold adaptation per process GROUP instead of one per rank (N ranks that tile one image hold the same scene and would each probe, rotate and fold for
  * identical records): the context's current 4-wide records -- the closest-hit rays' and the shadow rays' (n_shadow == 0: they share), as adapted so far -- to
  * host buffers of `capacity` records each (records NULL: size query; entries2 = {closest entry, shadow entry}), and into another context that has uploaded

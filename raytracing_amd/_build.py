@@ -44,7 +44,7 @@ def hipcc():
 # librt_hip.so = several translation units (rt_hip.hip alone was 3 600 lines): the C-ABI with the hot path's kernels, the tree work on the device
 # (a code object of its own: the hot path's is not rebuilt or re-hashed when the builder changes), the spatial and temporal filters' kernels (likewise), and the host
 # side of the tree work.  The scene queries are split the same way twice over: each family's kernels and launch driver are a unit with a code object of its own, and
-# the C entry points of all seven are one host-only unit (scene_queries.cpp, on context.h), so neither a kernel nor an entry point's bookkeeping rebuilds the hot path.
+# the C entry points of all eight are one host-only unit (scene_queries.cpp, on context.h), so neither a kernel nor an entry point's bookkeeping rebuilds the hot path.
 # The scene side -- upload, tree choice, the adaptation's worker, refit, pose and the tree work's debug forms -- is a host-only unit too (scene_upload.cpp).
 HIP_UNITS = [
     ("rt_hip", "rt_hip.hip", True),            # C-ABI, frames, launch logic + kernels.h (the hot path)
@@ -58,8 +58,9 @@ HIP_UNITS = [
     ("within", "within.hip", True),            # every triangle within a radius of caller-supplied points, counted and sorted: kernels on walk_kernels.h's stack and point_box_step + host driver on query.hip's core + the host's brute force and walk (a code object of its own)
     ("region", "region.hip", True),            # every triangle a caller-supplied convex region (up to 8 half-spaces) touches or encloses, counted and listed, and the per-triangle select of a few regions: kernels on walk_kernels.h's stack and region_box_step + host driver on query.hip's core + the host's brute force and walk (a code object of its own)
     ("cross", "cross.hip", True),              # every scene triangle a caller-supplied triangle crosses (boxes, the probe's plane, six segment tests) with contact points, and the scene's self-crossings: kernels on walk_kernels.h's stack, volume_step and cross_box_step + host driver on query.hip's core + the host's brute force and walk (a code object of its own)
+    ("separation", "separation.hip", True),    # the nearest scene triangle to a caller-supplied triangle (the crossing verdict, then fifteen point-triangle and edge-edge candidates) with the two closest points, and the scene's clearances: kernels on walk_kernels.h's stack, volume_step and probe_box_step + host driver on query.hip's core + the host's brute force and walk (a code object of its own)
     ("all_hits", "all_hits.hip", True),        # every surface a caller-supplied ray crosses, counted and sorted: kernels on walk_kernels.h + host driver on query.hip's core + the host's brute force (a code object of its own)
-    ("scene_queries", "scene_queries.cpp", False),   # the C entry points of the seven query families above (rt_scene_trace* .. rt_scene_cross*, their rt_debug_* forms) on context.h: an edit to a query's bookkeeping rebuilds no kernel (no device code)
+    ("scene_queries", "scene_queries.cpp", False),   # the C entry points of the eight query families above (rt_scene_trace* .. rt_scene_separation*, their rt_debug_* forms) on context.h: an edit to a query's bookkeeping rebuilds no kernel (no device code)
     ("scene_upload", "scene_upload.cpp", False),     # rt_scene_upload and its stages, tree choice, FoldAdapt's worker, rt_scene_refit* / set_objects / pose / export_folds / import_folds / tree_report, the tree work's rt_debug_* forms, on context.h + fold_adapt.h (no device code)
     ("wide_bvh", "wide_bvh.cpp", False),       # build_wide_bvh, pair layout, the adaptation's host walks (no device code)
 ]

@@ -120,6 +120,8 @@ EXPORTS = [
     "rt_scene_select", "rt_scene_select_buffer", "rt_debug_select", "rt_frame_pick_rect", "rt_debug_rect_region",
     "rt_scene_cross", "rt_scene_cross_buffer", "rt_scene_cross_self", "rt_scene_cross_self_buffer",
     "rt_debug_cross", "rt_debug_cross_walk", "rt_debug_cross_self",
+    "rt_scene_separation", "rt_scene_separation_buffer", "rt_scene_separation_self", "rt_scene_separation_self_buffer",
+    "rt_debug_separation", "rt_debug_separation_walk", "rt_debug_separation_self",
 ]
 
 OPT_MAX_BOUNCES, OPT_WHITE_FURNACE, OPT_SAMPLER, OPT_AOV, OPT_DENOISER, OPT_DROP_LAST, OPT_PROFILE, OPT_TRACE_VARIANT, OPT_TRACE_WAVES, OPT_SAMPLES_IN_FLIGHT, OPT_SELECT_FORM_BOX, OPT_PACKET_BOUNCES, OPT_TRACE_TUNE, OPT_DEBUG_ALLOC_LIMIT, OPT_PATH_STATE_LIMIT_MB, OPT_PIPELINES, OPT_SHADE_PARTITION, OPT_OVERLAP_SHADOW, OPT_SMALL_LAUNCH_PATHS, OPT_COMPACT_LOG, OPT_DEBUG_LOG_POOL_DIV, OPT_TRACE_TAIL_LANES, OPT_TRACE_TAIL_PATHS, OPT_CHUNK_REFILL, OPT_STAGE_PIPES, OPT_FRAME_KERNEL, OPT_SAMPLES_AHEAD = range(27)
@@ -232,6 +234,11 @@ def load():
         "rt_debug_cross": (i32, [vp, vp, u32, vp, u32, u32, u32, vp, vp]),
         "rt_debug_cross_walk": (i32, [vp, u32, vp, u32, i32, vp, u32, u32, u32, vp, vp, vp]),
         "rt_debug_cross_self": (i32, [vp, vp, u32, vp, u32, u32, u32, u32, vp, vp]),
+        "rt_scene_separation": (i32, [vp, vp, u32, C.c_float, u32, vp]), "rt_scene_separation_buffer": (i32, [vp, vp, u32, C.c_float, u32, vp]),
+        "rt_scene_separation_self": (i32, [vp, u32, u32, C.c_float, u32, vp]), "rt_scene_separation_self_buffer": (i32, [vp, u32, u32, C.c_float, u32, vp]),
+        "rt_debug_separation": (i32, [vp, vp, u32, vp, u32, C.c_float, vp]),
+        "rt_debug_separation_walk": (i32, [vp, u32, vp, u32, i32, vp, u32, C.c_float, vp, vp]),
+        "rt_debug_separation_self": (i32, [vp, vp, u32, vp, u32, u32, C.c_float, u32, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -728,6 +735,54 @@ def debug_cross_self(ctx, triangles, first=0, n=None, max_list=CROSS_LIST_MAX, o
     return out if members is None else (out, members)
 
 
+SEPARATION_OTHER_OBJECTS = 2     # RT_SEPARATION_OTHER_OBJECTS: options bit 1 (self forms), pairs of one object are skipped
+SEPARATION_SEARCHED = 1          # rt_separation.flags bit 0
+SEPARATION_FOUND = 2             # rt_separation.flags bit 1
+SEPARATION_CROSSING = 4          # rt_separation.flags bit 2
+SEPARATION_FEATURE_CROSSING = 15
+
+
+def debug_separation(ctx, triangles, probes, max_distance=float("inf")):
+    """rt_debug_separation: types.separation[n] of `probes` (probe_records' rule) by brute force over all `triangles` (types.triangle): the nearest triangle
+    within max_distance, the two closest points and their distance.  ctx None = the host (csrc/separation.h), else k_separation_brute on ctx's GPU."""
+    lib = load()
+    tris = np.ascontiguousarray(triangles, T.triangle)
+    pr = probe_records(probes)
+    out = np.zeros(len(pr), T.separation)
+    handle = ctx.handle if ctx is not None else None
+    if lib.rt_debug_separation(handle, _p(tris), len(tris), _p(pr), len(pr), max_distance, _p(out)) != 0:
+        raise RtError(lib.rt_last_error(handle).decode())
+    return out
+
+
+def debug_separation_walk(nodes, triangles, probes, max_distance=float("inf"), wide=True, counts=False):
+    """rt_debug_separation_walk (host only): k_separation's walk over the child-pair form of `nodes` (types.bvh_node; wide=False) or over build_wide_bvh's
+    4-wide records of them (wide=True): debug_separation's result, with uint32[n] triangles tested per probe when counts=True"""
+    lib = load()
+    nd = np.ascontiguousarray(nodes, T.bvh_node)
+    tris = np.ascontiguousarray(triangles, T.triangle)
+    pr = probe_records(probes)
+    out = np.zeros(len(pr), T.separation)
+    tested = np.zeros(len(pr), np.uint32)
+    if lib.rt_debug_separation_walk(_p(nd), len(nd), _p(tris), len(tris), int(wide), _p(pr), len(pr), max_distance, _p(out), _p(tested)) != 0:
+        raise RtError(lib.rt_last_error(None).decode())
+    return (out, tested) if counts else out
+
+
+def debug_separation_self(ctx, triangles, first=0, n=None, max_distance=float("inf"), options=0, object_of_triangle=None):
+    """rt_debug_separation_self: debug_separation's result where probe i is triangles[first + i] (n None: to the end); pairs of one index or of a shared
+    corner are skipped, and with SEPARATION_OTHER_OBJECTS pairs of one object (object_of_triangle uint32[nt]).  ctx None = the host, else the GPU."""
+    lib = load()
+    tris = np.ascontiguousarray(triangles, T.triangle)
+    n = len(tris) - first if n is None else n
+    ids = np.ascontiguousarray(object_of_triangle, np.uint32) if object_of_triangle is not None else None
+    out = np.zeros(n, T.separation)
+    handle = ctx.handle if ctx is not None else None
+    if lib.rt_debug_separation_self(handle, _p(tris), len(tris), _p(ids), first, n, max_distance, options, _p(out)) != 0:
+        raise RtError(lib.rt_last_error(handle).decode())
+    return out
+
+
 def choose_tree(scene, shadow=True, mode=1):
     """rt_debug_choose_tree (host only, no GPU): the 4-wide tree rt_scene_upload would give this scene's shadow / closest-hit
     rays under RT_CTX_OPT_SHADOW_TREE / RT_CTX_OPT_CLOSEST_TREE = mode.  scene: dict with triangles, nodes, lights.
@@ -1108,6 +1163,30 @@ class Context:
         """rt_scene_cross_self_buffer: the same into Buffers of this context.  Only enqueues."""
         h = lambda b: b.handle if b is not None else None
         _check(self.lib, self.handle, self.lib.rt_scene_cross_self_buffer(self.handle, first, n, max_list, options, h(out), h(members)))
+
+    def separation(self, probes, max_distance=float("inf"), options=0):
+        """rt_scene_separation: types.separation[n] -- per caller's triangle (probe_records' rule) the nearest triangle of the uploaded scene within
+        max_distance, the two closest points, their distance (0 and SEPARATION_CROSSING where the two cross).  Bit for bit debug_separation's brute force."""
+        pr = probe_records(probes)
+        out = np.zeros(len(pr), T.separation)
+        _check(self.lib, self.handle, self.lib.rt_scene_separation(self.handle, _p(pr), len(pr), max_distance, options, _p(out)))
+        return out
+
+    def separation_buffer(self, probes, n, max_distance, options, out):
+        """rt_scene_separation_buffer: the same over Buffers of this context (n probes, n records).  Only enqueues."""
+        h = lambda b: b.handle if b is not None else None
+        _check(self.lib, self.handle, self.lib.rt_scene_separation_buffer(self.handle, h(probes), n, max_distance, options, h(out)))
+
+    def separation_self(self, first, n, max_distance=float("inf"), options=0):
+        """rt_scene_separation_self: Context.separation's result where probe i is scene triangle first + i; pairs of one index or of a shared corner are
+        skipped, and with SEPARATION_OTHER_OBJECTS (needs set_objects) pairs of one object"""
+        out = np.zeros(n, T.separation)
+        _check(self.lib, self.handle, self.lib.rt_scene_separation_self(self.handle, first, n, max_distance, options, _p(out)))
+        return out
+
+    def separation_self_buffer(self, first, n, max_distance, options, out):
+        """rt_scene_separation_self_buffer: the same into a Buffer of this context.  Only enqueues."""
+        _check(self.lib, self.handle, self.lib.rt_scene_separation_self_buffer(self.handle, first, n, max_distance, options, out.handle if out is not None else None))
 
     def select(self, regions, objects=0):
         """rt_scene_select: at most 32 regions against every triangle: (touching uint32[num_triangles], inside uint32[num_triangles]), bit r for

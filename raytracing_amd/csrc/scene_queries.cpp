@@ -1,6 +1,6 @@
-// scene_queries.cpp -- the C entry points of the seven query families on an uploaded scene, the bookkeeping around the kernels and launch drivers of
-// query.hip, bake.hip, nearest.hip, all_hits.hip, within.hip, region.hip and cross.hip (DESIGN.md sections 7h - 7n): rt_scene_trace*, rt_scene_bake*,
-// rt_scene_nearest*, rt_scene_trace_all*, rt_scene_within*, rt_scene_overlap*, rt_scene_select*, rt_scene_cross* and their rt_debug_* forms.  Host code only, on context.h:
+// scene_queries.cpp -- the C entry points of the eight query families on an uploaded scene, the bookkeeping around the kernels and launch drivers of
+// query.hip, bake.hip, nearest.hip, all_hits.hip, within.hip, region.hip, cross.hip and separation.hip (DESIGN.md sections 7h - 7o): rt_scene_trace*, rt_scene_bake*,
+// rt_scene_nearest*, rt_scene_trace_all*, rt_scene_within*, rt_scene_overlap*, rt_scene_select*, rt_scene_cross*, rt_scene_separation* and their rt_debug_* forms.  Host code only, on context.h:
 // a query reads the scene and writes the caller's arrays, it launches on the context's stream -- behind every refit, pose and upload, which end there --
 // and touches no frame.  (The three picks read a frame's camera and tile: they are rt_hip.hip's and call the entries here.)  The stack spill area, the
 // status word and the staging arrays of every family but the bakes are the ray queries' (ctx->query), so rt_scene_tree_report's "ray queries" line
@@ -20,6 +20,8 @@
 #include "region_host.h"
 #include "cross_host.h"
 #include "cross.h"
+#include "separation_host.h"
+#include "separation.h"
 #include "device_memory.h"
 using namespace context;
 
@@ -677,6 +679,109 @@ int rt_debug_cross_self(rt_ctx* ctx, const rt_triangle* triangles, uint32_t num_
     return host_or_device(ctx, "rt_debug_cross_self",
         [&] { cross::brute_host(triangles, num_triangles, nullptr, object_of_triangle, first, n, max_list, options, out, members); },
         [&](hipStream_t st) { return cross::brute_device(st, triangles, num_triangles, nullptr, object_of_triangle, first, n, max_list, options, out, members); });
+}
+
+// ---- the nearest scene triangle to a caller's triangle, and a scene's clearances: rt_scene_separation / rt_scene_separation_buffer /
+// rt_scene_separation_self / rt_scene_separation_self_buffer / rt_debug_separation / rt_debug_separation_walk / rt_debug_separation_self (separation.hip,
+// DESIGN.md section 7o) ---------------------------------------------------------------------------------------------------------------------------------
+
+// everything the four scene forms refuse before anything is launched; self: probes are the scene's triangles first .. first + n - 1
+static int separation_refused(rt_ctx* ctx, const char* who, bool self, bool probes, uint32_t first, uint32_t n, uint32_t options, bool out)
+{
+    const std::string name(who);
+    if (opening_refused(ctx, name, {}, {{"probes", self || probes || n == 0u}, {"out", out}}) != RT_OK) return RT_ERROR;
+    if (const char* why = sep_shape_refused(options, self)) return fail(ctx, name + ": " + why);
+    if (self && (uint64_t)first + n > ctx->scene.n_tris) return fail(ctx, name + ": first + n is beyond the scene's triangles");
+    if ((options & RT_SEPARATION_OTHER_OBJECTS) && !ctx->scene.pose) return fail(ctx, name + ": RT_SEPARATION_OTHER_OBJECTS needs rt_scene_set_objects");
+    return RT_OK;
+}
+
+static int separation_launch(rt_ctx* ctx, const char* who, const rt_probe* d_probes, uint32_t n, float max_distance, rt_separation* d_out)
+{
+    const Scene& s = ctx->scene;
+    return launch_result(ctx, who, separation::launch(ctx->stream, ctx->query, s.d, s.wide_ok, ctx->prop.multiProcessorCount, d_probes, n, max_distance, d_out),
+        QUERY_NOT_LAUNCHED);
+}
+
+static int separation_self_launch(rt_ctx* ctx, const char* who, uint32_t first, uint32_t n, float max_distance, uint32_t options, rt_separation* d_out)
+{
+    const Scene& s = ctx->scene;
+    return launch_result(ctx, who, separation::launch_self(ctx->stream, ctx->query, s.d, s.wide_ok, ctx->prop.multiProcessorCount, s.pose ? s.pose->ids : nullptr, first, n,
+        max_distance, options, d_out), QUERY_NOT_LAUNCHED);
+}
+
+int rt_scene_separation(rt_ctx* ctx, const rt_probe* probes, uint32_t n, float max_distance, uint32_t options, rt_separation* out)
+{
+    if (ctx && n == 0u) return RT_OK;
+    if (separation_refused(ctx, "rt_scene_separation", false, probes != nullptr, 0u, n, options, out != nullptr) != RT_OK) return RT_ERROR;
+    (void)hipSetDevice(ctx->device);
+    query::Scratch& q = ctx->query;
+    // the ray queries' staging arrays: [0] the probes, [2] the records
+    return staged_call(ctx, "rt_scene_separation", q, {{(void*)probes, sizeof(rt_probe), 0, true}, {out, sizeof(rt_separation), 2, false}}, n, (uint32_t)query::CHUNK_RAYS,
+        [&](uint32_t, uint32_t m) { return separation_launch(ctx, "rt_scene_separation", (const rt_probe*)q.stage[0], m, max_distance, (rt_separation*)q.stage[2]); });
+}
+
+int rt_scene_separation_buffer(rt_ctx* ctx, rt_buffer* probes, uint32_t n, float max_distance, uint32_t options, rt_buffer* out)
+{
+    if (ctx && n == 0u) return RT_OK;
+    if (separation_refused(ctx, "rt_scene_separation_buffer", false, probes != nullptr, 0u, n, options, out != nullptr) != RT_OK) return RT_ERROR;
+    if (buffers_refused(ctx, "rt_scene_separation_buffer", {{probes, sizeof(rt_probe), "probes"}, {out, sizeof(rt_separation), "out"}}, n) != RT_OK) return RT_ERROR;
+    (void)hipSetDevice(ctx->device);
+    return separation_launch(ctx, "rt_scene_separation_buffer", (const rt_probe*)probes->ptr, n, max_distance, (rt_separation*)out->ptr);
+}
+
+int rt_scene_separation_self(rt_ctx* ctx, uint32_t first, uint32_t n, float max_distance, uint32_t options, rt_separation* out)
+{
+    if (ctx && n == 0u) return RT_OK;
+    if (separation_refused(ctx, "rt_scene_separation_self", true, true, first, n, options, out != nullptr) != RT_OK) return RT_ERROR;
+    (void)hipSetDevice(ctx->device);
+    query::Scratch& q = ctx->query;
+    // the ray queries' staging arrays: [2] the records; nothing goes up
+    return staged_call(ctx, "rt_scene_separation_self", q, {{out, sizeof(rt_separation), 2, false}}, n, (uint32_t)query::CHUNK_RAYS, [&](uint32_t done, uint32_t m)
+        {
+            return separation_self_launch(ctx, "rt_scene_separation_self", first + done, m, max_distance, options, (rt_separation*)q.stage[2]);
+        });
+}
+
+int rt_scene_separation_self_buffer(rt_ctx* ctx, uint32_t first, uint32_t n, float max_distance, uint32_t options, rt_buffer* out)
+{
+    if (ctx && n == 0u) return RT_OK;
+    if (separation_refused(ctx, "rt_scene_separation_self_buffer", true, true, first, n, options, out != nullptr) != RT_OK) return RT_ERROR;
+    if (buffers_refused(ctx, "rt_scene_separation_self_buffer", {{out, sizeof(rt_separation), "out"}}, n) != RT_OK) return RT_ERROR;
+    (void)hipSetDevice(ctx->device);
+    return separation_self_launch(ctx, "rt_scene_separation_self_buffer", first, n, max_distance, options, (rt_separation*)out->ptr);
+}
+
+int rt_debug_separation(rt_ctx* ctx, const rt_triangle* triangles, uint32_t num_triangles, const rt_probe* probes, uint32_t n, float max_distance, rt_separation* out)
+{
+    if (n == 0u) return RT_OK;
+    if (!probes || !out || (!triangles && num_triangles > 0u)) return fail(ctx, "rt_debug_separation: NULL argument");
+    return host_or_device(ctx, "rt_debug_separation", [&] { separation::brute_host(triangles, num_triangles, probes, nullptr, 0u, n, max_distance, 0u, out); },
+        [&](hipStream_t st) { return separation::brute_device(st, triangles, num_triangles, probes, nullptr, 0u, n, max_distance, 0u, out); });
+}
+
+int rt_debug_separation_walk(const rt_bvh_node* nodes, uint32_t num_nodes, const rt_triangle* triangles, uint32_t num_triangles, int wide, const rt_probe* probes,
+    uint32_t n, float max_distance, rt_separation* out, uint32_t* triangles_tested)
+{
+    if (n == 0u) return RT_OK;
+    if (!nodes || num_nodes == 0u || !triangles || !probes || !out) return fail(nullptr, "rt_debug_separation_walk: NULL argument");
+    if (wide != 0 && wide != 1) return fail(nullptr, std::string("rt_debug_separation_walk") + WIDE_REFUSED);
+    if (const char* why = separation::walk_host(nodes, num_nodes, triangles, num_triangles, wide != 0, probes, n, max_distance, out, triangles_tested))
+        return fail(nullptr, std::string("rt_debug_separation_walk: ") + why);
+    return RT_OK;
+}
+
+int rt_debug_separation_self(rt_ctx* ctx, const rt_triangle* triangles, uint32_t num_triangles, const uint32_t* object_of_triangle, uint32_t first, uint32_t n,
+    float max_distance, uint32_t options, rt_separation* out)
+{
+    if (n == 0u) return RT_OK;
+    if (const char* why = sep_shape_refused(options, true)) return fail(ctx, std::string("rt_debug_separation_self: ") + why);
+    if (!triangles || !out) return fail(ctx, "rt_debug_separation_self: NULL argument");
+    if ((uint64_t)first + n > num_triangles) return fail(ctx, "rt_debug_separation_self: first + n is beyond the triangles");
+    if ((options & RT_SEPARATION_OTHER_OBJECTS) && !object_of_triangle) return fail(ctx, "rt_debug_separation_self: RT_SEPARATION_OTHER_OBJECTS needs object_of_triangle");
+    return host_or_device(ctx, "rt_debug_separation_self",
+        [&] { separation::brute_host(triangles, num_triangles, nullptr, object_of_triangle, first, n, max_distance, options, out); },
+        [&](hipStream_t st) { return separation::brute_device(st, triangles, num_triangles, nullptr, object_of_triangle, first, n, max_distance, options, out); });
 }
 
 } // extern "C"

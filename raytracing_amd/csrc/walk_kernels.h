@@ -10,6 +10,8 @@
 //   point_box_step one pass of a point's walk (nearest, within) at a box record: the slots keyed by nearest_box_d2, nearest first
 //   region_box_step one pass of a region's walk (overlap) at a box record: every slot region.h's box test passes is visited, in no particular order
 //   cross_box_step  one pass of a probe's walk (cross, cross_kernels.h) at a box record: the probe's closed box and the two half-spaces of its plane
+//   probe_box_step  one pass of a probe's nearest-first walk (separation, separation_kernels.h) at a box record: point_box_step's ordering, keyed by the
+//                  caller's box-to-box bound
 //   point_surface, ray_surface   the rt_surface of one found record (a nearest point, a hit): the body of the four surface kernels
 //   ray_step       one pass of a ray's fused loop: the fetch of one 64-byte record and its leaf, child-pair or 4-wide step; what an accepted triangle does
 //                  to the walk is the step's mode (closest, any hit, all hits)
@@ -399,6 +401,46 @@ RT_DEV void cross_box_step(const float4 q0, const float4 q1, const float4 q2, co
         }
     if (next != RT_IDLE_REF) ref = next;
     else ref = stack.pop([](float) { return true; });
+}
+
+// One pass of a probe's nearest-first walk (separation, separation_kernels.h) at a box record: point_box_step's ordering with the box-to-box bound
+// key(lo, hi) = sep_box_d2(the probe's box, the slot's box) (separation.h) as the key -- the slots that pass !(key > best) ascending by key, the nearest
+// visited next, the others pushed with their bound, farthest deepest; none: a pop that re-tests !(entry > best).  The probe's 6 box floats are registers.
+template <bool WIDE, class Key>
+RT_DEV void probe_box_step(const float4 q0, const float4 q1, const float4 q2, const float4 q3, Key&& key_of, const float best, uint32_t& ref, Stack& stack)
+{
+    constexpr int N = WIDE ? 4 : 2;
+    const float INF = __builtin_inff();
+    uint32_t rn[N], r[4] = {RT_EMPTY_REF, RT_EMPTY_REF, RT_EMPTY_REF, RT_EMPTY_REF};
+    float lo[N][3], hi[N][3], e[4] = {INF, INF, INF, INF};
+    decode_slots<WIDE>(q0, q1, q2, q3, rn, lo, hi);
+#pragma unroll
+    for (int k = 0; k < N; ++k)
+    {
+        const float key = key_of(lo[k], hi[k]);
+        const bool pass = rn[k] != RT_EMPTY_REF && !(key > best);
+        r[k] = pass ? rn[k] : RT_EMPTY_REF;
+        e[k] = pass ? key : INF;
+    }
+    auto exchange = [&](int a, int b)
+    {
+        const bool s = e[b] < e[a];
+        const float te = s ? e[b] : e[a]; e[b] = s ? e[a] : e[b]; e[a] = te;
+        const uint32_t tr = s ? r[b] : r[a]; r[b] = s ? r[a] : r[b]; r[a] = tr;
+    };
+    exchange(0, 1);
+    if (WIDE) { exchange(2, 3); exchange(0, 2); exchange(1, 3); exchange(1, 2); }
+    uint32_t next = RT_IDLE_REF;
+    float next_e = 0.0f;
+#pragma unroll
+    for (int k = WIDE ? 3 : 1; k >= 0; --k)
+        if (r[k] != RT_EMPTY_REF)
+        {
+            if (next != RT_IDLE_REF) stack.push(next, next_e);
+            next = r[k]; next_e = e[k];
+        }
+    if (next != RT_IDLE_REF) ref = next;
+    else ref = stack.pop([&](float entry) { return !(entry > best); });
 }
 
 // a triangle's 128-byte shading record (p1 uv1.x | p2 uv1.y | p3 uv2.x | n1 uv2.y | n2 uv3.x | n3 uv3.y | mtl_index ...) as query_surface reads it

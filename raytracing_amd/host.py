@@ -26,7 +26,7 @@ EXPORTS = [
     "rth_render_upload_gpu_data", "rth_render_setup_seconds", "rth_render_create_with_options",
     "rth_render_set_refittable", "rth_render_refit", "rth_render_set_refit_motion",
     "rth_render_set_objects", "rth_render_pose", "rth_render_pick", "rth_render_integrator_pick", "rth_render_trace",
-    "rth_render_bake", "rth_render_occlusion_image", "rth_render_nearest", "rth_render_within", "rth_render_overlap", "rth_render_cross", "rth_render_self_cross", "rth_render_select", "rth_render_pick_rect", "rth_render_integrator_pick_rect", "rth_render_trace_all", "rth_render_pick_all",
+    "rth_render_bake", "rth_render_occlusion_image", "rth_render_nearest", "rth_render_within", "rth_render_overlap", "rth_render_cross", "rth_render_self_cross", "rth_render_separation", "rth_render_clearance", "rth_render_select", "rth_render_pick_rect", "rth_render_integrator_pick_rect", "rth_render_trace_all", "rth_render_pick_all",
     "rth_scene_set_triangle_objects", "rth_scene_num_objects", "rth_scene_object_name", "rth_scene_num_triangle_objects", "rth_scene_triangle_objects",
 ]
 
@@ -79,6 +79,7 @@ def load():
         "rth_render_nearest": (i32, [vp, vp, u32, vp, vp]),
         "rth_render_within": (i32, [vp, vp, u32, u32, u32, vp, vp, vp]),
         "rth_render_overlap": (i32, [vp, vp, u32, u32, vp, vp]),
+        "rth_render_separation": (i32, [vp, vp, u32, C.c_float, vp]), "rth_render_clearance": (i32, [vp, u32, u32, C.c_float, vp]),
         "rth_render_cross": (i32, [vp, vp, u32, u32, u32, vp, vp]), "rth_render_self_cross": (i32, [vp, u32, u32, u32, u32, vp, vp]), "rth_render_select": (i32, [vp, vp, u32, vp, vp, vp, vp]),
         "rth_render_pick_rect": (i32, [vp, u32, u32, u32, u32, C.c_float, C.c_float, vp, vp, vp, vp, vp]),
         "rth_render_integrator_pick_rect": (i32, [vp, u32, u32, u32, u32, C.c_float, C.c_float, vp, vp, vp]),
@@ -256,6 +257,39 @@ class Scene:
             self.close()
         except Exception:
             pass
+
+
+def reduce_clearances(records, objects, names):
+    """One entry per object from the self form's records (types.separation, record i = triangle i against the triangles of the other objects; objects: the
+    object of every triangle): {name: None when nothing was found, else {"other": the nearest other object's name, "distance", "crossing", "on_self",
+    "on_other", "triangle", "other_triangle"}}.  The reduction is per ordered pair of objects first: (A, B) keeps, of A's triangles whose record names a
+    triangle of B, the one of least distance, among equal distances the lowest (triangle, other triangle).  The rule's edge-pair routine is not symmetric,
+    so (A, B) and (B, A) may differ in the last bit: where both are present the pair's distance is the smaller of the two, and when that is (B, A)'s, A
+    reports that record seen from its side (points and triangles exchanged).  An object's entry is its pair of least distance, among equal distances the
+    lowest (triangle, other triangle) as the entry reports them."""
+    from . import capi
+    best = {}                                                             # (object, other object) -> (key, record index)
+    for i in np.flatnonzero(records["flags"] & capi.SEPARATION_FOUND):
+        r = records[i]
+        pair = (int(objects[i]), int(objects[r["primitive_id"]]))
+        key = (float(r["distance"]), int(i), int(r["primitive_id"]))
+        if pair not in best or key < best[pair][0]:
+            best[pair] = (key, int(i))
+    entries = {}
+    for (o, p), (key, i) in best.items():
+        back = best.get((p, o))
+        mine = back is None or not back[0][0] < key[0]
+        r = records[i if mine else back[1]]
+        t, u = (int(i), int(r["primitive_id"])) if mine else (int(r["primitive_id"]), back[1])
+        e = {"other": p, "distance": float(r["distance"]), "crossing": bool(r["flags"] & capi.SEPARATION_CROSSING),
+             "on_self": (r["on_probe"] if mine else r["on_scene"]).copy(), "on_other": (r["on_scene"] if mine else r["on_probe"]).copy(), "triangle": t, "other_triangle": u}
+        if o not in entries or (e["distance"], t, u) < (entries[o]["distance"], entries[o]["triangle"], entries[o]["other_triangle"]):
+            entries[o] = e
+    result = {}
+    for o, name in enumerate(names):
+        e = entries.get(o)
+        result[name] = None if e is None else dict(e, other=names[e["other"]])
+    return result
 
 
 class Render:
@@ -573,6 +607,39 @@ class Render:
             for m in got["members"]:
                 pairs.add(tuple(sorted((names[objects[i]], m["object_name"]))))
         return {"pairs": pairs, "complete": complete}
+
+    def separation(self, probes, max_distance=float("inf")):
+        """The nearest triangle of the scene as it is posed now to each of the caller's triangles (Render::Separation; probes: capi.probe_records' rule): one
+        dict per probe -- `searched`, `found`, `crossing`, `distance`, `on_probe` and `on_scene` (the two closest points), `primitive_id`, `feature` (0..2 a
+        probe corner, 3..5 a corner of the triangle, 6 + 3 i + j an edge pair, 15 a crossing) and, when the scene was loaded with objects, `object_name`"""
+        from . import capi
+        pr = capi.probe_records(probes)
+        n = len(pr)
+        out = np.zeros(n, T.separation)
+        self._c(self.lib.rth_render_separation(self.handle, pr.ctypes.data if n else None, n, max_distance, out.ctypes.data if n else None))
+        names = self.scene.object_names()
+        objects = self.scene.triangle_objects() if names else None
+        result = []
+        for r in out:
+            found = bool(r["flags"] & capi.SEPARATION_FOUND)
+            d = {"searched": bool(r["flags"] & capi.SEPARATION_SEARCHED), "found": found, "crossing": bool(r["flags"] & capi.SEPARATION_CROSSING),
+                 "distance": float(r["distance"]), "on_probe": r["on_probe"].copy(), "on_scene": r["on_scene"].copy(), "primitive_id": int(r["primitive_id"]),
+                 "feature": int(r["feature"])}
+            if names and found:
+                d["object_name"] = names[objects[d["primitive_id"]]]
+            result.append(d)
+        return result
+
+    def clearances(self, max_distance=float("inf")):
+        """How much room is left between the objects of the scene as it is posed now (the scene loaded with objects, after set_objects): the self form with
+        RT_SEPARATION_OTHER_OBJECTS over all triangles (Render::Clearance), reduced by reduce_clearances to one entry per object"""
+        names = self.scene.object_names()
+        if not names:
+            raise RtError("clearances: the scene was not loaded with objects")
+        nt = self.lib.rth_scene_num_triangles(self.scene.handle)
+        out = np.zeros(nt, T.separation)
+        self._c(self.lib.rth_render_clearance(self.handle, 0, nt, max_distance, out.ctypes.data))
+        return reduce_clearances(out, self.scene.triangle_objects(), names)
 
     def select(self, regions):
         """At most 32 regions against every triangle of the scene as it is posed now (Render::Select): one dict per region -- `touching` and `inside`, the

@@ -202,6 +202,18 @@ void HIPPathTraceIntegrator::SelfCross(std::uint32_t first, std::size_t count, s
     Check(rt_scene_cross_self(context_.Get(), first, (uint32_t)count, max_list, options, out, members));
 }
 
+void HIPPathTraceIntegrator::TrianglesSeparation(rt_probe const* probes, std::size_t count, float max_distance, rt_separation* out)
+{
+    if (count > 0xFFFFFFFFull) throw HIPException("HIPPathTraceIntegrator::TrianglesSeparation: more than 2^32 - 1 probes in one call");
+    Check(rt_scene_separation(context_.Get(), probes, (uint32_t)count, max_distance, 0u, out));
+}
+
+void HIPPathTraceIntegrator::SelfSeparation(std::uint32_t first, std::size_t count, float max_distance, std::uint32_t options, rt_separation* out)
+{
+    if (count > 0xFFFFFFFFull) throw HIPException("HIPPathTraceIntegrator::SelfSeparation: more than 2^32 - 1 probes in one call");
+    Check(rt_scene_separation_self(context_.Get(), first, (uint32_t)count, max_distance, options, out));
+}
+
 void HIPPathTraceIntegrator::RegionsOverlap(rt_region const* regions, std::size_t count, std::uint32_t max_list, rt_region_hits* out, rt_region_member* members)
 {
     if (count > 0xFFFFFFFFull) throw HIPException("HIPPathTraceIntegrator::RegionsOverlap: more than 2^32 - 1 regions in one call");

@@ -144,6 +144,12 @@ public:
     // touches the frame.
     void TrianglesCross(rt_probe const* probes, std::size_t count, std::uint32_t max_list, std::uint32_t options, rt_probe_hits* out, rt_cross_member* members);
     void SelfCross(std::uint32_t first, std::size_t count, std::uint32_t max_list, std::uint32_t options, rt_probe_hits* out, rt_cross_member* members);
+    // Separation (rt_scene_separation / rt_scene_separation_self): TrianglesSeparation -- per caller-supplied triangle the nearest scene
+    // triangle within max_distance, the two closest points and their distance (0 and RT_SEPARATION_CROSSING where the two cross); SelfSeparation -- the same
+    // where probe i is scene triangle first + i, neighbours that share a corner skipped (RT_SEPARATION_OTHER_OBJECTS: pairs of one object too, after
+    // SetObjects).  Both throw HIPException with the library's message on a refusal; neither requests a reset or touches the frame.
+    void TrianglesSeparation(rt_probe const* probes, std::size_t count, float max_distance, rt_separation* out);
+    void SelfSeparation(std::uint32_t first, std::size_t count, float max_distance, std::uint32_t options, rt_separation* out);
     // All hits (rt_scene_trace_all / rt_frame_pick_all): every surface each ray crosses -- the counts in out, the nearest max_hits crossings
     // in hits and surfaces (max_hits records per ray; either may be null).  PickAll: the ray through the centre of pixel (x, y) of the frame's current camera;
     // PickAllThrough: the same for a camera the frame has not been given, as PickThrough.  All throw HIPException with the library's message on a refusal; none

@@ -298,6 +298,14 @@ int rth_render_self_cross(void* r, uint32_t first, uint32_t n, uint32_t max_list
 {
     return guard([&]() { ((rt::Render*)r)->SelfCross(first, n, max_list, options, out, members); return 0; }, 1);
 }
+int rth_render_separation(void* r, const rt_probe* probes, uint32_t n, float max_distance, rt_separation* out)
+{
+    return guard([&]() { ((rt::Render*)r)->Separation(probes, n, max_distance, out); return 0; }, 1);
+}
+int rth_render_clearance(void* r, uint32_t first, uint32_t n, float max_distance, rt_separation* out)
+{
+    return guard([&]() { ((rt::Render*)r)->Clearance(first, n, max_distance, out); return 0; }, 1);
+}
 int rth_render_overlap(void* r, const rt_region* regions, uint32_t n, uint32_t max_list, rt_region_hits* out, rt_region_member* members)
 {
     return guard([&]() { ((rt::Render*)r)->Overlap(regions, n, max_list, out, members); return 0; }, 1);

@@ -9,6 +9,7 @@
 #include <cstring>
 #include <iostream>
 #include <limits>
+#include <map>
 #include <string>
 #include "render.hpp"
 
@@ -50,6 +51,9 @@ int main(int argc, char** argv)
         struct OverlapAt { float lo[3], hi[3]; std::uint32_t k; };
         struct CrossAt { rt_probe probe; std::uint32_t k; };
         std::vector<CrossAt> cross_probes;      // --cross x1,y1,z1,x2,y2,z2,x3,y3,z3[,k] (repeatable): after the scene is uploaded and posed, print the triangles that triangle crosses (the k lowest ids)
+        struct SeparationAt { rt_probe probe; float r; };
+        std::vector<SeparationAt> separation_probes;   // --separation x1,y1,z1,x2,y2,z2,x3,y3,z3[,r] (repeatable): after the scene is uploaded and posed, print the nearest triangle to that triangle (within r), the distance and the two closest points
+        bool clearance = false;                 // --clearance 1: print, per object, the nearest other object, the distance and the two closest points
         bool self_cross = false;                // --self_cross 1: print which triangles of the scene cross each other, neighbours that share a corner aside
         std::vector<OverlapAt> overlap_boxes;   // --overlap lx,ly,lz,hx,hy,hz[,k] (repeatable): after the scene is uploaded and posed, print the triangles the box touches (the k lowest ids)
         struct RectAt { std::uint32_t x0, y0, x1, y1; bool window; };
@@ -184,6 +188,21 @@ int main(int argc, char** argv)
                 cross_probes.push_back(q);
                 scene_options |= rt::Scene::kObjects;
             }
+            else if (!strcmp(argv[i], "--separation"))
+            {
+                SeparationAt q = {};
+                q.r = std::numeric_limits<float>::infinity();
+                float* p[3] = {q.probe.p1, q.probe.p2, q.probe.p3};
+                const int got = sscanf(next(), "%f,%f,%f,%f,%f,%f,%f,%f,%f,%f", &p[0][0], &p[0][1], &p[0][2], &p[1][0], &p[1][1], &p[1][2], &p[2][0], &p[2][1], &p[2][2], &q.r);
+                if (got < 9 || !(q.r >= 0.0f))
+                {
+                    std::cerr << "--separation wants x1,y1,z1,x2,y2,z2,x3,y3,z3 or the same followed by ,r (a triangle's corners and optionally the largest distance searched, >= 0)\n";
+                    return 2;
+                }
+                separation_probes.push_back(q);
+                scene_options |= rt::Scene::kObjects;
+            }
+            else if (!strcmp(argv[i], "--clearance")) { if (atoi(next()) != 0) { clearance = true; scene_options |= rt::Scene::kObjects; } }
             else if (!strcmp(argv[i], "--self_cross")) { if (atoi(next()) != 0) { self_cross = true; scene_options |= rt::Scene::kObjects; } }
             else if (!strcmp(argv[i], "--overlap"))
             {
@@ -248,6 +267,9 @@ int main(int argc, char** argv)
                              "  --cross x1,y1,z1,x2,y2,z2,x3,y3,z3[,k] (repeatable) prints the triangles that triangle crosses once the scene is uploaded and posed: how many, and\n"
                              "  one line for each of the k (default 8) lowest primitive ids with the two contact points; --self_cross 1 prints how many of the scene's own\n"
                              "  triangles cross another one (neighbours that share a corner aside) and the pairs of objects among them; one GPU only\n"
+                             "  --separation x1,y1,z1,x2,y2,z2,x3,y3,z3[,r] (repeatable) prints the nearest triangle to that triangle (within r, default any distance) once the\n"
+                             "  scene is uploaded and posed: the distance, the two closest points, the winning feature and the object; --clearance 1 prints, per object, the\n"
+                             "  nearest other object, the distance, the two closest points and the two triangles; one GPU only\n"
                              "  --overlap lx,ly,lz,hx,hy,hz[,k] (repeatable) prints the triangles that axis-aligned box touches once the scene is uploaded and posed: how many,\n"
                              "  how many lie wholly inside, and one line for each of the k (default 8) lowest primitive ids; --pick_rect x0,y0,x1,y1[,window] (repeatable)\n"
                              "  prints what lies under that inclusive pixel rectangle: the primitives its region touches (window: wholly inside) and their objects; one GPU only\n"
@@ -314,6 +336,11 @@ int main(int argc, char** argv)
         if ((!cross_probes.empty() || self_cross) && (gpus > 1 || tiled_path))
         {
             std::cerr << "--cross and --self_cross need one GPU\n";
+            return 2;
+        }
+        if ((!separation_probes.empty() || clearance) && (gpus > 1 || tiled_path))
+        {
+            std::cerr << "--separation and --clearance need one GPU\n";
             return 2;
         }
         if ((!overlap_boxes.empty() || !pick_rects.empty()) && (gpus > 1 || tiled_path))
@@ -586,6 +613,72 @@ int main(int argc, char** argv)
                 }
             }
         };
+        // --separation: one line per probe (rt_scene_separation through Render::Separation); --clearance: rt_scene_separation_self with
+        // RT_SEPARATION_OTHER_OBJECTS over all triangles (Render::Clearance), reduced per ordered pair of objects as host.reduce_clearances reduces it
+        auto print_separations = [&](bool objects_set)
+        {
+            for (const SeparationAt& q : separation_probes)
+            {
+                rt_separation rec;
+                render.Separation(&q.probe, 1, q.r, &rec);
+                std::cout << "separation " << q.probe.p1[0] << "," << q.probe.p1[1] << "," << q.probe.p1[2] << " " << q.probe.p2[0] << "," << q.probe.p2[1] << "," << q.probe.p2[2] << " "
+                          << q.probe.p3[0] << "," << q.probe.p3[1] << "," << q.probe.p3[2] << ": ";
+                if (!(rec.flags & RT_SEPARATION_SEARCHED)) { std::cout << "not searched" << std::endl; continue; }
+                if (!(rec.flags & RT_SEPARATION_FOUND)) { std::cout << "none" << std::endl; continue; }
+                std::cout << "distance " << rec.distance << ((rec.flags & RT_SEPARATION_CROSSING) ? " crossing" : "") << " primitive " << rec.primitive_id << " feature " << rec.feature
+                          << " from " << rec.on_probe[0] << "," << rec.on_probe[1] << "," << rec.on_probe[2] << " to " << rec.on_scene[0] << "," << rec.on_scene[1] << "," << rec.on_scene[2]
+                          << " object ";
+                print_object(object_of(rec.primitive_id));
+                std::cout << std::endl;
+            }
+            if (clearance)
+            {
+                const std::size_t nt = scene.GetTriangles().size(), n_objects = scene.GetObjectNames().size();
+                if (!objects_set)                                              // rt_scene_set_objects wants a refittable upload: upload again, as the posing loop does
+                {
+                    render.GetIntegrator().SetRefittable(true);
+                    render.UploadGPUData();
+                }
+                if (!objects_set) render.SetObjects(scene.GetTriangleObjects().data(), scene.GetTriangleObjects().size(), (std::uint32_t)n_objects);
+                std::vector<rt_separation> recs(nt);
+                render.Clearance(0u, nt, std::numeric_limits<float>::infinity(), recs.data());
+                struct Key { float d; std::uint32_t t, u; bool operator<(const Key& o) const { return d < o.d || (d == o.d && (t < o.t || (t == o.t && u < o.u))); } };
+                std::map<std::pair<std::uint32_t, std::uint32_t>, Key> best;                    // (object, other object) -> its nearest record
+                for (std::size_t t = 0; t < nt; ++t)
+                {
+                    if (!(recs[t].flags & RT_SEPARATION_FOUND)) continue;
+                    const std::pair<std::uint32_t, std::uint32_t> pair(object_of((std::uint32_t)t), object_of(recs[t].primitive_id));
+                    const Key key = {recs[t].distance, (std::uint32_t)t, recs[t].primitive_id};
+                    auto it = best.find(pair);
+                    if (it == best.end() || key < it->second) best[pair] = key;
+                }
+                std::cout << "clearance: objects " << n_objects << " triangles " << nt << std::endl;
+                for (std::uint32_t o = 0; o < n_objects; ++o)
+                {
+                    bool have = false, have_mine = true;
+                    Key entry = {};
+                    std::uint32_t other = 0u, record = 0u;
+                    for (const auto& b : best)
+                    {
+                        if (b.first.first != o) continue;
+                        const auto back = best.find({b.first.second, o});
+                        const bool mine = back == best.end() || !(back->second.d < b.second.d);     // the smaller of the two directions
+                        const Key e = mine ? b.second : Key{back->second.d, back->second.u, back->second.t};
+                        if (!have || e < entry) { have = true; entry = e; other = b.first.second; record = mine ? e.t : e.u; have_mine = mine; }
+                    }
+                    std::cout << "clearance   ";
+                    print_object(o);
+                    std::cout << " | ";
+                    if (!have) { std::cout << "none" << std::endl; continue; }
+                    const rt_separation& r = recs[record];
+                    const float* from = have_mine ? r.on_probe : r.on_scene;
+                    const float* to = have_mine ? r.on_scene : r.on_probe;
+                    print_object(other);
+                    std::cout << " distance " << entry.d << ((r.flags & RT_SEPARATION_CROSSING) ? " crossing" : "") << " triangles " << entry.t << " " << entry.u << " from " << from[0] << ","
+                              << from[1] << "," << from[2] << " to " << to[0] << "," << to[1] << "," << to[2] << std::endl;
+                }
+            }
+        };
         // --pick_rect: one line per rectangle and one per object (rt_scene_select of the rectangle's region through Render::PickRect)
         auto print_pick_rects = [&]()
         {
@@ -675,6 +768,7 @@ int main(int argc, char** argv)
             print_within();
             print_overlaps();
             print_crosses();
+            print_separations(posing);
             print_pick_rects();
             write_ao();
             return 0;
@@ -720,6 +814,7 @@ int main(int argc, char** argv)
         print_within();
         print_overlaps();
         print_crosses();
+        print_separations(false);
         print_pick_rects();
         write_ao();
         if (!out.empty() && (filter_iterations >= 0 || temporal_iterations >= 0))

@@ -59,6 +59,10 @@ public:
     // every scene triangle a caller's triangle crosses, with contact points, and the scene's self-crossings
     void Cross(rt_probe const* probes, std::size_t count, std::uint32_t max_list, std::uint32_t options, rt_probe_hits* out, rt_cross_member* members) { integrator_->TrianglesCross(probes, count, max_list, options, out, members); }
     void SelfCross(std::uint32_t first, std::size_t count, std::uint32_t max_list, std::uint32_t options, rt_probe_hits* out, rt_cross_member* members) { integrator_->SelfCross(first, count, max_list, options, out, members); }
+    // the nearest scene triangle to a caller's triangle with the two closest points (Separation), and the same for every scene triangle against the triangles
+    // of the OTHER objects (Clearance: out[i] is triangle i's record; after SetObjects)
+    void Separation(rt_probe const* probes, std::size_t count, float max_distance, rt_separation* out) { integrator_->TrianglesSeparation(probes, count, max_distance, out); }
+    void Clearance(std::uint32_t first, std::size_t count, float max_distance, rt_separation* out) { integrator_->SelfSeparation(first, count, max_distance, RT_SEPARATION_OTHER_OBJECTS, out); }
     void Overlap(rt_region const* regions, std::size_t count, std::uint32_t max_list, rt_region_hits* out, rt_region_member* members) { integrator_->RegionsOverlap(regions, count, max_list, out, members); }
     void Select(rt_region const* regions, std::uint32_t count, std::uint32_t* touching, std::uint32_t* inside, std::uint32_t* object_touching, std::uint32_t* object_inside) { integrator_->SelectRegions(regions, count, touching, inside, object_touching, object_inside); }
     void PickRect(std::uint32_t x0, std::uint32_t y0, std::uint32_t x1, std::uint32_t y1, float t_near, float t_far, rt_region* region, std::uint32_t* touching, std::uint32_t* inside, std::uint32_t* object_touching, std::uint32_t* object_inside) { integrator_->PickRectThrough(camera_, x0, y0, x1, y1, t_near, t_far, region, touching, inside, object_touching, object_inside); }

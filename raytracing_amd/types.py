@@ -43,6 +43,10 @@ region_member = np.dtype([("primitive_id", "<u4"), ("flags", "<u4")])
 probe = np.dtype([("p1", "<f4", (4,)), ("p2", "<f4", (4,)), ("p3", "<f4", (4,))])
 probe_hits = np.dtype([("count", "<u4"), ("stored", "<u4"), ("first_primitive", "<u4"), ("flags", "<u4")])
 cross_member = np.dtype([("primitive_id", "<u4"), ("flags", "<u4"), ("c0", "<f4", (3,)), ("c1", "<f4", (3,))])
+# rt_separation (include/rt_hip.h): a separation query's answer -- the two closest points, their distance, the nearest triangle, flags (bit 0 searched, bit 1
+# found, bit 2 the pair crosses) and the winning candidate (0..2 a probe corner, 3..5 a corner of the triangle, 6 + 3 i + j an edge pair, 15 a crossing)
+separation = np.dtype([("on_probe", "<f4", (3,)), ("distance", "<f4"), ("on_scene", "<f4", (3,)), ("primitive_id", "<u4"), ("flags", "<u4"), ("feature", "<u4"),
+                       ("pad", "<u4", (2,))])
 camera = np.dtype([("position", float3), ("front", float3), ("up", float3), ("fov", "<f4"),
                    ("aspect_ratio", "<f4"), ("aperture", "<f4"), ("focus_distance", "<f4")])
 
@@ -53,6 +57,7 @@ assert camera.itemsize == 64 and surface.itemsize == 64 and bake_result.itemsize
 assert point.itemsize == 16 and nearest.itemsize == 32 and ray_hits.itemsize == 16 and point_hits.itemsize == 16
 assert region.itemsize == 144 and region_hits.itemsize == 16 and region_member.itemsize == 8
 assert probe.itemsize == 48 and probe_hits.itemsize == 16 and cross_member.itemsize == 32
+assert separation.itemsize == 48
 
 
 def probes_from_corners(corners):
