@@ -594,8 +594,11 @@ int rt_debug_separation_self(rt_ctx* ctx_or_null, const rt_triangle* triangles, 
 /* One fold adaptation per process GROUP instead of one per rank (N ranks that tile one image hold the same scene and would each probe, rotate and fold for
  * identical records): the context's current 4-wide records -- the closest-hit rays' and the shadow rays' (n_shadow == 0: they share), as adapted so far -- to
  * host buffers of `capacity` records each (records NULL: size query; entries2 = {closest entry, shadow entry}), and into another context that has uploaded
- * the SAME scene (same triangle order): they replace its own, its adaptation is switched off, refs are range-checked.  The launcher's channel carries the
- * bytes in between (bench.py: torch.distributed).  Any fold of the same tree is exact: results do not change. */
+ * the SAME scene (same triangle order): they replace its own, its adaptation is switched off.  The launcher's channel carries the bytes in between (bench.py:
+ * torch.distributed).  Any fold of the same tree is exact: results do not change.  The importer refuses -- "... do not fit this scene (<the defect>)", the
+ * context left as it was -- records that are not a tree from the entry over exactly this scene's leaves, each reached once by its first triangle, at most
+ * 33 record levels deep, with slot counts and frames as build_wide_bvh writes them (records the entry does not reach are tolerated, their refs range-checked).
+ * A scene whose root is a leaf has no 4-wide tree: the export refuses it, and the import refuses a record count of 0. */
 int rt_scene_export_folds(rt_ctx* ctx, void* closest_records, void* shadow_records, uint32_t capacity, uint32_t* n_closest, uint32_t* n_shadow, uint32_t* entries2);
 int rt_scene_import_folds(rt_ctx* ctx, const void* closest_records, uint32_t n_closest, uint32_t entry_closest, const void* shadow_records, uint32_t n_shadow, uint32_t entry_shadow);
 
@@ -1043,6 +1046,9 @@ int rt_debug_device_fold(rt_ctx* ctx, const rt_bvh_node* nodes, uint32_t num_nod
 /* RT_CTX_OPT_WIDE_LAYOUT = 1 on its own (host only): the records of a fold of `nodes` (and the node each one tests) permuted in place into (parent,
  * likeliest child) pairs, by the area of the children's boxes. */
 int rt_debug_pair_layout(const rt_bvh_node* nodes, uint32_t num_nodes, void* records, uint32_t* roots, uint32_t num_records);
+/* rt_scene_import_folds' check on its own (host only, no context, no HIP call): would a scene whose binary tree is `nodes` take `records` with that entry?
+ * The leaves the records must cover are read from `nodes`.  RT_OK, or RT_ERROR with the importer's words for the defect in rt_last_error(NULL). */
+int rt_debug_check_folds(const rt_bvh_node* nodes, uint32_t num_nodes, const void* records, uint32_t num_records, uint32_t entry_ref);
 /* ploc_kernels.h on its own: a binary tree over the leaves of `nodes` built on ctx's device with the metric of rt_debug_own_bvh (the same layout comes back: out_nodes[2 leaves - 1];
  * NULL = count query); *seconds = the device path's time, *rounds = clustering rounds. */
 int rt_debug_device_tree(rt_ctx* ctx, const rt_bvh_node* nodes, uint32_t num_nodes, double iso_weight, const float* dirs, uint32_t n_dirs, rt_bvh_node* out_nodes, uint32_t capacity,

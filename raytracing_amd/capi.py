@@ -102,7 +102,7 @@ EXPORTS = [
     "rt_compute_aovs", "rt_denoise", "rt_copy_history",
     "rt_frame_resolve", "rt_frame_present", "rt_frame_present_wait", "rt_frame_read_radiance", "rt_frame_radiance_device_ptr", "rt_frame_sample_count",
     "rt_frame_get_stats", "rt_frame_get_profile", "rt_frame_copy_radiance", "rt_frame_debug_read_queue", "rt_frame_debug_read_hits", "rt_debug_eval",
-    "rt_debug_wide_bvh", "rt_frame_debug_timeline", "rt_frame_debug_frame_rows", "rt_debug_own_bvh", "rt_debug_wide_bvh_metric", "rt_scene_tree_report", "rt_debug_choose_tree", "rt_debug_adapt_fold", "rt_debug_fold_abandon", "rt_debug_adapt_shadow_side", "rt_debug_rotate_tree", "rt_debug_fold_view_left", "rt_debug_device_fold", "rt_debug_wide_bvh_weights", "rt_debug_pair_layout", "rt_debug_device_tree", "rt_debug_count_box_passes", "rt_scene_export_folds", "rt_scene_import_folds",
+    "rt_debug_wide_bvh", "rt_frame_debug_timeline", "rt_frame_debug_frame_rows", "rt_debug_own_bvh", "rt_debug_wide_bvh_metric", "rt_scene_tree_report", "rt_debug_choose_tree", "rt_debug_adapt_fold", "rt_debug_fold_abandon", "rt_debug_adapt_shadow_side", "rt_debug_rotate_tree", "rt_debug_fold_view_left", "rt_debug_device_fold", "rt_debug_wide_bvh_weights", "rt_debug_pair_layout", "rt_debug_check_folds", "rt_debug_device_tree", "rt_debug_count_box_passes", "rt_scene_export_folds", "rt_scene_import_folds",
     "rt_group_create", "rt_group_unique_id", "rt_group_join", "rt_group_size", "rt_group_local_count", "rt_group_local_rank", "rt_group_comm_count",
     "rt_group_gather_radiance", "rt_group_destroy", "rt_group_last_error", "rt_group_denoise", "rt_group_create_local",
     "rt_group_create_unchecked",
@@ -177,6 +177,7 @@ def load():
         "rt_debug_device_fold": (i32, [vp, vp, u32, C.c_double, vp, u32, vp, vp, vp, u32, C.POINTER(u32), C.POINTER(u32), C.POINTER(C.c_double)]),
         "rt_debug_wide_bvh_weights": (i32, [vp, u32, vp, vp, vp, u32, C.POINTER(u32), C.POINTER(u32)]),
         "rt_debug_pair_layout": (i32, [vp, u32, vp, vp, u32]),
+        "rt_debug_check_folds": (i32, [vp, u32, vp, u32, u32]),
         "rt_debug_device_tree": (i32, [vp, vp, u32, C.c_double, vp, u32, vp, u32, C.POINTER(u32), C.POINTER(C.c_double), C.POINTER(u32), u32, vp, C.c_double]),
         "rt_debug_count_box_passes": (i32, [vp, vp, u32, vp, vp, u32, vp, C.POINTER(C.c_ulonglong)]),
         "rt_scene_export_folds": (i32, [vp, vp, vp, u32, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32)]),
@@ -826,6 +827,17 @@ def import_folds(ctx_handle, closest, shadow, entries):
     sh = np.ascontiguousarray(shadow, np.uint8) if shadow is not None and len(shadow) else None
     if lib.rt_scene_import_folds(ctx_handle, cl.ctypes.data, len(cl), entries[0], sh.ctypes.data if sh is not None else None, len(sh) if sh is not None else 0, entries[1]):
         raise RtError(lib.rt_last_error(ctx_handle).decode())
+
+
+def check_folds(nodes, records, entry):
+    """rt_debug_check_folds (host only, no context): rt_scene_import_folds' check of `records` (uint8[n, 64] or any 64-byte record array) and their entry against
+    the leaves of the LinearBVHNode[] `nodes`.  Returns None, or raises RtError with the importer's words for the defect."""
+    lib = load()
+    nodes = np.ascontiguousarray(nodes)
+    recs = np.ascontiguousarray(records)
+    recs = recs.view(np.uint8).reshape(recs.nbytes // 64, 64)
+    if lib.rt_debug_check_folds(nodes.ctypes.data, len(nodes), recs.ctypes.data if len(recs) else None, len(recs), int(entry)):
+        raise RtError(lib.rt_last_error(None).decode())
 
 
 def device_fold(ctx, nodes, iso_weight=-1.0, dirs=None, weights=None):

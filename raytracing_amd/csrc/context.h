@@ -19,6 +19,8 @@
 #include "bake_host.h"       // bake::CHUNK_POINTS
 #include "device_memory.h"   // dev::Mem
 
+namespace rtw { struct LeafStarts; }        // the first triangles of a scene's leaves (wide_bvh.h)
+
 namespace context
 {
 struct FoldAdapt;                          // RT_CTX_OPT_ADAPTIVE_FOLD: the state of a scene's fold adaptation (fold_adapt.h)
@@ -50,6 +52,9 @@ struct Scene
     WideTree replace_tree(TreeSlot slot, WideTree tree) { std::swap(trees[slot], tree); publish_trees(); return tree; }
     void walk_trees(TreeSlot closest_rays, TreeSlot shadow_rays) { closest = closest_rays; shadow = shadow_rays; publish_trees(); }
     uint32_t n_tris = 0;         // triangles of the uploaded scene (rt_scene_import_folds checks leaf refs against it)
+    // the first triangles of the scene's leaves, one bit per triangle (wide_bvh.h; filled at upload from the nodes, freed by free_scene, left alone by a refit:
+    // the topology does not change): what rt_scene_import_folds checks the leaf refs of imported records against
+    rtw::LeafStarts* leaf_starts = nullptr;
     std::string tree_report;     // what rt_scene_upload measured when it chose the trees (rt_scene_tree_report)
     FoldAdapt* adapt = nullptr;  // RT_CTX_OPT_ADAPTIVE_FOLD: armed at upload, run by the first rt_integrate (fold_adapt_hook)
     DScene d = {};

@@ -9,6 +9,7 @@
 #include <stdio.h>
 #include <string.h>
 #include <cmath>
+#include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <string>
@@ -511,6 +512,7 @@ void context::free_scene(Scene& s)
     if (s.refit) { refit::release(*s.refit); delete s.refit; }
     if (s.pose_snap) (void)hipFree(s.pose_snap);
     if (s.pose) { pose::release(*s.pose); delete s.pose; }
+    delete s.leaf_starts;
     s = Scene();
 }
 
@@ -844,6 +846,7 @@ struct Upload
         s.d.emissive_nee = (sd->flags & RT_SCENE_EMISSIVE_NEE) && sd->num_emissive ? 1u : 0u;
         s.walk_trees(have_cl ? TREE_CLOSEST : TREE_REF, have_sh ? TREE_SHADOW : TREE_REF);
         s.n_tris = nt;
+        s.leaf_starts = new LeafStarts(leaf_starts(sd->nodes, nn, nt));     // what imported records are checked against (rt_scene_import_folds)
         s.wide_ok = have_wide;
         s.offsets32 = fits_offsets32(n_interior + 1) && fits_offsets32(nt);
         if (!s.offsets32)
@@ -1120,8 +1123,9 @@ int rt_debug_pose(rt_ctx* ctx, const rt_triangle* rest, const uint32_t* object_o
 // closest-hit rays' and the shadow rays', as adapted so far) to the host, the launcher's own channel carries them (torch.distributed, MPI, a file: 64 bytes
 // per record, ~240 MB for the 2.8 M-triangle scene), rt_scene_import_folds puts them in place of the receiver's own and switches its adaptation off.  The
 // records are indices into the triangle records every rank made from the same scene, so nothing else travels.  Exactness is the fold's: any fold of the same
-// binary tree over the same leaves gives the same results -- and the importer checks what it can: record count, refs within range,
-// leaf refs within the triangle array.
+// binary tree over the same leaves gives the same results -- and the importer checks that the records ARE such a fold as far as the
+// walks depend on it (rtw::check_fold): a tree from the entry, no deeper than the walks' stacks, every leaf of this scene reached exactly once by its first
+// triangle, slot counts and frames within what the kernels' arithmetic takes.  What it cannot check is what only the binary tree could tell: the boxes.
 int rt_scene_export_folds(rt_ctx* ctx, void* closest_records, void* shadow_records, uint32_t capacity, uint32_t* n_closest, uint32_t* n_shadow, uint32_t* entries2)
 {
     if (!ctx || !n_closest || !n_shadow) return fail(ctx, "rt_scene_export_folds: NULL argument");
@@ -1143,27 +1147,22 @@ int rt_scene_export_folds(rt_ctx* ctx, void* closest_records, void* shadow_recor
 
 int rt_scene_import_folds(rt_ctx* ctx, const void* closest_records, uint32_t n_closest, uint32_t entry_closest, const void* shadow_records, uint32_t n_shadow, uint32_t entry_shadow)
 {
-    if (!ctx || !closest_records || n_closest == 0) return fail(ctx, "rt_scene_import_folds: NULL argument");
+    if (!ctx || (!closest_records && n_closest != 0)) return fail(ctx, "rt_scene_import_folds: NULL argument");
+    // a scene whose root is a leaf has no 4-wide tree: rt_scene_export_folds refuses it ("the scene has no 4-wide tree"), so there is nothing to take
+    if (n_closest == 0) return fail(ctx, "rt_scene_import_folds: no records (a scene whose root is a leaf has no 4-wide tree; rt_scene_export_folds gives none for it)");
     Scene& s = ctx->scene;
     if (!s.valid || !s.wide_ok) return fail(ctx, "rt_scene_import_folds: the scene has no 4-wide tree to replace (upload it first, with RT_CTX_OPT_WIDE_BVH = 1)");
     if (n_closest >= (1u << 26) || n_shadow >= (1u << 26)) return fail(ctx, "rt_scene_import_folds: too many records");
     (void)hipSetDevice(ctx->device);
-    // what can be checked: every ref is a record of the same array, a leaf inside the triangle array, or empty
-    const uint32_t nt = s.n_tris;
-    auto sane = [&](const WideNode* r, uint32_t n, uint32_t entry) -> bool
-    {
-        if (entry >= n) return false;
-        for (uint32_t i = 0; i < n; ++i)
-            for (uint32_t ref : r[i].ref)
-            {
-                if (ref == RT_EMPTY_REF) continue;
-                if (ref & RT_LEAF_BIT) { if ((ref & ~RT_LEAF_BIT) >= nt) return false; }
-                else if (ref >= n) return false;
-            }
-        return true;
-    };
-    if (!sane((const WideNode*)closest_records, n_closest, entry_closest)) return fail(ctx, "rt_scene_import_folds: the closest-hit records do not fit this scene (a ref outside the records / the triangles)");
-    if (n_shadow && (!shadow_records || !sane((const WideNode*)shadow_records, n_shadow, entry_shadow))) return fail(ctx, "rt_scene_import_folds: the shadow records do not fit this scene");
+    // what records from outside must be before a walk may see them: a tree over this scene's leaves, no deeper than the walks' stacks, frames within the
+    // walks' arithmetic (check_fold, wide_bvh.cpp; DESIGN.md, "one adaptation per group").  Both arrays against the same leaves: the shadow rays' own tree is
+    // built over the reference's.  A refusal leaves the context as it was.
+    if (!s.leaf_starts) return fail(ctx, "rt_scene_import_folds: the scene has no record of its leaves");
+    const FoldDefect bad_cl = check_fold((const WideNode*)closest_records, n_closest, entry_closest, *s.leaf_starts);
+    if (bad_cl != FoldDefect::NONE) return fail(ctx, std::string("rt_scene_import_folds: the closest-hit records do not fit this scene (") + fold_defect_text(bad_cl) + ")");
+    if (n_shadow && !shadow_records) return fail(ctx, "rt_scene_import_folds: the shadow records do not fit this scene (a count without records)");
+    const FoldDefect bad_sh = n_shadow ? check_fold((const WideNode*)shadow_records, n_shadow, entry_shadow, *s.leaf_starts) : FoldDefect::NONE;
+    if (bad_sh != FoldDefect::NONE) return fail(ctx, std::string("rt_scene_import_folds: the shadow records do not fit this scene (") + fold_defect_text(bad_sh) + ")");
     // nothing in flight may still read the records that go: batches traced ahead are dropped, every stream drains, an adaptation of this context's own is abandoned
     if (quiesce(ctx) != RT_OK) return RT_ERROR;
     if (s.adapt) { drop_fold_adapt(s.adapt); s.adapt = nullptr; }
@@ -1288,6 +1287,20 @@ int rt_debug_pair_layout(const rt_bvh_node* nodes, uint32_t num_nodes, void* rec
     pair_layout_by_area(wide, r, nodes, num_nodes, (const ownbvh::Metric*)nullptr);
     memcpy(records, wide.data(), wide.size() * sizeof(WideNode));
     memcpy(roots, r.data(), r.size() * sizeof(uint32_t));
+    return RT_OK;
+}
+
+// rt_scene_import_folds' check without a context (no HIP call): are `records` a fold the walks can take over the leaves of `nodes`?
+int rt_debug_check_folds(const rt_bvh_node* nodes, uint32_t num_nodes, const void* records, uint32_t num_records, uint32_t entry_ref)
+{
+    if (!nodes || num_nodes == 0 || (!records && num_records != 0)) return fail(nullptr, "rt_debug_check_folds: NULL argument");
+    if (num_records >= (1u << 26)) return fail(nullptr, "rt_debug_check_folds: too many records");
+    uint64_t n_tris = 0;                                                // the triangle array ends where the last leaf does
+    for (uint32_t i = 0; i < num_nodes; ++i)
+        if ((nodes[i].num_primitives_axis >> 16) != 0u) n_tris = std::max<uint64_t>(n_tris, (uint64_t)nodes[i].offset + (nodes[i].num_primitives_axis >> 16));
+    if (n_tris >= RT_LEAF_BIT) return fail(nullptr, "rt_debug_check_folds: a leaf's triangles lie beyond what a ref can hold");
+    const FoldDefect bad = check_fold((const WideNode*)records, num_records, entry_ref, leaf_starts(nodes, num_nodes, (uint32_t)n_tris));
+    if (bad != FoldDefect::NONE) return fail(nullptr, std::string("rt_debug_check_folds: the records do not fit this scene (") + fold_defect_text(bad) + ")");
     return RT_OK;
 }
 

@@ -322,7 +322,7 @@ bool build_wide_bvh(const rt_bvh_node* nodes, uint32_t nn, int collapse, std::ve
                 todo.pop_back();
                 depth_of.pop_back();
                 if ((mine & 0xFFFFu) == 0u && (cancelled() || bad.load(std::memory_order_relaxed))) return false;
-                if (depth > 33u) return false;                                 // <= 3 pending slots per level must fit RT_W4_STACK_MAX
+                if (depth > RT_WIDE_MAX_LEVELS) return false;                  // <= 3 pending slots per level must fit RT_W4_STACK_MAX
                 if (cut_depth != 0u && depth == cut_depth) { met.push_back(Met{(uint32_t)subs.size(), true}); subs.push_back(Sub{n, depth, {}}); continue; }
                 if (!reach(n) || ++mine > nn) return false;
                 if (list) list->push_back(n); else met.push_back(Met{n, false});
@@ -499,6 +499,108 @@ void pair_layout_by_node_weights(std::vector<WideNode>& wide, std::vector<uint32
     std::vector<double> w(wide.size(), 0.0);
     for (size_t rec = 0; rec < wide.size(); ++rec) if (roots[rec] < nn) w[rec] = node_weights[roots[rec]];
     pair_layout(wide, &roots, w);
+}
+
+// ---- records that come from outside: rt_scene_import_folds, rt_debug_check_folds ("one adaptation per group": the rule and why each clause) ----
+LeafStarts leaf_starts(const rt_bvh_node* nodes, uint32_t nn, uint32_t n_tris)
+{
+    LeafStarts l;
+    l.n_tris = n_tris;
+    l.bits.assign(((size_t)n_tris + 63u) / 64u, 0ull);
+    std::map<uint32_t, uint32_t> again;
+    for (uint32_t i = 0; i < nn; ++i)
+    {
+        if ((nodes[i].num_primitives_axis >> 16) == 0u) continue;
+        const uint32_t t = nodes[i].offset;
+        if (t >= n_tris) continue;
+        const uint64_t bit = 1ull << (t & 63u);
+        if (l.bits[t >> 6] & bit) ++again[t];
+        else { l.bits[t >> 6] |= bit; ++l.distinct; }
+    }
+    for (const auto& kv : again) l.shared.emplace_back(kv.first, kv.second + 1u);
+    return l;
+}
+
+const char* fold_defect_text(FoldDefect d)
+{
+    switch (d)
+    {
+    case FoldDefect::NONE: return "no defect";
+    case FoldDefect::ENTRY: return "the entry is not a record of the array, or without records not a leaf";
+    case FoldDefect::REF_RANGE: return "a ref outside the records / the triangles";
+    case FoldDefect::REACHED_TWICE: return "a record is reached twice";
+    case FoldDefect::TOO_DEEP: return "deeper than the walk's stack";
+    case FoldDefect::SLOT_COUNT: return "a record's slot count is not the number of its refs, 2 to 4";
+    case FoldDefect::FRAME: return "a record's frame is outside what the walk's arithmetic takes";
+    case FoldDefect::LEAF_NOT_A_START: return "a leaf ref is not the first triangle of a leaf of the scene";
+    case FoldDefect::LEAF_TWICE: return "a leaf of the scene is reached twice";
+    case FoldDefect::LEAF_MISSING: return "a leaf of the scene is missing";
+    }
+    return "unknown defect";
+}
+
+FoldDefect check_fold(const WideNode* recs, uint32_t n, uint32_t entry, const LeafStarts& leaves)
+{
+    if (n == 0u ? (!(entry & RT_LEAF_BIT) || entry == RT_EMPTY_REF) : entry >= n) return FoldDefect::ENTRY;
+    // every ref of every record, reached or not: a record of this array, a triangle of the scene, or empty (n < 2^26: a record ref never has the leaf bit)
+    if (n == 0u && (entry & ~RT_LEAF_BIT) >= leaves.n_tris) return FoldDefect::REF_RANGE;
+    for (uint32_t i = 0; i < n; ++i)
+        for (uint32_t ref : recs[i].ref)
+        {
+            if (ref == RT_EMPTY_REF) continue;
+            if (ref & RT_LEAF_BIT) { if ((ref & ~RT_LEAF_BIT) >= leaves.n_tris) return FoldDefect::REF_RANGE; }
+            else if (ref >= n) return FoldDefect::REF_RANGE;
+        }
+    // the walk from the entry, depth as build_wide_bvh counts it: the entry's record is level 1, a record one more than the record that refers to it, leaves
+    // are no level.  Every record is opened at most once (a second arrival ends the check), so the walk ends whatever the refs say.
+    std::vector<uint64_t> reached(((size_t)n + 63u) / 64u, 0ull), seen(leaves.bits.size(), 0ull);
+    std::vector<uint32_t> more(leaves.shared.size(), 0u);               // arrivals after the first at a triangle where several leaves begin
+    struct Item { uint32_t ref, level; };
+    std::vector<Item> todo{Item{entry, 1u}};
+    uint32_t distinct_seen = 0;
+    bool deep = false, slots = false, frame = false, not_a_start = false, leaf_twice = false;
+    while (!todo.empty())
+    {
+        const Item it = todo.back();
+        todo.pop_back();
+        if (it.ref & RT_LEAF_BIT)
+        {
+            const uint32_t t = it.ref & ~RT_LEAF_BIT;
+            if (!leaves.is_start(t)) { not_a_start = true; continue; }
+            const uint64_t bit = 1ull << (t & 63u);
+            if (!(seen[t >> 6] & bit)) { seen[t >> 6] |= bit; ++distinct_seen; continue; }
+            const auto at = std::lower_bound(leaves.shared.begin(), leaves.shared.end(), std::make_pair(t, 0u));
+            if (at == leaves.shared.end() || at->first != t || ++more[(size_t)(at - leaves.shared.begin())] >= at->second) leaf_twice = true;
+            continue;
+        }
+        const uint64_t bit = 1ull << (it.ref & 63u);
+        if (reached[it.ref >> 6] & bit) return FoldDefect::REACHED_TWICE;
+        reached[it.ref >> 6] |= bit;
+        if (it.level > RT_WIDE_MAX_LEVELS) deep = true;
+        const WideNode& r = recs[it.ref];
+        uint32_t occupied = 0;
+        for (uint32_t ref : r.ref) occupied += ref != RT_EMPTY_REF ? 1u : 0u;
+        if ((r.meta >> 24) != occupied || occupied < 2u) slots = true;
+        // wide_frame's range: cell = 2^e with e in -126 .. 20, coordinates below 2^28 and the origin a multiple of the cell below them, so |origin| <= 2^28
+        // (w4_test_slots' operands stay below 2^127 with these: trace_kernels.h, "No overflow")
+        const float origin[3] = {r.ox, r.oy, r.oz};
+        for (int a = 0; a < 3; ++a)
+        {
+            const uint32_t e = (r.meta >> (8 * a)) & 0xFFu;
+            if (!std::isfinite(origin[a]) || std::fabs(origin[a]) > 268435456.0f || e < 1u || e > 147u) frame = true;
+        }
+        for (int k = 3; k >= 0; --k)
+            if (r.ref[k] != RT_EMPTY_REF) todo.push_back(Item{r.ref[k], it.level + 1u});
+    }
+    if (deep) return FoldDefect::TOO_DEEP;
+    if (slots) return FoldDefect::SLOT_COUNT;
+    if (frame) return FoldDefect::FRAME;
+    if (not_a_start) return FoldDefect::LEAF_NOT_A_START;
+    if (leaf_twice) return FoldDefect::LEAF_TWICE;
+    if (distinct_seen != leaves.distinct) return FoldDefect::LEAF_MISSING;
+    for (size_t i = 0; i < more.size(); ++i)
+        if (more[i] + 1u < leaves.shared[i].second) return FoldDefect::LEAF_MISSING;
+    return FoldDefect::NONE;
 }
 
 // The ray population a shadow tree serves (own_bvh.h): shadow rays go to the analytic lights only (hit_surface.cl:114-146,

@@ -5,6 +5,7 @@
 #pragma once
 #include <stdint.h>
 #include <atomic>
+#include <utility>
 #include <vector>
 #include <hip/hip_vector_types.h>      // float4 (the probe rays travel as the kernels' own queues)
 #include "rt_types.h"
@@ -14,6 +15,8 @@
 namespace rtw
 {
 enum { RT_WIDE_TWO_LEVELS = 0, RT_WIDE_SAH = 1 };
+// record levels a fold may have (the entry's record is level 1): three pending slots per level must fit RT_W4_STACK_MAX (trace_kernels.h)
+enum : uint32_t { RT_WIDE_MAX_LEVELS = 33u };
 
 // false: the tree does not qualify (non-finite or non-nested bounds, child order, too deep for the kernel's stack): k_trace2 is used
 bool build_wide_bvh(const rt_bvh_node* nodes, uint32_t nn, int collapse, std::vector<WideNode>& out, uint32_t& entry_ref,
@@ -29,6 +32,38 @@ void pair_layout(std::vector<WideNode>& wide, std::vector<uint32_t>* roots, cons
 // ... by the area (the own trees: their metric) of the records' boxes, or by per-NODE weights (an adaptation's measured crossings)
 void pair_layout_by_area(std::vector<WideNode>& wide, std::vector<uint32_t>& roots, const rt_bvh_node* nodes, uint32_t nn, const ownbvh::Metric* metric);
 void pair_layout_by_node_weights(std::vector<WideNode>& wide, std::vector<uint32_t>& roots, const double* node_weights, uint32_t nn);
+
+// ---- records that come from outside (rt_scene_import_folds, rt_debug_check_folds): are they a tree over the scene's leaves that the walks can take? ----
+// The first triangles of a scene's leaves: one bit per triangle, and -- for a node array in which several leaf nodes begin at the same triangle, which the
+// reference's builder never makes but an upload does not refuse -- how many leaves begin there.
+struct LeafStarts
+{
+    std::vector<uint64_t> bits;                                   // bit t: a leaf begins at triangle t
+    std::vector<std::pair<uint32_t, uint32_t>> shared;            // (triangle, leaves that begin there) where that is more than one, sorted by triangle
+    uint32_t n_tris = 0, distinct = 0;                            // distinct: bits set
+    bool is_start(uint32_t t) const { return t < n_tris && ((bits[t >> 6] >> (t & 63u)) & 1u) != 0u; }
+};
+// from the binary tree's leaf nodes (a leaf that begins at or beyond n_tris is left out: nothing can refer to it)
+LeafStarts leaf_starts(const rt_bvh_node* nodes, uint32_t nn, uint32_t n_tris);
+
+// What is wrong with a record array, in the order the classes are looked for: the first class in this order that applies to the array is its defect, whichever
+// record shows it, so the answer does not depend on the order of a walk.
+enum class FoldDefect
+{
+    NONE = 0,
+    ENTRY,            // the entry is not a record of the array; without records: not a leaf ref
+    REF_RANGE,        // some record's ref, reached or not, lies outside the records / the triangles
+    REACHED_TWICE,    // a record is reached through two slots: a cycle, a self-reference, a shared record
+    TOO_DEEP,         // more record levels than build_wide_bvh allows (RT_W4_STACK_MAX is sized from them)
+    SLOT_COUNT,       // meta >> 24 of a reached record is not the number of its non-empty refs, or not in 2 .. 4
+    FRAME,            // a reached record's origin is not finite or beyond 2^28, a cell exponent outside wide_frame's range
+    LEAF_NOT_A_START, // a reached leaf ref is not the first triangle of a leaf of the scene
+    LEAF_TWICE,       // a leaf of the scene is reached more often than the scene has it
+    LEAF_MISSING      // ... or less often
+};
+const char* fold_defect_text(FoldDefect d);
+// Iterative (a chain or a cycle of any length costs heap, not stack); records that the entry does not reach are tolerated, their refs are still range-checked.
+FoldDefect check_fold(const WideNode* recs, uint32_t n, uint32_t entry, const LeafStarts& leaves);
 
 ownbvh::Metric shadow_metric(const rt_light* lights, uint32_t n, double iso_share);
 

@@ -61,6 +61,12 @@ def test_every_refusal_without_a_context_keeps_its_text():
         ("rt_debug_pair_layout", (B, 1, None, B, 1), NULL_ARG),
         ("rt_debug_pair_layout", (B, 1, B, None, 1), NULL_ARG),
         ("rt_debug_pair_layout", (B, 0, B, B, 1), NULL_ARG),
+        ("rt_debug_check_folds", (None, 1, B, 1, 0), NULL_ARG),
+        ("rt_debug_check_folds", (L, 0, B, 1, 0), NULL_ARG),
+        ("rt_debug_check_folds", (L, 1, None, 1, 0), NULL_ARG),
+        ("rt_debug_check_folds", (L, 1, B, 1 << 26, 0), "too many records"),
+        ("rt_debug_check_folds", (L, 1, None, 0, 0), "the records do not fit this scene (the entry is not a record of the array, or without records not a leaf)"),
+        ("rt_debug_check_folds", (L, 1, B, 1, 0), "the records do not fit this scene (a record is reached twice)"),
         # the own trees and the choice between them
         ("rt_debug_own_bvh", (None, 1, 1.0, None, 0, None, 0, U), NULL_ARG),
         ("rt_debug_own_bvh", (B, 0, 1.0, None, 0, None, 0, U), NULL_ARG),
@@ -119,7 +125,7 @@ def test_every_refusal_without_a_context_keeps_its_text():
     silent = {"rt_scene_tree_report", "rt_debug_fold_view_left"}          # refuse without a message: below
     assert {name for name, _, _ in table} | silent == {n for n in capi.EXPORTS if n.startswith(("rt_scene_upload", "rt_scene_refit", "rt_scene_set_objects",
         "rt_scene_pose", "rt_scene_export_folds", "rt_scene_import_folds", "rt_scene_tree_report", "rt_debug_wide_bvh", "rt_debug_pair_layout", "rt_debug_own_bvh",
-        "rt_debug_choose_tree", "rt_debug_device_fold", "rt_debug_device_tree", "rt_debug_count_box_passes", "rt_debug_adapt_", "rt_debug_fold_", "rt_debug_rotate_tree",
+        "rt_debug_check_folds", "rt_debug_choose_tree", "rt_debug_device_fold", "rt_debug_device_tree", "rt_debug_count_box_passes", "rt_debug_adapt_", "rt_debug_fold_", "rt_debug_rotate_tree",
         "rt_debug_refit", "rt_debug_pose"))}
     for name, args, text in table:
         rc = getattr(lib, name)(*args)
