@@ -739,6 +739,14 @@ enum rt_option
                                       1080p frame of the 2.8 M-triangle scene where the rays are worth 1.6), a launch of k is not.  Costs: two more sets of
                                       per-path buffers for k samples in flight (within 64 GiB, or RT_OPT_PATH_STATE_LIMIT_MB); rt_stats' ray totals run ahead of
                                       its sample count by rt_stats.samples_ahead.  Not with AOVs / the denoiser / RT_OPT_STAGE_PIPES / profiling. */
+    , RT_OPT_FUSED_RAYGEN = 27      /* 1 (default) / 0: inside rt_integrate the bounce-0 closest-hit trace of a batch makes its primary rays itself, from the queue
+                                      index and the camera (the function k_raygen uses: the same bits), and leaves only their directions and path ids for the
+                                      bounce-0 k_shade, which knows the throughput to be 1 and the log to be empty; k_raygen runs as one block that folds and
+                                      resets the counters.  16 bytes per primary path written and read instead of 48 written and 64 read.
+                                      0: k_raygen writes the queue and the bounce-0 launches read it, as the stage calls (rt_generate_rays ...), the banks of
+                                      RT_OPT_SAMPLES_AHEAD and k_frame always do.  Batches whose primary queue somebody else reads (RT_OPT_AOV / RT_OPT_DENOISER,
+                                      rt_frame_debug_timeline) or whose trace variant has no primary instance (RT_OPT_TRACE_VARIANT other than 5 / 10, a scene
+                                      without the wide tree) take the written queue whatever the value.  Results are bit-identical for both values. */
     , RT_OPT_TRACE_TUNE = 12       /* k_trace2 (variants 8, 9) loop thresholds: value & 255 = lanes that must hold an
                                        interior node for a wave to stay in the node loop, value >> 8 & 255 = lanes that
                                        must wait at a triangle for another pass of the triangle loop, value >> 16 & 255 = rays a wave takes
@@ -920,6 +928,7 @@ typedef struct rt_stats
     uint32_t samples_ahead;            /* RT_OPT_SAMPLES_AHEAD: samples traced (or being traced) ahead of `samples` at the moment; closest_rays / shadow_rays
                                           INCLUDE their rays (the banks count per batch) */
     uint64_t samples_from_banks;       /* RT_OPT_SAMPLES_AHEAD: samples of the stage API that were replayed out of a batch traced ahead, since the frame was created */
+    uint64_t fused_raygen_launches;    /* RT_OPT_FUSED_RAYGEN: chunks of rt_integrate's batches whose bounce-0 launches made their primary rays themselves, since the frame was created */
 } rt_stats;
 int rt_frame_get_stats(rt_frame* frame, rt_stats* out);
 /* RT_OPT_FRAME_KERNEL's per-wave rows of the latest k_frame launch (diagnostics: rays per bounce and 100 MHz ticks per phase of every wave;

@@ -96,6 +96,7 @@ struct PathPipe
     uint32_t prev_bounces = 0;
     uint32_t fold_accumulates = 0;     // the sequence in flight is a 2nd+ chunk of its batch: its counters ADD to last_*
     bool shadow_pending = false;       // rt_shade issued, rt_intersect_shadow not yet
+    bool primary_fused = false;        // RT_OPT_FUSED_RAYGEN: the batch in flight has no bounce-0 queue in memory: its bounce-0 trace and shade launches make the primary rays (generate_rays)
     uint64_t batch_paths() const { return (uint64_t)chunk_count * (cur_slots ? cur_slots : 1u); }   // paths of the batch in flight (a trace launch's size class)
     // The per-path buffers for `paths` paths in flight and a log of `log_elems` entries, in the order they are allocated (alloc_path_buffers /
     // free_path_buffers; no arguments: all of them, for the free).  The queues carry 4 elements of padding, the slow lists 64, the log 16 bytes;
@@ -195,6 +196,7 @@ struct rt_frame
         void release() { free_buffers(buffers()); blocks = 0; }
     } kf;
     uint32_t frame_chunks_per_wave = 0;
+    uint64_t fused_launches = 0;                                                   // RT_OPT_FUSED_RAYGEN: k_raygen launches that ran their prologue only (rt_stats)
     uint64_t frame_launches = 0;                                                   // samples rendered by k_frame so far (rt_stats)
     // RT_OPT_FRAME_KERNEL = 255: the choice is MEASURED -- k_frame wins by 1.4 - 1.8 x on scenes of up to ~1 M triangles and loses 7 - 10 % on the 2.8 M /
     // 10 M ones (profiles/r05_call13.log), so the first frames of a scene time both: frames 0 - 1 (stage kernels) and 2 - 3 (k_frame) warm up, frames 4 - 19
@@ -229,6 +231,7 @@ struct rt_frame
     bool small_launch_set = false;              // ... set by the caller (otherwise the loop-D instance uses 8 M: launch_trace_w4)
     uint32_t trace_waves_per_cu = 0;   // RT_OPT_TRACE_WAVES_PER_CU (0 = LDS-limited residency)
     uint32_t chunk_refill = 1;                 // RT_OPT_CHUNK_REFILL: chunk mode refills idle lanes from the wave's own chunks
+    uint32_t fused_raygen = 1;                 // RT_OPT_FUSED_RAYGEN: rt_integrate's bounce-0 launches make their primary rays themselves (primary_fusable)
     uint64_t trace_tail_paths = 100000000ull; // RT_OPT_TRACE_TAIL_PATHS: batches of fewer paths launch the instance with loop D and refilled chunks (8 / 16 / 32 / 64 /
                                               // 128 samples of a 1080p frame in flight: +8 / +5 / +2.3 / -1.6 / -2.8 %, profiles/r04_call20_21.log, r04_call22.log)
     uint32_t trace_tail_lanes = 40;    // RT_OPT_TRACE_TAIL_LANES: k_trace_w4's loop D (0 = off); sweep: profiles/r04_call04_kernel_ab.log
@@ -1198,6 +1201,10 @@ int rt_set_option(rt_frame* f, int option, uint32_t value)
     case RT_OPT_TRACE_TAIL_LANES: f->trace_tail_lanes = value > 64u ? 64u : value; return RT_OK;
     case RT_OPT_TRACE_TAIL_PATHS: f->trace_tail_paths = value; return RT_OK;
     case RT_OPT_CHUNK_REFILL: f->chunk_refill = value ? 1u : 0u; return RT_OK;
+    case RT_OPT_FUSED_RAYGEN:
+        if (value > 1u) return fail(f->ctx, "rt_set_option: RT_OPT_FUSED_RAYGEN is 0 or 1");
+        f->fused_raygen = value;
+        return RT_OK;
     case RT_OPT_COMPACT_LOG:
     case RT_OPT_DEBUG_LOG_POOL_DIV:
         if (option == RT_OPT_DEBUG_LOG_POOL_DIV && value == 0) return fail(f->ctx, "rt_set_option: RT_OPT_DEBUG_LOG_POOL_DIV must be >= 1");
@@ -1328,6 +1335,7 @@ struct TraceTarget
     uint64_t paths;                        // paths of the batch the rays belong to (a launch's size class; its live count is on the device)
     uint32_t timeline_slot;                // rt_frame_debug_timeline: the bounce whose slot the instrumented closest-hit instance records into
     uint32_t variant, waves_per_cu;        // RT_OPT_TRACE_VARIANT, RT_OPT_TRACE_WAVES_PER_CU as this launch takes them
+    const PrimaryGen* primary = nullptr;   // RT_OPT_FUSED_RAYGEN: the launch makes its rays itself (bounce 0 of a batch for which primary_fusable held)
 };
 
 // the persistent grid of one-wave blocks for an LDS stack of `stack_entries` entries: 160 KiB / (entries * 512 B) waves per CU, at most 32 and at most
@@ -1363,6 +1371,18 @@ void launch_trace2(rt_frame* f, const TraceTarget& t, const float4* o4, const fl
         &t.counters->stack_spills);
 }
 
+// RT_OPT_FUSED_RAYGEN: the bounce-0 closest-hit launch that makes its primary rays itself, in place of the plain or the loop-D instance of the 12-entry stack
+void launch_trace_w4_primary(rt_frame* f, const TraceTarget& t, uint32_t blocks, uint32_t tune, uint32_t chunk_below, bool tail_instance, const uint32_t* count)
+{
+    DCounters* const c = t.counters;
+    if (tail_instance)
+        hipLaunchKernelGGL((k_trace_w4_primary<true>), dim3(blocks), dim3(64), 0, t.stream, f->ctx->scene.d, *t.primary, count, &c->head[0][0], t.hits,
+            t.spill, tune, t.slow_list, &c->slow_count[0], &c->stack_spills, chunk_below, f->trace_tail_lanes, f->chunk_refill);
+    else
+        hipLaunchKernelGGL((k_trace_w4_primary<false>), dim3(blocks), dim3(64), 0, t.stream, f->ctx->scene.d, *t.primary, count, &c->head[0][0], t.hits,
+            t.spill, tune, t.slow_list, &c->slow_count[0], &c->stack_spills, chunk_below, 0u, f->chunk_refill);
+}
+
 // k_trace_w4 over the 4-wide quantized tree, then k_trace2 over the (normally empty) list of rays it left out
 template <bool SHADOW, int STACK>
 void launch_trace_w4(rt_frame* f, const TraceTarget& t, const float4* o4, const float4* d4, const uint32_t* aux, const uint32_t* count)
@@ -1385,7 +1405,9 @@ void launch_trace_w4(rt_frame* f, const TraceTarget& t, const float4* o4, const 
     // (Camera-ray launches refilled instead of chunked -- coherent rays, short tails? -- measured: 2477 instead of 2876 Mrays/s per frame,
     // profiles/r04_call14.log: a refilling launch of any size pays its ~0.6 ms drain.)
     unsigned long long* const no_timeline = nullptr;
-    if (!SHADOW && STACK == 12 && f->timeline)          // tools/launch_timeline.py: the instrumented instance
+    if (!SHADOW && STACK == 12 && t.primary)            // RT_OPT_FUSED_RAYGEN (primary_fusable: no timeline, this variant)
+        launch_trace_w4_primary(f, t, blocks, tune, chunk_below, tail_instance, count);
+    else if (!SHADOW && STACK == 12 && f->timeline)          // tools/launch_timeline.py: the instrumented instance
         hipLaunchKernelGGL((k_trace_w4<false, 12, true, false>), dim3(blocks), dim3(64), 0, t.stream, ctx->scene.d, o4, d4, aux, count,
             &c->head[s][0], t.hits, t.log, t.spill, tune, t.slow_list,
             &c->slow_count[s], &c->stack_spills, &c->tl_start[t.timeline_slot & 63u],
@@ -1486,7 +1508,17 @@ namespace
 {
 // Primary rays for `n_slots` consecutive samples (sample indices sample_count ..
 // sample_count + n_slots - 1) in one launch on pipe `p`; they then travel through that pipe's queues.
-int generate_rays(rt_frame* f, PathPipe& p, uint32_t n_slots, uint32_t chunk_base = 0, bool later_chunk_on_this_pipe = false)
+// RT_OPT_FUSED_RAYGEN: may a batch of rt_integrate leave its bounce-0 queue unwritten?  Its bounce-0 closest-hit launch must be one of the k_trace_w4
+// instances that have a primary form (the 12-entry stack, plain or loop D: what launch_trace picks under these conditions), and nothing else may read that
+// queue: the instrumented instance (rt_frame_debug_timeline) does, and so does k_aov (per_frame: the caller rules it out).  The rays k_trace_w4 hands to
+// k_trace2's list are written out by the primary instance itself.
+bool primary_fusable(const rt_frame* f)
+{
+    return f->fused_raygen != 0u && !f->timeline && f->ctx->scene.wide_ok && (f->trace_variant == 5u || f->trace_variant == 10u);
+}
+
+// fused: only the prologue runs (one block); the pipe's bounce-0 launches make the rays (intersect_pipe, shade_pipe)
+int generate_rays(rt_frame* f, PathPipe& p, uint32_t n_slots, uint32_t chunk_base = 0, bool later_chunk_on_this_pipe = false, bool fused = false)
 {
     rt_ctx* ctx = f->ctx;
     if (p.cur_slots != 0) return fail(ctx, "rt_generate_rays: the previous sample was not advanced (rt_advance_sample)");
@@ -1497,11 +1529,13 @@ int generate_rays(rt_frame* f, PathPipe& p, uint32_t n_slots, uint32_t chunk_bas
     p.chunk_count = f->n_local - chunk_base < f->chunk_pixels ? f->n_local - chunk_base : f->chunk_pixels;
     float tan_half_fov = rt_tanf(0.5f * f->camera.fov);  // raygeneration.cl:108, uniform -> host
     uint32_t blocks = (p.chunk_count * n_slots + 255u) / 256u;
-    if (blocks == 0) blocks = 1;
+    if (blocks == 0 || fused) blocks = 1;
+    p.primary_fused = fused;
+    if (fused) ++f->fused_launches;
     KernelSpan span(f, 0, p.stream);
     hipLaunchKernelGGL(k_raygen, dim3(blocks), dim3(256), 0, p.stream, f->tile, f->camera, f->sample_count, n_slots,
         tan_half_fov, p.prev_bounces, p.o4[0], p.d4[0], p.thr[0], p.counters, p.chunk_base, p.chunk_count,
-        f->chunk_pixels, p.fold_accumulates);
+        f->chunk_pixels, p.fold_accumulates, fused ? 1u : 0u);
     p.fold_accumulates = later_chunk_on_this_pipe ? 1u : 0u;     // what the NEXT fold does with this sequence's counters
     p.prev_bounces = f->max_bounces;
     p.cur_slots = n_slots;
@@ -1623,7 +1657,11 @@ int intersect_pipe(rt_frame* f, PathPipe& p, uint32_t bounce)
 {
     rt_ctx* ctx = f->ctx;
     const uint32_t in = bounce & 1u;
-    const TraceTarget t = {p.stream, p.spill, p.slow_list, 0u, p.hits, dlog(f, p), p.counters, p.batch_paths(), bounce, f->trace_variant, f->trace_waves_per_cu};
+    PrimaryGen g;
+    const bool primary = bounce == 0u && p.primary_fused;
+    if (primary) g = PrimaryGen{f->tile, f->camera, rt_tanf(0.5f * f->camera.fov), f->sample_count, p.cur_slots, p.chunk_base, f->chunk_pixels, p.o4[0], p.d4[0]};
+    const TraceTarget t = {p.stream, p.spill, p.slow_list, 0u, p.hits, dlog(f, p), p.counters, p.batch_paths(), bounce, f->trace_variant, f->trace_waves_per_cu,
+                           primary ? &g : nullptr};
     KernelSpan span(f, 1, p.stream);
     launch_trace<false>(f, t, p.o4[in], p.d4[in], (const uint32_t*)nullptr, &p.counters->queue[bounce]);
     HIPCHK(ctx, hipGetLastError());
@@ -1648,6 +1686,7 @@ int shade_pipe(rt_frame* f, PathPipe& p, uint32_t bounce, bool count_in_ray)
     a.count_in_ray = count_in_ray ? 1u : 0u;
     a.partition = f->shade_partition;
     a.final_bounce = bounce >= f->max_bounces ? 1u : 0u;
+    const bool primary = bounce == 0u && p.primary_fused;        // (rt_integrate's batches: count_in_ray)
     uint32_t blocks = ((uint32_t)p.batch_paths() + RT_SHADE_BLOCK - 1u) / RT_SHADE_BLOCK;
     if (blocks == 0) blocks = 1;
     p.shadow_pending = true;
@@ -1657,7 +1696,9 @@ int shade_pipe(rt_frame* f, PathPipe& p, uint32_t bounce, bool count_in_ray)
     const bool blue = f->sampler == 1;   // kernel variants are AOT (the reference rebuilds with -D..., :267-285)
     const bool nee = ctx->scene.d.emissive_nee != 0;     // opt-in extension (rt_scene_desc::flags)
 #define RT_LAUNCH_SHADE(FURNACE, BLUE, NEE) \
-    do { if (f->log_ovf_blocks) hipLaunchKernelGGL((k_shade<FURNACE, BLUE, NEE, true>), dim3(blocks), dim3(RT_SHADE_BLOCK), 0, p.stream, ctx->scene.d, f->tile, a); \
+    do { if (primary && f->log_ovf_blocks) hipLaunchKernelGGL((k_shade<FURNACE, BLUE, NEE, true, true>), dim3(blocks), dim3(RT_SHADE_BLOCK), 0, p.stream, ctx->scene.d, f->tile, a); \
+         else if (primary) hipLaunchKernelGGL((k_shade<FURNACE, BLUE, NEE, false, true>), dim3(blocks), dim3(RT_SHADE_BLOCK), 0, p.stream, ctx->scene.d, f->tile, a); \
+         else if (f->log_ovf_blocks) hipLaunchKernelGGL((k_shade<FURNACE, BLUE, NEE, true>), dim3(blocks), dim3(RT_SHADE_BLOCK), 0, p.stream, ctx->scene.d, f->tile, a); \
          else hipLaunchKernelGGL((k_shade<FURNACE, BLUE, NEE, false>), dim3(blocks), dim3(RT_SHADE_BLOCK), 0, p.stream, ctx->scene.d, f->tile, a); } while (0)
     if (nee)
     {
@@ -2007,7 +2048,7 @@ int rt_integrate(rt_frame* f, uint32_t n_samples)       // n x Integrator::Integ
         for (uint32_t base = 0; base < tile_pixels(f) && rc == RT_OK; ++c)
         {
             PathPipe& p = f->ps[c % f->n_pipes];
-            if (generate_rays(f, p, batch, base, c >= f->n_pipes) != RT_OK) { rc = RT_ERROR; break; }
+            if (generate_rays(f, p, batch, base, c >= f->n_pipes, !per_frame && primary_fusable(f)) != RT_OK) { rc = RT_ERROR; break; }
             rc = trace_bounces(f, p, per_frame);
             // Compact log layout: did this sequence run the overflow pool dry?  (The one host synchronisation of a batch; the
             // full layout has none.)  If so nothing of it has reached the radiance yet: drop it, switch the frame to the full
@@ -2571,6 +2612,7 @@ int rt_frame_get_stats(rt_frame* f, rt_stats* out)
     out->log_inline_entries = f->log_ovf_blocks ? f->log_inline : 0u;
     out->log_fallbacks = f->log_fallbacks;
     out->frame_kernel_samples = (uint32_t)f->frame_launches;
+    out->fused_raygen_launches = f->fused_launches;
     out->chunk_pixels = f->chunk_pixels;
     out->pipelines = f->n_pipes;
     if (f->ahead)

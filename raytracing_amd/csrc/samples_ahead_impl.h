@@ -59,7 +59,8 @@ static bool ahead_wanted(const rt_frame* f)
 //    RT_OPT_PIPELINES, RT_OPT_STAGE_PIPES (one chunk on one stream).
 //  * DOES NOT CONCERN A BANK: RT_OPT_SAMPLES_AHEAD (the mode itself: its depth and stream bit are in the key), RT_OPT_PATH_STATE_LIMIT_MB (bounds the depth:
 //    in the key), RT_OPT_SAMPLES_IN_FLIGHT (a bank holds `depth` samples), RT_OPT_COMPACT_LOG, RT_OPT_DEBUG_LOG_POOL_DIV (a bank has no limit: full layout),
-//    RT_OPT_FRAME_KERNEL (banks trace batches), RT_OPT_DEBUG_ALLOC_LIMIT (the owner's test hook), RT_OPT_TRACE_PACKET_BOUNCES (accepts only 0).
+//    RT_OPT_FRAME_KERNEL (banks trace batches), RT_OPT_DEBUG_ALLOC_LIMIT (the owner's test hook), RT_OPT_TRACE_PACKET_BOUNCES (accepts only 0),
+//    RT_OPT_FUSED_RAYGEN (rt_integrate's batches only: a bank's batch writes its primary queue, ahead_launch).
 static const struct { int option; uint32_t rt_frame::*field; } RT_AHEAD_FOLLOWED[12] = {
     {RT_OPT_MAX_BOUNCES, &rt_frame::max_bounces}, {RT_OPT_SAMPLER, &rt_frame::sampler}, {RT_OPT_WHITE_FURNACE, &rt_frame::white_furnace},
     {RT_OPT_TRACE_DROP_LAST_BOUNCE_RAYS, &rt_frame::drop_last}, {RT_OPT_OVERLAP_SHADOW, &rt_frame::overlap_shadow}, {RT_OPT_TRACE_VARIANT, &rt_frame::trace_variant},

@@ -317,7 +317,10 @@ RT_DEV float SampleBlueNoise(const ShadeArgs& a, uint32_t px, uint32_t py, uint3
 // One queue entry of k_shade -- Miss (miss.cl:65-76) or HitSurface (hit_surface.cl:79-184) with the log entries, the deferred direct sample and the
 // BSDF sample -- as a function of its own: k_shade calls it per thread and compacts the outputs per block, k_frame (frame_kernels.h) per lane of a
 // wave that carries its own paths through the bounces.
-template <bool FURNACE, bool BLUE, bool NEE, bool COMPACT>
+// PRIMARY (RT_OPT_FUSED_RAYGEN): queue entry i of bounce 0 of an rt_integrate batch that k_raygen did not write.  Its direction and path id are where the
+// primary trace instance left them (in_d4: making them again here costs the VALU-bound kernel more than the 16 bytes it saves -- 12.9 against 12.2 ms on the
+// headline batch); its throughput is (1, 1, 1) -- x * 1.0f is x, so every product below keeps its bits -- and no entry has been logged: in_thr is not read.
+template <bool FURNACE, bool BLUE, bool NEE, bool COMPACT, bool PRIMARY = false>
 RT_DEV void shade_entry(const DScene& sc, const DTile& tile, const ShadeArgs& a, const uint32_t i, bool& want_shadow, bool& want_next, bool& no_block,
     uint32_t& next_flag, float4& sh_o, float4& sh_d, float4& nx_o, float4& nx_d, float4& nx_t, uint32_t& sh_entry)
 {
@@ -328,8 +331,10 @@ RT_DEV void shade_entry(const DScene& sc, const DTile& tile, const ShadeArgs& a,
     uint32_t slot = id / a.n_local;
     uint32_t pix = id - slot * a.n_local;
     uint32_t sample_idx = a.sample_base + slot;
-    float4 thr4 = a.in_thr[i];
-    uint32_t nlog = a.count_in_ray ? (__float_as_uint(thr4.w) & 0x7FFFFFFFu) : a.log.cnt[id];   // contributions logged so far
+    float4 thr4;
+    if constexpr (PRIMARY) thr4 = make_float4(1.0f, 1.0f, 1.0f, 0.0f);       // (count_in_ray: rt_integrate's batches)
+    else thr4 = a.in_thr[i];
+    uint32_t nlog = PRIMARY ? 0u : a.count_in_ray ? (__float_as_uint(thr4.w) & 0x7FFFFFFFu) : a.log.cnt[id];   // contributions logged so far
     // compact log: this bounce may write entries nlog and nlog + 1; those beyond the inline rows go to the path's overflow
     // block, which the previous bounce allocated (below) whenever that could happen
     uint32_t oblk = RT_EMPTY_REF;
@@ -509,7 +514,7 @@ RT_DEV void shade_entry(const DScene& sc, const DTile& tile, const ShadeArgs& a,
 // extension: DESIGN.md 7b); the other instances are the reference's estimator.
 // COMPACT: the radiance log is in its compact layout (DLog; RT_OPT_COMPACT_LOG): separate instances, so that the default ones
 // carry none of its code.
-template <bool FURNACE, bool BLUE, bool NEE = false, bool COMPACT = false>
+template <bool FURNACE, bool BLUE, bool NEE = false, bool COMPACT = false, bool PRIMARY = false>
 __global__ __launch_bounds__(RT_SHADE_BLOCK) __attribute__((amdgpu_waves_per_eu(NEE ? 5 : RT_SHADE_WAVES))) void k_shade(DScene sc, DTile tile, ShadeArgs a)
 {
     const uint32_t count = a.counters->queue[a.bounce];
@@ -564,7 +569,7 @@ __global__ __launch_bounds__(RT_SHADE_BLOCK) __attribute__((amdgpu_waves_per_eu(
     float4 sh_o = make_float4(0, 0, 0, 0), sh_d = sh_o, nx_o = sh_o, nx_d = sh_o, nx_t = sh_o;
     uint32_t sh_entry = 0;
 
-    if (active) shade_entry<FURNACE, BLUE, NEE, COMPACT>(sc, tile, a, i, want_shadow, want_next, no_block, next_flag, sh_o, sh_d, nx_o, nx_d, nx_t, sh_entry);
+    if (active) shade_entry<FURNACE, BLUE, NEE, COMPACT, PRIMARY>(sc, tile, a, i, want_shadow, want_next, no_block, next_flag, sh_o, sh_d, nx_o, nx_d, nx_t, sh_entry);
     // Compact log: the next bounce writes entries nlog, nlog + 1 -- a path that goes on and could cross the inline rows gets its
     // overflow block now (nx_t.w = its entries so far, nx_d.w = its id).  Entries so far <= 2 (bounce + 1): before that reaches
     // inline_entries - 1 no path of the launch can want one.

@@ -5,6 +5,7 @@
 // (their measurements: profiles/r01_*, r02_packet_kernel_on_coherent_bounces.log).
 #pragma once
 #include "kernels_common.h"
+#include "primary_rays.h"
 
 // ---------------------------------------------------------------------------
 // BVH traversal (trace_bvh.cl:28-211)
@@ -681,7 +682,11 @@ RT_DEV void w4_test_slots(const float4 q0, const float4 q1, const float4 q2, con
 // arrays (position p at chunk priv_first + (p >> 6) * priv_stride, slot p & 63), handed out to idle lanes in order, no atomics, nothing shared; a
 // ray the wide walk does not take (RT_SIGN_SLOW) comes back through `slow` for the caller to trace.  block_id / grid_blocks stand in for blockIdx.x /
 // gridDim.x (the kernel below passes them; a wave of k_frame passes what gives it its own spill area).
-template <bool SHADOW, int STACK, bool TIMELINE, bool TAIL, bool PRIVATE>
+// PRIMARY (RT_OPT_FUSED_RAYGEN, k_trace_w4_primary below): the closest-hit launch of bounce 0 of an rt_integrate batch.  Nothing has written its queue: a lane
+// that takes index i makes the ray k_raygen would have written there (primary_ray, primary_rays.h: the same function, the same bits) instead of loading
+// 32 bytes, and leaves d4[i] -- direction and path id -- for bounce 0's k_shade (16 bytes written where k_raygen wrote 48).  Instances of their own, so that
+// the others carry none of it.
+template <bool SHADOW, int STACK, bool TIMELINE, bool TAIL, bool PRIVATE, bool PRIMARY = false>
 RT_DEV void w4_trace_body(const DScene& sc, const float4* __restrict__ o4, const float4* __restrict__ d4,
     const uint32_t* __restrict__ aux /* shadow rays: log entry of the deferred direct sample */, const uint32_t count,
     uint32_t* __restrict__ heads,
@@ -692,8 +697,9 @@ RT_DEV void w4_trace_body(const DScene& sc, const float4* __restrict__ o4, const
     uint32_t tail_q /* loop D: with this many or fewer lanes busy and nothing to refill the others with, one fused pass serves all */,
     uint32_t chunk_refill /* chunk mode: idle lanes take the next rays of the wave's OWN chunks at once (below) */,
     uint2 (*stack)[64] /* LDS, STACK entries per lane */, const uint32_t block_id, const uint32_t grid_blocks,
-    const uint32_t priv_first, const uint32_t priv_stride)
+    const uint32_t priv_first, const uint32_t priv_stride, const PrimaryGen* primary = nullptr /* PRIMARY */)
 {
+    static_assert(!PRIMARY || (!SHADOW && !PRIVATE && !TIMELINE), "primary rays: the plain closest-hit instances");
     uint32_t* const stack32 = reinterpret_cast<uint32_t*>(&stack[0][0]);     // SHADOW: 2 * STACK entries of 4 bytes
     // spill area: plain (cached) stores; the loads go through spill_load*: written in C they are folded with the LDS side
     // of the pop into one flat_load on a selected generic address, and the common LDS pop loses its ds_read_b64
@@ -948,7 +954,9 @@ RT_DEV void w4_trace_body(const DScene& sc, const float4* __restrict__ o4, const
                 bool slow = false;
                 if (ref == RT_IDLE_REF && ray_i != RT_INVALID_ID)
                 {
-                    const float4 q0 = q_load(o4 + ray_i), q1 = q_load(d4 + ray_i);
+                    float4 q0, q1;
+                    if constexpr (PRIMARY) { primary_ray(*primary, ray_i, q0, q1); q_store(primary->d4 + ray_i, q1); }   // (direction + path id: bounce 0's k_shade reads them)
+                    else { q0 = q_load(o4 + ray_i); q1 = q_load(d4 + ray_i); }
                     if (SHADOW) { payload = __float_as_uint(q1.w); log_entry = aux[ray_i]; }
                     org = F3(q0.x, q0.y, q0.z);
                     dir = F3(q1.x, q1.y, q1.z);
@@ -965,6 +973,8 @@ RT_DEV void w4_trace_body(const DScene& sc, const float4* __restrict__ o4, const
                     slow = (sign_bits & RT_SIGN_SLOW) != 0u ||
                            !(hw_max3(__builtin_fabsf(org.x), __builtin_fabsf(org.y), __builtin_fabsf(org.z)) < 0x1p29f);
                     if (!slow) ref = entry_ref;
+                    // PRIMARY: k_trace2 reads the rays of its list by index -- this one is written out for it after all
+                    if constexpr (PRIMARY) if (slow) primary->o4[ray_i] = q0;
                 }
                 // rays this kernel does not take: hand their queue index to the BVH2 kernel's list
                 const unsigned long long slow_m = __ballot(slow);
@@ -1086,4 +1096,16 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(TAIL ? 7 : 4
     __shared__ uint2 stack[STACK][64];
     w4_trace_body<SHADOW, STACK, TIMELINE, TAIL, false>(sc, o4, d4, aux, *count_ptr, heads, hits, log, spill, tune, slow_list, slow_count, stat_counts, timeline,
         timeline_slot, chunk_below, tail_q, chunk_refill, stack, blockIdx.x, gridDim.x, 0u, 0u);
+}
+
+// RT_OPT_FUSED_RAYGEN: the closest-hit launch of bounce 0 of an rt_integrate batch, which makes its primary rays itself (w4_trace_body, PRIMARY).  The plain
+// and the loop-D instance of the 12-entry stack, as launch_trace_w4 picks them.
+template <bool TAIL>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(7, 8))) void k_trace_w4_primary(DScene sc, PrimaryGen primary,
+    const uint32_t* __restrict__ count_ptr, uint32_t* __restrict__ heads, float4* __restrict__ hits, uint2* __restrict__ spill, uint32_t tune,
+    uint32_t* __restrict__ slow_list, uint32_t* __restrict__ slow_count, uint32_t* __restrict__ stat_counts, uint32_t chunk_below, uint32_t tail_q, uint32_t chunk_refill)
+{
+    __shared__ uint2 stack[12][64];
+    w4_trace_body<false, 12, false, TAIL, false, true>(sc, nullptr, nullptr, nullptr, *count_ptr, heads, hits, DLog{}, spill, tune, slow_list, slow_count, stat_counts, nullptr,
+        0u, chunk_below, tail_q, chunk_refill, stack, blockIdx.x, gridDim.x, 0u, 0u, &primary);
 }
