@@ -46,6 +46,7 @@ def hipcc():
 # side of the tree work.  The scene queries are split the same way twice over: each family's kernels and launch driver are a unit with a code object of its own, and
 # the C entry points of all eight are one host-only unit (scene_queries.cpp, on context.h), so neither a kernel nor an entry point's bookkeeping rebuilds the hot path.
 # The scene side -- upload, tree choice, the adaptation's worker, refit, pose and the tree work's debug forms -- is a host-only unit too (scene_upload.cpp).
+# So are the two things that work on a frame without tracing a sample: the filters' entry points (frame_filters.cpp) and the kernel-less readers (frame_readers.cpp), on frame.h.
 HIP_UNITS = [
     ("rt_hip", "rt_hip.hip", True),            # C-ABI, frames, launch logic + kernels.h (the hot path)
     ("device_fold", "device_fold.hip", True),  # fold_kernels.h + its host driver
@@ -62,7 +63,9 @@ HIP_UNITS = [
     ("all_hits", "all_hits.hip", True),        # every surface a caller-supplied ray crosses, counted and sorted: kernels on walk_kernels.h + host driver on query.hip's core + the host's brute force (a code object of its own)
     ("scene_queries", "scene_queries.cpp", False),   # the C entry points of the eight query families above (rt_scene_trace* .. rt_scene_separation*, their rt_debug_* forms) on context.h: an edit to a query's bookkeeping rebuilds no kernel (no device code)
     ("scene_upload", "scene_upload.cpp", False),     # rt_scene_upload and its stages, tree choice, FoldAdapt's worker, rt_scene_refit* / set_objects / pose / export_folds / import_folds / tree_report, the tree work's rt_debug_* forms, on context.h + fold_adapt.h (no device code)
-    ("wide_bvh", "wide_bvh.cpp", False),       # build_wide_bvh, pair layout, the adaptation's host walks (no device code)
+    ("frame_filters", "frame_filters.cpp", False),   # the spatial and temporal filters' entry points on a frame and on caller arrays (rt_frame_filter* .. rt_frame_read_guide_motion, rt_debug_filter*, rt_debug_guide_motion) and the three states a filtered frame keeps, on frame.h + filters_host.h (no device code)
+    ("frame_readers", "frame_readers.cpp", False),   # the frame's readers that launch no kernel: rt_frame_read_radiance / copy_radiance / get_profile and the rt_frame_debug_* readers, on frame.h (no device code)
+    ("wide_bvh", "wide_bvh.cpp", False),     # build_wide_bvh, pair layout, the adaptation's host walks (no device code)
 ]
 
 

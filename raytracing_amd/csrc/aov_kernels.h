@@ -7,13 +7,7 @@
 // AOVs, temporal denoiser, resolve (aov.cl, denoiser.cl, resolve_radiance.cl)
 // Interactive per-frame features: one sample in flight, whole image on one GPU.
 // ---------------------------------------------------------------------------
-struct DAov
-{
-    float4* diffuse_albedo;   // float3 in the reference (16 B)
-    float* depth;
-    float4* normal;
-    float2* velocity;
-};
+// (DAov, the four AOV images: device_scene.h)
 
 // the AOV resets of RayGeneration (raygeneration.cl:129-132)
 __global__ __launch_bounds__(256) void k_aov_clear(DAov aov, uint32_t n)

@@ -2,8 +2,9 @@
 // uploaded scene and its trees, the context and the buffer records behind the C-ABI's opaque handles, how an entry point fails, and the device copies an
 // upload makes.  Internal: never installed, never included by include/.  A feature unit gets the scene (ctx->scene: the kernels' view `d`, the trees, the
 // objects' table), the queries' scratch areas, the stream, the device and its properties.  It may ask for everything in flight to drain before it frees or
-// rewrites what a launch could still read (quiesce).  It still cannot see a frame -- rt_frame is rt_hip.hip's alone, and so are sync_frame_streams and
-// ahead_discard, which quiesce calls there -- nor the fold adaptation's state, which is a name only here (fold_adapt.h, for the two units that work on it).
+// rewrites what a launch could still read (quiesce).  It cannot see a frame through this header: what a frame is, for the units that implement entry points
+// on one, is frame.h's (quiesce itself stays rt_hip.hip's, with ahead_discard, which it calls there) -- nor the fold adaptation's state, which is a name only
+// here (fold_adapt.h, for the two units that work on it).
 #pragma once
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>

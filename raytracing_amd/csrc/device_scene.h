@@ -1,6 +1,7 @@
 // device_scene.h -- DScene, the kernels' view of an uploaded scene: the record every launch receives by value.  Apart from kernels_common.h (which
 // includes it) so that host translation units that hold one (context.h: Scene::d) need no device code and compile as plain C++.  With it, for the same
-// reason, the two other things of the kernels' that the scene's host unit reads: DCounters and the re-layout kernels' error codes.
+// reason, the two other things of the kernels' that the scene's host unit reads -- DCounters and the re-layout kernels' error codes -- and the plain records
+// a frame holds (DTile, DLog, DAov) with the sizes its buffers are made by, for frame.h.
 #pragma once
 #include <hip/hip_vector_types.h>
 #include <stdint.h>
@@ -62,6 +63,42 @@ struct DCounters                  // one per frame, device memory
     unsigned long long tl_exit_hist[64];
     // compact radiance log (DLog): next free overflow block of the batch in flight, and "the pool ran dry"
     uint32_t log_ovf_next[RT_LOG_SUBPOOLS], log_ovf_flag;
+};
+
+// The plain records a frame holds or hands to its launches, and the four sizes its buffers are made by: here so that frame.h -- what a frame is, for the host
+// units that implement entry points on one (frame_filters.cpp, frame_readers.cpp) -- needs no device code either.  What the kernels do with them stays with
+// the kernels: log_index and log_put, tile_global_row (kernels_common.h).
+#define RT_TRACE_STACK_LDS 24     // per-lane stack entries kept in LDS
+#define RT_TRACE_STACK_MAX 64     // the reference's nodesToVisit[64] (trace_bvh.cl:142)
+#define RT_W4_STACK_MAX 104               // <= 3 pending slots per wide level, <= 33 wide levels + slack
+#define RT_FRAME_COUNT_STRIDE 136u       // per-wave row: [0..63] closest rays per bounce, [64..127] shadow rays per bounce, [128] spills, [129] slow rays, [130] scratch,
+                                         // [131..134] the wave's 100 MHz ticks in the closest walks / shading / shadow walks / in all (rt_frame_debug_frame_rows)
+
+// Where the entries of a path's radiance log live (the two layouts: kernels_common.h, above log_index)
+struct DLog
+{
+    float* rlog;                  // 3 floats per entry
+    uint32_t* cnt;                // entries of path id (k_flush replays that many)
+    uint32_t* ovf_slot;           // compact: the overflow block of path id (RT_EMPTY_REF: none); nullptr in the full layout
+    uint32_t stride;              // paths per row
+    uint32_t inline_entries;
+    uint32_t ovf_blocks;
+};
+
+struct DTile                      // which pixels of the full image this frame owns
+{
+    uint32_t width, height;       // full image
+    uint32_t band_h, rank, nranks;
+    uint32_t local_rows;
+};
+
+// the four AOV images (aov_kernels.h)
+struct DAov
+{
+    float4* diffuse_albedo;   // float3 in the reference (16 B)
+    float* depth;
+    float4* normal;
+    float2* velocity;
 };
 
 // What the re-layout kernels (relayout_kernels.h) report of the caller's arrays, the first one wins; decoded by the host (Upload::relayout_on_device, scene_upload.cpp).

@@ -1,7 +1,7 @@
 // filters_host.h -- the interface of filters.hip: the guide pass's ray generation and guide values, the spatial filter's a-trous passes and the
 // temporal filter's stages on the device, and their host restatements (rt_frame_filter, rt_frame_read_guides, rt_debug_filter,
-// rt_frame_filter_temporal, rt_debug_filter_temporal in rt_hip.hip).  A translation unit of its own, like device_fold.hip: the hot path's code
-// object (rt_hip.hip) is neither rebuilt nor re-hashed by the filters.
+// rt_frame_filter_temporal, rt_debug_filter_temporal in frame_filters.cpp; the pose a refit replaces in scene_upload.cpp).  A translation unit of its own,
+// like device_fold.hip: the hot path's code object (rt_hip.hip) is neither rebuilt nor re-hashed by the filters.
 #pragma once
 #include <hip/hip_runtime_api.h>
 #include <hip/hip_vector_types.h>

@@ -14,8 +14,7 @@
 #include "trace_kernels.h"
 #include "shade_kernels.h"
 
-#define RT_FRAME_COUNT_STRIDE 136u       // per-wave row: [0..63] closest rays per bounce, [64..127] shadow rays per bounce, [128] spills, [129] slow rays, [130] scratch,
-                                         // [131..134] the wave's 100 MHz ticks in the closest walks / shading / shadow walks / in all (rt_frame_debug_frame_rows)
+// (RT_FRAME_COUNT_STRIDE, the words of a per-wave row and what they hold: device_scene.h)
 
 struct FrameArgs
 {

@@ -41,8 +41,7 @@
 
 #define RT_LEAF_BIT 0x80000000u
 #define RT_EMPTY_REF 0xFFFFFFFFu
-#define RT_TRACE_STACK_LDS 24     // per-lane stack entries kept in LDS
-#define RT_TRACE_STACK_MAX 64     // the reference's nodesToVisit[64] (trace_bvh.cl:142)
+// (RT_TRACE_STACK_LDS, RT_TRACE_STACK_MAX: device_scene.h, where the frame's host units size the spill areas by them)
 // A shadow ray carries its path id in direction.w and the radiance-log entry of its deferred direct sample in sh_aux.
 
 // one entry of the radiance log: RGB, 12 bytes (global_load/store_dwordx3)
@@ -70,16 +69,7 @@ RT_DEV void q_store(float4* p, const float4& v) { const rt_v4f t = {v.x, v.y, v.
 // inline_entries .. 2 (B + 1) - 1 from a bump-allocated pool of ovf_blocks blocks (k_shade, one bounce ahead, one atomic per
 // 512-path block): entry k >= inline_entries of a path with block `slot` at inline_entries * stride + (k - inline_entries) *
 // ovf_blocks + slot.  A pool that runs dry raises DCounters::log_ovf_flag; the host then discards the batch and repeats it in
-// the full layout (rt_integrate), so the sum is exact either way.
-struct DLog
-{
-    float* rlog;                  // 3 floats per entry
-    uint32_t* cnt;                // entries of path id (k_flush replays that many)
-    uint32_t* ovf_slot;           // compact: the overflow block of path id (RT_EMPTY_REF: none); nullptr in the full layout
-    uint32_t stride;              // paths per row
-    uint32_t inline_entries;
-    uint32_t ovf_blocks;
-};
+// the full layout (rt_integrate), so the sum is exact either way.  (The record itself, DLog: device_scene.h.)
 // index of entry k of path id (in entries), or ~0 when the entry has no home (pool dry: the batch is being discarded)
 RT_DEV size_t log_index(const DLog& L, uint32_t k, uint32_t id, uint32_t slot)
 {
@@ -93,13 +83,7 @@ RT_DEV void log_put(const DLog& L, uint32_t k, uint32_t id, uint32_t slot, float
     if (i != ~(size_t)0) log_store(L.rlog, i, x, y, z);
 }
 
-struct DTile                      // which pixels of the full image this frame owns
-{
-    uint32_t width, height;       // full image
-    uint32_t band_h, rank, nranks;
-    uint32_t local_rows;
-};
-
+// (DTile, which pixels of the full image a frame owns: device_scene.h)
 RT_DEV uint32_t tile_global_row(const DTile& t, uint32_t ly)
 {
     uint32_t band = ly / t.band_h;

@@ -20,323 +20,26 @@
 #include "kernels.h"
 #include <chrono>
 #include "wide_bvh.h"        // truncated_walks_exchange, for the adaptation's report line (wide_bvh.cpp)
-#include "filters_host.h"        // the filters' guide pass, a-trous passes and temporal stages (filters.hip)
 #include "query_host.h"      // the queries' scratch areas and the ray through a pixel, for rt_frame_pick and rt_frame_pick_all (query.hip)
 #include "bake_host.h"       // bake::CHUNK_POINTS, for RT_CTX_OPT_BAKE_CHUNK_POINTS (bake.hip)
 #include "region_host.h"     // the region of a pixel rectangle, for rt_frame_pick_rect (region.hip)
-#include "device_memory.h"   // who owns a device allocation: dev::Mem, dev::Temps
+#include "device_memory.h"   // who owns a device allocation: dev::Mem
 #include "context.h"         // Scene, rt_ctx, rt_buffer, fail / HIPCHK: what this unit shares with the feature units that implement entry points (scene_upload.cpp, scene_queries.cpp)
+#include "frame.h"           // rt_frame, its pipes, banks and buffer lists, and what the frames' feature units call here (frame_filters.cpp, frame_readers.cpp): namespace frame
 #include "fold_adapt.h"      // FoldAdapt, for the render thread's side of the adaptation (fold_hooks_impl.h); the upload's side and the worker: scene_upload.cpp
 using namespace rtw;
 using namespace context;
+using namespace frame;
 
 namespace
 {
 thread_local std::string g_thread_error;
 } // namespace
 
-// An owner's device buffers: each one's address and size (clear: it starts from zero).  An owner lists them once (buffers()), for the allocation and for the free.
-struct DevBuf { void** p; size_t bytes; bool clear = false; };
-static size_t total_bytes(const std::vector<DevBuf>& bufs) { size_t n = 0; for (const DevBuf& b : bufs) n += b.bytes; return n; }
-static void free_buffers(const std::vector<DevBuf>& bufs)
-{
-    for (const DevBuf& b : bufs) if (*b.p) { (void)hipFree(*b.p); *b.p = nullptr; }
-}
-// a new state S with every buffer of s->buffers(sizes...) allocated, or nullptr with everything freed again if one allocation fails
-template <class S, class... Sizes> static S* alloc_state(Sizes... sizes)
-{
-    S* s = new S();
-    const std::vector<DevBuf> bufs = s->buffers(sizes...);
-    for (const DevBuf& b : bufs)
-        if (hipMalloc(b.p, b.bytes) != hipSuccess)
-        {
-            (void)hipGetLastError();
-            free_buffers(bufs);
-            delete s;
-            return nullptr;
-        }
-    return s;
-}
-template <class S> static void free_state(S*& s)
-{
-    if (!s) return;
-    free_buffers(s->buffers());
-    delete s;
-    s = nullptr;
-}
-
-#define RT_MAX_PIPES 4
-// Per-path state of one chunk in flight and the stream its launches go to (see rt_frame::ps).
-struct PathPipe
-{
-    hipStream_t stream = nullptr;      // pipe 0: the context's stream; others: their own
-    hipEvent_t done = nullptr;         // cross-stream ordering (fork_pipes / join_pipes)
-    // ray queues (ping-pong), hits, shadow queue
-    float4* o4[2] = {nullptr, nullptr}; float4* d4[2] = {nullptr, nullptr};
-    float4* thr[2] = {nullptr, nullptr};
-    float4* hits = nullptr;
-    // shadow queue, two of them: bounce b fills [b & 1] while the shadow trace of bounce b - 1 may still read the other
-    float4* sh_o4[2] = {nullptr, nullptr}; float4* sh_d4[2] = {nullptr, nullptr}; uint32_t* sh_aux[2] = {nullptr, nullptr};
-    // the shadow trace's own stream (rt_integrate: it runs beside the next bounce's closest-hit trace and k_shade,
-    // filling the tail of one and the ramp of the other), its spill area and slow-ray list
-    hipStream_t side = nullptr;
-    hipEvent_t ev_shaded = nullptr, ev_shadow[2] = {nullptr, nullptr};
-    bool shadow_in_flight[2] = {false, false};   // ev_shadow[i] recorded and not yet waited for by the main stream
-    uint2* sh_spill = nullptr;
-    uint32_t* sh_slow_list = nullptr;
-    // radiance log (kernels_common.h header): cnt[id], rlog[entry][id]; id < slots * chunk_pixels
-    float* rlog = nullptr; uint32_t* cnt = nullptr;   // rlog: 3 floats per entry
-    uint32_t* ovf_slot = nullptr;      // compact log layout: a path's overflow block (DLog, kernels_common.h)
-    uint32_t* slow_list = nullptr;     // queue indices k_trace_w4 leaves to k_trace2 (one per path)
-    DCounters* counters = nullptr;
-    uint2* spill = nullptr;
-    uint32_t cur_slots = 0;            // slots used by the batch in flight on this pipe (0 = nothing pending)
-    uint32_t chunk_base = 0;           // first local pixel of the chunk in flight
-    uint32_t chunk_count = 0;          // pixels of the chunk in flight
-    uint32_t prev_bounces = 0;
-    uint32_t fold_accumulates = 0;     // the sequence in flight is a 2nd+ chunk of its batch: its counters ADD to last_*
-    bool shadow_pending = false;       // rt_shade issued, rt_intersect_shadow not yet
-    bool primary_fused = false;        // RT_OPT_FUSED_RAYGEN: the batch in flight has no bounce-0 queue in memory: its bounce-0 trace and shade launches make the primary rays (generate_rays)
-    uint64_t batch_paths() const { return (uint64_t)chunk_count * (cur_slots ? cur_slots : 1u); }   // paths of the batch in flight (a trace launch's size class)
-    // The per-path buffers for `paths` paths in flight and a log of `log_elems` entries, in the order they are allocated (alloc_path_buffers /
-    // free_path_buffers; no arguments: all of them, for the free).  The queues carry 4 elements of padding, the slow lists 64, the log 16 bytes;
-    // ovf_slot exists in the compact layout only.  RT_PATH_FIXED_BYTES is this list without the log and ovf_slot, per path.
-    std::vector<DevBuf> buffers(size_t paths = 0, size_t log_elems = 0, bool compact = true)
-    {
-        const size_t q = (paths + 4) * sizeof(float4), w = (paths + 4) * sizeof(uint32_t), slow = (paths + 64) * sizeof(uint32_t);
-        std::vector<DevBuf> b = {{(void**)&o4[0], q}, {(void**)&o4[1], q}, {(void**)&d4[0], q}, {(void**)&d4[1], q}, {(void**)&thr[0], q}, {(void**)&thr[1], q},
-            {(void**)&hits, q}, {(void**)&sh_o4[0], q}, {(void**)&sh_d4[0], q}, {(void**)&sh_o4[1], q}, {(void**)&sh_d4[1], q}, {(void**)&sh_aux[0], w},
-            {(void**)&sh_aux[1], w}, {(void**)&rlog, log_elems * 3u * sizeof(float) + 16u}};
-        if (compact) b.push_back({(void**)&ovf_slot, w});
-        b.insert(b.end(), {DevBuf{(void**)&cnt, paths * sizeof(uint32_t)}, DevBuf{(void**)&slow_list, slow}, DevBuf{(void**)&sh_slow_list, slow}});
-        return b;
-    }
-    // what a pipe keeps for the frame's life (ensure_pipe_resources); its streams have drained.  Pipe 0's stream is borrowed: never destroyed.
-    void destroy(bool own_stream)
-    {
-        for (void* m : {(void*)counters, (void*)spill, (void*)sh_spill}) if (m) (void)hipFree(m);
-        for (hipEvent_t e : {done, ev_shaded, ev_shadow[0], ev_shadow[1]}) if (e) (void)hipEventDestroy(e);
-        if (side) (void)hipStreamDestroy(side);
-        if (own_stream && stream) (void)hipStreamDestroy(stream);
-    }
-};
-#define RT_PATH_FIXED_BYTES (11u * 16u + 5u * 4u)   // ray queues o4, d4, thr (x2), hits, shadow queue o4, d4 (x2) = 11 x 16; sh_aux (x2), cnt, two slow lists = 5 x 4
-
-// RT_OPT_SAMPLES_AHEAD: samples of the stage API traced ahead of the caller's Integrate() calls (below, "samples ahead").  A BANK is a frame of its
-// own -- same tile, same options, its own per-path buffers -- that holds one batch; two banks, so that one computes while the other is consumed.
-struct AheadBank
-{
-    rt_frame* h = nullptr;
-    uint32_t base = 0, n = 0, next = 0;     // holds samples base .. base + n - 1; slots < next have reached the owner's radiance
-    hipEvent_t done = nullptr;              // the batch's last launch (the bank's stream, after its side stream has been joined)
-    hipEvent_t order = nullptr;             // what the bank's stream waits for before it starts another batch: the owner's last replay of the old one
-};
-// what a bank is made for: a change in any of the sixteen makes the banks over (ahead_key / ahead_configure, samples_ahead_impl.h)
-struct AheadKey
-{
-    uint32_t followed[12] = {};             // the options of RT_AHEAD_FOLLOWED, in its order
-    uint32_t small_launch = 0, tail_paths = 0;   // RT_OPT_SMALL_LAUNCH_PATHS (unset: 0xFFFFFFFF), RT_OPT_TRACE_TAIL_PATHS
-    uint32_t depth = 0;                     // samples per batch (ahead_depth)
-    uint32_t two_streams = 0;               // RT_OPT_SAMPLES_AHEAD + 256: one stream per bank
-};
-struct Ahead
-{
-    AheadBank bank[2];
-    hipStream_t stream[2] = {nullptr, nullptr};
-    uint32_t quiet = 0;                     // samples advanced since the last reset / discard
-    uint32_t depth = 0, last_n = 0;         // the most samples a batch holds (resolved for this tile); the latest batch's size (the ramp: 2, 4, .. depth)
-    bool configured = false;
-    AheadKey mirrored;                      // the owner's options as the banks have them
-    rt_camera camera;                       // what the batches in flight were traced for
-    uint64_t scene = 0;
-    uint64_t launched = 0, consumed = 0, discarded = 0;   // samples
-};
-
-struct rt_frame
-{
-    rt_ctx* ctx;
-    DTile tile;
-    uint32_t n_local;
-    float4* radiance = nullptr; float4* resolved = nullptr;
-    // rt_frame_present: the resolved image goes to the host on a stream of its own while the next frame is traced
-    float4* resolved_b = nullptr;      // the second device image (double buffering)
-    hipStream_t present_stream = nullptr;
-    hipEvent_t ev_resolved[2] = {nullptr, nullptr}, ev_copied[2] = {nullptr, nullptr};
-    uint32_t present_flip = 0;
-    bool present_pending = false;
-    // Per-path state lives in PIPES (PathPipe): the tile is cut into chunks of pixels and chunk c travels through
-    // the wavefront loop on pipe c % n_pipes, each pipe on its own HIP stream.  One chunk on one pipe is the plain
-    // case.  More pipes let chunks overlap; measured on MI355X this does NOT pay (a trace launch costs ~0.8 ms
-    // beyond its rays whatever shares the machine with it: profiles/r02_pipelines_sweep.log), so the default is 1.
-    PathPipe ps[RT_MAX_PIPES];
-    uint32_t pipelines = 1;        // RT_OPT_PIPELINES: pipes rt_integrate may use
-    uint32_t stage_pipes = 1;      // RT_OPT_STAGE_PIPES: ONE sample per pixel in flight (the stage API, rt_integrate(f, 1): the reference's frame-by-frame
-                                   // pattern) is cut into this many chunks, each on a pipe (stream) of its own: every launch of that pattern is
-                                   // its own tail, and the chunks' tails overlap
-    uint32_t stage_chunks = 1;     // pipes holding a chunk of the stage API's sample in flight (set by rt_generate_rays)
-    // RT_OPT_FRAME_KERNEL: the stage API's sample as ONE launch (k_frame, frame_kernels.h).  The stage calls of a sample are only RECORDED
-    // while they come in the canonical order; rt_advance_sample launches the kernel.  Anything that needs the state between two stages
-    // (a debug reader, the radiance mid-sample, another order of calls) first replays the recorded stages with the stage kernels.
-    uint32_t frame_kernel = 0;
-    struct { bool active = false; uint32_t bounce = 0; int next = 0; bool ahead = false; } deferred;   // next: 0 = rt_intersect(bounce), 1 = rt_shade, 2 = rt_intersect_shadow;
-                                                                                                      // ahead: the sample is in a bank (RT_OPT_SAMPLES_AHEAD)
-    uint32_t ahead_opt = 0;            // RT_OPT_SAMPLES_AHEAD
-    Ahead* ahead = nullptr;            // ... its banks (made when the first batch is launched)
-    rt_frame* ahead_owner = nullptr;   // this frame IS a bank of that frame
-    struct KFrame                      // k_frame's grid and its buffers, all three or none (blocks != 0: they exist)
-    {
-        uint32_t* counts = nullptr; uint32_t* slow = nullptr;                      // per-wave rows and slow-ray lists
-        uint2* spill = nullptr;                                                    // ... and its blocks' stack spill area
-        uint32_t blocks = 0;
-        std::vector<DevBuf> buffers(size_t n_blocks = 0, size_t chunks_per_wave = 0)
-        {
-            return {{(void**)&counts, n_blocks * RT_FRAME_COUNT_STRIDE * sizeof(uint32_t)}, {(void**)&slow, n_blocks * chunks_per_wave * 64u * sizeof(uint32_t)},
-                    {(void**)&spill, n_blocks * 64u * (RT_W4_STACK_MAX - 12) * sizeof(uint2)}};
-        }
-        void release() { free_buffers(buffers()); blocks = 0; }
-    } kf;
-    uint32_t frame_chunks_per_wave = 0;
-    uint64_t fused_launches = 0;                                                   // RT_OPT_FUSED_RAYGEN: k_raygen launches that ran their prologue only (rt_stats)
-    uint64_t frame_launches = 0;                                                   // samples rendered by k_frame so far (rt_stats)
-    // RT_OPT_FRAME_KERNEL = 255: the choice is MEASURED -- k_frame wins by 1.4 - 1.8 x on scenes of up to ~1 M triangles and loses 7 - 10 % on the 2.8 M /
-    // 10 M ones (profiles/r05_call13.log), so the first frames of a scene time both: frames 0 - 1 (stage kernels) and 2 - 3 (k_frame) warm up, frames 4 - 19
-    // ALTERNATE between the two (the device's clocks ramp over a process's first frames: timed in two blocks, whichever came second looked faster --
-    // rt_render --frames chose k_frame for the 2.8 M-triangle scene, profiles/r05_call18.log) with HIP events around each frame's launches on the frame's
-    // stream, read once the last has completed; then the faster way stays.
-    struct { int frames = 0, timing = -1; bool decided = false, use_kernel = false, skip = false; uint64_t scene = 0; hipEvent_t ev[16][2] = {}; float ms_stage = 0.0f, ms_kernel = 0.0f; } fk_auto;
-    uint32_t n_pipes = 1;          // pipes the current allocation holds
-    uint32_t slots = 1;            // samples traced concurrently (resolved from slots_opt)
-    uint32_t slots_opt = 0;        // RT_OPT_SAMPLES_IN_FLIGHT as set by the caller (0 = auto)
-    uint32_t slots_limit = 0;      // != 0: a larger batch did not fit into device memory
-    bool reserved_explicitly = false;  // rt_frame_reserve_samples has been called: rt_integrate does not second-guess the buffers' size
-    uint64_t samples_asked = 0;        // samples rt_integrate has been asked for since the frame was made (lean growth of the buffers)
-    uint32_t log_stride = 0;       // elements per log entry row = slots * chunk_pixels
-    // Chunks also bound memory: RT_OPT_PATH_STATE_LIMIT_MB caps the per-path buffers of all pipes together
-    // (path ids are chunk-relative, the radiance log is replayed per chunk).
-    uint32_t chunk_pixels = 0;     // pixels per chunk as allocated (n_local when the tile is not chunked)
-    uint32_t state_limit_mb = 0;   // RT_OPT_PATH_STATE_LIMIT_MB (0 = only the built-in 144 GB rule)
-    uint32_t log_entries = 0;      // entries a path may log: 2 * (max_bounces + 1)
-    // Radiance-log layout (DLog): compact = log_inline rows for every path + a pool of log_ovf_blocks overflow blocks;
-    // full = every row for every path (log_inline == log_entries, no pool).
-    uint32_t log_inline = 0, log_ovf_blocks = 0;
-    uint32_t compact_log_opt = 2;  // RT_OPT_COMPACT_LOG: 0 = always the full layout, 1 = compact for batches of >= 8 samples in flight,
-                                   // 2 (default) = compact when the caller bounds the path state (RT_OPT_PATH_STATE_LIMIT_MB)
-    uint32_t log_pool_div = 8;     // the pool holds paths / log_pool_div blocks (RT_OPT_DEBUG_LOG_POOL_DIV: test hook)
-    bool log_full_forced = false;  // a batch ran its pool dry: this frame stays on the full layout (until bounces / scene change)
-    uint32_t fallback_limit_mb = 0;   // ... within the bytes the compact layout held (chunk_plan)
-    uint32_t log_fallbacks = 0;    // batches repeated in the full layout
-    uint32_t trace_blocks;       // v1 grid
-    uint32_t trace_variant = 5;  // RT_OPT_TRACE_VARIANT (5 = auto)
-    uint64_t small_launch_paths = 3000000ull;   // RT_OPT_SMALL_LAUNCH_PATHS: launches of fewer rays run k_trace_w4 in chunk mode
-    bool small_launch_set = false;              // ... set by the caller (otherwise the loop-D instance uses 8 M: launch_trace_w4)
-    uint32_t trace_waves_per_cu = 0;   // RT_OPT_TRACE_WAVES_PER_CU (0 = LDS-limited residency)
-    uint32_t chunk_refill = 1;                 // RT_OPT_CHUNK_REFILL: chunk mode refills idle lanes from the wave's own chunks
-    uint32_t fused_raygen = 1;                 // RT_OPT_FUSED_RAYGEN: rt_integrate's bounce-0 launches make their primary rays themselves (primary_fusable)
-    uint64_t trace_tail_paths = 100000000ull; // RT_OPT_TRACE_TAIL_PATHS: batches of fewer paths launch the instance with loop D and refilled chunks (8 / 16 / 32 / 64 /
-                                              // 128 samples of a 1080p frame in flight: +8 / +5 / +2.3 / -1.6 / -2.8 %, profiles/r04_call20_21.log, r04_call22.log)
-    uint32_t trace_tail_lanes = 40;    // RT_OPT_TRACE_TAIL_LANES: k_trace_w4's loop D (0 = off); sweep: profiles/r04_call04_kernel_ab.log
-    uint32_t select_form_box = 0;      // RT_OPT_TRACE_SELECT_FORM_BOX: every ray takes the select-form slab test
-    uint32_t trace_tune = 0;           // RT_OPT_TRACE_TUNE: k_trace2 loop thresholds (0 = defaults)
-    uint32_t timeline = 0;             // rt_frame_debug_timeline armed: k_trace_w4<closest> records its launch timeline
-    uint32_t overlap_shadow = 1;       // RT_OPT_OVERLAP_SHADOW
-    bool side_active = false;          // shadow traces go to PathPipe::side (what the last shade step decided, side_on(): it holds until that bounce's shadow trace)
-    uint32_t shade_partition = 3;      // RT_OPT_SHADE_PARTITION: bit 0: k_shade sorts each block's entries hits first / misses last; bit 1: groups its output rays by octant
-    uint32_t debug_alloc_limit = 0;    // RT_OPT_DEBUG_ALLOC_LIMIT: allocations above this many samples in flight fail
-    // integrator state
-    rt_camera camera;
-    rt_camera camera_last;        // Integrator::prev_camera_ (integrator.hpp:89)
-    rt_camera prev_camera;        // the kPrevCamera argument bound by the last rt_set_camera
-    uint32_t sampler = 0;         // RT_OPT_SAMPLER: 0 kRandom, 1 kBlueNoise
-    uint32_t aov = 0;             // RT_OPT_AOV
-    uint32_t denoiser = 0;        // RT_OPT_DENOISER
-    DAov aov_buf = {nullptr, nullptr, nullptr, nullptr};
-    float4* prev_radiance = nullptr; float* prev_depth = nullptr;
-    uint32_t max_bounces = 3;
-    uint32_t white_furnace = 0;
-    uint32_t drop_last = 1;
-    uint32_t sample_count = 0;
-    // RT_OPT_PROFILE_KERNELS
-    uint32_t profile = 0;
-    struct Span { hipEvent_t a, b; int cls; };
-    std::vector<Span> spans;
-    std::vector<hipEvent_t> event_pool;
-    struct SfGuides* sf = nullptr;     // rt_frame_filter / rt_frame_read_guides: the guide pass's buffers and what they were made for (made on first use)
-    struct TfState* tf = nullptr;      // rt_frame_filter_temporal: the history (made on first use)
-    struct SfMotion* sm = nullptr;     // RT_CTX_OPT_REFIT_MOTION: where each first hit was before the last refit (made on first use)
-    // the images a frame is made with, n pixels each (the radiance and the resolved image are written before they are read: rt_reset, rt_frame_resolve)
-    std::vector<DevBuf> images(size_t n = 0)
-    {
-        return {{(void**)&radiance, n * sizeof(float4)}, {(void**)&resolved, n * sizeof(float4)}, {(void**)&aov_buf.diffuse_albedo, n * sizeof(float4), true},
-                {(void**)&aov_buf.depth, n * sizeof(float), true}, {(void**)&aov_buf.normal, n * sizeof(float4), true}, {(void**)&aov_buf.velocity, n * sizeof(float2), true},
-                {(void**)&prev_radiance, n * sizeof(float4), true}, {(void**)&prev_depth, n * sizeof(float), true}};
-    }
-};
-
-// the tile's pixels, at least 1: a rank may hold no row of a small image, and buffers, grids and chunks are sized for one pixel then
-static uint32_t tile_pixels(const rt_frame* f) { return f->n_local ? f->n_local : 1u; }
-
-static int sync_frame_streams(rt_frame* f);
 static void ahead_discard(rt_frame* f);      // RT_OPT_SAMPLES_AHEAD: whatever was traced ahead is dropped (reset, another camera, another option, a peek)
 static void ahead_destroy(rt_frame* f);
 static bool ahead_wanted(const rt_frame* f);
 static int ahead_holds(const rt_frame* f, uint32_t sample);
-
-// The spatial filter's state on a frame (rt_frame_filter, rt_frame_read_guides): made on first use, freed by rt_frame_destroy.  Its own rays, hits,
-// counter and spill area: batches traced ahead (RT_OPT_SAMPLES_AHEAD) may be using the frame's per-path buffers on other streams.  After the guide
-// pass o4 / d4 are free again and serve as the a-trous passes' two ping-pong images.  80 bytes per pixel + the spill area.
-struct SfGuides
-{
-    float4* o4 = nullptr; float4* d4 = nullptr; float4* hits = nullptr;
-    float4* alb = nullptr; float4* nz = nullptr;       // the guides: albedo (w 0); unit normal + depth
-    uint32_t* count = nullptr;
-    uint2* spill = nullptr;
-    rt_camera camera;                                  // what the guides were made for
-    uint64_t scene = 0;
-    bool valid = false;
-    uint32_t passes = 0;                               // guide passes so far
-    std::vector<DevBuf> buffers(size_t n = 0, size_t spill_bytes = 0)
-    {
-        const size_t b = n * sizeof(float4);
-        return {{(void**)&o4, b}, {(void**)&d4, b}, {(void**)&hits, b}, {(void**)&alb, b}, {(void**)&nz, b}, {(void**)&count, sizeof(uint32_t)},
-                {(void**)&spill, spill_bytes}};
-    }
-};
-
-// The temporal filter's history on a frame (rt_frame_filter_temporal): made on first use, freed by rt_frame_destroy.  64 bytes per pixel: the colour
-// history, two moments images (mu1, mu2, L) -- the accumulation reads one and writes the other, which is then the history -- and the previous call's
-// normal + depth guide, copied after each call (the guide pass overwrites its own for a new camera).  Its scratch images are the spatial filter's o4 / d4.
-struct TfState
-{
-    float4* hist = nullptr;
-    float4* mom[2] = {nullptr, nullptr};
-    float4* prev_nz = nullptr;
-    uint32_t cur = 0;                                  // mom[cur] is the history
-    rt_camera prev_cam;                                // the previous call's camera and scene (rt_scene_upload count; upload epoch and refit index)
-    uint64_t prev_scene = 0;
-    uint64_t prev_epoch = 0, prev_refit = 0;
-    bool has_prev = false;                             // false: no call yet, or the history was dropped
-    std::vector<DevBuf> buffers(size_t n = 0)
-    {
-        const size_t b = n * sizeof(float4);
-        return {{(void**)&hist, b}, {(void**)&mom[0], b}, {(void**)&mom[1], b}, {(void**)&prev_nz, b}};
-    }
-};
-
-// RT_CTX_OPT_REFIT_MOTION on a frame (rt_frame_filter_temporal after a refit, rt_frame_read_guide_motion): per pixel where its first hit was in the pose
-// before the last refit and its normal there (filt::guide_motion over the guide pass's hits).  32 bytes per pixel, made on first use on a context that keeps
-// a pose, freed by rt_frame_destroy.
-struct SfMotion
-{
-    float4* prev_pos = nullptr; float4* prev_n = nullptr;
-    rt_camera camera;                                  // what the images were made for
-    uint64_t scene = 0;
-    bool valid = false;
-    std::vector<DevBuf> buffers(size_t n = 0)
-    {
-        const size_t b = n * sizeof(float4);
-        return {{(void**)&prev_pos, b}, {(void**)&prev_n, b}};
-    }
-};
 
 // context.h's functions: the one place a message is stored, the device copies of an upload, the queries' status word
 namespace context
@@ -767,7 +470,9 @@ int fork_pipes(rt_frame* f)
     return RT_OK;
 }
 
-int join_pipes(rt_frame* f)
+} // namespace
+
+int frame::join_pipes(rt_frame* f)
 {
     rt_ctx* ctx = f->ctx;
     for (uint32_t i = 1; i < RT_MAX_PIPES; ++i)
@@ -778,6 +483,9 @@ int join_pipes(rt_frame* f)
     }
     return RT_OK;
 }
+
+namespace
+{
 
 // stream, event, counters and spill area of pipes 0 .. count-1 (created once, kept for the frame's life)
 int ensure_pipe_resources(rt_frame* f, uint32_t count)
@@ -898,7 +606,7 @@ int flush_log(rt_frame* f, PathPipe& p, bool keep_open)
 } // namespace
 
 // waits (host side) for every stream a frame launches on besides the context's own
-static int sync_frame_streams(rt_frame* f)
+int frame::sync_frame_streams(rt_frame* f)
 {
     rt_ctx* ctx = f->ctx;
     for (PathPipe& q : f->ps)
@@ -910,8 +618,6 @@ static int sync_frame_streams(rt_frame* f)
     f->present_pending = false;
     return RT_OK;
 }
-
-extern "C" { static int deferred_materialize(rt_frame* f); }   // RT_OPT_FRAME_KERNEL (below, with the stage functions)
 
 namespace
 {
@@ -936,14 +642,19 @@ int for_stage_pipes(rt_frame* f, F&& body)
     return rc;
 }
 
+} // namespace
+
 // ... their logs replayed into the radiance (keep: the sample stays open), and the context's stream made to see all of them
-int flush_stage(rt_frame* f, bool keep = false)
+int frame::flush_stage(rt_frame* f, bool keep)
 {
     if (f->deferred.active && deferred_materialize(f) != RT_OK) return RT_ERROR;    // RT_OPT_FRAME_KERNEL: the recorded stages run after all
     const uint32_t n = f->stage_chunks ? f->stage_chunks : 1u;
     if (for_stage_pipes(f, [&](PathPipe& p) { return keep ? flush_log_keep(f, p) : flush_log(f, p); }) != RT_OK) return RT_ERROR;
     return n > 1 ? join_pipes(f) : RT_OK;
 }
+
+namespace
+{
 
 // RT_OPT_FRAME_KERNEL = 255 measures again: another workload, or another grid
 void fk_auto_restart(rt_frame* f) { f->fk_auto.frames = 0; f->fk_auto.timing = -1; f->fk_auto.decided = false; f->fk_auto.use_kernel = false; }
@@ -1093,9 +804,7 @@ int rt_frame_destroy(rt_frame* f)
     for (auto& sp : f->spans) { (void)hipEventDestroy(sp.a); (void)hipEventDestroy(sp.b); }
     for (auto e : f->event_pool) (void)hipEventDestroy(e);
     // the filters' states
-    free_state(f->sf);
-    free_state(f->tf);
-    free_state(f->sm);
+    free_filter_state(f);
     delete f;
     return RT_OK;
 }
@@ -1742,10 +1451,8 @@ int shadow_pipe(rt_frame* f, PathPipe& p, uint32_t bounce)
 
 } // namespace
 
-extern "C" {
-
 // The recorded stages of a deferred sample, run with the stage kernels after all (somebody wants the state between two stages).
-static int deferred_materialize(rt_frame* f)
+int frame::deferred_materialize(rt_frame* f)
 {
     if (!f->deferred.active) return RT_OK;
     const uint32_t done = f->deferred.bounce;
@@ -1764,6 +1471,8 @@ static int deferred_materialize(rt_frame* f)
     }
     return RT_OK;
 }
+
+extern "C" {
 
 int rt_generate_rays(rt_frame* f)                       // GenerateRays, :516-520
 {
@@ -2192,394 +1901,24 @@ int rt_frame_resolve(rt_frame* f, float* host_rgba)     // ResolveRadiance, :677
     return RT_OK;
 }
 
-int rt_frame_read_radiance(rt_frame* f, float* host_rgba)
-{
-    if (!f || !host_rgba) return fail(nullptr, "rt_frame_read_radiance: NULL argument");
-    rt_ctx* ctx = f->ctx;
-    (void)hipSetDevice(ctx->device);
-    if (f->n_local == 0) return RT_OK;
-    if (flush_stage(f, true) != RT_OK) return RT_ERROR;
-    HIPCHK(ctx, hipMemcpyAsync(host_rgba, f->radiance, (size_t)f->n_local * sizeof(float4), hipMemcpyDeviceToHost,
-        ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return RT_OK;
-}
+} // extern "C"
 
-
-// ---- the spatial and temporal filters (spatial_filter.h and temporal_filter.h state them; the kernels live in filters.hip)
-// the checks both filters' descriptors share: iterations, flags, (the temporal filter's alphas,) three sigmas > 0 and finite
-static int check_desc(rt_ctx* ctx, const char* who, uint32_t iterations, uint32_t flags, const float (&sigmas)[3], const char* sigma_names,
-    bool alphas_ok = true)
-{
-    if (iterations > RT_FILTER_MAX_ITERATIONS) return fail(ctx, std::string(who) + ": iterations must be 0 .. 8");
-    if (flags & ~RT_FILTER_DEMODULATE) return fail(ctx, std::string(who) + ": unknown flags (RT_FILTER_DEMODULATE is the only one)");
-    if (!alphas_ok) return fail(ctx, std::string(who) + ": alpha_color and alpha_moments must be in 0 .. 1");
-    for (float v : sigmas)
-        if (!(v > 0.0f) || !std::isfinite(v)) return fail(ctx, std::string(who) + ": " + sigma_names + " must be > 0 and finite");
-    return RT_OK;
-}
-
-static int check_filter_desc(rt_ctx* ctx, const char* who, const rt_filter_desc* d)
-{
-    return check_desc(ctx, who, d->iterations, d->flags, {d->sigma_color, d->sigma_normal, d->sigma_depth}, "sigma_color, sigma_normal and sigma_depth");
-}
-
-static int check_temporal_desc(rt_ctx* ctx, const char* who, const rt_temporal_filter_desc* d)
-{
-    const bool alphas_ok = d->alpha_color >= 0.0f && d->alpha_color <= 1.0f && d->alpha_moments >= 0.0f && d->alpha_moments <= 1.0f;
-    return check_desc(ctx, who, d->iterations, d->flags, {d->sigma_luminance, d->sigma_normal, d->sigma_depth},
-                      "sigma_luminance, sigma_normal and sigma_depth", alphas_ok);
-}
-
-static int check_filter_frame(rt_frame* f, const char* who)
-{
-    if (f->tile.nranks > 1) return fail(f->ctx, std::string(who) + ": a tile frame (tile_count > 1): the filter's stencil crosses rows, it needs the whole image");
-    return RT_OK;
-}
-
-// the guides for the frame's current camera: one pixel-centre ray per pixel, traced by k_trace_v1<false> (the reference's BVH2 walk) on the context's
-// stream with the filter's own buffers, then k_aov's formulas.  Recomputed when the camera or the scene (rt_scene_upload) has changed since.
-static int ensure_guides(rt_frame* f, const char* who)
+// The spatial and temporal filters and the readers that launch no kernel are units of their own (frame_filters.cpp, frame_readers.cpp, on frame.h).  What stays
+// here of the filters is the guide pass's one launch of this unit's code object.
+void frame::trace_guides(rt_frame* f, const float4* o4, const float4* d4, float4* hits, uint2* spill, const uint32_t* count, size_t n)
 {
     rt_ctx* ctx = f->ctx;
-    if (!ctx->scene.valid) return fail(ctx, std::string(who) + ": no scene uploaded");
-    const size_t n = f->n_local;
-    if (!f->sf)
-    {
-        const size_t spill_bytes = (size_t)f->trace_blocks * 64u * (RT_TRACE_STACK_MAX - RT_TRACE_STACK_LDS) * sizeof(uint2);
-        f->sf = alloc_state<SfGuides>(n, spill_bytes);
-        if (!f->sf) return fail(ctx, std::string(who) + ": out of device memory for the guide pass (80 bytes per pixel)");
-    }
-    SfGuides* g = f->sf;
-    if (g->valid && g->scene == ctx->scene_uploads && memcmp(&g->camera, &f->camera, sizeof(rt_camera)) == 0) return RT_OK;
-    g->valid = false;
-    HIPCHK(ctx, filt::guide_rays(ctx->stream, f->tile.width, f->tile.height, f->camera, rt_tanf(0.5f * f->camera.fov), g->o4, g->d4));
-    HIPCHK(ctx, hipMemsetD32Async((hipDeviceptr_t)g->count, (int)n, 1, ctx->stream));
     {
         // the closest-hit trace through launch_trace's per-ray kernel k_trace_v1<false> (variant 0: the reference's BVH2 walk; waves 0: the grid is trace_blocks), on the
         // context's stream with the filter's own hits and spill area; a closest-hit trace logs nothing and that kernel counts nothing.  (Through launch_trace and
         // not a launch of its own: a new use of the template kernel here moves where clang places its code, and the hot path's code object --
         // codeobj.code_object_sha256 -- must stay byte for byte what it is.)
-        const TraceTarget t = {ctx->stream, g->spill, nullptr, 0u, g->hits, DLog{}, nullptr, (uint64_t)n, 0u, 0u, 0u};
-        launch_trace<false>(f, t, g->o4, g->d4, (const uint32_t*)nullptr, g->count);
+        const TraceTarget t = {ctx->stream, spill, nullptr, 0u, hits, DLog{}, nullptr, (uint64_t)n, 0u, 0u, 0u};
+        launch_trace<false>(f, t, o4, d4, (const uint32_t*)nullptr, count);
     }
-    HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, filt::guide_values(ctx->stream, ctx->scene.d, g->o4, g->hits, (uint32_t)n, g->alb, g->nz));
-    g->camera = f->camera;
-    g->scene = ctx->scene_uploads;
-    g->valid = true;
-    ++g->passes;
-    return RT_OK;
 }
 
-// RT_CTX_OPT_REFIT_MOTION: the frame's motion images for its current camera and the context's current snapshot (which must exist); the guides first
-static int ensure_motion(rt_frame* f, const char* who)
-{
-    rt_ctx* ctx = f->ctx;
-    if (ensure_guides(f, who) != RT_OK) return RT_ERROR;
-    const size_t n = f->n_local;
-    if (!f->sm)
-    {
-        f->sm = alloc_state<SfMotion>(n);
-        if (!f->sm) return fail(ctx, std::string(who) + ": out of device memory for the motion images (32 bytes per pixel)");
-    }
-    SfMotion* m = f->sm;
-    if (m->valid && m->scene == ctx->scene_uploads && memcmp(&m->camera, &f->camera, sizeof(rt_camera)) == 0) return RT_OK;
-    m->valid = false;
-    HIPCHK(ctx, filt::guide_motion(ctx->stream, (const float4*)ctx->scene.pose_snap, ctx->scene.n_tris, f->sf->hits, (uint32_t)n, m->prev_pos, m->prev_n));
-    m->camera = f->camera;
-    m->scene = ctx->scene_uploads;
-    m->valid = true;
-    return RT_OK;
-}
-
-// the refusals both frame filters share after their descriptor's check: a tile frame, RT_OPT_AOV
-static int check_filter_call(rt_frame* f, const char* who)
-{
-    if (check_filter_frame(f, who) != RT_OK) return RT_ERROR;
-    if (f->aov != 0) return fail(f->ctx, std::string(who) + ": RT_OPT_AOV != 0: the filter is for the shaded colour only");
-    return RT_OK;
-}
-
-// what both frame filters need before their passes: the guides, the frame's own work done, f->resolved free to be the output image (as rt_frame_resolve)
-static int filter_inputs_ready(rt_frame* f, const char* who)
-{
-    if (ensure_guides(f, who) != RT_OK || rt_frame_present_wait(f) != RT_OK || flush_stage(f) != RT_OK) return RT_ERROR;
-    return RT_OK;
-}
-
-// the frame filters' read-back: the output image f->resolved to the caller
-static int read_filtered(rt_frame* f, float* host_rgba)
-{
-    rt_ctx* ctx = f->ctx;
-    HIPCHK(ctx, hipMemcpyAsync(host_rgba, f->resolved, (size_t)f->n_local * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return RT_OK;
-}
-
-// the debug entry points' guide: normal (xyz) + depth per pixel
-static std::vector<float> pack_nz(const float* normal_rgba, const float* depth, size_t n)
-{
-    std::vector<float> nz(4 * n);
-    for (size_t i = 0; i < n; ++i)
-    {
-        nz[4 * i] = normal_rgba[4 * i]; nz[4 * i + 1] = normal_rgba[4 * i + 1]; nz[4 * i + 2] = normal_rgba[4 * i + 2]; nz[4 * i + 3] = depth[i];
-    }
-    return nz;
-}
-
-// the debug entry points on ctx's device: n_images images of n pixels, the first in.size() uploaded from `in`, run(images), the last out.size()
-// downloaded to `out`; every image is freed on every path and a failure is reported as "who: <HIP error>" (a template: C++ linkage inside extern "C")
-extern "C++" template <class F> static int debug_on_device(rt_ctx* ctx, const char* who, size_t n, size_t n_images, std::initializer_list<const void*> in,
-    std::initializer_list<void*> out, F&& run)
-{
-    (void)hipSetDevice(ctx->device);
-    dev::Temps tmp(ctx->stream);
-    std::vector<float4*> buf(n_images, nullptr);
-    const size_t bytes = n * sizeof(float4);
-    bool ok = true;
-    for (float4*& b : buf) ok = ok && tmp.array(b, n);
-    size_t k = 0;
-    for (const void* p : in) ok = ok && hipMemcpyAsync(buf[k++], p, bytes, hipMemcpyHostToDevice, ctx->stream) == hipSuccess;
-    hipError_t e = ok ? run(buf.data()) : hipErrorOutOfMemory;
-    k = n_images - out.size();
-    for (void* p : out) if (e == hipSuccess) e = hipMemcpyAsync(p, buf[k++], bytes, hipMemcpyDeviceToHost, ctx->stream);
-    hipError_t es = hipStreamSynchronize(ctx->stream);
-    if (e == hipSuccess) e = es;
-    if (e != hipSuccess) { (void)hipGetLastError(); return fail(ctx, std::string(who) + ": " + hipGetErrorString(e)); }
-    return RT_OK;
-}
-
-int rt_frame_filter(rt_frame* f, const rt_filter_desc* desc, float* host_rgba)
-{
-    static const char* who = "rt_frame_filter";
-    if (!f || !desc || !host_rgba) return fail(nullptr, "rt_frame_filter: NULL argument");
-    rt_ctx* ctx = f->ctx;
-    (void)hipSetDevice(ctx->device);
-    if (check_filter_desc(ctx, who, desc) != RT_OK || check_filter_call(f, who) != RT_OK) return RT_ERROR;
-    if (desc->iterations == 0) return rt_frame_resolve(f, host_rgba);      // exactly rt_frame_resolve's image
-    if (f->n_local == 0) return RT_OK;
-    if (filter_inputs_ready(f, who) != RT_OK) return RT_ERROR;
-    SfGuides* g = f->sf;
-    const filt::Spatial s = {f->tile.width, f->tile.height, *desc, f->denoiser == 0u, (float)f->sample_count, 1};
-    HIPCHK(ctx, filt::spatial(ctx->stream, s, f->radiance, g->alb, g->nz, g->o4, g->d4, f->resolved));
-    return read_filtered(f, host_rgba);
-}
-
-int rt_frame_read_guides(rt_frame* f, float* albedo_rgba, float* normal_rgba, float* depth, uint32_t* passes)
-{
-    if (!f) return fail(nullptr, "rt_frame_read_guides: NULL argument");
-    rt_ctx* ctx = f->ctx;
-    (void)hipSetDevice(ctx->device);
-    if (check_filter_frame(f, "rt_frame_read_guides") != RT_OK) return RT_ERROR;
-    if (f->n_local == 0) { if (passes) *passes = 0; return RT_OK; }
-    if (ensure_guides(f, "rt_frame_read_guides") != RT_OK) return RT_ERROR;
-    const size_t n = f->n_local;
-    if (albedo_rgba) HIPCHK(ctx, hipMemcpyAsync(albedo_rgba, f->sf->alb, n * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
-    std::vector<float4> nz((normal_rgba || depth) ? n : 0);
-    if (!nz.empty()) HIPCHK(ctx, hipMemcpyAsync(nz.data(), f->sf->nz, n * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    for (size_t i = 0; i < nz.size(); ++i)
-    {
-        if (normal_rgba) { normal_rgba[4 * i] = nz[i].x; normal_rgba[4 * i + 1] = nz[i].y; normal_rgba[4 * i + 2] = nz[i].z; normal_rgba[4 * i + 3] = 0.0f; }
-        if (depth) depth[i] = nz[i].w;
-    }
-    if (passes) *passes = f->sf->passes;
-    return RT_OK;
-}
-
-int rt_debug_filter(rt_ctx* ctx, uint32_t width, uint32_t height, const float* hdr_rgba, const float* albedo_rgba, const float* normal_rgba,
-    const float* depth, const rt_filter_desc* desc, float* out_hdr_rgba)
-{
-    static const char* who = "rt_debug_filter";
-    if (!hdr_rgba || !albedo_rgba || !normal_rgba || !depth || !desc || !out_hdr_rgba) return fail(ctx, "rt_debug_filter: NULL argument");
-    if (width == 0 || height == 0) return fail(ctx, "rt_debug_filter: empty image");
-    if (check_filter_desc(ctx, who, desc) != RT_OK) return RT_ERROR;
-    const size_t n = (size_t)width * height;
-    if (desc->iterations == 0) { memcpy(out_hdr_rgba, hdr_rgba, n * sizeof(float4)); return RT_OK; }
-    const std::vector<float> nz = pack_nz(normal_rgba, depth, n);
-    const filt::Spatial s = {width, height, *desc, 0, 1.0f, 0};
-    if (!ctx)
-    {
-        filt::spatial_host(s, hdr_rgba, albedo_rgba, nz.data(), out_hdr_rgba);
-        return RT_OK;
-    }
-    // images: hdr, albedo, nz, ping, pong, out
-    return debug_on_device(ctx, who, n, 6, {hdr_rgba, albedo_rgba, nz.data()}, {out_hdr_rgba},
-                           [&](float4** b) { return filt::spatial(ctx->stream, s, b[0], b[1], b[2], b[3], b[4], b[5]); });
-}
-
-int rt_frame_filter_temporal(rt_frame* f, const rt_temporal_filter_desc* desc, float* host_rgba)
-{
-    static const char* who = "rt_frame_filter_temporal";
-    if (!f || !desc || !host_rgba) return fail(nullptr, "rt_frame_filter_temporal: NULL argument");
-    rt_ctx* ctx = f->ctx;
-    (void)hipSetDevice(ctx->device);
-    if (check_temporal_desc(ctx, who, desc) != RT_OK || check_filter_call(f, who) != RT_OK) return RT_ERROR;
-    if (f->denoiser != 0)
-        return fail(ctx, "rt_frame_filter_temporal: RT_OPT_DENOISER != 0: the frame is already accumulated over time by the reference's denoiser");
-    if (f->n_local == 0) return RT_OK;
-    const size_t n = f->n_local;
-    if (!f->tf)
-    {
-        TfState* t = alloc_state<TfState>(n);
-        if (t && (hipMemsetAsync(t->hist, 0, n * sizeof(float4), ctx->stream) != hipSuccess ||
-                  hipMemsetAsync(t->mom[0], 0, n * sizeof(float4), ctx->stream) != hipSuccess))
-        {
-            (void)hipGetLastError();
-            free_state(t);
-        }
-        if (!t) return fail(ctx, "rt_frame_filter_temporal: out of device memory for the history (64 bytes per pixel)");
-        f->tf = t;
-    }
-    if (filter_inputs_ready(f, who) != RT_OK) return RT_ERROR;
-    TfState* t = f->tf;
-    SfGuides* g = f->sf;
-    filt::Temporal c;
-    c.width = f->tile.width; c.height = f->tile.height;
-    c.cam = f->camera;
-    c.prev = t->has_prev ? t->prev_cam : f->camera;
-    // what the history was made for against the scene now: the same upload and pose = as ever; the same upload, one refit on and the context kept the pose
-    // that refit replaced = followed through the motion images; anything else (another upload, two refits or more, no pose kept) = dropped
-    const bool same_upload = t->has_prev && t->prev_epoch == ctx->upload_epoch;
-    const bool follow = same_upload && t->prev_refit + 1u == ctx->refit_index && ctx->scene.pose_snap && ctx->scene.pose_valid;
-    if (follow && ensure_motion(f, who) != RT_OK) return RT_ERROR;
-    c.mode = follow ? filt::REPROJECT
-           : !same_upload || t->prev_refit != ctx->refit_index ? filt::NO_HISTORY
-           : memcmp(&t->prev_cam, &f->camera, sizeof(rt_camera)) == 0 ? filt::IDENTITY : filt::REPROJECT;
-    c.desc = *desc;
-    c.divide = 1; c.spp = (float)f->sample_count; c.tonemap = 1;
-    HIPCHK(ctx, filt::temporal(ctx->stream, c, f->radiance, g->alb, g->nz, t->prev_nz, t->hist, t->mom[t->cur], t->hist, t->mom[t->cur ^ 1u], g->o4,
-        g->d4, f->resolved, follow ? f->sm->prev_pos : nullptr, follow ? f->sm->prev_n : nullptr));
-    t->cur ^= 1u;
-    HIPCHK(ctx, hipMemcpyAsync(t->prev_nz, g->nz, n * sizeof(float4), hipMemcpyDeviceToDevice, ctx->stream));
-    t->prev_cam = f->camera;
-    t->prev_scene = ctx->scene_uploads;
-    t->prev_epoch = ctx->upload_epoch; t->prev_refit = ctx->refit_index;
-    t->has_prev = true;
-    return read_filtered(f, host_rgba);
-}
-
-int rt_frame_filter_history_reset(rt_frame* f)
-{
-    if (!f) return fail(nullptr, "rt_frame_filter_history_reset: NULL argument");
-    rt_ctx* ctx = f->ctx;
-    (void)hipSetDevice(ctx->device);
-    if (!f->tf) return RT_OK;
-    f->tf->has_prev = false;
-    HIPCHK(ctx, hipMemsetAsync(f->tf->hist, 0, (size_t)f->n_local * sizeof(float4), ctx->stream));
-    HIPCHK(ctx, hipMemsetAsync(f->tf->mom[f->tf->cur], 0, (size_t)f->n_local * sizeof(float4), ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return RT_OK;
-}
-
-int rt_frame_read_filter_history(rt_frame* f, float* color_rgba, float* moments_len)
-{
-    if (!f) return fail(nullptr, "rt_frame_read_filter_history: NULL argument");
-    rt_ctx* ctx = f->ctx;
-    (void)hipSetDevice(ctx->device);
-    if (check_filter_frame(f, "rt_frame_read_filter_history") != RT_OK) return RT_ERROR;
-    const size_t n = f->n_local;
-    if (!f->tf)
-    {
-        if (color_rgba) memset(color_rgba, 0, n * sizeof(float4));
-        if (moments_len) memset(moments_len, 0, n * sizeof(float4));
-        return RT_OK;
-    }
-    if (color_rgba) HIPCHK(ctx, hipMemcpyAsync(color_rgba, f->tf->hist, n * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
-    if (moments_len) HIPCHK(ctx, hipMemcpyAsync(moments_len, f->tf->mom[f->tf->cur], n * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return RT_OK;
-}
-
-int rt_frame_read_guide_motion(rt_frame* f, float* prev_position_rgba, float* prev_normal_rgba)
-{
-    static const char* who = "rt_frame_read_guide_motion";
-    if (!f) return fail(nullptr, "rt_frame_read_guide_motion: NULL argument");
-    rt_ctx* ctx = f->ctx;
-    (void)hipSetDevice(ctx->device);
-    if (check_filter_frame(f, who) != RT_OK) return RT_ERROR;
-    const size_t n = f->n_local;
-    if (n == 0) return RT_OK;
-    if (!ctx->scene.valid || !ctx->scene.pose_snap || !ctx->scene.pose_valid)           // no snapshot: no motion known anywhere
-    {
-        if (prev_position_rgba) memset(prev_position_rgba, 0, n * sizeof(float4));
-        if (prev_normal_rgba) memset(prev_normal_rgba, 0, n * sizeof(float4));
-        return RT_OK;
-    }
-    if (ensure_motion(f, who) != RT_OK) return RT_ERROR;
-    if (prev_position_rgba) HIPCHK(ctx, hipMemcpyAsync(prev_position_rgba, f->sm->prev_pos, n * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
-    if (prev_normal_rgba) HIPCHK(ctx, hipMemcpyAsync(prev_normal_rgba, f->sm->prev_n, n * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return RT_OK;
-}
-
-int rt_debug_guide_motion(rt_ctx* ctx, uint32_t n, const float* hits, const rt_triangle* prev_triangles, uint32_t num_triangles, float* out_position_rgba,
-    float* out_normal_rgba)
-{
-    if (!hits || (!prev_triangles && num_triangles) || !out_position_rgba || !out_normal_rgba) return fail(ctx, "rt_debug_guide_motion: NULL argument");
-    if (n == 0) return RT_OK;
-    const std::vector<float> records = filt::pose_records(prev_triangles, num_triangles);
-    if (!ctx)
-    {
-        filt::guide_motion_host(records.data(), num_triangles, hits, n, out_position_rgba, out_normal_rgba);
-        return RT_OK;
-    }
-    (void)hipSetDevice(ctx->device);
-    const hipError_t e = filt::guide_motion_device(ctx->stream, records.data(), num_triangles, hits, n, out_position_rgba, out_normal_rgba);
-    if (e != hipSuccess) { (void)hipGetLastError(); return fail(ctx, std::string("rt_debug_guide_motion: ") + hipGetErrorString(e)); }
-    return RT_OK;
-}
-
-int rt_debug_filter_temporal(rt_ctx* ctx, uint32_t width, uint32_t height, const rt_camera* cam, const rt_camera* prev_cam, const float* hdr_rgba,
-    const float* albedo_rgba, const float* normal_rgba, const float* depth, const float* prev_normal_rgba, const float* prev_depth,
-    const float* hist_color, const float* hist_moments, const rt_temporal_filter_desc* desc, float* out_hdr_rgba, float* hist_color_out,
-    float* hist_moments_out)
-{
-    return rt_debug_filter_temporal_motion(ctx, width, height, cam, prev_cam, hdr_rgba, albedo_rgba, normal_rgba, depth, prev_normal_rgba, prev_depth, hist_color,
-        hist_moments, nullptr, nullptr, desc, out_hdr_rgba, hist_color_out, hist_moments_out);
-}
-
-int rt_debug_filter_temporal_motion(rt_ctx* ctx, uint32_t width, uint32_t height, const rt_camera* cam, const rt_camera* prev_cam, const float* hdr_rgba,
-    const float* albedo_rgba, const float* normal_rgba, const float* depth, const float* prev_normal_rgba, const float* prev_depth,
-    const float* hist_color, const float* hist_moments, const float* prev_position_rgba, const float* prev_pose_normal_rgba,
-    const rt_temporal_filter_desc* desc, float* out_hdr_rgba, float* hist_color_out, float* hist_moments_out)
-{
-    // (the messages name rt_debug_filter_temporal, the family: the entry without motion images is this one with two NULLs)
-    static const char* who = "rt_debug_filter_temporal";
-    if (!cam || !hdr_rgba || !albedo_rgba || !normal_rgba || !depth || !prev_normal_rgba || !prev_depth || !hist_color || !hist_moments || !desc ||
-        !out_hdr_rgba || !hist_color_out || !hist_moments_out)
-        return fail(ctx, "rt_debug_filter_temporal: NULL argument");
-    if (width == 0 || height == 0) return fail(ctx, "rt_debug_filter_temporal: empty image");
-    const bool motion = prev_position_rgba && prev_pose_normal_rgba;
-    if (check_temporal_desc(ctx, who, desc) != RT_OK) return RT_ERROR;
-    const size_t n = (size_t)width * height;
-    const std::vector<float> nz = pack_nz(normal_rgba, depth, n), pnz = pack_nz(prev_normal_rgba, prev_depth, n);
-    filt::Temporal c;
-    c.width = width; c.height = height;
-    c.cam = *cam;
-    c.prev = prev_cam ? *prev_cam : *cam;
-    c.mode = !motion && (!prev_cam || memcmp(prev_cam, cam, sizeof(rt_camera)) == 0) ? filt::IDENTITY : filt::REPROJECT;
-    c.desc = *desc;
-    c.divide = 0; c.spp = 1.0f; c.tonemap = 0;
-    if (!ctx)
-    {
-        filt::temporal_host(c, hdr_rgba, albedo_rgba, nz.data(), pnz.data(), hist_color, hist_moments, hist_color_out, hist_moments_out, out_hdr_rgba,
-            motion ? prev_position_rgba : nullptr, motion ? prev_pose_normal_rgba : nullptr);
-        return RT_OK;
-    }
-    // with motion images: hdr, albedo, nz, prev nz, hist in, moments in, prev position, prev pose normal, a, b, out, hist out, moments out
-    if (motion)
-        return debug_on_device(ctx, who, n, 13, {hdr_rgba, albedo_rgba, nz.data(), pnz.data(), hist_color, hist_moments, prev_position_rgba, prev_pose_normal_rgba},
-                               {out_hdr_rgba, hist_color_out, hist_moments_out},
-                               [&](float4** b) { return filt::temporal(ctx->stream, c, b[0], b[1], b[2], b[3], b[4], b[5], b[11], b[12], b[8], b[9], b[10], b[6], b[7]); });
-    // images: hdr, albedo, nz, prev nz, hist in, moments in, a, b, out, hist out, moments out
-    return debug_on_device(ctx, who, n, 11, {hdr_rgba, albedo_rgba, nz.data(), pnz.data(), hist_color, hist_moments},
-                           {out_hdr_rgba, hist_color_out, hist_moments_out},
-                           [&](float4** b) { return filt::temporal(ctx->stream, c, b[0], b[1], b[2], b[3], b[4], b[5], b[9], b[10], b[6], b[7], b[8]); });
-}
-void* rt_frame_radiance_device_ptr(rt_frame* f) { return f ? (void*)f->radiance : nullptr; }
-uint32_t rt_frame_sample_count(rt_frame* f) { return f ? f->sample_count : 0; }
+extern "C" {
 
 int rt_frame_get_stats(rt_frame* f, rt_stats* out)
 {
@@ -2631,173 +1970,6 @@ int rt_frame_get_stats(rt_frame* f, rt_stats* out)
         }
         out->samples_from_banks = f->ahead->consumed;
     }
-    return RT_OK;
-}
-
-int rt_frame_get_profile(rt_frame* f, rt_profile* out)
-{
-    if (!f || !out) return fail(nullptr, "rt_frame_get_profile: NULL argument");
-    rt_ctx* ctx = f->ctx;
-    (void)hipSetDevice(ctx->device);
-    if (join_pipes(f) != RT_OK || sync_frame_streams(f) != RT_OK) return RT_ERROR;   // spans on the side streams end when their launches do
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    memset(out, 0, sizeof(*out));
-    double* ms[4] = {&out->ms_raygen, &out->ms_trace_closest, &out->ms_shade, &out->ms_trace_shadow};
-    uint32_t* cnt[4] = {&out->n_raygen, &out->n_trace_closest, &out->n_shade, &out->n_trace_shadow};
-    for (auto& s : f->spans)
-    {
-        float t = 0.0f;
-        if (hipEventElapsedTime(&t, s.a, s.b) == hipSuccess) { *ms[s.cls] += t; (*cnt[s.cls])++; }
-        f->event_pool.push_back(s.a);
-        f->event_pool.push_back(s.b);
-    }
-    f->spans.clear();
-    return RT_OK;
-}
-
-int rt_frame_copy_radiance(rt_frame* f, void* device_dst)
-{
-    if (!f || !device_dst) return fail(nullptr, "rt_frame_copy_radiance: NULL argument");
-    rt_ctx* ctx = f->ctx;
-    (void)hipSetDevice(ctx->device);
-    if (f->n_local == 0) return RT_OK;
-    if (flush_stage(f, true) != RT_OK) return RT_ERROR;
-    HIPCHK(ctx, hipMemcpyAsync(device_dst, f->radiance, (size_t)f->n_local * sizeof(float4), hipMemcpyDeviceToDevice,
-        ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return RT_OK;
-}
-
-// ---- debug / parity --------------------------------------------------------
-int rt_frame_debug_read_queue(rt_frame* f, int which, uint32_t bounce, rt_ray* rays, uint32_t* pixel_indices,
-    rt_float4* payload, uint32_t capacity, uint32_t* count)
-{
-    if (!f || !count) return fail(nullptr, "rt_frame_debug_read_queue: NULL argument");
-    rt_ctx* ctx = f->ctx;
-    (void)hipSetDevice(ctx->device);
-    if (bounce > RT_MAX_BOUNCES_LIMIT + 1) return fail(ctx, "rt_frame_debug_read_queue: bounce out of range");
-    if (f->stage_chunks > 1) return fail(ctx, "rt_frame_debug_read_queue: the sample in flight is spread over several pipes (set RT_OPT_STAGE_PIPES to 1 for the debug readers)");
-    if (f->deferred.active && deferred_materialize(f) != RT_OK) return RT_ERROR;
-    const PathPipe& q = f->ps[0];                                          // (one chunk: the sample in flight is on pipe 0)
-    if (q.side) HIPCHK(ctx, hipStreamSynchronize(q.side));                 // a shadow trace may be retracting log entries
-    DCounters h;
-    HIPCHK(ctx, hipMemcpyAsync(&h, q.counters, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    uint32_t n = which == 0 ? h.queue[bounce] : h.shadow[bounce];
-    if (n > f->log_stride) return fail(ctx, "rt_frame_debug_read_queue: corrupt counter");
-    *count = n;
-    if (n == 0) return RT_OK;
-    if (!rays && !pixel_indices && !payload) return RT_OK;                 // size query (two-call pattern)
-    if (n > capacity) return fail(ctx, "rt_frame_debug_read_queue: the queue holds more entries than the caller's arrays");
-    const float4* so = which == 0 ? q.o4[bounce & 1u] : q.sh_o4[bounce & 1u];
-    const float4* sdir = which == 0 ? q.d4[bounce & 1u] : q.sh_d4[bounce & 1u];
-    std::vector<float4> o(n), d(n), p(n);
-    HIPCHK(ctx, hipMemcpy(o.data(), so, (size_t)n * 16, hipMemcpyDeviceToHost));
-    HIPCHK(ctx, hipMemcpy(d.data(), sdir, (size_t)n * 16, hipMemcpyDeviceToHost));
-    if (which == 0) HIPCHK(ctx, hipMemcpy(p.data(), q.thr[bounce & 1u], (size_t)n * 16, hipMemcpyDeviceToHost));
-    for (uint32_t i = 0; i < n; ++i)
-    {
-        uint32_t pl;
-        memcpy(&pl, &d[i].w, 4);
-        uint32_t id = pl;
-        uint32_t local_pix = q.chunk_base + id % (f->chunk_pixels ? f->chunk_pixels : 1);
-        if (which == 1)   // the deferred direct-light sample lives in the radiance log
-        {
-            uint32_t entry = 0;
-            HIPCHK(ctx, hipMemcpy(&entry, q.sh_aux[bounce & 1u] + i, 4, hipMemcpyDeviceToHost));
-            p[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-            uint32_t oblk = 0;
-            if (entry >= f->log_inline) HIPCHK(ctx, hipMemcpy(&oblk, q.ovf_slot + id, 4, hipMemcpyDeviceToHost));
-            const size_t at = entry < f->log_inline ? (size_t)entry * f->log_stride + id
-                                                    : (size_t)f->log_inline * f->log_stride + (size_t)(entry - f->log_inline) * f->log_ovf_blocks + oblk;
-            HIPCHK(ctx, hipMemcpy(&p[i], q.rlog + 3u * at, 12, hipMemcpyDeviceToHost));
-        }
-        if (rays)
-        {
-            rays[i].origin.x = o[i].x; rays[i].origin.y = o[i].y; rays[i].origin.z = o[i].z; rays[i].origin.w = 0.0f;
-            rays[i].direction.x = d[i].x; rays[i].direction.y = d[i].y; rays[i].direction.z = d[i].z;
-            rays[i].direction.w = o[i].w;
-        }
-        if (pixel_indices)
-        {
-            uint32_t ly = local_pix / f->tile.width, px = local_pix - ly * f->tile.width;
-            pixel_indices[i] = rt_frame_global_row(f, ly) * f->tile.width + px;   // GLOBAL pixel index
-        }
-        if (payload) { payload[i].x = p[i].x; payload[i].y = p[i].y; payload[i].z = p[i].z; payload[i].w = 0.0f; }
-    }
-    return RT_OK;
-}
-
-int rt_frame_debug_read_hits(rt_frame* f, rt_hit* hits, uint32_t count)
-{
-    if (!f || !hits) return fail(nullptr, "rt_frame_debug_read_hits: NULL argument");
-    rt_ctx* ctx = f->ctx;
-    (void)hipSetDevice(ctx->device);
-    if (count > f->log_stride) return fail(ctx, "rt_frame_debug_read_hits: count too large");
-    if (f->stage_chunks > 1) return fail(ctx, "rt_frame_debug_read_hits: the sample in flight is spread over several pipes (set RT_OPT_STAGE_PIPES to 1 for the debug readers)");
-    if (f->deferred.active && deferred_materialize(f) != RT_OK) return RT_ERROR;
-    std::vector<float4> h(count ? count : 1);
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    HIPCHK(ctx, hipMemcpy(h.data(), f->ps[0].hits, (size_t)count * 16, hipMemcpyDeviceToHost));
-    for (uint32_t i = 0; i < count; ++i)
-    {
-        hits[i].bc.x = h[i].x; hits[i].bc.y = h[i].y;
-        memcpy(&hits[i].primitive_id, &h[i].z, 4);
-        hits[i].t = h[i].w;
-    }
-    return RT_OK;
-}
-
-// Debug: launch timeline of the closest-hit wide-tree kernel.  arm = 1 clears the slots and starts recording
-// (pipe 0); arm = 0 reads them: out[b] = {first wave started, first wave found the queue dry, last wave left} of the
-// most recent bounce-b launch, in ticks of the 100 MHz wall clock (0 where nothing ran), then the most traversal steps
-// any ray took and the slowest ray's ticks from hand-out to retirement and its steps; after those 64 x 6 values, out[384 + i] =
-// waves (of all recorded launches) that left in the i-th 25 us after their launch's queue ran dry.
-// k_frame's per-wave rows of its latest launch (RT_FRAME_COUNT_STRIDE words each; frame_kernels.h): rays per bounce and the wave's ticks per phase
-int rt_frame_debug_frame_rows(rt_frame* f, uint32_t* out, uint32_t capacity_rows, uint32_t* n_rows, uint32_t* row_words)
-{
-    if (!f || !n_rows || !row_words) return fail(nullptr, "rt_frame_debug_frame_rows: NULL argument");
-    rt_ctx* ctx = f->ctx;
-    (void)hipSetDevice(ctx->device);
-    *n_rows = f->kf.blocks; *row_words = RT_FRAME_COUNT_STRIDE;
-    if (!out || f->kf.blocks == 0u || !f->kf.counts) return RT_OK;
-    if (capacity_rows < f->kf.blocks) return fail(ctx, "rt_frame_debug_frame_rows: the caller's array is too small");
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    HIPCHK(ctx, hipMemcpy(out, f->kf.counts, (size_t)f->kf.blocks * RT_FRAME_COUNT_STRIDE * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    return RT_OK;
-}
-
-int rt_frame_debug_timeline(rt_frame* f, int arm, unsigned long long* out /* [64][6] + [64] when reading */)
-{
-    if (!f) return fail(nullptr, "rt_frame_debug_timeline: frame is NULL");
-    rt_ctx* ctx = f->ctx;
-    (void)hipSetDevice(ctx->device);
-    if (join_pipes(f) != RT_OK) return RT_ERROR;
-    DCounters* c = f->ps[0].counters;
-    if (arm)
-    {
-        HIPCHK(ctx, hipMemsetAsync(c->tl_start, 0xFF, sizeof(c->tl_start) + sizeof(c->tl_dry), ctx->stream));
-        HIPCHK(ctx, hipMemsetAsync(c->tl_end, 0, sizeof(c->tl_end) + sizeof(c->tl_ray_steps) + sizeof(c->tl_ray_ticks) + sizeof(c->tl_exit_hist),
-            ctx->stream));
-        f->timeline = 1;
-        return RT_OK;
-    }
-    if (!out) return fail(ctx, "rt_frame_debug_timeline: NULL output");
-    f->timeline = 0;
-    std::vector<unsigned long long> h(384);
-    HIPCHK(ctx, hipMemcpyAsync(h.data(), c->tl_start, 384 * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    for (int b = 0; b < 64; ++b)
-    {
-        bool ran = h[128 + b] != 0ull;
-        out[b * 6 + 0] = ran ? h[b] : 0ull;
-        out[b * 6 + 1] = ran && h[64 + b] != ~0ull ? h[64 + b] : 0ull;
-        out[b * 6 + 2] = h[128 + b];
-        out[b * 6 + 3] = h[192 + b];                    // most steps any ray took
-        out[b * 6 + 4] = h[256 + b] >> 24;              // the slowest ray: ticks from hand-out to retirement ...
-        out[b * 6 + 5] = h[256 + b] & 0xFFFFFFull;      // ... and its steps
-    }
-    for (int b = 0; b < 64; ++b) out[384 + b] = h[320 + b];   // waves that left in the b-th 25 us after the queue ran dry
     return RT_OK;
 }
 

@@ -586,7 +586,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(STACK <= 10 
 // `slow_list` and k_trace2 runs over that list afterwards.
 //   stack entry: (ref, entry distance) as in k_trace2; up to three pushes per visit.
 #define RT_LEAF_CONT_BIT 0x40000000u      // the leaf's box has been tested: this is its 2nd+ triangle
-#define RT_W4_STACK_MAX 104               // <= 3 pending slots per wide level, <= 33 wide levels + slack
+// (RT_W4_STACK_MAX, the most entries a lane's stack holds: device_scene.h)
 
 // Reads from the per-lane HBM spill area of the traversal stack (rare path).  Inline assembly on purpose: see the note
 // at the use in k_trace_w4.  The wait inside covers every outstanding vector-memory operation of the wave.
