@@ -219,6 +219,29 @@ int rt_scene_refit_buffer(rt_ctx* ctx, rt_buffer* triangles);
 int rt_scene_set_objects(rt_ctx* ctx, const uint32_t* object_of_triangle, uint32_t num_triangles, uint32_t num_objects);
 int rt_scene_pose(rt_ctx* ctx, const float* matrices3x4, uint32_t num_objects);
 
+/* The scene's triangles SKINNED from a palette of bone matrices (the character that deforms): 48 bytes per bone and frame instead of 160 bytes per triangle
+ * (linear blend skinning).  One rt_skin_influence per triangle CORNER, 3 * num_triangles of them in the upload's BVH order: v1, v2, v3 of
+ * triangle 0, then triangle 1, ...  An unused slot has weight 0 and any valid bone.  The library does not normalise weights.
+ *   rt_scene_set_skin, after rt_scene_upload on a context with RT_CTX_OPT_REFITTABLE = 1: per_corner[3 * num_triangles], every bone < num_bones and every weight
+ *     finite, is copied to the device; the scene's CURRENT pose becomes the rest pose (made from the shading records as rt_scene_set_objects makes it); the
+ *     staging area of a skin and the palette's room are allocated, so rt_scene_skin allocates nothing.  392 bytes per triangle (rest pose 160, influences 72,
+ *     staging area 160; rt_scene_tree_report's "skinned triangles" line).  Refused, with what an earlier call set left in place: a NULL argument, no scene, a
+ *     scene that is not refittable, another triangle count, num_bones == 0 or above 65536, a bone index >= num_bones, a non-finite weight.  Calling it again
+ *     replaces influences and rest pose; rt_scene_upload drops both; rt_scene_refit*, rt_scene_set_objects and rt_scene_pose leave both alone, as this leaves
+ *     the objects alone: the two states are independent, each works from its own rest pose, and whichever of pose / skin / refit ran last is the scene.
+ *   rt_scene_skin: matrices3x4[num_bones * 12], rt_scene_pose's layout.  Skins are ABSOLUTE: every call skins the rest pose, so M1 then M2 equals M2 alone.
+ *     Per corner B[k] = ((w0 M[b0][k] + w1 M[b1][k]) + w2 M[b2][k]) + w3 M[b3][k] for the 12 entries, in that order, no slot skipped; a corner whose B is bit for
+ *     bit the identity is copied; otherwise position and normal go through rt_scene_pose's arithmetic with B (cofactors, det and sign made from B per corner);
+ *     the .w lanes, texture coordinates, mtl_index and padding are copied.  So with every bone the identity, weights that blend to exactly the identity --
+ *     (1,0,0,0), (0.5,0.5,0,0) -- give the rest pose back byte for byte; weights that sum to 0 collapse a corner to the origin with a zero normal (finite:
+ *     accepted).  k_skin_triangles writes the staging area and the refit above runs on it unchanged: afterwards the context is, for every entry point and
+ *     option, bit for bit what rt_scene_refit of rt_debug_skin(NULL, ...)'s output would have left (validation first, so an overflowing skin is refused with
+ *     the scene untouched; quiescence; the kept previous pose of RT_CTX_OPT_REFIT_MOTION; the report's "refit" line).  Refused before any launch: a NULL
+ *     argument, no skin set, another num_bones, a non-finite matrix entry, everything rt_scene_refit refuses. */
+typedef struct rt_skin_influence { uint16_t bone[4]; float weight[4]; } rt_skin_influence;
+int rt_scene_set_skin(rt_ctx* ctx, const rt_skin_influence* per_corner, uint32_t num_triangles, uint32_t num_bones);
+int rt_scene_skin(rt_ctx* ctx, const float* matrices3x4, uint32_t num_bones);
+
 /* ---- ray queries: the CALLER's rays against the uploaded scene (opt-in extension).  Every other ray this library traces is one a frame
  * generated; these are a host program's own: which object lies under a pixel, visibility and probe rays, baking over the uploaded trees, collision rays against
  * a posed scene.
@@ -1029,6 +1052,12 @@ int rt_debug_refit(rt_ctx* ctx, const rt_bvh_node* nodes, uint32_t num_nodes, co
  * agree bit for bit).  Refused: a NULL array, no triangles, no objects, an index >= num_objects, a non-finite matrix entry. */
 int rt_debug_pose(rt_ctx* ctx, const rt_triangle* rest, const uint32_t* object_of_triangle, uint32_t num_triangles, const float* matrices3x4, uint32_t num_objects,
                   rt_triangle* out);
+/* The skin on its own: out[num_triangles] = rest[num_triangles] with corner c of triangle i blended by per_corner[3 i + c] from the palette (rt_scene_skin's
+ * arithmetic; .w lanes, texture coordinates, mtl_index and padding copied).  ctx == NULL: the host restatement; otherwise k_skin_triangles on uploaded copies,
+ * on ctx's device (the two agree bit for bit).  Refused: a NULL array, no triangles, num_bones == 0 or above 65536, a bone index >= num_bones, a non-finite
+ * weight, a non-finite matrix entry. */
+int rt_debug_skin(rt_ctx* ctx, const rt_triangle* rest, const rt_skin_influence* per_corner, uint32_t num_triangles, const float* matrices3x4, uint32_t num_bones,
+                  rt_triangle* out);
 /* What the last rt_scene_upload measured when it chose the trees (one line per ray population; "" when it had no choice), then the
  * latest fold adaptation's line (RT_CTX_OPT_ADAPTIVE_FOLD).  The pointer is valid until the next rt_integrate or rt_scene_upload on
  * this context (an adaptation rewrites its line): copy it. */
@@ -1113,6 +1142,7 @@ int rt_debug_eval(rt_ctx* ctx, int fn, const float* a, const float* b, float* ou
 #ifdef __cplusplus
 }
 #endif
+RT_STATIC_ASSERT(sizeof(rt_skin_influence) == 24, "rt_skin_influence");
 RT_STATIC_ASSERT(sizeof(rt_surface) == 64, "rt_surface");
 RT_STATIC_ASSERT(sizeof(rt_bake_result) == 16 && sizeof(rt_bake_desc) == 20, "rt_bake_result / rt_bake_desc");
 RT_STATIC_ASSERT(sizeof(rt_point) == 16 && sizeof(rt_nearest) == 32, "rt_point / rt_nearest");

@@ -111,6 +111,7 @@ EXPORTS = [
     "rt_frame_filter_temporal", "rt_frame_filter_history_reset", "rt_frame_read_filter_history", "rt_debug_filter_temporal",
     "rt_scene_refit", "rt_scene_refit_buffer", "rt_debug_refit",
     "rt_scene_set_objects", "rt_scene_pose", "rt_debug_pose",
+    "rt_scene_set_skin", "rt_scene_skin", "rt_debug_skin",
     "rt_frame_read_guide_motion", "rt_debug_guide_motion", "rt_debug_filter_temporal_motion",
     "rt_scene_trace", "rt_scene_trace_buffer", "rt_frame_pick", "rt_debug_query_surface",
     "rt_scene_bake", "rt_scene_bake_buffer", "rt_debug_bake_rays", "rt_debug_bake_reduce",
@@ -206,6 +207,8 @@ def load():
         "rt_debug_refit": (i32, [vp, vp, u32, vp, u32, vp, u32, u32, vp, vp]),
         "rt_scene_set_objects": (i32, [vp, vp, u32, u32]), "rt_scene_pose": (i32, [vp, vp, u32]),
         "rt_debug_pose": (i32, [vp, vp, vp, u32, vp, u32, vp]),
+        "rt_scene_set_skin": (i32, [vp, vp, u32, u32]), "rt_scene_skin": (i32, [vp, vp, u32]),
+        "rt_debug_skin": (i32, [vp, vp, vp, u32, vp, u32, vp]),
         "rt_frame_read_guide_motion": (i32, [vp, vp, vp]),
         "rt_debug_guide_motion": (i32, [vp, u32, vp, vp, u32, vp, vp]),
         "rt_debug_filter_temporal_motion": (i32, [vp, u32, u32, vp, vp] + [vp] * 10 + [C.POINTER(rt_temporal_filter_desc), vp, vp, vp]),
@@ -380,6 +383,38 @@ def debug_pose(ctx, rest, object_of_triangle, matrices, num_objects=None):
     out = np.zeros_like(tris)
     handle = ctx.handle if ctx is not None else None
     rc = lib.rt_debug_pose(handle, tris.ctypes.data, ids.ctypes.data, len(tris), m.ctypes.data, len(m) if num_objects is None else num_objects, out.ctypes.data)
+    if rc != 0:
+        raise RtError(lib.rt_last_error(handle).decode())
+    return out
+
+
+SKIN_LDS_BONES, SKIN_MAX_BONES = 128, 65536     # skin_host.h: the largest palette k_skin_triangles stages in LDS (above it: gathered through L1 / L2); the most bones
+
+
+def _influences(per_corner, num_triangles, who):
+    """types.skin_influence[3 * num_triangles], from that or from [num_triangles, 3] of it"""
+    f = np.ascontiguousarray(per_corner)
+    if f.dtype != T.skin_influence:
+        raise RtError(who + ": influences must be types.skin_influence records (types.influences packs bones and weights)")
+    f = f.reshape(-1)
+    if num_triangles is not None and len(f) != 3 * num_triangles:
+        raise RtError(who + ": three influences per triangle")
+    if len(f) % 3:
+        raise RtError(who + ": three influences per triangle")
+    return f
+
+
+def debug_skin(ctx, rest, influences, matrices, num_bones=None):
+    """rt_debug_skin: `rest` (types.triangle) with corner c of triangle i blended by influences[3 i + c] (types.skin_influence; types.influences packs them)
+    from the palette `matrices` (float32[num_bones, 3, 4], rt_scene_pose's layout).  ctx None = the host restatement, else skin.hip's kernel on ctx's GPU.
+    Returns the skinned triangles."""
+    lib = load()
+    tris = np.ascontiguousarray(rest, T.triangle)
+    f = _influences(influences, len(tris), "debug_skin")
+    m = _matrices3x4(matrices, "debug_skin")
+    out = np.zeros_like(tris)
+    handle = ctx.handle if ctx is not None else None
+    rc = lib.rt_debug_skin(handle, tris.ctypes.data, f.ctypes.data, len(tris), m.ctypes.data, len(m) if num_bones is None else num_bones, out.ctypes.data)
     if rc != 0:
         raise RtError(lib.rt_last_error(handle).decode())
     return out
@@ -1041,6 +1076,19 @@ class Context:
         device and refitted as refit_scene() would.  Frames keep their sums: reset() them."""
         m = _matrices3x4(matrices, "pose_scene")
         _check(self.lib, self.handle, self.lib.rt_scene_pose(self.handle, m.ctypes.data, len(m)))
+
+    def set_skin(self, influences, num_bones):
+        """rt_scene_set_skin: four bones and weights per triangle CORNER of the uploaded scene (types.skin_influence[3 * triangles] or [triangles, 3], the
+        upload's order; types.influences packs them).  The scene's current pose becomes the rest pose of skin_scene(); needs set_refittable() before
+        upload_scene().  392 bytes per triangle on the device.  Independent of set_objects()."""
+        f = _influences(influences, None, "set_skin")
+        _check(self.lib, self.handle, self.lib.rt_scene_set_skin(self.handle, f.ctypes.data, len(f) // 3, num_bones))
+
+    def skin_scene(self, matrices):
+        """rt_scene_skin: the rest pose skinned by a palette of one matrix per bone (float32[num_bones, 3, 4]; absolute, never relative to the last skin),
+        written on the device and refitted as refit_scene() would.  Frames keep their sums: reset() them."""
+        m = _matrices3x4(matrices, "skin_scene")
+        _check(self.lib, self.handle, self.lib.rt_scene_skin(self.handle, m.ctypes.data, len(m)))
 
     def trace(self, rays, any_hit=False, surfaces=False):
         """rt_scene_trace: the caller's rays (ray_records' rule) against the uploaded scene.  Closest hits: types.hit[n], or (hits, types.surface[n]) with

@@ -26,6 +26,7 @@
 #include "device_fold.h"     // ... and the fold + crossing counts on the device (device_fold.hip)
 #include "refit.h"           // the refit of the scene's trees when its triangles move (refit.hip)
 #include "pose_host.h"       // the scene's objects posed from one matrix per object (pose.hip)
+#include "skin_host.h"       // the scene's triangles skinned from a palette of bone matrices (skin.hip)
 #include "filters_host.h"    // filt::snapshot_pose, the pose a refit replaces (filters.hip)
 #include "device_memory.h"   // who owns a device allocation: dev::Mem
 using namespace rtw;
@@ -512,6 +513,7 @@ void context::free_scene(Scene& s)
     if (s.refit) { refit::release(*s.refit); delete s.refit; }
     if (s.pose_snap) (void)hipFree(s.pose_snap);
     if (s.pose) { pose::release(*s.pose); delete s.pose; }
+    if (s.skin) { skin::release(*s.skin); delete s.skin; }
     delete s.leaf_starts;
     s = Scene();
 }
@@ -1051,6 +1053,21 @@ int rt_debug_refit(rt_ctx* ctx, const rt_bvh_node* nodes, uint32_t num_nodes, co
 // ---- posed objects: rt_scene_set_objects / rt_scene_pose / rt_debug_pose, the bookkeeping around pose.hip's kernels -------------
 // A pose IS a refit: rt_scene_pose writes the posed triangles into the staging area rt_scene_set_objects allocated and hands it to refit_device() unchanged.
 
+// the report keeps one line that begins with `prefix`, before the refit's own (which is replaced, with all that follows it, by every refit)
+static void keep_one_line_before_refit(std::string& r, const char* prefix, const char* line)
+{
+    auto line_that_begins = [&r](const char* word)                   // only at the start of a line: another line may hold the word
+    {
+        size_t at = r.find(word);
+        while (at != std::string::npos && at != 0 && r[at - 1] != '\n') at = r.find(word, at + 1);
+        return at;
+    };
+    const size_t old = line_that_begins(prefix);
+    if (old != std::string::npos) r.erase(old, r.find('\n', old) == std::string::npos ? std::string::npos : r.find('\n', old) - old + 1);
+    const size_t at = line_that_begins("refit ");
+    r.insert(at == std::string::npos ? r.size() : at, line);
+}
+
 int rt_scene_set_objects(rt_ctx* ctx, const uint32_t* object_of_triangle, uint32_t num_triangles, uint32_t num_objects)
 {
     if (!ctx || !object_of_triangle) return fail(ctx, "rt_scene_set_objects: NULL argument");
@@ -1067,21 +1084,10 @@ int rt_scene_set_objects(rt_ctx* ctx, const uint32_t* object_of_triangle, uint32
     }
     if (s.pose) { pose::release(*s.pose); delete s.pose; }
     s.pose = st;
-    // the report keeps one such line, before the refit's own (which is replaced, with all that follows it, by every refit)
     char line[300];
     snprintf(line, sizeof(line), "posed objects: %u objects, %u bytes per triangle kept (%.1f MB): rest pose %u + object index %u + staging area %u\n", num_objects,
         (unsigned)pose::BYTES_PER_TRIANGLE, (double)s.n_tris * pose::BYTES_PER_TRIANGLE / 1e6, (unsigned)pose::REST_BYTES, (unsigned)pose::ID_BYTES, (unsigned)pose::STAGED_BYTES);
-    std::string& r = s.tree_report;
-    auto line_that_begins = [&r](const char* prefix)                 // only at the start of a line: another line may hold the word
-    {
-        size_t at = r.find(prefix);
-        while (at != std::string::npos && at != 0 && r[at - 1] != '\n') at = r.find(prefix, at + 1);
-        return at;
-    };
-    const size_t old = line_that_begins("posed objects: ");
-    if (old != std::string::npos) r.erase(old, r.find('\n', old) == std::string::npos ? std::string::npos : r.find('\n', old) - old + 1);
-    const size_t at = line_that_begins("refit ");
-    r.insert(at == std::string::npos ? r.size() : at, line);
+    keep_one_line_before_refit(s.tree_report, "posed objects: ", line);
     return RT_OK;
 }
 
@@ -1114,6 +1120,77 @@ int rt_debug_pose(rt_ctx* ctx, const rt_triangle* rest, const uint32_t* object_o
     (void)hipSetDevice(ctx->device);
     if (!pose::debug_device(ctx->stream, rest, object_of_triangle, num_triangles, matrices3x4, num_objects, out))
         return fail(ctx, "rt_debug_pose: the device path failed (allocation, copy or launch)");
+    return RT_OK;
+}
+
+// ---- skinned triangles: rt_scene_set_skin / rt_scene_skin / rt_debug_skin, the bookkeeping around skin.hip's kernels --------------
+// A skin IS a refit, as a pose is: rt_scene_skin writes the skinned triangles into the staging area rt_scene_set_skin allocated and hands it to refit_device()
+// unchanged.  The skin's state and the objects' are independent: each keeps a rest pose of its own, and whichever of pose / skin / refit ran last is the scene.
+
+static int skin_table_refused(rt_ctx* ctx, const char* who, const rt_skin_influence* per_corner, uint32_t num_triangles, uint32_t num_bones)
+{
+    const std::string name(who);
+    if (num_bones == 0u) return fail(ctx, name + ": no bones");
+    if (num_bones > (uint32_t)skin::MAX_BONES) return fail(ctx, name + ": more than 65536 bones (a bone index is 16 bits)");
+    switch (skin::influences_fault(per_corner, num_triangles, num_bones))
+    {
+    case 0: return RT_OK;
+    case 1: return fail(ctx, name + ": a bone index is not below num_bones");
+    default: return fail(ctx, name + ": a weight is not finite");
+    }
+}
+
+int rt_scene_set_skin(rt_ctx* ctx, const rt_skin_influence* per_corner, uint32_t num_triangles, uint32_t num_bones)
+{
+    if (!ctx || !per_corner) return fail(ctx, "rt_scene_set_skin: NULL argument");
+    if (refit_refused(ctx, "rt_scene_set_skin", num_triangles, false) != RT_OK) return RT_ERROR;
+    if (skin_table_refused(ctx, "rt_scene_set_skin", per_corner, num_triangles, num_bones) != RT_OK) return RT_ERROR;
+    (void)hipSetDevice(ctx->device);
+    Scene& s = ctx->scene;
+    skin::State* st = new skin::State();
+    if (!skin::arm(ctx->stream, *st, (const float4*)s.tris_sh, per_corner, num_triangles, num_bones))
+    {
+        delete st;
+        return fail(ctx, "rt_scene_set_skin: the rest pose, the influences and the staging area could not be allocated");
+    }
+    if (s.skin) { skin::release(*s.skin); delete s.skin; }
+    s.skin = st;
+    char line[300];
+    snprintf(line, sizeof(line), "skinned triangles: %u bones, %u bytes per triangle kept (%.1f MB): rest pose %u + influences %u + staging area %u; the palette %u bytes per bone\n",
+        num_bones, (unsigned)skin::BYTES_PER_TRIANGLE, (double)s.n_tris * skin::BYTES_PER_TRIANGLE / 1e6, (unsigned)skin::REST_BYTES, (unsigned)skin::INFLUENCE_BYTES,
+        (unsigned)skin::STAGED_BYTES, (unsigned)skin::MATRIX_BYTES);
+    keep_one_line_before_refit(s.tree_report, "skinned triangles: ", line);
+    return RT_OK;
+}
+
+int rt_scene_skin(rt_ctx* ctx, const float* matrices3x4, uint32_t num_bones)
+{
+    if (!ctx || !matrices3x4) return fail(ctx, "rt_scene_skin: NULL argument");
+    Scene& s = ctx->scene;
+    if (refit_refused(ctx, "rt_scene_skin", s.n_tris, false) != RT_OK) return RT_ERROR;
+    if (!s.skin) return fail(ctx, "rt_scene_skin: no skin (rt_scene_set_skin has not been called for this scene)");
+    if (num_bones != s.skin->n_bones) return fail(ctx, "rt_scene_skin: the bone count differs from rt_scene_set_skin's");
+    if (!skin::matrices_finite(matrices3x4, num_bones)) return fail(ctx, "rt_scene_skin: a matrix entry is not finite");
+    (void)hipSetDevice(ctx->device);
+    if (!skin::run(ctx->stream, *s.skin, matrices3x4))
+    {
+        (void)hipGetLastError();
+        return fail(ctx, "rt_scene_skin: the skin kernel could not be launched");
+    }
+    return refit_device(ctx, s.skin->staged, "rt_scene_skin");
+}
+
+int rt_debug_skin(rt_ctx* ctx, const rt_triangle* rest, const rt_skin_influence* per_corner, uint32_t num_triangles, const float* matrices3x4, uint32_t num_bones,
+    rt_triangle* out)
+{
+    if (!rest || !per_corner || !matrices3x4 || !out) return fail(ctx, "rt_debug_skin: NULL argument");
+    if (num_triangles == 0u) return fail(ctx, "rt_debug_skin: no triangles");
+    if (skin_table_refused(ctx, "rt_debug_skin", per_corner, num_triangles, num_bones) != RT_OK) return RT_ERROR;
+    if (!skin::matrices_finite(matrices3x4, num_bones)) return fail(ctx, "rt_debug_skin: a matrix entry is not finite");
+    if (!ctx) { skin::debug_host(rest, per_corner, num_triangles, matrices3x4, num_bones, out); return RT_OK; }
+    (void)hipSetDevice(ctx->device);
+    if (!skin::debug_device(ctx->stream, rest, per_corner, num_triangles, matrices3x4, num_bones, out))
+        return fail(ctx, "rt_debug_skin: the device path failed (allocation, copy or launch)");
     return RT_OK;
 }
 

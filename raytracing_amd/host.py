@@ -28,6 +28,7 @@ EXPORTS = [
     "rth_render_set_objects", "rth_render_pose", "rth_render_pick", "rth_render_integrator_pick", "rth_render_trace",
     "rth_render_bake", "rth_render_occlusion_image", "rth_render_nearest", "rth_render_within", "rth_render_overlap", "rth_render_cross", "rth_render_self_cross", "rth_render_separation", "rth_render_clearance", "rth_render_select", "rth_render_pick_rect", "rth_render_integrator_pick_rect", "rth_render_trace_all", "rth_render_pick_all",
     "rth_scene_set_triangle_objects", "rth_scene_num_objects", "rth_scene_object_name", "rth_scene_num_triangle_objects", "rth_scene_triangle_objects",
+    "rth_render_set_skin", "rth_render_skin", "rth_scene_set_triangle_skin", "rth_scene_num_triangle_skin", "rth_scene_triangle_skin",
 ]
 
 
@@ -74,6 +75,8 @@ def load():
         "rth_render_set_refittable": (i32, [vp, i32]), "rth_render_refit": (i32, [vp, vp, u32]),
         "rth_render_set_refit_motion": (i32, [vp, i32]),
         "rth_render_set_objects": (i32, [vp, vp, u32, u32]), "rth_render_pose": (i32, [vp, vp, u32]),
+        "rth_render_set_skin": (i32, [vp, vp, u32, u32]), "rth_render_skin": (i32, [vp, vp, u32]),
+        "rth_scene_set_triangle_skin": (i32, [vp, vp, u32]), "rth_scene_num_triangle_skin": (u32, [vp]), "rth_scene_triangle_skin": (vp, [vp]),
         "rth_render_pick": (i32, [vp, u32, u32, vp, vp, vp]), "rth_render_integrator_pick": (i32, [vp, u32, u32, vp, vp, vp]), "rth_render_trace": (i32, [vp, vp, u32, i32, vp, vp, vp]),
         "rth_render_bake": (i32, [vp, vp, u32, vp, vp]), "rth_render_occlusion_image": (i32, [vp, vp, vp]),
         "rth_render_nearest": (i32, [vp, vp, u32, vp, vp]),
@@ -156,12 +159,18 @@ class Scene:
     _GETTERS = (("triangles", T.triangle), ("materials", T.packed_material), ("textures", T.texture),
                 ("texture_data", np.uint32), ("lights", T.light), ("emissive", np.uint32))
 
-    def __init__(self, path=None, scale=1.0, flip_yz=False, arrays=None, wide_texture_indices=False, emissive_nee=False, objects=False):
+    def __init__(self, path=None, scale=1.0, flip_yz=False, arrays=None, wide_texture_indices=False, emissive_nee=False, objects=False, skin=None):
         """wide_texture_indices / emissive_nee / objects: this repository's opt-in extensions (rt::Scene::Options).  objects=True numbers the OBJ's o / g
         shapes; with arrays=, `objects` (or arrays["objects"]) is the object index of every triangle (uint32).  Either way object_names() and, after
-        build_bvh() and finalize(), triangle_objects() say which triangles are which object: what Render.set_objects() takes."""
+        build_bvh() and finalize(), triangle_objects() say which triangles are which object: what Render.set_objects() takes.
+        skin=(bones, weights), with arrays= only: int[n, 3, 4] and float[n, 3, 4], four bones and weights per corner of arrays["triangles"] in that order
+        (types.influences' rule); after build_bvh() and finalize(), triangle_skin() gives them in the built order and num_bones() their count (the highest
+        index + 1): what Render.set_skin() takes."""
         self.lib = load()
         self.bvh = None
+        self._num_bones = 0
+        if skin is not None and arrays is None:
+            raise RtError("Scene: skin= needs arrays= (an OBJ carries no weights)")
         if arrays is not None:
             a = {k: np.ascontiguousarray(v) for k, v in arrays.items()}
             p = lambda x: x.ctypes.data if x.size else None
@@ -180,6 +189,16 @@ class Scene:
                 ids = np.ascontiguousarray(ids, np.uint32)
                 if self.lib.rth_scene_set_triangle_objects(self.handle, ids.ctypes.data, ids.size, None, 0):
                     raise _err(self.lib)
+            if self.handle and skin is not None:
+                try:
+                    f = np.ascontiguousarray(T.influences(*skin))
+                except ValueError as e:
+                    raise RtError("Scene: " + str(e))
+                if len(f) != len(a["triangles"]):
+                    raise RtError("Scene: skin= wants one row of three corners per triangle")
+                if self.lib.rth_scene_set_triangle_skin(self.handle, f.ctypes.data, len(f)):
+                    raise _err(self.lib)
+                self._num_bones = int(f["bone"].max()) + 1 if f.size else 0
         else:
             self.handle = self.lib.rth_scene_load_ex(path.encode(), scale, int(flip_yz),
                                                      (1 if wide_texture_indices else 0) | (2 if emissive_nee else 0) | (4 if objects else 0))
@@ -219,6 +238,16 @@ class Scene:
         """Scene::GetTriangleObjects: the object of every triangle, in the triangles' order after build_bvh() and finalize() (empty before)"""
         n = self.lib.rth_scene_num_triangle_objects(self.handle)
         return _arr(self.lib.rth_scene_triangle_objects(self.handle), n, np.uint32).copy() if n else np.zeros(0, np.uint32)
+
+    def triangle_skin(self):
+        """Scene::GetTriangleSkin: types.skin_influence[triangles, 3], in the triangles' order after build_bvh() and finalize() (the caller's before; empty
+        without skin=)"""
+        n = self.lib.rth_scene_num_triangle_skin(self.handle)
+        return _arr(self.lib.rth_scene_triangle_skin(self.handle), n, T.skin_influence).reshape(-1, 3)
+
+    def num_bones(self):
+        """the highest bone index of skin= plus one (0 without a skin)"""
+        return self._num_bones
 
     def save_cache(self, path):
         """Binary scene cache: reordered triangles + BVH nodes + materials + textures; Scene(path) loads it."""
@@ -393,6 +422,35 @@ class Render:
         except capi.RtError as e:
             raise RtError(str(e))
         self._c(self.lib.rth_render_pose(self.handle, m.ctypes.data, len(m)))
+
+    def set_skin(self, influences=None, num_bones=None):
+        """Four bones and weights per triangle corner (types.skin_influence[triangles, 3] or flat, the BVH order of scene_arrays()['triangles']), after
+        set_refittable(): the scene's current pose becomes the rest pose of skin().  Default: the scene's own table (Scene(arrays=, skin=): triangle_skin(),
+        num_bones()).  An upload (set_refittable, set_ctx_option, ...) drops the skin: set it again.  Independent of set_objects()."""
+        from . import capi
+        if influences is None:
+            influences = self.scene.triangle_skin()
+            if not len(influences):
+                raise RtError("set_skin: the scene carries no skin (Scene(arrays=, skin=)) and none was given")
+            num_bones = self.scene.num_bones() if num_bones is None else num_bones
+        if num_bones is None:
+            raise RtError("set_skin: num_bones is needed with influences of the caller's own")
+        try:
+            f = capi._influences(influences, None, "set_skin")
+        except capi.RtError as e:
+            raise RtError(str(e))
+        self._c(self.lib.rth_render_set_skin(self.handle, f.ctypes.data, len(f) // 3, num_bones))
+
+    def skin(self, matrices):
+        """The bones moved: one row-major 3x4 matrix per bone (float32[num_bones, 3, 4] or [num_bones, 12], the translation in the fourth column), always
+        applied to the rest pose.  The skinned triangles are written and refitted on the device and the accumulation restarts; results equal refit() of the
+        same triangles."""
+        from . import capi
+        try:
+            m = capi._matrices3x4(matrices, "skin")
+        except capi.RtError as e:
+            raise RtError(str(e))
+        self._c(self.lib.rth_render_skin(self.handle, m.ctypes.data, len(m)))
 
     def pick(self, x, y):
         """What lies under the centre of pixel (x, y) of the Render's current camera, also one set since the last frame (Render::Pick; the frame is not touched): a dict of the surface's fields (primitive_id

@@ -171,6 +171,17 @@ void HIPPathTraceIntegrator::PoseObjects(float const* matrices3x4, std::size_t o
     RequestReset();
 }
 
+void HIPPathTraceIntegrator::SetSkin(rt_skin_influence const* per_corner, std::size_t triangle_count, std::uint32_t bone_count)
+{
+    Check(rt_scene_set_skin(context_.Get(), per_corner, (uint32_t)triangle_count, bone_count));
+}
+
+void HIPPathTraceIntegrator::SkinBones(float const* matrices3x4, std::size_t bone_count)
+{
+    Check(rt_scene_skin(context_.Get(), matrices3x4, (uint32_t)bone_count));
+    RequestReset();
+}
+
 void HIPPathTraceIntegrator::TraceRays(rt_ray const* rays, std::size_t count, bool any_hit, rt_hit* hits, std::uint32_t* occluded, rt_surface* surfaces)
 {
     if (count > 0xFFFFFFFFull) throw HIPException("HIPPathTraceIntegrator::TraceRays: more than 2^32 - 1 rays in one call");

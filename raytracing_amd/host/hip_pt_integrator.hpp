@@ -102,6 +102,12 @@ public:
     // HIPException with the library's message on a refusal.
     void SetObjects(std::uint32_t const* object_of_triangle, std::size_t triangle_count, std::uint32_t object_count);
     void PoseObjects(float const* matrices3x4, std::size_t object_count);
+    // Skinned triangles (rt_scene_set_skin / rt_scene_skin), after SetRefittable(true) and UploadGPUData.  SetSkin: four bones and weights
+    // per triangle corner, 3 * triangle_count records in the uploaded BVH order (Scene::GetTriangleSkin); the scene's current pose becomes the rest pose; dropped
+    // by the next UploadGPUData; independent of SetObjects.  SkinBones: one row-major 3x4 matrix per bone, absolute; the triangles are written and refitted on
+    // the device; requests a reset.  Both throw HIPException with the library's message on a refusal.
+    void SetSkin(rt_skin_influence const* per_corner, std::size_t triangle_count, std::uint32_t bone_count);
+    void SkinBones(float const* matrices3x4, std::size_t bone_count);
     // Ray queries (rt_scene_trace / rt_frame_pick): the caller's rays against the uploaded scene as it is posed now.  TraceRays: closest hits
     // (hits and / or surfaces, either may be null) or, any_hit, one 0 / 1 word per ray in occluded; a count of 2^32 or more is refused.  Pick: the ray through the
     // centre of pixel (x, y) of the frame's current camera, its hit and surface (any may be null).  PickThrough: the same for a camera the frame has not been given

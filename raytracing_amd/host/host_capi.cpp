@@ -68,6 +68,13 @@ uint32_t rth_scene_num_objects(void* s) { return (uint32_t)((rt::Scene*)s)->GetO
 const char* rth_scene_object_name(void* s, uint32_t i) { return ((rt::Scene*)s)->GetObjectNames()[i].c_str(); }
 uint32_t rth_scene_num_triangle_objects(void* s) { return (uint32_t)((rt::Scene*)s)->GetTriangleObjects().size(); }
 const void* rth_scene_triangle_objects(void* s) { return ((rt::Scene*)s)->GetTriangleObjects().data(); }
+// SetTriangleSkin / GetTriangleSkin: three influences per triangle, the caller's triangle order in, the BVH's out (after Finalize)
+int rth_scene_set_triangle_skin(void* s, const rt_skin_influence* per_corner, uint32_t num_triangles)
+{
+    return guard([&]() { ((rt::Scene*)s)->SetTriangleSkin(std::vector<rt_skin_influence>(per_corner, per_corner + (size_t)num_triangles * 3)); return 0; }, 1);
+}
+uint32_t rth_scene_num_triangle_skin(void* s) { return (uint32_t)((rt::Scene*)s)->GetTriangleSkin().size(); }
+const void* rth_scene_triangle_skin(void* s) { return ((rt::Scene*)s)->GetTriangleSkin().data(); }
 
 void rth_scene_destroy(void* s) { delete (rt::Scene*)s; }
 void rth_scene_add_directional_light(void* s, float dx, float dy, float dz, float r, float g, float b)
@@ -256,6 +263,11 @@ int rth_render_set_objects(void* r, const uint32_t* object_of_triangle, uint32_t
     return guard([&]() { ((rt::Render*)r)->SetObjects(object_of_triangle, num_triangles, num_objects); return 0; }, 1);
 }
 int rth_render_pose(void* r, const float* matrices3x4, uint32_t num_objects) { return guard([&]() { ((rt::Render*)r)->PoseObjects(matrices3x4, num_objects); return 0; }, 1); }
+int rth_render_set_skin(void* r, const rt_skin_influence* per_corner, uint32_t num_triangles, uint32_t num_bones)
+{
+    return guard([&]() { ((rt::Render*)r)->SetSkin(per_corner, num_triangles, num_bones); return 0; }, 1);
+}
+int rth_render_skin(void* r, const float* matrices3x4, uint32_t num_bones) { return guard([&]() { ((rt::Render*)r)->SkinBones(matrices3x4, num_bones); return 0; }, 1); }
 int rth_render_pick(void* r, uint32_t x, uint32_t y, rt_ray* ray, rt_hit* hit, rt_surface* surface) { return guard([&]() { ((rt::Render*)r)->Pick(x, y, ray, hit, surface); return 0; }, 1); }
 // HIPPathTraceIntegrator::Pick itself: the FRAME's camera (what the last RenderFrame / RenderSamples handed over), where rth_render_pick uses the Render's
 int rth_render_integrator_pick(void* r, uint32_t x, uint32_t y, rt_ray* ray, rt_hit* hit, rt_surface* surface)

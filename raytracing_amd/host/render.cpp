@@ -175,6 +175,16 @@ void TiledRender::PoseObjects(float const* matrices3x4, std::size_t object_count
     for (auto& i : integrators_) i->PoseObjects(matrices3x4, object_count);
 }
 
+void TiledRender::SetSkin(rt_skin_influence const* per_corner, std::size_t triangle_count, std::uint32_t bone_count)
+{
+    for (auto& i : integrators_) i->SetSkin(per_corner, triangle_count, bone_count);
+}
+
+void TiledRender::SkinBones(float const* matrices3x4, std::size_t bone_count)
+{
+    for (auto& i : integrators_) i->SkinBones(matrices3x4, bone_count);
+}
+
 void TiledRender::SetMaxBounces(std::uint32_t max_bounces)
 {
     for (auto& i : integrators_) i->SetMaxBounces(max_bounces);

@@ -41,6 +41,11 @@ public:
     // matrix per object and pose -- 12 floats per object instead of RefitGeometry's 160 bytes per triangle.  An upload drops the objects: set them again.
     void SetObjects(std::uint32_t const* object_of_triangle, std::size_t triangle_count, std::uint32_t object_count) { integrator_->SetObjects(object_of_triangle, triangle_count, object_count); }
     void PoseObjects(float const* matrices3x4, std::size_t object_count) { integrator_->PoseObjects(matrices3x4, object_count); }
+    // Skinned triangles, after SetRefittable(true): four bones and weights per triangle corner (the finalised scene's BVH order:
+    // Scene::GetTriangleSkin), then one 3x4 matrix per bone and frame -- 48 bytes per bone instead of RefitGeometry's 160 bytes per triangle.  An upload drops
+    // the skin: set it again.
+    void SetSkin(rt_skin_influence const* per_corner, std::size_t triangle_count, std::uint32_t bone_count) { integrator_->SetSkin(per_corner, triangle_count, bone_count); }
+    void SkinBones(float const* matrices3x4, std::size_t bone_count) { integrator_->SkinBones(matrices3x4, bone_count); }
     // Ray queries: what lies under pixel (x, y) of the Render's current camera -- also one set since the last frame, which the integrator
     // has not been given yet: the ray is made from it here and traced as a query, the frame (its camera and previous camera included) is not touched -- and the
     // caller's own rays against the scene as it is posed now
@@ -116,7 +121,10 @@ public:
     // posed objects, forwarded to every tile's context likewise (tiles work because the refit does)
     void SetObjects(std::uint32_t const* object_of_triangle, std::size_t triangle_count, std::uint32_t object_count);
     void PoseObjects(float const* matrices3x4, std::size_t object_count);
-    void RenderSamples(std::uint32_t n);                  // every tile, concurrently; returns when all are enqueued and finished
+    // skinned triangles, likewise
+    void SetSkin(rt_skin_influence const* per_corner, std::size_t triangle_count, std::uint32_t bone_count);
+    void SkinBones(float const* matrices3x4, std::size_t bone_count);
+    void RenderSamples(std::uint32_t n);               // every tile, concurrently; returns when all are enqueued and finished
     std::vector<float> GatherRadiance(int root = 0);      // height x width x RGBA running sums, image order
     rt_stats GetStats() const;                            // ray counters summed over the tiles
     std::size_t GetTileCount() const { return integrators_.size(); }

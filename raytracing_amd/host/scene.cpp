@@ -423,6 +423,14 @@ void Scene::SetTriangleObjects(std::vector<std::uint32_t> const& object_of_trian
     objects_in_padding_ = true;
 }
 
+void Scene::SetTriangleSkin(std::vector<rt_skin_influence> per_corner)
+{
+    if (per_corner.size() != triangles_.size() * 3) throw std::runtime_error("SetTriangleSkin: three influences per triangle expected");
+    for (std::size_t i = 0; i < triangles_.size(); ++i) triangles_[i].padding[1] = (std::uint32_t)i;
+    triangle_skin_ = std::move(per_corner);
+    skin_in_padding_ = true;
+}
+
 void Scene::Load(const char* filename, float scale, bool flip_yz)
 {
     std::string fname(filename);
@@ -697,6 +705,19 @@ void Scene::Finalize()   // scene.cpp:353-361
         triangle_objects_.resize(triangles_.size());
         for (std::size_t i = 0; i < triangles_.size(); ++i) { triangle_objects_[i] = triangles_[i].padding[0]; triangles_[i].padding[0] = 0u; }
         objects_in_padding_ = false;
+    }
+    if (skin_in_padding_)                                    // the source indices have come through the reorder: the influences follow their triangles
+    {
+        std::vector<rt_skin_influence> ordered(triangle_skin_.size());
+        for (std::size_t i = 0; i < triangles_.size(); ++i)
+        {
+            const std::size_t from = triangles_[i].padding[1];
+            if (from >= triangles_.size()) throw std::runtime_error("Finalize: a triangle's source index did not survive the BVH build");
+            for (int c = 0; c < 3; ++c) ordered[i * 3 + c] = triangle_skin_[from * 3 + c];
+            triangles_[i].padding[1] = 0u;
+        }
+        triangle_skin_ = std::move(ordered);
+        skin_in_padding_ = false;
     }
     CollectEmissiveTriangles();
     scene_info_.analytic_light_count = (std::uint32_t)lights_.size();

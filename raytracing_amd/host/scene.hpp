@@ -6,6 +6,7 @@
 #include <unordered_map>
 #include <vector>
 #include "structures.hpp"
+#include "rt_hip.h"          // rt_skin_influence
 
 namespace rt
 {
@@ -75,6 +76,12 @@ public:
     std::vector<std::string> const& GetObjectNames() const { return object_names_; }
     std::vector<std::uint32_t> const& GetTriangleObjects() const { return triangle_objects_; }
     void SetTriangleObjects(std::vector<std::uint32_t> const& object_of_triangle, std::vector<std::string> names);   // before the BVH is built
+    // extension: four bones and weights per triangle corner, three records per triangle in the CALLER's triangle order, given before the
+    // BVH is built; after Finalize() GetTriangleSkin() returns them in the order the triangles then have (the BVH's): what Render::SetSkin takes.  A triangle's
+    // source index rides in Triangle::padding[1] through Bvh::BuildCPU's reorder, as the object index rides in padding[0]; Finalize() zeroes it again.  Without
+    // a skin the loaded bytes are the reference's.  A scene cache does not keep a skin.
+    void SetTriangleSkin(std::vector<rt_skin_influence> per_corner);
+    std::vector<rt_skin_influence> const& GetTriangleSkin() const { return triangle_skin_; }
 
 private:
     void Load(const char* filename, float scale, bool flip_yz);
@@ -97,6 +104,8 @@ private:
     bool objects_in_padding_ = false;                       // between Load / SetTriangleObjects and Finalize
     std::vector<std::string> object_names_;
     std::vector<std::uint32_t> triangle_objects_;
+    bool skin_in_padding_ = false;                          // between SetTriangleSkin and Finalize
+    std::vector<rt_skin_influence> triangle_skin_;          // the caller's order until Finalize, the BVH's after
     SceneInfo scene_info_ = {};
     Image env_image_;
     std::string env_path_ = "assets/ibl/CGSkies_0036_free.hdr";

@@ -494,6 +494,67 @@ def shader_balls_obj(directory, tris_per_ball=20_000):
     return path
 
 
+# --------------------------------------------------------------------------
+# a synthetic skin for any mesh (rt_scene_set_skin / rt_scene_skin)
+# --------------------------------------------------------------------------
+def _corner_positions(triangles):
+    """float32[n, 3, 3]: (triangle, corner, coordinate)"""
+    return np.stack([np.stack([triangles[v]["position"][c] for c in "xyz"], -1) for v in ("v1", "v2", "v3")], 1)
+
+
+def skin_extent(triangles, axis=None):
+    """(axis, lo, hi): the axis synthetic_skin's bones lie along -- the longest of the corners' bounding box unless given -- and the box's ends on it"""
+    p = _corner_positions(triangles).reshape(-1, 3).astype(np.float64)
+    lo, hi = p.min(0), p.max(0)
+    axis = int(np.argmax(hi - lo)) if axis is None else int(axis)
+    return axis, float(lo[axis]), float(hi[axis])
+
+
+def synthetic_skin(triangles, n_bones, axis=None):
+    """(bones uint16[n, 3, 4], weights float32[n, 3, 4]) for types.influences: n_bones bones, bone k = cell k of n_bones equal cells along the longest axis of
+    the mesh (or `axis`).  A corner is weighted linearly between the two nearest cell centres -- all of the first (last) bone before the first (after the last)
+    centre -- AS A FUNCTION OF ITS POSITION ONLY: corners that share a position share influences, so the skinned mesh does not crack.  Slots 2 and 3 are
+    unused (weight 0 on slot 0's bone).  w0 = 1 - w1 in binary32, so a corner's weights sum to 1 within an ulp.  Deterministic."""
+    if not 1 <= n_bones <= 65536:
+        raise ValueError("synthetic_skin: 1 to 65536 bones")
+    axis, lo, hi = skin_extent(triangles, axis)
+    x = _corner_positions(triangles)[:, :, axis].astype(np.float64)
+    t = (x - lo) / (hi - lo) * n_bones - 0.5 if hi > lo else np.zeros_like(x)      # in cells, 0 at the first cell's centre
+    t = np.clip(t, 0.0, float(n_bones - 1))
+    k = np.minimum(np.floor(t), max(n_bones - 2, 0)).astype(np.int64)
+    w1 = (t - k).astype(np.float32)
+    bones = np.zeros(x.shape + (4,), np.uint16)
+    weights = np.zeros(x.shape + (4,), np.float32)
+    bones[..., 0] = bones[..., 2] = bones[..., 3] = k
+    bones[..., 1] = np.minimum(k + 1, n_bones - 1)
+    weights[..., 1] = w1
+    weights[..., 0] = np.float32(1.0) - w1
+    return bones, weights
+
+
+def bend_palette(n_bones, angle, axis=0, lo=0.0, hi=1.0, about=None, centre=(0.0, 0.0, 0.0)):
+    """float32[n_bones, 3, 4]: a smooth bend of synthetic_skin's chain of bones by `angle` radians in all.  Bone 0 stands; bone k turns by angle / (n_bones - 1)
+    against bone k - 1 about the direction `about` (a coordinate axis, default the one after `axis`) through the joint between their cells: the point of
+    `centre` moved to lo + k (hi - lo) / n_bones on `axis` (skin_extent gives axis, lo, hi).  Computed in binary64, rounded once.  Deterministic."""
+    about = (axis + 1) % 3 if about is None else int(about)
+    out = np.zeros((n_bones, 3, 4), np.float32)
+    M = np.eye(4)
+    step = angle / (n_bones - 1) if n_bones > 1 else 0.0
+    c, s = math.cos(step), math.sin(step)
+    i, j = (about + 1) % 3, (about + 2) % 3
+    R = np.eye(3)
+    R[i, i], R[i, j], R[j, i], R[j, j] = c, -s, s, c
+    for k in range(n_bones):
+        if k:
+            pivot = np.array(centre, np.float64)
+            pivot[axis] = lo + k * (hi - lo) / n_bones
+            J = np.eye(4)
+            J[:3, :3], J[:3, 3] = R, pivot - R @ pivot
+            M = M @ J
+        out[k] = M[:3].astype(np.float32)
+    return out
+
+
 def blue_noise_tables(path=None):
     """(sobol_256spp_256d, scramblingTile, rankingTile) as int32 arrays from the packed asset
     (tools/make_blue_noise_asset.py)."""

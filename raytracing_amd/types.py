@@ -47,6 +47,8 @@ cross_member = np.dtype([("primitive_id", "<u4"), ("flags", "<u4"), ("c0", "<f4"
 # found, bit 2 the pair crosses) and the winning candidate (0..2 a probe corner, 3..5 a corner of the triangle, 6 + 3 i + j an edge pair, 15 a crossing)
 separation = np.dtype([("on_probe", "<f4", (3,)), ("distance", "<f4"), ("on_scene", "<f4", (3,)), ("primitive_id", "<u4"), ("flags", "<u4"), ("feature", "<u4"),
                        ("pad", "<u4", (2,))])
+# rt_skin_influence (include/rt_hip.h): one triangle corner's four bones and weights (rt_scene_set_skin); an unused slot is weight 0 on any valid bone
+skin_influence = np.dtype([("bone", "<u2", (4,)), ("weight", "<f4", (4,))])
 camera = np.dtype([("position", float3), ("front", float3), ("up", float3), ("fov", "<f4"),
                    ("aspect_ratio", "<f4"), ("aperture", "<f4"), ("focus_distance", "<f4")])
 
@@ -57,7 +59,20 @@ assert camera.itemsize == 64 and surface.itemsize == 64 and bake_result.itemsize
 assert point.itemsize == 16 and nearest.itemsize == 32 and ray_hits.itemsize == 16 and point_hits.itemsize == 16
 assert region.itemsize == 144 and region_hits.itemsize == 16 and region_member.itemsize == 8
 assert probe.itemsize == 48 and probe_hits.itemsize == 16 and cross_member.itemsize == 32
-assert separation.itemsize == 48
+assert separation.itemsize == 48 and skin_influence.itemsize == 24
+
+
+def influences(bones, weights):
+    """types.skin_influence[n, 3] of bones int[n, 3, 4] (each 0 .. 65535) and weights float[n, 3, 4]: (triangle, corner, slot), the order rt_scene_set_skin
+    takes them in when flattened"""
+    b, w = np.asarray(bones), np.asarray(weights, np.float32)
+    if b.ndim != 3 or b.shape[1:] != (3, 4) or w.shape != b.shape:
+        raise ValueError("influences: bones and weights must both be [n, 3, 4]")
+    if b.size and (b.min() < 0 or b.max() > 0xFFFF):
+        raise ValueError("influences: a bone index does not fit 16 bits")
+    out = np.zeros((len(b), 3), skin_influence)
+    out["bone"], out["weight"] = b, w
+    return out
 
 
 def probes_from_corners(corners):
