@@ -242,6 +242,41 @@ typedef struct rt_skin_influence { uint16_t bone[4]; float weight[4]; } rt_skin_
 int rt_scene_set_skin(rt_ctx* ctx, const rt_skin_influence* per_corner, uint32_t num_triangles, uint32_t num_bones);
 int rt_scene_skin(rt_ctx* ctx, const float* matrices3x4, uint32_t num_bones);
 
+/* The scene's triangles MORPHED from one weight per morph target (blend shapes: faces, muscle correctives, cloth caches): 4 bytes per target and frame instead of
+ * 160 bytes per triangle, alone or fused with the skin above -- morph the rest pose first, then skin the result, as glTF, FBX and Alembic do.
+ * A target is SPARSE: one rt_morph_delta per triangle corner it moves, corner = 3 * triangle + c in the upload's BVH order (c = 0, 1, 2 for v1, v2, v3), a
+ * position delta, a normal delta (three +0.0 words: the target leaves that normal alone) and pad = 0.  A vertex several triangles share is given once per
+ * corner, with the same delta, or the mesh cracks.
+ *   rt_scene_set_morph, after rt_scene_upload on a context with RT_CTX_OPT_REFITTABLE = 1: target t owns deltas[target_offsets[t] .. target_offsets[t + 1]),
+ *     in any order inside the target; target_offsets has num_targets + 1 entries.  The library keeps the deltas on the device as one row of 32-byte records per
+ *     triangle (sorted by triangle, then target, then corner); the scene's CURRENT pose becomes the morph's rest pose (made from the shading records as
+ *     rt_scene_set_skin makes its own); the staging area and the weights' device and pinned host memory are allocated, so a morph allocates nothing.  Kept:
+ *     320 bytes per triangle (rest pose 160, staging area 160), 4 per row, 32 per delta, 4 per target (rt_scene_tree_report's "morph targets" line).  Refused,
+ *     with what an earlier call set left in place: a NULL argument, no scene, a scene that is not refittable, another triangle count, num_targets == 0 or above
+ *     65536, target_offsets[0] != 0, decreasing offsets, a corner >= 3 * num_triangles, a non-finite delta word, pad != 0, the same (target, corner) twice --
+ *     the offsets are checked first, then the deltas in array order, and the first offence decides the message.  A set with no deltas at all is legal: every
+ *     morph returns the rest pose.  Calling it again replaces the targets and the rest pose; rt_scene_upload drops them; rt_scene_refit*, rt_scene_set_objects,
+ *     rt_scene_pose, rt_scene_set_skin and rt_scene_skin leave them alone, as this leaves theirs alone: the three states are independent and whichever of
+ *     pose / skin / morph / refit ran last is the scene.
+ *   rt_scene_morph: weights[num_targets], used as given (nothing normalises them).  Morphs are ABSOLUTE: every call morphs the rest pose, so w1 then w2 equals
+ *     w2 alone.  Per corner, its records in ascending target order: a record whose weight is +0 or -0 is skipped entirely; otherwise p.x = p.x + w * dp.x,
+ *     likewise y and z; if a word of dn is not zero, n.x = n.x + w * dn.x, likewise y and z, and the corner's normal is renormalised once after its last record
+ *     by rt_scene_pose's rule (l = (x^2 + y^2) + z^2, divided by sqrtf(l) if l > 0 and finite, else left as summed); a corner with no applied record is copied
+ *     byte for byte; the .w lanes, texture coordinates, mtl_index and padding are copied.  So all-zero weights give the rest pose back byte for byte and a
+ *     position-only target never touches a normal.  k_morph_triangles writes the staging area and the refit above runs on it unchanged: afterwards the context
+ *     is, for every entry point and option, bit for bit what rt_scene_refit of rt_debug_morph(NULL, ...)'s output would have left (validation first, so an
+ *     overflowing morph is refused with the scene untouched).  Refused before any launch: a NULL argument, no morph set, another num_targets, a non-finite
+ *     weight, everything rt_scene_refit refuses.
+ *   rt_scene_morph_skin, after both rt_scene_set_morph and rt_scene_set_skin: the morph above, then rt_scene_skin's arithmetic on its result, in ONE kernel
+ *     (k_morph_skin_triangles).  It uses THE MORPH'S REST POSE; from the skin it takes the influences and the palette's room and nothing else -- the skin's own
+ *     rest pose is not read, and the two can differ when a refit, pose, skin or morph ran between the two set calls.  Afterwards the context is bit for bit what
+ *     rt_scene_refit of rt_debug_skin(NULL, rt_debug_morph(NULL, rest, ..., weights), influences, matrices) would have left.  It refuses whatever either
+ *     single call refuses. */
+typedef struct rt_morph_delta { uint32_t corner; float position[3]; float normal[3]; uint32_t pad; } rt_morph_delta;
+int rt_scene_set_morph(rt_ctx* ctx, const rt_morph_delta* deltas, const uint32_t* target_offsets, uint32_t num_targets, uint32_t num_triangles);
+int rt_scene_morph(rt_ctx* ctx, const float* weights, uint32_t num_targets);
+int rt_scene_morph_skin(rt_ctx* ctx, const float* weights, uint32_t num_targets, const float* matrices3x4, uint32_t num_bones);
+
 /* ---- ray queries: the CALLER's rays against the uploaded scene (opt-in extension).  Every other ray this library traces is one a frame
  * generated; these are a host program's own: which object lies under a pixel, visibility and probe rays, baking over the uploaded trees, collision rays against
  * a posed scene.
@@ -1058,6 +1093,16 @@ int rt_debug_pose(rt_ctx* ctx, const rt_triangle* rest, const uint32_t* object_o
  * weight, a non-finite matrix entry. */
 int rt_debug_skin(rt_ctx* ctx, const rt_triangle* rest, const rt_skin_influence* per_corner, uint32_t num_triangles, const float* matrices3x4, uint32_t num_bones,
                   rt_triangle* out);
+/* The morph on its own: out[num_triangles] = rest[num_triangles] morphed by the targets and weights (rt_scene_morph's arithmetic).  ctx == NULL: the host
+ * restatement; otherwise k_morph_triangles on uploaded copies, on ctx's device (the two agree bit for bit).  Refused: a NULL array, no triangles, more than
+ * 1431655765 triangles (a corner index is 32 bits), host memory that runs out while the table is checked or transposed (never an exception), and what
+ * rt_scene_set_morph refuses in a table or rt_scene_morph in the weights, with the same messages.
+ * rt_debug_morph_skin: the same, then the skin per corner: rt_debug_skin(ctx, rt_debug_morph(ctx, ...), per_corner, matrices3x4) -- on the host that very
+ * composition, on the device k_morph_skin_triangles' one pass. */
+int rt_debug_morph(rt_ctx* ctx, const rt_triangle* rest, const rt_morph_delta* deltas, const uint32_t* target_offsets, uint32_t num_targets, uint32_t num_triangles,
+                   const float* weights, rt_triangle* out);
+int rt_debug_morph_skin(rt_ctx* ctx, const rt_triangle* rest, const rt_morph_delta* deltas, const uint32_t* target_offsets, uint32_t num_targets, uint32_t num_triangles,
+                        const float* weights, const rt_skin_influence* per_corner, const float* matrices3x4, uint32_t num_bones, rt_triangle* out);
 /* What the last rt_scene_upload measured when it chose the trees (one line per ray population; "" when it had no choice), then the
  * latest fold adaptation's line (RT_CTX_OPT_ADAPTIVE_FOLD).  The pointer is valid until the next rt_integrate or rt_scene_upload on
  * this context (an adaptation rewrites its line): copy it. */
@@ -1143,6 +1188,7 @@ int rt_debug_eval(rt_ctx* ctx, int fn, const float* a, const float* b, float* ou
 }
 #endif
 RT_STATIC_ASSERT(sizeof(rt_skin_influence) == 24, "rt_skin_influence");
+RT_STATIC_ASSERT(sizeof(rt_morph_delta) == 32, "rt_morph_delta");
 RT_STATIC_ASSERT(sizeof(rt_surface) == 64, "rt_surface");
 RT_STATIC_ASSERT(sizeof(rt_bake_result) == 16 && sizeof(rt_bake_desc) == 20, "rt_bake_result / rt_bake_desc");
 RT_STATIC_ASSERT(sizeof(rt_point) == 16 && sizeof(rt_nearest) == 32, "rt_point / rt_nearest");

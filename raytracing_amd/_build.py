@@ -54,6 +54,7 @@ HIP_UNITS = [
     ("refit", "refit.hip", True),              # the refit of the scene's trees when its triangles move: kernels + their host driver + the host restatement (a code object of its own)
     ("pose", "pose.hip", True),                # the scene's objects posed from one matrix per object: kernels + host driver + the host restatement (a code object of its own)
     ("skin", "skin.hip", True),                # the scene's triangles skinned from a palette of bone matrices, four bones per corner: kernels + host driver + the host restatement (a code object of its own)
+    ("morph", "morph.hip", True),              # the scene's triangles morphed from one weight per sparse morph target, alone or fused with the skin in one pass: kernels + host driver + the host restatement (a code object of its own)
     ("query", "query.hip", True),              # caller-supplied rays traced against the uploaded scene, the surface record of a hit: kernels (the walk itself: walk_kernels.h, shared with bake and nearest) + the host driver core of all three + the host restatement (a code object of its own)
     ("bake", "bake.hip", True),                # ambient occlusion and bent normals at caller-supplied points: kernels on walk_kernels.h + host driver on query.hip's core + the host restatement (a code object of its own)
     ("nearest", "nearest.hip", True),          # the nearest surface point to caller-supplied points: kernels on walk_kernels.h's stack + host driver on query.hip's core + the host's brute force and walk (a code object of its own)
@@ -63,7 +64,7 @@ HIP_UNITS = [
     ("separation", "separation.hip", True),    # the nearest scene triangle to a caller-supplied triangle (the crossing verdict, then fifteen point-triangle and edge-edge candidates) with the two closest points, and the scene's clearances: kernels on walk_kernels.h's stack, volume_step and probe_box_step + host driver on query.hip's core + the host's brute force and walk (a code object of its own)
     ("all_hits", "all_hits.hip", True),        # every surface a caller-supplied ray crosses, counted and sorted: kernels on walk_kernels.h + host driver on query.hip's core + the host's brute force (a code object of its own)
     ("scene_queries", "scene_queries.cpp", False),   # the C entry points of the eight query families above (rt_scene_trace* .. rt_scene_separation*, their rt_debug_* forms) on context.h: an edit to a query's bookkeeping rebuilds no kernel (no device code)
-    ("scene_upload", "scene_upload.cpp", False),     # rt_scene_upload and its stages, tree choice, FoldAdapt's worker, rt_scene_refit* / set_objects / pose / set_skin / skin / export_folds / import_folds / tree_report, the tree work's rt_debug_* forms, on context.h + fold_adapt.h (no device code)
+    ("scene_upload", "scene_upload.cpp", False),     # rt_scene_upload and its stages, tree choice, FoldAdapt's worker, rt_scene_refit* / set_objects / pose / set_skin / skin / set_morph / morph / morph_skin / export_folds / import_folds / tree_report, the tree work's rt_debug_* forms, on context.h + fold_adapt.h (no device code)
     ("frame_filters", "frame_filters.cpp", False),   # the spatial and temporal filters' entry points on a frame and on caller arrays (rt_frame_filter* .. rt_frame_read_guide_motion, rt_debug_filter*, rt_debug_guide_motion) and the three states a filtered frame keeps, on frame.h + filters_host.h (no device code)
     ("frame_readers", "frame_readers.cpp", False),   # the frame's readers that launch no kernel: rt_frame_read_radiance / copy_radiance / get_profile and the rt_frame_debug_* readers, on frame.h (no device code)
     ("wide_bvh", "wide_bvh.cpp", False),     # build_wide_bvh, pair layout, the adaptation's host walks (no device code)

@@ -112,6 +112,7 @@ EXPORTS = [
     "rt_scene_refit", "rt_scene_refit_buffer", "rt_debug_refit",
     "rt_scene_set_objects", "rt_scene_pose", "rt_debug_pose",
     "rt_scene_set_skin", "rt_scene_skin", "rt_debug_skin",
+    "rt_scene_set_morph", "rt_scene_morph", "rt_scene_morph_skin", "rt_debug_morph", "rt_debug_morph_skin",
     "rt_frame_read_guide_motion", "rt_debug_guide_motion", "rt_debug_filter_temporal_motion",
     "rt_scene_trace", "rt_scene_trace_buffer", "rt_frame_pick", "rt_debug_query_surface",
     "rt_scene_bake", "rt_scene_bake_buffer", "rt_debug_bake_rays", "rt_debug_bake_reduce",
@@ -209,6 +210,8 @@ def load():
         "rt_debug_pose": (i32, [vp, vp, vp, u32, vp, u32, vp]),
         "rt_scene_set_skin": (i32, [vp, vp, u32, u32]), "rt_scene_skin": (i32, [vp, vp, u32]),
         "rt_debug_skin": (i32, [vp, vp, vp, u32, vp, u32, vp]),
+        "rt_scene_set_morph": (i32, [vp, vp, vp, u32, u32]), "rt_scene_morph": (i32, [vp, vp, u32]), "rt_scene_morph_skin": (i32, [vp, vp, u32, vp, u32]),
+        "rt_debug_morph": (i32, [vp, vp, vp, vp, u32, u32, vp, vp]), "rt_debug_morph_skin": (i32, [vp, vp, vp, vp, u32, u32, vp, vp, vp, u32, vp]),
         "rt_frame_read_guide_motion": (i32, [vp, vp, vp]),
         "rt_debug_guide_motion": (i32, [vp, u32, vp, vp, u32, vp, vp]),
         "rt_debug_filter_temporal_motion": (i32, [vp, u32, u32, vp, vp] + [vp] * 10 + [C.POINTER(rt_temporal_filter_desc), vp, vp, vp]),
@@ -415,6 +418,67 @@ def debug_skin(ctx, rest, influences, matrices, num_bones=None):
     out = np.zeros_like(tris)
     handle = ctx.handle if ctx is not None else None
     rc = lib.rt_debug_skin(handle, tris.ctypes.data, f.ctypes.data, len(tris), m.ctypes.data, len(m) if num_bones is None else num_bones, out.ctypes.data)
+    if rc != 0:
+        raise RtError(lib.rt_last_error(handle).decode())
+    return out
+
+
+MORPH_LDS_TARGETS, MORPH_MAX_TARGETS = 1024, 65536     # morph_host.h: the most weights k_morph_triangles stages in LDS (above it: gathered through L1 / L2); the most targets
+
+
+def _morph_table(deltas, offsets, who):
+    """(types.morph_delta[total], uint32[targets + 1]), as types.morph_targets makes them; a flat array of at least one delta's room, so that its address is never NULL"""
+    d = np.ascontiguousarray(deltas)
+    if d.dtype != T.morph_delta:
+        raise RtError(who + ": deltas must be types.morph_delta records (types.morph_targets packs them)")
+    d = d.reshape(-1)
+    o = np.ascontiguousarray(offsets, np.uint32).reshape(-1)
+    if len(o) < 2:
+        raise RtError(who + ": offsets must have one entry per target and one more")
+    if int(o.max()) > len(d):
+        raise RtError(who + ": an offset lies past the deltas")
+    if len(d) == 0:
+        d = np.zeros(1, T.morph_delta)              # a set with no deltas at all is legal
+    return d, o
+
+
+def _weights(weights, who, num_targets=None):
+    w = np.ascontiguousarray(weights, np.float32).reshape(-1)
+    if len(w) == 0:
+        raise RtError(who + ": no weights")
+    if num_targets is not None and len(w) != num_targets:
+        raise RtError(who + ": one weight per target")
+    return w
+
+
+def debug_morph(ctx, rest, deltas, offsets, weights):
+    """rt_debug_morph: `rest` (types.triangle) morphed by the sparse targets (deltas, offsets: types.morph_targets) with one weight per target.  ctx None = the
+    host restatement, else morph.hip's k_morph_triangles on ctx's GPU.  Returns the morphed triangles."""
+    lib = load()
+    tris = np.ascontiguousarray(rest, T.triangle)
+    d, o = _morph_table(deltas, offsets, "debug_morph")
+    w = _weights(weights, "debug_morph", len(o) - 1)
+    out = np.zeros_like(tris)
+    handle = ctx.handle if ctx is not None else None
+    rc = lib.rt_debug_morph(handle, tris.ctypes.data, d.ctypes.data, o.ctypes.data, len(o) - 1, len(tris), w.ctypes.data, out.ctypes.data)
+    if rc != 0:
+        raise RtError(lib.rt_last_error(handle).decode())
+    return out
+
+
+def debug_morph_skin(ctx, rest, deltas, offsets, weights, influences, matrices):
+    """rt_debug_morph_skin: debug_morph's result skinned by debug_skin's rule.  ctx None = the host composition of the two restatements, else
+    k_morph_skin_triangles' one pass on ctx's GPU."""
+    lib = load()
+    tris = np.ascontiguousarray(rest, T.triangle)
+    d, o = _morph_table(deltas, offsets, "debug_morph_skin")
+    w = _weights(weights, "debug_morph_skin", len(o) - 1)
+    f = _influences(influences, len(tris), "debug_morph_skin")
+    m = _matrices3x4(matrices, "debug_morph_skin")
+    out = np.zeros_like(tris)
+    handle = ctx.handle if ctx is not None else None
+    rc = lib.rt_debug_morph_skin(handle, tris.ctypes.data, d.ctypes.data, o.ctypes.data, len(o) - 1, len(tris), w.ctypes.data,
+                                 f.ctypes.data, m.ctypes.data, len(m), out.ctypes.data)
     if rc != 0:
         raise RtError(lib.rt_last_error(handle).decode())
     return out
@@ -1089,6 +1153,26 @@ class Context:
         written on the device and refitted as refit_scene() would.  Frames keep their sums: reset() them."""
         m = _matrices3x4(matrices, "skin_scene")
         _check(self.lib, self.handle, self.lib.rt_scene_skin(self.handle, m.ctypes.data, len(m)))
+
+    def set_morph(self, deltas, offsets, num_triangles):
+        """rt_scene_set_morph: sparse morph targets of the uploaded scene (types.morph_delta records and uint32 offsets, one more than targets: types.morph_targets
+        packs them; corners are 3 * triangle + c in the upload's order).  The scene's current pose becomes the rest pose of morph_scene() and
+        morph_skin_scene(); needs set_refittable() before upload_scene().  Independent of set_objects() and set_skin()."""
+        d, o = _morph_table(deltas, offsets, "set_morph")
+        _check(self.lib, self.handle, self.lib.rt_scene_set_morph(self.handle, d.ctypes.data, o.ctypes.data, len(o) - 1, num_triangles))
+
+    def morph_scene(self, weights):
+        """rt_scene_morph: the rest pose morphed by one weight per target (float32[targets]; absolute, never relative to the last morph), written on the device
+        and refitted as refit_scene() would.  Frames keep their sums: reset() them."""
+        w = _weights(weights, "morph_scene")
+        _check(self.lib, self.handle, self.lib.rt_scene_morph(self.handle, w.ctypes.data, len(w)))
+
+    def morph_skin_scene(self, weights, matrices):
+        """rt_scene_morph_skin: the MORPH's rest pose morphed by `weights`, then skinned by set_skin()'s influences and the palette `matrices`
+        (float32[num_bones, 3, 4]) in one kernel, and refitted.  Needs set_morph() and set_skin()."""
+        w = _weights(weights, "morph_skin_scene")
+        m = _matrices3x4(matrices, "morph_skin_scene")
+        _check(self.lib, self.handle, self.lib.rt_scene_morph_skin(self.handle, w.ctypes.data, len(w), m.ctypes.data, len(m)))
 
     def trace(self, rays, any_hit=False, surfaces=False):
         """rt_scene_trace: the caller's rays (ray_records' rule) against the uploaded scene.  Closest hits: types.hit[n], or (hits, types.surface[n]) with

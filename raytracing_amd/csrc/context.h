@@ -17,6 +17,7 @@
 #include "refit.h"           // refit::State
 #include "pose_host.h"       // pose::State
 #include "skin_host.h"       // skin::State
+#include "morph_host.h"      // morph::State
 #include "query_host.h"      // query::Scratch
 #include "bake_host.h"       // bake::CHUNK_POINTS
 #include "device_memory.h"   // dev::Mem
@@ -82,6 +83,8 @@ struct Scene
     pose::State* pose = nullptr;
     // rt_scene_set_skin (scene_upload.cpp): the rest pose, every corner's influences, the palette and the staging area of rt_scene_skin; nullptr = no skin set
     skin::State* skin = nullptr;
+    // rt_scene_set_morph (scene_upload.cpp): the rest pose, the targets' records by triangle, the weights and the staging area of rt_scene_morph / _morph_skin; nullptr = no morph set
+    morph::State* morph = nullptr;
 };
 } // namespace context
 
@@ -157,7 +160,7 @@ int query_check_status(rt_ctx* ctx, const char* who);
 // launches on -- side streams, pipes, banks -- has drained.  rt_hip.hip's, where the frames are.
 int quiesce(rt_ctx* ctx);
 
-// Everything a scene holds on the device and beside it (its adaptation, refit, pose and skin states) is freed and `s` is an empty scene again.  scene_upload.cpp's:
+// Everything a scene holds on the device and beside it (its adaptation, refit, pose, skin and morph states) is freed and `s` is an empty scene again.  scene_upload.cpp's:
 // rt_scene_upload and an upload that ends early call it there, rt_ctx_destroy from rt_hip.hip.
 void free_scene(Scene& s);
 

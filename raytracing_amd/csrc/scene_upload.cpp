@@ -27,6 +27,8 @@
 #include "refit.h"           // the refit of the scene's trees when its triangles move (refit.hip)
 #include "pose_host.h"       // the scene's objects posed from one matrix per object (pose.hip)
 #include "skin_host.h"       // the scene's triangles skinned from a palette of bone matrices (skin.hip)
+#include "morph.h"           // morph::Record
+#include "morph_host.h"      // the scene's triangles morphed from one weight per target, alone or fused with the skin (morph.hip)
 #include "filters_host.h"    // filt::snapshot_pose, the pose a refit replaces (filters.hip)
 #include "device_memory.h"   // who owns a device allocation: dev::Mem
 using namespace rtw;
@@ -514,6 +516,7 @@ void context::free_scene(Scene& s)
     if (s.pose_snap) (void)hipFree(s.pose_snap);
     if (s.pose) { pose::release(*s.pose); delete s.pose; }
     if (s.skin) { skin::release(*s.skin); delete s.skin; }
+    if (s.morph) { morph::release(*s.morph); delete s.morph; }
     delete s.leaf_starts;
     s = Scene();
 }
@@ -1191,6 +1194,140 @@ int rt_debug_skin(rt_ctx* ctx, const rt_triangle* rest, const rt_skin_influence*
     (void)hipSetDevice(ctx->device);
     if (!skin::debug_device(ctx->stream, rest, per_corner, num_triangles, matrices3x4, num_bones, out))
         return fail(ctx, "rt_debug_skin: the device path failed (allocation, copy or launch)");
+    return RT_OK;
+}
+
+// ---- morphed triangles: rt_scene_set_morph / rt_scene_morph / rt_scene_morph_skin / rt_debug_morph*, the bookkeeping around morph.hip's kernels (DESIGN.md
+// section 7q).  A morph IS a refit, as a pose and a skin are: the kernel writes the staging area rt_scene_set_morph allocated and refit_device() takes it
+// unchanged.  The morph's state is independent of the objects' and the skin's; the fused call reads the skin's influences and palette, never its rest pose.
+
+static int morph_table_refused(rt_ctx* ctx, const char* who, const rt_morph_delta* deltas, const uint32_t* target_offsets, uint32_t num_targets, uint32_t num_triangles)
+{
+    const std::string name(who);
+    if (num_targets == 0u) return fail(ctx, name + ": no targets");
+    if (num_targets > (uint32_t)morph::MAX_TARGETS) return fail(ctx, name + ": more than 65536 targets");
+    if (num_triangles > morph::MAX_TRIANGLES) return fail(ctx, name + ": more than 1431655765 triangles (a corner index is 32 bits)");
+    switch (morph::table_fault(deltas, target_offsets, num_targets, num_triangles))
+    {
+    case morph::TABLE_OK: return RT_OK;
+    case morph::FIRST_OFFSET: return fail(ctx, name + ": target_offsets[0] is not 0");
+    case morph::DECREASING_OFFSET: return fail(ctx, name + ": target_offsets decrease");
+    case morph::BAD_CORNER: return fail(ctx, name + ": a corner is not below 3 * num_triangles");
+    case morph::NOT_FINITE: return fail(ctx, name + ": a delta is not finite");
+    case morph::BAD_PAD: return fail(ctx, name + ": a delta's pad is not 0");
+    case morph::NO_MEMORY: return fail(ctx, name + ": no host memory to check the table");
+    default: return fail(ctx, name + ": a target moves the same corner twice");
+    }
+}
+
+int rt_scene_set_morph(rt_ctx* ctx, const rt_morph_delta* deltas, const uint32_t* target_offsets, uint32_t num_targets, uint32_t num_triangles)
+{
+    if (!ctx || !deltas || !target_offsets) return fail(ctx, "rt_scene_set_morph: NULL argument");
+    if (refit_refused(ctx, "rt_scene_set_morph", num_triangles, false) != RT_OK) return RT_ERROR;
+    if (morph_table_refused(ctx, "rt_scene_set_morph", deltas, target_offsets, num_targets, num_triangles) != RT_OK) return RT_ERROR;
+    (void)hipSetDevice(ctx->device);
+    Scene& s = ctx->scene;
+    std::vector<uint32_t> row;
+    std::vector<morph::Record> records;
+    if (!morph::transpose(deltas, target_offsets, num_targets, num_triangles, row, records)) return fail(ctx, "rt_scene_set_morph: no host memory for the rows");
+    morph::State* st = new morph::State();
+    if (!morph::arm(ctx->stream, *st, (const float4*)s.tris_sh, row, records, num_triangles, num_targets))
+    {
+        delete st;
+        return fail(ctx, "rt_scene_set_morph: the rest pose, the records and the staging area could not be allocated");
+    }
+    if (s.morph) { morph::release(*s.morph); delete s.morph; }
+    s.morph = st;
+    char line[300];
+    snprintf(line, sizeof(line), "morph targets: %u targets, %u deltas, %.1f MB kept: rest pose %u + staging area %u + row %u bytes per triangle, %u per delta, %u per target\n",
+        num_targets, st->n_deltas, (double)st->bytes / 1e6, (unsigned)morph::REST_BYTES, (unsigned)morph::STAGED_BYTES, (unsigned)morph::ROW_BYTES,
+        (unsigned)morph::RECORD_BYTES, (unsigned)morph::WEIGHT_BYTES);
+    keep_one_line_before_refit(s.tree_report, "morph targets: ", line);
+    return RT_OK;
+}
+
+// what rt_scene_morph and rt_scene_morph_skin refuse in common, before any launch
+static int morph_refused(rt_ctx* ctx, const char* who, const float* weights, uint32_t num_targets)
+{
+    const std::string name(who);
+    Scene& s = ctx->scene;
+    if (refit_refused(ctx, who, s.n_tris, false) != RT_OK) return RT_ERROR;
+    if (!s.morph) return fail(ctx, name + ": no morph (rt_scene_set_morph has not been called for this scene)");
+    if (num_targets != s.morph->n_targets) return fail(ctx, name + ": the target count differs from rt_scene_set_morph's");
+    if (!morph::weights_finite(weights, num_targets)) return fail(ctx, name + ": a weight is not finite");
+    return RT_OK;
+}
+
+int rt_scene_morph(rt_ctx* ctx, const float* weights, uint32_t num_targets)
+{
+    if (!ctx || !weights) return fail(ctx, "rt_scene_morph: NULL argument");
+    if (morph_refused(ctx, "rt_scene_morph", weights, num_targets) != RT_OK) return RT_ERROR;
+    Scene& s = ctx->scene;
+    (void)hipSetDevice(ctx->device);
+    if (!morph::run(ctx->stream, *s.morph, weights))
+    {
+        (void)hipGetLastError();
+        return fail(ctx, "rt_scene_morph: the morph kernel could not be launched");
+    }
+    return refit_device(ctx, s.morph->staged, "rt_scene_morph");
+}
+
+int rt_scene_morph_skin(rt_ctx* ctx, const float* weights, uint32_t num_targets, const float* matrices3x4, uint32_t num_bones)
+{
+    if (!ctx || !weights || !matrices3x4) return fail(ctx, "rt_scene_morph_skin: NULL argument");
+    if (morph_refused(ctx, "rt_scene_morph_skin", weights, num_targets) != RT_OK) return RT_ERROR;
+    Scene& s = ctx->scene;
+    if (!s.skin) return fail(ctx, "rt_scene_morph_skin: no skin (rt_scene_set_skin has not been called for this scene)");
+    if (num_bones != s.skin->n_bones) return fail(ctx, "rt_scene_morph_skin: the bone count differs from rt_scene_set_skin's");
+    if (!skin::matrices_finite(matrices3x4, num_bones)) return fail(ctx, "rt_scene_morph_skin: a matrix entry is not finite");
+    (void)hipSetDevice(ctx->device);
+    if (!skin::upload_palette(ctx->stream, *s.skin, matrices3x4) ||
+        !morph::run_skin(ctx->stream, *s.morph, weights, s.skin->influences, s.skin->palette, num_bones))
+    {
+        (void)hipGetLastError();
+        return fail(ctx, "rt_scene_morph_skin: the morph-and-skin kernel could not be launched");
+    }
+    return refit_device(ctx, s.morph->staged, "rt_scene_morph_skin");
+}
+
+static int debug_morph_refused(rt_ctx* ctx, const char* who, const rt_morph_delta* deltas, const uint32_t* target_offsets, uint32_t num_targets, uint32_t num_triangles,
+    const float* weights)
+{
+    const std::string name(who);
+    if (num_triangles == 0u) return fail(ctx, name + ": no triangles");
+    if (morph_table_refused(ctx, who, deltas, target_offsets, num_targets, num_triangles) != RT_OK) return RT_ERROR;
+    if (!morph::weights_finite(weights, num_targets)) return fail(ctx, name + ": a weight is not finite");
+    return RT_OK;
+}
+
+int rt_debug_morph(rt_ctx* ctx, const rt_triangle* rest, const rt_morph_delta* deltas, const uint32_t* target_offsets, uint32_t num_targets, uint32_t num_triangles,
+    const float* weights, rt_triangle* out)
+{
+    if (!rest || !deltas || !target_offsets || !weights || !out) return fail(ctx, "rt_debug_morph: NULL argument");
+    if (debug_morph_refused(ctx, "rt_debug_morph", deltas, target_offsets, num_targets, num_triangles, weights) != RT_OK) return RT_ERROR;
+    if (!ctx) return morph::debug_host(rest, deltas, target_offsets, num_targets, num_triangles, weights, out) ? RT_OK : fail(ctx, "rt_debug_morph: no host memory for the rows");
+    (void)hipSetDevice(ctx->device);
+    if (!morph::debug_device(ctx->stream, rest, deltas, target_offsets, num_targets, num_triangles, weights, out))
+        return fail(ctx, "rt_debug_morph: the device path failed (allocation, copy or launch)");
+    return RT_OK;
+}
+
+int rt_debug_morph_skin(rt_ctx* ctx, const rt_triangle* rest, const rt_morph_delta* deltas, const uint32_t* target_offsets, uint32_t num_targets, uint32_t num_triangles,
+    const float* weights, const rt_skin_influence* per_corner, const float* matrices3x4, uint32_t num_bones, rt_triangle* out)
+{
+    if (!rest || !deltas || !target_offsets || !weights || !per_corner || !matrices3x4 || !out) return fail(ctx, "rt_debug_morph_skin: NULL argument");
+    if (debug_morph_refused(ctx, "rt_debug_morph_skin", deltas, target_offsets, num_targets, num_triangles, weights) != RT_OK) return RT_ERROR;
+    if (skin_table_refused(ctx, "rt_debug_morph_skin", per_corner, num_triangles, num_bones) != RT_OK) return RT_ERROR;
+    if (!skin::matrices_finite(matrices3x4, num_bones)) return fail(ctx, "rt_debug_morph_skin: a matrix entry is not finite");
+    if (!ctx)
+    {
+        if (!morph::debug_host(rest, deltas, target_offsets, num_targets, num_triangles, weights, out)) return fail(ctx, "rt_debug_morph_skin: no host memory for the rows");
+        skin::debug_host(out, per_corner, num_triangles, matrices3x4, num_bones, out);           // (triangle by triangle, each read before it is written)
+        return RT_OK;
+    }
+    (void)hipSetDevice(ctx->device);
+    if (!morph::debug_skin_device(ctx->stream, rest, deltas, target_offsets, num_targets, num_triangles, weights, per_corner, matrices3x4, num_bones, out))
+        return fail(ctx, "rt_debug_morph_skin: the device path failed (allocation, copy or launch)");
     return RT_OK;
 }
 

@@ -130,10 +130,15 @@ bool arm(hipStream_t stream, State& st, const float4* tris_sh, const rt_skin_inf
     return ok;
 }
 
-bool run(hipStream_t stream, State& st, const float* matrices3x4)
+bool upload_palette(hipStream_t stream, State& st, const float* matrices3x4)
 {
     memcpy(st.host_palette, matrices3x4, (size_t)st.n_bones * MATRIX_BYTES);
-    if (hipMemcpyAsync(st.palette, st.host_palette, (size_t)st.n_bones * MATRIX_BYTES, hipMemcpyHostToDevice, stream) != hipSuccess) return false;
+    return hipMemcpyAsync(st.palette, st.host_palette, (size_t)st.n_bones * MATRIX_BYTES, hipMemcpyHostToDevice, stream) == hipSuccess;
+}
+
+bool run(hipStream_t stream, State& st, const float* matrices3x4)
+{
+    if (!upload_palette(stream, st, matrices3x4)) return false;
     hipLaunchKernelGGL(k_skin_triangles, dim3(dev::blocks_for(st.n_tris, 256u)), dim3(256), 0, stream, (const float4*)st.rest, (const uint2*)st.influences,
         (const float*)st.palette, st.n_tris, st.n_bones, (float4*)st.staged);
     return dev::clean();

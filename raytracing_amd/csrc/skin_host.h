@@ -36,6 +36,8 @@ bool matrices_finite(const float* matrices3x4, uint32_t n_bones);
 // false: an allocation, a copy or the launch failed, and st is released
 bool arm(hipStream_t stream, State& st, const float4* tris_sh, const rt_skin_influence* per_corner, uint32_t nt, uint32_t n_bones);
 void release(State& st);
+// the palette into its pinned host copy and from there to the device, and no launch (rt_scene_morph_skin's kernel reads it: morph.hip).  Nothing is waited for.
+bool upload_palette(hipStream_t stream, State& st, const float* matrices3x4);
 // the palette uploaded, then k_skin_triangles: rest -> staged.  Nothing is waited for.
 bool run(hipStream_t stream, State& st, const float* matrices3x4);
 

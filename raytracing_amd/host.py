@@ -29,6 +29,7 @@ EXPORTS = [
     "rth_render_bake", "rth_render_occlusion_image", "rth_render_nearest", "rth_render_within", "rth_render_overlap", "rth_render_cross", "rth_render_self_cross", "rth_render_separation", "rth_render_clearance", "rth_render_select", "rth_render_pick_rect", "rth_render_integrator_pick_rect", "rth_render_trace_all", "rth_render_pick_all",
     "rth_scene_set_triangle_objects", "rth_scene_num_objects", "rth_scene_object_name", "rth_scene_num_triangle_objects", "rth_scene_triangle_objects",
     "rth_render_set_skin", "rth_render_skin", "rth_scene_set_triangle_skin", "rth_scene_num_triangle_skin", "rth_scene_triangle_skin",
+    "rth_render_set_morph", "rth_render_morph", "rth_render_morph_skin",
 ]
 
 
@@ -76,6 +77,7 @@ def load():
         "rth_render_set_refit_motion": (i32, [vp, i32]),
         "rth_render_set_objects": (i32, [vp, vp, u32, u32]), "rth_render_pose": (i32, [vp, vp, u32]),
         "rth_render_set_skin": (i32, [vp, vp, u32, u32]), "rth_render_skin": (i32, [vp, vp, u32]),
+        "rth_render_set_morph": (i32, [vp, vp, vp, u32, u32]), "rth_render_morph": (i32, [vp, vp, u32]), "rth_render_morph_skin": (i32, [vp, vp, u32, vp, u32]),
         "rth_scene_set_triangle_skin": (i32, [vp, vp, u32]), "rth_scene_num_triangle_skin": (u32, [vp]), "rth_scene_triangle_skin": (vp, [vp]),
         "rth_render_pick": (i32, [vp, u32, u32, vp, vp, vp]), "rth_render_integrator_pick": (i32, [vp, u32, u32, vp, vp, vp]), "rth_render_trace": (i32, [vp, vp, u32, i32, vp, vp, vp]),
         "rth_render_bake": (i32, [vp, vp, u32, vp, vp]), "rth_render_occlusion_image": (i32, [vp, vp, vp]),
@@ -451,6 +453,38 @@ class Render:
         except capi.RtError as e:
             raise RtError(str(e))
         self._c(self.lib.rth_render_skin(self.handle, m.ctypes.data, len(m)))
+
+    def set_morph(self, deltas, offsets):
+        """Sparse morph targets (types.morph_delta records and uint32 offsets, one more than targets: types.morph_targets packs them), after set_refittable():
+        corners are 3 * triangle + c in the BVH order of scene_arrays()['triangles'], as set_skin() with the caller's own influences is.  The scene's current
+        pose becomes the rest pose of morph() and morph_skin().  An upload (set_refittable, set_ctx_option, ...) drops the targets: set them again.
+        Independent of set_objects() and set_skin()."""
+        from . import capi
+        try:
+            d, o = capi._morph_table(deltas, offsets, "set_morph")
+        except capi.RtError as e:
+            raise RtError(str(e))
+        self._c(self.lib.rth_render_set_morph(self.handle, d.ctypes.data, o.ctypes.data, len(o) - 1, self.lib.rth_scene_num_triangles(self.scene.handle)))
+
+    def morph(self, weights):
+        """One weight per target (float32[targets]), always applied to the rest pose.  The morphed triangles are written and refitted on the device and the
+        accumulation restarts; results equal refit() of the same triangles."""
+        from . import capi
+        try:
+            w = capi._weights(weights, "morph")
+        except capi.RtError as e:
+            raise RtError(str(e))
+        self._c(self.lib.rth_render_morph(self.handle, w.ctypes.data, len(w)))
+
+    def morph_skin(self, weights, matrices):
+        """morph(), then set_skin()'s influences with the palette `matrices` (float32[num_bones, 3, 4]), in one kernel, from the MORPH's rest pose."""
+        from . import capi
+        try:
+            w = capi._weights(weights, "morph_skin")
+            m = capi._matrices3x4(matrices, "morph_skin")
+        except capi.RtError as e:
+            raise RtError(str(e))
+        self._c(self.lib.rth_render_morph_skin(self.handle, w.ctypes.data, len(w), m.ctypes.data, len(m)))
 
     def pick(self, x, y):
         """What lies under the centre of pixel (x, y) of the Render's current camera, also one set since the last frame (Render::Pick; the frame is not touched): a dict of the surface's fields (primitive_id

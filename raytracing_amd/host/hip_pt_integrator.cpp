@@ -182,6 +182,23 @@ void HIPPathTraceIntegrator::SkinBones(float const* matrices3x4, std::size_t bon
     RequestReset();
 }
 
+void HIPPathTraceIntegrator::SetMorph(rt_morph_delta const* deltas, std::uint32_t const* target_offsets, std::uint32_t target_count, std::size_t triangle_count)
+{
+    Check(rt_scene_set_morph(context_.Get(), deltas, target_offsets, target_count, (uint32_t)triangle_count));
+}
+
+void HIPPathTraceIntegrator::MorphTargets(float const* weights, std::size_t target_count)
+{
+    Check(rt_scene_morph(context_.Get(), weights, (uint32_t)target_count));
+    RequestReset();
+}
+
+void HIPPathTraceIntegrator::MorphAndSkin(float const* weights, std::size_t target_count, float const* matrices3x4, std::size_t bone_count)
+{
+    Check(rt_scene_morph_skin(context_.Get(), weights, (uint32_t)target_count, matrices3x4, (uint32_t)bone_count));
+    RequestReset();
+}
+
 void HIPPathTraceIntegrator::TraceRays(rt_ray const* rays, std::size_t count, bool any_hit, rt_hit* hits, std::uint32_t* occluded, rt_surface* surfaces)
 {
     if (count > 0xFFFFFFFFull) throw HIPException("HIPPathTraceIntegrator::TraceRays: more than 2^32 - 1 rays in one call");

@@ -108,6 +108,14 @@ public:
     // the device; requests a reset.  Both throw HIPException with the library's message on a refusal.
     void SetSkin(rt_skin_influence const* per_corner, std::size_t triangle_count, std::uint32_t bone_count);
     void SkinBones(float const* matrices3x4, std::size_t bone_count);
+    // Morph targets (rt_scene_set_morph / rt_scene_morph / rt_scene_morph_skin), after SetRefittable(true) and UploadGPUData.  SetMorph:
+    // sparse targets, target t owning deltas[target_offsets[t] .. target_offsets[t + 1]), corners = 3 * triangle + c in the uploaded BVH order; the scene's current
+    // pose becomes the morph's rest pose; dropped by the next UploadGPUData; independent of SetObjects and SetSkin.  MorphTargets: one weight per target, absolute;
+    // the triangles are written and refitted on the device; requests a reset.  MorphAndSkin: the morph, then SetSkin's influences with this palette, in one
+    // kernel, from the MORPH's rest pose.  All throw HIPException with the library's message on a refusal.
+    void SetMorph(rt_morph_delta const* deltas, std::uint32_t const* target_offsets, std::uint32_t target_count, std::size_t triangle_count);
+    void MorphTargets(float const* weights, std::size_t target_count);
+    void MorphAndSkin(float const* weights, std::size_t target_count, float const* matrices3x4, std::size_t bone_count);
     // Ray queries (rt_scene_trace / rt_frame_pick): the caller's rays against the uploaded scene as it is posed now.  TraceRays: closest hits
     // (hits and / or surfaces, either may be null) or, any_hit, one 0 / 1 word per ray in occluded; a count of 2^32 or more is refused.  Pick: the ray through the
     // centre of pixel (x, y) of the frame's current camera, its hit and surface (any may be null).  PickThrough: the same for a camera the frame has not been given

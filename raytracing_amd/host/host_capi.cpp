@@ -268,6 +268,15 @@ int rth_render_set_skin(void* r, const rt_skin_influence* per_corner, uint32_t n
     return guard([&]() { ((rt::Render*)r)->SetSkin(per_corner, num_triangles, num_bones); return 0; }, 1);
 }
 int rth_render_skin(void* r, const float* matrices3x4, uint32_t num_bones) { return guard([&]() { ((rt::Render*)r)->SkinBones(matrices3x4, num_bones); return 0; }, 1); }
+int rth_render_set_morph(void* r, const rt_morph_delta* deltas, const uint32_t* target_offsets, uint32_t num_targets, uint32_t num_triangles)
+{
+    return guard([&]() { ((rt::Render*)r)->SetMorph(deltas, target_offsets, num_targets, num_triangles); return 0; }, 1);
+}
+int rth_render_morph(void* r, const float* weights, uint32_t num_targets) { return guard([&]() { ((rt::Render*)r)->MorphTargets(weights, num_targets); return 0; }, 1); }
+int rth_render_morph_skin(void* r, const float* weights, uint32_t num_targets, const float* matrices3x4, uint32_t num_bones)
+{
+    return guard([&]() { ((rt::Render*)r)->MorphAndSkin(weights, num_targets, matrices3x4, num_bones); return 0; }, 1);
+}
 int rth_render_pick(void* r, uint32_t x, uint32_t y, rt_ray* ray, rt_hit* hit, rt_surface* surface) { return guard([&]() { ((rt::Render*)r)->Pick(x, y, ray, hit, surface); return 0; }, 1); }
 // HIPPathTraceIntegrator::Pick itself: the FRAME's camera (what the last RenderFrame / RenderSamples handed over), where rth_render_pick uses the Render's
 int rth_render_integrator_pick(void* r, uint32_t x, uint32_t y, rt_ray* ray, rt_hit* hit, rt_surface* surface)

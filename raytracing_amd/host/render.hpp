@@ -46,6 +46,11 @@ public:
     // the skin: set it again.
     void SetSkin(rt_skin_influence const* per_corner, std::size_t triangle_count, std::uint32_t bone_count) { integrator_->SetSkin(per_corner, triangle_count, bone_count); }
     void SkinBones(float const* matrices3x4, std::size_t bone_count) { integrator_->SkinBones(matrices3x4, bone_count); }
+    // Morph targets, after SetRefittable(true): sparse targets over the finalised scene's BVH order, then one weight per target and
+    // frame -- 4 bytes per target instead of RefitGeometry's 160 bytes per triangle -- alone or fused with the skin.  An upload drops the targets: set them again.
+    void SetMorph(rt_morph_delta const* deltas, std::uint32_t const* target_offsets, std::uint32_t target_count, std::size_t triangle_count) { integrator_->SetMorph(deltas, target_offsets, target_count, triangle_count); }
+    void MorphTargets(float const* weights, std::size_t target_count) { integrator_->MorphTargets(weights, target_count); }
+    void MorphAndSkin(float const* weights, std::size_t target_count, float const* matrices3x4, std::size_t bone_count) { integrator_->MorphAndSkin(weights, target_count, matrices3x4, bone_count); }
     // Ray queries: what lies under pixel (x, y) of the Render's current camera -- also one set since the last frame, which the integrator
     // has not been given yet: the ray is made from it here and traced as a query, the frame (its camera and previous camera included) is not touched -- and the
     // caller's own rays against the scene as it is posed now

@@ -555,6 +555,39 @@ def bend_palette(n_bones, angle, axis=0, lo=0.0, hi=1.0, about=None, centre=(0.0
     return out
 
 
+# --------------------------------------------------------------------------
+# synthetic morph targets for any mesh (rt_scene_set_morph / rt_scene_morph)
+# --------------------------------------------------------------------------
+def synthetic_morph(triangles, n_targets, radius=0.15, amplitude=0.05, normals=True, seed=0):
+    """n_targets sparse targets for types.morph_targets: a list of (corners int64[k], dpos float32[k, 3], dnormal float32[k, 3] or None).  Target t is a bump
+    about the position of one of the mesh's corners (corner t * (3 n // n_targets) of the flattened array): every corner within `radius` times the bounding
+    box's diagonal of it moves by amplitude * diagonal * (1 - (d / r)^2)^2 along a direction of the target's own, and (normals=True) its normal leans by
+    0.5 * (1 - (d / r)^2)^2 along another -- BOTH A FUNCTION OF THE CORNER'S POSITION ONLY, so corners that share a position share deltas and the morphed mesh
+    does not crack; a corner on or outside the radius is not in the target, so each target touches a bounded region.  Corners are 3 * triangle + c in the
+    order of `triangles`, ascending inside a target.  Deterministic (directions from default_rng(seed))."""
+    if not 1 <= n_targets <= 65536:
+        raise ValueError("synthetic_morph: 1 to 65536 targets")
+    if len(triangles) == 0:
+        raise ValueError("synthetic_morph: no triangles")
+    p = _corner_positions(triangles).reshape(-1, 3).astype(np.float64)
+    diagonal = float(np.linalg.norm(p.max(0) - p.min(0))) if len(p) else 0.0
+    r = radius * diagonal
+    rng = np.random.default_rng(seed)
+    directions = rng.normal(size=(n_targets, 2, 3))
+    directions /= np.linalg.norm(directions, axis=-1, keepdims=True)
+    stride = max(len(p) // n_targets, 1)
+    targets = []
+    for t in range(n_targets):
+        centre = p[(t * stride) % len(p)]
+        d2 = ((p - centre) ** 2).sum(1)
+        corners = np.flatnonzero(d2 < r * r)
+        fall = (1.0 - d2[corners] / (r * r)) ** 2 if r > 0 else np.zeros(0)
+        dpos = (amplitude * diagonal * fall[:, None] * directions[t, 0]).astype(np.float32)
+        dn = (0.5 * fall[:, None] * directions[t, 1]).astype(np.float32) if normals else None
+        targets.append((corners.astype(np.int64), dpos, dn))
+    return targets
+
+
 def blue_noise_tables(path=None):
     """(sobol_256spp_256d, scramblingTile, rankingTile) as int32 arrays from the packed asset
     (tools/make_blue_noise_asset.py)."""

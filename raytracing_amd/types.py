@@ -49,6 +49,8 @@ separation = np.dtype([("on_probe", "<f4", (3,)), ("distance", "<f4"), ("on_scen
                        ("pad", "<u4", (2,))])
 # rt_skin_influence (include/rt_hip.h): one triangle corner's four bones and weights (rt_scene_set_skin); an unused slot is weight 0 on any valid bone
 skin_influence = np.dtype([("bone", "<u2", (4,)), ("weight", "<f4", (4,))])
+# rt_morph_delta (include/rt_hip.h): one morph target's delta at one triangle corner (rt_scene_set_morph); corner = 3 * triangle + c, pad = 0
+morph_delta = np.dtype([("corner", "<u4"), ("position", "<f4", (3,)), ("normal", "<f4", (3,)), ("pad", "<u4")])
 camera = np.dtype([("position", float3), ("front", float3), ("up", float3), ("fov", "<f4"),
                    ("aspect_ratio", "<f4"), ("aperture", "<f4"), ("focus_distance", "<f4")])
 
@@ -59,7 +61,7 @@ assert camera.itemsize == 64 and surface.itemsize == 64 and bake_result.itemsize
 assert point.itemsize == 16 and nearest.itemsize == 32 and ray_hits.itemsize == 16 and point_hits.itemsize == 16
 assert region.itemsize == 144 and region_hits.itemsize == 16 and region_member.itemsize == 8
 assert probe.itemsize == 48 and probe_hits.itemsize == 16 and cross_member.itemsize == 32
-assert separation.itemsize == 48 and skin_influence.itemsize == 24
+assert separation.itemsize == 48 and skin_influence.itemsize == 24 and morph_delta.itemsize == 32
 
 
 def influences(bones, weights):
@@ -73,6 +75,33 @@ def influences(bones, weights):
     out = np.zeros((len(b), 3), skin_influence)
     out["bone"], out["weight"] = b, w
     return out
+
+
+def morph_targets(targets):
+    """(types.morph_delta[total], uint32[len(targets) + 1]) of a list of sparse targets, each (corners int[k], dpos float[k, 3], dnormal float[k, 3] or None):
+    what rt_scene_set_morph takes.  corners are 3 * triangle + c in the uploaded order; dnormal None = a position-only target (zeros: the normals stay)."""
+    counts = []
+    parts = []
+    for t, target in enumerate(targets):
+        if len(target) != 3:
+            raise ValueError("morph_targets: target %d is not (corners, dpos, dnormal)" % t)
+        corners = np.asarray(target[0])
+        if corners.ndim != 1 or (corners.size and (not np.issubdtype(corners.dtype, np.integer) or corners.min() < 0 or corners.max() > 0xFFFFFFFF)):
+            raise ValueError("morph_targets: target %d's corners must be a flat array of unsigned 32-bit indices" % t)
+        dp = np.asarray(target[1], np.float32).reshape(-1, 3) if np.size(target[1]) else np.zeros((0, 3), np.float32)
+        dn = np.zeros_like(dp) if target[2] is None else (np.asarray(target[2], np.float32).reshape(-1, 3) if np.size(target[2]) else np.zeros((0, 3), np.float32))
+        if len(dp) != len(corners) or len(dn) != len(corners):
+            raise ValueError("morph_targets: target %d wants one position delta (and one normal delta) per corner" % t)
+        d = np.zeros(len(corners), morph_delta)
+        d["corner"], d["position"], d["normal"] = corners, dp, dn
+        parts.append(d)
+        counts.append(len(d))
+    offsets = np.zeros(len(counts) + 1, np.uint64)
+    offsets[1:] = np.cumsum(np.asarray(counts, np.uint64))
+    if offsets[-1] > 0xFFFFFFFF:
+        raise ValueError("morph_targets: more than 2^32 - 1 deltas")
+    deltas = np.concatenate(parts) if parts else np.zeros(0, morph_delta)
+    return deltas, offsets.astype(np.uint32)
 
 
 def probes_from_corners(corners):
