@@ -45,13 +45,14 @@ def hipcc():
 # (a code object of its own: the hot path's is not rebuilt or re-hashed when the builder changes), the spatial and temporal filters' kernels (likewise), and the host
 # side of the tree work.  The scene queries are split the same way twice over: each family's kernels and launch driver are a unit with a code object of its own, and
 # the C entry points of all eight are one host-only unit (scene_queries.cpp, on context.h), so neither a kernel nor an entry point's bookkeeping rebuilds the hot path.
-# The scene side -- upload, tree choice, the adaptation's worker, refit, pose and the tree work's debug forms -- is a host-only unit too (scene_upload.cpp).
+# The scene side -- upload, tree choice, the adaptation's worker, refit and the tree work's debug forms -- is a host-only unit too (scene_upload.cpp), and so are the entry points of pose, skin and morph (scene_moved.cpp).
 # So are the two things that work on a frame without tracing a sample: the filters' entry points (frame_filters.cpp) and the kernel-less readers (frame_readers.cpp), on frame.h.
 HIP_UNITS = [
     ("rt_hip", "rt_hip.hip", True),            # C-ABI, frames, launch logic + kernels.h (the hot path)
     ("device_fold", "device_fold.hip", True),  # fold_kernels.h + its host driver
     ("filters", "filters.hip", True),          # the guide pass, the spatial filter's a-trous passes, the temporal filter's stages (a code object of its own, like device_fold's)
     ("refit", "refit.hip", True),              # the refit of the scene's trees when its triangles move: kernels + their host driver + the host restatement (a code object of its own)
+    ("moved", "moved.hip", True),              # what pose, skin and morph keep in common beside the scene, a rest pose and a staging area (moved::Stage), and the one kernel that makes a rest pose (a small code object of its own); the tile their kernels share is moved_tile.h, by inclusion
     ("pose", "pose.hip", True),                # the scene's objects posed from one matrix per object: kernels + host driver + the host restatement (a code object of its own)
     ("skin", "skin.hip", True),                # the scene's triangles skinned from a palette of bone matrices, four bones per corner: kernels + host driver + the host restatement (a code object of its own)
     ("morph", "morph.hip", True),              # the scene's triangles morphed from one weight per sparse morph target, alone or fused with the skin in one pass: kernels + host driver + the host restatement (a code object of its own)
@@ -64,7 +65,8 @@ HIP_UNITS = [
     ("separation", "separation.hip", True),    # the nearest scene triangle to a caller-supplied triangle (the crossing verdict, then fifteen point-triangle and edge-edge candidates) with the two closest points, and the scene's clearances: kernels on walk_kernels.h's stack, volume_step and probe_box_step + host driver on query.hip's core + the host's brute force and walk (a code object of its own)
     ("all_hits", "all_hits.hip", True),        # every surface a caller-supplied ray crosses, counted and sorted: kernels on walk_kernels.h + host driver on query.hip's core + the host's brute force (a code object of its own)
     ("scene_queries", "scene_queries.cpp", False),   # the C entry points of the eight query families above (rt_scene_trace* .. rt_scene_separation*, their rt_debug_* forms) on context.h: an edit to a query's bookkeeping rebuilds no kernel (no device code)
-    ("scene_upload", "scene_upload.cpp", False),     # rt_scene_upload and its stages, tree choice, FoldAdapt's worker, rt_scene_refit* / set_objects / pose / set_skin / skin / set_morph / morph / morph_skin / export_folds / import_folds / tree_report, the tree work's rt_debug_* forms, on context.h + fold_adapt.h (no device code)
+    ("scene_upload", "scene_upload.cpp", False),     # rt_scene_upload and its stages, tree choice, FoldAdapt's worker, rt_scene_refit* / export_folds / import_folds / tree_report, the tree work's rt_debug_* forms, on context.h + fold_adapt.h (no device code)
+    ("scene_moved", "scene_moved.cpp", False),       # the C entry points of pose, skin and morph (rt_scene_set_objects .. rt_scene_morph_skin, their rt_debug_* forms) on context.h; each ends in scene_upload.cpp's refit_device (no device code)
     ("frame_filters", "frame_filters.cpp", False),   # the spatial and temporal filters' entry points on a frame and on caller arrays (rt_frame_filter* .. rt_frame_read_guide_motion, rt_debug_filter*, rt_debug_guide_motion) and the three states a filtered frame keeps, on frame.h + filters_host.h (no device code)
     ("frame_readers", "frame_readers.cpp", False),   # the frame's readers that launch no kernel: rt_frame_read_radiance / copy_radiance / get_profile and the rt_frame_debug_* readers, on frame.h (no device code)
     ("wide_bvh", "wide_bvh.cpp", False),     # build_wide_bvh, pair layout, the adaptation's host walks (no device code)

@@ -1,4 +1,4 @@
-// context.h -- what a context is, for the translation units that implement entry points on it (rt_hip.hip, scene_upload.cpp, scene_queries.cpp): the
+// context.h -- what a context is, for the translation units that implement entry points on it (rt_hip.hip, scene_upload.cpp, scene_moved.cpp, scene_queries.cpp): the
 // uploaded scene and its trees, the context and the buffer records behind the C-ABI's opaque handles, how an entry point fails, and the device copies an
 // upload makes.  Internal: never installed, never included by include/.  A feature unit gets the scene (ctx->scene: the kernels' view `d`, the trees, the
 // objects' table), the queries' scratch areas, the stream, the device and its properties.  It may ask for everything in flight to drain before it frees or
@@ -79,11 +79,11 @@ struct Scene
     // allocation failed: treated as off).  pose_valid: a refit has filled it.
     void* pose_snap = nullptr;
     bool pose_valid = false;
-    // rt_scene_set_objects (scene_upload.cpp): the rest pose, every triangle's object and the staging area of rt_scene_pose; nullptr = no objects set
+    // rt_scene_set_objects (scene_moved.cpp): the rest pose, every triangle's object and the staging area of rt_scene_pose; nullptr = no objects set
     pose::State* pose = nullptr;
-    // rt_scene_set_skin (scene_upload.cpp): the rest pose, every corner's influences, the palette and the staging area of rt_scene_skin; nullptr = no skin set
+    // rt_scene_set_skin (scene_moved.cpp): the rest pose, every corner's influences, the palette and the staging area of rt_scene_skin; nullptr = no skin set
     skin::State* skin = nullptr;
-    // rt_scene_set_morph (scene_upload.cpp): the rest pose, the targets' records by triangle, the weights and the staging area of rt_scene_morph / _morph_skin; nullptr = no morph set
+    // rt_scene_set_morph (scene_moved.cpp): the rest pose, the targets' records by triangle, the weights and the staging area of rt_scene_morph / _morph_skin; nullptr = no morph set
     morph::State* morph = nullptr;
 };
 } // namespace context
@@ -163,6 +163,11 @@ int quiesce(rt_ctx* ctx);
 // Everything a scene holds on the device and beside it (its adaptation, refit, pose, skin and morph states) is freed and `s` is an empty scene again.  scene_upload.cpp's:
 // rt_scene_upload and an upload that ends early call it there, rt_ctx_destroy from rt_hip.hip.
 void free_scene(Scene& s);
+
+// The refit (scene_upload.cpp's, with rt_scene_refit*), for scene_moved.cpp's pose, skin and morph too.  refit_refused: why `who` cannot refit this scene now,
+// as the context's error, or RT_OK.  Then refit_device: d_tris (device memory, written on ctx's stream) are validated read-only and become the scene's triangles.
+int refit_refused(rt_ctx* ctx, const char* who, uint64_t count_or_bytes, bool bytes);
+int refit_device(rt_ctx* ctx, const rt_triangle* d_tris, const char* who);
 
 // The re-layout kernels' four launches on ctx's stream (relayout_kernels.h; they are of the hot path's code object, so rt_hip.hip launches them for
 // Upload::relayout_on_device): the reference's node and triangle arrays on the device -> the child-pair records `nodes` in the order `index` gives, the 64-byte

@@ -5,12 +5,12 @@
 // deltas on the device, transposed into one row of 32-byte records per triangle; a kernel writes the morphed triangles into a staging area in rt_triangle
 // layout, and the refit (refit.hip) runs on that as on any other triangle array.
 //
-//   k_morph_rest             once per rt_scene_set_morph: the 128-byte shading records back into rt_triangle layout (the rest pose; k_skin_rest's rule)
 //   k_morph_triangles        one thread per triangle, 256 per block: rest + row + records + weights -> staged (morph.h's arithmetic)
 //   k_morph_skin_triangles   the same morph, then skin.h's blend per corner from the skin's influences and palette -> staged, in one pass
 //
-// Both kernels move the block's 256 triangles (40 KB, contiguous) through LDS in 16-byte pieces exactly as k_pose_triangles and k_skin_triangles do, and a
-// thread morphs its own triangle in place there: a record names its corner at run time, which is an LDS address, not an index into registers (no scratch).
+// The rest pose and the staging area are a moved::Stage (moved.hip makes the rest pose, once per rt_scene_set_morph).  Both kernels move the block's 256
+// triangles (40 KB, contiguous) through LDS in 16-byte pieces as moved_tile.h describes, and a thread morphs its own triangle in place there: a record names
+// its corner at run time, which is an LDS address, not an index into registers (no scratch).
 // A thread streams its own records row[i] .. row[i + 1], each a 16-byte aligned 32-byte piece (the compiler emits a 16-byte and a 12-byte load: `pad` is
 // never used); a block's records are contiguous, so its lines are shared through L1.
 //   k_morph_triangles stages up to LDS_TARGETS weights (4 KB) in LDS once per block; more are gathered from global memory.  40 960 + 4 096 bytes: three
@@ -26,27 +26,14 @@
 #include "morph.h"
 #include "morph_host.h"
 #include "skin_host.h"
+#include "moved_tile.h"
 #include "device_memory.h"
 
 namespace morph
 {
-static_assert(sizeof(rt_triangle) == 10 * sizeof(float4), "rt_triangle = ten 16-byte pieces");
 static_assert(sizeof(rt_morph_delta) == 32 && sizeof(Record) == RECORD_BYTES, "32-byte deltas and records");
 static_assert(256 * 160 + LDS_TARGETS * WEIGHT_BYTES <= 163840 / 3, "k_morph_triangles' LDS: three blocks per CU");
 static_assert(256 * 160 + skin::LDS_BONES * skin::MATRIX_BYTES <= 163840 / 3, "k_morph_skin_triangles' LDS: three blocks per CU");
-
-__global__ __launch_bounds__(256) void k_morph_rest(const float4* __restrict__ tsh, uint32_t nt, float4* __restrict__ rest)
-{
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    if (i >= nt) return;
-    const float4* q = tsh + (size_t)i * 8;
-    const float4 a = q[0], b = q[1], c = q[2], n1 = q[3], n2 = q[4], n3 = q[5], m = q[6];
-    float4* o = rest + (size_t)i * 10;
-    o[0] = make_float4(a.x, a.y, a.z, 0.0f); o[1] = make_float4(a.w, b.w, 0.0f, 0.0f);   o[2] = make_float4(n1.x, n1.y, n1.z, 0.0f);
-    o[3] = make_float4(b.x, b.y, b.z, 0.0f); o[4] = make_float4(c.w, n1.w, 0.0f, 0.0f);  o[5] = make_float4(n2.x, n2.y, n2.z, 0.0f);
-    o[6] = make_float4(c.x, c.y, c.z, 0.0f); o[7] = make_float4(n2.w, n3.w, 0.0f, 0.0f); o[8] = make_float4(n3.x, n3.y, n3.z, 0.0f);
-    o[9] = make_float4(m.x, 0.0f, 0.0f, 0.0f);
-}
 
 // triangle i's row, never past row[nt] (i < nt) and never past the records
 __device__ inline void row_of(const uint32_t* __restrict__ row, uint32_t i, uint32_t n_records, uint32_t& begin, uint32_t& count)
@@ -61,41 +48,22 @@ __global__ __launch_bounds__(256) void k_morph_triangles(const float4* __restric
 {
     __shared__ float4 tile[256 * 10];
     __shared__ float staged_weights[LDS_TARGETS];
-    const uint32_t first = blockIdx.x * 256u;                      // < nt: the grid is ceil(nt / 256) blocks
-    const uint32_t n = nt - first < 256u ? nt - first : 256u;      // this block's triangles
-    const uint32_t pieces = n * 10u;
-    const size_t base = (size_t)first * 10;
-    for (uint32_t k = threadIdx.x; k < pieces; k += 256u) tile[k] = rest[base + k];
+    const moved::Tile b = moved::block_tile(nt);
+    moved::load_tile(b, rest, tile);
     const bool staged = n_targets <= (uint32_t)LDS_TARGETS;        // the same for every block of a launch
     if (staged)
         for (uint32_t k = threadIdx.x; k < n_targets; k += 256u) staged_weights[k] = weights[k];
     __syncthreads();
-    if (threadIdx.x < n)
+    if (threadIdx.x < b.n)
     {
         uint32_t begin, count;
-        row_of(row, first + threadIdx.x, n_records, begin, count);
+        row_of(row, b.first + threadIdx.x, n_records, begin, count);
         rt_triangle& t = *reinterpret_cast<rt_triangle*>(&tile[threadIdx.x * 10u]);
         if (staged) morph_triangle(records + begin, count, staged_weights, n_targets, t);
         else morph_triangle(records + begin, count, weights, n_targets, t);
     }
     __syncthreads();
-    for (uint32_t k = threadIdx.x; k < pieces; k += 256u) out[base + k] = tile[k];
-}
-
-// one corner from its three 8-byte words: (bone 0 | bone 1 << 16, bone 2 | bone 3 << 16), (w0, w1), (w2, w3) -- skin.hip's rule, restated for this code object
-__device__ inline void skin_corner(const float* palette, uint32_t n_bones, uint2 bones, uint2 w01, uint2 w23, rt_vertex& v)
-{
-    const uint32_t b0 = bones.x & 0xFFFFu, b1 = bones.x >> 16, b2 = bones.y & 0xFFFFu, b3 = bones.y >> 16;
-    if (b0 >= n_bones || b1 >= n_bones || b2 >= n_bones || b3 >= n_bones) return;       // (rt_scene_set_skin has checked every index)
-    const float w[4] = {__uint_as_float(w01.x), __uint_as_float(w01.y), __uint_as_float(w23.x), __uint_as_float(w23.y)};
-    skin::skin_vertex(palette + b0 * 12u, palette + b1 * 12u, palette + b2 * 12u, palette + b3 * 12u, w, v);
-}
-
-__device__ inline void skin_triangle(const float* palette, uint32_t n_bones, const uint2* q, rt_triangle& t)
-{
-    skin_corner(palette, n_bones, q[0], q[1], q[2], t.v1);
-    skin_corner(palette, n_bones, q[3], q[4], q[5], t.v2);
-    skin_corner(palette, n_bones, q[6], q[7], q[8], t.v3);
+    moved::store_tile(b, tile, out);
 }
 
 __global__ __launch_bounds__(256) void k_morph_skin_triangles(const float4* __restrict__ rest, const uint32_t* __restrict__ row, const Record* __restrict__ records,
@@ -104,29 +72,26 @@ __global__ __launch_bounds__(256) void k_morph_skin_triangles(const float4* __re
 {
     __shared__ float4 tile[256 * 10];
     __shared__ float4 bones[skin::LDS_BONES * 3];
-    const uint32_t first = blockIdx.x * 256u;                      // < nt: the grid is ceil(nt / 256) blocks
-    const uint32_t n = nt - first < 256u ? nt - first : 256u;      // this block's triangles
-    const uint32_t pieces = n * 10u;
-    const size_t base = (size_t)first * 10;
-    for (uint32_t k = threadIdx.x; k < pieces; k += 256u) tile[k] = rest[base + k];
+    const moved::Tile b = moved::block_tile(nt);
+    moved::load_tile(b, rest, tile);
     const bool staged = n_bones <= (uint32_t)skin::LDS_BONES;      // the same for every block of a launch
     if (staged)
         for (uint32_t k = threadIdx.x; k < n_bones * 3u; k += 256u) bones[k] = reinterpret_cast<const float4*>(palette)[k];
     __syncthreads();
-    if (threadIdx.x < n)
+    if (threadIdx.x < b.n)
     {
-        const uint32_t i = first + threadIdx.x;
+        const uint32_t i = b.first + threadIdx.x;
         uint2 q[9];                                                // this triangle's influences: 72 bytes from an 8-byte aligned address (i * 72)
         for (uint32_t j = 0; j < 9u; ++j) q[j] = influences[(size_t)i * 9 + j];
         uint32_t begin, count;
         row_of(row, i, n_records, begin, count);
         rt_triangle& t = *reinterpret_cast<rt_triangle*>(&tile[threadIdx.x * 10u]);
         morph_triangle(records + begin, count, weights, n_targets, t);
-        if (staged) skin_triangle(reinterpret_cast<const float*>(bones), n_bones, q, t);
-        else skin_triangle(palette, n_bones, q, t);
+        if (staged) skin::skin_triangle(reinterpret_cast<const float*>(bones), n_bones, q, t);
+        else skin::skin_triangle(palette, n_bones, q, t);
     }
     __syncthreads();
-    for (uint32_t k = threadIdx.x; k < pieces; k += 256u) out[base + k] = tile[k];
+    moved::store_tile(b, tile, out);
 }
 
 // ---- the host side ---------------------------------------------------------------------------------------------------------------------------------
@@ -182,7 +147,7 @@ bool transpose(const rt_morph_delta* deltas, const uint32_t* target_offsets, uin
 
 void release(State& st)
 {
-    dev::drop(st.rest); dev::drop(st.row); dev::drop(st.records); dev::drop(st.staged); dev::drop(st.weights);
+    st.stage.release(); dev::drop(st.row); dev::drop(st.records); dev::drop(st.weights);
     if (st.host_weights) (void)hipHostFree(st.host_weights);
     st = State();
 }
@@ -190,19 +155,14 @@ void release(State& st)
 bool arm(hipStream_t stream, State& st, const float4* tris_sh, const std::vector<uint32_t>& row, const std::vector<Record>& records, uint32_t nt, uint32_t n_targets)
 {
     release(st);
-    st.n_tris = nt; st.n_targets = n_targets; st.n_deltas = (uint32_t)records.size();
+    st.n_targets = n_targets; st.n_deltas = (uint32_t)records.size();
     const size_t row_bytes = ((size_t)nt + 1) * ROW_BYTES, record_bytes = records.size() * RECORD_BYTES;   // (no records: dev::alloc never asks for 0 bytes)
     st.bytes = (size_t)nt * (REST_BYTES + STAGED_BYTES) + row_bytes + record_bytes + (size_t)n_targets * WEIGHT_BYTES;
-    bool ok = dev::get(st.rest, (size_t)nt * REST_BYTES) && dev::get(st.staged, (size_t)nt * STAGED_BYTES) && dev::get(st.row, row_bytes) &&
+    bool ok = st.stage.arm(stream, tris_sh, nt) && dev::get(st.row, row_bytes) &&
               dev::get(st.records, record_bytes) && dev::get(st.weights, (size_t)n_targets * WEIGHT_BYTES) &&
               hipHostMalloc((void**)&st.host_weights, (size_t)n_targets * WEIGHT_BYTES) == hipSuccess &&
               hipMemcpyAsync(st.row, row.data(), row_bytes, hipMemcpyHostToDevice, stream) == hipSuccess &&
               (record_bytes == 0 || hipMemcpyAsync(st.records, records.data(), record_bytes, hipMemcpyHostToDevice, stream) == hipSuccess);
-    if (ok)
-    {
-        hipLaunchKernelGGL(k_morph_rest, dim3(dev::blocks_for(nt, 256u)), dim3(256), 0, stream, tris_sh, nt, (float4*)st.rest);
-        ok = dev::clean();
-    }
     ok = hipStreamSynchronize(stream) == hipSuccess && ok;          // row and records are the caller's vectors: read before they go
     if (!ok) { (void)hipGetLastError(); release(st); }
     return ok;
@@ -217,16 +177,17 @@ static bool upload_weights(hipStream_t stream, State& st, const float* weights)
 bool run(hipStream_t stream, State& st, const float* weights)
 {
     if (!upload_weights(stream, st, weights)) return false;
-    hipLaunchKernelGGL(k_morph_triangles, dim3(dev::blocks_for(st.n_tris, 256u)), dim3(256), 0, stream, (const float4*)st.rest, (const uint32_t*)st.row,
-        (const Record*)st.records, (const float*)st.weights, st.n_tris, st.n_targets, st.n_deltas, (float4*)st.staged);
+    hipLaunchKernelGGL(k_morph_triangles, dim3(dev::blocks_for(st.stage.n_tris, 256u)), dim3(256), 0, stream, (const float4*)st.stage.rest, (const uint32_t*)st.row,
+        (const Record*)st.records, (const float*)st.weights, st.stage.n_tris, st.n_targets, st.n_deltas, (float4*)st.stage.staged);
     return dev::clean();
 }
 
 bool run_skin(hipStream_t stream, State& st, const float* weights, const rt_skin_influence* d_influences, const float* d_palette, uint32_t n_bones)
 {
     if (!upload_weights(stream, st, weights)) return false;
-    hipLaunchKernelGGL(k_morph_skin_triangles, dim3(dev::blocks_for(st.n_tris, 256u)), dim3(256), 0, stream, (const float4*)st.rest, (const uint32_t*)st.row,
-        (const Record*)st.records, (const float*)st.weights, st.n_tris, st.n_targets, st.n_deltas, (const uint2*)d_influences, d_palette, n_bones, (float4*)st.staged);
+    hipLaunchKernelGGL(k_morph_skin_triangles, dim3(dev::blocks_for(st.stage.n_tris, 256u)), dim3(256), 0, stream, (const float4*)st.stage.rest, (const uint32_t*)st.row,
+        (const Record*)st.records, (const float*)st.weights, st.stage.n_tris, st.n_targets, st.n_deltas, (const uint2*)d_influences, d_palette, n_bones,
+        (float4*)st.stage.staged);
     return dev::clean();
 }
 

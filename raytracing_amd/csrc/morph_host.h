@@ -9,13 +9,14 @@
 #include <vector>
 #include "rt_hip.h"          // rt_morph_delta, rt_skin_influence
 #include "rt_types.h"
+#include "moved.h"           // moved::Stage
 
 namespace morph
 {
 struct Record;               // morph.h: one delta of one target at one corner, 32 bytes
 // what rt_scene_set_morph keeps beside the scene: per triangle the rest pose in rt_triangle layout (160 bytes), the staging area a morph is written to before
 // the refit reads it (160) and one word of the row table (4); per delta one record (32); per target one weight (4)
-enum { REST_BYTES = 160, STAGED_BYTES = 160, ROW_BYTES = 4, RECORD_BYTES = 32, WEIGHT_BYTES = 4 };
+enum { REST_BYTES = moved::REST_BYTES, STAGED_BYTES = moved::STAGED_BYTES, ROW_BYTES = 4, RECORD_BYTES = 32, WEIGHT_BYTES = 4 };
 // up to LDS_TARGETS weights are staged in LDS once per block by k_morph_triangles (4 KB: with the 40 KB tile, three blocks per CU); more are gathered through
 // the vector L1 / L2
 enum { MAX_TARGETS = 65536, LDS_TARGETS = 1024 };
@@ -24,11 +25,10 @@ enum : uint32_t { MAX_TRIANGLES = 0xFFFFFFFFu / 3u };
 
 struct State
 {
-    uint32_t n_tris = 0, n_targets = 0, n_deltas = 0;
-    rt_triangle* rest = nullptr;         // the pose rt_scene_set_morph saw
-    uint32_t* row = nullptr;             // n_tris + 1: triangle i owns records[row[i] .. row[i + 1])
+    uint32_t n_targets = 0, n_deltas = 0;
+    moved::Stage stage;                  // the pose rt_scene_set_morph saw; the kernels' output, refit_device's input
+    uint32_t* row = nullptr;             // stage.n_tris + 1: triangle i owns records[row[i] .. row[i + 1])
     Record* records = nullptr;           // n_deltas, by triangle, then target, then corner
-    rt_triangle* staged = nullptr;       // the kernels' output, refit_device's input
     float* weights = nullptr;            // n_targets on the device ...
     float* host_weights = nullptr;       // ... and in pinned host memory, filled by every morph
     size_t bytes = 0;
@@ -42,7 +42,7 @@ bool weights_finite(const float* weights, uint32_t n_targets);
 // a checked table by triangle: row[nt + 1] and the records sorted by triangle, then target, then corner.  false: no host memory for them
 bool transpose(const rt_morph_delta* deltas, const uint32_t* target_offsets, uint32_t n_targets, uint32_t nt, std::vector<uint32_t>& row, std::vector<Record>& records);
 
-// everything a morph needs, allocated here so that a morph allocates nothing; the rest pose by k_skin_rest's rule.  Waits for the stream.
+// everything a morph needs, allocated here so that a morph allocates nothing; the rest pose is moved::Stage::arm's.  Waits for the stream.
 // false: an allocation, a copy or the launch failed, and st is released
 bool arm(hipStream_t stream, State& st, const float4* tris_sh, const std::vector<uint32_t>& row, const std::vector<Record>& records, uint32_t nt, uint32_t n_targets);
 void release(State& st);

@@ -3,54 +3,36 @@
 // A rigid or affine move of an object is 12 floats, not 160 bytes per triangle: the scene keeps its rest pose and every triangle's object on the device,
 // k_pose_triangles writes the posed triangles into a staging area in rt_triangle layout, and the refit (refit.hip) runs on that as on any other triangle array.
 //
-//   k_pose_rest        once per rt_scene_set_objects: the 128-byte shading records back into rt_triangle layout (the rest pose)
 //   k_pose_triangles   one thread per triangle, 256 per block: rest + object -> staged (pose.h's arithmetic)
 //
-// k_pose_triangles is a pure stream, 164 bytes read and 160 written per triangle.  A lane's triangle is ten 16-byte pieces 160 bytes apart from its neighbour's,
-// so a block moves its 256 triangles (40 KB, contiguous) through LDS: piece k of the block is loaded and stored by thread k mod 256, one 16-byte access per lane
-// with consecutive lanes on consecutive addresses, and each thread transforms its own triangle in LDS in between (positions and normals; the other lanes are not
-// touched).  An object's 96 bytes come through the vector L1: neighbouring triangles share an object.  -ffp-contract=off like every other unit.
+// The rest pose and the staging area are a moved::Stage (moved.hip makes the rest pose, once per rt_scene_set_objects).  k_pose_triangles is a pure stream,
+// 164 bytes read and 160 written per triangle: a block moves its 256 triangles (40 KB, contiguous) through LDS as moved_tile.h describes, and each thread
+// transforms its own triangle in LDS in between (positions and normals; the other lanes are not touched).  An object's 96 bytes come through the vector L1:
+// neighbouring triangles share an object.  -ffp-contract=off like every other unit.
 #include <hip/hip_runtime.h>
 #include <vector>
 #include "pose.h"
 #include "pose_host.h"
+#include "moved_tile.h"
 #include "device_memory.h"
 
 namespace pose
 {
-static_assert(sizeof(rt_triangle) == 10 * sizeof(float4), "rt_triangle = ten 16-byte pieces");
-
-__global__ __launch_bounds__(256) void k_pose_rest(const float4* __restrict__ tsh, uint32_t nt, float4* __restrict__ rest)
-{
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    if (i >= nt) return;
-    const float4* q = tsh + (size_t)i * 8;
-    const float4 a = q[0], b = q[1], c = q[2], n1 = q[3], n2 = q[4], n3 = q[5], m = q[6];
-    float4* o = rest + (size_t)i * 10;
-    o[0] = make_float4(a.x, a.y, a.z, 0.0f); o[1] = make_float4(a.w, b.w, 0.0f, 0.0f);   o[2] = make_float4(n1.x, n1.y, n1.z, 0.0f);
-    o[3] = make_float4(b.x, b.y, b.z, 0.0f); o[4] = make_float4(c.w, n1.w, 0.0f, 0.0f);  o[5] = make_float4(n2.x, n2.y, n2.z, 0.0f);
-    o[6] = make_float4(c.x, c.y, c.z, 0.0f); o[7] = make_float4(n2.w, n3.w, 0.0f, 0.0f); o[8] = make_float4(n3.x, n3.y, n3.z, 0.0f);
-    o[9] = make_float4(m.x, 0.0f, 0.0f, 0.0f);
-}
-
 __global__ __launch_bounds__(256) void k_pose_triangles(const float4* __restrict__ rest, const uint32_t* __restrict__ ids, const Object* __restrict__ objects,
     uint32_t nt, uint32_t n_objects, float4* __restrict__ out)
 {
     __shared__ float4 tile[256 * 10];
-    const uint32_t first = blockIdx.x * 256u;                      // < nt: the grid is ceil(nt / 256) blocks
-    const uint32_t n = nt - first < 256u ? nt - first : 256u;      // this block's triangles
-    const uint32_t pieces = n * 10u;
-    const size_t base = (size_t)first * 10;
-    for (uint32_t k = threadIdx.x; k < pieces; k += 256u) tile[k] = rest[base + k];
+    const moved::Tile b = moved::block_tile(nt);
+    moved::load_tile(b, rest, tile);
     __syncthreads();
-    if (threadIdx.x < n)
+    if (threadIdx.x < b.n)
     {
-        const uint32_t id = ids[first + threadIdx.x];
+        const uint32_t id = ids[b.first + threadIdx.x];
         if (id < n_objects)                                        // (rt_scene_set_objects has checked every id)
             pose_triangle(objects[id], *reinterpret_cast<rt_triangle*>(&tile[threadIdx.x * 10u]));
     }
     __syncthreads();
-    for (uint32_t k = threadIdx.x; k < pieces; k += 256u) out[base + k] = tile[k];
+    moved::store_tile(b, tile, out);
 }
 
 // ---- the host side ---------------------------------------------------------------------------------------------------------------------------------
@@ -73,7 +55,7 @@ static void make_objects(const float* m, uint32_t n_objects, Object* out)
 
 void release(State& st)
 {
-    dev::drop(st.rest); dev::drop(st.ids); dev::drop(st.staged); dev::drop(st.objects);
+    st.stage.release(); dev::drop(st.ids); dev::drop(st.objects);
     if (st.host_objects) (void)hipHostFree(st.host_objects);
     st = State();
 }
@@ -81,16 +63,11 @@ void release(State& st)
 bool arm(hipStream_t stream, State& st, const float4* tris_sh, const uint32_t* ids, uint32_t nt, uint32_t n_objects)
 {
     release(st);
-    st.n_tris = nt; st.n_objects = n_objects;
+    st.n_objects = n_objects;
     st.bytes = (size_t)nt * BYTES_PER_TRIANGLE + (size_t)n_objects * sizeof(Object);
-    bool ok = dev::get(st.rest, (size_t)nt * REST_BYTES) && dev::get(st.ids, (size_t)nt * ID_BYTES) && dev::get(st.staged, (size_t)nt * STAGED_BYTES) &&
-              dev::get(st.objects, (size_t)n_objects * sizeof(Object)) && hipHostMalloc(&st.host_objects, (size_t)n_objects * sizeof(Object)) == hipSuccess &&
+    bool ok = st.stage.arm(stream, tris_sh, nt) && dev::get(st.ids, (size_t)nt * ID_BYTES) && dev::get(st.objects, (size_t)n_objects * sizeof(Object)) &&
+              hipHostMalloc(&st.host_objects, (size_t)n_objects * sizeof(Object)) == hipSuccess &&
               hipMemcpyAsync(st.ids, ids, (size_t)nt * ID_BYTES, hipMemcpyHostToDevice, stream) == hipSuccess;
-    if (ok)
-    {
-        hipLaunchKernelGGL(k_pose_rest, dim3(dev::blocks_for(nt, 256u)), dim3(256), 0, stream, tris_sh, nt, (float4*)st.rest);
-        ok = dev::clean();
-    }
     ok = hipStreamSynchronize(stream) == hipSuccess && ok;
     if (!ok) { (void)hipGetLastError(); release(st); }
     return ok;
@@ -100,8 +77,8 @@ bool run(hipStream_t stream, State& st, const float* matrices3x4)
 {
     make_objects(matrices3x4, st.n_objects, (Object*)st.host_objects);
     if (hipMemcpyAsync(st.objects, st.host_objects, (size_t)st.n_objects * sizeof(Object), hipMemcpyHostToDevice, stream) != hipSuccess) return false;
-    hipLaunchKernelGGL(k_pose_triangles, dim3(dev::blocks_for(st.n_tris, 256u)), dim3(256), 0, stream, (const float4*)st.rest, (const uint32_t*)st.ids, (const Object*)st.objects,
-        st.n_tris, st.n_objects, (float4*)st.staged);
+    hipLaunchKernelGGL(k_pose_triangles, dim3(dev::blocks_for(st.stage.n_tris, 256u)), dim3(256), 0, stream, (const float4*)st.stage.rest, (const uint32_t*)st.ids,
+        (const Object*)st.objects, st.stage.n_tris, st.n_objects, (float4*)st.stage.staged);
     return dev::clean();
 }
 

@@ -7,19 +7,19 @@
 #include <stdint.h>
 #include <stddef.h>
 #include "rt_types.h"
+#include "moved.h"           // moved::Stage
 
 namespace pose
 {
 // what rt_scene_set_objects keeps beside the scene, per triangle: the rest pose in rt_triangle layout (160 bytes), its object (4) and the staging area a pose
 // is written to before the refit reads it (160)
-enum { REST_BYTES = 160, ID_BYTES = 4, STAGED_BYTES = 160, BYTES_PER_TRIANGLE = REST_BYTES + ID_BYTES + STAGED_BYTES };
+enum { REST_BYTES = moved::REST_BYTES, ID_BYTES = 4, STAGED_BYTES = moved::STAGED_BYTES, BYTES_PER_TRIANGLE = REST_BYTES + ID_BYTES + STAGED_BYTES };
 
 struct State
 {
-    uint32_t n_tris = 0, n_objects = 0;
-    rt_triangle* rest = nullptr;         // the pose rt_scene_set_objects saw
+    uint32_t n_objects = 0;
+    moved::Stage stage;                  // the pose rt_scene_set_objects saw; k_pose_triangles' output, refit_device's input
     uint32_t* ids = nullptr;             // object of every triangle
-    rt_triangle* staged = nullptr;       // k_pose_triangles' output, refit_device's input
     void* objects = nullptr;             // pose::Object[n_objects] on the device ...
     void* host_objects = nullptr;        // ... and in pinned host memory, filled by every pose
     size_t bytes = 0;
@@ -28,8 +28,7 @@ struct State
 bool ids_in_range(const uint32_t* ids, uint32_t nt, uint32_t n_objects);
 bool matrices_finite(const float* matrices3x4, uint32_t n_objects);
 
-// everything a pose needs, allocated here so that a pose allocates nothing; the rest pose = the shading records' positions, normals, texture coordinates and
-// material index (every field k_refit_triangles reads from an rt_triangle; the .w lanes, texcoord.z and the padding are zero).  Waits for the stream.
+// everything a pose needs, allocated here so that a pose allocates nothing; the rest pose is moved::Stage::arm's.  Waits for the stream.
 // false: an allocation, a copy or the launch failed, and st is released
 bool arm(hipStream_t stream, State& st, const float4* tris_sh, const uint32_t* ids, uint32_t nt, uint32_t n_objects);
 void release(State& st);

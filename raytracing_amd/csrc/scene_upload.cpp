@@ -1,7 +1,7 @@
 // scene_upload.cpp -- the scene side of the library: how a scene is uploaded (rt_scene_upload and its stages), how its trees are chosen, folded and
-// adapted (OwnTree, choose_tree, FoldAdapt's worker), refitted (rt_scene_refit*), posed (rt_scene_set_objects, rt_scene_pose), handed from one context of a
-// group to another (rt_scene_export_folds, rt_scene_import_folds) and inspected (rt_scene_tree_report, the rt_debug_* forms of the tree work).  Host code
-// only, on context.h and fold_adapt.h: the tree work on the device goes through devfold::, refit::, pose:: and filt::, units of their own, and the three
+// adapted (OwnTree, choose_tree, FoldAdapt's worker), refitted (rt_scene_refit*; refit_device is also where every pose, skin and morph of scene_moved.cpp
+// ends), handed from one context of a group to another (rt_scene_export_folds, rt_scene_import_folds) and inspected (rt_scene_tree_report, the rt_debug_*
+// forms of the tree work).  Host code only, on context.h and fold_adapt.h: the tree work on the device goes through devfold::, refit:: and filt::, units of their own, and the three
 // things this file needs of the frames' unit are context.h's -- quiesce, relayout_records (the one place it would launch kernels of the hot path's code
 // object) and fail.  It touches no frame; the adaptation's render-thread side -- probe, hand-over, adoption -- is rt_hip.hip's (fold_hooks_impl.h).
 #include <hip/hip_runtime_api.h>
@@ -25,10 +25,6 @@
 #include "wide_bvh.h"        // the host-side fold, the pair layout, the adaptation's host walks (wide_bvh.cpp); wide_node.h: RT_LEAF_BIT, RT_EMPTY_REF
 #include "device_fold.h"     // ... and the fold + crossing counts on the device (device_fold.hip)
 #include "refit.h"           // the refit of the scene's trees when its triangles move (refit.hip)
-#include "pose_host.h"       // the scene's objects posed from one matrix per object (pose.hip)
-#include "skin_host.h"       // the scene's triangles skinned from a palette of bone matrices (skin.hip)
-#include "morph.h"           // morph::Record
-#include "morph_host.h"      // the scene's triangles morphed from one weight per target, alone or fused with the skin (morph.hip)
 #include "filters_host.h"    // filt::snapshot_pose, the pose a refit replaces (filters.hip)
 #include "device_memory.h"   // who owns a device allocation: dev::Mem
 using namespace rtw;
@@ -953,7 +949,9 @@ static bool refit_link_trees(rt_ctx* ctx)
            refit::link_tree(ctx->stream, *s.refit, 1, own_sh ? (WideNode*)sh.recs : nullptr, sh.n, s.d.w_sh_entry_ref);
 }
 
-static int refit_device(rt_ctx* ctx, const rt_triangle* d_tris, const char* who)
+} // extern "C": the next two are context.h's, for the producers of moved triangles too (scene_moved.cpp)
+
+int context::refit_device(rt_ctx* ctx, const rt_triangle* d_tris, const char* who)
 {
     Scene& s = ctx->scene;
     const std::string name(who);
@@ -1008,7 +1006,7 @@ static int refit_device(rt_ctx* ctx, const rt_triangle* d_tris, const char* who)
     return RT_OK;
 }
 
-static int refit_refused(rt_ctx* ctx, const char* who, uint64_t count_or_bytes, bool bytes)
+int context::refit_refused(rt_ctx* ctx, const char* who, uint64_t count_or_bytes, bool bytes)
 {
     const std::string name(who);
     Scene& s = ctx->scene;
@@ -1019,6 +1017,8 @@ static int refit_refused(rt_ctx* ctx, const char* who, uint64_t count_or_bytes, 
         return fail(ctx, name + ": the triangle count differs from the uploaded scene's");
     return RT_OK;
 }
+
+extern "C" {
 
 int rt_scene_refit_buffer(rt_ctx* ctx, rt_buffer* triangles)
 {
@@ -1051,284 +1051,6 @@ int rt_debug_refit(rt_ctx* ctx, const rt_bvh_node* nodes, uint32_t num_nodes, co
                         : refit::debug_host(nodes, num_nodes, triangles, num_triangles, (const WideNode*)records, num_records, entry_ref, out_nodes, (WideNode*)out_records, &bad, error);
     if (!ok) return fail(ctx, "rt_debug_refit: " + error);
     return bad ? RT_REFIT_DISQUALIFIED : RT_OK;
-}
-
-// ---- posed objects: rt_scene_set_objects / rt_scene_pose / rt_debug_pose, the bookkeeping around pose.hip's kernels -------------
-// A pose IS a refit: rt_scene_pose writes the posed triangles into the staging area rt_scene_set_objects allocated and hands it to refit_device() unchanged.
-
-// the report keeps one line that begins with `prefix`, before the refit's own (which is replaced, with all that follows it, by every refit)
-static void keep_one_line_before_refit(std::string& r, const char* prefix, const char* line)
-{
-    auto line_that_begins = [&r](const char* word)                   // only at the start of a line: another line may hold the word
-    {
-        size_t at = r.find(word);
-        while (at != std::string::npos && at != 0 && r[at - 1] != '\n') at = r.find(word, at + 1);
-        return at;
-    };
-    const size_t old = line_that_begins(prefix);
-    if (old != std::string::npos) r.erase(old, r.find('\n', old) == std::string::npos ? std::string::npos : r.find('\n', old) - old + 1);
-    const size_t at = line_that_begins("refit ");
-    r.insert(at == std::string::npos ? r.size() : at, line);
-}
-
-int rt_scene_set_objects(rt_ctx* ctx, const uint32_t* object_of_triangle, uint32_t num_triangles, uint32_t num_objects)
-{
-    if (!ctx || !object_of_triangle) return fail(ctx, "rt_scene_set_objects: NULL argument");
-    if (refit_refused(ctx, "rt_scene_set_objects", num_triangles, false) != RT_OK) return RT_ERROR;
-    if (num_objects == 0u) return fail(ctx, "rt_scene_set_objects: no objects");
-    if (!pose::ids_in_range(object_of_triangle, num_triangles, num_objects)) return fail(ctx, "rt_scene_set_objects: an object index is not below num_objects");
-    (void)hipSetDevice(ctx->device);
-    Scene& s = ctx->scene;
-    pose::State* st = new pose::State();
-    if (!pose::arm(ctx->stream, *st, (const float4*)s.tris_sh, object_of_triangle, num_triangles, num_objects))
-    {
-        delete st;
-        return fail(ctx, "rt_scene_set_objects: the rest pose and the staging area could not be allocated");
-    }
-    if (s.pose) { pose::release(*s.pose); delete s.pose; }
-    s.pose = st;
-    char line[300];
-    snprintf(line, sizeof(line), "posed objects: %u objects, %u bytes per triangle kept (%.1f MB): rest pose %u + object index %u + staging area %u\n", num_objects,
-        (unsigned)pose::BYTES_PER_TRIANGLE, (double)s.n_tris * pose::BYTES_PER_TRIANGLE / 1e6, (unsigned)pose::REST_BYTES, (unsigned)pose::ID_BYTES, (unsigned)pose::STAGED_BYTES);
-    keep_one_line_before_refit(s.tree_report, "posed objects: ", line);
-    return RT_OK;
-}
-
-int rt_scene_pose(rt_ctx* ctx, const float* matrices3x4, uint32_t num_objects)
-{
-    if (!ctx || !matrices3x4) return fail(ctx, "rt_scene_pose: NULL argument");
-    Scene& s = ctx->scene;
-    if (refit_refused(ctx, "rt_scene_pose", s.n_tris, false) != RT_OK) return RT_ERROR;
-    if (!s.pose) return fail(ctx, "rt_scene_pose: no objects (rt_scene_set_objects has not been called for this scene)");
-    if (num_objects != s.pose->n_objects) return fail(ctx, "rt_scene_pose: the object count differs from rt_scene_set_objects'");
-    if (!pose::matrices_finite(matrices3x4, num_objects)) return fail(ctx, "rt_scene_pose: a matrix entry is not finite");
-    (void)hipSetDevice(ctx->device);
-    if (!pose::run(ctx->stream, *s.pose, matrices3x4))
-    {
-        (void)hipGetLastError();
-        return fail(ctx, "rt_scene_pose: the pose kernel could not be launched");
-    }
-    return refit_device(ctx, s.pose->staged, "rt_scene_pose");
-}
-
-int rt_debug_pose(rt_ctx* ctx, const rt_triangle* rest, const uint32_t* object_of_triangle, uint32_t num_triangles, const float* matrices3x4, uint32_t num_objects,
-    rt_triangle* out)
-{
-    if (!rest || !object_of_triangle || !matrices3x4 || !out) return fail(ctx, "rt_debug_pose: NULL argument");
-    if (num_triangles == 0u) return fail(ctx, "rt_debug_pose: no triangles");
-    if (num_objects == 0u) return fail(ctx, "rt_debug_pose: no objects");
-    if (!pose::ids_in_range(object_of_triangle, num_triangles, num_objects)) return fail(ctx, "rt_debug_pose: an object index is not below num_objects");
-    if (!pose::matrices_finite(matrices3x4, num_objects)) return fail(ctx, "rt_debug_pose: a matrix entry is not finite");
-    if (!ctx) { pose::debug_host(rest, object_of_triangle, num_triangles, matrices3x4, num_objects, out); return RT_OK; }
-    (void)hipSetDevice(ctx->device);
-    if (!pose::debug_device(ctx->stream, rest, object_of_triangle, num_triangles, matrices3x4, num_objects, out))
-        return fail(ctx, "rt_debug_pose: the device path failed (allocation, copy or launch)");
-    return RT_OK;
-}
-
-// ---- skinned triangles: rt_scene_set_skin / rt_scene_skin / rt_debug_skin, the bookkeeping around skin.hip's kernels --------------
-// A skin IS a refit, as a pose is: rt_scene_skin writes the skinned triangles into the staging area rt_scene_set_skin allocated and hands it to refit_device()
-// unchanged.  The skin's state and the objects' are independent: each keeps a rest pose of its own, and whichever of pose / skin / refit ran last is the scene.
-
-static int skin_table_refused(rt_ctx* ctx, const char* who, const rt_skin_influence* per_corner, uint32_t num_triangles, uint32_t num_bones)
-{
-    const std::string name(who);
-    if (num_bones == 0u) return fail(ctx, name + ": no bones");
-    if (num_bones > (uint32_t)skin::MAX_BONES) return fail(ctx, name + ": more than 65536 bones (a bone index is 16 bits)");
-    switch (skin::influences_fault(per_corner, num_triangles, num_bones))
-    {
-    case 0: return RT_OK;
-    case 1: return fail(ctx, name + ": a bone index is not below num_bones");
-    default: return fail(ctx, name + ": a weight is not finite");
-    }
-}
-
-int rt_scene_set_skin(rt_ctx* ctx, const rt_skin_influence* per_corner, uint32_t num_triangles, uint32_t num_bones)
-{
-    if (!ctx || !per_corner) return fail(ctx, "rt_scene_set_skin: NULL argument");
-    if (refit_refused(ctx, "rt_scene_set_skin", num_triangles, false) != RT_OK) return RT_ERROR;
-    if (skin_table_refused(ctx, "rt_scene_set_skin", per_corner, num_triangles, num_bones) != RT_OK) return RT_ERROR;
-    (void)hipSetDevice(ctx->device);
-    Scene& s = ctx->scene;
-    skin::State* st = new skin::State();
-    if (!skin::arm(ctx->stream, *st, (const float4*)s.tris_sh, per_corner, num_triangles, num_bones))
-    {
-        delete st;
-        return fail(ctx, "rt_scene_set_skin: the rest pose, the influences and the staging area could not be allocated");
-    }
-    if (s.skin) { skin::release(*s.skin); delete s.skin; }
-    s.skin = st;
-    char line[300];
-    snprintf(line, sizeof(line), "skinned triangles: %u bones, %u bytes per triangle kept (%.1f MB): rest pose %u + influences %u + staging area %u; the palette %u bytes per bone\n",
-        num_bones, (unsigned)skin::BYTES_PER_TRIANGLE, (double)s.n_tris * skin::BYTES_PER_TRIANGLE / 1e6, (unsigned)skin::REST_BYTES, (unsigned)skin::INFLUENCE_BYTES,
-        (unsigned)skin::STAGED_BYTES, (unsigned)skin::MATRIX_BYTES);
-    keep_one_line_before_refit(s.tree_report, "skinned triangles: ", line);
-    return RT_OK;
-}
-
-int rt_scene_skin(rt_ctx* ctx, const float* matrices3x4, uint32_t num_bones)
-{
-    if (!ctx || !matrices3x4) return fail(ctx, "rt_scene_skin: NULL argument");
-    Scene& s = ctx->scene;
-    if (refit_refused(ctx, "rt_scene_skin", s.n_tris, false) != RT_OK) return RT_ERROR;
-    if (!s.skin) return fail(ctx, "rt_scene_skin: no skin (rt_scene_set_skin has not been called for this scene)");
-    if (num_bones != s.skin->n_bones) return fail(ctx, "rt_scene_skin: the bone count differs from rt_scene_set_skin's");
-    if (!skin::matrices_finite(matrices3x4, num_bones)) return fail(ctx, "rt_scene_skin: a matrix entry is not finite");
-    (void)hipSetDevice(ctx->device);
-    if (!skin::run(ctx->stream, *s.skin, matrices3x4))
-    {
-        (void)hipGetLastError();
-        return fail(ctx, "rt_scene_skin: the skin kernel could not be launched");
-    }
-    return refit_device(ctx, s.skin->staged, "rt_scene_skin");
-}
-
-int rt_debug_skin(rt_ctx* ctx, const rt_triangle* rest, const rt_skin_influence* per_corner, uint32_t num_triangles, const float* matrices3x4, uint32_t num_bones,
-    rt_triangle* out)
-{
-    if (!rest || !per_corner || !matrices3x4 || !out) return fail(ctx, "rt_debug_skin: NULL argument");
-    if (num_triangles == 0u) return fail(ctx, "rt_debug_skin: no triangles");
-    if (skin_table_refused(ctx, "rt_debug_skin", per_corner, num_triangles, num_bones) != RT_OK) return RT_ERROR;
-    if (!skin::matrices_finite(matrices3x4, num_bones)) return fail(ctx, "rt_debug_skin: a matrix entry is not finite");
-    if (!ctx) { skin::debug_host(rest, per_corner, num_triangles, matrices3x4, num_bones, out); return RT_OK; }
-    (void)hipSetDevice(ctx->device);
-    if (!skin::debug_device(ctx->stream, rest, per_corner, num_triangles, matrices3x4, num_bones, out))
-        return fail(ctx, "rt_debug_skin: the device path failed (allocation, copy or launch)");
-    return RT_OK;
-}
-
-// ---- morphed triangles: rt_scene_set_morph / rt_scene_morph / rt_scene_morph_skin / rt_debug_morph*, the bookkeeping around morph.hip's kernels (DESIGN.md
-// section 7q).  A morph IS a refit, as a pose and a skin are: the kernel writes the staging area rt_scene_set_morph allocated and refit_device() takes it
-// unchanged.  The morph's state is independent of the objects' and the skin's; the fused call reads the skin's influences and palette, never its rest pose.
-
-static int morph_table_refused(rt_ctx* ctx, const char* who, const rt_morph_delta* deltas, const uint32_t* target_offsets, uint32_t num_targets, uint32_t num_triangles)
-{
-    const std::string name(who);
-    if (num_targets == 0u) return fail(ctx, name + ": no targets");
-    if (num_targets > (uint32_t)morph::MAX_TARGETS) return fail(ctx, name + ": more than 65536 targets");
-    if (num_triangles > morph::MAX_TRIANGLES) return fail(ctx, name + ": more than 1431655765 triangles (a corner index is 32 bits)");
-    switch (morph::table_fault(deltas, target_offsets, num_targets, num_triangles))
-    {
-    case morph::TABLE_OK: return RT_OK;
-    case morph::FIRST_OFFSET: return fail(ctx, name + ": target_offsets[0] is not 0");
-    case morph::DECREASING_OFFSET: return fail(ctx, name + ": target_offsets decrease");
-    case morph::BAD_CORNER: return fail(ctx, name + ": a corner is not below 3 * num_triangles");
-    case morph::NOT_FINITE: return fail(ctx, name + ": a delta is not finite");
-    case morph::BAD_PAD: return fail(ctx, name + ": a delta's pad is not 0");
-    case morph::NO_MEMORY: return fail(ctx, name + ": no host memory to check the table");
-    default: return fail(ctx, name + ": a target moves the same corner twice");
-    }
-}
-
-int rt_scene_set_morph(rt_ctx* ctx, const rt_morph_delta* deltas, const uint32_t* target_offsets, uint32_t num_targets, uint32_t num_triangles)
-{
-    if (!ctx || !deltas || !target_offsets) return fail(ctx, "rt_scene_set_morph: NULL argument");
-    if (refit_refused(ctx, "rt_scene_set_morph", num_triangles, false) != RT_OK) return RT_ERROR;
-    if (morph_table_refused(ctx, "rt_scene_set_morph", deltas, target_offsets, num_targets, num_triangles) != RT_OK) return RT_ERROR;
-    (void)hipSetDevice(ctx->device);
-    Scene& s = ctx->scene;
-    std::vector<uint32_t> row;
-    std::vector<morph::Record> records;
-    if (!morph::transpose(deltas, target_offsets, num_targets, num_triangles, row, records)) return fail(ctx, "rt_scene_set_morph: no host memory for the rows");
-    morph::State* st = new morph::State();
-    if (!morph::arm(ctx->stream, *st, (const float4*)s.tris_sh, row, records, num_triangles, num_targets))
-    {
-        delete st;
-        return fail(ctx, "rt_scene_set_morph: the rest pose, the records and the staging area could not be allocated");
-    }
-    if (s.morph) { morph::release(*s.morph); delete s.morph; }
-    s.morph = st;
-    char line[300];
-    snprintf(line, sizeof(line), "morph targets: %u targets, %u deltas, %.1f MB kept: rest pose %u + staging area %u + row %u bytes per triangle, %u per delta, %u per target\n",
-        num_targets, st->n_deltas, (double)st->bytes / 1e6, (unsigned)morph::REST_BYTES, (unsigned)morph::STAGED_BYTES, (unsigned)morph::ROW_BYTES,
-        (unsigned)morph::RECORD_BYTES, (unsigned)morph::WEIGHT_BYTES);
-    keep_one_line_before_refit(s.tree_report, "morph targets: ", line);
-    return RT_OK;
-}
-
-// what rt_scene_morph and rt_scene_morph_skin refuse in common, before any launch
-static int morph_refused(rt_ctx* ctx, const char* who, const float* weights, uint32_t num_targets)
-{
-    const std::string name(who);
-    Scene& s = ctx->scene;
-    if (refit_refused(ctx, who, s.n_tris, false) != RT_OK) return RT_ERROR;
-    if (!s.morph) return fail(ctx, name + ": no morph (rt_scene_set_morph has not been called for this scene)");
-    if (num_targets != s.morph->n_targets) return fail(ctx, name + ": the target count differs from rt_scene_set_morph's");
-    if (!morph::weights_finite(weights, num_targets)) return fail(ctx, name + ": a weight is not finite");
-    return RT_OK;
-}
-
-int rt_scene_morph(rt_ctx* ctx, const float* weights, uint32_t num_targets)
-{
-    if (!ctx || !weights) return fail(ctx, "rt_scene_morph: NULL argument");
-    if (morph_refused(ctx, "rt_scene_morph", weights, num_targets) != RT_OK) return RT_ERROR;
-    Scene& s = ctx->scene;
-    (void)hipSetDevice(ctx->device);
-    if (!morph::run(ctx->stream, *s.morph, weights))
-    {
-        (void)hipGetLastError();
-        return fail(ctx, "rt_scene_morph: the morph kernel could not be launched");
-    }
-    return refit_device(ctx, s.morph->staged, "rt_scene_morph");
-}
-
-int rt_scene_morph_skin(rt_ctx* ctx, const float* weights, uint32_t num_targets, const float* matrices3x4, uint32_t num_bones)
-{
-    if (!ctx || !weights || !matrices3x4) return fail(ctx, "rt_scene_morph_skin: NULL argument");
-    if (morph_refused(ctx, "rt_scene_morph_skin", weights, num_targets) != RT_OK) return RT_ERROR;
-    Scene& s = ctx->scene;
-    if (!s.skin) return fail(ctx, "rt_scene_morph_skin: no skin (rt_scene_set_skin has not been called for this scene)");
-    if (num_bones != s.skin->n_bones) return fail(ctx, "rt_scene_morph_skin: the bone count differs from rt_scene_set_skin's");
-    if (!skin::matrices_finite(matrices3x4, num_bones)) return fail(ctx, "rt_scene_morph_skin: a matrix entry is not finite");
-    (void)hipSetDevice(ctx->device);
-    if (!skin::upload_palette(ctx->stream, *s.skin, matrices3x4) ||
-        !morph::run_skin(ctx->stream, *s.morph, weights, s.skin->influences, s.skin->palette, num_bones))
-    {
-        (void)hipGetLastError();
-        return fail(ctx, "rt_scene_morph_skin: the morph-and-skin kernel could not be launched");
-    }
-    return refit_device(ctx, s.morph->staged, "rt_scene_morph_skin");
-}
-
-static int debug_morph_refused(rt_ctx* ctx, const char* who, const rt_morph_delta* deltas, const uint32_t* target_offsets, uint32_t num_targets, uint32_t num_triangles,
-    const float* weights)
-{
-    const std::string name(who);
-    if (num_triangles == 0u) return fail(ctx, name + ": no triangles");
-    if (morph_table_refused(ctx, who, deltas, target_offsets, num_targets, num_triangles) != RT_OK) return RT_ERROR;
-    if (!morph::weights_finite(weights, num_targets)) return fail(ctx, name + ": a weight is not finite");
-    return RT_OK;
-}
-
-int rt_debug_morph(rt_ctx* ctx, const rt_triangle* rest, const rt_morph_delta* deltas, const uint32_t* target_offsets, uint32_t num_targets, uint32_t num_triangles,
-    const float* weights, rt_triangle* out)
-{
-    if (!rest || !deltas || !target_offsets || !weights || !out) return fail(ctx, "rt_debug_morph: NULL argument");
-    if (debug_morph_refused(ctx, "rt_debug_morph", deltas, target_offsets, num_targets, num_triangles, weights) != RT_OK) return RT_ERROR;
-    if (!ctx) return morph::debug_host(rest, deltas, target_offsets, num_targets, num_triangles, weights, out) ? RT_OK : fail(ctx, "rt_debug_morph: no host memory for the rows");
-    (void)hipSetDevice(ctx->device);
-    if (!morph::debug_device(ctx->stream, rest, deltas, target_offsets, num_targets, num_triangles, weights, out))
-        return fail(ctx, "rt_debug_morph: the device path failed (allocation, copy or launch)");
-    return RT_OK;
-}
-
-int rt_debug_morph_skin(rt_ctx* ctx, const rt_triangle* rest, const rt_morph_delta* deltas, const uint32_t* target_offsets, uint32_t num_targets, uint32_t num_triangles,
-    const float* weights, const rt_skin_influence* per_corner, const float* matrices3x4, uint32_t num_bones, rt_triangle* out)
-{
-    if (!rest || !deltas || !target_offsets || !weights || !per_corner || !matrices3x4 || !out) return fail(ctx, "rt_debug_morph_skin: NULL argument");
-    if (debug_morph_refused(ctx, "rt_debug_morph_skin", deltas, target_offsets, num_targets, num_triangles, weights) != RT_OK) return RT_ERROR;
-    if (skin_table_refused(ctx, "rt_debug_morph_skin", per_corner, num_triangles, num_bones) != RT_OK) return RT_ERROR;
-    if (!skin::matrices_finite(matrices3x4, num_bones)) return fail(ctx, "rt_debug_morph_skin: a matrix entry is not finite");
-    if (!ctx)
-    {
-        if (!morph::debug_host(rest, deltas, target_offsets, num_targets, num_triangles, weights, out)) return fail(ctx, "rt_debug_morph_skin: no host memory for the rows");
-        skin::debug_host(out, per_corner, num_triangles, matrices3x4, num_bones, out);           // (triangle by triangle, each read before it is written)
-        return RT_OK;
-    }
-    (void)hipSetDevice(ctx->device);
-    if (!morph::debug_skin_device(ctx->stream, rest, deltas, target_offsets, num_targets, num_triangles, weights, per_corner, matrices3x4, num_bones, out))
-        return fail(ctx, "rt_debug_morph_skin: the device path failed (allocation, copy or launch)");
-    return RT_OK;
 }
 
 // ---- one adaptation per process GROUP (round 6) ----------------------------------------------------------------------------------------

@@ -15,6 +15,9 @@
 //   * weights that sum to 0 collapse a corner to the origin with a zero normal (l = 0 is not normalised): finite, so accepted
 //   * a non-finite result is refused by the refit's own read-only validation with the scene untouched, as for a pose
 #pragma once
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>   // uint2, __uint_as_float: the decode at the end
+#endif
 #include "pose.h"
 
 namespace skin
@@ -63,4 +66,23 @@ POSE_HD void skin_vertex(const float* m0, const float* m1, const float* m2, cons
     const pose::Object o = make_object(B);
     pose::pose_vertex(o, v);
 }
+
+#if defined(__HIPCC__)
+// The device's decode of the influences, for the two kernels that skin (k_skin_triangles, k_morph_skin_triangles; shared by inclusion):
+// a triangle's 72 bytes are nine 8-byte words; one corner from its three: (bone 0 | bone 1 << 16, bone 2 | bone 3 << 16), (w0, w1), (w2, w3)
+__device__ inline void skin_corner(const float* palette, uint32_t n_bones, uint2 bones, uint2 w01, uint2 w23, rt_vertex& v)
+{
+    const uint32_t b0 = bones.x & 0xFFFFu, b1 = bones.x >> 16, b2 = bones.y & 0xFFFFu, b3 = bones.y >> 16;
+    if (b0 >= n_bones || b1 >= n_bones || b2 >= n_bones || b3 >= n_bones) return;       // (rt_scene_set_skin has checked every index)
+    const float w[4] = {__uint_as_float(w01.x), __uint_as_float(w01.y), __uint_as_float(w23.x), __uint_as_float(w23.y)};
+    skin_vertex(palette + b0 * 12u, palette + b1 * 12u, palette + b2 * 12u, palette + b3 * 12u, w, v);
+}
+
+__device__ inline void skin_triangle(const float* palette, uint32_t n_bones, const uint2* q, rt_triangle& t)
+{
+    skin_corner(palette, n_bones, q[0], q[1], q[2], t.v1);
+    skin_corner(palette, n_bones, q[3], q[4], q[5], t.v2);
+    skin_corner(palette, n_bones, q[6], q[7], q[8], t.v3);
+}
+#endif
 } // namespace skin

@@ -8,21 +8,21 @@
 #include <stddef.h>
 #include "rt_hip.h"          // rt_skin_influence
 #include "rt_types.h"
+#include "moved.h"           // moved::Stage
 
 namespace skin
 {
 // what rt_scene_set_skin keeps beside the scene, per triangle: the rest pose in rt_triangle layout (160 bytes), the three corners' influences (72) and the
 // staging area a skin is written to before the refit reads it (160)
-enum { REST_BYTES = 160, INFLUENCE_BYTES = 72, STAGED_BYTES = 160, BYTES_PER_TRIANGLE = REST_BYTES + INFLUENCE_BYTES + STAGED_BYTES };
+enum { REST_BYTES = moved::REST_BYTES, INFLUENCE_BYTES = 72, STAGED_BYTES = moved::STAGED_BYTES, BYTES_PER_TRIANGLE = REST_BYTES + INFLUENCE_BYTES + STAGED_BYTES };
 // a palette of up to LDS_BONES matrices is staged in LDS once per block (48 bytes each); a larger one is gathered through the vector L1 / L2
 enum { MAX_BONES = 65536, LDS_BONES = 128, MATRIX_BYTES = 48 };
 
 struct State
 {
-    uint32_t n_tris = 0, n_bones = 0;
-    rt_triangle* rest = nullptr;         // the pose rt_scene_set_skin saw
+    uint32_t n_bones = 0;
+    moved::Stage stage;                  // the pose rt_scene_set_skin saw; k_skin_triangles' output, refit_device's input
     rt_skin_influence* influences = nullptr;   // three per triangle
-    rt_triangle* staged = nullptr;       // k_skin_triangles' output, refit_device's input
     float* palette = nullptr;            // n_bones 3x4 matrices on the device ...
     float* host_palette = nullptr;       // ... and in pinned host memory, filled by every skin
     size_t bytes = 0;
@@ -32,7 +32,7 @@ struct State
 int influences_fault(const rt_skin_influence* per_corner, uint32_t nt, uint32_t n_bones);
 bool matrices_finite(const float* matrices3x4, uint32_t n_bones);
 
-// everything a skin needs, allocated here so that a skin allocates nothing; the rest pose by k_pose_rest's rule.  Waits for the stream.
+// everything a skin needs, allocated here so that a skin allocates nothing; the rest pose is moved::Stage::arm's.  Waits for the stream.
 // false: an allocation, a copy or the launch failed, and st is released
 bool arm(hipStream_t stream, State& st, const float4* tris_sh, const rt_skin_influence* per_corner, uint32_t nt, uint32_t n_bones);
 void release(State& st);

@@ -9,12 +9,12 @@ import numpy as np
 import pytest
 from raytracing_amd import capi, scenes as S, types as T
 from tests.test_refit import positions
-from tests.test_pose import same_bytes, decorated
+from tests.test_pose import IDENTITY, translation, rotation, same_bytes, decorated
 from tests.test_skin import random_case as random_skin_case
 from tests.test_morph import random_case, random_targets, np_morph
 from tests.test_motion_filter import moving_triangles, random_triangles, STEP
 from tests.test_gpu_temporal_filter import bits, moving_cameras
-from tests.test_gpu_pose import context, camera, frame, shoot, same_shot, sequence  # noqa: F401
+from tests.test_gpu_pose import context, camera, frame, shoot, same_shot, sequence, cornell_objects  # noqa: F401
 from tests.test_gpu_skin import skin_case
 
 pytestmark = pytest.mark.gpu
@@ -233,6 +233,49 @@ def test_morphs_are_absolute(golden_scenes, golden_radiance):
         same_shot(shoot(fa), uploaded, "zero weights give the upload's image")
     finally:
         a.close(); b.close()
+
+
+def test_every_producer_keeps_the_rest_pose_its_own_set_call_saw(golden_scenes, golden_radiance):
+    """the objects are set on the upload, the skin and the morph on the POSED scene: three rest poses in one context, each of them its producer's alone"""
+    sc, deltas, offsets, _, w = morph_case(golden_scenes)
+    _, infl, n_bones, bend = skin_case("cornell", golden_scenes, None)
+    tris = sc["triangles"]
+    assert len(tris) % 256 != 0                                   # the last block of every kernel here is a tail block
+    ids, n_objects = cornell_objects(tris)
+    M = np.stack([IDENTITY, translation(0.05, 0.02, -0.03), rotation((0, 1, 0), 0.02)])
+    cam = camera("cornell", golden_radiance)
+    a, p, u, d = context(), context(), context(), context()
+    try:
+        for c in (a, p, u, d):
+            c.upload_scene(sc)
+        fa, fp, fu, fd = frame(a, cam), frame(p, cam), frame(u, cam), frame(d, cam)
+        uploaded = shoot(fu)
+        p.set_objects(ids, n_objects)
+        p.pose_scene(M)
+        posed = shoot(fp)
+        assert posed["radiance"].tobytes() != uploaded["radiance"].tobytes()
+        a.set_objects(ids, n_objects)
+        a.pose_scene(M)
+        a.set_skin(infl, n_bones)                                 # their rest pose: the posed scene
+        a.set_morph(deltas, offsets, len(tris))
+        a.skin_scene(np.stack([IDENTITY] * n_bones))
+        same_shot(shoot(fa), posed, "the identity palette gives the scene rt_scene_set_skin saw")
+        a.pose_scene(np.stack([IDENTITY] * n_objects))
+        same_shot(shoot(fa), uploaded, "the identity pose gives the scene rt_scene_set_objects saw")
+        a.morph_scene(np.zeros(len(w), f32))
+        same_shot(shoot(fa), posed, "zero weights give the scene rt_scene_set_morph saw")
+        a.pose_scene(np.stack([IDENTITY] * n_objects))            # the scene is the upload again when the fused call starts from the morph's rest pose
+        a.morph_skin_scene(w, bend)
+        d.set_objects(ids, n_objects)
+        d.pose_scene(M)
+        d.set_skin(infl, n_bones)
+        d.set_morph(deltas, offsets, len(tris))
+        d.morph_skin_scene(w, bend)
+        got = shoot(fa)
+        same_shot(got, shoot(fd), "morph and skin after all that = morph and skin alone")
+        assert got["radiance"].tobytes() != posed["radiance"].tobytes()
+    finally:
+        a.close(); p.close(); u.close(); d.close()
 
 
 def test_refusals_leave_the_scene_and_an_earlier_morph_untouched(golden_scenes, golden_radiance):

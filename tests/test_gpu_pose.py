@@ -41,7 +41,7 @@ def context(refittable=True, motion=False, wide=True):
 
 # ---- 5. the kernel against the host restatement
 
-@pytest.mark.parametrize("n", [1, 63, 64, 65, 257, 1000])
+@pytest.mark.parametrize("n", [1, 2, 63, 64, 65, 255, 257, 1000])
 def test_kernel_equals_host_restatement_bit_for_bit(ctx, n):
     rng = np.random.default_rng(100 + n)
     for n_objects in sorted({1, 2, 7, n}):

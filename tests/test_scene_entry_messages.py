@@ -1,5 +1,5 @@
-"""The exact text of what the scene's own entry points (scene_upload.cpp: upload, refit, pose, the folds' export and import, the tree report and the
-rt_debug_* forms of the tree work) refuse without a context: every scene entry with its handle NULL, every debug form's NULL-argument refusals and the
+"""The exact text of what the scene's own entry points (scene_upload.cpp: upload, refit, the folds' export and import, the tree report and the
+rt_debug_* forms of the tree work; scene_moved.cpp: pose) refuse without a context: every scene entry with its handle NULL, every debug form's NULL-argument refusals and the
 mismatched arrays the host forms of rt_debug_refit, rt_debug_pose and rt_debug_count_box_passes turn down.  No device is needed: each call is refused
 before anything is launched, and what a refusal reads first is a few zeroed records."""
 import ctypes as C
