@@ -41,14 +41,18 @@ def hipcc():
     raise RuntimeError("hipcc not found")
 
 
-# librt_hip.so = several translation units (rt_hip.hip alone was 3 600 lines): the C-ABI with the hot path's kernels, the tree work on the device
-# (a code object of its own: the hot path's is not rebuilt or re-hashed when the builder changes), the spatial and temporal filters' kernels (likewise), and the host
-# side of the tree work.  The scene queries are split the same way twice over: each family's kernels and launch driver are a unit with a code object of its own, and
-# the C entry points of all eight are one host-only unit (scene_queries.cpp, on context.h), so neither a kernel nor an entry point's bookkeeping rebuilds the hot path.
-# The scene side -- upload, tree choice, the adaptation's worker, refit and the tree work's debug forms -- is a host-only unit too (scene_upload.cpp), and so are the entry points of pose, skin and morph (scene_moved.cpp).
-# So are the two things that work on a frame without tracing a sample: the filters' entry points (frame_filters.cpp) and the kernel-less readers (frame_readers.cpp), on frame.h.
+# librt_hip.so = several translation units.  Who owns what:
+#   rt_hip.hip holds every launch of the hot path's code object and nothing else: the units that schedule a frame's samples call it through frame_launch.h, and
+#   codeobj.code_object_sha256 identifies its code object, so no host bookkeeping rebuilds or re-hashes the hot path.
+#   Each other family of kernels -- the tree work on the device, the filters, the refit, pose / skin / morph, the eight scene queries -- is a unit with a code
+#   object of its own: its kernels and its launch driver.
+#   Everything else is host-only units (device=False: plain C++, no code object), each on the internal header that gives it what it needs and no more:
+#   on context.h the context and the buffers (context.cpp), the scene's upload, trees and adaptation worker (scene_upload.cpp), the entry points of pose, skin and
+#   morph (scene_moved.cpp) and of the queries (scene_queries.cpp); on frame.h + frame_launch.h what a frame is made of and how it is laid out (frame_layout.cpp)
+#   and when its samples run (frame_schedule.cpp); on frame.h alone the fold adaptation's render-thread side (frame_fold_hooks.cpp), the filters' entry points
+#   (frame_filters.cpp) and the kernel-less readers (frame_readers.cpp); and the host side of the tree work (wide_bvh.cpp).
 HIP_UNITS = [
-    ("rt_hip", "rt_hip.hip", True),            # C-ABI, frames, launch logic + kernels.h (the hot path)
+    ("rt_hip", "rt_hip.hip", True),            # every launch of kernels.h (the hot path), with its grid and arguments: namespace launch of frame_launch.h, the one-launch entries (rt_compute_aovs .. rt_debug_eval), the device groups
     ("device_fold", "device_fold.hip", True),  # fold_kernels.h + its host driver
     ("filters", "filters.hip", True),          # the guide pass, the spatial filter's a-trous passes, the temporal filter's stages (a code object of its own, like device_fold's)
     ("refit", "refit.hip", True),              # the refit of the scene's trees when its triangles move: kernels + their host driver + the host restatement (a code object of its own)
@@ -67,6 +71,10 @@ HIP_UNITS = [
     ("scene_queries", "scene_queries.cpp", False),   # the C entry points of the eight query families above (rt_scene_trace* .. rt_scene_separation*, their rt_debug_* forms) on context.h: an edit to a query's bookkeeping rebuilds no kernel (no device code)
     ("scene_upload", "scene_upload.cpp", False),     # rt_scene_upload and its stages, tree choice, FoldAdapt's worker, rt_scene_refit* / export_folds / import_folds / tree_report, the tree work's rt_debug_* forms, on context.h + fold_adapt.h (no device code)
     ("scene_moved", "scene_moved.cpp", False),       # the C entry points of pose, skin and morph (rt_scene_set_objects .. rt_scene_morph_skin, their rt_debug_* forms) on context.h; each ends in scene_upload.cpp's refit_device (no device code)
+    ("context", "context.cpp", False),               # the context and the buffers: context::fail and the thread's message, dev_fill / scene_array / query_check_status / quiesce, rt_ctx_* / rt_finish / rt_host_* / rt_upload_blue_noise_tables, every rt_buffer_*, on context.h + frame.h (no device code)
+    ("frame_layout", "frame_layout.cpp", False),     # what a frame is made of: rt_frame_create / destroy, the per-path buffers' layout (chunk_plan, alloc_path_buffers, ensure_slots), the pipes' streams, rt_set_option / rt_set_camera / rt_reset / rt_frame_reserve_samples, the three picks, on frame.h + frame_launch.h (no device code)
+    ("frame_schedule", "frame_schedule.cpp", False), # when a frame's samples run: the stage entries' record-or-run logic, the RT_OPT_FRAME_KERNEL = 255 measuring schedule, rt_advance_sample, rt_integrate's batches and compact-log fallback, the banks of RT_OPT_SAMPLES_AHEAD, on frame.h + frame_launch.h (no device code)
+    ("frame_fold_hooks", "frame_fold_hooks.cpp", False),   # the render thread's side of RT_CTX_OPT_ADAPTIVE_FOLD: probe frame, hand-over to the worker, adoption (frame::fold_adapt_hook), on frame.h + fold_adapt.h through the public rt_* entries (no device code)
     ("frame_filters", "frame_filters.cpp", False),   # the spatial and temporal filters' entry points on a frame and on caller arrays (rt_frame_filter* .. rt_frame_read_guide_motion, rt_debug_filter*, rt_debug_guide_motion) and the three states a filtered frame keeps, on frame.h + filters_host.h (no device code)
     ("frame_readers", "frame_readers.cpp", False),   # the frame's readers that launch no kernel: rt_frame_read_radiance / copy_radiance / get_profile and the rt_frame_debug_* readers, on frame.h (no device code)
     ("wide_bvh", "wide_bvh.cpp", False),     # build_wide_bvh, pair layout, the adaptation's host walks (no device code)

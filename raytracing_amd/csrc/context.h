@@ -1,10 +1,11 @@
-// context.h -- what a context is, for the translation units that implement entry points on it (rt_hip.hip, scene_upload.cpp, scene_moved.cpp, scene_queries.cpp): the
-// uploaded scene and its trees, the context and the buffer records behind the C-ABI's opaque handles, how an entry point fails, and the device copies an
-// upload makes.  Internal: never installed, never included by include/.  A feature unit gets the scene (ctx->scene: the kernels' view `d`, the trees, the
-// objects' table), the queries' scratch areas, the stream, the device and its properties.  It may ask for everything in flight to drain before it frees or
-// rewrites what a launch could still read (quiesce).  It cannot see a frame through this header: what a frame is, for the units that implement entry points
-// on one, is frame.h's (quiesce itself stays rt_hip.hip's, with ahead_discard, which it calls there) -- nor the fold adaptation's state, which is a name only
-// here (fold_adapt.h, for the two units that work on it).
+// context.h -- what a context is, for the translation units that implement entry points on it (context.cpp, scene_upload.cpp, scene_moved.cpp, scene_queries.cpp,
+// and through frame.h the frames' units and rt_hip.hip): the uploaded scene and its trees, the context and the buffer records behind the C-ABI's opaque handles,
+// how an entry point fails, and the device copies an upload makes.  Internal: never installed, never included by include/.  A feature unit gets the scene
+// (ctx->scene: the kernels' view `d`, the trees, the objects' table), the queries' scratch areas, the stream, the device and its properties.  It may ask for
+// everything in flight to drain before it frees or rewrites what a launch could still read (quiesce).  It cannot see a frame through this header: what a frame
+// is, for the units that implement entry points on one, is frame.h's (quiesce is context.cpp's, on frame.h's ahead_discard and sync_frame_streams) -- nor the
+// fold adaptation's state, which is a name only here (fold_adapt.h, for the units that work on it).  context.cpp owns the records' life, the thread's message,
+// the context's options and the buffers; the two launches a context needs of the hot path's code object (relayout_records, fill_gamma_lut) are rt_hip.hip's.
 #pragma once
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>
@@ -134,9 +135,11 @@ struct rt_buffer
 
 namespace context
 {
-// msg becomes the context's last error (no context: the calling thread's) and the call's result is RT_ERROR.  One definition, rt_hip.hip's, beside
+// msg becomes the context's last error (no context: the calling thread's) and the call's result is RT_ERROR.  One definition, context.cpp's, beside
 // rt_last_error and the thread's message.
 int fail(rt_ctx* ctx, const std::string& msg);
+// the calling thread's message (context.cpp); rt_group_last_error answers with it too (group_impl.h)
+extern thread_local std::string g_thread_error;
 
 #define HIPCHK(ctx, expr)                                                                         \
     do                                                                                            \
@@ -157,11 +160,11 @@ int scene_array(rt_ctx* ctx, void** field, const void* src, size_t bytes);
 int query_check_status(rt_ctx* ctx, const char* who);
 
 // Nothing in flight may still read what is about to be freed or rewritten: batches traced ahead are dropped (RT_OPT_SAMPLES_AHEAD), and every stream a frame
-// launches on -- side streams, pipes, banks -- has drained.  rt_hip.hip's, where the frames are.
+// launches on -- side streams, pipes, banks -- has drained.  context.cpp's, on what frame.h declares for it.
 int quiesce(rt_ctx* ctx);
 
 // Everything a scene holds on the device and beside it (its adaptation, refit, pose, skin and morph states) is freed and `s` is an empty scene again.  scene_upload.cpp's:
-// rt_scene_upload and an upload that ends early call it there, rt_ctx_destroy from rt_hip.hip.
+// rt_scene_upload and an upload that ends early call it there, rt_ctx_destroy from context.cpp.
 void free_scene(Scene& s);
 
 // The refit (scene_upload.cpp's, with rt_scene_refit*), for scene_moved.cpp's pose, skin and morph too.  refit_refused: why `who` cannot refit this scene now,

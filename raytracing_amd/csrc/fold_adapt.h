@@ -1,6 +1,6 @@
 // fold_adapt.h -- the state of RT_CTX_OPT_ADAPTIVE_FOLD (FoldAdapt; Scene::adapt points at one) for the two units that work on it: scene_upload.cpp arms it at
-// upload, owns its worker (crossing counts, re-fold, tree rotations, occluder-first slots, the upload of the adapted records) and drops it; rt_hip.hip's
-// render-thread side (fold_hooks_impl.h) probes, hands over to the worker and adopts.  Internal, like context.h -- which keeps the name only, so the
+// upload, owns its worker (crossing counts, re-fold, tree rotations, occluder-first slots, the upload of the adapted records) and drops it; the
+// render thread's side (frame_fold_hooks.cpp) probes, hands over to the worker and adopts.  Internal, like context.h -- which keeps the name only, so the
 // queries' unit sees no more than that.
 #pragma once
 #include <atomic>
@@ -79,7 +79,7 @@ struct FoldAdapt
     ~FoldAdapt();
 };
 
-// What rt_hip.hip calls on one; all of it is scene_upload.cpp's.
+// What the context's and the frames' units call on one; all of it is scene_upload.cpp's.
 void drop_fold_adapt(FoldAdapt* a);        // waits for its worker thread
 void fold_adapt_set_interval(FoldAdapt* a, uint32_t ms);
 void fold_adapt_set_wait(FoldAdapt* a, bool wait);

@@ -1,11 +1,14 @@
-// frame.h -- what a frame is, for the translation units that implement entry points on it (rt_hip.hip, frame_filters.cpp, frame_readers.cpp): the record
-// behind the C-ABI's opaque rt_frame with its pipes, its banks of samples traced ahead and its buffer lists, and the few functions of the frames' own file
-// that a filter or a reader calls before it touches a frame's memory.  Internal like context.h: never installed, never included by include/, plain C++ (no
-// device code: the records a frame hands to its launches are device_scene.h's).  A feature unit gets every field of a frame; it may have the stage API's
-// sample replayed into the radiance (flush_stage), a deferred sample run after all (deferred_materialize), the pipes joined and the frame's own streams
-// waited for (join_pipes, sync_frame_streams), and the guide pass's rays traced (trace_guides: the one launch of the hot path's code object a filter needs).
-// It cannot launch a stage, lay the per-path buffers out or reach the banks' schedule: those are rt_hip.hip's alone.  The filters' state on a frame is a name
-// only here (SfGuides, TfState, SfMotion: frame_filters.cpp), freed through free_filter_state.
+// frame.h -- what a frame is, for the translation units that implement entry points on it: the record behind the C-ABI's opaque rt_frame with its pipes, its
+// banks of samples traced ahead and its buffer lists, and the few functions of the frames' units that a filter, a reader or the context calls before it touches
+// a frame's memory.  Internal like context.h: never installed, never included by include/, plain C++ (no device code: the records a frame hands to its
+// launches are device_scene.h's).  Who owns what: frame_layout.cpp makes and destroys a frame, lays its per-path buffers out and takes its options;
+// frame_schedule.cpp decides when its samples run (the stage entries, rt_integrate, the banks); frame_fold_hooks.cpp is the render thread's side of the fold
+// adaptation; rt_hip.hip holds every launch of the hot path's code object (frame_launch.h: what the three call there and on each other).  A FEATURE unit
+// (frame_filters.cpp, frame_readers.cpp) includes this header alone.  It gets every field of a frame; it may have the stage API's sample replayed into the
+// radiance (flush_stage), a deferred sample run after all (deferred_materialize), the pipes joined and the frame's own streams waited for (join_pipes,
+// sync_frame_streams), and the guide pass's rays traced (trace_guides: the one launch of the hot path's code object a filter needs).  It cannot launch a
+// stage, lay the per-path buffers out or reach the banks' schedule: those are frame_launch.h's, which a feature unit does not include.  The filters' state on
+// a frame is a name only here (SfGuides, TfState, SfMotion: frame_filters.cpp), freed through free_filter_state.
 #pragma once
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>
@@ -111,7 +114,7 @@ struct AheadBank
     hipEvent_t done = nullptr;              // the batch's last launch (the bank's stream, after its side stream has been joined)
     hipEvent_t order = nullptr;             // what the bank's stream waits for before it starts another batch: the owner's last replay of the old one
 };
-// what a bank is made for: a change in any of the sixteen makes the banks over (ahead_key / ahead_configure, samples_ahead_impl.h)
+// what a bank is made for: a change in any of the sixteen makes the banks over (ahead_key / ahead_configure, frame_schedule.cpp)
 struct AheadKey
 {
     uint32_t followed[12] = {};             // the options of RT_AHEAD_FOLLOWED, in its order
@@ -260,7 +263,15 @@ struct rt_frame
 // the tile's pixels, at least 1: a rank may hold no row of a small image, and buffers, grids and chunks are sized for one pixel then
 static uint32_t tile_pixels(const rt_frame* f) { return f->n_local ? f->n_local : 1u; }
 
-// What a feature unit calls on the frames' file.  Each is defined in rt_hip.hip, among the functions it works with.
+// what every entry that works on a frame's scene begins with
+#define FRAME_PROLOGUE(f, name)                                                         \
+    if (!(f)) return fail(nullptr, name ": frame is NULL");                             \
+    rt_ctx* ctx = (f)->ctx;                                                             \
+    if (!ctx->scene.valid) return fail(ctx, name ": no scene uploaded");                \
+    (void)hipSetDevice(ctx->device)
+
+// What a feature unit, or the context, calls on the frames' units.  Each is defined among the functions it works with: flush_stage, deferred_materialize and
+// ahead_discard in frame_schedule.cpp, join_pipes and sync_frame_streams in frame_layout.cpp, fold_adapt_hook in frame_fold_hooks.cpp, trace_guides in rt_hip.hip.
 namespace frame
 {
 // the logs of the pipes that hold the stage API's sample replayed into the radiance (keep: the sample stays open; a deferred sample runs its recorded
@@ -272,8 +283,12 @@ int join_pipes(rt_frame* f);
 int sync_frame_streams(rt_frame* f);
 // RT_OPT_FRAME_KERNEL: the recorded stages of a deferred sample, run with the stage kernels after all (nothing deferred: nothing to do)
 int deferred_materialize(rt_frame* f);
+// RT_OPT_SAMPLES_AHEAD: whatever was traced ahead is dropped (reset, another camera, another option, a peek; context::quiesce before a scene changes)
+void ahead_discard(rt_frame* f);
+// RT_CTX_OPT_ADAPTIVE_FOLD on the render thread: probe, hand-over to the worker, adoption.  rt_generate_rays and rt_integrate call it before a frame's first stage.
+int fold_adapt_hook(rt_frame* f);
 // The guide pass's closest-hit trace (ensure_guides, frame_filters.cpp): the n rays o4 / d4, live count `count`, by the per-ray BVH2 kernel on the context's
-// stream into the filter's own `hits`, with its own `spill` area.  A launch of the hot path's code object, hence here; the caller reads hipGetLastError.
+// stream into the filter's own `hits`, with its own `spill` area.  A launch of the hot path's code object, hence rt_hip.hip's; the caller reads hipGetLastError.
 void trace_guides(rt_frame* f, const float4* o4, const float4* d4, float4* hits, uint2* spill, const uint32_t* count, size_t n);
 // frees the three filter states of a frame that is being destroyed (frame_filters.cpp, where their records are)
 void free_filter_state(rt_frame* f);

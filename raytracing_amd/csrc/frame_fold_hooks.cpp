@@ -1,8 +1,25 @@
-// fold_hooks_impl.h -- part of rt_hip.hip's translation unit (included inside its extern "C" block, before rt_integrate): the render-thread side of
-// RT_CTX_OPT_ADAPTIVE_FOLD -- the asynchronous probe frame, the hand-over to the worker, the adoption by pointer exchange, the trigger.  It reads rt_frame,
-// so it stays with the frames; FoldAdapt itself and what is called on it here -- fold_adapt_worker, fold_view_left, replace_report_line -- are fold_adapt.h's,
-// defined in scene_upload.cpp with the upload's side of the adaptation.
-#pragma once
+// frame_fold_hooks.cpp -- the render-thread side of RT_CTX_OPT_ADAPTIVE_FOLD: the asynchronous probe frame, the hand-over to the worker, the adoption by
+// pointer exchange, the trigger (frame::fold_adapt_hook, which rt_generate_rays and rt_integrate call before a frame's first stage).  Host code only, on
+// frame.h: it reads rt_frame and drives the probe frame through the public rt_* entries, nothing else of the frames' units.  FoldAdapt itself and what is
+// called on it here -- fold_adapt_worker, fold_view_left, replace_report_line -- are fold_adapt.h's, defined in scene_upload.cpp with the upload's side of
+// the adaptation.
+#include <hip/hip_runtime_api.h>
+#include <stdio.h>
+#include <stdint.h>
+#include <algorithm>
+#include <atomic>
+#include <chrono>
+#include <string>
+#include <thread>
+#include <utility>
+#include <vector>
+#include "rt_hip.h"
+#include "wide_bvh.h"        // truncated_walks_exchange, for the adaptation's report line (wide_bvh.cpp)
+#include "context.h"         // Scene, rt_ctx, fail
+#include "frame.h"           // rt_frame: the probe frame's queues and counters
+#include "fold_adapt.h"      // FoldAdapt
+using namespace rtw;
+using namespace context;
 
 // ---- RT_CTX_OPT_ADAPTIVE_FOLD: probe, worker hand-over, adoption (FoldAdapt) -------------------------------------------------
 // The probe: a frame of the same camera at 1/k of the resolution (about 32 K paths), one sample (several for tiny images), taken
@@ -150,7 +167,7 @@ static int fold_adopt(rt_ctx* ctx)
     return RT_OK;
 }
 
-static int fold_adapt_hook(rt_frame* f)
+int frame::fold_adapt_hook(rt_frame* f)
 {
     Scene& s = f->ctx->scene;
     FoldAdapt* a = s.adapt;

@@ -2,7 +2,7 @@
 // query.hip, bake.hip, nearest.hip, all_hits.hip, within.hip, region.hip, cross.hip and separation.hip (DESIGN.md sections 7h - 7o): rt_scene_trace*, rt_scene_bake*,
 // rt_scene_nearest*, rt_scene_trace_all*, rt_scene_within*, rt_scene_overlap*, rt_scene_select*, rt_scene_cross*, rt_scene_separation* and their rt_debug_* forms.  Host code only, on context.h:
 // a query reads the scene and writes the caller's arrays, it launches on the context's stream -- behind every refit, pose and upload, which end there --
-// and touches no frame.  (The three picks read a frame's camera and tile: they are rt_hip.hip's and call the entries here.)  The stack spill area, the
+// and touches no frame.  (The three picks read a frame's camera and tile: they are frame_layout.cpp's and call the entries here.)  The stack spill area, the
 // status word and the staging arrays of every family but the bakes are the ray queries' (ctx->query), so rt_scene_tree_report's "ray queries" line
 // counts them; the bakes have a scratch of their own (ctx->bake).
 #include <hip/hip_runtime_api.h>

@@ -3,7 +3,7 @@
 // ends), handed from one context of a group to another (rt_scene_export_folds, rt_scene_import_folds) and inspected (rt_scene_tree_report, the rt_debug_*
 // forms of the tree work).  Host code only, on context.h and fold_adapt.h: the tree work on the device goes through devfold::, refit:: and filt::, units of their own, and the three
 // things this file needs of the frames' unit are context.h's -- quiesce, relayout_records (the one place it would launch kernels of the hot path's code
-// object) and fail.  It touches no frame; the adaptation's render-thread side -- probe, hand-over, adoption -- is rt_hip.hip's (fold_hooks_impl.h).
+// object) and fail.  It touches no frame; the adaptation's render-thread side -- probe, hand-over, adoption -- is frame_fold_hooks.cpp's.
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -31,7 +31,7 @@ using namespace rtw;
 using namespace context;
 
 // ---- which tree a ray population walks, and the fold adaptation's worker ---------------------------------------------------------------------------
-// Everything is in the anonymous namespace but what fold_adapt.h declares for rt_hip.hip.
+// Everything is in the anonymous namespace but what fold_adapt.h declares for the context's and the frames' units.
 namespace
 {
 // (the host-side fold, the pair layout and the adaptation's host walks: wide_bvh.cpp; the fold on the device: device_fold.hip)

@@ -249,7 +249,7 @@ def test_the_layout_over_a_grid_of_options(point, ctx):
 
 
 # ---- the banks of RT_OPT_SAMPLES_AHEAD follow the frame's options --------------------------------------------------------------------------
-# every option of the class "followed by the banks" (raytracing_amd/csrc/samples_ahead_impl.h) with a value that is not the default
+# every option of the class "followed by the banks" (raytracing_amd/csrc/frame_schedule.cpp) with a value that is not the default
 FOLLOWED = {
     "max_bounces": (capi.OPT_MAX_BOUNCES, 2), "sampler": (capi.OPT_SAMPLER, 1), "white_furnace": (capi.OPT_WHITE_FURNACE, 1),
     "drop_last": (capi.OPT_DROP_LAST, 0), "overlap_shadow": (capi.OPT_OVERLAP_SHADOW, 0), "trace_variant": (capi.OPT_TRACE_VARIANT, 8),
