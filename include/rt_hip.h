@@ -363,6 +363,54 @@ int rt_debug_bake_rays(rt_ctx* ctx_or_null, const void* points, uint32_t n, uint
  * bake.h's order.  A point whose first ray has an all-zero direction is a skipped one. */
 int rt_debug_bake_reduce(const rt_ray* rays, const uint32_t* occluded, uint32_t n, uint32_t samples, rt_bake_result* out);
 
+/* ---- the UV atlas: which triangle every texel of a texture shows and where on it, and an occlusion bake into it (opt-in extension).
+ * A lightmap or AO map needs, per texel, the surface point that texel shows: the scene's triangles rasterised in UV space.  That runs on the device -- no
+ * tree is walked -- and is repeated for free after a pose, skin or morph.  raytracing_amd/csrc/atlas.h states the rule, in integers:
+ *   the atlas: width x height texels (1 .. 16384 each, width * height <= 2^26), texel (x, y) at index y * width + x, row 0 at v = 0; the texel's centre is
+ *     tested, in fixed point with 8 sub-texel bits.  No repeat or wrap: only the centres inside [0, 1) x [0, 1) exist.
+ *   a triangle's corners snap to X = rintf(u * 256 width), Y = rintf(v * 256 height); it is SKIPPED (triangles_skipped) when a component is not finite, a
+ *     snapped coordinate exceeds 2^24 in magnitude, or its snapped area is 0.  Every other triangle covers the centres inside it and those on the edges it owns
+ *     (atlas.h's rule): two triangles that share an edge give every centre on it to exactly one of them, whatever their winding; both windings rasterise.
+ *   rt_texel: count = the triangles that cover the centre (saturating at 65535), primitive_id = the lowest of them (BVH order, as everywhere in this ABI),
+ *     bc = that triangle's barycentrics at the centre as rt_hit's (the weights of corners 2 and 3: one exact binary64 divide each, rounded once to binary32),
+ *     flags = RT_TEXEL_COVERED.  Uncovered: RT_INVALID_ID and zeros.
+ *   gutter (0 .. 4 passes): each pass gives every texel without a record that of its first neighbour with one, in the order left, right, up (y - 1), down,
+ *     up-left, up-right, down-left, down-right, with flags = RT_TEXEL_GUTTER and count = 0, so a bilinear fetch at a chart's border reads no empty texel.
+ *   uv_or_null: six floats per triangle in BVH order (u1 v1 u2 v2 u3 v3), a second UV set -- the usual lightmap channel; NULL: the triangles' own texcoord.xy.
+ *   desc.object: only the triangles of that object of rt_scene_set_objects are rasterised (the others count in triangles_filtered and nowhere else);
+ *     RT_INVALID_ID: every triangle.
+ *   rt_atlas_stats: covered and overlapped (count > 1) texels before the gutter, the texels the gutter filled, and of the triangles those skipped, those
+ *     filtered, and those neither skipped nor filtered that cover no centre (triangles_without_texel: too small for this atlas -- a lightmapper's warning).
+ * The cover depends on the UVs alone: it stays valid across refit, pose, skin and morph.  Everything runs on the context's stream, after every upload, refit or
+ * pose before it, touches no frame and no rt_stats field, and keeps nothing between calls but scratch the context grows on demand (the bakes').
+ *   rt_scene_atlas: host arrays; returns when texels[width * height] (and *stats) are written.
+ *   rt_scene_atlas_buffer: rt_buffers of this context (uv: 24 bytes per triangle; texels: width * height records; stats: one rt_atlas_stats); only enqueues.
+ *   rt_scene_atlas_surfaces / _buffer: surfaces[i] = the rt_surface of (texels[i].primitive_id, texels[i].bc) on the scene's triangles AS POSED NOW, made as a
+ *     ray query makes it (query.h) with an all-zero direction and t = 0, so flags = hit, never back face; an uncovered record gives a miss record.  A
+ *     primitive_id that is neither RT_INVALID_ID nor below the scene's triangle count is refused by the host form and gives a miss record in the buffer form.
+ *     The records feed rt_scene_bake_buffer(RT_BAKE_FROM_SURFACES).
+ *   rt_scene_atlas_bake: the cover, its surfaces and rt_scene_bake(RT_BAKE_FROM_SURFACES) of them in one call, all on the device: out[i] of texel i is byte for
+ *     byte rt_scene_bake of rt_scene_atlas_surfaces' records with the same bake_desc (point index = texel index; the bake's chunking, which changes no result);
+ *     an uncovered texel is a skipped point (unoccluded = RT_INVALID_ID).  bake_desc->flags must be 0.  texels_or_null / stats_or_null: the cover itself.
+ *   rt_debug_atlas: the cover over caller triangles (primitive_id = the index).  ctx == NULL: the host restatement (atlas.h); otherwise the kernels on
+ *     uploaded copies.  The two agree byte for byte.
+ * Refused with nothing launched: a NULL context, desc, texels, surfaces or out; no scene; a size out of range; gutter > 4; desc.object set without
+ * rt_scene_set_objects (rt_debug_atlas: without object_of_triangle) or not below the object count; caller bits in bake_desc->flags, or a bake_desc that
+ * rt_scene_bake refuses; a buffer of another context or one that is too small. */
+#define RT_TEXEL_COVERED 1u
+#define RT_TEXEL_GUTTER  2u
+typedef struct rt_texel { float bc[2]; uint32_t primitive_id; uint16_t count; uint16_t flags; } rt_texel;   /* 16 bytes; count saturates at 65535; uncovered: RT_INVALID_ID, zeros */
+typedef struct rt_atlas_desc { uint32_t width, height, gutter, object; } rt_atlas_desc;                     /* object: RT_INVALID_ID = every triangle */
+typedef struct rt_atlas_stats { uint32_t covered, overlapped, gutter, triangles_skipped, triangles_without_texel, triangles_filtered; uint32_t reserved[2]; } rt_atlas_stats;
+int rt_scene_atlas(rt_ctx* ctx, const rt_atlas_desc* desc, const float* uv_or_null, rt_texel* texels, rt_atlas_stats* stats_or_null);
+int rt_scene_atlas_buffer(rt_ctx* ctx, const rt_atlas_desc* desc, rt_buffer* uv_or_null, rt_buffer* texels, rt_buffer* stats_or_null);
+int rt_scene_atlas_surfaces(rt_ctx* ctx, const rt_texel* texels, uint32_t n, rt_surface* surfaces);
+int rt_scene_atlas_surfaces_buffer(rt_ctx* ctx, rt_buffer* texels, uint32_t n, rt_buffer* surfaces);
+int rt_scene_atlas_bake(rt_ctx* ctx, const rt_atlas_desc* atlas_desc, const float* uv_or_null, const rt_bake_desc* bake_desc, rt_bake_result* out,
+                        rt_texel* texels_or_null, rt_atlas_stats* stats_or_null);
+int rt_debug_atlas(rt_ctx* ctx_or_null, const rt_triangle* triangles, uint32_t num_triangles, const uint32_t* object_of_triangle_or_null, const float* uv_or_null,
+                   const rt_atlas_desc* desc, rt_texel* texels, rt_atlas_stats* stats);
+
 /* ---- nearest surface point: which triangle is nearest to each of the CALLER's points, where on it, and how far (opt-in extension).
  * raytracing_amd/csrc/nearest.h states every step of the arithmetic: the distance to one triangle (Ericson's region test, the blend in rt_surface's operand
  * order, the clamp to the triangle's box, d2 = |p - q|^2) and the distance to a box that prunes the walk.
@@ -1191,6 +1239,7 @@ RT_STATIC_ASSERT(sizeof(rt_skin_influence) == 24, "rt_skin_influence");
 RT_STATIC_ASSERT(sizeof(rt_morph_delta) == 32, "rt_morph_delta");
 RT_STATIC_ASSERT(sizeof(rt_surface) == 64, "rt_surface");
 RT_STATIC_ASSERT(sizeof(rt_bake_result) == 16 && sizeof(rt_bake_desc) == 20, "rt_bake_result / rt_bake_desc");
+RT_STATIC_ASSERT(sizeof(rt_texel) == 16 && sizeof(rt_atlas_desc) == 16 && sizeof(rt_atlas_stats) == 32, "rt_texel / rt_atlas_desc / rt_atlas_stats");
 RT_STATIC_ASSERT(sizeof(rt_point) == 16 && sizeof(rt_nearest) == 32, "rt_point / rt_nearest");
 RT_STATIC_ASSERT(sizeof(rt_ray_hits) == 16, "rt_ray_hits");
 RT_STATIC_ASSERT(sizeof(rt_point_hits) == 16, "rt_point_hits");

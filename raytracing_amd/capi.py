@@ -116,6 +116,7 @@ EXPORTS = [
     "rt_frame_read_guide_motion", "rt_debug_guide_motion", "rt_debug_filter_temporal_motion",
     "rt_scene_trace", "rt_scene_trace_buffer", "rt_frame_pick", "rt_debug_query_surface",
     "rt_scene_bake", "rt_scene_bake_buffer", "rt_debug_bake_rays", "rt_debug_bake_reduce",
+    "rt_scene_atlas", "rt_scene_atlas_buffer", "rt_scene_atlas_surfaces", "rt_scene_atlas_surfaces_buffer", "rt_scene_atlas_bake", "rt_debug_atlas",
     "rt_scene_nearest", "rt_scene_nearest_buffer", "rt_debug_nearest", "rt_debug_nearest_walk",
     "rt_scene_trace_all", "rt_scene_trace_all_buffer", "rt_frame_pick_all", "rt_debug_trace_all",
     "rt_scene_within", "rt_scene_within_buffer", "rt_debug_within", "rt_debug_within_walk",
@@ -221,6 +222,10 @@ def load():
         "rt_scene_bake": (i32, [vp, vp, u32, C.POINTER(rt_bake_desc), vp]), "rt_scene_bake_buffer": (i32, [vp, vp, u32, C.POINTER(rt_bake_desc), vp]),
         "rt_debug_bake_rays": (i32, [vp, vp, u32, u32, C.POINTER(rt_bake_desc), vp]),
         "rt_debug_bake_reduce": (i32, [vp, vp, u32, u32, vp]),
+        "rt_scene_atlas": (i32, [vp, C.POINTER(rt_atlas_desc), vp, vp, vp]), "rt_scene_atlas_buffer": (i32, [vp, C.POINTER(rt_atlas_desc), vp, vp, vp]),
+        "rt_scene_atlas_surfaces": (i32, [vp, vp, u32, vp]), "rt_scene_atlas_surfaces_buffer": (i32, [vp, vp, u32, vp]),
+        "rt_scene_atlas_bake": (i32, [vp, C.POINTER(rt_atlas_desc), vp, C.POINTER(rt_bake_desc), vp, vp, vp]),
+        "rt_debug_atlas": (i32, [vp, vp, u32, vp, vp, C.POINTER(rt_atlas_desc), vp, vp]),
         "rt_scene_nearest": (i32, [vp, vp, u32, vp, vp]), "rt_scene_nearest_buffer": (i32, [vp, vp, u32, vp, vp]),
         "rt_debug_nearest": (i32, [vp, vp, u32, vp, u32, vp]),
         "rt_debug_nearest_walk": (i32, [vp, u32, vp, u32, i32, vp, u32, vp, vp]),
@@ -598,6 +603,63 @@ def debug_bake_reduce(rays, occluded, samples):
     if rc != 0:
         raise RtError(lib.rt_last_error(None).decode())
     return out
+
+
+TEXEL_COVERED, TEXEL_GUTTER = 1, 2
+ATLAS_MAX_SIDE, ATLAS_MAX_TEXELS, ATLAS_MAX_GUTTER = 16384, 1 << 26, 4
+
+
+class rt_atlas_desc(C.Structure):
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("gutter", C.c_uint32), ("object", C.c_uint32)]
+
+
+def atlas_desc(width, height, gutter=0, object=None):
+    """rt_atlas_desc; object None = every triangle"""
+    return rt_atlas_desc(int(width), int(height), int(gutter), INVALID_ID if object is None else int(object))
+
+
+def atlas_uv(uv, num_triangles):
+    """the one rule for a second UV set: float32[num_triangles, 6] = u1 v1 u2 v2 u3 v3 per triangle in BVH order (or [num_triangles, 3, 2]); None: the triangles' own"""
+    if uv is None:
+        return None
+    a = np.ascontiguousarray(uv, np.float32).reshape(-1)
+    if a.size != 6 * num_triangles:
+        raise RtError("uv must hold six floats per triangle (u1 v1 u2 v2 u3 v3)")
+    return a
+
+
+def _atlas_texels(d):
+    # (sized only for a description the library will accept: it refuses the others before it writes)
+    ok = 1 <= d.width <= ATLAS_MAX_SIDE and 1 <= d.height <= ATLAS_MAX_SIDE and d.width * d.height <= ATLAS_MAX_TEXELS
+    return np.zeros(d.width * d.height if ok else 1, T.texel)
+
+
+def debug_atlas(ctx, triangles, width, height, gutter=0, object=None, object_of_triangle=None, uv=None):
+    """rt_debug_atlas: (types.texel[height * width], types.atlas_stats record) -- the cover of a width x height atlas by caller triangles, primitive_id = the
+    index.  ctx None = the host restatement (csrc/atlas.h), else the kernels on ctx's GPU."""
+    lib = load()
+    tris = np.ascontiguousarray(triangles, T.triangle).reshape(-1)
+    ids = np.ascontiguousarray(object_of_triangle, np.uint32) if object_of_triangle is not None else None
+    if ids is not None and len(ids) != len(tris):
+        raise RtError("object_of_triangle must have one entry per triangle")
+    u = atlas_uv(uv, len(tris))
+    d = atlas_desc(width, height, gutter, object)
+    texels, stats = _atlas_texels(d), np.zeros(1, T.atlas_stats)
+    handle = ctx.handle if ctx is not None else None
+    rc = lib.rt_debug_atlas(handle, tris.ctypes.data if len(tris) else None, len(tris), ids.ctypes.data if ids is not None else None,
+                            u.ctypes.data if u is not None and u.size else None, C.byref(d), texels.ctypes.data, stats.ctypes.data)
+    if rc != 0:
+        raise RtError(lib.rt_last_error(handle).decode())
+    return texels, stats[0]
+
+
+def atlas_surfaces_host(triangles, texels, object_of_triangle=None):
+    """what rt_scene_atlas_surfaces gives for `texels` on `triangles`, on the host: rt_debug_query_surface(NULL) of the hits (bc, primitive_id, t = 0) met by
+    all-zero directions -- csrc/query.h's arithmetic; an uncovered record gives a miss record"""
+    tx = np.ascontiguousarray(texels, T.texel).reshape(-1)
+    hits = np.zeros(len(tx), T.hit)
+    hits["bc"]["x"], hits["bc"]["y"], hits["primitive_id"] = tx["bc"][:, 0], tx["bc"][:, 1], tx["primitive_id"]
+    return debug_query_surface(None, triangles, np.zeros(len(tx), T.ray), hits, object_of_triangle)
 
 
 NEAREST_FOUND, NEAREST_BACK_SIDE, NEAREST_FEATURE_SHIFT = 1, 2, 2
@@ -1365,6 +1427,46 @@ class Context:
         d = bake_desc(samples, seed, bias, radius, from_surfaces)
         h = lambda b: b.handle if b is not None else None
         _check(self.lib, self.handle, self.lib.rt_scene_bake_buffer(self.handle, h(points), n, C.byref(d), h(out)))
+
+    def atlas(self, width, height, gutter=0, object=None, uv=None):
+        """rt_scene_atlas: (types.texel[height * width], types.atlas_stats record) -- per texel of a width x height atlas the lowest triangle of the uploaded
+        scene whose UVs cover its centre, where on it (bc) and how many do (atlas_uv's rule for a second UV set).  Byte for byte debug_atlas's."""
+        d = atlas_desc(width, height, gutter, object)
+        u = atlas_uv(uv, self.num_triangles)
+        texels, stats = _atlas_texels(d), np.zeros(1, T.atlas_stats)
+        _check(self.lib, self.handle, self.lib.rt_scene_atlas(self.handle, C.byref(d), u.ctypes.data if u is not None and u.size else None, texels.ctypes.data, stats.ctypes.data))
+        return texels, stats[0]
+
+    def atlas_buffer(self, width, height, texels, gutter=0, object=None, uv=None, stats=None):
+        """rt_scene_atlas_buffer: the same over Buffers of this context (uv: 24 bytes per triangle or None; texels: width * height records; stats: one
+        types.atlas_stats or None).  Only enqueues: Buffer.read() or finish() waits."""
+        d = atlas_desc(width, height, gutter, object)
+        h = lambda b: b.handle if b is not None else None
+        _check(self.lib, self.handle, self.lib.rt_scene_atlas_buffer(self.handle, C.byref(d), h(uv), h(texels), h(stats)))
+
+    def atlas_surfaces(self, texels):
+        """rt_scene_atlas_surfaces: types.surface[n] of types.texel[n] on the scene's triangles as posed now (a miss record where a texel is uncovered)"""
+        tx = np.ascontiguousarray(texels, T.texel).reshape(-1)
+        out = np.zeros(len(tx), T.surface)
+        _check(self.lib, self.handle, self.lib.rt_scene_atlas_surfaces(self.handle, _p(tx), len(tx), _p(out)))
+        return out
+
+    def atlas_surfaces_buffer(self, texels, n, surfaces):
+        """rt_scene_atlas_surfaces_buffer: the same over Buffers of this context.  Only enqueues."""
+        h = lambda b: b.handle if b is not None else None
+        _check(self.lib, self.handle, self.lib.rt_scene_atlas_surfaces_buffer(self.handle, h(texels), n, h(surfaces)))
+
+    def bake_atlas(self, width, height, samples, seed=0, bias=BAKE_BIAS_DEFAULT, radius=BAKE_RADIUS_DEFAULT, gutter=0, object=None, uv=None, flags=0):
+        """rt_scene_atlas_bake: (types.bake_result[height * width], texels, stats) -- the cover, its surfaces and their occlusion bake in one call on the
+        device; an uncovered texel is a skipped point (unoccluded = 0xFFFFFFFF)"""
+        d = atlas_desc(width, height, gutter, object)
+        bd = bake_desc(samples, seed, bias, radius, flags=flags)
+        u = atlas_uv(uv, self.num_triangles)
+        texels, stats = _atlas_texels(d), np.zeros(1, T.atlas_stats)
+        out = np.zeros(len(texels), T.bake_result)
+        _check(self.lib, self.handle, self.lib.rt_scene_atlas_bake(self.handle, C.byref(d), u.ctypes.data if u is not None and u.size else None, C.byref(bd), out.ctypes.data,
+                                                                     texels.ctypes.data, stats.ctypes.data))
+        return out, texels, stats[0]
 
     def set_bake_chunk_points(self, points):
         """RT_CTX_OPT_BAKE_CHUNK_POINTS: bake() stages at most this many points at a time (0 = the default, 1 Mi); no result depends on it"""

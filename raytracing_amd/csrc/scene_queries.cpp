@@ -4,7 +4,8 @@
 // a query reads the scene and writes the caller's arrays, it launches on the context's stream -- behind every refit, pose and upload, which end there --
 // and touches no frame.  (The three picks read a frame's camera and tile: they are frame_layout.cpp's and call the entries here.)  The stack spill area, the
 // status word and the staging arrays of every family but the bakes are the ray queries' (ctx->query), so rt_scene_tree_report's "ray queries" line
-// counts them; the bakes have a scratch of their own (ctx->bake).
+// counts them; the bakes have a scratch of their own (ctx->bake).  The tree-less UV atlas (atlas.hip, section 7r: rt_scene_atlas*, rt_scene_atlas_surfaces*,
+// rt_scene_atlas_bake, rt_debug_atlas) has its entry points here too and works in the bakes' scratch.
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>
 #include <functional>
@@ -22,6 +23,8 @@
 #include "cross.h"
 #include "separation_host.h"
 #include "separation.h"
+#include "atlas_host.h"
+#include "atlas.h"
 #include "device_memory.h"
 using namespace context;
 
@@ -782,6 +785,132 @@ int rt_debug_separation_self(rt_ctx* ctx, const rt_triangle* triangles, uint32_t
     return host_or_device(ctx, "rt_debug_separation_self",
         [&] { separation::brute_host(triangles, num_triangles, nullptr, object_of_triangle, first, n, max_distance, options, out); },
         [&](hipStream_t st) { return separation::brute_device(st, triangles, num_triangles, nullptr, object_of_triangle, first, n, max_distance, options, out); });
+}
+
+// ---- the UV atlas: rt_scene_atlas / rt_scene_atlas_buffer / rt_scene_atlas_surfaces / rt_scene_atlas_surfaces_buffer / rt_scene_atlas_bake / rt_debug_atlas
+// (atlas.hip).  No tree is walked.  The work area and the host forms' arrays are the bakes' scratch (ctx->bake): [0] the UVs, then a
+// bake's surfaces, [1] a bake's results, [2] the cover's work area, [3] the texels ------------------------------------------------------------------------
+
+// everything the cover's forms refuse before anything is launched
+static int atlas_refused(rt_ctx* ctx, const char* who, const rt_atlas_desc* desc, std::initializer_list<Needed> outputs)
+{
+    const std::string name(who);
+    if (opening_refused(ctx, name, {{"desc", desc != nullptr}}, {}) != RT_OK) return RT_ERROR;
+    for (const Needed& a : outputs) if (!a.given) return fail(ctx, name + ": " + a.what + " is NULL");
+    if (const char* why = atlas_desc_refusal(*desc)) return fail(ctx, name + ": " + why);
+    if (desc->object != RT_INVALID_ID)
+    {
+        if (!ctx->scene.pose) return fail(ctx, name + ": desc.object needs rt_scene_set_objects");
+        if (desc->object >= ctx->scene.pose->n_objects) return fail(ctx, name + ": desc.object is not below the object count");
+    }
+    return RT_OK;
+}
+
+static int atlas_launch(rt_ctx* ctx, const char* who, void* d_work, const rt_atlas_desc& desc, const float* d_uv, rt_texel* d_texels)
+{
+    const Scene& s = ctx->scene;
+    return launch_result(ctx, who, atlas::launch(ctx->stream, d_work, desc, d_uv, s.d.tris_sh, s.n_tris, s.pose ? s.pose->ids : nullptr, d_texels),
+        ": the cover could not be launched (a launch failed)");
+}
+
+// the host forms' cover: afterwards, in stream order, the texels are the bakes' stage [3] and the statistics the head of stage [2]
+static int atlas_on_scratch(rt_ctx* ctx, const char* who, const rt_atlas_desc& desc, const float* uv)
+{
+    query::Scratch& b = ctx->bake;
+    const size_t n = (size_t)desc.width * desc.height, uv_bytes = (size_t)ctx->scene.n_tris * 24u;
+    if ((uv && !query::reserve(ctx->stream, b, 0, uv_bytes)) || !query::reserve(ctx->stream, b, 2, atlas::work_bytes(desc)) || !query::reserve(ctx->stream, b, 3, n * sizeof(rt_texel)))
+        return fail(ctx, std::string(who) + ": out of device memory for the atlas");
+    if (uv && uv_bytes) HIPCHK(ctx, hipMemcpyAsync(b.stage[0], uv, uv_bytes, hipMemcpyHostToDevice, ctx->stream));
+    return atlas_launch(ctx, who, b.stage[2], desc, uv ? (const float*)b.stage[0] : nullptr, (rt_texel*)b.stage[3]);
+}
+
+int rt_scene_atlas(rt_ctx* ctx, const rt_atlas_desc* desc, const float* uv, rt_texel* texels, rt_atlas_stats* stats)
+{
+    if (atlas_refused(ctx, "rt_scene_atlas", desc, {{"texels", texels != nullptr}}) != RT_OK) return RT_ERROR;
+    (void)hipSetDevice(ctx->device);
+    if (atlas_on_scratch(ctx, "rt_scene_atlas", *desc, uv) != RT_OK) return RT_ERROR;
+    HIPCHK(ctx, hipMemcpyAsync(texels, ctx->bake.stage[3], (size_t)desc->width * desc->height * sizeof(rt_texel), hipMemcpyDeviceToHost, ctx->stream));
+    if (stats) HIPCHK(ctx, hipMemcpyAsync(stats, ctx->bake.stage[2], sizeof(rt_atlas_stats), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return RT_OK;
+}
+
+int rt_scene_atlas_buffer(rt_ctx* ctx, const rt_atlas_desc* desc, rt_buffer* uv, rt_buffer* texels, rt_buffer* stats)
+{
+    if (atlas_refused(ctx, "rt_scene_atlas_buffer", desc, {{"texels", texels != nullptr}}) != RT_OK) return RT_ERROR;
+    if (buffers_refused(ctx, "rt_scene_atlas_buffer", {{uv, 24u, "uv"}}, ctx->scene.n_tris) != RT_OK) return RT_ERROR;
+    if (buffers_refused(ctx, "rt_scene_atlas_buffer", {{texels, sizeof(rt_texel), "texels"}}, desc->width * desc->height) != RT_OK) return RT_ERROR;
+    if (buffers_refused(ctx, "rt_scene_atlas_buffer", {{stats, sizeof(rt_atlas_stats), "stats"}}, 1u) != RT_OK) return RT_ERROR;
+    (void)hipSetDevice(ctx->device);
+    if (!query::reserve(ctx->stream, ctx->bake, 2, atlas::work_bytes(*desc))) return fail(ctx, "rt_scene_atlas_buffer: out of device memory for the atlas");
+    if (atlas_launch(ctx, "rt_scene_atlas_buffer", ctx->bake.stage[2], *desc, uv ? (const float*)uv->ptr : nullptr, (rt_texel*)texels->ptr) != RT_OK) return RT_ERROR;
+    if (stats) HIPCHK(ctx, hipMemcpyAsync(stats->ptr, ctx->bake.stage[2], sizeof(rt_atlas_stats), hipMemcpyDeviceToDevice, ctx->stream));
+    return RT_OK;
+}
+
+static int atlas_surfaces_launch(rt_ctx* ctx, const char* who, const rt_texel* d_texels, uint32_t n, rt_surface* d_surfaces)
+{
+    const Scene& s = ctx->scene;
+    return launch_result(ctx, who, atlas::launch_surfaces(ctx->stream, s.d.tris_sh, s.n_tris, s.pose ? s.pose->ids : nullptr, d_texels, n, d_surfaces),
+        ": the surfaces could not be launched (the launch failed)");
+}
+
+int rt_scene_atlas_surfaces(rt_ctx* ctx, const rt_texel* texels, uint32_t n, rt_surface* surfaces)
+{
+    if (ctx && n == 0u) return RT_OK;
+    if (opening_refused(ctx, "rt_scene_atlas_surfaces", {{"texels", texels != nullptr}, {"surfaces", surfaces != nullptr}}, {}) != RT_OK) return RT_ERROR;
+    for (uint32_t i = 0; i < n; ++i)
+        if (texels[i].primitive_id != RT_INVALID_ID && texels[i].primitive_id >= ctx->scene.n_tris)
+            return fail(ctx, "rt_scene_atlas_surfaces: a record's primitive_id is not below the scene's triangle count");
+    (void)hipSetDevice(ctx->device);
+    query::Scratch& q = ctx->query;
+    // the ray queries' staging arrays: [0] the texels, [3] the surfaces
+    return staged_call(ctx, "rt_scene_atlas_surfaces", q, {{(void*)texels, sizeof(rt_texel), 0, true}, {surfaces, sizeof(rt_surface), 3, false}}, n, (uint32_t)query::CHUNK_RAYS,
+        [&](uint32_t, uint32_t m) { return atlas_surfaces_launch(ctx, "rt_scene_atlas_surfaces", (const rt_texel*)q.stage[0], m, (rt_surface*)q.stage[3]); });
+}
+
+int rt_scene_atlas_surfaces_buffer(rt_ctx* ctx, rt_buffer* texels, uint32_t n, rt_buffer* surfaces)
+{
+    if (ctx && n == 0u) return RT_OK;
+    if (opening_refused(ctx, "rt_scene_atlas_surfaces_buffer", {{"texels", texels != nullptr}, {"surfaces", surfaces != nullptr}}, {}) != RT_OK) return RT_ERROR;
+    if (buffers_refused(ctx, "rt_scene_atlas_surfaces_buffer", {{texels, sizeof(rt_texel), "texels"}, {surfaces, sizeof(rt_surface), "surfaces"}}, n) != RT_OK) return RT_ERROR;
+    (void)hipSetDevice(ctx->device);
+    return atlas_surfaces_launch(ctx, "rt_scene_atlas_surfaces_buffer", (const rt_texel*)texels->ptr, n, (rt_surface*)surfaces->ptr);
+}
+
+int rt_scene_atlas_bake(rt_ctx* ctx, const rt_atlas_desc* atlas_desc, const float* uv, const rt_bake_desc* bake_desc, rt_bake_result* out, rt_texel* texels,
+    rt_atlas_stats* stats)
+{
+    static const char who[] = "rt_scene_atlas_bake";
+    if (atlas_refused(ctx, who, atlas_desc, {{"bake_desc", bake_desc != nullptr}, {"out", out != nullptr}}) != RT_OK) return RT_ERROR;
+    if (bake_desc->flags != 0u) return fail(ctx, std::string(who) + ": bake_desc->flags must be 0 (the records are the atlas's own surfaces)");
+    rt_bake_desc bd = *bake_desc;
+    bd.flags = RT_BAKE_FROM_SURFACES;
+    if (const char* why = bake::desc_refusal(bd)) return fail(ctx, std::string(who) + ": " + why);
+    (void)hipSetDevice(ctx->device);
+    if (atlas_on_scratch(ctx, who, *atlas_desc, uv) != RT_OK) return RT_ERROR;
+    query::Scratch& b = ctx->bake;
+    const uint32_t n = atlas_desc->width * atlas_desc->height;
+    if (texels) HIPCHK(ctx, hipMemcpyAsync(texels, b.stage[3], (size_t)n * sizeof(rt_texel), hipMemcpyDeviceToHost, ctx->stream));
+    if (stats) HIPCHK(ctx, hipMemcpyAsync(stats, b.stage[2], sizeof(rt_atlas_stats), hipMemcpyDeviceToHost, ctx->stream));
+    // the bake's chunks: a chunk's surfaces are made in stage [0] from the resident texels (the UVs there have been read: a stage is re-allocated only after
+    // the stream has been waited for), baked into stage [1] with the chunk's first index, and only the results come down
+    return staged_call(ctx, who, b, {{out, sizeof(rt_bake_result), 1, false}}, n, ctx->bake_chunk_points, [&](uint32_t first, uint32_t m)
+        {
+            if (!query::reserve(ctx->stream, b, 0, (size_t)m * sizeof(rt_surface))) return fail(ctx, std::string(who) + ": out of device memory for the staging arrays");
+            if (atlas_surfaces_launch(ctx, who, (const rt_texel*)b.stage[3] + first, m, (rt_surface*)b.stage[0]) != RT_OK) return (int)RT_ERROR;
+            return bake_launch(ctx, who, b.stage[0], m, first, bd, (rt_bake_result*)b.stage[1]);
+        });
+}
+
+int rt_debug_atlas(rt_ctx* ctx, const rt_triangle* triangles, uint32_t num_triangles, const uint32_t* object_of_triangle, const float* uv, const rt_atlas_desc* desc,
+    rt_texel* texels, rt_atlas_stats* stats)
+{
+    if (!desc || !texels || (!triangles && !uv && num_triangles > 0u)) return fail(ctx, "rt_debug_atlas: NULL argument");
+    if (const char* why = atlas_desc_refusal(*desc)) return fail(ctx, std::string("rt_debug_atlas: ") + why);
+    if (desc->object != RT_INVALID_ID && !object_of_triangle && num_triangles > 0u) return fail(ctx, "rt_debug_atlas: desc.object needs object_of_triangle");
+    return host_or_device(ctx, "rt_debug_atlas", [&] { atlas::cover_host(triangles, num_triangles, object_of_triangle, uv, *desc, texels, stats); },
+        [&](hipStream_t st) { return atlas::cover_device(st, triangles, num_triangles, object_of_triangle, uv, *desc, texels, stats); });
 }
 
 } // extern "C"

@@ -26,7 +26,7 @@ EXPORTS = [
     "rth_render_upload_gpu_data", "rth_render_setup_seconds", "rth_render_create_with_options",
     "rth_render_set_refittable", "rth_render_refit", "rth_render_set_refit_motion",
     "rth_render_set_objects", "rth_render_pose", "rth_render_pick", "rth_render_integrator_pick", "rth_render_trace",
-    "rth_render_bake", "rth_render_occlusion_image", "rth_render_nearest", "rth_render_within", "rth_render_overlap", "rth_render_cross", "rth_render_self_cross", "rth_render_separation", "rth_render_clearance", "rth_render_select", "rth_render_pick_rect", "rth_render_integrator_pick_rect", "rth_render_trace_all", "rth_render_pick_all",
+    "rth_render_bake", "rth_render_occlusion_image", "rth_render_atlas", "rth_render_occlusion_atlas", "rth_render_nearest", "rth_render_within", "rth_render_overlap", "rth_render_cross", "rth_render_self_cross", "rth_render_separation", "rth_render_clearance", "rth_render_select", "rth_render_pick_rect", "rth_render_integrator_pick_rect", "rth_render_trace_all", "rth_render_pick_all",
     "rth_scene_set_triangle_objects", "rth_scene_num_objects", "rth_scene_object_name", "rth_scene_num_triangle_objects", "rth_scene_triangle_objects",
     "rth_render_set_skin", "rth_render_skin", "rth_scene_set_triangle_skin", "rth_scene_num_triangle_skin", "rth_scene_triangle_skin",
     "rth_render_set_morph", "rth_render_morph", "rth_render_morph_skin",
@@ -81,6 +81,7 @@ def load():
         "rth_scene_set_triangle_skin": (i32, [vp, vp, u32]), "rth_scene_num_triangle_skin": (u32, [vp]), "rth_scene_triangle_skin": (vp, [vp]),
         "rth_render_pick": (i32, [vp, u32, u32, vp, vp, vp]), "rth_render_integrator_pick": (i32, [vp, u32, u32, vp, vp, vp]), "rth_render_trace": (i32, [vp, vp, u32, i32, vp, vp, vp]),
         "rth_render_bake": (i32, [vp, vp, u32, vp, vp]), "rth_render_occlusion_image": (i32, [vp, vp, vp]),
+        "rth_render_atlas": (i32, [vp, vp, vp, vp, vp]), "rth_render_occlusion_atlas": (i32, [vp, vp, vp, vp, vp, vp]),
         "rth_render_nearest": (i32, [vp, vp, u32, vp, vp]),
         "rth_render_within": (i32, [vp, vp, u32, u32, u32, vp, vp, vp]),
         "rth_render_overlap": (i32, [vp, vp, u32, u32, vp, vp]),
@@ -535,6 +536,27 @@ class Render:
         out = np.zeros((self.height, self.width), np.float32)
         self._c(self.lib.rth_render_occlusion_image(self.handle, C.addressof(d), out.ctypes.data))
         return out
+
+    def atlas(self, width, height, gutter=0, object=None, uv=None):
+        """The cover of a width x height UV atlas by the scene's triangles (HIPPathTraceIntegrator::AtlasCover): (types.texel[height * width],
+        types.atlas_stats record); uv: capi.atlas_uv's second UV set, None = the triangles' own texture coordinates"""
+        from . import capi
+        d = capi.atlas_desc(width, height, gutter, object)
+        u = None if uv is None else np.ascontiguousarray(uv, np.float32).reshape(-1)
+        texels, stats = capi._atlas_texels(d), np.zeros(1, T.atlas_stats)
+        self._c(self.lib.rth_render_atlas(self.handle, C.addressof(d), u.ctypes.data if u is not None and u.size else None, texels.ctypes.data, stats.ctypes.data))
+        return texels, stats[0]
+
+    def occlusion_atlas(self, width, height, samples, radius, bias=1e-3, seed=0, gutter=0, object=None, uv=None):
+        """Ambient occlusion baked into a UV atlas on the device (Render::OcclusionAtlas): (float32[height, width] = unoccluded / samples of the surface point
+        each texel shows, NaN where no triangle covers it, types.atlas_stats record)"""
+        from . import capi
+        d, bd = capi.atlas_desc(width, height, gutter, object), capi.bake_desc(samples, seed, bias, radius)
+        u = None if uv is None else np.ascontiguousarray(uv, np.float32).reshape(-1)
+        out, stats = np.zeros(len(capi._atlas_texels(d)), np.float32), np.zeros(1, T.atlas_stats)
+        self._c(self.lib.rth_render_occlusion_atlas(self.handle, C.addressof(d), u.ctypes.data if u is not None and u.size else None, C.addressof(bd), out.ctypes.data,
+                                                    stats.ctypes.data))
+        return out.reshape(height, width), stats[0]
 
     def _surface_dict(self, surf, names, objects):
         """a types.surface record as pick() reports it: its fields, and `object_name` when the scene was loaded with objects"""

@@ -367,6 +367,22 @@ void HIPPathTraceIntegrator::OcclusionImageThrough(Camera const& camera, rt_bake
     for (std::size_t i = 0; i < n; ++i) out[i] = results[i].unoccluded == RT_INVALID_ID ? 1.0f : (float)results[i].unoccluded / (float)desc.samples;
 }
 
+void HIPPathTraceIntegrator::AtlasCover(rt_atlas_desc const& desc, float const* uv, rt_texel* texels, rt_atlas_stats* stats)
+{
+    Check(rt_scene_atlas(context_.Get(), &desc, uv, texels, stats));
+}
+
+void HIPPathTraceIntegrator::AtlasSurfaces(rt_texel const* texels, std::size_t count, rt_surface* surfaces)
+{
+    if (count > 0xFFFFFFFFull) throw HIPException("HIPPathTraceIntegrator::AtlasSurfaces: more than 2^32 - 1 records in one call");
+    Check(rt_scene_atlas_surfaces(context_.Get(), texels, (uint32_t)count, surfaces));
+}
+
+void HIPPathTraceIntegrator::BakeAtlas(rt_atlas_desc const& atlas, float const* uv, rt_bake_desc const& desc, rt_bake_result* out, rt_texel* texels, rt_atlas_stats* stats)
+{
+    Check(rt_scene_atlas_bake(context_.Get(), &atlas, uv, &desc, out, texels, stats));
+}
+
 void HIPPathTraceIntegrator::SetCameraData(Camera const& camera)
 {
     prev_camera_ = camera_;

@@ -131,6 +131,13 @@ public:
     // library's message on a refusal; neither requests a reset or touches the frame.
     void BakeOcclusion(void const* points, std::size_t count, rt_bake_desc const& desc, rt_bake_result* out);
     void OcclusionImageThrough(Camera const& camera, rt_bake_desc desc, float* out);
+    // The UV atlas (rt_scene_atlas).  AtlasCover: per texel of desc's atlas the lowest triangle whose UVs cover its centre, where on it
+    // and how many do (uv: six floats per triangle, a second UV set, or nullptr for the triangles' own; stats may be nullptr).  AtlasSurfaces: the rt_surface of
+    // each record on the triangles as posed now.  BakeAtlas: the cover, its surfaces and their occlusion bake in one call on the device (desc.flags must be 0;
+    // texels and stats may be nullptr); an uncovered texel's result is a skipped point's.
+    void AtlasCover(rt_atlas_desc const& desc, float const* uv, rt_texel* texels, rt_atlas_stats* stats);
+    void AtlasSurfaces(rt_texel const* texels, std::size_t count, rt_surface* surfaces);
+    void BakeAtlas(rt_atlas_desc const& atlas, float const* uv, rt_bake_desc const& desc, rt_bake_result* out, rt_texel* texels, rt_atlas_stats* stats);
     // Nearest surface points (rt_scene_nearest): for each of the caller's points the nearest triangle of the scene as it is posed now, where
     // on it and how far, optionally with the rt_surface there; a count of 2^32 or more is refused.  Throws HIPException with the library's message on a
     // refusal; requests no reset and does not touch the frame.

@@ -303,6 +303,14 @@ int rth_render_occlusion_image(void* r, const rt_bake_desc* desc, float* out)
 {
     return guard([&]() { if (!desc) throw rt::HIPException("rth_render_occlusion_image: desc is NULL"); ((rt::Render*)r)->OcclusionImage(*desc, out); return 0; }, 1);
 }
+int rth_render_atlas(void* r, const rt_atlas_desc* desc, const float* uv, rt_texel* texels, rt_atlas_stats* stats)
+{
+    return guard([&]() { if (!desc) throw rt::HIPException("rth_render_atlas: desc is NULL"); ((rt::Render*)r)->AtlasCover(*desc, uv, texels, stats); return 0; }, 1);
+}
+int rth_render_occlusion_atlas(void* r, const rt_atlas_desc* atlas, const float* uv, const rt_bake_desc* desc, float* out, rt_atlas_stats* stats)
+{
+    return guard([&]() { if (!atlas || !desc) throw rt::HIPException("rth_render_occlusion_atlas: desc is NULL"); ((rt::Render*)r)->OcclusionAtlas(*atlas, uv, *desc, out, stats); return 0; }, 1);
+}
 int rth_render_nearest(void* r, const rt_point* points, uint32_t n, rt_nearest* out, rt_surface* surfaces)
 {
     return guard([&]() { ((rt::Render*)r)->Nearest(points, n, out, surfaces); return 0; }, 1);

@@ -46,6 +46,9 @@ int main(int argc, char** argv)
         bool nearest_signed = false;            // --signed 1: --nearest also prints whether the point is inside (exits outnumber entries along (0.36, 0.48, 0.8))
         std::string ao_out;                     // --ao out.pfm: after the scene is uploaded and posed, write the ambient occlusion image of the camera (grey, RGB equal)
         rt_bake_desc ao = {64u, 0u, 0u, 1e-3f, 1.0f};   // --ao_samples n --ao_radius r --ao_bias b
+        std::string ao_atlas_out;               // --ao_atlas out.pfm: after the scene is uploaded and posed, bake the ambient occlusion into a UV atlas (grey, NaN where uncovered)
+        rt_atlas_desc atlas = {0u, 0u, 0u, RT_INVALID_ID};   // --atlas_size w,h --atlas_gutter n
+        bool atlas_synthetic = false;           // --atlas_uv synthetic: a crack-free grid of two triangles per cell instead of the triangles' own UVs (scenes.synthetic_atlas)
         struct WithinAt { rt_point point; std::uint32_t k; };
         std::vector<WithinAt> within_points;    // --within x,y,z,r[,k] (repeatable): after the scene is uploaded and posed, print the triangles within r (the k nearest only)
         struct OverlapAt { float lo[3], hi[3]; std::uint32_t k; };
@@ -232,6 +235,10 @@ int main(int argc, char** argv)
                 scene_options |= rt::Scene::kObjects;
             }
             else if (!strcmp(argv[i], "--ao")) ao_out = next();
+            else if (!strcmp(argv[i], "--ao_atlas")) ao_atlas_out = next();
+            else if (!strcmp(argv[i], "--atlas_size")) { if (sscanf(next(), "%u,%u", &atlas.width, &atlas.height) != 2) { std::cerr << "--atlas_size w,h\n"; return 2; } }
+            else if (!strcmp(argv[i], "--atlas_gutter")) atlas.gutter = (unsigned)atoi(next());
+            else if (!strcmp(argv[i], "--atlas_uv")) atlas_synthetic = !strcmp(next(), "synthetic");
             else if (!strcmp(argv[i], "--ao_samples")) ao.samples = (unsigned)atoi(next());
             else if (!strcmp(argv[i], "--ao_radius")) ao.radius = (float)atof(next());
             else if (!strcmp(argv[i], "--ao_bias")) ao.bias = (float)atof(next());
@@ -259,6 +266,7 @@ int main(int argc, char** argv)
                              "  (rt_scene_pose: the scene is uploaded refittable, and with --temporal_filter the history follows the move); one GPU only\n"
                              "  --pick x,y (repeatable) prints what lies under the centre of that pixel once the scene is uploaded and posed: primitive, t, position,\n"
                              "  normals, texture coordinates, material and object (index and name); one GPU only\n"
+                             "  --ao_atlas out.pfm --atlas_size w,h [--atlas_gutter n] [--atlas_uv own|synthetic] bakes the ambient occlusion into a UV atlas (--ao_samples / --ao_radius; NaN where uncovered)\n"
                              "  --ao out.pfm --ao_samples n --ao_radius r [--ao_bias b] writes the exact ambient occlusion image of the camera once the scene is uploaded\n"
                              "  and posed: per pixel the share of n cosine-weighted rays (a power of two, 16 .. 4096; default 64) from the first hit that meet nothing within r\n"
                              "  (default 1), 1 where the pixel sees nothing; traced and baked on the device (rt_scene_bake_buffer); one GPU only\n"
@@ -719,6 +727,41 @@ int main(int argc, char** argv)
             WritePFM(ao_out.c_str(), rgba, width, height);
             std::cout << "ambient occlusion (" << ao.samples << " rays per pixel, radius " << ao.radius << ") written to " << ao_out << std::endl;
         };
+        // --ao_atlas: Render::OcclusionAtlas of the scene as it is posed, written as a grey PFM (row 0 = v 0 at the bottom, as a texture is addressed)
+        auto write_ao_atlas = [&]()
+        {
+            if (ao_atlas_out.empty()) return;
+            std::vector<float> uv;
+            if (atlas_synthetic)                                              // scenes.synthetic_atlas: cell k = (k % columns, k / columns) holds triangles 2 k and 2 k + 1
+            {
+                const std::size_t nt = scene.GetTriangles().size(), cells = nt / 2 + nt % 2 > 0 ? nt / 2 + nt % 2 : 1;
+                std::size_t columns = (std::size_t)std::ceil(std::sqrt((double)cells * (double)atlas.width / (double)(atlas.height ? atlas.height : 1u)));
+                if (columns == 0) columns = 1;
+                const std::size_t rows = (cells + columns - 1) / columns;
+                uv.resize(nt * 6);
+                for (std::size_t t = 0; t < nt; ++t)
+                {
+                    const std::size_t cx = (t / 2) % columns, cy = (t / 2) / columns;
+                    const float u0 = (float)((double)cx / (double)columns), u1 = (float)((double)(cx + 1) / (double)columns);
+                    const float v0 = (float)((double)cy / (double)rows), v1 = (float)((double)(cy + 1) / (double)rows);
+                    const float first[6] = {u0, v0, u1, v0, u1, v1}, second[6] = {u0, v0, u1, v1, u0, v1};
+                    for (int k = 0; k < 6; ++k) uv[t * 6 + k] = t % 2 == 0 ? first[k] : second[k];
+                }
+            }
+            const bool sized = atlas.width >= 1u && atlas.height >= 1u && atlas.width <= 16384u && atlas.height <= 16384u && (std::uint64_t)atlas.width * atlas.height <= (1ull << 26);
+            std::vector<float> grey(sized ? (size_t)atlas.width * atlas.height : 1u), rgba(grey.size() * 4);
+            rt_atlas_stats st;
+            render.OcclusionAtlas(atlas, atlas_synthetic ? uv.data() : nullptr, ao, grey.data(), &st);
+            for (size_t i = 0; i < grey.size(); ++i) { rgba[4 * i] = rgba[4 * i + 1] = rgba[4 * i + 2] = grey[i]; rgba[4 * i + 3] = 1.0f; }
+            // (WritePFM puts the image's top row last; an atlas's row 0 is v = 0, the bottom of the texture: written first)
+            std::vector<float> turned(rgba.size());
+            for (unsigned y = 0; y < atlas.height; ++y)
+                std::memcpy(&turned[(size_t)y * atlas.width * 4], &rgba[(size_t)(atlas.height - 1u - y) * atlas.width * 4], (size_t)atlas.width * 4 * sizeof(float));
+            WritePFM(ao_atlas_out.c_str(), turned, atlas.width, atlas.height);
+            std::cout << "ambient occlusion atlas " << atlas.width << "x" << atlas.height << " (" << ao.samples << " rays per texel, radius " << ao.radius << "): covered " << st.covered
+                      << " overlapped " << st.overlapped << " gutter " << st.gutter << " uncovered " << (size_t)atlas.width * atlas.height - st.covered - st.gutter
+                      << " triangles_skipped " << st.triangles_skipped << " triangles_without_texel " << st.triangles_without_texel << " written to " << ao_atlas_out << std::endl;
+        };
         const bool posing = !object_steps.empty();
         if (posing)                                                           // effective at the loop's upload below
         {
@@ -771,6 +814,7 @@ int main(int argc, char** argv)
             print_separations(posing);
             print_pick_rects();
             write_ao();
+            write_ao_atlas();
             return 0;
         }
         if (frames != 0)
@@ -817,6 +861,7 @@ int main(int argc, char** argv)
         print_separations(false);
         print_pick_rects();
         write_ao();
+        write_ao_atlas();
         if (!out.empty() && (filter_iterations >= 0 || temporal_iterations >= 0))
             WritePFM(out.c_str(), render.GetIntegrator().ResolveNow(), width, height);     // the filtered, tone-mapped image
         else if (!out.empty())

@@ -1,5 +1,7 @@
 #include "render.hpp"
 #include <chrono>
+#include <limits>
+#include <vector>
 #include <thread>
 
 namespace rt
@@ -19,6 +21,17 @@ Camera MakeCamera(float3 position, float yaw, float pitch, float fov, float aspe
     c.aperture = aperture;
     c.focus_distance = focus;
     return c;
+}
+
+void Render::OcclusionAtlas(rt_atlas_desc const& atlas, float const* uv, rt_bake_desc const& desc, float* out, rt_atlas_stats* stats)
+{
+    if (!out) throw HIPException("Render::OcclusionAtlas: out is NULL");
+    // (a size the library refuses is refused there, before anything is written: nothing is sized by it here)
+    const bool sized = atlas.width >= 1u && atlas.height >= 1u && atlas.width <= 16384u && atlas.height <= 16384u && (std::uint64_t)atlas.width * atlas.height <= (1ull << 26);
+    std::vector<rt_bake_result> results(sized ? (std::size_t)atlas.width * atlas.height : 1u);
+    integrator_->BakeAtlas(atlas, uv, desc, results.data(), nullptr, stats);
+    for (std::size_t i = 0; i < results.size(); ++i)
+        out[i] = results[i].unoccluded == RT_INVALID_ID ? std::numeric_limits<float>::quiet_NaN() : (float)results[i].unoccluded / (float)desc.samples;
 }
 
 Camera DefaultCamera(std::uint32_t width, std::uint32_t height)

@@ -60,6 +60,11 @@ public:
     // current camera (also one set since the last frame), width x height floats, 1 where the pixel-centre ray misses; the frame is not touched
     void BakeOcclusion(void const* points, std::size_t count, rt_bake_desc const& desc, rt_bake_result* out) { integrator_->BakeOcclusion(points, count, desc, out); }
     void OcclusionImage(rt_bake_desc const& desc, float* out) { integrator_->OcclusionImageThrough(camera_, desc, out); }
+    // The UV atlas: the cover, the surfaces of its records, and the ambient occlusion baked into it -- out[y * width + x] = unoccluded /
+    // samples of texel (x, y), NaN where no triangle covers it (after the gutter); stats may be nullptr.
+    void AtlasCover(rt_atlas_desc const& desc, float const* uv, rt_texel* texels, rt_atlas_stats* stats) { integrator_->AtlasCover(desc, uv, texels, stats); }
+    void AtlasSurfaces(rt_texel const* texels, std::size_t count, rt_surface* surfaces) { integrator_->AtlasSurfaces(texels, count, surfaces); }
+    void OcclusionAtlas(rt_atlas_desc const& atlas, float const* uv, rt_bake_desc const& desc, float* out, rt_atlas_stats* stats);
     // the nearest surface point to each of the caller's points; the frame is not touched
     void Nearest(rt_point const* points, std::size_t count, rt_nearest* out, rt_surface* surfaces) { integrator_->NearestPoints(points, count, out, surfaces); }
     // every triangle within max_distance of each of the caller's points, counted and the nearest max_near listed; the frame is not touched

@@ -588,6 +588,36 @@ def synthetic_morph(triangles, n_targets, radius=0.15, amplitude=0.05, normals=T
     return targets
 
 
+# --------------------------------------------------------------------------
+# a synthetic second UV set for any mesh (rt_scene_atlas / rt_scene_atlas_bake)
+# --------------------------------------------------------------------------
+def synthetic_atlas_grid(n_triangles, width, height):
+    """(columns, rows) of synthetic_atlas's cell grid: two triangles per cell, cells of the atlas's aspect.  At 2 * columns x 2 * rows texels or more (a
+    multiple of the grid each way) every triangle holds a texel centre."""
+    cells = max((int(n_triangles) + 1) // 2, 1)
+    columns = max(int(np.ceil(np.sqrt(cells * float(width) / float(height)))), 1)
+    return columns, (cells + columns - 1) // columns
+
+
+def synthetic_atlas(triangles, width, height):
+    """float32[n, 6] = u1 v1 u2 v2 u3 v3 per triangle: a crack-free, overlap-free UV set for any mesh, for scenes whose own UVs tile.  Cell k = (k % columns,
+    k // columns) of synthetic_atlas_grid's grid over [0, 1]^2 holds triangles 2 k and 2 k + 1, the two halves of its rectangle about the diagonal from its
+    corner nearest the origin; neighbouring cells compute their shared corners by the same division, so they share them exactly and the cover's edge rule
+    gives every texel centre on a shared edge to exactly one triangle."""
+    n = len(triangles)
+    columns, rows = synthetic_atlas_grid(n, width, height)
+    k = np.arange(n) // 2
+    cx, cy = k % columns, k // columns
+    u0, u1 = (cx / columns).astype(np.float32), ((cx + 1) / columns).astype(np.float32)
+    v0, v1 = (cy / rows).astype(np.float32), ((cy + 1) / rows).astype(np.float32)
+    first = (np.arange(n) % 2 == 0)
+    uv = np.empty((n, 6), np.float32)
+    uv[:, 0], uv[:, 1] = u0, v0
+    uv[:, 2], uv[:, 3] = u1, np.where(first, v0, v1)
+    uv[:, 4], uv[:, 5] = np.where(first, u1, u0), v1
+    return uv
+
+
 def blue_noise_tables(path=None):
     """(sobol_256spp_256d, scramblingTile, rankingTile) as int32 arrays from the packed asset
     (tools/make_blue_noise_asset.py)."""

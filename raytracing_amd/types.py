@@ -24,6 +24,12 @@ surface = np.dtype([("position", "<f4", (3,)), ("primitive_id", "<u4"), ("geomet
                     ("shading_normal", "<f4", (3,)), ("object", "<u4"), ("texcoord", "<f4", (2,)), ("t", "<f4"), ("flags", "<u4")])
 # rt_bake_result (include/rt_hip.h): what an occlusion bake reports of a point; a skipped point is unoccluded = 0xFFFFFFFF and zeros
 bake_result = np.dtype([("bent_normal", "<f4", (3,)), ("unoccluded", "<u4")])
+# rt_texel / rt_atlas_stats (include/rt_hip.h): what a UV atlas reports of a texel -- the lowest triangle that covers its centre, where on it, how many do;
+# flags 1 covered, 2 copied by the gutter; uncovered is primitive_id = 0xFFFFFFFF and zeros -- and of the whole cover
+texel = np.dtype([("bc", "<f4", (2,)), ("primitive_id", "<u4"), ("count", "<u2"), ("flags", "<u2")])
+atlas_stats = np.dtype([("covered", "<u4"), ("overlapped", "<u4"), ("gutter", "<u4"), ("triangles_skipped", "<u4"), ("triangles_without_texel", "<u4"),
+                        ("triangles_filtered", "<u4"), ("reserved", "<u4", (2,))])
+assert texel.itemsize == 16 and atlas_stats.itemsize == 32
 # rt_point / rt_nearest (include/rt_hip.h): a nearest-point query's point (max_distance may be +inf) and its answer; nothing found is primitive_id = 0xFFFFFFFF and zeros
 point = np.dtype([("position", "<f4", (3,)), ("max_distance", "<f4")])
 nearest = np.dtype([("position", "<f4", (3,)), ("distance", "<f4"), ("bc", "<f4", (2,)), ("primitive_id", "<u4"), ("flags", "<u4")])
