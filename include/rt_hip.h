@@ -411,6 +411,61 @@ int rt_scene_atlas_bake(rt_ctx* ctx, const rt_atlas_desc* atlas_desc, const floa
 int rt_debug_atlas(rt_ctx* ctx_or_null, const rt_triangle* triangles, uint32_t num_triangles, const uint32_t* object_of_triangle_or_null, const float* uv_or_null,
                    const rt_atlas_desc* desc, rt_texel* texels, rt_atlas_stats* stats);
 
+/* ---- light bakes: the irradiance the sky and the scene's analytic lights give the CALLER's points or the atlas's texels, direct terms only (opt-in
+ * extension).  Per point a cosine-weighted hemisphere of `samples` any-hit rays looks the environment up where it escapes, and one
+ * any-hit ray per light of the uploaded scene asks whether that light is seen: generated, walked and reduced on the device, 32 bytes per point out.
+ * raytracing_amd/csrc/light_bake.h states every step of the arithmetic (the items, the environment look-up, the lights' terms, the order of the reduction).
+ *   points, the skip rule, the frame, the biased origin, the rays' dependence on (i, seed): rt_scene_bake's, unchanged (RT_BAKE_FROM_SURFACES: rt_surface
+ *     records).  A SKIPPED point gives zeros and both counts RT_INVALID_ID.
+ *   sky = (pi / samples) * the sum of the environment (rt_scene_desc's env_rgba, the path tracer's own bilinear look-up) over the sky rays that meet nothing
+ *     within [0, sky_distance]: the irradiance from the environment, in its units; sky_unoccluded = how many those are -- with radius = sky_distance,
+ *     rt_scene_bake's unoccluded.
+ *   lights = the sum over the scene's lights that are above the point's horizon (cosine c > 0) and unshadowed of radiance * c / distance^2 (a point light;
+ *     its shadow ray is the segment to the light) or radiance * c (any other type: directional, light.origin its direction, shadowed within sky_distance);
+ *     lights_unshadowed = how many those are.  No material, no indirect light, no emissive triangle enters.
+ *   RT_LIGHT_BAKE_NO_SKY / RT_LIGHT_BAKE_NO_LIGHTS: that half makes no rays and stays zero.
+ * Everything runs on the context's stream, after every upload, refit or pose before it, touches no frame and no rt_stats field, and a traversal stack that ran
+ * over its bound is reported as a query's is.
+ *   rt_scene_light_bake: host arrays, staged in chunks of at most 1 Mi points (RT_CTX_OPT_BAKE_CHUNK_POINTS); a chunk carries the index of its first point,
+ *     so chunking changes no result; returns when `out` is written.
+ *   rt_scene_light_bake_buffer: rt_buffers of this context holding n records each; only enqueues.
+ *   rt_scene_atlas_bake_light: the cover, its surfaces and rt_scene_light_bake(RT_BAKE_FROM_SURFACES) of them in one call, all on the device: out[i] of texel i
+ *     is byte for byte rt_scene_light_bake of rt_scene_atlas_surfaces' records (point index = texel index); an uncovered texel is a skipped point.
+ *     desc->flags must be 0.  texels_or_null / stats_or_null: the cover itself.
+ *   rt_debug_light_bake_rays: rays_out[p * (samples + num_lights) + r] = the ray of item r of points[p], whose index is first_index + p (t_min 0 in origin.w,
+ *     t_max in direction.w); all zeros for an item that makes no ray and for a skipped point.  ctx == NULL: the host restatement (light_bake.h); otherwise
+ *     k_light_bake_rays on uploaded copies.  The two agree bit for bit.  At most 2^28 rays per call.
+ *   rt_debug_light_bake_reduce (host only): out[p] from the items of points[p] and their verdicts occluded[p * (samples + num_lights) + r] (!= 0: something
+ *     lies within the ray's range; ignored for items without a ray), in light_bake.h's order.  env_rgba: env_w x env_h RGBA floats; may be NULL with
+ *     RT_LIGHT_BAKE_NO_SKY.
+ * (The point forms are rt_scene_light_bake*, after rt_light_bake_desc and rt_debug_light_bake_*: the rt_scene_bake* family is the occlusion bake's two forms.)
+ * Refused with nothing launched: a NULL context, NULL points / desc / out with n > 0, no scene, samples not a power of two in 16 .. 4096, a bias or
+ * sky_distance that is not finite, sky_distance <= 0, unknown flag bits (rt_scene_atlas_bake_light: any flag bit), a buffer of another context or smaller than
+ * n records, NULL lights with num_lights > 0, more than 2^28 rays in a debug call.  n == 0 is RT_OK and does nothing. */
+#define RT_LIGHT_BAKE_NO_SKY    2u     /* beside RT_BAKE_FROM_SURFACES (1u) in rt_light_bake_desc.flags */
+#define RT_LIGHT_BAKE_NO_LIGHTS 4u
+typedef struct rt_light_bake_desc
+{
+    uint32_t samples;    /* sky rays per point: a power of two, 16 .. 4096 */
+    uint32_t seed;
+    uint32_t flags;      /* RT_BAKE_FROM_SURFACES | RT_LIGHT_BAKE_NO_SKY | RT_LIGHT_BAKE_NO_LIGHTS */
+    float bias;          /* origin = position + unit normal * bias */
+    float sky_distance;  /* t_max of the sky rays and of the directional lights' shadow rays; t_min = 0 */
+} rt_light_bake_desc;
+typedef struct rt_light_bake_result
+{
+    float sky[3];     uint32_t sky_unoccluded;
+    float lights[3];  uint32_t lights_unshadowed;
+} rt_light_bake_result;
+int rt_scene_light_bake(rt_ctx* ctx, const void* points, uint32_t n, const rt_light_bake_desc* desc, rt_light_bake_result* out);
+int rt_scene_light_bake_buffer(rt_ctx* ctx, rt_buffer* points, uint32_t n, const rt_light_bake_desc* desc, rt_buffer* out);
+int rt_scene_atlas_bake_light(rt_ctx* ctx, const rt_atlas_desc* atlas_desc, const float* uv_or_null, const rt_light_bake_desc* desc, rt_light_bake_result* out,
+                              rt_texel* texels_or_null, rt_atlas_stats* stats_or_null);
+int rt_debug_light_bake_rays(rt_ctx* ctx_or_null, const void* points, uint32_t n, uint32_t first_index, const rt_light_bake_desc* desc, const rt_light* lights,
+                             uint32_t num_lights, rt_ray* rays_out);
+int rt_debug_light_bake_reduce(const void* points, uint32_t n, uint32_t first_index, const rt_light_bake_desc* desc, const rt_light* lights, uint32_t num_lights,
+                               const float* env_rgba, uint32_t env_w, uint32_t env_h, const uint32_t* occluded, rt_light_bake_result* out);
+
 /* ---- nearest surface point: which triangle is nearest to each of the CALLER's points, where on it, and how far (opt-in extension).
  * raytracing_amd/csrc/nearest.h states every step of the arithmetic: the distance to one triangle (Ericson's region test, the blend in rt_surface's operand
  * order, the clamp to the triangle's box, d2 = |p - q|^2) and the distance to a box that prunes the walk.
@@ -1239,6 +1294,7 @@ RT_STATIC_ASSERT(sizeof(rt_skin_influence) == 24, "rt_skin_influence");
 RT_STATIC_ASSERT(sizeof(rt_morph_delta) == 32, "rt_morph_delta");
 RT_STATIC_ASSERT(sizeof(rt_surface) == 64, "rt_surface");
 RT_STATIC_ASSERT(sizeof(rt_bake_result) == 16 && sizeof(rt_bake_desc) == 20, "rt_bake_result / rt_bake_desc");
+RT_STATIC_ASSERT(sizeof(rt_light_bake_result) == 32 && sizeof(rt_light_bake_desc) == 20, "rt_light_bake_result / rt_light_bake_desc");
 RT_STATIC_ASSERT(sizeof(rt_texel) == 16 && sizeof(rt_atlas_desc) == 16 && sizeof(rt_atlas_stats) == 32, "rt_texel / rt_atlas_desc / rt_atlas_stats");
 RT_STATIC_ASSERT(sizeof(rt_point) == 16 && sizeof(rt_nearest) == 32, "rt_point / rt_nearest");
 RT_STATIC_ASSERT(sizeof(rt_ray_hits) == 16, "rt_ray_hits");

@@ -62,6 +62,7 @@ HIP_UNITS = [
     ("morph", "morph.hip", True),              # the scene's triangles morphed from one weight per sparse morph target, alone or fused with the skin in one pass: kernels + host driver + the host restatement (a code object of its own)
     ("query", "query.hip", True),              # caller-supplied rays traced against the uploaded scene, the surface record of a hit: kernels (the walk itself: walk_kernels.h, shared with bake and nearest) + the host driver core of all three + the host restatement (a code object of its own)
     ("bake", "bake.hip", True),                # ambient occlusion and bent normals at caller-supplied points: kernels on walk_kernels.h + host driver on query.hip's core + the host restatement (a code object of its own)
+    ("light_bake", "light_bake.hip", True),    # the irradiance of the sky and of the scene's analytic lights at caller-supplied points, direct terms only: kernels on walk_kernels.h + host driver on query.hip's core + the host restatement (a code object of its own: bake.hip's does not change)
     ("nearest", "nearest.hip", True),          # the nearest surface point to caller-supplied points: kernels on walk_kernels.h's stack + host driver on query.hip's core + the host's brute force and walk (a code object of its own)
     ("within", "within.hip", True),            # every triangle within a radius of caller-supplied points, counted and sorted: kernels on walk_kernels.h's stack and point_box_step + host driver on query.hip's core + the host's brute force and walk (a code object of its own)
     ("region", "region.hip", True),            # every triangle a caller-supplied convex region (up to 8 half-spaces) touches or encloses, counted and listed, and the per-triangle select of a few regions: kernels on walk_kernels.h's stack and region_box_step + host driver on query.hip's core + the host's brute force and walk (a code object of its own)
@@ -69,7 +70,7 @@ HIP_UNITS = [
     ("separation", "separation.hip", True),    # the nearest scene triangle to a caller-supplied triangle (the crossing verdict, then fifteen point-triangle and edge-edge candidates) with the two closest points, and the scene's clearances: kernels on walk_kernels.h's stack, volume_step and probe_box_step + host driver on query.hip's core + the host's brute force and walk (a code object of its own)
     ("all_hits", "all_hits.hip", True),        # every surface a caller-supplied ray crosses, counted and sorted: kernels on walk_kernels.h + host driver on query.hip's core + the host's brute force (a code object of its own)
     ("atlas", "atlas.hip", True),              # the scene's triangles rasterised into a UV atlas (no tree walked: one lane per triangle, the wave sweeps the large ones in 8 x 8 tiles), the gutter, the surfaces its texels show: kernels + host driver + the host restatement of atlas.h's integer rule (a code object of its own)
-    ("scene_queries", "scene_queries.cpp", False),   # the C entry points of the eight query families and the atlas above (rt_scene_trace* .. rt_scene_separation*, rt_scene_atlas* / rt_scene_atlas_bake, their rt_debug_* forms) on context.h: an edit to a query's bookkeeping rebuilds no kernel (no device code)
+    ("scene_queries", "scene_queries.cpp", False),   # the C entry points of the eight query families and the atlas above (rt_scene_trace* .. rt_scene_separation*, rt_scene_atlas* / rt_scene_atlas_bake, rt_scene_light_bake* / rt_scene_atlas_bake_light, their rt_debug_* forms) on context.h: an edit to a query's bookkeeping rebuilds no kernel (no device code)
     ("scene_upload", "scene_upload.cpp", False),     # rt_scene_upload and its stages, tree choice, FoldAdapt's worker, rt_scene_refit* / export_folds / import_folds / tree_report, the tree work's rt_debug_* forms, on context.h + fold_adapt.h (no device code)
     ("scene_moved", "scene_moved.cpp", False),       # the C entry points of pose, skin and morph (rt_scene_set_objects .. rt_scene_morph_skin, their rt_debug_* forms) on context.h; each ends in scene_upload.cpp's refit_device (no device code)
     ("context", "context.cpp", False),               # the context and the buffers: context::fail and the thread's message, dev_fill / scene_array / query_check_status / quiesce, rt_ctx_* / rt_finish / rt_host_* / rt_upload_blue_noise_tables, every rt_buffer_*, on context.h + frame.h (no device code)

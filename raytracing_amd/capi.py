@@ -116,6 +116,7 @@ EXPORTS = [
     "rt_frame_read_guide_motion", "rt_debug_guide_motion", "rt_debug_filter_temporal_motion",
     "rt_scene_trace", "rt_scene_trace_buffer", "rt_frame_pick", "rt_debug_query_surface",
     "rt_scene_bake", "rt_scene_bake_buffer", "rt_debug_bake_rays", "rt_debug_bake_reduce",
+    "rt_scene_light_bake", "rt_scene_light_bake_buffer", "rt_scene_atlas_bake_light", "rt_debug_light_bake_rays", "rt_debug_light_bake_reduce",
     "rt_scene_atlas", "rt_scene_atlas_buffer", "rt_scene_atlas_surfaces", "rt_scene_atlas_surfaces_buffer", "rt_scene_atlas_bake", "rt_debug_atlas",
     "rt_scene_nearest", "rt_scene_nearest_buffer", "rt_debug_nearest", "rt_debug_nearest_walk",
     "rt_scene_trace_all", "rt_scene_trace_all_buffer", "rt_frame_pick_all", "rt_debug_trace_all",
@@ -222,6 +223,10 @@ def load():
         "rt_scene_bake": (i32, [vp, vp, u32, C.POINTER(rt_bake_desc), vp]), "rt_scene_bake_buffer": (i32, [vp, vp, u32, C.POINTER(rt_bake_desc), vp]),
         "rt_debug_bake_rays": (i32, [vp, vp, u32, u32, C.POINTER(rt_bake_desc), vp]),
         "rt_debug_bake_reduce": (i32, [vp, vp, u32, u32, vp]),
+        "rt_scene_light_bake": (i32, [vp, vp, u32, C.POINTER(rt_light_bake_desc), vp]), "rt_scene_light_bake_buffer": (i32, [vp, vp, u32, C.POINTER(rt_light_bake_desc), vp]),
+        "rt_scene_atlas_bake_light": (i32, [vp, C.POINTER(rt_atlas_desc), vp, C.POINTER(rt_light_bake_desc), vp, vp, vp]),
+        "rt_debug_light_bake_rays": (i32, [vp, vp, u32, u32, C.POINTER(rt_light_bake_desc), vp, u32, vp]),
+        "rt_debug_light_bake_reduce": (i32, [vp, u32, u32, C.POINTER(rt_light_bake_desc), vp, u32, vp, u32, u32, vp, vp]),
         "rt_scene_atlas": (i32, [vp, C.POINTER(rt_atlas_desc), vp, vp, vp]), "rt_scene_atlas_buffer": (i32, [vp, C.POINTER(rt_atlas_desc), vp, vp, vp]),
         "rt_scene_atlas_surfaces": (i32, [vp, vp, u32, vp]), "rt_scene_atlas_surfaces_buffer": (i32, [vp, vp, u32, vp]),
         "rt_scene_atlas_bake": (i32, [vp, C.POINTER(rt_atlas_desc), vp, C.POINTER(rt_bake_desc), vp, vp, vp]),
@@ -600,6 +605,69 @@ def debug_bake_reduce(rays, occluded, samples):
     n = len(r) // samples
     out = np.zeros(n, T.bake_result)
     rc = lib.rt_debug_bake_reduce(r.ctypes.data if n else None, o.ctypes.data if n else None, n, samples, out.ctypes.data if n else None)
+    if rc != 0:
+        raise RtError(lib.rt_last_error(None).decode())
+    return out
+
+
+LIGHT_BAKE_NO_SKY, LIGHT_BAKE_NO_LIGHTS = 2, 4
+LIGHT_BAKE_SKY_DISTANCE_DEFAULT = 20000.0          # RT_MAX_RENDER_DIST
+
+
+class rt_light_bake_desc(C.Structure):
+    _fields_ = [("samples", C.c_uint32), ("seed", C.c_uint32), ("flags", C.c_uint32), ("bias", C.c_float), ("sky_distance", C.c_float)]
+
+
+def light_bake_desc(samples, seed=0, bias=BAKE_BIAS_DEFAULT, sky_distance=LIGHT_BAKE_SKY_DISTANCE_DEFAULT, from_surfaces=False, sky=True, lights=True, flags=None):
+    """rt_light_bake_desc; sky / lights False: RT_LIGHT_BAKE_NO_SKY / RT_LIGHT_BAKE_NO_LIGHTS; flags: the word itself"""
+    if flags is None:
+        flags = (BAKE_FROM_SURFACES if from_surfaces else 0) | (0 if sky else LIGHT_BAKE_NO_SKY) | (0 if lights else LIGHT_BAKE_NO_LIGHTS)
+    return rt_light_bake_desc(int(samples), int(seed) & 0xFFFFFFFF, flags, bias, sky_distance)
+
+
+def _lights(lights):
+    return np.ascontiguousarray(lights if lights is not None else np.zeros(0, T.light), T.light).reshape(-1)
+
+
+def debug_light_bake_rays(ctx, points, samples, lights=None, seed=0, bias=BAKE_BIAS_DEFAULT, sky_distance=LIGHT_BAKE_SKY_DISTANCE_DEFAULT, from_surfaces=False,
+                          sky=True, use_lights=True, first_index=0):
+    """rt_debug_light_bake_rays: the rays a light bake walks, types.ray[n, samples + len(lights)] (zeros for an item without a ray and for a skipped point); the
+    index of points[0] is first_index.  ctx None = the host restatement (csrc/light_bake.h), else k_light_bake_rays on ctx's GPU."""
+    lib = load()
+    pts = bake_points(points, from_surfaces)
+    lg = _lights(lights)
+    d = light_bake_desc(samples, seed, bias, sky_distance, from_surfaces, sky, use_lights)
+    n = len(pts)
+    out = np.zeros((n, max(int(samples), 0) + len(lg)), T.ray)
+    handle = ctx.handle if ctx is not None else None
+    rc = lib.rt_debug_light_bake_rays(handle, pts.ctypes.data if n else None, n, first_index, C.byref(d), lg.ctypes.data if len(lg) else None, len(lg),
+                                      out.ctypes.data if out.size else None)
+    if rc != 0:
+        raise RtError(lib.rt_last_error(handle).decode())
+    return out
+
+
+def debug_light_bake_reduce(points, samples, occluded, lights=None, env=None, seed=0, bias=BAKE_BIAS_DEFAULT, sky_distance=LIGHT_BAKE_SKY_DISTANCE_DEFAULT,
+                            from_surfaces=False, sky=True, use_lights=True, first_index=0):
+    """rt_debug_light_bake_reduce (host only): types.light_bake_result[n] of the points and the verdicts uint32[n, samples + len(lights)] of their items, in
+    light_bake.h's order.  env: float32[h, w, 4], the environment image (None only with sky=False)."""
+    lib = load()
+    pts = bake_points(points, from_surfaces)
+    lg = _lights(lights)
+    n = len(pts)
+    o = np.ascontiguousarray(occluded, np.uint32).reshape(-1)
+    if samples <= 0 or len(o) != n * (int(samples) + len(lg)):
+        raise RtError("debug_light_bake_reduce: one verdict per item (n * (samples + lights))")
+    e = None
+    if env is not None:
+        e = np.ascontiguousarray(env, np.float32)
+        if e.ndim != 3 or e.shape[2] != 4:
+            raise RtError("debug_light_bake_reduce: env must be float32[h, w, 4]")
+    d = light_bake_desc(samples, seed, bias, sky_distance, from_surfaces, sky, use_lights)
+    out = np.zeros(n, T.light_bake_result)
+    rc = lib.rt_debug_light_bake_reduce(pts.ctypes.data if n else None, n, first_index, C.byref(d), lg.ctypes.data if len(lg) else None, len(lg),
+                                        e.ctypes.data if e is not None else None, e.shape[1] if e is not None else 0, e.shape[0] if e is not None else 0,
+                                        o.ctypes.data if n else None, out.ctypes.data if n else None)
     if rc != 0:
         raise RtError(lib.rt_last_error(None).decode())
     return out
@@ -1466,6 +1534,35 @@ class Context:
         out = np.zeros(len(texels), T.bake_result)
         _check(self.lib, self.handle, self.lib.rt_scene_atlas_bake(self.handle, C.byref(d), u.ctypes.data if u is not None and u.size else None, C.byref(bd), out.ctypes.data,
                                                                      texels.ctypes.data, stats.ctypes.data))
+        return out, texels, stats[0]
+
+    def bake_light(self, points, samples, seed=0, bias=BAKE_BIAS_DEFAULT, sky_distance=LIGHT_BAKE_SKY_DISTANCE_DEFAULT, from_surfaces=False, sky=True, lights=True):
+        """rt_scene_light_bake: the irradiance of the sky and of the scene's analytic lights at the caller's points (bake_points' rule), direct terms only,
+        shadowed by the scene as posed now: types.light_bake_result[n]; a skipped point is zeros and both counts INVALID_ID"""
+        pts = bake_points(points, from_surfaces)
+        d = light_bake_desc(samples, seed, bias, sky_distance, from_surfaces, sky, lights)
+        out = np.zeros(len(pts), T.light_bake_result)
+        _check(self.lib, self.handle, self.lib.rt_scene_light_bake(self.handle, pts.ctypes.data if len(pts) else None, len(pts), C.byref(d), out.ctypes.data if len(pts) else None))
+        return out
+
+    def bake_light_buffer(self, points, n, out, samples, seed=0, bias=BAKE_BIAS_DEFAULT, sky_distance=LIGHT_BAKE_SKY_DISTANCE_DEFAULT, from_surfaces=False, sky=True,
+                          lights=True):
+        """rt_scene_light_bake_buffer: the same over Buffers of this context (n point records in, n types.light_bake_result out).  Only enqueues."""
+        d = light_bake_desc(samples, seed, bias, sky_distance, from_surfaces, sky, lights)
+        h = lambda b: b.handle if b is not None else None
+        _check(self.lib, self.handle, self.lib.rt_scene_light_bake_buffer(self.handle, h(points), n, C.byref(d), h(out)))
+
+    def bake_light_atlas(self, width, height, samples, seed=0, bias=BAKE_BIAS_DEFAULT, sky_distance=LIGHT_BAKE_SKY_DISTANCE_DEFAULT, gutter=0, object=None, uv=None,
+                         flags=0):
+        """rt_scene_atlas_bake_light: (types.light_bake_result[height * width], texels, stats) -- the cover, its surfaces and their light bake in one call on
+        the device; an uncovered texel is a skipped point"""
+        d = atlas_desc(width, height, gutter, object)
+        bd = light_bake_desc(samples, seed, bias, sky_distance, flags=flags)
+        u = atlas_uv(uv, self.num_triangles)
+        texels, stats = _atlas_texels(d), np.zeros(1, T.atlas_stats)
+        out = np.zeros(len(texels), T.light_bake_result)
+        _check(self.lib, self.handle, self.lib.rt_scene_atlas_bake_light(self.handle, C.byref(d), u.ctypes.data if u is not None and u.size else None, C.byref(bd),
+                                                                         out.ctypes.data, texels.ctypes.data, stats.ctypes.data))
         return out, texels, stats[0]
 
     def set_bake_chunk_points(self, points):

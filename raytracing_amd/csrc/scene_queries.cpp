@@ -5,7 +5,8 @@
 // and touches no frame.  (The three picks read a frame's camera and tile: they are frame_layout.cpp's and call the entries here.)  The stack spill area, the
 // status word and the staging arrays of every family but the bakes are the ray queries' (ctx->query), so rt_scene_tree_report's "ray queries" line
 // counts them; the bakes have a scratch of their own (ctx->bake).  The tree-less UV atlas (atlas.hip, section 7r: rt_scene_atlas*, rt_scene_atlas_surfaces*,
-// rt_scene_atlas_bake, rt_debug_atlas) has its entry points here too and works in the bakes' scratch.
+// rt_scene_atlas_bake, rt_debug_atlas) has its entry points here too and works in the bakes' scratch, and so do the light bakes (light_bake.hip, section 7s:
+// rt_scene_light_bake*, rt_scene_atlas_bake_light, rt_debug_light_bake_*).
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>
 #include <functional>
@@ -15,6 +16,8 @@
 #include "context.h"
 #include "query_host.h"
 #include "bake_host.h"
+#include "light_bake_host.h"
+#include "light_bake.h"
 #include "nearest_host.h"
 #include "all_hits_host.h"
 #include "within_host.h"
@@ -212,6 +215,69 @@ int rt_debug_bake_reduce(const rt_ray* rays, const uint32_t* occluded, uint32_t 
     if (!rays || !occluded || !out) return fail(nullptr, "rt_debug_bake_reduce: NULL argument");
     if (samples < 16u || samples > 4096u || (samples & (samples - 1u)) != 0u) return fail(nullptr, "rt_debug_bake_reduce: samples must be a power of two in 16 .. 4096");
     bake::debug_reduce_host(rays, occluded, n, samples, out);
+    return RT_OK;
+}
+
+// ---- light bakes: rt_scene_light_bake / rt_scene_light_bake_buffer / rt_debug_light_bake_rays / rt_debug_light_bake_reduce (light_bake.hip, DESIGN.md
+// section 7s; rt_scene_atlas_bake_light is with the atlas below).  They work in the bakes' scratch, as the occlusion bakes do ----------------------------
+
+// everything both forms refuse before anything is launched
+static int light_bake_refused(rt_ctx* ctx, const char* who, bool points, const rt_light_bake_desc* desc, bool out)
+{
+    const std::string name(who);
+    if (opening_refused(ctx, name, {{"points", points}, {"desc", desc != nullptr}, {"out", out}}, {}) != RT_OK) return RT_ERROR;
+    if (const char* why = light_bake::desc_refusal(*desc)) return fail(ctx, name + ": " + why);
+    return RT_OK;
+}
+
+static int light_bake_launch(rt_ctx* ctx, const char* who, const void* d_points, uint32_t n, uint32_t first_index, const rt_light_bake_desc& desc, rt_light_bake_result* d_out)
+{
+    const Scene& s = ctx->scene;
+    return launch_result(ctx, who, light_bake::launch(ctx->stream, ctx->bake, &ctx->query.status, s.d, s.wide_ok, ctx->prop.multiProcessorCount, d_points, n, first_index,
+        desc, d_out), ": the bake could not be launched (the stack spill area could not be allocated, or the launch failed)");
+}
+
+int rt_scene_light_bake(rt_ctx* ctx, const void* points, uint32_t n, const rt_light_bake_desc* desc, rt_light_bake_result* out)
+{
+    if (ctx && n == 0u) return RT_OK;
+    if (light_bake_refused(ctx, "rt_scene_light_bake", points != nullptr, desc, out != nullptr) != RT_OK) return RT_ERROR;
+    (void)hipSetDevice(ctx->device);
+    query::Scratch& b = ctx->bake;
+    return staged_call(ctx, "rt_scene_light_bake", b, {{(void*)points, light_bake::point_bytes(*desc), 0, true}, {out, sizeof(rt_light_bake_result), 1, false}}, n,
+        ctx->bake_chunk_points, [&](uint32_t first, uint32_t m) { return light_bake_launch(ctx, "rt_scene_light_bake", b.stage[0], m, first, *desc, (rt_light_bake_result*)b.stage[1]); });
+}
+
+int rt_scene_light_bake_buffer(rt_ctx* ctx, rt_buffer* points, uint32_t n, const rt_light_bake_desc* desc, rt_buffer* out)
+{
+    if (ctx && n == 0u) return RT_OK;
+    if (light_bake_refused(ctx, "rt_scene_light_bake_buffer", points != nullptr, desc, out != nullptr) != RT_OK) return RT_ERROR;
+    if (buffers_refused(ctx, "rt_scene_light_bake_buffer", {{points, light_bake::point_bytes(*desc), "points"}, {out, sizeof(rt_light_bake_result), "out"}}, n) != RT_OK)
+        return RT_ERROR;
+    (void)hipSetDevice(ctx->device);
+    return light_bake_launch(ctx, "rt_scene_light_bake_buffer", points->ptr, n, 0u, *desc, (rt_light_bake_result*)out->ptr);
+}
+
+int rt_debug_light_bake_rays(rt_ctx* ctx, const void* points, uint32_t n, uint32_t first_index, const rt_light_bake_desc* desc, const rt_light* lights,
+    uint32_t num_lights, rt_ray* rays_out)
+{
+    if (n == 0u) return RT_OK;
+    if (!points || !desc || !rays_out || (!lights && num_lights > 0u)) return fail(ctx, "rt_debug_light_bake_rays: NULL argument");
+    if (const char* why = light_bake::desc_refusal(*desc)) return fail(ctx, std::string("rt_debug_light_bake_rays: ") + why);
+    if ((uint64_t)n * ((uint64_t)desc->samples + num_lights) > (1ull << 28)) return fail(ctx, "rt_debug_light_bake_rays: more than 2^28 rays");
+    return host_or_device(ctx, "rt_debug_light_bake_rays", [&] { light_bake::debug_rays_host(points, n, first_index, *desc, lights, num_lights, rays_out); },
+        [&](hipStream_t st) { return light_bake::debug_rays_device(st, points, n, first_index, *desc, lights, num_lights, rays_out); });
+}
+
+int rt_debug_light_bake_reduce(const void* points, uint32_t n, uint32_t first_index, const rt_light_bake_desc* desc, const rt_light* lights, uint32_t num_lights,
+    const float* env_rgba, uint32_t env_w, uint32_t env_h, const uint32_t* occluded, rt_light_bake_result* out)
+{
+    if (n == 0u) return RT_OK;
+    if (!points || !desc || !occluded || !out || (!lights && num_lights > 0u)) return fail(nullptr, "rt_debug_light_bake_reduce: NULL argument");
+    if (const char* why = light_bake::desc_refusal(*desc)) return fail(nullptr, std::string("rt_debug_light_bake_reduce: ") + why);
+    if (!(desc->flags & RT_LIGHT_BAKE_NO_SKY) && (!env_rgba || env_w == 0u || env_h == 0u || env_w > 0x7FFFFFFFu || env_h > 0x7FFFFFFFu))
+        return fail(nullptr, "rt_debug_light_bake_reduce: no environment image (env_rgba NULL or a size of 0) and RT_LIGHT_BAKE_NO_SKY is not set");
+    if ((uint64_t)n * ((uint64_t)desc->samples + num_lights) > (1ull << 28)) return fail(nullptr, "rt_debug_light_bake_reduce: more than 2^28 rays");
+    light_bake::debug_reduce_host(points, n, first_index, *desc, lights, num_lights, env_rgba, env_w, env_h, occluded, out);
     return RT_OK;
 }
 
@@ -900,6 +966,30 @@ int rt_scene_atlas_bake(rt_ctx* ctx, const rt_atlas_desc* atlas_desc, const floa
             if (!query::reserve(ctx->stream, b, 0, (size_t)m * sizeof(rt_surface))) return fail(ctx, std::string(who) + ": out of device memory for the staging arrays");
             if (atlas_surfaces_launch(ctx, who, (const rt_texel*)b.stage[3] + first, m, (rt_surface*)b.stage[0]) != RT_OK) return (int)RT_ERROR;
             return bake_launch(ctx, who, b.stage[0], m, first, bd, (rt_bake_result*)b.stage[1]);
+        });
+}
+
+// rt_scene_atlas_bake with the light bake in the occlusion bake's place (light_bake.hip): the same cover, the same chunks
+int rt_scene_atlas_bake_light(rt_ctx* ctx, const rt_atlas_desc* atlas_desc, const float* uv, const rt_light_bake_desc* desc, rt_light_bake_result* out, rt_texel* texels,
+    rt_atlas_stats* stats)
+{
+    static const char who[] = "rt_scene_atlas_bake_light";
+    if (atlas_refused(ctx, who, atlas_desc, {{"desc", desc != nullptr}, {"out", out != nullptr}}) != RT_OK) return RT_ERROR;
+    if (desc->flags != 0u) return fail(ctx, std::string(who) + ": desc->flags must be 0 (the records are the atlas's own surfaces)");
+    rt_light_bake_desc bd = *desc;
+    bd.flags = RT_BAKE_FROM_SURFACES;
+    if (const char* why = light_bake::desc_refusal(bd)) return fail(ctx, std::string(who) + ": " + why);
+    (void)hipSetDevice(ctx->device);
+    if (atlas_on_scratch(ctx, who, *atlas_desc, uv) != RT_OK) return RT_ERROR;
+    query::Scratch& b = ctx->bake;
+    const uint32_t n = atlas_desc->width * atlas_desc->height;
+    if (texels) HIPCHK(ctx, hipMemcpyAsync(texels, b.stage[3], (size_t)n * sizeof(rt_texel), hipMemcpyDeviceToHost, ctx->stream));
+    if (stats) HIPCHK(ctx, hipMemcpyAsync(stats, b.stage[2], sizeof(rt_atlas_stats), hipMemcpyDeviceToHost, ctx->stream));
+    return staged_call(ctx, who, b, {{out, sizeof(rt_light_bake_result), 1, false}}, n, ctx->bake_chunk_points, [&](uint32_t first, uint32_t m)
+        {
+            if (!query::reserve(ctx->stream, b, 0, (size_t)m * sizeof(rt_surface))) return fail(ctx, std::string(who) + ": out of device memory for the staging arrays");
+            if (atlas_surfaces_launch(ctx, who, (const rt_texel*)b.stage[3] + first, m, (rt_surface*)b.stage[0]) != RT_OK) return (int)RT_ERROR;
+            return light_bake_launch(ctx, who, b.stage[0], m, first, bd, (rt_light_bake_result*)b.stage[1]);
         });
 }
 

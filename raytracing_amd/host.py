@@ -26,7 +26,7 @@ EXPORTS = [
     "rth_render_upload_gpu_data", "rth_render_setup_seconds", "rth_render_create_with_options",
     "rth_render_set_refittable", "rth_render_refit", "rth_render_set_refit_motion",
     "rth_render_set_objects", "rth_render_pose", "rth_render_pick", "rth_render_integrator_pick", "rth_render_trace",
-    "rth_render_bake", "rth_render_occlusion_image", "rth_render_atlas", "rth_render_occlusion_atlas", "rth_render_nearest", "rth_render_within", "rth_render_overlap", "rth_render_cross", "rth_render_self_cross", "rth_render_separation", "rth_render_clearance", "rth_render_select", "rth_render_pick_rect", "rth_render_integrator_pick_rect", "rth_render_trace_all", "rth_render_pick_all",
+    "rth_render_bake", "rth_render_occlusion_image", "rth_render_atlas", "rth_render_occlusion_atlas", "rth_render_bake_light", "rth_render_irradiance_image", "rth_render_irradiance_atlas", "rth_render_nearest", "rth_render_within", "rth_render_overlap", "rth_render_cross", "rth_render_self_cross", "rth_render_separation", "rth_render_clearance", "rth_render_select", "rth_render_pick_rect", "rth_render_integrator_pick_rect", "rth_render_trace_all", "rth_render_pick_all",
     "rth_scene_set_triangle_objects", "rth_scene_num_objects", "rth_scene_object_name", "rth_scene_num_triangle_objects", "rth_scene_triangle_objects",
     "rth_render_set_skin", "rth_render_skin", "rth_scene_set_triangle_skin", "rth_scene_num_triangle_skin", "rth_scene_triangle_skin",
     "rth_render_set_morph", "rth_render_morph", "rth_render_morph_skin",
@@ -81,6 +81,8 @@ def load():
         "rth_scene_set_triangle_skin": (i32, [vp, vp, u32]), "rth_scene_num_triangle_skin": (u32, [vp]), "rth_scene_triangle_skin": (vp, [vp]),
         "rth_render_pick": (i32, [vp, u32, u32, vp, vp, vp]), "rth_render_integrator_pick": (i32, [vp, u32, u32, vp, vp, vp]), "rth_render_trace": (i32, [vp, vp, u32, i32, vp, vp, vp]),
         "rth_render_bake": (i32, [vp, vp, u32, vp, vp]), "rth_render_occlusion_image": (i32, [vp, vp, vp]),
+        "rth_render_bake_light": (i32, [vp, vp, u32, vp, vp]), "rth_render_irradiance_image": (i32, [vp, vp, vp]),
+        "rth_render_irradiance_atlas": (i32, [vp, vp, vp, vp, vp, vp]),
         "rth_render_atlas": (i32, [vp, vp, vp, vp, vp]), "rth_render_occlusion_atlas": (i32, [vp, vp, vp, vp, vp, vp]),
         "rth_render_nearest": (i32, [vp, vp, u32, vp, vp]),
         "rth_render_within": (i32, [vp, vp, u32, u32, u32, vp, vp, vp]),
@@ -557,6 +559,36 @@ class Render:
         self._c(self.lib.rth_render_occlusion_atlas(self.handle, C.addressof(d), u.ctypes.data if u is not None and u.size else None, C.addressof(bd), out.ctypes.data,
                                                     stats.ctypes.data))
         return out.reshape(height, width), stats[0]
+
+    def bake_light(self, points, samples, seed=0, bias=1e-3, sky_distance=20000.0, from_surfaces=False, sky=True, lights=True):
+        """The irradiance of the sky and of the scene's analytic lights at the caller's points, direct terms only, against the scene as it is posed now
+        (HIPPathTraceIntegrator::BakeLight; points as bake()'s): types.light_bake_result[n]"""
+        from . import capi
+        pts = capi.bake_points(points, from_surfaces)
+        d = capi.light_bake_desc(samples, seed, bias, sky_distance, from_surfaces, sky, lights)
+        out = np.zeros(len(pts), T.light_bake_result)
+        self._c(self.lib.rth_render_bake_light(self.handle, pts.ctypes.data if len(pts) else None, len(pts), C.addressof(d), out.ctypes.data if len(pts) else None))
+        return out
+
+    def irradiance_image(self, samples, sky_distance=20000.0, bias=1e-3, seed=0, sky=True, lights=True):
+        """The direct irradiance image of the Render's current camera (Render::IrradianceImage): float32[height, width, 3] = sky + lights at the pixel-centre
+        ray's first hit, zeros where it misses; picked and baked on the device, the frame is not touched"""
+        from . import capi
+        d = capi.light_bake_desc(samples, seed, bias, sky_distance, sky=sky, lights=lights)
+        out = np.zeros((self.height, self.width, 3), np.float32)
+        self._c(self.lib.rth_render_irradiance_image(self.handle, C.addressof(d), out.ctypes.data))
+        return out
+
+    def irradiance_atlas(self, width, height, samples, sky_distance=20000.0, bias=1e-3, seed=0, gutter=0, object=None, uv=None):
+        """The lightmap, baked into a UV atlas on the device (Render::IrradianceAtlas): (float32[height, width, 3] = sky + lights of the surface point each
+        texel shows, NaN where no triangle covers it, types.atlas_stats record)"""
+        from . import capi
+        d, bd = capi.atlas_desc(width, height, gutter, object), capi.light_bake_desc(samples, seed, bias, sky_distance)
+        u = None if uv is None else np.ascontiguousarray(uv, np.float32).reshape(-1)
+        out, stats = np.zeros(3 * len(capi._atlas_texels(d)), np.float32), np.zeros(1, T.atlas_stats)
+        self._c(self.lib.rth_render_irradiance_atlas(self.handle, C.addressof(d), u.ctypes.data if u is not None and u.size else None, C.addressof(bd), out.ctypes.data,
+                                                     stats.ctypes.data))
+        return out.reshape(height, width, 3), stats[0]
 
     def _surface_dict(self, surf, names, objects):
         """a types.surface record as pick() reports it: its fields, and `object_name` when the scene was loaded with objects"""

@@ -383,6 +383,53 @@ void HIPPathTraceIntegrator::BakeAtlas(rt_atlas_desc const& atlas, float const* 
     Check(rt_scene_atlas_bake(context_.Get(), &atlas, uv, &desc, out, texels, stats));
 }
 
+void HIPPathTraceIntegrator::BakeLight(void const* points, std::size_t count, rt_light_bake_desc const& desc, rt_light_bake_result* out)
+{
+    if (count > 0xFFFFFFFFull) throw HIPException("HIPPathTraceIntegrator::BakeLight: more than 2^32 - 1 points in one call");
+    Check(rt_scene_light_bake(context_.Get(), points, (uint32_t)count, &desc, out));
+}
+
+void HIPPathTraceIntegrator::IrradianceImageThrough(Camera const& camera, rt_light_bake_desc desc, float* out)
+{
+    if (!out) throw HIPException("HIPPathTraceIntegrator::IrradianceImageThrough: out is NULL");
+    if (rt_frame_local_rows(frame_) != height_) throw HIPException("HIPPathTraceIntegrator::IrradianceImageThrough: a tile frame: bake on a frame of the whole image");
+    rt_camera cam;
+    std::memcpy(&cam, &camera, sizeof(cam));
+    const float tan_half = rt_tanf(0.5f * cam.fov);
+    const std::size_t n = (std::size_t)width_ * height_;
+    std::vector<rt_ray> rays(n);
+    for (std::uint32_t y = 0; y < height_; ++y)
+        for (std::uint32_t x = 0; x < width_; ++x)
+        {
+            float d[3];
+            sf_guide_dir(cam, tan_half, width_, height_, x, y, d);              // PickThrough's ray
+            rt_ray& r = rays[(std::size_t)y * width_ + x];
+            r.origin = {cam.position.x, cam.position.y, cam.position.z, 0.0f};
+            r.direction = {d[0], d[1], d[2], RT_MAX_RENDER_DIST};
+        }
+    desc.flags |= RT_BAKE_FROM_SURFACES;
+    rt_buffer *b_rays = nullptr, *b_surf = nullptr, *b_out = nullptr;
+    std::vector<rt_light_bake_result> results(n);
+    // rays up, surfaces and results stay on the device, 32 bytes per pixel come back
+    int rc = rt_buffer_create(context_.Get(), n * sizeof(rt_ray), rays.data(), &b_rays);
+    if (rc == RT_OK) rc = rt_buffer_create(context_.Get(), n * sizeof(rt_surface), nullptr, &b_surf);
+    if (rc == RT_OK) rc = rt_buffer_create(context_.Get(), n * sizeof(rt_light_bake_result), nullptr, &b_out);
+    if (rc == RT_OK) rc = rt_scene_trace_buffer(context_.Get(), b_rays, (uint32_t)n, RT_QUERY_CLOSEST, nullptr, nullptr, b_surf);
+    if (rc == RT_OK) rc = rt_scene_light_bake_buffer(context_.Get(), b_surf, (uint32_t)n, &desc, b_out);
+    if (rc == RT_OK) rc = rt_buffer_read(b_out, 0, results.data(), n * sizeof(rt_light_bake_result));
+    const std::string why = rc == RT_OK ? std::string() : std::string(rt_last_error(context_.Get()));
+    rt_buffer_destroy(b_rays); rt_buffer_destroy(b_surf); rt_buffer_destroy(b_out);
+    if (rc != RT_OK) throw HIPException(why);
+    for (std::size_t i = 0; i < n; ++i)
+        for (int q = 0; q < 3; ++q) out[3 * i + q] = results[i].sky[q] + results[i].lights[q];       // (a skipped point's are zeros)
+}
+
+void HIPPathTraceIntegrator::BakeLightAtlas(rt_atlas_desc const& atlas, float const* uv, rt_light_bake_desc const& desc, rt_light_bake_result* out, rt_texel* texels,
+    rt_atlas_stats* stats)
+{
+    Check(rt_scene_atlas_bake_light(context_.Get(), &atlas, uv, &desc, out, texels, stats));
+}
+
 void HIPPathTraceIntegrator::SetCameraData(Camera const& camera)
 {
     prev_camera_ = camera_;

@@ -138,6 +138,13 @@ public:
     void AtlasCover(rt_atlas_desc const& desc, float const* uv, rt_texel* texels, rt_atlas_stats* stats);
     void AtlasSurfaces(rt_texel const* texels, std::size_t count, rt_surface* surfaces);
     void BakeAtlas(rt_atlas_desc const& atlas, float const* uv, rt_bake_desc const& desc, rt_bake_result* out, rt_texel* texels, rt_atlas_stats* stats);
+    // Light bakes (rt_scene_light_bake).  BakeLight: the irradiance of the sky and of the scene's analytic lights at the caller's points
+    // (BakeOcclusion's records), direct terms only; a count of 2^32 or more is refused.  IrradianceImageThrough: OcclusionImageThrough's pixel-centre surfaces,
+    // light-baked on the device; out[(y * width + x) * 3 ..] = sky + lights, zeros where nothing is walked.  BakeLightAtlas: the cover, its surfaces and their
+    // light bake in one call on the device (desc.flags must be 0; texels and stats may be nullptr); an uncovered texel's result is a skipped point's.
+    void BakeLight(void const* points, std::size_t count, rt_light_bake_desc const& desc, rt_light_bake_result* out);
+    void IrradianceImageThrough(Camera const& camera, rt_light_bake_desc desc, float* out);
+    void BakeLightAtlas(rt_atlas_desc const& atlas, float const* uv, rt_light_bake_desc const& desc, rt_light_bake_result* out, rt_texel* texels, rt_atlas_stats* stats);
     // Nearest surface points (rt_scene_nearest): for each of the caller's points the nearest triangle of the scene as it is posed now, where
     // on it and how far, optionally with the rt_surface there; a count of 2^32 or more is refused.  Throws HIPException with the library's message on a
     // refusal; requests no reset and does not touch the frame.

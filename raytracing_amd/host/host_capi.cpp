@@ -311,6 +311,18 @@ int rth_render_occlusion_atlas(void* r, const rt_atlas_desc* atlas, const float*
 {
     return guard([&]() { if (!atlas || !desc) throw rt::HIPException("rth_render_occlusion_atlas: desc is NULL"); ((rt::Render*)r)->OcclusionAtlas(*atlas, uv, *desc, out, stats); return 0; }, 1);
 }
+int rth_render_bake_light(void* r, const void* points, uint32_t n, const rt_light_bake_desc* desc, rt_light_bake_result* out)
+{
+    return guard([&]() { if (!desc) throw rt::HIPException("rth_render_bake_light: desc is NULL"); ((rt::Render*)r)->BakeLight(points, n, *desc, out); return 0; }, 1);
+}
+int rth_render_irradiance_image(void* r, const rt_light_bake_desc* desc, float* out)
+{
+    return guard([&]() { if (!desc) throw rt::HIPException("rth_render_irradiance_image: desc is NULL"); ((rt::Render*)r)->IrradianceImage(*desc, out); return 0; }, 1);
+}
+int rth_render_irradiance_atlas(void* r, const rt_atlas_desc* atlas, const float* uv, const rt_light_bake_desc* desc, float* out, rt_atlas_stats* stats)
+{
+    return guard([&]() { if (!atlas || !desc) throw rt::HIPException("rth_render_irradiance_atlas: desc is NULL"); ((rt::Render*)r)->IrradianceAtlas(*atlas, uv, *desc, out, stats); return 0; }, 1);
+}
 int rth_render_nearest(void* r, const rt_point* points, uint32_t n, rt_nearest* out, rt_surface* surfaces)
 {
     return guard([&]() { ((rt::Render*)r)->Nearest(points, n, out, surfaces); return 0; }, 1);

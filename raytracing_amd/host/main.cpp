@@ -48,6 +48,7 @@ int main(int argc, char** argv)
         rt_bake_desc ao = {64u, 0u, 0u, 1e-3f, 1.0f};   // --ao_samples n --ao_radius r --ao_bias b
         std::string ao_atlas_out;               // --ao_atlas out.pfm: after the scene is uploaded and posed, bake the ambient occlusion into a UV atlas (grey, NaN where uncovered)
         rt_atlas_desc atlas = {0u, 0u, 0u, RT_INVALID_ID};   // --atlas_size w,h --atlas_gutter n
+        std::string lightmap_out;               // --lightmap out.pfm: after the scene is uploaded and posed, bake the direct irradiance (sky + lights) into a UV atlas (RGB, NaN where uncovered)
         bool atlas_synthetic = false;           // --atlas_uv synthetic: a crack-free grid of two triangles per cell instead of the triangles' own UVs (scenes.synthetic_atlas)
         struct WithinAt { rt_point point; std::uint32_t k; };
         std::vector<WithinAt> within_points;    // --within x,y,z,r[,k] (repeatable): after the scene is uploaded and posed, print the triangles within r (the k nearest only)
@@ -236,6 +237,7 @@ int main(int argc, char** argv)
             }
             else if (!strcmp(argv[i], "--ao")) ao_out = next();
             else if (!strcmp(argv[i], "--ao_atlas")) ao_atlas_out = next();
+            else if (!strcmp(argv[i], "--lightmap")) lightmap_out = next();
             else if (!strcmp(argv[i], "--atlas_size")) { if (sscanf(next(), "%u,%u", &atlas.width, &atlas.height) != 2) { std::cerr << "--atlas_size w,h\n"; return 2; } }
             else if (!strcmp(argv[i], "--atlas_gutter")) atlas.gutter = (unsigned)atoi(next());
             else if (!strcmp(argv[i], "--atlas_uv")) atlas_synthetic = !strcmp(next(), "synthetic");
@@ -266,6 +268,7 @@ int main(int argc, char** argv)
                              "  (rt_scene_pose: the scene is uploaded refittable, and with --temporal_filter the history follows the move); one GPU only\n"
                              "  --pick x,y (repeatable) prints what lies under the centre of that pixel once the scene is uploaded and posed: primitive, t, position,\n"
                              "  normals, texture coordinates, material and object (index and name); one GPU only\n"
+                             "  --lightmap out.pfm --atlas_size w,h [--atlas_gutter n] [--atlas_uv own|synthetic] bakes the irradiance of the sky and of the scene's lights into a UV atlas (--ao_samples rays per texel; NaN where uncovered)\n"
                              "  --ao_atlas out.pfm --atlas_size w,h [--atlas_gutter n] [--atlas_uv own|synthetic] bakes the ambient occlusion into a UV atlas (--ao_samples / --ao_radius; NaN where uncovered)\n"
                              "  --ao out.pfm --ao_samples n --ao_radius r [--ao_bias b] writes the exact ambient occlusion image of the camera once the scene is uploaded\n"
                              "  and posed: per pixel the share of n cosine-weighted rays (a power of two, 16 .. 4096; default 64) from the first hit that meet nothing within r\n"
@@ -727,10 +730,11 @@ int main(int argc, char** argv)
             WritePFM(ao_out.c_str(), rgba, width, height);
             std::cout << "ambient occlusion (" << ao.samples << " rays per pixel, radius " << ao.radius << ") written to " << ao_out << std::endl;
         };
-        // --ao_atlas: Render::OcclusionAtlas of the scene as it is posed, written as a grey PFM (row 0 = v 0 at the bottom, as a texture is addressed)
+        // --ao_atlas / --lightmap: Render::OcclusionAtlas / IrradianceAtlas of the scene as it is posed, written as a grey / RGB PFM (row 0 = v 0 at the
+        // bottom, as a texture is addressed)
         auto write_ao_atlas = [&]()
         {
-            if (ao_atlas_out.empty()) return;
+            if (ao_atlas_out.empty() && lightmap_out.empty()) return;
             std::vector<float> uv;
             if (atlas_synthetic)                                              // scenes.synthetic_atlas: cell k = (k % columns, k / columns) holds triangles 2 k and 2 k + 1
             {
@@ -751,6 +755,25 @@ int main(int argc, char** argv)
             const bool sized = atlas.width >= 1u && atlas.height >= 1u && atlas.width <= 16384u && atlas.height <= 16384u && (std::uint64_t)atlas.width * atlas.height <= (1ull << 26);
             std::vector<float> grey(sized ? (size_t)atlas.width * atlas.height : 1u), rgba(grey.size() * 4);
             rt_atlas_stats st;
+            if (!lightmap_out.empty())
+            {
+                rt_light_bake_desc lb;
+                lb.samples = ao.samples; lb.seed = ao.seed; lb.flags = 0u; lb.bias = ao.bias; lb.sky_distance = RT_MAX_RENDER_DIST;
+                std::vector<float> rgb(grey.size() * 3), turned(rgba.size());
+                render.IrradianceAtlas(atlas, atlas_synthetic ? uv.data() : nullptr, lb, rgb.data(), &st);
+                for (unsigned y = 0; y < atlas.height; ++y)
+                    for (unsigned x = 0; x < atlas.width; ++x)
+                    {
+                        const float* s = &rgb[((size_t)(atlas.height - 1u - y) * atlas.width + x) * 3];
+                        float* d = &turned[((size_t)y * atlas.width + x) * 4];
+                        d[0] = s[0]; d[1] = s[1]; d[2] = s[2]; d[3] = 1.0f;
+                    }
+                WritePFM(lightmap_out.c_str(), turned, atlas.width, atlas.height);
+                std::cout << "lightmap " << atlas.width << "x" << atlas.height << " (" << lb.samples << " sky rays per texel, sky + lights): covered " << st.covered
+                          << " overlapped " << st.overlapped << " gutter " << st.gutter << " uncovered " << (size_t)atlas.width * atlas.height - st.covered - st.gutter
+                          << " triangles_skipped " << st.triangles_skipped << " triangles_without_texel " << st.triangles_without_texel << " written to " << lightmap_out << std::endl;
+            }
+            if (ao_atlas_out.empty()) return;
             render.OcclusionAtlas(atlas, atlas_synthetic ? uv.data() : nullptr, ao, grey.data(), &st);
             for (size_t i = 0; i < grey.size(); ++i) { rgba[4 * i] = rgba[4 * i + 1] = rgba[4 * i + 2] = grey[i]; rgba[4 * i + 3] = 1.0f; }
             // (WritePFM puts the image's top row last; an atlas's row 0 is v = 0, the bottom of the texture: written first)

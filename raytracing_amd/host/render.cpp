@@ -34,6 +34,18 @@ void Render::OcclusionAtlas(rt_atlas_desc const& atlas, float const* uv, rt_bake
         out[i] = results[i].unoccluded == RT_INVALID_ID ? std::numeric_limits<float>::quiet_NaN() : (float)results[i].unoccluded / (float)desc.samples;
 }
 
+void Render::IrradianceAtlas(rt_atlas_desc const& atlas, float const* uv, rt_light_bake_desc const& desc, float* out, rt_atlas_stats* stats)
+{
+    if (!out) throw HIPException("Render::IrradianceAtlas: out is NULL");
+    // (a size the library refuses is refused there, before anything is written: nothing is sized by it here)
+    const bool sized = atlas.width >= 1u && atlas.height >= 1u && atlas.width <= 16384u && atlas.height <= 16384u && (std::uint64_t)atlas.width * atlas.height <= (1ull << 26);
+    std::vector<rt_light_bake_result> results(sized ? (std::size_t)atlas.width * atlas.height : 1u);
+    integrator_->BakeLightAtlas(atlas, uv, desc, results.data(), nullptr, stats);
+    for (std::size_t i = 0; i < results.size(); ++i)
+        for (int q = 0; q < 3; ++q)
+            out[3 * i + q] = results[i].sky_unoccluded == RT_INVALID_ID ? std::numeric_limits<float>::quiet_NaN() : results[i].sky[q] + results[i].lights[q];
+}
+
 Camera DefaultCamera(std::uint32_t width, std::uint32_t height)
 {
     const float kPiDiv2 = 1.570796327f;                       // MATH_PIDIV2, mathlib.hpp:37

@@ -65,6 +65,12 @@ public:
     void AtlasCover(rt_atlas_desc const& desc, float const* uv, rt_texel* texels, rt_atlas_stats* stats) { integrator_->AtlasCover(desc, uv, texels, stats); }
     void AtlasSurfaces(rt_texel const* texels, std::size_t count, rt_surface* surfaces) { integrator_->AtlasSurfaces(texels, count, surfaces); }
     void OcclusionAtlas(rt_atlas_desc const& atlas, float const* uv, rt_bake_desc const& desc, float* out, rt_atlas_stats* stats);
+    // Light bakes: the irradiance of the sky and of the scene's lights at the caller's points; the irradiance image of the Render's current
+    // camera, width x height x 3 floats of sky + lights, zeros where the pixel-centre ray misses; and the lightmap -- out[(y * width + x) * 3 ..] = sky + lights
+    // of texel (x, y), NaN where no triangle covers it (after the gutter); stats may be nullptr.  The frame is not touched.
+    void BakeLight(void const* points, std::size_t count, rt_light_bake_desc const& desc, rt_light_bake_result* out) { integrator_->BakeLight(points, count, desc, out); }
+    void IrradianceImage(rt_light_bake_desc const& desc, float* out) { integrator_->IrradianceImageThrough(camera_, desc, out); }
+    void IrradianceAtlas(rt_atlas_desc const& atlas, float const* uv, rt_light_bake_desc const& desc, float* out, rt_atlas_stats* stats);
     // the nearest surface point to each of the caller's points; the frame is not touched
     void Nearest(rt_point const* points, std::size_t count, rt_nearest* out, rt_surface* surfaces) { integrator_->NearestPoints(points, count, out, surfaces); }
     // every triangle within max_distance of each of the caller's points, counted and the nearest max_near listed; the frame is not touched

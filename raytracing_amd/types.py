@@ -24,6 +24,9 @@ surface = np.dtype([("position", "<f4", (3,)), ("primitive_id", "<u4"), ("geomet
                     ("shading_normal", "<f4", (3,)), ("object", "<u4"), ("texcoord", "<f4", (2,)), ("t", "<f4"), ("flags", "<u4")])
 # rt_bake_result (include/rt_hip.h): what an occlusion bake reports of a point; a skipped point is unoccluded = 0xFFFFFFFF and zeros
 bake_result = np.dtype([("bent_normal", "<f4", (3,)), ("unoccluded", "<u4")])
+# rt_light_bake_result (include/rt_hip.h): what a light bake reports of a point -- the irradiance from the sky and from the scene's analytic lights, and how many
+# sky rays and lights reached it; a skipped point is zeros and both counts 0xFFFFFFFF
+light_bake_result = np.dtype([("sky", "<f4", (3,)), ("sky_unoccluded", "<u4"), ("lights", "<f4", (3,)), ("lights_unshadowed", "<u4")])
 # rt_texel / rt_atlas_stats (include/rt_hip.h): what a UV atlas reports of a texel -- the lowest triangle that covers its centre, where on it, how many do;
 # flags 1 covered, 2 copied by the gutter; uncovered is primitive_id = 0xFFFFFFFF and zeros -- and of the whole cover
 texel = np.dtype([("bc", "<f4", (2,)), ("primitive_id", "<u4"), ("count", "<u2"), ("flags", "<u2")])
@@ -63,7 +66,7 @@ camera = np.dtype([("position", float3), ("front", float3), ("up", float3), ("fo
 assert ray.itemsize == 32 and hit.itemsize == 16 and scene_info.itemsize == 16
 assert packed_material.itemsize == 20 and light.itemsize == 48 and texture.itemsize == 16
 assert vertex.itemsize == 48 and triangle.itemsize == 160 and bvh_node.itemsize == 48
-assert camera.itemsize == 64 and surface.itemsize == 64 and bake_result.itemsize == 16
+assert camera.itemsize == 64 and surface.itemsize == 64 and bake_result.itemsize == 16 and light_bake_result.itemsize == 32
 assert point.itemsize == 16 and nearest.itemsize == 32 and ray_hits.itemsize == 16 and point_hits.itemsize == 16
 assert region.itemsize == 144 and region_hits.itemsize == 16 and region_member.itemsize == 8
 assert probe.itemsize == 48 and probe_hits.itemsize == 16 and cross_member.itemsize == 32
