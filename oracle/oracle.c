@@ -1606,3 +1606,34 @@ ORC_EXPORT float orc_cosf(float x) { return rt_cosf(x); }
 ORC_EXPORT float orc_powf(float x, float y) { return rt_powf(x, y); }
 ORC_EXPORT float orc_atan2f(float y, float x) { return rt_atan2f(y, x); }
 ORC_EXPORT float orc_acosf(float x) { return rt_acosf(x); }
+
+/* k_debug_eval's switch (raygen_kernels.h) restated over whole arrays: the same codes, the same header functions */
+ORC_EXPORT void orc_debug_eval(int fn, const float* a, const float* b, float* out, uint32_t n)
+{
+    for (uint32_t i = 0; i < n; ++i)
+    {
+        float x = a[i], y = b ? b[i] : 0.0f, r = 0.0f;
+        uint32_t xb, yb;
+        memcpy(&xb, &x, 4);
+        memcpy(&yb, &y, 4);
+        switch (fn)
+        {
+        case 0: r = rt_sinf(x); break;
+        case 1: r = rt_cosf(x); break;
+        case 2: r = rt_tanf(x); break;
+        case 3: r = rt_powf(x, y); break;
+        case 4: r = rt_atan2f(x, y); break;
+        case 5: r = rt_acosf(x); break;
+        case 6: r = __builtin_sqrtf(x); break;
+        case 7: r = x / y; break;
+        case 8: r = SampleRandom(xb & 0xFFFFu, xb >> 16, yb & 0xFFFFu, (yb >> 16) / 5u, (yb >> 16) % 5u); break;
+        case 9: r = (float)(1.0 / __builtin_sqrt(1.0 + (double)x / (1.0 - (double)y))); break;
+        case 10: r = rt_expf(x); break;
+        case 11: r = rt_ldexpf(x, (int)yb); break;
+        case 12: r = (float)((double)x / (double)y); break;
+        case 13: r = (float)__builtin_sqrt((double)x); break;
+        default: break;
+        }
+        out[i] = r;
+    }
+}

@@ -106,6 +106,10 @@ __global__ void k_debug_eval(int fn, const float* a, const float* b, float* out,
     case 9:   // fp64 path of GGX_Sample: x = alpha*alpha*s.y, y = s.y
         r = (float)(1.0 / __builtin_sqrt(1.0 + (double)x / (1.0 - (double)y)));
         break;
+    case 10: r = rt_expf(x); break;
+    case 11: r = rt_ldexpf(x, (int)__float_as_uint(y)); break;   // k = the int bit pattern of b[i]
+    case 12: r = (float)((double)x / (double)y); break;          // the fp64 divide and sqrt every rt_detmath.h function stands on
+    case 13: r = (float)__builtin_sqrt((double)x); break;
     default: break;
     }
     out[i] = r;

@@ -21,7 +21,13 @@
  *
  * Plain C99, header only; compiles as C, C++ and HIP (host + device).
  * Domain notes: sin/cos/tan reduce with a 2-term Cody-Waite pi/2 and are
- * accurate for |x| < 1e5 (the path uses phi in [0, 2pi] and fov/2).
+ * accurate for |x| < 1e5 (the path uses phi in [0, 2pi] and fov/2).  For
+ * 1e5 <= |x| < 1e9 they are deterministic and within [-1, 1] but not accurate;
+ * for |x| >= 1e9 (1e9f included), as for inf and NaN, they are NaN by definition.
+ * Zeros, infinities and NaN follow C99 Annex F throughout (pow's and atan2's
+ * tables, sin(-0) = tan(-0) = -0).  Measured edge by edge, host against a
+ * 200-bit reference and device against host: tests/test_detmath_edges.py,
+ * tests/test_gpu_detmath_edges.py.
  */
 #ifndef RT_DETMATH_H
 #define RT_DETMATH_H
@@ -100,8 +106,10 @@ RTD_FN void rtd_sincos(double x, double* s, double* c)
 {
     if (!(x > -1.0e9 && x < 1.0e9))
     {
-        *s = x - x; /* NaN for inf/NaN, never hit for finite huge on this path */
-        *c = x - x;
+        /* outside the reduction's range, 1e9 itself included: NaN for inf and NaN as C99 has it, and NaN by definition
+         * for a finite huge x (x - x would give sin = cos = 0 there); never hit on the path */
+        *s = rtd_from_bits(0x7ff8000000000000ULL);
+        *c = *s;
         return;
     }
     double kf = __builtin_floor(x * RTD_TWO_OVER_PI + 0.5);
@@ -118,6 +126,7 @@ RTD_FN void rtd_sincos(double x, double* s, double* c)
 RTD_FN float rt_sinf(float x)
 {
     double s, c;
+    if (x == 0.0f) return x;   /* sin(-0) = -0: rtd_ksin's r + (r z) p gives -0 + +0 = +0 */
     rtd_sincos((double)x, &s, &c);
     return (float)s;
 }
@@ -132,6 +141,7 @@ RTD_FN float rt_cosf(float x)
 RTD_FN float rt_tanf(float x)
 {
     double s, c;
+    if (x == 0.0f) return x;   /* tan(-0) = -0, as rt_sinf */
     rtd_sincos((double)x, &s, &c);
     return (float)(s / c);
 }
@@ -229,7 +239,8 @@ RTD_FN float rt_powf(float xf, float yf)
         if (!y_is_int)
         {
             if (ax == 0.0) return y < 0.0 ? __builtin_inff() : 0.0f;
-            return (float)((x - x) / (x - x)); /* NaN */
+            /* a negative finite base: NaN.  pow(-inf, y) is +0 or +inf as for +inf: the infinity branch below, sign = 1 */
+            if (!(ax > 1.7976931348623157e308)) return (float)((x - x) / (x - x));
         }
         if (y_is_odd) sign = -1.0;
     }

@@ -43,6 +43,7 @@ def load():
         "orc_wang_hash": (u32, [u32]), "orc_sample_random": (f32, [u32] * 5),
         "orc_tanf": (f32, [f32]), "orc_sinf": (f32, [f32]), "orc_cosf": (f32, [f32]),
         "orc_powf": (f32, [f32, f32]), "orc_atan2f": (f32, [f32, f32]), "orc_acosf": (f32, [f32]),
+        "orc_debug_eval": (None, [C.c_int, vp, vp, vp, u32]),
         "orc_wide_trace": (C.c_int, [vp, vp, u32, u32, vp, u32, C.c_int, vp, vp, vp]),
         "orc_wide_trace_events": (C.c_int, [vp, vp, u32, u32, vp, u32, C.c_int, vp, vp, vp, vp, u32, vp]),
     }
@@ -58,6 +59,20 @@ def _arr(ptr, n, dtype):
         return np.zeros(0, dtype=dtype)
     buf = (C.c_char * (n * np.dtype(dtype).itemsize)).from_address(ptr)
     return np.frombuffer(buf, dtype=dtype, count=n).copy()
+
+
+def debug_eval(fn, a, b=None):
+    """orc_debug_eval over whole arrays: the host twin of capi.Context.debug_eval (same codes, same bits in and out)."""
+    lib = load()
+    a = np.ascontiguousarray(a, np.float32)
+    out = np.zeros_like(a)
+    bp = None
+    if b is not None:
+        b = np.ascontiguousarray(b, np.float32)
+        assert b.size == a.size
+        bp = b.ctypes.data
+    lib.orc_debug_eval(fn, a.ctypes.data, bp, out.ctypes.data, a.size)
+    return out
 
 
 STAT_NAMES = ("closest_nodes", "closest_tris", "shadow_nodes", "shadow_tris", "escaped", "hits", "emissive",
